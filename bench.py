@@ -13,6 +13,17 @@ resident in HBM: noise/flow-match mix/pack -> 28-block DiT forward -> weighted M
 the bf16 (hi, lo) LoRA working copies.
 Nothing is skipped or cached between steps; weights are random-init of the production architecture (no checkpoints
 are reachable offline).  Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline figure needs: set up, warm up, time --steps steps, print the line (metric, value, unit,
+higher_is_better, dtype, ms_per_step).  --full adds everything else the line can carry: the in-stream per-kernel event profiler and
+the roofline / HBM figures derived from it and from the committed counter passes under profiles/, and the CPU baseline of the reference
+step (--no-prof / --no-cpu-baseline / --cpu-baseline select among those).
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step handed its caller -- the loss and the global gradient norm --
+and the training state it advanced (ltx: the flat LoRA parameters and both AdamW moments) as DIR/<name>.npy in float32 (float64 stays
+float64).  An output of more than DUMP_SAMPLE elements is written as a fixed sample: the same seeded indices in every run.  All inputs
+are seeded, so two builds run with the same arguments can be compared output for output.  The weight-gradient reduction adds fp32 partial
+sums with atomics, so two runs of one build agree to summation order, not bit for bit.
 """
 
 from __future__ import annotations
@@ -51,13 +62,17 @@ def parse():
     ap.add_argument("--gemm-variant", type=int, default=int(os.environ.get("FTMI_GEMM_VARIANT", "8")))
     ap.add_argument("--gradient-checkpointing", action="store_true",
                     help="ltx / hunyuan: every block keeps its input and recomputes its forward inside the backward (the reference's --gradient_checkpointing)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: per-kernel event profile + roofline / HBM figures, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs and the training state it advanced as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-baseline", choices=["full", "quick"], default="full",
-                    help="full: SURVEY 8d protocol (1 warm-up + 3 timed steps; cfg 2 on --cpu-baseline-layers blocks in bf16 and fp32, cfg 1 at full depth); "
-                         "quick: one un-warmed cfg-2 step on 2 blocks")
+                    help="--full: full = SURVEY 8d protocol (1 warm-up + 3 timed steps; cfg 2 on --cpu-baseline-layers blocks in bf16 and fp32, cfg 1 at full depth); "
+                         "quick = one un-warmed cfg-2 step on 2 blocks")
     ap.add_argument("--cpu-baseline-layers", type=int, default=4)
-    ap.add_argument("--no-prof", action="store_true", help="do not bracket kernels with HIP events inside the timed region")
-    ap.add_argument("--prof-stride", type=int, default=29, help="bracket every N-th launch of a kernel class with HIP events (1 = all)")
+    ap.add_argument("--no-prof", action="store_true", help="--full: do not bracket kernels with HIP events inside the timed region")
+    ap.add_argument("--prof-stride", type=int, default=29, help="--full: bracket every N-th launch of a kernel class with HIP events (1 = all)")
     a = ap.parse_args()
     if a.steps <= 0:
         a.steps = 30 if a.workload == "ltx" else 10
@@ -65,7 +80,34 @@ def parse():
         a.layers = 28
     if a.gradient_checkpointing and a.workload not in ("ltx", "hunyuan"):
         ap.error("--gradient-checkpointing: the ltx and hunyuan workloads recompute (cogvideox and wan keep their activations: 45 / 74 GiB of 288)")
+    if not a.full:  # a plain run: the timed steps and nothing else
+        a.no_prof, a.no_cpu_baseline = True, True
     return a
+
+
+DUMP_SAMPLE = 1 << 20   # elements written of a larger output (4 MB in float32)
+DUMP_LIMIT = 64 << 20   # bytes written in all
+
+
+def dump_outputs(path: str, arrays) -> None:
+    """--dump-outputs: each tensor of `arrays` (name -> tensor) as path/<name>.npy, float32 (float64 stays float64).  A tensor of more than
+    DUMP_SAMPLE elements is reduced to the elements at DUMP_SAMPLE indices drawn from a fixed seed, sorted: the same positions in every run."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        t = torch.as_tensor(t).detach().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t[idx.to(t.device)]
+        a = t.cpu().numpy() if t.dtype == torch.float64 else t.float().cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_LIMIT:
+            raise RuntimeError(f"--dump-outputs: more than {DUMP_LIMIT >> 20} MB at {name}")
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def _profile_json(name: str):
@@ -233,6 +275,8 @@ def _build_ltx(args, par, dev):
             "gemm_variant": args.gemm_variant,
         },
         "cpu_baseline": lambda: cpu_baseline(args),
+        # what a step advances in place (--dump-outputs): the flat fp32 LoRA parameters [A | B] and the AdamW moments laid out like them
+        "state": lambda: {"lora_params": model.lora_flat, "adam_exp_avg": step.exp_avg, "adam_exp_avg_sq": step.exp_avg_sq},
     }
 
 
@@ -422,6 +466,9 @@ def main():
     elapsed = t.item()
     loss = out["loss"].item()
 
+    if par.rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {**out, **(ctx["state"]() if "state" in ctx else {})})
+
     if par.rank == 0:
         ms = elapsed / args.steps * 1e3
         samples_per_s = par.world_size * B * args.steps / elapsed
@@ -525,7 +572,7 @@ def main():
                     a_fl = kern["attn_fwd"]["tflops"] * kern["attn_fwd"]["ms_per_step"] + kern["attn_bwd"]["tflops"] * kern["attn_bwd"]["ms_per_step"]
                     res["attention_roofline"] = {"achieved": a_fl / a_ms, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": a_fl / a_ms / PEAK_BF16_TFLOPS,
                                                  "share_of_step": a_ms / ms}
-        if args.workload == "ltx":
+        if args.workload == "ltx" and args.full:
             # north_star: "rocprof HBM-GB/s ... reported against peak".  Bytes from the committed counter passes of this command (FETCH_SIZE x 2 -- the gfx950
             # correction of MI355X_MICROARCH.md -- + WRITE_SIZE, separate passes), time from THIS run.
             step_bytes, src = _pmc_step_traffic()

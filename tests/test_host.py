@@ -574,12 +574,13 @@ def test_dp_gradient_average_equals_large_batch_gradient():
 
 def test_bench_and_entry_points_exist():
     src = open(os.path.join(ROOT, "bench.py")).read()
-    for key in ('"metric"', '"roofline"', '"cpu_baseline"', '"ms_per_step"', '"vs_baseline"', "--gpus", "--steps", "--warmup"):
+    for key in ('"metric"', '"roofline"', '"cpu_baseline"', '"ms_per_step"', '"vs_baseline"', "--gpus", "--steps", "--warmup", "--full", "--dump-outputs"):
         assert key in src
     import __graft_entry__ as ge
 
     assert callable(ge.build) and callable(ge.smoke)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1"], capture_output=True, text=True)
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")  # no device visible, on a GPU machine too
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1"], capture_output=True, text=True, env=env)
     assert out.returncode != 0 and "MI355X" in (out.stderr + out.stdout)  # refuses to run without the GPU
 
 
@@ -985,41 +986,38 @@ def test_block_orchestrator_planners_agree_with_the_python_layouts():
 
 def test_spec_classes_subclass_the_reference_when_it_is_importable():
     """B1 as a drop-in: the MI355X specification classes are the MI355X overrides ON TOP of the reference's own specification class when one is
-    importable.  The reference package cannot be imported here (no diffusers), so its ModelSpecification base + LTXVideoModelSpecification are
-    compiled out of /root/reference with stubbed third-party names (the make_golden.py technique) and injected as the base."""
-    import ast
-    import types
-
-    ref_root = os.environ.get("FTMI_REFERENCE", "/root/reference")
-    if not os.path.isdir(ref_root):
-        pytest.skip("the reference tree is not on this machine (GPU box)")
+    importable.  The reference package cannot be imported here (no diffusers), so a stand-in with the reference's surface is injected as the base: a
+    ModelSpecification that takes the reference constructor's keyword arguments and carries the methods SFTTrainer calls, and an LTX-Video subclass
+    whose constructor installs the default processors (one for the conditions, one for the latents) and which defines its own loaders / forward."""
     from finetrainers_amd.ltx_video import specification as ltx_spec
-    from finetrainers_amd.utils.reference_base import StandaloneModelSpecification, as_drop_in
+    from finetrainers_amd.utils.reference_base import REFERENCE_CTOR_KEYS, StandaloneModelSpecification, as_drop_in
 
-    def compile_classes(relpath, names, ns):
-        tree = ast.parse(open(os.path.join(ref_root, relpath)).read())
-        body = [n for n in tree.body if isinstance(n, ast.ClassDef) and n.name in names]
-        loads = {n.id for c in body for n in ast.walk(c) if isinstance(n, ast.Name)}
-        import builtins
-        for name in loads:  # every third-party name the class bodies mention becomes an inert stub
-            if name not in ns and not hasattr(builtins, name):
-                ns[name] = type(name, (), {"__init__": lambda self, *a, **k: None})
-        for c in body:
-            for f in ast.walk(c):
-                if isinstance(f, ast.FunctionDef):
-                    f.decorator_list = [d for d in f.decorator_list if isinstance(d, ast.Name) and d.id == "property"]
-        mod = ast.Module(body=body, type_ignores=[])
-        ast.fix_missing_locations(mod)
-        exec(compile(mod, relpath, "exec"), ns)
-        return ns
+    inherited = ("prepare_conditions", "prepare_latents", "load_condition_models", "load_latent_models", "load_pipeline", "validation", "collate_conditions",
+                 "collate_latents", "_trainer_init")
+    own = ("load_diffusion_models", "forward", "_save_lora_weights")
 
-    import typing
-    ns = {k: getattr(typing, k) for k in ("Any", "Dict", "List", "Optional", "Tuple", "Union")}
-    ns.update(torch=torch, logger=types.SimpleNamespace(warning=lambda *a, **k: None), IGNORE_KEYS_FOR_COLLATION=ltx_spec.IGNORE_KEYS_FOR_COLLATION)
-    compile_classes("finetrainers/models/modeling_utils.py", {"ModelSpecification"}, ns)
-    ns["ModelSpecification"]._load_configs = lambda self: None  # the hub lookup of the constructor
-    compile_classes("finetrainers/models/ltx_video/base_specification.py", {"LTXVideoModelSpecification"}, ns)
-    Ref = ns["LTXVideoModelSpecification"]
+    def method(name):
+        def f(self, *args, **kwargs):
+            return name
+        f.__name__ = name
+        return f
+
+    def base_init(self, **kwargs):
+        unknown = set(kwargs) - set(REFERENCE_CTOR_KEYS)
+        assert not unknown, unknown  # as_drop_in hands the base the reference's own keyword arguments only
+        for k in REFERENCE_CTOR_KEYS:
+            setattr(self, k, kwargs.get(k))
+        self.condition_model_processors = kwargs.get("condition_model_processors") or []
+        self.latent_model_processors = kwargs.get("latent_model_processors") or []
+
+    def ltx_init(self, pretrained_model_name_or_path="Lightricks/LTX-Video", condition_model_processors=None, latent_model_processors=None, **kwargs):
+        condition_model_processors = condition_model_processors or [("text", ["encoder_hidden_states", "encoder_attention_mask"])]
+        latent_model_processors = latent_model_processors or [("latents", ["latents", "num_frames", "height", "width", "latents_mean", "latents_std"])]
+        base_init(self, pretrained_model_name_or_path=pretrained_model_name_or_path, condition_model_processors=condition_model_processors,
+                  latent_model_processors=latent_model_processors, **kwargs)
+
+    ns = {"ModelSpecification": type("ModelSpecification", (), {"__init__": base_init, **{n: method(n) for n in inherited + own}})}
+    Ref = type("LTXVideoModelSpecification", (ns["ModelSpecification"],), {"__init__": ltx_init, **{n: method(n) for n in own}})
 
     overrides = ltx_spec.MI355XLTXVideoModelSpecification.MI355X_OVERRIDES
     Spec = as_drop_in(overrides, "finetrainers.models.ltx_video", "LTXVideoModelSpecification", base_override=Ref)
@@ -1032,7 +1030,7 @@ def test_spec_classes_subclass_the_reference_when_it_is_importable():
     # overridden by the MI355X backend
     for name in ("load_diffusion_models", "forward", "_save_lora_weights"):
         assert getattr(Spec, name) is getattr(overrides, name) and getattr(Spec, name) is not getattr(Ref, name), name
-    # the reference constructor ran: its default processors are in place (two stub instances), ours did not wipe them
+    # the reference constructor ran: its default processors are in place (one each), ours did not wipe them
     assert len(spec.condition_model_processors) == 1 and len(spec.latent_model_processors) == 1 and spec._resolution_dim_keys == {"latents": (2, 3, 4)}
     assert spec.pretrained_model_name_or_path == "somewhere/LTX-Video" and spec.first_frame_conditioning_p == 0.1
 
@@ -1077,30 +1075,18 @@ def test_gemm_dispatch_rule_matches_the_design(lib):
 
 def test_parallel_backend_has_the_reference_surface():
     """N2: every method / property of BaseParallelBackend (finetrainers/parallel/base.py:9-115) exists on MI355XParallelBackend with the
-    reference's signatures where the trainer passes arguments; degrees the path does not implement are refused at construction."""
-    import ast
+    reference's signatures where the trainer passes arguments; degrees the path does not implement are refused at construction.  The lists are those of
+    the surveyed reference: BaseParallelBackend's methods / properties, PytorchDTensorParallelBackend.__init__ and PTDCheckpointer.__init__ arguments."""
     import inspect
 
     from finetrainers_amd.parallel import MI355XCheckpointer, MI355XParallelBackend
 
-    ref_root = os.environ.get("FTMI_REFERENCE", "/root/reference")
-    if os.path.isdir(ref_root):
-        tree = ast.parse(open(os.path.join(ref_root, "finetrainers/parallel/base.py")).read())
-        base = next(n for n in tree.body if isinstance(n, ast.ClassDef) and n.name == "BaseParallelBackend")
-        names = [f.name for f in base.body if isinstance(f, ast.FunctionDef) and f.name != "__init__"]
-        ptd = ast.parse(open(os.path.join(ref_root, "finetrainers/parallel/ptd.py")).read())
-        ctor = next(f for c in ptd.body if isinstance(c, ast.ClassDef) and c.name == "PytorchDTensorParallelBackend" for f in c.body
-                    if isinstance(f, ast.FunctionDef) and f.name == "__init__")
-        ref_ctor_args = [a.arg for a in ctor.args.args[1:]]
-        ckpt = next(f for c in ptd.body if isinstance(c, ast.ClassDef) and c.name == "PTDCheckpointer" for f in c.body if isinstance(f, ast.FunctionDef) and f.name == "__init__")
-        ref_ckpt_args = [a.arg for a in ckpt.args.args[1:]]
-    else:  # GPU box: the lists as of the surveyed reference
-        names = ["enable_determinism", "apply_ddp", "apply_fsdp2", "apply_context_parallel", "prepare_model", "prepare_dataset", "prepare_dataloader", "prepare_optimizer",
-                 "get_mesh", "get_checkpointer", "initialize_trackers", "log", "wait_for_everyone", "main_process_first", "destroy", "world_size", "rank", "local_rank",
-                 "is_main_process", "is_local_main_process", "device", "pipeline_parallel_enabled", "data_parallel_enabled", "data_replication_enabled",
-                 "data_sharding_enabled", "context_parallel_enabled", "tensor_parallel_enabled"]
-        ref_ctor_args = ["world_size", "pp_degree", "dp_degree", "dp_shards", "cp_degree", "tp_degree", "backend", "timeout", "logging_dir", "output_dir", "gradient_accumulation_steps"]
-        ref_ckpt_args = ["dataloader", "model_parts", "optimizers", "schedulers", "states", "checkpointing_steps", "checkpointing_limit", "output_dir", "enable", "_callback_fn", "_prefix"]
+    names = ["enable_determinism", "apply_ddp", "apply_fsdp2", "apply_context_parallel", "prepare_model", "prepare_dataset", "prepare_dataloader", "prepare_optimizer",
+             "get_mesh", "get_checkpointer", "initialize_trackers", "log", "wait_for_everyone", "main_process_first", "destroy", "world_size", "rank", "local_rank",
+             "is_main_process", "is_local_main_process", "device", "pipeline_parallel_enabled", "data_parallel_enabled", "data_replication_enabled",
+             "data_sharding_enabled", "context_parallel_enabled", "tensor_parallel_enabled"]
+    ref_ctor_args = ["world_size", "pp_degree", "dp_degree", "dp_shards", "cp_degree", "tp_degree", "backend", "timeout", "logging_dir", "output_dir", "gradient_accumulation_steps"]
+    ref_ckpt_args = ["dataloader", "model_parts", "optimizers", "schedulers", "states", "checkpointing_steps", "checkpointing_limit", "output_dir", "enable", "_callback_fn", "_prefix"]
     assert len(names) >= 27
     for n in names:
         assert n in MI355XParallelBackend.__dict__ or any(n in k.__dict__ for k in MI355XParallelBackend.__mro__[1:-1]), n
@@ -1268,6 +1254,39 @@ def test_bench_eight_ranks_rehearsal_ltx():
     assert isinstance(d["exposed_comm_ms"], float) and d["value"] > 0
 
 
+def test_bench_plain_run_leaves_the_extras_to_full(monkeypatch):
+    """A plain `bench.py` run times the steps and nothing else: the in-stream event profiler and the CPU baseline only run under --full."""
+    import bench
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "4"])
+    a = bench.parse()
+    assert (a.full, a.no_prof, a.no_cpu_baseline, a.steps) == (False, True, True, 4)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--steps", "4"])
+    a = bench.parse()
+    assert (a.full, a.no_prof, a.no_cpu_baseline, a.steps) == (True, False, False, 4)
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: the last step's outputs as DIR/<name>.npy (rehearsal on CPU: the step's loss); a large output is written as a fixed sample,
+    the same elements in every run, in float32 (float64 kept), within the 64 MB budget."""
+    import numpy as np
+
+    import bench
+
+    d = _bench_rehearsal("--gpus", "2", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "run"))
+    assert d["steps"] == 2
+    loss = np.load(tmp_path / "run" / "loss.npy")
+    assert loss.dtype == np.float32 and loss.shape == (1,)
+    big = torch.arange(3 * bench.DUMP_SAMPLE, dtype=torch.bfloat16)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"big": big, "small": torch.ones(3, dtype=torch.float64)})
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_SAMPLE,) and np.array_equal(a, b)
+    assert np.load(tmp_path / "a" / "small.npy").dtype == np.float64
+    with pytest.raises(RuntimeError, match="MB"):
+        bench.dump_outputs(str(tmp_path / "c"), {f"t{i}": torch.zeros(bench.DUMP_SAMPLE) for i in range(17)})
+
+
 @pytest.mark.parametrize("n", [2, 8])
 def test_bench_rehearsal_wan_parameter_sharding(n):
     """BASELINE config 4 (`--workload wan`, parallel/ptd.py:466-499: fully_shard per block + root): the real ParameterSharder on n gloo ranks walks the
@@ -1428,7 +1447,7 @@ def test_narrow_ltx_layout_embeds_the_reference_dummy_in_the_wide_one():
             continue
         sp = lay.spaces_of(k)
         w = lay.widen(v, *sp)
-        assert torch.equal(lay.narrow(w, *sp), v) and w.float().abs().sum() == v.float().abs().sum(), k
+        assert torch.equal(lay.narrow(w, *sp), v) and w.double().abs().sum() == v.double().abs().sum(), k  # float64: exact for bf16 values, in any summation order
         n += 1
     assert n == 15 + 25  # 15 top-level tensors, 25 of the block
     w = lay.widen(model.state_dict()["transformer_blocks.0.attn1.to_q.base_layer.weight"], "h", "d")
