@@ -1435,37 +1435,44 @@ int attn_bwd(const AttnArgs& a, hipStream_t st) {
         // (from 256 keys on: shorter problems keep attn_bwd_dq2_kernel, whose bits the resident few-keys kernel reproduces -- the shipped stream differs by one rounding per score)
         if ((pl & 1) && !a.kbias && a.Sk >= 256) {
             const int var = (pl >> 4) & 15, nq = (pl & 0x100) ? 2 : 1;
+            const bool ragged = (a.Sk % 64) != 0;  // the last tile's stream clamps the exp2 argument of the zero-filled keys (attention_pl.hip.h)
             const dim3 gridp(((a.Sq + 128 * nq - 1) / (128 * nq)) * a.H * a.B);
-#define FTMI_PL_LAUNCH(NQ_, V_)                                                                                                                         \
+#define FTMI_PL_LAUNCH1(NQ_, V_, R_)                                                                                                                    \
     do {                                                                                                                                                \
-        static const bool ok_ = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dq_pl_kernel<NQ_, V_>), hipFuncAttributeMaxDynamicSharedMemorySize, kPlLds) == hipSuccess; \
+        static const bool ok_ = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dq_pl_kernel<NQ_, V_, R_>), hipFuncAttributeMaxDynamicSharedMemorySize, kPlLds) == hipSuccess; \
         if (!ok_) return set_error(FTMI_ERR_LAUNCH, "attn_bwd: cannot raise the dynamic LDS limit");                                                    \
-        hipLaunchKernelGGL((attn_bwd_dq_pl_kernel<NQ_, V_>), gridp, dim3(256), kPlLds, st, a);                                                          \
+        hipLaunchKernelGGL((attn_bwd_dq_pl_kernel<NQ_, V_, R_>), gridp, dim3(256), kPlLds, st, a);                                                      \
+    } while (0)
+#define FTMI_PL_LAUNCH(NQ_, V_)                   \
+    do {                                          \
+        if (ragged) FTMI_PL_LAUNCH1(NQ_, V_, true);  \
+        else FTMI_PL_LAUNCH1(NQ_, V_, false);        \
     } while (0)
             if (nq == 1) {
                 if (var == 0) FTMI_PL_LAUNCH(1, 0);
                 else if (var == 2) FTMI_PL_LAUNCH(1, 2);
 #ifdef FTMI_LAB
-                else if (var == 6) FTMI_PL_LAUNCH(1, 6);
-                else if (var == 7) FTMI_PL_LAUNCH(1, 7);
-                else if (var == 3) FTMI_PL_LAUNCH(1, 3);
-                else if (var == 4) FTMI_PL_LAUNCH(1, 4);
-                else if (var == 5) FTMI_PL_LAUNCH(1, 5);
+                else if (var == 6) FTMI_PL_LAUNCH1(1, 6, false);
+                else if (var == 7) FTMI_PL_LAUNCH1(1, 7, false);
+                else if (var == 3) FTMI_PL_LAUNCH1(1, 3, false);
+                else if (var == 4) FTMI_PL_LAUNCH1(1, 4, false);
+                else if (var == 5) FTMI_PL_LAUNCH1(1, 5, false);
 #endif
                 else FTMI_PL_LAUNCH(1, 1);
             } else {
                 if (var == 0) FTMI_PL_LAUNCH(2, 0);
                 else if (var == 2) FTMI_PL_LAUNCH(2, 2);
 #ifdef FTMI_LAB
-                else if (var == 6) FTMI_PL_LAUNCH(2, 6);
-                else if (var == 7) FTMI_PL_LAUNCH(2, 7);
-                else if (var == 3) FTMI_PL_LAUNCH(2, 3);
-                else if (var == 4) FTMI_PL_LAUNCH(2, 4);
-                else if (var == 5) FTMI_PL_LAUNCH(2, 5);
+                else if (var == 6) FTMI_PL_LAUNCH1(2, 6, false);
+                else if (var == 7) FTMI_PL_LAUNCH1(2, 7, false);
+                else if (var == 3) FTMI_PL_LAUNCH1(2, 3, false);
+                else if (var == 4) FTMI_PL_LAUNCH1(2, 4, false);
+                else if (var == 5) FTMI_PL_LAUNCH1(2, 5, false);
 #endif
                 else FTMI_PL_LAUNCH(2, 1);
             }
 #undef FTMI_PL_LAUNCH
+#undef FTMI_PL_LAUNCH1
         } else if (a.kbias)
             hipLaunchKernelGGL(attn_bwd_dq2_kernel<true>, grid2, dim3(256), kDqLds, st, a);
         else if ((a.Sk % 64) != 0)

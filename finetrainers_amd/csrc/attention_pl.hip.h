@@ -35,8 +35,10 @@ static constexpr int kPlLds = 3 * 16384;  // three (K, V) [or (Q, dO)] tile slot
 // VAR: 0 = exact arithmetic of attn_bwd_dq2_kernel (bit-identical outputs: the pipeline's test), 1 = -delta through the accumulator input of the
 // dP chain, 2 = as 1 with the VALU work in passes over groups of four elements; lab only: 6 = packed fp32 VALU (same bits, 9 % slower), 3 / 4 / 5 / 7 = ablations of 1
 // (no VALU / no LDS reads / no MFMA / the MFMAs as 16 x 16 x 32 on dummy accumulators: results wrong on purpose, tools/attn_lab.hip reads their time only)
-template <int NQ, int VAR>
+// RAGGED: Sk is not a multiple of 64 -- the tile loop runs the clamped *_clamp streams (see the tile DMA below); VAR 0 / 1 / 2 only.
+template <int NQ, int VAR, bool RAGGED = false>
 __global__ __launch_bounds__(256, NQ == 1 ? 2 : 1) void attn_bwd_dq_pl_kernel(AttnArgs a) {
+    static_assert(!RAGGED || VAR <= 2, "the lab streams have no clamped form");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 31, g = lane >> 5;
@@ -101,8 +103,11 @@ __global__ __launch_bounds__(256, NQ == 1 ? 2 : 1) void attn_bwd_dq_pl_kernel(At
 
     // tile DMA: the four pieces of tile `dma_t` (past the end: the last tile again, into a slot nobody reads -- branch-free tail) -> ring slot dma_t % 3.
     // Buffer loads with EXACT bounds (descriptor = the rest of this head's rows from the tile on): rows past the end of a ragged last tile arrive as
-    // ZEROS, and zero K rows cancel whatever their scores turn into -- the dQ products read them through the same LDS image (K^T fragments = 0) -- so a
-    // ragged key count needs no masking instruction anywhere in the stream (CogVideoX: 17 776 = 277 x 64 + 48 tokens).
+    // ZEROS, and the dQ products read them through the same LDS image (K^T fragments = 0).  A zero K row cancels its dS only while dS is finite: the
+    // padded key's score is 0, its exp2 argument -lse2, and once every real logit of a row is below ~ -88.7 nat (lse2 < -128) exp2 gives inf and
+    // inf * 0 = NaN.  So a RAGGED launch runs the *_clamp streams: the shipped v1 / v2 streams set the clamp bit of v_exp_f32 (P clamped to [0, 1] at no
+    // issue cost: a padded key's P becomes 1 and meets K = 0, a real key's P changes only where rounding put it above 1); the x0 streams clamp the exp2
+    // argument to <= 64 by one v_min_f32 per score (padded P <= 2^64, real keys keep their bits) and so stay bit-identical to the masking kernel attn_bwd_dq2_kernel<false, true> (tests/test_gpu_attention_edges.py, R1 at ragged key counts; CogVideoX: 17 776 = 277 x 64 + 48).
     int dma_t = 0;
     uint32_t dma_dst = lds0;
     const char *ksrc = (const char*)kbase, *vsrc = (const char*)vbase;
@@ -218,8 +223,28 @@ __global__ __launch_bounds__(256, NQ == 1 ? 2 : 1) void attn_bwd_dq_pl_kernel(At
     }
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
 
+    // RAGGED: every tile runs the clamped stream.  (Clamping the last tile only -- a branch inside the loop, or the tile peeled off behind it -- made hipcc
+    // spill fragments of in-flight LDS reads, resp. gave wrong dQ at 64 rows per wave: the loop body must stay the only copy of the stream.)
     for (int t = 0; t < nt; ++t) {
-        if constexpr (NQ == 1) {
+        if constexpr (RAGGED) {
+            if constexpr (NQ == 1) {
+                if constexpr (VAR == 0) {
+#include "attn_pl_dq1_x0_clamp.inc"
+                } else if constexpr (VAR == 1) {
+#include "attn_pl_dq1_v1_clamp.inc"
+                } else {
+#include "attn_pl_dq1_v2_clamp.inc"
+                }
+            } else {
+                if constexpr (VAR == 0) {
+#include "attn_pl_dq2_x0_clamp.inc"
+                } else if constexpr (VAR == 1) {
+#include "attn_pl_dq2_v1_clamp.inc"
+                } else {
+#include "attn_pl_dq2_v2_clamp.inc"
+                }
+            }
+        } else if constexpr (NQ == 1) {
             if constexpr (VAR == 0) {
 #include "attn_pl_dq1_x0.inc"
             } else if constexpr (VAR == 1) {

@@ -359,7 +359,9 @@ def test_pipelined_dq_kernels_match_the_kernel_they_replace(B, H, Sq, Sk, sw):
     (0x001) and 64 rows x one wave (0x101), at whole and ragged query counts, one and many key tiles.  The shipped streams (0x011 / 0x111) put -delta into the
     accumulator input of the dP chain: one rounding differs per score, checked against the old kernel to 1e-3 and against fp32 autograd like every attention case.
     Sk = 64 (one tile) keeps the old kernel: the switch must fall through.  Ragged key counts (1000, 1777: CogVideoX's 17 776 = 277 x 64 + 48 in the lab, profiles/
-    r05_attn_lab_4_ragged.txt): the bounds-checked DMA zero-fills the rows past the end, and zero K rows cancel in the dQ products -- same bits as the masking kernel."""
+    r05_attn_lab_4_ragged.txt): the bounds-checked DMA zero-fills the rows past the end, and zero K rows cancel in the dQ products -- same bits as the masking kernel.
+    Cancelling needs a finite dS: ragged launches run the clamped streams (the x0 ones clamp the exp2 argument to <= 64, which no real key reaches), else a row
+    whose logits all lie below ~ -88.7 nat turns the padded keys' exp2 into inf and dQ into NaN (tests/test_gpu_attention_edges.py, regime R1)."""
     from finetrainers_amd import ops
 
     dev = _dev()

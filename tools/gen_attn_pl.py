@@ -70,8 +70,13 @@ def spread(n_items: int, n_gaps: int, weights=None) -> list[int]:
 #   C(u-1): 4 MFMAs  dqt[qt'] += K^T . dS[p^1];   A(u+1): 8 MFMAs  S[p^1] = K.Q^T, DP[p^1] = V.dO^T (- delta);
 #   B(u): VALU  dS[p] = exp2(S[p] * sl - lse) * DP[p] -> bf16 fragments.
 # ------------------------------------------------------------------------------------------------------------------------------
-def dq_valu_ops(par: int, qt: int, exact: bool, order: str) -> list[tuple[str, str, str]]:
+def dq_valu_ops(par: int, qt: int, exact: bool, order: str, clamp: bool = False) -> list[tuple[str, str, str]]:
     """The VALU list of B(u) in issue order; (text, outs, ins) per instruction.
+    clamp: the stream of ragged launches.  A padded key has K = 0, so its score is 0 and its argument is -lse2, which exceeds 128 once every real logit of
+    the row is below ~ -88.7 nat; exp2 would give inf and inf * (K = 0) = NaN in the dQ products.  The shipped streams (v1 / v2) set the clamp bit of
+    v_exp_f32 (result clamped to [0, 1], same issue cost): a padded key's P becomes 1 and meets K = 0; a real key's P is <= 1 up to rounding, so at most a
+    P a rounding above 1 changes (to 1).  The exact stream (x0) keeps the bits of the masking kernel instead: its argument is clamped to <= 64 by one more
+    v_min_f32 (padded P <= 2^64, finite), which real keys (argument <= 0) never reach.
     order "g16" / "g4": passes over groups of 16 / 4 score elements (all fma, all exp2, all mul, the packs);
     order "roll": a rolling pipeline (fma of element s, exp2 of element s-4, mul of element s-8, pack of a finished pair) -- the exp2s
     (transcendental unit, ~7 cycles each) never come back to back.
@@ -83,6 +88,10 @@ def dq_valu_ops(par: int, qt: int, exact: bool, order: str) -> list[tuple[str, s
         return ("v_fma_f32 %0, %1, %2, %3", f'"=v"(x[{r}])', f'"v"({S}[{r}]), "v"(sl), "v"(nlse[{qt}])')
 
     def E(r):
+        if clamp and exact:
+            return ("v_min_f32 %0, 0x42800000, %0\\n\\tv_exp_f32 %0, %0", f'"+v"(x[{r}])', "")  # 0x42800000 = 64.0
+        if clamp:
+            return ("v_exp_f32_e64 %0, %0 clamp", f'"+v"(x[{r}])', "")  # result clamped to [0, 1]: no extra instruction
         return ("v_exp_f32 %0, %0", f'"+v"(x[{r}])', "")
 
     def U(r):
@@ -142,10 +151,11 @@ def dq_valu_ops(par: int, qt: int, exact: bool, order: str) -> list[tuple[str, s
     return ops
 
 
-def gen_dq(name: str, nq: int, exact: bool, order: str = "roll", weights=None, drop=()):
-    """drop: ablation builds for the lab (results wrong on purpose): 'valu', 'lds', 'dma', 'mfma'."""
+def gen_dq(name: str, nq: int, exact: bool, order: str = "roll", weights=None, drop=(), clamp: bool = False):
+    """drop: ablation builds for the lab (results wrong on purpose): 'valu', 'lds', 'dma', 'mfma'.  clamp: the stream of ragged launches (dq_valu_ops)."""
     s = Stream()
-    s.emit(f"// GENERATED by tools/gen_attn_pl.py (dq{nq}_{name}: exact={int(exact)} order={order} drop={','.join(drop) or '-'}) -- do not edit")
+    tag = f"{name}_clamp" if clamp else name
+    s.emit(f"// GENERATED by tools/gen_attn_pl.py (dq{nq}_{tag}: exact={int(exact)} order={order} drop={','.join(drop) or '-'}{' clamp=64' if clamp else ''}) -- do not edit")
     units = [(js, qt) for js in range(2) for qt in range(nq)]
     n = len(units)
     # two waves per SIMD share 512 registers: hipcc halves a 256-register budget into 128 VGPRs + 128 AGPRs as soon as a kernel touches an AGPR,
@@ -157,7 +167,7 @@ def gen_dq(name: str, nq: int, exact: bool, order: str = "roll", weights=None, d
         jsp, qtp = units[(i - 1) % n]
         s.emit(f"// ---- slot {i} (js {js}, qt {qt}): C(u-1) on dqt[{qtp}], A(u+1) into S/DP[{parn}] (js {jsn}, qt {qtn}), B(u) on S/DP[{par}]")
         s.emit("{")
-        valu = [] if "valu" in drop else dq_valu_ops(par, qt, exact, order)
+        valu = [] if "valu" in drop else dq_valu_ops(par, qt, exact, order, clamp)
         mf = []
         for hh in range(2):
             for dt in range(2):
@@ -219,7 +229,7 @@ def gen_dq(name: str, nq: int, exact: bool, order: str = "roll", weights=None, d
                 vi += 1
         assert vi == len(valu)
         s.emit("}")
-    path = os.path.join(_out_dir(name), f"attn_pl_dq{nq}_{name}.inc")
+    path = os.path.join(_out_dir(name), f"attn_pl_dq{nq}_{tag}.inc")
     with open(path, "w") as f:
         f.write("\n".join(s.lines) + "\n")
     return path
@@ -766,6 +776,10 @@ def main():
         made.append(gen_dq("v1", nq, False))
         # v2: as v1, VALU in passes over groups of four elements
         made.append(gen_dq("v2", nq, False, order="g4"))
+        # the same three streams for ragged key counts: exp2 argument clamped to 64 (padded keys, K = 0)
+        made.append(gen_dq("x0", nq, True, clamp=True))
+        made.append(gen_dq("v1", nq, False, clamp=True))
+        made.append(gen_dq("v2", nq, False, order="g4", clamp=True))
         # v6: as v1 with packed fp32 fma / mul (two scores per instruction)
         made.append(gen_dq("v6", nq, False, order="pk"))
         # ablations of v1 (lab only; results wrong on purpose)
