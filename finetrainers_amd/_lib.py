@@ -138,6 +138,29 @@ class WanRowArgs(Structure):
     ]
 
 
+class GemmNtArgs(Structure):
+    """include/ftmi355.h: ftmi_gemm_nt_args."""
+
+    _fields_ = [
+        ("x", c_void_p), ("ldx", c_long), ("w", c_void_p), ("ldw", c_long), ("M", c_int), ("N", c_int), ("K", c_int),
+        ("xk_grp_n", c_int), ("xk_grp_stride", c_long), ("w_grp_n", c_int), ("w_grp_stride", c_long), ("w2_grp_n", c_int), ("w2_grp_stride", c_long),
+        ("x2", c_void_p), ("ldx2", c_long), ("w2", c_void_p), ("ldw2", c_long), ("K2", c_int), ("x2_grp_n", c_int), ("x2_grp_stride", c_long),
+        ("bias", c_void_p), ("alpha", c_float), ("out", c_void_p), ("ldo", c_long), ("out2", c_void_p), ("ldo2", c_long),
+        ("resid", c_void_p), ("ldr", c_long), ("gate", c_void_p), ("gate_bstride", c_long), ("rows_per_batch", c_int),
+        ("gate2", c_void_p), ("gate2_bstride", c_long), ("aux", c_void_p), ("ldaux", c_long), ("epilogue", c_int), ("variant", c_int), ("split_r", c_int),
+    ]
+
+
+class GemmTnArgs(Structure):
+    """include/ftmi355.h: ftmi_gemm_tn_args."""
+
+    _fields_ = [
+        ("u", c_void_p), ("ldu", c_long), ("v", c_void_p), ("ldv", c_long), ("c", c_void_p), ("ldc", c_long), ("M", c_int), ("P", c_int), ("Q", c_int),
+        ("v_grp_p", c_int), ("v_grp_stride", c_long), ("u_grp_p", c_int), ("u_grp_stride", c_long), ("u_fold", c_long), ("v_fold", c_long),
+        ("scale", c_float), ("batch", c_int), ("u_bstride", c_long), ("v_bstride", c_long), ("c_bstride", c_long),
+    ]
+
+
 _SIGS = {
     "ftmi_version": (c_int, []),
     "ftmi_last_error": (c_int, [c_char_p, c_size_t]),
@@ -161,6 +184,8 @@ _SIGS = {
     "ftmi_gemm_nt": (c_int, [c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long, c_void_p, c_float, c_void_p, c_long, c_int,
                              c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_long, c_int, c_void_p]),
     "ftmi_gemm_tn": (c_int, [c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_float, c_void_p]),
+    "ftmi_gemm_nt_ex": (c_int, [POINTER(GemmNtArgs), c_void_p]),
+    "ftmi_gemm_tn_ex": (c_int, [POINTER(GemmTnArgs), c_void_p]),
     "ftmi_fp8_upcast": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "ftmi_transpose_bf16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "ftmi_norm_modulate_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p]),

@@ -268,6 +268,38 @@ int ftmi_gemm_tn(int M, int P, int Q, const void* u, long ldu, const void* v, lo
     return gemm_tn(a, (hipStream_t)stream);
 }
 
+int ftmi_gemm_nt_ex(const ftmi_gemm_nt_args* p, ftmi_stream stream) {
+    if (!p) return set_error(FTMI_ERR_INVALID, "ftmi_gemm_nt_ex: null argument block");
+    if (!p->x || !p->w || !p->out) return set_error(FTMI_ERR_INVALID, "ftmi_gemm_nt_ex: null tensor");
+    if (p->epilogue < 0 || p->epilogue > 3) return set_error(FTMI_ERR_INVALID, "ftmi_gemm_nt_ex: bad epilogue");
+    if (p->epilogue == EPI_RESID && !p->resid) return set_error(FTMI_ERR_INVALID, "ftmi_gemm_nt_ex: residual epilogue without residual");
+    if (p->epilogue == EPI_DGELU && !p->aux) return set_error(FTMI_ERR_INVALID, "ftmi_gemm_nt_ex: gelu' epilogue without pre-activation");
+    if (p->epilogue == EPI_RESID && p->out2 && !p->gate2) return set_error(FTMI_ERR_INVALID, "ftmi_gemm_nt_ex: out2 on the residual epilogue without gate2");
+    if (p->K2 > 0 && (!p->x2 || !p->w2)) return set_error(FTMI_ERR_INVALID, "ftmi_gemm_nt_ex: K-extension without its operands");
+    GemmNtArgs a;
+    a.X = (const bf16_t*)p->x; a.ldx = p->ldx; a.W = (const bf16_t*)p->w; a.ldw = p->ldw; a.M = p->M; a.N = p->N; a.K = p->K;
+    a.xk_grp_n = p->xk_grp_n; a.xk_grp_stride = p->xk_grp_stride; a.w_grp_n = p->w_grp_n; a.w_grp_stride = p->w_grp_stride;
+    a.w2_grp_n = p->w2_grp_n; a.w2_grp_stride = p->w2_grp_stride;
+    a.X2 = (const bf16_t*)p->x2; a.ldx2 = p->ldx2; a.W2 = (const bf16_t*)p->w2; a.ldw2 = p->ldw2; a.K2 = p->K2;
+    a.x2_grp_n = p->x2_grp_n; a.x2_grp_stride = p->x2_grp_stride;
+    a.bias = (const bf16_t*)p->bias; a.alpha = p->alpha; a.out = (bf16_t*)p->out; a.ldo = p->ldo; a.out2 = (bf16_t*)p->out2; a.ldo2 = p->ldo2;
+    a.resid = (const bf16_t*)p->resid; a.ldr = p->ldr; a.gate = (const bf16_t*)p->gate; a.gate_bstride = p->gate_bstride;
+    a.rows_per_batch = p->rows_per_batch; a.gate2 = (const bf16_t*)p->gate2; a.gate2_bstride = p->gate2_bstride;
+    a.aux = (const bf16_t*)p->aux; a.ldaux = p->ldaux; a.epi = p->epilogue; a.variant = p->variant; a.split_r = p->split_r;
+    return gemm_nt(a, (hipStream_t)stream);
+}
+
+int ftmi_gemm_tn_ex(const ftmi_gemm_tn_args* p, ftmi_stream stream) {
+    if (!p) return set_error(FTMI_ERR_INVALID, "ftmi_gemm_tn_ex: null argument block");
+    if (!p->u || !p->v || !p->c) return set_error(FTMI_ERR_INVALID, "ftmi_gemm_tn_ex: null tensor");
+    GemmTnArgs a;
+    a.U = (const bf16_t*)p->u; a.ldu = p->ldu; a.V = (const bf16_t*)p->v; a.ldv = p->ldv; a.C = p->c; a.ldc = p->ldc; a.M = p->M; a.P = p->P; a.Q = p->Q;
+    a.v_grp_p = p->v_grp_p; a.v_grp_stride = p->v_grp_stride; a.u_grp_p = p->u_grp_p; a.u_grp_stride = p->u_grp_stride;
+    a.u_fold = p->u_fold; a.v_fold = p->v_fold; a.scale = p->scale; a.batch = p->batch;
+    a.u_bstride = p->u_bstride; a.v_bstride = p->v_bstride; a.c_bstride = p->c_bstride;
+    return gemm_tn(a, (hipStream_t)stream);
+}
+
 int ftmi_fp8_upcast(const void* src, void* dst, int rows, int cols, int transpose, ftmi_stream stream) {
     if (!src || !dst) return set_error(FTMI_ERR_INVALID, "ftmi_fp8_upcast: null tensor");
     return fp8_upcast((const uint8_t*)src, (bf16_t*)dst, rows, cols, transpose, (hipStream_t)stream);

@@ -115,6 +115,54 @@ def gemm_tn(u: torch.Tensor, v: torch.Tensor, out: Optional[torch.Tensor] = None
     return out
 
 
+def _ld(t: Optional[torch.Tensor], name: str) -> int:
+    if t is None:
+        return 0
+    if t.dim() != 2 or t.stride(1) != 1:
+        raise ValueError(f"{name} must be a 2-D view with contiguous columns")
+    return t.stride(0)
+
+
+def gemm_nt_ex(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, M: int, N: int, K: int, bias=None, alpha: float = 1.0, epilogue: int = 0, out2=None,
+               resid=None, gate=None, gate_bstride: Optional[int] = None, rows_per_batch: int = 0, gate2=None, gate2_bstride: Optional[int] = None, aux=None,
+               x2=None, w2=None, K2: int = 0, xk_grp_n: int = 0, xk_grp_stride: int = 0, w_grp_n: int = 0, w_grp_stride: int = 0, w2_grp_n: int = 0,
+               w2_grp_stride: int = 0, x2_grp_n: int = 0, x2_grp_stride: int = 0, split_r: int = 0, variant: int = 8, _override: Optional[dict] = None) -> None:
+    """The NT GEMM with its full launch description (ftmi_gemm_nt_ex; the contract is stated in include/ftmi355.h).  Tensors are 2-D bf16 views with contiguous
+    columns whose row strides become ldx / ldw / ldo / ...; M, N, K (and the group fields) say which part of them the launch uses.  gate / gate2 are
+    [samples, >= N] views (their row stride is the sample stride unless given).  ``_override``: test hook -- raw values written over fields of the descriptor by name after it has been filled (the refusal tests pass misaligned leading dimensions)."""
+    for n, t in (("x", x), ("w", w), ("out", out)):
+        require_gpu_tensor(t, n, bf16)
+    a = _lib.GemmNtArgs()
+    a.x, a.ldx, a.w, a.ldw, a.M, a.N, a.K = ptr(x), _ld(x, "x"), ptr(w), _ld(w, "w"), M, N, K
+    a.xk_grp_n, a.xk_grp_stride, a.w_grp_n, a.w_grp_stride, a.w2_grp_n, a.w2_grp_stride = xk_grp_n, xk_grp_stride, w_grp_n, w_grp_stride, w2_grp_n, w2_grp_stride
+    a.x2, a.ldx2, a.w2, a.ldw2, a.K2, a.x2_grp_n, a.x2_grp_stride = ptr(x2), _ld(x2, "x2"), ptr(w2), _ld(w2, "w2"), K2, x2_grp_n, x2_grp_stride
+    a.bias, a.alpha, a.out, a.ldo, a.out2, a.ldo2 = ptr(bias), float(alpha), ptr(out), _ld(out, "out"), ptr(out2), _ld(out2, "out2")
+    a.resid, a.ldr, a.aux, a.ldaux = ptr(resid), _ld(resid, "resid"), ptr(aux), _ld(aux, "aux")
+    a.gate, a.gate_bstride = ptr(gate), (_ld(gate, "gate") if gate_bstride is None else gate_bstride)
+    a.gate2, a.gate2_bstride = ptr(gate2), (_ld(gate2, "gate2") if gate2_bstride is None else gate2_bstride)
+    a.rows_per_batch, a.epilogue, a.variant, a.split_r = rows_per_batch, epilogue, variant, split_r
+    for k_, v_ in (_override or {}).items():
+        setattr(a, k_, v_)
+    check(_lib.load().ftmi_gemm_nt_ex(ctypes.byref(a), stream_ptr()), "ftmi_gemm_nt_ex")
+
+
+def gemm_tn_ex(u: torch.Tensor, v: torch.Tensor, c: torch.Tensor, *, M: int, P: int, Q: int, scale: float = 1.0, u_grp_p: int = 0, u_grp_stride: int = 0,
+               v_grp_p: int = 0, v_grp_stride: int = 0, u_fold: int = 0, v_fold: int = 0, batch: int = 1, u_bstride: int = 0, v_bstride: int = 0,
+               c_bstride: int = 0, _override: Optional[dict] = None) -> None:
+    """The TN GEMM with its full launch description (ftmi_gemm_tn_ex): c (fp32) += scale * u^T v.  u, v, c: the 2-D views of problem 0 (row strides = ldu / ldv /
+    ldc); a batched launch steps them by the element strides *_bstride (0 = shared).  ``_override``: as in gemm_nt_ex."""
+    require_gpu_tensor(u, "u", bf16)
+    require_gpu_tensor(v, "v", bf16)
+    require_gpu_tensor(c, "c", torch.float32)
+    a = _lib.GemmTnArgs()
+    a.u, a.ldu, a.v, a.ldv, a.c, a.ldc, a.M, a.P, a.Q = ptr(u), _ld(u, "u"), ptr(v), _ld(v, "v"), ptr(c), _ld(c, "c"), M, P, Q
+    a.v_grp_p, a.v_grp_stride, a.u_grp_p, a.u_grp_stride, a.u_fold, a.v_fold = v_grp_p, v_grp_stride, u_grp_p, u_grp_stride, u_fold, v_fold
+    a.scale, a.batch, a.u_bstride, a.v_bstride, a.c_bstride = float(scale), batch, u_bstride, v_bstride, c_bstride
+    for k_, v_ in (_override or {}).items():
+        setattr(a, k_, v_)
+    check(_lib.load().ftmi_gemm_tn_ex(ctypes.byref(a), stream_ptr()), "ftmi_gemm_tn_ex")
+
+
 def fp8_upcast(w8: torch.Tensor, out: Optional[torch.Tensor] = None, transpose: bool = False) -> torch.Tensor:
     """bf16 copy of a [rows, cols] ``torch.float8_e4m3fn`` weight (exact), optionally transposed to [cols, rows]; ``out``: a contiguous bf16 tensor of the
     result's size (e.g. a slice of a per-model weight arena)."""

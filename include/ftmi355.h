@@ -173,6 +173,55 @@ int ftmi_gemm_sk_trace(unsigned long long* out, int capacity);
 /* c[P,Q] (fp32) += scale * u[M,P]^T v[M,Q] */
 int ftmi_gemm_tn(int M, int P, int Q, const void* u, long ldu, const void* v, long ldv, float* c, long ldc, float scale,
                  ftmi_stream stream);
+/* The two GEMMs with their FULL launch description (tests: tests/test_gpu_gemm_contract.py states the contract).  Every caller-owned field of the
+ * launchers' argument blocks (csrc/kernels.h: GemmNtArgs / GemmTnArgs, same names, same meaning; a zeroed block with alpha / scale = 1 and batch = 1 is the
+ * plain launch).  Checked like ftmi_gemm_nt (null tensors, epilogue range, an epilogue without its input, out2 on the residual epilogue without gate2); every
+ * other refusal is the launcher's own (FTMI_ERR_UNSUPPORTED / FTMI_ERR_INVALID, nothing launched).
+ *   NT  y = alpha * x w^T + bias;  with a K-extension (K2 > 0)  y = bf(y) + x2 w2^T;  then the epilogue:
+ *       0 out = bf(y)    1 out2 = bf(y), out = bf(gelu_tanh(out2))    3 out = bf(bf(y) * gelu_tanh'(aux))
+ *       2 t = bf(y); gate: t = bf(t * gate[b, n]); out = bf(resid + t); out2 = bf(out * gate2[b, n])       (b = m / rows_per_batch; 0 = one sample)
+ *       column groups: tile column n0 reads X at column offset (n0 / xk_grp_n) * xk_grp_stride (X2: x2_grp_*), W row n lives at
+ *       (n / w_grp_n) * w_grp_stride + (n % w_grp_n) * ldw (W2: w2_grp_*); split_r > 0: the (hi, lo) down-projection, see ftmi_linear_lora_fwd
+ *   TN  c[b][p][q] += scale * sum_m u[b][m][col(p)] v[b][m][(p / v_grp_p) * v_grp_stride + q],  col(p) = (p / u_grp_p) * u_grp_stride + p % u_grp_p;
+ *       u_fold / v_fold > 0: that operand is a (hi, lo) pair of column planes this many elements apart, both contribute */
+typedef struct ftmi_gemm_nt_args {
+    const void* x; long ldx;
+    const void* w; long ldw;
+    int M, N, K;
+    int xk_grp_n; long xk_grp_stride;
+    int w_grp_n; long w_grp_stride;
+    int w2_grp_n; long w2_grp_stride;
+    const void* x2; long ldx2;
+    const void* w2; long ldw2;
+    int K2;
+    int x2_grp_n; long x2_grp_stride;
+    const void* bias;
+    float alpha;
+    void* out; long ldo;
+    void* out2; long ldo2;
+    const void* resid; long ldr;
+    const void* gate; long gate_bstride;
+    int rows_per_batch;
+    const void* gate2; long gate2_bstride;
+    const void* aux; long ldaux;
+    int epilogue;
+    int variant;
+    int split_r;
+} ftmi_gemm_nt_args;
+int ftmi_gemm_nt_ex(const ftmi_gemm_nt_args* args, ftmi_stream stream);
+typedef struct ftmi_gemm_tn_args {
+    const void* u; long ldu;
+    const void* v; long ldv;
+    float* c; long ldc;
+    int M, P, Q;
+    int v_grp_p; long v_grp_stride;
+    int u_grp_p; long u_grp_stride;
+    long u_fold, v_fold;
+    float scale;
+    int batch;
+    long u_bstride, v_bstride, c_bstride;
+} ftmi_gemm_tn_args;
+int ftmi_gemm_tn_ex(const ftmi_gemm_tn_args* args, ftmi_stream stream);
 /* fp8 weight storage of the layerwise up-casting recipe (finetrainers/trainer/sft_trainer/trainer.py:111-118: storage float8_e4m3fn, compute bf16):
  * dst (bf16) = exact up-cast of src [rows, cols] (OCP e4m3fn bytes); transpose != 0: dst is [cols, rows] = src^T (rows, cols multiples of 64) -- the layout
  * the input-gradient GEMMs read.  Called per block right before it runs; 1 byte read + 2 bytes written per weight. */
