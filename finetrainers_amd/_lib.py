@@ -185,6 +185,7 @@ _SIGS = {
                              c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_long, c_int, c_void_p]),
     "ftmi_gemm_tn": (c_int, [c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_float, c_void_p]),
     "ftmi_gemm_nt_ex": (c_int, [POINTER(GemmNtArgs), c_void_p]),
+    "ftmi_gemm_nt_route": (c_int, [POINTER(GemmNtArgs), POINTER(c_int)]),
     "ftmi_gemm_tn_ex": (c_int, [POINTER(GemmTnArgs), c_void_p]),
     "ftmi_fp8_upcast": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "ftmi_transpose_bf16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),

@@ -268,6 +268,20 @@ int ftmi_gemm_tn(int M, int P, int Q, const void* u, long ldu, const void* v, lo
     return gemm_tn(a, (hipStream_t)stream);
 }
 
+static GemmNtArgs nt_args_of(const ftmi_gemm_nt_args& p) {
+    GemmNtArgs a;
+    a.X = (const bf16_t*)p.x; a.ldx = p.ldx; a.W = (const bf16_t*)p.w; a.ldw = p.ldw; a.M = p.M; a.N = p.N; a.K = p.K;
+    a.xk_grp_n = p.xk_grp_n; a.xk_grp_stride = p.xk_grp_stride; a.w_grp_n = p.w_grp_n; a.w_grp_stride = p.w_grp_stride;
+    a.w2_grp_n = p.w2_grp_n; a.w2_grp_stride = p.w2_grp_stride;
+    a.X2 = (const bf16_t*)p.x2; a.ldx2 = p.ldx2; a.W2 = (const bf16_t*)p.w2; a.ldw2 = p.ldw2; a.K2 = p.K2;
+    a.x2_grp_n = p.x2_grp_n; a.x2_grp_stride = p.x2_grp_stride;
+    a.bias = (const bf16_t*)p.bias; a.alpha = p.alpha; a.out = (bf16_t*)p.out; a.ldo = p.ldo; a.out2 = (bf16_t*)p.out2; a.ldo2 = p.ldo2;
+    a.resid = (const bf16_t*)p.resid; a.ldr = p.ldr; a.gate = (const bf16_t*)p.gate; a.gate_bstride = p.gate_bstride;
+    a.rows_per_batch = p.rows_per_batch; a.gate2 = (const bf16_t*)p.gate2; a.gate2_bstride = p.gate2_bstride;
+    a.aux = (const bf16_t*)p.aux; a.ldaux = p.ldaux; a.epi = p.epilogue; a.variant = p.variant; a.split_r = p.split_r;
+    return a;
+}
+
 int ftmi_gemm_nt_ex(const ftmi_gemm_nt_args* p, ftmi_stream stream) {
     if (!p) return set_error(FTMI_ERR_INVALID, "ftmi_gemm_nt_ex: null argument block");
     if (!p->x || !p->w || !p->out) return set_error(FTMI_ERR_INVALID, "ftmi_gemm_nt_ex: null tensor");
@@ -276,17 +290,14 @@ int ftmi_gemm_nt_ex(const ftmi_gemm_nt_args* p, ftmi_stream stream) {
     if (p->epilogue == EPI_DGELU && !p->aux) return set_error(FTMI_ERR_INVALID, "ftmi_gemm_nt_ex: gelu' epilogue without pre-activation");
     if (p->epilogue == EPI_RESID && p->out2 && !p->gate2) return set_error(FTMI_ERR_INVALID, "ftmi_gemm_nt_ex: out2 on the residual epilogue without gate2");
     if (p->K2 > 0 && (!p->x2 || !p->w2)) return set_error(FTMI_ERR_INVALID, "ftmi_gemm_nt_ex: K-extension without its operands");
-    GemmNtArgs a;
-    a.X = (const bf16_t*)p->x; a.ldx = p->ldx; a.W = (const bf16_t*)p->w; a.ldw = p->ldw; a.M = p->M; a.N = p->N; a.K = p->K;
-    a.xk_grp_n = p->xk_grp_n; a.xk_grp_stride = p->xk_grp_stride; a.w_grp_n = p->w_grp_n; a.w_grp_stride = p->w_grp_stride;
-    a.w2_grp_n = p->w2_grp_n; a.w2_grp_stride = p->w2_grp_stride;
-    a.X2 = (const bf16_t*)p->x2; a.ldx2 = p->ldx2; a.W2 = (const bf16_t*)p->w2; a.ldw2 = p->ldw2; a.K2 = p->K2;
-    a.x2_grp_n = p->x2_grp_n; a.x2_grp_stride = p->x2_grp_stride;
-    a.bias = (const bf16_t*)p->bias; a.alpha = p->alpha; a.out = (bf16_t*)p->out; a.ldo = p->ldo; a.out2 = (bf16_t*)p->out2; a.ldo2 = p->ldo2;
-    a.resid = (const bf16_t*)p->resid; a.ldr = p->ldr; a.gate = (const bf16_t*)p->gate; a.gate_bstride = p->gate_bstride;
-    a.rows_per_batch = p->rows_per_batch; a.gate2 = (const bf16_t*)p->gate2; a.gate2_bstride = p->gate2_bstride;
-    a.aux = (const bf16_t*)p->aux; a.ldaux = p->ldaux; a.epi = p->epilogue; a.variant = p->variant; a.split_r = p->split_r;
-    return gemm_nt(a, (hipStream_t)stream);
+    return gemm_nt(nt_args_of(*p), (hipStream_t)stream);
+}
+
+int ftmi_gemm_nt_route(const ftmi_gemm_nt_args* p, int* route) {
+    if (!p || !route) return set_error(FTMI_ERR_INVALID, "ftmi_gemm_nt_route: null argument");
+    const NtRoute r = nt_route(nt_args_of(*p));
+    route[0] = r.kind; route[1] = r.variant; route[2] = r.bm; route[3] = r.bn;
+    return r.rc;
 }
 
 int ftmi_gemm_tn_ex(const ftmi_gemm_tn_args* p, ftmi_stream stream) {

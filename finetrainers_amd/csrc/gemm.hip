@@ -833,15 +833,12 @@ extern "C" int ftmi_trace_dump(const char* path) {
 namespace ftmi {
 #endif  // FTMI_TRACE
 
-template <int BM, int BN, int BK, int WM, int WN, bool GLDS, int MINW, int EPI, bool EXT, int LOOP>
-static int launch_nt3(const GemmNtArgs& a0, hipStream_t st) {
-    using T = NtTile<BM, BN, BK, WM, WN>;
-    const int ntm = (a0.M + BM - 1) / BM, ntn = a0.N / BN;
-    GemmNtArgs a = a0;
-    // Choose the XCD grid gm x gn = 8 by predicted fabric->L2 operand traffic: every XCD streams the X panels of its tile rows
-    // once per round of resident tiles and W panels once per tile column, so traffic ~ gn*|X|*rounds + gm*|W|.  Measured
-    // with rocprofv3 FETCH_SIZE on the step's shapes (profiles/r01_pmc_traffic.json, tools/gpu_map_exp.sh): splitting the
-    // token dimension over all 8 XCDs (gm = 8) moves the fewest bytes whenever M >= N; the launch grid is padded to 8*rm*rn.
+// tile -> XCD rasterisation shared by the tiled kernels: choose the XCD grid gm x gn = 8 by predicted fabric->L2 operand traffic.  Every XCD streams the
+// X panels of its tile rows once per round of resident tiles and W panels once per tile column, so traffic ~ gn*|X|*rounds + gm*|W|.  Measured
+// with rocprofv3 FETCH_SIZE on the step's shapes (profiles/r01_pmc_traffic.json, tools/gpu_map_exp.sh): splitting the
+// token dimension over all 8 XCDs (gm = 8) moves the fewest bytes whenever M >= N; the launch grid is padded to 8*rm*rn.
+static void choose_xcd_map(GemmNtArgs& a, int BM, int BN) {
+    const int ntm = (a.M + BM - 1) / BM, ntn = a.N / BN;
     long best = -1;
     static const int force_gm = env_int("FTMI_MAP_GM", 0);
     for (int gm = 1; gm <= 8; gm *= 2) {
@@ -860,6 +857,13 @@ static int launch_nt3(const GemmNtArgs& a0, hipStream_t st) {
             a.map_gm = gm; a.map_gn = gn; a.map_rm = rm; a.map_rn = rn;
         }
     }
+}
+
+template <int BM, int BN, int BK, int WM, int WN, bool GLDS, int MINW, int EPI, bool EXT, int LOOP>
+static int launch_nt3(const GemmNtArgs& a0, hipStream_t st) {
+    using T = NtTile<BM, BN, BK, WM, WN>;
+    GemmNtArgs a = a0;
+    choose_xcd_map(a, BM, BN);
     const size_t smem = (size_t)kl_lds_stages(LOOP) * T::STAGE;
     // algorithmic FLOPs: the extension's K2 carries the (hi, lo, hi) bf16 planes of an fp32 operand -- three executed K-steps per algorithmic one
     ProfScope prof(PROF_GEMM_NT, 2.0 * a.M * a.N * ((double)a.K + (double)a.K2 / 3.0), st);
@@ -1692,29 +1696,6 @@ __global__ __launch_bounds__(256, 1) void gemm_nt16_kernel(GemmNtArgs p) {
     nt16_body<TMW, EPI, EXT, DBG, RING, NoHook, RS>(p, smem, blockIdx.x);
 }
 
-// tile -> XCD rasterisation shared by the tiled kernels: choose the XCD grid gm x gn = 8 by predicted fabric->L2 operand traffic
-static void choose_xcd_map(GemmNtArgs& a, int BM, int BN) {
-    const int ntm = (a.M + BM - 1) / BM, ntn = a.N / BN;
-    long best = -1;
-    static const int force_gm = env_int("FTMI_MAP_GM", 0);
-    for (int gm = 1; gm <= 8; gm *= 2) {
-        if (force_gm > 0 && gm != force_gm) continue;
-        const int gn = 8 / gm;
-        const int rm = (ntm + gm - 1) / gm, rn = (ntn + gn - 1) / gn;
-        const long resident = 64;
-        const long rounds = ((long)rm * rn + resident - 1) / resident;
-        const long cols_per_round = (rn + rounds - 1) / rounds;
-        const long x_reads = (long)rm * BM * ((rn + cols_per_round - 1) / cols_per_round);
-        const long w_reads = (long)rn * BN;
-        const long waste = (long)rm * rn * 8 - (long)ntm * ntn;
-        const long cost = (x_reads + w_reads) * 8 + waste * 64;
-        if (best < 0 || cost < best) {
-            best = cost;
-            a.map_gm = gm; a.map_gn = gn; a.map_rm = rm; a.map_rn = rn;
-        }
-    }
-}
-
 template <int TMW, int EPI, bool EXT, int DBG, bool RING, int RS = 0>
 static int launch_nt16_3(const GemmNtArgs& a0, hipStream_t st) {
     GemmNtArgs a = a0;
@@ -2233,7 +2214,7 @@ __global__ __launch_bounds__(256, 1) void gemm_nt16_fused_kernel(FusedArgs a) {
 #endif  // FTMI_EXPERIMENTAL (fused down-projection + GEMM launch)
 
 // The automatic kernel choice for a "wide" NT launch (N % 128 == 0), as a pure function of the launch description (and of the FTMI_NT* switches, read once):
-// what gemm_nt() runs for variant 8 / 61, and what ftmi_gemm_nt_plan reports to the host tests.  Returns a variant number of the switch in gemm_nt().
+// what nt_route() takes for variant 8 / 61.  Returns a variant number of nt_variant_row().
 static int nt_auto_variant(const GemmNtArgs& a, bool ok256) {
     int variant = 8;
     // auto: pick the tile by the measured cost model of DESIGN.md section 6 -- a K-tile costs its SIMD 32 cycles per MFMA
@@ -2323,15 +2304,131 @@ static int nt_auto_variant(const GemmNtArgs& a, bool ok256) {
     return variant;
 }
 
-// variant: 0 = 128x128 BK64 register-staged, 1 = 128x128 BK64 direct-to-LDS, 2/3 = 128x128 BK32 direct-to-LDS,
-// 4 = 256x128 (8 waves), 5 = 256x256 (8 waves, 128x64 per wave), 6 = 256x256 (8 waves, 64x128 per wave),
-// 7 = 192x128 (4 waves, 96x64 per wave), 8 = auto (7 for M >= 1024 else 1)
-int gemm_nt(const GemmNtArgs& a, hipStream_t st) {
-    if (a.M <= 0 || a.N <= 0) return 0;
-    if (a.K % 64 != 0 || a.K2 % 64 != 0) return set_error(FTMI_ERR_UNSUPPORTED, "gemm_nt: K and K2 must be multiples of 64");
-    if (a.N % 64 != 0) return set_error(FTMI_ERR_UNSUPPORTED, "gemm_nt: N must be a multiple of 64");
+// ---- the variant table: the one place that says which tiled kernel a variant number is ----
+// A row is unconditional: nt_route() decides whether a launch may take it (a 256-wide tile needs 256-wide column groups) before it is looked up.
+//   variant         tile                   K loop                                                      who chooses it
+//   42              192 x 128              4 waves, buffer-descriptor direct-to-LDS, 2 workgroups per CU  auto where the 16 x 16 pipeline is not taken; every unknown
+//                                                                                                      number; every 256-wide variant without 256-wide column groups
+//   44              128 x 128              the same loop                                               auto: M < 1024 or fewer than FTMI_NT128_BELOW tiles
+//   47              256 x 256              the same loop, 8 waves x (128 x 64)                         the cost model (never at the default switches), FTMI_NT256
+//   70 / 71 / 72    256 x 256              hand-placed pipeline: 4 waves / loads over 3 slices / 8 waves  pinned only (tests, tools/ab_variants.sh)
+//   80 / 86 / 87    256 / 192 / 224 x 256  16 x 16 x 32 MFMA pipeline, direct-to-LDS on two slots      auto: 80 and 87 by default; 86 with FTMI_NT16_RS=0 FTMI_NT16_W3=0
+//   2286 / 2287     192 / 224 x 256        ... operands prefetched through register sets               auto: 2286 with FTMI_NT16_W3=0, 2287 with FTMI_NT16_RS bit 1
+//   1386 / 1387 / 1380  192 / 224 / 256 x 256  ... W on a three-slot direct-to-LDS ring                auto: 1386 by default, FTMI_NT16_W3 bits 1 / 2 for the others
+//   8 and 61 = the automatic choice (nt_auto_variant(); FTMI_NT_FORCE), 60 = the stream-K kernel of research builds.  N % 128 != 0 never gets here: 128 x 64 kernel.
+struct NtRow { int bm, bn; int (*launch)(const GemmNtArgs&, hipStream_t); };
+template <int BM, int BN, int BK, int WM, int WN, bool GLDS, int MINW, int LOOP = KL_GEN2_BUF>
+static NtRow nt_tile() { return {BM, BN, &launch_nt<BM, BN, BK, WM, WN, GLDS, MINW, LOOP>}; }
+template <int TMW, int DBG = 0, bool RING = false, int RS = 0>
+static NtRow nt_tile16() { return {32 * TMW, 256, &launch_nt16<TMW, DBG, RING, RS>}; }
+
+static NtRow nt_variant_row(int variant) {
+    switch (variant) {
+        case 42: return nt_tile<192, 128, 64, 2, 2, true, 2, KL_GEN2_BUF>();  // 192 x 128, 2 workgroups per CU
+        case 44: return nt_tile<128, 128, 64, 2, 2, true, 1, KL_GEN2_BUF>();  // 128 x 128 tiles (few rows)
+        case 47: return nt_tile<256, 256, 64, 2, 4, true, 1, KL_GEN2_BUF>();  // 8 waves x (128 x 64)
+        case 70: return nt_tile<256, 256, 64, 2, 2, true, 1, KL_PIPE2>();     // 4 waves x (128 x 128), hand-placed pipeline
+        case 71: return nt_tile<256, 256, 64, 2, 2, true, 1, KL_PIPE3>();     // ... loads spread over 3 slices
+        case 72: return nt_tile<256, 256, 64, 2, 4, true, 1, KL_PIPE2>();     // the same pipeline, 8 waves x (128 x 64)
+        case 80: return nt_tile16<8>();                  // 256 x 256 on 16 x 16 x 32 MFMAs
+        case 86: return nt_tile16<6>();                  // 192 x 256
+        case 87: return nt_tile16<7>();                  // 224 x 256
+        case 2286: return nt_tile16<6, 0, false, 2>();   // 192 x 256, register-staged prefetch (two register sets)
+        case 2287: return nt_tile16<7, 0, false, 2>();   // 224 x 256 (never with a K-extension: nt_route())
+        case 1386: return nt_tile16<6, 0, false, 13>();  // 192 x 256, W on the three-slot ring
+        case 1387: return nt_tile16<7, 0, false, 13>();  // 224 x 256
+        case 1380: return nt_tile16<8, 0, false, 13>();  // 256 x 256
+#ifdef FTMI_EXPERIMENTAL  // research builds (tools/bench_gemm.py, tools/ab_variants.sh): earlier K loops and timing experiments
+        case 0: return nt_tile<128, 128, 64, 2, 2, false, 1>();
+        case 1: return nt_tile<128, 128, 64, 2, 2, true, 1>();  // (the kernel of 44 under its first number)
+        case 2: return nt_tile<128, 128, 32, 2, 2, true, 1>();
+        case 3: return nt_tile<128, 128, 32, 2, 2, true, 3>();
+        case 4: return nt_tile<256, 128, 64, 4, 2, true, 1>();
+        case 5: return nt_tile<256, 256, 64, 2, 4, true, 1>();
+        case 6: return nt_tile<256, 256, 64, 4, 2, true, 1>();
+        case 7: return nt_tile<192, 128, 64, 2, 2, true, 1>();
+        case 13: return nt_tile<192, 128, 64, 2, 2, true, 1, KL_2STAGE_PIN>();  // 7 + pinned read/MFMA order
+        case 20: return nt_tile<192, 128, 64, 2, 2, true, 1, KL_DBG_NOLOAD>();  // timing experiment: no global loads in the K loop
+        case 21: return nt_tile<192, 128, 64, 2, 2, true, 1, KL_DBG_NOMFMA>();  // timing experiment: no MFMAs
+        case 24: return nt_tile<192, 128, 64, 2, 2, true, 1, KL_DBG_LDSONLY>();  // timing experiment: loads + LDS reads, no MFMAs
+        case 22: return nt_tile<256, 256, 64, 2, 4, true, 1, KL_DBG_NOLOAD>();
+        case 23: return nt_tile<256, 256, 64, 2, 4, true, 1, KL_DBG_NOMFMA>();
+        case 30: return nt_tile<192, 128, 64, 2, 2, true, 1, KL_GEN2>();  // second-generation 2-stage loop
+        case 36: return nt_tile<192, 128, 64, 2, 2, true, 1, KL_GEN2_SPREAD2>();  // 30 with the loads spread over 2 slices
+        case 43: return nt_tile<192, 128, 64, 2, 2, true, 1, KL_GEN2_REG>();  // register-staged twin of 42
+        case 45: return nt_tile<192, 128, 64, 2, 2, true, 1, KL_GEN2_REG2>();  // register-staged, two-tile global prefetch
+        case 46: return nt_tile<256, 256, 64, 2, 2, true, 1, KL_GEN2_BUF>();  // 4 waves x (128 x 128)
+        case 48: return nt_tile<384, 128, 64, 4, 2, true, 1, KL_GEN2_BUF>();  // two stacked 192 x 128 tiles sharing one W tile (8 waves, 1 WG / CU)
+        case 49: return nt_tile<192, 256, 64, 2, 4, true, 1, KL_GEN2_BUF>();  // 192 x 256, 8 waves
+        case 55: return nt_tile<256, 256, 32, 2, 4, true, 1, KL_ASM_RING4>();  // hand-placed K loop
+        case 56: return nt_tile<256, 256, 64, 2, 4, true, 1, KL_ASM_2STAGE>();  // hand-placed 2-stage loop
+        case 37: return nt_tile<192, 128, 64, 2, 2, true, 1, KL_GEN2_BURST>();  // 30 with the loads in one burst
+        case 38: return nt_tile<192, 128, 64, 2, 2, true, 1, KL_GEN2_PIN>();  // 30 + pinned read / MFMA order
+        case 39: return nt_tile<192, 128, 64, 2, 2, true, 1, KL_RING3>();   // 3-stage ring, 120 KB -> 1 WG / CU
+        case 41: return nt_tile<256, 256, 32, 2, 4, true, 1, KL_RING4_PIPE>();  // pipelined 4-stage ring
+        case 40: return nt_tile<192, 128, 32, 2, 2, true, 1, KL_RING4>();  // 4-stage ring, BK 32, 80 KB -> 2 WG / CU, 60 KB in flight each
+        case 31: return nt_tile<256, 256, 64, 2, 4, true, 1, KL_GEN2>();
+        case 32: return nt_tile<256, 256, 64, 2, 2, true, 1, KL_GEN2>();  // 4 waves, 128 x 128 per wave
+        case 33: return nt_tile<256, 256, 64, 2, 4, true, 1, KL_8PHASE>();  // 8-phase loop
+        case 34: return nt_tile<256, 256, 64, 2, 4, true, 1, KL_8PHASE_DBG_NOLOAD>();  // timing experiment: no staging in the loop
+        case 35: return nt_tile<256, 256, 64, 2, 4, true, 1, KL_8PHASE_DBG_NOMFMA>();  // timing experiment: no MFMAs
+        case 14: return nt_tile<256, 256, 32, 2, 4, true, 1, KL_PINGPONG>();
+        case 12: return nt_tile<192, 256, 32, 2, 4, true, 1, KL_PINGPONG>();
+        case 9: return nt_tile<192, 128, 32, 2, 2, true, 1, KL_RING3>();   // 3-stage ring, BK 32: 60 KB -> 2 WG / CU
+        case 10: return nt_tile<128, 128, 64, 2, 2, true, 1, KL_RING3>();  // 3-stage ring, BK 64: 96 KB -> 1 WG / CU
+        case 11: return nt_tile<128, 128, 32, 2, 2, true, 1, KL_RING3>();  // 3-stage ring, BK 32: 48 KB -> 3 WG / CU
+#endif
+#ifdef FTMI_LAB  // the ablation builds of tools/gemm_lab.hip (results wrong on purpose: only their time is read)
+        case 90: return nt_tile16<8, 0, true>();   // ... on the five-slot K = 32 ring
+        case 96: return nt_tile16<6, 0, true>();
+        case 190: return nt_tile16<8, 1, true>();
+        case 290: return nt_tile16<8, 2, true>();
+        case 186: return nt_tile16<6, 1>();
+        case 286: return nt_tile16<6, 2>();
+        case 386: return nt_tile16<6, 3>();
+        case 3286: return nt_tile16<6, 0, false, 3>();  // register-staged prefetch, three register sets
+        case 2280: return nt_tile16<8, 0, false, 2>();
+        case 586: return nt_tile16<6, 5>();   // no MFMAs (memory side alone)
+        case 1286: case 12086: return nt_tile16<6, 0, false, 12>();  // hybrid: X register-staged, W on a three-slot direct-to-LDS ring
+        case 1287: case 12087: return nt_tile16<7, 0, false, 12>();
+        case 1280: case 12080: return nt_tile16<8, 0, false, 12>();
+        case 13086: return nt_tile16<6, 0, false, 13>();  // X direct-to-LDS too (two slots), W three-slot ring (= 1386 / 1387 / 1380)
+        case 13087: return nt_tile16<7, 0, false, 13>();
+        case 13080: return nt_tile16<8, 0, false, 13>();
+        case 12586: return nt_tile16<6, 5, false, 12>();  // ... without MFMAs
+        case 5286: return nt_tile16<6, 5, false, 2>();   // register-staged loop: no MFMAs
+        case 12286: return nt_tile16<6, 12, false, 2>(); // ... and no LDS stores
+        case 13286: return nt_tile16<6, 13, false, 2>(); // ... and no fragment reads
+        case 1086: return nt_tile16<6, 10>(); // no MFMAs, no rendezvous: the loads as fast as they issue
+        case 1080: return nt_tile16<8, 10>();
+        case 686: return nt_tile16<6, 6>();   // no loads, no rendezvous
+        case 580: return nt_tile16<8, 5>();
+        case 180: return nt_tile16<8, 1>();
+        case 280: return nt_tile16<8, 2>();
+        case 380: return nt_tile16<8, 3>();
+        case 170: return nt_tile<256, 256, 64, 2, 2, true, 1, 100 + KL_PIPE2>();  // no loads in the loop
+        case 270: return nt_tile<256, 256, 64, 2, 2, true, 1, 200 + KL_PIPE2>();  // no rendezvous in the loop
+        case 370: return nt_tile<256, 256, 64, 2, 2, true, 1, 300 + KL_PIPE2>();  // no fragment reads in the loop
+        case 470: return nt_tile<256, 256, 64, 2, 2, true, 1, 400 + KL_PIPE2>();  // staggered waves
+        case 172: return nt_tile<256, 256, 64, 2, 4, true, 1, 100 + KL_PIPE2>();
+        case 272: return nt_tile<256, 256, 64, 2, 4, true, 1, 200 + KL_PIPE2>();
+        case 372: return nt_tile<256, 256, 64, 2, 4, true, 1, 300 + KL_PIPE2>();
+#endif
+        default: return {0, 0, nullptr};  // not a variant of this build: nt_route() takes 42
+    }
+}
+
+// Which kernel runs a launch: ALL of the routing, as a pure function of the launch description and of the FTMI_* switches (each read once).  gemm_nt() launches
+// what this returns, ftmi_gemm_nt_plan / ftmi_gemm_nt_route report it to the host tests, gemm_nt_lora_fused() takes its tile choice from it.  A refusal has set
+// the error message (rc != 0).  `variant` is the row of nt_variant_row() after every fall-back (0 for the kernels outside the table), bm x bn the tile that runs.
+NtRoute nt_route(const GemmNtArgs& a) {
+    const auto refuse = [](int code, const char* msg) { NtRoute r; r.rc = set_error(code, msg); return r; };
+    const auto route = [](int kind, int variant, int bm, int bn, bool ok256 = false) { NtRoute r; r.kind = kind; r.variant = variant; r.bm = bm; r.bn = bn; r.ok256 = ok256; return r; };
+    if (a.M <= 0 || a.N <= 0) return NtRoute();
+    if (a.K % 64 != 0 || a.K2 % 64 != 0) return refuse(FTMI_ERR_UNSUPPORTED, "gemm_nt: K and K2 must be multiples of 64");
+    if (a.N % 64 != 0) return refuse(FTMI_ERR_UNSUPPORTED, "gemm_nt: N must be a multiple of 64");
     if ((a.ldx % 8) || (a.ldw % 8) || (a.ldo % 8) || (a.K2 > 0 && ((a.ldx2 % 8) || (a.ldw2 % 8))))
-        return set_error(FTMI_ERR_INVALID, "gemm_nt: leading dimensions must keep 16-byte row alignment");
+        return refuse(FTMI_ERR_INVALID, "gemm_nt: leading dimensions must keep 16-byte row alignment");
     // the persistent 256 x 256 stream-K kernel (gemm_sk.hip): 60 pins it; 61 = the automatic choice among the one-tile-per-workgroup kernels
     // below.  8 (auto) takes it only with FTMI_SK=1: measured on the step's shapes (profiles/r03_gemm_streamk.txt) it is correct but 5-25 %
     // SLOWER than the one-tile kernels -- a persistent workgroup waits for its own 128 KB of output stores (vmcnt counts stores in order with
@@ -2339,208 +2436,93 @@ int gemm_nt(const GemmNtArgs& a, hipStream_t st) {
     // while its successor on the CU already computes; the fp32 fix-up of a 256 x 256 partial costs another ~6 us per hand-off.
 #ifdef FTMI_EXPERIMENTAL
     if (a.variant == 60) {
-        if (!gemm_nt_sk_eligible(a)) return set_error(FTMI_ERR_UNSUPPORTED, "gemm_nt: the stream-K kernel needs N % 256 == 0, M >= 1024, K >= 256 and 256-wide groups");
-        return gemm_nt_sk(a, st);
+        if (!gemm_nt_sk_eligible(a)) return refuse(FTMI_ERR_UNSUPPORTED, "gemm_nt: the stream-K kernel needs N % 256 == 0, M >= 1024, K >= 256 and 256-wide groups");
+        return route(NT_STREAMK, 60, 256, 256);
     }
     if (a.variant == 8) {
         static const int use_sk = env_int("FTMI_SK", 0);
-        if (use_sk && gemm_nt_sk_eligible(a)) return gemm_nt_sk(a, st);
+        if (use_sk && gemm_nt_sk_eligible(a)) return route(NT_STREAMK, 60, 256, 256);
     }
 #else
-    if (a.variant == 60) return set_error(FTMI_ERR_UNSUPPORTED, "gemm_nt: the stream-K kernel (variant 60) exists in FTMI_EXPERIMENTAL builds only");
+    if (a.variant == 60) return refuse(FTMI_ERR_UNSUPPORTED, "gemm_nt: the stream-K kernel (variant 60) exists in FTMI_EXPERIMENTAL builds only");
 #endif
-    if (a.split_r > 0) {  // fp32-equivalent LoRA down-projection: always the LDS-ring skinny kernel (any M, any N, grouped W allowed)
+    if (a.split_r > 0) {  // fp32-equivalent LoRA down-projection: always a skinny kernel (any M, any N, grouped W allowed)
         if (a.K2 != 0 || a.epi != EPI_STORE || a.bias || a.K < 256 || a.split_r % 64 != 0 || (a.N / 2) % a.split_r != 0)
-            return set_error(FTMI_ERR_UNSUPPORTED, "gemm_nt: split (hi/lo) mode needs a plain store, K >= 256 and whole groups of split_r outputs");
-        if ((a.w_grp_n > 0 && a.w_grp_n % 64) || (a.xk_grp_n > 0 && a.xk_grp_n % 64)) return set_error(FTMI_ERR_UNSUPPORTED, "gemm_nt: group width must be a multiple of 64");
+            return refuse(FTMI_ERR_UNSUPPORTED, "gemm_nt: split (hi/lo) mode needs a plain store, K >= 256 and whole groups of split_r outputs");
+        if ((a.w_grp_n > 0 && a.w_grp_n % 64) || (a.xk_grp_n > 0 && a.xk_grp_n % 64)) return refuse(FTMI_ERR_UNSUPPORTED, "gemm_nt: group width must be a multiple of 64");
 #ifdef FTMI_EXPERIMENTAL
         // third-generation kernel (gemm_skinny.hip: 64 x 128 tiles, optional K cut across workgroups): correct, and 3-30 % SLOWER in the step than
-        // the kernel below on every setting tried (profiles/r03_skinny_experiments.txt) -- research build only
+        // the kernels below on every setting tried (profiles/r03_skinny_experiments.txt) -- research build only
         static const int use_sk3 = env_int("FTMI_SKINNY3", 0);
-        if (use_sk3 && gemm_nt_skinny3_eligible(a)) return gemm_nt_skinny3(a, st);
+        if (use_sk3 && gemm_nt_skinny3_eligible(a)) return route(NT_SKINNY3, 0, 64, 128);
 #endif
-        ProfScope prof(PROF_GEMM_SKINNY, 2.0 * a.M * a.N * (double)a.K, st);
         // 64-row tiles (fourth generation) wherever they fill at least a third of the chip; FTMI_SKINNY4 is read once (EnvSwitch: one process can still
         // compare the kernels through ftmi_reload_switches() -- they are bit-identical: tests/test_gpu_kernels.py)
         static const EnvSwitch sk4_sw("FTMI_SKINNY4", 1);
         const int sk4 = sk4_sw.get();  // 1: 64-deep stages, 2: 32-deep stages
-        if (sk4 && (long)((a.M + 63) / 64) * (a.N / 64) >= 84) {
-            constexpr int kSmem4 = 4 * 2 * 16384;
-            static const bool attr_ok4 =
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_skinny4_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmem4) == hipSuccess &&
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_skinny4_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmem4) == hipSuccess;
-            if (!attr_ok4) return set_error(FTMI_ERR_LAUNCH, "gemm_nt: cannot raise the dynamic LDS limit");
-            const dim3 grid4(8 * (a.N / 64), ((a.M + 63) / 64 + 7) / 8);
-            if (sk4 == 2) hipLaunchKernelGGL(gemm_nt_skinny4_kernel<32>, grid4, dim3(256), kSmem4, st, a);
-            else hipLaunchKernelGGL(gemm_nt_skinny4_kernel<64>, grid4, dim3(256), kSmem4, st, a);
-            return check_launch("gemm_nt_skinny");
-        }
-        constexpr int kSmem = 4 * 3 * 12288;
-        static const bool attr_ok =
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_skinny2_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmem) == hipSuccess;
-        if (!attr_ok) return set_error(FTMI_ERR_LAUNCH, "gemm_nt: cannot raise the dynamic LDS limit");
-        hipLaunchKernelGGL(gemm_nt_skinny2_kernel<0>, dim3(((a.M + 31) / 32) * (a.N / 64)), dim3(256), kSmem, st, a);
-        return check_launch("gemm_nt_skinny");
+        if (sk4 && (long)((a.M + 63) / 64) * (a.N / 64) >= 84) return route(sk4 == 2 ? NT_SPLIT64_K32 : NT_SPLIT64_K64, 0, 64, 64);
+        return route(NT_SKINNY_RING, 0, 32, 64);
     }
     if (a.variant != 0 && a.N <= 256 && a.K2 == 0 && a.epi == EPI_STORE && a.M >= 512 && a.w_grp_n == 0 && (a.xk_grp_n == 0 || a.xk_grp_n % 64 == 0)) {
-        ProfScope prof(PROF_GEMM_SKINNY, 2.0 * a.M * a.N * (double)a.K, st);
         static const int ks = env_int("FTMI_SKINNY_KS", 2);  // 2 = LDS-ring kernel, 4 / 8 = direct-gather kernel with a 4- / 8-way K split
+        if (ks == 2 && a.K % 256 == 0) return route(NT_SKINNY_RING, 0, 32, 64);
         // 8-way K split when it divides into whole load batches: halves the dependent load->MFMA chain of every wave
-        if (ks == 2 && a.K % 256 == 0) {
-            constexpr int kSmem = 4 * 3 * 12288;
-            static const bool attr_ok =
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_skinny2_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, kSmem) == hipSuccess;
-            if (!attr_ok) return set_error(FTMI_ERR_LAUNCH, "gemm_nt: cannot raise the dynamic LDS limit");
-            hipLaunchKernelGGL(gemm_nt_skinny2_kernel<0>, dim3(((a.M + 31) / 32) * (a.N / 64)), dim3(256), kSmem, st, a);
-        } else if (ks == 8 && a.K % 1024 == 0)
-            hipLaunchKernelGGL(gemm_nt_skinny_kernel<8>, dim3(((a.M + 31) / 32) * (a.N / 64)), dim3(512), 0, st, a);
-        else
-            hipLaunchKernelGGL(gemm_nt_skinny_kernel<4>, dim3(((a.M + 31) / 32) * (a.N / 64)), dim3(256), 0, st, a);
-        return check_launch("gemm_nt_skinny");
+        return route(ks == 8 && a.K % 1024 == 0 ? NT_SKINNY_GATHER8 : NT_SKINNY_GATHER4, 0, 32, 64);
     }
     if ((a.w_grp_n > 0 && a.w_grp_n % 64) || (a.w2_grp_n > 0 && a.w2_grp_n % 64))
-        return set_error(FTMI_ERR_UNSUPPORTED, "gemm_nt: weight group size must be a multiple of 64");
+        return refuse(FTMI_ERR_UNSUPPORTED, "gemm_nt: weight group size must be a multiple of 64");
     const bool wide = a.N % 128 == 0 && !(a.w_grp_n > 0 && a.w_grp_n % 128 != 0) && !(a.w2_grp_n > 0 && a.w2_grp_n % 128 != 0) && !(a.xk_grp_n > 0 && a.xk_grp_n % 128 != 0) && !(a.x2_grp_n > 0 && a.x2_grp_n % 128 != 0);
-    if (!wide && ((a.xk_grp_n > 0 && a.xk_grp_n % 64 != 0) || (a.x2_grp_n > 0 && a.x2_grp_n % 64 != 0)))
-        return set_error(FTMI_ERR_UNSUPPORTED, "gemm_nt: group width must be a multiple of 64");
-    if (wide) {
-        int variant = a.variant == 61 ? 8 : a.variant;
-        // FTMI_NT_FORCE=<variant>: every launch the automatic choice would make takes this kernel instead (in-step A/B: tools/ab_env.sh)
-        static const int force_all = env_int("FTMI_NT_FORCE", 0);
-        auto g256 = [](int g) { return g <= 0 || g % 256 == 0; };
-        const bool ok256 = a.N % 256 == 0 && g256(a.w_grp_n) && g256(a.w2_grp_n) && g256(a.xk_grp_n) && g256(a.x2_grp_n);  // 256-wide column tiles allowed
-        if (variant == 8 && force_all > 0 && a.M >= 1024 && ok256) variant = force_all;
-        if (variant == 8) variant = nt_auto_variant(a, ok256);
-#if defined(FTMI_LAB)
-        switch (variant) {
-            case 47: return launch_nt<256, 256, 64, 2, 4, true, 1, KL_GEN2_BUF>(a, st);
-            case 70: return launch_nt<256, 256, 64, 2, 2, true, 1, KL_PIPE2>(a, st);
-            case 71: return launch_nt<256, 256, 64, 2, 2, true, 1, KL_PIPE3>(a, st);
-            case 72: return launch_nt<256, 256, 64, 2, 4, true, 1, KL_PIPE2>(a, st);
-            case 80: return launch_nt16<8>(a, st);   // 16 x 16 x 32 MFMA, 256 x 256 tiles
-            case 90: return launch_nt16<8, 0, true>(a, st);   // ... on the five-slot K = 32 ring
-            case 96: return launch_nt16<6, 0, true>(a, st);
-            case 190: return launch_nt16<8, 1, true>(a, st);
-            case 290: return launch_nt16<8, 2, true>(a, st);
-            case 86: return launch_nt16<6>(a, st);   // ... 192 x 256 tiles
-            case 87: return launch_nt16<7>(a, st);   // ... 224 x 256 tiles
-            case 186: return launch_nt16<6, 1>(a, st);
-            case 286: return launch_nt16<6, 2>(a, st);
-            case 386: return launch_nt16<6, 3>(a, st);
-            case 2286: return launch_nt16<6, 0, false, 2>(a, st);  // register-staged prefetch, two / three register sets
-            case 3286: return launch_nt16<6, 0, false, 3>(a, st);
-            case 2287: return launch_nt16<7, 0, false, 2>(a, st);
-            case 2280: return launch_nt16<8, 0, false, 2>(a, st);
-            case 586: return launch_nt16<6, 5>(a, st);   // no MFMAs (memory side alone)
-            case 1386: return launch_nt16<6, 0, false, 13>(a, st);
-            case 1387: return launch_nt16<7, 0, false, 13>(a, st);
-            case 1380: return launch_nt16<8, 0, false, 13>(a, st);
-            case 1286: return launch_nt16<6, 0, false, 12>(a, st);
-            case 1287: return launch_nt16<7, 0, false, 12>(a, st);
-            case 1280: return launch_nt16<8, 0, false, 12>(a, st);
-            case 12086: return launch_nt16<6, 0, false, 12>(a, st);  // hybrid: X register-staged, W on a three-slot direct-to-LDS ring
-            case 12087: return launch_nt16<7, 0, false, 12>(a, st);
-            case 13086: return launch_nt16<6, 0, false, 13>(a, st);  // X direct-to-LDS too (two slots), W three-slot ring
-            case 13087: return launch_nt16<7, 0, false, 13>(a, st);
-            case 13080: return launch_nt16<8, 0, false, 13>(a, st);
-            case 12080: return launch_nt16<8, 0, false, 12>(a, st);
-            case 12586: return launch_nt16<6, 5, false, 12>(a, st);  // ... without MFMAs
-            case 5286: return launch_nt16<6, 5, false, 2>(a, st);   // register-staged loop: no MFMAs
-            case 12286: return launch_nt16<6, 12, false, 2>(a, st); // ... and no LDS stores
-            case 13286: return launch_nt16<6, 13, false, 2>(a, st); // ... and no fragment reads
-            case 1086: return launch_nt16<6, 10>(a, st); // no MFMAs, no rendezvous: the loads as fast as they issue
-            case 1080: return launch_nt16<8, 10>(a, st);
-            case 686: return launch_nt16<6, 6>(a, st);   // no loads, no rendezvous
-            case 580: return launch_nt16<8, 5>(a, st);
-            case 180: return launch_nt16<8, 1>(a, st);
-            case 280: return launch_nt16<8, 2>(a, st);
-            case 380: return launch_nt16<8, 3>(a, st);
-            case 170: return launch_nt<256, 256, 64, 2, 2, true, 1, 100 + KL_PIPE2>(a, st);  // no loads in the loop
-            case 270: return launch_nt<256, 256, 64, 2, 2, true, 1, 200 + KL_PIPE2>(a, st);  // no rendezvous in the loop
-            case 370: return launch_nt<256, 256, 64, 2, 2, true, 1, 300 + KL_PIPE2>(a, st);  // no fragment reads in the loop
-            case 470: return launch_nt<256, 256, 64, 2, 2, true, 1, 400 + KL_PIPE2>(a, st);  // staggered waves
-            case 172: return launch_nt<256, 256, 64, 2, 4, true, 1, 100 + KL_PIPE2>(a, st);
-            case 272: return launch_nt<256, 256, 64, 2, 4, true, 1, 200 + KL_PIPE2>(a, st);
-            case 372: return launch_nt<256, 256, 64, 2, 4, true, 1, 300 + KL_PIPE2>(a, st);
-            default: return launch_nt<192, 128, 64, 2, 2, true, 2, KL_GEN2_BUF>(a, st);
-        }
+    if (!wide) {
+        if ((a.xk_grp_n > 0 && a.xk_grp_n % 64 != 0) || (a.x2_grp_n > 0 && a.x2_grp_n % 64 != 0))
+            return refuse(FTMI_ERR_UNSUPPORTED, "gemm_nt: group width must be a multiple of 64");
+        return route(NT_TILE_128x64, 0, 128, 64);
     }
-#elif defined(FTMI_EXPERIMENTAL)
-        switch (variant) {
-            case 80: if (ok256) return launch_nt16<8>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 2, KL_GEN2_BUF>(a, st);  // 256 x 256 on 16 x 16 x 32 MFMAs
-            case 86: if (ok256) return launch_nt16<6>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 2, KL_GEN2_BUF>(a, st);  // 192 x 256
-            case 87: if (ok256) return launch_nt16<7>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 2, KL_GEN2_BUF>(a, st);  // 224 x 256
-            case 1386: if (ok256) return launch_nt16<6, 0, false, 13>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 2, KL_GEN2_BUF>(a, st);  // 192 x 256, W on the three-slot ring
-            case 1387: if (ok256) return launch_nt16<7, 0, false, 13>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 2, KL_GEN2_BUF>(a, st);  // 224 x 256
-            case 1380: if (ok256) return launch_nt16<8, 0, false, 13>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 2, KL_GEN2_BUF>(a, st);  // 256 x 256
-            case 2286: if (ok256) return launch_nt16<6, 0, false, 2>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 2, KL_GEN2_BUF>(a, st);  // 192 x 256, register-staged prefetch
-            case 2287: if (ok256 && a.K2 == 0) return launch_nt16<7, 0, false, 2>(a, st); else if (ok256) return launch_nt16<7>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 2, KL_GEN2_BUF>(a, st);  // 224 x 256, register-staged prefetch
-            case 70: if (ok256) return launch_nt<256, 256, 64, 2, 2, true, 1, KL_PIPE2>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 2, KL_GEN2_BUF>(a, st);  // 4 waves x (128 x 128), hand-placed pipeline
-            case 71: if (ok256) return launch_nt<256, 256, 64, 2, 2, true, 1, KL_PIPE3>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 2, KL_GEN2_BUF>(a, st);  // ... loads spread over 3 slices
-            case 72: if (ok256) return launch_nt<256, 256, 64, 2, 4, true, 1, KL_PIPE2>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 2, KL_GEN2_BUF>(a, st);  // the same pipeline, 8 waves x (128 x 64)
-            case 0: return launch_nt<128, 128, 64, 2, 2, false, 1>(a, st);
-            case 2: return launch_nt<128, 128, 32, 2, 2, true, 1>(a, st);
-            case 3: return launch_nt<128, 128, 32, 2, 2, true, 3>(a, st);
-            case 4: return launch_nt<256, 128, 64, 4, 2, true, 1>(a, st);
-            case 5: if (a.N % 256 == 0) return launch_nt<256, 256, 64, 2, 4, true, 1>(a, st); else return launch_nt<256, 128, 64, 4, 2, true, 1>(a, st);
-            case 6: if (a.N % 256 == 0) return launch_nt<256, 256, 64, 4, 2, true, 1>(a, st); else return launch_nt<256, 128, 64, 4, 2, true, 1>(a, st);
-            case 7: return launch_nt<192, 128, 64, 2, 2, true, 1>(a, st);
-            case 13: return launch_nt<192, 128, 64, 2, 2, true, 1, KL_2STAGE_PIN>(a, st);  // 7 + pinned read/MFMA order
-            case 20: return launch_nt<192, 128, 64, 2, 2, true, 1, KL_DBG_NOLOAD>(a, st);  // timing experiment: no global loads in the K loop
-            case 21: return launch_nt<192, 128, 64, 2, 2, true, 1, KL_DBG_NOMFMA>(a, st);  // timing experiment: no MFMAs
-            case 24: return launch_nt<192, 128, 64, 2, 2, true, 1, KL_DBG_LDSONLY>(a, st);  // timing experiment: loads + LDS reads, no MFMAs
-            case 22: return launch_nt<256, 256, 64, 2, 4, true, 1, KL_DBG_NOLOAD>(a, st);
-            case 30: return launch_nt<192, 128, 64, 2, 2, true, 1, KL_GEN2>(a, st);  // second-generation 2-stage loop
-            case 36: return launch_nt<192, 128, 64, 2, 2, true, 1, KL_GEN2_SPREAD2>(a, st);  // 30 with the loads spread over 2 slices
-            case 42: return launch_nt<192, 128, 64, 2, 2, true, 2, KL_GEN2_BUF>(a, st);  // 36 with buffer-descriptor loads
-            case 43: return launch_nt<192, 128, 64, 2, 2, true, 1, KL_GEN2_REG>(a, st);  // register-staged twin of 42
-            case 45: return launch_nt<192, 128, 64, 2, 2, true, 1, KL_GEN2_REG2>(a, st);  // register-staged, two-tile global prefetch
-            case 46: if (a.N % 256 == 0) return launch_nt<256, 256, 64, 2, 2, true, 1, KL_GEN2_BUF>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 1, KL_GEN2_BUF>(a, st);  // 4 waves x (128 x 128)
-            case 47: if (ok256) return launch_nt<256, 256, 64, 2, 4, true, 1, KL_GEN2_BUF>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 1, KL_GEN2_BUF>(a, st);  // 8 waves x (128 x 64)
-            case 48: return launch_nt<384, 128, 64, 4, 2, true, 1, KL_GEN2_BUF>(a, st);  // two stacked 192 x 128 tiles sharing one W tile (8 waves, 1 WG / CU)
-            case 49: if (a.N % 256 == 0) return launch_nt<192, 256, 64, 2, 4, true, 1, KL_GEN2_BUF>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 1, KL_GEN2_BUF>(a, st);  // 192 x 256, 8 waves
-            case 55: if (a.N % 256 == 0) return launch_nt<256, 256, 32, 2, 4, true, 1, KL_ASM_RING4>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 2, KL_GEN2_BUF>(a, st);  // hand-placed K loop
-            case 56: if (a.N % 256 == 0) return launch_nt<256, 256, 64, 2, 4, true, 1, KL_ASM_2STAGE>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 2, KL_GEN2_BUF>(a, st);  // hand-placed 2-stage loop
-            case 44: return launch_nt<128, 128, 64, 2, 2, true, 1, KL_GEN2_BUF>(a, st);  // production loop on 128 x 128 tiles
-            case 37: return launch_nt<192, 128, 64, 2, 2, true, 1, KL_GEN2_BURST>(a, st);  // 30 with the loads in one burst
-            case 38: return launch_nt<192, 128, 64, 2, 2, true, 1, KL_GEN2_PIN>(a, st);  // 30 + pinned read / MFMA order
-            case 39: return launch_nt<192, 128, 64, 2, 2, true, 1, KL_RING3>(a, st);   // 3-stage ring, 120 KB -> 1 WG / CU
-            case 41: if (a.N % 256 == 0) return launch_nt<256, 256, 32, 2, 4, true, 1, KL_RING4_PIPE>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 1, KL_GEN2_SPREAD2>(a, st);  // pipelined 4-stage ring
-            case 40: return launch_nt<192, 128, 32, 2, 2, true, 1, KL_RING4>(a, st);  // 4-stage ring, BK 32, 80 KB -> 2 WG / CU, 60 KB in flight each
-            case 31: if (a.N % 256 == 0) return launch_nt<256, 256, 64, 2, 4, true, 1, KL_GEN2>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 1, KL_GEN2>(a, st);
-            case 33: if (a.N % 256 == 0) return launch_nt<256, 256, 64, 2, 4, true, 1, KL_8PHASE>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 1, KL_GEN2>(a, st);  // 8-phase loop
-            case 34: return launch_nt<256, 256, 64, 2, 4, true, 1, KL_8PHASE_DBG_NOLOAD>(a, st);  // timing experiment: no staging in the loop
-            case 35: return launch_nt<256, 256, 64, 2, 4, true, 1, KL_8PHASE_DBG_NOMFMA>(a, st);  // timing experiment: no MFMAs
-            case 32: if (a.N % 256 == 0) return launch_nt<256, 256, 64, 2, 2, true, 1, KL_GEN2>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 1, KL_GEN2>(a, st);  // 4 waves, 128 x 128 per wave
-            case 23: return launch_nt<256, 256, 64, 2, 4, true, 1, KL_DBG_NOMFMA>(a, st);
-            case 14: if (a.N % 256 == 0) return launch_nt<256, 256, 32, 2, 4, true, 1, KL_PINGPONG>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 1>(a, st);
-            case 12: if (a.N % 256 == 0) return launch_nt<192, 256, 32, 2, 4, true, 1, KL_PINGPONG>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 1>(a, st);
-            case 9: return launch_nt<192, 128, 32, 2, 2, true, 1, KL_RING3>(a, st);   // 3-stage ring, BK 32: 60 KB -> 2 WG / CU
-            case 10: return launch_nt<128, 128, 64, 2, 2, true, 1, KL_RING3>(a, st);  // 3-stage ring, BK 64: 96 KB -> 1 WG / CU
-            case 11: return launch_nt<128, 128, 32, 2, 2, true, 1, KL_RING3>(a, st);  // 3-stage ring, BK 32: 48 KB -> 3 WG / CU
-            default: return launch_nt<128, 128, 64, 2, 2, true, 1>(a, st);
-        }
+    int variant = a.variant == 61 ? 8 : a.variant;
+    // FTMI_NT_FORCE=<variant>: every launch the automatic choice would make takes this kernel instead (in-step A/B: tools/ab_env.sh)
+    static const int force_all = env_int("FTMI_NT_FORCE", 0);
+    auto g256 = [](int g) { return g <= 0 || g % 256 == 0; };
+    const bool ok256 = a.N % 256 == 0 && g256(a.w_grp_n) && g256(a.w2_grp_n) && g256(a.xk_grp_n) && g256(a.x2_grp_n);  // 256-wide column tiles allowed
+    if (variant == 8 && force_all > 0 && a.M >= 1024 && ok256) variant = force_all;
+    if (variant == 8) variant = nt_auto_variant(a, ok256);
+    // (with a K-extension the 224-row register-staged kernel would spill -- launch_nt16() does not even instantiate it: the direct-to-LDS loop takes the launch)
+    if (variant == 2287 && a.K2 > 0) variant = 87;
+    NtRow row = nt_variant_row(variant);
+    // an unknown number, or a 256-wide tile that would straddle a narrower column group (ok256, not N % 256 alone): 192 x 128, two workgroups per CU
+    if (!row.launch || (row.bn == 256 && !ok256)) {
+        variant = 42;
+        row = nt_variant_row(42);
     }
-#else
-        switch (variant) {
-            case 80: if (ok256) return launch_nt16<8>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 2, KL_GEN2_BUF>(a, st);  // 256 x 256 on 16 x 16 x 32 MFMAs
-            case 86: if (ok256) return launch_nt16<6>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 2, KL_GEN2_BUF>(a, st);  // 192 x 256
-            case 87: if (ok256) return launch_nt16<7>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 2, KL_GEN2_BUF>(a, st);  // 224 x 256
-            case 1386: if (ok256) return launch_nt16<6, 0, false, 13>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 2, KL_GEN2_BUF>(a, st);  // 192 x 256, W on the three-slot ring
-            case 1387: if (ok256) return launch_nt16<7, 0, false, 13>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 2, KL_GEN2_BUF>(a, st);  // 224 x 256
-            case 1380: if (ok256) return launch_nt16<8, 0, false, 13>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 2, KL_GEN2_BUF>(a, st);  // 256 x 256
-            case 2286: if (ok256) return launch_nt16<6, 0, false, 2>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 2, KL_GEN2_BUF>(a, st);  // 192 x 256, register-staged prefetch
-            case 2287: if (ok256 && a.K2 == 0) return launch_nt16<7, 0, false, 2>(a, st); else if (ok256) return launch_nt16<7>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 2, KL_GEN2_BUF>(a, st);  // 224 x 256, register-staged prefetch
-            case 70: if (ok256) return launch_nt<256, 256, 64, 2, 2, true, 1, KL_PIPE2>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 2, KL_GEN2_BUF>(a, st);  // 4 waves x (128 x 128), hand-placed pipeline
-            case 71: if (ok256) return launch_nt<256, 256, 64, 2, 2, true, 1, KL_PIPE3>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 2, KL_GEN2_BUF>(a, st);  // ... loads spread over 3 slices
-            case 72: if (ok256) return launch_nt<256, 256, 64, 2, 4, true, 1, KL_PIPE2>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 2, KL_GEN2_BUF>(a, st);  // the same pipeline, 8 waves x (128 x 64)
-            case 44: return launch_nt<128, 128, 64, 2, 2, true, 1, KL_GEN2_BUF>(a, st);  // 128 x 128 tiles (few rows)
-            case 47: if (ok256) return launch_nt<256, 256, 64, 2, 4, true, 1, KL_GEN2_BUF>(a, st); else return launch_nt<192, 128, 64, 2, 2, true, 2, KL_GEN2_BUF>(a, st);  // 8 waves x (128 x 64); (ok256, not N % 256 alone: a 256-wide tile must not straddle a 128-wide column group)
-            default: return launch_nt<192, 128, 64, 2, 2, true, 2, KL_GEN2_BUF>(a, st);  // 42: 192 x 128, 2 workgroups per CU
-        }
-    }
+    return route(NT_TILE, variant, row.bm, row.bn, ok256);
+}
+
+// the narrow kernels: the dynamic-LDS limit raised once per kernel, the launch, its error check
+template <void (*KERNEL)(GemmNtArgs), int THREADS, int SMEM>
+static int launch_skinny(const GemmNtArgs& a, dim3 grid, hipStream_t st) {
+    ProfScope prof(PROF_GEMM_SKINNY, 2.0 * a.M * a.N * (double)a.K, st);
+    static const bool attr_ok = SMEM <= 65536 || hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM) == hipSuccess;
+    if (!attr_ok) return set_error(FTMI_ERR_LAUNCH, "gemm_nt: cannot raise the dynamic LDS limit");
+    hipLaunchKernelGGL(KERNEL, grid, dim3(THREADS), SMEM, st, a);
+    return check_launch("gemm_nt_skinny");
+}
+
+int gemm_nt(const GemmNtArgs& a, hipStream_t st) {
+    const NtRoute r = nt_route(a);
+    if (r.rc) return r.rc;
+    switch (r.kind) {
+        case NT_EMPTY: return 0;
+        case NT_TILE: return nt_variant_row(r.variant).launch(a, st);
+        case NT_TILE_128x64: return launch_nt<128, 64, 64, 2, 2, true, 1, KL_GEN2_BUF>(a, st);
+        case NT_SKINNY_RING: return launch_skinny<gemm_nt_skinny2_kernel<0>, 256, 4 * 3 * 12288>(a, dim3(((a.M + 31) / 32) * (a.N / 64)), st);
+        case NT_SKINNY_GATHER4: return launch_skinny<gemm_nt_skinny_kernel<4>, 256, 0>(a, dim3(((a.M + 31) / 32) * (a.N / 64)), st);
+        case NT_SKINNY_GATHER8: return launch_skinny<gemm_nt_skinny_kernel<8>, 512, 0>(a, dim3(((a.M + 31) / 32) * (a.N / 64)), st);
+        case NT_SPLIT64_K64: return launch_skinny<gemm_nt_skinny4_kernel<64>, 256, 4 * 2 * 16384>(a, dim3(8 * (a.N / 64), ((a.M + 63) / 64 + 7) / 8), st);
+        case NT_SPLIT64_K32: return launch_skinny<gemm_nt_skinny4_kernel<32>, 256, 4 * 2 * 16384>(a, dim3(8 * (a.N / 64), ((a.M + 63) / 64 + 7) / 8), st);
+#ifdef FTMI_EXPERIMENTAL
+        case NT_STREAMK: return gemm_nt_sk(a, st);
+        case NT_SKINNY3: return gemm_nt_skinny3(a, st);
 #endif
-    return launch_nt<128, 64, 64, 2, 2, true, 1, KL_GEN2_BUF>(a, st);  // N % 128 != 0
+        default: return set_error(FTMI_ERR_UNSUPPORTED, "gemm_nt: no kernel for this route");
+    }
 }
 
 #ifdef FTMI_EXPERIMENTAL
@@ -2567,15 +2549,14 @@ static int launch_fused(const GemmNtArgs& g0, const GemmNtArgs& d, int* flags, i
 int gemm_nt_lora_fused(const GemmNtArgs& g, const GemmNtArgs& d, int* flags, int* expect, hipStream_t st) {
     static const EnvSwitch fuse_sw("FTMI_FUSE_DOWN", 0);  // (read once; ftmi_reload_switches() lets one process compare the fused launch with the two launches)
     const int fuse = fuse_sw.get();
-    auto g256 = [](int x) { return x <= 0 || x % 256 == 0; };
-    const bool ok256 = g.N % 256 == 0 && g256(g.w_grp_n) && g256(g.w2_grp_n) && g256(g.xk_grp_n) && g256(g.x2_grp_n);
-    bool ok = fuse && flags && expect && g.K2 > 0 && g.K >= 128 && g.K % 64 == 0 && g.K2 % 64 == 0 && ok256 && g.M >= 1024 && g.variant == 8 && g.M == d.M &&
-              // the down-projection must be one the 64-row kernel takes (gemm_nt(): split mode, >= 84 tiles) and must write exactly the GEMM's X2
+    const NtRoute gr = fuse && g.variant == 8 ? nt_route(g) : NtRoute();  // the GEMM's own route: the fused kernel exists for its 16 x 16 x 32 tiles only
+    bool ok = fuse && flags && expect && g.K2 > 0 && g.K >= 128 && g.K % 64 == 0 && g.K2 % 64 == 0 && gr.kind == NT_TILE && gr.ok256 && g.M >= 1024 && g.variant == 8 && g.M == d.M &&
+              // the down-projection must be one the 64-row kernel takes (nt_route(): split mode, >= 84 tiles) and must write exactly the GEMM's X2
               d.split_r > 0 && d.K2 == 0 && d.epi == EPI_STORE && !d.bias && d.K >= 256 && d.K % 64 == 0 && d.split_r % 64 == 0 && (d.N / 2) % d.split_r == 0 &&
               (long)((d.M + 63) / 64) * (d.N / 64) >= 84 && (d.w_grp_n % 64) == 0 && (d.xk_grp_n % 64) == 0 && (const void*)d.out == (const void*)g.X2;
     int variant = 0;
     if (ok) {
-        variant = nt_auto_variant(g, ok256);
+        variant = gr.variant;
         // FTMI_FUSE_DOWN bit 0: the launches that run the 16 x 16 x 32 pipeline anyway (several rounds of tiles or a long K); bit 1: also the single-round short-K
         // launches (N = K = 2048), which move from the 192 x 128 two-per-CU kernel to 192 x 256 tiles for it
         if (variant == 42 && (fuse & 2)) variant = 86;
@@ -2617,18 +2598,17 @@ int gemm_nt_lora_fused(const GemmNtArgs& g, const GemmNtArgs& d, int*, int*, hip
 int gemm_fused_status() { return 0; }
 #endif
 
-// Which kernel the automatic choice takes for a plain [M, K] x [N, K]^T launch with an optional K-extension and epilogue (no groups): the variant numbers of
-// gemm_nt()'s switch -- 80 / 86 / 87 = gemm_nt16_kernel with 256- / 192- / 224-row tiles, 42 = 192 x 128 (two workgroups per CU), 47 = 256 x 256 (8 waves), 44 = 128 x 128,
-// 1 = the 128 x 64 kernel for N % 128 != 0, 0 = a launch the tiled kernels do not take (N % 64, K % 64).  No launch, no device: host tests pin the rule.
+// Which kernel the automatic choice takes for a plain [M, K] x [N, K]^T launch with an optional K-extension and epilogue (no groups), read off nt_route(): the
+// resolved variant of nt_variant_row() -- 80 / 86 / 87 = gemm_nt16_kernel with 256- / 192- / 224-row tiles, 42 = 192 x 128 (two workgroups per CU), 47 = 256 x 256 (8 waves),
+// 44 = 128 x 128 -- or 2 = a skinny kernel, 1 = the 128 x 64 kernel for N % 128 != 0, 0 = a launch gemm_nt() refuses (N % 64, K % 64) or an empty one.  It is what the
+// launcher does, so with an FTMI_* switch set (FTMI_NT_FORCE, FTMI_SKINNY_KS, ...) it reports the switched route.  No launch, no device: host tests pin the rule.
 int gemm_nt_plan(int M, int N, int K, int K2, int epi) {
-    if (M <= 0 || N <= 0 || K % 64 != 0 || K2 % 64 != 0 || N % 64 != 0) return 0;
-    // gemm_nt() routes narrow plain-store launches of many rows to the LDS-ring skinny kernel BEFORE any tile choice (the predicate below is the one in
-    // gemm_nt(), for ungrouped operands): report it with its own code instead of the tile the shape would otherwise get
-    if (N <= 256 && K2 == 0 && epi == EPI_STORE && M >= 512) return 2;
-    if (N % 128 != 0) return 1;
     GemmNtArgs a;
     a.M = M; a.N = N; a.K = K; a.K2 = K2; a.epi = epi; a.variant = 8;
-    return nt_auto_variant(a, N % 256 == 0);
+    a.ldx = a.ldw = K; a.ldx2 = a.ldw2 = K2; a.ldo = N;
+    const NtRoute r = nt_route(a);
+    if (r.rc || r.kind == NT_EMPTY) return 0;
+    return r.kind == NT_TILE_128x64 ? 1 : r.kind == NT_TILE ? r.variant : r.kind == NT_STREAMK ? 60 : 2;
 }
 
 // ------------------------------------------------------------------------------------------------

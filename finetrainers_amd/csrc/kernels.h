@@ -132,7 +132,18 @@ int gemm_nt(const GemmNtArgs& a, hipStream_t st);
 // Falls back to the two launches (down-projection, then GEMM) wherever the pair is not eligible or FTMI_FUSE_DOWN=0.
 int gemm_nt_lora_fused(const GemmNtArgs& gemm, const GemmNtArgs& down, int* flags, int* expect, hipStream_t st);
 int gemm_fused_status();  // 1 if a poll inside a fused launch ever gave up (synchronises the device: tests only)
-int gemm_nt_plan(int M, int N, int K, int K2, int epi);  // the automatic kernel choice as a pure host function (tests)
+// Which kernel gemm_nt() runs for a launch description, as a pure host function (no device, no launch): the launcher itself goes through it.
+// kind: the kernel family (the values are part of ftmi_gemm_nt_route's contract); variant: the resolved row of the variant table in gemm.hip, after
+// every fall-back (0 outside the table); bm x bn: the tile that runs; ok256: 256-wide column tiles are allowed (N and every column group).
+enum NtKind { NT_EMPTY = 0, NT_TILE = 1, NT_TILE_128x64 = 2, NT_SKINNY_RING = 3, NT_SKINNY_GATHER4 = 4, NT_SKINNY_GATHER8 = 5, NT_SPLIT64_K64 = 6, NT_SPLIT64_K32 = 7,
+              NT_STREAMK = 8, NT_SKINNY3 = 9 };
+struct NtRoute {
+    int rc = 0;  // != 0: refused, the error message is set
+    int kind = NT_EMPTY, variant = 0, bm = 0, bn = 0;
+    bool ok256 = false;
+};
+NtRoute nt_route(const GemmNtArgs& a);
+int gemm_nt_plan(int M, int N, int K, int K2, int epi);  // nt_route() of a plain automatic launch as one code (tests)
 // persistent 256 x 256 stream-K form of the same contract (gemm_sk.hip); gemm_nt() routes eligible launches to it
 bool gemm_nt_sk_eligible(const GemmNtArgs& a);
 int gemm_nt_sk(const GemmNtArgs& a, hipStream_t st);

@@ -123,15 +123,11 @@ def _ld(t: Optional[torch.Tensor], name: str) -> int:
     return t.stride(0)
 
 
-def gemm_nt_ex(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, M: int, N: int, K: int, bias=None, alpha: float = 1.0, epilogue: int = 0, out2=None,
-               resid=None, gate=None, gate_bstride: Optional[int] = None, rows_per_batch: int = 0, gate2=None, gate2_bstride: Optional[int] = None, aux=None,
-               x2=None, w2=None, K2: int = 0, xk_grp_n: int = 0, xk_grp_stride: int = 0, w_grp_n: int = 0, w_grp_stride: int = 0, w2_grp_n: int = 0,
-               w2_grp_stride: int = 0, x2_grp_n: int = 0, x2_grp_stride: int = 0, split_r: int = 0, variant: int = 8, _override: Optional[dict] = None) -> None:
-    """The NT GEMM with its full launch description (ftmi_gemm_nt_ex; the contract is stated in include/ftmi355.h).  Tensors are 2-D bf16 views with contiguous
-    columns whose row strides become ldx / ldw / ldo / ...; M, N, K (and the group fields) say which part of them the launch uses.  gate / gate2 are
-    [samples, >= N] views (their row stride is the sample stride unless given).  ``_override``: test hook -- raw values written over fields of the descriptor by name after it has been filled (the refusal tests pass misaligned leading dimensions)."""
-    for n, t in (("x", x), ("w", w), ("out", out)):
-        require_gpu_tensor(t, n, bf16)
+def _gemm_nt_args(x, w, out, *, M: int, N: int, K: int, bias=None, alpha: float = 1.0, epilogue: int = 0, out2=None,
+                  resid=None, gate=None, gate_bstride: Optional[int] = None, rows_per_batch: int = 0, gate2=None, gate2_bstride: Optional[int] = None, aux=None,
+                  x2=None, w2=None, K2: int = 0, xk_grp_n: int = 0, xk_grp_stride: int = 0, w_grp_n: int = 0, w_grp_stride: int = 0, w2_grp_n: int = 0,
+                  w2_grp_stride: int = 0, x2_grp_n: int = 0, x2_grp_stride: int = 0, split_r: int = 0, variant: int = 8, _override: Optional[dict] = None):
+    """The ftmi_gemm_nt_args block of gemm_nt_ex / gemm_nt_route."""
     a = _lib.GemmNtArgs()
     a.x, a.ldx, a.w, a.ldw, a.M, a.N, a.K = ptr(x), _ld(x, "x"), ptr(w), _ld(w, "w"), M, N, K
     a.xk_grp_n, a.xk_grp_stride, a.w_grp_n, a.w_grp_stride, a.w2_grp_n, a.w2_grp_stride = xk_grp_n, xk_grp_stride, w_grp_n, w_grp_stride, w2_grp_n, w2_grp_stride
@@ -143,7 +139,30 @@ def gemm_nt_ex(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, M: int, N
     a.rows_per_batch, a.epilogue, a.variant, a.split_r = rows_per_batch, epilogue, variant, split_r
     for k_, v_ in (_override or {}).items():
         setattr(a, k_, v_)
-    check(_lib.load().ftmi_gemm_nt_ex(ctypes.byref(a), stream_ptr()), "ftmi_gemm_nt_ex")
+    return a
+
+
+def gemm_nt_ex(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor, **desc) -> None:
+    """The NT GEMM with its full launch description (ftmi_gemm_nt_ex; the contract is stated in include/ftmi355.h).  Tensors are 2-D bf16 views with contiguous
+    columns whose row strides become ldx / ldw / ldo / ...; the keywords (those of _gemm_nt_args: M, N, K required) say which part of them the launch uses and
+    name the other operands.  gate / gate2 are [samples, >= N] views (their row stride is the sample stride unless given).  ``_override``: test hook -- raw values written over fields of the descriptor by name after it has been filled (the refusal tests pass misaligned leading dimensions)."""
+    for n, t in (("x", x), ("w", w), ("out", out)):
+        require_gpu_tensor(t, n, bf16)
+    check(_lib.load().ftmi_gemm_nt_ex(ctypes.byref(_gemm_nt_args(x, w, out, **desc)), stream_ptr()), "ftmi_gemm_nt_ex")
+
+
+def gemm_nt_route(**desc):
+    """What gemm_nt_ex would run for the same description (ftmi_gemm_nt_route: host only -- nothing is launched, no tensor is read, no GPU is needed).  The
+    keywords of gemm_nt_ex without the tensors; leading dimensions by name (ldx, ldw, ldo, ldx2, ldw2; default: the dense K, K, N, K2, K2).
+    Returns (kind, variant, tile_rows, tile_cols) as include/ftmi355.h states them; a refusal raises like gemm_nt_ex."""
+    ld = {"ldx": desc["K"], "ldw": desc["K"], "ldo": desc["N"], "ldx2": desc.get("K2", 0), "ldw2": desc.get("K2", 0)}
+    ld.update({k_: desc.pop(k_) for k_ in list(ld) if k_ in desc})
+    a = _gemm_nt_args(None, None, None, **desc)
+    for k_, v_ in ld.items():
+        setattr(a, k_, v_)
+    route = (ctypes.c_int * 4)()
+    check(_lib.load().ftmi_gemm_nt_route(ctypes.byref(a), route), "ftmi_gemm_nt_route")
+    return tuple(route)
 
 
 def gemm_tn_ex(u: torch.Tensor, v: torch.Tensor, c: torch.Tensor, *, M: int, P: int, Q: int, scale: float = 1.0, u_grp_p: int = 0, u_grp_stride: int = 0,

@@ -115,7 +115,8 @@ int ftmi_gemm_nt(int M, int N, int K, const void* x, long ldx, const void* w, lo
 /* Which kernel variant 8 takes for a plain launch of this shape (K2 = depth of a fused LoRA K-extension or 0; epilogue as above), as a pure host function
  * (no device, no launch): 80 / 86 / 87 = the 16 x 16 x 32 pipeline with 256- / 192- / 224-row tiles (1386 = 192-row tiles with the W operand on a three-slot direct-to-LDS ring: the default of the 192-row launches; 2286 = 192-row tiles with the register-staged operand prefetch, FTMI_NT16_W3=0), 42 = 192 x 128 tiles (two workgroups per CU), 47 = 256 x 256
  * (8 waves), 44 = 128 x 128, 2 = a skinny kernel (N <= 256, plain store, no extension, M >= 512: the LDS-ring kernel when K % 256 == 0, else the direct-gather one), 1 = the 128 x 64 kernel of N % 128 != 0,
- * 0 = not a tiled launch (N % 64 or K % 64).  Host tests pin the choice to DESIGN.md. */
+ * 0 = not a tiled launch (N % 64 or K % 64).  It is the launcher's own routing function applied to the plain launch (ftmi_gemm_nt_route below, for any launch): with an
+ * FTMI_* switch set it reports what the launcher then does.  Host tests pin the choice to DESIGN.md. */
 int ftmi_gemm_nt_plan(int M, int N, int K, int K2, int epilogue);
 /* ---- in-library gradient exchange (replaces what replicate(model, bucket_cap_mb=100) does for the LoRA gradients: finetrainers/parallel/ptd.py:462-463) ----
  * One process per GPU; the collectives are RCCL's (xGMI inside a node), looked up with dlopen at the first call -- libftmi355.so has no link-time dependency on
@@ -209,6 +210,13 @@ typedef struct ftmi_gemm_nt_args {
     int split_r;
 } ftmi_gemm_nt_args;
 int ftmi_gemm_nt_ex(const ftmi_gemm_nt_args* args, ftmi_stream stream);
+/* What ftmi_gemm_nt_ex would run for this launch description, as a pure host function (no device, no launch; the tensor pointers are not read): the launcher
+ * itself takes its decision from the same function, FTMI_* switches included.  route[0] = the kernel family: 0 nothing to do (M or N <= 0), 1 a tiled kernel of
+ * the variant table, 2 the 128 x 64 tiled kernel (N or a column group no multiple of 128), 3 the LDS-ring skinny kernel, 4 / 5 the direct-gather skinny kernel with
+ * a 4- / 8-way K split, 6 / 7 the 64-row split (hi, lo) kernel with 64- / 32-deep stages, 8 stream-K and 9 the 64 x 128 skinny kernel (research builds);
+ * route[1] = the variant that runs after every fall-back (family 1; 0 otherwise); route[2] x route[3] = rows x columns of the output tile of one workgroup.
+ * Returns 0, or the launcher's refusal (FTMI_ERR_UNSUPPORTED / FTMI_ERR_INVALID) with route[0] = 0. */
+int ftmi_gemm_nt_route(const ftmi_gemm_nt_args* args, int route[4]);
 typedef struct ftmi_gemm_tn_args {
     const void* u; long ldu;
     const void* v; long ldv;

@@ -33,7 +33,7 @@ BOUNDS, per element, u = 2^-24, ulp(a) = the bf16 spacing at |a| (2^(floor(log2 
 
 CPU SELF-CHECKS (unmarked tests at the end): the fp32 stand-ins (torch matmul; K in 64-chunks last to first, TN: eight partial sums) pass every bound with at
 most 0.2 % per block; every seeded fault is rejected; the automatic cases reach every kernel the product build can choose; the tails pair every pinned
-kernel with its own tile height.  (The production-size cases, M >= 1024 of TN and split mode and the automatic shapes, are not part of the CPU stand-in test:
+kernel with its own tile height; the library's own route (ftmi_gemm_nt_route, what gemm_nt() launches) has, for every case, the tile this file states.  (The production-size cases, M >= 1024 of TN and split mode and the automatic shapes, are not part of the CPU stand-in test:
 their fp64 products belong on the GPU; the epilogue and addressing code they run is the same.)
   seeded fault                                   stands for
   bias from column n - 64 in the 2nd column tile  column offset of bias / gate / resid / aux / out2 in a second column tile
@@ -47,7 +47,7 @@ their fp64 products belong on the GPU; the epilogue and addressing code they run
   batch 1 reads batch 0's V                       batch, u_bstride / v_bstride / c_bstride
   TN overwrites instead of adding                 the accumulate contract of C
 
-CASES -> KERNEL (gemm_nt(): split_r > 0 -> skinny2 / skinny4; N <= 256, plain store, M >= 512 -> skinny2 (K % 256 == 0) or skinny<4>; else by variant):
+CASES -> KERNEL (nt_route() of csrc/gemm.hip: split_r > 0 -> skinny2 / skinny4; N <= 256, plain store, M >= 512 -> skinny2 (K % 256 == 0) or skinny<4>; else by variant):
   tails      each of the 13 shipped variants at an N that is a multiple of its tile width (TILE below; on_own_kernel()), all 6 epilogue forms, M = h - 1, h + 1,
              2 h - 1, 2 h + 1 of ITS tile height h under two forms each, a short M (1 / 31 / 33) and a long one (449 / 1000); N over one, two and three column
              tiles, K over {64 .. 2112}, rows_per_batch over {1, 77, 150, M}, every stride padded                                        the pinned kernel (8: 128 x 128)
@@ -56,7 +56,7 @@ CASES -> KERNEL (gemm_nt(): split_r > 0 -> skinny2 / skinny4; N <= 256, plain st
   samples    M = 449 / 1000, rows_per_batch 77 / 128 / 150 (boundaries on and off a tile edge), gate and gate2, every variant              the pinned kernel
   ext        K2 in {64, 192, 384} x 6 epilogue forms with x2 / w2 groups                                                                     as above, EXT kernels
   groups     xk_grp_n = w_grp_n in {64, 128, 256} x variants {8, 44, 47, 70, 80, 1386}                                                       128 x 64 / 128-wide / pinned
-             (a variant that pins a 256-wide tile takes the 192 x 128 kernel over 128-wide groups: the product switch and, for 47, the research one)
+             (a variant that pins a 256-wide tile takes the 192 x 128 kernel over 128-wide groups: one rule of nt_route() for every row of the variant table)
   narrow     N <= 256, M >= 512, plain store                                                                                                 skinny2 / skinny<4>
   split      M in {1, 33, 300, 5400}, split_r in {64, 128}, grouped W, FTMI_SKINNY4 in {0, 1, 2}                                             skinny2 / skinny4<64> / <32>
   auto       the shapes of test_gemm_dispatch_rule_matches_the_design + M = 2688, 256, N = 1920, 192, all four epilogues, variant 8          80 / 87 / 1386 / 42 / 44 / 1 / 2
@@ -174,8 +174,9 @@ def nt_id(c):
 
 TAIL_MS = [1, 31, 33, 127, 129, 191, 193, 223, 225, 255, 257, 449, 1000]
 TAIL_KS = [64, 128, 192, 320, 2112]
-# rows x columns of the tile a PINNED variant runs at an ungrouped N that is a multiple of its tile width (product switch of gemm_nt(); variant 8 is the automatic
-# choice: 128 x 128 (44) at these small M).  Other wide N (N % 128 == 0) fall back to the 192 x 128 kernel, N % 128 != 0 takes the 128 x 64 kernel.
+# rows x columns of the tile a PINNED variant runs at an ungrouped N that is a multiple of its tile width (written against the variant table of csrc/gemm.hip and held
+# against the library by test_the_library_routes_every_case_as_the_table_states; variant 8 is the automatic choice: 128 x 128 (44) at these small M).  Other wide N
+# (N % 128 == 0) fall back to the 192 x 128 kernel, N % 128 != 0 takes the 128 x 64 kernel.
 TILE = {8: (128, 128), 42: (192, 128), 44: (128, 128), 47: (256, 256), 70: (256, 256), 72: (256, 256), 80: (256, 256), 86: (192, 256), 87: (224, 256),
         2286: (192, 256), 1386: (192, 256), 1387: (224, 256), 1380: (256, 256)}
 
@@ -1134,3 +1135,69 @@ def scan_for_47(lib):
                     if lib.ftmi_gemm_nt_plan(M, N, K, 0, epi) == 47:
                         return (M, N, K, 0, epi)
     return None
+
+
+SKINNY_KINDS = {3, 4, 5, 6, 7}  # include/ftmi355.h, ftmi_gemm_nt_route: LDS ring, direct gather x 4 / x 8, 64-row split kernel with 64- / 32-deep stages
+
+
+def stated_tile(c):
+    """What this file says the launch of case c runs: "skinny", or rows x columns of a tiled kernel.  For ungrouped cases this is TILE / on_own_kernel() and the two
+    fall-backs stated above TILE; column groups count like N (module docstring, groups: 128 x 64 / 128-wide / pinned)."""
+    if c["split_r"] or (c["N"] <= 256 and c["K2"] == 0 and c["form"] == "store" and c["M"] >= 512):
+        return "skinny"
+    fits = lambda wd: all(v % wd == 0 for v in (c["N"], c["xk_grp_n"], c["w_grp_n"], c["x2_grp_n"], c["w2_grp_n"]))
+    if not fits(128):
+        return (128, 64)
+    return TILE[c["variant"]] if fits(TILE[c["variant"]][1]) else (192, 128)
+
+
+def test_the_library_routes_every_case_as_the_table_states(lib, sw):
+    """ftmi_gemm_nt_route (host only; gemm_nt() launches what it returns) for EVERY case of NT_CASES, SPLIT_CASES and the automatic shapes: the tile is the one
+    TILE / on_own_kernel() state -- TILE[variant] on the variant's own kernel, 192 x 128 for other wide N, 128 x 64 for N % 128 != 0, a skinny kernel for the narrow
+    stores and split mode -- and the resolved variant is the pinned one, 42 after the fall-back.  The automatic shapes: the route is the plan's code, with TILE's tile."""
+    from finetrainers_amd import ops
+
+    def route(c):
+        inp_ld = {n: 8 * ((w + 15) // 8) for n, w in (("ldx", c["K"]), ("ldw", c["K"]), ("ldo", c["N"]), ("ldx2", c["K2"]), ("ldw2", c["K2"]))}  # padded, 16-byte rows
+        return ops.gemm_nt_route(M=c["M"], N=c["N"], K=c["K"], K2=c["K2"], epilogue=FORM_EPI[c["form"]], variant=c["variant"], split_r=c["split_r"],
+                                 xk_grp_n=c["xk_grp_n"], w_grp_n=c["w_grp_n"], x2_grp_n=c["x2_grp_n"], w2_grp_n=c["w2_grp_n"], **inp_ld)
+
+    own = set()
+    for c in NT_CASES:
+        kind, variant, bm, bn = route(c)
+        want = stated_tile(c)
+        if on_own_kernel(c):
+            assert want == TILE[c["variant"]], nt_id(c)
+            own.add(c["variant"])
+        if want == "skinny":
+            assert kind in SKINNY_KINDS and not on_own_kernel(c), (nt_id(c), kind)
+        else:
+            assert (bm, bn) == want, (nt_id(c), kind, variant, (bm, bn), want)
+            assert kind == (2 if want == (128, 64) else 1), (nt_id(c), kind)
+            if kind == 1:
+                assert variant == ((44 if c["variant"] == 8 else c["variant"]) if want == TILE[c["variant"]] else 42), (nt_id(c), variant)
+    assert own == set(SHIPPED_VARIANTS)
+    kinds = set()
+    for c in SPLIT_CASES:
+        sw("FTMI_SKINNY4", str(c["sk4"]))
+        kind, variant, bm, bn = route(c)
+        assert stated_tile(c) == "skinny" and kind in SKINNY_KINDS and bn == 64, (nt_id(c), kind)
+        assert (kind in (6, 7)) == (bm == 64) and (c["sk4"] != 0 or kind == 3), (nt_id(c), kind, bm)  # FTMI_SKINNY4=0: the 32-row LDS-ring kernel
+        kinds.add(kind)
+    assert kinds == {3, 6, 7}  # skinny2 / skinny4<64> / skinny4<32> (module docstring, split)
+    sw("FTMI_SKINNY4", "1")
+    reached = set()
+    for (M, N, K, K2) in AUTO_SHAPES:
+        for form in AUTO_FORMS:
+            kind, variant, bm, bn = route(nt_case(M, N, K, form, 8, K2=K2))
+            plan = lib.ftmi_gemm_nt_plan(M, N, K, K2, FORM_EPI[form])
+            reached.add(plan)
+            if plan == 2:
+                assert kind in SKINNY_KINDS, (M, N, K, K2, form, kind)
+            elif plan == 1:
+                assert (kind, bm, bn) == (2, 128, 64), (M, N, K, K2, form, kind, bm, bn)
+            else:
+                assert (kind, variant) == (1, plan) and (bm, bn) == TILE[plan], (M, N, K, K2, form, kind, variant, bm, bn)
+    assert AUTO_MUST_REACH <= reached
+    with pytest.raises(ValueError, match="multiples of 64"):
+        ops.gemm_nt_route(M=5376, N=2048, K=100)  # refused like the launch (test_gemm_nt_ex_refusals)

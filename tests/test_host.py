@@ -1073,6 +1073,37 @@ def test_gemm_dispatch_rule_matches_the_design(lib):
     assert plan(17776, 1920, 1920, 0, EPI_STORE) not in (80, 86, 87, 2286, 1386, 1387, 1380) and plan(17776, 7680, 1920, 0, EPI_GELU) in (80, 86, 87, 2286, 1386, 1387, 1380)
 
 
+def test_gemm_plan_is_the_recorded_one(lib):
+    """ftmi_gemm_nt_plan over a grid that reaches every branch of the routing (refusals, skinny, 128 x 64, every automatic tile choice, K-extensions, all four
+    epilogues), at the default switches, against tests/golden/gemm_nt_plan_grid.txt: the values the library returned BEFORE gemm_nt() and the plan were put on one
+    routing function (recorded from that library, never from the code under test)."""
+    import os
+
+    axes, rows = {}, []
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gemm_nt_plan_grid.txt")) as f:
+        for line in f:
+            if line.startswith("#"):
+                name, _, vals = line[1:].partition(":")
+                if name.strip() in ("M", "N", "K", "K2"):
+                    axes[name.strip()] = [int(v) for v in vals.split()]
+            else:
+                rows.append([int(v) for v in line.split()])
+    assert [len(axes[n]) for n in ("M", "N", "K", "K2")] == [11, 14, 6, 3] and len(rows) == 11 * 14 and all(len(r) == 6 * 3 * 4 for r in rows)
+    assert not [k for k in os.environ if k.startswith("FTMI_NT") or k.startswith("FTMI_SK")], "the grid is the plan at the default switches"
+    bad = []
+    for mi, M in enumerate(axes["M"]):
+        for ni, N in enumerate(axes["N"]):
+            want = iter(rows[mi * len(axes["N"]) + ni])
+            for K in axes["K"]:
+                for K2 in axes["K2"]:
+                    for epi in range(4):
+                        w, got = next(want), lib.ftmi_gemm_nt_plan(M, N, K, K2, epi)
+                        if got != w:
+                            bad.append(((M, N, K, K2, epi), w, got))
+    assert not bad, f"{len(bad)} of 11088 plans moved, first (shape, recorded, now): {bad[:5]}"
+    assert {v for r in rows for v in r} >= {0, 1, 2, 42, 44, 80, 87, 1386}  # the grid does reach every default route
+
+
 def test_parallel_backend_has_the_reference_surface():
     """N2: every method / property of BaseParallelBackend (finetrainers/parallel/base.py:9-115) exists on MI355XParallelBackend with the
     reference's signatures where the trainer passes arguments; degrees the path does not implement are refused at construction.  The lists are those of
