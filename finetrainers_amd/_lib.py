@@ -203,6 +203,11 @@ _SIGS = {
     "ftmi_ltx_backward_range": (c_int, [POINTER(LtxConfig), POINTER(LtxWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_size_t, c_int, c_int, c_int, c_void_p]),
     "ftmi_ltx_noise_pack": (c_int, [c_void_p] * 6 + [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "ftmi_ltx_cfg_euler_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_long, c_void_p]),
+    "ftmi_ltx_unpack_denorm": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "ftmi_ltx_sample_workspace_bytes": (c_size_t, [POINTER(LtxConfig), c_int]),
+    "ftmi_ltx_sample": (c_int, [POINTER(LtxConfig), POINTER(LtxWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float,
+                                c_void_p, c_size_t, c_void_p]),
     "ftmi_ddim_add_noise": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_long, c_void_p]),
     "ftmi_ddim_get_velocity": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_void_p]),
     "ftmi_posterior_sample": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_long, c_void_p]),

@@ -108,6 +108,10 @@ int ltx_forward(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const bf16_
                 const float* sigma, bf16_t* pred, void* ws, size_t ws_bytes, hipStream_t st);
 int ltx_backward_range(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const bf16_t* text, const float* key_bias, const bf16_t* dpred,
                        float* grad_a, float* grad_b, void* ws, size_t ws_bytes, int l_hi, int l_lo, int accumulate, hipStream_t st);
+size_t ltx_sample_workspace_bytes(const ftmi_ltx_config& c, int two_pass);
+int ltx_sample(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const bf16_t* text_cond, const bf16_t* text_uncond, const float* kbias_cond,
+               const float* kbias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, void* ws, size_t ws_bytes,
+               hipStream_t st);
 
 static int fill_attn(const ftmi_attn_desc* d, AttnArgs& a) {
     if (!d) return set_error(FTMI_ERR_INVALID, "attention: null descriptor");
@@ -432,6 +436,31 @@ int ftmi_ltx_backward(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, con
                       float* grad_a, float* grad_b, void* ws, size_t ws_bytes, ftmi_stream stream) {
     if (!cfg) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_backward: null argument");
     return ftmi_ltx_backward_range(cfg, w, text, key_bias, dpred, grad_a, grad_b, ws, ws_bytes, cfg->L, 0, /*accumulate=*/1, stream);
+}
+
+int ftmi_ltx_cfg_euler_step(const void* pred, float* x, const float* sigma, const float* sigma_next, float guidance, void* x_next_bf16, int B,
+                            long per_sample, ftmi_stream stream) {
+    if (!pred || !x || !sigma || !sigma_next || !x_next_bf16) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_cfg_euler_step: null argument");
+    return cfg_euler_step((const bf16_t*)pred, x, sigma, sigma_next, 1, guidance, (bf16_t*)x_next_bf16, B, per_sample, (hipStream_t)stream);
+}
+
+int ftmi_ltx_unpack_denorm(const float* x, const float* mean, const float* std_, void* latents, int B, int C, int S, ftmi_stream stream) {
+    if (!x || !mean || !std_ || !latents) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_unpack_denorm: null argument");
+    return unpack_denorm(x, mean, std_, (bf16_t*)latents, B, C, S, (hipStream_t)stream);
+}
+
+size_t ftmi_ltx_sample_workspace_bytes(const ftmi_ltx_config* cfg, int two_pass) { return cfg ? ltx_sample_workspace_bytes(*cfg, two_pass) : 0; }
+
+int ftmi_ltx_sample(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const void* text_cond, const void* text_uncond, const float* key_bias_cond,
+                    const float* key_bias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, void* ws,
+                    size_t ws_bytes, ftmi_stream stream) {
+    if (!cfg || !w || !text_cond || !x || !sigmas || !timesteps || !ws) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_sample: null argument");
+    if (guidance != 1.0f && !text_uncond) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_sample: guidance != 1 needs the unconditional prompt embeddings");
+    if (guidance != 1.0f && (key_bias_cond == nullptr) != (key_bias_uncond == nullptr))
+        return set_error(FTMI_ERR_INVALID, "ftmi_ltx_sample: give the key bias of both prompts or of neither");
+    if (cfg->r > 0 && (!w->lora_a_sp || !w->lora_b_ext)) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_sample: LoRA working copies missing");
+    return ltx_sample(*cfg, *w, (const bf16_t*)text_cond, (const bf16_t*)text_uncond, key_bias_cond, key_bias_uncond, x, sigmas, timesteps, n_steps,
+                      guidance, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int ftmi_ltx_noise_pack(const void* latents, const void* noise, const float* mean, const float* std_, const float* sigma,

@@ -243,6 +243,17 @@ int noise_pack(const bf16_t* latents, const bf16_t* noise, const float* mean, co
                const float* sigma_first, int first_frame_tokens, bf16_t* xt, bf16_t* target, int B, int C, int S,
                hipStream_t st);
 
+// ---- latent sampling (ltx_sample.hip) ----
+// one sampler step: v = u + g (c - u), x += (sigma_next - sigma) v in fp32, bf16 copy of the new x into both halves of xin ([2B, per_sample]; guidance == 1:
+// pred and xin are [B, per_sample]).  sigma / sigma_next element b at [b * sig_stride] (0: one value for every sample).  pred == nullptr: only the bf16
+// copies of x (the first model input); xin == nullptr: only the update (the last step)
+int cfg_euler_step(const bf16_t* pred, float* x, const float* sigma, const float* sigma_next, long sig_stride, float guidance, bf16_t* xin, int B,
+                   long per_sample, hipStream_t st);
+// x fp32 [B, S, C] -> latents bf16 [B, C, S] = x * std[c] + mean[c]
+int unpack_denorm(const float* x, const float* mean, const float* std_, bf16_t* out, int B, int C, int S, hipStream_t st);
+// dst[0..n) = src[0]  (n <= 64)
+int bcast_f32(const float* src, float* dst, int n, hipStream_t st);
+
 // loss (fp32 scalar, accumulated) and dpred
 int mse_loss_fwd_bwd(const bf16_t* pred, const bf16_t* target, const float* weight, float* loss, bf16_t* dpred, int B,
                      long per_sample, float grad_scale, float* partials, hipStream_t st);

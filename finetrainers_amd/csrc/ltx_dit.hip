@@ -316,29 +316,25 @@ static int ltx_block_forward(const ftmi_ltx_config& c, const ftmi_ltx_weights& w
     return 0;
 }
 
-int ltx_forward(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const bf16_t* x_t, const bf16_t* text, const float* key_bias,
-                const float* sigma, bf16_t* pred, void* ws, size_t ws_bytes, hipStream_t st) {
-    FTMI_TRY(check_cfg(c));
-    struct ValidWidth {  // (normalisations of a zero-padded narrow model take their mean over d_valid channels; reset when the pass has queued its launches)
-        explicit ValidWidth(int dv) { rowwise_set_valid_width(dv); }
-        ~ValidWidth() { rowwise_set_valid_width(0); }
-    } valid_width_guard(c.d_valid);
-    const WsLayout L = make_layout(c);
-    if (ws_bytes < L.total) return set_error(FTMI_ERR_INVALID, "ltx_forward: workspace too small");
-    const int M = c.B * c.S, Mt = c.B * c.T, D = c.D, r = c.r, V = c.gemm_variant;
-    const long D2 = (long)D * D;
-    const float s = c.lora_scale;
-
-    // ---- conditioning (one row per sample: every token of a sample shares its timestep) ----
+// The forward's prologue comes in two parts.  The TEXT part depends on the prompt and the adapters only: the caption projection and the text-side k|v
+// of every block with its LoRA extension and norm_k2 (kv2_all, k2n_all, xa_kv2_all).  The TIMESTEP part is the conditioning of one timestep (one row
+// per sample: every token of a sample shares its timestep).  A training step runs both (ltx_forward); the sampler runs the text part once per call and
+// the timestep part once per denoising step (ltx_sample).
+static int ltx_prologue_time(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const WsLayout& L, void* ws, const float* sigma, hipStream_t st) {
+    const int D = c.D;
     FTMI_TRY(timestep_sinusoid(sigma, W(ws, L.tsin), c.B, st));
     FTMI_TRY(small_linear(W(ws, L.tsin), P(w.time_l1_w, 0), P(w.time_l1_b, 0), W(ws, L.t1), c.B, D, 256, 0, 0, st));
     FTMI_TRY(small_linear(W(ws, L.t1), P(w.time_l2_w, 0), P(w.time_l2_b, 0), W(ws, L.emb), c.B, D, D, 1, 0, st));
     FTMI_TRY(small_linear(W(ws, L.emb), P(w.time_lin_w, 0), P(w.time_lin_b, 0), W(ws, L.temb), c.B, 6 * D, D, 1, 0, st));
     FTMI_TRY(ada_prep(P(w.tables, 0), W(ws, L.temb), W(ws, L.ada), c.L, c.B, D, st));
     FTMI_TRY(ada_out_prep(P(w.table_out, 0), W(ws, L.emb), W(ws, L.ada_out), c.B, D, st));
+    return 0;
+}
 
-    // ---- proj_in, caption projection ----
-    FTMI_TRY(linear(x_t, c.C_in, M, P(w.proj_in_w, 0), c.C_in, D, c.C_in, P(w.proj_in_b, 0), W(ws, L.hs), D, V, st));
+static int ltx_prologue_text(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const WsLayout& L, void* ws, const bf16_t* text, hipStream_t st) {
+    const int Mt = c.B * c.T, D = c.D, r = c.r, V = c.gemm_variant;
+    const float s = c.lora_scale;
+    // ---- caption projection ----
     {
         GemmNtArgs a;
         a.X = text; a.ldx = c.D_cap; a.W = P(w.cap_l1_w, 0); a.ldw = c.D_cap; a.M = Mt; a.N = D; a.K = c.D_cap;
@@ -367,7 +363,17 @@ int ltx_forward(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const bf16_
         FTMI_TRY(qknorm_rope_fwd(W(ws, L.kv2_all), 2 * D, P(w.norm_k2, 0), nullptr, nullptr, W(ws, L.k2n_all), D, Mt * c.L, Mt * c.L, D,
                                  c.eps_qk, st, c.L));
     }
+    return 0;
+}
 
+static int ltx_proj_in(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const WsLayout& L, void* ws, const bf16_t* x_t, hipStream_t st) {
+    return linear(x_t, c.C_in, c.B * c.S, P(w.proj_in_w, 0), c.C_in, c.D, c.C_in, P(w.proj_in_b, 0), W(ws, L.hs), c.D, c.gemm_variant, st);
+}
+
+// The block stack and the tail (LayerNorm + modulate + proj_out) over a prepared workspace: hs[0], the conditioning and the text-side k|v are in place.
+static int ltx_blocks_tail(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const WsLayout& L, void* ws, const float* key_bias, bf16_t* pred,
+                           hipStream_t st) {
+    const int M = c.B * c.S, D = c.D, V = c.gemm_variant;
     FuseCtx fx{reinterpret_cast<int*>(reinterpret_cast<char*>(ws) + L.sk_flags), 0};
     if (hipMemsetAsync(fx.flags, 0, 4096, st) != hipSuccess) return set_error(FTMI_ERR_LAUNCH, "ltx_forward: memset of the row-tile counters failed");
     for (int l = 0; l < c.L; ++l) FTMI_TRY(ltx_block_forward(c, w, L, ws, l, key_bias, st, fx));
@@ -377,6 +383,105 @@ int ltx_forward(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const bf16_
     const bf16_t* ao = W(ws, L.ada_out);
     FTMI_TRY(norm_modulate_fwd(hL, ao, ao + 2 * D, 3L * D, W(ws, L.s_ln), M, c.S, D, c.eps_norm, 1, st));
     FTMI_TRY(linear(W(ws, L.s_ln), D, M, P(w.proj_out_w, 0), D, c.C_out, D, P(w.proj_out_b, 0), pred, c.C_out, V, st));
+    return 0;
+}
+
+int ltx_forward(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const bf16_t* x_t, const bf16_t* text, const float* key_bias,
+                const float* sigma, bf16_t* pred, void* ws, size_t ws_bytes, hipStream_t st) {
+    FTMI_TRY(check_cfg(c));
+    struct ValidWidth {  // (normalisations of a zero-padded narrow model take their mean over d_valid channels; reset when the pass has queued its launches)
+        explicit ValidWidth(int dv) { rowwise_set_valid_width(dv); }
+        ~ValidWidth() { rowwise_set_valid_width(0); }
+    } valid_width_guard(c.d_valid);
+    const WsLayout L = make_layout(c);
+    if (ws_bytes < L.total) return set_error(FTMI_ERR_INVALID, "ltx_forward: workspace too small");
+    FTMI_TRY(ltx_prologue_time(c, w, L, ws, sigma, st));
+    FTMI_TRY(ltx_proj_in(c, w, L, ws, x_t, st));
+    FTMI_TRY(ltx_prologue_text(c, w, L, ws, text, st));
+    return ltx_blocks_tail(c, w, L, ws, key_bias, pred, st);
+}
+
+// ---- latent sampling: the whole denoising loop as one call, zero host syncs -------------------------------------------------------------------------
+// The model runs at batch nb = 2B (rows [0, B) unconditional, [B, 2B) conditional) or B (guidance == 1) over the checkpoint = 1 workspace layout -- one
+// block slot plus the residual stream, nothing kept for a backward -- followed by the sampler's own buffers.
+struct SampleLayout {
+    ftmi_ltx_config mc;  // the model's configuration: batch nb, checkpoint = 1
+    WsLayout L;
+    size_t xin, pred, text, kbias, tval, total;
+};
+static SampleLayout make_sample_layout(const ftmi_ltx_config& c, int two_pass) {
+    SampleLayout s;
+    s.mc = c;
+    s.mc.B = c.B * (two_pass ? 2 : 1);
+    s.mc.checkpoint = 1;
+    s.L = make_layout(s.mc);
+    Bump g;
+    g.off = s.L.total;
+    const size_t nb = (size_t)s.mc.B;
+    s.xin = g.take(nb * c.S * c.C_in * 2);
+    s.pred = g.take(nb * c.S * c.C_out * 2);
+    s.text = g.take(nb * c.T * c.D_cap * 2);
+    s.kbias = g.take(nb * c.T * 4);
+    s.tval = g.take(nb * 4);
+    s.total = g.off;
+    return s;
+}
+
+size_t ltx_sample_workspace_bytes(const ftmi_ltx_config& c, int two_pass) { return make_sample_layout(c, two_pass).total; }
+
+// FTMI_SAMPLE_HOIST=0 (read once; ftmi_reload_switches() re-reads it) repeats the text part of the prologue in every step, as a loop over ltx_forward
+// does: the A/B partner of the measurement in DESIGN.md section 7, same bits.
+int ltx_sample(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const bf16_t* text_cond, const bf16_t* text_uncond, const float* kbias_cond,
+               const float* kbias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, void* ws, size_t ws_bytes,
+               hipStream_t st) {
+    static const EnvSwitch hoist_sw("FTMI_SAMPLE_HOIST", 1);
+    const int hoist_text = hoist_sw.get();
+    const int two_pass = guidance != 1.0f;
+    if (n_steps <= 0) return set_error(FTMI_ERR_INVALID, "ltx_sample: no steps");
+    if (c.B <= 0 || c.B * (two_pass ? 2 : 1) > 8) return set_error(FTMI_ERR_UNSUPPORTED, "ltx_sample: at most 4 videos with guidance, 8 without (model batch <= 8)");
+    if (c.C_in != c.C_out) return set_error(FTMI_ERR_INVALID, "ltx_sample: the model's output is fed back as its input: C_in must equal C_out");
+    if (c.d_valid || c.head_dim_valid) return set_error(FTMI_ERR_UNSUPPORTED, "ltx_sample: narrow (zero-padded) geometries are not supported");
+    const SampleLayout sl = make_sample_layout(c, two_pass);
+    const ftmi_ltx_config& mc = sl.mc;
+    FTMI_TRY(check_cfg(mc));
+    if (ws_bytes < sl.total) return set_error(FTMI_ERR_INVALID, "ltx_sample: workspace too small");
+    const WsLayout& L = sl.L;
+    const int B = c.B, nb = mc.B;
+    const long per_sample = (long)c.S * c.C_in;
+    bf16_t* xin = W(ws, sl.xin);
+    bf16_t* pred = W(ws, sl.pred);
+    bf16_t* text = W(ws, sl.text);
+    float* tval = WF(ws, sl.tval);
+    const float* kbias = nullptr;
+
+    // rows [0, B) unconditional, [B, 2B) conditional: one text tensor / one bias tensor for the batched model call
+    const size_t tbytes = (size_t)B * c.T * c.D_cap * 2, kbytes = (size_t)B * c.T * 4;
+    bool ok = true;
+    if (two_pass) {
+        ok = ok && hipMemcpyAsync(text, text_uncond, tbytes, hipMemcpyDeviceToDevice, st) == hipSuccess;
+        ok = ok && hipMemcpyAsync(reinterpret_cast<char*>(text) + tbytes, text_cond, tbytes, hipMemcpyDeviceToDevice, st) == hipSuccess;
+        if (kbias_cond) {
+            float* kb = WF(ws, sl.kbias);
+            ok = ok && hipMemcpyAsync(kb, kbias_uncond, kbytes, hipMemcpyDeviceToDevice, st) == hipSuccess;
+            ok = ok && hipMemcpyAsync(kb + (size_t)B * c.T, kbias_cond, kbytes, hipMemcpyDeviceToDevice, st) == hipSuccess;
+            kbias = kb;
+        }
+    } else {
+        ok = ok && hipMemcpyAsync(text, text_cond, tbytes, hipMemcpyDeviceToDevice, st) == hipSuccess;
+        kbias = kbias_cond;
+    }
+    if (!ok) return set_error(FTMI_ERR_LAUNCH, "ltx_sample: copy of the prompt embeddings failed");
+
+    if (hoist_text) FTMI_TRY(ltx_prologue_text(mc, w, L, ws, text, st));
+    FTMI_TRY(cfg_euler_step(nullptr, x, nullptr, nullptr, 0, guidance, xin, B, per_sample, st));  // the first model input: bf16(x) in every half
+    for (int i = 0; i < n_steps; ++i) {
+        FTMI_TRY(bcast_f32(timesteps + i, tval, nb, st));
+        FTMI_TRY(ltx_prologue_time(mc, w, L, ws, tval, st));
+        FTMI_TRY(ltx_proj_in(mc, w, L, ws, xin, st));
+        if (!hoist_text) FTMI_TRY(ltx_prologue_text(mc, w, L, ws, text, st));
+        FTMI_TRY(ltx_blocks_tail(mc, w, L, ws, kbias, pred, st));
+        FTMI_TRY(cfg_euler_step(pred, x, sigmas + i, sigmas + i + 1, 0, guidance, i + 1 < n_steps ? xin : nullptr, B, per_sample, st));
+    }
     return 0;
 }
 

@@ -5,7 +5,8 @@ Mirrors the part of finetrainers' ``ModelSpecification`` interface the SFT step 
 base_specification.py:93-459): ``_resolution_dim_keys``, ``load_diffusion_models``, ``collate_conditions``,
 ``collate_latents`` and ``forward`` (same names, argument meaning and return convention).  Everything that
 feeds the step from outside the hot path (VAE / T5 loading, validation pipeline, saving) is out of scope for
-this backend and raises ``NotImplementedError`` -- the reference's own spec stays in charge of those.
+this backend and raises ``NotImplementedError`` -- the reference's own spec stays in charge of those.  ``validation_latents`` (an addition: the
+denoising loop of the validation pipeline in latent space, ``ltx_video/sampler.py``) is the exception.
 
 ``forward`` = base_specification.py:271-345: normalise latents, draw noise, flow-match mix (with the 10 %
 first-frame conditioning branch), pack, timesteps, DiT call, target.  Normalise + mix + pack + target run in one
@@ -212,6 +213,14 @@ class MI355XLTXVideoModelSpecification:
             return_dict=False,
         )[0]
         return pred, target, sigmas_bs1
+
+    def validation_latents(self, transformer: MI355XLTXVideoTransformer3DModel, scheduler_config: Optional[Dict[str, Any]] = None, **kwargs) -> torch.Tensor:
+        """The denoising loop of ``validation`` (base_specification.py:347-377) on the native kernels, in latent space: prompt embeddings in, denormalised
+        latents [B, C, F, H, W] out (``MI355XLTXLatentSampler.sample`` takes the keyword arguments).  Text encoding and the VAE decode are not here:
+        ``validation`` itself stays the reference's."""
+        from .sampler import MI355XLTXLatentSampler
+
+        return MI355XLTXLatentSampler(transformer, scheduler_config=scheduler_config).sample(**kwargs)
 
 
 # The public class: these overrides on top of the reference's own LTXVideoModelSpecification when finetrainers is importable (prepare_conditions,

@@ -299,6 +299,93 @@ def noise_pack(latents, noise, mean, std, sigma, sigma_first=None, first_frame_t
     return xt, target
 
 
+def ltx_cfg_euler_step(pred, x, sigma, sigma_next, guidance: float, x_next: Optional[torch.Tensor] = None):
+    """One sampler step (include/ftmi355.h: ftmi_ltx_cfg_euler_step).  ``pred`` bf16 [2B, ...] (unconditional rows first; ``guidance == 1``: [B, ...]),
+    ``x`` fp32 [B, ...] updated IN PLACE, ``sigma`` / ``sigma_next`` fp32 [B].  Returns the next model input: bf16(x) in both halves, shaped like ``pred``."""
+    require_gpu_tensor(pred, "pred", bf16)
+    require_gpu_tensor(x, "x", torch.float32)
+    require_gpu_tensor(sigma, "sigma", torch.float32)
+    require_gpu_tensor(sigma_next, "sigma_next", torch.float32)
+    if not (pred.is_contiguous() and x.is_contiguous() and sigma.is_contiguous() and sigma_next.is_contiguous()):
+        raise ValueError("ltx_cfg_euler_step: tensors must be contiguous (x is updated in place)")
+    B = x.shape[0]
+    halves = 1 if float(guidance) == 1.0 else 2
+    if pred.shape[0] != halves * B or tuple(pred.shape[1:]) != tuple(x.shape[1:]):
+        raise ValueError(f"ltx_cfg_euler_step: pred {tuple(pred.shape)} must be [{halves} x {B}, ...] over x {tuple(x.shape)}")
+    if sigma.numel() != B or sigma_next.numel() != B:
+        raise ValueError("ltx_cfg_euler_step: sigma / sigma_next hold one value per sample")
+    if x_next is None:
+        x_next = torch.empty_like(pred)
+    else:
+        require_gpu_tensor(x_next, "x_next", bf16)
+        if x_next.shape != pred.shape or not x_next.is_contiguous():
+            raise ValueError("ltx_cfg_euler_step: x_next must be a contiguous tensor shaped like pred")
+    check(_lib.load().ftmi_ltx_cfg_euler_step(ptr(pred), ptr(x), ptr(sigma), ptr(sigma_next), float(guidance), ptr(x_next), B, x[0].numel(), stream_ptr()),
+          "ftmi_ltx_cfg_euler_step")
+    return x_next
+
+
+def ltx_unpack_denorm(x, mean, std, num_frames: int, height: int, width: int):
+    """Inverse of ``noise_pack``'s normalise + pack: x fp32 [B, S, C] -> latents bf16 [B, C, F, H, W] = x * std[c] + mean[c]."""
+    require_gpu_tensor(x, "x", torch.float32)
+    require_gpu_tensor(mean, "mean", torch.float32)
+    require_gpu_tensor(std, "std", torch.float32)
+    B, S, C = x.shape
+    if S != num_frames * height * width:
+        raise ValueError(f"ltx_unpack_denorm: {S} tokens != num_frames * height * width = {num_frames * height * width}")
+    if mean.numel() != C or std.numel() != C:
+        raise ValueError("ltx_unpack_denorm: mean / std hold one value per channel")
+    x, mean, std = x.contiguous(), mean.contiguous(), std.contiguous()
+    out = torch.empty((B, C, num_frames, height, width), dtype=bf16, device=x.device)
+    check(_lib.load().ftmi_ltx_unpack_denorm(ptr(x), ptr(mean), ptr(std), ptr(out), B, C, S, stream_ptr()), "ftmi_ltx_unpack_denorm")
+    return out
+
+
+def ltx_sample_workspace_bytes(cfg, two_pass: bool) -> int:
+    return int(_lib.load().ftmi_ltx_sample_workspace_bytes(ctypes.byref(cfg), int(bool(two_pass))))
+
+
+def ltx_sample(cfg, weights, text_cond, text_uncond, key_bias_cond, key_bias_uncond, x, sigmas, timesteps, guidance: float, workspace=None):
+    """The whole denoising loop as one C call (include/ftmi355.h: ftmi_ltx_sample).  ``cfg`` / ``weights``: ``_lib.LtxConfig`` (B = videos) /
+    ``_lib.LtxWeights``; text_* bf16 [B, T, D_cap]; key_bias_* fp32 [B, T] or None; ``x`` fp32 [B, S, C] (noise in, latents out, IN PLACE);
+    ``sigmas`` fp32 [n + 1], ``timesteps`` fp32 [n] on the device.  Returns ``x``."""
+    two_pass = float(guidance) != 1.0
+    require_gpu_tensor(text_cond, "text_cond", bf16)
+    require_gpu_tensor(x, "x", torch.float32)
+    require_gpu_tensor(sigmas, "sigmas", torch.float32)
+    require_gpu_tensor(timesteps, "timesteps", torch.float32)
+    B, S, T = cfg.B, cfg.S, cfg.T
+    if tuple(x.shape) != (B, S, cfg.C_in) or not x.is_contiguous():
+        raise ValueError(f"ltx_sample: x must be a contiguous [{B}, {S}, {cfg.C_in}] tensor (it is updated in place), got {tuple(x.shape)}")
+    n = timesteps.numel()
+    if n < 1 or sigmas.numel() != n + 1 or not (sigmas.is_contiguous() and timesteps.is_contiguous()):
+        raise ValueError("ltx_sample: sigmas must hold one more value than timesteps")
+    texts = [("text_cond", text_cond)] + ([("text_uncond", text_uncond)] if two_pass else [])
+    for name, t in texts:
+        if t is None:
+            raise ValueError("ltx_sample: guidance != 1 needs the unconditional prompt embeddings")
+        require_gpu_tensor(t, name, bf16)
+        if tuple(t.shape) != (B, T, cfg.D_cap) or not t.is_contiguous():
+            raise ValueError(f"ltx_sample: {name} must be a contiguous [{B}, {T}, {cfg.D_cap}] tensor, got {tuple(t.shape)}")
+    biases = [("key_bias_cond", key_bias_cond)] + ([("key_bias_uncond", key_bias_uncond)] if two_pass else [])
+    if len({b is None for _, b in biases}) != 1:
+        raise ValueError("ltx_sample: give the key bias of both prompts or of neither")
+    for name, b in biases:
+        if b is not None:
+            require_gpu_tensor(b, name, torch.float32)
+            if tuple(b.shape) != (B, T) or not b.is_contiguous():
+                raise ValueError(f"ltx_sample: {name} must be a contiguous [{B}, {T}] tensor")
+    ws_bytes = ltx_sample_workspace_bytes(cfg, two_pass)
+    if workspace is None:
+        workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=x.device)
+    elif workspace.numel() < ws_bytes:
+        raise ValueError("ltx_sample: workspace too small")
+    check(_lib.load().ftmi_ltx_sample(ctypes.byref(cfg), ctypes.byref(weights), ptr(text_cond), ptr(text_uncond) if two_pass else None, ptr(key_bias_cond),
+                                       ptr(key_bias_uncond) if two_pass else None, ptr(x), ptr(sigmas), ptr(timesteps), n, float(guidance), ptr(workspace),
+                                       workspace.numel(), stream_ptr()), "ftmi_ltx_sample")
+    return x
+
+
 def ddim_add_noise(latents, noise, sqrt_alpha, sqrt_one_minus_alpha, scaling_factor: float = 1.0):
     """CogVideoX noising: (x0 = bf16(latents * scaling_factor), noisy = scheduler.add_noise(x0, noise, t)); per-sample coefficients fp32 [B]."""
     require_gpu_tensor(latents, "latents", bf16)

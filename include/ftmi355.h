@@ -16,6 +16,8 @@
  *                                        _patched_LTXVideoTransformer3D_forward (finetrainers/patches/models/
  *                                        ltx_video/patch.py:38-127) + loss.backward() through it
  *                                        (finetrainers/trainer/sft_trainer/trainer.py:481)
+ *   ftmi_ltx_sample (+ _cfg_euler_step, _unpack_denorm) the denoising loop of the validation pipeline, latents only
+ *                                        (finetrainers/models/ltx_video/base_specification.py:347-377)
  *   ftmi_ltx_noise_pack ................ normalise / noise / flow-match mix / pack / target of
  *                                        base_specification.py:295-320,343,427-459 + functional/diffusion.py:4-11
  *   ftmi_mse_loss ...................... trainer/sft_trainer/trainer.py:463-480 (+ d loss / d pred)
@@ -349,6 +351,40 @@ int ftmi_ltx_backward_range(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* 
 int ftmi_ltx_noise_pack(const void* latents, const void* noise, const float* mean, const float* std_, const float* sigma,
                         const float* sigma_first, int first_frame_tokens, void* x_t, void* target, int B, int C, int S,
                         ftmi_stream stream);
+
+/* ---- latent sampling (validation): the denoising loop around the forward above.  Replaces, up to the VAE decode, what the reference's validation runs
+ * per prompt: LTXPipeline.__call__ as driven by LTXVideoModelSpecification.validation (finetrainers/models/ltx_video/base_specification.py:347-377;
+ * [upstream] diffusers LTXPipeline + FlowMatchEulerDiscreteScheduler.step). ---- */
+
+/* One sampler step, one pass over memory.  pred bf16 [2B, per_sample]: rows [0, B) the unconditional, [B, 2B) the conditional prediction; guidance == 1:
+ * pred is [B, per_sample] and there is no unconditional half.  x fp32 [B, per_sample]: the sampler state, updated IN PLACE.  sigma, sigma_next fp32 [B]
+ * (device).  All in fp32, four roundings per element:   d = c - u;  v = fma(guidance, d, u);  dt = sigma_next - sigma;  x <- fma(dt, v, x)
+ * (guidance == 1: v = c).  x_next_bf16 [2B, per_sample] (guidance == 1: [B, per_sample]) receives the round-to-nearest-even bf16 copy of the new x in
+ * both halves: the next model input.  per_sample % 8 == 0; tensors 16-byte aligned. */
+int ftmi_ltx_cfg_euler_step(const void* pred, float* x, const float* sigma, const float* sigma_next, float guidance, void* x_next_bf16, int B,
+                            long per_sample, ftmi_stream stream);
+
+/* The inverse of ftmi_ltx_noise_pack's normalise + pack: x fp32 [B, S, C] -> latents bf16 [B, C, S] = x * std[c] + mean[c] (mean, std fp32 [C];
+ * the convention of _normalize_latents, base_specification.py:427-436, scaling factor 1).  C % 4 == 0. */
+int ftmi_ltx_unpack_denorm(const float* x, const float* mean, const float* std_, void* latents, int B, int C, int S, ftmi_stream stream);
+
+/* The whole denoising loop as ONE call with no host synchronisation.  cfg->B = number of videos; the model runs at batch 2 cfg->B (unconditional rows
+ * first) or, with guidance == 1, at batch cfg->B on the conditional prompt alone (text_uncond / key_bias_uncond may then be NULL).  cfg->checkpoint is
+ * ignored: nothing is kept for a backward, the workspace is the checkpoint = 1 layout (one block slot + the residual stream) at the model's batch plus
+ * the sampler's own buffers -- ftmi_ltx_sample_workspace_bytes(cfg, guidance != 1).
+ *   text_cond, text_uncond bf16 [B, T, D_cap]; key_bias_* fp32 [B, T] as for ftmi_ltx_forward (both NULL: no mask)
+ *   x fp32 [B, S, C_in]: the initial noise in packed token order on entry, the final normalised latents on return (ftmi_ltx_unpack_denorm turns them
+ *     into the VAE's input)
+ *   sigmas fp32 [n_steps + 1] (device), timesteps fp32 [n_steps] (device): step i feeds the model timesteps[i] for every sample and moves x from
+ *     sigmas[i] to sigmas[i + 1] with ftmi_ltx_cfg_euler_step.  The caller supplies both, so the timestep rounding convention is the caller's.
+ * What depends on the prompt and the adapters only -- the caption projection and the text-side k|v of every block with its LoRA extension and norm_k2
+ * -- runs once per call, not once per step; w->rope_cos / rope_sin are the caller's tables as for the forward.  The LoRA working copies in w are used
+ * as they are (refresh them after an optimiser step); cfg->r == 0 samples the base model.  The result is, bit for bit, that of a loop over
+ * ftmi_ltx_forward at batch 2B and ftmi_ltx_cfg_euler_step. */
+size_t ftmi_ltx_sample_workspace_bytes(const ftmi_ltx_config* cfg, int two_pass);
+int ftmi_ltx_sample(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const void* text_cond, const void* text_uncond, const float* key_bias_cond,
+                    const float* key_bias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, void* ws,
+                    size_t ws_bytes, ftmi_stream stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * CogVideoX spec level (first kernels of the next model family): the DDIM noising and the velocity -> x0 conversion of
