@@ -198,6 +198,9 @@ _SIGS = {
     "ftmi_ltx_workspace_offset": (c_int, [POINTER(LtxConfig), c_char_p, c_int, POINTER(c_size_t)]),
     "ftmi_ltx_forward": (c_int, [POINTER(LtxConfig), POINTER(LtxWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_size_t, c_void_p]),
+    "ftmi_ltx_forward_frames_workspace_bytes": (c_size_t, [POINTER(LtxConfig), c_int]),
+    "ftmi_ltx_forward_frames": (c_int, [POINTER(LtxConfig), POINTER(LtxWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                        c_size_t, c_void_p]),
     "ftmi_ltx_backward": (c_int, [POINTER(LtxConfig), POINTER(LtxWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_size_t, c_void_p]),
     "ftmi_ltx_backward_range": (c_int, [POINTER(LtxConfig), POINTER(LtxWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -208,6 +211,10 @@ _SIGS = {
     "ftmi_ltx_sample_workspace_bytes": (c_size_t, [POINTER(LtxConfig), c_int]),
     "ftmi_ltx_sample": (c_int, [POINTER(LtxConfig), POINTER(LtxWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float,
                                 c_void_p, c_size_t, c_void_p]),
+    "ftmi_ltx_cfg_euler_step_held": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_long, c_long, c_void_p]),
+    "ftmi_ltx_sample_cond_workspace_bytes": (c_size_t, [POINTER(LtxConfig), c_int, c_int]),
+    "ftmi_ltx_sample_cond": (c_int, [POINTER(LtxConfig), POINTER(LtxWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float,
+                                     c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "ftmi_ddim_add_noise": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_long, c_void_p]),
     "ftmi_ddim_get_velocity": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_void_p]),
     "ftmi_posterior_sample": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_long, c_void_p]),

@@ -108,7 +108,14 @@ int ltx_forward(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const bf16_
                 const float* sigma, bf16_t* pred, void* ws, size_t ws_bytes, hipStream_t st);
 int ltx_backward_range(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const bf16_t* text, const float* key_bias, const bf16_t* dpred,
                        float* grad_a, float* grad_b, void* ws, size_t ws_bytes, int l_hi, int l_lo, int accumulate, hipStream_t st);
+size_t ltx_forward_frames_workspace_bytes(const ftmi_ltx_config& c, int frames);
+int ltx_forward_frames(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const bf16_t* x_t, const bf16_t* text, const float* key_bias,
+                       const float* timesteps, int frames, bf16_t* pred, void* ws, size_t ws_bytes, hipStream_t st);
 size_t ltx_sample_workspace_bytes(const ftmi_ltx_config& c, int two_pass);
+size_t ltx_sample_cond_workspace_bytes(const ftmi_ltx_config& c, int two_pass, int frames);
+int ltx_sample_cond(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const bf16_t* text_cond, const bf16_t* text_uncond, const float* kbias_cond,
+                    const float* kbias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, int frames,
+                    int cond_frames, void* ws, size_t ws_bytes, hipStream_t st);
 int ltx_sample(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const bf16_t* text_cond, const bf16_t* text_uncond, const float* kbias_cond,
                const float* kbias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, void* ws, size_t ws_bytes,
                hipStream_t st);
@@ -423,6 +430,16 @@ int ftmi_ltx_forward(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, cons
     return ltx_forward(*cfg, *w, (const bf16_t*)x_t, (const bf16_t*)text, key_bias, sigma, (bf16_t*)pred, ws, ws_bytes, (hipStream_t)stream);
 }
 
+size_t ftmi_ltx_forward_frames_workspace_bytes(const ftmi_ltx_config* cfg, int frames) { return cfg ? ltx_forward_frames_workspace_bytes(*cfg, frames) : 0; }
+
+int ftmi_ltx_forward_frames(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const void* x_t, const void* text, const float* key_bias,
+                            const float* timesteps, int frames, void* pred, void* ws, size_t ws_bytes, ftmi_stream stream) {
+    if (!cfg || !w || !x_t || !text || !timesteps || !pred || !ws) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_forward_frames: null argument");
+    if (cfg->r > 0 && (!w->lora_a_sp || !w->lora_b_ext)) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_forward_frames: LoRA working copies missing");
+    return ltx_forward_frames(*cfg, *w, (const bf16_t*)x_t, (const bf16_t*)text, key_bias, timesteps, frames, (bf16_t*)pred, ws, ws_bytes,
+                              (hipStream_t)stream);
+}
+
 int ftmi_ltx_backward_range(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const void* text, const float* key_bias, const void* dpred,
                             float* grad_a, float* grad_b, void* ws, size_t ws_bytes, int l_hi, int l_lo, int accumulate, ftmi_stream stream) {
     if (!cfg || !w || !dpred || !ws) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_backward: null argument");
@@ -444,6 +461,12 @@ int ftmi_ltx_cfg_euler_step(const void* pred, float* x, const float* sigma, cons
     return cfg_euler_step((const bf16_t*)pred, x, sigma, sigma_next, 1, guidance, (bf16_t*)x_next_bf16, B, per_sample, (hipStream_t)stream);
 }
 
+int ftmi_ltx_cfg_euler_step_held(const void* pred, float* x, const float* sigma, const float* sigma_next, float guidance, void* x_next_bf16, int B,
+                                 long per_sample, long hold, ftmi_stream stream) {
+    if (!pred || !x || !sigma || !sigma_next || !x_next_bf16) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_cfg_euler_step_held: null argument");
+    return cfg_euler_step((const bf16_t*)pred, x, sigma, sigma_next, 1, guidance, (bf16_t*)x_next_bf16, B, per_sample, (hipStream_t)stream, hold);
+}
+
 int ftmi_ltx_unpack_denorm(const float* x, const float* mean, const float* std_, void* latents, int B, int C, int S, ftmi_stream stream) {
     if (!x || !mean || !std_ || !latents) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_unpack_denorm: null argument");
     return unpack_denorm(x, mean, std_, (bf16_t*)latents, B, C, S, (hipStream_t)stream);
@@ -461,6 +484,22 @@ int ftmi_ltx_sample(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const
     if (cfg->r > 0 && (!w->lora_a_sp || !w->lora_b_ext)) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_sample: LoRA working copies missing");
     return ltx_sample(*cfg, *w, (const bf16_t*)text_cond, (const bf16_t*)text_uncond, key_bias_cond, key_bias_uncond, x, sigmas, timesteps, n_steps,
                       guidance, ws, ws_bytes, (hipStream_t)stream);
+}
+
+size_t ftmi_ltx_sample_cond_workspace_bytes(const ftmi_ltx_config* cfg, int two_pass, int frames) {
+    return cfg ? ltx_sample_cond_workspace_bytes(*cfg, two_pass, frames) : 0;
+}
+
+int ftmi_ltx_sample_cond(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const void* text_cond, const void* text_uncond, const float* key_bias_cond,
+                         const float* key_bias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, int frames,
+                         int cond_frames, void* ws, size_t ws_bytes, ftmi_stream stream) {
+    if (!cfg || !w || !text_cond || !x || !sigmas || !timesteps || !ws) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_sample_cond: null argument");
+    if (guidance != 1.0f && !text_uncond) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_sample_cond: guidance != 1 needs the unconditional prompt embeddings");
+    if (guidance != 1.0f && (key_bias_cond == nullptr) != (key_bias_uncond == nullptr))
+        return set_error(FTMI_ERR_INVALID, "ftmi_ltx_sample_cond: give the key bias of both prompts or of neither");
+    if (cfg->r > 0 && (!w->lora_a_sp || !w->lora_b_ext)) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_sample_cond: LoRA working copies missing");
+    return ltx_sample_cond(*cfg, *w, (const bf16_t*)text_cond, (const bf16_t*)text_uncond, key_bias_cond, key_bias_uncond, x, sigmas, timesteps, n_steps,
+                           guidance, frames, cond_frames, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int ftmi_ltx_noise_pack(const void* latents, const void* noise, const float* mean, const float* std_, const float* sigma,

@@ -247,8 +247,13 @@ int noise_pack(const bf16_t* latents, const bf16_t* noise, const float* mean, co
 // one sampler step: v = u + g (c - u), x += (sigma_next - sigma) v in fp32, bf16 copy of the new x into both halves of xin ([2B, per_sample]; guidance == 1:
 // pred and xin are [B, per_sample]).  sigma / sigma_next element b at [b * sig_stride] (0: one value for every sample).  pred == nullptr: only the bf16
 // copies of x (the first model input); xin == nullptr: only the update (the last step)
+// hold > 0 (hold % 8 == 0): the first `hold` elements of every sample are held -- x untouched, pred not read, only the bf16 copy into xin
 int cfg_euler_step(const bf16_t* pred, float* x, const float* sigma, const float* sigma_next, long sig_stride, float guidance, bf16_t* xin, int B,
-                   long per_sample, hipStream_t st);
+                   long per_sample, hipStream_t st, long hold = 0);
+// per-frame conditioning of image-to-video sampling: out[g] = (g % F) < k ? 0 : t[0], g < G
+int frame_timesteps(const float* t, float* out, int G, int F, int k, hipStream_t st);
+// emb [G, D] / temb [G, 6D] <- row (g % F < k ? 0 : 1) of emb2 [2, D] / temb2 [2, 6D]
+int cond_rows_expand(const bf16_t* emb2, const bf16_t* temb2, bf16_t* emb, bf16_t* temb, int G, int F, int k, int D, hipStream_t st);
 // x fp32 [B, S, C] -> latents bf16 [B, C, S] = x * std[c] + mean[c]
 int unpack_denorm(const float* x, const float* mean, const float* std_, bf16_t* out, int B, int C, int S, hipStream_t st);
 // dst[0..n) = src[0]  (n <= 64)

@@ -41,17 +41,23 @@ struct Bump {
     }
 };
 
-WsLayout make_layout(const ftmi_ltx_config& c) {
+// A modulation group is a run of consecutive token rows that shares one timestep, i.e. one row of the conditioning tables: a whole sample in training and in
+// text-to-video sampling ({B, S}), one latent frame of a sample where the timestep differs per frame ({B F, S / F}: ltx_forward_frames, ltx_sample_cond).
+struct ModGroups { int n, rows; };
+constexpr int kMaxModGroups = 128;  // 8 model rows (the batch cap of the sampler) x 16 latent frames (a 121-frame clip)
+
+WsLayout make_layout(const ftmi_ltx_config& c, int groups = 0) {
     WsLayout w;
     const size_t M = (size_t)c.B * c.S, Mt = (size_t)c.B * c.T, D = c.D, r = c.r > 0 ? c.r : 64;
+    const size_t G = groups > 0 ? groups : c.B;  // rows of the conditioning tables
     const size_t e2 = 2;  // bf16
     Bump g;
-    w.tsin = g.take((size_t)c.B * 256 * e2);
-    w.t1 = g.take((size_t)c.B * D * e2);
-    w.emb = g.take((size_t)c.B * D * e2);
-    w.temb = g.take((size_t)c.B * 6 * D * e2);
-    w.ada = g.take((size_t)c.L * c.B * 8 * D * e2);
-    w.ada_out = g.take((size_t)c.B * 3 * D * e2);
+    w.tsin = g.take(G * 256 * e2);
+    w.t1 = g.take(G * D * e2);
+    w.emb = g.take(G * D * e2);
+    w.temb = g.take(G * 6 * D * e2);
+    w.ada = g.take((size_t)c.L * G * 8 * D * e2);
+    w.ada_out = g.take(G * 3 * D * e2);
     w.cap_h = g.take(Mt * D * e2);
     w.e = g.take(Mt * D * e2);
     w.hs = g.take((size_t)(c.L + 1) * M * D * e2);
@@ -109,10 +115,13 @@ WsLayout make_layout(const ftmi_ltx_config& c) {
     return w;
 }
 
-int check_cfg(const ftmi_ltx_config& c) {
+// frames > 0: the per-frame entries, whose timestep embedding runs in chunks of 8 rows -- the bound is on the modulation groups B x frames, not on B
+int check_cfg(const ftmi_ltx_config& c, int frames = 0) {
     if (c.B <= 0 || c.S <= 0 || c.T <= 0 || c.L <= 0) return set_error(FTMI_ERR_INVALID, "ltx: empty problem");
     if (c.D != 2048 || c.H * 64 != c.D) return set_error(FTMI_ERR_UNSUPPORTED, "ltx: kernels are built for width 2048 = 32 heads x 64");
-    if (c.B > 8) return set_error(FTMI_ERR_UNSUPPORTED, "ltx: per-rank batch must be <= 8 (timestep-embedding kernel)");
+    if (frames <= 0 && c.B > 8) return set_error(FTMI_ERR_UNSUPPORTED, "ltx: per-rank batch must be <= 8 (timestep-embedding kernel)");
+    if (frames > 0 && (c.S % frames != 0 || (long)c.B * frames > kMaxModGroups))
+        return set_error(FTMI_ERR_UNSUPPORTED, "ltx: per-frame timesteps need S % frames == 0 and batch x frames <= 128 (8 model rows x 16 latent frames)");
     if (c.r < 0 || (c.r % 64) != 0) return set_error(FTMI_ERR_UNSUPPORTED, "ltx: LoRA rank must be 0 or a multiple of 64");
     if ((c.C_in % 64) || (c.C_out % 64) || (c.D_ff % 128) || (c.D_cap % 64))
         return set_error(FTMI_ERR_UNSUPPORTED, "ltx: channel counts must be multiples of 64");
@@ -202,7 +211,8 @@ int ltx_workspace_offset(const ftmi_ltx_config& c, const char* name, int layer, 
 // One transformer block of the forward (steps 1-13 of patches/models/ltx_video/patch.py:82-123 + the upstream block): reads hs[l], writes hs[l+1] and the
 // block's activations into its slot.  Called by the forward for every block and -- under gradient checkpointing -- again by the backward right before a
 // block's gradient computation (deterministic kernels: the recomputed activations are the forward's, bit for bit).
-static int ltx_block_forward(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const WsLayout& L, void* ws, int l, const float* key_bias, hipStream_t st, FuseCtx& fx) {
+static int ltx_block_forward(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const WsLayout& L, void* ws, int l, const float* key_bias, hipStream_t st, FuseCtx& fx,
+                             const ModGroups& mg) {
     const int M = c.B * c.S, D = c.D, r = c.r, V = c.gemm_variant;
     const long D2 = (long)D * D;
     const float s = c.lora_scale;
@@ -210,7 +220,7 @@ static int ltx_block_forward(const ftmi_ltx_config& c, const ftmi_ltx_weights& w
         char* blk = reinterpret_cast<char*>(ws) + L.blk0 + L.blk_stride * l;
         const bf16_t* h0 = W(ws, L.hs) + (size_t)l * M * D;
         bf16_t* hout = W(ws, L.hs) + (size_t)(l + 1) * M * D;
-        const bf16_t* ada = W(ws, L.ada) + (size_t)l * c.B * 8 * D;  // [B][8][D]
+        const bf16_t* ada = W(ws, L.ada) + (size_t)l * mg.n * 8 * D;  // [groups][8][D]: one row per sample, or per latent frame of a sample
         const long ab = 8L * D;
         const bf16_t* la = w.lora_a_sp ? P(w.lora_a_sp, (size_t)l * 8 * 2 * r * D) : nullptr;   // [8][2r][D]  (hi, lo) planes of A
         const bf16_t* lb = w.lora_b_ext ? P(w.lora_b_ext, (size_t)l * 8 * D * 3 * r) : nullptr;  // [8][D][3r]  [B_hi | B_hi | B_lo]
@@ -218,7 +228,7 @@ static int ltx_block_forward(const ftmi_ltx_config& c, const ftmi_ltx_weights& w
         bf16_t* qkv = W(blk, L.qkv);
 
         // 1. norm1 + AdaLN modulate
-        FTMI_TRY(norm_modulate_fwd(h0, ada + 0 * D, ada + 6 * D, ab, n1, M, c.S, D, c.eps_norm, 0, st));
+        FTMI_TRY(norm_modulate_fwd(h0, ada + 0 * D, ada + 6 * D, ab, n1, M, mg.rows, D, c.eps_norm, 0, st));
         // 2-3. fused q,k,v projection (+ LoRA)
         {
             GemmNtArgs a;
@@ -249,7 +259,7 @@ static int ltx_block_forward(const ftmi_ltx_config& c, const ftmi_ltx_weights& w
             GemmNtArgs a;
             a.X = W(blk, L.o1); a.ldx = D; a.W = P(w.w_o, (size_t)l * D2); a.ldw = D; a.M = M; a.N = D; a.K = D;
             a.bias = P(w.b_o, (size_t)l * D); a.out = W(blk, L.h1); a.ldo = D; a.variant = V;
-            a.epi = EPI_RESID; a.resid = h0; a.ldr = D; a.gate = ada + 2 * D; a.gate_bstride = ab; a.rows_per_batch = c.S;
+            a.epi = EPI_RESID; a.resid = h0; a.ldr = D; a.gate = ada + 2 * D; a.gate_bstride = ab; a.rows_per_batch = mg.rows;
             GemmNtArgs dn;
             if (r > 0) {
                 dn = lora_down_args(W(blk, L.o1), D, M, la + 3L * 2 * r * D, r, D, r, s, W(blk, L.xa_o));
@@ -297,7 +307,7 @@ static int ltx_block_forward(const ftmi_ltx_config& c, const ftmi_ltx_weights& w
         }
         const bf16_t* h2 = W(blk, L.h2);
         // 11-13. norm2 + modulate, feed-forward, gate * residual
-        FTMI_TRY(norm_modulate_fwd(h2, ada + 3 * D, ada + 7 * D, ab, W(ws, L.s_n2), M, c.S, D, c.eps_norm, 0, st));
+        FTMI_TRY(norm_modulate_fwd(h2, ada + 3 * D, ada + 7 * D, ab, W(ws, L.s_n2), M, mg.rows, D, c.eps_norm, 0, st));
         {
             GemmNtArgs a;
             a.X = W(ws, L.s_n2); a.ldx = D; a.W = P(w.w_ff1, (size_t)l * c.D_ff * D); a.ldw = D; a.M = M; a.N = c.D_ff; a.K = D;
@@ -309,7 +319,7 @@ static int ltx_block_forward(const ftmi_ltx_config& c, const ftmi_ltx_weights& w
             GemmNtArgs a;
             a.X = W(ws, L.s_g); a.ldx = c.D_ff; a.W = P(w.w_ff2, (size_t)l * D * c.D_ff); a.ldw = c.D_ff; a.M = M; a.N = D; a.K = c.D_ff;
             a.bias = P(w.b_ff2, (size_t)l * D); a.out = hout; a.ldo = D; a.variant = V;
-            a.epi = EPI_RESID; a.resid = h2; a.ldr = D; a.gate = ada + 5 * D; a.gate_bstride = ab; a.rows_per_batch = c.S;
+            a.epi = EPI_RESID; a.resid = h2; a.ldr = D; a.gate = ada + 5 * D; a.gate_bstride = ab; a.rows_per_batch = mg.rows;
             FTMI_TRY(gemm_nt(a, st));
         }
     }
@@ -317,18 +327,31 @@ static int ltx_block_forward(const ftmi_ltx_config& c, const ftmi_ltx_weights& w
 }
 
 // The forward's prologue comes in two parts.  The TEXT part depends on the prompt and the adapters only: the caption projection and the text-side k|v
-// of every block with its LoRA extension and norm_k2 (kv2_all, k2n_all, xa_kv2_all).  The TIMESTEP part is the conditioning of one timestep (one row
-// per sample: every token of a sample shares its timestep).  A training step runs both (ltx_forward); the sampler runs the text part once per call and
-// the timestep part once per denoising step (ltx_sample).
-static int ltx_prologue_time(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const WsLayout& L, void* ws, const float* sigma, hipStream_t st) {
+// of every block with its LoRA extension and norm_k2 (kv2_all, k2n_all, xa_kv2_all).  The TIMESTEP part is the conditioning of `groups` timesteps, one
+// row per modulation group (one per sample where every token of a sample shares its timestep).  A training step runs both (ltx_forward); the sampler runs
+// the text part once per call and the timestep part once per denoising step (ltx_sample).
+// The embedding MLP (sinusoid, two linears, the 6D linear) is small_linear's: 1-8 rows per launch, every row computed on its own, so more than 8 groups run
+// in chunks of 8 and a row holds the bits it would hold in any other chunk (or alone).
+static int ltx_time_embed(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const WsLayout& L, void* ws, const float* tvals, int groups, bf16_t* emb,
+                          bf16_t* temb, hipStream_t st) {
     const int D = c.D;
-    FTMI_TRY(timestep_sinusoid(sigma, W(ws, L.tsin), c.B, st));
-    FTMI_TRY(small_linear(W(ws, L.tsin), P(w.time_l1_w, 0), P(w.time_l1_b, 0), W(ws, L.t1), c.B, D, 256, 0, 0, st));
-    FTMI_TRY(small_linear(W(ws, L.t1), P(w.time_l2_w, 0), P(w.time_l2_b, 0), W(ws, L.emb), c.B, D, D, 1, 0, st));
-    FTMI_TRY(small_linear(W(ws, L.emb), P(w.time_lin_w, 0), P(w.time_lin_b, 0), W(ws, L.temb), c.B, 6 * D, D, 1, 0, st));
-    FTMI_TRY(ada_prep(P(w.tables, 0), W(ws, L.temb), W(ws, L.ada), c.L, c.B, D, st));
-    FTMI_TRY(ada_out_prep(P(w.table_out, 0), W(ws, L.emb), W(ws, L.ada_out), c.B, D, st));
+    FTMI_TRY(timestep_sinusoid(tvals, W(ws, L.tsin), groups, st));
+    for (int g0 = 0; g0 < groups; g0 += 8) {
+        const int n = groups - g0 < 8 ? groups - g0 : 8;
+        FTMI_TRY(small_linear(W(ws, L.tsin) + (size_t)g0 * 256, P(w.time_l1_w, 0), P(w.time_l1_b, 0), W(ws, L.t1) + (size_t)g0 * D, n, D, 256, 0, 0, st));
+        FTMI_TRY(small_linear(W(ws, L.t1) + (size_t)g0 * D, P(w.time_l2_w, 0), P(w.time_l2_b, 0), emb + (size_t)g0 * D, n, D, D, 1, 0, st));
+        FTMI_TRY(small_linear(emb + (size_t)g0 * D, P(w.time_lin_w, 0), P(w.time_lin_b, 0), temb + (size_t)g0 * 6 * D, n, 6 * D, D, 1, 0, st));
+    }
     return 0;
+}
+static int ltx_ada_tables(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const WsLayout& L, void* ws, int groups, hipStream_t st) {
+    FTMI_TRY(ada_prep(P(w.tables, 0), W(ws, L.temb), W(ws, L.ada), c.L, groups, c.D, st));
+    FTMI_TRY(ada_out_prep(P(w.table_out, 0), W(ws, L.emb), W(ws, L.ada_out), groups, c.D, st));
+    return 0;
+}
+static int ltx_prologue_time(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const WsLayout& L, void* ws, const float* tvals, int groups, hipStream_t st) {
+    FTMI_TRY(ltx_time_embed(c, w, L, ws, tvals, groups, W(ws, L.emb), W(ws, L.temb), st));
+    return ltx_ada_tables(c, w, L, ws, groups, st);
 }
 
 static int ltx_prologue_text(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const WsLayout& L, void* ws, const bf16_t* text, hipStream_t st) {
@@ -372,16 +395,16 @@ static int ltx_proj_in(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, cons
 
 // The block stack and the tail (LayerNorm + modulate + proj_out) over a prepared workspace: hs[0], the conditioning and the text-side k|v are in place.
 static int ltx_blocks_tail(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const WsLayout& L, void* ws, const float* key_bias, bf16_t* pred,
-                           hipStream_t st) {
+                           hipStream_t st, const ModGroups& mg) {
     const int M = c.B * c.S, D = c.D, V = c.gemm_variant;
     FuseCtx fx{reinterpret_cast<int*>(reinterpret_cast<char*>(ws) + L.sk_flags), 0};
     if (hipMemsetAsync(fx.flags, 0, 4096, st) != hipSuccess) return set_error(FTMI_ERR_LAUNCH, "ltx_forward: memset of the row-tile counters failed");
-    for (int l = 0; l < c.L; ++l) FTMI_TRY(ltx_block_forward(c, w, L, ws, l, key_bias, st, fx));
+    for (int l = 0; l < c.L; ++l) FTMI_TRY(ltx_block_forward(c, w, L, ws, l, key_bias, st, fx, mg));
 
     // ---- tail: LayerNorm + modulate + proj_out ----
     const bf16_t* hL = W(ws, L.hs) + (size_t)c.L * M * D;
     const bf16_t* ao = W(ws, L.ada_out);
-    FTMI_TRY(norm_modulate_fwd(hL, ao, ao + 2 * D, 3L * D, W(ws, L.s_ln), M, c.S, D, c.eps_norm, 1, st));
+    FTMI_TRY(norm_modulate_fwd(hL, ao, ao + 2 * D, 3L * D, W(ws, L.s_ln), M, mg.rows, D, c.eps_norm, 1, st));
     FTMI_TRY(linear(W(ws, L.s_ln), D, M, P(w.proj_out_w, 0), D, c.C_out, D, P(w.proj_out_b, 0), pred, c.C_out, V, st));
     return 0;
 }
@@ -395,10 +418,38 @@ int ltx_forward(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const bf16_
     } valid_width_guard(c.d_valid);
     const WsLayout L = make_layout(c);
     if (ws_bytes < L.total) return set_error(FTMI_ERR_INVALID, "ltx_forward: workspace too small");
-    FTMI_TRY(ltx_prologue_time(c, w, L, ws, sigma, st));
+    FTMI_TRY(ltx_prologue_time(c, w, L, ws, sigma, c.B, st));
     FTMI_TRY(ltx_proj_in(c, w, L, ws, x_t, st));
     FTMI_TRY(ltx_prologue_text(c, w, L, ws, text, st));
-    return ltx_blocks_tail(c, w, L, ws, key_bias, pred, st);
+    return ltx_blocks_tail(c, w, L, ws, key_bias, pred, st, ModGroups{c.B, c.S});
+}
+
+// ---- forward with one timestep per latent frame (forward only) -----------------------------------------------------------------------------------
+// timesteps fp32 [B, frames]: tokens [f S / frames, (f + 1) S / frames) of sample b are modulated by the conditioning of timesteps[b][f].  The tables are
+// [L][B frames][8][D] / [B frames][3][D]; norm_modulate_fwd and the gated-residual GEMM epilogues pick row (token row) / (S / frames) of them -- every output
+// row by its own index, in every kernel nt_route() can choose (gemm_nt_kernel and nt16_body compute m / rows_per_batch per lane: there is no per-tile gate).
+// Attention, RoPE and the text side see the true batch.  Workspace: the checkpoint = 1 layout with the taller tables; nothing is kept for a backward.
+static ftmi_ltx_config frames_cfg(const ftmi_ltx_config& c) {
+    ftmi_ltx_config fc = c;
+    fc.checkpoint = 1;
+    return fc;
+}
+size_t ltx_forward_frames_workspace_bytes(const ftmi_ltx_config& c, int frames) {
+    return frames > 0 ? make_layout(frames_cfg(c), c.B * frames).total : 0;
+}
+int ltx_forward_frames(const ftmi_ltx_config& c0, const ftmi_ltx_weights& w, const bf16_t* x_t, const bf16_t* text, const float* key_bias,
+                       const float* timesteps, int frames, bf16_t* pred, void* ws, size_t ws_bytes, hipStream_t st) {
+    if (frames <= 0) return set_error(FTMI_ERR_INVALID, "ltx_forward_frames: frames must be positive");
+    if (c0.d_valid || c0.head_dim_valid) return set_error(FTMI_ERR_UNSUPPORTED, "ltx_forward_frames: narrow (zero-padded) geometries are not supported");
+    const ftmi_ltx_config c = frames_cfg(c0);
+    FTMI_TRY(check_cfg(c, frames));
+    const int G = c.B * frames;
+    const WsLayout L = make_layout(c, G);
+    if (ws_bytes < L.total) return set_error(FTMI_ERR_INVALID, "ltx_forward_frames: workspace too small");
+    FTMI_TRY(ltx_prologue_time(c, w, L, ws, timesteps, G, st));
+    FTMI_TRY(ltx_proj_in(c, w, L, ws, x_t, st));
+    FTMI_TRY(ltx_prologue_text(c, w, L, ws, text, st));
+    return ltx_blocks_tail(c, w, L, ws, key_bias, pred, st, ModGroups{G, c.S / frames});
 }
 
 // ---- latent sampling: the whole denoising loop as one call, zero host syncs -------------------------------------------------------------------------
@@ -408,13 +459,14 @@ struct SampleLayout {
     ftmi_ltx_config mc;  // the model's configuration: batch nb, checkpoint = 1
     WsLayout L;
     size_t xin, pred, text, kbias, tval, total;
+    size_t emb2, temb2;  // conditioned sampling (frames > 0): the embedding rows of the two distinct timesteps of a step, [2][D] and [2][6D] (row 0: timestep 0)
 };
-static SampleLayout make_sample_layout(const ftmi_ltx_config& c, int two_pass) {
+static SampleLayout make_sample_layout(const ftmi_ltx_config& c, int two_pass, int frames = 0) {
     SampleLayout s;
     s.mc = c;
     s.mc.B = c.B * (two_pass ? 2 : 1);
     s.mc.checkpoint = 1;
-    s.L = make_layout(s.mc);
+    s.L = make_layout(s.mc, frames > 0 ? s.mc.B * frames : 0);
     Bump g;
     g.off = s.L.total;
     const size_t nb = (size_t)s.mc.B;
@@ -422,32 +474,51 @@ static SampleLayout make_sample_layout(const ftmi_ltx_config& c, int two_pass) {
     s.pred = g.take(nb * c.S * c.C_out * 2);
     s.text = g.take(nb * c.T * c.D_cap * 2);
     s.kbias = g.take(nb * c.T * 4);
-    s.tval = g.take(nb * 4);
+    s.tval = g.take((frames > 0 ? nb * frames : nb) * 4);
+    s.emb2 = s.temb2 = 0;
+    if (frames > 0) {
+        s.emb2 = g.take(2 * (size_t)c.D * 2);
+        s.temb2 = g.take(2 * 6 * (size_t)c.D * 2);
+    }
     s.total = g.off;
     return s;
 }
 
 size_t ltx_sample_workspace_bytes(const ftmi_ltx_config& c, int two_pass) { return make_sample_layout(c, two_pass).total; }
+size_t ltx_sample_cond_workspace_bytes(const ftmi_ltx_config& c, int two_pass, int frames) {
+    return frames > 0 ? make_sample_layout(c, two_pass, frames).total : 0;
+}
 
 // FTMI_SAMPLE_HOIST=0 (read once; ftmi_reload_switches() re-reads it) repeats the text part of the prologue in every step, as a loop over ltx_forward
 // does: the A/B partner of the measurement in DESIGN.md section 7, same bits.
-int ltx_sample(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const bf16_t* text_cond, const bf16_t* text_uncond, const float* kbias_cond,
-               const float* kbias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, void* ws, size_t ws_bytes,
-               hipStream_t st) {
+//
+// frames > 0: conditioned (image-to-video) sampling, ltx_sample_cond.  Restates [upstream, unpinned] LTXImageToVideoPipeline.__call__: the first
+// cond_frames latent frames of every sample of x are clean conditioning latents -- the model sees timestep 0 on them and timesteps[i] on the other frames
+// (t * (1 - conditioning_mask)), the guidance combine and the Euler update touch the other frames only.  The conditioning tables have one row per
+// (model row, frame).  A step knows two distinct timesteps only, so the embedding MLP runs on ONE row per step (the live timestep); the timestep-0 row is
+// computed once per call, next to the text hoist, and cond_rows_expand deals the two rows out to the groups.  With FTMI_SAMPLE_HOIST=0 every step runs the
+// whole per-frame prologue of ltx_forward_frames instead (all groups through the MLP): same bits, a row's embedding does not depend on its neighbours.
+static int ltx_sample_impl(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const bf16_t* text_cond, const bf16_t* text_uncond, const float* kbias_cond,
+                           const float* kbias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, int frames,
+                           int cond_frames, void* ws, size_t ws_bytes, hipStream_t st) {
     static const EnvSwitch hoist_sw("FTMI_SAMPLE_HOIST", 1);
-    const int hoist_text = hoist_sw.get();
+    const int hoist = hoist_sw.get();
     const int two_pass = guidance != 1.0f;
     if (n_steps <= 0) return set_error(FTMI_ERR_INVALID, "ltx_sample: no steps");
     if (c.B <= 0 || c.B * (two_pass ? 2 : 1) > 8) return set_error(FTMI_ERR_UNSUPPORTED, "ltx_sample: at most 4 videos with guidance, 8 without (model batch <= 8)");
     if (c.C_in != c.C_out) return set_error(FTMI_ERR_INVALID, "ltx_sample: the model's output is fed back as its input: C_in must equal C_out");
     if (c.d_valid || c.head_dim_valid) return set_error(FTMI_ERR_UNSUPPORTED, "ltx_sample: narrow (zero-padded) geometries are not supported");
-    const SampleLayout sl = make_sample_layout(c, two_pass);
+    if (frames > 0 && (cond_frames < 0 || cond_frames > frames)) return set_error(FTMI_ERR_INVALID, "ltx_sample_cond: cond_frames must lie in [0, frames]");
+    if (frames > 0 && c.C_in % 8) return set_error(FTMI_ERR_UNSUPPORTED, "ltx_sample_cond: the channel count must be a multiple of 8 (the held prefix moves in 16-byte vectors)");
+    const SampleLayout sl = make_sample_layout(c, two_pass, frames);
     const ftmi_ltx_config& mc = sl.mc;
-    FTMI_TRY(check_cfg(mc));
+    FTMI_TRY(check_cfg(mc, frames));
     if (ws_bytes < sl.total) return set_error(FTMI_ERR_INVALID, "ltx_sample: workspace too small");
     const WsLayout& L = sl.L;
     const int B = c.B, nb = mc.B;
+    const ModGroups mg = frames > 0 ? ModGroups{nb * frames, c.S / frames} : ModGroups{nb, c.S};
     const long per_sample = (long)c.S * c.C_in;
+    const long hold = frames > 0 ? (long)cond_frames * (c.S / frames) * c.C_in : 0;  // the held prefix of every sample, in elements
     bf16_t* xin = W(ws, sl.xin);
     bf16_t* pred = W(ws, sl.pred);
     bf16_t* text = W(ws, sl.text);
@@ -472,17 +543,45 @@ int ltx_sample(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const bf16_t
     }
     if (!ok) return set_error(FTMI_ERR_LAUNCH, "ltx_sample: copy of the prompt embeddings failed");
 
-    if (hoist_text) FTMI_TRY(ltx_prologue_text(mc, w, L, ws, text, st));
+    if (hoist) FTMI_TRY(ltx_prologue_text(mc, w, L, ws, text, st));
+    bf16_t* emb2 = frames > 0 ? W(ws, sl.emb2) : nullptr;
+    bf16_t* temb2 = frames > 0 ? W(ws, sl.temb2) : nullptr;
+    if (frames > 0 && hoist) {  // the timestep-0 row of the conditioning: constant over the loop
+        if (hipMemsetAsync(tval, 0, 4, st) != hipSuccess) return set_error(FTMI_ERR_LAUNCH, "ltx_sample_cond: memset of the timestep failed");
+        FTMI_TRY(ltx_time_embed(mc, w, L, ws, tval, 1, emb2, temb2, st));
+    }
     FTMI_TRY(cfg_euler_step(nullptr, x, nullptr, nullptr, 0, guidance, xin, B, per_sample, st));  // the first model input: bf16(x) in every half
     for (int i = 0; i < n_steps; ++i) {
-        FTMI_TRY(bcast_f32(timesteps + i, tval, nb, st));
-        FTMI_TRY(ltx_prologue_time(mc, w, L, ws, tval, st));
+        if (frames <= 0) {
+            FTMI_TRY(bcast_f32(timesteps + i, tval, nb, st));
+            FTMI_TRY(ltx_prologue_time(mc, w, L, ws, tval, nb, st));
+        } else if (hoist) {
+            FTMI_TRY(ltx_time_embed(mc, w, L, ws, timesteps + i, 1, emb2 + mc.D, temb2 + 6 * (size_t)mc.D, st));
+            FTMI_TRY(cond_rows_expand(emb2, temb2, W(ws, L.emb), W(ws, L.temb), mg.n, frames, cond_frames, mc.D, st));
+            FTMI_TRY(ltx_ada_tables(mc, w, L, ws, mg.n, st));
+        } else {
+            FTMI_TRY(frame_timesteps(timesteps + i, tval, mg.n, frames, cond_frames, st));
+            FTMI_TRY(ltx_prologue_time(mc, w, L, ws, tval, mg.n, st));
+        }
         FTMI_TRY(ltx_proj_in(mc, w, L, ws, xin, st));
-        if (!hoist_text) FTMI_TRY(ltx_prologue_text(mc, w, L, ws, text, st));
-        FTMI_TRY(ltx_blocks_tail(mc, w, L, ws, kbias, pred, st));
-        FTMI_TRY(cfg_euler_step(pred, x, sigmas + i, sigmas + i + 1, 0, guidance, i + 1 < n_steps ? xin : nullptr, B, per_sample, st));
+        if (!hoist) FTMI_TRY(ltx_prologue_text(mc, w, L, ws, text, st));
+        FTMI_TRY(ltx_blocks_tail(mc, w, L, ws, kbias, pred, st, mg));
+        FTMI_TRY(cfg_euler_step(pred, x, sigmas + i, sigmas + i + 1, 0, guidance, i + 1 < n_steps ? xin : nullptr, B, per_sample, st, hold));
     }
     return 0;
+}
+
+int ltx_sample(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const bf16_t* text_cond, const bf16_t* text_uncond, const float* kbias_cond,
+               const float* kbias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, void* ws, size_t ws_bytes,
+               hipStream_t st) {
+    return ltx_sample_impl(c, w, text_cond, text_uncond, kbias_cond, kbias_uncond, x, sigmas, timesteps, n_steps, guidance, 0, 0, ws, ws_bytes, st);
+}
+
+int ltx_sample_cond(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const bf16_t* text_cond, const bf16_t* text_uncond, const float* kbias_cond,
+                    const float* kbias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, int frames,
+                    int cond_frames, void* ws, size_t ws_bytes, hipStream_t st) {
+    if (frames <= 0) return set_error(FTMI_ERR_INVALID, "ltx_sample_cond: frames must be positive");
+    return ltx_sample_impl(c, w, text_cond, text_uncond, kbias_cond, kbias_uncond, x, sigmas, timesteps, n_steps, guidance, frames, cond_frames, ws, ws_bytes, st);
 }
 
 // Backward of blocks [l_lo, l_hi) in descending order (the tail first when l_hi == L).  When the call returns (stream order) the LoRA
@@ -575,7 +674,7 @@ int ltx_backward_range(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, cons
         const bf16_t* h1 = W(blk, L.h1);
         const bf16_t* h2 = W(blk, L.h2);
         const bf16_t* dhin = dh[cur];
-        if (c.checkpoint) FTMI_TRY(ltx_block_forward(c, w, L, ws, l, key_bias, st, fx));  // the block's activations again, into the one slot
+        if (c.checkpoint) FTMI_TRY(ltx_block_forward(c, w, L, ws, l, key_bias, st, fx, ModGroups{c.B, c.S}));  // the block's activations again, into the one slot
 
         // ---- feed-forward ----
         // (dO holds bf(dhin * gate_mlp): written by the kernel that produced dhin)

@@ -1,4 +1,4 @@
-// LTX-Video latent sampling, the two kernels around the DiT forward of a denoising loop (the orchestrator is ltx_sample in ltx_dit.hip).
+// LTX-Video latent sampling, the kernels around the DiT forward of a denoising loop (the orchestrators are ltx_sample / ltx_sample_cond in ltx_dit.hip).
 //
 // cfg_euler_step: classifier-free-guidance combine + flow-match Euler update of one sampler step, one pass over memory.
 //   pred bf16 [2B, n] (rows [0, B) unconditional, [B, 2B) conditional; guidance == 1: [B, n], no unconditional half), state x fp32 [B, n]
@@ -9,6 +9,15 @@
 //   pipeline's noise_pred_uncond + guidance_scale * (noise_pred_text - noise_pred_uncond).
 //   Bytes moved per element of x: 16 with guidance (read u 2 + c 2 + x 4, write x 4 + 2 x 2), 12 without (read c 2 + x 4, write x 4 + 2).
 //   Pure streaming: 8 elements per thread, every access a 16-byte vector, grid sized from the element count.
+//
+//   Held prefix (image-to-video sampling, ltx_sample_cond): the first `hold` elements of every sample are conditioning latents.  For them the kernel reads x
+//   once and writes its bf16 copy to xin -- no read of pred, no write of x -- and does nothing at all when there is no xin; the other elements take the
+//   update above.  Still one streaming pass of 16-byte accesses (hold % 8 == 0).  Restates [upstream, unpinned] LTXImageToVideoPipeline.__call__: the
+//   scheduler steps the frames past the conditioning ones only and the conditioning latents are concatenated back unchanged.
+//
+// frame_timesteps / cond_rows_expand: the per-frame conditioning of that loop.  A model row sees timestep 0 on its first k latent frames and the step's
+//   timestep on the others (t * (1 - conditioning_mask)): frame_timesteps writes that vector [G] (G = model rows x frames); cond_rows_expand copies one
+//   of TWO embedding rows (row 0: timestep 0, row 1: the live timestep) into each of the G rows of emb [G, D] and temb [G, 6D].
 //
 // unpack_denorm: the inverse of noise_pack's normalise + pack: x fp32 [B, S, C] -> latents bf16 [B, C, S] = x * std[c] + mean[c]
 //   (_denormalize of finetrainers/models/ltx_video/base_specification.py:427-436 with scaling_factor 1: the normalisation there is
@@ -30,18 +39,25 @@ FTMI_DEVICE void unpack8(const u32x4& p, float* f) {
 }
 
 // n8 = B * per8 vectors of 8 elements; per8 = per_sample / 8.  kCfg: pred has an unconditional half.  pred == nullptr: no update, only the
-// bf16 copies of x (the model input of the first step).
-template <bool kCfg>
+// bf16 copies of x (the model input of the first step).  kHold: the first hold8 vectors of every sample are held (copied to xin, never updated).
+template <bool kCfg, bool kHold>
 __global__ __launch_bounds__(256) void cfg_euler_step_kernel(const bf16_t* __restrict__ pred, float* __restrict__ x, const float* __restrict__ sigma,
                                                              const float* __restrict__ sigma_next, long sig_stride, float g, bf16_t* __restrict__ xin,
-                                                             long n8, long per8) {
+                                                             long n8, long per8, long hold8) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n8) return;
+    long b = 0;
+    bool held = false;
+    if (kHold) {
+        b = i / per8;
+        held = i - b * per8 < hold8;
+        if (held && !xin) return;  // nothing to copy, nothing to update
+    }
     f32x4* xp = reinterpret_cast<f32x4*>(x) + 2 * i;
     f32x4 x0 = xp[0], x1 = xp[1];
     float xv[8] = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
-    if (pred) {
-        const long b = i / per8;
+    if (pred && !held) {
+        if (!kHold) b = i / per8;
         const float dt = sigma_next[b * sig_stride] - sigma[b * sig_stride];
         float v[8];
         const u32x4* pp = reinterpret_cast<const u32x4*>(pred);
@@ -110,21 +126,58 @@ __global__ void bcast_f32_kernel(const float* __restrict__ src, float* __restric
     if ((int)threadIdx.x < n) dst[threadIdx.x] = src[0];
 }
 
+// out[g] = (g % F) < k ? 0 : t[0]  for the G = model rows x F modulation groups of one denoising step
+__global__ void frame_timesteps_kernel(const float* __restrict__ t, float* __restrict__ out, int G, int F, int k) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g < G) out[g] = (g % F) < k ? 0.0f : t[0];
+}
+
+// emb [G, D] / temb [G, 6D] <- row (g % F < k ? 0 : 1) of emb2 [2, D] / temb2 [2, 6D]; one 16-byte vector per thread, grid (ceil(7 D / 8 / 256), G)
+__global__ __launch_bounds__(256) void cond_rows_expand_kernel(const bf16_t* __restrict__ emb2, const bf16_t* __restrict__ temb2, bf16_t* __restrict__ emb,
+                                                               bf16_t* __restrict__ temb, int F, int k, int D) {
+    const int g = blockIdx.y;
+    const int v = blockIdx.x * 256 + threadIdx.x, d8 = D / 8;
+    if (v >= 7 * d8) return;
+    const int src = (g % F) < k ? 0 : 1;
+    if (v < d8)
+        reinterpret_cast<u32x4*>(emb + (long)g * D)[v] = reinterpret_cast<const u32x4*>(emb2 + (long)src * D)[v];
+    else
+        reinterpret_cast<u32x4*>(temb + (long)g * 6 * D)[v - d8] = reinterpret_cast<const u32x4*>(temb2 + (long)src * 6 * D)[v - d8];
+}
+
 }  // namespace
 
 int cfg_euler_step(const bf16_t* pred, float* x, const float* sigma, const float* sigma_next, long sig_stride, float guidance, bf16_t* xin, int B,
-                   long per_sample, hipStream_t st) {
+                   long per_sample, hipStream_t st, long hold) {
     if (B <= 0 || per_sample <= 0) return set_error(FTMI_ERR_INVALID, "cfg_euler_step: empty problem");
     if (per_sample % 8) return set_error(FTMI_ERR_UNSUPPORTED, "cfg_euler_step: elements per sample must be a multiple of 8 (16-byte vectors)");
+    if (hold < 0 || hold > per_sample) return set_error(FTMI_ERR_INVALID, "cfg_euler_step: the held prefix must lie inside the sample");
+    if (hold % 8) return set_error(FTMI_ERR_UNSUPPORTED, "cfg_euler_step: the held prefix must be a multiple of 8 elements (16-byte vectors)");
     if (((uintptr_t)pred | (uintptr_t)x | (uintptr_t)xin) & 15) return set_error(FTMI_ERR_INVALID, "cfg_euler_step: tensors must be 16-byte aligned");
-    const long per8 = per_sample / 8, n8 = per8 * B;
+    const long per8 = per_sample / 8, n8 = per8 * B, hold8 = hold / 8;
     const long blocks = (n8 + 255) / 256;
     if (blocks > 0x7fffffffL) return set_error(FTMI_ERR_UNSUPPORTED, "cfg_euler_step: too many elements for one launch");
-    if (guidance != 1.0f)
-        hipLaunchKernelGGL(cfg_euler_step_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, pred, x, sigma, sigma_next, sig_stride, guidance, xin, n8, per8);
-    else
-        hipLaunchKernelGGL(cfg_euler_step_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, pred, x, sigma, sigma_next, sig_stride, guidance, xin, n8, per8);
+#define FTMI_STEP(CFG, HOLD) \
+    hipLaunchKernelGGL((cfg_euler_step_kernel<CFG, HOLD>), dim3((unsigned)blocks), dim3(256), 0, st, pred, x, sigma, sigma_next, sig_stride, guidance, xin, n8, per8, hold8)
+    if (guidance != 1.0f) {
+        if (hold8 > 0) FTMI_STEP(true, true); else FTMI_STEP(true, false);
+    } else {
+        if (hold8 > 0) FTMI_STEP(false, true); else FTMI_STEP(false, false);
+    }
+#undef FTMI_STEP
     return check_launch("cfg_euler_step");
+}
+
+int frame_timesteps(const float* t, float* out, int G, int F, int k, hipStream_t st) {
+    if (G <= 0 || F <= 0 || k < 0 || k > F) return set_error(FTMI_ERR_INVALID, "frame_timesteps: bad argument");
+    hipLaunchKernelGGL(frame_timesteps_kernel, dim3((G + 63) / 64), dim3(64), 0, st, t, out, G, F, k);
+    return check_launch("frame_timesteps");
+}
+
+int cond_rows_expand(const bf16_t* emb2, const bf16_t* temb2, bf16_t* emb, bf16_t* temb, int G, int F, int k, int D, hipStream_t st) {
+    if (G <= 0 || G > 65535 || F <= 0 || k < 0 || k > F || D <= 0 || D % 8) return set_error(FTMI_ERR_INVALID, "cond_rows_expand: bad argument");
+    hipLaunchKernelGGL(cond_rows_expand_kernel, dim3((7 * (D / 8) + 255) / 256, G), dim3(256), 0, st, emb2, temb2, emb, temb, F, k, D);
+    return check_launch("cond_rows_expand");
 }
 
 int unpack_denorm(const float* x, const float* mean, const float* std_, bf16_t* out, int B, int C, int S, hipStream_t st) {

@@ -2,8 +2,9 @@
 
 The reference validates by building an ``LTXPipeline`` and running its denoising loop per prompt (finetrainers/models/ltx_video/
 base_specification.py:347-377).  Here the loop -- DiT forward on the conditional + unconditional prompt, classifier-free-guidance combine, flow-match Euler
-update -- is ONE C call (``ftmi_ltx_sample``, no host synchronisation) over the transformer that is being trained, with its current LoRA state.  Text
-encoding and VAE decoding stay outside: the sampler takes prompt embeddings and returns denormalised latents (INTEGRATION.md shows the hand-over to the
+update -- is ONE C call (``ftmi_ltx_sample``, no host synchronisation) over the transformer that is being trained, with its current LoRA state.  A
+validation row with an image runs the image-to-video pipeline there (:360-361); here that is ``image_latents``: the first latent frames held, timestep 0
+on them (``ftmi_ltx_sample_cond``).  Text encoding, VAE encoding of the image and VAE decoding stay outside: the sampler takes prompt embeddings and returns denormalised latents (INTEGRATION.md shows the hand-over to the
 reference pipeline's VAE decode).
 """
 
@@ -73,7 +74,7 @@ def latent_grid(num_frames: int, height: int, width: int, temporal_compression: 
 
 
 class MI355XLTXLatentSampler:
-    """Denoising loop over a ``MI355XLTXVideoTransformer3DModel`` (``ftmi_ltx_sample``)."""
+    """Denoising loop over a ``MI355XLTXVideoTransformer3DModel`` (``ftmi_ltx_sample`` / ``ftmi_ltx_sample_cond``)."""
 
     def __init__(self, transformer: MI355XLTXVideoTransformer3DModel, scheduler_config: Optional[Dict[str, Any]] = None, frame_rate: int = 25):
         if getattr(transformer, "_narrow", None) is not None:
@@ -90,19 +91,62 @@ class MI355XLTXLatentSampler:
         # patch.py:55-57, as MI355XLTXVideoTransformer3DModel.forward builds it
         return ((1 - mask.to(device=dev).reshape(B, T).to(bf16)) * -10000.0).float().contiguous()
 
+    @staticmethod
+    def _cond_frames(image_latents: Optional[torch.Tensor], cond_frames: Optional[int], B: int, C: int, num_frames: int, height: int, width: int) -> int:
+        """The number of held latent frames, after checking ``image_latents`` [B, C, k, H, W] against the grid."""
+        k_img = 0
+        if image_latents is not None:
+            if image_latents.ndim != 5 or tuple(image_latents.shape[:2]) != (B, C) or tuple(image_latents.shape[3:]) != (height, width):
+                raise ValueError(f"sample: image_latents must be [{B}, {C}, k, {height}, {width}], got {tuple(image_latents.shape)}")
+            k_img = image_latents.shape[2]
+            if not 1 <= k_img <= num_frames:
+                raise ValueError(f"sample: image_latents hold {k_img} frames, the clip has {num_frames}")
+        k = k_img if cond_frames is None else int(cond_frames)
+        if not 0 <= k <= num_frames:
+            raise ValueError(f"sample: cond_frames {k} outside [0, {num_frames}]")
+        if image_latents is not None and k != k_img:
+            raise ValueError(f"sample: cond_frames {k} != the {k_img} frames of image_latents")
+        return k
+
+    @staticmethod
+    def initial_state(B: int, C: int, num_frames: int, height: int, width: int, device, generator: Optional[torch.Generator] = None,
+                      latents: Optional[torch.Tensor] = None, image_latents: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The sampler state at step 0, packed fp32 [B, S, C]: ``latents`` or ``randn([B, C, F, H, W], generator)`` -- drawn for the whole shape, whatever is
+        held, so one seed gives one noise tensor -- with ``image_latents`` [B, C, k, H, W] written over latent frames [0, k)."""
+        if latents is None:
+            latents = torch.randn((B, C, num_frames, height, width), generator=generator, device=device, dtype=torch.float32)
+        elif tuple(latents.shape) != (B, C, num_frames, height, width):
+            raise ValueError(f"sample: latents must be [{B}, {C}, {num_frames}, {height}, {width}]")
+        latents = latents.to(device=device, dtype=torch.float32)
+        if image_latents is not None:
+            MI355XLTXLatentSampler._cond_frames(image_latents, None, B, C, num_frames, height, width)
+            latents = latents.clone()
+            latents[:, :, :image_latents.shape[2]] = image_latents.to(device=device, dtype=torch.float32)
+        return latents.flatten(2).transpose(1, 2).contiguous()  # pack: [B, S, C]
+
     @torch.no_grad()
     def sample(self, prompt_embeds: torch.Tensor, prompt_attention_mask: Optional[torch.Tensor], negative_prompt_embeds: Optional[torch.Tensor],
                negative_prompt_attention_mask: Optional[torch.Tensor], num_frames: int, height: int, width: int, num_inference_steps: int = 50,
                guidance_scale: float = 3.0, sigmas: Optional[Sequence[float]] = None, timesteps: Optional[Sequence[float]] = None,
                generator: Optional[torch.Generator] = None, latents: Optional[torch.Tensor] = None, latents_mean: Optional[torch.Tensor] = None,
-               latents_std: Optional[torch.Tensor] = None) -> torch.Tensor:
+               latents_std: Optional[torch.Tensor] = None, image_latents: Optional[torch.Tensor] = None,
+               cond_frames: Optional[int] = None) -> torch.Tensor:
         """-> denormalised latents [B, C, F, H, W] bf16 (the VAE decoder's input).
 
         ``num_frames`` / ``height`` / ``width`` are the LATENT grid, as for the transformer's forward (``latent_grid`` converts a pixel-space clip).
         ``sigmas`` [n + 1] / ``timesteps`` [n] override the schedule (default: ``flow_match_sigmas`` and ``sigma * num_train_timesteps``, the value the
         pipeline feeds the model).  The initial noise is ``torch.randn([B, C, F, H, W], generator=generator)`` in fp32 on the transformer's device, then
         packed -- the order a pipeline draws it in, so one seed gives the same noise -- or ``latents`` in that layout.  ``latents_mean`` / ``latents_std``
-        ([C], the VAE's statistics) denormalise the result; without them it stays normalised (mean 0, std 1)."""
+        ([C], the VAE's statistics) denormalise the result; without them it stays normalised (mean 0, std 1).
+
+        Image-to-video ([upstream, unpinned] restates ``LTXImageToVideoPipeline.prepare_latents`` / ``__call__``): ``image_latents`` [B, C, k, H, W] are the
+        NORMALISED latents of the conditioning frames -- the VAE encoding of the image after ``_normalize_latents`` (base_specification.py:427-436), not the
+        raw encoder output; ``latents_mean`` / ``latents_std`` are used for the final denormalisation only.  They occupy latent frames [0, k) of the initial
+        state and are held: the model sees timestep 0 on them, the guidance combine and the Euler update skip them, and they come back in the result,
+        denormalised like the rest (``ftmi_ltx_sample_cond``).  The noise is drawn for the whole [B, C, F, H, W] shape first and the held frames are then
+        overwritten, so one seed gives the noise the pipeline draws; upstream repeats the one encoded frame over all frames and blends by its mask, which for
+        k = 1 is this state.  ``cond_frames`` (default: the k of ``image_latents``; 0 without them) holds the first frames of ``latents`` when the caller
+        supplies the whole initial state itself."""
         tr = self.transformer
         dev = tr.device
         c = tr.config
@@ -137,11 +181,8 @@ class MI355XLTXLatentSampler:
         if ts.numel() != n:
             raise ValueError("sample: timesteps must hold one value per step")
 
-        if latents is None:
-            latents = torch.randn((B, C, num_frames, height, width), generator=generator, device=dev, dtype=torch.float32)
-        elif tuple(latents.shape) != (B, C, num_frames, height, width):
-            raise ValueError(f"sample: latents must be [{B}, {C}, {num_frames}, {height}, {width}]")
-        x = latents.to(device=dev, dtype=torch.float32).flatten(2).transpose(1, 2).contiguous()  # pack: [B, S, C]
+        k = self._cond_frames(image_latents, cond_frames, B, C, num_frames, height, width)
+        x = self.initial_state(B, C, num_frames, height, width, dev, generator=generator, latents=latents, image_latents=image_latents)
 
         # specification.py forward / base_specification.py:324-334
         temporal_compression_ratio, vae_spatial_compression_ratio = 8, 32
@@ -150,9 +191,14 @@ class MI355XLTXLatentSampler:
         tr.refresh_lora_copies()  # mid-training validation sees the adapters as they are now
         cfg = tr._c_config(B, S, T)
         weights = tr._c_weights(cos, sin)
-        ws = tr._acquire_workspace(ops.ltx_sample_workspace_bytes(cfg, two_pass), dev)
+        conditioned = image_latents is not None or cond_frames is not None
+        ws_bytes = ops.ltx_sample_cond_workspace_bytes(cfg, two_pass, num_frames) if conditioned else ops.ltx_sample_workspace_bytes(cfg, two_pass)
+        ws = tr._acquire_workspace(ws_bytes, dev)
         try:
-            ops.ltx_sample(cfg, weights, text_c, text_u, kb_c, kb_u, x, sig.to(dev), ts.to(dev), g, workspace=ws)
+            if conditioned:
+                ops.ltx_sample_cond(cfg, weights, text_c, text_u, kb_c, kb_u, x, sig.to(dev), ts.to(dev), g, num_frames, k, workspace=ws)
+            else:
+                ops.ltx_sample(cfg, weights, text_c, text_u, kb_c, kb_u, x, sig.to(dev), ts.to(dev), g, workspace=ws)
         finally:
             tr._release_workspace(ws)
         mean = torch.zeros(C, dtype=torch.float32, device=dev) if latents_mean is None else latents_mean.reshape(-1)[:C].to(device=dev, dtype=torch.float32)

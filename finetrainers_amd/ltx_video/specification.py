@@ -216,8 +216,9 @@ class MI355XLTXVideoModelSpecification:
 
     def validation_latents(self, transformer: MI355XLTXVideoTransformer3DModel, scheduler_config: Optional[Dict[str, Any]] = None, **kwargs) -> torch.Tensor:
         """The denoising loop of ``validation`` (base_specification.py:347-377) on the native kernels, in latent space: prompt embeddings in, denormalised
-        latents [B, C, F, H, W] out (``MI355XLTXLatentSampler.sample`` takes the keyword arguments).  Text encoding and the VAE decode are not here:
-        ``validation`` itself stays the reference's."""
+        latents [B, C, F, H, W] out (``MI355XLTXLatentSampler.sample`` takes the keyword arguments, ``image_latents`` / ``cond_frames`` of the
+        image-to-video rows, :360-361, among them).  Text encoding, the VAE encoding of the image and the VAE decode are not here: ``validation`` itself
+        stays the reference's."""
         from .sampler import MI355XLTXLatentSampler
 
         return MI355XLTXLatentSampler(transformer, scheduler_config=scheduler_config).sample(**kwargs)

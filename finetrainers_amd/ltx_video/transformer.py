@@ -568,7 +568,12 @@ class MI355XLTXVideoTransformer3DModel(nn.Module):
     # ------------------------------------------------------------------ forward (patch.py:38-50 signature)
     def forward(self, hidden_states: torch.Tensor, encoder_hidden_states: torch.Tensor, timestep: torch.Tensor,
                 encoder_attention_mask: Optional[torch.Tensor], num_frames: int, height: int, width: int,
-                rope_interpolation_scale=None, return_dict: bool = True, *args, **kwargs):
+                rope_interpolation_scale=None, return_dict: bool = True, *args, frame_timestep: Optional[torch.Tensor] = None, **kwargs):
+        """``frame_timestep`` [B, num_frames] (an addition to the patch.py signature): one timestep per latent frame -- what the image-to-video pipeline
+        feeds the model (0 on the conditioning frame, t on the others).  ``timestep`` is then not read.  Forward only (``ftmi_ltx_forward_frames``)."""
+        if frame_timestep is not None:
+            return self._forward_frames(hidden_states, encoder_hidden_states, frame_timestep, encoder_attention_mask, num_frames, height, width,
+                                        rope_interpolation_scale, return_dict)
         if not hidden_states.is_cuda:
             raise RuntimeError("MI355XLTXVideoTransformer3DModel runs on the GPU only (no CPU path)")
         B, S, _ = hidden_states.shape
@@ -594,6 +599,43 @@ class MI355XLTXVideoTransformer3DModel(nn.Module):
         la = self.lora_A if self.lora_A is not None else None
         lb = self.lora_B if self.lora_B is not None else None
         out = _LTXDiTFunction.apply(self, x_t, text, key_bias, tvals, cos, sin, la, lb)
+        if not return_dict:
+            return (out,)
+        return {"sample": out}
+
+    def _forward_frames(self, hidden_states, encoder_hidden_states, frame_timestep, encoder_attention_mask, num_frames, height, width,
+                        rope_interpolation_scale, return_dict):
+        """The forward with one timestep per latent frame.  There is no backward through per-frame timesteps: refused where autograd would want one."""
+        if tuple(frame_timestep.shape) != (hidden_states.shape[0], num_frames):
+            raise ValueError(f"frame_timestep must be [batch, num_frames] = [{hidden_states.shape[0]}, {num_frames}], got {tuple(frame_timestep.shape)}")
+        if torch.is_grad_enabled() and self.lora_A is not None and (self.lora_A.requires_grad or self.lora_B.requires_grad):
+            raise NotImplementedError("frame_timestep: the per-frame forward (ftmi_ltx_forward_frames) has no backward -- call it under torch.no_grad() or "
+                                      "with no adapter that requires grad")
+        if getattr(self, "_narrow", None) is not None:
+            raise NotImplementedError("frame_timestep: narrow (zero-padded) geometries (ltx_video/narrow.py) are not supported")
+        if not hidden_states.is_cuda:
+            raise RuntimeError("MI355XLTXVideoTransformer3DModel runs on the GPU only (no CPU path)")
+        B, S, _ = hidden_states.shape
+        if S != num_frames * height * width:
+            raise ValueError(f"sequence length {S} != num_frames*height*width = {num_frames * height * width}")
+        x_t = hidden_states.detach().to(bf16).contiguous()
+        text = encoder_hidden_states.detach().to(bf16).contiguous()
+        T = text.shape[1]
+        if encoder_attention_mask is None:
+            key_bias = None
+        elif encoder_attention_mask.ndim == 2:  # patch.py:55-57, as forward builds it
+            key_bias = ((1 - encoder_attention_mask.to(bf16)) * -10000.0).float().contiguous()
+        else:
+            key_bias = encoder_attention_mask.reshape(B, T).float().contiguous()
+        tvals = frame_timestep.detach().to(device=x_t.device, dtype=torch.float32).contiguous()
+        cos, sin = self.rope_tables(num_frames, height, width, rope_interpolation_scale)
+        self.refresh_lora_copies()
+        cfg = self._c_config(B, S, T)
+        ws = self._acquire_workspace(ops.ltx_forward_frames_workspace_bytes(cfg, num_frames), x_t.device)
+        try:
+            out = ops.ltx_forward_frames(cfg, self._c_weights(cos, sin), x_t, text, key_bias, tvals, workspace=ws)
+        finally:
+            self._release_workspace(ws)
         if not return_dict:
             return (out,)
         return {"sample": out}

@@ -325,6 +325,68 @@ def ltx_cfg_euler_step(pred, x, sigma, sigma_next, guidance: float, x_next: Opti
     return x_next
 
 
+def ltx_cfg_euler_step_held(pred, x, sigma, sigma_next, guidance: float, hold: int, x_next: Optional[torch.Tensor] = None):
+    """``ltx_cfg_euler_step`` with the first ``hold`` elements of every sample held (include/ftmi355.h: ftmi_ltx_cfg_euler_step_held): ``x`` stays as it is
+    there and only its bf16 copy reaches the returned model input.  ``hold % 8 == 0``."""
+    require_gpu_tensor(pred, "pred", bf16)
+    require_gpu_tensor(x, "x", torch.float32)
+    require_gpu_tensor(sigma, "sigma", torch.float32)
+    require_gpu_tensor(sigma_next, "sigma_next", torch.float32)
+    if not (pred.is_contiguous() and x.is_contiguous() and sigma.is_contiguous() and sigma_next.is_contiguous()):
+        raise ValueError("ltx_cfg_euler_step_held: tensors must be contiguous (x is updated in place)")
+    B = x.shape[0]
+    halves = 1 if float(guidance) == 1.0 else 2
+    if pred.shape[0] != halves * B or tuple(pred.shape[1:]) != tuple(x.shape[1:]):
+        raise ValueError(f"ltx_cfg_euler_step_held: pred {tuple(pred.shape)} must be [{halves} x {B}, ...] over x {tuple(x.shape)}")
+    if sigma.numel() != B or sigma_next.numel() != B:
+        raise ValueError("ltx_cfg_euler_step_held: sigma / sigma_next hold one value per sample")
+    if x_next is None:
+        x_next = torch.empty_like(pred)
+    else:
+        require_gpu_tensor(x_next, "x_next", bf16)
+        if x_next.shape != pred.shape or not x_next.is_contiguous():
+            raise ValueError("ltx_cfg_euler_step_held: x_next must be a contiguous tensor shaped like pred")
+    check(_lib.load().ftmi_ltx_cfg_euler_step_held(ptr(pred), ptr(x), ptr(sigma), ptr(sigma_next), float(guidance), ptr(x_next), B, x[0].numel(), int(hold),
+                                                   stream_ptr()), "ftmi_ltx_cfg_euler_step_held")
+    return x_next
+
+
+def ltx_forward_frames_workspace_bytes(cfg, frames: int) -> int:
+    return int(_lib.load().ftmi_ltx_forward_frames_workspace_bytes(ctypes.byref(cfg), int(frames)))
+
+
+def ltx_forward_frames(cfg, weights, x_t, text, key_bias, timesteps, workspace=None, pred=None):
+    """DiT forward with one timestep per latent frame, forward only (include/ftmi355.h: ftmi_ltx_forward_frames).  ``x_t`` bf16 [B, S, C_in], ``text`` bf16
+    [B, T, D_cap], ``key_bias`` fp32 [B, T] or None, ``timesteps`` fp32 [B, F] with S % F == 0.  Returns ``pred`` bf16 [B, S, C_out]."""
+    require_gpu_tensor(x_t, "x_t", bf16)
+    require_gpu_tensor(text, "text", bf16)
+    require_gpu_tensor(timesteps, "timesteps", torch.float32)
+    B, S, T = cfg.B, cfg.S, cfg.T
+    if tuple(x_t.shape) != (B, S, cfg.C_in) or not x_t.is_contiguous():
+        raise ValueError(f"ltx_forward_frames: x_t must be a contiguous [{B}, {S}, {cfg.C_in}] tensor, got {tuple(x_t.shape)}")
+    if tuple(text.shape) != (B, T, cfg.D_cap) or not text.is_contiguous():
+        raise ValueError(f"ltx_forward_frames: text must be a contiguous [{B}, {T}, {cfg.D_cap}] tensor, got {tuple(text.shape)}")
+    if timesteps.ndim != 2 or timesteps.shape[0] != B or not timesteps.is_contiguous():
+        raise ValueError(f"ltx_forward_frames: timesteps must be a contiguous [{B}, frames] tensor, got {tuple(timesteps.shape)}")
+    frames = timesteps.shape[1]
+    if frames < 1 or S % frames:
+        raise ValueError(f"ltx_forward_frames: {S} tokens do not split into {frames} frames")
+    if key_bias is not None:
+        require_gpu_tensor(key_bias, "key_bias", torch.float32)
+        if tuple(key_bias.shape) != (B, T) or not key_bias.is_contiguous():
+            raise ValueError(f"ltx_forward_frames: key_bias must be a contiguous [{B}, {T}] tensor")
+    ws_bytes = ltx_forward_frames_workspace_bytes(cfg, frames)
+    if workspace is None:
+        workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=x_t.device)
+    elif workspace.numel() < ws_bytes:
+        raise ValueError("ltx_forward_frames: workspace too small")
+    if pred is None:
+        pred = torch.empty((B, S, cfg.C_out), dtype=bf16, device=x_t.device)
+    check(_lib.load().ftmi_ltx_forward_frames(ctypes.byref(cfg), ctypes.byref(weights), ptr(x_t), ptr(text), ptr(key_bias), ptr(timesteps), frames, ptr(pred),
+                                               ptr(workspace), workspace.numel(), stream_ptr()), "ftmi_ltx_forward_frames")
+    return pred
+
+
 def ltx_unpack_denorm(x, mean, std, num_frames: int, height: int, width: int):
     """Inverse of ``noise_pack``'s normalise + pack: x fp32 [B, S, C] -> latents bf16 [B, C, F, H, W] = x * std[c] + mean[c]."""
     require_gpu_tensor(x, "x", torch.float32)
@@ -383,6 +445,56 @@ def ltx_sample(cfg, weights, text_cond, text_uncond, key_bias_cond, key_bias_unc
     check(_lib.load().ftmi_ltx_sample(ctypes.byref(cfg), ctypes.byref(weights), ptr(text_cond), ptr(text_uncond) if two_pass else None, ptr(key_bias_cond),
                                        ptr(key_bias_uncond) if two_pass else None, ptr(x), ptr(sigmas), ptr(timesteps), n, float(guidance), ptr(workspace),
                                        workspace.numel(), stream_ptr()), "ftmi_ltx_sample")
+    return x
+
+
+def ltx_sample_cond_workspace_bytes(cfg, two_pass: bool, frames: int) -> int:
+    return int(_lib.load().ftmi_ltx_sample_cond_workspace_bytes(ctypes.byref(cfg), int(bool(two_pass)), int(frames)))
+
+
+def ltx_sample_cond(cfg, weights, text_cond, text_uncond, key_bias_cond, key_bias_uncond, x, sigmas, timesteps, guidance: float, frames: int, cond_frames: int,
+                    workspace=None):
+    """``ltx_sample`` with the first ``cond_frames`` of the ``frames`` latent frames of every sample held (include/ftmi355.h: ftmi_ltx_sample_cond): those
+    tokens of ``x`` are the clean conditioning latents on entry and are never written; the model sees timestep 0 on them.  Returns ``x``."""
+    two_pass = float(guidance) != 1.0
+    require_gpu_tensor(text_cond, "text_cond", bf16)
+    require_gpu_tensor(x, "x", torch.float32)
+    require_gpu_tensor(sigmas, "sigmas", torch.float32)
+    require_gpu_tensor(timesteps, "timesteps", torch.float32)
+    B, S, T = cfg.B, cfg.S, cfg.T
+    frames, cond_frames = int(frames), int(cond_frames)
+    if frames < 1 or S % frames:
+        raise ValueError(f"ltx_sample_cond: {S} tokens do not split into {frames} frames")
+    if not 0 <= cond_frames <= frames:
+        raise ValueError(f"ltx_sample_cond: cond_frames {cond_frames} outside [0, {frames}]")
+    if tuple(x.shape) != (B, S, cfg.C_in) or not x.is_contiguous():
+        raise ValueError(f"ltx_sample_cond: x must be a contiguous [{B}, {S}, {cfg.C_in}] tensor (it is updated in place), got {tuple(x.shape)}")
+    n = timesteps.numel()
+    if n < 1 or sigmas.numel() != n + 1 or not (sigmas.is_contiguous() and timesteps.is_contiguous()):
+        raise ValueError("ltx_sample_cond: sigmas must hold one more value than timesteps")
+    texts = [("text_cond", text_cond)] + ([("text_uncond", text_uncond)] if two_pass else [])
+    for name, t in texts:
+        if t is None:
+            raise ValueError("ltx_sample_cond: guidance != 1 needs the unconditional prompt embeddings")
+        require_gpu_tensor(t, name, bf16)
+        if tuple(t.shape) != (B, T, cfg.D_cap) or not t.is_contiguous():
+            raise ValueError(f"ltx_sample_cond: {name} must be a contiguous [{B}, {T}, {cfg.D_cap}] tensor, got {tuple(t.shape)}")
+    biases = [("key_bias_cond", key_bias_cond)] + ([("key_bias_uncond", key_bias_uncond)] if two_pass else [])
+    if len({b is None for _, b in biases}) != 1:
+        raise ValueError("ltx_sample_cond: give the key bias of both prompts or of neither")
+    for name, b in biases:
+        if b is not None:
+            require_gpu_tensor(b, name, torch.float32)
+            if tuple(b.shape) != (B, T) or not b.is_contiguous():
+                raise ValueError(f"ltx_sample_cond: {name} must be a contiguous [{B}, {T}] tensor")
+    ws_bytes = ltx_sample_cond_workspace_bytes(cfg, two_pass, frames)
+    if workspace is None:
+        workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=x.device)
+    elif workspace.numel() < ws_bytes:
+        raise ValueError("ltx_sample_cond: workspace too small")
+    check(_lib.load().ftmi_ltx_sample_cond(ctypes.byref(cfg), ctypes.byref(weights), ptr(text_cond), ptr(text_uncond) if two_pass else None,
+                                            ptr(key_bias_cond), ptr(key_bias_uncond) if two_pass else None, ptr(x), ptr(sigmas), ptr(timesteps), n,
+                                            float(guidance), frames, cond_frames, ptr(workspace), workspace.numel(), stream_ptr()), "ftmi_ltx_sample_cond")
     return x
 
 

@@ -17,6 +17,7 @@
  *                                        ltx_video/patch.py:38-127) + loss.backward() through it
  *                                        (finetrainers/trainer/sft_trainer/trainer.py:481)
  *   ftmi_ltx_sample (+ _cfg_euler_step, _unpack_denorm) the denoising loop of the validation pipeline, latents only
+ *   ftmi_ltx_forward_frames / ftmi_ltx_sample_cond        the same with one timestep per latent frame / the first latent frames held (image-to-video)
  *                                        (finetrainers/models/ltx_video/base_specification.py:347-377)
  *   ftmi_ltx_noise_pack ................ normalise / noise / flow-match mix / pack / target of
  *                                        base_specification.py:295-320,343,427-459 + functional/diffusion.py:4-11
@@ -331,6 +332,19 @@ int ftmi_ltx_workspace_offset(const ftmi_ltx_config* cfg, const char* name, int 
 int ftmi_ltx_forward(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const void* x_t, const void* text,
                      const float* key_bias, const float* timestep, void* pred, void* ws, size_t ws_bytes, ftmi_stream stream);
 
+/* Forward with ONE TIMESTEP PER LATENT FRAME -- forward only.  The image-to-video mode of the reference's validation (finetrainers/models/ltx_video/
+ * base_specification.py:360-361 switches to LTXImageToVideoPipeline when a validation row has an image; its training counterpart is the first-frame branch,
+ * :282-311) feeds the model timestep 0 on the conditioning frame and t on the others; the oracle takes per-token timesteps as upstream does
+ * (oracle/ltx.py:450-457).  Same arguments as ftmi_ltx_forward, except timesteps fp32 [B, frames] (device): the S / frames tokens of latent frame f of
+ * sample b are modulated by the conditioning of timesteps[b * frames + f].  S % frames == 0 and B * frames <= 128 (8 model rows x 16 latent frames, a
+ * 121-frame clip; B itself is not limited to 8 here); narrow geometries (d_valid / head_dim_valid) are refused.  With all timesteps of a sample equal the
+ * result is ftmi_ltx_forward's, bit for bit.
+ * NO BACKWARD MAY FOLLOW: cfg->checkpoint is ignored, the workspace is the checkpoint = 1 layout (one block slot + the residual stream) with conditioning
+ * tables of B * frames rows -- ftmi_ltx_forward_frames_workspace_bytes(cfg, frames) -- and ftmi_ltx_backward* would read tables of another shape. */
+size_t ftmi_ltx_forward_frames_workspace_bytes(const ftmi_ltx_config* cfg, int frames);
+int ftmi_ltx_forward_frames(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const void* x_t, const void* text, const float* key_bias,
+                            const float* timesteps, int frames, void* pred, void* ws, size_t ws_bytes, ftmi_stream stream);
+
 /* Backward: dpred [B,S,C_out] bf16 -> LoRA gradients ACCUMULATED (+=) into fp32 grad_a [L,8,r,D] and grad_b [L,8,D,r]. */
 int ftmi_ltx_backward(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const void* text, const float* key_bias,
                       const void* dpred, float* grad_a, float* grad_b, void* ws, size_t ws_bytes, ftmi_stream stream);
@@ -364,6 +378,13 @@ int ftmi_ltx_noise_pack(const void* latents, const void* noise, const float* mea
 int ftmi_ltx_cfg_euler_step(const void* pred, float* x, const float* sigma, const float* sigma_next, float guidance, void* x_next_bf16, int B,
                             long per_sample, ftmi_stream stream);
 
+/* The same step with a HELD PREFIX: the first `hold` elements of every sample (the conditioning frames of image-to-video sampling, [upstream, unpinned]
+ * LTXImageToVideoPipeline.__call__: the scheduler steps latents[:, :, 1:] only and the conditioning frame is concatenated back) are left untouched in x --
+ * pred is not read there -- and only their bf16 copy goes to x_next_bf16; the other elements take the update above.  hold % 8 == 0, 0 <= hold <= per_sample;
+ * hold == 0 is ftmi_ltx_cfg_euler_step. */
+int ftmi_ltx_cfg_euler_step_held(const void* pred, float* x, const float* sigma, const float* sigma_next, float guidance, void* x_next_bf16, int B,
+                                 long per_sample, long hold, ftmi_stream stream);
+
 /* The inverse of ftmi_ltx_noise_pack's normalise + pack: x fp32 [B, S, C] -> latents bf16 [B, C, S] = x * std[c] + mean[c] (mean, std fp32 [C];
  * the convention of _normalize_latents, base_specification.py:427-436, scaling factor 1).  C % 4 == 0. */
 int ftmi_ltx_unpack_denorm(const float* x, const float* mean, const float* std_, void* latents, int B, int C, int S, ftmi_stream stream);
@@ -385,6 +406,22 @@ size_t ftmi_ltx_sample_workspace_bytes(const ftmi_ltx_config* cfg, int two_pass)
 int ftmi_ltx_sample(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const void* text_cond, const void* text_uncond, const float* key_bias_cond,
                     const float* key_bias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, void* ws,
                     size_t ws_bytes, ftmi_stream stream);
+
+/* Conditioned (image-to-video) sampling: ftmi_ltx_sample with the first cond_frames of the `frames` latent frames of every sample HELD.  Replaces the
+ * denoising loop of the pipeline the reference's validation builds for a row with an image (base_specification.py:360-361); restates [upstream, unpinned]
+ * LTXImageToVideoPipeline.__call__:
+ *   - on entry the first cond_frames * (S / frames) tokens of every sample of x are the clean, normalised conditioning latents, the rest noise; the held
+ *     tokens are never written: on return they are the input, bit for bit
+ *   - the model sees timestep 0 on the held frames and timesteps[i] on the others (timestep * (1 - conditioning_mask)), through the per-frame conditioning
+ *     of ftmi_ltx_forward_frames
+ *   - the guidance combine and the Euler update apply to the other tokens only (ftmi_ltx_cfg_euler_step_held)
+ * S % frames == 0, C_in % 8 == 0, (model rows) * frames <= 128.  cond_frames == 0 computes the bits of ftmi_ltx_sample.  The timestep-0 conditioning row
+ * is computed once per call, the embedding MLP runs on the one live timestep per step; the result is, bit for bit, that of a loop over
+ * ftmi_ltx_forward_frames and ftmi_ltx_cfg_euler_step_held.  No host synchronisation.  Workspace: ftmi_ltx_sample_cond_workspace_bytes. */
+size_t ftmi_ltx_sample_cond_workspace_bytes(const ftmi_ltx_config* cfg, int two_pass, int frames);
+int ftmi_ltx_sample_cond(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const void* text_cond, const void* text_uncond, const float* key_bias_cond,
+                         const float* key_bias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, int frames,
+                         int cond_frames, void* ws, size_t ws_bytes, ftmi_stream stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * CogVideoX spec level (first kernels of the next model family): the DDIM noising and the velocity -> x0 conversion of

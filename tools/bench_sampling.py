@@ -1,6 +1,8 @@
 """LTX-Video latent sampling at BASELINE config 2 size (28 blocks, one 49 x 512 x 768 video = 2 688 tokens, cond + uncond, rank 64): HIP-event time per
 denoising step of ftmi_ltx_sample with the text-side work hoisted out of the step loop (the product) and repeated in every step (FTMI_SAMPLE_HOIST=0),
-interleaved on one box, beside a plain batch-2 forward of the same model.  `python tools/bench_sampling.py [--steps 8] [--rounds 5] [--out FILE]`"""
+interleaved on one box, beside a plain batch-2 forward of the same model.  --cond-frames K (repeatable) adds ftmi_ltx_sample_cond with the first K latent
+frames held to the interleaved rounds (K = 0: per-frame conditioning tables, nothing held).
+`python tools/bench_sampling.py [--steps 8] [--rounds 5] [--cond-frames 0 --cond-frames 1] [--out FILE]`"""
 import argparse
 import ctypes
 import json
@@ -18,6 +20,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--steps", type=int, default=8)
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--layers", type=int, default=28)
+ap.add_argument("--cond-frames", type=int, action="append", default=[], help="also time ftmi_ltx_sample_cond with this many latent frames held (repeatable)")
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 
@@ -44,7 +47,8 @@ cos, sin = model.rope_tables(F_, H_, W_, [1 / (25 / 8), 32, 32])
 model.refresh_lora_copies()
 cfg = model._c_config(1, S, T)
 weights = model._c_weights(cos, sin)
-ws = torch.empty((ops.ltx_sample_workspace_bytes(cfg, True),), dtype=torch.uint8, device=dev)
+ws = torch.empty((max([ops.ltx_sample_workspace_bytes(cfg, True)] + [ops.ltx_sample_cond_workspace_bytes(cfg, True, F_) for _ in a.cond_frames]),),
+                 dtype=torch.uint8, device=dev)
 lib = _lib.load()
 
 
@@ -62,6 +66,13 @@ def sample(hoist):
     lib.ftmi_reload_switches()
     x = x0.clone()
     return event_ms(lambda: ops.ltx_sample(cfg, weights, text_c, text_u, kb_c, kb_u, x, sigmas, timesteps, 3.0, workspace=ws)) / a.steps
+
+
+def sample_cond(k):
+    os.environ["FTMI_SAMPLE_HOIST"] = "1"
+    lib.ftmi_reload_switches()
+    x = x0.clone()
+    return event_ms(lambda: ops.ltx_sample_cond(cfg, weights, text_c, text_u, kb_c, kb_u, x, sigmas, timesteps, 3.0, F_, k, workspace=ws)) / a.steps
 
 
 # plain forward at batch 2 (what one denoising step would cost through the training forward, activations kept)
@@ -84,9 +95,13 @@ def forward():
 
 for _ in range(2):  # warm-up
     sample(True), sample(False), forward()
-rows = {"hoisted": [], "unhoisted": [], "forward_batch2": []}
+    for k in a.cond_frames:
+        sample_cond(k)
+rows = {"hoisted": [], "unhoisted": [], "forward_batch2": [], **{f"cond_frames_{k}": [] for k in a.cond_frames}}
 for _ in range(a.rounds):  # interleaved
     rows["hoisted"].append(sample(True))
+    for k in a.cond_frames:
+        rows[f"cond_frames_{k}"].append(sample_cond(k))
     rows["unhoisted"].append(sample(False))
     rows["forward_batch2"].append(forward())
 del os.environ["FTMI_SAMPLE_HOIST"]
