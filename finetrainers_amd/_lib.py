@@ -127,6 +127,21 @@ class WanBlockConfig(Structure):
     _fields_ = [("B", c_int), ("S", c_int), ("T", c_int), ("D", c_int), ("H", c_int), ("F", c_int), ("eps", c_float), ("gemm_variant", c_int)]
 
 
+class WanLoraBlockConfig(Structure):
+    """include/ftmi355.h: ftmi_wan_lora_block_config."""
+
+    _fields_ = WanBlockConfig._fields_ + [("r", c_int), ("lora_scale", c_float)]
+
+
+WAN_LORA_WEIGHT_FIELDS = ["params", "w_qkv1_t", "w_o1_t", "w_q2_t", "w_kv2_t", "w_o2_t", "w_f1_t", "w_f2_t", "lora_a", "lora_b"]
+
+
+class WanLoraBlockWeights(Structure):
+    """include/ftmi355.h: ftmi_wan_lora_block_weights."""
+
+    _fields_ = [(n, c_void_p) for n in WAN_LORA_WEIGHT_FIELDS]
+
+
 class WanRowArgs(Structure):
     """include/ftmi355.h: ftmi_wan_row_args."""
 
@@ -248,6 +263,12 @@ _SIGS = {
     "ftmi_hy_single_scratch_bytes": (c_size_t, [POINTER(HySingleConfig)]),
     "ftmi_hy_single_forward": (c_int, [POINTER(HySingleConfig), POINTER(HySingleWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    "ftmi_wan_lora_block_saved_bytes": (c_size_t, [POINTER(WanLoraBlockConfig)]),
+    "ftmi_wan_lora_block_scratch_bytes": (c_size_t, [POINTER(WanLoraBlockConfig)]),
+    "ftmi_wan_lora_block_forward": (c_int, [POINTER(WanLoraBlockConfig), POINTER(WanLoraBlockWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    "ftmi_wan_lora_block_backward": (c_int, [POINTER(WanLoraBlockConfig), POINTER(WanLoraBlockWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
     "ftmi_wan_block_saved_bytes": (c_size_t, [POINTER(WanBlockConfig)]),
     "ftmi_wan_block_scratch_bytes": (c_size_t, [POINTER(WanBlockConfig)]),
     "ftmi_wan_block_param_elements": (c_size_t, [POINTER(WanBlockConfig)]),

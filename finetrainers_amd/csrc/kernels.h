@@ -372,6 +372,15 @@ int wan_block_forward(const ftmi_wan_block_config& c, const bf16_t* params, cons
 int wan_block_backward(const ftmi_wan_block_config& c, const bf16_t* params, float* grads, const bf16_t* x, const bf16_t* enc, const float* mod,
                        const float* rope_cos, const float* rope_sin, const bf16_t* dout, bf16_t* dx, bf16_t* denc, float* dmod, void* saved,
                        size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st);
+// the same block over a frozen base with LoRA adapters on the eight attention projections (wan_dit.hip)
+size_t wan_lora_block_saved_bytes(const ftmi_wan_lora_block_config& c);
+size_t wan_lora_block_scratch_bytes(const ftmi_wan_lora_block_config& c);
+int wan_lora_block_forward(const ftmi_wan_lora_block_config& c, const ftmi_wan_lora_block_weights& w, const bf16_t* x, const bf16_t* enc, const float* mod,
+                           const float* rope_cos, const float* rope_sin, bf16_t* out, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
+                           hipStream_t st);
+int wan_lora_block_backward(const ftmi_wan_lora_block_config& c, const ftmi_wan_lora_block_weights& w, const bf16_t* x, const bf16_t* enc, const float* mod,
+                            const float* rope_cos, const float* rope_sin, const bf16_t* dout, bf16_t* dx, bf16_t* denc, float* grad_a, float* grad_b, void* saved,
+                            size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st);
 int adamw_bf16_step(bf16_t* p, const float* g, bf16_t* m, bf16_t* v, long n, const float* sumsq_in, float max_norm, float lr, float beta1, float beta2,
                     float eps, float wd, int step, float* grad_norm_out, hipStream_t st);
 

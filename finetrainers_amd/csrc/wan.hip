@@ -384,10 +384,10 @@ __global__ __launch_bounds__(256) void gate_res_bwd_kernel(WanRowArgs a) {
             if (c < nchunk) {
                 float dv[8], yv[8], o[8];
                 up8(a.x + (long)row * a.ld_x + c * 8, dv);
-                up8(a.dy + (long)row * a.ld_dy + c * 8, yv);
+                if (a.red1) up8(a.dy + (long)row * a.ld_dy + c * 8, yv);  // (no d gate wanted -- a frozen gate: the branch output is not read)
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
-                    r1[it][e] += dv[e] * yv[e];
+                    if (a.red1) r1[it][e] += dv[e] * yv[e];
                     o[e] = dv[e] * gt[it][e];
                 }
                 st8(a.y + (long)row * a.ld_y + c * 8, o);
@@ -491,7 +491,7 @@ int wan_gate_res_fwd(const WanRowArgs& a, hipStream_t st) {
 }
 int wan_gate_res_bwd(const WanRowArgs& a, hipStream_t st) {
     if (int rc = check_args(a, "gate_res_bwd")) return rc;
-    if (!a.x || !a.dy || !a.y || !a.scale) return set_error(FTMI_ERR_INVALID, "wan_gate_res_bwd: bad argument");
+    if (!a.x || (!a.dy && a.red1) || !a.y || !a.scale) return set_error(FTMI_ERR_INVALID, "wan_gate_res_bwd: bad argument");  // (dy is read for red1 only)
     if (a.rows <= 0) return 0;
     const dim3 grid = strip_grid(a);
     FTMI_WAN_DISPATCH(gate_res_bwd_kernel)

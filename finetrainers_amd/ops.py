@@ -773,8 +773,10 @@ def wan_gate_res(x, y, rows_per_batch: int, gate=None, out=None):
 
 
 def wan_gate_res_bwd(dout, y, gate, rows_per_batch: int, dgate=None):
-    """dy = bf(d out * gate_b); dgate (fp32 contiguous [B, D]) += sum_rows d out * y."""
-    dout, y = _rows2d(dout, "dout"), _rows2d(y, "y")
+    """dy = bf(d out * gate_b); dgate (fp32 contiguous [B, D]) += sum_rows d out * y (dgate None -- a frozen gate: y is not read and may be None)."""
+    if y is None and dgate is not None:
+        raise ValueError("the gate's gradient needs the branch output y")
+    dout, y = _rows2d(dout, "dout"), (None if y is None else _rows2d(y, "y"))
     B, D = dout.shape[0] // rows_per_batch, dout.shape[1]
     if dgate is not None and (tuple(dgate.shape) != (B, D) or dgate.stride(0) != D):
         raise ValueError("dgate must be contiguous [B, D] fp32")

@@ -22,7 +22,7 @@ import ctypes
 import os
 
 from .. import _lib, ops
-from .._lib import WanBlockConfig, check, ptr, stream_ptr
+from .._lib import WanBlockConfig, WanLoraBlockConfig, WanLoraBlockWeights, check, ptr, stream_ptr
 
 bf16 = torch.bfloat16
 _NATIVE_SCRATCH: Dict[int, torch.Tensor] = {}  # device index -> byte buffer shared by every natively run block on that device (one stream at a time)
@@ -247,6 +247,243 @@ class _WanBlockNativeFunction(torch.autograd.Function):
         return None, dx, denc, dmod.to(ctx.temb_dtype), None, None
 
 
+# ---- LoRA over a frozen base ------------------------------------------------------------------------------------------------------------------
+# Adapter order inside lora_A [8, r, D] / lora_B [8, D, r] (the projections the recipe's regex "blocks.*(to_q|to_k|to_v|to_out.0)" selects: BOTH attentions)
+LORA_TARGETS = ("attn1.to_q", "attn1.to_k", "attn1.to_v", "attn1.to_out.0", "attn2.to_q", "attn2.to_k", "attn2.to_v", "attn2.to_out.0")
+_TWINS = (("w_qkv1_t", "w_qkv1"), ("w_o1_t", "attn1.to_out.0.weight"), ("w_q2_t", "attn2.to_q.weight"), ("w_kv2_t", "w_kv2"), ("w_o2_t", "attn2.to_out.0.weight"),
+          ("w_f1_t", "ffn.net.0.proj.weight"), ("w_f2_t", "ffn.net.2.weight"))
+
+
+def _lora_linear_fwd(x, w, bias, adp: int, nadp: int, a_sp, b_ext, r: int, s: float):
+    """[rows, nadp D] = x W^T + b + s (x A^T) B^T for the adapters adp .. adp + nadp - 1 on one input: the two launches of csrc/wan_dit.hip lora_linear_fwd.
+    Returns (y, xa [rows, 3 nadp r])."""
+    if r == 0:
+        return ops.gemm_nt(x, w, bias), None
+    rows, D = x.shape
+    xa = torch.empty((rows, 3 * nadp * r), dtype=bf16, device=x.device)
+    ops.gemm_nt_ex(x, a_sp[adp:adp + nadp].reshape(2 * nadp * r, D), xa, M=rows, N=2 * nadp * r, K=D, alpha=s, split_r=r, variant=8)
+    y = torch.empty((rows, nadp * D), dtype=bf16, device=x.device)
+    grp = dict(x2_grp_n=D, x2_grp_stride=3 * r) if nadp > 1 else {}
+    ops.gemm_nt_ex(x, w, y, M=rows, N=nadp * D, K=D, bias=bias, x2=xa, w2=b_ext[adp:adp + nadp].reshape(nadp * D, 3 * r), K2=3 * r, variant=8, **grp)
+    return y, xa
+
+
+def _lora_linear_bwd(x, dy, w_t, adp: int, nadp: int, xa, bt_sp, at_ext, r: int, s: float, ga, gb, need_dx: bool = True):
+    """dx = dY W (+ dXA A); gb[adp ..] += dY^T XA, ga[adp ..] += dXA^T x (csrc/wan_dit.hip lora_linear_bwd)."""
+    rows, D = x.shape
+    if r == 0:
+        return ops.gemm_nt(dy, w_t, None) if need_dx else None
+    dxa = torch.empty((rows, 3 * nadp * r), dtype=bf16, device=x.device)
+    grp = dict(xk_grp_n=2 * r, xk_grp_stride=D) if nadp > 1 else {}
+    ops.gemm_nt_ex(dy, bt_sp[adp:adp + nadp].reshape(2 * nadp * r, D), dxa, M=rows, N=2 * nadp * r, K=D, alpha=s, split_r=r, variant=8, **grp)
+    dx = None
+    if need_dx:
+        dx = torch.empty((rows, D), dtype=bf16, device=x.device)
+        ops.gemm_nt_ex(dy, w_t, dx, M=rows, N=D, K=nadp * D, x2=dxa, w2=at_ext[:, adp * 3 * r:(adp + nadp) * 3 * r], K2=3 * nadp * r, variant=8)
+    ops.gemm_tn_ex(dy, xa, gb[adp:adp + nadp].view(nadp * D, r), M=rows, P=nadp * D, Q=r, v_fold=r, **(dict(v_grp_p=D, v_grp_stride=3 * r) if nadp > 1 else {}))
+    ops.gemm_tn_ex(dxa, x, ga[adp:adp + nadp].view(nadp * r, D), M=rows, P=nadp * r, Q=D, u_fold=r, **(dict(u_grp_p=r, u_grp_stride=3 * r) if nadp > 1 else {}))
+    return dx
+
+
+def _grad_targets(blk: "MI355XWanBlock", lora_a, lora_b):
+    """Where the adapter gradients go: the step object's flat views (added in place), or fresh tensors returned to autograd."""
+    if lora_a is None:
+        return False, None, None
+    own = blk._grad_a_view is not None
+    return own, (blk._grad_a_view if own else torch.zeros_like(lora_a)), (blk._grad_b_view if own else torch.zeros_like(lora_b))
+
+
+class _WanLoRABlockFunction(torch.autograd.Function):
+    """The block over a FROZEN base with the adapters on the eight attention projections, as a composition of the library's launches from Python
+    (``FTMI_NATIVE_BLOCKS=0``): the second implementation ``_WanLoRABlockNativeFunction`` is compared with.  The backward forms dx, denc (only if asked for)
+    and the 16 adapter gradients -- no base-weight gradient, no bias / norm / modulation reduction, and it keeps neither a1, n3, act nor f."""
+
+    @staticmethod
+    def _run(blk: "MI355XWanBlock", x, enc, mod, rope, lora_a, lora_b, need_out: bool = True):
+        B, S, D = x.shape
+        T = enc.shape[1]
+        M, H, hd, eps, s = B * S, blk.heads, blk.head_dim, blk.eps, blk.lora_scale
+        P = blk.param
+        r = 0 if lora_a is None else int(lora_a.shape[1])
+        a_sp = b_ext = None
+        if r:
+            a_sp = torch.stack([ops.lora_split(lora_a[i], sp=True)[0] for i in range(8)])
+            b_ext = torch.stack([ops.lora_split(lora_b[i], ext=True)[0] for i in range(8)])
+        lin = lambda t, w, b, adp, nadp: _lora_linear_fwd(t, w, b, adp, nadp, a_sp, b_ext, r, s)
+        x2d, enc2d = x.view(M, D), enc.view(B * T, D)
+        heads = lambda t, n: t.view(B, n, H, hd).permute(0, 2, 1, 3)
+        tok = lambda t: t.permute(0, 2, 1, 3).reshape(t.shape[0] * t.shape[2], D)
+        n1 = ops.wan_ln(x2d, S, shift=mod[:, 0], scale=mod[:, 1], eps=eps)
+        qkv, xa_qkv = lin(n1, P("w_qkv1"), P("b_qkv1"), 0, 3)
+        qn = ops.wan_rms_rope(qkv[:, :D], P("attn1.norm_q.weight"), S, rope=rope, head_dim=hd, eps=eps)
+        kn = ops.wan_rms_rope(qkv[:, D:2 * D], P("attn1.norm_k.weight"), S, rope=rope, head_dim=hd, eps=eps)
+        o1, lse1 = ops.attn_fwd(heads(qn, S), heads(kn, S), heads(qkv[:, 2 * D:], S))
+        a1, xa_o1 = lin(tok(o1), P("attn1.to_out.0.weight"), P("attn1.to_out.0.bias"), 3, 1)
+        x1 = ops.wan_gate_res(x2d, a1, S, gate=mod[:, 2])
+        n2 = ops.wan_ln(x1, S, w=P("norm2.weight"), b=P("norm2.bias"), eps=eps)
+        q2, xa_q2 = lin(n2, P("attn2.to_q.weight"), P("attn2.to_q.bias"), 4, 1)
+        kv2, xa_kv2 = lin(enc2d, P("w_kv2"), P("b_kv2"), 5, 2)
+        q2n = ops.wan_rms_rope(q2, P("attn2.norm_q.weight"), S, eps=eps)
+        k2n = ops.wan_rms_rope(kv2[:, :D], P("attn2.norm_k.weight"), T, eps=eps)
+        o2, lse2 = ops.attn_fwd(heads(q2n, S), heads(k2n, T), heads(kv2[:, D:], T))
+        a2, xa_o2 = lin(tok(o2), P("attn2.to_out.0.weight"), P("attn2.to_out.0.bias"), 7, 1)
+        x2 = ops.wan_gate_res(x1, a2, S)
+        n3 = ops.wan_ln(x2, S, shift=mod[:, 3], scale=mod[:, 4], eps=eps)
+        act, pre = ops.gemm_nt(n3, P("ffn.net.0.proj.weight"), P("ffn.net.0.proj.bias"), epilogue=1, want_out2=True)
+        acts = (n1, qkv, qn, kn, o1, lse1, x1, n2, q2, kv2, q2n, k2n, o2, lse2, x2, pre, xa_qkv, xa_o1, xa_q2, xa_kv2, xa_o2)
+        if not need_out:
+            return None, acts
+        f = ops.gemm_nt(act, P("ffn.net.2.weight"), P("ffn.net.2.bias"))
+        out = ops.wan_gate_res(x2, f, S, gate=mod[:, 5])
+        return out.view(B, S, D), acts
+
+    @staticmethod
+    def forward(ctx, blk: "MI355XWanBlock", x, enc, temb, rope_cos, rope_sin, lora_a, lora_b):
+        mod = (blk.param("scale_shift_table").float() + temb.float()).contiguous()
+        out, acts = _WanLoRABlockFunction._run(blk, x, enc, mod, (rope_cos, rope_sin), lora_a, lora_b)
+        ctx.blk, ctx.rope, ctx.has_lora = blk, (rope_cos, rope_sin), lora_a is not None
+        ctx.recompute = bool(blk.gradient_checkpointing)
+        la, lb = (lora_a, lora_b) if lora_a is not None else (x.new_empty(0), x.new_empty(0))
+        ctx.save_for_backward(x, enc, mod, la, lb)
+        ctx.acts = None if ctx.recompute else acts
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        blk, rope = ctx.blk, ctx.rope
+        x, enc, mod, lora_a, lora_b = ctx.saved_tensors
+        if not ctx.has_lora:
+            lora_a = lora_b = None
+        acts = ctx.acts
+        ctx.acts = None
+        if ctx.recompute:
+            _, acts = _WanLoRABlockFunction._run(blk, x, enc, mod, rope, lora_a, lora_b, need_out=False)
+        n1, qkv, qn, kn, o1, lse1, x1, n2, q2, kv2, q2n, k2n, o2, lse2, x2, pre, xa_qkv, xa_o1, xa_q2, xa_kv2, xa_o2 = acts
+        B, S, D = x.shape
+        T = enc.shape[1]
+        M, H, hd, eps, s = B * S, blk.heads, blk.head_dim, blk.eps, blk.lora_scale
+        P, Wt = blk.param, blk.transposed()
+        r = 0 if lora_a is None else int(lora_a.shape[1])
+        own, ga, gb = _grad_targets(blk, lora_a, lora_b)
+        bt_sp = at_ext = None
+        if r:
+            bt_sp = torch.stack([ops.lora_split(lora_b[i], t_sp=True)[0] for i in range(8)])
+            at_ext = torch.cat([ops.lora_split(lora_a[i], t_ext=True)[0] for i in range(8)], dim=1)  # the eight adapters side by side: [D, 24r]
+        lin = lambda t, dy, w_t, adp, nadp, xa, need_dx=True: _lora_linear_bwd(t, dy, w_t, adp, nadp, xa, bt_sp, at_ext, r, s, ga, gb, need_dx)
+        need_denc = ctx.needs_input_grad[2]
+        x2d, enc2d = x.view(M, D), enc.view(B * T, D)
+        dout = dout.contiguous().view(M, D)
+        heads = lambda t, n: t.view(B, n, H, hd).permute(0, 2, 1, 3)
+        tok = lambda t: t.permute(0, 2, 1, 3).reshape(t.shape[0] * t.shape[2], D)
+        # feed-forward branch
+        df = ops.wan_gate_res_bwd(dout, None, mod[:, 5], S)
+        dpre = ops.gemm_nt(df, Wt["ffn.net.2.weight"], None, epilogue=3, aux=pre)
+        dn3 = ops.gemm_nt(dpre, Wt["ffn.net.0.proj.weight"], None)
+        dx2 = ops.wan_ln_bwd(x2, dn3, S, scale=mod[:, 4], eps=eps, dres=dout)
+        # cross-attention branch
+        do2 = lin(tok(o2), dx2, Wt["attn2.to_out.0.weight"], 7, 1, xa_o2)
+        dkv2 = torch.empty_like(kv2)
+        dq2n, dk2n, _ = ops.attn_bwd(heads(q2n, S), heads(k2n, T), heads(kv2[:, D:], T), o2, lse2, heads(do2, S), dv_out=heads(dkv2[:, D:], T))
+        dq2 = ops.wan_rms_rope_bwd(q2, P("attn2.norm_q.weight"), tok(dq2n), S, eps=eps)
+        ops.wan_rms_rope_bwd(kv2[:, :D], P("attn2.norm_k.weight"), tok(dk2n), T, eps=eps, out=dkv2[:, :D])
+        denc = lin(enc2d, dkv2, Wt["w_kv2"], 5, 2, xa_kv2, need_denc)
+        dn2 = lin(n2, dq2, Wt["attn2.to_q.weight"], 4, 1, xa_q2)
+        dx1 = ops.wan_ln_bwd(x1, dn2, S, w=P("norm2.weight"), eps=eps, dres=dx2)
+        # self-attention branch
+        da1 = ops.wan_gate_res_bwd(dx1, None, mod[:, 2], S)
+        do1 = lin(tok(o1), da1, Wt["attn1.to_out.0.weight"], 3, 1, xa_o1)
+        dqkv = torch.empty_like(qkv)
+        dqn, dkn, _ = ops.attn_bwd(heads(qn, S), heads(kn, S), heads(qkv[:, 2 * D:], S), o1, lse1, heads(do1, S), dv_out=heads(dqkv[:, 2 * D:], S))
+        ops.wan_rms_rope_bwd(qkv[:, :D], P("attn1.norm_q.weight"), tok(dqn), S, rope=rope, head_dim=hd, eps=eps, out=dqkv[:, :D])
+        ops.wan_rms_rope_bwd(qkv[:, D:2 * D], P("attn1.norm_k.weight"), tok(dkn), S, rope=rope, head_dim=hd, eps=eps, out=dqkv[:, D:2 * D])
+        dn1 = lin(n1, dqkv, Wt["w_qkv1"], 0, 3, xa_qkv)
+        dx = ops.wan_ln_bwd(x2d, dn1, S, scale=mod[:, 1], eps=eps, dres=dx1)
+        denc = denc.view(B, T, D) if denc is not None else None
+        if own:
+            blk._backward_done()
+            ga = gb = None
+        return None, dx.view(B, S, D), denc, None, None, None, ga, gb
+
+
+class _WanLoRABlockNativeFunction(torch.autograd.Function):
+    """``_WanLoRABlockFunction`` with ONE C call per direction (``ftmi_wan_lora_block_forward / _backward``, csrc/wan_dit.hip).  The K-contiguous twins of
+    the weights come from ``blk.transposed()``: cached, and the frozen base never invalidates them.  Gradient checkpointing keeps the block's input only and
+    refills ``saved`` inside the backward (the forward call with ``out = NULL``)."""
+
+    @staticmethod
+    def _args(blk: "MI355XWanBlock", B: int, S: int, T: int, lora_a, lora_b, backward: bool):
+        cfg = WanLoraBlockConfig(B=B, S=S, T=T, D=blk.dim, H=blk.heads, F=blk.ffn_dim, eps=float(blk.eps), gemm_variant=8,
+                                 r=0 if lora_a is None else int(lora_a.shape[1]), lora_scale=float(blk.lora_scale))
+        w = WanLoraBlockWeights()
+        params = blk._params()
+        if params.numel() != blk.layout.total or not params.is_contiguous():
+            raise RuntimeError("Wan block: the flat parameter buffer does not have the layout the C orchestrator expects")
+        keep = [params]
+        w.params = ptr(params)
+        if backward:
+            Wt = blk.transposed()
+            for field, name in _TWINS:
+                keep.append(Wt[name])
+                setattr(w, field, ptr(Wt[name]))
+        if lora_a is not None:
+            la, lb = lora_a.contiguous(), lora_b.contiguous()
+            keep += [la, lb]
+            w.lora_a, w.lora_b = ptr(la), ptr(lb)
+        return cfg, w, keep
+
+    @staticmethod
+    def _forward_call(blk, x, enc, mod, rope_cos, rope_sin, lora_a, lora_b, out):
+        B, S, _ = x.shape
+        cfg, w, keep = _WanLoRABlockNativeFunction._args(blk, B, S, enc.shape[1], lora_a, lora_b, backward=False)
+        lib = _lib.load()
+        saved = torch.empty(lib.ftmi_wan_lora_block_saved_bytes(ctypes.byref(cfg)), dtype=torch.uint8, device=x.device)
+        scratch = _native_scratch(x.device, lib.ftmi_wan_lora_block_scratch_bytes(ctypes.byref(cfg)))
+        check(lib.ftmi_wan_lora_block_forward(ctypes.byref(cfg), ctypes.byref(w), ptr(x), ptr(enc), ptr(mod), ptr(rope_cos), ptr(rope_sin), ptr(out), ptr(saved),
+                                              saved.numel(), ptr(scratch), scratch.numel(), stream_ptr()), "ftmi_wan_lora_block_forward")
+        return saved
+
+    @staticmethod
+    def forward(ctx, blk: "MI355XWanBlock", x, enc, temb, rope_cos, rope_sin, lora_a, lora_b):
+        mod = (blk.param("scale_shift_table").float() + temb.float()).contiguous()
+        out = torch.empty_like(x)
+        saved = _WanLoRABlockNativeFunction._forward_call(blk, x, enc, mod, rope_cos, rope_sin, lora_a, lora_b, out)
+        ctx.blk, ctx.rope, ctx.has_lora = blk, (rope_cos, rope_sin), lora_a is not None
+        ctx.recompute = bool(blk.gradient_checkpointing)
+        la, lb = (lora_a, lora_b) if lora_a is not None else (x.new_empty(0), x.new_empty(0))
+        if ctx.recompute:
+            ctx.save_for_backward(x, enc, mod, la, lb)
+        else:
+            ctx.save_for_backward(x, enc, mod, la, lb, saved)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        blk, rope = ctx.blk, ctx.rope
+        if ctx.recompute:
+            x, enc, mod, lora_a, lora_b = ctx.saved_tensors
+        else:
+            x, enc, mod, lora_a, lora_b, saved = ctx.saved_tensors
+        if not ctx.has_lora:
+            lora_a = lora_b = None
+        if ctx.recompute:
+            saved = _WanLoRABlockNativeFunction._forward_call(blk, x, enc, mod, rope[0], rope[1], lora_a, lora_b, None)
+        B, S, _ = x.shape
+        dout = dout.contiguous()
+        own, ga, gb = _grad_targets(blk, lora_a, lora_b)
+        cfg, w, keep = _WanLoRABlockNativeFunction._args(blk, B, S, enc.shape[1], lora_a, lora_b, backward=True)
+        lib = _lib.load()
+        scratch = _native_scratch(x.device, lib.ftmi_wan_lora_block_scratch_bytes(ctypes.byref(cfg)))
+        dx = torch.empty_like(x)
+        denc = torch.empty_like(enc) if ctx.needs_input_grad[2] else None  # frozen text embedder: no gradient into the text rows, its GEMM is skipped
+        check(lib.ftmi_wan_lora_block_backward(ctypes.byref(cfg), ctypes.byref(w), ptr(x), ptr(enc), ptr(mod), ptr(rope[0]), ptr(rope[1]), ptr(dout), ptr(dx),
+                                               ptr(denc), ptr(ga), ptr(gb), ptr(saved), saved.numel(), ptr(scratch), scratch.numel(), stream_ptr()),
+              "ftmi_wan_lora_block_backward")
+        if own:
+            blk._backward_done()
+            ga = gb = None
+        return None, dx, denc, None, None, None, ga, gb
+
+
 class MI355XWanBlock(nn.Module):
     """Holds the block's flat bf16 parameters and flat fp32 gradients; ``forward(hidden_states, encoder_hidden_states, temb, rotary)`` like the
     reference block, ``temb`` = the [B, 6, D] time projection, ``rotary`` = (cos, sin) fp32 [S, head_dim / 2]."""
@@ -270,6 +507,14 @@ class MI355XWanBlock(nn.Module):
         self._pre_forward = None   # callable(block) before the block's forward / backward: sharded training gathers the parameters there
         self._pre_backward = None
         self._param_src: Optional[torch.Tensor] = None  # sharded training: the all-gathered parameters to compute with instead of ``flat``
+        # LoRA over a frozen base (add_adapter): fp32 adapters on the eight attention projections, LORA_TARGETS order, ranks zero-padded to multiples of 64
+        self.frozen = False
+        self.lora_A: Optional[nn.Parameter] = None  # [8, r, D]
+        self.lora_B: Optional[nn.Parameter] = None  # [8, D, r]
+        self.lora_scale, self.lora_rank_user = 0.0, 0
+        self.gradient_checkpointing = False  # True: the block keeps only its input and refills its saved activations inside the backward
+        self._grad_a_view: Optional[torch.Tensor] = None  # the step object's flat gradient views (wan/trainer.py MI355XWanLoRAStep): added to in place
+        self._grad_b_view: Optional[torch.Tensor] = None
 
     # -- parameter / gradient views -----------------------------------------------------------------------------------------------------------
     def _params(self) -> torch.Tensor:
@@ -312,6 +557,29 @@ class MI355XWanBlock(nn.Module):
         """The parameters were changed in place by the library (optimiser kernel, all-gather into the same buffer): drop the cached transposes."""
         self._epoch += 1
 
+    # -- LoRA -----------------------------------------------------------------------------------------------------------------------------------
+    def freeze_base(self) -> None:
+        """Run the block with frozen base weights (input gradients only); ``add_adapter`` implies it."""
+        self.frozen = True
+
+    def add_adapter(self, rank: int = 32, lora_alpha: float = 32.0) -> None:
+        """peft ``LoraConfig(r, lora_alpha, init_lora_weights=True)`` on the eight attention projections: A kaiming-uniform(a = sqrt(5)), B zero.  Ranks that
+        are not multiples of 64 are stored zero-padded; the padding stays zero (a padded row of A only receives gradient through the matching zero column
+        of B and the other way round, and AdamW moves a zero parameter with zero gradient nowhere)."""
+        if rank <= 0 or rank > 128:
+            raise ValueError(f"LoRA rank must lie in 1..128, got {rank}")
+        rp = -(-int(rank) // 64) * 64
+        dev, D = self.flat.device, self.dim
+        a = torch.zeros(8, rp, D, dtype=torch.float32, device=dev)
+        a[:, :rank].uniform_(-(1.0 / D) ** 0.5, (1.0 / D) ** 0.5)  # kaiming_uniform_(a = sqrt(5)) on [r, D]: bound = 1 / sqrt(fan_in)
+        self.lora_A, self.lora_B = nn.Parameter(a), nn.Parameter(torch.zeros(8, D, rp, dtype=torch.float32, device=dev))
+        self.lora_rank_user, self.lora_scale = int(rank), float(lora_alpha) / rank
+        self.frozen = True
+
+    def _backward_done(self) -> None:
+        if self._grad_hook is not None:
+            self._grad_hook(self)  # this block's adapter gradients are final: the step object may start their all-reduce
+
     # -- loading --------------------------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def load_diffusers_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
@@ -331,5 +599,8 @@ class MI355XWanBlock(nn.Module):
     def forward(self, hidden_states: torch.Tensor, encoder_hidden_states: torch.Tensor, temb: torch.Tensor, rotary) -> torch.Tensor:
         if self._pre_forward is not None:
             self._pre_forward(self)
+        if self.frozen:
+            fn = _WanLoRABlockNativeFunction if self.native else _WanLoRABlockFunction
+            return fn.apply(self, hidden_states.contiguous(), encoder_hidden_states.contiguous(), temb.contiguous(), rotary[0], rotary[1], self.lora_A, self.lora_B)
         fn = _WanBlockNativeFunction if self.native else _WanBlockFunction
         return fn.apply(self, hidden_states.contiguous(), encoder_hidden_states.contiguous(), temb.contiguous(), rotary[0], rotary[1])

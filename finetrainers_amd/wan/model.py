@@ -19,7 +19,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..cogvideox.model import timestep_embedding
-from .block import MI355XWanBlock
+from .block import LORA_TARGETS, MI355XWanBlock
 
 bf16 = torch.bfloat16
 
@@ -147,6 +147,19 @@ def _dgelu(dy: torch.Tensor, pre: torch.Tensor) -> torch.Tensor:
     return (dy.float() * dg).to(bf16)
 
 
+class _FrozenLinearFunction(torch.autograd.Function):
+    """y = x W^T + b over FROZEN W, b (LoRA training: the root's output projection): input gradient only, against a cached K-contiguous twin of W."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, w_t):
+        ctx.w_t, ctx.xshape = w_t, x.shape
+        return ops.gemm_nt(x.reshape(-1, x.shape[-1]), w, b).view(*x.shape[:-1], w.shape[0])
+
+    @staticmethod
+    def backward(ctx, dy):
+        return ops.gemm_nt(dy.reshape(-1, dy.shape[-1]).contiguous(), ctx.w_t, None).view(ctx.xshape), None, None, None
+
+
 class _LnModFunction(torch.autograd.Function):
     """y = bf(LN(float(x)) * (1 + scale_b) + shift_b) with fp32 [B, D] shift / scale (the output norm); returns gradients for x, shift and scale."""
 
@@ -163,6 +176,8 @@ class _LnModFunction(torch.autograd.Function):
     def backward(ctx, dy):
         x, scale = ctx.saved_tensors
         B, S, D = x.shape
+        if not (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):  # frozen modulation (LoRA training): no reductions
+            return ops.wan_ln_bwd(x.view(B * S, D), dy.contiguous().view(B * S, D), S, scale=scale, eps=ctx.eps).view(B, S, D), None, None, None
         red = torch.zeros((2, B, D), dtype=torch.float32, device=x.device)
         dx = ops.wan_ln_bwd(x.view(B * S, D), dy.contiguous().view(B * S, D), S, scale=scale, eps=ctx.eps, red1=red[0], red2=red[1], red_per_batch=True)
         return dx.view(B, S, D), red[0], red[1], None
@@ -182,6 +197,8 @@ class MI355XWanTransformer3DModel(nn.Module):
         self.blocks = nn.ModuleList([MI355XWanBlock(c.inner_dim, c.num_attention_heads, c.ffn_dim, c.eps, dev) for _ in range(c.num_layers)])
         self._rope_cache: Dict[Tuple[int, int, int], Tuple[torch.Tensor, torch.Tensor]] = {}
         self._anchor = torch.zeros(1, dtype=bf16, device=dev, requires_grad=True)  # tells autograd that the graph has trainable inputs
+        self.lora_config: Optional[Dict[str, object]] = None  # set by add_adapter: {"r", "lora_alpha", "target_modules"}
+        self._proj_out_t: Optional[torch.Tensor] = None       # LoRA training: the frozen output projection's K-contiguous twin
 
     @property
     def device(self) -> torch.device:
@@ -233,6 +250,104 @@ class MI355XWanTransformer3DModel(nn.Module):
         """(name, parameter buffer, gradient buffer) of the shardable units: root first, then the blocks."""
         return [("root", self.root.data, self.root_grad)] + [(f"blocks.{i}", b.flat.data, b.grad_flat) for i, b in enumerate(self.blocks)]
 
+    # -- LoRA over the frozen base ------------------------------------------------------------------------------------------------------------
+    # the spellings of "to_q, to_k, to_v, to_out.0 of every attention of every block" the reference's recipes and its default use
+    _LORA_PATTERNS = ("blocks.*(to_q|to_k|to_v|to_out.0)", ["to_q", "to_k", "to_v", "to_out.0"], ("to_q", "to_k", "to_v", "to_out.0"))
+
+    def add_adapter(self, rank: int = 32, lora_alpha: float = 32.0, target_modules="blocks.*(to_q|to_k|to_v|to_out.0)") -> None:
+        """``--training_type lora --rank R --lora_alpha A --target_modules "blocks.*(to_q|to_k|to_v|to_out.0)"`` (the reference's Wan SFT recipes): fp32
+        adapters on the eight attention projections of every block (attn1 AND attn2: the regex matches both), base frozen.  Any other selection raises:
+        a silently different adapter set is impossible."""
+        tm = list(target_modules) if isinstance(target_modules, tuple) else target_modules
+        if tm not in [list(p) if isinstance(p, tuple) else p for p in self._LORA_PATTERNS]:
+            raise NotImplementedError(f"target_modules {target_modules!r}: this backend places adapters on exactly to_q / to_k / to_v / to_out.0 of both "
+                                      "attentions of every block (\"blocks.*(to_q|to_k|to_v|to_out.0)\")")
+        for blk in self.blocks:
+            blk.add_adapter(rank, lora_alpha)
+        self.lora_config = {"r": int(rank), "lora_alpha": lora_alpha, "target_modules": target_modules}
+
+    def lora_parameters(self) -> List[nn.Parameter]:
+        return [p for blk in self.blocks for p in (blk.lora_A, blk.lora_B) if p is not None]
+
+    def lora_state_dict(self) -> Dict[str, torch.Tensor]:
+        """peft / diffusers keys ``blocks.{i}.attn{1,2}.to_{q,k,v}.lora_{A,B}.weight`` and ``blocks.{i}.attn{1,2}.to_out.0.lora_{A,B}.weight``: views of the
+        user's rank inside the zero-padded storage, [r, D] / [D, r]."""
+        out = {}
+        for i, blk in enumerate(self.blocks):
+            if blk.lora_A is None:
+                continue
+            r = blk.lora_rank_user
+            for j, n in enumerate(LORA_TARGETS):
+                out[f"blocks.{i}.{n}.lora_A.weight"] = blk.lora_A.data[j, :r]
+                out[f"blocks.{i}.{n}.lora_B.weight"] = blk.lora_B.data[j, :, :r]
+        return out
+
+    def lora_grad_state_dict(self) -> Dict[str, torch.Tensor]:
+        """The adapters' gradients under the same keys (after a backward): the step object's flat views, or ``.grad``."""
+        out = {}
+        for i, blk in enumerate(self.blocks):
+            r = blk.lora_rank_user
+            ga = blk._grad_a_view if blk._grad_a_view is not None else blk.lora_A.grad
+            gb = blk._grad_b_view if blk._grad_b_view is not None else blk.lora_B.grad
+            for j, n in enumerate(LORA_TARGETS):
+                out[f"blocks.{i}.{n}.lora_A.weight"] = ga[j, :r]
+                out[f"blocks.{i}.{n}.lora_B.weight"] = gb[j, :, :r]
+        return out
+
+    @torch.no_grad()
+    def load_lora_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
+        sd = {k.replace(".default.", "."): v for k, v in sd.items()}
+        mine = self.lora_state_dict()
+        missing, extra = sorted(set(mine) - set(sd)), sorted(set(sd) - set(mine))
+        if missing or extra:
+            raise KeyError(f"LoRA state dict does not match the attached adapters: missing {missing[:3]}, unexpected {extra[:3]}")
+        for k, v in mine.items():
+            if tuple(sd[k].shape) != tuple(v.shape):
+                raise ValueError(f"{k}: expected shape {tuple(v.shape)}, got {tuple(sd[k].shape)}")
+            v.copy_(sd[k].to(v))
+
+    def apply_activation_checkpointing(self, checkpointing_type: str = "full", n_layer: int = 1) -> "MI355XWanTransformer3DModel":
+        """``--gradient_checkpointing`` (utils/activation_checkpoint.py:24-49) for LoRA training: every block ("block_skip": every ``n_layer``-th) keeps
+        only its input and refills its saved activations inside the backward with the identical kernel sequence."""
+        if checkpointing_type not in ("full", "block_skip"):
+            raise ValueError(f"Checkpointing type '{checkpointing_type}' not supported. Supported types are ['full', 'block_skip']")
+        if self.lora_config is None:
+            raise NotImplementedError("activation checkpointing covers LoRA training (add_adapter first); the full fine-tune keeps its activations")
+        for i, blk in enumerate(self.blocks):
+            blk.gradient_checkpointing = checkpointing_type == "full" or i % max(1, int(n_layer)) == 0
+        return self
+
+    def _forward_frozen_root(self, hidden_states, timestep, encoder_hidden_states, return_dict: bool):
+        """The forward with adapters attached: patch embedding, condition embedder and head run FROZEN (plain launches of the same GEMMs: same bits as the
+        full fine-tune's forward); the only graph autograd sees is blocks -> output norm -> output projection, which hands d x back to the last block."""
+        c = self.config
+        B, C, F_, H, W = hidden_states.shape
+        pt, ph, pw = c.patch_size
+        f, h, w = F_ // pt, H // ph, W // pw
+        S = f * h * w
+        rope = self._rope(F_, H, W)
+        lin = lambda t, name, **kw: ops.gemm_nt(t.reshape(-1, t.shape[-1]), self.rparam(f"{name}.weight"), self.rparam(f"{name}.bias"), **kw)
+        silu = torch.nn.functional.silu
+        with torch.no_grad():
+            cols = hidden_states.to(bf16).view(B, C, f, pt, h, ph, w, pw).permute(0, 2, 4, 6, 1, 3, 5, 7).reshape(B, S, C * pt * ph * pw)
+            x = lin(cols, "patch_embedding").view(B, S, -1)
+            t_emb = timestep_embedding(timestep.to(self.device), c.freq_dim).to(bf16)
+            temb = lin(silu(lin(t_emb, "condition_embedder.time_embedder.linear_1")), "condition_embedder.time_embedder.linear_2")
+            tproj = lin(silu(temb), "condition_embedder.time_proj").unflatten(1, (6, -1))
+            text = encoder_hidden_states.to(bf16)
+            act, _ = lin(text, "condition_embedder.text_embedder.linear_1", epilogue=1, want_out2=True)  # (the full fine-tune's launch, pre-activation and all)
+            enc = lin(act, "condition_embedder.text_embedder.linear_2").view(B, text.shape[1], -1)
+            mod = self.rparam("scale_shift_table") + temb.unsqueeze(1)  # [B, 2, D] bf16
+            shift, scale = mod[:, 0].float(), (1 + mod[:, 1]).float() - 1
+        for blk in self.blocks:
+            x = blk(x, enc, tproj, rope)
+        y = _LnModFunction.apply(x, shift, scale, c.eps)
+        if self._proj_out_t is None:
+            self._proj_out_t = ops.transpose_bf16(self.rparam("proj_out.weight"))
+        y = _FrozenLinearFunction.apply(y, self.rparam("proj_out.weight"), self.rparam("proj_out.bias"), self._proj_out_t)
+        out = y.reshape(B, f, h, w, pt, ph, pw, -1).permute(0, 7, 1, 4, 2, 5, 3, 6).reshape(B, -1, F_, H, W)
+        return {"sample": out} if return_dict else (out,)
+
     # -- forward ------------------------------------------------------------------------------------------------------------------------------
     def _rope(self, frames: int, height: int, width: int):
         key = (frames, height, width)
@@ -249,6 +364,8 @@ class MI355XWanTransformer3DModel(nn.Module):
     def forward(self, hidden_states, timestep, encoder_hidden_states, encoder_hidden_states_image=None, return_dict: bool = False, **kwargs):
         if encoder_hidden_states_image is not None:
             raise NotImplementedError("the image-to-video branch is not part of this path")
+        if self.lora_config is not None:
+            return self._forward_frozen_root(hidden_states, timestep, encoder_hidden_states, return_dict)
         c = self.config
         B, C, F_, H, W = hidden_states.shape
         pt, ph, pw = c.patch_size

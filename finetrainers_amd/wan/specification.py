@@ -163,6 +163,22 @@ class MI355XWanModelSpecification(MI355XWanSpecOps):
             with open(os.path.join(directory, "scheduler", "scheduler_config.json"), "w") as f:
                 json.dump({"_class_name": "FlowMatchEulerDiscreteScheduler", "num_train_timesteps": 1000, "shift": 1.0}, f, indent=2)
 
+    def _save_lora_weights(self, directory: str, transformer_state_dict: Optional[Dict[str, torch.Tensor]] = None, scheduler=None,
+                           metadata: Optional[Dict[str, str]] = None, *args, **kwargs) -> None:
+        """base_specification.py:531-550: ``pytorch_lora_weights.safetensors`` (``transformer.``-prefixed peft keys + the ``lora_config`` metadata of
+        ``wire.lora_config_metadata``) and the scheduler config; ``wire.load_lora_weights`` reads it back for ``load_lora_state_dict``."""
+        import json
+        import os
+
+        from .. import wire
+
+        if transformer_state_dict is not None:
+            wire.save_lora_weights(directory, transformer_state_dict, metadata)
+        if scheduler is not None:
+            os.makedirs(os.path.join(directory, "scheduler"), exist_ok=True)
+            with open(os.path.join(directory, "scheduler", "scheduler_config.json"), "w") as f:
+                json.dump({"_class_name": "FlowMatchEulerDiscreteScheduler", "num_train_timesteps": 1000, "shift": 1.0}, f, indent=2)
+
 
 # The public class: these overrides on top of the reference's own WanModelSpecification when finetrainers is importable (prepare_conditions,
 # prepare_latents, load_condition_models, load_latent_models, load_pipeline, validation are then inherited), on StandaloneModelSpecification otherwise

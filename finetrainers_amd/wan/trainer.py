@@ -1,14 +1,17 @@
-"""One Wan-T2V FULL fine-tune optimisation step (BASELINE config 4; reference loop: finetrainers/trainer/sft_trainer/trainer.py:430-503 with
+"""``MI355XWanFullFinetuneStep``: one Wan-T2V FULL fine-tune optimisation step (BASELINE config 4; reference loop: finetrainers/trainer/sft_trainer/trainer.py:430-503 with
 ``--training_type full-finetune`` and FSDP-2, :171-181): posterior sample + flow-match noising -> DiT forward -> MSE -> backward producing every parameter
 gradient -> fp32 reduce-scatter of each unit's gradient to its owners -> global-norm clip over the shards -> AdamW on the bf16 shards.
 
 Parameters are sharded over the data-parallel ranks unit by unit (wan/fsdp.py): the blocks gather their parameters right before they compute, the next
 block's all-gather and the previous block's reduce-scatter run on RCCL's stream meanwhile.  On one GPU the same code runs with whole "shards" and no
-collectives."""
+collectives.
+
+``MI355XWanLoRAStep`` (below): the LoRA step of the reference's Wan SFT recipes (``--training_type lora``, DDP) over the frozen base -- 8 x 30 small fp32
+adapters in one flat buffer, no parameter sharder."""
 
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Dict, List, Optional, Tuple
 
 import torch
 import torch.distributed as dist
@@ -153,3 +156,138 @@ class MI355XWanFullFinetuneStep:
             out[u.name] = sh.acquire(i).clone()
             sh.release_all()
         return out
+
+
+class MI355XWanLoRAStep:
+    """One Wan-T2V LoRA SFT optimisation step (reference loop: trainer/sft_trainer/trainer.py:430-503 with ``--training_type lora`` and DDP): posterior
+    sample + flow-match noising -> DiT forward over the frozen base -> MSE -> backward producing dx and the adapter gradients only -> average of the
+    adapter gradients over the data-parallel ranks -> global-norm clip -> AdamW, the last two fused over ONE flat fp32 buffer the blocks' adapter
+    Parameters are views of.  The gradients live in a second flat buffer of the same layout: every block's backward adds into its two views, and under data
+    parallelism every ``grad_bucket_blocks`` finished blocks -- one contiguous slice, the backward walks the buffer from its end -- are all-reduced
+    asynchronously while the earlier blocks still compute.  With gradient accumulation the buffer is kept over the window's micro-steps (each backward
+    scaled by 1 / steps) and only the last one exchanges, clips and steps (DDP's no_sync + trainer.py:498)."""
+
+    def __init__(self, transformer: MI355XWanTransformer3DModel, spec: Optional[MI355XWanSpecOps] = None, lr: float = 1e-4, betas=(0.9, 0.95),
+                 eps: float = 1e-8, weight_decay: float = 1e-4, max_grad_norm: float = 1.0, parallel=None, generator: Optional[torch.Generator] = None,
+                 lr_scheduler=None, gradient_accumulation_steps: int = 1, grad_bucket_blocks: int = 8):
+        if gradient_accumulation_steps < 1:
+            raise ValueError("gradient_accumulation_steps must be >= 1")
+        self.params = transformer.lora_parameters()
+        if not self.params:
+            raise ValueError("attach a LoRA adapter first (transformer.add_adapter)")
+        self.gradient_accumulation_steps, self._micro_step = gradient_accumulation_steps, 0
+        self.transformer, self.spec = transformer, spec or MI355XWanSpecOps()
+        self.lr, self.betas, self.eps, self.weight_decay, self.max_grad_norm = lr, betas, eps, weight_decay, max_grad_norm
+        self.parallel, self.generator, self.lr_scheduler = parallel, generator, lr_scheduler
+        dev = transformer.device
+        self.flat = torch.cat([p.detach().reshape(-1) for p in self.params]).contiguous()
+        off = 0
+        for p in self.params:  # the adapters now live in one buffer: one fused clip + AdamW launch covers all 240 of them
+            n = p.numel()
+            p.data = self.flat[off:off + n].view(p.shape)
+            off += n
+        if parallel is not None and parallel.active:  # replicas start from rank 0's adapters (DDP broadcasts at construction)
+            parallel.broadcast_(self.flat, src=0)
+        self.gflat = torch.zeros_like(self.flat)
+        self.grad_bucket_blocks = max(1, int(grad_bucket_blocks))
+        self._spans: Dict[int, Tuple[int, int]] = {}
+        off = 0
+        for blk in transformer.blocks:
+            na, nb = blk.lora_A.numel(), blk.lora_B.numel()
+            blk._grad_a_view = self.gflat[off:off + na].view(blk.lora_A.shape)
+            blk._grad_b_view = self.gflat[off + na:off + na + nb].view(blk.lora_B.shape)
+            self._spans[id(blk)] = (off, off + na + nb)
+            off += na + nb
+        assert off == self.flat.numel()
+        self.buckets_issued = 0
+        self.bucket_log: List[Tuple[int, int]] = []  # (lo, hi) element slices of the last exchange, in issue order
+        self._pending, self._ready = [], []
+        self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
+        self._scratch = torch.zeros(ops.CLIP_SCRATCH_FLOATS, dtype=torch.float32, device=dev)
+        self.step_count = 0
+
+    # ---- the bucketed exchange (driven by the blocks' backward through ``_grad_hook``) ------------------------------------------------------------
+    def _begin_exchange(self, exchange: bool) -> None:
+        self._pending, self._ready, self.bucket_log = [], [], []
+        for blk in self.transformer.blocks:
+            blk._grad_hook = self._block_done if exchange else None
+
+    def _flush(self) -> None:
+        lo, hi = min(s_[0] for s_ in self._ready), max(s_[1] for s_ in self._ready)
+        assert hi - lo == sum(s_[1] - s_[0] for s_ in self._ready), "finished blocks must form one contiguous slice of the flat gradient"
+        h = self.parallel.all_reduce_mean_async(self.gflat[lo:hi])
+        if h is not None:
+            self._pending.append(h)
+        self.bucket_log.append((lo, hi))
+        self._ready.clear()
+
+    def _block_done(self, blk) -> None:
+        """A block's adapter gradients are final (last block first): every rank issues the same bucket sequence."""
+        span = self._spans[id(blk)]
+        self._ready.append(span)
+        if len(self._ready) >= self.grad_bucket_blocks or span[0] == 0:
+            self._flush()
+
+    def _finish_exchange(self, failed: bool = False) -> None:
+        for blk in self.transformer.blocks:
+            blk._grad_hook = None
+        if failed:
+            # a backward that raised after issuing some buckets: every rank issued the same collectives, so they complete -- wait for them and drop
+            # the handles (the next step must not race the collective's stream on the gradient buffer, nor divide a tensor twice)
+            for work, _ in self._pending:
+                try:
+                    work.wait()
+                except Exception:
+                    pass
+            self._pending, self._ready = [], []
+            return
+        if self._ready:
+            self._flush()
+        for work, div in self._pending:  # device-side wait on RCCL; gloo: host wait + divide
+            work.wait()
+            if div is not None:
+                div.div_(self.parallel.world_size)
+        self.buckets_issued = len(self._pending)
+        self._pending = []
+
+    # ---- the step ---------------------------------------------------------------------------------------------------------------------------------
+    def step(self, moments: torch.Tensor, encoder_hidden_states: torch.Tensor, latents_mean: torch.Tensor, latents_std: torch.Tensor,
+             sigmas: torch.Tensor, posterior_noise: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        pred, target, _ = self.spec.forward(self.transformer, moments, encoder_hidden_states, sigmas, latents_mean, latents_std, posterior_noise=posterior_noise,
+                                            noise=noise, generator=self.generator)
+        gas = self.gradient_accumulation_steps
+        if self._micro_step % gas == 0:
+            self.gflat.zero_()  # a new accumulation window
+        self._micro_step += 1
+        sync = self._micro_step % gas == 0  # last micro-step of the window: exchange, clip, optimiser step
+        dp = self.parallel is not None and self.parallel.active
+        self._begin_exchange(dp and sync)
+        try:
+            loss = self.spec.loss_backward(pred, target, grad_scale=1.0 / gas)
+        except BaseException:
+            self._finish_exchange(failed=True)
+            raise
+        self._finish_exchange()
+        gn = torch.empty(1, dtype=torch.float32, device=self.gflat.device)
+        if sync:
+            self.step_count += 1
+            lr = self.lr if self.lr_scheduler is None else self.lr_scheduler.current_lr()
+            ops.clip_adamw_step(self.flat, self.gflat, self.exp_avg, self.exp_avg_sq, self.step_count, lr, self.betas, self.eps, self.weight_decay,
+                                self.max_grad_norm, scratch=self._scratch, grad_norm_out=gn)
+            if self.lr_scheduler is not None:
+                self.lr_scheduler.step()
+        else:  # report the norm of what has accumulated so far; the window's clip happens with its optimiser step
+            gn.copy_(ops.grad_sumsq(self.gflat, self._scratch).sqrt())
+        return {"loss": loss.detach(), "grad_norm": gn}
+
+    def state_dict(self) -> Dict[str, object]:
+        """Optimiser state and counters; the adapters themselves are ``transformer.lora_state_dict()``."""
+        return {"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq, "step": self.step_count, "micro_step": self._micro_step,
+                "lr_scheduler": None if self.lr_scheduler is None else self.lr_scheduler.state_dict()}
+
+    def load_state_dict(self, sd: Dict[str, object]) -> None:
+        self.exp_avg.copy_(sd["exp_avg"])
+        self.exp_avg_sq.copy_(sd["exp_avg_sq"])
+        self.step_count, self._micro_step = int(sd["step"]), int(sd.get("micro_step", 0))
+        if self.lr_scheduler is not None and sd.get("lr_scheduler") is not None:
+            self.lr_scheduler.load_state_dict(sd["lr_scheduler"])

@@ -617,7 +617,8 @@ int ftmi_hy_dual_backward(const ftmi_hy_dual_config* cfg, const ftmi_hy_dual_wei
  *                          [rows_per_batch, head_dim / 2], the complex pair (2k, 2k+1) of every head times cos_k + i sin_k); rope null: y = n
  *   ftmi_wan_rms_rope_bwd  y = dx;  red2 += sum dn * xhat (d weight)
  *   ftmi_wan_gate_res_fwd  y = bf(float(x) + float(dy) * scale_b)   ("dy" = the branch output; scale = fp32 gate [B, D], null: bf(x + dy))
- *   ftmi_wan_gate_res_bwd  x = d out, dy = the branch output of the forward: y = bf(d out * scale_b), red1 += sum d out * branch (d gate)
+ *   ftmi_wan_gate_res_bwd  x = d out, dy = the branch output of the forward: y = bf(d out * scale_b), red1 += sum d out * branch (d gate);
+ *                          red1 NULL (a frozen gate): dy is not read and may be NULL
  *   ftmi_wan_colsum        red1 += sum over rows of x   (Linear bias gradients) */
 typedef struct ftmi_wan_row_args {
     const void* x; long ld_x;
@@ -661,6 +662,39 @@ int ftmi_wan_block_forward(const ftmi_wan_block_config* cfg, const void* params,
 int ftmi_wan_block_backward(const ftmi_wan_block_config* cfg, const void* params, float* grads, const void* x, const void* enc, const float* mod,
                             const float* rope_cos, const float* rope_sin, const void* dout, void* dx, void* denc, float* dmod, void* saved, size_t saved_bytes,
                             void* scratch, size_t scratch_bytes, ftmi_stream stream);
+
+/* The same block for LoRA fine-tuning (the reference's Wan SFT recipes: --training_type lora --target_modules "blocks.*(to_q|to_k|to_v|to_out.0)"): the
+ * base weights are frozen; fp32 adapters lora_a [8, r, D] / lora_b [8, D, r] sit on attn1.to_q, to_k, to_v, to_out.0, attn2.to_q, to_k, to_v, to_out.0
+ * (in this order) and every projection computes x W^T + b + lora_scale (x A^T) B^T.  The configuration is ftmi_wan_block_config plus r and lora_scale.
+ * params: the flat bf16 buffer as above; w_*_t: K-contiguous (transposed) twins of the seven weight matrices, backward only -- [D, 3D] of attn1 q|k|v,
+ * [D, D] of attn1.to_out.0, attn2.to_q, [D, 2D] of attn2 k|v, [D, D] of attn2.to_out.0, [D, F] of ffn.net.0.proj, [F, D] of ffn.net.2.
+ * `saved` (ftmi_wan_lora_block_saved_bytes; smaller than the full fine-tune's by B S (3D + F) 2 bytes, larger by the down-projected rows) lives from the
+ * forward to the backward of the block, or is rebuilt inside the backward by calling the forward with out = NULL (gradient checkpointing);
+ * `scratch` (ftmi_wan_lora_block_scratch_bytes, both directions) may be shared by all blocks of a stream.  With r = 0 the forward's output and the backward's
+ * dx are those of ftmi_wan_block_forward / _backward, bit for bit.  The backward writes dx, writes denc unless it is NULL (frozen text embedder: that
+ * GEMM is skipped) and ADDS to grad_a [8, r, D] / grad_b [8, D, r] (fp32); no base-weight, norm, bias or modulation gradient is formed. */
+typedef struct {
+    int B, S, T;      /* batch, video tokens, text tokens */
+    int D, H, F;      /* width = H x 128, feed-forward width */
+    float eps;        /* 1e-6 */
+    int gemm_variant; /* 8 */
+    int r;            /* LoRA rank: 0, 64 or 128 (other ranks zero-padded by the caller) */
+    float lora_scale; /* alpha / (the user's) r */
+} ftmi_wan_lora_block_config;
+typedef struct {
+    const void* params;                                                          /* flat bf16, WanBlockLayout order */
+    const void *w_qkv1_t, *w_o1_t, *w_q2_t, *w_kv2_t, *w_o2_t, *w_f1_t, *w_f2_t; /* transposed twins: backward only */
+    const float *lora_a, *lora_b;                                                /* fp32 [8, r, D], [8, D, r]; NULL when r == 0 */
+} ftmi_wan_lora_block_weights;
+size_t ftmi_wan_lora_block_saved_bytes(const ftmi_wan_lora_block_config* cfg);
+size_t ftmi_wan_lora_block_scratch_bytes(const ftmi_wan_lora_block_config* cfg);
+/* out [B, S, D]; out == NULL: recomputation pass (refills `saved` with the identical kernel sequence) */
+int ftmi_wan_lora_block_forward(const ftmi_wan_lora_block_config* cfg, const ftmi_wan_lora_block_weights* w, const void* x, const void* enc, const float* mod,
+                                const float* rope_cos, const float* rope_sin, void* out, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
+                                ftmi_stream stream);
+int ftmi_wan_lora_block_backward(const ftmi_wan_lora_block_config* cfg, const ftmi_wan_lora_block_weights* w, const void* x, const void* enc, const float* mod,
+                                 const float* rope_cos, const float* rope_sin, const void* dout, void* dx, void* denc, float* grad_a, float* grad_b, void* saved,
+                                 size_t saved_bytes, void* scratch, size_t scratch_bytes, ftmi_stream stream);
 
 /* Sum of squares of a flat fp32 gradient (shard): scratch[0] <- sum g^2 (order-fixed; scratch >= FTMI_CLIP_SCRATCH_FLOATS floats).  Sharded training
  * all-reduces scratch[0] over the ranks before the optimiser call below (the reference's clip_grad_norm_ over DTensor shards, utils/torch.py:99-161). */

@@ -1,4 +1,5 @@
-"""The four workloads `bench.py --workload {ltx,cogvideox,wan,hunyuan}` can time (BASELINE.json configs[1], [2], [3], [4]): for each one a
+"""The workloads `bench.py --workload {ltx,cogvideox,wan,hunyuan}` can time (BASELINE.json configs[1], [2], [3], [4]), plus the Wan LoRA recipe
+(`wan_lora`, run through this file's own command line: `python tools/bench_workloads.py --workload wan_lora`): for each one a
 builder that puts a random-init model of the named architecture, its step object and one synthetic batch of the named clip shape on the GPU
 and returns the step closure + the static part of the JSON line, and a `cpu_baseline` that times the oracle (CPU restatement of the reference
 path, kind "port") on a bounded sample of the same workload.  Bench infrastructure: the only place outside tests/ and __graft_entry__.smoke()
@@ -174,6 +175,64 @@ def cpu_baseline_wan(args, layers: int) -> Dict[str, Any]:
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------------
+# Wan2.1-T2V-1.3B LoRA (the reference's Wan SFT recipes, examples/training/sft/wan/*/train.sh): rank 32 on to_q / to_k / to_v / to_out.0 of both
+# attentions, 49 x 480 x 832 -> latents [1, 16, 13, 60, 104], 20 280 video + 512 text tokens, 30 blocks, batch 1 per GPU, frozen base.
+# bench.py's --workload list is fixed: this row runs through this file's own command line (python tools/bench_workloads.py --workload wan_lora).
+# ------------------------------------------------------------------------------------------------------------------------------------------
+def build_wan_lora(args, par, dev) -> Dict[str, Any]:
+    from finetrainers_amd.wan import MI355XWanLoRAStep, MI355XWanTransformer3DModel, WanTransformerConfig
+
+    layers = args.layers if args.layers > 0 else 30
+    cfg = WanTransformerConfig(num_layers=layers)
+    model = MI355XWanTransformer3DModel(cfg, device=dev)
+    g = torch.Generator(device=dev).manual_seed(0)
+    D = cfg.inner_dim
+    with torch.no_grad():
+        for name, v in model.state_dict_views().items():
+            if name.endswith("weight") and v.dim() >= 2:
+                v.copy_((torch.randn(v.shape, generator=g, device=dev) / v.shape[-1] ** 0.5).to(bf16))
+            elif "norm" in name and name.endswith("weight"):
+                v.fill_(1.0)
+            elif "scale_shift_table" in name:
+                v.copy_((torch.randn(v.shape, generator=g, device=dev) / D ** 0.5).to(bf16))
+            else:
+                v.copy_((0.02 * torch.randn(v.shape, generator=g, device=dev)).to(bf16))
+    for blk in model.blocks:
+        blk.mark_updated()
+    model.add_adapter(args.rank, float(args.rank))
+    ckpt = bool(getattr(args, "gradient_checkpointing", False))
+    if ckpt:
+        model.apply_activation_checkpointing("full")
+    with torch.no_grad():
+        for p in model.lora_parameters()[1::2]:
+            p[:, :, :args.rank].normal_(0, 0.01, generator=g)  # B != 0 so every gradient path carries data
+    step = MI355XWanLoRAStep(model, lr=1e-4, generator=torch.Generator(device=dev).manual_seed(1 + par.rank), parallel=par if par.world_size > 1 else None)
+    g.manual_seed(100 + par.rank)
+    B, C, F_, H, W, T = 1, 16, 13, 60, 104, 512
+    moments = torch.randn((B, 2 * C, F_, H, W), generator=g, device=dev).to(bf16)
+    moments[:, C:] = (moments[:, C:].float() * 0.3 - 2.0).to(bf16)
+    text = torch.randn((B, T, cfg.text_dim), generator=g, device=dev).to(bf16)
+    mean, std = torch.zeros(C, device=dev), torch.ones(C, device=dev)
+    sig = torch.tensor([0.6], device=dev)
+    S, Fd = 13 * 30 * 52, cfg.ffn_dim
+    lin = 2.0 * S * (6 * D * D + 2 * D * Fd) + 2.0 * T * 2 * D * D
+    att = 4.0 * S * S * D + 4.0 * S * T * D
+    flop = layers * ((3.0 if ckpt else 2.0) * lin + (4.5 if ckpt else 3.5) * att)  # linears: forward + input gradient (no weight gradient); checkpointing: one more forward
+    return {
+        "one_step": lambda: step.step(moments, text, mean, std, sig),
+        "samples_per_step": 1,
+        "step_tflop": flop / 1e12,
+        "metric": "train samples/sec (+ step ms) Wan-T2V-1.3B LoRA 49x480x832 (the reference's Wan SFT recipes)",
+        "data": "synthetic posterior moments [1,32,13,60,104] + random text embeds [1,512,4096], random-init weights of the Wan2.1-T2V-1.3B DiT",
+        "config": {"workload": f"Wan-T2V-1.3B LoRA rank={args.rank} bf16 SFT step over the frozen base, 49x480x832 clip ({S} video + {T} text tokens), batch 1 per GPU, {layers} blocks"
+                               + ("" if layers == 30 else " -- REDUCED depth"),
+                   "model": "Wan2.1-T2V-1.3B DiT: 30 blocks, width 1536, 12 x 128 heads, frozen; 240 fp32 adapters", "seq_len": S,
+                   "activation_checkpointing": ckpt, "orchestration": ("one C call per block and direction (ftmi_wan_lora_block_forward / _backward)" if os.environ.get("FTMI_NATIVE_BLOCKS", "1") != "0" else "python, per kernel over the C ABI")},
+        "layers": layers,
+    }
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------------
 # HunyuanVideo LoRA, fp8 weight storage (configs[4]): 61 x 544 x 960 -> latents [1, 16, 16, 68, 120], 32 640 video + 256 text tokens,
 # 20 dual-stream + 40 single-stream blocks (12.8 B parameters), batch 1 per GPU
 # ------------------------------------------------------------------------------------------------------------------------------------------
@@ -279,4 +338,46 @@ def cpu_baseline_hunyuan(args, ctx) -> Dict[str, Any]:
 
 WORKLOADS = {"cogvideox": (build_cogvideox, lambda a, c: cpu_baseline_cogvideox(a, c["layers"])),
              "wan": (build_wan, lambda a, c: cpu_baseline_wan(a, c["layers"])),
+             "wan_lora": (build_wan_lora, lambda a, c: cpu_baseline_wan(a, c["layers"])),  # (yardstick on the host: the full fine-tune block, an upper bound of the LoRA block's work)
              "hunyuan": (build_hunyuan, cpu_baseline_hunyuan)}
+
+
+def main() -> None:
+    """One workload on one GPU, outside bench.py (whose --workload list is fixed): 1 JSON line with the builder's static part plus step_ms (median), every
+    step's ms, samples/s, achieved TFLOP/s and the peak allocated memory.  ``python tools/bench_workloads.py --workload wan_lora --steps 5 --warmup 1
+    [--gradient-checkpointing]``."""
+    import argparse
+    import json
+    import sys
+    import types
+
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workload", choices=sorted(WORKLOADS), default="wan_lora")
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--layers", type=int, default=0)
+    ap.add_argument("--rank", type=int, default=32)
+    ap.add_argument("--gradient-checkpointing", dest="gradient_checkpointing", action="store_true")
+    args = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    ctx = WORKLOADS[args.workload][0](args, types.SimpleNamespace(world_size=1, rank=0), dev)
+    one_step = ctx.pop("one_step")
+    ms = []
+    for it in range(args.warmup + args.steps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = one_step()
+        torch.cuda.synchronize()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    timed = sorted(ms[args.warmup:])
+    med = timed[len(timed) // 2]
+    ctx.pop("dual_single", None)
+    ctx.update(step_ms=med, steps_ms=ms, value=ctx["samples_per_step"] / (med / 1e3), unit="samples/s", achieved_tflops=ctx["step_tflop"] / (med / 1e3),
+               peak_memory_gb=torch.cuda.max_memory_allocated() / 1e9, loss=float(out["loss"]), grad_norm=float(out["grad_norm"]), gpus=1, steps=args.steps,
+               warmup=args.warmup)
+    print(json.dumps(ctx))
+
+
+if __name__ == "__main__":
+    main()
