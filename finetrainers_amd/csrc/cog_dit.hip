@@ -30,15 +30,6 @@ struct CogLayout {
     size_t s_act, s_f, s_big, s_d1, s_d2, s_d3, s_dq, s_dk, s_dh0, s_dh1, s_delta;
 };
 
-struct Bump {
-    size_t off = 0;
-    size_t take(size_t bytes) {
-        size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    }
-};
-
 CogLayout make_layout(const ftmi_cog_config& c) {
     CogLayout w;
     const size_t N = (size_t)c.T + c.S, M = (size_t)c.B * N, D = c.D, r = c.r > 0 ? c.r : 64, e2 = 2;
@@ -88,14 +79,6 @@ int check_cfg(const ftmi_cog_config& c) {
 }
 
 inline const bf16_t* P(const void* base, size_t elem_off) { return reinterpret_cast<const bf16_t*>(base) + elem_off; }
-inline bf16_t* W(void* ws, size_t byte_off) { return reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(ws) + byte_off); }
-inline float* WF(void* ws, size_t byte_off) { return reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + byte_off); }
-
-#define FTMI_TRY(x)          \
-    do {                     \
-        int _rc = (x);       \
-        if (_rc) return _rc; \
-    } while (0)
 
 // fp32-equivalent LoRA down-projection (see ltx_dit.hip lora_down): out [M, 3 nout] = (hi | lo | hi) planes of alpha * X . Wf^T
 int lora_down(const bf16_t* X, long ldx, int M, const bf16_t* w_sp, int nout, int K, int r, float alpha, bf16_t* out, hipStream_t st, int xk_grp_stride = 0) {

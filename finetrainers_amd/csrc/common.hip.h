@@ -176,3 +176,22 @@ FTMI_DEVICE int xcd_remap(int bid, int nwg) {
     int start = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
     return start + idx;
 }
+
+// ---- host side, for the block orchestrators (ltx_dit / cog_dit / hy_dit / wan_dit .hip) ---------------------------------------------------------
+// Buffer planning: every entry is rounded to 256 bytes on its own, so a plan's total does not depend on the order of its entries.
+struct Bump {
+    size_t off = 0;
+    size_t take(size_t bytes) {
+        size_t o = off;
+        off += (bytes + 255) & ~(size_t)255;
+        return o;
+    }
+};
+inline bf16_t* W(void* ws, size_t byte_off) { return reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(ws) + byte_off); }
+inline float* WF(void* ws, size_t byte_off) { return reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + byte_off); }
+
+#define FTMI_TRY(x)          \
+    do {                     \
+        int _rc = (x);       \
+        if (_rc) return _rc; \
+    } while (0)

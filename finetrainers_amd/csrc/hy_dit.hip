@@ -22,15 +22,6 @@ namespace ftmi {
 
 namespace {
 
-struct Bump {
-    size_t off = 0;
-    size_t take(size_t bytes) {
-        size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    }
-};
-
 struct HyLayout {
     // saved
     size_t mod, shift, onep, gate, n, q, k, v, qn, kn, o, lse, pre, xa, saved_total;
@@ -94,15 +85,7 @@ int check_cfg(const ftmi_hy_single_config& c) {
     return 0;
 }
 
-inline bf16_t* W(void* ws, size_t byte_off) { return reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(ws) + byte_off); }
-inline float* WF(void* ws, size_t byte_off) { return reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + byte_off); }
 inline const bf16_t* C16(const void* p) { return reinterpret_cast<const bf16_t*>(p); }
-
-#define FTMI_TRY(x)          \
-    do {                     \
-        int _rc = (x);       \
-        if (_rc) return _rc; \
-    } while (0)
 
 // mod [B, 3D] = (shift | scale | gate) -> three contiguous [B, D] tables: shift, bf(1 + scale), gate   (the eager graph's `1 + scale` is a bf16 op)
 __global__ __launch_bounds__(256) void hy_mod3_kernel(const bf16_t* __restrict__ mod, bf16_t* __restrict__ shift, bf16_t* __restrict__ onep,

@@ -32,15 +32,6 @@ struct WsLayout {
     size_t blk_slot;  // bytes of one block slot (blk_stride is 0 under gradient checkpointing: every block uses the same slot)
 };
 
-struct Bump {
-    size_t off = 0;
-    size_t take(size_t bytes) {
-        size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    }
-};
-
 // A modulation group is a run of consecutive token rows that shares one timestep, i.e. one row of the conditioning tables: a whole sample in training and in
 // text-to-video sampling ({B, S}), one latent frame of a sample where the timestep differs per frame ({B F, S / F}: ltx_forward_frames, ltx_sample_cond).
 struct ModGroups { int n, rows; };
@@ -131,14 +122,6 @@ int check_cfg(const ftmi_ltx_config& c, int frames = 0) {
 }
 
 inline const bf16_t* P(const void* base, size_t elem_off) { return reinterpret_cast<const bf16_t*>(base) + elem_off; }
-inline bf16_t* W(void* ws, size_t byte_off) { return reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(ws) + byte_off); }
-inline float* WF(void* ws, size_t byte_off) { return reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + byte_off); }
-
-#define FTMI_TRY(x)            \
-    do {                       \
-        int _rc = (x);         \
-        if (_rc) return _rc;   \
-    } while (0)
 
 // plain linear helper
 int linear(const bf16_t* X, long ldx, int M, const bf16_t* Wt, long ldw, int N, int K, const bf16_t* bias, bf16_t* out, long ldo,

@@ -1,8 +1,8 @@
-// Wan-T2V DiT block for FULL fine-tuning (and, below, for LoRA fine-tuning over a frozen base), forward / backward orchestrator: ONE C call per block and direction -- the unit FSDP-2 shards
-// (finetrainers/parallel/ptd.py:466-499 wraps every block with fully_shard), so the sharder keeps interleaving its all-gathers and reduce-scatters
-// between the calls.  Parameters arrive as the block's ONE flat bf16 buffer, gradients leave in ONE flat fp32 buffer of the same layout
-// (finetrainers_amd/wan/block.py WanBlockLayout; the order is restated in Offsets below), activations live in a caller-owned `saved` buffer per
-// block (every one of them is read again: all parameters train) and transients in a `scratch` buffer shared by all blocks.
+// Wan-T2V DiT block, forward / backward orchestrator for FULL fine-tuning and for LoRA fine-tuning over a frozen base: ONE C call per block and direction
+// -- the unit FSDP-2 shards (finetrainers/parallel/ptd.py:466-499 wraps every block with fully_shard), so the sharder keeps interleaving its all-gathers
+// and reduce-scatters between the calls.  Parameters arrive as the block's ONE flat bf16 buffer, gradients leave in ONE flat fp32 buffer of the same
+// layout (finetrainers_amd/wan/block.py WanBlockLayout; the order is restated in Offsets below), activations live in a caller-owned `saved` buffer per
+// block and transients in a `scratch` buffer shared by all blocks.
 //
 //   x [B, S, D] video tokens, enc [B, T, D] text tokens, mod fp32 [B, 6, D] = scale_shift_table + time projection (shift, scale, gate) x 2:
 //     n1 = LN(x) * (1 + scale_msa) + shift_msa;  q|k|v = n1 W^T + b;  q, k <- RMSNorm across heads, rotary embedding;  o1 = attention(q, k, v)
@@ -11,23 +11,35 @@
 //     n3 = LN(x2) * (1 + scale_ff) + shift_ff;  out = x2 + gate_ff * (gelu_tanh(n3 W_1^T + b) W_2^T + b)
 //
 // Reference: [upstream] diffusers WanTransformerBlock / WanAttnProcessor2_0 as driven by finetrainers/models/wan/base_specification.py:433-493,
-// restated in oracle/wan.py.  The kernel sequence is the one finetrainers_amd/wan/block.py (_WanBlockFunction) issues from Python, which stays as the
-// second implementation (the tests compare the two bit for bit, parameter gradients up to the order of their fp32 atomics).
+// restated in oracle/wan.py.  There is ONE walk per direction (block_forward / block_backward); the four entry points differ in the context they hand
+// it.  The kernel sequence is the one finetrainers_amd/wan/block.py (_block_forward / _block_backward) issues from Python, which stays as the second
+// implementation (the tests compare the two bit for bit, what is summed with fp32 atomics up to their order).
+//
+// LoRA (the reference's Wan SFT recipes: --training_type lora, --target_modules "blocks.*(to_q|to_k|to_v|to_out.0)"): the base weights are FROZEN, fp32
+// adapters A [8, r, D] / B [8, D, r] sit on the eight attention projections, in the order
+//   0 attn1.to_q, 1 attn1.to_k, 2 attn1.to_v, 3 attn1.to_out.0, 4 attn2.to_q, 5 attn2.to_k, 6 attn2.to_v, 7 attn2.to_out.0
+// and every projection computes y = x W^T + b + s (x A^T) B^T, s = alpha / r, through the NT GEMM's K-extension (attn1's q|k|v stay ONE N = 3D launch with
+// three adapters on one input and attn2's k|v ONE N = 2D launch over the text rows, laid out as ltx_dit.hip's fused QKV).  The adapters are split into
+// bf16 (hi, lo) planes once per call.  With r = 0 the walk issues the full fine-tune's launches, argument for argument.
+//
+// What the frozen base removes from the backward: the seven weight-gradient GEMMs, the bias / norm-weight / modulation / gate reductions (null
+// reduction pointers), dmod, the seven weight transposes (K-contiguous twins arrive as pointers: the frozen base never invalidates them) and -- when
+// denc == NULL, the text embedder being frozen too -- the [B T, 2D] x [2D, D] input-gradient GEMM into the text rows.
+//
+// saved (what the backward reads again), both modes:  n1, qkv, qn, kn, o1, lse1, x1, n2, q2, kv2, q2n, k2n, o2, lse2, x2, pre
+//   full fine-tune, in addition: a1, n3, act, f -- read only by the gradients of gate_msa, W_1, W_2, gate_ff; the frozen base drops them: B S (3D + F) 2 bytes
+//   r > 0, in addition: xa_qkv [M, 9r], xa_o1 [M, 3r], xa_q2 [M, 3r], xa_kv2 [Mt, 6r], xa_o2 [M, 3r]  (s x A^T as (hi | lo | hi) planes)
+// scratch, full fine-tune (backward only): the seven transposed weights and the backward's transients.
+// scratch, frozen base: forward transients (a1, n3, act, f, operand copies of A and B) overlaid with the backward's (+ dxa, operand copies of B^T and A^T).
+// Launcher calls per block (an attention counts once): full fine-tune forward 19, backward 39.  Frozen base, r > 0: forward 2 splits + 5 down-projections
+// + the full path's 19 = 26; backward 2 splits + 5 down-projections + 10 adapter-gradient GEMMs + 18 of the full path's 39 (its 7 transposes, 7
+// weight-gradient GEMMs and 7 column sums are gone) = 35, 34 without denc.
 #include "common.hip.h"
 #include "kernels.h"
 
 namespace ftmi {
 
 namespace {
-
-struct Bump {
-    size_t off = 0;
-    size_t take(size_t bytes) {
-        size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    }
-};
 
 // element offsets of the parameters inside a block's flat buffer (WanBlockLayout.entries, same order)
 struct Offsets {
@@ -61,66 +73,89 @@ Offsets offsets_of(size_t D, size_t F) {
     return o;
 }
 
-struct WanLayout {
-    // saved
-    size_t n1, qkv, qn, kn, o1, lse1, a1, x1, n2, q2, kv2, q2n, k2n, o2, lse2, x2, n3, act, pre, f, saved_total;
-    // scratch (backward)
-    size_t t_f2, t_f1, t_o2, t_q2, t_kv2, t_o1, t_qkv1;                      // transposed weights
-    size_t df, dpre, dn3, dx2, do2, dkv2, dq2n, dk2n, dq2, dn2, dx1, da1, do1, dqkv, dqn, dkn, dn1, delta, scratch_total;
+// Every buffer of one call as a pointer, so that the walks never ask where a buffer lives.
+struct Bufs {
+    bf16_t *n1, *qkv, *qn, *kn, *o1, *a1, *x1, *n2, *q2, *kv2, *q2n, *k2n, *o2, *x2, *n3, *act, *pre, *f;  // activations
+    float *lse1, *lse2;
+    bf16_t *xa_qkv, *xa_o1, *xa_q2, *xa_kv2, *xa_o2;                     // down-projected rows of the adapters (zero-size at r = 0)
+    bf16_t *a_sp, *b_ext;                                                // forward operand copies of the adapters
+    bf16_t *t_f2, *t_f1, *t_o2, *t_q2, *t_kv2, *t_o1, *t_qkv1;           // transposed weights (full fine-tune only)
+    bf16_t *df, *dpre, *dn3, *dx2, *do2, *dkv2, *dq2n, *dk2n, *dq2, *dn2, *dx1, *da1, *do1, *dqkv, *dqn, *dkn, *dn1;  // backward transients
+    float* delta;
+    bf16_t *dxa, *bt_sp, *at_ext;                                        // backward down-projection and operand copies of the adapters
+    size_t saved_total, scratch_total;
 };
 
-WanLayout make_layout(const ftmi_wan_block_config& c) {
-    WanLayout w;
-    const size_t M = (size_t)c.B * c.S, Mt = (size_t)c.B * c.T, D = c.D, F = c.F, e2 = 2;
-    Bump s;
-    w.n1 = s.take(M * D * e2);
-    w.qkv = s.take(M * 3 * D * e2);
-    w.qn = s.take(M * D * e2);
-    w.kn = s.take(M * D * e2);
-    w.o1 = s.take(M * D * e2);
-    w.lse1 = s.take((size_t)c.B * c.H * c.S * 4);
-    w.a1 = s.take(M * D * e2);
-    w.x1 = s.take(M * D * e2);
-    w.n2 = s.take(M * D * e2);
-    w.q2 = s.take(M * D * e2);
-    w.kv2 = s.take(Mt * 2 * D * e2);
-    w.q2n = s.take(M * D * e2);
-    w.k2n = s.take(Mt * D * e2);
-    w.o2 = s.take(M * D * e2);
-    w.lse2 = s.take((size_t)c.B * c.H * c.S * 4);
-    w.x2 = s.take(M * D * e2);
-    w.n3 = s.take(M * D * e2);
-    w.act = s.take(M * F * e2);
-    w.pre = s.take(M * F * e2);
-    w.f = s.take(M * D * e2);
+// The plan of both buffers, resolved against their bases (the byte planners pass none and read the totals).  frozen: a1, n3, act and f are forward
+// transients instead of saved activations, and the transposed weights are the caller's.
+Bufs make_layout(const ftmi_wan_block_config& c, int rank, bool frozen, void* saved = nullptr, void* scratch = nullptr) {
+    Bufs w;
+    const size_t M = (size_t)c.B * c.S, Mt = (size_t)c.B * c.T, D = c.D, F = c.F, r = rank > 0 ? rank : 0, e2 = 2, stat = (size_t)c.B * c.H * c.S * 4;
+    Bump s, f, b;  // saved; scratch of the forward and of the backward, which overlay each other
+    auto at = [](void* base, size_t off) { return reinterpret_cast<bf16_t*>(reinterpret_cast<uintptr_t>(base) + off); };
+    auto S = [&](size_t bytes) { return at(saved, s.take(bytes)); };
+    auto Fw = [&](size_t bytes) { return at(scratch, f.take(bytes)); };
+    auto Bw = [&](size_t bytes) { return at(scratch, b.take(bytes)); };
+    auto K = [&](size_t bytes) { return frozen ? Fw(bytes) : S(bytes); };                     // read again only by gradients of base parameters
+    auto T = [&](size_t bytes) { return frozen ? (bf16_t*)nullptr : Bw(bytes); };
+    auto f32 = [](bf16_t* p) { return reinterpret_cast<float*>(p); };
+    w.n1 = S(M * D * e2);
+    w.qkv = S(M * 3 * D * e2);
+    w.qn = S(M * D * e2);
+    w.kn = S(M * D * e2);
+    w.o1 = S(M * D * e2);
+    w.lse1 = f32(S(stat));
+    w.a1 = K(M * D * e2);
+    w.x1 = S(M * D * e2);
+    w.n2 = S(M * D * e2);
+    w.q2 = S(M * D * e2);
+    w.kv2 = S(Mt * 2 * D * e2);
+    w.q2n = S(M * D * e2);
+    w.k2n = S(Mt * D * e2);
+    w.o2 = S(M * D * e2);
+    w.lse2 = f32(S(stat));
+    w.x2 = S(M * D * e2);
+    w.n3 = K(M * D * e2);
+    w.act = K(M * F * e2);
+    w.pre = S(M * F * e2);
+    w.f = K(M * D * e2);
+    w.xa_qkv = S(M * 9 * r * e2);
+    w.xa_o1 = S(M * 3 * r * e2);
+    w.xa_q2 = S(M * 3 * r * e2);
+    w.xa_kv2 = S(Mt * 6 * r * e2);
+    w.xa_o2 = S(M * 3 * r * e2);
     w.saved_total = s.off;
-    Bump b;
-    w.t_f2 = b.take(D * F * e2);
-    w.t_f1 = b.take(D * F * e2);
-    w.t_o2 = b.take(D * D * e2);
-    w.t_q2 = b.take(D * D * e2);
-    w.t_kv2 = b.take(2 * D * D * e2);
-    w.t_o1 = b.take(D * D * e2);
-    w.t_qkv1 = b.take(3 * D * D * e2);
-    w.df = b.take(M * D * e2);
-    w.dpre = b.take(M * F * e2);
-    w.dn3 = b.take(M * D * e2);
-    w.dx2 = b.take(M * D * e2);
-    w.do2 = b.take(M * D * e2);
-    w.dkv2 = b.take(Mt * 2 * D * e2);
-    w.dq2n = b.take(M * D * e2);
-    w.dk2n = b.take(Mt * D * e2);
-    w.dq2 = b.take(M * D * e2);
-    w.dn2 = b.take(M * D * e2);
-    w.dx1 = b.take(M * D * e2);
-    w.da1 = b.take(M * D * e2);
-    w.do1 = b.take(M * D * e2);
-    w.dqkv = b.take(M * 3 * D * e2);
-    w.dqn = b.take(M * D * e2);
-    w.dkn = b.take(M * D * e2);
-    w.dn1 = b.take(M * D * e2);
-    w.delta = b.take((size_t)c.B * c.H * c.S * 4);
-    w.scratch_total = b.off;
+    w.a_sp = Fw(8 * 2 * r * D * e2);
+    w.b_ext = Fw(8 * D * 3 * r * e2);
+    w.t_f2 = T(D * F * e2);
+    w.t_f1 = T(D * F * e2);
+    w.t_o2 = T(D * D * e2);
+    w.t_q2 = T(D * D * e2);
+    w.t_kv2 = T(2 * D * D * e2);
+    w.t_o1 = T(D * D * e2);
+    w.t_qkv1 = T(3 * D * D * e2);
+    w.df = Bw(M * D * e2);
+    w.dpre = Bw(M * F * e2);
+    w.dn3 = Bw(M * D * e2);
+    w.dx2 = Bw(M * D * e2);
+    w.do2 = Bw(M * D * e2);
+    w.dkv2 = Bw(Mt * 2 * D * e2);
+    w.dq2n = Bw(M * D * e2);
+    w.dk2n = Bw(Mt * D * e2);
+    w.dq2 = Bw(M * D * e2);
+    w.dn2 = Bw(M * D * e2);
+    w.dx1 = Bw(M * D * e2);
+    w.da1 = Bw(M * D * e2);
+    w.do1 = Bw(M * D * e2);
+    w.dqkv = Bw(M * 3 * D * e2);
+    w.dqn = Bw(M * D * e2);
+    w.dkn = Bw(M * D * e2);
+    w.dn1 = Bw(M * D * e2);
+    w.delta = f32(Bw(stat));
+    w.dxa = Bw((M > Mt ? M : Mt) * 9 * r * e2);
+    w.bt_sp = Bw(8 * 2 * r * D * e2);
+    w.at_ext = Bw(D * 24 * r * e2);
+    w.scratch_total = f.off > b.off ? f.off : b.off;
     return w;
 }
 
@@ -129,367 +164,6 @@ int check_cfg(const ftmi_wan_block_config& c) {
     if (c.H * 128 != c.D || c.D % 128 != 0 || c.D > 4096) return set_error(FTMI_ERR_UNSUPPORTED, "wan_block: width must be heads x 128, at most 4096");
     if (c.F <= 0 || (c.F % 64)) return set_error(FTMI_ERR_UNSUPPORTED, "wan_block: the feed-forward width must be a multiple of 64");
     return 0;
-}
-
-inline bf16_t* W(void* ws, size_t byte_off) { return reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(ws) + byte_off); }
-inline float* WF(void* ws, size_t byte_off) { return reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + byte_off); }
-
-#define FTMI_TRY(x)          \
-    do {                     \
-        int _rc = (x);       \
-        if (_rc) return _rc; \
-    } while (0)
-
-int linear(const bf16_t* X, long ldx, int M, int K, const bf16_t* Wm, const bf16_t* bias, int N, bf16_t* out, long ldo, int V, hipStream_t st) {
-    GemmNtArgs a;
-    a.X = X; a.ldx = ldx; a.W = Wm; a.ldw = K; a.M = M; a.N = N; a.K = K; a.bias = bias; a.out = out; a.ldo = ldo; a.variant = V;
-    return gemm_nt(a, st);
-}
-// dW += dY^T X (fp32), db += column sums of dY
-int linear_grads(const bf16_t* dy, long lddy, const bf16_t* inp, long ldi, int M, int N, int K, float* gw, float* gb, hipStream_t st) {
-    GemmTnArgs t;
-    t.U = dy; t.ldu = lddy; t.V = inp; t.ldv = ldi; t.C = gw; t.ldc = K; t.M = M; t.P = N; t.Q = K;
-    FTMI_TRY(gemm_tn(t, st));
-    WanRowArgs a;
-    a.x = dy; a.ld_x = lddy; a.red1 = gb; a.rows = M; a.D = N; a.rows_per_batch = M;
-    return wan_colsum(a, st);
-}
-WanRowArgs row_args(const bf16_t* x, long ldx, bf16_t* y, long ldy, int rows, int D, int rpb, float eps) {
-    WanRowArgs a;
-    a.x = x; a.ld_x = ldx; a.y = y; a.ld_y = ldy; a.rows = rows; a.D = D; a.rows_per_batch = rpb; a.eps = eps;
-    return a;
-}
-AttnArgs attn_base(int B, int H, int Sq, int Sk) {
-    AttnArgs a;
-    a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.d = 128;
-    a.scale = 0.08838834764831845f;  // 1 / sqrt(128)
-    return a;
-}
-inline void tok_strides(long& sb, long& sh, long& ss, long rows_per_batch, long ld) {
-    sb = rows_per_batch * ld;
-    sh = 128;
-    ss = ld;
-}
-
-}  // namespace
-
-size_t wan_block_saved_bytes(const ftmi_wan_block_config& c) { return make_layout(c).saved_total; }
-size_t wan_block_scratch_bytes(const ftmi_wan_block_config& c) { return make_layout(c).scratch_total; }
-size_t wan_block_param_elements(const ftmi_wan_block_config& c) { return offsets_of(c.D, c.F).total; }
-
-int wan_block_forward(const ftmi_wan_block_config& c, const bf16_t* params, const bf16_t* x, const bf16_t* enc, const float* mod, const float* rope_cos,
-                      const float* rope_sin, bf16_t* out, void* saved, size_t saved_bytes, hipStream_t st) {
-    FTMI_TRY(check_cfg(c));
-    const WanLayout L = make_layout(c);
-    if (saved_bytes < L.saved_total) return set_error(FTMI_ERR_INVALID, "wan_block_forward: saved buffer too small");
-    const Offsets O = offsets_of(c.D, c.F);
-    const int B = c.B, S = c.S, T = c.T, D = c.D, F = c.F, M = B * S, Mt = B * T, V = c.gemm_variant;
-    const float eps = c.eps;
-    const long mb = 6L * D;  // sample stride of the modulation rows
-    auto P = [&](size_t off) { return params + off; };
-    auto MOD = [&](int i) { return mod + (size_t)i * D; };
-    bf16_t *n1 = W(saved, L.n1), *qkv = W(saved, L.qkv), *qn = W(saved, L.qn), *kn = W(saved, L.kn), *o1 = W(saved, L.o1), *a1 = W(saved, L.a1), *x1 = W(saved, L.x1);
-    // self-attention
-    {
-        WanRowArgs a = row_args(x, D, n1, D, M, D, S, eps);
-        a.shift = MOD(0); a.scale = MOD(1); a.mod_bstride = mb;
-        FTMI_TRY(wan_ln_fwd(a, st));
-    }
-    FTMI_TRY(linear(n1, D, M, D, P(O.w_qkv1), P(O.b_qkv1), 3 * D, qkv, 3 * D, V, st));
-    for (int i = 0; i < 2; ++i) {
-        WanRowArgs a = row_args(qkv + (size_t)i * D, 3 * D, i ? kn : qn, D, M, D, S, eps);
-        a.w = P(i ? O.nk1 : O.nq1); a.rope_cos = rope_cos; a.rope_sin = rope_sin; a.head_dim = 128;
-        FTMI_TRY(wan_rms_rope_fwd(a, st));
-    }
-    {
-        AttnArgs a = attn_base(B, c.H, S, S);
-        a.q = qn; tok_strides(a.q_sb, a.q_sh, a.q_ss, S, D);
-        a.k = kn; tok_strides(a.k_sb, a.k_sh, a.k_ss, S, D);
-        a.v = qkv + 2 * D; tok_strides(a.v_sb, a.v_sh, a.v_ss, S, 3 * D);
-        a.o = o1; tok_strides(a.o_sb, a.o_sh, a.o_ss, S, D);
-        a.lse2 = WF(saved, L.lse1);
-        FTMI_TRY(attn_fwd(a, st));
-    }
-    FTMI_TRY(linear(o1, D, M, D, P(O.w_o1), P(O.b_o1), D, a1, D, V, st));
-    {
-        WanRowArgs a = row_args(x, D, x1, D, M, D, S, eps);
-        a.scale = MOD(2); a.mod_bstride = mb; a.dy = a1; a.ld_dy = D;
-        FTMI_TRY(wan_gate_res_fwd(a, st));
-    }
-    // cross-attention to the text tokens (no rotary embedding, no gate)
-    bf16_t *n2 = W(saved, L.n2), *q2 = W(saved, L.q2), *kv2 = W(saved, L.kv2), *q2n = W(saved, L.q2n), *k2n = W(saved, L.k2n), *o2 = W(saved, L.o2), *x2 = W(saved, L.x2);
-    {
-        WanRowArgs a = row_args(x1, D, n2, D, M, D, S, eps);
-        a.w = P(O.n2w); a.b = P(O.n2b);
-        FTMI_TRY(wan_ln_fwd(a, st));
-    }
-    FTMI_TRY(linear(n2, D, M, D, P(O.w_q2), P(O.b_q2), D, q2, D, V, st));
-    FTMI_TRY(linear(enc, D, Mt, D, P(O.w_kv2), P(O.b_kv2), 2 * D, kv2, 2 * D, V, st));
-    {
-        WanRowArgs a = row_args(q2, D, q2n, D, M, D, S, eps);
-        a.w = P(O.nq2);
-        FTMI_TRY(wan_rms_rope_fwd(a, st));
-        WanRowArgs b = row_args(kv2, 2 * D, k2n, D, Mt, D, T, eps);
-        b.w = P(O.nk2);
-        FTMI_TRY(wan_rms_rope_fwd(b, st));
-    }
-    {
-        AttnArgs a = attn_base(B, c.H, S, T);
-        a.q = q2n; tok_strides(a.q_sb, a.q_sh, a.q_ss, S, D);
-        a.k = k2n; tok_strides(a.k_sb, a.k_sh, a.k_ss, T, D);
-        a.v = kv2 + D; tok_strides(a.v_sb, a.v_sh, a.v_ss, T, 2 * D);
-        a.o = o2; tok_strides(a.o_sb, a.o_sh, a.o_ss, S, D);
-        a.lse2 = WF(saved, L.lse2);
-        FTMI_TRY(attn_fwd(a, st));
-    }
-    bf16_t* a2 = W(saved, L.f);  // (the feed-forward output buffer doubles as the staging of o2 W_o2^T + b: it is consumed by the next launch)
-    FTMI_TRY(linear(o2, D, M, D, P(O.w_o2), P(O.b_o2), D, a2, D, V, st));
-    {
-        WanRowArgs a = row_args(x1, D, x2, D, M, D, S, eps);
-        a.dy = a2; a.ld_dy = D;
-        FTMI_TRY(wan_gate_res_fwd(a, st));
-    }
-    // feed-forward
-    bf16_t *n3 = W(saved, L.n3), *act = W(saved, L.act), *pre = W(saved, L.pre), *f = W(saved, L.f);
-    {
-        WanRowArgs a = row_args(x2, D, n3, D, M, D, S, eps);
-        a.shift = MOD(3); a.scale = MOD(4); a.mod_bstride = mb;
-        FTMI_TRY(wan_ln_fwd(a, st));
-    }
-    {
-        GemmNtArgs a;  // GELU-tanh, pre-activation kept
-        a.X = n3; a.ldx = D; a.W = P(O.w_f1); a.ldw = D; a.M = M; a.N = F; a.K = D; a.bias = P(O.b_f1); a.out = act; a.ldo = F; a.out2 = pre; a.ldo2 = F;
-        a.epi = EPI_GELU; a.variant = V;
-        FTMI_TRY(gemm_nt(a, st));
-    }
-    FTMI_TRY(linear(act, F, M, F, P(O.w_f2), P(O.b_f2), D, f, D, V, st));
-    {
-        WanRowArgs a = row_args(x2, D, out, D, M, D, S, eps);
-        a.scale = MOD(5); a.mod_bstride = mb; a.dy = f; a.ld_dy = D;
-        FTMI_TRY(wan_gate_res_fwd(a, st));
-    }
-    return 0;
-}
-
-// grads: the block's flat fp32 gradient buffer (ADDED to); dmod fp32 [6, B, D] (ADDED to: column sums of d shift / d scale / d gate per sample);
-// dx [B, S, D], denc [B, T, D] written.
-int wan_block_backward(const ftmi_wan_block_config& c, const bf16_t* params, float* grads, const bf16_t* x, const bf16_t* enc, const float* mod,
-                       const float* rope_cos, const float* rope_sin, const bf16_t* dout, bf16_t* dx, bf16_t* denc, float* dmod, void* saved,
-                       size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st) {
-    FTMI_TRY(check_cfg(c));
-    const WanLayout L = make_layout(c);
-    if (saved_bytes < L.saved_total || scratch_bytes < L.scratch_total) return set_error(FTMI_ERR_INVALID, "wan_block_backward: buffer too small");
-    const Offsets O = offsets_of(c.D, c.F);
-    const int B = c.B, S = c.S, T = c.T, D = c.D, F = c.F, M = B * S, Mt = B * T, V = c.gemm_variant;
-    const float eps = c.eps;
-    const long mb = 6L * D;
-    auto P = [&](size_t off) { return params + off; };
-    auto G = [&](size_t off) { return grads + off; };
-    auto MOD = [&](int i) { return mod + (size_t)i * D; };
-    auto DMOD = [&](int i) { return dmod + (size_t)i * B * D; };
-    // K-contiguous copies of the weights for the input-gradient GEMMs (dX = dY W as an NT GEMM against W^T)
-    FTMI_TRY(transpose_bf16(P(O.w_f2), W(scratch, L.t_f2), D, F, st));
-    FTMI_TRY(transpose_bf16(P(O.w_f1), W(scratch, L.t_f1), F, D, st));
-    FTMI_TRY(transpose_bf16(P(O.w_o2), W(scratch, L.t_o2), D, D, st));
-    FTMI_TRY(transpose_bf16(P(O.w_q2), W(scratch, L.t_q2), D, D, st));
-    FTMI_TRY(transpose_bf16(P(O.w_kv2), W(scratch, L.t_kv2), 2 * D, D, st));
-    FTMI_TRY(transpose_bf16(P(O.w_o1), W(scratch, L.t_o1), D, D, st));
-    FTMI_TRY(transpose_bf16(P(O.w_qkv1), W(scratch, L.t_qkv1), 3 * D, D, st));
-    const bf16_t *n1 = W(saved, L.n1), *qkv = W(saved, L.qkv), *qn = W(saved, L.qn), *kn = W(saved, L.kn), *o1 = W(saved, L.o1), *a1 = W(saved, L.a1), *x1 = W(saved, L.x1);
-    const bf16_t *n2 = W(saved, L.n2), *q2 = W(saved, L.q2), *kv2 = W(saved, L.kv2), *q2n = W(saved, L.q2n), *k2n = W(saved, L.k2n), *o2 = W(saved, L.o2), *x2 = W(saved, L.x2);
-    const bf16_t *n3 = W(saved, L.n3), *act = W(saved, L.act), *pre = W(saved, L.pre), *f = W(saved, L.f);
-
-    // feed-forward branch: out = x2 + f * gate_ff
-    bf16_t* df = W(scratch, L.df);
-    {
-        WanRowArgs a = row_args(dout, D, df, D, M, D, S, eps);
-        a.scale = MOD(5); a.mod_bstride = mb; a.dy = f; a.ld_dy = D; a.red1 = DMOD(5); a.red_per_batch = 1;
-        FTMI_TRY(wan_gate_res_bwd(a, st));
-    }
-    FTMI_TRY(linear_grads(df, D, act, F, M, D, F, G(O.w_f2), G(O.b_f2), st));
-    bf16_t* dpre = W(scratch, L.dpre);
-    {
-        GemmNtArgs a;  // (d f W2) * gelu'(pre)
-        a.X = df; a.ldx = D; a.W = W(scratch, L.t_f2); a.ldw = D; a.M = M; a.N = F; a.K = D; a.out = dpre; a.ldo = F; a.epi = EPI_DGELU; a.aux = pre; a.ldaux = F; a.variant = V;
-        FTMI_TRY(gemm_nt(a, st));
-    }
-    FTMI_TRY(linear_grads(dpre, F, n3, D, M, F, D, G(O.w_f1), G(O.b_f1), st));
-    bf16_t* dn3 = W(scratch, L.dn3);
-    FTMI_TRY(linear(dpre, F, M, F, W(scratch, L.t_f1), nullptr, D, dn3, D, V, st));
-    bf16_t* dx2 = W(scratch, L.dx2);
-    {
-        WanRowArgs a = row_args(x2, D, dx2, D, M, D, S, eps);
-        a.scale = MOD(4); a.mod_bstride = mb; a.dy = dn3; a.ld_dy = D; a.dres = dout; a.red1 = DMOD(3); a.red2 = DMOD(4); a.red_per_batch = 1;
-        FTMI_TRY(wan_ln_bwd(a, st));
-    }
-    // cross-attention branch: x2 = x1 + a2
-    FTMI_TRY(linear_grads(dx2, D, o2, D, M, D, D, G(O.w_o2), G(O.b_o2), st));
-    bf16_t* do2 = W(scratch, L.do2);
-    FTMI_TRY(linear(dx2, D, M, D, W(scratch, L.t_o2), nullptr, D, do2, D, V, st));
-    bf16_t *dkv2 = W(scratch, L.dkv2), *dq2n = W(scratch, L.dq2n), *dk2n = W(scratch, L.dk2n);
-    {
-        AttnArgs a = attn_base(B, c.H, S, T);
-        a.q = q2n; tok_strides(a.q_sb, a.q_sh, a.q_ss, S, D);
-        a.k = k2n; tok_strides(a.k_sb, a.k_sh, a.k_ss, T, D);
-        a.v = kv2 + D; tok_strides(a.v_sb, a.v_sh, a.v_ss, T, 2 * D);
-        a.o = const_cast<bf16_t*>(o2); tok_strides(a.o_sb, a.o_sh, a.o_ss, S, D);
-        a.lse2 = WF(saved, L.lse2);
-        a.dout = do2; tok_strides(a.do_sb, a.do_sh, a.do_ss, S, D);
-        a.dq = dq2n; tok_strides(a.dq_sb, a.dq_sh, a.dq_ss, S, D);
-        a.dk = dk2n; tok_strides(a.dk_sb, a.dk_sh, a.dk_ss, T, D);
-        a.dv = dkv2 + D; tok_strides(a.dv_sb, a.dv_sh, a.dv_ss, T, 2 * D);
-        a.delta = WF(scratch, L.delta);
-        FTMI_TRY(attn_bwd(a, st));
-    }
-    bf16_t* dq2 = W(scratch, L.dq2);
-    {
-        WanRowArgs a = row_args(q2, D, dq2, D, M, D, S, eps);
-        a.w = P(O.nq2); a.dy = dq2n; a.ld_dy = D; a.red2 = G(O.nq2);
-        FTMI_TRY(wan_rms_rope_bwd(a, st));
-        WanRowArgs b = row_args(kv2, 2 * D, dkv2, 2 * D, Mt, D, T, eps);
-        b.w = P(O.nk2); b.dy = dk2n; b.ld_dy = D; b.red2 = G(O.nk2);
-        FTMI_TRY(wan_rms_rope_bwd(b, st));
-    }
-    FTMI_TRY(linear_grads(dq2, D, n2, D, M, D, D, G(O.w_q2), G(O.b_q2), st));
-    FTMI_TRY(linear_grads(dkv2, 2 * D, enc, D, Mt, 2 * D, D, G(O.w_kv2), G(O.b_kv2), st));
-    FTMI_TRY(linear(dkv2, 2 * D, Mt, 2 * D, W(scratch, L.t_kv2), nullptr, D, denc, D, V, st));
-    bf16_t* dn2 = W(scratch, L.dn2);
-    FTMI_TRY(linear(dq2, D, M, D, W(scratch, L.t_q2), nullptr, D, dn2, D, V, st));
-    bf16_t* dx1 = W(scratch, L.dx1);
-    {
-        WanRowArgs a = row_args(x1, D, dx1, D, M, D, S, eps);
-        a.w = P(O.n2w); a.dy = dn2; a.ld_dy = D; a.dres = dx2; a.red1 = G(O.n2b); a.red2 = G(O.n2w);
-        FTMI_TRY(wan_ln_bwd(a, st));
-    }
-    // self-attention branch: x1 = x + a1 * gate_msa
-    bf16_t* da1 = W(scratch, L.da1);
-    {
-        WanRowArgs a = row_args(dx1, D, da1, D, M, D, S, eps);
-        a.scale = MOD(2); a.mod_bstride = mb; a.dy = a1; a.ld_dy = D; a.red1 = DMOD(2); a.red_per_batch = 1;
-        FTMI_TRY(wan_gate_res_bwd(a, st));
-    }
-    FTMI_TRY(linear_grads(da1, D, o1, D, M, D, D, G(O.w_o1), G(O.b_o1), st));
-    bf16_t* do1 = W(scratch, L.do1);
-    FTMI_TRY(linear(da1, D, M, D, W(scratch, L.t_o1), nullptr, D, do1, D, V, st));
-    bf16_t *dqkv = W(scratch, L.dqkv), *dqn = W(scratch, L.dqn), *dkn = W(scratch, L.dkn);
-    {
-        AttnArgs a = attn_base(B, c.H, S, S);
-        a.q = qn; tok_strides(a.q_sb, a.q_sh, a.q_ss, S, D);
-        a.k = kn; tok_strides(a.k_sb, a.k_sh, a.k_ss, S, D);
-        a.v = qkv + 2 * D; tok_strides(a.v_sb, a.v_sh, a.v_ss, S, 3 * D);
-        a.o = const_cast<bf16_t*>(o1); tok_strides(a.o_sb, a.o_sh, a.o_ss, S, D);
-        a.lse2 = WF(saved, L.lse1);
-        a.dout = do1; tok_strides(a.do_sb, a.do_sh, a.do_ss, S, D);
-        a.dq = dqn; tok_strides(a.dq_sb, a.dq_sh, a.dq_ss, S, D);
-        a.dk = dkn; tok_strides(a.dk_sb, a.dk_sh, a.dk_ss, S, D);
-        a.dv = dqkv + 2 * D; tok_strides(a.dv_sb, a.dv_sh, a.dv_ss, S, 3 * D);
-        a.delta = WF(scratch, L.delta);
-        FTMI_TRY(attn_bwd(a, st));
-    }
-    for (int i = 0; i < 2; ++i) {
-        WanRowArgs a = row_args(qkv + (size_t)i * D, 3 * D, dqkv + (size_t)i * D, 3 * D, M, D, S, eps);
-        a.w = P(i ? O.nk1 : O.nq1); a.dy = i ? dkn : dqn; a.ld_dy = D; a.red2 = G(i ? O.nk1 : O.nq1); a.rope_cos = rope_cos; a.rope_sin = rope_sin; a.head_dim = 128;
-        FTMI_TRY(wan_rms_rope_bwd(a, st));
-    }
-    FTMI_TRY(linear_grads(dqkv, 3 * D, n1, D, M, 3 * D, D, G(O.w_qkv1), G(O.b_qkv1), st));
-    bf16_t* dn1 = W(scratch, L.dn1);
-    FTMI_TRY(linear(dqkv, 3 * D, M, 3 * D, W(scratch, L.t_qkv1), nullptr, D, dn1, D, V, st));  // the three projections' input gradients summed in the fp32 accumulator
-    {
-        WanRowArgs a = row_args(x, D, dx, D, M, D, S, eps);
-        a.scale = MOD(1); a.mod_bstride = mb; a.dy = dn1; a.ld_dy = D; a.dres = dx1; a.red1 = DMOD(0); a.red2 = DMOD(1); a.red_per_batch = 1;
-        FTMI_TRY(wan_ln_bwd(a, st));
-    }
-    return 0;
-}
-
-
-// ------------------------------------------------------------------------------------------------------------------------------------------------
-// The same block for LoRA fine-tuning (the reference's Wan SFT recipes: --training_type lora, --target_modules "blocks.*(to_q|to_k|to_v|to_out.0)"):
-// the base weights are FROZEN, fp32 adapters A [8, r, D] / B [8, D, r] sit on the eight attention projections, in the order
-//   0 attn1.to_q, 1 attn1.to_k, 2 attn1.to_v, 3 attn1.to_out.0, 4 attn2.to_q, 5 attn2.to_k, 6 attn2.to_v, 7 attn2.to_out.0
-// and every projection computes y = x W^T + b + s (x A^T) B^T, s = alpha / r, through the NT GEMM's K-extension (hy_dit.hip lora_linear_fwd; attn1's
-// q|k|v stay ONE N = 3D launch with three adapters on one input and attn2's k|v ONE N = 2D launch over the text rows, laid out as ltx_dit.hip's fused QKV).
-// The adapters are split into bf16 (hi, lo) planes once per call.  With r = 0 the launches are those of wan_block_forward, argument for argument.
-//
-// What the frozen base removes from the backward: the seven weight-gradient GEMMs, the bias / norm-weight / modulation / gate reductions (null
-// reduction pointers), dmod, the seven weight transposes (K-contiguous twins arrive as pointers: the frozen base never invalidates them) and -- when
-// denc == NULL, the text embedder being frozen too -- the [B T, 2D] x [2D, D] input-gradient GEMM into the text rows.
-//
-// saved (what the backward reads again):  n1, qkv, qn, kn, o1, lse1, x1, n2, q2, kv2, q2n, k2n, o2, lse2, x2, pre,
-//                                         xa_qkv [M, 9r], xa_o1 [M, 3r], xa_q2 [M, 3r], xa_kv2 [Mt, 6r], xa_o2 [M, 3r]  (s x A^T as (hi | lo | hi) planes)
-//   dropped against WanLayout: a1, n3, act, f -- read only by the gradients of frozen parameters (gate_msa, W_1, W_2, gate_ff): B S (3D + F) 2 bytes.
-// scratch: forward transients (a1, n3, act, f, operand copies of A and B) overlaid with the backward's.
-// Launcher calls per block (r > 0; an attention counts once): forward 2 splits + 5 down-projections + the full path's 19 = 26; backward 2 splits + 5
-// down-projections + 10 adapter-gradient GEMMs + 18 of the full path's 39 (its 7 transposes, 7 weight-gradient GEMMs and 7 column sums are gone) = 35, 34
-// without denc.
-namespace {
-
-struct WanLoraLayout {
-    // saved
-    size_t n1, qkv, qn, kn, o1, lse1, x1, n2, q2, kv2, q2n, k2n, o2, lse2, x2, pre, xa_qkv, xa_o1, xa_q2, xa_kv2, xa_o2, saved_total;
-    // scratch, forward
-    size_t a1, n3, act, f, a_sp, b_ext;
-    // scratch, backward
-    size_t df, dpre, dn3, dx2, do2, dkv2, dq2n, dk2n, dq2, dn2, dx1, da1, do1, dqkv, dqn, dkn, dn1, delta, dxa, bt_sp, at_ext, scratch_total;
-};
-
-WanLoraLayout make_lora_layout(const ftmi_wan_lora_block_config& c) {
-    WanLoraLayout w;
-    const size_t M = (size_t)c.B * c.S, Mt = (size_t)c.B * c.T, D = c.D, F = c.F, r = c.r > 0 ? c.r : 0, e2 = 2;
-    Bump s;
-    w.n1 = s.take(M * D * e2);
-    w.qkv = s.take(M * 3 * D * e2);
-    w.qn = s.take(M * D * e2);
-    w.kn = s.take(M * D * e2);
-    w.o1 = s.take(M * D * e2);
-    w.lse1 = s.take((size_t)c.B * c.H * c.S * 4);
-    w.x1 = s.take(M * D * e2);
-    w.n2 = s.take(M * D * e2);
-    w.q2 = s.take(M * D * e2);
-    w.kv2 = s.take(Mt * 2 * D * e2);
-    w.q2n = s.take(M * D * e2);
-    w.k2n = s.take(Mt * D * e2);
-    w.o2 = s.take(M * D * e2);
-    w.lse2 = s.take((size_t)c.B * c.H * c.S * 4);
-    w.x2 = s.take(M * D * e2);
-    w.pre = s.take(M * F * e2);
-    w.xa_qkv = s.take(M * 9 * r * e2);
-    w.xa_o1 = s.take(M * 3 * r * e2);
-    w.xa_q2 = s.take(M * 3 * r * e2);
-    w.xa_kv2 = s.take(Mt * 6 * r * e2);
-    w.xa_o2 = s.take(M * 3 * r * e2);
-    w.saved_total = s.off;
-    Bump f;  // forward and backward transients overlay each other
-    w.a1 = f.take(M * D * e2);
-    w.n3 = f.take(M * D * e2);
-    w.act = f.take(M * F * e2);
-    w.f = f.take(M * D * e2);
-    w.a_sp = f.take(8 * 2 * r * D * e2);
-    w.b_ext = f.take(8 * D * 3 * r * e2);
-    Bump b;
-    w.df = b.take(M * D * e2);
-    w.dpre = b.take(M * F * e2);
-    w.dn3 = b.take(M * D * e2);
-    w.dx2 = b.take(M * D * e2);
-    w.do2 = b.take(M * D * e2);
-    w.dkv2 = b.take(Mt * 2 * D * e2);
-    w.dq2n = b.take(M * D * e2);
-    w.dk2n = b.take(Mt * D * e2);
-    w.dq2 = b.take(M * D * e2);
-    w.dn2 = b.take(M * D * e2);
-    w.dx1 = b.take(M * D * e2);
-    w.da1 = b.take(M * D * e2);
-    w.do1 = b.take(M * D * e2);
-    w.dqkv = b.take(M * 3 * D * e2);
-    w.dqn = b.take(M * D * e2);
-    w.dkn = b.take(M * D * e2);
-    w.dn1 = b.take(M * D * e2);
-    w.delta = b.take((size_t)c.B * c.H * c.S * 4);
-    w.dxa = b.take((M > Mt ? M : Mt) * 9 * r * e2);
-    w.bt_sp = b.take(8 * 2 * r * D * e2);
-    w.at_ext = b.take(D * 24 * r * e2);
-    w.scratch_total = f.off > b.off ? f.off : b.off;
-    return w;
 }
 
 ftmi_wan_block_config base_cfg(const ftmi_wan_lora_block_config& c) {
@@ -514,6 +188,69 @@ struct LoraOps {
     const bf16_t* ext = nullptr;  // forward: B as [hi | hi | lo] columns [8][D][3r];   backward: A^T columns, the eight adapters side by side [D][24r]
 };
 
+// K-contiguous copies of the weights for the input-gradient GEMMs (dX = dY W as an NT GEMM against W^T)
+struct Twins {
+    const bf16_t *qkv1 = nullptr, *o1 = nullptr, *q2 = nullptr, *kv2 = nullptr, *o2 = nullptr, *f1 = nullptr, *f2 = nullptr;
+};
+
+// What one call hands the walks.  Full fine-tune: lo.r = 0, grads and dmod set, twins transposed into scratch by the call.  Frozen base: grads = dmod = null,
+// the caller's twins, the adapters' gradients in grad_a / grad_b when lo.r > 0.
+struct Block {
+    ftmi_wan_block_config c;
+    const bf16_t* params = nullptr;
+    Bufs L;
+    LoraOps lo;
+    const bf16_t *x = nullptr, *enc = nullptr;
+    const float *mod = nullptr, *rope_cos = nullptr, *rope_sin = nullptr;
+    float *grads = nullptr, *dmod = nullptr;      // backward: flat fp32 base gradients, fp32 [6, B, D] modulation sums (both ADDED to)
+    float *grad_a = nullptr, *grad_b = nullptr;  // backward: fp32 [8, r, D] / [8, D, r] (ADDED to)
+    Twins t;
+    hipStream_t st = nullptr;
+};
+
+// dW += dY^T X (fp32), db += column sums of dY; nothing when the base is frozen (gw == null)
+int linear_grads(const bf16_t* dy, long lddy, const bf16_t* inp, long ldi, int M, int N, int K, float* gw, float* gb, hipStream_t st) {
+    if (!gw) return 0;
+    GemmTnArgs t;
+    t.U = dy; t.ldu = lddy; t.V = inp; t.ldv = ldi; t.C = gw; t.ldc = K; t.M = M; t.P = N; t.Q = K;
+    FTMI_TRY(gemm_tn(t, st));
+    WanRowArgs a;
+    a.x = dy; a.ld_x = lddy; a.red1 = gb; a.rows = M; a.D = N; a.rows_per_batch = M;
+    return wan_colsum(a, st);
+}
+WanRowArgs row_args(const bf16_t* x, long ldx, bf16_t* y, long ldy, int rows, int D, int rpb, float eps) {
+    WanRowArgs a;
+    a.x = x; a.ld_x = ldx; a.y = y; a.ld_y = ldy; a.rows = rows; a.D = D; a.rows_per_batch = rpb; a.eps = eps;
+    return a;
+}
+inline void tok_strides(long& sb, long& sh, long& ss, long rows_per_batch, long ld) {
+    sb = rows_per_batch * ld;
+    sh = 128;
+    ss = ld;
+}
+// q, k, o: token rows [B S, D]; v: the last D columns of the fused projection v_base [B Sk, ld_v]
+AttnArgs attn_args(const ftmi_wan_block_config& c, const bf16_t* q, const bf16_t* k, const bf16_t* v_base, long ld_v, bf16_t* o, float* lse, int Sq, int Sk) {
+    AttnArgs a;
+    a.B = c.B; a.H = c.H; a.Sq = Sq; a.Sk = Sk; a.d = 128;
+    a.scale = 0.08838834764831845f;  // 1 / sqrt(128)
+    a.q = q; tok_strides(a.q_sb, a.q_sh, a.q_ss, Sq, c.D);
+    a.k = k; tok_strides(a.k_sb, a.k_sh, a.k_ss, Sk, c.D);
+    a.v = v_base + (ld_v - c.D); tok_strides(a.v_sb, a.v_sh, a.v_ss, Sk, ld_v);
+    a.o = o; tok_strides(a.o_sb, a.o_sh, a.o_ss, Sq, c.D);
+    a.lse2 = lse;
+    return a;
+}
+// the backward's fields on top: dv goes where v sits in its fused projection, into dv_base
+AttnArgs attn_bwd_args(AttnArgs a, const bf16_t* dout, bf16_t* dq, bf16_t* dk, bf16_t* dv_base, float* delta) {
+    const long D = a.q_ss, ld_v = a.v_ss;
+    a.dout = dout; tok_strides(a.do_sb, a.do_sh, a.do_ss, a.Sq, D);
+    a.dq = dq; tok_strides(a.dq_sb, a.dq_sh, a.dq_ss, a.Sq, D);
+    a.dk = dk; tok_strides(a.dk_sb, a.dk_sh, a.dk_ss, a.Sk, D);
+    a.dv = dv_base + (ld_v - D); tok_strides(a.dv_sb, a.dv_sh, a.dv_ss, a.Sk, ld_v);
+    a.delta = delta;
+    return a;
+}
+
 // s * X A^T (or s * dY B) of `nadp` adjacent adapters as ONE split down-projection: out [rows, 3 nadp r]; X columns step by xk_stride per adapter (0: shared input)
 int lora_down(const LoraOps& lo, const bf16_t* X, long ldx, int rows, int D, int adp, int nadp, long xk_stride, bf16_t* out, hipStream_t st) {
     const int r = lo.r;
@@ -524,289 +261,295 @@ int lora_down(const LoraOps& lo, const bf16_t* X, long ldx, int rows, int D, int
     return gemm_nt(d, st);
 }
 
-// out [rows, nadp D] = X W^T + bias (+ the adapters adp .. adp + nadp - 1 on the same input X); xa [rows, 3 nadp r] is kept for the backward
-int lora_linear_fwd(const LoraOps& lo, const bf16_t* X, int rows, int D, const bf16_t* Wm, const bf16_t* bias, int adp, int nadp, bf16_t* xa, bf16_t* out, int V,
-                    hipStream_t st) {
-    const int r = lo.r;
+// out [rows, N] = X W^T + bias, X [rows, K].  nadp > 0 (then N = nadp K): + the adapters adp .. adp + nadp - 1 on the same input when the call has any;
+// xa [rows, 3 nadp r] is kept for the backward
+int proj_fwd(const Block& k, const bf16_t* X, int rows, int K, const bf16_t* Wm, const bf16_t* bias, int N, int adp, int nadp, bf16_t* xa, bf16_t* out) {
+    const int r = nadp > 0 ? k.lo.r : 0;
     GemmNtArgs a;
-    a.X = X; a.ldx = D; a.W = Wm; a.ldw = D; a.M = rows; a.N = nadp * D; a.K = D; a.bias = bias; a.out = out; a.ldo = (long)nadp * D; a.variant = V;
+    a.X = X; a.ldx = K; a.W = Wm; a.ldw = K; a.M = rows; a.N = N; a.K = K; a.bias = bias; a.out = out; a.ldo = N; a.variant = k.c.gemm_variant;
     if (r > 0) {
-        FTMI_TRY(lora_down(lo, X, D, rows, D, adp, nadp, 0, xa, st));
-        a.X2 = xa; a.ldx2 = 3L * nadp * r; a.W2 = lo.ext + (size_t)adp * D * 3 * r; a.ldw2 = 3 * r; a.K2 = 3 * r;
-        if (nadp > 1) { a.x2_grp_n = D; a.x2_grp_stride = 3 * r; }
+        FTMI_TRY(lora_down(k.lo, X, K, rows, K, adp, nadp, 0, xa, k.st));
+        a.X2 = xa; a.ldx2 = 3L * nadp * r; a.W2 = k.lo.ext + (size_t)adp * K * 3 * r; a.ldw2 = 3 * r; a.K2 = 3 * r;
+        if (nadp > 1) { a.x2_grp_n = K; a.x2_grp_stride = 3 * r; }
     }
-    return gemm_nt(a, st);
+    return gemm_nt(a, k.st);
 }
 
-// dx [rows, D] = dY Wt^T (+ dXA A) (dx == nullptr: skipped), dB += dY^T XA, dA += dXA^T X for the adapters adp .. adp + nadp - 1 (dY [rows, nadp D])
-int lora_linear_bwd(const LoraOps& lo, const bf16_t* X, const bf16_t* dy, int rows, int D, const bf16_t* Wt, int adp, int nadp, const bf16_t* xa, bf16_t* dxa,
-                    bf16_t* dx, float* grad_a, float* grad_b, int V, hipStream_t st) {
-    const int r = lo.r;
-    const long lddy = (long)nadp * D;
-    if (r > 0) FTMI_TRY(lora_down(lo, dy, lddy, rows, D, adp, nadp, nadp > 1 ? D : 0, dxa, st));
+// The backward of proj_fwd for dY [rows, N], X [rows, K], Wt [K, N] the K-contiguous twin of W, in this order: dW += dY^T X and db += column sums (gw != null:
+// the base trains); dXA = s dY B (adapters); dx [rows, K] = dY Wt^T (+ dXA A) (dx == null: skipped); dB += dY^T XA, dA += dXA^T X (adapters)
+int proj_bwd(const Block& k, const bf16_t* X, const bf16_t* dy, int rows, int N, int K, const bf16_t* Wt, int adp, int nadp, const bf16_t* xa, bf16_t* dx,
+             float* gw, float* gb) {
+    const int r = nadp > 0 ? k.lo.r : 0;
+    bf16_t* dxa = k.L.dxa;
+    FTMI_TRY(linear_grads(dy, N, X, K, rows, N, K, gw, gb, k.st));
+    if (r > 0) FTMI_TRY(lora_down(k.lo, dy, N, rows, K, adp, nadp, nadp > 1 ? K : 0, dxa, k.st));
     if (dx) {
         GemmNtArgs a;
-        a.X = dy; a.ldx = lddy; a.W = Wt; a.ldw = lddy; a.M = rows; a.N = D; a.K = nadp * D; a.out = dx; a.ldo = D; a.variant = V;
-        if (r > 0) { a.X2 = dxa; a.ldx2 = 3L * nadp * r; a.W2 = lo.ext + (size_t)adp * 3 * r; a.ldw2 = 24L * r; a.K2 = 3 * nadp * r; }
-        FTMI_TRY(gemm_nt(a, st));
+        a.X = dy; a.ldx = N; a.W = Wt; a.ldw = N; a.M = rows; a.N = K; a.K = N; a.out = dx; a.ldo = K; a.variant = k.c.gemm_variant;
+        if (r > 0) { a.X2 = dxa; a.ldx2 = 3L * nadp * r; a.W2 = k.lo.ext + (size_t)adp * 3 * r; a.ldw2 = 24L * r; a.K2 = 3 * nadp * r; }
+        FTMI_TRY(gemm_nt(a, k.st));
     }
     if (r > 0) {
         GemmTnArgs t;  // dB += dY^T XA   (XA = hi + lo planes)
-        t.U = dy; t.ldu = lddy; t.V = xa; t.ldv = 3L * nadp * r; t.v_fold = r; t.C = grad_b + (size_t)adp * D * r; t.ldc = r; t.M = rows; t.P = nadp * D; t.Q = r;
-        if (nadp > 1) { t.v_grp_p = D; t.v_grp_stride = 3 * r; }
-        FTMI_TRY(gemm_tn(t, st));
+        t.U = dy; t.ldu = N; t.V = xa; t.ldv = 3L * nadp * r; t.v_fold = r; t.C = k.grad_b + (size_t)adp * K * r; t.ldc = r; t.M = rows; t.P = N; t.Q = r;
+        if (nadp > 1) { t.v_grp_p = K; t.v_grp_stride = 3 * r; }
+        FTMI_TRY(gemm_tn(t, k.st));
         GemmTnArgs u;  // dA += dXA^T X
-        u.U = dxa; u.ldu = 3L * nadp * r; u.u_fold = r; u.V = X; u.ldv = D; u.C = grad_a + (size_t)adp * r * D; u.ldc = D; u.M = rows; u.P = nadp * r; u.Q = D;
+        u.U = dxa; u.ldu = 3L * nadp * r; u.u_fold = r; u.V = X; u.ldv = K; u.C = k.grad_a + (size_t)adp * r * K; u.ldc = K; u.M = rows; u.P = nadp * r; u.Q = K;
         if (nadp > 1) { u.u_grp_p = r; u.u_grp_stride = 3 * r; }
-        FTMI_TRY(gemm_tn(u, st));
+        FTMI_TRY(gemm_tn(u, k.st));
     }
     return 0;
 }
 
-}  // namespace
-
-size_t wan_lora_block_saved_bytes(const ftmi_wan_lora_block_config& c) { return make_lora_layout(c).saved_total; }
-size_t wan_lora_block_scratch_bytes(const ftmi_wan_lora_block_config& c) { return make_lora_layout(c).scratch_total; }
-
 // out == nullptr: the recomputation pass of gradient checkpointing -- the identical kernel sequence refills `saved` from the block's input and stops after
 // the feed-forward's first GEMM (its pre-activation is the last thing the backward reads)
-int wan_lora_block_forward(const ftmi_wan_lora_block_config& c, const ftmi_wan_lora_block_weights& w, const bf16_t* x, const bf16_t* enc, const float* mod,
-                           const float* rope_cos, const float* rope_sin, bf16_t* out, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
-                           hipStream_t st) {
-    FTMI_TRY(check_lora_cfg(c));
-    const WanLoraLayout L = make_lora_layout(c);
-    if (saved_bytes < L.saved_total || scratch_bytes < L.scratch_total) return set_error(FTMI_ERR_INVALID, "wan_lora_block_forward: buffer too small");
-    if (c.r > 0 && (!w.lora_a || !w.lora_b)) return set_error(FTMI_ERR_INVALID, "wan_lora_block_forward: LoRA rank without adapters");
+int block_forward(const Block& k, bf16_t* out) {
+    const ftmi_wan_block_config& c = k.c;
+    const Bufs& L = k.L;
     const Offsets O = offsets_of(c.D, c.F);
-    const bf16_t* params = reinterpret_cast<const bf16_t*>(w.params);
-    const int B = c.B, S = c.S, T = c.T, D = c.D, F = c.F, M = B * S, Mt = B * T, V = c.gemm_variant, r = c.r;
+    const int B = c.B, S = c.S, T = c.T, D = c.D, F = c.F, M = B * S, Mt = B * T;
     const float eps = c.eps;
-    const long mb = 6L * D;
-    auto P = [&](size_t off) { return params + off; };
-    auto MOD = [&](int i) { return mod + (size_t)i * D; };
-    LoraOps lo;
-    lo.r = r; lo.s = c.lora_scale;
-    if (r > 0) {  // operand copies of the fp32 adapters, once per call: A as (hi, lo) row planes, B as [hi | hi | lo] K-extension columns
-        LoraSplitArgs sa;
-        sa.w = w.lora_a; sa.rows = r; sa.cols = D; sa.nmat = 8; sa.in_bstride = (long)r * D; sa.sp = W(scratch, L.a_sp); sa.sp_bstride = 2L * r * D;
-        FTMI_TRY(lora_split(sa, st));
-        LoraSplitArgs sb;
-        sb.w = w.lora_b; sb.rows = D; sb.cols = r; sb.nmat = 8; sb.in_bstride = (long)D * r; sb.ext = W(scratch, L.b_ext); sb.ext_bstride = 3L * D * r; sb.ld_ext = 3 * r;
-        FTMI_TRY(lora_split(sb, st));
-        lo.sp = W(scratch, L.a_sp); lo.ext = W(scratch, L.b_ext);
-    }
-    bf16_t *n1 = W(saved, L.n1), *qkv = W(saved, L.qkv), *qn = W(saved, L.qn), *kn = W(saved, L.kn), *o1 = W(saved, L.o1), *a1 = W(scratch, L.a1), *x1 = W(saved, L.x1);
+    const long mb = 6L * D;  // sample stride of the modulation rows
+    hipStream_t st = k.st;
+    auto P = [&](size_t off) { return k.params + off; };
+    auto MOD = [&](int i) { return k.mod + (size_t)i * D; };
     // self-attention
     {
-        WanRowArgs a = row_args(x, D, n1, D, M, D, S, eps);
+        WanRowArgs a = row_args(k.x, D, L.n1, D, M, D, S, eps);
         a.shift = MOD(0); a.scale = MOD(1); a.mod_bstride = mb;
         FTMI_TRY(wan_ln_fwd(a, st));
     }
-    FTMI_TRY(lora_linear_fwd(lo, n1, M, D, P(O.w_qkv1), P(O.b_qkv1), 0, 3, W(saved, L.xa_qkv), qkv, V, st));
+    FTMI_TRY(proj_fwd(k, L.n1, M, D, P(O.w_qkv1), P(O.b_qkv1), 3 * D, 0, 3, L.xa_qkv, L.qkv));
     for (int i = 0; i < 2; ++i) {
-        WanRowArgs a = row_args(qkv + (size_t)i * D, 3 * D, i ? kn : qn, D, M, D, S, eps);
-        a.w = P(i ? O.nk1 : O.nq1); a.rope_cos = rope_cos; a.rope_sin = rope_sin; a.head_dim = 128;
+        WanRowArgs a = row_args(L.qkv + (size_t)i * D, 3 * D, i ? L.kn : L.qn, D, M, D, S, eps);
+        a.w = P(i ? O.nk1 : O.nq1); a.rope_cos = k.rope_cos; a.rope_sin = k.rope_sin; a.head_dim = 128;
         FTMI_TRY(wan_rms_rope_fwd(a, st));
     }
+    FTMI_TRY(attn_fwd(attn_args(c, L.qn, L.kn, L.qkv, 3 * D, L.o1, L.lse1, S, S), st));
+    FTMI_TRY(proj_fwd(k, L.o1, M, D, P(O.w_o1), P(O.b_o1), D, 3, 1, L.xa_o1, L.a1));
     {
-        AttnArgs a = attn_base(B, c.H, S, S);
-        a.q = qn; tok_strides(a.q_sb, a.q_sh, a.q_ss, S, D);
-        a.k = kn; tok_strides(a.k_sb, a.k_sh, a.k_ss, S, D);
-        a.v = qkv + 2 * D; tok_strides(a.v_sb, a.v_sh, a.v_ss, S, 3 * D);
-        a.o = o1; tok_strides(a.o_sb, a.o_sh, a.o_ss, S, D);
-        a.lse2 = WF(saved, L.lse1);
-        FTMI_TRY(attn_fwd(a, st));
-    }
-    FTMI_TRY(lora_linear_fwd(lo, o1, M, D, P(O.w_o1), P(O.b_o1), 3, 1, W(saved, L.xa_o1), a1, V, st));
-    {
-        WanRowArgs a = row_args(x, D, x1, D, M, D, S, eps);
-        a.scale = MOD(2); a.mod_bstride = mb; a.dy = a1; a.ld_dy = D;
+        WanRowArgs a = row_args(k.x, D, L.x1, D, M, D, S, eps);
+        a.scale = MOD(2); a.mod_bstride = mb; a.dy = L.a1; a.ld_dy = D;
         FTMI_TRY(wan_gate_res_fwd(a, st));
     }
-    // cross-attention to the text tokens
-    bf16_t *n2 = W(saved, L.n2), *q2 = W(saved, L.q2), *kv2 = W(saved, L.kv2), *q2n = W(saved, L.q2n), *k2n = W(saved, L.k2n), *o2 = W(saved, L.o2), *x2 = W(saved, L.x2);
+    // cross-attention to the text tokens (no rotary embedding, no gate)
     {
-        WanRowArgs a = row_args(x1, D, n2, D, M, D, S, eps);
+        WanRowArgs a = row_args(L.x1, D, L.n2, D, M, D, S, eps);
         a.w = P(O.n2w); a.b = P(O.n2b);
         FTMI_TRY(wan_ln_fwd(a, st));
     }
-    FTMI_TRY(lora_linear_fwd(lo, n2, M, D, P(O.w_q2), P(O.b_q2), 4, 1, W(saved, L.xa_q2), q2, V, st));
-    FTMI_TRY(lora_linear_fwd(lo, enc, Mt, D, P(O.w_kv2), P(O.b_kv2), 5, 2, W(saved, L.xa_kv2), kv2, V, st));
+    FTMI_TRY(proj_fwd(k, L.n2, M, D, P(O.w_q2), P(O.b_q2), D, 4, 1, L.xa_q2, L.q2));
+    FTMI_TRY(proj_fwd(k, k.enc, Mt, D, P(O.w_kv2), P(O.b_kv2), 2 * D, 5, 2, L.xa_kv2, L.kv2));
     {
-        WanRowArgs a = row_args(q2, D, q2n, D, M, D, S, eps);
+        WanRowArgs a = row_args(L.q2, D, L.q2n, D, M, D, S, eps);
         a.w = P(O.nq2);
         FTMI_TRY(wan_rms_rope_fwd(a, st));
-        WanRowArgs b = row_args(kv2, 2 * D, k2n, D, Mt, D, T, eps);
+        WanRowArgs b = row_args(L.kv2, 2 * D, L.k2n, D, Mt, D, T, eps);
         b.w = P(O.nk2);
         FTMI_TRY(wan_rms_rope_fwd(b, st));
     }
+    FTMI_TRY(attn_fwd(attn_args(c, L.q2n, L.k2n, L.kv2, 2 * D, L.o2, L.lse2, S, T), st));
+    bf16_t* a2 = L.f;  // (the feed-forward output buffer doubles as the staging of o2 W_o2^T + b: it is consumed by the next launch)
+    FTMI_TRY(proj_fwd(k, L.o2, M, D, P(O.w_o2), P(O.b_o2), D, 7, 1, L.xa_o2, a2));
     {
-        AttnArgs a = attn_base(B, c.H, S, T);
-        a.q = q2n; tok_strides(a.q_sb, a.q_sh, a.q_ss, S, D);
-        a.k = k2n; tok_strides(a.k_sb, a.k_sh, a.k_ss, T, D);
-        a.v = kv2 + D; tok_strides(a.v_sb, a.v_sh, a.v_ss, T, 2 * D);
-        a.o = o2; tok_strides(a.o_sb, a.o_sh, a.o_ss, S, D);
-        a.lse2 = WF(saved, L.lse2);
-        FTMI_TRY(attn_fwd(a, st));
-    }
-    bf16_t* a2 = W(scratch, L.f);  // (the feed-forward output buffer doubles as the staging of o2 W_o2^T + b: it is consumed by the next launch)
-    FTMI_TRY(lora_linear_fwd(lo, o2, M, D, P(O.w_o2), P(O.b_o2), 7, 1, W(saved, L.xa_o2), a2, V, st));
-    {
-        WanRowArgs a = row_args(x1, D, x2, D, M, D, S, eps);
+        WanRowArgs a = row_args(L.x1, D, L.x2, D, M, D, S, eps);
         a.dy = a2; a.ld_dy = D;
         FTMI_TRY(wan_gate_res_fwd(a, st));
     }
-    // feed-forward (frozen: only the pre-activation is kept)
-    bf16_t *n3 = W(scratch, L.n3), *act = W(scratch, L.act), *pre = W(saved, L.pre), *f = W(scratch, L.f);
+    // feed-forward
     {
-        WanRowArgs a = row_args(x2, D, n3, D, M, D, S, eps);
+        WanRowArgs a = row_args(L.x2, D, L.n3, D, M, D, S, eps);
         a.shift = MOD(3); a.scale = MOD(4); a.mod_bstride = mb;
         FTMI_TRY(wan_ln_fwd(a, st));
     }
     {
         GemmNtArgs a;  // GELU-tanh, pre-activation kept
-        a.X = n3; a.ldx = D; a.W = P(O.w_f1); a.ldw = D; a.M = M; a.N = F; a.K = D; a.bias = P(O.b_f1); a.out = act; a.ldo = F; a.out2 = pre; a.ldo2 = F;
-        a.epi = EPI_GELU; a.variant = V;
+        a.X = L.n3; a.ldx = D; a.W = P(O.w_f1); a.ldw = D; a.M = M; a.N = F; a.K = D; a.bias = P(O.b_f1); a.out = L.act; a.ldo = F; a.out2 = L.pre; a.ldo2 = F;
+        a.epi = EPI_GELU; a.variant = c.gemm_variant;
         FTMI_TRY(gemm_nt(a, st));
     }
     if (!out) return 0;
-    FTMI_TRY(linear(act, F, M, F, P(O.w_f2), P(O.b_f2), D, f, D, V, st));
+    FTMI_TRY(proj_fwd(k, L.act, M, F, P(O.w_f2), P(O.b_f2), D, 0, 0, nullptr, L.f));
     {
-        WanRowArgs a = row_args(x2, D, out, D, M, D, S, eps);
-        a.scale = MOD(5); a.mod_bstride = mb; a.dy = f; a.ld_dy = D;
+        WanRowArgs a = row_args(L.x2, D, out, D, M, D, S, eps);
+        a.scale = MOD(5); a.mod_bstride = mb; a.dy = L.f; a.ld_dy = D;
         FTMI_TRY(wan_gate_res_fwd(a, st));
     }
     return 0;
 }
 
-// dx [B, S, D] written; denc [B, T, D] written, or NULL (frozen text embedder: its GEMM is skipped); grad_a fp32 [8, r, D] / grad_b fp32 [8, D, r] ADDED to.
+// dx [B, S, D] written; denc [B, T, D] written, or null (frozen text embedder: its GEMM is skipped).  A frozen base (k.grads == k.dmod == null) turns every
+// base-gradient launch and every row-wise reduction off through the null pointers G and DMOD return.
+int block_backward(const Block& k, const bf16_t* dout, bf16_t* dx, bf16_t* denc) {
+    const ftmi_wan_block_config& c = k.c;
+    const Bufs& L = k.L;
+    const Offsets O = offsets_of(c.D, c.F);
+    const int B = c.B, S = c.S, T = c.T, D = c.D, F = c.F, M = B * S, Mt = B * T;
+    const float eps = c.eps;
+    const long mb = 6L * D;
+    hipStream_t st = k.st;
+    auto P = [&](size_t off) { return k.params + off; };
+    auto G = [&](size_t off) { return k.grads ? k.grads + off : nullptr; };
+    auto MOD = [&](int i) { return k.mod + (size_t)i * D; };
+    auto DMOD = [&](int i) { return k.dmod ? k.dmod + (size_t)i * B * D : nullptr; };
+    const int per_batch = k.dmod != nullptr;
+    // y = d out * gate;  d gate += sum d out * branch when the gate trains (the only reader of the branch output)
+    auto gate_bwd = [&](const bf16_t* d_out, bf16_t* y, const bf16_t* branch, int gate) {
+        WanRowArgs a = row_args(d_out, D, y, D, M, D, S, eps);
+        a.scale = MOD(gate); a.mod_bstride = mb; a.red1 = DMOD(gate); a.red_per_batch = per_batch;
+        if (a.red1) { a.dy = branch; a.ld_dy = D; }
+        return wan_gate_res_bwd(a, st);
+    };
+
+    // feed-forward branch: out = x2 + f * gate_ff
+    FTMI_TRY(gate_bwd(dout, L.df, L.f, 5));
+    FTMI_TRY(linear_grads(L.df, D, L.act, F, M, D, F, G(O.w_f2), G(O.b_f2), st));
+    {
+        GemmNtArgs a;  // (d f W2) * gelu'(pre)
+        a.X = L.df; a.ldx = D; a.W = k.t.f2; a.ldw = D; a.M = M; a.N = F; a.K = D; a.out = L.dpre; a.ldo = F; a.epi = EPI_DGELU; a.aux = L.pre; a.ldaux = F;
+        a.variant = c.gemm_variant;
+        FTMI_TRY(gemm_nt(a, st));
+    }
+    FTMI_TRY(proj_bwd(k, L.n3, L.dpre, M, F, D, k.t.f1, 0, 0, nullptr, L.dn3, G(O.w_f1), G(O.b_f1)));
+    {
+        WanRowArgs a = row_args(L.x2, D, L.dx2, D, M, D, S, eps);
+        a.scale = MOD(4); a.mod_bstride = mb; a.dy = L.dn3; a.ld_dy = D; a.dres = dout; a.red1 = DMOD(3); a.red2 = DMOD(4); a.red_per_batch = per_batch;
+        FTMI_TRY(wan_ln_bwd(a, st));
+    }
+    // cross-attention branch: x2 = x1 + a2
+    FTMI_TRY(proj_bwd(k, L.o2, L.dx2, M, D, D, k.t.o2, 7, 1, L.xa_o2, L.do2, G(O.w_o2), G(O.b_o2)));
+    FTMI_TRY(attn_bwd(attn_bwd_args(attn_args(c, L.q2n, L.k2n, L.kv2, 2 * D, L.o2, L.lse2, S, T), L.do2, L.dq2n, L.dk2n, L.dkv2, L.delta), st));
+    {
+        WanRowArgs a = row_args(L.q2, D, L.dq2, D, M, D, S, eps);
+        a.w = P(O.nq2); a.dy = L.dq2n; a.ld_dy = D; a.red2 = G(O.nq2);
+        FTMI_TRY(wan_rms_rope_bwd(a, st));
+        WanRowArgs b = row_args(L.kv2, 2 * D, L.dkv2, 2 * D, Mt, D, T, eps);
+        b.w = P(O.nk2); b.dy = L.dk2n; b.ld_dy = D; b.red2 = G(O.nk2);
+        FTMI_TRY(wan_rms_rope_bwd(b, st));
+    }
+    FTMI_TRY(linear_grads(L.dq2, D, L.n2, D, M, D, D, G(O.w_q2), G(O.b_q2), st));  // (attn2.to_q's weight gradient goes ahead of the text rows' projection)
+    FTMI_TRY(proj_bwd(k, k.enc, L.dkv2, Mt, 2 * D, D, k.t.kv2, 5, 2, L.xa_kv2, denc, G(O.w_kv2), G(O.b_kv2)));
+    FTMI_TRY(proj_bwd(k, L.n2, L.dq2, M, D, D, k.t.q2, 4, 1, L.xa_q2, L.dn2, nullptr, nullptr));
+    {
+        WanRowArgs a = row_args(L.x1, D, L.dx1, D, M, D, S, eps);
+        a.w = P(O.n2w); a.dy = L.dn2; a.ld_dy = D; a.dres = L.dx2; a.red1 = G(O.n2b); a.red2 = G(O.n2w);
+        FTMI_TRY(wan_ln_bwd(a, st));
+    }
+    // self-attention branch: x1 = x + a1 * gate_msa
+    FTMI_TRY(gate_bwd(L.dx1, L.da1, L.a1, 2));
+    FTMI_TRY(proj_bwd(k, L.o1, L.da1, M, D, D, k.t.o1, 3, 1, L.xa_o1, L.do1, G(O.w_o1), G(O.b_o1)));
+    FTMI_TRY(attn_bwd(attn_bwd_args(attn_args(c, L.qn, L.kn, L.qkv, 3 * D, L.o1, L.lse1, S, S), L.do1, L.dqn, L.dkn, L.dqkv, L.delta), st));
+    for (int i = 0; i < 2; ++i) {
+        WanRowArgs a = row_args(L.qkv + (size_t)i * D, 3 * D, L.dqkv + (size_t)i * D, 3 * D, M, D, S, eps);
+        a.w = P(i ? O.nk1 : O.nq1); a.dy = i ? L.dkn : L.dqn; a.ld_dy = D; a.red2 = G(i ? O.nk1 : O.nq1); a.rope_cos = k.rope_cos; a.rope_sin = k.rope_sin; a.head_dim = 128;
+        FTMI_TRY(wan_rms_rope_bwd(a, st));
+    }
+    // the three projections' input gradients (and their adapters') summed in the fp32 accumulator
+    FTMI_TRY(proj_bwd(k, L.n1, L.dqkv, M, 3 * D, D, k.t.qkv1, 0, 3, L.xa_qkv, L.dn1, G(O.w_qkv1), G(O.b_qkv1)));
+    {
+        WanRowArgs a = row_args(k.x, D, dx, D, M, D, S, eps);
+        a.scale = MOD(1); a.mod_bstride = mb; a.dy = L.dn1; a.ld_dy = D; a.dres = L.dx1; a.red1 = DMOD(0); a.red2 = DMOD(1); a.red_per_batch = per_batch;
+        FTMI_TRY(wan_ln_bwd(a, st));
+    }
+    return 0;
+}
+
+Block make_block(const ftmi_wan_block_config& c, const void* params, const Bufs& L, const bf16_t* x, const bf16_t* enc, const float* mod, const float* rope_cos,
+                 const float* rope_sin, hipStream_t st) {
+    Block k;
+    k.c = c; k.params = reinterpret_cast<const bf16_t*>(params); k.L = L; k.x = x; k.enc = enc; k.mod = mod; k.rope_cos = rope_cos; k.rope_sin = rope_sin; k.st = st;
+    return k;
+}
+
+}  // namespace
+
+size_t wan_block_saved_bytes(const ftmi_wan_block_config& c) { return make_layout(c, 0, false).saved_total; }
+size_t wan_block_scratch_bytes(const ftmi_wan_block_config& c) { return make_layout(c, 0, false).scratch_total; }
+size_t wan_block_param_elements(const ftmi_wan_block_config& c) { return offsets_of(c.D, c.F).total; }
+size_t wan_lora_block_saved_bytes(const ftmi_wan_lora_block_config& c) { return make_layout(base_cfg(c), c.r, true).saved_total; }
+size_t wan_lora_block_scratch_bytes(const ftmi_wan_lora_block_config& c) { return make_layout(base_cfg(c), c.r, true).scratch_total; }
+
+int wan_block_forward(const ftmi_wan_block_config& c, const bf16_t* params, const bf16_t* x, const bf16_t* enc, const float* mod, const float* rope_cos,
+                      const float* rope_sin, bf16_t* out, void* saved, size_t saved_bytes, hipStream_t st) {
+    FTMI_TRY(check_cfg(c));
+    const Bufs L = make_layout(c, 0, false, saved);
+    if (saved_bytes < L.saved_total) return set_error(FTMI_ERR_INVALID, "wan_block_forward: saved buffer too small");
+    return block_forward(make_block(c, params, L, x, enc, mod, rope_cos, rope_sin, st), out);
+}
+
+// grads: the block's flat fp32 gradient buffer (ADDED to); dmod fp32 [6, B, D] (ADDED to: column sums of d shift / d scale / d gate per sample);
+// dx [B, S, D], denc [B, T, D] written.
+int wan_block_backward(const ftmi_wan_block_config& c, const bf16_t* params, float* grads, const bf16_t* x, const bf16_t* enc, const float* mod,
+                       const float* rope_cos, const float* rope_sin, const bf16_t* dout, bf16_t* dx, bf16_t* denc, float* dmod, void* saved,
+                       size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st) {
+    FTMI_TRY(check_cfg(c));
+    const Bufs L = make_layout(c, 0, false, saved, scratch);
+    if (saved_bytes < L.saved_total || scratch_bytes < L.scratch_total) return set_error(FTMI_ERR_INVALID, "wan_block_backward: buffer too small");
+    Block k = make_block(c, params, L, x, enc, mod, rope_cos, rope_sin, st);
+    k.grads = grads; k.dmod = dmod;
+    const Offsets O = offsets_of(c.D, c.F);
+    const int D = c.D, F = c.F;
+    // the weights train: their K-contiguous copies are made per call
+    FTMI_TRY(transpose_bf16(params + O.w_f2, L.t_f2, D, F, st));
+    FTMI_TRY(transpose_bf16(params + O.w_f1, L.t_f1, F, D, st));
+    FTMI_TRY(transpose_bf16(params + O.w_o2, L.t_o2, D, D, st));
+    FTMI_TRY(transpose_bf16(params + O.w_q2, L.t_q2, D, D, st));
+    FTMI_TRY(transpose_bf16(params + O.w_kv2, L.t_kv2, 2 * D, D, st));
+    FTMI_TRY(transpose_bf16(params + O.w_o1, L.t_o1, D, D, st));
+    FTMI_TRY(transpose_bf16(params + O.w_qkv1, L.t_qkv1, 3 * D, D, st));
+    k.t.qkv1 = L.t_qkv1; k.t.o1 = L.t_o1; k.t.q2 = L.t_q2; k.t.kv2 = L.t_kv2; k.t.o2 = L.t_o2; k.t.f1 = L.t_f1; k.t.f2 = L.t_f2;
+    return block_backward(k, dout, dx, denc);
+}
+
+int wan_lora_block_forward(const ftmi_wan_lora_block_config& c, const ftmi_wan_lora_block_weights& w, const bf16_t* x, const bf16_t* enc, const float* mod,
+                           const float* rope_cos, const float* rope_sin, bf16_t* out, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
+                           hipStream_t st) {
+    FTMI_TRY(check_lora_cfg(c));
+    const Bufs L = make_layout(base_cfg(c), c.r, true, saved, scratch);
+    if (saved_bytes < L.saved_total || scratch_bytes < L.scratch_total) return set_error(FTMI_ERR_INVALID, "wan_lora_block_forward: buffer too small");
+    if (c.r > 0 && (!w.lora_a || !w.lora_b)) return set_error(FTMI_ERR_INVALID, "wan_lora_block_forward: LoRA rank without adapters");
+    Block k = make_block(base_cfg(c), w.params, L, x, enc, mod, rope_cos, rope_sin, st);
+    const int D = c.D, r = c.r;
+    k.lo.r = r; k.lo.s = c.lora_scale;
+    if (r > 0) {  // operand copies of the fp32 adapters, once per call: A as (hi, lo) row planes, B as [hi | hi | lo] K-extension columns
+        LoraSplitArgs sa;
+        sa.w = w.lora_a; sa.rows = r; sa.cols = D; sa.nmat = 8; sa.in_bstride = (long)r * D; sa.sp = L.a_sp; sa.sp_bstride = 2L * r * D;
+        FTMI_TRY(lora_split(sa, st));
+        LoraSplitArgs sb;
+        sb.w = w.lora_b; sb.rows = D; sb.cols = r; sb.nmat = 8; sb.in_bstride = (long)D * r; sb.ext = L.b_ext; sb.ext_bstride = 3L * D * r; sb.ld_ext = 3 * r;
+        FTMI_TRY(lora_split(sb, st));
+        k.lo.sp = L.a_sp; k.lo.ext = L.b_ext;
+    }
+    return block_forward(k, out);
+}
+
+// grad_a fp32 [8, r, D] / grad_b fp32 [8, D, r] ADDED to.
 int wan_lora_block_backward(const ftmi_wan_lora_block_config& c, const ftmi_wan_lora_block_weights& w, const bf16_t* x, const bf16_t* enc, const float* mod,
                             const float* rope_cos, const float* rope_sin, const bf16_t* dout, bf16_t* dx, bf16_t* denc, float* grad_a, float* grad_b, void* saved,
                             size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st) {
     FTMI_TRY(check_lora_cfg(c));
-    const WanLoraLayout L = make_lora_layout(c);
+    const Bufs L = make_layout(base_cfg(c), c.r, true, saved, scratch);
     if (saved_bytes < L.saved_total || scratch_bytes < L.scratch_total) return set_error(FTMI_ERR_INVALID, "wan_lora_block_backward: buffer too small");
     if (c.r > 0 && (!w.lora_a || !w.lora_b || !grad_a || !grad_b)) return set_error(FTMI_ERR_INVALID, "wan_lora_block_backward: LoRA rank without adapters / gradient buffers");
     if (!w.w_qkv1_t || !w.w_o1_t || !w.w_q2_t || !w.w_kv2_t || !w.w_o2_t || !w.w_f1_t || !w.w_f2_t)
         return set_error(FTMI_ERR_INVALID, "wan_lora_block_backward: transposed weights missing");
-    const Offsets O = offsets_of(c.D, c.F);
-    const bf16_t* params = reinterpret_cast<const bf16_t*>(w.params);
-    const int B = c.B, S = c.S, T = c.T, D = c.D, F = c.F, M = B * S, Mt = B * T, V = c.gemm_variant, r = c.r;
-    const float eps = c.eps;
-    const long mb = 6L * D;
-    auto P = [&](size_t off) { return params + off; };
-    auto MOD = [&](int i) { return mod + (size_t)i * D; };
+    Block k = make_block(base_cfg(c), w.params, L, x, enc, mod, rope_cos, rope_sin, st);
     auto WT = [](const void* p) { return reinterpret_cast<const bf16_t*>(p); };
-    LoraOps lo;
-    lo.r = r; lo.s = c.lora_scale;
+    k.t.qkv1 = WT(w.w_qkv1_t); k.t.o1 = WT(w.w_o1_t); k.t.q2 = WT(w.w_q2_t); k.t.kv2 = WT(w.w_kv2_t); k.t.o2 = WT(w.w_o2_t); k.t.f1 = WT(w.w_f1_t); k.t.f2 = WT(w.w_f2_t);
+    k.grad_a = grad_a; k.grad_b = grad_b;
+    const int D = c.D, r = c.r;
+    k.lo.r = r; k.lo.s = c.lora_scale;
     if (r > 0) {
         LoraSplitArgs sb;  // B^T as (hi, lo) row planes: operand of dXA = s * dY B
-        sb.w = w.lora_b; sb.rows = D; sb.cols = r; sb.nmat = 8; sb.in_bstride = (long)D * r; sb.t_sp = W(scratch, L.bt_sp); sb.t_sp_bstride = 2L * r * D;
+        sb.w = w.lora_b; sb.rows = D; sb.cols = r; sb.nmat = 8; sb.in_bstride = (long)D * r; sb.t_sp = L.bt_sp; sb.t_sp_bstride = 2L * r * D;
         FTMI_TRY(lora_split(sb, st));
         LoraSplitArgs sa;  // A^T as K-extension columns, the eight adapters side by side [D, 24r]: dx += dXA A, fused projections take adjacent column groups
-        sa.w = w.lora_a; sa.rows = r; sa.cols = D; sa.nmat = 8; sa.in_bstride = (long)r * D; sa.t_ext = W(scratch, L.at_ext); sa.t_ext_bstride = 3L * r; sa.ld_t_ext = 24L * r;
+        sa.w = w.lora_a; sa.rows = r; sa.cols = D; sa.nmat = 8; sa.in_bstride = (long)r * D; sa.t_ext = L.at_ext; sa.t_ext_bstride = 3L * r; sa.ld_t_ext = 24L * r;
         FTMI_TRY(lora_split(sa, st));
-        lo.sp = W(scratch, L.bt_sp); lo.ext = W(scratch, L.at_ext);
+        k.lo.sp = L.bt_sp; k.lo.ext = L.at_ext;
     }
-    const bf16_t *n1 = W(saved, L.n1), *qkv = W(saved, L.qkv), *qn = W(saved, L.qn), *kn = W(saved, L.kn), *o1 = W(saved, L.o1), *x1 = W(saved, L.x1);
-    const bf16_t *n2 = W(saved, L.n2), *q2 = W(saved, L.q2), *kv2 = W(saved, L.kv2), *q2n = W(saved, L.q2n), *k2n = W(saved, L.k2n), *o2 = W(saved, L.o2), *x2 = W(saved, L.x2);
-    const bf16_t* pre = W(saved, L.pre);
-    bf16_t* dxa = W(scratch, L.dxa);
-
-    // feed-forward branch: out = x2 + f * gate_ff
-    bf16_t* df = W(scratch, L.df);
-    {
-        WanRowArgs a = row_args(dout, D, df, D, M, D, S, eps);
-        a.scale = MOD(5); a.mod_bstride = mb;
-        FTMI_TRY(wan_gate_res_bwd(a, st));
-    }
-    bf16_t* dpre = W(scratch, L.dpre);
-    {
-        GemmNtArgs a;  // (d f W2) * gelu'(pre)
-        a.X = df; a.ldx = D; a.W = WT(w.w_f2_t); a.ldw = D; a.M = M; a.N = F; a.K = D; a.out = dpre; a.ldo = F; a.epi = EPI_DGELU; a.aux = pre; a.ldaux = F; a.variant = V;
-        FTMI_TRY(gemm_nt(a, st));
-    }
-    bf16_t* dn3 = W(scratch, L.dn3);
-    FTMI_TRY(linear(dpre, F, M, F, WT(w.w_f1_t), nullptr, D, dn3, D, V, st));
-    bf16_t* dx2 = W(scratch, L.dx2);
-    {
-        WanRowArgs a = row_args(x2, D, dx2, D, M, D, S, eps);
-        a.scale = MOD(4); a.mod_bstride = mb; a.dy = dn3; a.ld_dy = D; a.dres = dout;
-        FTMI_TRY(wan_ln_bwd(a, st));
-    }
-    // cross-attention branch: x2 = x1 + a2
-    bf16_t* do2 = W(scratch, L.do2);
-    FTMI_TRY(lora_linear_bwd(lo, o2, dx2, M, D, WT(w.w_o2_t), 7, 1, W(saved, L.xa_o2), dxa, do2, grad_a, grad_b, V, st));
-    bf16_t *dkv2 = W(scratch, L.dkv2), *dq2n = W(scratch, L.dq2n), *dk2n = W(scratch, L.dk2n);
-    {
-        AttnArgs a = attn_base(B, c.H, S, T);
-        a.q = q2n; tok_strides(a.q_sb, a.q_sh, a.q_ss, S, D);
-        a.k = k2n; tok_strides(a.k_sb, a.k_sh, a.k_ss, T, D);
-        a.v = kv2 + D; tok_strides(a.v_sb, a.v_sh, a.v_ss, T, 2 * D);
-        a.o = const_cast<bf16_t*>(o2); tok_strides(a.o_sb, a.o_sh, a.o_ss, S, D);
-        a.lse2 = WF(saved, L.lse2);
-        a.dout = do2; tok_strides(a.do_sb, a.do_sh, a.do_ss, S, D);
-        a.dq = dq2n; tok_strides(a.dq_sb, a.dq_sh, a.dq_ss, S, D);
-        a.dk = dk2n; tok_strides(a.dk_sb, a.dk_sh, a.dk_ss, T, D);
-        a.dv = dkv2 + D; tok_strides(a.dv_sb, a.dv_sh, a.dv_ss, T, 2 * D);
-        a.delta = WF(scratch, L.delta);
-        FTMI_TRY(attn_bwd(a, st));
-    }
-    bf16_t* dq2 = W(scratch, L.dq2);
-    {
-        WanRowArgs a = row_args(q2, D, dq2, D, M, D, S, eps);
-        a.w = P(O.nq2); a.dy = dq2n; a.ld_dy = D;
-        FTMI_TRY(wan_rms_rope_bwd(a, st));
-        WanRowArgs b = row_args(kv2, 2 * D, dkv2, 2 * D, Mt, D, T, eps);
-        b.w = P(O.nk2); b.dy = dk2n; b.ld_dy = D;
-        FTMI_TRY(wan_rms_rope_bwd(b, st));
-    }
-    FTMI_TRY(lora_linear_bwd(lo, enc, dkv2, Mt, D, WT(w.w_kv2_t), 5, 2, W(saved, L.xa_kv2), dxa, denc, grad_a, grad_b, V, st));
-    bf16_t* dn2 = W(scratch, L.dn2);
-    FTMI_TRY(lora_linear_bwd(lo, n2, dq2, M, D, WT(w.w_q2_t), 4, 1, W(saved, L.xa_q2), dxa, dn2, grad_a, grad_b, V, st));
-    bf16_t* dx1 = W(scratch, L.dx1);
-    {
-        WanRowArgs a = row_args(x1, D, dx1, D, M, D, S, eps);
-        a.w = P(O.n2w); a.dy = dn2; a.ld_dy = D; a.dres = dx2;
-        FTMI_TRY(wan_ln_bwd(a, st));
-    }
-    // self-attention branch: x1 = x + a1 * gate_msa
-    bf16_t* da1 = W(scratch, L.da1);
-    {
-        WanRowArgs a = row_args(dx1, D, da1, D, M, D, S, eps);
-        a.scale = MOD(2); a.mod_bstride = mb;
-        FTMI_TRY(wan_gate_res_bwd(a, st));
-    }
-    bf16_t* do1 = W(scratch, L.do1);
-    FTMI_TRY(lora_linear_bwd(lo, o1, da1, M, D, WT(w.w_o1_t), 3, 1, W(saved, L.xa_o1), dxa, do1, grad_a, grad_b, V, st));
-    bf16_t *dqkv = W(scratch, L.dqkv), *dqn = W(scratch, L.dqn), *dkn = W(scratch, L.dkn);
-    {
-        AttnArgs a = attn_base(B, c.H, S, S);
-        a.q = qn; tok_strides(a.q_sb, a.q_sh, a.q_ss, S, D);
-        a.k = kn; tok_strides(a.k_sb, a.k_sh, a.k_ss, S, D);
-        a.v = qkv + 2 * D; tok_strides(a.v_sb, a.v_sh, a.v_ss, S, 3 * D);
-        a.o = const_cast<bf16_t*>(o1); tok_strides(a.o_sb, a.o_sh, a.o_ss, S, D);
-        a.lse2 = WF(saved, L.lse1);
-        a.dout = do1; tok_strides(a.do_sb, a.do_sh, a.do_ss, S, D);
-        a.dq = dqn; tok_strides(a.dq_sb, a.dq_sh, a.dq_ss, S, D);
-        a.dk = dkn; tok_strides(a.dk_sb, a.dk_sh, a.dk_ss, S, D);
-        a.dv = dqkv + 2 * D; tok_strides(a.dv_sb, a.dv_sh, a.dv_ss, S, 3 * D);
-        a.delta = WF(scratch, L.delta);
-        FTMI_TRY(attn_bwd(a, st));
-    }
-    for (int i = 0; i < 2; ++i) {
-        WanRowArgs a = row_args(qkv + (size_t)i * D, 3 * D, dqkv + (size_t)i * D, 3 * D, M, D, S, eps);
-        a.w = P(i ? O.nk1 : O.nq1); a.dy = i ? dkn : dqn; a.ld_dy = D; a.rope_cos = rope_cos; a.rope_sin = rope_sin; a.head_dim = 128;
-        FTMI_TRY(wan_rms_rope_bwd(a, st));
-    }
-    bf16_t* dn1 = W(scratch, L.dn1);  // the three projections' input gradients and their adapters' summed in the fp32 accumulator
-    FTMI_TRY(lora_linear_bwd(lo, n1, dqkv, M, D, WT(w.w_qkv1_t), 0, 3, W(saved, L.xa_qkv), dxa, dn1, grad_a, grad_b, V, st));
-    {
-        WanRowArgs a = row_args(x, D, dx, D, M, D, S, eps);
-        a.scale = MOD(1); a.mod_bstride = mb; a.dy = dn1; a.ld_dy = D; a.dres = dx1;
-        FTMI_TRY(wan_ln_bwd(a, st));
-    }
-    return 0;
+    return block_backward(k, dout, dx, denc);
 }
 
 }  // namespace ftmi

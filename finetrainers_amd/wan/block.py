@@ -13,7 +13,7 @@ with ``fully_shard``), gradients one flat fp32 buffer of the same layout (``grad
 
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Tuple
+from typing import Any, Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -92,107 +92,198 @@ class WanBlockLayout:
         return {name: self.view(flat, name) for name, _ in self.entries}
 
 
+# ---- the block as a composition of the library's launches from Python ----------------------------------------------------------------------------
+# ONE forward and ONE backward walk for full fine-tuning and for LoRA over a frozen base, launch for launch what csrc/wan_dit.hip block_forward /
+# block_backward issue: the second implementation the tests compare the C calls with (``native = False`` / ``FTMI_NATIVE_BLOCKS=0``).
+# Adapter order inside lora_A [8, r, D] / lora_B [8, D, r] (the projections the recipe's regex "blocks.*(to_q|to_k|to_v|to_out.0)" selects: BOTH attentions)
+LORA_TARGETS = ("attn1.to_q", "attn1.to_k", "attn1.to_v", "attn1.to_out.0", "attn2.to_q", "attn2.to_k", "attn2.to_v", "attn2.to_out.0")
+_TWINS = (("w_qkv1_t", "w_qkv1"), ("w_o1_t", "attn1.to_out.0.weight"), ("w_q2_t", "attn2.to_q.weight"), ("w_kv2_t", "w_kv2"), ("w_o2_t", "attn2.to_out.0.weight"),
+          ("w_f1_t", "ffn.net.0.proj.weight"), ("w_f2_t", "ffn.net.2.weight"))
+
+
+class _Lora(NamedTuple):
+    """One call's adapters (None: no adapters, r = 0) and, for the backward, where their gradients are added."""
+    a: Optional[torch.Tensor] = None  # fp32 [8, r, D]
+    b: Optional[torch.Tensor] = None  # fp32 [8, D, r]
+    ga: Optional[torch.Tensor] = None
+    gb: Optional[torch.Tensor] = None
+
+    @property
+    def r(self) -> int:
+        return 0 if self.a is None else int(self.a.shape[1])
+
+
+class _Acts(NamedTuple):
+    """What the forward walk leaves for the backward.  a1, n3, act and f are read only by gradients of base parameters (gate_msa, W_1, W_2, gate_ff): a
+    frozen base drops them; xa_*: the adapters' down-projected rows (None at r = 0)."""
+    n1: Any; qkv: Any; qn: Any; kn: Any; o1: Any; lse1: Any; a1: Any; x1: Any; n2: Any; q2: Any; kv2: Any; q2n: Any; k2n: Any; o2: Any; lse2: Any; x2: Any
+    n3: Any; act: Any; pre: Any; f: Any; xa_qkv: Any; xa_o1: Any; xa_q2: Any; xa_kv2: Any; xa_o2: Any
+
+    def for_frozen_base(self) -> "_Acts":
+        return self._replace(a1=None, n3=None, act=None, f=None)
+
+
+def _lora_linear_fwd(x, w, bias, adp: int, nadp: int, a_sp, b_ext, r: int, s: float):
+    """[rows, nadp D] = x W^T + b + s (x A^T) B^T for the adapters adp .. adp + nadp - 1 on one input: the two launches of csrc/wan_dit.hip proj_fwd.
+    Returns (y, xa [rows, 3 nadp r])."""
+    if r == 0:
+        return ops.gemm_nt(x, w, bias), None
+    rows, D = x.shape
+    xa = torch.empty((rows, 3 * nadp * r), dtype=bf16, device=x.device)
+    ops.gemm_nt_ex(x, a_sp[adp:adp + nadp].reshape(2 * nadp * r, D), xa, M=rows, N=2 * nadp * r, K=D, alpha=s, split_r=r, variant=8)
+    y = torch.empty((rows, nadp * D), dtype=bf16, device=x.device)
+    grp = dict(x2_grp_n=D, x2_grp_stride=3 * r) if nadp > 1 else {}
+    ops.gemm_nt_ex(x, w, y, M=rows, N=nadp * D, K=D, bias=bias, x2=xa, w2=b_ext[adp:adp + nadp].reshape(nadp * D, 3 * r), K2=3 * r, variant=8, **grp)
+    return y, xa
+
+
+def _linear_grads(dy, inp, gw, gbias):
+    """dW += dY^T X (fp32, token-reduction GEMM), db += column sums of dY; nothing when the base is frozen (gw None)."""
+    if gw is not None:
+        ops.gemm_tn(dy, inp, out=gw)
+        ops.wan_colsum(dy, gbias)
+
+
+def _lora_linear_bwd(x, dy, w_t, adp: int, nadp: int, xa, bt_sp, at_ext, r: int, s: float, ga, gb, need_dx: bool = True, gw=None, gbias=None):
+    """csrc/wan_dit.hip proj_bwd, in its order: gw += dY^T x and gbias += column sums (a training base); dx = dY W (+ dXA A); gb[adp ..] += dY^T XA,
+    ga[adp ..] += dXA^T x."""
+    _linear_grads(dy, x, gw, gbias)
+    rows, D = x.shape
+    if r == 0:
+        return ops.gemm_nt(dy, w_t, None) if need_dx else None
+    dxa = torch.empty((rows, 3 * nadp * r), dtype=bf16, device=x.device)
+    grp = dict(xk_grp_n=2 * r, xk_grp_stride=D) if nadp > 1 else {}
+    ops.gemm_nt_ex(dy, bt_sp[adp:adp + nadp].reshape(2 * nadp * r, D), dxa, M=rows, N=2 * nadp * r, K=D, alpha=s, split_r=r, variant=8, **grp)
+    dx = None
+    if need_dx:
+        dx = torch.empty((rows, D), dtype=bf16, device=x.device)
+        ops.gemm_nt_ex(dy, w_t, dx, M=rows, N=D, K=nadp * D, x2=dxa, w2=at_ext[:, adp * 3 * r:(adp + nadp) * 3 * r], K2=3 * nadp * r, variant=8)
+    ops.gemm_tn_ex(dy, xa, gb[adp:adp + nadp].view(nadp * D, r), M=rows, P=nadp * D, Q=r, v_fold=r, **(dict(v_grp_p=D, v_grp_stride=3 * r) if nadp > 1 else {}))
+    ops.gemm_tn_ex(dxa, x, ga[adp:adp + nadp].view(nadp * r, D), M=rows, P=nadp * r, Q=D, u_fold=r, **(dict(u_grp_p=r, u_grp_stride=3 * r) if nadp > 1 else {}))
+    return dx
+
+
+def _block_forward(blk: "MI355XWanBlock", x, enc, mod, rope, lora: _Lora, need_out: bool = True):
+    """mod: fp32 [B, 6, D] = (shift, scale, gate) of the attention, then of the feed-forward.  Returns (out [B, S, D], _Acts); ``need_out=False`` (the
+    recomputation pass of gradient checkpointing) stops after the feed-forward's first GEMM: its pre-activation is the last thing the backward reads."""
+    B, S, D = x.shape
+    T = enc.shape[1]
+    M, H, hd, eps, s, r = B * S, blk.heads, blk.head_dim, blk.eps, blk.lora_scale, lora.r
+    P = blk.param
+    a_sp = b_ext = None
+    if r:
+        a_sp = torch.stack([ops.lora_split(lora.a[i], sp=True)[0] for i in range(8)])
+        b_ext = torch.stack([ops.lora_split(lora.b[i], ext=True)[0] for i in range(8)])
+    lin = lambda t, w, b, adp, nadp: _lora_linear_fwd(t, w, b, adp, nadp, a_sp, b_ext, r, s)
+    x2d, enc2d = x.view(M, D), enc.view(B * T, D)
+    heads = lambda t, n: t.view(B, n, H, hd).permute(0, 2, 1, 3)  # [rows, D] view (any row stride) -> [B, H, n, hd]
+    tok = lambda t: t.permute(0, 2, 1, 3).reshape(t.shape[0] * t.shape[2], D)  # attention output [B, H, n, hd] laid out [B, n, H, hd] -> [rows, D]
+    # self-attention
+    n1 = ops.wan_ln(x2d, S, shift=mod[:, 0], scale=mod[:, 1], eps=eps)
+    qkv, xa_qkv = lin(n1, P("w_qkv1"), P("b_qkv1"), 0, 3)
+    qn = ops.wan_rms_rope(qkv[:, :D], P("attn1.norm_q.weight"), S, rope=rope, head_dim=hd, eps=eps)
+    kn = ops.wan_rms_rope(qkv[:, D:2 * D], P("attn1.norm_k.weight"), S, rope=rope, head_dim=hd, eps=eps)
+    o1, lse1 = ops.attn_fwd(heads(qn, S), heads(kn, S), heads(qkv[:, 2 * D:], S))
+    a1, xa_o1 = lin(tok(o1), P("attn1.to_out.0.weight"), P("attn1.to_out.0.bias"), 3, 1)
+    x1 = ops.wan_gate_res(x2d, a1, S, gate=mod[:, 2])
+    # cross-attention to the text tokens (no rotary embedding, no gate)
+    n2 = ops.wan_ln(x1, S, w=P("norm2.weight"), b=P("norm2.bias"), eps=eps)
+    q2, xa_q2 = lin(n2, P("attn2.to_q.weight"), P("attn2.to_q.bias"), 4, 1)
+    kv2, xa_kv2 = lin(enc2d, P("w_kv2"), P("b_kv2"), 5, 2)
+    q2n = ops.wan_rms_rope(q2, P("attn2.norm_q.weight"), S, eps=eps)
+    k2n = ops.wan_rms_rope(kv2[:, :D], P("attn2.norm_k.weight"), T, eps=eps)
+    o2, lse2 = ops.attn_fwd(heads(q2n, S), heads(k2n, T), heads(kv2[:, D:], T))
+    a2, xa_o2 = lin(tok(o2), P("attn2.to_out.0.weight"), P("attn2.to_out.0.bias"), 7, 1)
+    x2 = ops.wan_gate_res(x1, a2, S)
+    # feed-forward
+    n3 = ops.wan_ln(x2, S, shift=mod[:, 3], scale=mod[:, 4], eps=eps)
+    act, pre = ops.gemm_nt(n3, P("ffn.net.0.proj.weight"), P("ffn.net.0.proj.bias"), epilogue=1, want_out2=True)  # GELU-tanh, pre-activation kept
+    f = out = None
+    if need_out:
+        f = ops.gemm_nt(act, P("ffn.net.2.weight"), P("ffn.net.2.bias"))
+        out = ops.wan_gate_res(x2, f, S, gate=mod[:, 5]).view(B, S, D)
+    return out, _Acts(n1, qkv, qn, kn, o1, lse1, a1, x1, n2, q2, kv2, q2n, k2n, o2, lse2, x2, n3, act, pre, f, xa_qkv, xa_o1, xa_q2, xa_kv2, xa_o2)
+
+
+def _block_backward(blk: "MI355XWanBlock", acts: _Acts, x, enc, mod, rope, dout, lora: _Lora, train_base: bool, need_denc: bool = True):
+    """Returns (dx [B, S, D], denc [B, T, D] or None, dmod fp32 [6, B, D] or None).  ``train_base``: all base gradients are added into ``blk.grad`` and the
+    (shift, scale, gate) sums over the tokens into dmod; a frozen base forms none of them (no weight-gradient GEMM, no bias / norm / modulation
+    reduction, and a1, n3, act and f are not read).  The adapter gradients are added into ``lora.ga / lora.gb``."""
+    c = acts
+    B, S, D = x.shape
+    T = enc.shape[1]
+    M, H, hd, eps, s, r = B * S, blk.heads, blk.head_dim, blk.eps, blk.lora_scale, lora.r
+    P, Wt = blk.param, blk.transposed()
+    G = blk.grad if train_base else (lambda name: None)
+    dmod = torch.zeros((6, B, D), dtype=torch.float32, device=x.device) if train_base else None
+    DM = (lambda i: dmod[i]) if train_base else (lambda i: None)
+    bt_sp = at_ext = None
+    if r:
+        bt_sp = torch.stack([ops.lora_split(lora.b[i], t_sp=True)[0] for i in range(8)])
+        at_ext = torch.cat([ops.lora_split(lora.a[i], t_ext=True)[0] for i in range(8)], dim=1)  # the eight adapters side by side: [D, 24r]
+
+    def lin(t, dy, w_t, adp, nadp, xa, need_dx=True, gw=None, gbias=None):
+        return _lora_linear_bwd(t, dy, w_t, adp, nadp, xa, bt_sp, at_ext, r, s, lora.ga, lora.gb, need_dx, gw, gbias)
+
+    x2d, enc2d = x.view(M, D), enc.view(B * T, D)
+    dout = dout.contiguous().view(M, D)
+    heads = lambda t, n: t.view(B, n, H, hd).permute(0, 2, 1, 3)
+    tok = lambda t: t.permute(0, 2, 1, 3).reshape(t.shape[0] * t.shape[2], D)
+    # feed-forward branch: out = x2 + f * gate_ff
+    df = ops.wan_gate_res_bwd(dout, c.f if train_base else None, mod[:, 5], S, dgate=DM(5))
+    _linear_grads(df, c.act, G("ffn.net.2.weight"), G("ffn.net.2.bias"))
+    dpre = ops.gemm_nt(df, Wt["ffn.net.2.weight"], None, epilogue=3, aux=c.pre)  # (d f W2) * gelu'(pre)
+    _linear_grads(dpre, c.n3, G("ffn.net.0.proj.weight"), G("ffn.net.0.proj.bias"))
+    dn3 = ops.gemm_nt(dpre, Wt["ffn.net.0.proj.weight"], None)
+    dx2 = ops.wan_ln_bwd(c.x2, dn3, S, scale=mod[:, 4], eps=eps, dres=dout, red1=DM(3), red2=DM(4), red_per_batch=train_base)
+    # cross-attention branch: x2 = x1 + a2
+    do2 = lin(tok(c.o2), dx2, Wt["attn2.to_out.0.weight"], 7, 1, c.xa_o2, gw=G("attn2.to_out.0.weight"), gbias=G("attn2.to_out.0.bias"))
+    dkv2 = torch.empty_like(c.kv2)
+    dq2n, dk2n, _ = ops.attn_bwd(heads(c.q2n, S), heads(c.k2n, T), heads(c.kv2[:, D:], T), c.o2, c.lse2, heads(do2, S), dv_out=heads(dkv2[:, D:], T))
+    dq2 = ops.wan_rms_rope_bwd(c.q2, P("attn2.norm_q.weight"), tok(dq2n), S, eps=eps, dweight=G("attn2.norm_q.weight"))
+    ops.wan_rms_rope_bwd(c.kv2[:, :D], P("attn2.norm_k.weight"), tok(dk2n), T, eps=eps, dweight=G("attn2.norm_k.weight"), out=dkv2[:, :D])
+    _linear_grads(dq2, c.n2, G("attn2.to_q.weight"), G("attn2.to_q.bias"))  # (attn2.to_q's weight gradient goes ahead of the text rows' projection)
+    denc = lin(enc2d, dkv2, Wt["w_kv2"], 5, 2, c.xa_kv2, need_denc, gw=G("w_kv2"), gbias=G("b_kv2"))
+    dn2 = lin(c.n2, dq2, Wt["attn2.to_q.weight"], 4, 1, c.xa_q2)
+    dx1 = ops.wan_ln_bwd(c.x1, dn2, S, w=P("norm2.weight"), eps=eps, dres=dx2, red1=G("norm2.bias"), red2=G("norm2.weight"))
+    # self-attention branch: x1 = x + a1 * gate_msa
+    da1 = ops.wan_gate_res_bwd(dx1, c.a1 if train_base else None, mod[:, 2], S, dgate=DM(2))
+    do1 = lin(tok(c.o1), da1, Wt["attn1.to_out.0.weight"], 3, 1, c.xa_o1, gw=G("attn1.to_out.0.weight"), gbias=G("attn1.to_out.0.bias"))
+    dqkv = torch.empty_like(c.qkv)
+    dqn, dkn, _ = ops.attn_bwd(heads(c.qn, S), heads(c.kn, S), heads(c.qkv[:, 2 * D:], S), c.o1, c.lse1, heads(do1, S), dv_out=heads(dqkv[:, 2 * D:], S))
+    ops.wan_rms_rope_bwd(c.qkv[:, :D], P("attn1.norm_q.weight"), tok(dqn), S, rope=rope, head_dim=hd, eps=eps, dweight=G("attn1.norm_q.weight"), out=dqkv[:, :D])
+    ops.wan_rms_rope_bwd(c.qkv[:, D:2 * D], P("attn1.norm_k.weight"), tok(dkn), S, rope=rope, head_dim=hd, eps=eps, dweight=G("attn1.norm_k.weight"),
+                         out=dqkv[:, D:2 * D])
+    dn1 = lin(c.n1, dqkv, Wt["w_qkv1"], 0, 3, c.xa_qkv, gw=G("w_qkv1"), gbias=G("b_qkv1"))  # the three projections' input gradients summed in the GEMM's fp32 accumulator
+    dx = ops.wan_ln_bwd(x2d, dn1, S, scale=mod[:, 1], eps=eps, dres=dx1, red1=DM(0), red2=DM(1), red_per_batch=train_base)
+    return dx.view(B, S, D), (denc.view(B, T, D) if denc is not None else None), dmod
+
+
 class _WanBlockFunction(torch.autograd.Function):
+    """Full fine-tuning through the Python walks: every parameter of the block trains."""
+
     @staticmethod
     def forward(ctx, blk: "MI355XWanBlock", x, enc, temb, rope_cos, rope_sin):
-        B, S, D = x.shape
         # scale_shift_table (bf16 parameter [1, 6, D]) + temb.float(): fp32 [B, 6, D] = (shift, scale, gate) of the attention, then of the feed-forward
         mod = (blk.param("scale_shift_table").float() + temb.float()).contiguous()
-        T = enc.shape[1]
-        M, H, hd = B * S, blk.heads, blk.head_dim
-        P = blk.param
-        eps = blk.eps
-        rope = (rope_cos, rope_sin)
-        x2d, enc2d = x.view(M, D), enc.view(B * T, D)
-        heads = lambda t, n: t.view(B, n, H, hd).permute(0, 2, 1, 3)  # [rows, D] view (any row stride) -> [B, H, n, hd]
-        tok = lambda t: t.permute(0, 2, 1, 3).reshape(t.shape[0] * t.shape[2], D)  # attention output [B, H, n, hd] laid out [B, n, H, hd] -> [rows, D]
-
-        # self-attention
-        n1 = ops.wan_ln(x2d, S, shift=mod[:, 0], scale=mod[:, 1], eps=eps)
-        qkv = ops.gemm_nt(n1, P("w_qkv1"), P("b_qkv1"))
-        qn = ops.wan_rms_rope(qkv[:, :D], P("attn1.norm_q.weight"), S, rope=rope, head_dim=hd, eps=eps)
-        kn = ops.wan_rms_rope(qkv[:, D:2 * D], P("attn1.norm_k.weight"), S, rope=rope, head_dim=hd, eps=eps)
-        o1, lse1 = ops.attn_fwd(heads(qn, S), heads(kn, S), heads(qkv[:, 2 * D:], S))
-        a1 = ops.gemm_nt(tok(o1), P("attn1.to_out.0.weight"), P("attn1.to_out.0.bias"))
-        x1 = ops.wan_gate_res(x2d, a1, S, gate=mod[:, 2])
-        # cross-attention to the text tokens (no rotary embedding, no gate)
-        n2 = ops.wan_ln(x1, S, w=P("norm2.weight"), b=P("norm2.bias"), eps=eps)
-        q2 = ops.gemm_nt(n2, P("attn2.to_q.weight"), P("attn2.to_q.bias"))
-        kv2 = ops.gemm_nt(enc2d, P("w_kv2"), P("b_kv2"))
-        q2n = ops.wan_rms_rope(q2, P("attn2.norm_q.weight"), S, eps=eps)
-        k2n = ops.wan_rms_rope(kv2[:, :D], P("attn2.norm_k.weight"), T, eps=eps)
-        o2, lse2 = ops.attn_fwd(heads(q2n, S), heads(k2n, T), heads(kv2[:, D:], T))
-        a2 = ops.gemm_nt(tok(o2), P("attn2.to_out.0.weight"), P("attn2.to_out.0.bias"))
-        x2 = ops.wan_gate_res(x1, a2, S)
-        # feed-forward
-        n3 = ops.wan_ln(x2, S, shift=mod[:, 3], scale=mod[:, 4], eps=eps)
-        act, pre = ops.gemm_nt(n3, P("ffn.net.0.proj.weight"), P("ffn.net.0.proj.bias"), epilogue=1, want_out2=True)  # GELU-tanh, pre-activation kept
-        f = ops.gemm_nt(act, P("ffn.net.2.weight"), P("ffn.net.2.bias"))
-        out = ops.wan_gate_res(x2, f, S, gate=mod[:, 5])
-
-        ctx.blk, ctx.dims, ctx.rope = blk, (B, S, T, D), rope
-        ctx.temb_dtype = temb.dtype
+        out, ctx.acts = _block_forward(blk, x, enc, mod, (rope_cos, rope_sin), _Lora())
+        ctx.blk, ctx.rope, ctx.temb_dtype = blk, (rope_cos, rope_sin), temb.dtype
         ctx.save_for_backward(x, enc, mod)
-        ctx.acts = (n1, qkv, qn, kn, o1, lse1, a1, x1, n2, q2, kv2, q2n, k2n, o2, lse2, x2, n3, act, pre, f)
-        return out.view(B, S, D)
+        return out
 
     @staticmethod
     def backward(ctx, dout):
         blk = ctx.blk
         if blk._pre_backward is not None:
             blk._pre_backward(blk)  # sharded training: gather this block's parameters (prefetch the previous block's), take a gradient buffer
-        B, S, T, D = ctx.dims
         x, enc, mod = ctx.saved_tensors
-        n1, qkv, qn, kn, o1, lse1, a1, x1, n2, q2, kv2, q2n, k2n, o2, lse2, x2, n3, act, pre, f = ctx.acts
-        ctx.acts = None
-        M, H, hd, eps, rope = B * S, blk.heads, blk.head_dim, blk.eps, ctx.rope
-        P, G, Wt = blk.param, blk.grad, blk.transposed()
-        x2d, enc2d = x.view(M, D), enc.view(B * T, D)
-        dout = dout.contiguous().view(M, D)
-        heads = lambda t, n: t.view(B, n, H, hd).permute(0, 2, 1, 3)
-        tok = lambda t: t.permute(0, 2, 1, 3).reshape(t.shape[0] * t.shape[2], D)
-        dmod = torch.zeros((6, B, D), dtype=torch.float32, device=x.device)  # (shift, scale, gate) x (attention, feed-forward), summed over the tokens
-
-        def linear_grads(name_w, name_b, dy, inp):  # dW += dY^T X (fp32, token-reduction GEMM), db += column sums of dY
-            ops.gemm_tn(dy, inp, out=G(name_w))
-            ops.wan_colsum(dy, G(name_b))
-
-        # feed-forward branch: out = x2 + f * gate_ff
-        df = ops.wan_gate_res_bwd(dout, f, mod[:, 5], S, dgate=dmod[5])
-        linear_grads("ffn.net.2.weight", "ffn.net.2.bias", df, act)
-        dpre = ops.gemm_nt(df, Wt["ffn.net.2.weight"], None, epilogue=3, aux=pre)  # (d f W2) * gelu'(pre)
-        linear_grads("ffn.net.0.proj.weight", "ffn.net.0.proj.bias", dpre, n3)
-        dn3 = ops.gemm_nt(dpre, Wt["ffn.net.0.proj.weight"], None)
-        dx2 = ops.wan_ln_bwd(x2, dn3, S, scale=mod[:, 4], eps=eps, dres=dout, red1=dmod[3], red2=dmod[4], red_per_batch=True)
-        # cross-attention branch: x2 = x1 + a2
-        linear_grads("attn2.to_out.0.weight", "attn2.to_out.0.bias", dx2, tok(o2))
-        do2 = ops.gemm_nt(dx2, Wt["attn2.to_out.0.weight"], None)
-        dkv2 = torch.empty_like(kv2)
-        dq2n, dk2n, _ = ops.attn_bwd(heads(q2n, S), heads(k2n, T), heads(kv2[:, D:], T), o2, lse2, heads(do2, S), dv_out=heads(dkv2[:, D:], T))
-        dq2 = ops.wan_rms_rope_bwd(q2, P("attn2.norm_q.weight"), tok(dq2n), S, eps=eps, dweight=G("attn2.norm_q.weight"))
-        ops.wan_rms_rope_bwd(kv2[:, :D], P("attn2.norm_k.weight"), tok(dk2n), T, eps=eps, dweight=G("attn2.norm_k.weight"), out=dkv2[:, :D])
-        linear_grads("attn2.to_q.weight", "attn2.to_q.bias", dq2, n2)
-        linear_grads("w_kv2", "b_kv2", dkv2, enc2d)
-        denc = ops.gemm_nt(dkv2, Wt["w_kv2"], None).view(B, T, D)
-        dn2 = ops.gemm_nt(dq2, Wt["attn2.to_q.weight"], None)
-        dx1 = ops.wan_ln_bwd(x1, dn2, S, w=P("norm2.weight"), eps=eps, dres=dx2, red1=G("norm2.bias"), red2=G("norm2.weight"))
-        # self-attention branch: x1 = x + a1 * gate_msa
-        da1 = ops.wan_gate_res_bwd(dx1, a1, mod[:, 2], S, dgate=dmod[2])
-        linear_grads("attn1.to_out.0.weight", "attn1.to_out.0.bias", da1, tok(o1))
-        do1 = ops.gemm_nt(da1, Wt["attn1.to_out.0.weight"], None)
-        dqkv = torch.empty_like(qkv)
-        dqn, dkn, _ = ops.attn_bwd(heads(qn, S), heads(kn, S), heads(qkv[:, 2 * D:], S), o1, lse1, heads(do1, S), dv_out=heads(dqkv[:, 2 * D:], S))
-        ops.wan_rms_rope_bwd(qkv[:, :D], P("attn1.norm_q.weight"), tok(dqn), S, rope=rope, head_dim=hd, eps=eps, dweight=G("attn1.norm_q.weight"), out=dqkv[:, :D])
-        ops.wan_rms_rope_bwd(qkv[:, D:2 * D], P("attn1.norm_k.weight"), tok(dkn), S, rope=rope, head_dim=hd, eps=eps, dweight=G("attn1.norm_k.weight"),
-                             out=dqkv[:, D:2 * D])
-        linear_grads("w_qkv1", "b_qkv1", dqkv, n1)
-        dn1 = ops.gemm_nt(dqkv, Wt["w_qkv1"], None)  # the three projections' input gradients summed in the GEMM's fp32 accumulator
-        dx = ops.wan_ln_bwd(x2d, dn1, S, scale=mod[:, 1], eps=eps, dres=dx1, red1=dmod[0], red2=dmod[1], red_per_batch=True)
+        acts, ctx.acts = ctx.acts, None
+        dx, denc, dmod = _block_backward(blk, acts, x, enc, mod, ctx.rope, dout, _Lora(), train_base=True)
         dmod = dmod.permute(1, 0, 2)  # [B, 6, D]
-        G("scale_shift_table").add_(dmod.sum(0, keepdim=True))
+        blk.grad("scale_shift_table").add_(dmod.sum(0, keepdim=True))
         if blk._grad_hook is not None:
             blk._grad_hook(blk)  # sharded training: this block's gradients are final -- start their reduce-scatter while the earlier blocks run
-        return None, dx.view(B, S, D), denc, dmod.to(ctx.temb_dtype), None, None
+        return None, dx, denc, dmod.to(ctx.temb_dtype), None, None
 
 
 class _WanBlockNativeFunction(torch.autograd.Function):
@@ -247,44 +338,6 @@ class _WanBlockNativeFunction(torch.autograd.Function):
         return None, dx, denc, dmod.to(ctx.temb_dtype), None, None
 
 
-# ---- LoRA over a frozen base ------------------------------------------------------------------------------------------------------------------
-# Adapter order inside lora_A [8, r, D] / lora_B [8, D, r] (the projections the recipe's regex "blocks.*(to_q|to_k|to_v|to_out.0)" selects: BOTH attentions)
-LORA_TARGETS = ("attn1.to_q", "attn1.to_k", "attn1.to_v", "attn1.to_out.0", "attn2.to_q", "attn2.to_k", "attn2.to_v", "attn2.to_out.0")
-_TWINS = (("w_qkv1_t", "w_qkv1"), ("w_o1_t", "attn1.to_out.0.weight"), ("w_q2_t", "attn2.to_q.weight"), ("w_kv2_t", "w_kv2"), ("w_o2_t", "attn2.to_out.0.weight"),
-          ("w_f1_t", "ffn.net.0.proj.weight"), ("w_f2_t", "ffn.net.2.weight"))
-
-
-def _lora_linear_fwd(x, w, bias, adp: int, nadp: int, a_sp, b_ext, r: int, s: float):
-    """[rows, nadp D] = x W^T + b + s (x A^T) B^T for the adapters adp .. adp + nadp - 1 on one input: the two launches of csrc/wan_dit.hip lora_linear_fwd.
-    Returns (y, xa [rows, 3 nadp r])."""
-    if r == 0:
-        return ops.gemm_nt(x, w, bias), None
-    rows, D = x.shape
-    xa = torch.empty((rows, 3 * nadp * r), dtype=bf16, device=x.device)
-    ops.gemm_nt_ex(x, a_sp[adp:adp + nadp].reshape(2 * nadp * r, D), xa, M=rows, N=2 * nadp * r, K=D, alpha=s, split_r=r, variant=8)
-    y = torch.empty((rows, nadp * D), dtype=bf16, device=x.device)
-    grp = dict(x2_grp_n=D, x2_grp_stride=3 * r) if nadp > 1 else {}
-    ops.gemm_nt_ex(x, w, y, M=rows, N=nadp * D, K=D, bias=bias, x2=xa, w2=b_ext[adp:adp + nadp].reshape(nadp * D, 3 * r), K2=3 * r, variant=8, **grp)
-    return y, xa
-
-
-def _lora_linear_bwd(x, dy, w_t, adp: int, nadp: int, xa, bt_sp, at_ext, r: int, s: float, ga, gb, need_dx: bool = True):
-    """dx = dY W (+ dXA A); gb[adp ..] += dY^T XA, ga[adp ..] += dXA^T x (csrc/wan_dit.hip lora_linear_bwd)."""
-    rows, D = x.shape
-    if r == 0:
-        return ops.gemm_nt(dy, w_t, None) if need_dx else None
-    dxa = torch.empty((rows, 3 * nadp * r), dtype=bf16, device=x.device)
-    grp = dict(xk_grp_n=2 * r, xk_grp_stride=D) if nadp > 1 else {}
-    ops.gemm_nt_ex(dy, bt_sp[adp:adp + nadp].reshape(2 * nadp * r, D), dxa, M=rows, N=2 * nadp * r, K=D, alpha=s, split_r=r, variant=8, **grp)
-    dx = None
-    if need_dx:
-        dx = torch.empty((rows, D), dtype=bf16, device=x.device)
-        ops.gemm_nt_ex(dy, w_t, dx, M=rows, N=D, K=nadp * D, x2=dxa, w2=at_ext[:, adp * 3 * r:(adp + nadp) * 3 * r], K2=3 * nadp * r, variant=8)
-    ops.gemm_tn_ex(dy, xa, gb[adp:adp + nadp].view(nadp * D, r), M=rows, P=nadp * D, Q=r, v_fold=r, **(dict(v_grp_p=D, v_grp_stride=3 * r) if nadp > 1 else {}))
-    ops.gemm_tn_ex(dxa, x, ga[adp:adp + nadp].view(nadp * r, D), M=rows, P=nadp * r, Q=D, u_fold=r, **(dict(u_grp_p=r, u_grp_stride=3 * r) if nadp > 1 else {}))
-    return dx
-
-
 def _grad_targets(blk: "MI355XWanBlock", lora_a, lora_b):
     """Where the adapter gradients go: the step object's flat views (added in place), or fresh tensors returned to autograd."""
     if lora_a is None:
@@ -294,58 +347,18 @@ def _grad_targets(blk: "MI355XWanBlock", lora_a, lora_b):
 
 
 class _WanLoRABlockFunction(torch.autograd.Function):
-    """The block over a FROZEN base with the adapters on the eight attention projections, as a composition of the library's launches from Python
-    (``FTMI_NATIVE_BLOCKS=0``): the second implementation ``_WanLoRABlockNativeFunction`` is compared with.  The backward forms dx, denc (only if asked for)
-    and the 16 adapter gradients -- no base-weight gradient, no bias / norm / modulation reduction, and it keeps neither a1, n3, act nor f."""
-
-    @staticmethod
-    def _run(blk: "MI355XWanBlock", x, enc, mod, rope, lora_a, lora_b, need_out: bool = True):
-        B, S, D = x.shape
-        T = enc.shape[1]
-        M, H, hd, eps, s = B * S, blk.heads, blk.head_dim, blk.eps, blk.lora_scale
-        P = blk.param
-        r = 0 if lora_a is None else int(lora_a.shape[1])
-        a_sp = b_ext = None
-        if r:
-            a_sp = torch.stack([ops.lora_split(lora_a[i], sp=True)[0] for i in range(8)])
-            b_ext = torch.stack([ops.lora_split(lora_b[i], ext=True)[0] for i in range(8)])
-        lin = lambda t, w, b, adp, nadp: _lora_linear_fwd(t, w, b, adp, nadp, a_sp, b_ext, r, s)
-        x2d, enc2d = x.view(M, D), enc.view(B * T, D)
-        heads = lambda t, n: t.view(B, n, H, hd).permute(0, 2, 1, 3)
-        tok = lambda t: t.permute(0, 2, 1, 3).reshape(t.shape[0] * t.shape[2], D)
-        n1 = ops.wan_ln(x2d, S, shift=mod[:, 0], scale=mod[:, 1], eps=eps)
-        qkv, xa_qkv = lin(n1, P("w_qkv1"), P("b_qkv1"), 0, 3)
-        qn = ops.wan_rms_rope(qkv[:, :D], P("attn1.norm_q.weight"), S, rope=rope, head_dim=hd, eps=eps)
-        kn = ops.wan_rms_rope(qkv[:, D:2 * D], P("attn1.norm_k.weight"), S, rope=rope, head_dim=hd, eps=eps)
-        o1, lse1 = ops.attn_fwd(heads(qn, S), heads(kn, S), heads(qkv[:, 2 * D:], S))
-        a1, xa_o1 = lin(tok(o1), P("attn1.to_out.0.weight"), P("attn1.to_out.0.bias"), 3, 1)
-        x1 = ops.wan_gate_res(x2d, a1, S, gate=mod[:, 2])
-        n2 = ops.wan_ln(x1, S, w=P("norm2.weight"), b=P("norm2.bias"), eps=eps)
-        q2, xa_q2 = lin(n2, P("attn2.to_q.weight"), P("attn2.to_q.bias"), 4, 1)
-        kv2, xa_kv2 = lin(enc2d, P("w_kv2"), P("b_kv2"), 5, 2)
-        q2n = ops.wan_rms_rope(q2, P("attn2.norm_q.weight"), S, eps=eps)
-        k2n = ops.wan_rms_rope(kv2[:, :D], P("attn2.norm_k.weight"), T, eps=eps)
-        o2, lse2 = ops.attn_fwd(heads(q2n, S), heads(k2n, T), heads(kv2[:, D:], T))
-        a2, xa_o2 = lin(tok(o2), P("attn2.to_out.0.weight"), P("attn2.to_out.0.bias"), 7, 1)
-        x2 = ops.wan_gate_res(x1, a2, S)
-        n3 = ops.wan_ln(x2, S, shift=mod[:, 3], scale=mod[:, 4], eps=eps)
-        act, pre = ops.gemm_nt(n3, P("ffn.net.0.proj.weight"), P("ffn.net.0.proj.bias"), epilogue=1, want_out2=True)
-        acts = (n1, qkv, qn, kn, o1, lse1, x1, n2, q2, kv2, q2n, k2n, o2, lse2, x2, pre, xa_qkv, xa_o1, xa_q2, xa_kv2, xa_o2)
-        if not need_out:
-            return None, acts
-        f = ops.gemm_nt(act, P("ffn.net.2.weight"), P("ffn.net.2.bias"))
-        out = ops.wan_gate_res(x2, f, S, gate=mod[:, 5])
-        return out.view(B, S, D), acts
+    """The block over a FROZEN base with the adapters on the eight attention projections, through the Python walks.  The backward forms dx, denc (only if
+    asked for) and the 16 adapter gradients -- no base-weight gradient, no bias / norm / modulation reduction, and it keeps neither a1, n3, act nor f."""
 
     @staticmethod
     def forward(ctx, blk: "MI355XWanBlock", x, enc, temb, rope_cos, rope_sin, lora_a, lora_b):
         mod = (blk.param("scale_shift_table").float() + temb.float()).contiguous()
-        out, acts = _WanLoRABlockFunction._run(blk, x, enc, mod, (rope_cos, rope_sin), lora_a, lora_b)
+        out, acts = _block_forward(blk, x, enc, mod, (rope_cos, rope_sin), _Lora(lora_a, lora_b))
         ctx.blk, ctx.rope, ctx.has_lora = blk, (rope_cos, rope_sin), lora_a is not None
         ctx.recompute = bool(blk.gradient_checkpointing)
         la, lb = (lora_a, lora_b) if lora_a is not None else (x.new_empty(0), x.new_empty(0))
         ctx.save_for_backward(x, enc, mod, la, lb)
-        ctx.acts = None if ctx.recompute else acts
+        ctx.acts = None if ctx.recompute else acts.for_frozen_base()
         return out
 
     @staticmethod
@@ -354,55 +367,15 @@ class _WanLoRABlockFunction(torch.autograd.Function):
         x, enc, mod, lora_a, lora_b = ctx.saved_tensors
         if not ctx.has_lora:
             lora_a = lora_b = None
-        acts = ctx.acts
-        ctx.acts = None
+        acts, ctx.acts = ctx.acts, None
         if ctx.recompute:
-            _, acts = _WanLoRABlockFunction._run(blk, x, enc, mod, rope, lora_a, lora_b, need_out=False)
-        n1, qkv, qn, kn, o1, lse1, x1, n2, q2, kv2, q2n, k2n, o2, lse2, x2, pre, xa_qkv, xa_o1, xa_q2, xa_kv2, xa_o2 = acts
-        B, S, D = x.shape
-        T = enc.shape[1]
-        M, H, hd, eps, s = B * S, blk.heads, blk.head_dim, blk.eps, blk.lora_scale
-        P, Wt = blk.param, blk.transposed()
-        r = 0 if lora_a is None else int(lora_a.shape[1])
+            acts = _block_forward(blk, x, enc, mod, rope, _Lora(lora_a, lora_b), need_out=False)[1].for_frozen_base()
         own, ga, gb = _grad_targets(blk, lora_a, lora_b)
-        bt_sp = at_ext = None
-        if r:
-            bt_sp = torch.stack([ops.lora_split(lora_b[i], t_sp=True)[0] for i in range(8)])
-            at_ext = torch.cat([ops.lora_split(lora_a[i], t_ext=True)[0] for i in range(8)], dim=1)  # the eight adapters side by side: [D, 24r]
-        lin = lambda t, dy, w_t, adp, nadp, xa, need_dx=True: _lora_linear_bwd(t, dy, w_t, adp, nadp, xa, bt_sp, at_ext, r, s, ga, gb, need_dx)
-        need_denc = ctx.needs_input_grad[2]
-        x2d, enc2d = x.view(M, D), enc.view(B * T, D)
-        dout = dout.contiguous().view(M, D)
-        heads = lambda t, n: t.view(B, n, H, hd).permute(0, 2, 1, 3)
-        tok = lambda t: t.permute(0, 2, 1, 3).reshape(t.shape[0] * t.shape[2], D)
-        # feed-forward branch
-        df = ops.wan_gate_res_bwd(dout, None, mod[:, 5], S)
-        dpre = ops.gemm_nt(df, Wt["ffn.net.2.weight"], None, epilogue=3, aux=pre)
-        dn3 = ops.gemm_nt(dpre, Wt["ffn.net.0.proj.weight"], None)
-        dx2 = ops.wan_ln_bwd(x2, dn3, S, scale=mod[:, 4], eps=eps, dres=dout)
-        # cross-attention branch
-        do2 = lin(tok(o2), dx2, Wt["attn2.to_out.0.weight"], 7, 1, xa_o2)
-        dkv2 = torch.empty_like(kv2)
-        dq2n, dk2n, _ = ops.attn_bwd(heads(q2n, S), heads(k2n, T), heads(kv2[:, D:], T), o2, lse2, heads(do2, S), dv_out=heads(dkv2[:, D:], T))
-        dq2 = ops.wan_rms_rope_bwd(q2, P("attn2.norm_q.weight"), tok(dq2n), S, eps=eps)
-        ops.wan_rms_rope_bwd(kv2[:, :D], P("attn2.norm_k.weight"), tok(dk2n), T, eps=eps, out=dkv2[:, :D])
-        denc = lin(enc2d, dkv2, Wt["w_kv2"], 5, 2, xa_kv2, need_denc)
-        dn2 = lin(n2, dq2, Wt["attn2.to_q.weight"], 4, 1, xa_q2)
-        dx1 = ops.wan_ln_bwd(x1, dn2, S, w=P("norm2.weight"), eps=eps, dres=dx2)
-        # self-attention branch
-        da1 = ops.wan_gate_res_bwd(dx1, None, mod[:, 2], S)
-        do1 = lin(tok(o1), da1, Wt["attn1.to_out.0.weight"], 3, 1, xa_o1)
-        dqkv = torch.empty_like(qkv)
-        dqn, dkn, _ = ops.attn_bwd(heads(qn, S), heads(kn, S), heads(qkv[:, 2 * D:], S), o1, lse1, heads(do1, S), dv_out=heads(dqkv[:, 2 * D:], S))
-        ops.wan_rms_rope_bwd(qkv[:, :D], P("attn1.norm_q.weight"), tok(dqn), S, rope=rope, head_dim=hd, eps=eps, out=dqkv[:, :D])
-        ops.wan_rms_rope_bwd(qkv[:, D:2 * D], P("attn1.norm_k.weight"), tok(dkn), S, rope=rope, head_dim=hd, eps=eps, out=dqkv[:, D:2 * D])
-        dn1 = lin(n1, dqkv, Wt["w_qkv1"], 0, 3, xa_qkv)
-        dx = ops.wan_ln_bwd(x2d, dn1, S, scale=mod[:, 1], eps=eps, dres=dx1)
-        denc = denc.view(B, T, D) if denc is not None else None
+        dx, denc, _ = _block_backward(blk, acts, x, enc, mod, rope, dout, _Lora(lora_a, lora_b, ga, gb), train_base=False, need_denc=ctx.needs_input_grad[2])
         if own:
             blk._backward_done()
             ga = gb = None
-        return None, dx.view(B, S, D), denc, None, None, None, ga, gb
+        return None, dx, denc, None, None, None, ga, gb
 
 
 class _WanLoRABlockNativeFunction(torch.autograd.Function):

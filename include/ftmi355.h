@@ -664,7 +664,7 @@ int ftmi_wan_block_backward(const ftmi_wan_block_config* cfg, const void* params
                             void* scratch, size_t scratch_bytes, ftmi_stream stream);
 
 /* The same block for LoRA fine-tuning (the reference's Wan SFT recipes: --training_type lora --target_modules "blocks.*(to_q|to_k|to_v|to_out.0)"): the
- * base weights are frozen; fp32 adapters lora_a [8, r, D] / lora_b [8, D, r] sit on attn1.to_q, to_k, to_v, to_out.0, attn2.to_q, to_k, to_v, to_out.0
+ * same forward and backward walk behind other entry points (one implementation, csrc/wan_dit.hip), run with frozen base weights; fp32 adapters lora_a [8, r, D] / lora_b [8, D, r] sit on attn1.to_q, to_k, to_v, to_out.0, attn2.to_q, to_k, to_v, to_out.0
  * (in this order) and every projection computes x W^T + b + lora_scale (x A^T) B^T.  The configuration is ftmi_wan_block_config plus r and lora_scale.
  * params: the flat bf16 buffer as above; w_*_t: K-contiguous (transposed) twins of the seven weight matrices, backward only -- [D, 3D] of attn1 q|k|v,
  * [D, D] of attn1.to_out.0, attn2.to_q, [D, 2D] of attn2 k|v, [D, D] of attn2.to_out.0, [D, F] of ffn.net.0.proj, [F, D] of ffn.net.2.

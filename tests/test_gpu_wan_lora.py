@@ -112,14 +112,16 @@ def _run_gpu_block(gblk, x, enc, temb, dout, rope, enc_grad=True):
     return out.detach().clone(), xg.grad.clone(), (eg.grad.clone() if enc_grad else None), ga, gb
 
 
+@pytest.mark.parametrize("native", [True, False])
 @pytest.mark.parametrize("geom,B,S,T", [((256, 2, 512), 2, 48, 16), (REAL, 1, 200, 64)])
-def test_frozen_path_has_the_full_finetune_bits(geom, B, S, T):
-    """r = 0 and (r = 32, B = 0): the LoRA block's output is ``ftmi_wan_block_forward``'s, bit for bit; with r = 0 its dx (and d text) is the full
-    fine-tune backward's."""
+def test_frozen_path_has_the_full_finetune_bits(geom, B, S, T, native):
+    """r = 0 and (r = 32, B = 0): the LoRA block's output is the full fine-tune block's, bit for bit; with r = 0 its dx (and d text) is the full
+    fine-tune backward's.  Through the C calls (``native``) and through the Python walk, both blocks the same way."""
     from finetrainers_amd.wan import MI355XWanBlock
 
     _, frozen = _block_pair(geom, rank=0)
     full = MI355XWanBlock(dim=geom[0], heads=geom[1], ffn_dim=geom[2], eps=frozen.eps, device=_dev())
+    frozen.native = full.native = native
     full.flat.data.copy_(frozen.flat.data)
     full.mark_updated()
     x, enc, temb, dout = _block_inputs(B, S, T, geom[0], seed=B * 1000 + S + 1)

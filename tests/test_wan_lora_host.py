@@ -45,6 +45,23 @@ def test_lora_block_keeps_less_than_the_full_finetune_block():
     assert full - r0 >= B * S * (3 * D + F) * 2  # the four dropped buffers
 
 
+def test_wan_planners_return_the_recorded_bytes():
+    """The four byte planners and ``param_elements`` against tests/golden/wan_block_bytes.txt, recorded once from the library as it was before the full and
+    the LoRA block shared one buffer plan: the callers' allocations (and what a checkpoint of ``saved`` would hold) must not move by a byte."""
+    from finetrainers_amd import _lib
+
+    lib = _lib.load()
+    rows = [ln.split() for ln in open(os.path.join(ROOT, "tests", "golden", "wan_block_bytes.txt")) if ln.strip() and not ln.startswith("#")]
+    assert len(rows) == 18  # six geometries x r in {0, 64, 128}
+    for row in rows:
+        B, S, T, D, H, F, r, full_saved, full_scratch, elements, lora_saved, lora_scratch = map(int, row)
+        full = ctypes.byref(_lib.WanBlockConfig(B=B, S=S, T=T, D=D, H=H, F=F, eps=1e-6, gemm_variant=8))
+        lora = ctypes.byref(_lib.WanLoraBlockConfig(B=B, S=S, T=T, D=D, H=H, F=F, eps=1e-6, gemm_variant=8, r=r, lora_scale=1.0))
+        got = (lib.ftmi_wan_block_saved_bytes(full), lib.ftmi_wan_block_scratch_bytes(full), lib.ftmi_wan_block_param_elements(full),
+               lib.ftmi_wan_lora_block_saved_bytes(lora), lib.ftmi_wan_lora_block_scratch_bytes(lora))
+        assert got == (full_saved, full_scratch, elements, lora_saved, lora_scratch), (row, got)
+
+
 def _models(layers, rank=32, alpha=32.0):
     from finetrainers_amd.wan import MI355XWanTransformer3DModel, WanTransformerConfig
     from oracle import wan
