@@ -133,6 +133,12 @@ class WanLoraBlockConfig(Structure):
     _fields_ = WanBlockConfig._fields_ + [("r", c_int), ("lora_scale", c_float)]
 
 
+class WanI2VLoraBlockConfig(Structure):
+    """include/ftmi355.h: ftmi_wan_i2v_lora_block_config."""
+
+    _fields_ = WanLoraBlockConfig._fields_ + [("TI", c_int)]
+
+
 WAN_LORA_WEIGHT_FIELDS = ["params", "w_qkv1_t", "w_o1_t", "w_q2_t", "w_kv2_t", "w_o2_t", "w_f1_t", "w_f2_t", "lora_a", "lora_b"]
 
 
@@ -184,6 +190,8 @@ _SIGS = {
                                   POINTER(ctypes.c_double), c_int]),
     "ftmi_attn_fwd": (c_int, [POINTER(AttnDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ftmi_attn_bwd": (c_int, [POINTER(AttnDesc)] + [c_void_p] * 12),
+    "ftmi_attn_ctx2_fwd": (c_int, [POINTER(AttnDesc)] + [c_void_p] * 7),
+    "ftmi_attn_ctx2_dq": (c_int, [POINTER(AttnDesc)] + [c_void_p] * 8),
     "ftmi_linear_lora_fwd": (c_int, [c_int, c_int, c_int, c_int, c_float] + [c_void_p] * 7 + [c_int, c_void_p]),
     "ftmi_linear_lora_bwd": (c_int, [c_int, c_int, c_int, c_int, c_float] + [c_void_p] * 10 + [c_int, c_void_p]),
     "ftmi_gemm_nt_plan": (c_int, [c_int, c_int, c_int, c_int, c_int]),
@@ -269,6 +277,10 @@ _SIGS = {
                                             c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
     "ftmi_wan_lora_block_backward": (c_int, [POINTER(WanLoraBlockConfig), POINTER(WanLoraBlockWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    "ftmi_wan_i2v_lora_block_saved_bytes": (c_size_t, [POINTER(WanI2VLoraBlockConfig)]),
+    "ftmi_wan_i2v_lora_block_scratch_bytes": (c_size_t, [POINTER(WanI2VLoraBlockConfig)]),
+    "ftmi_wan_i2v_lora_block_forward": (c_int, [POINTER(WanI2VLoraBlockConfig), POINTER(WanLoraBlockWeights)] + [c_void_p] * 9 + [c_size_t, c_void_p, c_size_t, c_void_p]),
+    "ftmi_wan_i2v_lora_block_backward": (c_int, [POINTER(WanI2VLoraBlockConfig), POINTER(WanLoraBlockWeights)] + [c_void_p] * 13 + [c_size_t, c_void_p, c_size_t, c_void_p]),
     "ftmi_wan_block_saved_bytes": (c_size_t, [POINTER(WanBlockConfig)]),
     "ftmi_wan_block_scratch_bytes": (c_size_t, [POINTER(WanBlockConfig)]),
     "ftmi_wan_block_param_elements": (c_size_t, [POINTER(WanBlockConfig)]),

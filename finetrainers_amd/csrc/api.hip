@@ -235,6 +235,26 @@ int ftmi_attn_bwd(const ftmi_attn_desc* desc, const void* q, const void* k, cons
     return attn_bwd(a, (hipStream_t)stream);
 }
 
+int ftmi_attn_ctx2_fwd(const ftmi_attn_desc* desc, const void* q, const void* k, const void* v, const void* out_first, void* out, float* lse,
+                       ftmi_stream stream) {
+    AttnArgs a;
+    int rc = fill_attn(desc, a);
+    if (rc) return rc;
+    if (!q || !k || !v || !out_first || !out || !lse) return set_error(FTMI_ERR_INVALID, "ftmi_attn_ctx2_fwd: null tensor");
+    a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (bf16_t*)out; a.lse2 = lse;
+    return attn_ctx2_fwd(a, (const bf16_t*)out_first, (hipStream_t)stream);
+}
+
+int ftmi_attn_ctx2_dq(const ftmi_attn_desc* desc, const void* q, const void* k, const void* v, const float* lse, const void* dout, const void* dq_first,
+                      void* dq, ftmi_stream stream) {
+    AttnArgs a;
+    int rc = fill_attn(desc, a);
+    if (rc) return rc;
+    if (!q || !k || !v || !lse || !dout || !dq_first || !dq) return set_error(FTMI_ERR_INVALID, "ftmi_attn_ctx2_dq: null tensor");
+    a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.lse2 = (float*)lse; a.dout = (const bf16_t*)dout; a.dq = (bf16_t*)dq;
+    return attn_ctx2_dq(a, (const bf16_t*)dq_first, (hipStream_t)stream);
+}
+
 int ftmi_gemm_nt_plan(int M, int N, int K, int K2, int epilogue) { return gemm_nt_plan(M, N, K, K2, epilogue); }
 
 int ftmi_reload_switches(void) { return EnvSwitch::reload_all(); }
@@ -769,6 +789,27 @@ int ftmi_wan_lora_block_backward(const ftmi_wan_lora_block_config* cfg, const ft
         return set_error(FTMI_ERR_INVALID, "ftmi_wan_lora_block_backward: null argument");
     return wan_lora_block_backward(*cfg, *w, (const bf16_t*)x, (const bf16_t*)enc, mod, rope_cos, rope_sin, (const bf16_t*)dout, (bf16_t*)dx, (bf16_t*)denc, grad_a,
                                    grad_b, saved, saved_bytes, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+size_t ftmi_wan_i2v_lora_block_saved_bytes(const ftmi_wan_i2v_lora_block_config* cfg) { return cfg ? wan_i2v_lora_block_saved_bytes(*cfg) : 0; }
+size_t ftmi_wan_i2v_lora_block_scratch_bytes(const ftmi_wan_i2v_lora_block_config* cfg) { return cfg ? wan_i2v_lora_block_scratch_bytes(*cfg) : 0; }
+int ftmi_wan_i2v_lora_block_forward(const ftmi_wan_i2v_lora_block_config* cfg, const ftmi_wan_lora_block_weights* w, const void* img_params, const void* x,
+                                    const void* enc, const void* enc_img, const float* mod, const float* rope_cos, const float* rope_sin, void* out, void* saved,
+                                    size_t saved_bytes, void* scratch, size_t scratch_bytes, ftmi_stream stream) {
+    if (!cfg || !w || !w->params || !x || !enc || !mod || !rope_cos || !rope_sin || !saved || !scratch || (cfg->TI > 0 && (!img_params || !enc_img)))
+        return set_error(FTMI_ERR_INVALID, "ftmi_wan_i2v_lora_block_forward: null argument");
+    return wan_i2v_lora_block_forward(*cfg, *w, (const bf16_t*)img_params, (const bf16_t*)x, (const bf16_t*)enc, (const bf16_t*)enc_img, mod, rope_cos, rope_sin,
+                                      (bf16_t*)out, saved, saved_bytes, scratch, scratch_bytes, (hipStream_t)stream);
+}
+int ftmi_wan_i2v_lora_block_backward(const ftmi_wan_i2v_lora_block_config* cfg, const ftmi_wan_lora_block_weights* w, const void* img_params, const void* x,
+                                     const void* enc, const void* enc_img, const float* mod, const float* rope_cos, const float* rope_sin, const void* dout,
+                                     void* dx, void* denc, float* grad_a, float* grad_b, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
+                                     ftmi_stream stream) {
+    if (!cfg || !w || !w->params || !x || !enc || !mod || !rope_cos || !rope_sin || !dout || !dx || !saved || !scratch || (cfg->TI > 0 && (!img_params || !enc_img)))
+        return set_error(FTMI_ERR_INVALID, "ftmi_wan_i2v_lora_block_backward: null argument");
+    return wan_i2v_lora_block_backward(*cfg, *w, (const bf16_t*)img_params, (const bf16_t*)x, (const bf16_t*)enc, (const bf16_t*)enc_img, mod, rope_cos, rope_sin,
+                                       (const bf16_t*)dout, (bf16_t*)dx, (bf16_t*)denc, grad_a, grad_b, saved, saved_bytes, scratch, scratch_bytes,
+                                       (hipStream_t)stream);
 }
 
 int ftmi_lora_refresh(const float* a_f32, const float* b_f32, void* lora_a_sp, void* lora_bt_sp, void* lora_b_ext, void* lora_at_ext,

@@ -9,7 +9,7 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ["gemm.hip", "attention.hip", "rowwise.hip", "cast.hip", "cogvideox.hip", "ltx_dit.hip", "ltx_sample.hip", "cog_dit.hip", "hy_dit.hip", "wan.hip", "wan_dit.hip", "collective.hip", "api.hip"]
+SOURCES = ["gemm.hip", "attention.hip", "attn_ctx2.hip", "rowwise.hip", "cast.hip", "cogvideox.hip", "ltx_dit.hip", "ltx_sample.hip", "cog_dit.hip", "hy_dit.hip", "wan.hip", "wan_dit.hip", "collective.hip", "api.hip"]
 HEADERS = ["common.hip.h", "kernels.h", os.path.join("..", "..", "include", "ftmi355.h"), "attention_pl.hip.h"]
 HEADERS += sorted(f for f in os.listdir(HERE) if f.startswith("attn_pl_") and f.endswith(".inc"))  # generated statement lists (tools/gen_attn_pl.py)
 LIB = os.path.join(HERE, "..", "libftmi355.so")
@@ -25,7 +25,7 @@ FLAGS = [
 # per-file extras.  attention: keep the MFMA accumulators in the (unified) VGPR file -- the online-softmax rescale and the
 # dS products read/modify them with VALU every tile, and the accumulator-file round trip (v_accvgpr_read/write) was 25-35 %
 # of the loop's instructions in a VALU-bound kernel.
-EXTRA_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
+EXTRA_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "attn_ctx2.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 # FTMI_EXPERIMENTAL=1: also compile the research K loops / timing experiments of tools/experimental/gemm_experimental.hip.h (tools/bench_gemm.py,
 # tools/ab_variants.sh).  Never set for the product library.
 if os.environ.get("FTMI_EXPERIMENTAL", "0") not in ("", "0"):

@@ -212,6 +212,10 @@ struct AttnArgs {
 };
 int attn_fwd(const AttnArgs& a, hipStream_t st);
 int attn_bwd(const AttnArgs& a, hipStream_t st);  // delta pre-pass + dK/dV kernel + dQ kernel
+// second context of a two-context cross-attention (attn_ctx2.hip; head_dim 128, at most 320 keys), folded into the first context's results:
+// a.o = bf(o_t + bf(softmax(q k^T) v)), a.lse2 written;  a.dq = bf(dq_t + bf(dq of this context)), a.lse2 / a.dout read.  o_t / dq_t use a.o's / a.dq's strides
+int attn_ctx2_fwd(const AttnArgs& a, const bf16_t* o_t, hipStream_t st);
+int attn_ctx2_dq(const AttnArgs& a, const bf16_t* dq_t, hipStream_t st);
 
 // ---- row-wise / elementwise ------------------------------------------------------------------------
 // ada[l][b][slot][D]: slots 0..5 = table[i] + temb[b][i] (shift_msa, scale_msa, gate_msa, shift_mlp,
@@ -381,6 +385,16 @@ int wan_lora_block_forward(const ftmi_wan_lora_block_config& c, const ftmi_wan_l
 int wan_lora_block_backward(const ftmi_wan_lora_block_config& c, const ftmi_wan_lora_block_weights& w, const bf16_t* x, const bf16_t* enc, const float* mod,
                             const float* rope_cos, const float* rope_sin, const bf16_t* dout, bf16_t* dx, bf16_t* denc, float* grad_a, float* grad_b, void* saved,
                             size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st);
+// image-to-video: the LoRA block with the image context in attn2 (cfg.TI image tokens; TI = 0: the calls above)
+size_t wan_i2v_lora_block_saved_bytes(const ftmi_wan_i2v_lora_block_config& c);
+size_t wan_i2v_lora_block_scratch_bytes(const ftmi_wan_i2v_lora_block_config& c);
+int wan_i2v_lora_block_forward(const ftmi_wan_i2v_lora_block_config& c, const ftmi_wan_lora_block_weights& w, const bf16_t* img_params, const bf16_t* x,
+                               const bf16_t* enc, const bf16_t* enc_img, const float* mod, const float* rope_cos, const float* rope_sin, bf16_t* out, void* saved,
+                               size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st);
+int wan_i2v_lora_block_backward(const ftmi_wan_i2v_lora_block_config& c, const ftmi_wan_lora_block_weights& w, const bf16_t* img_params, const bf16_t* x,
+                                const bf16_t* enc, const bf16_t* enc_img, const float* mod, const float* rope_cos, const float* rope_sin, const bf16_t* dout,
+                                bf16_t* dx, bf16_t* denc, float* grad_a, float* grad_b, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
+                                hipStream_t st);
 int adamw_bf16_step(bf16_t* p, const float* g, bf16_t* m, bf16_t* v, long n, const float* sumsq_in, float max_norm, float lr, float beta1, float beta2,
                     float eps, float wd, int step, float* grad_norm_out, hipStream_t st);
 

@@ -1,5 +1,5 @@
-// Wan-T2V (BASELINE config 4: full fine-tune) row-wise kernels of the DiT block, any row width D that is a multiple of 64
-// (Wan2.1-T2V-1.3B: 1536 = 12 heads x 128).  HBM-bound: one wavefront per token row, 16-byte loads, shuffle reductions, one pass over [M, D].
+// Wan-T2V (BASELINE config 4: full fine-tune) row-wise kernels of the DiT block, any row width D <= 5120 that is a multiple of 64
+// (Wan2.1-T2V-1.3B: 1536 = 12 heads x 128; the 14B checkpoints: 5120 = 40 x 128, ten 16-byte chunks per lane).  HBM-bound: one wavefront per token row, 16-byte loads, shuffle reductions, one pass over [M, D].
 // Unlike the LoRA paths of LTX / CogVideoX, EVERY parameter is trainable here, so each backward kernel also produces the per-column sums that the
 // parameter gradients need (modulation shift / scale / gate, LayerNorm and RMSNorm weights, Linear biases): a block walks a strip of rows of ONE
 // sample keeping the column sums in registers, the four waves combine them in LDS, and one fp32 atomic per column and block adds them to the
@@ -17,7 +17,8 @@ namespace ftmi {
 
 namespace {
 
-constexpr int kMaxChunks = 8;      // 64 lanes x 8 chunks x 8 elements: D <= 4096
+constexpr int kMaxChunks = 10;     // 64 lanes x 10 chunks x 8 elements: D <= 5120 (Wan2.1-I2V-14B)
+constexpr int kSlabCols = 4096;    // wan_colsum walks wider rows (the feed-forward's) in slabs of this many columns
 constexpr int kStripRows = 32;     // rows of one sample per block in the kernels that reduce over rows
 
 FTMI_DEVICE float wsum(float v) {
@@ -138,7 +139,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(WanRowArgs a) {
 // (modulated, no affine: red1 = d shift, red2 = d scale, g = sample;   affine, not modulated: red1 = d bias, red2 = d weight, g = 0)
 template <int NC>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(WanRowArgs a) {
-    __shared__ float lds[kMaxChunks * 512];
+    __shared__ float lds[NC * 512];
     const int lane = threadIdx.x & 63, nchunk = a.D / 8;
     const Strip sp = my_strip(a.rows_per_batch);
     const long mr = (long)sp.b * a.mod_bstride;
@@ -229,7 +230,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(WanRowArgs a) {
 // cos / sin: fp32 [rows_per_batch, head_dim / 2], one entry per complex pair of a head, shared by the heads.
 template <int NC, bool BWD>
 __global__ __launch_bounds__(256) void rms_rope_kernel(WanRowArgs a) {
-    __shared__ float lds[BWD ? kMaxChunks * 512 : 1];
+    __shared__ float lds[BWD ? NC * 512 : 1];
     const int lane = threadIdx.x & 63, nchunk = a.D / 8, half = a.head_dim / 2;
     int row, row_end, step;
     if constexpr (BWD) {
@@ -365,7 +366,7 @@ __global__ __launch_bounds__(256) void gate_res_fwd_kernel(WanRowArgs a) {
 // (x = dout, dy field = the forward's y operand, y field = the dy output)
 template <int NC>
 __global__ __launch_bounds__(256) void gate_res_bwd_kernel(WanRowArgs a) {
-    __shared__ float lds[kMaxChunks * 512];
+    __shared__ float lds[NC * 512];
     const int lane = threadIdx.x & 63, nchunk = a.D / 8;
     const Strip sp = my_strip(a.rows_per_batch);
     const long mr = (long)sp.b * a.mod_bstride;
@@ -400,7 +401,7 @@ __global__ __launch_bounds__(256) void gate_res_bwd_kernel(WanRowArgs a) {
 // ---- red1[g] += sum_rows x   (Linear bias gradients) ----------------------------------------------------------------------------------------
 template <int NC>
 __global__ __launch_bounds__(256) void colsum_kernel(WanRowArgs a) {
-    __shared__ float lds[kMaxChunks * 512];
+    __shared__ float lds[NC * 512];
     const int lane = threadIdx.x & 63, nchunk = a.D / 8;
     const Strip sp = my_strip(a.rows_per_batch);
     float r1[NC][8];
@@ -426,7 +427,7 @@ __global__ __launch_bounds__(256) void colsum_kernel(WanRowArgs a) {
 int check_args(const WanRowArgs& a, const char* who) {
     (void)who;
     if (a.D <= 0 || a.D % 64 != 0 || a.D > kMaxChunks * 512)
-        return set_error(FTMI_ERR_UNSUPPORTED, "wan row-wise kernels: row width must be a multiple of 64, at most 4096");
+        return set_error(FTMI_ERR_UNSUPPORTED, "wan row-wise kernels: row width must be a multiple of 64, at most 5120");
     if (a.rows_per_batch <= 0 || a.rows % a.rows_per_batch != 0) return set_error(FTMI_ERR_INVALID, "wan row-wise kernels: rows must be whole samples");
     if ((a.ld_x % 8) || (a.ld_y % 8) || (a.ld_dy % 8)) return set_error(FTMI_ERR_INVALID, "wan row-wise kernels: row strides must keep 16-byte alignment");
     if (a.rope_cos && (a.head_dim <= 0 || a.head_dim % 8 != 0 || a.D % a.head_dim != 0))
@@ -440,7 +441,9 @@ int check_args(const WanRowArgs& a, const char* who) {
         case 2: hipLaunchKernelGGL((KERNEL<2 __VA_ARGS__>), grid, dim3(256), 0, st, a); break;                    \
         case 3: hipLaunchKernelGGL((KERNEL<3 __VA_ARGS__>), grid, dim3(256), 0, st, a); break;                    \
         case 4: hipLaunchKernelGGL((KERNEL<4 __VA_ARGS__>), grid, dim3(256), 0, st, a); break;                    \
-        default: hipLaunchKernelGGL((KERNEL<8 __VA_ARGS__>), grid, dim3(256), 0, st, a); break;                   \
+        case 5: case 6: case 7: case 8:                                                                           \
+            hipLaunchKernelGGL((KERNEL<8 __VA_ARGS__>), grid, dim3(256), 0, st, a); break;                        \
+        default: hipLaunchKernelGGL((KERNEL<10 __VA_ARGS__>), grid, dim3(256), 0, st, a); break;                  \
     }
 
 inline dim3 row_grid(const WanRowArgs& a) { return dim3((a.rows + 3) / 4); }
@@ -501,9 +504,9 @@ int wan_colsum(const WanRowArgs& a0, hipStream_t st) {
     if (!a0.x || !a0.red1 || a0.D <= 0 || a0.D % 64 != 0) return set_error(FTMI_ERR_INVALID, "wan_colsum: bad argument");
     if (a0.rows <= 0) return 0;
     const int full = a0.D;
-    for (int c0 = 0; c0 < full; c0 += kMaxChunks * 512) {  // wide rows (the feed-forward's 8960): slabs of 4096 columns
+    for (int c0 = 0; c0 < full; c0 += kSlabCols) {  // wide rows (the feed-forward's 8960): slabs of 4096 columns
         WanRowArgs a = a0;
-        a.D = full - c0 < kMaxChunks * 512 ? full - c0 : kMaxChunks * 512;
+        a.D = full - c0 < kSlabCols ? full - c0 : kSlabCols;
         a.x = a0.x + c0;
         a.red1 = a0.red1 + c0;
         if (a0.red_per_batch && a0.rows != a0.rows_per_batch) return set_error(FTMI_ERR_UNSUPPORTED, "wan_colsum: per-sample sums of wide rows are not needed");

@@ -34,6 +34,15 @@
 // Launcher calls per block (an attention counts once): full fine-tune forward 19, backward 39.  Frozen base, r > 0: forward 2 splits + 5 down-projections
 // + the full path's 19 = 26; backward 2 splits + 5 down-projections + 10 adapter-gradient GEMMs + 18 of the full path's 39 (its 7 transposes, 7
 // weight-gradient GEMMs and 7 column sums are gone) = 35, 34 without denc.
+//
+// Image-to-video (Wan2.1-I2V: attn2 with added_kv_proj_dim; the ftmi_wan_i2v_lora_block_* entries, TI > 0 image tokens enc_img [B, TI, D]): attn2 attends to a
+// second, FROZEN key/value set  k_i = RMSNorm(enc_img W_ak^T + b), v_i = enc_img W_av^T + b  (one N = 2D GEMM and one RMSNorm over the B TI image rows) and
+//   o2 = bf(attention(q2, k2, v2)) + bf(attention(q2, k_i, v_i))
+// -- the second attention (attn_ctx2.hip) reads the first one's output and writes the sum, so the forward adds 3 launches (29) and the backward ONE (36): the
+// image branch's dQ, which accumulates onto the text branch's.  No adapter sits on add_k_proj / add_v_proj / norm_added_k (the recipe's regex does not match
+// them): they arrive in a separate flat buffer  W_ak | W_av [2D, D], b_ak | b_av [2D], norm_added_k [D]  and nothing flows back into them or into enc_img.
+// saved, in addition: kvi [B TI, 2D], kin [B TI, D], lse_i, o2s [B S, D] (the summed output: the input of to_out.0; o2 stays the text branch's own output,
+// which its backward needs for rowsum(dO o O)).
 #include "common.hip.h"
 #include "kernels.h"
 
@@ -77,6 +86,8 @@ Offsets offsets_of(size_t D, size_t F) {
 struct Bufs {
     bf16_t *n1, *qkv, *qn, *kn, *o1, *a1, *x1, *n2, *q2, *kv2, *q2n, *k2n, *o2, *x2, *n3, *act, *pre, *f;  // activations
     float *lse1, *lse2;
+    bf16_t *kvi, *kin, *o2s;                                             // image context of attn2 (zero-size at TI = 0)
+    float* lse_i;
     bf16_t *xa_qkv, *xa_o1, *xa_q2, *xa_kv2, *xa_o2;                     // down-projected rows of the adapters (zero-size at r = 0)
     bf16_t *a_sp, *b_ext;                                                // forward operand copies of the adapters
     bf16_t *t_f2, *t_f1, *t_o2, *t_q2, *t_kv2, *t_o1, *t_qkv1;           // transposed weights (full fine-tune only)
@@ -88,9 +99,9 @@ struct Bufs {
 
 // The plan of both buffers, resolved against their bases (the byte planners pass none and read the totals).  frozen: a1, n3, act and f are forward
 // transients instead of saved activations, and the transposed weights are the caller's.
-Bufs make_layout(const ftmi_wan_block_config& c, int rank, bool frozen, void* saved = nullptr, void* scratch = nullptr) {
+Bufs make_layout(const ftmi_wan_block_config& c, int rank, bool frozen, void* saved = nullptr, void* scratch = nullptr, int TI = 0) {
     Bufs w;
-    const size_t M = (size_t)c.B * c.S, Mt = (size_t)c.B * c.T, D = c.D, F = c.F, r = rank > 0 ? rank : 0, e2 = 2, stat = (size_t)c.B * c.H * c.S * 4;
+    const size_t M = (size_t)c.B * c.S, Mt = (size_t)c.B * c.T, Mi = (size_t)c.B * (TI > 0 ? TI : 0), D = c.D, F = c.F, r = rank > 0 ? rank : 0, e2 = 2, stat = (size_t)c.B * c.H * c.S * 4;
     Bump s, f, b;  // saved; scratch of the forward and of the backward, which overlay each other
     auto at = [](void* base, size_t off) { return reinterpret_cast<bf16_t*>(reinterpret_cast<uintptr_t>(base) + off); };
     auto S = [&](size_t bytes) { return at(saved, s.take(bytes)); };
@@ -124,6 +135,10 @@ Bufs make_layout(const ftmi_wan_block_config& c, int rank, bool frozen, void* sa
     w.xa_q2 = S(M * 3 * r * e2);
     w.xa_kv2 = S(Mt * 6 * r * e2);
     w.xa_o2 = S(M * 3 * r * e2);
+    w.kvi = S(Mi * 2 * D * e2);
+    w.kin = S(Mi * D * e2);
+    w.lse_i = f32(S(Mi ? stat : 0));
+    w.o2s = S(Mi ? M * D * e2 : 0);
     w.saved_total = s.off;
     w.a_sp = Fw(8 * 2 * r * D * e2);
     w.b_ext = Fw(8 * D * 3 * r * e2);
@@ -161,7 +176,7 @@ Bufs make_layout(const ftmi_wan_block_config& c, int rank, bool frozen, void* sa
 
 int check_cfg(const ftmi_wan_block_config& c) {
     if (c.B <= 0 || c.S <= 0 || c.T <= 0) return set_error(FTMI_ERR_INVALID, "wan_block: empty problem");
-    if (c.H * 128 != c.D || c.D % 128 != 0 || c.D > 4096) return set_error(FTMI_ERR_UNSUPPORTED, "wan_block: width must be heads x 128, at most 4096");
+    if (c.H * 128 != c.D || c.D % 128 != 0 || c.D > 5120) return set_error(FTMI_ERR_UNSUPPORTED, "wan_block: width must be heads x 128, at most 5120");
     if (c.F <= 0 || (c.F % 64)) return set_error(FTMI_ERR_UNSUPPORTED, "wan_block: the feed-forward width must be a multiple of 64");
     return 0;
 }
@@ -179,6 +194,25 @@ int check_lora_cfg(const ftmi_wan_lora_block_config& c) {
     if (c.r > 0 && c.D < 256) return set_error(FTMI_ERR_UNSUPPORTED, "wan_lora_block: adapters need a width of at least 256");
     return 0;
 }
+
+ftmi_wan_lora_block_config lora_cfg(const ftmi_wan_i2v_lora_block_config& c) {
+    ftmi_wan_lora_block_config l;
+    l.B = c.B; l.S = c.S; l.T = c.T; l.D = c.D; l.H = c.H; l.F = c.F; l.eps = c.eps; l.gemm_variant = c.gemm_variant; l.r = c.r; l.lora_scale = c.lora_scale;
+    return l;
+}
+
+int check_i2v_cfg(const ftmi_wan_i2v_lora_block_config& c) {
+    FTMI_TRY(check_lora_cfg(lora_cfg(c)));
+    if (c.TI < 0 || c.TI > 320) return set_error(FTMI_ERR_UNSUPPORTED, "wan_i2v_lora_block: the image context holds 0 .. 320 tokens");
+    return 0;
+}
+
+// the image context of attn2: TI tokens enc_img [B, TI, D] and the frozen flat buffer  add_k | add_v weight [2D, D], their biases [2D], norm_added_k [D]
+struct ImgCtx {
+    int TI = 0;
+    const bf16_t* params = nullptr;
+    const bf16_t* enc = nullptr;
+};
 
 // the operand copies of one call's adapters and where its (hi | lo | hi) down-projections go
 struct LoraOps {
@@ -205,6 +239,7 @@ struct Block {
     float *grads = nullptr, *dmod = nullptr;      // backward: flat fp32 base gradients, fp32 [6, B, D] modulation sums (both ADDED to)
     float *grad_a = nullptr, *grad_b = nullptr;  // backward: fp32 [8, r, D] / [8, D, r] (ADDED to)
     Twins t;
+    ImgCtx img;
     hipStream_t st = nullptr;
 };
 
@@ -350,8 +385,19 @@ int block_forward(const Block& k, bf16_t* out) {
         FTMI_TRY(wan_rms_rope_fwd(b, st));
     }
     FTMI_TRY(attn_fwd(attn_args(c, L.q2n, L.k2n, L.kv2, 2 * D, L.o2, L.lse2, S, T), st));
+    const bf16_t* o2 = L.o2;
+    if (k.img.TI > 0) {  // the image tokens' keys and values (frozen, no adapters), then their attention summed onto the text branch's output
+        const int TI = k.img.TI, Mi = B * TI;
+        const bf16_t* ip = k.img.params;
+        FTMI_TRY(proj_fwd(k, k.img.enc, Mi, D, ip, ip + 2 * (size_t)D * D, 2 * D, 0, 0, nullptr, L.kvi));
+        WanRowArgs a = row_args(L.kvi, 2 * D, L.kin, D, Mi, D, TI, eps);
+        a.w = ip + 2 * (size_t)D * D + 2 * D;
+        FTMI_TRY(wan_rms_rope_fwd(a, st));
+        FTMI_TRY(attn_ctx2_fwd(attn_args(c, L.q2n, L.kin, L.kvi, 2 * D, L.o2s, L.lse_i, S, TI), L.o2, st));
+        o2 = L.o2s;
+    }
     bf16_t* a2 = L.f;  // (the feed-forward output buffer doubles as the staging of o2 W_o2^T + b: it is consumed by the next launch)
-    FTMI_TRY(proj_fwd(k, L.o2, M, D, P(O.w_o2), P(O.b_o2), D, 7, 1, L.xa_o2, a2));
+    FTMI_TRY(proj_fwd(k, o2, M, D, P(O.w_o2), P(O.b_o2), D, 7, 1, L.xa_o2, a2));
     {
         WanRowArgs a = row_args(L.x1, D, L.x2, D, M, D, S, eps);
         a.dy = a2; a.ld_dy = D;
@@ -418,8 +464,10 @@ int block_backward(const Block& k, const bf16_t* dout, bf16_t* dx, bf16_t* denc)
         FTMI_TRY(wan_ln_bwd(a, st));
     }
     // cross-attention branch: x2 = x1 + a2
-    FTMI_TRY(proj_bwd(k, L.o2, L.dx2, M, D, D, k.t.o2, 7, 1, L.xa_o2, L.do2, G(O.w_o2), G(O.b_o2)));
+    FTMI_TRY(proj_bwd(k, k.img.TI > 0 ? L.o2s : L.o2, L.dx2, M, D, D, k.t.o2, 7, 1, L.xa_o2, L.do2, G(O.w_o2), G(O.b_o2)));
     FTMI_TRY(attn_bwd(attn_bwd_args(attn_args(c, L.q2n, L.k2n, L.kv2, 2 * D, L.o2, L.lse2, S, T), L.do2, L.dq2n, L.dk2n, L.dkv2, L.delta), st));
+    if (k.img.TI > 0)  // the image branch's dQ, added onto the text branch's in place (its keys and values are frozen: no dK, dV)
+        FTMI_TRY(attn_ctx2_dq(attn_bwd_args(attn_args(c, L.q2n, L.kin, L.kvi, 2 * D, L.o2s, L.lse_i, S, k.img.TI), L.do2, L.dq2n, nullptr, L.dkv2, nullptr), L.dq2n, st));
     {
         WanRowArgs a = row_args(L.q2, D, L.dq2, D, M, D, S, eps);
         a.w = P(O.nq2); a.dy = L.dq2n; a.ld_dy = D; a.red2 = G(O.nq2);
@@ -502,14 +550,15 @@ int wan_block_backward(const ftmi_wan_block_config& c, const bf16_t* params, flo
     return block_backward(k, dout, dx, denc);
 }
 
-int wan_lora_block_forward(const ftmi_wan_lora_block_config& c, const ftmi_wan_lora_block_weights& w, const bf16_t* x, const bf16_t* enc, const float* mod,
-                           const float* rope_cos, const float* rope_sin, bf16_t* out, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
-                           hipStream_t st) {
-    FTMI_TRY(check_lora_cfg(c));
-    const Bufs L = make_layout(base_cfg(c), c.r, true, saved, scratch);
+namespace {
+
+int lora_forward(const ftmi_wan_lora_block_config& c, const ftmi_wan_lora_block_weights& w, const ImgCtx& img, const bf16_t* x, const bf16_t* enc, const float* mod,
+                 const float* rope_cos, const float* rope_sin, bf16_t* out, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st) {
+    const Bufs L = make_layout(base_cfg(c), c.r, true, saved, scratch, img.TI);
     if (saved_bytes < L.saved_total || scratch_bytes < L.scratch_total) return set_error(FTMI_ERR_INVALID, "wan_lora_block_forward: buffer too small");
     if (c.r > 0 && (!w.lora_a || !w.lora_b)) return set_error(FTMI_ERR_INVALID, "wan_lora_block_forward: LoRA rank without adapters");
     Block k = make_block(base_cfg(c), w.params, L, x, enc, mod, rope_cos, rope_sin, st);
+    k.img = img;
     const int D = c.D, r = c.r;
     k.lo.r = r; k.lo.s = c.lora_scale;
     if (r > 0) {  // operand copies of the fp32 adapters, once per call: A as (hi, lo) row planes, B as [hi | hi | lo] K-extension columns
@@ -525,11 +574,10 @@ int wan_lora_block_forward(const ftmi_wan_lora_block_config& c, const ftmi_wan_l
 }
 
 // grad_a fp32 [8, r, D] / grad_b fp32 [8, D, r] ADDED to.
-int wan_lora_block_backward(const ftmi_wan_lora_block_config& c, const ftmi_wan_lora_block_weights& w, const bf16_t* x, const bf16_t* enc, const float* mod,
-                            const float* rope_cos, const float* rope_sin, const bf16_t* dout, bf16_t* dx, bf16_t* denc, float* grad_a, float* grad_b, void* saved,
-                            size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st) {
-    FTMI_TRY(check_lora_cfg(c));
-    const Bufs L = make_layout(base_cfg(c), c.r, true, saved, scratch);
+int lora_backward(const ftmi_wan_lora_block_config& c, const ftmi_wan_lora_block_weights& w, const ImgCtx& img, const bf16_t* x, const bf16_t* enc, const float* mod,
+                  const float* rope_cos, const float* rope_sin, const bf16_t* dout, bf16_t* dx, bf16_t* denc, float* grad_a, float* grad_b, void* saved,
+                  size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st) {
+    const Bufs L = make_layout(base_cfg(c), c.r, true, saved, scratch, img.TI);
     if (saved_bytes < L.saved_total || scratch_bytes < L.scratch_total) return set_error(FTMI_ERR_INVALID, "wan_lora_block_backward: buffer too small");
     if (c.r > 0 && (!w.lora_a || !w.lora_b || !grad_a || !grad_b)) return set_error(FTMI_ERR_INVALID, "wan_lora_block_backward: LoRA rank without adapters / gradient buffers");
     if (!w.w_qkv1_t || !w.w_o1_t || !w.w_q2_t || !w.w_kv2_t || !w.w_o2_t || !w.w_f1_t || !w.w_f2_t)
@@ -538,6 +586,7 @@ int wan_lora_block_backward(const ftmi_wan_lora_block_config& c, const ftmi_wan_
     auto WT = [](const void* p) { return reinterpret_cast<const bf16_t*>(p); };
     k.t.qkv1 = WT(w.w_qkv1_t); k.t.o1 = WT(w.w_o1_t); k.t.q2 = WT(w.w_q2_t); k.t.kv2 = WT(w.w_kv2_t); k.t.o2 = WT(w.w_o2_t); k.t.f1 = WT(w.w_f1_t); k.t.f2 = WT(w.w_f2_t);
     k.grad_a = grad_a; k.grad_b = grad_b;
+    k.img = img;
     const int D = c.D, r = c.r;
     k.lo.r = r; k.lo.s = c.lora_scale;
     if (r > 0) {
@@ -550,6 +599,51 @@ int wan_lora_block_backward(const ftmi_wan_lora_block_config& c, const ftmi_wan_
         k.lo.sp = L.bt_sp; k.lo.ext = L.at_ext;
     }
     return block_backward(k, dout, dx, denc);
+}
+
+ImgCtx img_ctx(const ftmi_wan_i2v_lora_block_config& c, const bf16_t* img_params, const bf16_t* enc_img) {
+    ImgCtx g;
+    g.TI = c.TI; g.params = img_params; g.enc = enc_img;
+    return g;
+}
+
+}  // namespace
+
+int wan_lora_block_forward(const ftmi_wan_lora_block_config& c, const ftmi_wan_lora_block_weights& w, const bf16_t* x, const bf16_t* enc, const float* mod,
+                           const float* rope_cos, const float* rope_sin, bf16_t* out, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
+                           hipStream_t st) {
+    FTMI_TRY(check_lora_cfg(c));
+    return lora_forward(c, w, ImgCtx(), x, enc, mod, rope_cos, rope_sin, out, saved, saved_bytes, scratch, scratch_bytes, st);
+}
+int wan_lora_block_backward(const ftmi_wan_lora_block_config& c, const ftmi_wan_lora_block_weights& w, const bf16_t* x, const bf16_t* enc, const float* mod,
+                            const float* rope_cos, const float* rope_sin, const bf16_t* dout, bf16_t* dx, bf16_t* denc, float* grad_a, float* grad_b, void* saved,
+                            size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st) {
+    FTMI_TRY(check_lora_cfg(c));
+    return lora_backward(c, w, ImgCtx(), x, enc, mod, rope_cos, rope_sin, dout, dx, denc, grad_a, grad_b, saved, saved_bytes, scratch, scratch_bytes, st);
+}
+
+// (0 for a configuration the block refuses: the message is in ftmi_last_error)
+size_t wan_i2v_lora_block_saved_bytes(const ftmi_wan_i2v_lora_block_config& c) {
+    return check_i2v_cfg(c) ? 0 : make_layout(base_cfg(lora_cfg(c)), c.r, true, nullptr, nullptr, c.TI).saved_total;
+}
+size_t wan_i2v_lora_block_scratch_bytes(const ftmi_wan_i2v_lora_block_config& c) {
+    return check_i2v_cfg(c) ? 0 : make_layout(base_cfg(lora_cfg(c)), c.r, true, nullptr, nullptr, c.TI).scratch_total;
+}
+int wan_i2v_lora_block_forward(const ftmi_wan_i2v_lora_block_config& c, const ftmi_wan_lora_block_weights& w, const bf16_t* img_params, const bf16_t* x,
+                               const bf16_t* enc, const bf16_t* enc_img, const float* mod, const float* rope_cos, const float* rope_sin, bf16_t* out, void* saved,
+                               size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st) {
+    FTMI_TRY(check_i2v_cfg(c));
+    if (c.TI > 0 && (!img_params || !enc_img)) return set_error(FTMI_ERR_INVALID, "wan_i2v_lora_block_forward: image tokens without their parameters");
+    return lora_forward(lora_cfg(c), w, img_ctx(c, img_params, enc_img), x, enc, mod, rope_cos, rope_sin, out, saved, saved_bytes, scratch, scratch_bytes, st);
+}
+int wan_i2v_lora_block_backward(const ftmi_wan_i2v_lora_block_config& c, const ftmi_wan_lora_block_weights& w, const bf16_t* img_params, const bf16_t* x,
+                                const bf16_t* enc, const bf16_t* enc_img, const float* mod, const float* rope_cos, const float* rope_sin, const bf16_t* dout,
+                                bf16_t* dx, bf16_t* denc, float* grad_a, float* grad_b, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
+                                hipStream_t st) {
+    FTMI_TRY(check_i2v_cfg(c));
+    if (c.TI > 0 && (!img_params || !enc_img)) return set_error(FTMI_ERR_INVALID, "wan_i2v_lora_block_backward: image tokens without their parameters");
+    return lora_backward(lora_cfg(c), w, img_ctx(c, img_params, enc_img), x, enc, mod, rope_cos, rope_sin, dout, dx, denc, grad_a, grad_b, saved, saved_bytes, scratch,
+                         scratch_bytes, st);
 }
 
 }  // namespace ftmi

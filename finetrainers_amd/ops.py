@@ -80,6 +80,42 @@ def attn_bwd(q, k, v, out, lse, dout, key_bias=None, scale=None, dv_out=None):
     return dq, dk, dv
 
 
+def attn_ctx2_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out_first: torch.Tensor, scale: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Second context of a two-context cross-attention (head_dim 128, at most 320 keys), run after ``attn_fwd`` on the first one: returns
+    (bf16(out_first + bf16(softmax(q k^T scale) v)) laid out like ``out_first``, lse [B, H, Sq] of this context)."""
+    for n, t in (("query", q), ("key", k), ("value", v), ("out_first", out_first)):
+        require_gpu_tensor(t, n, bf16)
+    B, H, Sq, d = q.shape
+    if out_first.shape != q.shape:
+        raise ValueError("attn_ctx2_fwd: out_first must be [B, H, Sq, head_dim]")
+    scale = (1.0 / d**0.5) if scale is None else scale
+    out = torch.empty_strided(out_first.shape, out_first.stride(), dtype=bf16, device=q.device)
+    lse = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
+    desc = _desc(q, k, v, out, scale)
+    check(_lib.load().ftmi_attn_ctx2_fwd(ctypes.byref(desc), ptr(q), ptr(k), ptr(v), ptr(out_first), ptr(out), ptr(lse), stream_ptr()), "ftmi_attn_ctx2_fwd")
+    return out, lse
+
+
+def attn_ctx2_dq(q, k, v, lse, dout, dq_first, scale=None, inplace: bool = False):
+    """dQ of the second context added onto the first context's: bf16(dq_first + bf16(dq of this context)), laid out like ``dq_first`` (``inplace``: written
+    into it).  There is no dK / dV (the second context's keys and values are frozen where this is used)."""
+    for n, t in (("query", q), ("key", k), ("value", v), ("dout", dout), ("dq_first", dq_first)):
+        require_gpu_tensor(t, n, bf16)
+    require_gpu_tensor(lse, "lse", torch.float32)
+    B, H, Sq, d = q.shape
+    scale = (1.0 / d**0.5) if scale is None else scale
+    if dout.stride(3) != 1:
+        dout = dout.contiguous()
+    if dq_first.shape != q.shape or dout.shape != q.shape:
+        raise ValueError("attn_ctx2_dq: dout and dq_first must be [B, H, Sq, head_dim]")
+    if lse.shape != (B, H, Sq) or not lse.is_contiguous():
+        raise ValueError("attn_ctx2_dq: lse must be the contiguous fp32 [B, H, Sq] tensor attn_ctx2_fwd returned")
+    dq = dq_first if inplace else torch.empty_strided(dq_first.shape, dq_first.stride(), dtype=bf16, device=q.device)
+    desc = _desc(q, k, v, None, scale, dout, dq)
+    check(_lib.load().ftmi_attn_ctx2_dq(ctypes.byref(desc), ptr(q), ptr(k), ptr(v), ptr(lse), ptr(dout), ptr(dq_first), ptr(dq), stream_ptr()), "ftmi_attn_ctx2_dq")
+    return dq
+
+
 def gemm_nt(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, alpha: float = 1.0, epilogue: int = 0,
             resid: Optional[torch.Tensor] = None, gate: Optional[torch.Tensor] = None, rows_per_batch: int = 0,
             aux: Optional[torch.Tensor] = None, want_out2: bool = False, variant: int = 8, out: Optional[torch.Tensor] = None):

@@ -22,7 +22,7 @@ import ctypes
 import os
 
 from .. import _lib, ops
-from .._lib import WanBlockConfig, WanLoraBlockConfig, WanLoraBlockWeights, check, ptr, stream_ptr
+from .._lib import WanBlockConfig, WanI2VLoraBlockConfig, WanLoraBlockConfig, WanLoraBlockWeights, check, ptr, stream_ptr
 
 bf16 = torch.bfloat16
 _NATIVE_SCRATCH: Dict[int, torch.Tensor] = {}  # device index -> byte buffer shared by every natively run block on that device (one stream at a time)
@@ -92,6 +92,32 @@ class WanBlockLayout:
         return {name: self.view(flat, name) for name, _ in self.entries}
 
 
+class WanImageLayout:
+    """Image-to-video (``added_kv_proj_dim``): attn2's second, frozen key / value set in a flat buffer of its OWN -- ``WanBlockLayout`` and the block's
+    flat buffer stay what they are.  add_k_proj | add_v_proj are ONE [2D, D] matrix for the GEMM over the image rows."""
+
+    def __init__(self, dim: int):
+        D = dim
+        self.entries: List[Tuple[str, Tuple[int, ...]]] = [
+            ("attn2.add_k_proj.weight", (D, D)), ("attn2.add_v_proj.weight", (D, D)), ("attn2.add_k_proj.bias", (D,)), ("attn2.add_v_proj.bias", (D,)),
+            ("attn2.norm_added_k.weight", (D,)),
+        ]
+        self.offsets = {"attn2.add_k_proj.weight": (0, (D, D)), "attn2.add_v_proj.weight": (D * D, (D, D)), "attn2.add_k_proj.bias": (2 * D * D, (D,)),
+                        "attn2.add_v_proj.bias": (2 * D * D + D, (D,)), "attn2.norm_added_k.weight": (2 * D * D + 2 * D, (D,)),
+                        "w_kvi": (0, (2 * D, D)), "b_kvi": (2 * D * D, (2 * D,))}
+        self.total = 2 * D * D + 3 * D
+
+    def view(self, flat: torch.Tensor, name: str) -> torch.Tensor:
+        off, shape = self.offsets[name]
+        n = 1
+        for d in shape:
+            n *= d
+        return flat[off:off + n].view(shape)
+
+    def named_views(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
+        return {name: self.view(flat, name) for name, _ in self.entries}
+
+
 # ---- the block as a composition of the library's launches from Python ----------------------------------------------------------------------------
 # ONE forward and ONE backward walk for full fine-tuning and for LoRA over a frozen base, launch for launch what csrc/wan_dit.hip block_forward /
 # block_backward issue: the second implementation the tests compare the C calls with (``native = False`` / ``FTMI_NATIVE_BLOCKS=0``).
@@ -118,6 +144,8 @@ class _Acts(NamedTuple):
     frozen base drops them; xa_*: the adapters' down-projected rows (None at r = 0)."""
     n1: Any; qkv: Any; qn: Any; kn: Any; o1: Any; lse1: Any; a1: Any; x1: Any; n2: Any; q2: Any; kv2: Any; q2n: Any; k2n: Any; o2: Any; lse2: Any; x2: Any
     n3: Any; act: Any; pre: Any; f: Any; xa_qkv: Any; xa_o1: Any; xa_q2: Any; xa_kv2: Any; xa_o2: Any
+    # image-to-video: the image tokens' k|v rows, their normed keys, the image attention's lse and the SUMMED attention output (o2 stays the text branch's own)
+    kvi: Any = None; kin: Any = None; lse_i: Any = None; o2s: Any = None
 
     def for_frozen_base(self) -> "_Acts":
         return self._replace(a1=None, n3=None, act=None, f=None)
@@ -163,7 +191,7 @@ def _lora_linear_bwd(x, dy, w_t, adp: int, nadp: int, xa, bt_sp, at_ext, r: int,
     return dx
 
 
-def _block_forward(blk: "MI355XWanBlock", x, enc, mod, rope, lora: _Lora, need_out: bool = True):
+def _block_forward(blk: "MI355XWanBlock", x, enc, mod, rope, lora: _Lora, need_out: bool = True, enc_img=None):
     """mod: fp32 [B, 6, D] = (shift, scale, gate) of the attention, then of the feed-forward.  Returns (out [B, S, D], _Acts); ``need_out=False`` (the
     recomputation pass of gradient checkpointing) stops after the feed-forward's first GEMM: its pre-activation is the last thing the backward reads."""
     B, S, D = x.shape
@@ -193,7 +221,13 @@ def _block_forward(blk: "MI355XWanBlock", x, enc, mod, rope, lora: _Lora, need_o
     q2n = ops.wan_rms_rope(q2, P("attn2.norm_q.weight"), S, eps=eps)
     k2n = ops.wan_rms_rope(kv2[:, :D], P("attn2.norm_k.weight"), T, eps=eps)
     o2, lse2 = ops.attn_fwd(heads(q2n, S), heads(k2n, T), heads(kv2[:, D:], T))
-    a2, xa_o2 = lin(tok(o2), P("attn2.to_out.0.weight"), P("attn2.to_out.0.bias"), 7, 1)
+    kvi = kin = lse_i = o2s = None
+    if enc_img is not None and enc_img.shape[1] > 0:  # the image tokens' frozen keys and values; their attention is summed onto the text branch's output
+        TI, IP = enc_img.shape[1], blk.img_param
+        kvi = ops.gemm_nt(enc_img.view(B * TI, D), IP("w_kvi"), IP("b_kvi"))
+        kin = ops.wan_rms_rope(kvi[:, :D], IP("attn2.norm_added_k.weight"), TI, eps=eps)
+        o2s, lse_i = ops.attn_ctx2_fwd(heads(q2n, S), heads(kin, TI), heads(kvi[:, D:], TI), o2)
+    a2, xa_o2 = lin(tok(o2 if o2s is None else o2s), P("attn2.to_out.0.weight"), P("attn2.to_out.0.bias"), 7, 1)
     x2 = ops.wan_gate_res(x1, a2, S)
     # feed-forward
     n3 = ops.wan_ln(x2, S, shift=mod[:, 3], scale=mod[:, 4], eps=eps)
@@ -202,7 +236,7 @@ def _block_forward(blk: "MI355XWanBlock", x, enc, mod, rope, lora: _Lora, need_o
     if need_out:
         f = ops.gemm_nt(act, P("ffn.net.2.weight"), P("ffn.net.2.bias"))
         out = ops.wan_gate_res(x2, f, S, gate=mod[:, 5]).view(B, S, D)
-    return out, _Acts(n1, qkv, qn, kn, o1, lse1, a1, x1, n2, q2, kv2, q2n, k2n, o2, lse2, x2, n3, act, pre, f, xa_qkv, xa_o1, xa_q2, xa_kv2, xa_o2)
+    return out, _Acts(n1, qkv, qn, kn, o1, lse1, a1, x1, n2, q2, kv2, q2n, k2n, o2, lse2, x2, n3, act, pre, f, xa_qkv, xa_o1, xa_q2, xa_kv2, xa_o2, kvi, kin, lse_i, o2s)
 
 
 def _block_backward(blk: "MI355XWanBlock", acts: _Acts, x, enc, mod, rope, dout, lora: _Lora, train_base: bool, need_denc: bool = True):
@@ -237,9 +271,12 @@ def _block_backward(blk: "MI355XWanBlock", acts: _Acts, x, enc, mod, rope, dout,
     dn3 = ops.gemm_nt(dpre, Wt["ffn.net.0.proj.weight"], None)
     dx2 = ops.wan_ln_bwd(c.x2, dn3, S, scale=mod[:, 4], eps=eps, dres=dout, red1=DM(3), red2=DM(4), red_per_batch=train_base)
     # cross-attention branch: x2 = x1 + a2
-    do2 = lin(tok(c.o2), dx2, Wt["attn2.to_out.0.weight"], 7, 1, c.xa_o2, gw=G("attn2.to_out.0.weight"), gbias=G("attn2.to_out.0.bias"))
+    do2 = lin(tok(c.o2 if c.o2s is None else c.o2s), dx2, Wt["attn2.to_out.0.weight"], 7, 1, c.xa_o2, gw=G("attn2.to_out.0.weight"), gbias=G("attn2.to_out.0.bias"))
     dkv2 = torch.empty_like(c.kv2)
     dq2n, dk2n, _ = ops.attn_bwd(heads(c.q2n, S), heads(c.k2n, T), heads(c.kv2[:, D:], T), c.o2, c.lse2, heads(do2, S), dv_out=heads(dkv2[:, D:], T))
+    if c.o2s is not None:  # the image branch's dQ, added onto the text branch's in place (frozen keys and values: no dK, dV)
+        TI = c.kin.shape[0] // B
+        ops.attn_ctx2_dq(heads(c.q2n, S), heads(c.kin, TI), heads(c.kvi[:, D:], TI), c.lse_i, heads(do2, S), dq2n, inplace=True)
     dq2 = ops.wan_rms_rope_bwd(c.q2, P("attn2.norm_q.weight"), tok(dq2n), S, eps=eps, dweight=G("attn2.norm_q.weight"))
     ops.wan_rms_rope_bwd(c.kv2[:, :D], P("attn2.norm_k.weight"), tok(dk2n), T, eps=eps, dweight=G("attn2.norm_k.weight"), out=dkv2[:, :D])
     _linear_grads(dq2, c.n2, G("attn2.to_q.weight"), G("attn2.to_q.bias"))  # (attn2.to_q's weight gradient goes ahead of the text rows' projection)
@@ -352,30 +389,54 @@ class _WanLoRABlockFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, blk: "MI355XWanBlock", x, enc, temb, rope_cos, rope_sin, lora_a, lora_b):
+        return _WanLoRABlockFunction._fwd(ctx, blk, x, enc, None, temb, rope_cos, rope_sin, lora_a, lora_b)
+
+    @staticmethod
+    def backward(ctx, dout):
+        dx, denc, ga, gb = _WanLoRABlockFunction._bwd(ctx, dout)
+        return None, dx, denc, None, None, None, ga, gb
+
+    @staticmethod
+    def _fwd(ctx, blk, x, enc, enc_img, temb, rope_cos, rope_sin, lora_a, lora_b):
         mod = (blk.param("scale_shift_table").float() + temb.float()).contiguous()
-        out, acts = _block_forward(blk, x, enc, mod, (rope_cos, rope_sin), _Lora(lora_a, lora_b))
-        ctx.blk, ctx.rope, ctx.has_lora = blk, (rope_cos, rope_sin), lora_a is not None
+        out, acts = _block_forward(blk, x, enc, mod, (rope_cos, rope_sin), _Lora(lora_a, lora_b), enc_img=enc_img)
+        ctx.blk, ctx.rope, ctx.has_lora, ctx.has_img = blk, (rope_cos, rope_sin), lora_a is not None, enc_img is not None
         ctx.recompute = bool(blk.gradient_checkpointing)
         la, lb = (lora_a, lora_b) if lora_a is not None else (x.new_empty(0), x.new_empty(0))
-        ctx.save_for_backward(x, enc, mod, la, lb)
+        ctx.save_for_backward(x, enc, mod, la, lb, enc_img if enc_img is not None else x.new_empty(0))
         ctx.acts = None if ctx.recompute else acts.for_frozen_base()
         return out
 
     @staticmethod
-    def backward(ctx, dout):
+    def _bwd(ctx, dout):
         blk, rope = ctx.blk, ctx.rope
-        x, enc, mod, lora_a, lora_b = ctx.saved_tensors
+        x, enc, mod, lora_a, lora_b, enc_img = ctx.saved_tensors
         if not ctx.has_lora:
             lora_a = lora_b = None
+        if not ctx.has_img:
+            enc_img = None
         acts, ctx.acts = ctx.acts, None
         if ctx.recompute:
-            acts = _block_forward(blk, x, enc, mod, rope, _Lora(lora_a, lora_b), need_out=False)[1].for_frozen_base()
+            acts = _block_forward(blk, x, enc, mod, rope, _Lora(lora_a, lora_b), need_out=False, enc_img=enc_img)[1].for_frozen_base()
         own, ga, gb = _grad_targets(blk, lora_a, lora_b)
         dx, denc, _ = _block_backward(blk, acts, x, enc, mod, rope, dout, _Lora(lora_a, lora_b, ga, gb), train_base=False, need_denc=ctx.needs_input_grad[2])
         if own:
             blk._backward_done()
             ga = gb = None
-        return None, dx, denc, None, None, None, ga, gb
+        return dx, denc, ga, gb
+
+
+class _WanI2VLoRABlockFunction(torch.autograd.Function):
+    """``_WanLoRABlockFunction`` with the image context ``enc_img`` [B, TI, D] in attn2 (frozen: no gradient flows into it)."""
+
+    @staticmethod
+    def forward(ctx, blk: "MI355XWanBlock", x, enc, temb, rope_cos, rope_sin, lora_a, lora_b, enc_img):
+        return _WanLoRABlockFunction._fwd(ctx, blk, x, enc, enc_img, temb, rope_cos, rope_sin, lora_a, lora_b)
+
+    @staticmethod
+    def backward(ctx, dout):
+        dx, denc, ga, gb = _WanLoRABlockFunction._bwd(ctx, dout)
+        return None, dx, denc, None, None, None, ga, gb, None
 
 
 class _WanLoRABlockNativeFunction(torch.autograd.Function):
@@ -384,9 +445,10 @@ class _WanLoRABlockNativeFunction(torch.autograd.Function):
     refills ``saved`` inside the backward (the forward call with ``out = NULL``)."""
 
     @staticmethod
-    def _args(blk: "MI355XWanBlock", B: int, S: int, T: int, lora_a, lora_b, backward: bool):
-        cfg = WanLoraBlockConfig(B=B, S=S, T=T, D=blk.dim, H=blk.heads, F=blk.ffn_dim, eps=float(blk.eps), gemm_variant=8,
-                                 r=0 if lora_a is None else int(lora_a.shape[1]), lora_scale=float(blk.lora_scale))
+    def _args(blk: "MI355XWanBlock", B: int, S: int, T: int, lora_a, lora_b, backward: bool, TI: Optional[int] = None):
+        kw = dict(B=B, S=S, T=T, D=blk.dim, H=blk.heads, F=blk.ffn_dim, eps=float(blk.eps), gemm_variant=8, r=0 if lora_a is None else int(lora_a.shape[1]),
+                  lora_scale=float(blk.lora_scale))
+        cfg = WanLoraBlockConfig(**kw) if TI is None else WanI2VLoraBlockConfig(TI=TI, **kw)  # TI given: the ftmi_wan_i2v_lora_block_* entries
         w = WanLoraBlockWeights()
         params = blk._params()
         if params.numel() != blk.layout.total or not params.is_contiguous():
@@ -405,10 +467,19 @@ class _WanLoRABlockNativeFunction(torch.autograd.Function):
         return cfg, w, keep
 
     @staticmethod
-    def _forward_call(blk, x, enc, mod, rope_cos, rope_sin, lora_a, lora_b, out):
+    def _forward_call(blk, x, enc, mod, rope_cos, rope_sin, lora_a, lora_b, out, enc_img=None):
         B, S, _ = x.shape
-        cfg, w, keep = _WanLoRABlockNativeFunction._args(blk, B, S, enc.shape[1], lora_a, lora_b, backward=False)
         lib = _lib.load()
+        if enc_img is not None:
+            cfg, w, keep = _WanLoRABlockNativeFunction._args(blk, B, S, enc.shape[1], lora_a, lora_b, backward=False, TI=enc_img.shape[1])
+            saved = torch.empty(lib.ftmi_wan_i2v_lora_block_saved_bytes(ctypes.byref(cfg)), dtype=torch.uint8, device=x.device)
+            scratch = _native_scratch(x.device, lib.ftmi_wan_i2v_lora_block_scratch_bytes(ctypes.byref(cfg)))
+            img = blk._img_params() if cfg.TI > 0 else None
+            check(lib.ftmi_wan_i2v_lora_block_forward(ctypes.byref(cfg), ctypes.byref(w), ptr(img), ptr(x), ptr(enc), ptr(enc_img if cfg.TI > 0 else None), ptr(mod),
+                                                      ptr(rope_cos), ptr(rope_sin), ptr(out), ptr(saved), saved.numel(), ptr(scratch), scratch.numel(), stream_ptr()),
+                  "ftmi_wan_i2v_lora_block_forward")
+            return saved
+        cfg, w, keep = _WanLoRABlockNativeFunction._args(blk, B, S, enc.shape[1], lora_a, lora_b, backward=False)
         saved = torch.empty(lib.ftmi_wan_lora_block_saved_bytes(ctypes.byref(cfg)), dtype=torch.uint8, device=x.device)
         scratch = _native_scratch(x.device, lib.ftmi_wan_lora_block_scratch_bytes(ctypes.byref(cfg)))
         check(lib.ftmi_wan_lora_block_forward(ctypes.byref(cfg), ctypes.byref(w), ptr(x), ptr(enc), ptr(mod), ptr(rope_cos), ptr(rope_sin), ptr(out), ptr(saved),
@@ -417,44 +488,73 @@ class _WanLoRABlockNativeFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, blk: "MI355XWanBlock", x, enc, temb, rope_cos, rope_sin, lora_a, lora_b):
-        mod = (blk.param("scale_shift_table").float() + temb.float()).contiguous()
-        out = torch.empty_like(x)
-        saved = _WanLoRABlockNativeFunction._forward_call(blk, x, enc, mod, rope_cos, rope_sin, lora_a, lora_b, out)
-        ctx.blk, ctx.rope, ctx.has_lora = blk, (rope_cos, rope_sin), lora_a is not None
-        ctx.recompute = bool(blk.gradient_checkpointing)
-        la, lb = (lora_a, lora_b) if lora_a is not None else (x.new_empty(0), x.new_empty(0))
-        if ctx.recompute:
-            ctx.save_for_backward(x, enc, mod, la, lb)
-        else:
-            ctx.save_for_backward(x, enc, mod, la, lb, saved)
-        return out
+        return _WanLoRABlockNativeFunction._fwd(ctx, blk, x, enc, None, temb, rope_cos, rope_sin, lora_a, lora_b)
 
     @staticmethod
     def backward(ctx, dout):
+        dx, denc, ga, gb = _WanLoRABlockNativeFunction._bwd(ctx, dout)
+        return None, dx, denc, None, None, None, ga, gb
+
+    @staticmethod
+    def _fwd(ctx, blk, x, enc, enc_img, temb, rope_cos, rope_sin, lora_a, lora_b):
+        mod = (blk.param("scale_shift_table").float() + temb.float()).contiguous()
+        out = torch.empty_like(x)
+        saved = _WanLoRABlockNativeFunction._forward_call(blk, x, enc, mod, rope_cos, rope_sin, lora_a, lora_b, out, enc_img)
+        ctx.blk, ctx.rope, ctx.has_lora, ctx.has_img = blk, (rope_cos, rope_sin), lora_a is not None, enc_img is not None
+        ctx.recompute = bool(blk.gradient_checkpointing)
+        la, lb = (lora_a, lora_b) if lora_a is not None else (x.new_empty(0), x.new_empty(0))
+        keep = (x, enc, mod, la, lb, enc_img if enc_img is not None else x.new_empty(0))
+        ctx.save_for_backward(*(keep if ctx.recompute else keep + (saved,)))
+        return out
+
+    @staticmethod
+    def _bwd(ctx, dout):
         blk, rope = ctx.blk, ctx.rope
-        if ctx.recompute:
-            x, enc, mod, lora_a, lora_b = ctx.saved_tensors
-        else:
-            x, enc, mod, lora_a, lora_b, saved = ctx.saved_tensors
+        x, enc, mod, lora_a, lora_b, enc_img = ctx.saved_tensors[:6]
         if not ctx.has_lora:
             lora_a = lora_b = None
+        if not ctx.has_img:
+            enc_img = None
         if ctx.recompute:
-            saved = _WanLoRABlockNativeFunction._forward_call(blk, x, enc, mod, rope[0], rope[1], lora_a, lora_b, None)
+            saved = _WanLoRABlockNativeFunction._forward_call(blk, x, enc, mod, rope[0], rope[1], lora_a, lora_b, None, enc_img)
+        else:
+            saved = ctx.saved_tensors[6]
         B, S, _ = x.shape
         dout = dout.contiguous()
         own, ga, gb = _grad_targets(blk, lora_a, lora_b)
-        cfg, w, keep = _WanLoRABlockNativeFunction._args(blk, B, S, enc.shape[1], lora_a, lora_b, backward=True)
         lib = _lib.load()
-        scratch = _native_scratch(x.device, lib.ftmi_wan_lora_block_scratch_bytes(ctypes.byref(cfg)))
         dx = torch.empty_like(x)
         denc = torch.empty_like(enc) if ctx.needs_input_grad[2] else None  # frozen text embedder: no gradient into the text rows, its GEMM is skipped
-        check(lib.ftmi_wan_lora_block_backward(ctypes.byref(cfg), ctypes.byref(w), ptr(x), ptr(enc), ptr(mod), ptr(rope[0]), ptr(rope[1]), ptr(dout), ptr(dx),
-                                               ptr(denc), ptr(ga), ptr(gb), ptr(saved), saved.numel(), ptr(scratch), scratch.numel(), stream_ptr()),
-              "ftmi_wan_lora_block_backward")
+        if enc_img is not None:
+            cfg, w, keep = _WanLoRABlockNativeFunction._args(blk, B, S, enc.shape[1], lora_a, lora_b, backward=True, TI=enc_img.shape[1])
+            scratch = _native_scratch(x.device, lib.ftmi_wan_i2v_lora_block_scratch_bytes(ctypes.byref(cfg)))
+            img = blk._img_params() if cfg.TI > 0 else None
+            check(lib.ftmi_wan_i2v_lora_block_backward(ctypes.byref(cfg), ctypes.byref(w), ptr(img), ptr(x), ptr(enc), ptr(enc_img if cfg.TI > 0 else None), ptr(mod),
+                                                       ptr(rope[0]), ptr(rope[1]), ptr(dout), ptr(dx), ptr(denc), ptr(ga), ptr(gb), ptr(saved), saved.numel(),
+                                                       ptr(scratch), scratch.numel(), stream_ptr()), "ftmi_wan_i2v_lora_block_backward")
+        else:
+            cfg, w, keep = _WanLoRABlockNativeFunction._args(blk, B, S, enc.shape[1], lora_a, lora_b, backward=True)
+            scratch = _native_scratch(x.device, lib.ftmi_wan_lora_block_scratch_bytes(ctypes.byref(cfg)))
+            check(lib.ftmi_wan_lora_block_backward(ctypes.byref(cfg), ctypes.byref(w), ptr(x), ptr(enc), ptr(mod), ptr(rope[0]), ptr(rope[1]), ptr(dout), ptr(dx),
+                                                   ptr(denc), ptr(ga), ptr(gb), ptr(saved), saved.numel(), ptr(scratch), scratch.numel(), stream_ptr()),
+                  "ftmi_wan_lora_block_backward")
         if own:
             blk._backward_done()
             ga = gb = None
-        return None, dx, denc, None, None, None, ga, gb
+        return dx, denc, ga, gb
+
+
+class _WanI2VLoRABlockNativeFunction(torch.autograd.Function):
+    """``_WanLoRABlockNativeFunction`` with the image context: ``ftmi_wan_i2v_lora_block_forward / _backward``."""
+
+    @staticmethod
+    def forward(ctx, blk: "MI355XWanBlock", x, enc, temb, rope_cos, rope_sin, lora_a, lora_b, enc_img):
+        return _WanLoRABlockNativeFunction._fwd(ctx, blk, x, enc, enc_img, temb, rope_cos, rope_sin, lora_a, lora_b)
+
+    @staticmethod
+    def backward(ctx, dout):
+        dx, denc, ga, gb = _WanLoRABlockNativeFunction._bwd(ctx, dout)
+        return None, dx, denc, None, None, None, ga, gb, None
 
 
 class MI355XWanBlock(nn.Module):
@@ -464,8 +564,11 @@ class MI355XWanBlock(nn.Module):
     # one C call per direction (csrc/wan_dit.hip); False (or FTMI_NATIVE_BLOCKS=0 in the environment): the per-kernel composition from Python -- the tests compare the two
     native = os.environ.get("FTMI_NATIVE_BLOCKS", "1") != "0"
 
-    def __init__(self, dim: int = 1536, heads: int = 12, ffn_dim: int = 8960, eps: float = 1e-6, device: Optional[torch.device] = None):
+    def __init__(self, dim: int = 1536, heads: int = 12, ffn_dim: int = 8960, eps: float = 1e-6, device: Optional[torch.device] = None,
+                 added_kv_proj_dim: Optional[int] = None):
         super().__init__()
+        if added_kv_proj_dim is not None and added_kv_proj_dim != dim:
+            raise ValueError("Wan image-to-video: added_kv_proj_dim is the block width (the image embedder projects to it)")
         if dim % heads != 0 or dim // heads != 128:
             raise ValueError("the Wan path uses the head_dim-128 attention kernels")
         self.dim, self.heads, self.head_dim, self.ffn_dim, self.eps = dim, heads, dim // heads, ffn_dim, eps
@@ -473,6 +576,10 @@ class MI355XWanBlock(nn.Module):
         dev = device or torch.device("cuda", 0)
         # gradients do not go through ``.grad`` (they are fp32, the parameters bf16): the block's backward writes ``grad_flat``
         self.flat = nn.Parameter(torch.zeros(self.layout.total, dtype=bf16, device=dev), requires_grad=False)
+        # image-to-video: attn2.add_k_proj / add_v_proj / norm_added_k in a flat buffer of their own (frozen; LoRA training only)
+        self.added_kv_proj_dim = added_kv_proj_dim
+        self.img_layout = WanImageLayout(dim) if added_kv_proj_dim is not None else None
+        self.img_flat = nn.Parameter(torch.zeros(self.img_layout.total, dtype=bf16, device=dev), requires_grad=False) if self.img_layout else None
         self.grad_flat: Optional[torch.Tensor] = None  # fp32, allocated by ``zero_grad_flat`` (the sharded trainer hands in its own buffer)
         self._transposed: Optional[Dict[str, torch.Tensor]] = None
         self._transposed_version = None
@@ -495,6 +602,12 @@ class MI355XWanBlock(nn.Module):
 
     def param(self, name: str) -> torch.Tensor:
         return self.layout.view(self._params(), name)
+
+    def _img_params(self) -> torch.Tensor:
+        return self.img_flat.data
+
+    def img_param(self, name: str) -> torch.Tensor:
+        return self.img_layout.view(self.img_flat.data, name)
 
     def grad(self, name: str) -> torch.Tensor:
         if self.grad_flat is None:
@@ -557,21 +670,36 @@ class MI355XWanBlock(nn.Module):
     @torch.no_grad()
     def load_diffusers_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
         """``sd``: a diffusers ``WanTransformerBlock`` state dict."""
-        missing = [n for n, _ in self.layout.entries if n not in sd]
+        img = self.img_layout.entries if self.img_layout else []
+        missing = [n for n, _ in self.layout.entries + img if n not in sd]
         if missing:
             raise KeyError(f"Wan block state dict lacks {missing[:4]}")
         for name, view in self.layout.named_views(self.flat.data).items():
             view.copy_(sd[name].to(bf16).reshape(view.shape))
+        if self.img_layout:
+            for name, view in self.img_layout.named_views(self.img_flat.data).items():
+                view.copy_(sd[name].to(bf16).reshape(view.shape))
         self.mark_updated()
 
     def state_dict_views(self) -> Dict[str, torch.Tensor]:
         if self.flat.numel() < self.layout.total:
             raise RuntimeError("this block's parameters are sharded over the ranks: use the step object's gathered_state_dict()")
-        return self.layout.named_views(self.flat.data)
+        out = self.layout.named_views(self.flat.data)
+        if self.img_layout:
+            out.update(self.img_layout.named_views(self.img_flat.data))
+        return out
 
-    def forward(self, hidden_states: torch.Tensor, encoder_hidden_states: torch.Tensor, temb: torch.Tensor, rotary) -> torch.Tensor:
+    def forward(self, hidden_states: torch.Tensor, encoder_hidden_states: torch.Tensor, temb: torch.Tensor, rotary, encoder_hidden_states_image=None) -> torch.Tensor:
         if self._pre_forward is not None:
             self._pre_forward(self)
+        if (encoder_hidden_states_image is not None) != (self.img_layout is not None):
+            raise ValueError("Wan block: the image context goes with added_kv_proj_dim, and only with it")
+        if self.img_layout is not None:
+            if not self.frozen:
+                raise NotImplementedError("Wan image-to-video: full fine-tuning is not covered; attach adapters (add_adapter) or freeze the base (freeze_base)")
+            fn = _WanI2VLoRABlockNativeFunction if self.native else _WanI2VLoRABlockFunction
+            return fn.apply(self, hidden_states.contiguous(), encoder_hidden_states.contiguous(), temb.contiguous(), rotary[0], rotary[1], self.lora_A, self.lora_B,
+                            encoder_hidden_states_image.detach().contiguous())
         if self.frozen:
             fn = _WanLoRABlockNativeFunction if self.native else _WanLoRABlockFunction
             return fn.apply(self, hidden_states.contiguous(), encoder_hidden_states.contiguous(), temb.contiguous(), rotary[0], rotary[1], self.lora_A, self.lora_B)

@@ -83,8 +83,11 @@ class RootLayout:
         pt, ph, pw = cfg.patch_size
         pk = cfg.in_channels * pt * ph * pw
         po = cfg.out_channels * pt * ph * pw
-        if pk % 64 != 0 or po % 64 != 0:
+        if po % 64 != 0 or (pk % 64 != 0 and cfg.image_dim is None):
             raise ValueError("patch embedding / output projection widths must be multiples of 64 for the GEMM")
+        # image-to-video: 36 input channels (16 noised | 4 mask | 16 conditioning latents) make 144 patch columns -- stored zero-padded to the GEMM's
+        # multiple of 64 (the tokens' columns are padded the same way; the state-dict view is the first ``patch_cols`` columns)
+        self.patch_cols, pk = pk, (pk + 63) // 64 * 64
         self.entries: List[Tuple[str, Tuple[int, ...]]] = [
             ("patch_embedding.weight", (D, pk)), ("patch_embedding.bias", (D,)),
             ("condition_embedder.time_embedder.linear_1.weight", (D, cfg.freq_dim)), ("condition_embedder.time_embedder.linear_1.bias", (D,)),
@@ -95,6 +98,10 @@ class RootLayout:
             ("scale_shift_table", (1, 2, D)),
             ("proj_out.weight", (po, D)), ("proj_out.bias", (po,)),
         ]
+        if cfg.image_dim is not None:  # WanImageEmbedding: FP32LayerNorm -> Linear -> GELU (erf) -> Linear -> FP32LayerNorm
+            Di, ie = cfg.image_dim, "condition_embedder.image_embedder."
+            self.entries += [(ie + "norm1.weight", (Di,)), (ie + "norm1.bias", (Di,)), (ie + "ff.net.0.proj.weight", (Di, Di)), (ie + "ff.net.0.proj.bias", (Di,)),
+                             (ie + "ff.net.2.weight", (D, Di)), (ie + "ff.net.2.bias", (D,)), (ie + "norm2.weight", (D,)), (ie + "norm2.bias", (D,))]
         self.offsets: Dict[str, Tuple[int, Tuple[int, ...]]] = {}
         off = 0
         for name, shape in self.entries:
@@ -107,7 +114,10 @@ class RootLayout:
         return flat[off:off + math.prod(shape)].view(shape)
 
     def named_views(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
-        return {n: self.view(flat, n) for n, _ in self.entries}
+        """{diffusers name: view}; the patch embedding without its padding columns."""
+        out = {n: self.view(flat, n) for n, _ in self.entries}
+        out["patch_embedding.weight"] = out["patch_embedding.weight"][:, :self.patch_cols]
+        return out
 
 
 class _LinearFunction(torch.autograd.Function):
@@ -187,14 +197,15 @@ class MI355XWanTransformer3DModel(nn.Module):
     def __init__(self, config: Optional[WanTransformerConfig] = None, device: Optional[torch.device] = None):
         super().__init__()
         self.config = c = config or WanTransformerConfig()
-        if c.attention_head_dim != 128 or c.image_dim is not None or c.qk_norm != "rms_norm_across_heads" or not c.cross_attn_norm:
-            raise ValueError("this path covers the T2V architecture: heads of 128, RMSNorm across heads, cross_attn_norm, no image branch")
+        if c.attention_head_dim != 128 or c.qk_norm != "rms_norm_across_heads" or not c.cross_attn_norm:
+            raise ValueError("this path covers the Wan2.1 architecture: heads of 128, RMSNorm across heads, cross_attn_norm")
         dev = device or torch.device("cuda", 0)
         self.root_layout = RootLayout(c)
         self.root = nn.Parameter(torch.zeros(self.root_layout.total, dtype=bf16, device=dev), requires_grad=False)
         self.root_grad: Optional[torch.Tensor] = None
         self._root_src: Optional[torch.Tensor] = None  # sharded training: the all-gathered root parameters
-        self.blocks = nn.ModuleList([MI355XWanBlock(c.inner_dim, c.num_attention_heads, c.ffn_dim, c.eps, dev) for _ in range(c.num_layers)])
+        self.blocks = nn.ModuleList([MI355XWanBlock(c.inner_dim, c.num_attention_heads, c.ffn_dim, c.eps, dev, added_kv_proj_dim=c.inner_dim if c.image_dim is not None else None)
+                                     for _ in range(c.num_layers)])
         self._rope_cache: Dict[Tuple[int, int, int], Tuple[torch.Tensor, torch.Tensor]] = {}
         self._anchor = torch.zeros(1, dtype=bf16, device=dev, requires_grad=True)  # tells autograd that the graph has trainable inputs
         self.lora_config: Optional[Dict[str, object]] = None  # set by add_adapter: {"r", "lora_alpha", "target_modules"}
@@ -317,7 +328,31 @@ class MI355XWanTransformer3DModel(nn.Module):
             blk.gradient_checkpointing = checkpointing_type == "full" or i % max(1, int(n_layer)) == 0
         return self
 
-    def _forward_frozen_root(self, hidden_states, timestep, encoder_hidden_states, return_dict: bool):
+    def _patch_columns(self, hidden_states: torch.Tensor) -> torch.Tensor:
+        """Conv3d(kernel = stride = patch) as a GEMM: the patch columns (c, pt, ph, pw) of every token in (f, h, w) order, zero-padded to the stored width."""
+        B, C, F_, H, W = hidden_states.shape
+        pt, ph, pw = self.config.patch_size
+        f, h, w = F_ // pt, H // ph, W // pw
+        cols = hidden_states.to(bf16).view(B, C, f, pt, h, ph, w, pw).permute(0, 2, 4, 6, 1, 3, 5, 7).reshape(B, f * h * w, C * pt * ph * pw)
+        pad = self.root_layout.offsets["patch_embedding.weight"][1][1] - cols.shape[-1]
+        return torch.nn.functional.pad(cols, (0, pad)) if pad else cols
+
+    @torch.no_grad()
+    def _embed_image(self, image_embeds: torch.Tensor) -> torch.Tensor:
+        """``condition_embedder.image_embedder`` on [B, TI, image_dim] (frozen; B x 257 rows once per step, plain torch ops at the reference's rounding
+        points): FP32LayerNorm -> Linear -> exact GELU -> Linear -> FP32LayerNorm."""
+        F_, ie = torch.nn.functional, "condition_embedder.image_embedder."
+        P = lambda n: self.rparam(ie + n)
+        x = image_embeds.to(self.device, bf16)
+        if x.dim() != 3 or x.shape[-1] != self.config.image_dim:
+            raise ValueError(f"encoder_hidden_states_image must be [B, tokens, {self.config.image_dim}]")
+        if x.shape[1] > 320:
+            raise NotImplementedError("the image context holds at most 320 tokens (257 CLIP tokens; the first/last-frame form is not covered)")
+        ln = lambda t, n: F_.layer_norm(t.float(), (t.shape[-1],), P(n + ".weight").float(), P(n + ".bias").float(), 1e-5).to(bf16)
+        x = F_.gelu(F_.linear(ln(x, "norm1"), P("ff.net.0.proj.weight"), P("ff.net.0.proj.bias")))
+        return ln(F_.linear(x, P("ff.net.2.weight"), P("ff.net.2.bias")), "norm2").contiguous()
+
+    def _forward_frozen_root(self, hidden_states, timestep, encoder_hidden_states, return_dict: bool, encoder_hidden_states_image=None):
         """The forward with adapters attached: patch embedding, condition embedder and head run FROZEN (plain launches of the same GEMMs: same bits as the
         full fine-tune's forward); the only graph autograd sees is blocks -> output norm -> output projection, which hands d x back to the last block."""
         c = self.config
@@ -329,8 +364,7 @@ class MI355XWanTransformer3DModel(nn.Module):
         lin = lambda t, name, **kw: ops.gemm_nt(t.reshape(-1, t.shape[-1]), self.rparam(f"{name}.weight"), self.rparam(f"{name}.bias"), **kw)
         silu = torch.nn.functional.silu
         with torch.no_grad():
-            cols = hidden_states.to(bf16).view(B, C, f, pt, h, ph, w, pw).permute(0, 2, 4, 6, 1, 3, 5, 7).reshape(B, S, C * pt * ph * pw)
-            x = lin(cols, "patch_embedding").view(B, S, -1)
+            x = lin(self._patch_columns(hidden_states), "patch_embedding").view(B, S, -1)
             t_emb = timestep_embedding(timestep.to(self.device), c.freq_dim).to(bf16)
             temb = lin(silu(lin(t_emb, "condition_embedder.time_embedder.linear_1")), "condition_embedder.time_embedder.linear_2")
             tproj = lin(silu(temb), "condition_embedder.time_proj").unflatten(1, (6, -1))
@@ -339,8 +373,9 @@ class MI355XWanTransformer3DModel(nn.Module):
             enc = lin(act, "condition_embedder.text_embedder.linear_2").view(B, text.shape[1], -1)
             mod = self.rparam("scale_shift_table") + temb.unsqueeze(1)  # [B, 2, D] bf16
             shift, scale = mod[:, 0].float(), (1 + mod[:, 1]).float() - 1
+            enc_img = None if encoder_hidden_states_image is None else self._embed_image(encoder_hidden_states_image)
         for blk in self.blocks:
-            x = blk(x, enc, tproj, rope)
+            x = blk(x, enc, tproj, rope, enc_img)
         y = _LnModFunction.apply(x, shift, scale, c.eps)
         if self._proj_out_t is None:
             self._proj_out_t = ops.transpose_bf16(self.rparam("proj_out.weight"))
@@ -362,19 +397,22 @@ class MI355XWanTransformer3DModel(nn.Module):
         return _LinearFunction.apply(x, w, b, self.rgrad(f"{name}.weight"), self.rgrad(f"{name}.bias"), gelu, need_dx, self._anchor)
 
     def forward(self, hidden_states, timestep, encoder_hidden_states, encoder_hidden_states_image=None, return_dict: bool = False, **kwargs):
-        if encoder_hidden_states_image is not None:
-            raise NotImplementedError("the image-to-video branch is not part of this path")
-        if self.lora_config is not None:
-            return self._forward_frozen_root(hidden_states, timestep, encoder_hidden_states, return_dict)
         c = self.config
+        if (encoder_hidden_states_image is not None) != (c.image_dim is not None):
+            raise NotImplementedError("encoder_hidden_states_image goes with an image-to-video model (config.image_dim), and such a model needs it")
+        if hidden_states.shape[1] != c.in_channels:
+            raise ValueError(f"hidden_states has {hidden_states.shape[1]} channels, the model takes {c.in_channels}")
+        if self.lora_config is not None:
+            return self._forward_frozen_root(hidden_states, timestep, encoder_hidden_states, return_dict, encoder_hidden_states_image)
+        if c.image_dim is not None:
+            raise NotImplementedError("Wan image-to-video: full fine-tuning is not covered by this backend; attach adapters first (add_adapter: LoRA training)")
         B, C, F_, H, W = hidden_states.shape
         pt, ph, pw = c.patch_size
         f, h, w = F_ // pt, H // ph, W // pw
         D, S = c.inner_dim, f * h * w
         rope = self._rope(F_, H, W)
         # Conv3d(kernel = stride = patch) as a GEMM over the patch columns (c, pt, ph, pw), tokens in (f, h, w) order
-        cols = hidden_states.to(bf16).view(B, C, f, pt, h, ph, w, pw).permute(0, 2, 4, 6, 1, 3, 5, 7).reshape(B, S, C * pt * ph * pw)
-        x = self._linear(cols, "patch_embedding", need_dx=False)
+        x = self._linear(self._patch_columns(hidden_states), "patch_embedding", need_dx=False)
         # condition embedder, the reference's patched forward (patches/models/wan/patch.py:17-33): the sinusoid takes the text dtype
         t_emb = timestep_embedding(timestep.to(self.device), c.freq_dim).to(bf16)
         temb = self._linear(torch.nn.functional.silu(self._linear(t_emb, "condition_embedder.time_embedder.linear_1", need_dx=False)),

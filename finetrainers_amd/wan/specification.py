@@ -48,10 +48,30 @@ class MI355XWanSpecOps:
         noisy = ((1.0 - s) * latents + s * noise).to(latents)  # functional/diffusion.py:4-6 (fp32 sigmas promote the mix; one cast back)
         return noisy, noise - latents, (sigmas.flatten() * 1000.0).long()
 
+    def image_condition(self, noisy: torch.Tensor, latent_condition: torch.Tensor, latent_condition_mask: torch.Tensor, latents_mean: torch.Tensor,
+                        latents_std: torch.Tensor) -> torch.Tensor:
+        """Image-to-video input (base_specification.py:465-481): the reference normalises both halves of the conditioning latents' stored moments and takes
+        the posterior's MODE, which is the normalised mean -- the log-variance half drops out; the model's input is [noisy | mask | condition] on the
+        channel axis."""
+        mu = torch.chunk(latent_condition.to(noisy), 2, dim=1)[0]
+        return torch.cat([noisy, latent_condition_mask.to(noisy), self.normalize_latents(mu, latents_mean, latents_std)], dim=1)
+
     def forward(self, transformer: Callable, moments: torch.Tensor, encoder_hidden_states: torch.Tensor, sigmas: torch.Tensor, latents_mean: torch.Tensor,
-                latents_std: torch.Tensor, posterior_noise=None, noise=None, generator=None):
+                latents_std: torch.Tensor, posterior_noise=None, noise=None, generator=None, latent_condition=None, latent_condition_mask=None,
+                encoder_hidden_states_image=None):
         noisy, target, timesteps = self.noise_and_target(moments, latents_mean, latents_std, sigmas, posterior_noise, noise, generator)
-        pred = transformer(hidden_states=noisy, timestep=timesteps, encoder_hidden_states=encoder_hidden_states, return_dict=False)[0]
+        extra = {}
+        # the reference keys the concatenation on the model's config (image_dim, :480); a callable without a config is judged by what it is handed
+        cfg = getattr(transformer, "config", None)
+        i2v = getattr(cfg, "image_dim", None) is not None if cfg is not None else (latent_condition is not None or encoder_hidden_states_image is not None)
+        if not i2v and (latent_condition is not None or encoder_hidden_states_image is not None):
+            raise ValueError("latent_condition / encoder_hidden_states_image were handed to a text-to-video model (its config has no image_dim)")
+        if i2v:  # all three inputs go together
+            if latent_condition is None or latent_condition_mask is None or encoder_hidden_states_image is None:
+                raise ValueError("image-to-video needs latent_condition, latent_condition_mask and encoder_hidden_states_image together")
+            noisy = self.image_condition(noisy, latent_condition, latent_condition_mask, latents_mean, latents_std)
+            extra["encoder_hidden_states_image"] = encoder_hidden_states_image
+        pred = transformer(hidden_states=noisy, timestep=timesteps, encoder_hidden_states=encoder_hidden_states, return_dict=False, **extra)[0]
         return pred, target, sigmas
 
     def loss_backward(self, pred: torch.Tensor, target: torch.Tensor, grad_scale: float = 1.0) -> torch.Tensor:
@@ -67,7 +87,7 @@ IGNORE_KEYS_FOR_COLLATION = {"height", "width", "num_frames", "frame_rate", "rop
 
 
 class MI355XWanModelSpecification(MI355XWanSpecOps):
-    """Mirror of ``WanModelSpecification`` (finetrainers/models/wan/base_specification.py:210-577) for the SFT hot path (T2V): same constructor keywords,
+    """Mirror of ``WanModelSpecification`` (finetrainers/models/wan/base_specification.py:210-577) for the SFT hot path (T2V, and I2V LoRA): same constructor keywords,
     ``_resolution_dim_keys``, ``load_diffusion_models``, ``collate_*`` (``latents_mean`` / ``latents_std`` pass through uncollated, modeling_utils.py:22),
     ``forward`` with the reference's signature, ``_save_model`` writing a diffusers transformer directory.  Text encoder, VAE, pipeline and validation stay
     with the reference."""
@@ -130,12 +150,13 @@ class MI355XWanModelSpecification(MI355XWanSpecOps):
                 noise: Optional[torch.Tensor] = None, posterior_noise: Optional[torch.Tensor] = None, **kwargs):
         """base_specification.py:433-493 -> (pred, target, sigmas).  ``compute_posterior`` is accepted and ignored exactly like the reference does (:446):
         "latents" are always the stored moments [B, 2C, F, H, W], with "latents_mean" / "latents_std" (= 1 / std) next to them."""
-        if latent_model_conditions.get("latent_condition") is not None or condition_model_conditions.get("encoder_hidden_states_image") is not None:
-            raise NotImplementedError("the image-to-video conditioning is not part of this path")
         latents = latent_model_conditions.pop("latents")
         mean, std = latent_model_conditions.pop("latents_mean"), latent_model_conditions.pop("latents_std")
         return MI355XWanSpecOps.forward(self, transformer, latents, condition_model_conditions["encoder_hidden_states"], sigmas, mean, std,
-                                        posterior_noise=posterior_noise, noise=noise, generator=generator)
+                                        posterior_noise=posterior_noise, noise=noise, generator=generator,
+                                        latent_condition=latent_model_conditions.pop("latent_condition", None),
+                                        latent_condition_mask=latent_model_conditions.pop("latent_condition_mask", None),
+                                        encoder_hidden_states_image=condition_model_conditions.get("encoder_hidden_states_image"))
 
     def _save_model(self, directory: str, transformer, transformer_state_dict: Optional[Dict[str, torch.Tensor]] = None, scheduler=None) -> None:
         """base_specification.py:554-568: ``<directory>/transformer`` = config.json + diffusion_pytorch_model.safetensors with the diffusers parameter

@@ -252,9 +252,10 @@ class MI355XWanLoRAStep:
 
     # ---- the step ---------------------------------------------------------------------------------------------------------------------------------
     def step(self, moments: torch.Tensor, encoder_hidden_states: torch.Tensor, latents_mean: torch.Tensor, latents_std: torch.Tensor,
-             sigmas: torch.Tensor, posterior_noise: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+             sigmas: torch.Tensor, posterior_noise: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, **image_conditioning) -> Dict[str, torch.Tensor]:
+        """``image_conditioning`` (an image-to-video model): latent_condition, latent_condition_mask, encoder_hidden_states_image, handed to the specification."""
         pred, target, _ = self.spec.forward(self.transformer, moments, encoder_hidden_states, sigmas, latents_mean, latents_std, posterior_noise=posterior_noise,
-                                            noise=noise, generator=self.generator)
+                                            noise=noise, generator=self.generator, **image_conditioning)
         gas = self.gradient_accumulation_steps
         if self._micro_step % gas == 0:
             self.gflat.zero_()  # a new accumulation window

@@ -87,6 +87,17 @@ int ftmi_attn_bwd(const ftmi_attn_desc* desc, const void* q, const void* k, cons
                   const float* lse, const void* dout, void* dq, void* dk, void* dv, float* delta_ws,
                   const float* key_bias, ftmi_stream stream);
 
+/* Second context of a cross-attention with two key/value sets (Wan image-to-video: the CLIP image tokens next to the text tokens; two independent
+ * softmaxes whose bf16 outputs are summed).  desc.d = 128, 1 <= desc.Sk <= 320, no key bias.  Run AFTER the first context's ftmi_attn_fwd / ftmi_attn_bwd:
+ *   fwd: out = bf16(float(out_first) + float(bf16(softmax(q k^T scale) v))), lse [B,H,Sq] of THIS context written; out_first has desc.o_strides
+ *   dq:  dq  = bf16(float(dq_first)  + float(bf16(dq of this context))); reads lse and dout; dq_first has desc.dq_strides and may be dq itself
+ * rowsum(dO * O) of this context is formed inside the dq kernel (no output of this context alone is kept).  There is no dK / dV: the only caller's image
+ * keys and values are frozen.  Keys past Sk are never read. */
+int ftmi_attn_ctx2_fwd(const ftmi_attn_desc* desc, const void* q, const void* k, const void* v, const void* out_first, void* out, float* lse,
+                       ftmi_stream stream);
+int ftmi_attn_ctx2_dq(const ftmi_attn_desc* desc, const void* q, const void* k, const void* v, const float* lse, const void* dout, const void* dq_first,
+                      void* dq, ftmi_stream stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Linear (+ LoRA) building block:  y = bf16( bf16(x W^T + b) + lora_scale * (x A^T) B^T ), the LoRA branch at fp32-equivalent
  * precision (peft lora.Linear with fp32 adapter weights).  a_sp [2r,K] and b_ext [N,3r] are working copies of the fp32 A [r,K] and
@@ -650,7 +661,7 @@ int ftmi_wan_colsum(const ftmi_wan_row_args* args, ftmi_stream stream);
  * backward only) may be shared by all blocks of a stream.  dmod fp32 [6, B, D] is ADDED to (per-sample column sums of d shift / d scale / d gate). */
 typedef struct {
     int B, S, T;      /* batch, video tokens, text tokens */
-    int D, H, F;      /* width = H x 128, feed-forward width */
+    int D, H, F;      /* width = H x 128 <= 5120, feed-forward width */
     float eps;        /* 1e-6 */
     int gemm_variant; /* 8 */
 } ftmi_wan_block_config;
@@ -695,6 +706,32 @@ int ftmi_wan_lora_block_forward(const ftmi_wan_lora_block_config* cfg, const ftm
 int ftmi_wan_lora_block_backward(const ftmi_wan_lora_block_config* cfg, const ftmi_wan_lora_block_weights* w, const void* x, const void* enc, const float* mod,
                                  const float* rope_cos, const float* rope_sin, const void* dout, void* dx, void* denc, float* grad_a, float* grad_b, void* saved,
                                  size_t saved_bytes, void* scratch, size_t scratch_bytes, ftmi_stream stream);
+
+/* The LoRA block of a Wan image-to-video model (Wan2.1-I2V: attn2 has added_kv_proj_dim): the same walk with the image context in the cross-attention,
+ *   o2 = bf(SDPA(q2, k_text, v_text)) + bf(SDPA(q2, k_img, v_img)),  k_img = norm_added_k(add_k_proj(enc_img)),  v_img = add_v_proj(enc_img).
+ * The configuration is ftmi_wan_lora_block_config plus TI, the number of image tokens (257); enc_img [B, TI, D] bf16 is the image embedder's output.
+ * img_params: a SEPARATE flat bf16 buffer (the block's own flat buffer keeps its layout): add_k_proj | add_v_proj weight [2D, D], their biases [2D],
+ * norm_added_k weight [D].  No adapter sits on them (the recipe's regex does not match), so the backward adds only the image branch's dQ: no gradient to
+ * enc_img or to img_params.  `saved` grows by the projected image rows [B TI, 3D], lse of the image branch and the summed attention output [B, S, D].
+ * TI = 0 (img_params / enc_img may then be NULL): the launches and bits of ftmi_wan_lora_block_forward / _backward. */
+typedef struct {
+    int B, S, T;      /* batch, video tokens, text tokens */
+    int D, H, F;      /* width = H x 128 <= 5120, feed-forward width */
+    float eps;        /* 1e-6 */
+    int gemm_variant; /* 8 */
+    int r;            /* LoRA rank: 0, 64 or 128 (other ranks zero-padded by the caller) */
+    float lora_scale; /* alpha / (the user's) r */
+    int TI;           /* image tokens, 0 .. 320 */
+} ftmi_wan_i2v_lora_block_config;
+size_t ftmi_wan_i2v_lora_block_saved_bytes(const ftmi_wan_i2v_lora_block_config* cfg);
+size_t ftmi_wan_i2v_lora_block_scratch_bytes(const ftmi_wan_i2v_lora_block_config* cfg);
+int ftmi_wan_i2v_lora_block_forward(const ftmi_wan_i2v_lora_block_config* cfg, const ftmi_wan_lora_block_weights* w, const void* img_params, const void* x,
+                                    const void* enc, const void* enc_img, const float* mod, const float* rope_cos, const float* rope_sin, void* out, void* saved,
+                                    size_t saved_bytes, void* scratch, size_t scratch_bytes, ftmi_stream stream);
+int ftmi_wan_i2v_lora_block_backward(const ftmi_wan_i2v_lora_block_config* cfg, const ftmi_wan_lora_block_weights* w, const void* img_params, const void* x,
+                                     const void* enc, const void* enc_img, const float* mod, const float* rope_cos, const float* rope_sin, const void* dout,
+                                     void* dx, void* denc, float* grad_a, float* grad_b, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
+                                     ftmi_stream stream);
 
 /* Sum of squares of a flat fp32 gradient (shard): scratch[0] <- sum g^2 (order-fixed; scratch >= FTMI_CLIP_SCRATCH_FLOATS floats).  Sharded training
  * all-reduces scratch[0] over the ranks before the optimiser call below (the reference's clip_grad_norm_ over DTensor shards, utils/torch.py:99-161). */

@@ -233,6 +233,65 @@ def build_wan_lora(args, par, dev) -> Dict[str, Any]:
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------------
+# Wan2.1-I2V-14B-480P LoRA (examples/training/sft/wan_i2v/3dgs_dissolve/train.sh): the same adapters on the image-to-video model -- width 5120,
+# 40 x 128 heads, feed-forward 13824, 40 blocks, 36 input channels, 257 CLIP image tokens in every block's attn2; the recipe's 49 x 480 x 832 bucket
+# (20 280 video + 512 text tokens), gradient checkpointing as in the recipe.  --layers N runs fewer blocks; the row states how many ran.
+# ------------------------------------------------------------------------------------------------------------------------------------------
+def build_wan_i2v_lora(args, par, dev) -> Dict[str, Any]:
+    from finetrainers_amd.wan import MI355XWanLoRAStep, MI355XWanTransformer3DModel, WanTransformerConfig
+
+    layers = args.layers if args.layers > 0 else 40
+    cfg = WanTransformerConfig(num_layers=layers, num_attention_heads=40, ffn_dim=13824, in_channels=36, image_dim=1280)
+    model = MI355XWanTransformer3DModel(cfg, device=dev)
+    g = torch.Generator(device=dev).manual_seed(0)
+    D = cfg.inner_dim
+    with torch.no_grad():
+        for name, v in model.state_dict_views().items():
+            if name.endswith("weight") and v.dim() >= 2:
+                v.copy_((torch.randn(v.shape, generator=g, device=dev) / v.shape[-1] ** 0.5).to(bf16))
+            elif "norm" in name and name.endswith("weight"):
+                v.fill_(1.0)
+            elif "scale_shift_table" in name:
+                v.copy_((torch.randn(v.shape, generator=g, device=dev) / D ** 0.5).to(bf16))
+            else:
+                v.copy_((0.02 * torch.randn(v.shape, generator=g, device=dev)).to(bf16))
+    for blk in model.blocks:
+        blk.mark_updated()
+    model.add_adapter(args.rank, float(args.rank))
+    model.apply_activation_checkpointing("full")
+    with torch.no_grad():
+        for p in model.lora_parameters()[1::2]:
+            p[:, :, :args.rank].normal_(0, 0.01, generator=g)
+    step = MI355XWanLoRAStep(model, lr=1e-4, generator=torch.Generator(device=dev).manual_seed(1 + par.rank), parallel=par if par.world_size > 1 else None)
+    g.manual_seed(100 + par.rank)
+    B, C, F_, H, W, T, TI = 1, 16, 13, 60, 104, 512, 257
+    mom = lambda: torch.cat([torch.randn((B, C, F_, H, W), generator=g, device=dev), 0.3 * torch.randn((B, C, F_, H, W), generator=g, device=dev) - 2.0], dim=1).to(bf16)
+    moments, cond = mom(), mom()
+    mask = torch.zeros((B, 4, F_, H, W), dtype=bf16, device=dev)
+    mask[:, :, 0] = 1  # the first frame is the conditioning image
+    text = torch.randn((B, T, cfg.text_dim), generator=g, device=dev).to(bf16)
+    image = torch.randn((B, TI, cfg.image_dim), generator=g, device=dev).to(bf16)
+    mean, std = torch.zeros(C, device=dev), torch.ones(C, device=dev)
+    sig = torch.tensor([0.6], device=dev)
+    S, Fd = 13 * 30 * 52, cfg.ffn_dim
+    lin = 2.0 * S * (6 * D * D + 2 * D * Fd) + 2.0 * (T + TI) * 2 * D * D
+    att = 4.0 * S * S * D + 4.0 * S * (T + TI) * D
+    flop = layers * (3.0 * lin + 4.5 * att)  # checkpointing: forward twice + input gradients (the image branch's backward is dQ only: counted slightly high)
+    return {
+        "one_step": lambda: step.step(moments, text, mean, std, sig, latent_condition=cond, latent_condition_mask=mask, encoder_hidden_states_image=image),
+        "samples_per_step": 1,
+        "step_tflop": flop / 1e12,
+        "metric": "train samples/sec (+ step ms) Wan-I2V-14B LoRA 49x480x832 (the reference's wan_i2v SFT recipe)",
+        "data": "synthetic posterior moments [1,32,13,60,104] + conditioning moments + first-frame mask + random text [1,512,4096] and image [1,257,1280] embeds, random-init weights",
+        "config": {"workload": f"Wan-I2V-14B LoRA rank={args.rank} bf16 SFT step over the frozen base, 49x480x832 clip ({S} video + {T} text + {TI} image tokens), batch 1 per GPU, "
+                               f"{layers} blocks" + ("" if layers == 40 else " -- REDUCED depth"),
+                   "model": "Wan2.1-I2V-14B DiT geometry: width 5120, 40 x 128 heads, feed-forward 13824, frozen; 8 fp32 adapters per block", "seq_len": S,
+                   "activation_checkpointing": True, "orchestration": ("one C call per block and direction (ftmi_wan_i2v_lora_block_forward / _backward)" if os.environ.get("FTMI_NATIVE_BLOCKS", "1") != "0" else "python, per kernel over the C ABI")},
+        "layers": layers,
+    }
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------------
 # HunyuanVideo LoRA, fp8 weight storage (configs[4]): 61 x 544 x 960 -> latents [1, 16, 16, 68, 120], 32 640 video + 256 text tokens,
 # 20 dual-stream + 40 single-stream blocks (12.8 B parameters), batch 1 per GPU
 # ------------------------------------------------------------------------------------------------------------------------------------------
@@ -339,6 +398,7 @@ def cpu_baseline_hunyuan(args, ctx) -> Dict[str, Any]:
 WORKLOADS = {"cogvideox": (build_cogvideox, lambda a, c: cpu_baseline_cogvideox(a, c["layers"])),
              "wan": (build_wan, lambda a, c: cpu_baseline_wan(a, c["layers"])),
              "wan_lora": (build_wan_lora, lambda a, c: cpu_baseline_wan(a, c["layers"])),  # (yardstick on the host: the full fine-tune block, an upper bound of the LoRA block's work)
+             "wan_i2v_lora": (build_wan_i2v_lora, None),  # (no host yardstick: this row runs through this file's own command line only)
              "hunyuan": (build_hunyuan, cpu_baseline_hunyuan)}
 
 
