@@ -17,6 +17,7 @@
 
 #include "common.hip.h"
 #include "kernels.h"
+#include "lora_proj.hip.h"
 
 namespace ftmi {
 
@@ -78,17 +79,6 @@ int check_cfg(const ftmi_cog_config& c) {
     return 0;
 }
 
-inline const bf16_t* P(const void* base, size_t elem_off) { return reinterpret_cast<const bf16_t*>(base) + elem_off; }
-
-// fp32-equivalent LoRA down-projection (see ltx_dit.hip lora_down): out [M, 3 nout] = (hi | lo | hi) planes of alpha * X . Wf^T
-int lora_down(const bf16_t* X, long ldx, int M, const bf16_t* w_sp, int nout, int K, int r, float alpha, bf16_t* out, hipStream_t st, int xk_grp_stride = 0) {
-    GemmNtArgs a;
-    a.X = X; a.ldx = ldx; a.W = w_sp; a.ldw = K; a.M = M; a.N = 2 * nout; a.K = K; a.alpha = alpha;
-    if (xk_grp_stride > 0) { a.xk_grp_n = 2 * r; a.xk_grp_stride = xk_grp_stride; }
-    a.split_r = r; a.out = out; a.ldo = 3L * nout; a.variant = 8;
-    return gemm_nt(a, st);
-}
-
 struct Tables {  // the six modulation tables of one block, each [B][2][D]
     const bf16_t *shift1, *onep1, *gate1, *shift2, *onep2, *gate2;
 };
@@ -117,10 +107,16 @@ AttnArgs attn_args(const ftmi_cog_config& c) {
     a.B = c.B; a.H = c.H; a.Sq = a.Sk = c.T + c.S; a.scale = 0.125f; a.d = 64;
     return a;
 }
-inline void set3(long& sb, long& sh, long& ss, long rows_per_batch, long ld) {
-    sb = rows_per_batch * ld;
-    sh = 64;
-    ss = ld;
+// q, k, o: token rows [B N, D]; v: the last D columns of the fused projection qkv [B N, 3D]
+AttnArgs attn_args(const ftmi_cog_config& c, const bf16_t* q, const bf16_t* k, const bf16_t* qkv, bf16_t* o, float* lse) {
+    AttnArgs a = attn_args(c);
+    const long N = c.T + c.S, D = c.D;
+    a.q = q; tok_strides(a.q_sb, a.q_sh, a.q_ss, N, D, 64);
+    a.k = k; tok_strides(a.k_sb, a.k_sh, a.k_ss, N, D, 64);
+    a.v = qkv + 2 * D; tok_strides(a.v_sb, a.v_sh, a.v_ss, N, 3 * D, 64);
+    a.o = o; tok_strides(a.o_sb, a.o_sh, a.o_ss, N, D, 64);
+    a.lse2 = lse;
+    return a;
 }
 
 }  // namespace
@@ -138,10 +134,8 @@ int cog_blocks_forward(const ftmi_cog_config& c, const ftmi_cog_weights& w, cons
 
     // modulation of every LayerNorm-zero of every block: one GEMM over the stacked [L, 2, 6D, D_temb] weights, one table-building pass
     {
-        GemmNtArgs a;
-        a.X = temb_silu; a.ldx = c.D_temb; a.W = P(w.mod_w, 0); a.ldw = c.D_temb; a.M = c.B; a.N = c.L * 2 * 6 * D; a.K = c.D_temb;
-        a.bias = P(w.mod_b, 0); a.out = W(ws, L.mod_raw); a.ldo = (long)c.L * 2 * 6 * D; a.variant = V;
-        FTMI_TRY(gemm_nt(a, st));
+        const int nmod = c.L * 2 * 6 * D;
+        FTMI_TRY(gemm_nt(linear_args(temb_silu, c.D_temb, c.B, P(w.mod_w, 0), c.D_temb, nmod, c.D_temb, P(w.mod_b, 0), W(ws, L.mod_raw), nmod, V), st));
         FTMI_TRY(cog_mod_tables(W(ws, L.mod_raw), W(ws, L.tables), c.L * 2, c.B, D, st));
     }
 
@@ -161,12 +155,10 @@ int cog_blocks_forward(const ftmi_cog_config& c, const ftmi_cog_weights& w, cons
             FTMI_TRY(cog_ln_mod_fwd(a, st));
         }
         {  // fused q|k|v projection (+ LoRA)
-            GemmNtArgs a;
-            a.X = n1; a.ldx = D; a.W = P(w.w_qkv, (size_t)l * 3 * D2); a.ldw = D; a.M = M; a.N = 3 * D; a.K = D;
-            a.bias = P(w.b_qkv, (size_t)l * 3 * D); a.out = qkv; a.ldo = 3 * D; a.variant = V;
+            GemmNtArgs a = linear_args(n1, D, M, P(w.w_qkv, (size_t)l * 3 * D2), D, 3 * D, D, P(w.b_qkv, (size_t)l * 3 * D), qkv, 3 * D, V);
             if (r > 0) {
-                FTMI_TRY(lora_down(n1, D, M, la, 3 * r, D, r, s, W(blk, L.xa_qkv), st));
-                a.X2 = W(blk, L.xa_qkv); a.ldx2 = 9 * r; a.W2 = lb; a.ldw2 = 3 * r; a.K2 = 3 * r; a.x2_grp_n = D; a.x2_grp_stride = 3 * r;
+                FTMI_TRY(gemm_nt(lora_down_args(n1, D, M, la, 3, D, r, s, W(blk, L.xa_qkv)), st));
+                lora_ext_fwd(a, W(blk, L.xa_qkv), 3, r, lb);
             }
             FTMI_TRY(gemm_nt(a, st));
         }
@@ -178,21 +170,13 @@ int cog_blocks_forward(const ftmi_cog_config& c, const ftmi_cog_weights& w, cons
             FTMI_TRY(cog_head_ln_fwd(a, st));
         }
         {  // joint attention
-            AttnArgs a = attn_args(c);
-            a.q = W(blk, L.qn); set3(a.q_sb, a.q_sh, a.q_ss, N, D);
-            a.k = W(blk, L.kn); set3(a.k_sb, a.k_sh, a.k_ss, N, D);
-            a.v = qkv + 2 * D;  set3(a.v_sb, a.v_sh, a.v_ss, N, 3 * D);
-            a.o = W(blk, L.o);  set3(a.o_sb, a.o_sh, a.o_ss, N, D);
-            a.lse2 = WF(blk, L.lse);
-            FTMI_TRY(attn_fwd(a, st));
+            FTMI_TRY(attn_fwd(attn_args(c, W(blk, L.qn), W(blk, L.kn), qkv, W(blk, L.o), WF(blk, L.lse)), st));
         }
         {  // to_out (+ LoRA), gated residual
-            GemmNtArgs a;
-            a.X = W(blk, L.o); a.ldx = D; a.W = P(w.w_o, (size_t)l * D2); a.ldw = D; a.M = M; a.N = D; a.K = D;
-            a.bias = P(w.b_o, (size_t)l * D); a.out = W(ws, L.s_f); a.ldo = D; a.variant = V;
+            GemmNtArgs a = linear_args(W(blk, L.o), D, M, P(w.w_o, (size_t)l * D2), D, D, D, P(w.b_o, (size_t)l * D), W(ws, L.s_f), D, V);
             if (r > 0) {
-                FTMI_TRY(lora_down(W(blk, L.o), D, M, la + 3L * 2 * r * D, r, D, r, s, W(blk, L.xa_o), st));
-                a.X2 = W(blk, L.xa_o); a.ldx2 = 3 * r; a.W2 = lb + 3L * D * 3 * r; a.ldw2 = 3 * r; a.K2 = 3 * r;
+                FTMI_TRY(gemm_nt(lora_down_args(W(blk, L.o), D, M, la + 3L * 2 * r * D, 1, D, r, s, W(blk, L.xa_o)), st));
+                lora_ext_fwd(a, W(blk, L.xa_o), 1, r, lb + 3L * D * 3 * r);
             }
             FTMI_TRY(gemm_nt(a, st));
             FTMI_TRY(gate_res(c, h0, W(ws, L.s_f), t.gate1, W(blk, L.h1), st));
@@ -201,15 +185,10 @@ int cog_blocks_forward(const ftmi_cog_config& c, const ftmi_cog_weights& w, cons
             CogLnArgs a = ln_args(c, W(blk, L.h1), 1, l, w);
             a.shift = t.shift2; a.onep = t.onep2; a.y = W(blk, L.n2);
             FTMI_TRY(cog_ln_mod_fwd(a, st));
-            GemmNtArgs f1;
-            f1.X = W(blk, L.n2); f1.ldx = D; f1.W = P(w.w_ff1, (size_t)l * c.D_ff * D); f1.ldw = D; f1.M = M; f1.N = c.D_ff; f1.K = D;
-            f1.bias = P(w.b_ff1, (size_t)l * c.D_ff); f1.out = W(ws, L.s_act); f1.ldo = c.D_ff; f1.out2 = W(blk, L.z); f1.ldo2 = c.D_ff;
-            f1.epi = EPI_GELU; f1.variant = V;
+            GemmNtArgs f1 = linear_args(W(blk, L.n2), D, M, P(w.w_ff1, (size_t)l * c.D_ff * D), D, c.D_ff, D, P(w.b_ff1, (size_t)l * c.D_ff), W(ws, L.s_act), c.D_ff, V);
+            f1.out2 = W(blk, L.z); f1.ldo2 = c.D_ff; f1.epi = EPI_GELU;
             FTMI_TRY(gemm_nt(f1, st));
-            GemmNtArgs f2;
-            f2.X = W(ws, L.s_act); f2.ldx = c.D_ff; f2.W = P(w.w_ff2, (size_t)l * D * c.D_ff); f2.ldw = c.D_ff; f2.M = M; f2.N = D; f2.K = c.D_ff;
-            f2.bias = P(w.b_ff2, (size_t)l * D); f2.out = W(ws, L.s_f); f2.ldo = D; f2.variant = V;
-            FTMI_TRY(gemm_nt(f2, st));
+            FTMI_TRY(gemm_nt(linear_args(W(ws, L.s_act), c.D_ff, M, P(w.w_ff2, (size_t)l * D * c.D_ff), c.D_ff, D, c.D_ff, P(w.b_ff2, (size_t)l * D), W(ws, L.s_f), D, V), st));
             FTMI_TRY(gate_res(c, W(blk, L.h1), W(ws, L.s_f), t.gate2, hout, st));
         }
     }
@@ -252,39 +231,29 @@ int cog_blocks_backward(const ftmi_cog_config& c, const ftmi_cog_weights& w, con
         // ---- feed-forward branch ----
         FTMI_TRY(gate_res(c, nullptr, dout, t.gate2, d1, st));  // d f = gate_ff * d out
         {
-            GemmNtArgs a;
-            a.X = d1; a.ldx = D; a.W = P(w.w_ff2_t, (size_t)l * c.D_ff * D); a.ldw = D; a.M = M; a.N = c.D_ff; a.K = D;
-            a.out = W(ws, L.s_big); a.ldo = c.D_ff; a.epi = EPI_DGELU; a.aux = W(blk, L.z); a.ldaux = c.D_ff; a.variant = V;
+            GemmNtArgs a = linear_args(d1, D, M, P(w.w_ff2_t, (size_t)l * c.D_ff * D), D, c.D_ff, D, nullptr, W(ws, L.s_big), c.D_ff, V);
+            a.epi = EPI_DGELU; a.aux = W(blk, L.z); a.ldaux = c.D_ff;
             FTMI_TRY(gemm_nt(a, st));
-            GemmNtArgs b;
-            b.X = W(ws, L.s_big); b.ldx = c.D_ff; b.W = P(w.w_ff1_t, (size_t)l * D * c.D_ff); b.ldw = c.D_ff; b.M = M; b.N = D; b.K = c.D_ff;
-            b.out = d2; b.ldo = D; b.variant = V;
-            FTMI_TRY(gemm_nt(b, st));
+            FTMI_TRY(gemm_nt(linear_args(W(ws, L.s_big), c.D_ff, M, P(w.w_ff1_t, (size_t)l * D * c.D_ff), c.D_ff, D, c.D_ff, nullptr, d2, D, V), st));
             CogLnArgs n = ln_args(c, W(blk, L.h1), 1, l, w);
             n.onep = t.onep2; n.dy = d2; n.dres = dout; n.dx = d3;  // d3 = d h1
             FTMI_TRY(cog_ln_mod_bwd(n, st));
         }
         // ---- attention branch ----
         FTMI_TRY(gate_res(c, nullptr, d3, t.gate1, go, st));  // d(to_out output), kept for its weight gradient
-        if (r > 0) FTMI_TRY(lora_down(go, D, M, lbt + 3L * 2 * r * D, r, D, r, s, W(blk, L.dxa_o), st));
+        if (r > 0) FTMI_TRY(gemm_nt(lora_down_args(go, D, M, lbt + 3L * 2 * r * D, 1, D, r, s, W(blk, L.dxa_o)), st));
         {
-            GemmNtArgs a;
-            a.X = go; a.ldx = D; a.W = P(w.w_o_t, (size_t)l * D2); a.ldw = D; a.M = M; a.N = D; a.K = D; a.out = d1; a.ldo = D; a.variant = V;
-            if (r > 0) { a.X2 = W(blk, L.dxa_o); a.ldx2 = 3 * r; a.W2 = lat + 3L * D * 3 * r; a.ldw2 = 3 * r; a.K2 = 3 * r; }
+            GemmNtArgs a = linear_args(go, D, M, P(w.w_o_t, (size_t)l * D2), D, D, D, nullptr, d1, D, V);
+            if (r > 0) lora_ext_bwd(a, W(blk, L.dxa_o), 1, r, lat + 3L * D * 3 * r, 3 * r);
             FTMI_TRY(gemm_nt(a, st));  // d1 = d o
         }
         {
-            AttnArgs a = attn_args(c);
-            a.q = W(blk, L.qn); set3(a.q_sb, a.q_sh, a.q_ss, N, D);
-            a.k = W(blk, L.kn); set3(a.k_sb, a.k_sh, a.k_ss, N, D);
-            a.v = qkv + 2 * D;  set3(a.v_sb, a.v_sh, a.v_ss, N, 3 * D);
-            a.o = W(blk, L.o);  set3(a.o_sb, a.o_sh, a.o_ss, N, D);
-            a.lse2 = WF(blk, L.lse);
-            a.dout = d1;              set3(a.do_sb, a.do_sh, a.do_ss, N, D);
+            AttnArgs a = attn_args(c, W(blk, L.qn), W(blk, L.kn), qkv, W(blk, L.o), WF(blk, L.lse));
+            a.dout = d1;              tok_strides(a.do_sb, a.do_sh, a.do_ss, N, D, 64);
             a.delta = WF(ws, L.s_delta);
-            a.dq = W(ws, L.s_dq);     set3(a.dq_sb, a.dq_sh, a.dq_ss, N, D);
-            a.dk = W(ws, L.s_dk);     set3(a.dk_sb, a.dk_sh, a.dk_ss, N, D);
-            a.dv = gqkv + 2 * D;      set3(a.dv_sb, a.dv_sh, a.dv_ss, N, 3 * D);
+            a.dq = W(ws, L.s_dq);     tok_strides(a.dq_sb, a.dq_sh, a.dq_ss, N, D, 64);
+            a.dk = W(ws, L.s_dk);     tok_strides(a.dk_sb, a.dk_sh, a.dk_ss, N, D, 64);
+            a.dv = gqkv + 2 * D;      tok_strides(a.dv_sb, a.dv_sh, a.dv_ss, N, 3 * D, 64);
             FTMI_TRY(attn_bwd(a, st));
         }
         for (int qk = 0; qk < 2; ++qk) {  // head LayerNorm (+ RoPE) backward into the q / k thirds of d(q|k|v)
@@ -294,11 +263,10 @@ int cog_blocks_backward(const ftmi_cog_config& c, const ftmi_cog_weights& w, con
             a.cos = w.rope_cos; a.sin = w.rope_sin; a.rows_per_batch = N; a.seg0 = w.rope_cos ? c.T : 0;
             FTMI_TRY(cog_head_ln_bwd(a, st));
         }
-        if (r > 0) FTMI_TRY(lora_down(gqkv, 3 * D, M, lbt, 3 * r, D, r, s, W(blk, L.dxa_qkv), st, D));
+        if (r > 0) FTMI_TRY(gemm_nt(lora_down_args(gqkv, 3 * D, M, lbt, 3, D, r, s, W(blk, L.dxa_qkv), D), st));
         {
-            GemmNtArgs a;  // d n1 = d(q|k|v) W_qkv + d XA A: the three paths in one fp32 accumulator
-            a.X = gqkv; a.ldx = 3 * D; a.W = P(w.w_qkv_t, (size_t)l * 3 * D2); a.ldw = 3 * D; a.M = M; a.N = D; a.K = 3 * D; a.out = d2; a.ldo = D; a.variant = V;
-            if (r > 0) { a.X2 = W(blk, L.dxa_qkv); a.ldx2 = 9 * r; a.W2 = P(w.lora_at_qkv_ext, (size_t)l * D * 9 * r); a.ldw2 = 9 * r; a.K2 = 9 * r; }
+            GemmNtArgs a = linear_args(gqkv, 3 * D, M, P(w.w_qkv_t, (size_t)l * 3 * D2), 3 * D, D, 3 * D, nullptr, d2, D, V);  // d n1 = d(q|k|v) W_qkv + d XA A
+            if (r > 0) lora_ext_bwd(a, W(blk, L.dxa_qkv), 3, r, P(w.lora_at_qkv_ext, (size_t)l * D * 9 * r), 9 * r);
             FTMI_TRY(gemm_nt(a, st));
             CogLnArgs n = ln_args(c, h0, 0, l, w);
             n.onep = t.onep1; n.dy = d2; n.dres = d3; n.dx = dx;
@@ -317,17 +285,11 @@ int cog_blocks_backward(const ftmi_cog_config& c, const ftmi_cog_weights& w, con
         float* ga = grad_a + (size_t)l_lo * 4 * r * D;
         float* gb = grad_b + (size_t)l_lo * 4 * D * r;
         for (const G& gr : groups) {
-            GemmTnArgs tb;  // dB[l] += dY[l]^T XA[l]
-            tb.U = W(blk0, gr.dy); tb.ldu = gr.lddy; tb.V = W(blk0, gr.xa); tb.ldv = (long)gr.nadp * 3 * r; tb.v_fold = r;
-            tb.C = gb + (size_t)gr.adp * D * r; tb.ldc = r; tb.M = M; tb.P = gr.nadp * D; tb.Q = r;
-            if (gr.nadp > 1) { tb.v_grp_p = D; tb.v_grp_stride = 3 * r; }
-            tb.batch = nb; tb.u_bstride = bs; tb.v_bstride = bs; tb.c_bstride = 4L * D * r;
+            GemmTnArgs tb = lora_db_args(W(blk0, gr.dy), gr.lddy, W(blk0, gr.xa), gr.nadp, r, D, gb + (size_t)gr.adp * D * r, M);  // dB[l] += dY[l]^T XA[l]
+            tn_batch(tb, nb, bs, bs, 4L * D * r);
             FTMI_TRY(gemm_tn(tb, st));
-            GemmTnArgs ta;  // dA[l] += dXA[l]^T X[l]
-            ta.U = W(blk0, gr.dxa); ta.ldu = (long)gr.nadp * 3 * r; ta.u_fold = r; ta.V = W(blk0, gr.x); ta.ldv = D;
-            if (gr.nadp > 1) { ta.u_grp_p = r; ta.u_grp_stride = 3 * r; }
-            ta.C = ga + (size_t)gr.adp * r * D; ta.ldc = D; ta.M = M; ta.P = gr.nadp * r; ta.Q = D;
-            ta.batch = nb; ta.u_bstride = bs; ta.v_bstride = bs; ta.c_bstride = 4L * r * D;
+            GemmTnArgs ta = lora_da_args(W(blk0, gr.dxa), gr.nadp, r, W(blk0, gr.x), D, D, ga + (size_t)gr.adp * r * D, M);  // dA[l] += dXA[l]^T X[l]
+            tn_batch(ta, nb, bs, bs, 4L * r * D);
             FTMI_TRY(gemm_tn(ta, st));
         }
     }

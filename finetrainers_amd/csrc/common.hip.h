@@ -189,6 +189,8 @@ struct Bump {
 };
 inline bf16_t* W(void* ws, size_t byte_off) { return reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(ws) + byte_off); }
 inline float* WF(void* ws, size_t byte_off) { return reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + byte_off); }
+// element `elem_off` of a stacked bf16 weight tensor handed over as an untyped pointer
+inline const bf16_t* P(const void* base, size_t elem_off) { return reinterpret_cast<const bf16_t*>(base) + elem_off; }
 
 #define FTMI_TRY(x)          \
     do {                     \

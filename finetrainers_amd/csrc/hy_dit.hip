@@ -17,6 +17,7 @@
 // round trips per block and direction, six LoRA operand splits (done once per call here) and torch's allocation of every intermediate.
 #include "common.hip.h"
 #include "kernels.h"
+#include "lora_proj.hip.h"
 
 namespace ftmi {
 
@@ -99,23 +100,21 @@ __global__ __launch_bounds__(256) void hy_mod3_kernel(const bf16_t* __restrict__
     gate[i] = m[2 * D + d];
 }
 
-int lora_down(const bf16_t* X, long ldx, int M, const bf16_t* w_sp, int r, int K, float alpha, bf16_t* out, hipStream_t st) {
-    GemmNtArgs d;
-    d.X = X; d.ldx = ldx; d.W = w_sp; d.ldw = K; d.M = M; d.N = 2 * r; d.K = K; d.alpha = alpha; d.split_r = r;
-    d.out = out; d.ldo = 3L * r; d.variant = 8;
-    return gemm_nt(d, st);
-}
-
-AttnArgs attn_args(const ftmi_hy_single_config& c, const float* key_bias) {
+// joint attention over B sequences of N = T + S token rows [N, D], heads of 128 columns, one key-bias row per sequence
+AttnArgs attn_args(int B, int H, long N, long D, const float* key_bias) {
     AttnArgs a;
-    const long N = (long)c.T + c.S, D = c.D;
-    a.B = c.B; a.H = c.H; a.Sq = (int)N; a.Sk = (int)N; a.d = 128;
+    a.B = B; a.H = H; a.Sq = (int)N; a.Sk = (int)N; a.d = 128;
     a.scale = 0.08838834764831845f;  // 1 / sqrt(128)
-    a.q_sb = a.k_sb = a.v_sb = a.o_sb = N * D;
-    a.q_sh = a.k_sh = a.v_sh = a.o_sh = 128;
-    a.q_ss = a.k_ss = a.v_ss = a.o_ss = D;
+    tok_strides(a.q_sb, a.q_sh, a.q_ss, N, D, 128); tok_strides(a.k_sb, a.k_sh, a.k_ss, N, D, 128);
+    tok_strides(a.v_sb, a.v_sh, a.v_ss, N, D, 128); tok_strides(a.o_sb, a.o_sh, a.o_ss, N, D, 128);
     a.kbias = key_bias; a.kb_sb = N; a.kb_sh = 0;
     return a;
+}
+// the backward's gradient tensors: token rows like the forward's
+void attn_bwd_strides(AttnArgs& a) {
+    const long N = a.Sq, D = a.q_ss;
+    tok_strides(a.do_sb, a.do_sh, a.do_ss, N, D, 128); tok_strides(a.dq_sb, a.dq_sh, a.dq_ss, N, D, 128);
+    tok_strides(a.dk_sb, a.dk_sh, a.dk_ss, N, D, 128); tok_strides(a.dv_sb, a.dv_sh, a.dv_ss, N, D, 128);
 }
 
 }  // namespace
@@ -136,10 +135,7 @@ int hy_single_forward(const ftmi_hy_single_config& c, const ftmi_hy_single_weigh
     bf16_t *shift = W(saved, L.shift), *onep = W(saved, L.onep), *gate = W(saved, L.gate), *n = W(saved, L.n);
 
     {   // modulation
-        GemmNtArgs a;
-        a.X = temb_silu; a.ldx = D; a.W = C16(w.norm_lin_w); a.ldw = D; a.M = c.B; a.N = 3 * D; a.K = D; a.bias = C16(w.norm_lin_b);
-        a.out = W(saved, L.mod); a.ldo = 3 * D; a.variant = V;
-        FTMI_TRY(gemm_nt(a, st));
+        FTMI_TRY(gemm_nt(linear_args(temb_silu, D, c.B, C16(w.norm_lin_w), D, 3 * D, D, C16(w.norm_lin_b), W(saved, L.mod), 3 * D, V), st));
         hipLaunchKernelGGL(hy_mod3_kernel, dim3((c.B * D + 255) / 256), dim3(256), 0, st, W(saved, L.mod), shift, onep, gate, c.B, D);
         FTMI_TRY(check_launch("hy_mod3"));
     }
@@ -150,9 +146,8 @@ int hy_single_forward(const ftmi_hy_single_config& c, const ftmi_hy_single_weigh
     }
     bf16_t* cat = W(scratch, L.cat);
     {   // MLP branch: gelu_tanh(n W_mlp^T + b) straight into the [attention | MLP] feature buffer, pre-activation kept
-        GemmNtArgs a;
-        a.X = n; a.ldx = D; a.W = C16(w.proj_mlp_w); a.ldw = D; a.M = M; a.N = mlp; a.K = D; a.bias = C16(w.proj_mlp_b);
-        a.out = cat + D; a.ldo = D + mlp; a.out2 = W(saved, L.pre); a.ldo2 = mlp; a.epi = EPI_GELU; a.variant = V;
+        GemmNtArgs a = linear_args(n, D, M, C16(w.proj_mlp_w), D, mlp, D, C16(w.proj_mlp_b), cat + D, D + mlp, V);
+        a.out2 = W(saved, L.pre); a.ldo2 = mlp; a.epi = EPI_GELU;
         FTMI_TRY(gemm_nt(a, st));
     }
     if (r > 0) {  // operand copies of the fp32 adapters, once per call: A as (hi, lo) row planes, B as [hi | hi | lo] K-extension columns
@@ -167,12 +162,11 @@ int hy_single_forward(const ftmi_hy_single_config& c, const ftmi_hy_single_weigh
     const void* bs[3] = {w.bq, w.bk, w.bv};
     const size_t outs[3] = {L.q, L.k, L.v};
     for (int i = 0; i < 3; ++i) {
-        GemmNtArgs a;
-        a.X = n; a.ldx = D; a.W = C16(wts[i]); a.ldw = D; a.M = M; a.N = D; a.K = D; a.bias = C16(bs[i]); a.out = W(saved, outs[i]); a.ldo = D; a.variant = V;
+        GemmNtArgs a = linear_args(n, D, M, C16(wts[i]), D, D, D, C16(bs[i]), W(saved, outs[i]), D, V);
         if (r > 0) {
             bf16_t* xa = W(saved, L.xa) + (size_t)i * M * 3 * r;
-            FTMI_TRY(lora_down(n, D, M, W(scratch, L.a_sp) + (size_t)i * 2 * r * D, r, D, s, xa, st));
-            a.X2 = xa; a.ldx2 = 3 * r; a.W2 = W(scratch, L.b_ext) + (size_t)i * D * 3 * r; a.ldw2 = 3 * r; a.K2 = 3 * r;
+            FTMI_TRY(gemm_nt(lora_down_args(n, D, M, W(scratch, L.a_sp) + (size_t)i * 2 * r * D, 1, D, r, s, xa), st));
+            lora_ext_fwd(a, xa, 1, r, W(scratch, L.b_ext) + (size_t)i * D * 3 * r);
         }
         FTMI_TRY(gemm_nt(a, st));
     }
@@ -183,7 +177,7 @@ int hy_single_forward(const ftmi_hy_single_config& c, const ftmi_hy_single_weigh
         FTMI_TRY(cog_head_ln_fwd(a, st));
     }
     {
-        AttnArgs a = attn_args(c, key_bias);
+        AttnArgs a = attn_args(c.B, c.H, N, D, key_bias);
         a.q = W(saved, L.qn); a.k = W(saved, L.kn); a.v = W(saved, L.v); a.o = W(saved, L.o); a.lse2 = WF(saved, L.lse);
         FTMI_TRY(attn_fwd(a, st));
     }
@@ -191,10 +185,7 @@ int hy_single_forward(const ftmi_hy_single_config& c, const ftmi_hy_single_weigh
     if (hipMemcpy2DAsync(cat, (size_t)(D + mlp) * 2, W(saved, L.o), (size_t)D * 2, (size_t)D * 2, M, hipMemcpyDeviceToDevice, st) != hipSuccess)
         return set_error(FTMI_ERR_LAUNCH, "hy_single_forward: copy of the attention features failed");
     {
-        GemmNtArgs a;
-        a.X = cat; a.ldx = D + mlp; a.W = C16(w.proj_out_w); a.ldw = D + mlp; a.M = M; a.N = D; a.K = D + mlp; a.bias = C16(w.proj_out_b);
-        a.out = W(scratch, L.y); a.ldo = D; a.variant = V;
-        FTMI_TRY(gemm_nt(a, st));
+        FTMI_TRY(gemm_nt(linear_args(cat, D + mlp, M, C16(w.proj_out_w), D + mlp, D, D + mlp, C16(w.proj_out_b), W(scratch, L.y), D, V), st));
     }
     {   // out = x + bf(gate * y)
         CogLnArgs a;
@@ -224,24 +215,17 @@ int hy_single_backward(const ftmi_hy_single_config& c, const ftmi_hy_single_weig
     }
     const bf16_t* wt = C16(w.proj_out_w_t);  // [D + mlp, D]
     {
-        GemmNtArgs a;  // gradient of the attention features
-        a.X = dy; a.ldx = D; a.W = wt; a.ldw = D; a.M = M; a.N = D; a.K = D; a.out = W(scratch, L.d_o); a.ldo = D; a.variant = V;
-        FTMI_TRY(gemm_nt(a, st));
-        GemmNtArgs b;  // (gradient of the MLP features) * gelu'(pre)
-        b.X = dy; b.ldx = D; b.W = wt + (size_t)D * D; b.ldw = D; b.M = M; b.N = mlp; b.K = D; b.out = W(scratch, L.dpre); b.ldo = mlp;
-        b.epi = EPI_DGELU; b.aux = W(saved, L.pre); b.ldaux = mlp; b.variant = V;
+        FTMI_TRY(gemm_nt(linear_args(dy, D, M, wt, D, D, D, nullptr, W(scratch, L.d_o), D, V), st));  // gradient of the attention features
+        GemmNtArgs b = linear_args(dy, D, M, wt + (size_t)D * D, D, mlp, D, nullptr, W(scratch, L.dpre), mlp, V);  // (gradient of the MLP features) * gelu'(pre)
+        b.epi = EPI_DGELU; b.aux = W(saved, L.pre); b.ldaux = mlp;
         FTMI_TRY(gemm_nt(b, st));
-        GemmNtArgs d;
-        d.X = W(scratch, L.dpre); d.ldx = mlp; d.W = C16(w.proj_mlp_w_t); d.ldw = mlp; d.M = M; d.N = D; d.K = mlp; d.out = W(scratch, L.dn_mlp); d.ldo = D; d.variant = V;
-        FTMI_TRY(gemm_nt(d, st));
+        FTMI_TRY(gemm_nt(linear_args(W(scratch, L.dpre), mlp, M, C16(w.proj_mlp_w_t), mlp, D, mlp, nullptr, W(scratch, L.dn_mlp), D, V), st));
     }
     {
-        AttnArgs a = attn_args(c, key_bias);
+        AttnArgs a = attn_args(c.B, c.H, N, D, key_bias);
         a.q = W(saved, L.qn); a.k = W(saved, L.kn); a.v = W(saved, L.v); a.o = W(saved, L.o); a.lse2 = WF(saved, L.lse);
         a.dout = W(scratch, L.d_o); a.dq = W(scratch, L.dqn); a.dk = W(scratch, L.dkn); a.dv = W(scratch, L.dv); a.delta = WF(scratch, L.delta);
-        a.do_sb = a.dq_sb = a.dk_sb = a.dv_sb = (long)N * D;
-        a.do_sh = a.dq_sh = a.dk_sh = a.dv_sh = 128;
-        a.do_ss = a.dq_ss = a.dk_ss = a.dv_ss = D;
+        attn_bwd_strides(a);
         FTMI_TRY(attn_bwd(a, st));
     }
     for (int i = 0; i < 2; ++i) {
@@ -265,18 +249,13 @@ int hy_single_backward(const ftmi_hy_single_config& c, const ftmi_hy_single_weig
     for (int i = 0; i < 3; ++i) {
         bf16_t* dxa = W(scratch, L.dxa);
         const bf16_t* xa = W(saved, L.xa) + (size_t)i * M * 3 * r;
-        if (r > 0) FTMI_TRY(lora_down(dys[i], D, M, W(scratch, L.bt_sp) + (size_t)i * 2 * r * D, r, D, s, dxa, st));
-        GemmNtArgs a;  // dn_i = dy_i W_i (+ dxa A_i)
-        a.X = dys[i]; a.ldx = D; a.W = C16(wts[i]); a.ldw = D; a.M = M; a.N = D; a.K = D; a.out = W(scratch, dns[i]); a.ldo = D; a.variant = V;
-        if (r > 0) { a.X2 = dxa; a.ldx2 = 3 * r; a.W2 = W(scratch, L.at_ext) + (size_t)i * D * 3 * r; a.ldw2 = 3 * r; a.K2 = 3 * r; }
+        if (r > 0) FTMI_TRY(gemm_nt(lora_down_args(dys[i], D, M, W(scratch, L.bt_sp) + (size_t)i * 2 * r * D, 1, D, r, s, dxa), st));
+        GemmNtArgs a = linear_args(dys[i], D, M, C16(wts[i]), D, D, D, nullptr, W(scratch, dns[i]), D, V);  // dn_i = dy_i W_i (+ dxa A_i)
+        if (r > 0) lora_ext_bwd(a, dxa, 1, r, W(scratch, L.at_ext) + (size_t)i * D * 3 * r, 3 * r);
         FTMI_TRY(gemm_nt(a, st));
         if (r > 0) {
-            GemmTnArgs t;  // dB_i += dy_i^T xa_i
-            t.U = dys[i]; t.ldu = D; t.V = xa; t.ldv = 3 * r; t.v_fold = r; t.C = grad_b + (size_t)i * D * r; t.ldc = r; t.M = M; t.P = D; t.Q = r;
-            FTMI_TRY(gemm_tn(t, st));
-            GemmTnArgs u;  // dA_i += dxa^T n
-            u.U = dxa; u.ldu = 3 * r; u.u_fold = r; u.V = n; u.ldv = D; u.C = grad_a + (size_t)i * r * D; u.ldc = D; u.M = M; u.P = r; u.Q = D;
-            FTMI_TRY(gemm_tn(u, st));
+            FTMI_TRY(gemm_tn(lora_db_args(dys[i], D, xa, 1, r, D, grad_b + (size_t)i * D * r, M), st));  // dB_i += dy_i^T xa_i
+            FTMI_TRY(gemm_tn(lora_da_args(dxa, 1, r, n, D, D, grad_a + (size_t)i * r * D, M), st));       // dA_i += dxa^T n
         }
     }
     // the four consumers of n: their gradients add as bf16 tensors, in autograd's order (MLP + v, + k, + q)
@@ -407,10 +386,9 @@ __global__ __launch_bounds__(256) void hy_mod6_kernel(const bf16_t* __restrict__
     t[5 * D + d] = f2bf(1.0f + bf2f(m[4 * D + d]));
 }
 
-int plain_linear(const bf16_t* X, int M, int K, const void* Wm, const void* bias, int N, bf16_t* out, int V, hipStream_t st) {
-    GemmNtArgs a;
-    a.X = X; a.ldx = K; a.W = C16(Wm); a.ldw = K; a.M = M; a.N = N; a.K = K; a.bias = C16(bias); a.out = out; a.ldo = N; a.variant = V;
-    return gemm_nt(a, st);
+// out [M, N] = X W^T + bias over packed rows
+int linear(const bf16_t* X, int M, int K, const void* Wm, const void* bias, int N, bf16_t* out, int V, hipStream_t st) {
+    return gemm_nt(linear_args(X, K, M, C16(Wm), K, N, K, C16(bias), out, N, V), st);
 }
 int ln_mod(const bf16_t* x, const ftmi_hy_dual_weights& w, const bf16_t* shift, const bf16_t* onep, bf16_t* y, int rows, int D, float eps, hipStream_t st) {
     CogLnArgs a;
@@ -437,26 +415,14 @@ int head_norm(const bf16_t* x, const void* wn, bf16_t* y, const bf16_t* dy, int 
     a.y = y;
     return cog_head_ln_fwd(a, st);
 }
-AttnArgs dual_attn_args(const ftmi_hy_dual_config& c, const float* key_bias) {
-    AttnArgs a;
-    const long N = (long)c.T + c.S, D = c.D;
-    a.B = 1; a.H = c.H; a.Sq = (int)N; a.Sk = (int)N; a.d = 128;
-    a.scale = 0.08838834764831845f;
-    a.q_sb = a.k_sb = a.v_sb = a.o_sb = N * D;
-    a.q_sh = a.k_sh = a.v_sh = a.o_sh = 128;
-    a.q_ss = a.k_ss = a.v_ss = a.o_ss = D;
-    a.kbias = key_bias; a.kb_sb = N; a.kb_sh = 0;
-    return a;
-}
 // y = x W^T + b (+ LoRA adapter i); xa_i kept
 int lora_linear_fwd(const bf16_t* X, int M, int D, const void* Wm, const void* bias, int i, int r, float s, void* scratch, const HyDualLayout& L, bf16_t* xa_all,
                     size_t xa_stride, bf16_t* out, int V, hipStream_t st) {
-    GemmNtArgs a;
-    a.X = X; a.ldx = D; a.W = C16(Wm); a.ldw = D; a.M = M; a.N = D; a.K = D; a.bias = C16(bias); a.out = out; a.ldo = D; a.variant = V;
+    GemmNtArgs a = linear_args(X, D, M, C16(Wm), D, D, D, C16(bias), out, D, V);
     if (r > 0) {
         bf16_t* xa = xa_all + (size_t)i * xa_stride;
-        FTMI_TRY(lora_down(X, D, M, W(scratch, L.a_sp) + (size_t)i * 2 * r * D, r, D, s, xa, st));
-        a.X2 = xa; a.ldx2 = 3 * r; a.W2 = W(scratch, L.b_ext) + (size_t)i * D * 3 * r; a.ldw2 = 3 * r; a.K2 = 3 * r;
+        FTMI_TRY(gemm_nt(lora_down_args(X, D, M, W(scratch, L.a_sp) + (size_t)i * 2 * r * D, 1, D, r, s, xa), st));
+        lora_ext_fwd(a, xa, 1, r, W(scratch, L.b_ext) + (size_t)i * D * 3 * r);
     }
     return gemm_nt(a, st);
 }
@@ -464,18 +430,13 @@ int lora_linear_fwd(const bf16_t* X, int M, int D, const void* Wm, const void* b
 int lora_linear_bwd(const bf16_t* X, const bf16_t* dy, int M, int D, const void* Wt, int i, int r, float s, void* scratch, const HyDualLayout& L, const bf16_t* xa_all,
                     size_t xa_stride, bf16_t* dx, float* grad_a, float* grad_b, int V, hipStream_t st) {
     bf16_t* dxa = W(scratch, L.dxa);
-    if (r > 0) FTMI_TRY(lora_down(dy, D, M, W(scratch, L.bt_sp) + (size_t)i * 2 * r * D, r, D, s, dxa, st));
-    GemmNtArgs a;
-    a.X = dy; a.ldx = D; a.W = C16(Wt); a.ldw = D; a.M = M; a.N = D; a.K = D; a.out = dx; a.ldo = D; a.variant = V;
-    if (r > 0) { a.X2 = dxa; a.ldx2 = 3 * r; a.W2 = W(scratch, L.at_ext) + (size_t)i * D * 3 * r; a.ldw2 = 3 * r; a.K2 = 3 * r; }
+    if (r > 0) FTMI_TRY(gemm_nt(lora_down_args(dy, D, M, W(scratch, L.bt_sp) + (size_t)i * 2 * r * D, 1, D, r, s, dxa), st));
+    GemmNtArgs a = linear_args(dy, D, M, C16(Wt), D, D, D, nullptr, dx, D, V);
+    if (r > 0) lora_ext_bwd(a, dxa, 1, r, W(scratch, L.at_ext) + (size_t)i * D * 3 * r, 3 * r);
     FTMI_TRY(gemm_nt(a, st));
     if (r > 0) {
-        GemmTnArgs t;
-        t.U = dy; t.ldu = D; t.V = xa_all + (size_t)i * xa_stride; t.ldv = 3 * r; t.v_fold = r; t.C = grad_b + (size_t)i * D * r; t.ldc = r; t.M = M; t.P = D; t.Q = r;
-        FTMI_TRY(gemm_tn(t, st));
-        GemmTnArgs u;
-        u.U = dxa; u.ldu = 3 * r; u.u_fold = r; u.V = X; u.ldv = D; u.C = grad_a + (size_t)i * r * D; u.ldc = D; u.M = M; u.P = r; u.Q = D;
-        FTMI_TRY(gemm_tn(u, st));
+        FTMI_TRY(gemm_tn(lora_db_args(dy, D, xa_all + (size_t)i * xa_stride, 1, r, D, grad_b + (size_t)i * D * r, M), st));
+        FTMI_TRY(gemm_tn(lora_da_args(dxa, 1, r, X, D, D, grad_a + (size_t)i * r * D, M), st));
     }
     return 0;
 }
@@ -499,8 +460,8 @@ int hy_dual_forward(const ftmi_hy_dual_config& c, const ftmi_hy_dual_weights& w,
     bf16_t* tab = W(saved, L.tables);
     auto TV = [&](int i) { return tab + (size_t)i * D; };            // video: shift, gate, shift_mlp, gate_mlp, 1 + scale, 1 + scale_mlp
     auto TT = [&](int i) { return tab + (size_t)(6 + i) * D; };      // text
-    FTMI_TRY(plain_linear(temb_silu, 1, D, w.norm1_lin_w, w.norm1_lin_b, 6 * D, W(saved, L.mod), V, st));
-    FTMI_TRY(plain_linear(temb_silu, 1, D, w.norm1c_lin_w, w.norm1c_lin_b, 6 * D, W(saved, L.mod) + (size_t)6 * D, V, st));
+    FTMI_TRY(linear(temb_silu, 1, D, w.norm1_lin_w, w.norm1_lin_b, 6 * D, W(saved, L.mod), V, st));
+    FTMI_TRY(linear(temb_silu, 1, D, w.norm1c_lin_w, w.norm1c_lin_b, 6 * D, W(saved, L.mod) + (size_t)6 * D, V, st));
     hipLaunchKernelGGL(hy_mod6_kernel, dim3((2 * D + 255) / 256), dim3(256), 0, st, W(saved, L.mod), tab, D);
     FTMI_TRY(check_launch("hy_mod6"));
     bf16_t *n_v = W(saved, L.n_v), *n_t = W(saved, L.n_t);
@@ -521,35 +482,35 @@ int hy_dual_forward(const ftmi_hy_dual_config& c, const ftmi_hy_dual_weights& w,
     FTMI_TRY(lora_linear_fwd(n_v, S, D, w.wv, w.bv, 2, r, s, scratch, L, xa, xas, vj + (size_t)T * D, V, st));  // v of the video rows straight into the joint buffer
     FTMI_TRY(head_norm(W(saved, L.q_v), w.norm_q_w, qj + (size_t)T * D, nullptr, S, D, eps, rope_cos, rope_sin, false, st));
     FTMI_TRY(head_norm(W(saved, L.k_v), w.norm_k_w, kj + (size_t)T * D, nullptr, S, D, eps, rope_cos, rope_sin, false, st));
-    FTMI_TRY(plain_linear(n_t, T, D, w.add_q_w, w.add_q_b, D, W(saved, L.q_t), V, st));
-    FTMI_TRY(plain_linear(n_t, T, D, w.add_k_w, w.add_k_b, D, W(saved, L.k_t), V, st));
-    FTMI_TRY(plain_linear(n_t, T, D, w.add_v_w, w.add_v_b, D, vj, V, st));
+    FTMI_TRY(linear(n_t, T, D, w.add_q_w, w.add_q_b, D, W(saved, L.q_t), V, st));
+    FTMI_TRY(linear(n_t, T, D, w.add_k_w, w.add_k_b, D, W(saved, L.k_t), V, st));
+    FTMI_TRY(linear(n_t, T, D, w.add_v_w, w.add_v_b, D, vj, V, st));
     FTMI_TRY(head_norm(W(saved, L.q_t), w.norm_added_q_w, qj, nullptr, T, D, eps, nullptr, nullptr, false, st));
     FTMI_TRY(head_norm(W(saved, L.k_t), w.norm_added_k_w, kj, nullptr, T, D, eps, nullptr, nullptr, false, st));
     bf16_t* o = W(saved, L.o);
     {
-        AttnArgs a = dual_attn_args(c, key_bias);
+        AttnArgs a = attn_args(1, c.H, N, D, key_bias);
         a.q = qj; a.k = kj; a.v = vj; a.o = o; a.lse2 = WF(saved, L.lse);
         FTMI_TRY(attn_fwd(a, st));
     }
     bf16_t *a_v = W(scratch, L.a_v), *a_t = W(scratch, L.a_t), *h_v = W(saved, L.h_v), *h_t = W(saved, L.h_t);
     FTMI_TRY(lora_linear_fwd(o + (size_t)T * D, S, D, w.wo, w.bo, 3, r, s, scratch, L, xa, xas, a_v, V, st));
-    FTMI_TRY(plain_linear(o, T, D, w.add_out_w, w.add_out_b, D, a_t, V, st));
+    FTMI_TRY(linear(o, T, D, w.add_out_w, w.add_out_b, D, a_t, V, st));
     FTMI_TRY(gate_res(x_v, a_v, TV(1), h_v, S, D, st));
     FTMI_TRY(gate_res(x_t, a_t, TT(1), h_t, T, D, st));
     bf16_t *n2_v = W(scratch, L.n2_v), *n2_t = W(scratch, L.n2_t);
     FTMI_TRY(ln_mod(h_v, w, TV(2), TV(5), n2_v, S, D, eps, st));
     FTMI_TRY(ln_mod(h_t, w, TT(2), TT(5), n2_t, T, D, eps, st));
     for (int sidx = 0; sidx < 2; ++sidx) {  // feed-forward, first GEMM: gelu_tanh, pre-activation kept
-        GemmNtArgs a;
-        a.X = sidx ? n2_t : n2_v; a.ldx = D; a.W = C16(sidx ? w.ffc1_w : w.ff1_w); a.ldw = D; a.M = sidx ? T : S; a.N = mlp; a.K = D; a.bias = C16(sidx ? w.ffc1_b : w.ff1_b);
-        a.out = W(scratch, sidx ? L.act_t : L.act_v); a.ldo = mlp; a.out2 = W(saved, sidx ? L.pre_t : L.pre_v); a.ldo2 = mlp; a.epi = EPI_GELU; a.variant = V;
+        GemmNtArgs a = linear_args(sidx ? n2_t : n2_v, D, sidx ? T : S, C16(sidx ? w.ffc1_w : w.ff1_w), D, mlp, D, C16(sidx ? w.ffc1_b : w.ff1_b),
+                                   W(scratch, sidx ? L.act_t : L.act_v), mlp, V);
+        a.out2 = W(saved, sidx ? L.pre_t : L.pre_v); a.ldo2 = mlp; a.epi = EPI_GELU;
         FTMI_TRY(gemm_nt(a, st));
     }
     if (!out_v) return 0;
-    FTMI_TRY(plain_linear(W(scratch, L.act_v), S, mlp, w.ff2_w, w.ff2_b, D, W(scratch, L.f_v), V, st));
+    FTMI_TRY(linear(W(scratch, L.act_v), S, mlp, w.ff2_w, w.ff2_b, D, W(scratch, L.f_v), V, st));
     FTMI_TRY(gate_res(h_v, W(scratch, L.f_v), TV(3), out_v, S, D, st));
-    FTMI_TRY(plain_linear(W(scratch, L.act_t), T, mlp, w.ffc2_w, w.ffc2_b, D, W(scratch, L.f_t), V, st));
+    FTMI_TRY(linear(W(scratch, L.act_t), T, mlp, w.ffc2_w, w.ffc2_b, D, W(scratch, L.f_t), V, st));
     FTMI_TRY(gate_res(h_t, W(scratch, L.f_t), TT(3), out_t, T, D, st));
     return 0;
 }
@@ -575,14 +536,10 @@ int hy_dual_backward(const ftmi_hy_dual_config& c, const ftmi_hy_dual_weights& w
         bf16_t* df = W(scratch, sidx ? L.df_t : L.df_v);
         const bf16_t* dout = sidx ? dout_t : dout_v;
         FTMI_TRY(gate_res(nullptr, dout, sidx ? TT(3) : TV(3), df, rows, D, st));
-        GemmNtArgs a;  // (d of the activations) * gelu'(pre)
-        a.X = df; a.ldx = D; a.W = C16(sidx ? w.ffc2_w_t : w.ff2_w_t); a.ldw = D; a.M = rows; a.N = mlp; a.K = D; a.out = W(scratch, sidx ? L.dg_t : L.dg_v); a.ldo = mlp;
-        a.epi = EPI_DGELU; a.aux = W(saved, sidx ? L.pre_t : L.pre_v); a.ldaux = mlp; a.variant = V;
+        GemmNtArgs a = linear_args(df, D, rows, C16(sidx ? w.ffc2_w_t : w.ff2_w_t), D, mlp, D, nullptr, W(scratch, sidx ? L.dg_t : L.dg_v), mlp, V);
+        a.epi = EPI_DGELU; a.aux = W(saved, sidx ? L.pre_t : L.pre_v); a.ldaux = mlp;  // (d of the activations) * gelu'(pre)
         FTMI_TRY(gemm_nt(a, st));
-        GemmNtArgs b;
-        b.X = W(scratch, sidx ? L.dg_t : L.dg_v); b.ldx = mlp; b.W = C16(sidx ? w.ffc1_w_t : w.ff1_w_t); b.ldw = mlp; b.M = rows; b.N = D; b.K = mlp;
-        b.out = W(scratch, sidx ? L.dn2_t : L.dn2_v); b.ldo = D; b.variant = V;
-        FTMI_TRY(gemm_nt(b, st));
+        FTMI_TRY(linear(W(scratch, sidx ? L.dg_t : L.dg_v), rows, mlp, sidx ? w.ffc1_w_t : w.ff1_w_t, nullptr, D, W(scratch, sidx ? L.dn2_t : L.dn2_v), V, st));
         FTMI_TRY(ln_mod_back(W(saved, sidx ? L.h_t : L.h_v), w, sidx ? TT(5) : TV(5), W(scratch, sidx ? L.dn2_t : L.dn2_v), dout, W(scratch, sidx ? L.dh_t : L.dh_v), rows, D,
                              eps, st));
     }
@@ -601,14 +558,12 @@ int hy_dual_backward(const ftmi_hy_dual_config& c, const ftmi_hy_dual_weights& w
     FTMI_TRY(gate_res(nullptr, dh_v, TV(1), W(scratch, L.da_v), S, D, st));
     FTMI_TRY(lora_linear_bwd(o + (size_t)T * D, W(scratch, L.da_v), S, D, w.wo_t, 3, r, s, scratch, L, xa, xas, doj + (size_t)T * D, grad_a, grad_b, V, st));
     FTMI_TRY(gate_res(nullptr, dh_t, TT(1), W(scratch, L.da_t), T, D, st));
-    FTMI_TRY(plain_linear(W(scratch, L.da_t), T, D, w.add_out_w_t, nullptr, D, doj, V, st));
+    FTMI_TRY(linear(W(scratch, L.da_t), T, D, w.add_out_w_t, nullptr, D, doj, V, st));
     {
-        AttnArgs a = dual_attn_args(c, key_bias);
+        AttnArgs a = attn_args(1, c.H, N, D, key_bias);
         a.q = W(saved, L.qj); a.k = W(saved, L.kj); a.v = W(saved, L.vj); a.o = W(saved, L.o); a.lse2 = WF(saved, L.lse);
         a.dout = doj; a.dq = W(scratch, L.dqj); a.dk = W(scratch, L.dkj); a.dv = W(scratch, L.dvj); a.delta = WF(scratch, L.delta);
-        a.do_sb = a.dq_sb = a.dk_sb = a.dv_sb = (long)N * D;
-        a.do_sh = a.dq_sh = a.dk_sh = a.dv_sh = 128;
-        a.do_ss = a.dq_ss = a.dk_ss = a.dv_ss = D;
+        attn_bwd_strides(a);
         FTMI_TRY(attn_bwd(a, st));
     }
     const bf16_t *dqj = W(scratch, L.dqj), *dkj = W(scratch, L.dkj), *dvj = W(scratch, L.dvj);
@@ -625,10 +580,10 @@ int hy_dual_backward(const ftmi_hy_dual_config& c, const ftmi_hy_dual_weights& w
     // text stream
     FTMI_TRY(head_norm(W(saved, L.q_t), w.norm_added_q_w, W(scratch, L.dq_t), dqj, T, D, eps, nullptr, nullptr, true, st));
     FTMI_TRY(head_norm(W(saved, L.k_t), w.norm_added_k_w, W(scratch, L.dk_t), dkj, T, D, eps, nullptr, nullptr, true, st));
-    FTMI_TRY(plain_linear(dvj, T, D, w.add_v_w_t, nullptr, D, W(scratch, L.t1), V, st));
-    FTMI_TRY(plain_linear(W(scratch, L.dk_t), T, D, w.add_k_w_t, nullptr, D, W(scratch, L.t2), V, st));
+    FTMI_TRY(linear(dvj, T, D, w.add_v_w_t, nullptr, D, W(scratch, L.t1), V, st));
+    FTMI_TRY(linear(W(scratch, L.dk_t), T, D, w.add_k_w_t, nullptr, D, W(scratch, L.t2), V, st));
     FTMI_TRY(gate_res(W(scratch, L.t1), W(scratch, L.t2), ones_row, W(scratch, L.dn_t), T, D, st));
-    FTMI_TRY(plain_linear(W(scratch, L.dq_t), T, D, w.add_q_w_t, nullptr, D, W(scratch, L.t3), V, st));
+    FTMI_TRY(linear(W(scratch, L.dq_t), T, D, w.add_q_w_t, nullptr, D, W(scratch, L.t3), V, st));
     FTMI_TRY(gate_res(W(scratch, L.dn_t), W(scratch, L.t3), ones_row, W(scratch, L.dn_t), T, D, st));
     FTMI_TRY(ln_mod_back(x_t, w, TT(4), W(scratch, L.dn_t), dh_t, dx_t, T, D, eps, st));
     return 0;

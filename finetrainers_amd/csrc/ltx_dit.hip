@@ -11,6 +11,7 @@
 
 #include "common.hip.h"
 #include "kernels.h"
+#include "lora_proj.hip.h"
 
 namespace ftmi {
 
@@ -121,31 +122,6 @@ int check_cfg(const ftmi_ltx_config& c, int frames = 0) {
     return 0;
 }
 
-inline const bf16_t* P(const void* base, size_t elem_off) { return reinterpret_cast<const bf16_t*>(base) + elem_off; }
-
-// plain linear helper
-int linear(const bf16_t* X, long ldx, int M, const bf16_t* Wt, long ldw, int N, int K, const bf16_t* bias, bf16_t* out, long ldo,
-           int variant, hipStream_t st, float alpha = 1.f) {
-    GemmNtArgs a;
-    a.X = X; a.ldx = ldx; a.W = Wt; a.ldw = ldw; a.M = M; a.N = N; a.K = K;
-    a.bias = bias; a.alpha = alpha; a.out = out; a.ldo = ldo; a.variant = variant;
-    return gemm_nt(a, st);
-}
-
-// LoRA down-projection at fp32-equivalent precision: t = alpha * X . Wf^T for an fp32 matrix Wf given as interleaved bf16 (hi, lo) row
-// planes `w_sp` ([2 nout, K], kernels.h LoraSplitArgs), t kept as bf16 planes (hi | lo | hi) per group of r outputs: out [M, 3 nout].
-// The reference runs this product in fp32 (trainer/sft_trainer/trainer.py:132-136 casts the LoRA parameters to fp32).
-GemmNtArgs lora_down_args(const bf16_t* X, long ldx, int M, const bf16_t* w_sp, int nout, int K, int r, float alpha, bf16_t* out, int xk_grp_stride = 0) {
-    GemmNtArgs a;
-    a.X = X; a.ldx = ldx; a.W = w_sp; a.ldw = K; a.M = M; a.N = 2 * nout; a.K = K; a.alpha = alpha;
-    if (xk_grp_stride > 0) { a.xk_grp_n = 2 * r; a.xk_grp_stride = xk_grp_stride; }  // output group g (one adapter) reads X columns g * stride ...
-    a.split_r = r; a.out = out; a.ldo = 3L * nout; a.variant = 8;
-    return a;
-}
-int lora_down(const bf16_t* X, long ldx, int M, const bf16_t* w_sp, int nout, int K, int r, float alpha, bf16_t* out, hipStream_t st,
-              int xk_grp_stride = 0) {
-    return gemm_nt(lora_down_args(X, ldx, M, w_sp, nout, K, r, alpha, out, xk_grp_stride), st);
-}
 // A projection with its LoRA: the down-projection `dn` (writes a.X2) and the GEMM `a` (K-extension over X2) -- one fused launch where the pair is eligible
 // (gemm_nt_lora_fused: FTMI_FUSE_DOWN=1), else the two launches of rounds 1-5.  `fx` = the workspace's row-tile counters + the running expectation of this call.
 struct FuseCtx { int* flags; int expect; };
@@ -159,10 +135,27 @@ AttnArgs attn_args(const ftmi_ltx_config& c, int Sq, int Sk) {
     a.scale = (c.head_dim_valid > 0 && c.head_dim_valid < 64) ? 1.0f / sqrtf((float)c.head_dim_valid) : 0.125f;  // (a zero-padded narrow head: the scale of its true width)
     return a;
 }
-inline void set3(long& sb, long& sh, long& ss, long rows_per_batch, long ld) {
-    sb = rows_per_batch * ld;
-    sh = 64;
-    ss = ld;
+// self-attention over a block slot: q, k, o token rows [B S, D]; v the last D columns of the fused projection qkv [B S, 3D]
+AttnArgs self_attn_args(const ftmi_ltx_config& c, const WsLayout& L, char* blk) {
+    const long D = c.D;
+    AttnArgs a = attn_args(c, c.S, c.S);
+    a.q = W(blk, L.qrot); tok_strides(a.q_sb, a.q_sh, a.q_ss, c.S, D, 64);
+    a.k = W(blk, L.krot); tok_strides(a.k_sb, a.k_sh, a.k_ss, c.S, D, 64);
+    a.v = W(blk, L.qkv) + 2 * D; tok_strides(a.v_sb, a.v_sh, a.v_ss, c.S, 3 * D, 64);
+    a.o = W(blk, L.o1); tok_strides(a.o_sb, a.o_sh, a.o_ss, c.S, D, 64);
+    a.lse2 = WF(blk, L.lse1);
+    return a;
+}
+// cross-attention of block l with the text-mask bias: its keys / values are block l's columns of the all-block arrays [B T, L D] / [B T, L 2D]
+AttnArgs cross_attn_args(const ftmi_ltx_config& c, const WsLayout& L, void* ws, char* blk, int l, const float* key_bias) {
+    const long D = c.D;
+    AttnArgs a = attn_args(c, c.S, c.T);
+    a.q = W(blk, L.q2n); tok_strides(a.q_sb, a.q_sh, a.q_ss, c.S, D, 64);
+    a.k = W(ws, L.k2n_all) + (size_t)l * D; tok_strides(a.k_sb, a.k_sh, a.k_ss, c.T, c.L * D, 64);
+    a.v = W(ws, L.kv2_all) + (size_t)l * 2 * D + D; tok_strides(a.v_sb, a.v_sh, a.v_ss, c.T, c.L * 2 * D, 64);
+    a.o = W(blk, L.o2); tok_strides(a.o_sb, a.o_sh, a.o_ss, c.S, D, 64);
+    a.lse2 = WF(blk, L.lse2); a.kbias = key_bias; a.kb_sb = c.T;
+    return a;
 }
 
 }  // namespace
@@ -209,99 +202,56 @@ static int ltx_block_forward(const ftmi_ltx_config& c, const ftmi_ltx_weights& w
         const bf16_t* lb = w.lora_b_ext ? P(w.lora_b_ext, (size_t)l * 8 * D * 3 * r) : nullptr;  // [8][D][3r]  [B_hi | B_hi | B_lo]
         bf16_t* n1 = W(blk, L.n1);
         bf16_t* qkv = W(blk, L.qkv);
+        // the projection `a` (+ the adapters adp .. adp + nadp - 1 on its input, xa [M, 3 nadp r] kept for the backward)
+        auto proj = [&](GemmNtArgs& a, int adp, int nadp, bf16_t* xa) -> int {
+            if (r <= 0) return gemm_nt(a, st);
+            lora_ext_fwd(a, xa, nadp, r, lb + (size_t)adp * D * 3 * r);
+            return lora_gemm(a, lora_down_args(a.X, a.ldx, M, la + (size_t)adp * 2 * r * D, nadp, D, r, s, xa), fx, st);
+        };
 
         // 1. norm1 + AdaLN modulate
         FTMI_TRY(norm_modulate_fwd(h0, ada + 0 * D, ada + 6 * D, ab, n1, M, mg.rows, D, c.eps_norm, 0, st));
         // 2-3. fused q,k,v projection (+ LoRA)
         {
-            GemmNtArgs a;
-            a.X = n1; a.ldx = D; a.W = P(w.w_qkv, (size_t)l * 3 * D2); a.ldw = D; a.M = M; a.N = 3 * D; a.K = D;
-            a.bias = P(w.b_qkv, (size_t)l * 3 * D); a.out = qkv; a.ldo = 3 * D; a.variant = V;
-            GemmNtArgs dn;
-            if (r > 0) {
-                dn = lora_down_args(n1, D, M, la, 3 * r, D, r, s, W(blk, L.xa_qkv));
-                a.X2 = W(blk, L.xa_qkv); a.ldx2 = 9 * r; a.W2 = lb; a.ldw2 = 3 * r; a.K2 = 3 * r; a.x2_grp_n = D; a.x2_grp_stride = 3 * r;
-            }
-            FTMI_TRY(r > 0 ? lora_gemm(a, dn, fx, st) : gemm_nt(a, st));
+            GemmNtArgs a = linear_args(n1, D, M, P(w.w_qkv, (size_t)l * 3 * D2), D, 3 * D, D, P(w.b_qkv, (size_t)l * 3 * D), qkv, 3 * D, V);
+            FTMI_TRY(proj(a, 0, 3, W(blk, L.xa_qkv)));
         }
         // 4. QK RMSNorm across heads + RoPE
         FTMI_TRY(qknorm_rope_fwd(qkv, 3 * D, P(w.norm_q, (size_t)l * D), w.rope_cos, w.rope_sin, W(blk, L.qrot), D, M, c.S, D, c.eps_qk, st, 1,
                                  qkv + D, P(w.norm_k, (size_t)l * D), W(blk, L.krot)));  // q and k in one launch
         // 5. self-attention
-        {
-            AttnArgs a = attn_args(c, c.S, c.S);
-            a.q = W(blk, L.qrot); set3(a.q_sb, a.q_sh, a.q_ss, c.S, D);
-            a.k = W(blk, L.krot); set3(a.k_sb, a.k_sh, a.k_ss, c.S, D);
-            a.v = qkv + 2 * D;    set3(a.v_sb, a.v_sh, a.v_ss, c.S, 3 * D);
-            a.o = W(blk, L.o1);   set3(a.o_sb, a.o_sh, a.o_ss, c.S, D);
-            a.lse2 = WF(blk, L.lse1);
-            FTMI_TRY(attn_fwd(a, st));
-        }
+        FTMI_TRY(attn_fwd(self_attn_args(c, L, blk), st));
         // 6. to_out (+ LoRA), gate * residual
         {
-            GemmNtArgs a;
-            a.X = W(blk, L.o1); a.ldx = D; a.W = P(w.w_o, (size_t)l * D2); a.ldw = D; a.M = M; a.N = D; a.K = D;
-            a.bias = P(w.b_o, (size_t)l * D); a.out = W(blk, L.h1); a.ldo = D; a.variant = V;
+            GemmNtArgs a = linear_args(W(blk, L.o1), D, M, P(w.w_o, (size_t)l * D2), D, D, D, P(w.b_o, (size_t)l * D), W(blk, L.h1), D, V);
             a.epi = EPI_RESID; a.resid = h0; a.ldr = D; a.gate = ada + 2 * D; a.gate_bstride = ab; a.rows_per_batch = mg.rows;
-            GemmNtArgs dn;
-            if (r > 0) {
-                dn = lora_down_args(W(blk, L.o1), D, M, la + 3L * 2 * r * D, r, D, r, s, W(blk, L.xa_o));
-                a.X2 = W(blk, L.xa_o); a.ldx2 = 3 * r; a.W2 = lb + 3L * D * 3 * r; a.ldw2 = 3 * r; a.K2 = 3 * r;
-            }
-            FTMI_TRY(r > 0 ? lora_gemm(a, dn, fx, st) : gemm_nt(a, st));
+            FTMI_TRY(proj(a, 3, 1, W(blk, L.xa_o)));
         }
         const bf16_t* h1 = W(blk, L.h1);
         // 7. cross-attention query (no pre-norm, no RoPE)
         {
-            GemmNtArgs a;
-            a.X = h1; a.ldx = D; a.W = P(w.w_q2, (size_t)l * D2); a.ldw = D; a.M = M; a.N = D; a.K = D;
-            a.bias = P(w.b_q2, (size_t)l * D); a.out = W(blk, L.q2raw); a.ldo = D; a.variant = V;
-            GemmNtArgs dn;
-            if (r > 0) {
-                dn = lora_down_args(h1, D, M, la + 4L * 2 * r * D, r, D, r, s, W(blk, L.xa_q2));
-                a.X2 = W(blk, L.xa_q2); a.ldx2 = 3 * r; a.W2 = lb + 4L * D * 3 * r; a.ldw2 = 3 * r; a.K2 = 3 * r;
-            }
-            FTMI_TRY(r > 0 ? lora_gemm(a, dn, fx, st) : gemm_nt(a, st));
+            GemmNtArgs a = linear_args(h1, D, M, P(w.w_q2, (size_t)l * D2), D, D, D, P(w.b_q2, (size_t)l * D), W(blk, L.q2raw), D, V);
+            FTMI_TRY(proj(a, 4, 1, W(blk, L.xa_q2)));
             FTMI_TRY(qknorm_rope_fwd(W(blk, L.q2raw), D, P(w.norm_q2, (size_t)l * D), nullptr, nullptr, W(blk, L.q2n), D, M, c.S, D, c.eps_qk, st));
         }
         // 9. cross-attention with the text-mask bias
-        {
-            AttnArgs a = attn_args(c, c.S, c.T);
-            a.q = W(blk, L.q2n);          set3(a.q_sb, a.q_sh, a.q_ss, c.S, D);
-            a.k = W(ws, L.k2n_all) + (size_t)l * D;              set3(a.k_sb, a.k_sh, a.k_ss, c.T, (long)c.L * D);
-            a.v = W(ws, L.kv2_all) + (size_t)l * 2 * D + D;      set3(a.v_sb, a.v_sh, a.v_ss, c.T, (long)c.L * 2 * D);
-            a.o = W(blk, L.o2);           set3(a.o_sb, a.o_sh, a.o_ss, c.S, D);
-            a.lse2 = WF(blk, L.lse2);
-            a.kbias = key_bias; a.kb_sb = c.T;
-            FTMI_TRY(attn_fwd(a, st));
-        }
+        FTMI_TRY(attn_fwd(cross_attn_args(c, L, ws, blk, l, key_bias), st));
         // 10. to_out (+ LoRA), residual (no gate)
         {
-            GemmNtArgs a;
-            a.X = W(blk, L.o2); a.ldx = D; a.W = P(w.w_o2, (size_t)l * D2); a.ldw = D; a.M = M; a.N = D; a.K = D;
-            a.bias = P(w.b_o2, (size_t)l * D); a.out = W(blk, L.h2); a.ldo = D; a.variant = V;
+            GemmNtArgs a = linear_args(W(blk, L.o2), D, M, P(w.w_o2, (size_t)l * D2), D, D, D, P(w.b_o2, (size_t)l * D), W(blk, L.h2), D, V);
             a.epi = EPI_RESID; a.resid = h1; a.ldr = D;
-            GemmNtArgs dn;
-            if (r > 0) {
-                dn = lora_down_args(W(blk, L.o2), D, M, la + 7L * 2 * r * D, r, D, r, s, W(blk, L.xa_o2));
-                a.X2 = W(blk, L.xa_o2); a.ldx2 = 3 * r; a.W2 = lb + 7L * D * 3 * r; a.ldw2 = 3 * r; a.K2 = 3 * r;
-            }
-            FTMI_TRY(r > 0 ? lora_gemm(a, dn, fx, st) : gemm_nt(a, st));
+            FTMI_TRY(proj(a, 7, 1, W(blk, L.xa_o2)));
         }
         const bf16_t* h2 = W(blk, L.h2);
         // 11-13. norm2 + modulate, feed-forward, gate * residual
         FTMI_TRY(norm_modulate_fwd(h2, ada + 3 * D, ada + 7 * D, ab, W(ws, L.s_n2), M, mg.rows, D, c.eps_norm, 0, st));
         {
-            GemmNtArgs a;
-            a.X = W(ws, L.s_n2); a.ldx = D; a.W = P(w.w_ff1, (size_t)l * c.D_ff * D); a.ldw = D; a.M = M; a.N = c.D_ff; a.K = D;
-            a.bias = P(w.b_ff1, (size_t)l * c.D_ff); a.out = W(ws, L.s_g); a.ldo = c.D_ff; a.out2 = W(blk, L.z); a.ldo2 = c.D_ff;
-            a.epi = EPI_GELU; a.variant = V;
+            GemmNtArgs a = linear_args(W(ws, L.s_n2), D, M, P(w.w_ff1, (size_t)l * c.D_ff * D), D, c.D_ff, D, P(w.b_ff1, (size_t)l * c.D_ff), W(ws, L.s_g), c.D_ff, V);
+            a.out2 = W(blk, L.z); a.ldo2 = c.D_ff; a.epi = EPI_GELU;
             FTMI_TRY(gemm_nt(a, st));
         }
         {
-            GemmNtArgs a;
-            a.X = W(ws, L.s_g); a.ldx = c.D_ff; a.W = P(w.w_ff2, (size_t)l * D * c.D_ff); a.ldw = c.D_ff; a.M = M; a.N = D; a.K = c.D_ff;
-            a.bias = P(w.b_ff2, (size_t)l * D); a.out = hout; a.ldo = D; a.variant = V;
+            GemmNtArgs a = linear_args(W(ws, L.s_g), c.D_ff, M, P(w.w_ff2, (size_t)l * D * c.D_ff), c.D_ff, D, c.D_ff, P(w.b_ff2, (size_t)l * D), hout, D, V);
             a.epi = EPI_RESID; a.resid = h2; a.ldr = D; a.gate = ada + 5 * D; a.gate_bstride = ab; a.rows_per_batch = mg.rows;
             FTMI_TRY(gemm_nt(a, st));
         }
@@ -342,27 +292,24 @@ static int ltx_prologue_text(const ftmi_ltx_config& c, const ftmi_ltx_weights& w
     const float s = c.lora_scale;
     // ---- caption projection ----
     {
-        GemmNtArgs a;
-        a.X = text; a.ldx = c.D_cap; a.W = P(w.cap_l1_w, 0); a.ldw = c.D_cap; a.M = Mt; a.N = D; a.K = c.D_cap;
-        a.bias = P(w.cap_l1_b, 0); a.out = W(ws, L.cap_h); a.ldo = D; a.epi = EPI_GELU; a.variant = V;
+        GemmNtArgs a = linear_args(text, c.D_cap, Mt, P(w.cap_l1_w, 0), c.D_cap, D, c.D_cap, P(w.cap_l1_b, 0), W(ws, L.cap_h), D, V);
+        a.epi = EPI_GELU;
         FTMI_TRY(gemm_nt(a, st));
-        FTMI_TRY(linear(W(ws, L.cap_h), D, Mt, P(w.cap_l2_w, 0), D, D, D, P(w.cap_l2_b, 0), W(ws, L.e), D, V, st));
+        FTMI_TRY(gemm_nt(linear_args(W(ws, L.cap_h), D, Mt, P(w.cap_l2_w, 0), D, D, D, P(w.cap_l2_b, 0), W(ws, L.e), D, V), st));
     }
     const bf16_t* e = W(ws, L.e);
 
     // ---- cross-attention keys/values of EVERY block (the text stream does not change across blocks) ----
     {
-        const long ldkv = (long)c.L * 2 * D;
-        GemmNtArgs a;
-        a.X = e; a.ldx = D; a.W = P(w.w_kv2, 0); a.ldw = D; a.M = Mt; a.N = c.L * 2 * D; a.K = D;
-        a.bias = P(w.b_kv2, 0); a.out = W(ws, L.kv2_all); a.ldo = ldkv; a.variant = V;
+        // the k | v adapters of all L blocks as 2L adapters on the one input e
+        GemmNtArgs a = linear_args(e, D, Mt, P(w.w_kv2, 0), D, c.L * 2 * D, D, P(w.b_kv2, 0), W(ws, L.kv2_all), (long)c.L * 2 * D, V);
         if (r > 0) {
-            GemmNtArgs x;  // XA[:, (l,k|v)] = s * e A_{l,k|v}^T : adapters 5,6 of block l are 2 * 2r consecutive plane rows, blocks 8 * 2r * D apart
-            x.X = e; x.ldx = D; x.W = P(w.lora_a_sp, 5L * 2 * r * D); x.ldw = D; x.w_grp_n = 4 * r; x.w_grp_stride = 16L * r * D;
-            x.M = Mt; x.N = c.L * 4 * r; x.K = D; x.alpha = s; x.split_r = r; x.out = W(ws, L.xa_kv2_all); x.ldo = (long)c.L * 6 * r; x.variant = V;
+            // XA[:, (l,k|v)] = s * e A_{l,k|v}^T : adapters 5,6 of block l are 2 * 2r consecutive plane rows, blocks 8 * 2r * D apart
+            GemmNtArgs x = lora_down_args(e, D, Mt, P(w.lora_a_sp, 5L * 2 * r * D), 2 * c.L, D, r, s, W(ws, L.xa_kv2_all));
+            x.w_grp_n = 4 * r; x.w_grp_stride = 16L * r * D; x.variant = V;
             FTMI_TRY(gemm_nt(x, st));
-            a.X2 = W(ws, L.xa_kv2_all); a.ldx2 = (long)c.L * 6 * r; a.x2_grp_n = D; a.x2_grp_stride = 3 * r; a.K2 = 3 * r;
-            a.W2 = P(w.lora_b_ext, 5L * D * 3 * r); a.ldw2 = 3 * r; a.w2_grp_n = 2 * D; a.w2_grp_stride = 8L * D * 3 * r;
+            lora_ext_fwd(a, W(ws, L.xa_kv2_all), 2 * c.L, r, P(w.lora_b_ext, 5L * D * 3 * r));
+            a.w2_grp_n = 2 * D; a.w2_grp_stride = 8L * D * 3 * r;
         }
         FTMI_TRY(gemm_nt(a, st));
         // k2 = norm_k(k2raw): rows ordered (token, block): row i = t * L + l reads kv2_all + i * 2D, weight row l
@@ -373,7 +320,7 @@ static int ltx_prologue_text(const ftmi_ltx_config& c, const ftmi_ltx_weights& w
 }
 
 static int ltx_proj_in(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const WsLayout& L, void* ws, const bf16_t* x_t, hipStream_t st) {
-    return linear(x_t, c.C_in, c.B * c.S, P(w.proj_in_w, 0), c.C_in, c.D, c.C_in, P(w.proj_in_b, 0), W(ws, L.hs), c.D, c.gemm_variant, st);
+    return gemm_nt(linear_args(x_t, c.C_in, c.B * c.S, P(w.proj_in_w, 0), c.C_in, c.D, c.C_in, P(w.proj_in_b, 0), W(ws, L.hs), c.D, c.gemm_variant), st);
 }
 
 // The block stack and the tail (LayerNorm + modulate + proj_out) over a prepared workspace: hs[0], the conditioning and the text-side k|v are in place.
@@ -388,7 +335,7 @@ static int ltx_blocks_tail(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, 
     const bf16_t* hL = W(ws, L.hs) + (size_t)c.L * M * D;
     const bf16_t* ao = W(ws, L.ada_out);
     FTMI_TRY(norm_modulate_fwd(hL, ao, ao + 2 * D, 3L * D, W(ws, L.s_ln), M, mg.rows, D, c.eps_norm, 1, st));
-    FTMI_TRY(linear(W(ws, L.s_ln), D, M, P(w.proj_out_w, 0), D, c.C_out, D, P(w.proj_out_b, 0), pred, c.C_out, V, st));
+    FTMI_TRY(gemm_nt(linear_args(W(ws, L.s_ln), D, M, P(w.proj_out_w, 0), D, c.C_out, D, P(w.proj_out_b, 0), pred, c.C_out, V), st));
     return 0;
 }
 
@@ -599,7 +546,7 @@ int ltx_backward_range(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, cons
 
     // ---- tail ----
     if (l_hi == c.L) {
-        FTMI_TRY(linear(dpred, c.C_out, M, P(w.proj_out_w_t, 0), c.C_out, D, c.C_out, nullptr, d1, D, V, st));
+        FTMI_TRY(gemm_nt(linear_args(dpred, c.C_out, M, P(w.proj_out_w_t, 0), c.C_out, D, c.C_out, nullptr, d1, D, V), st));
         const bf16_t* hL = W(ws, L.hs) + (size_t)c.L * M * D;
         const bf16_t* ao = W(ws, L.ada_out);
         // the gated copy bf(dh * gate_mlp) that opens the last block's backward is written by the same kernel (into dO, idle here)
@@ -613,7 +560,7 @@ int ltx_backward_range(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, cons
     // blocks of one adapter are reduced by ONE batched launch after the loop (fills the GPU instead of 28 latency-bound ones).
     auto lora_dxa = [&](const bf16_t* dY, long lddy, int rows, int nadp, int adp, int l, bf16_t* dxa_out) -> GemmNtArgs {
         const bf16_t* lbt = P(w.lora_bt_sp, ((size_t)l * 8 + adp) * 2 * r * D);  // [nadp * 2r][D]: (hi, lo) planes of B^T
-        return lora_down_args(dY, lddy, rows, lbt, nadp * r, D, r, s, dxa_out, nadp > 1 ? D : 0);
+        return lora_down_args(dY, lddy, rows, lbt, nadp, D, r, s, dxa_out, nadp > 1 ? D : 0);
     };
     FuseCtx fx{reinterpret_cast<int*>(reinterpret_cast<char*>(ws) + L.sk_flags), 0};  // row-tile counters of the fused down-projection + GEMM launches of this call
     if (r > 0 && hipMemsetAsync(fx.flags, 0, 4096, st) != hipSuccess) return set_error(FTMI_ERR_LAUNCH, "ltx_backward: memset of the row-tile counters failed");
@@ -633,17 +580,11 @@ int ltx_backward_range(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, cons
         float* ga = grad_a + (size_t)l0 * 8 * r * D;
         float* gb = grad_b + (size_t)l0 * 8 * D * r;
         for (const G& gr : groups) {
-            GemmTnArgs t;  // dB[l] += dY[l]^T XA[l]
-            t.U = W(blk0, gr.dy); t.ldu = gr.lddy; t.V = W(blk0, gr.xa); t.ldv = (long)gr.nadp * 3 * r; t.v_fold = r;  // XA = hi + lo planes
-            t.C = gb + (size_t)gr.adp * D * r; t.ldc = r; t.M = gr.rows; t.P = gr.nadp * D; t.Q = r;
-            if (gr.nadp > 1) { t.v_grp_p = D; t.v_grp_stride = 3 * r; }
-            t.batch = nb; t.u_bstride = bs; t.v_bstride = bs; t.c_bstride = 8L * D * r;
+            GemmTnArgs t = lora_db_args(W(blk0, gr.dy), gr.lddy, W(blk0, gr.xa), gr.nadp, r, D, gb + (size_t)gr.adp * D * r, gr.rows);  // dB[l] += dY[l]^T XA[l]
+            tn_batch(t, nb, bs, bs, 8L * D * r);
             FTMI_TRY(gemm_tn(t, s2));
-            GemmTnArgs u;  // dA[l] += dXA[l]^T X[l]
-            u.U = W(blk0, gr.dxa); u.ldu = (long)gr.nadp * 3 * r; u.u_fold = r; u.V = gr.x; u.ldv = gr.ldx;
-            if (gr.nadp > 1) { u.u_grp_p = r; u.u_grp_stride = 3 * r; }
-            u.C = ga + (size_t)gr.adp * r * D; u.ldc = D; u.M = gr.rows; u.P = gr.nadp * r; u.Q = D;
-            u.batch = nb; u.u_bstride = bs; u.v_bstride = gr.x_bs; u.c_bstride = 8L * r * D;
+            GemmTnArgs u = lora_da_args(W(blk0, gr.dxa), gr.nadp, r, gr.x, gr.ldx, D, ga + (size_t)gr.adp * r * D, gr.rows);  // dA[l] += dXA[l]^T X[l]
+            tn_batch(u, nb, bs, gr.x_bs, 8L * r * D);
             FTMI_TRY(gemm_tn(u, s2));
         }
         return 0;
@@ -657,84 +598,71 @@ int ltx_backward_range(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, cons
         const bf16_t* h1 = W(blk, L.h1);
         const bf16_t* h2 = W(blk, L.h2);
         const bf16_t* dhin = dh[cur];
+        // the input gradient `a` of a projection (a.X = dY) + dXA A of its adapters adp .. adp + nadp - 1, at_ext [D, 3 nadp r]; dxa is kept for dA
+        auto proj_bwd = [&](GemmNtArgs& a, int adp, int nadp, bf16_t* dxa, const bf16_t* at_ext) -> int {
+            if (r <= 0) return gemm_nt(a, st);
+            lora_ext_bwd(a, dxa, nadp, r, at_ext, 3L * nadp * r);
+            return lora_gemm(a, lora_dxa(a.X, a.ldx, M, nadp, adp, l, dxa), fx, st);
+        };
         if (c.checkpoint) FTMI_TRY(ltx_block_forward(c, w, L, ws, l, key_bias, st, fx, ModGroups{c.B, c.S}));  // the block's activations again, into the one slot
 
         // ---- feed-forward ----
         // (dO holds bf(dhin * gate_mlp): written by the kernel that produced dhin)
         {
-            GemmNtArgs a;
-            a.X = dO; a.ldx = D; a.W = P(w.w_ff2_t, (size_t)l * c.D_ff * D); a.ldw = D; a.M = M; a.N = c.D_ff; a.K = D;
-            a.out = W(ws, L.s_dbig); a.ldo = c.D_ff; a.epi = EPI_DGELU; a.aux = W(blk, L.z); a.ldaux = c.D_ff; a.variant = V;
+            GemmNtArgs a = linear_args(dO, D, M, P(w.w_ff2_t, (size_t)l * c.D_ff * D), D, c.D_ff, D, nullptr, W(ws, L.s_dbig), c.D_ff, V);
+            a.epi = EPI_DGELU; a.aux = W(blk, L.z); a.ldaux = c.D_ff;
             FTMI_TRY(gemm_nt(a, st));
         }
-        FTMI_TRY(linear(W(ws, L.s_dbig), c.D_ff, M, P(w.w_ff1_t, (size_t)l * D * c.D_ff), c.D_ff, D, c.D_ff, nullptr, d2, D, V, st));
+        FTMI_TRY(gemm_nt(linear_args(W(ws, L.s_dbig), c.D_ff, M, P(w.w_ff1_t, (size_t)l * D * c.D_ff), c.D_ff, D, c.D_ff, nullptr, d2, D, V), st));
         bf16_t* d3 = W(blk, L.g_o2);  // dh2: also the dY of attn2.to_out
         FTMI_TRY(norm_modulate_bwd(h2, d2, ada + 7 * D, ab, dhin, d3, M, c.S, D, c.eps_norm, 0, st));
 
         // ---- cross-attention ----
         {
-            GemmNtArgs a;
-            a.X = d3; a.ldx = D; a.W = P(w.w_o2_t, (size_t)l * D2); a.ldw = D; a.M = M; a.N = D; a.K = D; a.out = d1; a.ldo = D; a.variant = V;
-            if (r > 0) { a.X2 = W(blk, L.dxa_o2); a.ldx2 = 3 * r; a.W2 = lat + 7L * D * 3 * r; a.ldw2 = 3 * r; a.K2 = 3 * r; }
-            FTMI_TRY(r > 0 ? lora_gemm(a, lora_dxa(d3, D, M, 1, 7, l, W(blk, L.dxa_o2)), fx, st) : gemm_nt(a, st));  // d1 = dO2
+            GemmNtArgs a = linear_args(d3, D, M, P(w.w_o2_t, (size_t)l * D2), D, D, D, nullptr, d1, D, V);
+            FTMI_TRY(proj_bwd(a, 7, 1, W(blk, L.dxa_o2), lat + 7L * D * 3 * r));  // d1 = dO2
         }
         {
-            AttnArgs a = attn_args(c, c.S, c.T);
-            a.q = W(blk, L.q2n);          set3(a.q_sb, a.q_sh, a.q_ss, c.S, D);
-            a.k = W(ws, L.k2n_all) + (size_t)l * D;              set3(a.k_sb, a.k_sh, a.k_ss, c.T, (long)c.L * D);
-            a.v = W(ws, L.kv2_all) + (size_t)l * 2 * D + D;      set3(a.v_sb, a.v_sh, a.v_ss, c.T, (long)c.L * 2 * D);
-            a.o = W(blk, L.o2);           set3(a.o_sb, a.o_sh, a.o_ss, c.S, D);
-            a.lse2 = WF(blk, L.lse2); a.kbias = key_bias; a.kb_sb = c.T;
-            a.dout = d1;                  set3(a.do_sb, a.do_sh, a.do_ss, c.S, D);
+            AttnArgs a = cross_attn_args(c, L, ws, blk, l, key_bias);
+            a.dout = d1;                  tok_strides(a.do_sb, a.do_sh, a.do_ss, c.S, D, 64);
             a.delta = WF(ws, L.s_delta);
-            a.dq = d2;                    set3(a.dq_sb, a.dq_sh, a.dq_ss, c.S, D);
-            a.dk = W(ws, L.g_k2n_all) + (size_t)l * D;            set3(a.dk_sb, a.dk_sh, a.dk_ss, c.T, (long)c.L * D);
-            a.dv = W(ws, L.g_kv2_all) + (size_t)l * 2 * D + D;    set3(a.dv_sb, a.dv_sh, a.dv_ss, c.T, (long)c.L * 2 * D);
+            a.dq = d2;                    tok_strides(a.dq_sb, a.dq_sh, a.dq_ss, c.S, D, 64);
+            a.dk = W(ws, L.g_k2n_all) + (size_t)l * D;            tok_strides(a.dk_sb, a.dk_sh, a.dk_ss, c.T, (long)c.L * D, 64);
+            a.dv = W(ws, L.g_kv2_all) + (size_t)l * 2 * D + D;    tok_strides(a.dv_sb, a.dv_sh, a.dv_ss, c.T, (long)c.L * 2 * D, 64);
             FTMI_TRY(attn_bwd(a, st));
         }
         bf16_t* gq2 = W(blk, L.g_q2);  // dq2raw
         FTMI_TRY(qknorm_rope_bwd(W(blk, L.q2raw), D, P(w.norm_q2, (size_t)l * D), nullptr, nullptr, d2, D, gq2, D, M, c.S, D, c.eps_qk, st));
         {
-            GemmNtArgs a;
-            a.X = gq2; a.ldx = D; a.W = P(w.w_q2_t, (size_t)l * D2); a.ldw = D; a.M = M; a.N = D; a.K = D; a.out = d2; a.ldo = D; a.variant = V;
+            GemmNtArgs a = linear_args(gq2, D, M, P(w.w_q2_t, (size_t)l * D2), D, D, D, nullptr, d2, D, V);
             a.epi = EPI_RESID; a.resid = d3; a.ldr = D;
             a.out2 = W(blk, L.g_o); a.ldo2 = D; a.gate2 = ada + 2 * D; a.gate2_bstride = ab; a.rows_per_batch = c.S;  // go = bf(dh1 * gate_msa), fused
-            if (r > 0) { a.X2 = W(blk, L.dxa_q2); a.ldx2 = 3 * r; a.W2 = lat + 4L * D * 3 * r; a.ldw2 = 3 * r; a.K2 = 3 * r; }
-            FTMI_TRY(r > 0 ? lora_gemm(a, lora_dxa(gq2, D, M, 1, 4, l, W(blk, L.dxa_q2)), fx, st) : gemm_nt(a, st));  // d2 = dh1
+            FTMI_TRY(proj_bwd(a, 4, 1, W(blk, L.dxa_q2), lat + 4L * D * 3 * r));  // d2 = dh1
         }
 
         // ---- self-attention ----
         bf16_t* go = W(blk, L.g_o);  // d(attn1.to_out output)
         {
-            GemmNtArgs a;
-            a.X = go; a.ldx = D; a.W = P(w.w_o_t, (size_t)l * D2); a.ldw = D; a.M = M; a.N = D; a.K = D; a.out = dO; a.ldo = D; a.variant = V;
-            if (r > 0) { a.X2 = W(blk, L.dxa_o); a.ldx2 = 3 * r; a.W2 = lat + 3L * D * 3 * r; a.ldw2 = 3 * r; a.K2 = 3 * r; }
-            FTMI_TRY(r > 0 ? lora_gemm(a, lora_dxa(go, D, M, 1, 3, l, W(blk, L.dxa_o)), fx, st) : gemm_nt(a, st));
+            GemmNtArgs a = linear_args(go, D, M, P(w.w_o_t, (size_t)l * D2), D, D, D, nullptr, dO, D, V);
+            FTMI_TRY(proj_bwd(a, 3, 1, W(blk, L.dxa_o), lat + 3L * D * 3 * r));
         }
         bf16_t* dqkv = W(blk, L.g_qkv);
         const bf16_t* qkv = W(blk, L.qkv);
         {
-            AttnArgs a = attn_args(c, c.S, c.S);
-            a.q = W(blk, L.qrot); set3(a.q_sb, a.q_sh, a.q_ss, c.S, D);
-            a.k = W(blk, L.krot); set3(a.k_sb, a.k_sh, a.k_ss, c.S, D);
-            a.v = qkv + 2 * D;    set3(a.v_sb, a.v_sh, a.v_ss, c.S, 3 * D);
-            a.o = W(blk, L.o1);   set3(a.o_sb, a.o_sh, a.o_ss, c.S, D);
-            a.lse2 = WF(blk, L.lse1);
-            a.dout = dO;          set3(a.do_sb, a.do_sh, a.do_ss, c.S, D);
+            AttnArgs a = self_attn_args(c, L, blk);
+            a.dout = dO;          tok_strides(a.do_sb, a.do_sh, a.do_ss, c.S, D, 64);
             a.delta = WF(ws, L.s_delta);
-            a.dq = W(ws, L.s_dqr); set3(a.dq_sb, a.dq_sh, a.dq_ss, c.S, D);
-            a.dk = W(ws, L.s_dkr); set3(a.dk_sb, a.dk_sh, a.dk_ss, c.S, D);
-            a.dv = dqkv + 2 * D;   set3(a.dv_sb, a.dv_sh, a.dv_ss, c.S, 3 * D);
+            a.dq = W(ws, L.s_dqr); tok_strides(a.dq_sb, a.dq_sh, a.dq_ss, c.S, D, 64);
+            a.dk = W(ws, L.s_dkr); tok_strides(a.dk_sb, a.dk_sh, a.dk_ss, c.S, D, 64);
+            a.dv = dqkv + 2 * D;   tok_strides(a.dv_sb, a.dv_sh, a.dv_ss, c.S, 3 * D, 64);
             FTMI_TRY(attn_bwd(a, st));
         }
         FTMI_TRY(qknorm_rope_bwd(qkv, 3 * D, P(w.norm_q, (size_t)l * D), w.rope_cos, w.rope_sin, W(ws, L.s_dqr), D, dqkv, 3 * D, M, c.S, D, c.eps_qk, st, 1,
                                  qkv + D, P(w.norm_k, (size_t)l * D), W(ws, L.s_dkr), dqkv + D));  // q and k in one launch
         if (r > 0 && l == 0) FTMI_TRY(gemm_nt(lora_dxa(dqkv, 3 * D, M, 3, 0, l, W(blk, L.dxa_qkv)), st));  // (block 0 has no input gradient: the dXA alone, for dA)
         if (l > 0) {
-            GemmNtArgs a;
-            a.X = dqkv; a.ldx = 3 * D; a.W = P(w.w_qkv_t, (size_t)l * 3 * D2); a.ldw = 3 * D; a.M = M; a.N = D; a.K = 3 * D; a.out = d1; a.ldo = D; a.variant = V;
-            if (r > 0) { a.X2 = W(blk, L.dxa_qkv); a.ldx2 = 9 * r; a.W2 = P(w.lora_at_qkv_ext, (size_t)l * D * 9 * r); a.ldw2 = 9 * r; a.K2 = 9 * r; }
-            FTMI_TRY(r > 0 ? lora_gemm(a, lora_dxa(dqkv, 3 * D, M, 3, 0, l, W(blk, L.dxa_qkv)), fx, st) : gemm_nt(a, st));  // d1 = dn1
+            GemmNtArgs a = linear_args(dqkv, 3 * D, M, P(w.w_qkv_t, (size_t)l * 3 * D2), 3 * D, D, 3 * D, nullptr, d1, D, V);
+            FTMI_TRY(proj_bwd(a, 0, 3, W(blk, L.dxa_qkv), P(w.lora_at_qkv_ext, (size_t)l * D * 9 * r)));  // d1 = dn1
             const bf16_t* ada_prev = W(ws, L.ada) + (size_t)(l - 1) * c.B * 8 * D;  // the next block processed is l - 1
             FTMI_TRY(norm_modulate_bwd(h0, d1, ada + 6 * D, ab, d2, dh[cur ^ 1], M, c.S, D, c.eps_norm, 0, st, ada_prev + 5 * D, ab, dO));
             cur ^= 1;
@@ -751,25 +679,25 @@ int ltx_backward_range(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, cons
         FTMI_TRY(qknorm_rope_bwd(W(ws, L.kv2_all) + (size_t)l_lo * 2 * D, 2 * D, P(w.norm_k2, (size_t)l_lo * D), nullptr, nullptr,
                                  W(ws, L.g_k2n_all) + (size_t)l_lo * D, D, W(ws, L.g_kv2_all) + (size_t)l_lo * 2 * D, 2 * D,
                                  Mt * nb, Mt * nb, D, c.eps_qk, st, nb, nullptr, nullptr, nullptr, nullptr, nb, c.L));
-        GemmNtArgs a;  // dXA[:, (l,k|v)] = s * dY[:, (l,k|v) slice] B_{l,k|v}
-        a.X = W(ws, L.g_kv2_all) + (size_t)l_lo * 2 * D; a.ldx = (long)c.L * 2 * D; a.xk_grp_n = 2 * r; a.xk_grp_stride = D;
-        a.W = P(w.lora_bt_sp, ((size_t)l_lo * 8 + 5) * 2 * r * D); a.ldw = D; a.w_grp_n = 4 * r; a.w_grp_stride = 16L * r * D;
-        a.M = Mt; a.N = nb * 4 * r; a.K = D; a.alpha = s; a.split_r = r; a.out = W(ws, L.dxa_kv2_all) + (size_t)l_lo * 6 * r; a.ldo = (long)c.L * 6 * r; a.variant = V;
+        // dXA[:, (l,k|v)] = s * dY[:, (l,k|v) slice] B_{l,k|v}: the 2 nb adapters of this range, written into their columns of the all-block array
+        GemmNtArgs a = lora_down_args(W(ws, L.g_kv2_all) + (size_t)l_lo * 2 * D, (long)c.L * 2 * D, Mt, P(w.lora_bt_sp, ((size_t)l_lo * 8 + 5) * 2 * r * D), 2 * nb, D, r, s,
+                                      W(ws, L.dxa_kv2_all) + (size_t)l_lo * 6 * r, D);
+        a.w_grp_n = 4 * r; a.w_grp_stride = 16L * r * D; a.ldo = (long)c.L * 6 * r; a.variant = V;
         FTMI_TRY(gemm_nt(a, st));
     }
 
     // ---- LoRA weight gradients of the text-side adapters (all blocks in one launch each) ----
     if (r > 0) {
         {   // attn2.to_k / to_v: operands are column slices of the all-block arrays (batch stride = one block's columns)
-            GemmTnArgs t;
-            t.U = W(ws, L.g_kv2_all) + (size_t)l_lo * 2 * D; t.ldu = (long)c.L * 2 * D; t.V = W(ws, L.xa_kv2_all) + (size_t)l_lo * 6 * r; t.ldv = (long)c.L * 6 * r; t.v_fold = r;
-            t.C = grad_b + ((size_t)l_lo * 8 + 5) * D * r; t.ldc = r; t.M = Mt; t.P = 2 * D; t.Q = r; t.v_grp_p = D; t.v_grp_stride = 3 * r;
-            t.batch = nb; t.u_bstride = 2L * D; t.v_bstride = 6L * r; t.c_bstride = 8L * D * r;
+            const long ldxa = (long)c.L * 6 * r;
+            GemmTnArgs t = lora_db_args(W(ws, L.g_kv2_all) + (size_t)l_lo * 2 * D, (long)c.L * 2 * D, W(ws, L.xa_kv2_all) + (size_t)l_lo * 6 * r, 2, r, D,
+                                        grad_b + ((size_t)l_lo * 8 + 5) * D * r, Mt);
+            t.ldv = ldxa;
+            tn_batch(t, nb, 2L * D, 6L * r, 8L * D * r);
             FTMI_TRY(gemm_tn(t, st));
-            GemmTnArgs u;
-            u.U = W(ws, L.dxa_kv2_all) + (size_t)l_lo * 6 * r; u.ldu = (long)c.L * 6 * r; u.u_fold = r; u.u_grp_p = r; u.u_grp_stride = 3 * r; u.V = e; u.ldv = D;
-            u.C = grad_a + ((size_t)l_lo * 8 + 5) * r * D; u.ldc = D; u.M = Mt; u.P = 2 * r; u.Q = D;
-            u.batch = nb; u.u_bstride = 6L * r; u.v_bstride = 0; u.c_bstride = 8L * r * D;
+            GemmTnArgs u = lora_da_args(W(ws, L.dxa_kv2_all) + (size_t)l_lo * 6 * r, 2, r, e, D, D, grad_a + ((size_t)l_lo * 8 + 5) * r * D, Mt);
+            u.ldu = ldxa;
+            tn_batch(u, nb, 6L * r, 0, 8L * r * D);
             FTMI_TRY(gemm_tn(u, st));
         }
     }

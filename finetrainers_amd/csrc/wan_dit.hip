@@ -45,6 +45,7 @@
 // which its backward needs for rowsum(dO o O)).
 #include "common.hip.h"
 #include "kernels.h"
+#include "lora_proj.hip.h"
 
 namespace ftmi {
 
@@ -258,54 +259,42 @@ WanRowArgs row_args(const bf16_t* x, long ldx, bf16_t* y, long ldy, int rows, in
     a.x = x; a.ld_x = ldx; a.y = y; a.ld_y = ldy; a.rows = rows; a.D = D; a.rows_per_batch = rpb; a.eps = eps;
     return a;
 }
-inline void tok_strides(long& sb, long& sh, long& ss, long rows_per_batch, long ld) {
-    sb = rows_per_batch * ld;
-    sh = 128;
-    ss = ld;
-}
 // q, k, o: token rows [B S, D]; v: the last D columns of the fused projection v_base [B Sk, ld_v]
 AttnArgs attn_args(const ftmi_wan_block_config& c, const bf16_t* q, const bf16_t* k, const bf16_t* v_base, long ld_v, bf16_t* o, float* lse, int Sq, int Sk) {
     AttnArgs a;
     a.B = c.B; a.H = c.H; a.Sq = Sq; a.Sk = Sk; a.d = 128;
     a.scale = 0.08838834764831845f;  // 1 / sqrt(128)
-    a.q = q; tok_strides(a.q_sb, a.q_sh, a.q_ss, Sq, c.D);
-    a.k = k; tok_strides(a.k_sb, a.k_sh, a.k_ss, Sk, c.D);
-    a.v = v_base + (ld_v - c.D); tok_strides(a.v_sb, a.v_sh, a.v_ss, Sk, ld_v);
-    a.o = o; tok_strides(a.o_sb, a.o_sh, a.o_ss, Sq, c.D);
+    a.q = q; tok_strides(a.q_sb, a.q_sh, a.q_ss, Sq, c.D, 128);
+    a.k = k; tok_strides(a.k_sb, a.k_sh, a.k_ss, Sk, c.D, 128);
+    a.v = v_base + (ld_v - c.D); tok_strides(a.v_sb, a.v_sh, a.v_ss, Sk, ld_v, 128);
+    a.o = o; tok_strides(a.o_sb, a.o_sh, a.o_ss, Sq, c.D, 128);
     a.lse2 = lse;
     return a;
 }
 // the backward's fields on top: dv goes where v sits in its fused projection, into dv_base
 AttnArgs attn_bwd_args(AttnArgs a, const bf16_t* dout, bf16_t* dq, bf16_t* dk, bf16_t* dv_base, float* delta) {
     const long D = a.q_ss, ld_v = a.v_ss;
-    a.dout = dout; tok_strides(a.do_sb, a.do_sh, a.do_ss, a.Sq, D);
-    a.dq = dq; tok_strides(a.dq_sb, a.dq_sh, a.dq_ss, a.Sq, D);
-    a.dk = dk; tok_strides(a.dk_sb, a.dk_sh, a.dk_ss, a.Sk, D);
-    a.dv = dv_base + (ld_v - D); tok_strides(a.dv_sb, a.dv_sh, a.dv_ss, a.Sk, ld_v);
+    a.dout = dout; tok_strides(a.do_sb, a.do_sh, a.do_ss, a.Sq, D, 128);
+    a.dq = dq; tok_strides(a.dq_sb, a.dq_sh, a.dq_ss, a.Sq, D, 128);
+    a.dk = dk; tok_strides(a.dk_sb, a.dk_sh, a.dk_ss, a.Sk, D, 128);
+    a.dv = dv_base + (ld_v - D); tok_strides(a.dv_sb, a.dv_sh, a.dv_ss, a.Sk, ld_v, 128);
     a.delta = delta;
     return a;
 }
 
-// s * X A^T (or s * dY B) of `nadp` adjacent adapters as ONE split down-projection: out [rows, 3 nadp r]; X columns step by xk_stride per adapter (0: shared input)
+// s * X A^T (or s * dY B) of the adapters adp .. adp + nadp - 1 as ONE split down-projection: out [rows, 3 nadp r]
 int lora_down(const LoraOps& lo, const bf16_t* X, long ldx, int rows, int D, int adp, int nadp, long xk_stride, bf16_t* out, hipStream_t st) {
-    const int r = lo.r;
-    GemmNtArgs d;
-    d.X = X; d.ldx = ldx; d.W = lo.sp + (size_t)adp * 2 * r * D; d.ldw = D; d.M = rows; d.N = 2 * nadp * r; d.K = D; d.alpha = lo.s; d.split_r = r;
-    if (xk_stride > 0) { d.xk_grp_n = 2 * r; d.xk_grp_stride = xk_stride; }
-    d.out = out; d.ldo = 3L * nadp * r; d.variant = 8;
-    return gemm_nt(d, st);
+    return gemm_nt(lora_down_args(X, ldx, rows, lo.sp + (size_t)adp * 2 * lo.r * D, nadp, D, lo.r, lo.s, out, xk_stride), st);
 }
 
 // out [rows, N] = X W^T + bias, X [rows, K].  nadp > 0 (then N = nadp K): + the adapters adp .. adp + nadp - 1 on the same input when the call has any;
 // xa [rows, 3 nadp r] is kept for the backward
 int proj_fwd(const Block& k, const bf16_t* X, int rows, int K, const bf16_t* Wm, const bf16_t* bias, int N, int adp, int nadp, bf16_t* xa, bf16_t* out) {
     const int r = nadp > 0 ? k.lo.r : 0;
-    GemmNtArgs a;
-    a.X = X; a.ldx = K; a.W = Wm; a.ldw = K; a.M = rows; a.N = N; a.K = K; a.bias = bias; a.out = out; a.ldo = N; a.variant = k.c.gemm_variant;
+    GemmNtArgs a = linear_args(X, K, rows, Wm, K, N, K, bias, out, N, k.c.gemm_variant);
     if (r > 0) {
         FTMI_TRY(lora_down(k.lo, X, K, rows, K, adp, nadp, 0, xa, k.st));
-        a.X2 = xa; a.ldx2 = 3L * nadp * r; a.W2 = k.lo.ext + (size_t)adp * K * 3 * r; a.ldw2 = 3 * r; a.K2 = 3 * r;
-        if (nadp > 1) { a.x2_grp_n = K; a.x2_grp_stride = 3 * r; }
+        lora_ext_fwd(a, xa, nadp, r, k.lo.ext + (size_t)adp * K * 3 * r);
     }
     return gemm_nt(a, k.st);
 }
@@ -319,20 +308,13 @@ int proj_bwd(const Block& k, const bf16_t* X, const bf16_t* dy, int rows, int N,
     FTMI_TRY(linear_grads(dy, N, X, K, rows, N, K, gw, gb, k.st));
     if (r > 0) FTMI_TRY(lora_down(k.lo, dy, N, rows, K, adp, nadp, nadp > 1 ? K : 0, dxa, k.st));
     if (dx) {
-        GemmNtArgs a;
-        a.X = dy; a.ldx = N; a.W = Wt; a.ldw = N; a.M = rows; a.N = K; a.K = N; a.out = dx; a.ldo = K; a.variant = k.c.gemm_variant;
-        if (r > 0) { a.X2 = dxa; a.ldx2 = 3L * nadp * r; a.W2 = k.lo.ext + (size_t)adp * 3 * r; a.ldw2 = 24L * r; a.K2 = 3 * nadp * r; }
+        GemmNtArgs a = linear_args(dy, N, rows, Wt, N, K, N, nullptr, dx, K, k.c.gemm_variant);
+        if (r > 0) lora_ext_bwd(a, dxa, nadp, r, k.lo.ext + (size_t)adp * 3 * r, 24L * r);
         FTMI_TRY(gemm_nt(a, k.st));
     }
-    if (r > 0) {
-        GemmTnArgs t;  // dB += dY^T XA   (XA = hi + lo planes)
-        t.U = dy; t.ldu = N; t.V = xa; t.ldv = 3L * nadp * r; t.v_fold = r; t.C = k.grad_b + (size_t)adp * K * r; t.ldc = r; t.M = rows; t.P = N; t.Q = r;
-        if (nadp > 1) { t.v_grp_p = K; t.v_grp_stride = 3 * r; }
-        FTMI_TRY(gemm_tn(t, k.st));
-        GemmTnArgs u;  // dA += dXA^T X
-        u.U = dxa; u.ldu = 3L * nadp * r; u.u_fold = r; u.V = X; u.ldv = K; u.C = k.grad_a + (size_t)adp * r * K; u.ldc = K; u.M = rows; u.P = nadp * r; u.Q = K;
-        if (nadp > 1) { u.u_grp_p = r; u.u_grp_stride = 3 * r; }
-        FTMI_TRY(gemm_tn(u, k.st));
+    if (r > 0) {  // (an adapted projection has N = nadp K)
+        FTMI_TRY(gemm_tn(lora_db_args(dy, N, xa, nadp, r, K, k.grad_b + (size_t)adp * K * r, rows), k.st));
+        FTMI_TRY(gemm_tn(lora_da_args(dxa, nadp, r, X, K, K, k.grad_a + (size_t)adp * r * K, rows), k.st));
     }
     return 0;
 }
