@@ -148,6 +148,18 @@ class WanLoraBlockWeights(Structure):
     _fields_ = [(n, c_void_p) for n in WAN_LORA_WEIGHT_FIELDS]
 
 
+class WanLoraFfnBlockConfig(Structure):
+    """include/ftmi355.h: ftmi_wan_lora_ffn_block_config."""
+
+    _fields_ = WanI2VLoraBlockConfig._fields_ + [("ffn", c_int)]
+
+
+class WanLoraFfnBlockWeights(Structure):
+    """include/ftmi355.h: ftmi_wan_lora_ffn_block_weights."""
+
+    _fields_ = [("base", WanLoraBlockWeights)] + [(n, c_void_p) for n in ("ffn_a1", "ffn_b1", "ffn_a2", "ffn_b2")]
+
+
 class WanRowArgs(Structure):
     """include/ftmi355.h: ftmi_wan_row_args."""
 
@@ -281,6 +293,10 @@ _SIGS = {
     "ftmi_wan_i2v_lora_block_scratch_bytes": (c_size_t, [POINTER(WanI2VLoraBlockConfig)]),
     "ftmi_wan_i2v_lora_block_forward": (c_int, [POINTER(WanI2VLoraBlockConfig), POINTER(WanLoraBlockWeights)] + [c_void_p] * 9 + [c_size_t, c_void_p, c_size_t, c_void_p]),
     "ftmi_wan_i2v_lora_block_backward": (c_int, [POINTER(WanI2VLoraBlockConfig), POINTER(WanLoraBlockWeights)] + [c_void_p] * 13 + [c_size_t, c_void_p, c_size_t, c_void_p]),
+    "ftmi_wan_lora_ffn_block_saved_bytes": (c_size_t, [POINTER(WanLoraFfnBlockConfig)]),
+    "ftmi_wan_lora_ffn_block_scratch_bytes": (c_size_t, [POINTER(WanLoraFfnBlockConfig)]),
+    "ftmi_wan_lora_ffn_block_forward": (c_int, [POINTER(WanLoraFfnBlockConfig), POINTER(WanLoraFfnBlockWeights)] + [c_void_p] * 9 + [c_size_t, c_void_p, c_size_t, c_void_p]),
+    "ftmi_wan_lora_ffn_block_backward": (c_int, [POINTER(WanLoraFfnBlockConfig), POINTER(WanLoraFfnBlockWeights)] + [c_void_p] * 17 + [c_size_t, c_void_p, c_size_t, c_void_p]),
     "ftmi_wan_block_saved_bytes": (c_size_t, [POINTER(WanBlockConfig)]),
     "ftmi_wan_block_scratch_bytes": (c_size_t, [POINTER(WanBlockConfig)]),
     "ftmi_wan_block_param_elements": (c_size_t, [POINTER(WanBlockConfig)]),

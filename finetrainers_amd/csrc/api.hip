@@ -812,6 +812,28 @@ int ftmi_wan_i2v_lora_block_backward(const ftmi_wan_i2v_lora_block_config* cfg, 
                                        (hipStream_t)stream);
 }
 
+size_t ftmi_wan_lora_ffn_block_saved_bytes(const ftmi_wan_lora_ffn_block_config* cfg) { return cfg ? wan_lora_ffn_block_saved_bytes(*cfg) : 0; }
+size_t ftmi_wan_lora_ffn_block_scratch_bytes(const ftmi_wan_lora_ffn_block_config* cfg) { return cfg ? wan_lora_ffn_block_scratch_bytes(*cfg) : 0; }
+int ftmi_wan_lora_ffn_block_forward(const ftmi_wan_lora_ffn_block_config* cfg, const ftmi_wan_lora_ffn_block_weights* w, const void* img_params, const void* x,
+                                    const void* enc, const void* enc_img, const float* mod, const float* rope_cos, const float* rope_sin, void* out, void* saved,
+                                    size_t saved_bytes, void* scratch, size_t scratch_bytes, ftmi_stream stream) {
+    if (!cfg || !w || !w->base.params || !x || !enc || !mod || !rope_cos || !rope_sin || !saved || !scratch || (cfg->TI > 0 && (!img_params || !enc_img)))
+        return set_error(FTMI_ERR_INVALID, "ftmi_wan_lora_ffn_block_forward: null argument");
+    return wan_lora_ffn_block_forward(*cfg, *w, (const bf16_t*)img_params, (const bf16_t*)x, (const bf16_t*)enc, (const bf16_t*)enc_img, mod, rope_cos, rope_sin,
+                                      (bf16_t*)out, saved, saved_bytes, scratch, scratch_bytes, (hipStream_t)stream);
+}
+int ftmi_wan_lora_ffn_block_backward(const ftmi_wan_lora_ffn_block_config* cfg, const ftmi_wan_lora_ffn_block_weights* w, const void* img_params, const void* x,
+                                     const void* enc, const void* enc_img, const float* mod, const float* rope_cos, const float* rope_sin, const void* dout,
+                                     void* dx, void* denc, float* grad_a, float* grad_b, float* grad_ffn_a1, float* grad_ffn_b1, float* grad_ffn_a2,
+                                     float* grad_ffn_b2, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, ftmi_stream stream) {
+    if (!cfg || !w || !w->base.params || !x || !enc || !mod || !rope_cos || !rope_sin || !dout || !dx || !saved || !scratch ||
+        (cfg->TI > 0 && (!img_params || !enc_img)))
+        return set_error(FTMI_ERR_INVALID, "ftmi_wan_lora_ffn_block_backward: null argument");
+    return wan_lora_ffn_block_backward(*cfg, *w, (const bf16_t*)img_params, (const bf16_t*)x, (const bf16_t*)enc, (const bf16_t*)enc_img, mod, rope_cos, rope_sin,
+                                       (const bf16_t*)dout, (bf16_t*)dx, (bf16_t*)denc, grad_a, grad_b, grad_ffn_a1, grad_ffn_b1, grad_ffn_a2, grad_ffn_b2, saved,
+                                       saved_bytes, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
 int ftmi_lora_refresh(const float* a_f32, const float* b_f32, void* lora_a_sp, void* lora_bt_sp, void* lora_b_ext, void* lora_at_ext,
                       void* lora_at_qkv_ext, int L, int r, int D, ftmi_stream stream) {
     return ftmi_lora_refresh_n(a_f32, b_f32, lora_a_sp, lora_bt_sp, lora_b_ext, lora_at_ext, lora_at_qkv_ext, L, 8, r, D, stream);

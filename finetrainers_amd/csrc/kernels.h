@@ -395,6 +395,16 @@ int wan_i2v_lora_block_backward(const ftmi_wan_i2v_lora_block_config& c, const f
                                 const bf16_t* enc, const bf16_t* enc_img, const float* mod, const float* rope_cos, const float* rope_sin, const bf16_t* dout,
                                 bf16_t* dx, bf16_t* denc, float* grad_a, float* grad_b, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
                                 hipStream_t st);
+// ... and with adapters on the two feed-forward projections (cfg.ffn; TI = 0 and ffn = 0: the calls above)
+size_t wan_lora_ffn_block_saved_bytes(const ftmi_wan_lora_ffn_block_config& c);
+size_t wan_lora_ffn_block_scratch_bytes(const ftmi_wan_lora_ffn_block_config& c);
+int wan_lora_ffn_block_forward(const ftmi_wan_lora_ffn_block_config& c, const ftmi_wan_lora_ffn_block_weights& w, const bf16_t* img_params, const bf16_t* x,
+                               const bf16_t* enc, const bf16_t* enc_img, const float* mod, const float* rope_cos, const float* rope_sin, bf16_t* out, void* saved,
+                               size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st);
+int wan_lora_ffn_block_backward(const ftmi_wan_lora_ffn_block_config& c, const ftmi_wan_lora_ffn_block_weights& w, const bf16_t* img_params, const bf16_t* x,
+                                const bf16_t* enc, const bf16_t* enc_img, const float* mod, const float* rope_cos, const float* rope_sin, const bf16_t* dout,
+                                bf16_t* dx, bf16_t* denc, float* grad_a, float* grad_b, float* grad_ffn_a1, float* grad_ffn_b1, float* grad_ffn_a2,
+                                float* grad_ffn_b2, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st);
 int adamw_bf16_step(bf16_t* p, const float* g, bf16_t* m, bf16_t* v, long n, const float* sumsq_in, float max_norm, float lr, float beta1, float beta2,
                     float eps, float wd, int step, float* grad_norm_out, hipStream_t st);
 

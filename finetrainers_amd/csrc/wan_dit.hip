@@ -33,7 +33,23 @@
 // scratch, frozen base: forward transients (a1, n3, act, f, operand copies of A and B) overlaid with the backward's (+ dxa, operand copies of B^T and A^T).
 // Launcher calls per block (an attention counts once): full fine-tune forward 19, backward 39.  Frozen base, r > 0: forward 2 splits + 5 down-projections
 // + the full path's 19 = 26; backward 2 splits + 5 down-projections + 10 adapter-gradient GEMMs + 18 of the full path's 39 (its 7 transposes, 7
-// weight-gradient GEMMs and 7 column sums are gone) = 35, 34 without denc.
+// weight-gradient GEMMs and 7 column sums are gone) = 35, 34 without denc.  With the feed-forward adapters: forward + 4 splits + 2 down-projections = 32 (the
+// recomputation pass: 30 -- it runs net.2's down-projection, not its GEMM); backward + 4 splits + 2 down-projections + 4 adapter-gradient GEMMs = 45, 44
+// without denc.
+//
+// Feed-forward adapters (the ftmi_wan_lora_ffn_block_* entries with cfg.ffn = 1; the reference hands --target_modules to peft unchanged, and a string that
+// spells "ffn.net.0.proj|ffn.net.2" selects them -- its control trainer's default "...|ff.net.0.proj|ff.net.2" does NOT match Wan's "ffn"): two more adapters
+// at the block's rank, rectangular,
+//   ffn.net.0.proj  A_1 [r, D], B_1 [F, r]:  pre = n3 W_1^T + b_1 + XA_1 B_1^T and act = gelu(pre) in ONE launch (K-extension under the GELU epilogue);
+//                                            dXA_1 = s dpre B_1 contracts over F;  dn3 = dpre W_1 + dXA_1 A_1
+//   ffn.net.2       A_2 [r, F], B_2 [D, r]:  XA_2 = s act A_2^T contracts over F;  f = act W_2^T + b_2 + XA_2 B_2^T;
+//                                            dpre = (df W_2 + dXA_2 A_2) * gelu'(pre) in ONE launch (K-extension under the GELU' epilogue)
+// through the same proj_fwd / proj_bwd as the attention projections.  The four fp32 matrices arrive as pointers of their own (they are not [r, D] / [D, r]
+// like the eight) and are split into the same (hi, lo) operand copies per call.  saved, in addition: xa_f1, xa_f2 [M, 3r] -- and n3 and act, which the frozen
+// base otherwise drops: dA_1 += dXA_1^T n3 and dA_2 += dXA_2^T act read them.  They are KEPT, not recomputed: act is the GELU epilogue's rounding of an fp32
+// accumulator, so recomputing its bits means running the [M, D] x [D, F] GEMM (and its down-projection) a second time in every backward, against
+// B S (D + F) 2 bytes per block -- 426 MB at the recipe's bucket (20 280 tokens, D 1536, F 8960).  Gradient checkpointing brings that back to one block's
+// worth: its recomputation pass refills n3, act, pre, xa_f1 with the identical launches and xa_f2 with net.2's down-projection alone.
 //
 // Image-to-video (Wan2.1-I2V: attn2 with added_kv_proj_dim; the ftmi_wan_i2v_lora_block_* entries, TI > 0 image tokens enc_img [B, TI, D]): attn2 attends to a
 // second, FROZEN key/value set  k_i = RMSNorm(enc_img W_ak^T + b), v_i = enc_img W_av^T + b  (one N = 2D GEMM and one RMSNorm over the B TI image rows) and
@@ -90,25 +106,31 @@ struct Bufs {
     bf16_t *kvi, *kin, *o2s;                                             // image context of attn2 (zero-size at TI = 0)
     float* lse_i;
     bf16_t *xa_qkv, *xa_o1, *xa_q2, *xa_kv2, *xa_o2;                     // down-projected rows of the adapters (zero-size at r = 0)
+    bf16_t *xa_f1, *xa_f2;                                               // ... of the feed-forward adapters (zero-size without them)
     bf16_t *a_sp, *b_ext;                                                // forward operand copies of the adapters
+    bf16_t *f_a1_sp, *f_b1_ext, *f_a2_sp, *f_b2_ext;                     // ... of the feed-forward adapters: A_1 [2r, D], B_1 [F, 3r], A_2 [2r, F], B_2 [D, 3r]
     bf16_t *t_f2, *t_f1, *t_o2, *t_q2, *t_kv2, *t_o1, *t_qkv1;           // transposed weights (full fine-tune only)
     bf16_t *df, *dpre, *dn3, *dx2, *do2, *dkv2, *dq2n, *dk2n, *dq2, *dn2, *dx1, *da1, *do1, *dqkv, *dqn, *dkn, *dn1;  // backward transients
     float* delta;
     bf16_t *dxa, *bt_sp, *at_ext;                                        // backward down-projection and operand copies of the adapters
+    bf16_t *f_b1t_sp, *f_a1t_ext, *f_b2t_sp, *f_a2t_ext;                 // ... of the feed-forward adapters: B_1^T [2r, F], A_1^T [D, 3r], B_2^T [2r, D], A_2^T [F, 3r]
     size_t saved_total, scratch_total;
 };
 
 // The plan of both buffers, resolved against their bases (the byte planners pass none and read the totals).  frozen: a1, n3, act and f are forward
-// transients instead of saved activations, and the transposed weights are the caller's.
-Bufs make_layout(const ftmi_wan_block_config& c, int rank, bool frozen, void* saved = nullptr, void* scratch = nullptr, int TI = 0) {
+// transients instead of saved activations, and the transposed weights are the caller's.  ffn (feed-forward adapters at the same rank): n3 and act stay
+// saved, and everything the two adapters add is appended -- without them no offset moves.
+Bufs make_layout(const ftmi_wan_block_config& c, int rank, bool frozen, void* saved = nullptr, void* scratch = nullptr, int TI = 0, bool ffn = false) {
     Bufs w;
     const size_t M = (size_t)c.B * c.S, Mt = (size_t)c.B * c.T, Mi = (size_t)c.B * (TI > 0 ? TI : 0), D = c.D, F = c.F, r = rank > 0 ? rank : 0, e2 = 2, stat = (size_t)c.B * c.H * c.S * 4;
+    const size_t rf = ffn ? r : 0;
     Bump s, f, b;  // saved; scratch of the forward and of the backward, which overlay each other
     auto at = [](void* base, size_t off) { return reinterpret_cast<bf16_t*>(reinterpret_cast<uintptr_t>(base) + off); };
     auto S = [&](size_t bytes) { return at(saved, s.take(bytes)); };
     auto Fw = [&](size_t bytes) { return at(scratch, f.take(bytes)); };
     auto Bw = [&](size_t bytes) { return at(scratch, b.take(bytes)); };
     auto K = [&](size_t bytes) { return frozen ? Fw(bytes) : S(bytes); };                     // read again only by gradients of base parameters
+    auto KF = [&](size_t bytes) { return ffn ? S(bytes) : K(bytes); };                        // ... and by the feed-forward adapters' dA
     auto T = [&](size_t bytes) { return frozen ? (bf16_t*)nullptr : Bw(bytes); };
     auto f32 = [](bf16_t* p) { return reinterpret_cast<float*>(p); };
     w.n1 = S(M * D * e2);
@@ -127,8 +149,8 @@ Bufs make_layout(const ftmi_wan_block_config& c, int rank, bool frozen, void* sa
     w.o2 = S(M * D * e2);
     w.lse2 = f32(S(stat));
     w.x2 = S(M * D * e2);
-    w.n3 = K(M * D * e2);
-    w.act = K(M * F * e2);
+    w.n3 = KF(M * D * e2);
+    w.act = KF(M * F * e2);
     w.pre = S(M * F * e2);
     w.f = K(M * D * e2);
     w.xa_qkv = S(M * 9 * r * e2);
@@ -140,9 +162,15 @@ Bufs make_layout(const ftmi_wan_block_config& c, int rank, bool frozen, void* sa
     w.kin = S(Mi * D * e2);
     w.lse_i = f32(S(Mi ? stat : 0));
     w.o2s = S(Mi ? M * D * e2 : 0);
+    w.xa_f1 = S(M * 3 * rf * e2);
+    w.xa_f2 = S(M * 3 * rf * e2);
     w.saved_total = s.off;
     w.a_sp = Fw(8 * 2 * r * D * e2);
     w.b_ext = Fw(8 * D * 3 * r * e2);
+    w.f_a1_sp = Fw(2 * rf * D * e2);
+    w.f_b1_ext = Fw(F * 3 * rf * e2);
+    w.f_a2_sp = Fw(2 * rf * F * e2);
+    w.f_b2_ext = Fw(D * 3 * rf * e2);
     w.t_f2 = T(D * F * e2);
     w.t_f1 = T(D * F * e2);
     w.t_o2 = T(D * D * e2);
@@ -171,6 +199,10 @@ Bufs make_layout(const ftmi_wan_block_config& c, int rank, bool frozen, void* sa
     w.dxa = Bw((M > Mt ? M : Mt) * 9 * r * e2);
     w.bt_sp = Bw(8 * 2 * r * D * e2);
     w.at_ext = Bw(D * 24 * r * e2);
+    w.f_b1t_sp = Bw(2 * rf * F * e2);
+    w.f_a1t_ext = Bw(D * 3 * rf * e2);
+    w.f_b2t_sp = Bw(2 * rf * D * e2);
+    w.f_a2t_ext = Bw(F * 3 * rf * e2);
     w.scratch_total = f.off > b.off ? f.off : b.off;
     return w;
 }
@@ -208,6 +240,21 @@ int check_i2v_cfg(const ftmi_wan_i2v_lora_block_config& c) {
     return 0;
 }
 
+ftmi_wan_i2v_lora_block_config i2v_cfg(const ftmi_wan_lora_ffn_block_config& c) {
+    ftmi_wan_i2v_lora_block_config l;
+    l.B = c.B; l.S = c.S; l.T = c.T; l.D = c.D; l.H = c.H; l.F = c.F; l.eps = c.eps; l.gemm_variant = c.gemm_variant; l.r = c.r; l.lora_scale = c.lora_scale; l.TI = c.TI;
+    return l;
+}
+
+int check_ffn_cfg(const ftmi_wan_lora_ffn_block_config& c) {
+    FTMI_TRY(check_i2v_cfg(i2v_cfg(c)));
+    if (c.ffn != 0 && c.ffn != 1) return set_error(FTMI_ERR_INVALID, "wan_lora_ffn_block: ffn is 0 or 1");
+    if (c.ffn && c.r == 0) return set_error(FTMI_ERR_UNSUPPORTED, "wan_lora_ffn_block: feed-forward adapters take the block's rank, which is 0");
+    // (the split down-projection contracts over at least 256 columns: XA_2 = s act A_2^T and dXA_1 = s dpre B_1 contract over F)
+    if (c.ffn && c.F < 256) return set_error(FTMI_ERR_UNSUPPORTED, "wan_lora_ffn_block: feed-forward adapters need a feed-forward width of at least 256");
+    return 0;
+}
+
 // the image context of attn2: TI tokens enc_img [B, TI, D] and the frozen flat buffer  add_k | add_v weight [2D, D], their biases [2D], norm_added_k [D]
 struct ImgCtx {
     int TI = 0;
@@ -221,6 +268,18 @@ struct LoraOps {
     float s = 0.f;
     const bf16_t* sp = nullptr;   // forward: A as (hi, lo) row planes [8][2r][D];   backward: B^T planes [8][2r][D]
     const bf16_t* ext = nullptr;  // forward: B as [hi | hi | lo] columns [8][D][3r];   backward: A^T columns, the eight adapters side by side [D][24r]
+    long ext_step = 0, ld_ext = 0;  // elements from one adapter's ext to the next, row stride of ext: forward 3 r D, 3r;   backward 3r, 24r
+};
+
+// `n` adjacent adapters on one projection, as one direction of the walk sees them (n = 0: a projection without adapters)
+struct Adp {
+    int n = 0, r = 0;
+    float s = 0.f;
+    const bf16_t* sp = nullptr;   // forward: A (hi, lo) row planes [n 2r, K_in];             backward: B^T planes [n 2r, N_out]
+    const bf16_t* ext = nullptr;  // forward: B [hi | hi | lo] columns [n N_out, 3r];         backward: A^T columns [K_in, ld_ext], the n adapters side by side
+    long ld_ext = 0;              // backward only
+    bf16_t* xa = nullptr;         // [rows, 3 n r]: written by the forward, read by the backward
+    float *ga = nullptr, *gb = nullptr;  // backward: fp32 [n r, K_in] / [n N_out, r] (ADDED to)
 };
 
 // K-contiguous copies of the weights for the input-gradient GEMMs (dX = dY W as an NT GEMM against W^T)
@@ -239,6 +298,7 @@ struct Block {
     const float *mod = nullptr, *rope_cos = nullptr, *rope_sin = nullptr;
     float *grads = nullptr, *dmod = nullptr;      // backward: flat fp32 base gradients, fp32 [6, B, D] modulation sums (both ADDED to)
     float *grad_a = nullptr, *grad_b = nullptr;  // backward: fp32 [8, r, D] / [8, D, r] (ADDED to)
+    Adp f1, f2;                                  // the feed-forward adapters on ffn.net.0.proj / ffn.net.2 (n = 0: none), filled for the call's direction
     Twins t;
     ImgCtx img;
     hipStream_t st = nullptr;
@@ -282,45 +342,60 @@ AttnArgs attn_bwd_args(AttnArgs a, const bf16_t* dout, bf16_t* dq, bf16_t* dk, b
     return a;
 }
 
-// s * X A^T (or s * dY B) of the adapters adp .. adp + nadp - 1 as ONE split down-projection: out [rows, 3 nadp r]
-int lora_down(const LoraOps& lo, const bf16_t* X, long ldx, int rows, int D, int adp, int nadp, long xk_stride, bf16_t* out, hipStream_t st) {
-    return gemm_nt(lora_down_args(X, ldx, rows, lo.sp + (size_t)adp * 2 * lo.r * D, nadp, D, lo.r, lo.s, out, xk_stride), st);
+// the attention adapters adp .. adp + nadp - 1 (order of the header comment) for the direction the call's LoraOps were filled for
+Adp attn_adp(const Block& k, int adp, int nadp, bf16_t* xa) {
+    Adp a;
+    if (k.lo.r <= 0 || nadp <= 0) return a;
+    const size_t r = k.lo.r, D = k.c.D;
+    a.n = nadp; a.r = k.lo.r; a.s = k.lo.s; a.xa = xa;
+    a.sp = k.lo.sp + adp * 2 * r * D;
+    a.ext = k.lo.ext + adp * k.lo.ext_step;
+    a.ld_ext = k.lo.ld_ext;
+    if (k.grad_a) { a.ga = k.grad_a + adp * r * D; a.gb = k.grad_b + adp * D * r; }
+    return a;
 }
 
-// out [rows, N] = X W^T + bias, X [rows, K].  nadp > 0 (then N = nadp K): + the adapters adp .. adp + nadp - 1 on the same input when the call has any;
-// xa [rows, 3 nadp r] is kept for the backward
-int proj_fwd(const Block& k, const bf16_t* X, int rows, int K, const bf16_t* Wm, const bf16_t* bias, int N, int adp, int nadp, bf16_t* xa, bf16_t* out) {
-    const int r = nadp > 0 ? k.lo.r : 0;
+// s * X A^T (or s * dY B) of the adapters `ad` as ONE split down-projection contracting over K: out [rows, 3 n r]
+int lora_down(const Adp& ad, const bf16_t* X, long ldx, int rows, int K, long xk_stride, bf16_t* out, hipStream_t st) {
+    return gemm_nt(lora_down_args(X, ldx, rows, ad.sp, ad.n, K, ad.r, ad.s, out, xk_stride), st);
+}
+
+// out [rows, N] = X W^T + bias, X [rows, K], + the adapters `ad` on the same input (then N = ad.n N_out); ad.xa [rows, 3 n r] is kept for the backward.
+// pre != null: out = gelu_tanh(the sum), pre = the sum (the feed-forward's first projection)
+int proj_fwd(const Block& k, const bf16_t* X, int rows, int K, const bf16_t* Wm, const bf16_t* bias, int N, const Adp& ad, bf16_t* out, bf16_t* pre = nullptr) {
     GemmNtArgs a = linear_args(X, K, rows, Wm, K, N, K, bias, out, N, k.c.gemm_variant);
-    if (r > 0) {
-        FTMI_TRY(lora_down(k.lo, X, K, rows, K, adp, nadp, 0, xa, k.st));
-        lora_ext_fwd(a, xa, nadp, r, k.lo.ext + (size_t)adp * K * 3 * r);
+    if (pre) { a.out2 = pre; a.ldo2 = N; a.epi = EPI_GELU; }
+    if (ad.n > 0) {
+        FTMI_TRY(lora_down(ad, X, K, rows, K, 0, ad.xa, k.st));
+        lora_ext_fwd(a, ad.xa, ad.n, ad.r, ad.ext);
     }
     return gemm_nt(a, k.st);
 }
 
 // The backward of proj_fwd for dY [rows, N], X [rows, K], Wt [K, N] the K-contiguous twin of W, in this order: dW += dY^T X and db += column sums (gw != null:
-// the base trains); dXA = s dY B (adapters); dx [rows, K] = dY Wt^T (+ dXA A) (dx == null: skipped); dB += dY^T XA, dA += dXA^T X (adapters)
-int proj_bwd(const Block& k, const bf16_t* X, const bf16_t* dy, int rows, int N, int K, const bf16_t* Wt, int adp, int nadp, const bf16_t* xa, bf16_t* dx,
-             float* gw, float* gb) {
-    const int r = nadp > 0 ? k.lo.r : 0;
+// the base trains); dXA = s dY B (adapters); dx [rows, K] = dY Wt^T (+ dXA A) (dx == null: skipped); dB += dY^T XA, dA += dXA^T X (adapters).
+// pre != null: dx = (the sum) * gelu_tanh'(pre), pre [rows, K] (the feed-forward's second projection hands its input gradient through the activation)
+int proj_bwd(const Block& k, const bf16_t* X, const bf16_t* dy, int rows, int N, int K, const bf16_t* Wt, const Adp& ad, bf16_t* dx, float* gw, float* gb,
+             const bf16_t* pre = nullptr) {
+    const int r = ad.n > 0 ? ad.r : 0, No = ad.n > 0 ? N / ad.n : N;  // (No: outputs per adapter)
     bf16_t* dxa = k.L.dxa;
     FTMI_TRY(linear_grads(dy, N, X, K, rows, N, K, gw, gb, k.st));
-    if (r > 0) FTMI_TRY(lora_down(k.lo, dy, N, rows, K, adp, nadp, nadp > 1 ? K : 0, dxa, k.st));
+    if (r > 0) FTMI_TRY(lora_down(ad, dy, N, rows, No, ad.n > 1 ? No : 0, dxa, k.st));
     if (dx) {
         GemmNtArgs a = linear_args(dy, N, rows, Wt, N, K, N, nullptr, dx, K, k.c.gemm_variant);
-        if (r > 0) lora_ext_bwd(a, dxa, nadp, r, k.lo.ext + (size_t)adp * 3 * r, 24L * r);
+        if (pre) { a.epi = EPI_DGELU; a.aux = pre; a.ldaux = K; }
+        if (r > 0) lora_ext_bwd(a, dxa, ad.n, r, ad.ext, ad.ld_ext);
         FTMI_TRY(gemm_nt(a, k.st));
     }
-    if (r > 0) {  // (an adapted projection has N = nadp K)
-        FTMI_TRY(gemm_tn(lora_db_args(dy, N, xa, nadp, r, K, k.grad_b + (size_t)adp * K * r, rows), k.st));
-        FTMI_TRY(gemm_tn(lora_da_args(dxa, nadp, r, X, K, K, k.grad_a + (size_t)adp * r * K, rows), k.st));
+    if (r > 0) {
+        FTMI_TRY(gemm_tn(lora_db_args(dy, N, ad.xa, ad.n, r, No, ad.gb, rows), k.st));
+        FTMI_TRY(gemm_tn(lora_da_args(dxa, ad.n, r, X, K, K, ad.ga, rows), k.st));
     }
     return 0;
 }
 
 // out == nullptr: the recomputation pass of gradient checkpointing -- the identical kernel sequence refills `saved` from the block's input and stops after
-// the feed-forward's first GEMM (its pre-activation is the last thing the backward reads)
+// the feed-forward's first GEMM (its pre-activation is the last thing the backward reads; with an adapter on ffn.net.2, its down-projected rows are)
 int block_forward(const Block& k, bf16_t* out) {
     const ftmi_wan_block_config& c = k.c;
     const Bufs& L = k.L;
@@ -337,14 +412,14 @@ int block_forward(const Block& k, bf16_t* out) {
         a.shift = MOD(0); a.scale = MOD(1); a.mod_bstride = mb;
         FTMI_TRY(wan_ln_fwd(a, st));
     }
-    FTMI_TRY(proj_fwd(k, L.n1, M, D, P(O.w_qkv1), P(O.b_qkv1), 3 * D, 0, 3, L.xa_qkv, L.qkv));
+    FTMI_TRY(proj_fwd(k, L.n1, M, D, P(O.w_qkv1), P(O.b_qkv1), 3 * D, attn_adp(k, 0, 3, L.xa_qkv), L.qkv));
     for (int i = 0; i < 2; ++i) {
         WanRowArgs a = row_args(L.qkv + (size_t)i * D, 3 * D, i ? L.kn : L.qn, D, M, D, S, eps);
         a.w = P(i ? O.nk1 : O.nq1); a.rope_cos = k.rope_cos; a.rope_sin = k.rope_sin; a.head_dim = 128;
         FTMI_TRY(wan_rms_rope_fwd(a, st));
     }
     FTMI_TRY(attn_fwd(attn_args(c, L.qn, L.kn, L.qkv, 3 * D, L.o1, L.lse1, S, S), st));
-    FTMI_TRY(proj_fwd(k, L.o1, M, D, P(O.w_o1), P(O.b_o1), D, 3, 1, L.xa_o1, L.a1));
+    FTMI_TRY(proj_fwd(k, L.o1, M, D, P(O.w_o1), P(O.b_o1), D, attn_adp(k, 3, 1, L.xa_o1), L.a1));
     {
         WanRowArgs a = row_args(k.x, D, L.x1, D, M, D, S, eps);
         a.scale = MOD(2); a.mod_bstride = mb; a.dy = L.a1; a.ld_dy = D;
@@ -356,8 +431,8 @@ int block_forward(const Block& k, bf16_t* out) {
         a.w = P(O.n2w); a.b = P(O.n2b);
         FTMI_TRY(wan_ln_fwd(a, st));
     }
-    FTMI_TRY(proj_fwd(k, L.n2, M, D, P(O.w_q2), P(O.b_q2), D, 4, 1, L.xa_q2, L.q2));
-    FTMI_TRY(proj_fwd(k, k.enc, Mt, D, P(O.w_kv2), P(O.b_kv2), 2 * D, 5, 2, L.xa_kv2, L.kv2));
+    FTMI_TRY(proj_fwd(k, L.n2, M, D, P(O.w_q2), P(O.b_q2), D, attn_adp(k, 4, 1, L.xa_q2), L.q2));
+    FTMI_TRY(proj_fwd(k, k.enc, Mt, D, P(O.w_kv2), P(O.b_kv2), 2 * D, attn_adp(k, 5, 2, L.xa_kv2), L.kv2));
     {
         WanRowArgs a = row_args(L.q2, D, L.q2n, D, M, D, S, eps);
         a.w = P(O.nq2);
@@ -371,7 +446,7 @@ int block_forward(const Block& k, bf16_t* out) {
     if (k.img.TI > 0) {  // the image tokens' keys and values (frozen, no adapters), then their attention summed onto the text branch's output
         const int TI = k.img.TI, Mi = B * TI;
         const bf16_t* ip = k.img.params;
-        FTMI_TRY(proj_fwd(k, k.img.enc, Mi, D, ip, ip + 2 * (size_t)D * D, 2 * D, 0, 0, nullptr, L.kvi));
+        FTMI_TRY(proj_fwd(k, k.img.enc, Mi, D, ip, ip + 2 * (size_t)D * D, 2 * D, Adp(), L.kvi));
         WanRowArgs a = row_args(L.kvi, 2 * D, L.kin, D, Mi, D, TI, eps);
         a.w = ip + 2 * (size_t)D * D + 2 * D;
         FTMI_TRY(wan_rms_rope_fwd(a, st));
@@ -379,7 +454,7 @@ int block_forward(const Block& k, bf16_t* out) {
         o2 = L.o2s;
     }
     bf16_t* a2 = L.f;  // (the feed-forward output buffer doubles as the staging of o2 W_o2^T + b: it is consumed by the next launch)
-    FTMI_TRY(proj_fwd(k, o2, M, D, P(O.w_o2), P(O.b_o2), D, 7, 1, L.xa_o2, a2));
+    FTMI_TRY(proj_fwd(k, o2, M, D, P(O.w_o2), P(O.b_o2), D, attn_adp(k, 7, 1, L.xa_o2), a2));
     {
         WanRowArgs a = row_args(L.x1, D, L.x2, D, M, D, S, eps);
         a.dy = a2; a.ld_dy = D;
@@ -391,14 +466,9 @@ int block_forward(const Block& k, bf16_t* out) {
         a.shift = MOD(3); a.scale = MOD(4); a.mod_bstride = mb;
         FTMI_TRY(wan_ln_fwd(a, st));
     }
-    {
-        GemmNtArgs a;  // GELU-tanh, pre-activation kept
-        a.X = L.n3; a.ldx = D; a.W = P(O.w_f1); a.ldw = D; a.M = M; a.N = F; a.K = D; a.bias = P(O.b_f1); a.out = L.act; a.ldo = F; a.out2 = L.pre; a.ldo2 = F;
-        a.epi = EPI_GELU; a.variant = c.gemm_variant;
-        FTMI_TRY(gemm_nt(a, st));
-    }
-    if (!out) return 0;
-    FTMI_TRY(proj_fwd(k, L.act, M, F, P(O.w_f2), P(O.b_f2), D, 0, 0, nullptr, L.f));
+    FTMI_TRY(proj_fwd(k, L.n3, M, D, P(O.w_f1), P(O.b_f1), F, k.f1, L.act, L.pre));  // GELU-tanh, pre-activation kept
+    if (!out) return k.f2.n > 0 ? lora_down(k.f2, L.act, F, M, F, 0, k.f2.xa, st) : 0;
+    FTMI_TRY(proj_fwd(k, L.act, M, F, P(O.w_f2), P(O.b_f2), D, k.f2, L.f));
     {
         WanRowArgs a = row_args(L.x2, D, out, D, M, D, S, eps);
         a.scale = MOD(5); a.mod_bstride = mb; a.dy = L.f; a.ld_dy = D;
@@ -432,21 +502,15 @@ int block_backward(const Block& k, const bf16_t* dout, bf16_t* dx, bf16_t* denc)
 
     // feed-forward branch: out = x2 + f * gate_ff
     FTMI_TRY(gate_bwd(dout, L.df, L.f, 5));
-    FTMI_TRY(linear_grads(L.df, D, L.act, F, M, D, F, G(O.w_f2), G(O.b_f2), st));
-    {
-        GemmNtArgs a;  // (d f W2) * gelu'(pre)
-        a.X = L.df; a.ldx = D; a.W = k.t.f2; a.ldw = D; a.M = M; a.N = F; a.K = D; a.out = L.dpre; a.ldo = F; a.epi = EPI_DGELU; a.aux = L.pre; a.ldaux = F;
-        a.variant = c.gemm_variant;
-        FTMI_TRY(gemm_nt(a, st));
-    }
-    FTMI_TRY(proj_bwd(k, L.n3, L.dpre, M, F, D, k.t.f1, 0, 0, nullptr, L.dn3, G(O.w_f1), G(O.b_f1)));
+    FTMI_TRY(proj_bwd(k, L.act, L.df, M, D, F, k.t.f2, k.f2, L.dpre, G(O.w_f2), G(O.b_f2), L.pre));  // (d f W2 [+ dXA_2 A_2]) * gelu'(pre)
+    FTMI_TRY(proj_bwd(k, L.n3, L.dpre, M, F, D, k.t.f1, k.f1, L.dn3, G(O.w_f1), G(O.b_f1)));
     {
         WanRowArgs a = row_args(L.x2, D, L.dx2, D, M, D, S, eps);
         a.scale = MOD(4); a.mod_bstride = mb; a.dy = L.dn3; a.ld_dy = D; a.dres = dout; a.red1 = DMOD(3); a.red2 = DMOD(4); a.red_per_batch = per_batch;
         FTMI_TRY(wan_ln_bwd(a, st));
     }
     // cross-attention branch: x2 = x1 + a2
-    FTMI_TRY(proj_bwd(k, k.img.TI > 0 ? L.o2s : L.o2, L.dx2, M, D, D, k.t.o2, 7, 1, L.xa_o2, L.do2, G(O.w_o2), G(O.b_o2)));
+    FTMI_TRY(proj_bwd(k, k.img.TI > 0 ? L.o2s : L.o2, L.dx2, M, D, D, k.t.o2, attn_adp(k, 7, 1, L.xa_o2), L.do2, G(O.w_o2), G(O.b_o2)));
     FTMI_TRY(attn_bwd(attn_bwd_args(attn_args(c, L.q2n, L.k2n, L.kv2, 2 * D, L.o2, L.lse2, S, T), L.do2, L.dq2n, L.dk2n, L.dkv2, L.delta), st));
     if (k.img.TI > 0)  // the image branch's dQ, added onto the text branch's in place (its keys and values are frozen: no dK, dV)
         FTMI_TRY(attn_ctx2_dq(attn_bwd_args(attn_args(c, L.q2n, L.kin, L.kvi, 2 * D, L.o2s, L.lse_i, S, k.img.TI), L.do2, L.dq2n, nullptr, L.dkv2, nullptr), L.dq2n, st));
@@ -459,8 +523,8 @@ int block_backward(const Block& k, const bf16_t* dout, bf16_t* dx, bf16_t* denc)
         FTMI_TRY(wan_rms_rope_bwd(b, st));
     }
     FTMI_TRY(linear_grads(L.dq2, D, L.n2, D, M, D, D, G(O.w_q2), G(O.b_q2), st));  // (attn2.to_q's weight gradient goes ahead of the text rows' projection)
-    FTMI_TRY(proj_bwd(k, k.enc, L.dkv2, Mt, 2 * D, D, k.t.kv2, 5, 2, L.xa_kv2, denc, G(O.w_kv2), G(O.b_kv2)));
-    FTMI_TRY(proj_bwd(k, L.n2, L.dq2, M, D, D, k.t.q2, 4, 1, L.xa_q2, L.dn2, nullptr, nullptr));
+    FTMI_TRY(proj_bwd(k, k.enc, L.dkv2, Mt, 2 * D, D, k.t.kv2, attn_adp(k, 5, 2, L.xa_kv2), denc, G(O.w_kv2), G(O.b_kv2)));
+    FTMI_TRY(proj_bwd(k, L.n2, L.dq2, M, D, D, k.t.q2, attn_adp(k, 4, 1, L.xa_q2), L.dn2, nullptr, nullptr));
     {
         WanRowArgs a = row_args(L.x1, D, L.dx1, D, M, D, S, eps);
         a.w = P(O.n2w); a.dy = L.dn2; a.ld_dy = D; a.dres = L.dx2; a.red1 = G(O.n2b); a.red2 = G(O.n2w);
@@ -468,7 +532,7 @@ int block_backward(const Block& k, const bf16_t* dout, bf16_t* dx, bf16_t* denc)
     }
     // self-attention branch: x1 = x + a1 * gate_msa
     FTMI_TRY(gate_bwd(L.dx1, L.da1, L.a1, 2));
-    FTMI_TRY(proj_bwd(k, L.o1, L.da1, M, D, D, k.t.o1, 3, 1, L.xa_o1, L.do1, G(O.w_o1), G(O.b_o1)));
+    FTMI_TRY(proj_bwd(k, L.o1, L.da1, M, D, D, k.t.o1, attn_adp(k, 3, 1, L.xa_o1), L.do1, G(O.w_o1), G(O.b_o1)));
     FTMI_TRY(attn_bwd(attn_bwd_args(attn_args(c, L.qn, L.kn, L.qkv, 3 * D, L.o1, L.lse1, S, S), L.do1, L.dqn, L.dkn, L.dqkv, L.delta), st));
     for (int i = 0; i < 2; ++i) {
         WanRowArgs a = row_args(L.qkv + (size_t)i * D, 3 * D, L.dqkv + (size_t)i * D, 3 * D, M, D, S, eps);
@@ -476,7 +540,7 @@ int block_backward(const Block& k, const bf16_t* dout, bf16_t* dx, bf16_t* denc)
         FTMI_TRY(wan_rms_rope_bwd(a, st));
     }
     // the three projections' input gradients (and their adapters') summed in the fp32 accumulator
-    FTMI_TRY(proj_bwd(k, L.n1, L.dqkv, M, 3 * D, D, k.t.qkv1, 0, 3, L.xa_qkv, L.dn1, G(O.w_qkv1), G(O.b_qkv1)));
+    FTMI_TRY(proj_bwd(k, L.n1, L.dqkv, M, 3 * D, D, k.t.qkv1, attn_adp(k, 0, 3, L.xa_qkv), L.dn1, G(O.w_qkv1), G(O.b_qkv1)));
     {
         WanRowArgs a = row_args(k.x, D, dx, D, M, D, S, eps);
         a.scale = MOD(1); a.mod_bstride = mb; a.dy = L.dn1; a.ld_dy = D; a.dres = L.dx1; a.red1 = DMOD(0); a.red2 = DMOD(1); a.red_per_batch = per_batch;
@@ -534,9 +598,29 @@ int wan_block_backward(const ftmi_wan_block_config& c, const bf16_t* params, flo
 
 namespace {
 
+// the feed-forward adapters of one call (on: a1 != null) and, for the backward, where their gradients are added
+struct FfnLora {
+    const float *a1 = nullptr, *b1 = nullptr, *a2 = nullptr, *b2 = nullptr;  // fp32 A_1 [r, D], B_1 [F, r], A_2 [r, F], B_2 [D, r]
+    float *ga1 = nullptr, *gb1 = nullptr, *ga2 = nullptr, *gb2 = nullptr;
+};
+
+// one fp32 matrix [rows, cols] into one of its four operand layouts (LoraSplitArgs)
+int split_one(const float* wm, int rows, int cols, bf16_t* sp, bf16_t* ext, bf16_t* t_sp, bf16_t* t_ext, hipStream_t st) {
+    LoraSplitArgs a;
+    a.w = wm; a.rows = rows; a.cols = cols; a.nmat = 1; a.sp = sp; a.ext = ext; a.ld_ext = 3L * cols; a.t_sp = t_sp; a.t_ext = t_ext; a.ld_t_ext = 3L * rows;
+    return lora_split(a, st);
+}
+
+Adp ffn_adp(const ftmi_wan_lora_block_config& c, const bf16_t* sp, const bf16_t* ext, bf16_t* xa, float* ga, float* gb) {
+    Adp a;
+    a.n = 1; a.r = c.r; a.s = c.lora_scale; a.sp = sp; a.ext = ext; a.ld_ext = 3L * c.r; a.xa = xa; a.ga = ga; a.gb = gb;
+    return a;
+}
+
 int lora_forward(const ftmi_wan_lora_block_config& c, const ftmi_wan_lora_block_weights& w, const ImgCtx& img, const bf16_t* x, const bf16_t* enc, const float* mod,
-                 const float* rope_cos, const float* rope_sin, bf16_t* out, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st) {
-    const Bufs L = make_layout(base_cfg(c), c.r, true, saved, scratch, img.TI);
+                 const float* rope_cos, const float* rope_sin, bf16_t* out, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st,
+                 const FfnLora& ffn = FfnLora()) {
+    const Bufs L = make_layout(base_cfg(c), c.r, true, saved, scratch, img.TI, ffn.a1 != nullptr);
     if (saved_bytes < L.saved_total || scratch_bytes < L.scratch_total) return set_error(FTMI_ERR_INVALID, "wan_lora_block_forward: buffer too small");
     if (c.r > 0 && (!w.lora_a || !w.lora_b)) return set_error(FTMI_ERR_INVALID, "wan_lora_block_forward: LoRA rank without adapters");
     Block k = make_block(base_cfg(c), w.params, L, x, enc, mod, rope_cos, rope_sin, st);
@@ -550,7 +634,16 @@ int lora_forward(const ftmi_wan_lora_block_config& c, const ftmi_wan_lora_block_
         LoraSplitArgs sb;
         sb.w = w.lora_b; sb.rows = D; sb.cols = r; sb.nmat = 8; sb.in_bstride = (long)D * r; sb.ext = L.b_ext; sb.ext_bstride = 3L * D * r; sb.ld_ext = 3 * r;
         FTMI_TRY(lora_split(sb, st));
-        k.lo.sp = L.a_sp; k.lo.ext = L.b_ext;
+        k.lo.sp = L.a_sp; k.lo.ext = L.b_ext; k.lo.ext_step = 3L * r * D; k.lo.ld_ext = 3L * r;
+    }
+    if (ffn.a1) {
+        const int F = c.F;
+        FTMI_TRY(split_one(ffn.a1, r, D, L.f_a1_sp, nullptr, nullptr, nullptr, st));
+        FTMI_TRY(split_one(ffn.b1, F, r, nullptr, L.f_b1_ext, nullptr, nullptr, st));
+        FTMI_TRY(split_one(ffn.a2, r, F, L.f_a2_sp, nullptr, nullptr, nullptr, st));
+        FTMI_TRY(split_one(ffn.b2, D, r, nullptr, L.f_b2_ext, nullptr, nullptr, st));
+        k.f1 = ffn_adp(c, L.f_a1_sp, L.f_b1_ext, L.xa_f1, nullptr, nullptr);
+        k.f2 = ffn_adp(c, L.f_a2_sp, L.f_b2_ext, L.xa_f2, nullptr, nullptr);
     }
     return block_forward(k, out);
 }
@@ -558,8 +651,8 @@ int lora_forward(const ftmi_wan_lora_block_config& c, const ftmi_wan_lora_block_
 // grad_a fp32 [8, r, D] / grad_b fp32 [8, D, r] ADDED to.
 int lora_backward(const ftmi_wan_lora_block_config& c, const ftmi_wan_lora_block_weights& w, const ImgCtx& img, const bf16_t* x, const bf16_t* enc, const float* mod,
                   const float* rope_cos, const float* rope_sin, const bf16_t* dout, bf16_t* dx, bf16_t* denc, float* grad_a, float* grad_b, void* saved,
-                  size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st) {
-    const Bufs L = make_layout(base_cfg(c), c.r, true, saved, scratch, img.TI);
+                  size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st, const FfnLora& ffn = FfnLora()) {
+    const Bufs L = make_layout(base_cfg(c), c.r, true, saved, scratch, img.TI, ffn.a1 != nullptr);
     if (saved_bytes < L.saved_total || scratch_bytes < L.scratch_total) return set_error(FTMI_ERR_INVALID, "wan_lora_block_backward: buffer too small");
     if (c.r > 0 && (!w.lora_a || !w.lora_b || !grad_a || !grad_b)) return set_error(FTMI_ERR_INVALID, "wan_lora_block_backward: LoRA rank without adapters / gradient buffers");
     if (!w.w_qkv1_t || !w.w_o1_t || !w.w_q2_t || !w.w_kv2_t || !w.w_o2_t || !w.w_f1_t || !w.w_f2_t)
@@ -578,7 +671,16 @@ int lora_backward(const ftmi_wan_lora_block_config& c, const ftmi_wan_lora_block
         LoraSplitArgs sa;  // A^T as K-extension columns, the eight adapters side by side [D, 24r]: dx += dXA A, fused projections take adjacent column groups
         sa.w = w.lora_a; sa.rows = r; sa.cols = D; sa.nmat = 8; sa.in_bstride = (long)r * D; sa.t_ext = L.at_ext; sa.t_ext_bstride = 3L * r; sa.ld_t_ext = 24L * r;
         FTMI_TRY(lora_split(sa, st));
-        k.lo.sp = L.bt_sp; k.lo.ext = L.at_ext;
+        k.lo.sp = L.bt_sp; k.lo.ext = L.at_ext; k.lo.ext_step = 3L * r; k.lo.ld_ext = 24L * r;
+    }
+    if (ffn.a1) {  // B^T as (hi, lo) row planes, A^T as K-extension columns, per adapter
+        const int F = c.F;
+        FTMI_TRY(split_one(ffn.b1, F, r, nullptr, nullptr, L.f_b1t_sp, nullptr, st));
+        FTMI_TRY(split_one(ffn.a1, r, D, nullptr, nullptr, nullptr, L.f_a1t_ext, st));
+        FTMI_TRY(split_one(ffn.b2, D, r, nullptr, nullptr, L.f_b2t_sp, nullptr, st));
+        FTMI_TRY(split_one(ffn.a2, r, F, nullptr, nullptr, nullptr, L.f_a2t_ext, st));
+        k.f1 = ffn_adp(c, L.f_b1t_sp, L.f_a1t_ext, L.xa_f1, ffn.ga1, ffn.gb1);
+        k.f2 = ffn_adp(c, L.f_b2t_sp, L.f_a2t_ext, L.xa_f2, ffn.ga2, ffn.gb2);
     }
     return block_backward(k, dout, dx, denc);
 }
@@ -626,6 +728,44 @@ int wan_i2v_lora_block_backward(const ftmi_wan_i2v_lora_block_config& c, const f
     if (c.TI > 0 && (!img_params || !enc_img)) return set_error(FTMI_ERR_INVALID, "wan_i2v_lora_block_backward: image tokens without their parameters");
     return lora_backward(lora_cfg(c), w, img_ctx(c, img_params, enc_img), x, enc, mod, rope_cos, rope_sin, dout, dx, denc, grad_a, grad_b, saved, saved_bytes, scratch,
                          scratch_bytes, st);
+}
+
+// the LoRA block with the image context (cfg.TI, 0: none) and, cfg.ffn = 1, adapters on the two feed-forward projections as well
+size_t wan_lora_ffn_block_saved_bytes(const ftmi_wan_lora_ffn_block_config& c) {
+    return check_ffn_cfg(c) ? 0 : make_layout(base_cfg(lora_cfg(i2v_cfg(c))), c.r, true, nullptr, nullptr, c.TI, c.ffn != 0).saved_total;
+}
+size_t wan_lora_ffn_block_scratch_bytes(const ftmi_wan_lora_ffn_block_config& c) {
+    return check_ffn_cfg(c) ? 0 : make_layout(base_cfg(lora_cfg(i2v_cfg(c))), c.r, true, nullptr, nullptr, c.TI, c.ffn != 0).scratch_total;
+}
+int wan_lora_ffn_block_forward(const ftmi_wan_lora_ffn_block_config& c, const ftmi_wan_lora_ffn_block_weights& w, const bf16_t* img_params, const bf16_t* x,
+                               const bf16_t* enc, const bf16_t* enc_img, const float* mod, const float* rope_cos, const float* rope_sin, bf16_t* out, void* saved,
+                               size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st) {
+    FTMI_TRY(check_ffn_cfg(c));
+    if (c.TI > 0 && (!img_params || !enc_img)) return set_error(FTMI_ERR_INVALID, "wan_lora_ffn_block_forward: image tokens without their parameters");
+    FfnLora f;
+    if (c.ffn) {
+        if (!w.ffn_a1 || !w.ffn_b1 || !w.ffn_a2 || !w.ffn_b2) return set_error(FTMI_ERR_INVALID, "wan_lora_ffn_block_forward: feed-forward adapters missing");
+        f.a1 = w.ffn_a1; f.b1 = w.ffn_b1; f.a2 = w.ffn_a2; f.b2 = w.ffn_b2;
+    }
+    const ftmi_wan_i2v_lora_block_config ci = i2v_cfg(c);
+    return lora_forward(lora_cfg(ci), w.base, img_ctx(ci, img_params, enc_img), x, enc, mod, rope_cos, rope_sin, out, saved, saved_bytes, scratch, scratch_bytes, st, f);
+}
+int wan_lora_ffn_block_backward(const ftmi_wan_lora_ffn_block_config& c, const ftmi_wan_lora_ffn_block_weights& w, const bf16_t* img_params, const bf16_t* x,
+                                const bf16_t* enc, const bf16_t* enc_img, const float* mod, const float* rope_cos, const float* rope_sin, const bf16_t* dout,
+                                bf16_t* dx, bf16_t* denc, float* grad_a, float* grad_b, float* grad_ffn_a1, float* grad_ffn_b1, float* grad_ffn_a2,
+                                float* grad_ffn_b2, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st) {
+    FTMI_TRY(check_ffn_cfg(c));
+    if (c.TI > 0 && (!img_params || !enc_img)) return set_error(FTMI_ERR_INVALID, "wan_lora_ffn_block_backward: image tokens without their parameters");
+    FfnLora f;
+    if (c.ffn) {
+        if (!w.ffn_a1 || !w.ffn_b1 || !w.ffn_a2 || !w.ffn_b2 || !grad_ffn_a1 || !grad_ffn_b1 || !grad_ffn_a2 || !grad_ffn_b2)
+            return set_error(FTMI_ERR_INVALID, "wan_lora_ffn_block_backward: feed-forward adapters / gradient buffers missing");
+        f.a1 = w.ffn_a1; f.b1 = w.ffn_b1; f.a2 = w.ffn_a2; f.b2 = w.ffn_b2;
+        f.ga1 = grad_ffn_a1; f.gb1 = grad_ffn_b1; f.ga2 = grad_ffn_a2; f.gb2 = grad_ffn_b2;
+    }
+    const ftmi_wan_i2v_lora_block_config ci = i2v_cfg(c);
+    return lora_backward(lora_cfg(ci), w.base, img_ctx(ci, img_params, enc_img), x, enc, mod, rope_cos, rope_sin, dout, dx, denc, grad_a, grad_b, saved, saved_bytes,
+                         scratch, scratch_bytes, st, f);
 }
 
 }  // namespace ftmi

@@ -22,7 +22,8 @@ import ctypes
 import os
 
 from .. import _lib, ops
-from .._lib import WanBlockConfig, WanI2VLoraBlockConfig, WanLoraBlockConfig, WanLoraBlockWeights, check, ptr, stream_ptr
+from .._lib import (WanBlockConfig, WanI2VLoraBlockConfig, WanLoraBlockConfig, WanLoraBlockWeights, WanLoraFfnBlockConfig, WanLoraFfnBlockWeights, check, ptr,
+                     stream_ptr)
 
 bf16 = torch.bfloat16
 _NATIVE_SCRATCH: Dict[int, torch.Tensor] = {}  # device index -> byte buffer shared by every natively run block on that device (one stream at a time)
@@ -123,6 +124,9 @@ class WanImageLayout:
 # block_backward issue: the second implementation the tests compare the C calls with (``native = False`` / ``FTMI_NATIVE_BLOCKS=0``).
 # Adapter order inside lora_A [8, r, D] / lora_B [8, D, r] (the projections the recipe's regex "blocks.*(to_q|to_k|to_v|to_out.0)" selects: BOTH attentions)
 LORA_TARGETS = ("attn1.to_q", "attn1.to_k", "attn1.to_v", "attn1.to_out.0", "attn2.to_q", "attn2.to_k", "attn2.to_v", "attn2.to_out.0")
+# the two feed-forward projections a target_modules spelled "...|ffn.net.0.proj|ffn.net.2" adds: rectangular, so their adapters are four Parameters of their own
+# (``MI355XWanBlock.lora_ffn``: A_1 [r, D], B_1 [F, r], A_2 [r, F], B_2 [D, r], in this order)
+LORA_FFN_TARGETS = ("ffn.net.0.proj", "ffn.net.2")
 _TWINS = (("w_qkv1_t", "w_qkv1"), ("w_o1_t", "attn1.to_out.0.weight"), ("w_q2_t", "attn2.to_q.weight"), ("w_kv2_t", "w_kv2"), ("w_o2_t", "attn2.to_out.0.weight"),
           ("w_f1_t", "ffn.net.0.proj.weight"), ("w_f2_t", "ffn.net.2.weight"))
 
@@ -133,6 +137,8 @@ class _Lora(NamedTuple):
     b: Optional[torch.Tensor] = None  # fp32 [8, D, r]
     ga: Optional[torch.Tensor] = None
     gb: Optional[torch.Tensor] = None
+    f: Optional[Tuple[torch.Tensor, ...]] = None   # the feed-forward adapters (A_1 [r, D], B_1 [F, r], A_2 [r, F], B_2 [D, r]), or None
+    gf: Optional[Tuple[torch.Tensor, ...]] = None  # their gradients, same order
 
     @property
     def r(self) -> int:
@@ -146,23 +152,27 @@ class _Acts(NamedTuple):
     n3: Any; act: Any; pre: Any; f: Any; xa_qkv: Any; xa_o1: Any; xa_q2: Any; xa_kv2: Any; xa_o2: Any
     # image-to-video: the image tokens' k|v rows, their normed keys, the image attention's lse and the SUMMED attention output (o2 stays the text branch's own)
     kvi: Any = None; kin: Any = None; lse_i: Any = None; o2s: Any = None
+    xa_f1: Any = None; xa_f2: Any = None  # the feed-forward adapters' down-projected rows; with them n3 and act stay (dA_1 and dA_2 read them)
 
     def for_frozen_base(self) -> "_Acts":
-        return self._replace(a1=None, n3=None, act=None, f=None)
+        return self._replace(a1=None, f=None) if self.xa_f1 is not None else self._replace(a1=None, n3=None, act=None, f=None)
 
 
-def _lora_linear_fwd(x, w, bias, adp: int, nadp: int, a_sp, b_ext, r: int, s: float):
-    """[rows, nadp D] = x W^T + b + s (x A^T) B^T for the adapters adp .. adp + nadp - 1 on one input: the two launches of csrc/wan_dit.hip proj_fwd.
-    Returns (y, xa [rows, 3 nadp r])."""
+def _lora_linear_fwd(x, w, bias, nadp: int, a_sp, b_ext, r: int, s: float, gelu: bool = False):
+    """[rows, N] = x W^T + b + s (x A^T) B^T for ``nadp`` adapters on one input (N = nadp N_out; a_sp [2 nadp r, K], b_ext [N, 3r]): the two launches of
+    csrc/wan_dit.hip proj_fwd.  Returns (y, xa [rows, 3 nadp r], pre); ``gelu``: y = gelu_tanh(the sum), pre = the sum (else None)."""
     if r == 0:
-        return ops.gemm_nt(x, w, bias), None
-    rows, D = x.shape
+        y, pre = ops.gemm_nt(x, w, bias, epilogue=1, want_out2=True) if gelu else (ops.gemm_nt(x, w, bias), None)
+        return y, None, pre
+    rows, K = x.shape
+    N = w.shape[0]
     xa = torch.empty((rows, 3 * nadp * r), dtype=bf16, device=x.device)
-    ops.gemm_nt_ex(x, a_sp[adp:adp + nadp].reshape(2 * nadp * r, D), xa, M=rows, N=2 * nadp * r, K=D, alpha=s, split_r=r, variant=8)
-    y = torch.empty((rows, nadp * D), dtype=bf16, device=x.device)
-    grp = dict(x2_grp_n=D, x2_grp_stride=3 * r) if nadp > 1 else {}
-    ops.gemm_nt_ex(x, w, y, M=rows, N=nadp * D, K=D, bias=bias, x2=xa, w2=b_ext[adp:adp + nadp].reshape(nadp * D, 3 * r), K2=3 * r, variant=8, **grp)
-    return y, xa
+    ops.gemm_nt_ex(x, a_sp, xa, M=rows, N=2 * nadp * r, K=K, alpha=s, split_r=r, variant=8)
+    y = torch.empty((rows, N), dtype=bf16, device=x.device)
+    pre = torch.empty_like(y) if gelu else None
+    grp = dict(x2_grp_n=N // nadp, x2_grp_stride=3 * r) if nadp > 1 else {}
+    ops.gemm_nt_ex(x, w, y, M=rows, N=N, K=K, bias=bias, x2=xa, w2=b_ext, K2=3 * r, variant=8, epilogue=1 if gelu else 0, out2=pre, **grp)
+    return y, xa, pre
 
 
 def _linear_grads(dy, inp, gw, gbias):
@@ -172,22 +182,26 @@ def _linear_grads(dy, inp, gw, gbias):
         ops.wan_colsum(dy, gbias)
 
 
-def _lora_linear_bwd(x, dy, w_t, adp: int, nadp: int, xa, bt_sp, at_ext, r: int, s: float, ga, gb, need_dx: bool = True, gw=None, gbias=None):
-    """csrc/wan_dit.hip proj_bwd, in its order: gw += dY^T x and gbias += column sums (a training base); dx = dY W (+ dXA A); gb[adp ..] += dY^T XA,
-    ga[adp ..] += dXA^T x."""
+def _lora_linear_bwd(x, dy, w_t, nadp: int, xa, bt_sp, at_ext, r: int, s: float, ga, gb, need_dx: bool = True, gw=None, gbias=None, pre=None):
+    """csrc/wan_dit.hip proj_bwd, in its order, for x [rows, K], dy [rows, N = nadp N_out]: gw += dY^T x and gbias += column sums (a training base);
+    dXA = s dY B (bt_sp [2 nadp r, N_out]); dx = dY W (+ dXA A: at_ext [K, 3 nadp r]), times gelu_tanh'(pre) when ``pre`` is given; gb [N, r] += dY^T XA,
+    ga [nadp r, K] += dXA^T x."""
     _linear_grads(dy, x, gw, gbias)
-    rows, D = x.shape
-    if r == 0:
-        return ops.gemm_nt(dy, w_t, None) if need_dx else None
+    epi = dict(epilogue=3, aux=pre) if pre is not None else {}
+    if r == 0:  # (x may be None here: a frozen base without adapters on this projection does not keep it)
+        return ops.gemm_nt(dy, w_t, None, **epi) if need_dx else None
+    rows, K = x.shape
+    N = dy.shape[1]
+    No = N // nadp
     dxa = torch.empty((rows, 3 * nadp * r), dtype=bf16, device=x.device)
-    grp = dict(xk_grp_n=2 * r, xk_grp_stride=D) if nadp > 1 else {}
-    ops.gemm_nt_ex(dy, bt_sp[adp:adp + nadp].reshape(2 * nadp * r, D), dxa, M=rows, N=2 * nadp * r, K=D, alpha=s, split_r=r, variant=8, **grp)
+    grp = dict(xk_grp_n=2 * r, xk_grp_stride=No) if nadp > 1 else {}
+    ops.gemm_nt_ex(dy, bt_sp, dxa, M=rows, N=2 * nadp * r, K=No, alpha=s, split_r=r, variant=8, **grp)
     dx = None
     if need_dx:
-        dx = torch.empty((rows, D), dtype=bf16, device=x.device)
-        ops.gemm_nt_ex(dy, w_t, dx, M=rows, N=D, K=nadp * D, x2=dxa, w2=at_ext[:, adp * 3 * r:(adp + nadp) * 3 * r], K2=3 * nadp * r, variant=8)
-    ops.gemm_tn_ex(dy, xa, gb[adp:adp + nadp].view(nadp * D, r), M=rows, P=nadp * D, Q=r, v_fold=r, **(dict(v_grp_p=D, v_grp_stride=3 * r) if nadp > 1 else {}))
-    ops.gemm_tn_ex(dxa, x, ga[adp:adp + nadp].view(nadp * r, D), M=rows, P=nadp * r, Q=D, u_fold=r, **(dict(u_grp_p=r, u_grp_stride=3 * r) if nadp > 1 else {}))
+        dx = torch.empty((rows, K), dtype=bf16, device=x.device)
+        ops.gemm_nt_ex(dy, w_t, dx, M=rows, N=K, K=N, x2=dxa, w2=at_ext, K2=3 * nadp * r, variant=8, **epi)
+    ops.gemm_tn_ex(dy, xa, gb, M=rows, P=N, Q=r, v_fold=r, **(dict(v_grp_p=No, v_grp_stride=3 * r) if nadp > 1 else {}))
+    ops.gemm_tn_ex(dxa, x, ga, M=rows, P=nadp * r, Q=K, u_fold=r, **(dict(u_grp_p=r, u_grp_stride=3 * r) if nadp > 1 else {}))
     return dx
 
 
@@ -202,7 +216,17 @@ def _block_forward(blk: "MI355XWanBlock", x, enc, mod, rope, lora: _Lora, need_o
     if r:
         a_sp = torch.stack([ops.lora_split(lora.a[i], sp=True)[0] for i in range(8)])
         b_ext = torch.stack([ops.lora_split(lora.b[i], ext=True)[0] for i in range(8)])
-    lin = lambda t, w, b, adp, nadp: _lora_linear_fwd(t, w, b, adp, nadp, a_sp, b_ext, r, s)
+
+    def lin(t, w, b, adp, nadp):  # the attention adapters adp .. adp + nadp - 1 (all [r, D] / [D, r])
+        if not r:
+            return _lora_linear_fwd(t, w, b, nadp, None, None, 0, s)[:2]
+        return _lora_linear_fwd(t, w, b, nadp, a_sp[adp:adp + nadp].reshape(2 * nadp * r, D), b_ext[adp:adp + nadp].reshape(nadp * D, 3 * r), r, s)[:2]
+
+    f_sp = f_ext = (None, None)  # the feed-forward adapters' operand copies: (A_1, A_2) as row planes, (B_1, B_2) as K-extension columns
+    rf = r if lora.f is not None else 0
+    if rf:
+        f_sp = tuple(ops.lora_split(lora.f[i], sp=True)[0] for i in (0, 2))
+        f_ext = tuple(ops.lora_split(lora.f[i], ext=True)[0] for i in (1, 3))
     x2d, enc2d = x.view(M, D), enc.view(B * T, D)
     heads = lambda t, n: t.view(B, n, H, hd).permute(0, 2, 1, 3)  # [rows, D] view (any row stride) -> [B, H, n, hd]
     tok = lambda t: t.permute(0, 2, 1, 3).reshape(t.shape[0] * t.shape[2], D)  # attention output [B, H, n, hd] laid out [B, n, H, hd] -> [rows, D]
@@ -231,12 +255,16 @@ def _block_forward(blk: "MI355XWanBlock", x, enc, mod, rope, lora: _Lora, need_o
     x2 = ops.wan_gate_res(x1, a2, S)
     # feed-forward
     n3 = ops.wan_ln(x2, S, shift=mod[:, 3], scale=mod[:, 4], eps=eps)
-    act, pre = ops.gemm_nt(n3, P("ffn.net.0.proj.weight"), P("ffn.net.0.proj.bias"), epilogue=1, want_out2=True)  # GELU-tanh, pre-activation kept
-    f = out = None
+    act, xa_f1, pre = _lora_linear_fwd(n3, P("ffn.net.0.proj.weight"), P("ffn.net.0.proj.bias"), 1, f_sp[0], f_ext[0], rf, s, gelu=True)  # GELU-tanh, pre-activation kept
+    f = out = xa_f2 = None
     if need_out:
-        f = ops.gemm_nt(act, P("ffn.net.2.weight"), P("ffn.net.2.bias"))
+        f, xa_f2, _ = _lora_linear_fwd(act, P("ffn.net.2.weight"), P("ffn.net.2.bias"), 1, f_sp[1], f_ext[1], rf, s)
         out = ops.wan_gate_res(x2, f, S, gate=mod[:, 5]).view(B, S, D)
-    return out, _Acts(n1, qkv, qn, kn, o1, lse1, a1, x1, n2, q2, kv2, q2n, k2n, o2, lse2, x2, n3, act, pre, f, xa_qkv, xa_o1, xa_q2, xa_kv2, xa_o2, kvi, kin, lse_i, o2s)
+    elif rf:  # the recomputation pass: net.2's down-projected rows are read by dB_2, its GEMM is not needed
+        xa_f2 = torch.empty((M, 3 * rf), dtype=bf16, device=x.device)
+        ops.gemm_nt_ex(act, f_sp[1], xa_f2, M=M, N=2 * rf, K=blk.ffn_dim, alpha=s, split_r=rf, variant=8)
+    return out, _Acts(n1, qkv, qn, kn, o1, lse1, a1, x1, n2, q2, kv2, q2n, k2n, o2, lse2, x2, n3, act, pre, f, xa_qkv, xa_o1, xa_q2, xa_kv2, xa_o2, kvi, kin, lse_i, o2s,
+                      xa_f1, xa_f2)
 
 
 def _block_backward(blk: "MI355XWanBlock", acts: _Acts, x, enc, mod, rope, dout, lora: _Lora, train_base: bool, need_denc: bool = True):
@@ -257,7 +285,17 @@ def _block_backward(blk: "MI355XWanBlock", acts: _Acts, x, enc, mod, rope, dout,
         at_ext = torch.cat([ops.lora_split(lora.a[i], t_ext=True)[0] for i in range(8)], dim=1)  # the eight adapters side by side: [D, 24r]
 
     def lin(t, dy, w_t, adp, nadp, xa, need_dx=True, gw=None, gbias=None):
-        return _lora_linear_bwd(t, dy, w_t, adp, nadp, xa, bt_sp, at_ext, r, s, lora.ga, lora.gb, need_dx, gw, gbias)
+        if not r:
+            return _lora_linear_bwd(t, dy, w_t, nadp, None, None, None, 0, s, None, None, need_dx, gw, gbias)
+        return _lora_linear_bwd(t, dy, w_t, nadp, xa, bt_sp[adp:adp + nadp].reshape(2 * nadp * r, D), at_ext[:, adp * 3 * r:(adp + nadp) * 3 * r], r, s,
+                                lora.ga[adp:adp + nadp].view(nadp * r, D), lora.gb[adp:adp + nadp].view(nadp * D, r), need_dx, gw, gbias)
+
+    rf = r if lora.f is not None else 0
+    f_tsp = f_text = gf = (None,) * 4  # the feed-forward adapters: B^T as row planes, A^T as K-extension columns, per adapter
+    if rf:
+        f_tsp = tuple(ops.lora_split(lora.f[i], t_sp=True)[0] if i in (1, 3) else None for i in range(4))
+        f_text = tuple(ops.lora_split(lora.f[i], t_ext=True)[0] if i in (0, 2) else None for i in range(4))
+        gf = lora.gf
 
     x2d, enc2d = x.view(M, D), enc.view(B * T, D)
     dout = dout.contiguous().view(M, D)
@@ -265,10 +303,11 @@ def _block_backward(blk: "MI355XWanBlock", acts: _Acts, x, enc, mod, rope, dout,
     tok = lambda t: t.permute(0, 2, 1, 3).reshape(t.shape[0] * t.shape[2], D)
     # feed-forward branch: out = x2 + f * gate_ff
     df = ops.wan_gate_res_bwd(dout, c.f if train_base else None, mod[:, 5], S, dgate=DM(5))
-    _linear_grads(df, c.act, G("ffn.net.2.weight"), G("ffn.net.2.bias"))
-    dpre = ops.gemm_nt(df, Wt["ffn.net.2.weight"], None, epilogue=3, aux=c.pre)  # (d f W2) * gelu'(pre)
-    _linear_grads(dpre, c.n3, G("ffn.net.0.proj.weight"), G("ffn.net.0.proj.bias"))
-    dn3 = ops.gemm_nt(dpre, Wt["ffn.net.0.proj.weight"], None)
+    # (d f W2 [+ dXA_2 A_2]) * gelu'(pre); act and n3 are read by the base's weight gradients and by the feed-forward adapters' dA only
+    dpre = _lora_linear_bwd(c.act, df, Wt["ffn.net.2.weight"], 1, c.xa_f2, f_tsp[3], f_text[2], rf, s, gf[2], gf[3], gw=G("ffn.net.2.weight"),
+                            gbias=G("ffn.net.2.bias"), pre=c.pre)
+    dn3 = _lora_linear_bwd(c.n3, dpre, Wt["ffn.net.0.proj.weight"], 1, c.xa_f1, f_tsp[1], f_text[0], rf, s, gf[0], gf[1], gw=G("ffn.net.0.proj.weight"),
+                           gbias=G("ffn.net.0.proj.bias"))
     dx2 = ops.wan_ln_bwd(c.x2, dn3, S, scale=mod[:, 4], eps=eps, dres=dout, red1=DM(3), red2=DM(4), red_per_batch=train_base)
     # cross-attention branch: x2 = x1 + a2
     do2 = lin(tok(c.o2 if c.o2s is None else c.o2s), dx2, Wt["attn2.to_out.0.weight"], 7, 1, c.xa_o2, gw=G("attn2.to_out.0.weight"), gbias=G("attn2.to_out.0.bias"))
@@ -375,12 +414,21 @@ class _WanBlockNativeFunction(torch.autograd.Function):
         return None, dx, denc, dmod.to(ctx.temb_dtype), None, None
 
 
-def _grad_targets(blk: "MI355XWanBlock", lora_a, lora_b):
-    """Where the adapter gradients go: the step object's flat views (added in place), or fresh tensors returned to autograd."""
+def _planned(nbytes: int) -> int:
+    """A byte planner's answer; 0 means the library refused the configuration (the reason is in ftmi_last_error)."""
+    if nbytes == 0:
+        raise ValueError(f"Wan LoRA block: {_lib.last_error()}")
+    return nbytes
+
+
+def _grad_targets(blk: "MI355XWanBlock", lora_a, lora_b, ffn=None):
+    """Where the adapter gradients go: the step object's flat views (added in place), or fresh tensors returned to autograd.  Returns (own, ga, gb, gf):
+    gf = the four gradients of the feed-forward adapters ``ffn``, or None."""
     if lora_a is None:
-        return False, None, None
+        return False, None, None, None
     own = blk._grad_a_view is not None
-    return own, (blk._grad_a_view if own else torch.zeros_like(lora_a)), (blk._grad_b_view if own else torch.zeros_like(lora_b))
+    gf = None if ffn is None else (blk._grad_ffn_views if own else tuple(torch.zeros_like(t) for t in ffn))
+    return own, (blk._grad_a_view if own else torch.zeros_like(lora_a)), (blk._grad_b_view if own else torch.zeros_like(lora_b)), gf
 
 
 class _WanLoRABlockFunction(torch.autograd.Function):
@@ -393,37 +441,39 @@ class _WanLoRABlockFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        dx, denc, ga, gb = _WanLoRABlockFunction._bwd(ctx, dout)
+        dx, denc, ga, gb, _ = _WanLoRABlockFunction._bwd(ctx, dout)
         return None, dx, denc, None, None, None, ga, gb
 
     @staticmethod
-    def _fwd(ctx, blk, x, enc, enc_img, temb, rope_cos, rope_sin, lora_a, lora_b):
+    def _fwd(ctx, blk, x, enc, enc_img, temb, rope_cos, rope_sin, lora_a, lora_b, ffn=None):
         mod = (blk.param("scale_shift_table").float() + temb.float()).contiguous()
-        out, acts = _block_forward(blk, x, enc, mod, (rope_cos, rope_sin), _Lora(lora_a, lora_b), enc_img=enc_img)
-        ctx.blk, ctx.rope, ctx.has_lora, ctx.has_img = blk, (rope_cos, rope_sin), lora_a is not None, enc_img is not None
+        out, acts = _block_forward(blk, x, enc, mod, (rope_cos, rope_sin), _Lora(lora_a, lora_b, f=ffn), enc_img=enc_img)
+        ctx.blk, ctx.rope, ctx.has_lora, ctx.has_img, ctx.has_ffn = blk, (rope_cos, rope_sin), lora_a is not None, enc_img is not None, ffn is not None
         ctx.recompute = bool(blk.gradient_checkpointing)
         la, lb = (lora_a, lora_b) if lora_a is not None else (x.new_empty(0), x.new_empty(0))
-        ctx.save_for_backward(x, enc, mod, la, lb, enc_img if enc_img is not None else x.new_empty(0))
+        ctx.save_for_backward(x, enc, mod, la, lb, enc_img if enc_img is not None else x.new_empty(0), *(ffn or ()))
         ctx.acts = None if ctx.recompute else acts.for_frozen_base()
         return out
 
     @staticmethod
     def _bwd(ctx, dout):
+        """Returns (dx, denc, ga, gb, gf): gf = the feed-forward adapters' four gradients (None when the step object owns them, or without such adapters)."""
         blk, rope = ctx.blk, ctx.rope
-        x, enc, mod, lora_a, lora_b, enc_img = ctx.saved_tensors
+        x, enc, mod, lora_a, lora_b, enc_img = ctx.saved_tensors[:6]
+        ffn = tuple(ctx.saved_tensors[6:10]) if ctx.has_ffn else None
         if not ctx.has_lora:
             lora_a = lora_b = None
         if not ctx.has_img:
             enc_img = None
         acts, ctx.acts = ctx.acts, None
         if ctx.recompute:
-            acts = _block_forward(blk, x, enc, mod, rope, _Lora(lora_a, lora_b), need_out=False, enc_img=enc_img)[1].for_frozen_base()
-        own, ga, gb = _grad_targets(blk, lora_a, lora_b)
-        dx, denc, _ = _block_backward(blk, acts, x, enc, mod, rope, dout, _Lora(lora_a, lora_b, ga, gb), train_base=False, need_denc=ctx.needs_input_grad[2])
+            acts = _block_forward(blk, x, enc, mod, rope, _Lora(lora_a, lora_b, f=ffn), need_out=False, enc_img=enc_img)[1].for_frozen_base()
+        own, ga, gb, gf = _grad_targets(blk, lora_a, lora_b, ffn)
+        dx, denc, _ = _block_backward(blk, acts, x, enc, mod, rope, dout, _Lora(lora_a, lora_b, ga, gb, ffn, gf), train_base=False, need_denc=ctx.needs_input_grad[2])
         if own:
             blk._backward_done()
-            ga = gb = None
-        return dx, denc, ga, gb
+            ga = gb = gf = None
+        return dx, denc, ga, gb, gf
 
 
 class _WanI2VLoRABlockFunction(torch.autograd.Function):
@@ -435,8 +485,22 @@ class _WanI2VLoRABlockFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        dx, denc, ga, gb = _WanLoRABlockFunction._bwd(ctx, dout)
+        dx, denc, ga, gb, _ = _WanLoRABlockFunction._bwd(ctx, dout)
         return None, dx, denc, None, None, None, ga, gb, None
+
+
+class _WanFfnLoRABlockFunction(torch.autograd.Function):
+    """``_WanLoRABlockFunction`` with adapters on ffn.net.0.proj and ffn.net.2 as well (``fa1`` [r, D], ``fb1`` [F, r], ``fa2`` [r, F], ``fb2`` [D, r]);
+    ``enc_img``: the image context of an image-to-video block, or None."""
+
+    @staticmethod
+    def forward(ctx, blk: "MI355XWanBlock", x, enc, temb, rope_cos, rope_sin, lora_a, lora_b, enc_img, fa1, fb1, fa2, fb2):
+        return _WanLoRABlockFunction._fwd(ctx, blk, x, enc, enc_img, temb, rope_cos, rope_sin, lora_a, lora_b, (fa1, fb1, fa2, fb2))
+
+    @staticmethod
+    def backward(ctx, dout):
+        dx, denc, ga, gb, gf = _WanLoRABlockFunction._bwd(ctx, dout)
+        return (None, dx, denc, None, None, None, ga, gb, None) + (gf or (None,) * 4)
 
 
 class _WanLoRABlockNativeFunction(torch.autograd.Function):
@@ -445,11 +509,15 @@ class _WanLoRABlockNativeFunction(torch.autograd.Function):
     refills ``saved`` inside the backward (the forward call with ``out = NULL``)."""
 
     @staticmethod
-    def _args(blk: "MI355XWanBlock", B: int, S: int, T: int, lora_a, lora_b, backward: bool, TI: Optional[int] = None):
+    def _args(blk: "MI355XWanBlock", B: int, S: int, T: int, lora_a, lora_b, backward: bool, TI: Optional[int] = None, ffn=None, ffn_entry: bool = False):
         kw = dict(B=B, S=S, T=T, D=blk.dim, H=blk.heads, F=blk.ffn_dim, eps=float(blk.eps), gemm_variant=8, r=0 if lora_a is None else int(lora_a.shape[1]),
                   lora_scale=float(blk.lora_scale))
-        cfg = WanLoraBlockConfig(**kw) if TI is None else WanI2VLoraBlockConfig(TI=TI, **kw)  # TI given: the ftmi_wan_i2v_lora_block_* entries
-        w = WanLoraBlockWeights()
+        if ffn_entry:  # the ftmi_wan_lora_ffn_block_* entries: image context or not, feed-forward adapters or not
+            cfg, wf = WanLoraFfnBlockConfig(TI=TI or 0, ffn=int(ffn is not None), **kw), WanLoraFfnBlockWeights()
+            w = wf.base
+        else:
+            cfg = WanLoraBlockConfig(**kw) if TI is None else WanI2VLoraBlockConfig(TI=TI, **kw)  # TI given: the ftmi_wan_i2v_lora_block_* entries
+            w = wf = WanLoraBlockWeights()
         params = blk._params()
         if params.numel() != blk.layout.total or not params.is_contiguous():
             raise RuntimeError("Wan block: the flat parameter buffer does not have the layout the C orchestrator expects")
@@ -464,12 +532,26 @@ class _WanLoRABlockNativeFunction(torch.autograd.Function):
             la, lb = lora_a.contiguous(), lora_b.contiguous()
             keep += [la, lb]
             w.lora_a, w.lora_b = ptr(la), ptr(lb)
-        return cfg, w, keep
+        if ffn is not None:
+            ffn = [t.contiguous() for t in ffn]
+            keep += ffn
+            wf.ffn_a1, wf.ffn_b1, wf.ffn_a2, wf.ffn_b2 = (ptr(t) for t in ffn)
+        return cfg, wf, keep
 
     @staticmethod
-    def _forward_call(blk, x, enc, mod, rope_cos, rope_sin, lora_a, lora_b, out, enc_img=None):
+    def _forward_call(blk, x, enc, mod, rope_cos, rope_sin, lora_a, lora_b, out, enc_img=None, ffn=None):
         B, S, _ = x.shape
         lib = _lib.load()
+        if ffn is not None or blk.ffn_entry:
+            TI = 0 if enc_img is None else enc_img.shape[1]
+            cfg, w, keep = _WanLoRABlockNativeFunction._args(blk, B, S, enc.shape[1], lora_a, lora_b, backward=False, TI=TI, ffn=ffn, ffn_entry=True)
+            saved = torch.empty(_planned(lib.ftmi_wan_lora_ffn_block_saved_bytes(ctypes.byref(cfg))), dtype=torch.uint8, device=x.device)
+            scratch = _native_scratch(x.device, _planned(lib.ftmi_wan_lora_ffn_block_scratch_bytes(ctypes.byref(cfg))))
+            img = blk._img_params() if TI > 0 else None
+            check(lib.ftmi_wan_lora_ffn_block_forward(ctypes.byref(cfg), ctypes.byref(w), ptr(img), ptr(x), ptr(enc), ptr(enc_img if TI > 0 else None), ptr(mod),
+                                                      ptr(rope_cos), ptr(rope_sin), ptr(out), ptr(saved), saved.numel(), ptr(scratch), scratch.numel(), stream_ptr()),
+                  "ftmi_wan_lora_ffn_block_forward")
+            return saved
         if enc_img is not None:
             cfg, w, keep = _WanLoRABlockNativeFunction._args(blk, B, S, enc.shape[1], lora_a, lora_b, backward=False, TI=enc_img.shape[1])
             saved = torch.empty(lib.ftmi_wan_i2v_lora_block_saved_bytes(ctypes.byref(cfg)), dtype=torch.uint8, device=x.device)
@@ -492,40 +574,52 @@ class _WanLoRABlockNativeFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        dx, denc, ga, gb = _WanLoRABlockNativeFunction._bwd(ctx, dout)
+        dx, denc, ga, gb, _ = _WanLoRABlockNativeFunction._bwd(ctx, dout)
         return None, dx, denc, None, None, None, ga, gb
 
     @staticmethod
-    def _fwd(ctx, blk, x, enc, enc_img, temb, rope_cos, rope_sin, lora_a, lora_b):
+    def _fwd(ctx, blk, x, enc, enc_img, temb, rope_cos, rope_sin, lora_a, lora_b, ffn=None):
         mod = (blk.param("scale_shift_table").float() + temb.float()).contiguous()
         out = torch.empty_like(x)
-        saved = _WanLoRABlockNativeFunction._forward_call(blk, x, enc, mod, rope_cos, rope_sin, lora_a, lora_b, out, enc_img)
-        ctx.blk, ctx.rope, ctx.has_lora, ctx.has_img = blk, (rope_cos, rope_sin), lora_a is not None, enc_img is not None
+        saved = _WanLoRABlockNativeFunction._forward_call(blk, x, enc, mod, rope_cos, rope_sin, lora_a, lora_b, out, enc_img, ffn)
+        ctx.blk, ctx.rope, ctx.has_lora, ctx.has_img, ctx.has_ffn = blk, (rope_cos, rope_sin), lora_a is not None, enc_img is not None, ffn is not None
         ctx.recompute = bool(blk.gradient_checkpointing)
         la, lb = (lora_a, lora_b) if lora_a is not None else (x.new_empty(0), x.new_empty(0))
-        keep = (x, enc, mod, la, lb, enc_img if enc_img is not None else x.new_empty(0))
+        keep = (x, enc, mod, la, lb, enc_img if enc_img is not None else x.new_empty(0)) + tuple(ffn or ())
         ctx.save_for_backward(*(keep if ctx.recompute else keep + (saved,)))
         return out
 
     @staticmethod
     def _bwd(ctx, dout):
+        """Returns (dx, denc, ga, gb, gf) like ``_WanLoRABlockFunction._bwd``."""
         blk, rope = ctx.blk, ctx.rope
         x, enc, mod, lora_a, lora_b, enc_img = ctx.saved_tensors[:6]
+        ffn = tuple(ctx.saved_tensors[6:10]) if ctx.has_ffn else None
         if not ctx.has_lora:
             lora_a = lora_b = None
         if not ctx.has_img:
             enc_img = None
         if ctx.recompute:
-            saved = _WanLoRABlockNativeFunction._forward_call(blk, x, enc, mod, rope[0], rope[1], lora_a, lora_b, None, enc_img)
+            saved = _WanLoRABlockNativeFunction._forward_call(blk, x, enc, mod, rope[0], rope[1], lora_a, lora_b, None, enc_img, ffn)
         else:
-            saved = ctx.saved_tensors[6]
+            saved = ctx.saved_tensors[-1]
         B, S, _ = x.shape
         dout = dout.contiguous()
-        own, ga, gb = _grad_targets(blk, lora_a, lora_b)
+        own, ga, gb, gf = _grad_targets(blk, lora_a, lora_b, ffn)
         lib = _lib.load()
         dx = torch.empty_like(x)
         denc = torch.empty_like(enc) if ctx.needs_input_grad[2] else None  # frozen text embedder: no gradient into the text rows, its GEMM is skipped
-        if enc_img is not None:
+        if ffn is not None or blk.ffn_entry:
+            TI = 0 if enc_img is None else enc_img.shape[1]
+            cfg, w, keep = _WanLoRABlockNativeFunction._args(blk, B, S, enc.shape[1], lora_a, lora_b, backward=True, TI=TI, ffn=ffn, ffn_entry=True)
+            scratch = _native_scratch(x.device, _planned(lib.ftmi_wan_lora_ffn_block_scratch_bytes(ctypes.byref(cfg))))
+            img = blk._img_params() if TI > 0 else None
+            g4 = gf or (None,) * 4
+            check(lib.ftmi_wan_lora_ffn_block_backward(ctypes.byref(cfg), ctypes.byref(w), ptr(img), ptr(x), ptr(enc), ptr(enc_img if TI > 0 else None), ptr(mod),
+                                                       ptr(rope[0]), ptr(rope[1]), ptr(dout), ptr(dx), ptr(denc), ptr(ga), ptr(gb), ptr(g4[0]), ptr(g4[1]),
+                                                       ptr(g4[2]), ptr(g4[3]), ptr(saved), saved.numel(), ptr(scratch), scratch.numel(), stream_ptr()),
+                  "ftmi_wan_lora_ffn_block_backward")
+        elif enc_img is not None:
             cfg, w, keep = _WanLoRABlockNativeFunction._args(blk, B, S, enc.shape[1], lora_a, lora_b, backward=True, TI=enc_img.shape[1])
             scratch = _native_scratch(x.device, lib.ftmi_wan_i2v_lora_block_scratch_bytes(ctypes.byref(cfg)))
             img = blk._img_params() if cfg.TI > 0 else None
@@ -540,8 +634,8 @@ class _WanLoRABlockNativeFunction(torch.autograd.Function):
                   "ftmi_wan_lora_block_backward")
         if own:
             blk._backward_done()
-            ga = gb = None
-        return dx, denc, ga, gb
+            ga = gb = gf = None
+        return dx, denc, ga, gb, gf
 
 
 class _WanI2VLoRABlockNativeFunction(torch.autograd.Function):
@@ -553,8 +647,21 @@ class _WanI2VLoRABlockNativeFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        dx, denc, ga, gb = _WanLoRABlockNativeFunction._bwd(ctx, dout)
+        dx, denc, ga, gb, _ = _WanLoRABlockNativeFunction._bwd(ctx, dout)
         return None, dx, denc, None, None, None, ga, gb, None
+
+
+class _WanFfnLoRABlockNativeFunction(torch.autograd.Function):
+    """``_WanFfnLoRABlockFunction`` with ONE C call per direction: ``ftmi_wan_lora_ffn_block_forward / _backward`` (``enc_img`` None: TI = 0)."""
+
+    @staticmethod
+    def forward(ctx, blk: "MI355XWanBlock", x, enc, temb, rope_cos, rope_sin, lora_a, lora_b, enc_img, fa1, fb1, fa2, fb2):
+        return _WanLoRABlockNativeFunction._fwd(ctx, blk, x, enc, enc_img, temb, rope_cos, rope_sin, lora_a, lora_b, (fa1, fb1, fa2, fb2))
+
+    @staticmethod
+    def backward(ctx, dout):
+        dx, denc, ga, gb, gf = _WanLoRABlockNativeFunction._bwd(ctx, dout)
+        return (None, dx, denc, None, None, None, ga, gb, None) + (gf or (None,) * 4)
 
 
 class MI355XWanBlock(nn.Module):
@@ -563,6 +670,9 @@ class MI355XWanBlock(nn.Module):
 
     # one C call per direction (csrc/wan_dit.hip); False (or FTMI_NATIVE_BLOCKS=0 in the environment): the per-kernel composition from Python -- the tests compare the two
     native = os.environ.get("FTMI_NATIVE_BLOCKS", "1") != "0"
+    # True: a natively run LoRA block goes through ftmi_wan_lora_ffn_block_* also WITHOUT feed-forward adapters (with them it always does) -- the tests compare
+    # the entries bit for bit
+    ffn_entry = False
 
     def __init__(self, dim: int = 1536, heads: int = 12, ffn_dim: int = 8960, eps: float = 1e-6, device: Optional[torch.device] = None,
                  added_kv_proj_dim: Optional[int] = None):
@@ -591,10 +701,12 @@ class MI355XWanBlock(nn.Module):
         self.frozen = False
         self.lora_A: Optional[nn.Parameter] = None  # [8, r, D]
         self.lora_B: Optional[nn.Parameter] = None  # [8, D, r]
+        self.lora_ffn: Optional[nn.ParameterList] = None  # add_adapter(ffn=True): A_1 [r, D], B_1 [F, r], A_2 [r, F], B_2 [D, r] of ffn.net.0.proj / ffn.net.2
         self.lora_scale, self.lora_rank_user = 0.0, 0
         self.gradient_checkpointing = False  # True: the block keeps only its input and refills its saved activations inside the backward
         self._grad_a_view: Optional[torch.Tensor] = None  # the step object's flat gradient views (wan/trainer.py MI355XWanLoRAStep): added to in place
         self._grad_b_view: Optional[torch.Tensor] = None
+        self._grad_ffn_views: Optional[Tuple[torch.Tensor, ...]] = None
 
     # -- parameter / gradient views -----------------------------------------------------------------------------------------------------------
     def _params(self) -> torch.Tensor:
@@ -648,19 +760,55 @@ class MI355XWanBlock(nn.Module):
         """Run the block with frozen base weights (input gradients only); ``add_adapter`` implies it."""
         self.frozen = True
 
-    def add_adapter(self, rank: int = 32, lora_alpha: float = 32.0) -> None:
+    def add_adapter(self, rank: int = 32, lora_alpha: float = 32.0, ffn: bool = False) -> None:
         """peft ``LoraConfig(r, lora_alpha, init_lora_weights=True)`` on the eight attention projections: A kaiming-uniform(a = sqrt(5)), B zero.  Ranks that
         are not multiples of 64 are stored zero-padded; the padding stays zero (a padded row of A only receives gradient through the matching zero column
-        of B and the other way round, and AdamW moves a zero parameter with zero gradient nowhere)."""
+        of B and the other way round, and AdamW moves a zero parameter with zero gradient nowhere).  ``ffn``: ffn.net.0.proj and ffn.net.2 as well, with the
+        same rank and scale and the same initialisation (fan_in of ffn.net.2's A is the feed-forward width)."""
         if rank <= 0 or rank > 128:
             raise ValueError(f"LoRA rank must lie in 1..128, got {rank}")
+        if ffn and (self.dim < 256 or self.ffn_dim < 256):
+            raise NotImplementedError("Wan block: feed-forward adapters need a width and a feed-forward width of at least 256")
         rp = -(-int(rank) // 64) * 64
-        dev, D = self.flat.device, self.dim
+        dev, D, F = self.flat.device, self.dim, self.ffn_dim
         a = torch.zeros(8, rp, D, dtype=torch.float32, device=dev)
         a[:, :rank].uniform_(-(1.0 / D) ** 0.5, (1.0 / D) ** 0.5)  # kaiming_uniform_(a = sqrt(5)) on [r, D]: bound = 1 / sqrt(fan_in)
         self.lora_A, self.lora_B = nn.Parameter(a), nn.Parameter(torch.zeros(8, D, rp, dtype=torch.float32, device=dev))
+        self.lora_ffn = None
+        if ffn:
+            a1, a2 = torch.zeros(rp, D, dtype=torch.float32, device=dev), torch.zeros(rp, F, dtype=torch.float32, device=dev)
+            a1[:rank].uniform_(-(1.0 / D) ** 0.5, (1.0 / D) ** 0.5)
+            a2[:rank].uniform_(-(1.0 / F) ** 0.5, (1.0 / F) ** 0.5)
+            z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
+            self.lora_ffn = nn.ParameterList([nn.Parameter(a1), nn.Parameter(z(F, rp)), nn.Parameter(a2), nn.Parameter(z(D, rp))])
         self.lora_rank_user, self.lora_scale = int(rank), float(lora_alpha) / rank
         self.frozen = True
+
+    def lora_parameters(self) -> List[nn.Parameter]:
+        """The block's adapter Parameters in the order the step object lays them out: lora_A, lora_B, then the four feed-forward matrices."""
+        if self.lora_A is None:
+            return []
+        return [self.lora_A, self.lora_B] + (list(self.lora_ffn) if self.lora_ffn is not None else [])
+
+    def lora_named_views(self, grads: bool = False) -> Dict[str, torch.Tensor]:
+        """{peft key relative to the block: view of the user's rank inside the zero-padded storage}; ``grads``: the gradients (the step object's flat views,
+        or ``.grad``) under the same keys."""
+        if self.lora_A is None:
+            return {}
+        r = self.lora_rank_user
+        own = grads and self._grad_a_view is not None
+        pick = (lambda p: p.grad) if grads and not own else (lambda p: p.data)
+        a, b = (self._grad_a_view, self._grad_b_view) if own else (pick(self.lora_A), pick(self.lora_B))
+        out = {}
+        for j, n in enumerate(LORA_TARGETS):
+            out[f"{n}.lora_A.weight"] = a[j, :r]
+            out[f"{n}.lora_B.weight"] = b[j, :, :r]
+        if self.lora_ffn is not None:
+            f = self._grad_ffn_views if own else [pick(p) for p in self.lora_ffn]
+            for j, n in enumerate(LORA_FFN_TARGETS):
+                out[f"{n}.lora_A.weight"] = f[2 * j][:r]
+                out[f"{n}.lora_B.weight"] = f[2 * j + 1][:, :r]
+        return out
 
     def _backward_done(self) -> None:
         if self._grad_hook is not None:
@@ -694,9 +842,14 @@ class MI355XWanBlock(nn.Module):
             self._pre_forward(self)
         if (encoder_hidden_states_image is not None) != (self.img_layout is not None):
             raise ValueError("Wan block: the image context goes with added_kv_proj_dim, and only with it")
+        if self.img_layout is not None and not self.frozen:
+            raise NotImplementedError("Wan image-to-video: full fine-tuning is not covered; attach adapters (add_adapter) or freeze the base (freeze_base)")
+        if self.lora_ffn is not None:
+            fn = _WanFfnLoRABlockNativeFunction if self.native else _WanFfnLoRABlockFunction
+            img = None if encoder_hidden_states_image is None else encoder_hidden_states_image.detach().contiguous()
+            return fn.apply(self, hidden_states.contiguous(), encoder_hidden_states.contiguous(), temb.contiguous(), rotary[0], rotary[1], self.lora_A, self.lora_B,
+                            img, *self.lora_ffn)
         if self.img_layout is not None:
-            if not self.frozen:
-                raise NotImplementedError("Wan image-to-video: full fine-tuning is not covered; attach adapters (add_adapter) or freeze the base (freeze_base)")
             fn = _WanI2VLoRABlockNativeFunction if self.native else _WanI2VLoRABlockFunction
             return fn.apply(self, hidden_states.contiguous(), encoder_hidden_states.contiguous(), temb.contiguous(), rotary[0], rotary[1], self.lora_A, self.lora_B,
                             encoder_hidden_states_image.detach().contiguous())

@@ -11,6 +11,7 @@ Restated in oracle/wan.py ([upstream] diffusers transformer_wan.py + the referen
 from __future__ import annotations
 
 import math
+import re
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
 
@@ -19,7 +20,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..cogvideox.model import timestep_embedding
-from .block import LORA_TARGETS, MI355XWanBlock
+from .block import LORA_FFN_TARGETS, LORA_TARGETS, MI355XWanBlock
 
 bf16 = torch.bfloat16
 
@@ -262,48 +263,72 @@ class MI355XWanTransformer3DModel(nn.Module):
         return [("root", self.root.data, self.root_grad)] + [(f"blocks.{i}", b.flat.data, b.grad_flat) for i, b in enumerate(self.blocks)]
 
     # -- LoRA over the frozen base ------------------------------------------------------------------------------------------------------------
-    # the spellings of "to_q, to_k, to_v, to_out.0 of every attention of every block" the reference's recipes and its default use
-    _LORA_PATTERNS = ("blocks.*(to_q|to_k|to_v|to_out.0)", ["to_q", "to_k", "to_v", "to_out.0"], ("to_q", "to_k", "to_v", "to_out.0"))
+    def linear_module_names(self) -> List[str]:
+        """The diffusers names of every module of this model peft could wrap (the Conv3d patch embedding and every Linear), in ``named_modules`` order:
+        what a ``target_modules`` is resolved against."""
+        c, ce = self.config, "condition_embedder."
+        names = ["patch_embedding", ce + "time_embedder.linear_1", ce + "time_embedder.linear_2", ce + "time_proj", ce + "text_embedder.linear_1",
+                 ce + "text_embedder.linear_2"]
+        if c.image_dim is not None:
+            names += [ce + "image_embedder.ff.net.0.proj", ce + "image_embedder.ff.net.2"]
+        per_block = list(LORA_TARGETS) + (["attn2.add_k_proj", "attn2.add_v_proj"] if c.image_dim is not None else []) + list(LORA_FFN_TARGETS)
+        per_block.sort(key=lambda n: (n.split(".")[0], n))  # (order within a block does not matter to the resolution; keep it stable)
+        for i in range(c.num_layers):
+            names += [f"blocks.{i}.{n}" for n in per_block]
+        return names + ["proj_out"]
+
+    def resolve_target_modules(self, target_modules) -> bool:
+        """peft's rule (tuners_utils.check_target_module_exists): a string is ``re.fullmatch``ed against every module name; a list or tuple selects a name
+        that equals an entry or ends with "." + entry.  Two resulting sets are accepted: the eight attention projections of every block (returns False) or
+        those plus ffn.net.0.proj and ffn.net.2 of every block (returns True).  Anything else raises, naming the first module that is selected but not
+        covered or covered but not selected: a silently different adapter set is impossible.  Note that the reference's Wan control recipe spells the
+        feed-forward members "ff.net.0.proj|ff.net.2", which does not match Wan's "ffn.net...": as written it selects the eight, like peft does."""
+        names = self.linear_module_names()
+        if isinstance(target_modules, str):
+            hit = lambda n: re.fullmatch(target_modules, n) is not None
+        elif isinstance(target_modules, (list, tuple)) and all(isinstance(t, str) for t in target_modules):
+            hit = lambda n: any(n == t or n.endswith("." + t) for t in target_modules)
+        else:
+            raise TypeError("target_modules is a regular expression (str) or a list of module-name suffixes")
+        selected = [n for n in names if hit(n)]
+        L = self.config.num_layers
+        attn = [f"blocks.{i}.{t}" for i in range(L) for t in LORA_TARGETS]
+        ffn = [f"blocks.{i}.{t}" for i in range(L) for t in LORA_FFN_TARGETS]
+        covered = "this backend places adapters on to_q / to_k / to_v / to_out.0 of both attentions of every block, or on those and ffn.net.0.proj / ffn.net.2 of every block"
+        extra = [n for n in selected if n not in set(attn) | set(ffn)]
+        if extra:
+            raise NotImplementedError(f"target_modules {target_modules!r} selects {extra[0]}; {covered}")
+        if not selected:
+            raise NotImplementedError(f"target_modules {target_modules!r} selects no module of this model; {covered}")
+        sel = set(selected)
+        want = attn + ffn if sel & set(ffn) else attn
+        missing = [n for n in want if n not in sel]
+        if missing:
+            raise NotImplementedError(f"target_modules {target_modules!r} leaves out {missing[0]}; {covered}")
+        return bool(sel & set(ffn))
 
     def add_adapter(self, rank: int = 32, lora_alpha: float = 32.0, target_modules="blocks.*(to_q|to_k|to_v|to_out.0)") -> None:
-        """``--training_type lora --rank R --lora_alpha A --target_modules "blocks.*(to_q|to_k|to_v|to_out.0)"`` (the reference's Wan SFT recipes): fp32
-        adapters on the eight attention projections of every block (attn1 AND attn2: the regex matches both), base frozen.  Any other selection raises:
-        a silently different adapter set is impossible."""
-        tm = list(target_modules) if isinstance(target_modules, tuple) else target_modules
-        if tm not in [list(p) if isinstance(p, tuple) else p for p in self._LORA_PATTERNS]:
-            raise NotImplementedError(f"target_modules {target_modules!r}: this backend places adapters on exactly to_q / to_k / to_v / to_out.0 of both "
-                                      "attentions of every block (\"blocks.*(to_q|to_k|to_v|to_out.0)\")")
+        """``--training_type lora --rank R --lora_alpha A --target_modules ...``: fp32 adapters over a frozen base on what ``target_modules`` selects by peft's
+        rule -- the eight attention projections of every block (the Wan SFT recipes' "blocks.*(to_q|to_k|to_v|to_out.0)": attn1 AND attn2, the regex matches
+        both), or those and the two feed-forward projections ("blocks.*(to_q|to_k|to_v|to_out.0|ffn.net.0.proj|ffn.net.2)").  Any other selection raises
+        (``resolve_target_modules``)."""
+        ffn = self.resolve_target_modules(target_modules)
         for blk in self.blocks:
-            blk.add_adapter(rank, lora_alpha)
+            blk.add_adapter(rank, lora_alpha, ffn=ffn)
         self.lora_config = {"r": int(rank), "lora_alpha": lora_alpha, "target_modules": target_modules}
 
     def lora_parameters(self) -> List[nn.Parameter]:
-        return [p for blk in self.blocks for p in (blk.lora_A, blk.lora_B) if p is not None]
+        return [p for blk in self.blocks for p in blk.lora_parameters()]
 
     def lora_state_dict(self) -> Dict[str, torch.Tensor]:
-        """peft / diffusers keys ``blocks.{i}.attn{1,2}.to_{q,k,v}.lora_{A,B}.weight`` and ``blocks.{i}.attn{1,2}.to_out.0.lora_{A,B}.weight``: views of the
-        user's rank inside the zero-padded storage, [r, D] / [D, r]."""
-        out = {}
-        for i, blk in enumerate(self.blocks):
-            if blk.lora_A is None:
-                continue
-            r = blk.lora_rank_user
-            for j, n in enumerate(LORA_TARGETS):
-                out[f"blocks.{i}.{n}.lora_A.weight"] = blk.lora_A.data[j, :r]
-                out[f"blocks.{i}.{n}.lora_B.weight"] = blk.lora_B.data[j, :, :r]
-        return out
+        """peft / diffusers keys ``blocks.{i}.attn{1,2}.to_{q,k,v}.lora_{A,B}.weight`` and ``blocks.{i}.attn{1,2}.to_out.0.lora_{A,B}.weight`` -- with the
+        feed-forward adapters also ``blocks.{i}.ffn.net.0.proj.lora_{A,B}.weight`` ([r, D], [F, r]) and ``blocks.{i}.ffn.net.2.lora_{A,B}.weight`` ([r, F],
+        [D, r]): views of the user's rank inside the zero-padded storage."""
+        return {f"blocks.{i}.{k}": v for i, blk in enumerate(self.blocks) for k, v in blk.lora_named_views().items()}
 
     def lora_grad_state_dict(self) -> Dict[str, torch.Tensor]:
         """The adapters' gradients under the same keys (after a backward): the step object's flat views, or ``.grad``."""
-        out = {}
-        for i, blk in enumerate(self.blocks):
-            r = blk.lora_rank_user
-            ga = blk._grad_a_view if blk._grad_a_view is not None else blk.lora_A.grad
-            gb = blk._grad_b_view if blk._grad_b_view is not None else blk.lora_B.grad
-            for j, n in enumerate(LORA_TARGETS):
-                out[f"blocks.{i}.{n}.lora_A.weight"] = ga[j, :r]
-                out[f"blocks.{i}.{n}.lora_B.weight"] = gb[j, :, :r]
-        return out
+        return {f"blocks.{i}.{k}": v for i, blk in enumerate(self.blocks) for k, v in blk.lora_named_views(grads=True).items()}
 
     @torch.no_grad()
     def load_lora_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:

@@ -192,12 +192,14 @@ class MI355XWanLoRAStep:
         self.grad_bucket_blocks = max(1, int(grad_bucket_blocks))
         self._spans: Dict[int, Tuple[int, int]] = {}
         off = 0
-        for blk in transformer.blocks:
-            na, nb = blk.lora_A.numel(), blk.lora_B.numel()
-            blk._grad_a_view = self.gflat[off:off + na].view(blk.lora_A.shape)
-            blk._grad_b_view = self.gflat[off + na:off + na + nb].view(blk.lora_B.shape)
-            self._spans[id(blk)] = (off, off + na + nb)
-            off += na + nb
+        for blk in transformer.blocks:  # (the order of transformer.lora_parameters(): per block lora_A, lora_B, then the four feed-forward matrices)
+            views, lo = [], off
+            for p in blk.lora_parameters():
+                views.append(self.gflat[off:off + p.numel()].view(p.shape))
+                off += p.numel()
+            blk._grad_a_view, blk._grad_b_view = views[0], views[1]
+            blk._grad_ffn_views = tuple(views[2:]) if len(views) > 2 else None
+            self._spans[id(blk)] = (lo, off)
         assert off == self.flat.numel()
         self.buckets_issued = 0
         self.bucket_log: List[Tuple[int, int]] = []  # (lo, hi) element slices of the last exchange, in issue order

@@ -733,6 +733,43 @@ int ftmi_wan_i2v_lora_block_backward(const ftmi_wan_i2v_lora_block_config* cfg, 
                                      void* dx, void* denc, float* grad_a, float* grad_b, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
                                      ftmi_stream stream);
 
+/* The LoRA block with adapters on the feed-forward projections as well (ffn = 1): ffn.net.0.proj (A_1 [r, D], B_1 [F, r]) and ffn.net.2 (A_2 [r, F],
+ * B_2 [D, r]) next to the eight attention projections, at the same rank and scale -- what peft attaches when the reference's --target_modules (handed over
+ * unchanged: finetrainers/trainer/sft_trainer/trainer.py:121-128 builds LoraConfig(r, lora_alpha, target_modules) and calls transformer.add_adapter) also
+ * names "ffn.net.0.proj" and "ffn.net.2"; they are the two "ff" members of the control trainer's default list (finetrainers/trainer/control_trainer/config.py:60-62
+ * --target_modules "(transformer_blocks|single_transformer_blocks).*(to_q|to_k|to_v|to_out.0|ff.net.0.proj|ff.net.2)") spelled for Wan, whose feed-forward
+ * module is named "ffn".  One entry for text-to-video (TI = 0) and image-to-video (TI > 0): the configuration is ftmi_wan_i2v_lora_block_config plus ffn, the
+ * weights are ftmi_wan_lora_block_weights plus the four fp32 matrices, the same walk (csrc/wan_dit.hip) runs behind it.
+ *   pre = n3 W_1^T + b_1 + s (n3 A_1^T) B_1^T,  act = gelu_tanh(pre)  (one launch);   f = act W_2^T + b_2 + s (act A_2^T) B_2^T
+ * `saved` grows by the two down-projected rows [B S, 3r] each and by n3 [B S, D] and act [B S, F], which the frozen base otherwise drops (dA_1 and dA_2 read
+ * them).  ffn = 0: the launches, bits and byte counts of ftmi_wan_i2v_lora_block_* (ffn_* and grad_ffn_* may be NULL).  ffn = 1 needs r > 0 and F >= 256;
+ * what the kernels cannot take returns FTMI_ERR_UNSUPPORTED (the byte planners then return 0).  The backward ADDS to grad_a / grad_b and to
+ * grad_ffn_a1 [r, D], grad_ffn_b1 [F, r], grad_ffn_a2 [r, F], grad_ffn_b2 [D, r] (fp32). */
+typedef struct {
+    int B, S, T;      /* batch, video tokens, text tokens */
+    int D, H, F;      /* width = H x 128 <= 5120, feed-forward width */
+    float eps;        /* 1e-6 */
+    int gemm_variant; /* 8 */
+    int r;            /* LoRA rank: 0, 64 or 128 (other ranks zero-padded by the caller) */
+    float lora_scale; /* alpha / (the user's) r */
+    int TI;           /* image tokens, 0 .. 320 */
+    int ffn;          /* 1: adapters on ffn.net.0.proj and ffn.net.2 as well */
+} ftmi_wan_lora_ffn_block_config;
+typedef struct {
+    ftmi_wan_lora_block_weights base;
+    const float *ffn_a1, *ffn_b1, *ffn_a2, *ffn_b2; /* fp32 [r, D], [F, r], [r, F], [D, r]; NULL when ffn == 0 */
+} ftmi_wan_lora_ffn_block_weights;
+size_t ftmi_wan_lora_ffn_block_saved_bytes(const ftmi_wan_lora_ffn_block_config* cfg);
+size_t ftmi_wan_lora_ffn_block_scratch_bytes(const ftmi_wan_lora_ffn_block_config* cfg);
+/* out == NULL: recomputation pass (refills `saved`, the feed-forward adapters' rows included) */
+int ftmi_wan_lora_ffn_block_forward(const ftmi_wan_lora_ffn_block_config* cfg, const ftmi_wan_lora_ffn_block_weights* w, const void* img_params, const void* x,
+                                    const void* enc, const void* enc_img, const float* mod, const float* rope_cos, const float* rope_sin, void* out, void* saved,
+                                    size_t saved_bytes, void* scratch, size_t scratch_bytes, ftmi_stream stream);
+int ftmi_wan_lora_ffn_block_backward(const ftmi_wan_lora_ffn_block_config* cfg, const ftmi_wan_lora_ffn_block_weights* w, const void* img_params, const void* x,
+                                     const void* enc, const void* enc_img, const float* mod, const float* rope_cos, const float* rope_sin, const void* dout,
+                                     void* dx, void* denc, float* grad_a, float* grad_b, float* grad_ffn_a1, float* grad_ffn_b1, float* grad_ffn_a2,
+                                     float* grad_ffn_b2, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, ftmi_stream stream);
+
 /* Sum of squares of a flat fp32 gradient (shard): scratch[0] <- sum g^2 (order-fixed; scratch >= FTMI_CLIP_SCRATCH_FLOATS floats).  Sharded training
  * all-reduces scratch[0] over the ranks before the optimiser call below (the reference's clip_grad_norm_ over DTensor shards, utils/torch.py:99-161). */
 int ftmi_grad_sumsq(const float* grads, long n, float* scratch, ftmi_stream stream);

@@ -199,13 +199,17 @@ def build_wan_lora(args, par, dev) -> Dict[str, Any]:
                 v.copy_((0.02 * torch.randn(v.shape, generator=g, device=dev)).to(bf16))
     for blk in model.blocks:
         blk.mark_updated()
-    model.add_adapter(args.rank, float(args.rank))
+    ffn = bool(getattr(args, "ffn_adapters", False))  # --ffn-adapters: the ten-adapter set (ffn.net.0.proj and ffn.net.2 as well)
+    model.add_adapter(args.rank, float(args.rank), target_modules="blocks.*(to_q|to_k|to_v|to_out.0" + ("|ffn.net.0.proj|ffn.net.2)" if ffn else ")"))
     ckpt = bool(getattr(args, "gradient_checkpointing", False))
     if ckpt:
         model.apply_activation_checkpointing("full")
     with torch.no_grad():
-        for p in model.lora_parameters()[1::2]:
-            p[:, :, :args.rank].normal_(0, 0.01, generator=g)  # B != 0 so every gradient path carries data
+        for blk in model.blocks:
+            blk.lora_B[:, :, :args.rank].normal_(0, 0.01, generator=g)  # B != 0 so every gradient path carries data
+        for blk in model.blocks if ffn else ():
+            for p in (blk.lora_ffn[1], blk.lora_ffn[3]):
+                p[:, :args.rank].normal_(0, 0.01, generator=g)
     step = MI355XWanLoRAStep(model, lr=1e-4, generator=torch.Generator(device=dev).manual_seed(1 + par.rank), parallel=par if par.world_size > 1 else None)
     g.manual_seed(100 + par.rank)
     B, C, F_, H, W, T = 1, 16, 13, 60, 104, 512
@@ -226,8 +230,9 @@ def build_wan_lora(args, par, dev) -> Dict[str, Any]:
         "data": "synthetic posterior moments [1,32,13,60,104] + random text embeds [1,512,4096], random-init weights of the Wan2.1-T2V-1.3B DiT",
         "config": {"workload": f"Wan-T2V-1.3B LoRA rank={args.rank} bf16 SFT step over the frozen base, 49x480x832 clip ({S} video + {T} text tokens), batch 1 per GPU, {layers} blocks"
                                + ("" if layers == 30 else " -- REDUCED depth"),
-                   "model": "Wan2.1-T2V-1.3B DiT: 30 blocks, width 1536, 12 x 128 heads, frozen; 240 fp32 adapters", "seq_len": S,
-                   "activation_checkpointing": ckpt, "orchestration": ("one C call per block and direction (ftmi_wan_lora_block_forward / _backward)" if os.environ.get("FTMI_NATIVE_BLOCKS", "1") != "0" else "python, per kernel over the C ABI")},
+                   "model": f"Wan2.1-T2V-1.3B DiT: 30 blocks, width 1536, 12 x 128 heads, frozen; {300 if ffn else 240} fp32 adapters", "seq_len": S,
+                   "adapters_per_block": 10 if ffn else 8,
+                   "activation_checkpointing": ckpt, "orchestration": (f"one C call per block and direction (ftmi_wan_lora{'_ffn' if ffn else ''}_block_forward / _backward)" if os.environ.get("FTMI_NATIVE_BLOCKS", "1") != "0" else "python, per kernel over the C ABI")},
         "layers": layers,
     }
 
@@ -405,7 +410,7 @@ WORKLOADS = {"cogvideox": (build_cogvideox, lambda a, c: cpu_baseline_cogvideox(
 def main() -> None:
     """One workload on one GPU, outside bench.py (whose --workload list is fixed): 1 JSON line with the builder's static part plus step_ms (median), every
     step's ms, samples/s, achieved TFLOP/s and the peak allocated memory.  ``python tools/bench_workloads.py --workload wan_lora --steps 5 --warmup 1
-    [--gradient-checkpointing]``."""
+    [--gradient-checkpointing] [--ffn-adapters]``."""
     import argparse
     import json
     import sys
@@ -419,6 +424,7 @@ def main() -> None:
     ap.add_argument("--layers", type=int, default=0)
     ap.add_argument("--rank", type=int, default=32)
     ap.add_argument("--gradient-checkpointing", dest="gradient_checkpointing", action="store_true")
+    ap.add_argument("--ffn-adapters", dest="ffn_adapters", action="store_true", help="wan_lora: adapters on ffn.net.0.proj and ffn.net.2 as well (ten per block)")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     ctx = WORKLOADS[args.workload][0](args, types.SimpleNamespace(world_size=1, rank=0), dev)
