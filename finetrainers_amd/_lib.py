@@ -160,6 +160,18 @@ class WanLoraFfnBlockWeights(Structure):
     _fields_ = [("base", WanLoraBlockWeights)] + [(n, c_void_p) for n in ("ffn_a1", "ffn_b1", "ffn_a2", "ffn_b2")]
 
 
+class WanControlPackConfig(Structure):
+    """include/ftmi355.h: ftmi_wan_control_pack_config."""
+
+    _fields_ = [(n, c_int) for n in ("B", "C", "F", "Fc", "H", "W", "pt", "ph", "pw")]
+
+
+class WanPatchLoraConfig(Structure):
+    """include/ftmi355.h: ftmi_wan_patch_lora_config."""
+
+    _fields_ = [("M", c_int), ("D", c_int), ("Kp", c_int), ("r", c_int), ("s", c_float), ("gemm_variant", c_int), ("refold", c_int)]
+
+
 class WanRowArgs(Structure):
     """include/ftmi355.h: ftmi_wan_row_args."""
 
@@ -303,6 +315,10 @@ _SIGS = {
     "ftmi_wan_block_forward": (c_int, [POINTER(WanBlockConfig), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ftmi_wan_block_backward": (c_int, [POINTER(WanBlockConfig), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    "ftmi_f32_gemm": (c_int, [c_int, c_int, c_int, c_void_p, c_long, c_long, c_void_p, c_long, c_long, c_void_p, c_long, c_float, c_int, c_void_p, c_long, c_void_p]),
+    "ftmi_wan_control_pack": (c_int, [POINTER(WanControlPackConfig)] + [c_void_p] * 10),
+    "ftmi_wan_patch_lora_forward": (c_int, [POINTER(WanPatchLoraConfig)] + [c_void_p] * 9),
+    "ftmi_wan_patch_lora_backward": (c_int, [POINTER(WanPatchLoraConfig)] + [c_void_p] * 8),
     "ftmi_hy_dual_saved_bytes": (c_size_t, [POINTER(HyDualConfig)]),
     "ftmi_hy_dual_scratch_bytes": (c_size_t, [POINTER(HyDualConfig)]),
     "ftmi_hy_dual_forward": (c_int, [POINTER(HyDualConfig), POINTER(HyDualWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -871,4 +871,30 @@ int ftmi_lora_split(const float* w, int rows, int cols, void* sp, void* ext, voi
     return lora_split(a, (hipStream_t)stream);
 }
 
+int ftmi_f32_gemm(int M, int N, int K, const float* a, long lda_row, long lda_col, const float* b, long ldb_row, long ldb_col, float* c, long ldc, float scale,
+                  int accumulate, void* hi_lo_out, long ld_hl, ftmi_stream stream) {
+    return f32_gemm(M, N, K, a, lda_row, lda_col, b, ldb_row, ldb_col, c, ldc, scale, accumulate, (bf16_t*)hi_lo_out, ld_hl, (hipStream_t)stream);
+}
+
+int ftmi_wan_control_pack(const ftmi_wan_control_pack_config* cfg, const void* moments, const void* control_moments, const void* noise, const float* sigmas,
+                          const float* latents_mean, const float* latents_std, const unsigned char* keep, void* cols2, void* target, ftmi_stream stream) {
+    if (!cfg || !moments || !control_moments || !noise || !sigmas || !latents_mean || !latents_std || !keep || !cols2 || !target)
+        return set_error(FTMI_ERR_INVALID, "ftmi_wan_control_pack: null argument");
+    return wan_control_pack(*cfg, (const bf16_t*)moments, (const bf16_t*)control_moments, (const bf16_t*)noise, sigmas, latents_mean, latents_std, keep,
+                            (bf16_t*)cols2, (bf16_t*)target, (hipStream_t)stream);
+}
+
+int ftmi_wan_patch_lora_forward(const ftmi_wan_patch_lora_config* cfg, const void* w, const void* bias, const float* a_f32, const float* b_f32, const void* cols2,
+                                float* dw_f32, void* w2, void* out, ftmi_stream stream) {
+    if (!cfg || !w || !cols2 || !w2 || !out || (cfg->refold && (!a_f32 || !b_f32 || !dw_f32)))
+        return set_error(FTMI_ERR_INVALID, "ftmi_wan_patch_lora_forward: null argument");
+    return wan_patch_lora_forward(*cfg, (const bf16_t*)w, (const bf16_t*)bias, a_f32, b_f32, (const bf16_t*)cols2, dw_f32, (bf16_t*)w2, (bf16_t*)out, (hipStream_t)stream);
+}
+
+int ftmi_wan_patch_lora_backward(const ftmi_wan_patch_lora_config* cfg, const float* a_f32, const float* b_f32, const void* cols2, const void* dx0, float* g_ws,
+                                 float* grad_a, float* grad_b, ftmi_stream stream) {
+    if (!cfg || !a_f32 || !b_f32 || !cols2 || !dx0 || !g_ws || !grad_a || !grad_b) return set_error(FTMI_ERR_INVALID, "ftmi_wan_patch_lora_backward: null argument");
+    return wan_patch_lora_backward(*cfg, a_f32, b_f32, (const bf16_t*)cols2, (const bf16_t*)dx0, g_ws, grad_a, grad_b, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -367,6 +367,16 @@ int wan_rms_rope_bwd(const WanRowArgs& a, hipStream_t st);
 int wan_gate_res_fwd(const WanRowArgs& a, hipStream_t st);
 int wan_gate_res_bwd(const WanRowArgs& a, hipStream_t st);
 int wan_colsum(const WanRowArgs& a, hipStream_t st);
+// Wan control LoRA outside the blocks (wan_control.hip): the fp32 GEMM of the folded full-rank patch-embedding adapter, the batch -> patch-column pack,
+// and the adapter's two launch sequences
+int f32_gemm(int M, int N, int K, const float* a, long lda_row, long lda_col, const float* b, long ldb_row, long ldb_col, float* c, long ldc, float scale,
+             int accumulate, bf16_t* hi_lo_out, long ld_hl, hipStream_t st);
+int wan_control_pack(const ftmi_wan_control_pack_config& c, const bf16_t* moments, const bf16_t* control_moments, const bf16_t* noise, const float* sigmas,
+                     const float* latents_mean, const float* latents_std, const unsigned char* keep, bf16_t* cols2, bf16_t* target, hipStream_t st);
+int wan_patch_lora_forward(const ftmi_wan_patch_lora_config& c, const bf16_t* w, const bf16_t* bias, const float* a_f32, const float* b_f32, const bf16_t* cols2,
+                           float* dw_f32, bf16_t* w2, bf16_t* out, hipStream_t st);
+int wan_patch_lora_backward(const ftmi_wan_patch_lora_config& c, const float* a_f32, const float* b_f32, const bf16_t* cols2, const bf16_t* dx0, float* g_ws,
+                            float* grad_a, float* grad_b, hipStream_t st);
 // Wan block orchestrator (wan_dit.hip)
 size_t wan_block_saved_bytes(const ftmi_wan_block_config& c);
 size_t wan_block_scratch_bytes(const ftmi_wan_block_config& c);

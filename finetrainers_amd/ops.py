@@ -881,3 +881,93 @@ def head_rms_rope_bwd(x2d, w, dy2d, head_dim: int = 128, eps: float = 1e-6, rope
     check(_lib.load().ftmi_head_rms_rope_bwd(ptr(x2d), x2d.stride(0), ptr(w), ptr(dy2d), dy2d.stride(0), ptr(out), out.stride(0), rows, D, int(head_dim), float(eps),
                                              ptr(cos), ptr(sin), int(rows_per_batch or rows), int(rope_from), stream_ptr()), "ftmi_head_rms_rope_bwd")
     return out
+
+
+# ---- Wan control LoRA outside the blocks (csrc/wan_control.hip) -----------------------------------------------------------------------------------
+def f32_gemm(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None, scale: float = 1.0, accumulate: bool = False,
+             hi_lo: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out [M, N] (fp32) = (accumulate ? out : 0) + scale * a [M, K] @ b [K, N] in fp32 FMAs with a fixed accumulation order.  ``a`` and ``b`` are 2-D fp32 views
+    of any strides (pass ``w.t()`` for a transposed operand: nothing is copied).  ``hi_lo`` [M, >= 2N] bf16: also receives the result's [hi | lo] planes."""
+    require_gpu_tensor(a, "a", torch.float32)
+    require_gpu_tensor(b, "b", torch.float32)
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[0]:
+        raise ValueError(f"f32_gemm: a {tuple(a.shape)} and b {tuple(b.shape)} do not multiply")
+    M, K = a.shape
+    N = b.shape[1]
+    if out is None:
+        if accumulate:
+            raise ValueError("f32_gemm: accumulate needs out")
+        out = torch.empty((M, N), dtype=torch.float32, device=a.device)
+    require_gpu_tensor(out, "out", torch.float32)
+    if out.shape != (M, N) or out.stride(1) != 1:
+        raise ValueError("f32_gemm: out must be an [M, N] fp32 view with contiguous columns")
+    ld_hl = 0
+    if hi_lo is not None:
+        require_gpu_tensor(hi_lo, "hi_lo", bf16)
+        if hi_lo.dim() != 2 or hi_lo.shape[0] != M or hi_lo.shape[1] < 2 * N or hi_lo.stride(1) != 1:
+            raise ValueError("f32_gemm: hi_lo must be an [M, >= 2N] bf16 view with contiguous columns")
+        ld_hl = hi_lo.stride(0)
+    check(_lib.load().ftmi_f32_gemm(M, N, K, ptr(a), a.stride(0), a.stride(1), ptr(b), b.stride(0), b.stride(1), ptr(out), out.stride(0), float(scale),
+                                     int(bool(accumulate)), ptr(hi_lo), ld_hl, stream_ptr()), "ftmi_f32_gemm")
+    return out
+
+
+def wan_control_pack(moments, control_moments, noise, sigmas, latents_mean, latents_std, keep, patch_size=(1, 2, 2)):
+    """-> (cols2 [B S, 2 Kp] bf16 = [cols | cols], target [B, C, F, H, W] bf16): include/ftmi355.h, ftmi_wan_control_pack.  ``keep`` [B, F] uint8."""
+    for n, t in (("moments", moments), ("control_moments", control_moments), ("noise", noise)):
+        require_gpu_tensor(t, n, bf16)
+    for n, t in (("sigmas", sigmas), ("latents_mean", latents_mean), ("latents_std", latents_std)):
+        require_gpu_tensor(t, n, torch.float32)
+    require_gpu_tensor(keep, "keep", torch.uint8)
+    B, C, F_, H, W = noise.shape
+    Fc = control_moments.shape[2]
+    if tuple(moments.shape) != (B, 2 * C, F_, H, W) or tuple(control_moments.shape) != (B, 2 * C, Fc, H, W):
+        raise ValueError(f"wan_control_pack: moments {tuple(moments.shape)} / control moments {tuple(control_moments.shape)} do not go with noise {tuple(noise.shape)}")
+    if sigmas.numel() != B or latents_mean.numel() != C or latents_std.numel() != C or tuple(keep.shape) != (B, F_):
+        raise ValueError("wan_control_pack: sigmas [B], latents_mean / latents_std [C] and keep [B, F] expected")
+    pt, ph, pw = patch_size
+    if F_ % pt or H % ph or W % pw:
+        raise ValueError("wan_control_pack: the latent size must be whole patches")
+    S, Kp = (F_ // pt) * (H // ph) * (W // pw), 2 * C * pt * ph * pw
+    cols2 = torch.empty((B * S, 2 * Kp), dtype=bf16, device=noise.device)
+    target = torch.empty_like(noise, memory_format=torch.contiguous_format)
+    cfg = _lib.WanControlPackConfig(B=B, C=C, F=F_, Fc=Fc, H=H, W=W, pt=pt, ph=ph, pw=pw)
+    args = [t.contiguous() for t in (moments, control_moments, noise, sigmas, latents_mean, latents_std, keep)]
+    check(_lib.load().ftmi_wan_control_pack(ctypes.byref(cfg), *[ptr(t) for t in args], ptr(cols2), ptr(target), stream_ptr()), "ftmi_wan_control_pack")
+    return cols2, target
+
+
+def _patch_lora_cfg(M: int, D: int, Kp: int, r: int, s: float, refold: bool, variant: int):
+    return _lib.WanPatchLoraConfig(M=M, D=D, Kp=Kp, r=r, s=float(s), gemm_variant=variant, refold=int(bool(refold)))
+
+
+def wan_patch_lora_forward(cols2, w, bias, lora_a, lora_b, dw, w2, s: float = 1.0, refold: bool = True, variant: int = 8, out=None):
+    """y [M, D] = bf(bf(cols W^T + b) + s (cols A^T) B^T) through the folded adapter (ftmi_wan_patch_lora_forward).  cols2 [M, 2 Kp] = [cols | cols]; w [D, Kp] bf16;
+    lora_a [r, Kp], lora_b [D, r] fp32; dw [D, Kp] fp32 and w2 [D, 2 Kp] bf16 are the caller's fold buffers (``refold=False`` reuses w2)."""
+    M, Kp = cols2.shape[0], cols2.shape[1] // 2
+    D, r = lora_b.shape
+    for n, t, dt, shape in (("cols2", cols2, bf16, (M, 2 * Kp)), ("w", w, bf16, (D, Kp)), ("lora_a", lora_a, torch.float32, (r, Kp)), ("lora_b", lora_b, torch.float32, (D, r)),
+                            ("dw", dw, torch.float32, (D, Kp)), ("w2", w2, bf16, (D, 2 * Kp))):
+        require_gpu_tensor(t, n, dt)
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"wan_patch_lora_forward: {n} must be a contiguous {shape} tensor, got {tuple(t.shape)}")
+    if out is None:
+        out = torch.empty((M, D), dtype=bf16, device=cols2.device)
+    cfg = _patch_lora_cfg(M, D, Kp, r, s, refold, variant)
+    check(_lib.load().ftmi_wan_patch_lora_forward(ctypes.byref(cfg), ptr(w), ptr(bias), ptr(lora_a), ptr(lora_b), ptr(cols2), ptr(dw), ptr(w2), ptr(out), stream_ptr()),
+          "ftmi_wan_patch_lora_forward")
+    return out
+
+
+def wan_patch_lora_backward(cols2, dx0, lora_a, lora_b, g_ws, grad_a, grad_b, s: float = 1.0) -> None:
+    """grad_a [r, Kp] += s B^T G, grad_b [D, r] += s G A^T with G = dx0^T cols written to g_ws [D, Kp] fp32 (ftmi_wan_patch_lora_backward)."""
+    M, Kp = cols2.shape[0], cols2.shape[1] // 2
+    D, r = lora_b.shape
+    for n, t, dt, shape in (("cols2", cols2, bf16, (M, 2 * Kp)), ("dx0", dx0, bf16, (M, D)), ("lora_a", lora_a, torch.float32, (r, Kp)), ("lora_b", lora_b, torch.float32, (D, r)),
+                            ("g_ws", g_ws, torch.float32, (D, Kp)), ("grad_a", grad_a, torch.float32, (r, Kp)), ("grad_b", grad_b, torch.float32, (D, r))):
+        require_gpu_tensor(t, n, dt)
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"wan_patch_lora_backward: {n} must be a contiguous {shape} tensor, got {tuple(t.shape)}")
+    cfg = _patch_lora_cfg(M, D, Kp, r, s, False, 8)
+    check(_lib.load().ftmi_wan_patch_lora_backward(ctypes.byref(cfg), ptr(lora_a), ptr(lora_b), ptr(cols2), ptr(dx0), ptr(g_ws), ptr(grad_a), ptr(grad_b), stream_ptr()),
+          "ftmi_wan_patch_lora_backward")

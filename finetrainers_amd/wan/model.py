@@ -194,6 +194,37 @@ class _LnModFunction(torch.autograd.Function):
         return dx.view(B, S, D), red[0], red[1], None
 
 
+class _PatchLoRAFunction(torch.autograd.Function):
+    """The widened patch embedding with its full-rank adapter, folded: y = bf(bf(cols W^T + b) + s (cols A^T) B^T) as ONE NT GEMM whose K-extension
+    runs over the bf16 planes of dW = s B A.  The backward takes block 0's input gradient and forms the two adapter gradients (``ftmi_wan_patch_lora_backward``);
+    the input is data: no gradient flows further.  With a step object the gradients are added into its flat views and ``model._patch_grad_hook`` fires."""
+
+    @staticmethod
+    def forward(ctx, model: "MI355XWanTransformer3DModel", cols2, lora_a, lora_b):
+        w, b = model.rparam("patch_embedding.weight"), model.rparam("patch_embedding.bias")
+        key = (lora_a.data_ptr(), lora_a._version, lora_b.data_ptr(), lora_b._version, model._patch_epoch, w.data_ptr())
+        refold, model._patch_fold_key = key != model._patch_fold_key, key
+        dw, w2, _ = model._patch_ws
+        y = ops.wan_patch_lora_forward(cols2, w, b, lora_a.detach(), lora_b.detach(), dw, w2, s=model.patch_lora_scale, refold=refold)
+        ctx.model = model
+        ctx.save_for_backward(cols2, lora_a, lora_b)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        model = ctx.model
+        cols2, lora_a, lora_b = ctx.saved_tensors
+        own = model._patch_grad_views is not None
+        ga, gb = model._patch_grad_views if own else (torch.zeros_like(lora_a), torch.zeros_like(lora_b))
+        ops.wan_patch_lora_backward(cols2, dy.reshape(cols2.shape[0], -1).contiguous(), lora_a.detach(), lora_b.detach(), model._patch_ws[2], ga, gb,
+                                    s=model.patch_lora_scale)
+        if own:
+            if model._patch_grad_hook is not None:
+                model._patch_grad_hook(model)  # the first trainable thing of the model: its gradients are the last to become final
+            return None, None, None, None
+        return None, None, ga, gb
+
+
 class MI355XWanTransformer3DModel(nn.Module):
     def __init__(self, config: Optional[WanTransformerConfig] = None, device: Optional[torch.device] = None):
         super().__init__()
@@ -211,6 +242,14 @@ class MI355XWanTransformer3DModel(nn.Module):
         self._anchor = torch.zeros(1, dtype=bf16, device=dev, requires_grad=True)  # tells autograd that the graph has trainable inputs
         self.lora_config: Optional[Dict[str, object]] = None  # set by add_adapter: {"r", "lora_alpha", "target_modules"}
         self._proj_out_t: Optional[torch.Tensor] = None       # LoRA training: the frozen output projection's K-contiguous twin
+        # control LoRA: the full-rank adapter of the (widened) patch embedding, fp32 [r, Kp] / [D, r] with r = D; state-dict shapes are the Conv3d ones
+        self.patch_lora_A: Optional[nn.Parameter] = None
+        self.patch_lora_B: Optional[nn.Parameter] = None
+        self.patch_lora_scale = 0.0
+        self._patch_ws: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None  # dW [D, Kp] fp32, its planes [D, 2 Kp] bf16, G [D, Kp] fp32
+        self._patch_fold_key, self._patch_epoch = None, 0
+        self._patch_grad_views: Optional[Tuple[torch.Tensor, torch.Tensor]] = None  # the step object's flat gradient views
+        self._patch_grad_hook = None
 
     @property
     def device(self) -> torch.device:
@@ -277,12 +316,9 @@ class MI355XWanTransformer3DModel(nn.Module):
             names += [f"blocks.{i}.{n}" for n in per_block]
         return names + ["proj_out"]
 
-    def resolve_target_modules(self, target_modules) -> bool:
+    def select_modules(self, target_modules) -> List[str]:
         """peft's rule (tuners_utils.check_target_module_exists): a string is ``re.fullmatch``ed against every module name; a list or tuple selects a name
-        that equals an entry or ends with "." + entry.  Two resulting sets are accepted: the eight attention projections of every block (returns False) or
-        those plus ffn.net.0.proj and ffn.net.2 of every block (returns True).  Anything else raises, naming the first module that is selected but not
-        covered or covered but not selected: a silently different adapter set is impossible.  Note that the reference's Wan control recipe spells the
-        feed-forward members "ff.net.0.proj|ff.net.2", which does not match Wan's "ffn.net...": as written it selects the eight, like peft does."""
+        that equals an entry or ends with "." + entry."""
         names = self.linear_module_names()
         if isinstance(target_modules, str):
             hit = lambda n: re.fullmatch(target_modules, n) is not None
@@ -290,45 +326,145 @@ class MI355XWanTransformer3DModel(nn.Module):
             hit = lambda n: any(n == t or n.endswith("." + t) for t in target_modules)
         else:
             raise TypeError("target_modules is a regular expression (str) or a list of module-name suffixes")
-        selected = [n for n in names if hit(n)]
+        return [n for n in names if hit(n)]
+
+    @staticmethod
+    def _pattern_lookup(name: str, rank_pattern, alpha_pattern, rank, lora_alpha):
+        """peft's per-module override (tuners/lora/model.py, _create_and_replace): the first key of rank_pattern / alpha_pattern with ``.*\\.key$`` matching the
+        module name, else the name itself, is looked up in both dictionaries."""
+        rank_pattern, alpha_pattern = rank_pattern or {}, alpha_pattern or {}
+        key = next((k for k in list(rank_pattern) + list(alpha_pattern) if re.match(rf".*\.{k}$", name)), name)
+        return rank_pattern.get(key, rank), alpha_pattern.get(key, lora_alpha)
+
+    def resolve_target_modules(self, target_modules, rank_pattern=None, alpha_pattern=None, rank=None, lora_alpha=None) -> bool:
+        """Which adapters ``target_modules`` asks for (``select_modules``).  Accepted sets: the eight attention projections of every block (returns False) or
+        those plus ffn.net.0.proj and ffn.net.2 of every block (returns True); either may come with ``patch_embedding`` (the control recipe's
+        "(^patch_embedding$)|(...)"; ``patch_adapter_spec`` says whether it does) provided ``rank_pattern`` gives that module the full rank ``inner_dim``.
+        Anything else raises, naming the first module that is selected but not covered or covered but not selected: a silently different adapter set is
+        impossible.  Note that the reference's Wan control recipe spells the feed-forward members "ff.net.0.proj|ff.net.2", which does not match Wan's
+        "ffn.net...": as written it selects the eight, like peft does; and that the list form's appended "^patch_embedding$" is a suffix no name ends with."""
+        selected = self.select_modules(target_modules)
         L = self.config.num_layers
         attn = [f"blocks.{i}.{t}" for i in range(L) for t in LORA_TARGETS]
         ffn = [f"blocks.{i}.{t}" for i in range(L) for t in LORA_FFN_TARGETS]
         covered = "this backend places adapters on to_q / to_k / to_v / to_out.0 of both attentions of every block, or on those and ffn.net.0.proj / ffn.net.2 of every block"
-        extra = [n for n in selected if n not in set(attn) | set(ffn)]
+        if "patch_embedding" in selected:
+            r, alpha = self._pattern_lookup("patch_embedding", rank_pattern, alpha_pattern, rank, lora_alpha)
+            if r != self.config.inner_dim or not alpha or float(alpha) <= 0:
+                raise NotImplementedError(f"target_modules {target_modules!r} selects patch_embedding; {covered}; a patch_embedding adapter is the control recipe's "
+                                          f"full-rank one: rank_pattern must give it r = inner_dim = {self.config.inner_dim} (got {r!r}) and alpha_pattern a positive alpha")
+            if self.config.image_dim is not None:
+                raise NotImplementedError(f"target_modules {target_modules!r} selects patch_embedding; control on an image-to-video model is not covered")
+        extra = [n for n in selected if n not in set(attn) | set(ffn) | {"patch_embedding"}]
         if extra:
             raise NotImplementedError(f"target_modules {target_modules!r} selects {extra[0]}; {covered}")
-        if not selected:
-            raise NotImplementedError(f"target_modules {target_modules!r} selects no module of this model; {covered}")
-        sel = set(selected)
+        blocks = [n for n in selected if n != "patch_embedding"]
+        if not blocks:
+            raise NotImplementedError(f"target_modules {target_modules!r} selects no module of this model's blocks; {covered}")
+        for n in blocks:  # a pattern that reaches into the blocks would give one projection another rank or scale
+            if self._pattern_lookup(n, rank_pattern, alpha_pattern, rank, lora_alpha) != (rank, lora_alpha):
+                raise NotImplementedError(f"rank_pattern / alpha_pattern change the rank or alpha of {n}; {covered} with ONE rank and alpha")
+        sel = set(blocks)
         want = attn + ffn if sel & set(ffn) else attn
         missing = [n for n in want if n not in sel]
         if missing:
             raise NotImplementedError(f"target_modules {target_modules!r} leaves out {missing[0]}; {covered}")
         return bool(sel & set(ffn))
 
-    def add_adapter(self, rank: int = 32, lora_alpha: float = 32.0, target_modules="blocks.*(to_q|to_k|to_v|to_out.0)") -> None:
+    def patch_adapter_spec(self, target_modules, rank_pattern=None, alpha_pattern=None, rank=None, lora_alpha=None) -> Optional[Tuple[int, float]]:
+        """(r, s = alpha / r) of the patch-embedding adapter ``target_modules`` selects (after ``resolve_target_modules`` accepted it), or None."""
+        if "patch_embedding" not in self.select_modules(target_modules):
+            return None
+        r, alpha = self._pattern_lookup("patch_embedding", rank_pattern, alpha_pattern, rank, lora_alpha)
+        return int(r), float(alpha) / int(r)
+
+    def expand_patch_embedding(self, new_in_channels: int) -> None:
+        """The control specification's widened input layer (models/utils.py: _expand_conv3d_with_zeroed_weights): the patch embedding takes
+        ``new_in_channels`` channels, the weight columns of the new channels are zero, ``config.in_channels`` follows.  The root buffer is laid out again."""
+        c = self.config
+        if self.lora_config is not None:
+            raise RuntimeError("expand_patch_embedding comes before add_adapter (the adapter is laid out for the widened layer)")
+        if c.image_dim is not None:
+            raise NotImplementedError("control on an image-to-video model is not covered (its input already carries mask and conditioning channels)")
+        pt, ph, pw = c.patch_size
+        if new_in_channels < c.in_channels or (new_in_channels * pt * ph * pw) % 64 != 0:
+            raise ValueError(f"new_in_channels {new_in_channels}: at least the present {c.in_channels} channels, and patch columns ({pt * ph * pw} per channel) "
+                             "that are a multiple of 64")
+        if self.root.numel() < self.root_layout.total or self._root_src is not None:
+            raise RuntimeError("the parameters are sharded over the ranks: expand the patch embedding before sharding")
+        old_layout, old = self.root_layout, self.root.data
+        c.in_channels = int(new_in_channels)
+        self.root_layout = RootLayout(c)
+        new = torch.zeros(self.root_layout.total, dtype=bf16, device=old.device)
+        new_views = self.root_layout.named_views(new)
+        for name, view in old_layout.named_views(old).items():
+            if name == "patch_embedding.weight":
+                new_views[name][:, :view.shape[1]].copy_(view)  # columns are (c, pt, ph, pw): the old channels come first
+            else:
+                new_views[name].copy_(view)
+        self.root = nn.Parameter(new, requires_grad=False)
+        self.root_grad, self._proj_out_t = None, None
+
+    def add_adapter(self, rank: int = 32, lora_alpha: float = 32.0, target_modules="blocks.*(to_q|to_k|to_v|to_out.0)", rank_pattern=None, alpha_pattern=None) -> None:
         """``--training_type lora --rank R --lora_alpha A --target_modules ...``: fp32 adapters over a frozen base on what ``target_modules`` selects by peft's
         rule -- the eight attention projections of every block (the Wan SFT recipes' "blocks.*(to_q|to_k|to_v|to_out.0)": attn1 AND attn2, the regex matches
-        both), or those and the two feed-forward projections ("blocks.*(to_q|to_k|to_v|to_out.0|ffn.net.0.proj|ffn.net.2)").  Any other selection raises
-        (``resolve_target_modules``)."""
-        ffn = self.resolve_target_modules(target_modules)
+        both), or those and the two feed-forward projections ("blocks.*(to_q|to_k|to_v|to_out.0|ffn.net.0.proj|ffn.net.2)").  ``--training_type control-lora``
+        passes "(^patch_embedding$)|(...)" with ``rank_pattern = alpha_pattern = {"patch_embedding": inner_dim}``: the full-rank adapter of the widened patch
+        embedding next to the block adapters (A kaiming-uniform(a = sqrt(5)) over its fan-in Cin pt ph pw, B zero, like peft initialises a conv adapter).
+        Any other selection raises (``resolve_target_modules``)."""
+        ffn = self.resolve_target_modules(target_modules, rank_pattern, alpha_pattern, rank, lora_alpha)
+        patch = self.patch_adapter_spec(target_modules, rank_pattern, alpha_pattern, rank, lora_alpha)
         for blk in self.blocks:
             blk.add_adapter(rank, lora_alpha, ffn=ffn)
         self.lora_config = {"r": int(rank), "lora_alpha": lora_alpha, "target_modules": target_modules}
+        if rank_pattern:
+            self.lora_config["rank_pattern"] = dict(rank_pattern)
+        if alpha_pattern:
+            self.lora_config["alpha_pattern"] = dict(alpha_pattern)
+        if patch is not None:
+            r, s = patch
+            D, Kp = self.root_layout.offsets["patch_embedding.weight"][1]
+            dev = self.device
+            a = torch.empty(r, Kp, dtype=torch.float32, device=dev).uniform_(-(1.0 / Kp) ** 0.5, (1.0 / Kp) ** 0.5)  # kaiming_uniform_(a = sqrt(5)): 1 / sqrt(fan_in)
+            self.patch_lora_A, self.patch_lora_B = nn.Parameter(a), nn.Parameter(torch.zeros(D, r, dtype=torch.float32, device=dev))
+            self.patch_lora_scale = s
+            self._patch_ws = (torch.zeros(D, Kp, dtype=torch.float32, device=dev), torch.zeros(D, 2 * Kp, dtype=bf16, device=dev),
+                              torch.zeros(D, Kp, dtype=torch.float32, device=dev))
+            self._patch_fold_key = None
+
+    def mark_patch_adapter_updated(self) -> None:
+        """The patch adapter's parameters were changed in place by the library (the step object's fused optimiser launch): fold again at the next forward."""
+        self._patch_epoch += 1
+
+    def _patch_lora_views(self, grads: bool = False) -> Dict[str, torch.Tensor]:
+        if self.patch_lora_A is None:
+            return {}
+        if grads and self._patch_grad_views is not None:
+            a, b = self._patch_grad_views
+        else:
+            a, b = ((self.patch_lora_A.grad, self.patch_lora_B.grad) if grads else (self.patch_lora_A.data, self.patch_lora_B.data))
+        pt, ph, pw = self.config.patch_size
+        return {"patch_embedding.lora_A.weight": a.view(a.shape[0], self.config.in_channels, pt, ph, pw), "patch_embedding.lora_B.weight": b.view(*b.shape, 1, 1, 1)}
 
     def lora_parameters(self) -> List[nn.Parameter]:
-        return [p for blk in self.blocks for p in blk.lora_parameters()]
+        """The patch-embedding adapter first (the front of the step object's flat buffers: its gradients are the last to become final), then the blocks'."""
+        patch = [self.patch_lora_A, self.patch_lora_B] if self.patch_lora_A is not None else []
+        return patch + [p for blk in self.blocks for p in blk.lora_parameters()]
 
     def lora_state_dict(self) -> Dict[str, torch.Tensor]:
         """peft / diffusers keys ``blocks.{i}.attn{1,2}.to_{q,k,v}.lora_{A,B}.weight`` and ``blocks.{i}.attn{1,2}.to_out.0.lora_{A,B}.weight`` -- with the
         feed-forward adapters also ``blocks.{i}.ffn.net.0.proj.lora_{A,B}.weight`` ([r, D], [F, r]) and ``blocks.{i}.ffn.net.2.lora_{A,B}.weight`` ([r, F],
-        [D, r]): views of the user's rank inside the zero-padded storage."""
-        return {f"blocks.{i}.{k}": v for i, blk in enumerate(self.blocks) for k, v in blk.lora_named_views().items()}
+        [D, r]): views of the user's rank inside the zero-padded storage.  Control LoRA adds ``patch_embedding.lora_A.weight`` [r, Cin, pt, ph, pw] and
+        ``patch_embedding.lora_B.weight`` [D, r, 1, 1, 1]."""
+        out = self._patch_lora_views()
+        out.update({f"blocks.{i}.{k}": v for i, blk in enumerate(self.blocks) for k, v in blk.lora_named_views().items()})
+        return out
 
     def lora_grad_state_dict(self) -> Dict[str, torch.Tensor]:
         """The adapters' gradients under the same keys (after a backward): the step object's flat views, or ``.grad``."""
-        return {f"blocks.{i}.{k}": v for i, blk in enumerate(self.blocks) for k, v in blk.lora_named_views(grads=True).items()}
+        out = self._patch_lora_views(grads=True)
+        out.update({f"blocks.{i}.{k}": v for i, blk in enumerate(self.blocks) for k, v in blk.lora_named_views(grads=True).items()})
+        return out
 
     @torch.no_grad()
     def load_lora_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
@@ -341,6 +477,7 @@ class MI355XWanTransformer3DModel(nn.Module):
             if tuple(sd[k].shape) != tuple(v.shape):
                 raise ValueError(f"{k}: expected shape {tuple(v.shape)}, got {tuple(sd[k].shape)}")
             v.copy_(sd[k].to(v))
+        self.mark_patch_adapter_updated()
 
     def apply_activation_checkpointing(self, checkpointing_type: str = "full", n_layer: int = 1) -> "MI355XWanTransformer3DModel":
         """``--gradient_checkpointing`` (utils/activation_checkpoint.py:24-49) for LoRA training: every block ("block_skip": every ``n_layer``-th) keeps
@@ -377,19 +514,27 @@ class MI355XWanTransformer3DModel(nn.Module):
         x = F_.gelu(F_.linear(ln(x, "norm1"), P("ff.net.0.proj.weight"), P("ff.net.0.proj.bias")))
         return ln(F_.linear(x, P("ff.net.2.weight"), P("ff.net.2.bias")), "norm2").contiguous()
 
-    def _forward_frozen_root(self, hidden_states, timestep, encoder_hidden_states, return_dict: bool, encoder_hidden_states_image=None):
+    def _forward_frozen_root(self, hidden_states, timestep, encoder_hidden_states, return_dict: bool, encoder_hidden_states_image=None, patch_columns=None,
+                             latent_shape=None):
         """The forward with adapters attached: patch embedding, condition embedder and head run FROZEN (plain launches of the same GEMMs: same bits as the
         full fine-tune's forward); the only graph autograd sees is blocks -> output norm -> output projection, which hands d x back to the last block."""
         c = self.config
-        B, C, F_, H, W = hidden_states.shape
+        B, F_, H, W = latent_shape if hidden_states is None else (hidden_states.shape[0],) + tuple(hidden_states.shape[2:])
         pt, ph, pw = c.patch_size
         f, h, w = F_ // pt, H // ph, W // pw
         S = f * h * w
         rope = self._rope(F_, H, W)
         lin = lambda t, name, **kw: ops.gemm_nt(t.reshape(-1, t.shape[-1]), self.rparam(f"{name}.weight"), self.rparam(f"{name}.bias"), **kw)
         silu = torch.nn.functional.silu
+        if self.patch_lora_A is not None:  # the first trainable thing of the frozen root: block 0's dx comes back to it
+            if patch_columns is None:
+                cols = self._patch_columns(hidden_states)
+                patch_columns = torch.cat([cols, cols], dim=-1).view(B * S, -1)
+            x = _PatchLoRAFunction.apply(self, patch_columns, self.patch_lora_A, self.patch_lora_B).view(B, S, -1)
         with torch.no_grad():
-            x = lin(self._patch_columns(hidden_states), "patch_embedding").view(B, S, -1)
+            if self.patch_lora_A is None:
+                cols = self._patch_columns(hidden_states) if patch_columns is None else patch_columns[:, :patch_columns.shape[1] // 2]
+                x = lin(cols, "patch_embedding").view(B, S, -1)
             t_emb = timestep_embedding(timestep.to(self.device), c.freq_dim).to(bf16)
             temb = lin(silu(lin(t_emb, "condition_embedder.time_embedder.linear_1")), "condition_embedder.time_embedder.linear_2")
             tproj = lin(silu(temb), "condition_embedder.time_proj").unflatten(1, (6, -1))
@@ -421,14 +566,27 @@ class MI355XWanTransformer3DModel(nn.Module):
         w, b = self.rparam(f"{name}.weight"), self.rparam(f"{name}.bias")
         return _LinearFunction.apply(x, w, b, self.rgrad(f"{name}.weight"), self.rgrad(f"{name}.bias"), gelu, need_dx, self._anchor)
 
-    def forward(self, hidden_states, timestep, encoder_hidden_states, encoder_hidden_states_image=None, return_dict: bool = False, **kwargs):
+    def forward(self, hidden_states, timestep, encoder_hidden_states, encoder_hidden_states_image=None, return_dict: bool = False, patch_columns=None,
+                latent_shape=None, **kwargs):
+        """``patch_columns`` (LoRA training of a control model): the patch embedding's GEMM operand [B S, 2 Kp] = [cols | cols] as ``ops.wan_control_pack``
+        writes it, in place of ``hidden_states`` (then None, with ``latent_shape`` = (B, F, H, W) of the latents)."""
         c = self.config
         if (encoder_hidden_states_image is not None) != (c.image_dim is not None):
             raise NotImplementedError("encoder_hidden_states_image goes with an image-to-video model (config.image_dim), and such a model needs it")
-        if hidden_states.shape[1] != c.in_channels:
+        if patch_columns is not None:
+            if self.lora_config is None or c.image_dim is not None:
+                raise NotImplementedError("patch_columns is the control LoRA path: a text-to-video model with adapters attached")
+            if hidden_states is not None or latent_shape is None or len(latent_shape) != 4:
+                raise ValueError("patch_columns replaces hidden_states (pass None) and needs latent_shape = (B, F, H, W)")
+            pt, ph, pw = c.patch_size
+            B, F_, H, W = latent_shape
+            want = (B * (F_ // pt) * (H // ph) * (W // pw), 2 * self.root_layout.offsets["patch_embedding.weight"][1][1])
+            if tuple(patch_columns.shape) != want or patch_columns.dtype != bf16 or not patch_columns.is_contiguous():
+                raise ValueError(f"patch_columns must be a contiguous bf16 {want} tensor ([cols | cols]), got {tuple(patch_columns.shape)}")
+        elif hidden_states.shape[1] != c.in_channels:
             raise ValueError(f"hidden_states has {hidden_states.shape[1]} channels, the model takes {c.in_channels}")
         if self.lora_config is not None:
-            return self._forward_frozen_root(hidden_states, timestep, encoder_hidden_states, return_dict, encoder_hidden_states_image)
+            return self._forward_frozen_root(hidden_states, timestep, encoder_hidden_states, return_dict, encoder_hidden_states_image, patch_columns, latent_shape)
         if c.image_dim is not None:
             raise NotImplementedError("Wan image-to-video: full fine-tuning is not covered by this backend; attach adapters first (add_adapter: LoRA training)")
         B, C, F_, H, W = hidden_states.shape

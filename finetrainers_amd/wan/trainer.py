@@ -192,6 +192,15 @@ class MI355XWanLoRAStep:
         self.grad_bucket_blocks = max(1, int(grad_bucket_blocks))
         self._spans: Dict[int, Tuple[int, int]] = {}
         off = 0
+        # control LoRA: the patch-embedding adapter sits at the FRONT of the flat buffers -- the backward finishes contiguous slices from the end, and the first
+        # trainable thing of the model is the last whose gradients become final
+        self._patch_span: Optional[Tuple[int, int]] = None
+        if transformer.patch_lora_A is not None:
+            views = []
+            for p in (transformer.patch_lora_A, transformer.patch_lora_B):
+                views.append(self.gflat[off:off + p.numel()].view(p.shape))
+                off += p.numel()
+            transformer._patch_grad_views, self._patch_span = (views[0], views[1]), (0, off)
         for blk in transformer.blocks:  # (the order of transformer.lora_parameters(): per block lora_A, lora_B, then the four feed-forward matrices)
             views, lo = [], off
             for p in blk.lora_parameters():
@@ -213,6 +222,7 @@ class MI355XWanLoRAStep:
         self._pending, self._ready, self.bucket_log = [], [], []
         for blk in self.transformer.blocks:
             blk._grad_hook = self._block_done if exchange else None
+        self.transformer._patch_grad_hook = self._patch_done if exchange and self._patch_span is not None else None
 
     def _flush(self) -> None:
         lo, hi = min(s_[0] for s_ in self._ready), max(s_[1] for s_ in self._ready)
@@ -230,9 +240,15 @@ class MI355XWanLoRAStep:
         if len(self._ready) >= self.grad_bucket_blocks or span[0] == 0:
             self._flush()
 
+    def _patch_done(self, transformer) -> None:
+        """The patch-embedding adapter's gradients are final (after block 0's): the last bucket, which starts at element 0, goes out."""
+        self._ready.append(self._patch_span)
+        self._flush()
+
     def _finish_exchange(self, failed: bool = False) -> None:
         for blk in self.transformer.blocks:
             blk._grad_hook = None
+        self.transformer._patch_grad_hook = None
         if failed:
             # a backward that raised after issuing some buckets: every rank issued the same collectives, so they complete -- wait for them and drop
             # the handles (the next step must not race the collective's stream on the gradient buffer, nor divide a tensor twice)
@@ -254,8 +270,12 @@ class MI355XWanLoRAStep:
 
     # ---- the step ---------------------------------------------------------------------------------------------------------------------------------
     def step(self, moments: torch.Tensor, encoder_hidden_states: torch.Tensor, latents_mean: torch.Tensor, latents_std: torch.Tensor,
-             sigmas: torch.Tensor, posterior_noise: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, **image_conditioning) -> Dict[str, torch.Tensor]:
-        """``image_conditioning`` (an image-to-video model): latent_condition, latent_condition_mask, encoder_hidden_states_image, handed to the specification."""
+             sigmas: torch.Tensor, posterior_noise: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
+             control_latents: Optional[torch.Tensor] = None, **image_conditioning) -> Dict[str, torch.Tensor]:
+        """``image_conditioning`` (an image-to-video model): latent_condition, latent_condition_mask, encoder_hidden_states_image, handed to the specification.
+        ``control_latents`` (a control model, with a control specification's ops as ``spec``): the control clip's stored moments [B, 2C, Fc, H, W]."""
+        if control_latents is not None:
+            image_conditioning["control_latents"] = control_latents
         pred, target, _ = self.spec.forward(self.transformer, moments, encoder_hidden_states, sigmas, latents_mean, latents_std, posterior_noise=posterior_noise,
                                             noise=noise, generator=self.generator, **image_conditioning)
         gas = self.gradient_accumulation_steps
@@ -277,6 +297,7 @@ class MI355XWanLoRAStep:
             lr = self.lr if self.lr_scheduler is None else self.lr_scheduler.current_lr()
             ops.clip_adamw_step(self.flat, self.gflat, self.exp_avg, self.exp_avg_sq, self.step_count, lr, self.betas, self.eps, self.weight_decay,
                                 self.max_grad_norm, scratch=self._scratch, grad_norm_out=gn)
+            self.transformer.mark_patch_adapter_updated()  # (the fused launch moved the adapters in place: the patch adapter folds again)
             if self.lr_scheduler is not None:
                 self.lr_scheduler.step()
         else:  # report the norm of what has accumulated so far; the window's clip happens with its optimiser step

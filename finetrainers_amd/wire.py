@@ -202,9 +202,15 @@ class PrecomputedSampleFeeder:
 # --------------------------------------------------------------------------------------------------------------------------
 # LoRA checkpoint
 # --------------------------------------------------------------------------------------------------------------------------
-def lora_config_metadata(rank: int, lora_alpha: float, target_modules) -> Dict[str, str]:
-    """The metadata block of finetrainers/trainer/sft_trainer/trainer.py:285-291."""
+def lora_config_metadata(rank: int, lora_alpha: float, target_modules, rank_pattern: Optional[Dict[str, int]] = None,
+                         alpha_pattern: Optional[Dict[str, float]] = None) -> Dict[str, str]:
+    """The metadata block of finetrainers/trainer/sft_trainer/trainer.py:285-291; with ``rank_pattern`` / ``alpha_pattern`` the control trainer's
+    (trainer/control_trainer/trainer.py:331-339: the full-rank adapter of the control injection layer)."""
     cfg = {"r": rank, "lora_alpha": lora_alpha, "init_lora_weights": True, "target_modules": target_modules}
+    if rank_pattern is not None:
+        cfg["rank_pattern"] = dict(rank_pattern)
+    if alpha_pattern is not None:
+        cfg["alpha_pattern"] = dict(alpha_pattern)
     return {"lora_config": json.dumps(cfg, indent=4)}
 
 

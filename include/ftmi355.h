@@ -795,6 +795,43 @@ int ftmi_lora_refresh_n(const float* a_f32, const float* b_f32, void* lora_a_sp,
  * t_sp [2 cols, rows], t_ext [cols, 3 rows]: the same two layouts of w^T. */
 int ftmi_lora_split(const float* w, int rows, int cols, void* sp, void* ext, void* t_sp, void* t_ext, ftmi_stream stream);
 
+/* ---- Wan control LoRA outside the blocks (csrc/wan_control.hip) ----
+ * c [M, N] (fp32, row stride ldc) = (accumulate ? c : 0) + scale * a b, a (m, k) at a[m * lda_row + k * lda_col], b (k, n) at b[k * ldb_row + n * ldb_col]: strides
+ * express transposes.  fp32 FMAs, k ascending, one owner per output, no atomics: two runs give the same bits.  hi_lo_out != NULL: the result also as two bf16
+ * column planes, hi_lo_out[m * ld_hl + n] = bf(c), hi_lo_out[m * ld_hl + N + n] = bf(c - bf(c)).  M, N, K multiples of 64 (FTMI_ERR_UNSUPPORTED otherwise);
+ * c 16-byte aligned with ldc % 4 == 0. */
+int ftmi_f32_gemm(int M, int N, int K, const float* a, long lda_row, long lda_col, const float* b, long ldb_row, long ldb_col, float* c, long ldc, float scale,
+                  int accumulate, void* hi_lo_out, long ld_hl, ftmi_stream stream);
+/* The control specification's input construction in one pass (finetrainers/models/wan/control_specification.py:243-308).  moments [B, 2C, F, H, W] and
+ * control_moments [B, 2C, Fc, H, W] bf16 (only the mean halves are read: the posterior's mode), noise [B, C, F, H, W] bf16, sigmas [B] fp32, latents_mean /
+ * latents_std [C] fp32 (latents_std is 1 / std: multiplied), keep [B, F] bytes (1 keeps the control frame, 0 drops it; frames >= Fc are zero).
+ *   z = bf((mu - mean) * std)      noisy = bf((1 - sigma) * z + sigma * noise)      target [B, C, F, H, W] = bf(noise - z)
+ *   cols2 [B S, 2 Kp] = [cols | cols], Kp = 2C pt ph pw, tokens in (f, h, w) order, columns in (c, pt, ph, pw) order: channels 0..C-1 the noisy latents,
+ *   channels C..2C-1 bf((mu_c - mean) * std) of a kept control frame, that value times zero for a dropped one, +0 past the control clip. */
+typedef struct ftmi_wan_control_pack_config {
+    int B, C, F, Fc, H, W;
+    int pt, ph, pw;
+} ftmi_wan_control_pack_config;
+int ftmi_wan_control_pack(const ftmi_wan_control_pack_config* cfg, const void* moments, const void* control_moments, const void* noise, const float* sigmas,
+                          const float* latents_mean, const float* latents_std, const unsigned char* keep, void* cols2, void* target, ftmi_stream stream);
+/* The full-rank LoRA adapter of the widened patch embedding, folded: y [M, D] = bf(bf(cols W^T + bias) + s (cols A^T) B^T) with fp32 A [r, Kp], B [D, r],
+ * computed through dW = s B A (fp32, [D, Kp]) because r >= Kp.
+ *   forward : refold != 0: dw_f32 [D, Kp] <- s B A and w2 [D, 2 Kp] <- its bf16 planes [hi | lo] (refold = 0 reuses w2: the parameters did not move);
+ *             then ONE NT GEMM: K = Kp over cols2[:, :Kp] and w [D, Kp], K-extension K2 = 2 Kp over cols2 = [cols | cols] and w2, plain store into out.
+ *   backward: g_ws [D, Kp] fp32 <- dx0^T cols (zeroed here, one TN GEMM; dx0 [M, D] bf16 = block 0's input gradient), grad_b [D, r] += s g_ws A^T,
+ *             grad_a [r, Kp] += s B^T g_ws.  No input gradient: the input is data.
+ * FTMI_ERR_UNSUPPORTED for r % 64, Kp % 64 or D % 64. */
+typedef struct ftmi_wan_patch_lora_config {
+    int M, D, Kp, r;
+    float s;
+    int gemm_variant;
+    int refold;
+} ftmi_wan_patch_lora_config;
+int ftmi_wan_patch_lora_forward(const ftmi_wan_patch_lora_config* cfg, const void* w, const void* bias, const float* a_f32, const float* b_f32, const void* cols2,
+                                float* dw_f32, void* w2, void* out, ftmi_stream stream);
+int ftmi_wan_patch_lora_backward(const ftmi_wan_patch_lora_config* cfg, const float* a_f32, const float* b_f32, const void* cols2, const void* dx0, float* g_ws,
+                                 float* grad_a, float* grad_b, ftmi_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

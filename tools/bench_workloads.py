@@ -1,5 +1,5 @@
 """The workloads `bench.py --workload {ltx,cogvideox,wan,hunyuan}` can time (BASELINE.json configs[1], [2], [3], [4]), plus the Wan LoRA recipe
-(`wan_lora`, run through this file's own command line: `python tools/bench_workloads.py --workload wan_lora`): for each one a
+(`wan_lora`) and control recipe (`wan_control_lora`), run through this file's own command line (`python tools/bench_workloads.py --workload wan_lora`): for each one a
 builder that puts a random-init model of the named architecture, its step object and one synthetic batch of the named clip shape on the GPU
 and returns the step closure + the static part of the JSON line, and a `cpu_baseline` that times the oracle (CPU restatement of the reference
 path, kind "port") on a bounded sample of the same workload.  Bench infrastructure: the only place outside tests/ and __graft_entry__.smoke()
@@ -238,6 +238,70 @@ def build_wan_lora(args, par, dev) -> Dict[str, Any]:
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------------
+# Wan2.1-T2V-1.3B control LoRA (examples/training/control/wan/image_condition/train.sh): rank 128 on the eight attention projections of every block (the
+# recipe's target_modules as written selects those), the patch embedding widened to 32 input channels with its full-rank (r = 1536) adapter, `index` frame
+# conditioning on frame 0, gradient checkpointing, one 49 x 480 x 832 bucket; the control clip has the latents' 13 frames.
+# ------------------------------------------------------------------------------------------------------------------------------------------
+def build_wan_control_lora(args, par, dev) -> Dict[str, Any]:
+    from finetrainers_amd.wan import MI355XWanControlSpecOps, MI355XWanLoRAStep, MI355XWanTransformer3DModel, WanTransformerConfig
+
+    layers = args.layers if args.layers > 0 else 30
+    cfg = WanTransformerConfig(num_layers=layers)
+    model = MI355XWanTransformer3DModel(cfg, device=dev)
+    g = torch.Generator(device=dev).manual_seed(0)
+    D = cfg.inner_dim
+    with torch.no_grad():
+        for name, v in model.state_dict_views().items():
+            if name.endswith("weight") and v.dim() >= 2:
+                v.copy_((torch.randn(v.shape, generator=g, device=dev) / v.shape[-1] ** 0.5).to(bf16))
+            elif "norm" in name and name.endswith("weight"):
+                v.fill_(1.0)
+            elif "scale_shift_table" in name:
+                v.copy_((torch.randn(v.shape, generator=g, device=dev) / D ** 0.5).to(bf16))
+            else:
+                v.copy_((0.02 * torch.randn(v.shape, generator=g, device=dev)).to(bf16))
+    for blk in model.blocks:
+        blk.mark_updated()
+    model.expand_patch_embedding(32)
+    rank = args.rank
+    model.add_adapter(rank, float(rank), target_modules="(^patch_embedding$)|(blocks.*(to_q|to_k|to_v|to_out.0|ff.net.0.proj|ff.net.2))",
+                      rank_pattern={"patch_embedding": D}, alpha_pattern={"patch_embedding": D})
+    model.apply_activation_checkpointing("full")
+    with torch.no_grad():
+        for blk in model.blocks:
+            blk.lora_B[:, :, :rank].normal_(0, 0.01, generator=g)  # B != 0 so every gradient path carries data
+        model.patch_lora_B.normal_(0, 0.01, generator=g)
+    spec = MI355XWanControlSpecOps()
+    spec.frame_conditioning_type, spec.frame_conditioning_index = "index", 0
+    step = MI355XWanLoRAStep(model, spec=spec, lr=1e-4, generator=torch.Generator(device=dev).manual_seed(1 + par.rank), parallel=par if par.world_size > 1 else None)
+    g.manual_seed(100 + par.rank)
+    B, C, F_, H, W, T = 1, 16, 13, 60, 104, 512
+    moments = torch.randn((B, 2 * C, F_, H, W), generator=g, device=dev).to(bf16)
+    control = torch.randn((B, 2 * C, F_, H, W), generator=g, device=dev).to(bf16)
+    text = torch.randn((B, T, cfg.text_dim), generator=g, device=dev).to(bf16)
+    mean, std = torch.zeros(C, device=dev), torch.ones(C, device=dev)
+    sig = torch.tensor([0.6], device=dev)
+    S, Fd, Kp = 13 * 30 * 52, cfg.ffn_dim, 128
+    lin = 2.0 * S * (6 * D * D + 2 * D * Fd) + 2.0 * T * 2 * D * D
+    att = 4.0 * S * S * D + 4.0 * S * T * D
+    patch = 2.0 * S * D * 4 * Kp + 3 * 2.0 * D * D * Kp  # forward K = Kp + 2 Kp, backward Kp; the fold and its two gradients
+    flop = layers * (3.0 * lin + 4.5 * att) + patch
+    return {
+        "one_step": lambda: step.step(moments, text, mean, std, sig, control_latents=control),
+        "samples_per_step": 1,
+        "step_tflop": flop / 1e12,
+        "metric": "train samples/sec (+ step ms) Wan-T2V-1.3B control LoRA 49x480x832 (the reference's Wan control recipe)",
+        "data": "synthetic posterior moments [1,32,13,60,104] for the clip and for the control clip + random text embeds [1,512,4096], random-init weights of the Wan2.1-T2V-1.3B DiT",
+        "config": {"workload": f"Wan-T2V-1.3B control LoRA rank={rank} + full-rank patch-embedding adapter, bf16 step over the frozen base, index conditioning on frame 0, "
+                               f"49x480x832 clip ({S} video + {T} text tokens), batch 1 per GPU, {layers} blocks" + ("" if layers == 30 else " -- REDUCED depth"),
+                   "model": f"Wan2.1-T2V-1.3B DiT with a 32-channel patch embedding: 30 blocks, width 1536, 12 x 128 heads, frozen; 240 fp32 block adapters + patch_embedding (r = {D})",
+                   "seq_len": S, "adapters_per_block": 8, "activation_checkpointing": True,
+                   "orchestration": "one C call per block and direction; pack kernel + folded patch adapter at the root"},
+        "layers": layers,
+    }
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------------
 # Wan2.1-I2V-14B-480P LoRA (examples/training/sft/wan_i2v/3dgs_dissolve/train.sh): the same adapters on the image-to-video model -- width 5120,
 # 40 x 128 heads, feed-forward 13824, 40 blocks, 36 input channels, 257 CLIP image tokens in every block's attn2; the recipe's 49 x 480 x 832 bucket
 # (20 280 video + 512 text tokens), gradient checkpointing as in the recipe.  --layers N runs fewer blocks; the row states how many ran.
@@ -403,6 +467,7 @@ def cpu_baseline_hunyuan(args, ctx) -> Dict[str, Any]:
 WORKLOADS = {"cogvideox": (build_cogvideox, lambda a, c: cpu_baseline_cogvideox(a, c["layers"])),
              "wan": (build_wan, lambda a, c: cpu_baseline_wan(a, c["layers"])),
              "wan_lora": (build_wan_lora, lambda a, c: cpu_baseline_wan(a, c["layers"])),  # (yardstick on the host: the full fine-tune block, an upper bound of the LoRA block's work)
+             "wan_control_lora": (build_wan_control_lora, None),  # (no host yardstick; run with --rank 128: the recipe's rank)
              "wan_i2v_lora": (build_wan_i2v_lora, None),  # (no host yardstick: this row runs through this file's own command line only)
              "hunyuan": (build_hunyuan, cpu_baseline_hunyuan)}
 
