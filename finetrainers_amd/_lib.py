@@ -172,6 +172,27 @@ class WanPatchLoraConfig(Structure):
     _fields_ = [("M", c_int), ("D", c_int), ("Kp", c_int), ("r", c_int), ("s", c_float), ("gemm_variant", c_int), ("refold", c_int)]
 
 
+class WanSampleGeometry(Structure):
+    """include/ftmi355.h: ftmi_wan_sample_geometry."""
+
+    _fields_ = [(n, c_int) for n in ("B", "C", "Cx", "F", "H", "W", "pt", "ph", "pw", "Kp", "copies", "P", "po")]
+
+
+class WanSampleConfig(Structure):
+    """include/ftmi355.h: ftmi_wan_sample_config."""
+
+    _fields_ = [("geo", WanSampleGeometry), ("T", c_int), ("TI", c_int), ("D", c_int), ("heads", c_int), ("ffn_dim", c_int), ("L", c_int), ("eps", c_float),
+                ("gemm_variant", c_int), ("r", c_int), ("lora_scale", c_float), ("ffn", c_int), ("patch_fold", c_int), ("patch_r", c_int),
+                ("patch_scale", c_float), ("steps", c_int), ("guidance", c_float)]
+
+
+class WanSampleWeights(Structure):
+    """include/ftmi355.h: ftmi_wan_sample_weights (``blocks``: a host array of WanLoraFfnBlockWeights, ``img_params``: a host array of pointers)."""
+
+    _fields_ = [("blocks", POINTER(WanLoraFfnBlockWeights)), ("img_params", POINTER(c_void_p))] + [
+        (n, c_void_p) for n in ("patch_w", "patch_b", "proj_w", "proj_b", "patch_lora_a", "patch_lora_b", "patch_dw", "patch_w2")]
+
+
 class WanRowArgs(Structure):
     """include/ftmi355.h: ftmi_wan_row_args."""
 
@@ -319,6 +340,12 @@ _SIGS = {
     "ftmi_wan_control_pack": (c_int, [POINTER(WanControlPackConfig)] + [c_void_p] * 10),
     "ftmi_wan_patch_lora_forward": (c_int, [POINTER(WanPatchLoraConfig)] + [c_void_p] * 9),
     "ftmi_wan_patch_lora_backward": (c_int, [POINTER(WanPatchLoraConfig)] + [c_void_p] * 8),
+    "ftmi_wan_sample_init": (c_int, [POINTER(WanSampleGeometry)] + [c_void_p] * 5),
+    "ftmi_wan_sample_step": (c_int, [POINTER(WanSampleGeometry), c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
+    "ftmi_wan_sample_finish": (c_int, [POINTER(WanSampleGeometry)] + [c_void_p] * 5),
+    "ftmi_wan_sample_mod": (c_int, [POINTER(c_void_p), c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "ftmi_wan_sample_workspace_bytes": (c_size_t, [POINTER(WanSampleConfig)]),
+    "ftmi_wan_sample": (c_int, [POINTER(WanSampleConfig), POINTER(WanSampleWeights)] + [c_void_p] * 11 + [c_size_t, c_void_p]),
     "ftmi_hy_dual_saved_bytes": (c_size_t, [POINTER(HyDualConfig)]),
     "ftmi_hy_dual_scratch_bytes": (c_size_t, [POINTER(HyDualConfig)]),
     "ftmi_hy_dual_forward": (c_int, [POINTER(HyDualConfig), POINTER(HyDualWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -897,4 +897,36 @@ int ftmi_wan_patch_lora_backward(const ftmi_wan_patch_lora_config* cfg, const fl
     return wan_patch_lora_backward(*cfg, a_f32, b_f32, (const bf16_t*)cols2, (const bf16_t*)dx0, g_ws, grad_a, grad_b, (hipStream_t)stream);
 }
 
+int ftmi_wan_sample_init(const ftmi_wan_sample_geometry* geo, const float* latents, const void* extra, float* x, void* cols, ftmi_stream stream) {
+    if (!geo || !latents || !x || !cols) return set_error(FTMI_ERR_INVALID, "ftmi_wan_sample_init: null argument");
+    return wan_sample_init(*geo, latents, (const bf16_t*)extra, x, (bf16_t*)cols, (hipStream_t)stream);
+}
+
+int ftmi_wan_sample_step(const ftmi_wan_sample_geometry* geo, const void* pred, float* x, const float* sigma, const float* sigma_next, float guidance, void* cols,
+                         ftmi_stream stream) {
+    if (!geo || !x || (!pred && !cols)) return set_error(FTMI_ERR_INVALID, "ftmi_wan_sample_step: null argument");
+    return wan_sample_step(*geo, (const bf16_t*)pred, x, sigma, sigma_next, 1, guidance, (bf16_t*)cols, (hipStream_t)stream);
+}
+
+int ftmi_wan_sample_finish(const ftmi_wan_sample_geometry* geo, const float* x, const float* mean, const float* std_, void* latents, ftmi_stream stream) {
+    if (!geo || !x || !mean || !std_ || !latents) return set_error(FTMI_ERR_INVALID, "ftmi_wan_sample_finish: null argument");
+    return wan_sample_finish(*geo, x, mean, std_, (bf16_t*)latents, (hipStream_t)stream);
+}
+
+int ftmi_wan_sample_mod(const void* const* tables, int L, const void* tproj, float* mod, int rows, int D, ftmi_stream stream) {
+    if (!tables || !tproj || !mod) return set_error(FTMI_ERR_INVALID, "ftmi_wan_sample_mod: null argument");
+    return wan_sample_mod((const bf16_t* const*)tables, L, (const bf16_t*)tproj, mod, rows, D, (hipStream_t)stream);
+}
+
+size_t ftmi_wan_sample_workspace_bytes(const ftmi_wan_sample_config* cfg) { return cfg ? wan_sample_workspace_bytes(*cfg) : 0; }
+
+int ftmi_wan_sample(const ftmi_wan_sample_config* cfg, const ftmi_wan_sample_weights* w, void* cols, float* x, const void* tproj, const float* head_shift,
+                    const float* head_scale, const void* enc, const void* enc_img, const float* rope_cos, const float* rope_sin, const float* sigmas,
+                    void* workspace, size_t workspace_bytes, ftmi_stream stream) {
+    if (!cfg || !w || !cols || !x || !tproj || !head_shift || !head_scale || !enc || !rope_cos || !rope_sin || !sigmas || !workspace)
+        return set_error(FTMI_ERR_INVALID, "ftmi_wan_sample: null argument");
+    return wan_sample(*cfg, *w, (bf16_t*)cols, x, (const bf16_t*)tproj, head_shift, head_scale, (const bf16_t*)enc, (const bf16_t*)enc_img, rope_cos, rope_sin, sigmas,
+                      workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -415,6 +415,16 @@ int wan_lora_ffn_block_backward(const ftmi_wan_lora_ffn_block_config& c, const f
                                 const bf16_t* enc, const bf16_t* enc_img, const float* mod, const float* rope_cos, const float* rope_sin, const bf16_t* dout,
                                 bf16_t* dx, bf16_t* denc, float* grad_a, float* grad_b, float* grad_ffn_a1, float* grad_ffn_b1, float* grad_ffn_a2,
                                 float* grad_ffn_b2, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st);
+// Wan latent sampling (wan_sample.hip: the layout kernels; wan_sample_dit.hip: the loop).  sigma / sigma_next element b at [b * sig_stride] (0: one value for all)
+int wan_sample_init(const ftmi_wan_sample_geometry& g, const float* latents, const bf16_t* extra, float* x, bf16_t* cols, hipStream_t st);
+int wan_sample_step(const ftmi_wan_sample_geometry& g, const bf16_t* pred, float* x, const float* sigma, const float* sigma_next, long sig_stride, float guidance,
+                    bf16_t* cols, hipStream_t st);
+int wan_sample_finish(const ftmi_wan_sample_geometry& g, const float* x, const float* mean, const float* std_, bf16_t* latents, hipStream_t st);
+int wan_sample_mod(const bf16_t* const* tables, int L, const bf16_t* tproj, float* mod, int rows, int D, hipStream_t st);
+size_t wan_sample_workspace_bytes(const ftmi_wan_sample_config& c);
+int wan_sample(const ftmi_wan_sample_config& c, const ftmi_wan_sample_weights& w, bf16_t* cols, float* x, const bf16_t* tproj, const float* head_shift,
+               const float* head_scale, const bf16_t* enc, const bf16_t* enc_img, const float* rope_cos, const float* rope_sin, const float* sigmas, void* ws,
+               size_t ws_bytes, hipStream_t st);
 int adamw_bf16_step(bf16_t* p, const float* g, bf16_t* m, bf16_t* v, long n, const float* sumsq_in, float max_norm, float lr, float beta1, float beta2,
                     float eps, float wd, int step, float* grad_norm_out, hipStream_t st);
 

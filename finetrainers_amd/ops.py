@@ -971,3 +971,118 @@ def wan_patch_lora_backward(cols2, dx0, lora_a, lora_b, g_ws, grad_a, grad_b, s:
     cfg = _patch_lora_cfg(M, D, Kp, r, s, False, 8)
     check(_lib.load().ftmi_wan_patch_lora_backward(ctypes.byref(cfg), ptr(lora_a), ptr(lora_b), ptr(cols2), ptr(dx0), ptr(g_ws), ptr(grad_a), ptr(grad_b), stream_ptr()),
           "ftmi_wan_patch_lora_backward")
+
+
+# ---- Wan latent sampling (include/ftmi355.h: ftmi_wan_sample_*; csrc/wan_sample.hip, csrc/wan_sample_dit.hip) -------------------------------------------
+def wan_sample_geometry(B: int, C: int, frames: int, height: int, width: int, Kp: int, extra_channels: int = 0, copies: int = 1, guidance: bool = True,
+                        patch_size=(1, 2, 2), po: Optional[int] = None) -> "_lib.WanSampleGeometry":
+    """The layout of a sampling run: latents [B, C, frames, height, width] (+ ``extra_channels``), cols [P B S, copies Kp], pred [P B, S, po]."""
+    pt, ph, pw = patch_size
+    return _lib.WanSampleGeometry(B=B, C=C, Cx=extra_channels, F=frames, H=height, W=width, pt=pt, ph=ph, pw=pw, Kp=Kp, copies=copies, P=2 if guidance else 1,
+                                  po=C * pt * ph * pw if po is None else po)
+
+
+def _wan_sample_tokens(geo) -> int:
+    if geo.F % geo.pt or geo.H % geo.ph or geo.W % geo.pw:
+        raise ValueError("wan_sample: the latent size must be whole patches")
+    return (geo.F // geo.pt) * (geo.H // geo.ph) * (geo.W // geo.pw)
+
+
+def _wan_sample_buffers(geo, x, cols, what: str) -> None:
+    S, Kc = _wan_sample_tokens(geo), geo.C * geo.pt * geo.ph * geo.pw
+    if x is not None and (tuple(x.shape) != (geo.B, S, Kc) or x.dtype != torch.float32 or not x.is_contiguous() or not x.is_cuda):
+        raise ValueError(f"{what}: x must be a contiguous fp32 [{geo.B}, {S}, {Kc}] GPU tensor, got {tuple(x.shape)}")
+    if cols is not None and (tuple(cols.shape) != (geo.P * geo.B * S, geo.copies * geo.Kp) or cols.dtype != bf16 or not cols.is_contiguous() or not cols.is_cuda):
+        raise ValueError(f"{what}: cols must be a contiguous bf16 [{geo.P * geo.B * S}, {geo.copies * geo.Kp}] GPU tensor, got {tuple(cols.shape)}")
+
+
+def wan_sample_init(geo, latents, extra=None, x=None, cols=None):
+    """latents fp32 [B, C, F, H, W] (+ extra bf16 [B, Cx, F, H, W]) -> (x fp32 [B, S, Kc], cols bf16 [P B S, copies Kp]): ftmi_wan_sample_init."""
+    require_gpu_tensor(latents, "latents", torch.float32)
+    if tuple(latents.shape) != (geo.B, geo.C, geo.F, geo.H, geo.W) or not latents.is_contiguous():
+        raise ValueError(f"wan_sample_init: latents must be contiguous [{geo.B}, {geo.C}, {geo.F}, {geo.H}, {geo.W}], got {tuple(latents.shape)}")
+    if (extra is not None) != (geo.Cx > 0):
+        raise ValueError("wan_sample_init: the extra channels go with their tensor, and only with it")
+    if extra is not None:
+        require_gpu_tensor(extra, "extra", bf16)
+        if tuple(extra.shape) != (geo.B, geo.Cx, geo.F, geo.H, geo.W) or not extra.is_contiguous():
+            raise ValueError(f"wan_sample_init: extra must be contiguous [{geo.B}, {geo.Cx}, {geo.F}, {geo.H}, {geo.W}], got {tuple(extra.shape)}")
+    S, Kc = _wan_sample_tokens(geo), geo.C * geo.pt * geo.ph * geo.pw
+    x = torch.empty((geo.B, S, Kc), dtype=torch.float32, device=latents.device) if x is None else x
+    cols = torch.empty((geo.P * geo.B * S, geo.copies * geo.Kp), dtype=bf16, device=latents.device) if cols is None else cols
+    _wan_sample_buffers(geo, x, cols, "wan_sample_init")
+    check(_lib.load().ftmi_wan_sample_init(ctypes.byref(geo), ptr(latents), ptr(extra), ptr(x), ptr(cols), stream_ptr()), "ftmi_wan_sample_init")
+    return x, cols
+
+
+def wan_sample_step(geo, pred, x, sigma, sigma_next, guidance: float, cols=None) -> None:
+    """One sampler step in place (ftmi_wan_sample_step): pred bf16 [P B, S, po] (None: only the bf16 copies), x fp32 [B, S, Kc], sigma / sigma_next fp32 [B] on
+    the device, cols bf16 [P B S, copies Kp] (None: only the update)."""
+    _wan_sample_buffers(geo, x, cols, "wan_sample_step")
+    S = _wan_sample_tokens(geo)
+    if pred is not None:
+        require_gpu_tensor(pred, "pred", bf16)
+        if pred.numel() != geo.P * geo.B * S * geo.po or not pred.is_contiguous():
+            raise ValueError(f"wan_sample_step: pred must be contiguous [{geo.P * geo.B}, {S}, {geo.po}], got {tuple(pred.shape)}")
+        for n, t in (("sigma", sigma), ("sigma_next", sigma_next)):
+            require_gpu_tensor(t, n, torch.float32)
+            if t.numel() != geo.B or not t.is_contiguous():
+                raise ValueError(f"wan_sample_step: {n} holds one value per sample")
+    check(_lib.load().ftmi_wan_sample_step(ctypes.byref(geo), ptr(pred), ptr(x), ptr(sigma), ptr(sigma_next), float(guidance), ptr(cols), stream_ptr()),
+          "ftmi_wan_sample_step")
+
+
+def wan_sample_finish(geo, x, mean, std):
+    """x fp32 [B, S, Kc] -> latents bf16 [B, C, F, H, W] = bf16(x * std[c] + mean[c]); ``std`` is the VAE's standard deviation itself (ftmi_wan_sample_finish)."""
+    _wan_sample_buffers(geo, x, None, "wan_sample_finish")
+    for n, t in (("mean", mean), ("std", std)):
+        require_gpu_tensor(t, n, torch.float32)
+        if t.numel() != geo.C or not t.is_contiguous():
+            raise ValueError(f"wan_sample_finish: {n} holds one value per channel")
+    out = torch.empty((geo.B, geo.C, geo.F, geo.H, geo.W), dtype=bf16, device=x.device)
+    check(_lib.load().ftmi_wan_sample_finish(ctypes.byref(geo), ptr(x), ptr(mean), ptr(std), ptr(out), stream_ptr()), "ftmi_wan_sample_finish")
+    return out
+
+
+def wan_sample_mod(tables, tproj, rows: int):
+    """mod fp32 [L, rows, 6, D] = float(tables[l]) + float(tproj) for the L blocks' scale_shift_table views (bf16, 6 D elements each) and one step's time
+    projection bf16 [6 D] (ftmi_wan_sample_mod)."""
+    L, D = len(tables), tproj.numel() // 6
+    for t in list(tables) + [tproj]:
+        require_gpu_tensor(t, "scale_shift_table / tproj", bf16)
+        if t.numel() != 6 * D or not t.is_contiguous():
+            raise ValueError("wan_sample_mod: every table and the time projection hold 6 D contiguous values")
+    out = torch.empty((L, rows, 6, D), dtype=torch.float32, device=tproj.device)
+    arr = (ctypes.c_void_p * L)(*[t.data_ptr() for t in tables])
+    check(_lib.load().ftmi_wan_sample_mod(arr, L, ptr(tproj), ptr(out), int(rows), D, stream_ptr()), "ftmi_wan_sample_mod")
+    return out
+
+
+def wan_sample_workspace_bytes(cfg) -> int:
+    n = int(_lib.load().ftmi_wan_sample_workspace_bytes(ctypes.byref(cfg)))
+    if n == 0:
+        raise ValueError(f"wan_sample: {_lib.last_error()}")
+    return n
+
+
+def wan_sample(cfg, weights, cols, x, tproj, head_shift, head_scale, enc, enc_img, rope, sigmas, workspace=None) -> None:
+    """The whole denoising loop in ONE call (ftmi_wan_sample), in place on ``x`` / ``cols`` (as ``wan_sample_init`` wrote them).  tproj bf16 [steps, 6 D];
+    head_shift / head_scale fp32 [steps, D]; enc bf16 [P B, T, D] (unconditional rows first); enc_img bf16 [P B, TI, D] or None; rope = (cos, sin) fp32 [S, 64];
+    sigmas fp32 [steps + 1] on the device.  ``workspace``: a uint8 GPU tensor of at least ``wan_sample_workspace_bytes(cfg)`` (allocated when None)."""
+    geo, n, D = cfg.geo, cfg.steps, cfg.D
+    _wan_sample_buffers(geo, x, cols, "wan_sample")
+    S, rows = _wan_sample_tokens(geo), geo.P * geo.B
+    want = [("tproj", tproj, bf16, (n, 6 * D)), ("head_shift", head_shift, torch.float32, (n, D)), ("head_scale", head_scale, torch.float32, (n, D)),
+            ("enc", enc, bf16, (rows, cfg.T, D)), ("rope cos", rope[0], torch.float32, (S, 64)), ("rope sin", rope[1], torch.float32, (S, 64)),
+            ("sigmas", sigmas, torch.float32, (n + 1,))]
+    if cfg.TI > 0:
+        want.append(("enc_img", enc_img, bf16, (rows, cfg.TI, D)))
+    for name, t, dt, shape in want:
+        if t is None or not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"wan_sample: {name} must be a contiguous {dt} {shape} GPU tensor, got {None if t is None else tuple(t.shape)}")
+    need = wan_sample_workspace_bytes(cfg)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
+    check(_lib.load().ftmi_wan_sample(ctypes.byref(cfg), ctypes.byref(weights), ptr(cols), ptr(x), ptr(tproj), ptr(head_shift), ptr(head_scale), ptr(enc),
+                                      ptr(enc_img if cfg.TI > 0 else None), ptr(rope[0]), ptr(rope[1]), ptr(sigmas), ptr(workspace), workspace.numel(),
+                                      stream_ptr()), "ftmi_wan_sample")

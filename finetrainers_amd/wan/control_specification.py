@@ -20,7 +20,7 @@ from typing import Dict, List, Optional
 import torch
 
 from .. import ops
-from ..control import frame_keep_mask
+from ..control import apply_frame_conditioning_on_latents, frame_keep_mask
 from ..utils.reference_base import as_drop_in, keep_or_default
 from .specification import MI355XWanModelSpecification, MI355XWanSpecOps
 
@@ -95,7 +95,8 @@ class MI355XWanControlModelSpecification(MI355XWanControlSpecOps, MI355XWanModel
     """Mirror of ``WanControlModelSpecification``: the constructor keywords (``control_model_processors`` included), ``control_injection_layer_name``,
     ``_original_control_layer_in_features`` / ``_out_features``, ``_qk_norm_identifiers``, ``_trainer_init``, ``load_diffusion_models(new_in_features)``,
     ``forward`` with the reference's signature and ``_save_lora_weights`` with the norm state dict.  Text encoder, VAE, ``prepare_latents`` (which adds
-    ``control_latents`` through ``control_model_processors``), pipeline and validation stay with the reference."""
+    ``control_latents`` through ``control_model_processors``), pipeline and the inherited ``validation`` stay with the reference; ``validation_latents`` runs its
+    denoising loop over this backend's transformer (wan/sampler.py)."""
 
     def __init__(self, control_model_processors: Optional[List] = None, **kwargs) -> None:
         MI355XWanModelSpecification.MI355X_OVERRIDES.__init__(self, **kwargs)
@@ -163,6 +164,26 @@ class MI355XWanControlModelSpecification(MI355XWanControlSpecOps, MI355XWanModel
         mean, std = latent_model_conditions.pop("latents_mean"), latent_model_conditions.pop("latents_std")
         return MI355XWanControlSpecOps.forward(self, transformer, latents, condition_model_conditions["encoder_hidden_states"], sigmas, mean, std, generator=generator,
                                                control_latents=control, noise=kwargs.get("noise"), use_pack_kernel=kwargs.get("use_pack_kernel"), keep=kwargs.get("keep"))
+
+    def validation_latents(self, transformer, prompt_embeds: torch.Tensor, negative_prompt_embeds: Optional[torch.Tensor], control_latents: torch.Tensor,
+                           num_frames: int, height: int, width: int, latents_mean: torch.Tensor, latents_std: torch.Tensor, num_inference_steps: int = 50,
+                           guidance_scale: float = 5.0, generator: Optional[torch.Generator] = None, frame_conditioning_type="full",
+                           frame_conditioning_index: int = 0, scheduler_config=None, **sample_kwargs) -> torch.Tensor:
+        """The denoising loop of ``validation`` (control_specification.py:310-377) in latent space.  ``control_latents`` [B, C, Fc, H, W]: the VAE encoding of the
+        control clip (the posterior's mode), not yet normalised; ``latents_mean`` / ``latents_std`` [C]: the VAE's statistics themselves.  As the reference
+        does (:350-359) the control latents are normalised with ``1 / std`` and frame-conditioned to ``num_frames`` latent frames (control.py); the sampler
+        then holds them in the second half of the model's input channels.  -> denormalised latents [B, C, F, H, W] bf16 for the pipeline's VAE decode."""
+        from .sampler import MI355XWanLatentSampler
+
+        if self.frame_conditioning_concatenate_mask:
+            raise NotImplementedError(_MASK_REASON)
+        ctrl = self.normalize_latents(control_latents.to(bf16), latents_mean.float(), 1.0 / latents_std.float())
+        ctrl = apply_frame_conditioning_on_latents(ctrl, num_frames, channel_dim=1, frame_dim=2, frame_conditioning_type=frame_conditioning_type,
+                                                   frame_conditioning_index=frame_conditioning_index, concatenate_mask=False)
+        return MI355XWanLatentSampler(transformer, scheduler_config).sample(prompt_embeds, negative_prompt_embeds, num_frames, height, width,
+                                                                            num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
+                                                                            generator=generator, latents_mean=latents_mean, latents_std=latents_std,
+                                                                            control_latents=ctrl, **sample_kwargs)
 
     def _save_lora_weights(self, directory: str, transformer_state_dict: Optional[Dict[str, torch.Tensor]] = None,
                            norm_state_dict: Optional[Dict[str, torch.Tensor]] = None, scheduler=None, metadata: Optional[Dict[str, str]] = None, *args, **kwargs) -> None:

@@ -89,8 +89,8 @@ IGNORE_KEYS_FOR_COLLATION = {"height", "width", "num_frames", "frame_rate", "rop
 class MI355XWanModelSpecification(MI355XWanSpecOps):
     """Mirror of ``WanModelSpecification`` (finetrainers/models/wan/base_specification.py:210-577) for the SFT hot path (T2V, and I2V LoRA): same constructor keywords,
     ``_resolution_dim_keys``, ``load_diffusion_models``, ``collate_*`` (``latents_mean`` / ``latents_std`` pass through uncollated, modeling_utils.py:22),
-    ``forward`` with the reference's signature, ``_save_model`` writing a diffusers transformer directory.  Text encoder, VAE, pipeline and validation stay
-    with the reference."""
+    ``forward`` with the reference's signature, ``_save_model`` writing a diffusers transformer directory.  Text encoder, VAE and pipeline stay with the
+    reference, and so does the inherited ``validation``; ``validation_latents`` runs its denoising loop over this backend's transformer (wan/sampler.py)."""
 
     def __init__(self, pretrained_model_name_or_path: Optional[str] = "Wan-AI/Wan2.1-T2V-1.3B-Diffusers", tokenizer_id: Optional[str] = None,
                  text_encoder_id: Optional[str] = None, transformer_id: Optional[str] = None, vae_id: Optional[str] = None,
@@ -157,6 +157,19 @@ class MI355XWanModelSpecification(MI355XWanSpecOps):
                                         latent_condition=latent_model_conditions.pop("latent_condition", None),
                                         latent_condition_mask=latent_model_conditions.pop("latent_condition_mask", None),
                                         encoder_hidden_states_image=condition_model_conditions.get("encoder_hidden_states_image"))
+
+    def validation_latents(self, transformer, prompt_embeds: torch.Tensor, negative_prompt_embeds: Optional[torch.Tensor], num_frames: int, height: int, width: int,
+                           num_inference_steps: int = 50, guidance_scale: float = 5.0, generator: Optional[torch.Generator] = None, scheduler_config=None,
+                           **sample_kwargs) -> torch.Tensor:
+        """The denoising loop of ``validation`` (base_specification.py:495-529 runs a pipeline) over this backend's transformer, in latent space:
+        ``MI355XWanLatentSampler.sample`` on the LATENT grid -> denormalised latents [B, C, F, H, W] bf16 for the reference pipeline's VAE decode.
+        ``sample_kwargs``: ``latents_mean`` / ``latents_std`` (the VAE's statistics themselves), ``image_embeds`` / ``condition_latents`` for an
+        image-to-video model, ``sigmas`` / ``timesteps`` / ``latents``."""
+        from .sampler import MI355XWanLatentSampler
+
+        return MI355XWanLatentSampler(transformer, scheduler_config).sample(prompt_embeds, negative_prompt_embeds, num_frames, height, width,
+                                                                            num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
+                                                                            generator=generator, **sample_kwargs)
 
     def _save_model(self, directory: str, transformer, transformer_state_dict: Optional[Dict[str, torch.Tensor]] = None, scheduler=None) -> None:
         """base_specification.py:554-568: ``<directory>/transformer`` = config.json + diffusion_pytorch_model.safetensors with the diffusers parameter

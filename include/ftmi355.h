@@ -832,6 +832,74 @@ int ftmi_wan_patch_lora_forward(const ftmi_wan_patch_lora_config* cfg, const voi
 int ftmi_wan_patch_lora_backward(const ftmi_wan_patch_lora_config* cfg, const float* a_f32, const float* b_f32, const void* cols2, const void* dx0, float* g_ws,
                                  float* grad_a, float* grad_b, ftmi_stream stream);
 
+/* ---- Wan latent sampling (csrc/wan_sample.hip, csrc/wan_sample_dit.hip; DESIGN.md "Wan latent sampling") ----
+ * The denoising loop of the reference's validation (finetrainers/models/wan/base_specification.py:495-529, control_specification.py:310-377 run a pipeline over
+ * the transformer that is being trained) in latent space.  The sampler state lives in the patch embedding's operand layout:
+ *   x     fp32 [B, S, Kc]      Kc = C pt ph pw columns in (c, pt, ph, pw) order, S tokens in (f, h, w) order
+ *   cols  bf16 [P B S, ld]     the patch-embedding GEMM's operand, ld = copies Kp; columns [0, Kc) of every copy are bf16(x), the others are constant over the loop
+ *                              (extra channels, then +0 padding); copies = 2: [cols | cols] as ftmi_wan_control_pack writes it (folded patch adapter);
+ *                              P = 2 row groups with guidance (unconditional rows first), 1 without
+ *   pred  bf16 [P B, S, po]    as proj_out writes it: po = Kc columns in (pt, ph, pw, c) order
+ * FTMI_ERR_UNSUPPORTED: Kc % 8, ld % 8, 2048 % Kc, a latent size that is not whole patches; FTMI_ERR_INVALID: Kc != po, misaligned tensors (16 bytes). */
+typedef struct ftmi_wan_sample_geometry {
+    int B, C, Cx;   /* samples, latent channels, extra input channels (I2V: 4 mask + 16 condition; control: 16; 0: none) */
+    int F, H, W;    /* latent grid */
+    int pt, ph, pw; /* patch size */
+    int Kp;         /* stored patch width of one copy: >= (C + Cx) pt ph pw */
+    int copies;     /* 1, or 2 for [cols | cols] */
+    int P;          /* row groups of cols / pred: 2 with guidance, 1 without */
+    int po;         /* width of proj_out */
+} ftmi_wan_sample_geometry;
+/* latents fp32 [B, C, F, H, W], extra bf16 [B, Cx, F, H, W] (NULL when Cx == 0) -> x (the patchified values, exact) and all P row groups and copies of cols. */
+int ftmi_wan_sample_init(const ftmi_wan_sample_geometry* geo, const float* latents, const void* extra, float* x, void* cols, ftmi_stream stream);
+/* One step: v = fma(g, c - u, u) (guidance == 1: v = c, pred has no unconditional half), x <- fma(sigma_next[b] - sigma[b], v, x) in fp32, bf16(x) into columns
+ * [0, Kc) of every row group and copy of cols.  sigma / sigma_next: device fp32 [B].  pred == NULL: only the copies; cols == NULL: only the update. */
+int ftmi_wan_sample_step(const ftmi_wan_sample_geometry* geo, const void* pred, float* x, const float* sigma, const float* sigma_next, float guidance, void* cols,
+                         ftmi_stream stream);
+/* latents bf16 [B, C, F, H, W] = bf16(x * std[c] + mean[c]); std is the VAE's standard deviation itself, NOT the 1 / std the training processors hand over. */
+int ftmi_wan_sample_finish(const ftmi_wan_sample_geometry* geo, const float* x, const float* mean, const float* std_, void* latents, ftmi_stream stream);
+/* mod fp32 [L, rows, 6, D] = float(tables[l]) + float(tproj): the modulation of all L <= 40 blocks for one step.  tables: HOST array of L device pointers to the
+ * blocks' scale_shift_table (bf16 [6 D]); tproj bf16 [6 D]. */
+int ftmi_wan_sample_mod(const void* const* tables, int L, const void* tproj, float* mod, int rows, int D, ftmi_stream stream);
+
+/* The whole denoising loop as ONE call, no host synchronisation.  Per step: ftmi_wan_sample_mod; the patch-embedding NT GEMM over cols (patch_fold: the
+ * ftmi_wan_patch_lora_forward launch, refolding at step 0 only); L block forwards through ftmi_wan_lora_ffn_block_forward at batch P B (TI = 0: text-to-video, r = 0: no
+ * adapters), all blocks sharing ONE `saved` slot and one scratch area, activations alternating between two [P B S, D] buffers; ftmi_wan_ln_fwd with the step's
+ * head shift / scale and the proj_out NT GEMM; ftmi_wan_sample_step.  Bit-identical to that composition issued call by call.
+ * The caller supplies what does not depend on the state: tproj bf16 [steps, 6 D], head_shift / head_scale fp32 [steps, D], enc bf16 [P B, T, D] (unconditional
+ * rows first), enc_img bf16 [P B, TI, D], the rotary tables fp32 [S, 64], sigmas fp32 [steps + 1] on the device.  The rows of one step share one timestep.
+ * x / cols: in and out (ftmi_wan_sample_init wrote them; on return x is the final state and cols its bf16 copies).
+ * Workspace: ftmi_wan_sample_workspace_bytes (0 for a refused configuration; it does not depend on L); a smaller one is FTMI_ERR_INVALID. */
+typedef struct ftmi_wan_sample_config {
+    ftmi_wan_sample_geometry geo;
+    int T, TI;          /* text tokens, image tokens (0: none) */
+    int D, heads, ffn_dim;
+    int L;              /* blocks, 1 .. 40 */
+    float eps;          /* 1e-6 */
+    int gemm_variant;   /* 8 */
+    int r;              /* LoRA rank of the block adapters: 0, 64 or 128 */
+    float lora_scale;
+    int ffn;            /* 1: adapters on ffn.net.0.proj and ffn.net.2 as well */
+    int patch_fold;     /* 1: folded full-rank patch adapter (geo.copies must be 2) */
+    int patch_r;        /* its rank */
+    float patch_scale;
+    int steps;
+    float guidance;     /* != 1 needs geo.P == 2 */
+} ftmi_wan_sample_config;
+typedef struct ftmi_wan_sample_weights {
+    const ftmi_wan_lora_ffn_block_weights* blocks; /* HOST array [L] */
+    const void* const* img_params;                 /* HOST array [L] of the blocks' image-context buffers; NULL when TI == 0 */
+    const void *patch_w, *patch_b;                 /* bf16 [D, Kp], [D] */
+    const void *proj_w, *proj_b;                   /* bf16 [po, D], [po] */
+    const float *patch_lora_a, *patch_lora_b;      /* patch_fold: fp32 [patch_r, Kp], [D, patch_r] */
+    float* patch_dw;                               /* patch_fold: fp32 [D, Kp], written at step 0 */
+    void* patch_w2;                                /* patch_fold: bf16 [D, 2 Kp], written at step 0 */
+} ftmi_wan_sample_weights;
+size_t ftmi_wan_sample_workspace_bytes(const ftmi_wan_sample_config* cfg);
+int ftmi_wan_sample(const ftmi_wan_sample_config* cfg, const ftmi_wan_sample_weights* w, void* cols, float* x, const void* tproj, const float* head_shift,
+                    const float* head_scale, const void* enc, const void* enc_img, const float* rope_cos, const float* rope_sin, const float* sigmas,
+                    void* workspace, size_t workspace_bytes, ftmi_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

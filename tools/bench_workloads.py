@@ -1,5 +1,5 @@
 """The workloads `bench.py --workload {ltx,cogvideox,wan,hunyuan}` can time (BASELINE.json configs[1], [2], [3], [4]), plus the Wan LoRA recipe
-(`wan_lora`) and control recipe (`wan_control_lora`), run through this file's own command line (`python tools/bench_workloads.py --workload wan_lora`): for each one a
+(`wan_lora`), control recipe (`wan_control_lora`) and latent sampling (`wan_sample`), run through this file's own command line (`python tools/bench_workloads.py --workload wan_lora`): for each one a
 builder that puts a random-init model of the named architecture, its step object and one synthetic batch of the named clip shape on the GPU
 and returns the step closure + the static part of the JSON line, and a `cpu_baseline` that times the oracle (CPU restatement of the reference
 path, kind "port") on a bounded sample of the same workload.  Bench infrastructure: the only place outside tests/ and __graft_entry__.smoke()
@@ -464,11 +464,124 @@ def cpu_baseline_hunyuan(args, ctx) -> Dict[str, Any]:
                       f"blocks priced at {dual / single:.2f} x a single block (their algorithmic FLOP ratio) = {per_step:.0f} s per sample-step"}
 
 
+# ------------------------------------------------------------------------------------------------------------------------------------------
+# Wan2.1-T2V-1.3B validation sampling in latent space (finetrainers_amd/wan/sampler.py): 49 x 480 x 832 -> latents 13 x 60 x 104 = 20 280 tokens, unconditional +
+# conditional rows (guidance 5), random weights with rank-`--rank` adapters.  One "step" of this workload is one ftmi_wan_sample call of `SAMPLE_STEPS`
+# denoising steps; the report adds the same loop composed in Python (model.forward + ops.wan_sample_step) and the step kernel on its own.
+# ------------------------------------------------------------------------------------------------------------------------------------------
+SAMPLE_STEPS = 4
+
+
+def build_wan_sample(args, par, dev) -> Dict[str, Any]:
+    from finetrainers_amd import ops
+    from finetrainers_amd.wan import MI355XWanLatentSampler, MI355XWanTransformer3DModel, WanTransformerConfig
+
+    layers = args.layers if args.layers > 0 else 30
+    cfg = WanTransformerConfig(num_layers=layers)
+    model = MI355XWanTransformer3DModel(cfg, device=dev)
+    g = torch.Generator(device=dev).manual_seed(0)
+    D = cfg.inner_dim
+    with torch.no_grad():
+        for name, v in model.state_dict_views().items():
+            if name.endswith("weight") and v.dim() >= 2:
+                v.copy_((torch.randn(v.shape, generator=g, device=dev) / v.shape[-1] ** 0.5).to(bf16))
+            elif "norm" in name and name.endswith("weight"):
+                v.fill_(1.0)
+            elif "scale_shift_table" in name:
+                v.copy_((torch.randn(v.shape, generator=g, device=dev) / D ** 0.5).to(bf16))
+            else:
+                v.copy_((0.02 * torch.randn(v.shape, generator=g, device=dev)).to(bf16))
+    for blk in model.blocks:
+        blk.mark_updated()
+    model.add_adapter(args.rank, float(args.rank))
+    with torch.no_grad():
+        for blk in model.blocks:
+            blk.lora_B[:, :, :args.rank].normal_(0, 0.01, generator=g)
+    B, C, F_, H, W, T, guidance, n = 1, 16, 13, 60, 104, 512, 5.0, SAMPLE_STEPS
+    S = F_ * (H // 2) * (W // 2)
+    sampler = MI355XWanLatentSampler(model)
+    pos, neg = (torch.randn((B, T, cfg.text_dim), generator=g, device=dev).to(bf16) for _ in range(2))
+    latents = torch.randn((B, C, F_, H, W), generator=g, device=dev)
+    sig, ts = sampler.schedule(n, None, None)
+    geo = sampler.geometry(B, F_, H, W, guidance=True)
+    enc = sampler.text_rows(pos, neg)
+    tproj, shift, scale = sampler.step_tables(ts, 2 * B)
+    ccfg, weights, keep = sampler.c_arguments(geo, T, 0, n, guidance)
+    ws_bytes = ops.wan_sample_workspace_bytes(ccfg)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    rope, sig_dev = model._rope(F_, H, W), sig.to(dev)
+
+    def one_call():
+        x, cols = ops.wan_sample_init(geo, latents)
+        ops.wan_sample(ccfg, weights, cols, x, tproj, shift, scale, enc, None, rope, sig_dev, workspace=ws)
+        return None
+
+    def timed(fn, reps):
+        ms = []
+        for _ in range(reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ms.append((time.perf_counter() - t0) * 1e3)
+        return sorted(ms)[len(ms) // 2]
+
+    @torch.no_grad()
+    def composed():
+        x, cols = ops.wan_sample_init(geo, latents)
+        text = torch.cat([neg, pos])
+        for i in range(n):
+            t = torch.full((2 * B,), float(ts[i]), dtype=torch.float32, device=dev)
+            hidden = cols.view(2 * B, F_, H // 2, W // 2, C, 1, 2, 2).permute(0, 4, 1, 5, 2, 6, 3, 7).reshape(2 * B, C, F_, H, W)
+            out = model(hidden, t, text)[0]
+            pred = out.reshape(2 * B, C, F_, 1, H // 2, 2, W // 2, 2).permute(0, 2, 4, 6, 3, 5, 7, 1).reshape(2 * B, S, 4 * C).contiguous()
+            ops.wan_sample_step(geo, pred, x, sig_dev[i:i + 1].expand(B).contiguous(), sig_dev[i + 1:i + 2].expand(B).contiguous(), guidance, cols)
+
+    def report(one_call_ms: float) -> Dict[str, Any]:
+        peak_one = torch.cuda.max_memory_allocated() / 1e9
+        torch.cuda.reset_peak_memory_stats()
+        composed()  # warm
+        comp_ms = timed(composed, 3)
+        peak_comp = torch.cuda.max_memory_allocated() / 1e9
+        x, cols = ops.wan_sample_init(geo, latents)
+        pred = torch.randn((2 * B, S, 4 * C), generator=g, device=dev).to(bf16)
+        s0, s1 = sig_dev[0:1].contiguous(), sig_dev[1:2].contiguous()
+        reps = 50
+        for _ in range(5):
+            ops.wan_sample_step(geo, pred, x, s0, s1, guidance, cols)
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps):
+            ops.wan_sample_step(geo, pred, x, s0, s1, guidance, cols)
+        b.record()
+        torch.cuda.synchronize()
+        us = a.elapsed_time(b) * 1e3 / reps
+        nbytes = B * S * 4 * C * 16  # per element of x: read u 2 + c 2 + x 4, write x 4 + 2 x 2
+        return {"ms_per_denoising_step_one_call": one_call_ms / n, "ms_per_denoising_step_python_composition": comp_ms / n,
+                "peak_memory_gb_one_call": peak_one, "peak_memory_gb_python_composition": peak_comp, "workspace_gb": ws_bytes / 1e9,
+                "step_kernel_us": us, "step_kernel_bytes": nbytes, "step_kernel_gbps": nbytes / (us * 1e-6) / 1e9}
+
+    lin = 2.0 * 2 * S * (6 * D * D + 2 * D * cfg.ffn_dim) + 2.0 * 2 * T * 2 * D * D
+    att = 4.0 * 2 * S * S * D + 4.0 * 2 * S * T * D
+    return {
+        "one_step": one_call,
+        "report": report,
+        "samples_per_step": 1.0 / n,
+        "step_tflop": n * layers * (lin + att) / 1e12,
+        "metric": f"ftmi_wan_sample: one call of {n} denoising steps, Wan-T2V-1.3B 49x480x832, guidance 5 (value: denoising steps per ms are in the report)",
+        "data": "random noise [1,16,13,60,104] + random text embeds [1,512,4096] (conditional and unconditional), random-init weights of the Wan2.1-T2V-1.3B DiT",
+        "config": {"workload": f"Wan-T2V-1.3B latent sampling, rank={args.rank} adapters, {S} video + {T} text tokens, 2 model rows (unconditional + conditional), {layers} blocks"
+                               + ("" if layers == 30 else " -- REDUCED depth"), "seq_len": S, "denoising_steps_per_call": n},
+        "layers": layers,
+    }
+
+
 WORKLOADS = {"cogvideox": (build_cogvideox, lambda a, c: cpu_baseline_cogvideox(a, c["layers"])),
              "wan": (build_wan, lambda a, c: cpu_baseline_wan(a, c["layers"])),
              "wan_lora": (build_wan_lora, lambda a, c: cpu_baseline_wan(a, c["layers"])),  # (yardstick on the host: the full fine-tune block, an upper bound of the LoRA block's work)
              "wan_control_lora": (build_wan_control_lora, None),  # (no host yardstick; run with --rank 128: the recipe's rank)
              "wan_i2v_lora": (build_wan_i2v_lora, None),  # (no host yardstick: this row runs through this file's own command line only)
+             "wan_sample": (build_wan_sample, None),  # (validation sampling: forward only; this file's own command line only)
              "hunyuan": (build_hunyuan, cpu_baseline_hunyuan)}
 
 
@@ -504,9 +617,10 @@ def main() -> None:
     timed = sorted(ms[args.warmup:])
     med = timed[len(timed) // 2]
     ctx.pop("dual_single", None)
+    report = ctx.pop("report", None)  # a forward-only workload (wan_sample) reports its own figures instead of loss and gradient norm
     ctx.update(step_ms=med, steps_ms=ms, value=ctx["samples_per_step"] / (med / 1e3), unit="samples/s", achieved_tflops=ctx["step_tflop"] / (med / 1e3),
-               peak_memory_gb=torch.cuda.max_memory_allocated() / 1e9, loss=float(out["loss"]), grad_norm=float(out["grad_norm"]), gpus=1, steps=args.steps,
-               warmup=args.warmup)
+               peak_memory_gb=torch.cuda.max_memory_allocated() / 1e9, gpus=1, steps=args.steps, warmup=args.warmup)
+    ctx.update(report(med) if report else dict(loss=float(out["loss"]), grad_norm=float(out["grad_norm"])))
     print(json.dumps(ctx))
 
 
