@@ -262,6 +262,13 @@ _SIGS = {
     "ftmi_qknorm_rope_fwd": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_float, c_void_p]),
     "ftmi_qknorm_rope_bwd": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_int, c_float,
                                      c_void_p]),
+    "ftmi_norm_modulate_fwd_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p]),
+    "ftmi_norm_modulate_bwd_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_long,
+                                          c_void_p, c_int, c_void_p]),
+    "ftmi_qknorm_rope_fwd_ex": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p,
+                                        c_void_p, c_int, c_void_p]),
+    "ftmi_qknorm_rope_bwd_ex": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_int, c_float, c_int,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "ftmi_ltx_workspace_bytes": (c_size_t, [POINTER(LtxConfig)]),
     "ftmi_ltx_workspace_offset": (c_int, [POINTER(LtxConfig), c_char_p, c_int, POINTER(c_size_t)]),
     "ftmi_ltx_forward": (c_int, [POINTER(LtxConfig), POINTER(LtxWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -436,6 +436,56 @@ int ftmi_qknorm_rope_bwd(const void* x, long ldx, const void* w, const float* co
                            (hipStream_t)stream);
 }
 
+// The full argument lists of the four launchers above (w_rows, the q / k pair launch, row groups, gate2 / dx2) and the valid width of zero-padded rows, which the
+// DiT pass sets around its launches: here it is set around the one launch and reset.
+namespace {
+struct ValidWidthScope {
+    explicit ValidWidthScope(int dv) { rowwise_set_valid_width(dv); }
+    ~ValidWidthScope() { rowwise_set_valid_width(0); }
+};
+}  // namespace
+
+int ftmi_norm_modulate_fwd_ex(const void* x, const void* shift, const void* onep, long mod_bstride, void* y, int rows, int rows_per_batch, int D, float eps,
+                              int layernorm, int valid_width, ftmi_stream stream) {
+    if (!x || !shift || !onep || !y || rows < 0 || rows_per_batch <= 0 || valid_width < 0 || valid_width > D)
+        return set_error(FTMI_ERR_INVALID, "ftmi_norm_modulate_fwd_ex: bad argument");
+    ValidWidthScope scope(valid_width);
+    return norm_modulate_fwd((const bf16_t*)x, (const bf16_t*)shift, (const bf16_t*)onep, mod_bstride, (bf16_t*)y, rows, rows_per_batch, D, eps, layernorm,
+                             (hipStream_t)stream);
+}
+
+int ftmi_norm_modulate_bwd_ex(const void* x, const void* dy, const void* onep, long mod_bstride, const void* dres, void* dx, int rows, int rows_per_batch, int D,
+                              float eps, int layernorm, const void* gate2, long gate2_bstride, void* dx2, int valid_width, ftmi_stream stream) {
+    if (!x || !dy || !onep || !dx || rows < 0 || rows_per_batch <= 0 || (gate2 == nullptr) != (dx2 == nullptr) || valid_width < 0 || valid_width > D)
+        return set_error(FTMI_ERR_INVALID, "ftmi_norm_modulate_bwd_ex: bad argument");
+    ValidWidthScope scope(valid_width);
+    return norm_modulate_bwd((const bf16_t*)x, (const bf16_t*)dy, (const bf16_t*)onep, mod_bstride, (const bf16_t*)dres, (bf16_t*)dx, rows, rows_per_batch, D,
+                             eps, layernorm, (hipStream_t)stream, (const bf16_t*)gate2, gate2_bstride, (bf16_t*)dx2);
+}
+
+int ftmi_qknorm_rope_fwd_ex(const void* x, long ldx, const void* w, const float* cos_t, const float* sin_t, void* y, long ldy, int rows, int rows_per_batch, int D,
+                            float eps, int w_rows, const void* x2, const void* w2, void* y2, int valid_width, ftmi_stream stream) {
+    const bool pair = x2 || w2 || y2;
+    if (!x || !w || !y || rows < 0 || rows_per_batch <= 0 || (!cos_t) != (!sin_t) || w_rows < 1 || (pair && (!x2 || !w2 || !y2)) || ldx < D || ldy < D ||
+        valid_width < 0 || valid_width > D)
+        return set_error(FTMI_ERR_INVALID, "ftmi_qknorm_rope_fwd_ex: bad argument");
+    ValidWidthScope scope(valid_width);
+    return qknorm_rope_fwd((const bf16_t*)x, ldx, (const bf16_t*)w, cos_t, sin_t, (bf16_t*)y, ldy, rows, rows_per_batch, D, eps, (hipStream_t)stream, w_rows,
+                           (const bf16_t*)x2, (const bf16_t*)w2, (bf16_t*)y2);
+}
+
+int ftmi_qknorm_rope_bwd_ex(const void* x, long ldx, const void* w, const float* cos_t, const float* sin_t, const void* dy, long lddy, void* dx, long lddx, int rows,
+                            int rows_per_batch, int D, float eps, int w_rows, const void* x2, const void* w2, const void* dy2, void* dx2, int row_grp,
+                            int row_grp_span, int valid_width, ftmi_stream stream) {
+    const bool pair = x2 || w2 || dy2 || dx2;
+    if (!x || !w || !dy || !dx || rows < 0 || rows_per_batch <= 0 || (!cos_t) != (!sin_t) || w_rows < 1 || (pair && (!x2 || !w2 || !dy2 || !dx2)) || ldx < D ||
+        lddy < D || lddx < D || row_grp < 0 || (row_grp > 0 && row_grp_span < row_grp) || valid_width < 0 || valid_width > D)
+        return set_error(FTMI_ERR_INVALID, "ftmi_qknorm_rope_bwd_ex: bad argument");
+    ValidWidthScope scope(valid_width);
+    return qknorm_rope_bwd((const bf16_t*)x, ldx, (const bf16_t*)w, cos_t, sin_t, (const bf16_t*)dy, lddy, (bf16_t*)dx, lddx, rows, rows_per_batch, D, eps,
+                           (hipStream_t)stream, w_rows, (const bf16_t*)x2, (const bf16_t*)w2, (const bf16_t*)dy2, (bf16_t*)dx2, row_grp, row_grp_span);
+}
+
 size_t ftmi_ltx_workspace_bytes(const ftmi_ltx_config* cfg) { return cfg ? ltx_workspace_bytes(*cfg) : 0; }
 
 int ftmi_ltx_workspace_offset(const ftmi_ltx_config* cfg, const char* name, int layer, size_t* offset) {
@@ -589,7 +639,7 @@ int ftmi_cog_head_ln_bwd(const void* x, long ld, const void* w, const void* dy, 
 
 int ftmi_head_rms_rope_fwd(const void* x, long ld, const void* w, void* y, long ld_y, int rows, int D, int head_dim, float eps, const float* rope_cos,
                            const float* rope_sin, int rows_per_batch, int rope_from, ftmi_stream stream) {
-    if (!x || !w || !y || ld < D || (ld % 8) || (ld_y % 8) || (rope_cos == nullptr) != (rope_sin == nullptr))
+    if (!x || !w || !y || ld < D || ld_y < D || (ld % 8) || (ld_y % 8) || (rope_cos == nullptr) != (rope_sin == nullptr))
         return set_error(FTMI_ERR_INVALID, "ftmi_head_rms_rope_fwd: bad argument");
     CogLnArgs a;
     a.x = (const bf16_t*)x; a.w = (const bf16_t*)w; a.y = (bf16_t*)y; a.rows = rows; a.D = D; a.ld = ld; a.ld_out = ld_y; a.eps = eps; a.head_dim = head_dim; a.rms = 1;
@@ -600,7 +650,7 @@ int ftmi_head_rms_rope_fwd(const void* x, long ld, const void* w, void* y, long 
 
 int ftmi_head_rms_rope_bwd(const void* x, long ld, const void* w, const void* dy, long ld_dy, void* dx, long ld_dx, int rows, int D, int head_dim, float eps,
                            const float* rope_cos, const float* rope_sin, int rows_per_batch, int rope_from, ftmi_stream stream) {
-    if (!x || !w || !dy || !dx || ld < D || (ld % 8) || (ld_dy % 8) || (ld_dx % 8) || (rope_cos == nullptr) != (rope_sin == nullptr))
+    if (!x || !w || !dy || !dx || ld < D || ld_dy < D || ld_dx < D || (ld % 8) || (ld_dy % 8) || (ld_dx % 8) || (rope_cos == nullptr) != (rope_sin == nullptr))
         return set_error(FTMI_ERR_INVALID, "ftmi_head_rms_rope_bwd: bad argument");
     CogLnArgs a;
     a.x = (const bf16_t*)x; a.w = (const bf16_t*)w; a.dy = (const bf16_t*)dy; a.dx = (bf16_t*)dx; a.rows = rows; a.D = D; a.ld = ld; a.ld_dy = ld_dy; a.ld_out = ld_dx;

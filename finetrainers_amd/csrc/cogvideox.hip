@@ -291,6 +291,11 @@ int check_args(const CogLnArgs& a, const char* who) {
     (void)who;
     return 0;
 }
+// a row of the head norms is whole heads: a last head of fewer channels would be normalised over head_dim with the missing lanes read as zeros
+int check_heads(const CogLnArgs& a) {
+    if (a.head_dim > 0 && a.D % a.head_dim != 0) return set_error(FTMI_ERR_UNSUPPORTED, "head norm: the row width must be a multiple of head_dim");
+    return 0;
+}
 
 // ---- modulation tables of all blocks: mod [B][L2][6][D] = linear(silu(temb)) of every LayerNorm-zero (L2 = 2 per block), chunks (shift, scale, gate,
 // enc_shift, enc_scale, enc_gate)  ->  tables [L2][3][B][2][D]: (shift, bf(1 + scale), gate) x (text row, video row) ---------------------------------
@@ -375,6 +380,7 @@ int cog_ln_mod_bwd(const CogLnArgs& a, hipStream_t st) {
 int cog_head_ln_fwd(const CogLnArgs& a, hipStream_t st) {
     if (int rc = check_args(a, "head_ln_fwd")) return rc;
     if (a.rows <= 0) return 0;
+    if (int rc = check_heads(a)) return rc;
     const dim3 grid((a.rows + 3) / 4);
 #define COMMA_FALSE , false
 #define COMMA_FALSE_RMS128 , false, 128, true
@@ -390,6 +396,7 @@ int cog_head_ln_fwd(const CogLnArgs& a, hipStream_t st) {
 int cog_head_ln_bwd(const CogLnArgs& a, hipStream_t st) {
     if (int rc = check_args(a, "head_ln_bwd")) return rc;
     if (a.rows <= 0) return 0;
+    if (int rc = check_heads(a)) return rc;
     const dim3 grid((a.rows + 3) / 4);
 #define COMMA_TRUE , true
 #define COMMA_TRUE_RMS128 , true, 128, true

@@ -112,11 +112,9 @@ __global__ __launch_bounds__(256) void norm_modulate_fwd_kernel(const bf16_t* __
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 float c = xv[it][e] - mean;
-                v += c * c;
+                if ((lane + 64 * it) * 8 + e < Dv) v += c * c;  // the padded zeros are not part of the row (taking their mean^2 out of the full sum afterwards cancels)
             }
-        v = wave_sum(v);
-        if (Dv < D) v -= (float)(D - Dv) * mean * mean;  // the padded zeros are not part of the row
-        rstd = rsqrtf(v * invD + eps);
+        rstd = rsqrtf(wave_sum(v) * invD + eps);
     } else {
         rstd = rsqrtf(wave_sum(s2) * invD + eps);
     }
@@ -141,6 +139,7 @@ __global__ __launch_bounds__(256) void norm_modulate_fwd_kernel(const bf16_t* __
 int norm_modulate_fwd(const bf16_t* x, const bf16_t* shift, const bf16_t* onep, long mod_bstride, bf16_t* y, int rows,
                       int rows_per_batch, int D, float eps, int layernorm, hipStream_t st) {
     if (D != kNch * 512) return set_error(FTMI_ERR_UNSUPPORTED, "norm_modulate: row width must be 2048");
+    if (rows <= 0) return 0;  // (an empty range: nothing to launch, like the Wan and CogVideoX launchers)
     dim3 grid((rows + 3) / 4);
     if (layernorm)
         hipLaunchKernelGGL(norm_modulate_fwd_kernel<true>, grid, dim3(256), 0, st, x, shift, onep, mod_bstride, y, rows, rows_per_batch, eps, valid_width(D));
@@ -189,11 +188,9 @@ __global__ __launch_bounds__(256) void norm_modulate_bwd_kernel(const bf16_t* __
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 float c = xv[it][e] - mean;
-                v += c * c;
+                if ((lane + 64 * it) * 8 + e < Dv) v += c * c;
             }
-        v = wave_sum(v);
-        if (Dv < D) v -= (float)(D - Dv) * mean * mean;
-        rstd = rsqrtf(v * invD + eps);
+        rstd = rsqrtf(wave_sum(v) * invD + eps);
     } else {
         rstd = rsqrtf(wave_sum(s2) * invD + eps);
     }
@@ -237,6 +234,7 @@ int norm_modulate_bwd(const bf16_t* x, const bf16_t* dy, const bf16_t* onep, lon
                       int rows, int rows_per_batch, int D, float eps, int layernorm, hipStream_t st, const bf16_t* gate2, long gate2_bstride,
                       bf16_t* dx2) {
     if (D != kNch * 512) return set_error(FTMI_ERR_UNSUPPORTED, "norm_modulate: row width must be 2048");
+    if (rows <= 0) return 0;  // (an empty range: nothing to launch, like the Wan and CogVideoX launchers)
     dim3 grid((rows + 3) / 4);
     if (layernorm)
         hipLaunchKernelGGL(norm_modulate_bwd_kernel<true>, grid, dim3(256), 0, st, x, dy, onep, mod_bstride, dres, dx, rows, rows_per_batch, eps, gate2, gate2_bstride, dx2, valid_width(D));
@@ -296,6 +294,7 @@ int qknorm_rope_fwd(const bf16_t* x, long ldx, const bf16_t* w, const float* cos
                     int rows, int rows_per_batch, int D, float eps, hipStream_t st, int w_rows, const bf16_t* x2, const bf16_t* w2, bf16_t* y2) {
     if (D != kNch * 512) return set_error(FTMI_ERR_UNSUPPORTED, "qknorm_rope: row width must be 2048");
     if ((ldx % 8) || (ldy % 8)) return set_error(FTMI_ERR_INVALID, "qknorm_rope: row strides must keep 16-byte alignment");
+    if (rows <= 0) return 0;
     hipLaunchKernelGGL(qknorm_rope_fwd_kernel, dim3((rows + 3) / 4, x2 ? 2 : 1), dim3(256), 0, st, x, ldx, w, cos_t, sin_t, y, ldy, rows, rows_per_batch, eps, w_rows,
                        x2, w2, y2, valid_width(D));
     return check_launch("qknorm_rope_fwd");
@@ -370,6 +369,7 @@ int qknorm_rope_bwd(const bf16_t* x, long ldx, const bf16_t* w, const float* cos
                     const bf16_t* dy2, bf16_t* dx2, int row_grp, int row_grp_span) {
     if (D != kNch * 512) return set_error(FTMI_ERR_UNSUPPORTED, "qknorm_rope: row width must be 2048");
     if ((ldx % 8) || (lddy % 8) || (lddx % 8)) return set_error(FTMI_ERR_INVALID, "qknorm_rope: row strides must keep 16-byte alignment");
+    if (rows <= 0) return 0;
     hipLaunchKernelGGL(qknorm_rope_bwd_kernel, dim3((rows + 3) / 4, x2 ? 2 : 1), dim3(256), 0, st, x, ldx, w, cos_t, sin_t, dy, lddy, dx, lddx, rows, rows_per_batch, eps, w_rows,
                        x2, w2, dy2, dx2, row_grp, row_grp_span, valid_width(D));
     return check_launch("qknorm_rope_bwd");

@@ -322,6 +322,51 @@ def qknorm_rope_bwd(x, w, dy, cos=None, sin=None, rows_per_batch: Optional[int] 
     return dx
 
 
+def norm_modulate_ex(x, shift, onep, y, rows_per_batch: int, eps: float = 1e-6, layernorm: bool = False, valid_width: int = 0):
+    """ftmi_norm_modulate_fwd_ex: norm_modulate into ``y`` with the valid width of zero-padded rows; x / y contiguous [rows, 2048], shift / onep [B, 2048] views
+    sharing one sample stride."""
+    rows, D = x.shape
+    check(_lib.load().ftmi_norm_modulate_fwd_ex(ptr(x), ptr(shift), ptr(onep), onep.stride(0), ptr(y), rows, int(rows_per_batch), D, float(eps), int(layernorm),
+                                                 int(valid_width), stream_ptr()), "ftmi_norm_modulate_fwd_ex")
+    return y
+
+
+def norm_modulate_bwd_ex(x, dy, onep, dx, rows_per_batch: int, eps: float = 1e-6, layernorm: bool = False, dres=None, gate2=None, dx2=None, valid_width: int = 0):
+    """ftmi_norm_modulate_bwd_ex: norm_modulate_bwd into ``dx`` and, with ``gate2`` ([B, 2048] view) and ``dx2``, dx2 = bf(bf(dx) * gate2[b])."""
+    rows, D = x.shape
+    check(_lib.load().ftmi_norm_modulate_bwd_ex(ptr(x), ptr(dy), ptr(onep), onep.stride(0), ptr(dres), ptr(dx), rows, int(rows_per_batch), D, float(eps),
+                                                 int(layernorm), ptr(gate2), gate2.stride(0) if gate2 is not None else 0, ptr(dx2), int(valid_width),
+                                                 stream_ptr()), "ftmi_norm_modulate_bwd_ex")
+    return dx
+
+
+def qknorm_rope_ex(x, w, y, cos=None, sin=None, rows_per_batch: Optional[int] = None, eps: float = 1e-5, w_rows: int = 1, pair=None, valid_width: int = 0):
+    """ftmi_qknorm_rope_fwd_ex: x / y [rows, 2048] views (own row strides), w [w_rows, 2048] contiguous; ``pair = (x2, w2, y2)``: a second tensor set with the
+    strides of the first, same launch."""
+    rows, D = x.shape
+    x2, w2, y2 = pair if pair is not None else (None, None, None)
+    if pair is not None and (x2.stride(0) != x.stride(0) or y2.stride(0) != y.stride(0)):
+        raise ValueError("qknorm_rope_ex: the second tensor set shares the row strides of the first")
+    check(_lib.load().ftmi_qknorm_rope_fwd_ex(ptr(x), x.stride(0), ptr(w), ptr(cos), ptr(sin), ptr(y), y.stride(0), rows, int(rows_per_batch or rows), D,
+                                               float(eps), int(w_rows), ptr(x2), ptr(w2), ptr(y2), int(valid_width), stream_ptr()), "ftmi_qknorm_rope_fwd_ex")
+    return y
+
+
+def qknorm_rope_bwd_ex(x, w, dy, dx, cos=None, sin=None, rows: Optional[int] = None, rows_per_batch: Optional[int] = None, eps: float = 1e-5, w_rows: int = 1,
+                       pair=None, row_grp: int = 0, row_grp_span: int = 0, valid_width: int = 0):
+    """ftmi_qknorm_rope_bwd_ex: ``pair = (x2, w2, dy2, dx2)``; with ``row_grp`` the ``rows`` logical rows sit in groups of row_grp, row_grp_span buffer rows
+    apart (``rows`` must then be given: the buffers hold more rows than are processed)."""
+    rows = x.shape[0] if rows is None else int(rows)
+    D = x.shape[1]
+    x2, w2, dy2, dx2 = pair if pair is not None else (None, None, None, None)
+    if pair is not None and (x2.stride(0) != x.stride(0) or dy2.stride(0) != dy.stride(0) or dx2.stride(0) != dx.stride(0)):
+        raise ValueError("qknorm_rope_bwd_ex: the second tensor set shares the row strides of the first")
+    check(_lib.load().ftmi_qknorm_rope_bwd_ex(ptr(x), x.stride(0), ptr(w), ptr(cos), ptr(sin), ptr(dy), dy.stride(0), ptr(dx), dx.stride(0), rows,
+                                               int(rows_per_batch or rows), D, float(eps), int(w_rows), ptr(x2), ptr(w2), ptr(dy2), ptr(dx2), int(row_grp),
+                                               int(row_grp_span), int(valid_width), stream_ptr()), "ftmi_qknorm_rope_bwd_ex")
+    return dx
+
+
 def noise_pack(latents, noise, mean, std, sigma, sigma_first=None, first_frame_tokens: int = 0):
     """latents/noise [B,C,F,H,W] bf16 -> (x_t, target) [B, F*H*W, C] bf16."""
     B, C = latents.shape[:2]

@@ -268,6 +268,24 @@ int ftmi_qknorm_rope_fwd(const void* x, long ldx, const void* w, const float* co
                          int rows_per_batch, int D, float eps, ftmi_stream stream);
 int ftmi_qknorm_rope_bwd(const void* x, long ldx, const void* w, const float* cos_t, const float* sin_t, const void* dy, long lddy,
                          void* dx, long lddx, int rows, int rows_per_batch, int D, float eps, ftmi_stream stream);
+/* The same four launches with every argument of their launchers (what the DiT pass uses between its GEMMs), so that each can be tested on its own:
+ *  valid_width: the row is a narrower one zero-padded to D -- means are taken over valid_width channels and the padded channels of the LayerNorm form come out
+ *    as exact zeros (0 or D: the whole row).  Set around this one launch and reset.
+ *  gate2 / gate2_bstride / dx2 (norm_modulate_bwd): a second output dx2 = bf16(bf16(dx) * gate2[b]) (both or neither).
+ *  w_rows > 1: row i uses weight row i % w_rows of a [w_rows, D] table.   x2 / w2 / y2 (dy2 / dx2): a second tensor set with the same strides, RoPE rows and
+ *    w_rows, handled by the same launch (q and k of one projection; all or none).
+ *  row_grp > 0 (qknorm_rope_bwd): row i of x / dy / dx sits at row (i / row_grp) * row_grp_span + i % row_grp of its buffer (row_grp_span >= row_grp); the
+ *    RoPE row and the weight row still follow i.
+ * rows = 0 is an empty launch (returns 0). */
+int ftmi_norm_modulate_fwd_ex(const void* x, const void* shift, const void* onep, long mod_bstride, void* y, int rows, int rows_per_batch, int D, float eps,
+                              int layernorm, int valid_width, ftmi_stream stream);
+int ftmi_norm_modulate_bwd_ex(const void* x, const void* dy, const void* onep, long mod_bstride, const void* dres, void* dx, int rows, int rows_per_batch, int D,
+                              float eps, int layernorm, const void* gate2, long gate2_bstride, void* dx2, int valid_width, ftmi_stream stream);
+int ftmi_qknorm_rope_fwd_ex(const void* x, long ldx, const void* w, const float* cos_t, const float* sin_t, void* y, long ldy, int rows, int rows_per_batch, int D,
+                            float eps, int w_rows, const void* x2, const void* w2, void* y2, int valid_width, ftmi_stream stream);
+int ftmi_qknorm_rope_bwd_ex(const void* x, long ldx, const void* w, const float* cos_t, const float* sin_t, const void* dy, long lddy, void* dx, long lddx, int rows,
+                            int rows_per_batch, int D, float eps, int w_rows, const void* x2, const void* w2, const void* dy2, void* dx2, int row_grp,
+                            int row_grp_span, int valid_width, ftmi_stream stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * LTX-Video DiT level
@@ -542,7 +560,8 @@ int ftmi_clip_grad_norm(float* grads, long n, float max_norm, float* scratch, fl
  * RMSNorm over each head's head_dim channels (128; weight [head_dim] bf16, eps 1e-6, the reference's patched F.rms_norm: one bf16 rounding), then -- on
  * the rows at position >= rope_from of a sample of rows_per_batch tokens (the video tokens of a joint [text | video] sequence) -- the rotary embedding
  * in its real form: rope_cos / rope_sin fp32 [rows_per_batch - rope_from, head_dim], every frequency repeated for its channel pair; NULL: none.
- * x / y / dy / dx: [rows, D] bf16 views with their own row strides (multiples of 8).  Only the input gradient is produced (LoRA training). */
+ * x / y / dy / dx: [rows, D] bf16 views with their own row strides (multiples of 8, at least D).  D is a multiple of head_dim (a row is whole heads).
+ * Only the input gradient is produced (LoRA training). */
 int ftmi_head_rms_rope_fwd(const void* x, long ld, const void* w, void* y, long ld_y, int rows, int D, int head_dim, float eps, const float* rope_cos,
                            const float* rope_sin, int rows_per_batch, int rope_from, ftmi_stream stream);
 int ftmi_head_rms_rope_bwd(const void* x, long ld, const void* w, const void* dy, long ld_dy, void* dx, long ld_dx, int rows, int D, int head_dim, float eps,

@@ -35,6 +35,8 @@ def test_c_abi_exports_every_declared_symbol(lib):
     for name in declared:
         assert hasattr(lib, name), f"libftmi355.so does not export {name}"
     assert declared == set(_lib.EXPORTED_SYMBOLS), declared ^ set(_lib.EXPORTED_SYMBOLS)
+    # the full-argument entries of the LTX row-wise launchers (tests/test_gpu_rowwise_contract.py launches through them)
+    assert {"ftmi_norm_modulate_fwd_ex", "ftmi_norm_modulate_bwd_ex", "ftmi_qknorm_rope_fwd_ex", "ftmi_qknorm_rope_bwd_ex"} <= declared
     assert lib.ftmi_version() >= 100
 
 
