@@ -193,6 +193,29 @@ class WanSampleWeights(Structure):
         (n, c_void_p) for n in ("patch_w", "patch_b", "proj_w", "proj_b", "patch_lora_a", "patch_lora_b", "patch_dw", "patch_w2")]
 
 
+class CogSampleGeometry(Structure):
+    """include/ftmi355.h: ftmi_cog_sample_geometry."""
+
+    _fields_ = [(n, c_int) for n in ("B", "C", "F", "H", "W", "p", "pt", "P", "drop")]
+
+
+class CogSampleConfig(Structure):
+    """include/ftmi355.h: ftmi_cog_sample_config."""
+
+    _fields_ = [("geo", CogSampleGeometry), ("T", c_int), ("D_text", c_int), ("D", c_int), ("heads", c_int), ("L", c_int), ("D_ff", c_int), ("D_temb", c_int),
+                ("r", c_int), ("lora_scale", c_float), ("eps_norm", c_float), ("eps_qk", c_float), ("gemm_variant", c_int), ("steps", c_int), ("guidance", c_float)]
+
+
+COG_SAMPLE_WEIGHT_FIELDS = ["patch_w", "patch_b", "text_w", "text_b", "pos", "norm_final_w", "norm_final_b", "norm_out_w", "norm_out_b", "proj_w", "proj_b", "ones",
+                            "zeros"]
+
+
+class CogSampleWeights(Structure):
+    """include/ftmi355.h: ftmi_cog_sample_weights."""
+
+    _fields_ = [("blocks", CogWeights)] + [(n, c_void_p) for n in COG_SAMPLE_WEIGHT_FIELDS]
+
+
 class WanRowArgs(Structure):
     """include/ftmi355.h: ftmi_wan_row_args."""
 
@@ -353,6 +376,11 @@ _SIGS = {
     "ftmi_wan_sample_mod": (c_int, [POINTER(c_void_p), c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "ftmi_wan_sample_workspace_bytes": (c_size_t, [POINTER(WanSampleConfig)]),
     "ftmi_wan_sample": (c_int, [POINTER(WanSampleConfig), POINTER(WanSampleWeights)] + [c_void_p] * 11 + [c_size_t, c_void_p]),
+    "ftmi_cog_sample_init": (c_int, [POINTER(CogSampleGeometry), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ftmi_cog_sample_step": (c_int, [POINTER(CogSampleGeometry), c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p]),
+    "ftmi_cog_sample_finish": (c_int, [POINTER(CogSampleGeometry), c_void_p, c_float, c_void_p, c_void_p]),
+    "ftmi_cog_sample_workspace_bytes": (c_size_t, [POINTER(CogSampleConfig)]),
+    "ftmi_cog_sample": (c_int, [POINTER(CogSampleConfig), POINTER(CogSampleWeights)] + [c_void_p] * 8 + [c_size_t, c_void_p]),
     "ftmi_hy_dual_saved_bytes": (c_size_t, [POINTER(HyDualConfig)]),
     "ftmi_hy_dual_scratch_bytes": (c_size_t, [POINTER(HyDualConfig)]),
     "ftmi_hy_dual_forward": (c_int, [POINTER(HyDualConfig), POINTER(HyDualWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -70,6 +70,7 @@ class MI355XCogVideoXSpecOps:
 
     def __init__(self, scaling_factor: float = 1.15258426, invert_scale_latents: bool = False, scheduler: Optional[CogVideoXDDIMTables] = None):
         self.scaling_factor = 1.0 if invert_scale_latents else scaling_factor
+        self.vae_scaling_factor, self.invert_scale_latents = scaling_factor, invert_scale_latents  # what validation_latents denormalises with
         self.scheduler = scheduler or CogVideoXDDIMTables()
 
     @property
@@ -195,6 +196,25 @@ class MI355XCogVideoXModelSpecification(MI355XCogVideoXSpecOps):
             latents = ops.posterior_sample(mom, posterior_noise.reshape(B * F_, C2 // 2, H, W).to(mom)).view(B, F_, C2 // 2, H, W)
         return MI355XCogVideoXSpecOps.forward(self, transformer, latents, condition_model_conditions["encoder_hidden_states"], sigmas, noise=noise,
                                               generator=generator)
+
+    def validation_latents(self, transformer, prompt_embeds: torch.Tensor, negative_prompt_embeds: Optional[torch.Tensor], num_frames: int, height: int,
+                           width: int, num_inference_steps: int = 50, guidance_scale: float = 6.0, generator: Optional[torch.Generator] = None,
+                           scheduler_config=None, latents: Optional[torch.Tensor] = None, **sample_kwargs) -> torch.Tensor:
+        """The denoising loop of ``validation`` (base_specification.py:335-364 runs ``CogVideoXPipeline``) over this backend's transformer, in latent space:
+        ``MI355XCogVideoXLatentSampler.sample`` on the LATENT grid -> denormalised latents [B, num_frames, C, height, width] bf16 for the reference
+        pipeline's VAE decode.  The noise is ``randn([B, F_pad, C, H, W], fp32, generator)`` on the transformer's device (or ``latents``), ``F_pad`` =
+        ``num_frames`` raised to a multiple of ``patch_size_t``: the pipeline pads at the front and drops those frames after the loop, and so does this."""
+        from .sampler import MI355XCogVideoXLatentSampler
+
+        c = transformer.config
+        pt = c.patch_size_t or 1
+        extra = (pt - num_frames % pt) % pt
+        if latents is None:
+            latents = torch.randn((prompt_embeds.shape[0], num_frames + extra, c.in_channels, height, width), generator=generator, device=transformer.device,
+                                  dtype=torch.float32)
+        return MI355XCogVideoXLatentSampler(transformer, scheduler_config).sample(
+            latents, prompt_embeds, negative_prompt_embeds, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale, drop_frames=extra,
+            scaling_factor=self.vae_scaling_factor, invert_scale_latents=self.invert_scale_latents, **sample_kwargs)
 
     def _save_lora_weights(self, directory: str, transformer_state_dict: Optional[Dict[str, torch.Tensor]] = None, scheduler=None,
                            metadata: Optional[Dict[str, str]] = None, *args, **kwargs) -> None:

@@ -979,4 +979,30 @@ int ftmi_wan_sample(const ftmi_wan_sample_config* cfg, const ftmi_wan_sample_wei
                       workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+int ftmi_cog_sample_init(const ftmi_cog_sample_geometry* geo, const float* latents, float* x, void* cols, ftmi_stream stream) {
+    if (!geo || !latents || !x || !cols) return set_error(FTMI_ERR_INVALID, "ftmi_cog_sample_init: null argument");
+    return cog_sample_init(*geo, latents, x, (bf16_t*)cols, (hipStream_t)stream);
+}
+
+int ftmi_cog_sample_step(const ftmi_cog_sample_geometry* geo, const void* pred, float* x, const float* coef, int step, float guidance, void* cols,
+                         ftmi_stream stream) {
+    if (!geo || !x || (!pred && !cols)) return set_error(FTMI_ERR_INVALID, "ftmi_cog_sample_step: null argument");
+    return cog_sample_step(*geo, (const bf16_t*)pred, x, coef, step, guidance, (bf16_t*)cols, (hipStream_t)stream);
+}
+
+int ftmi_cog_sample_finish(const ftmi_cog_sample_geometry* geo, const float* x, float k, void* latents, ftmi_stream stream) {
+    if (!geo || !x || !latents) return set_error(FTMI_ERR_INVALID, "ftmi_cog_sample_finish: null argument");
+    return cog_sample_finish(*geo, x, k, (bf16_t*)latents, (hipStream_t)stream);
+}
+
+size_t ftmi_cog_sample_workspace_bytes(const ftmi_cog_sample_config* cfg) { return cfg ? cog_sample_workspace_bytes(*cfg) : 0; }
+
+int ftmi_cog_sample(const ftmi_cog_sample_config* cfg, const ftmi_cog_sample_weights* w, void* cols, float* x, const void* text, const void* temb_silu,
+                    const void* head_shift, const void* head_onep, const float* coef, void* workspace, size_t workspace_bytes, ftmi_stream stream) {
+    if (!cfg || !w || !cols || !x || !text || !temb_silu || !head_shift || !head_onep || !coef || !workspace)
+        return set_error(FTMI_ERR_INVALID, "ftmi_cog_sample: null argument");
+    return cog_sample(*cfg, *w, (bf16_t*)cols, x, (const bf16_t*)text, (const bf16_t*)temb_silu, (const bf16_t*)head_shift, (const bf16_t*)head_onep, coef, workspace,
+                      workspace_bytes, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -23,22 +23,23 @@ namespace ftmi {
 
 namespace {
 
-struct CogLayout {
-    size_t total = 0;
+// What the forward walk reads of a workspace plan: the training layout (make_layout: one slot per block, the inputs of blocks 1 .. L-1 kept) and the
+// sampling layout (make_sample_plan: every block writes the SAME slot, blk_stride = 0, and the hidden state alternates between two buffers) share it.
+struct CogFwdLayout {
     size_t mod_raw, tables, hs, blk0, blk_stride;
+    int hs_slots = 1;                                         // block l > 0 reads slot (l - 1) % hs_slots of hs and block l < L - 1 writes slot l % hs_slots
     size_t n1, qkv, qn, kn, o, lse, xa_qkv, xa_o, h1, n2, z;  // per block, forward
+    size_t s_act, s_f;
+};
+struct CogLayout : CogFwdLayout {
+    size_t total = 0;
     size_t g_qkv, g_o, dxa_qkv, dxa_o;                        // per block, backward stash for the batched weight gradients
-    size_t s_act, s_f, s_big, s_d1, s_d2, s_d3, s_dq, s_dk, s_dh0, s_dh1, s_delta;
+    size_t s_big, s_d1, s_d2, s_d3, s_dq, s_dk, s_dh0, s_dh1, s_delta;
 };
 
-CogLayout make_layout(const ftmi_cog_config& c) {
-    CogLayout w;
+// the forward entries of one block's slot, in the order both layouts keep them
+void take_fwd_slot(CogFwdLayout& w, Bump& b, const ftmi_cog_config& c) {
     const size_t N = (size_t)c.T + c.S, M = (size_t)c.B * N, D = c.D, r = c.r > 0 ? c.r : 64, e2 = 2;
-    Bump g;
-    w.mod_raw = g.take((size_t)c.B * c.L * 2 * 6 * D * e2);
-    w.tables = g.take((size_t)c.L * 2 * 3 * c.B * 2 * D * e2);
-    w.hs = g.take((size_t)(c.L > 1 ? c.L - 1 : 1) * M * D * e2);  // inputs of blocks 1 .. L-1
-    Bump b;
     w.n1 = b.take(M * D * e2);
     w.qkv = b.take(M * 3 * D * e2);
     w.qn = b.take(M * D * e2);
@@ -50,6 +51,18 @@ CogLayout make_layout(const ftmi_cog_config& c) {
     w.h1 = b.take(M * D * e2);
     w.n2 = b.take(M * D * e2);
     w.z = b.take(M * (size_t)c.D_ff * e2);
+}
+
+CogLayout make_layout(const ftmi_cog_config& c) {
+    CogLayout w;
+    const size_t N = (size_t)c.T + c.S, M = (size_t)c.B * N, D = c.D, r = c.r > 0 ? c.r : 64, e2 = 2;
+    Bump g;
+    w.mod_raw = g.take((size_t)c.B * c.L * 2 * 6 * D * e2);
+    w.tables = g.take((size_t)c.L * 2 * 3 * c.B * 2 * D * e2);
+    w.hs = g.take((size_t)(c.L > 1 ? c.L - 1 : 1) * M * D * e2);  // inputs of blocks 1 .. L-1
+    w.hs_slots = c.L > 1 ? c.L - 1 : 1;
+    Bump b;
+    take_fwd_slot(w, b, c);
     w.g_qkv = b.take(M * 3 * D * e2);
     w.g_o = b.take(M * D * e2);
     w.dxa_qkv = b.take(M * 9 * r * e2);
@@ -82,7 +95,7 @@ int check_cfg(const ftmi_cog_config& c) {
 struct Tables {  // the six modulation tables of one block, each [B][2][D]
     const bf16_t *shift1, *onep1, *gate1, *shift2, *onep2, *gate2;
 };
-Tables tables_of(const ftmi_cog_config& c, void* ws, const CogLayout& L, int l) {
+Tables tables_of(const ftmi_cog_config& c, void* ws, const CogFwdLayout& L, int l) {
     const size_t one = (size_t)c.B * 2 * c.D;
     const bf16_t* t = W(ws, L.tables) + (size_t)l * 6 * one;
     return {t, t + one, t + 2 * one, t + 3 * one, t + 4 * one, t + 5 * one};
@@ -119,15 +132,9 @@ AttnArgs attn_args(const ftmi_cog_config& c, const bf16_t* q, const bf16_t* k, c
     return a;
 }
 
-}  // namespace
-
-size_t cog_workspace_bytes(const ftmi_cog_config& c) { return make_layout(c).total; }
-
-int cog_blocks_forward(const ftmi_cog_config& c, const ftmi_cog_weights& w, const bf16_t* tokens_in, const bf16_t* temb_silu, bf16_t* tokens_out, void* ws,
-                       size_t ws_bytes, hipStream_t st) {
-    FTMI_TRY(check_cfg(c));
-    const CogLayout L = make_layout(c);
-    if (ws_bytes < L.total) return set_error(FTMI_ERR_INVALID, "cog_blocks_forward: workspace too small");
+// The forward walk over all L blocks, for either layout: the modulation GEMM + table pass, then per block the launches listed at the top of this file.
+int cog_walk_forward(const ftmi_cog_config& c, const ftmi_cog_weights& w, const CogFwdLayout& L, const bf16_t* tokens_in, const bf16_t* temb_silu, bf16_t* tokens_out,
+                     void* ws, hipStream_t st) {
     const int N = c.T + c.S, M = c.B * N, D = c.D, r = c.r, V = c.gemm_variant;
     const long D2 = (long)D * D;
     const float s = c.lora_scale;
@@ -141,8 +148,8 @@ int cog_blocks_forward(const ftmi_cog_config& c, const ftmi_cog_weights& w, cons
 
     for (int l = 0; l < c.L; ++l) {
         char* blk = reinterpret_cast<char*>(ws) + L.blk0 + L.blk_stride * l;
-        const bf16_t* h0 = l == 0 ? tokens_in : W(ws, L.hs) + (size_t)(l - 1) * M * D;
-        bf16_t* hout = l == c.L - 1 ? tokens_out : W(ws, L.hs) + (size_t)l * M * D;
+        const bf16_t* h0 = l == 0 ? tokens_in : W(ws, L.hs) + (size_t)((l - 1) % L.hs_slots) * M * D;
+        bf16_t* hout = l == c.L - 1 ? tokens_out : W(ws, L.hs) + (size_t)(l % L.hs_slots) * M * D;
         const Tables t = tables_of(c, ws, L, l);
         const bf16_t* la = w.lora_a_sp ? P(w.lora_a_sp, (size_t)l * 4 * 2 * r * D) : nullptr;   // [4][2r][D]
         const bf16_t* lb = w.lora_b_ext ? P(w.lora_b_ext, (size_t)l * 4 * D * 3 * r) : nullptr;  // [4][D][3r]
@@ -193,6 +200,18 @@ int cog_blocks_forward(const ftmi_cog_config& c, const ftmi_cog_weights& w, cons
         }
     }
     return 0;
+}
+
+}  // namespace
+
+size_t cog_workspace_bytes(const ftmi_cog_config& c) { return make_layout(c).total; }
+
+int cog_blocks_forward(const ftmi_cog_config& c, const ftmi_cog_weights& w, const bf16_t* tokens_in, const bf16_t* temb_silu, bf16_t* tokens_out, void* ws,
+                       size_t ws_bytes, hipStream_t st) {
+    FTMI_TRY(check_cfg(c));
+    const CogLayout L = make_layout(c);
+    if (ws_bytes < L.total) return set_error(FTMI_ERR_INVALID, "cog_blocks_forward: workspace too small");
+    return cog_walk_forward(c, w, L, tokens_in, temb_silu, tokens_out, ws, st);
 }
 
 // Blocks [l_lo, l_hi) of the backward, l_hi - 1 first.  d_out = gradient of block l_hi - 1's output when l_hi == L, otherwise the state left in the workspace by
@@ -292,6 +311,120 @@ int cog_blocks_backward(const ftmi_cog_config& c, const ftmi_cog_weights& w, con
             tn_batch(ta, nb, bs, bs, 4L * r * D);
             FTMI_TRY(gemm_tn(ta, st));
         }
+    }
+    return 0;
+}
+
+// ---- latent sampling: the whole denoising loop of a validation run as ONE call (include/ftmi355.h: ftmi_cog_sample; the kernels are in cog_sample.hip) ----
+// Restates what the reference gets from CogVideoXPipeline over the transformer it trains (finetrainers/models/cogvideox/base_specification.py:335-364), in
+// latent space, text-to-video.  Before the loop the text projection fills the text rows of tokens_in [P B, T + S, D]; they are never written again.  Per step,
+// on one stream, no host synchronisation -- the launches of MI355XCogVideoXTransformer3DModel.forward at batch P B, in its order, so the bits are its bits:
+//   patch embedding                 one NT GEMM per model row over its S rows of cols, into the video rows of tokens_in
+//   + sincos table (2b geometry)    cog_gate_residual per model row with a unit gate (text rows: + 0)
+//   cog_walk_forward                the block walk over the sampling layout: every block writes the SAME slot, the hidden state alternates between two buffers
+//   norm_final                      cog_ln_mod_fwd on the video rows of each model row (unit scale, zero shift)
+//   norm_out                        cog_ln_mod_fwd with the step's shift / 1 + scale (one row for all: they share the timestep)
+//   proj_out                        NT GEMM -> pred [P B S, Kc]
+//   cog_sample_step                 guidance combine + DDIM update on the state, bf16 copies into cols
+// Workspace: the modulation GEMM's output and tables (the only part that grows with L), tokens_in, the two hidden-state buffers, ONE block's forward slot, the
+// two forward scratch buffers, nf / no of the head and pred.  None of the backward's stash or scratch areas.
+namespace {
+
+struct CogSamplePlan {
+    CogFwdLayout lay;
+    size_t tokens, nf, no, pred, total;
+    long S, Kc;
+    ftmi_cog_config bc;
+};
+
+int make_sample_plan(const ftmi_cog_sample_config& c, CogSamplePlan& p) {
+    const ftmi_cog_sample_geometry& g = c.geo;
+    if (g.B <= 0 || g.C <= 0 || g.F <= 0 || g.H <= 0 || g.W <= 0 || g.p <= 0 || g.pt <= 0 || c.T <= 0 || c.D_text <= 0 || c.steps <= 0)
+        return set_error(FTMI_ERR_INVALID, "cog_sample: extents and steps must be positive");
+    if (g.F % g.pt || g.H % g.p || g.W % g.p) return set_error(FTMI_ERR_UNSUPPORTED, "cog_sample: the latent size must be whole patches");
+    if ((c.guidance != 1.0f) != (g.P == 2) || (g.P != 1 && g.P != 2)) return set_error(FTMI_ERR_INVALID, "cog_sample: P is 2 with guidance != 1 and 1 with guidance == 1");
+    p.S = (long)(g.F / g.pt) * (g.H / g.p) * (g.W / g.p);
+    p.Kc = (long)g.C * g.pt * g.p * g.p;
+    if (p.Kc % 64 || p.Kc > 2048 || c.D_text % 64) return set_error(FTMI_ERR_UNSUPPORTED, "cog_sample: C pt p p and the text width must be multiples of 64 (GEMM)");
+    if ((long)g.P * g.B * (c.T + p.S) > 0x7fffffffL) return set_error(FTMI_ERR_UNSUPPORTED, "cog_sample: too many tokens");
+    ftmi_cog_config& b = p.bc;
+    b.B = g.P * g.B; b.T = c.T; b.S = (int)p.S; b.D = c.D; b.H = c.heads; b.L = c.L; b.D_ff = c.D_ff; b.D_temb = c.D_temb; b.r = c.r;
+    b.lora_scale = c.lora_scale; b.eps_norm = c.eps_norm; b.eps_qk = c.eps_qk; b.gemm_variant = c.gemm_variant;
+    FTMI_TRY(check_cfg(b));
+    const size_t M = (size_t)b.B * (c.T + p.S), Mv = (size_t)b.B * p.S, D = c.D, e2 = 2;
+    Bump w;
+    p.lay.mod_raw = w.take((size_t)b.B * c.L * 2 * 6 * D * e2);
+    p.lay.tables = w.take((size_t)c.L * 2 * 3 * b.B * 2 * D * e2);
+    p.tokens = w.take(M * D * e2);
+    p.lay.hs = w.take(2 * M * D * e2);
+    p.lay.hs_slots = 2;
+    Bump slot;
+    take_fwd_slot(p.lay, slot, b);
+    p.lay.blk_stride = 0;
+    p.lay.blk0 = w.take(slot.off);
+    p.lay.s_act = w.take(M * (size_t)c.D_ff * e2);
+    p.lay.s_f = w.take(M * D * e2);
+    p.nf = w.take(Mv * D * e2);
+    p.no = w.take(Mv * D * e2);
+    p.pred = w.take(Mv * p.Kc * e2);
+    p.total = w.off;
+    return 0;
+}
+
+}  // namespace
+
+size_t cog_sample_workspace_bytes(const ftmi_cog_sample_config& c) {
+    CogSamplePlan p;
+    return make_sample_plan(c, p) ? 0 : p.total;
+}
+
+int cog_sample(const ftmi_cog_sample_config& c, const ftmi_cog_sample_weights& w, bf16_t* cols, float* x, const bf16_t* text, const bf16_t* temb_silu,
+               const bf16_t* head_shift, const bf16_t* head_onep, const float* coef, void* ws, size_t ws_bytes, hipStream_t st) {
+    CogSamplePlan p;
+    FTMI_TRY(make_sample_plan(c, p));
+    if (ws_bytes < p.total) return set_error(FTMI_ERR_INVALID, "cog_sample: workspace too small (ftmi_cog_sample_workspace_bytes)");
+    if (reinterpret_cast<uintptr_t>(ws) & 255) return set_error(FTMI_ERR_INVALID, "cog_sample: the workspace must be 256-byte aligned");
+    if (!w.patch_w || !w.patch_b || !w.text_w || !w.text_b || !w.norm_final_w || !w.norm_final_b || !w.norm_out_w || !w.norm_out_b || !w.proj_w || !w.proj_b ||
+        !w.ones || !w.zeros || !w.blocks.mod_w || !w.blocks.w_qkv)
+        return set_error(FTMI_ERR_INVALID, "cog_sample: weights missing");
+    if (c.r > 0 && (!w.blocks.lora_a_sp || !w.blocks.lora_b_ext)) return set_error(FTMI_ERR_INVALID, "cog_sample: adapters of rank r without their working copies");
+    if ((w.blocks.rope_cos != nullptr) != (w.blocks.rope_sin != nullptr)) return set_error(FTMI_ERR_INVALID, "cog_sample: the rotary tables come as a pair");
+    if ((w.blocks.rope_cos != nullptr) == (w.pos != nullptr))
+        return set_error(FTMI_ERR_INVALID, "cog_sample: a model has the sincos table (pos) or the rotary tables, one of the two");
+    const ftmi_cog_sample_geometry& g = c.geo;
+    const ftmi_cog_config& b = p.bc;
+    const int D = c.D, T = c.T, S = (int)p.S, N = T + S, rows = b.B, Kc = (int)p.Kc, V = c.gemm_variant;
+    bf16_t *tokens = W(ws, p.tokens), *nf = W(ws, p.nf), *no = W(ws, p.no), *pred = W(ws, p.pred);
+    bf16_t* out = W(ws, p.lay.hs) + (size_t)((c.L - 1) % 2) * rows * N * D;  // the slot the last block would write if the walk went on: free while it runs
+
+    for (int m = 0; m < rows; ++m)  // text rows, once: [neg; pos] through text_proj, one launch per model row as the model's forward issues them
+        FTMI_TRY(gemm_nt(linear_args(text + (size_t)m * T * c.D_text, c.D_text, T, P(w.text_w, 0), c.D_text, D, c.D_text, P(w.text_b, 0), tokens + (size_t)m * N * D, D, V), st));
+
+    for (int i = 0; i < c.steps; ++i) {
+        for (int m = 0; m < rows; ++m) {
+            bf16_t* tm = tokens + (size_t)m * N * D;
+            FTMI_TRY(gemm_nt(linear_args(cols + (size_t)m * S * Kc, Kc, S, P(w.patch_w, 0), Kc, D, Kc, P(w.patch_b, 0), tm + (size_t)T * D, D, V), st));
+            if (w.pos) {  // + sincos table (text rows: + 0), in place
+                CogLnArgs a;
+                a.x = tm; a.onep = P(w.ones, 0); a.dres = P(w.pos, 0); a.y = tm; a.rows = N; a.D = D; a.rows_per_batch = N; a.seg0 = 0;
+                FTMI_TRY(cog_gate_residual(a, st));
+            }
+        }
+        FTMI_TRY(cog_walk_forward(b, w.blocks, p.lay, tokens, temb_silu + (size_t)i * rows * c.D_temb, out, ws, st));
+        for (int m = 0; m < rows; ++m) {  // norm_final on the video rows of a model row (contiguous; the model rows are T rows apart)
+            CogLnArgs a;
+            a.x = out + ((size_t)m * N + T) * D; a.w = P(w.norm_final_w, 0); a.b = P(w.norm_final_b, 0); a.shift = P(w.zeros, 0); a.onep = P(w.ones, 0);
+            a.y = nf + (size_t)m * S * D; a.rows = S; a.D = D; a.rows_per_batch = S; a.seg0 = 0; a.eps = c.eps_norm;
+            FTMI_TRY(cog_ln_mod_fwd(a, st));
+        }
+        {  // norm_out with the step's modulation (every model row shares the timestep: one table row), proj_out
+            CogLnArgs a;
+            a.x = nf; a.w = P(w.norm_out_w, 0); a.b = P(w.norm_out_b, 0); a.shift = head_shift + (size_t)i * D; a.onep = head_onep + (size_t)i * D;
+            a.y = no; a.rows = rows * S; a.D = D; a.rows_per_batch = rows * S; a.seg0 = 0; a.eps = c.eps_norm;
+            FTMI_TRY(cog_ln_mod_fwd(a, st));
+            FTMI_TRY(gemm_nt(linear_args(no, D, rows * S, P(w.proj_w, 0), D, Kc, D, P(w.proj_b, 0), pred, Kc, V), st));
+        }
+        FTMI_TRY(cog_sample_step(g, pred, x, coef, i, c.guidance, cols, st));
     }
     return 0;
 }

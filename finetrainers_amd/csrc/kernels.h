@@ -337,6 +337,13 @@ int cog_blocks_forward(const ftmi_cog_config& c, const ftmi_cog_weights& w, cons
 int cog_blocks_backward(const ftmi_cog_config& c, const ftmi_cog_weights& w, const bf16_t* tokens_in, const bf16_t* d_out, bf16_t* d_in, float* grad_a,
                         float* grad_b, void* ws, size_t ws_bytes, int l_hi, int l_lo, int accumulate, hipStream_t st);
 int cog_mod_tables(const bf16_t* mod, bf16_t* tables, int L2, int B, int D, hipStream_t st);  // linear(silu(temb)) rows -> (shift, 1 + scale, gate) x (text, video)
+// CogVideoX latent sampling (cog_sample.hip: the layout kernels; cog_dit.hip: the loop over the forward-only walk)
+int cog_sample_init(const ftmi_cog_sample_geometry& g, const float* latents, float* x, bf16_t* cols, hipStream_t st);
+int cog_sample_step(const ftmi_cog_sample_geometry& g, const bf16_t* pred, float* x, const float* coef, int step, float guidance, bf16_t* cols, hipStream_t st);
+int cog_sample_finish(const ftmi_cog_sample_geometry& g, const float* x, float k, bf16_t* latents, hipStream_t st);
+size_t cog_sample_workspace_bytes(const ftmi_cog_sample_config& c);
+int cog_sample(const ftmi_cog_sample_config& c, const ftmi_cog_sample_weights& w, bf16_t* cols, float* x, const bf16_t* text, const bf16_t* temb_silu,
+               const bf16_t* head_shift, const bf16_t* head_onep, const float* coef, void* ws, size_t ws_bytes, hipStream_t st);
 // ---- Wan-T2V row-wise kernels (wan.hip): one argument block for the seven launchers --------------------------------------------------------
 struct WanRowArgs {
     const bf16_t* x = nullptr;   // input rows [rows, ld_x]   (gate_res_bwd: d out)

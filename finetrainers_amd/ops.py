@@ -1131,3 +1131,88 @@ def wan_sample(cfg, weights, cols, x, tproj, head_shift, head_scale, enc, enc_im
     check(_lib.load().ftmi_wan_sample(ctypes.byref(cfg), ctypes.byref(weights), ptr(cols), ptr(x), ptr(tproj), ptr(head_shift), ptr(head_scale), ptr(enc),
                                       ptr(enc_img if cfg.TI > 0 else None), ptr(rope[0]), ptr(rope[1]), ptr(sigmas), ptr(workspace), workspace.numel(),
                                       stream_ptr()), "ftmi_wan_sample")
+
+
+# ---- CogVideoX latent sampling (include/ftmi355.h: ftmi_cog_sample_*; csrc/cog_sample.hip, csrc/cog_dit.hip) ---------------------------------------------
+def cog_sample_geometry(B: int, C: int, frames: int, height: int, width: int, patch: int = 2, patch_t: Optional[int] = None, guidance: bool = True,
+                        drop: int = 0) -> "_lib.CogSampleGeometry":
+    """The layout of a sampling run: latents [B, frames, C, height, width], x [B, S, Kc], cols [P B S, Kc], pred [P B, S, Kc]; ``drop``: the padded leading
+    frames that ``cog_sample_finish`` leaves out."""
+    return _lib.CogSampleGeometry(B=B, C=C, F=frames, H=height, W=width, p=patch, pt=patch_t or 1, P=2 if guidance else 1, drop=drop)
+
+
+def _cog_sample_dims(geo) -> Tuple[int, int]:
+    if geo.F % geo.pt or geo.H % geo.p or geo.W % geo.p:
+        raise ValueError("cog_sample: the latent size must be whole patches")
+    return (geo.F // geo.pt) * (geo.H // geo.p) * (geo.W // geo.p), geo.C * geo.pt * geo.p * geo.p
+
+
+def _cog_sample_buffers(geo, x, cols, what: str) -> None:
+    S, Kc = _cog_sample_dims(geo)
+    if x is not None and (tuple(x.shape) != (geo.B, S, Kc) or x.dtype != torch.float32 or not x.is_contiguous() or not x.is_cuda):
+        raise ValueError(f"{what}: x must be a contiguous fp32 [{geo.B}, {S}, {Kc}] GPU tensor, got {tuple(x.shape)}")
+    if cols is not None and (tuple(cols.shape) != (geo.P * geo.B * S, Kc) or cols.dtype != bf16 or not cols.is_contiguous() or not cols.is_cuda):
+        raise ValueError(f"{what}: cols must be a contiguous bf16 [{geo.P * geo.B * S}, {Kc}] GPU tensor, got {tuple(cols.shape)}")
+
+
+def cog_sample_init(geo, latents, x=None, cols=None):
+    """noise fp32 [B, F, C, H, W] -> (x fp32 [B, S, Kc], cols bf16 [P B S, Kc]): ftmi_cog_sample_init."""
+    require_gpu_tensor(latents, "latents", torch.float32)
+    if tuple(latents.shape) != (geo.B, geo.F, geo.C, geo.H, geo.W) or not latents.is_contiguous():
+        raise ValueError(f"cog_sample_init: latents must be contiguous [{geo.B}, {geo.F}, {geo.C}, {geo.H}, {geo.W}], got {tuple(latents.shape)}")
+    S, Kc = _cog_sample_dims(geo)
+    x = torch.empty((geo.B, S, Kc), dtype=torch.float32, device=latents.device) if x is None else x
+    cols = torch.empty((geo.P * geo.B * S, Kc), dtype=bf16, device=latents.device) if cols is None else cols
+    _cog_sample_buffers(geo, x, cols, "cog_sample_init")
+    check(_lib.load().ftmi_cog_sample_init(ctypes.byref(geo), ptr(latents), ptr(x), ptr(cols), stream_ptr()), "ftmi_cog_sample_init")
+    return x, cols
+
+
+def cog_sample_step(geo, pred, x, coef, step: int, guidance: float, cols=None) -> None:
+    """One sampler step in place (ftmi_cog_sample_step): pred bf16 [P B, S, Kc] (None: only the bf16 copies), x fp32 [B, S, Kc], coef fp32 [n, 2] on the device
+    (row ``step`` = (cx, cv): x <- cx x + cv v), cols bf16 [P B S, Kc] (None: only the update)."""
+    _cog_sample_buffers(geo, x, cols, "cog_sample_step")
+    S, Kc = _cog_sample_dims(geo)
+    if pred is not None:
+        require_gpu_tensor(pred, "pred", bf16)
+        if pred.numel() != geo.P * geo.B * S * Kc or not pred.is_contiguous():
+            raise ValueError(f"cog_sample_step: pred must be contiguous [{geo.P * geo.B}, {S}, {Kc}], got {tuple(pred.shape)}")
+        require_gpu_tensor(coef, "coef", torch.float32)
+        if coef.dim() != 2 or coef.shape[1] != 2 or not coef.is_contiguous() or not 0 <= int(step) < coef.shape[0]:
+            raise ValueError("cog_sample_step: coef is a contiguous fp32 [n, 2] table and step one of its rows")
+    check(_lib.load().ftmi_cog_sample_step(ctypes.byref(geo), ptr(pred), ptr(x), ptr(coef), int(step), float(guidance), ptr(cols), stream_ptr()),
+          "ftmi_cog_sample_step")
+
+
+def cog_sample_finish(geo, x, k: float):
+    """x fp32 [B, S, Kc] -> latents bf16 [B, F - drop, C, H, W] = bf16(x * k) (ftmi_cog_sample_finish)."""
+    _cog_sample_buffers(geo, x, None, "cog_sample_finish")
+    out = torch.empty((geo.B, geo.F - geo.drop, geo.C, geo.H, geo.W), dtype=bf16, device=x.device)
+    check(_lib.load().ftmi_cog_sample_finish(ctypes.byref(geo), ptr(x), float(k), ptr(out), stream_ptr()), "ftmi_cog_sample_finish")
+    return out
+
+
+def cog_sample_workspace_bytes(cfg) -> int:
+    n = int(_lib.load().ftmi_cog_sample_workspace_bytes(ctypes.byref(cfg)))
+    if n == 0:
+        raise ValueError(f"cog_sample: {_lib.last_error()}")
+    return n
+
+
+def cog_sample(cfg, weights, cols, x, text, temb_silu, head_shift, head_onep, coef, workspace=None) -> None:
+    """The whole denoising loop in ONE call (ftmi_cog_sample), in place on ``x`` / ``cols`` (as ``cog_sample_init`` wrote them).  text bf16 [P B, T, D_text]
+    (unconditional rows first); temb_silu bf16 [steps, P B, D_temb]; head_shift / head_onep bf16 [steps, D]; coef fp32 [steps, 2] on the device.
+    ``workspace``: a uint8 GPU tensor of at least ``cog_sample_workspace_bytes(cfg)`` (allocated when None)."""
+    geo, n, D = cfg.geo, cfg.steps, cfg.D
+    _cog_sample_buffers(geo, x, cols, "cog_sample")
+    rows = geo.P * geo.B
+    want = [("text", text, bf16, (rows, cfg.T, cfg.D_text)), ("temb_silu", temb_silu, bf16, (n, rows, cfg.D_temb)), ("head_shift", head_shift, bf16, (n, D)),
+            ("head_onep", head_onep, bf16, (n, D)), ("coef", coef, torch.float32, (n, 2))]
+    for name, t, dt, shape in want:
+        if t is None or not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"cog_sample: {name} must be a contiguous {dt} {shape} GPU tensor, got {None if t is None else tuple(t.shape)}")
+    need = cog_sample_workspace_bytes(cfg)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
+    check(_lib.load().ftmi_cog_sample(ctypes.byref(cfg), ctypes.byref(weights), ptr(cols), ptr(x), ptr(text), ptr(temb_silu), ptr(head_shift), ptr(head_onep),
+                                      ptr(coef), ptr(workspace), workspace.numel(), stream_ptr()), "ftmi_cog_sample")

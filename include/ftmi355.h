@@ -919,6 +919,68 @@ int ftmi_wan_sample(const ftmi_wan_sample_config* cfg, const ftmi_wan_sample_wei
                     const float* head_scale, const void* enc, const void* enc_img, const float* rope_cos, const float* rope_sin, const float* sigmas,
                     void* workspace, size_t workspace_bytes, ftmi_stream stream);
 
+/* ---- CogVideoX latent sampling (csrc/cog_sample.hip: the layout kernels; csrc/cog_dit.hip: the loop) ----
+ * The denoising loop of the reference's validation (finetrainers/models/cogvideox/base_specification.py:335-364 runs CogVideoXPipeline over the transformer
+ * that is being trained) in latent space, text-to-video: [upstream, unpinned] CogVideoXPipeline + CogVideoXDDIMScheduler (v-prediction, eta = 0).
+ * The patch embedding's operand order and proj_out's column order are the same, (c, ph, pw) or (c, pt, ph, pw) with patch_size_t, so the state lives there:
+ *   x     fp32 [B, S, Kc]      Kc = C pt p p columns, S = (F / pt)(H / p)(W / p) tokens in (f, h, w) order
+ *   cols  bf16 [P B S, Kc]     the patch-embedding GEMM's operand, bf16(x) in every row group; P = 2 with guidance (unconditional rows first), 1 without
+ *   pred  bf16 [P B, S, Kc]    as proj_out writes it: the same columns, so a step is a row-major stream with no permutation
+ * FTMI_ERR_UNSUPPORTED: Kc % 8, a latent size that is not whole patches, pt > 2; FTMI_ERR_INVALID: empty extents, P, drop, misaligned tensors (16 bytes). */
+typedef struct ftmi_cog_sample_geometry {
+    int B, C;    /* samples, latent channels */
+    int F, H, W; /* latent grid; F counts the frames the pipeline pads at the front (patch_size_t) */
+    int p, pt;   /* spatial patch, temporal patch (1: none; 2: CogVideoX 1.5) */
+    int P;       /* row groups of cols / pred: 2 with guidance, 1 without */
+    int drop;    /* leading frames ftmi_cog_sample_finish leaves out (the pipeline's latents[:, additional_frames:]); 0 <= drop < pt */
+} ftmi_cog_sample_geometry;
+/* noise fp32 [B, F, C, H, W] -> x (the patchified values, exact) and bf16(x) in all P row groups of cols (replaces the pipeline's prepare_latents hand-over to the
+ * transformer's patch embedding, CogVideoXPatchEmbed's reshape / permute per step). */
+int ftmi_cog_sample_init(const ftmi_cog_sample_geometry* geo, const float* latents, float* x, void* cols, ftmi_stream stream);
+/* One step (replaces the pipeline's noise_pred_uncond + guidance_scale * (noise_pred_text - noise_pred_uncond) and CogVideoXDDIMScheduler.step): with
+ * (cx, cv) = coef[2 step], coef[2 step + 1] read on the device:  d = c - u; v = fma(g, d, u) (guidance == 1: v = c, pred has no unconditional half);
+ * x <- fma(cx, x, cv * v) in fp32; bf16(x) into every row group of cols.  pred == NULL: only the copies; cols == NULL: only the update. */
+int ftmi_cog_sample_step(const ftmi_cog_sample_geometry* geo, const void* pred, float* x, const float* coef, int step, float guidance, void* cols,
+                         ftmi_stream stream);
+/* latents bf16 [B, F - drop, C, H, W] = bf16(x * k), the inverse permutation of init without the first `drop` frames (replaces the pipeline's
+ * latents[:, additional_frames:] and decode_latents' 1 / scaling_factor; k = scaling_factor for the invert_scale_latents checkpoints). */
+int ftmi_cog_sample_finish(const ftmi_cog_sample_geometry* geo, const float* x, float k, void* latents, ftmi_stream stream);
+
+/* The whole denoising loop as ONE call, no host synchronisation (replaces the loop of CogVideoXPipeline.__call__ the reference's validation drives,
+ * base_specification.py:335-364).  Before the loop the text projection writes the text rows of tokens_in [P B, T + S, D] once.  Per step: the patch-embedding
+ * NT GEMM over cols into the video rows of tokens_in (one launch per model row, as the model's forward issues them); pos != NULL: + the sincos table
+ * (ftmi_cog_gate_residual); the block walk of ftmi_cog_blocks_forward at batch P B over a forward-only layout (every block writes the same slot, the hidden
+ * state alternates between two buffers); norm_final on the video rows; norm_out with the step's shift / 1 + scale; proj_out; ftmi_cog_sample_step.
+ * Bit-identical to that composition issued call by call.
+ * The caller supplies what does not depend on the state: text bf16 [P B, T, D_text] (unconditional rows first), temb_silu bf16 [steps, P B, D_temb],
+ * head_shift / head_onep bf16 [steps, D], coef fp32 [steps, 2] on the device, the rotary tables in blocks.rope_cos / rope_sin.
+ * x / cols: in and out (ftmi_cog_sample_init wrote them).  Workspace: ftmi_cog_sample_workspace_bytes (0 for a refused configuration; it depends on L only
+ * through the modulation tables); a smaller one is FTMI_ERR_INVALID. */
+typedef struct ftmi_cog_sample_config {
+    ftmi_cog_sample_geometry geo;
+    int T, D_text;            /* text tokens, width of the text embeddings */
+    int D, heads, L;          /* width = heads x 64, blocks */
+    int D_ff, D_temb;
+    int r;                    /* LoRA rank (0: none; multiple of 64) */
+    float lora_scale, eps_norm, eps_qk;
+    int gemm_variant;         /* 8 */
+    int steps;
+    float guidance;           /* != 1 needs geo.P == 2 */
+} ftmi_cog_sample_config;
+typedef struct ftmi_cog_sample_weights {
+    ftmi_cog_weights blocks;                      /* the "_t" copies and the backward's adapter copies are not read */
+    const void *patch_w, *patch_b;                /* bf16 [D, Kc], [D] */
+    const void *text_w, *text_b;                  /* bf16 [D, D_text], [D] */
+    const void* pos;                              /* bf16 [T + S, D]: the sincos table, text rows zero; NULL for the rotary checkpoints */
+    const void *norm_final_w, *norm_final_b;      /* bf16 [D] */
+    const void *norm_out_w, *norm_out_b;          /* bf16 [D] */
+    const void *proj_w, *proj_b;                  /* bf16 [Kc, D], [Kc] */
+    const void *ones, *zeros;                     /* bf16 [D] of 1 and of 0 (the unmodulated norm_final, the position table's unit gate) */
+} ftmi_cog_sample_weights;
+size_t ftmi_cog_sample_workspace_bytes(const ftmi_cog_sample_config* cfg);
+int ftmi_cog_sample(const ftmi_cog_sample_config* cfg, const ftmi_cog_sample_weights* w, void* cols, float* x, const void* text, const void* temb_silu,
+                    const void* head_shift, const void* head_onep, const float* coef, void* workspace, size_t workspace_bytes, ftmi_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -576,12 +576,141 @@ def build_wan_sample(args, par, dev) -> Dict[str, Any]:
     }
 
 
+# ------------------------------------------------------------------------------------------------------------------------------------------
+# CogVideoX-2b validation sampling in latent space (finetrainers_amd/cogvideox/sampler.py): 49 x 480 x 720 -> latents 13 x 60 x 90 = 17 550 video + 226 text
+# tokens, unconditional + conditional rows (guidance 6), random weights with rank-`--rank` adapters (run with --rank 64: the recipe's rank).  One "step" of
+# this workload is one ftmi_cog_sample call of `SAMPLE_STEPS` denoising steps; the report interleaves it with the same loop composed in Python (model.forward +
+# ops.cog_sample_step, whose workspace keeps every block's activations) and times the step kernel on its own.
+# ------------------------------------------------------------------------------------------------------------------------------------------
+def _random_cogvideox(cfg, rank: int, dev):
+    """Random-init weights of the DiT (the recipe of build_cogvideox) with rank-``rank`` adapters whose B is non-zero; no optimiser state."""
+    from finetrainers_amd.cogvideox import MI355XCogVideoXTransformer3DModel
+
+    model = MI355XCogVideoXTransformer3DModel(cfg, device=dev)
+    g = torch.Generator(device=dev).manual_seed(0)
+    D = cfg.inner_dim
+    rnd = lambda shape, fan_in: (torch.randn(shape, generator=g, device=dev) / fan_in ** 0.5).to(bf16)
+
+    def one(k, shp):
+        if len(shp) == 2:
+            return rnd(shp, shp[1])
+        return torch.ones(shp, device=dev, dtype=bf16) if "norm" in k and k.endswith("weight") else 0.02 * rnd(shp, 1)
+
+    sd = {k: one(k, getattr(model, name).shape) for k, name in model._KEYS.items()}
+    sd["patch_embed.proj.weight"] = rnd((D, cfg.in_channels, 2, 2), 64)
+    for i, blk in enumerate(model.transformer_blocks):
+        for k, name in blk._KEYS.items():
+            sd[f"transformer_blocks.{i}.{k}"] = one(k, getattr(blk, name).shape)
+    model.load_diffusers_state_dict(sd)
+    del sd
+    model.add_adapter(r=rank, lora_alpha=float(rank))
+    with torch.no_grad():
+        n = model.lora_flat.numel() // 2
+        model.lora_flat[n:].normal_(0, 0.01, generator=g)
+    return model
+
+
+def build_cog_sample(args, par, dev) -> Dict[str, Any]:
+    from finetrainers_amd import ops
+    from finetrainers_amd.cogvideox import CogVideoXTransformerConfig, MI355XCogVideoXLatentSampler, cog_ddim_tables
+
+    layers = args.layers if args.layers > 0 else 30
+    cfg = CogVideoXTransformerConfig(num_layers=layers)
+    model = _random_cogvideox(cfg, args.rank, dev)
+    g = torch.Generator(device=dev).manual_seed(3)
+    B, C, F_, H, W, T, guidance, n = 1, 16, 13, 60, 90, 226, 6.0, SAMPLE_STEPS
+    S, Kc, D = F_ * (H // 2) * (W // 2), 4 * C, cfg.inner_dim
+    sampler = MI355XCogVideoXLatentSampler(model)
+    pos, neg = (torch.randn((B, T, cfg.text_embed_dim), generator=g, device=dev).to(bf16) for _ in range(2))
+    noise = torch.randn((B, F_, C, H, W), generator=g, device=dev)
+    ts, coef = cog_ddim_tables(n)
+    coef = coef.to(dev)
+    geo = sampler.geometry(B, F_, H, W, guidance=True)
+    text = torch.cat([neg, pos]).contiguous()
+    temb, shift, onep = sampler.step_tables(ts, 2 * B)
+    ccfg, weights, keep = sampler.c_arguments(geo, n, guidance)
+    ws_bytes = ops.cog_sample_workspace_bytes(ccfg)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+
+    def one_call():
+        x, cols = ops.cog_sample_init(geo, noise)
+        ops.cog_sample(ccfg, weights, cols, x, text, temb, shift, onep, coef, workspace=ws)
+        return None
+
+    @torch.no_grad()
+    def composed():
+        x, cols = ops.cog_sample_init(geo, noise)
+        for i in range(n):
+            t = torch.full((2 * B,), int(ts[i]), dtype=torch.int64, device=dev)
+            hidden = ops.cog_unpatchify(cols.view(2 * B, S, Kc), F_, C, H, W, 2)
+            out = model(hidden, text, t)[0]
+            ops.cog_sample_step(geo, ops.cog_patchify(out, 2), x, coef, i, guidance, cols)
+
+    def once(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    def report(one_call_ms: float) -> Dict[str, Any]:
+        peak_one = torch.cuda.max_memory_allocated() / 1e9
+        torch.cuda.reset_peak_memory_stats()
+        composed()  # warm (allocates the training workspace)
+        a_ms, b_ms = [], []
+        for _ in range(3):  # interleaved: both paths see the same clocks and the same neighbours
+            a_ms.append(once(one_call))
+            b_ms.append(once(composed))
+        peak_comp = torch.cuda.max_memory_allocated() / 1e9
+        x, cols = ops.cog_sample_init(geo, noise)
+        pred = torch.randn((2 * B, S, Kc), generator=g, device=dev).to(bf16)
+        reps = 50
+        for _ in range(5):
+            ops.cog_sample_step(geo, pred, x, coef, 1, guidance, cols)
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps):
+            ops.cog_sample_step(geo, pred, x, coef, 1, guidance, cols)
+        b.record()
+        torch.cuda.synchronize()
+        us = a.elapsed_time(b) * 1e3 / reps
+        nbytes = B * S * Kc * 16  # per element of x: read u 2 + c 2 + x 4, write x 4 + 2 x 2
+        return {"ms_per_denoising_step_one_call": sorted(a_ms)[1] / n, "ms_per_denoising_step_python_composition": sorted(b_ms)[1] / n,
+                "ms_per_denoising_step_one_call_first_pass": one_call_ms / n, "interleaved_ms_one_call": a_ms, "interleaved_ms_python_composition": b_ms,
+                "peak_memory_gb_one_call": peak_one, "peak_memory_gb_python_composition": peak_comp, "workspace_gb": ws_bytes / 1e9,
+                "training_workspace_gb": int(_cog_training_workspace(model, 2 * B, T + S)) / 1e9,
+                "step_kernel_us": us, "step_kernel_bytes": nbytes, "step_kernel_gbps": nbytes / (us * 1e-6) / 1e9}
+
+    N = T + S
+    flop = 2 * layers * (2.0 * N * D * D * 12 + 4.0 * N * N * D)  # two model rows: linears + joint attention, forward only
+    return {
+        "one_step": one_call,
+        "report": report,
+        "samples_per_step": 1.0 / n,
+        "step_tflop": n * flop / 1e12,
+        "metric": f"ftmi_cog_sample: one call of {n} denoising steps, CogVideoX-2b 49x480x720, guidance 6 (value: denoising steps per ms are in the report)",
+        "data": "random noise [1,13,16,60,90] + random text embeds [1,226,4096] (conditional and unconditional), random-init weights of the CogVideoX-2b DiT",
+        "config": {"workload": f"CogVideoX-2b latent sampling, rank={args.rank} adapters, {S} video + {T} text tokens, 2 model rows (unconditional + conditional), {layers} blocks"
+                               + ("" if layers == 30 else " -- REDUCED depth"), "seq_len": N, "denoising_steps_per_call": n},
+        "layers": layers,
+    }
+
+
+def _cog_training_workspace(model, B: int, N: int) -> int:
+    import ctypes
+
+    from finetrainers_amd import _lib
+
+    return _lib.load().ftmi_cog_workspace_bytes(ctypes.byref(model._c_config(B, N)))
+
+
 WORKLOADS = {"cogvideox": (build_cogvideox, lambda a, c: cpu_baseline_cogvideox(a, c["layers"])),
              "wan": (build_wan, lambda a, c: cpu_baseline_wan(a, c["layers"])),
              "wan_lora": (build_wan_lora, lambda a, c: cpu_baseline_wan(a, c["layers"])),  # (yardstick on the host: the full fine-tune block, an upper bound of the LoRA block's work)
              "wan_control_lora": (build_wan_control_lora, None),  # (no host yardstick; run with --rank 128: the recipe's rank)
              "wan_i2v_lora": (build_wan_i2v_lora, None),  # (no host yardstick: this row runs through this file's own command line only)
              "wan_sample": (build_wan_sample, None),  # (validation sampling: forward only; this file's own command line only)
+             "cog_sample": (build_cog_sample, None),  # (validation sampling: forward only; this file's own command line only; --rank 64)
              "hunyuan": (build_hunyuan, cpu_baseline_hunyuan)}
 
 
