@@ -6,7 +6,7 @@ The reference validates by running ``CogVideoXPipeline`` over the transformer th
 workspace keeps every block's activations for a backward).  Here the loop -- DiT forward on the unconditional + conditional prompt, classifier-free-guidance
 combine, DDIM update -- is ONE C call (``ftmi_cog_sample``, no host synchronisation) over a forward-only walk of the same block launches, with the adapters as
 they are at the moment of the call.  The sampler state stays in the patch embedding's operand layout, which is also ``proj_out``'s column order
-(csrc/cog_sample.hip), so nothing is patchified between steps.  Text encoding and the VAE stay outside: the sampler takes embeddings and noise and returns
+(csrc/sample_layout.hip), so nothing is patchified between steps.  Text encoding and the VAE stay outside: the sampler takes embeddings and noise and returns
 denormalised latents (INTEGRATION.md shows the hand-over to the reference pipeline's VAE decode).
 
 [upstream, unpinned] The arithmetic restates ``CogVideoXDDIMScheduler`` / ``CogVideoXPipeline`` as of diffusers 0.33 (neither is vendored here):

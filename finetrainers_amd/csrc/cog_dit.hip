@@ -315,7 +315,7 @@ int cog_blocks_backward(const ftmi_cog_config& c, const ftmi_cog_weights& w, con
     return 0;
 }
 
-// ---- latent sampling: the whole denoising loop of a validation run as ONE call (include/ftmi355.h: ftmi_cog_sample; the kernels are in cog_sample.hip) ----
+// ---- latent sampling: the whole denoising loop of a validation run as ONE call (include/ftmi355.h: ftmi_cog_sample; the kernels are in sample_layout.hip) ----
 // Restates what the reference gets from CogVideoXPipeline over the transformer it trains (finetrainers/models/cogvideox/base_specification.py:335-364), in
 // latent space, text-to-video.  Before the loop the text projection fills the text rows of tokens_in [P B, T + S, D]; they are never written again.  Per step,
 // on one stream, no host synchronisation -- the launches of MI355XCogVideoXTransformer3DModel.forward at batch P B, in its order, so the bits are its bits:

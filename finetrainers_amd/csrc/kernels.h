@@ -247,7 +247,7 @@ int noise_pack(const bf16_t* latents, const bf16_t* noise, const float* mean, co
                const float* sigma_first, int first_frame_tokens, bf16_t* xt, bf16_t* target, int B, int C, int S,
                hipStream_t st);
 
-// ---- latent sampling (ltx_sample.hip) ----
+// ---- latent sampling (ltx_sample.hip; the step arithmetic the three samplers share is in sample_step.hip.h) ----
 // one sampler step: v = u + g (c - u), x += (sigma_next - sigma) v in fp32, bf16 copy of the new x into both halves of xin ([2B, per_sample]; guidance == 1:
 // pred and xin are [B, per_sample]).  sigma / sigma_next element b at [b * sig_stride] (0: one value for every sample).  pred == nullptr: only the bf16
 // copies of x (the first model input); xin == nullptr: only the update (the last step)
@@ -337,7 +337,7 @@ int cog_blocks_forward(const ftmi_cog_config& c, const ftmi_cog_weights& w, cons
 int cog_blocks_backward(const ftmi_cog_config& c, const ftmi_cog_weights& w, const bf16_t* tokens_in, const bf16_t* d_out, bf16_t* d_in, float* grad_a,
                         float* grad_b, void* ws, size_t ws_bytes, int l_hi, int l_lo, int accumulate, hipStream_t st);
 int cog_mod_tables(const bf16_t* mod, bf16_t* tables, int L2, int B, int D, hipStream_t st);  // linear(silu(temb)) rows -> (shift, 1 + scale, gate) x (text, video)
-// CogVideoX latent sampling (cog_sample.hip: the layout kernels; cog_dit.hip: the loop over the forward-only walk)
+// CogVideoX latent sampling (sample_layout.hip: the layout kernels, shared with Wan; cog_dit.hip: the loop over the forward-only walk)
 int cog_sample_init(const ftmi_cog_sample_geometry& g, const float* latents, float* x, bf16_t* cols, hipStream_t st);
 int cog_sample_step(const ftmi_cog_sample_geometry& g, const bf16_t* pred, float* x, const float* coef, int step, float guidance, bf16_t* cols, hipStream_t st);
 int cog_sample_finish(const ftmi_cog_sample_geometry& g, const float* x, float k, bf16_t* latents, hipStream_t st);
@@ -422,7 +422,7 @@ int wan_lora_ffn_block_backward(const ftmi_wan_lora_ffn_block_config& c, const f
                                 const bf16_t* enc, const bf16_t* enc_img, const float* mod, const float* rope_cos, const float* rope_sin, const bf16_t* dout,
                                 bf16_t* dx, bf16_t* denc, float* grad_a, float* grad_b, float* grad_ffn_a1, float* grad_ffn_b1, float* grad_ffn_a2,
                                 float* grad_ffn_b2, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st);
-// Wan latent sampling (wan_sample.hip: the layout kernels; wan_sample_dit.hip: the loop).  sigma / sigma_next element b at [b * sig_stride] (0: one value for all)
+// Wan latent sampling (sample_layout.hip: the layout kernels, shared with CogVideoX; wan_sample_dit.hip: the loop).  sigma / sigma_next element b at [b * sig_stride] (0: one value for all)
 int wan_sample_init(const ftmi_wan_sample_geometry& g, const float* latents, const bf16_t* extra, float* x, bf16_t* cols, hipStream_t st);
 int wan_sample_step(const ftmi_wan_sample_geometry& g, const bf16_t* pred, float* x, const float* sigma, const float* sigma_next, long sig_stride, float guidance,
                     bf16_t* cols, hipStream_t st);

@@ -25,18 +25,11 @@
 //   Bytes moved per element: 4 read + 2 written.
 #include "common.hip.h"
 #include "kernels.h"
+#include "sample_step.hip.h"
 
 namespace ftmi {
 
 namespace {
-
-FTMI_DEVICE void unpack8(const u32x4& p, float* f) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        f[2 * i] = __uint_as_float(p[i] << 16);
-        f[2 * i + 1] = __uint_as_float(p[i] & 0xffff0000u);
-    }
-}
 
 // n8 = B * per8 vectors of 8 elements; per8 = per_sample / 8.  kCfg: pred has an unconditional half.  pred == nullptr: no update, only the
 // bf16 copies of x (the model input of the first step).  kHold: the first hold8 vectors of every sample are held (copied to xin, never updated).
@@ -60,16 +53,7 @@ __global__ __launch_bounds__(256) void cfg_euler_step_kernel(const bf16_t* __res
         if (!kHold) b = i / per8;
         const float dt = sigma_next[b * sig_stride] - sigma[b * sig_stride];
         float v[8];
-        const u32x4* pp = reinterpret_cast<const u32x4*>(pred);
-        if (kCfg) {
-            float u[8], c[8];
-            unpack8(pp[i], u);
-            unpack8(pp[n8 + i], c);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = __builtin_fmaf(g, c[e] - u[e], u[e]);
-        } else {
-            unpack8(pp[i], v);
-        }
+        cfg_combine8<kCfg>(pred, i, n8, g, v);
 #pragma unroll
         for (int e = 0; e < 8; ++e) xv[e] = __builtin_fmaf(dt, v[e], xv[e]);
         x0 = f32x4{xv[0], xv[1], xv[2], xv[3]};
@@ -77,14 +61,7 @@ __global__ __launch_bounds__(256) void cfg_euler_step_kernel(const bf16_t* __res
         xp[0] = x0;
         xp[1] = x1;
     }
-    if (xin) {
-        u32x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = pack2bf(xv[2 * e], xv[2 * e + 1]);
-        u32x4* op = reinterpret_cast<u32x4*>(xin);
-        op[i] = o;
-        if (kCfg) op[n8 + i] = o;
-    }
+    if (xin) store_groups8<kCfg>(xin, xv, 8 * i, 8 * n8);
 }
 
 constexpr int kUnpackPitch = 72;  // bf16 elements per LDS row: 144 bytes, keeps the 16-byte reads aligned
@@ -153,7 +130,7 @@ int cfg_euler_step(const bf16_t* pred, float* x, const float* sigma, const float
     if (per_sample % 8) return set_error(FTMI_ERR_UNSUPPORTED, "cfg_euler_step: elements per sample must be a multiple of 8 (16-byte vectors)");
     if (hold < 0 || hold > per_sample) return set_error(FTMI_ERR_INVALID, "cfg_euler_step: the held prefix must lie inside the sample");
     if (hold % 8) return set_error(FTMI_ERR_UNSUPPORTED, "cfg_euler_step: the held prefix must be a multiple of 8 elements (16-byte vectors)");
-    if (((uintptr_t)pred | (uintptr_t)x | (uintptr_t)xin) & 15) return set_error(FTMI_ERR_INVALID, "cfg_euler_step: tensors must be 16-byte aligned");
+    if (misaligned(pred) || misaligned(x) || misaligned(xin)) return set_error(FTMI_ERR_INVALID, "cfg_euler_step: tensors must be 16-byte aligned");
     const long per8 = per_sample / 8, n8 = per8 * B, hold8 = hold / 8;
     const long blocks = (n8 + 255) / 256;
     if (blocks > 0x7fffffffL) return set_error(FTMI_ERR_UNSUPPORTED, "cfg_euler_step: too many elements for one launch");

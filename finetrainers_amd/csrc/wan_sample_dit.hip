@@ -10,7 +10,7 @@
 //                                        is kept for a backward -- and shares one scratch area; activations alternate between two [P B S, D] buffers
 //   wan_ln_fwd + proj_out                the head with the step's fp32 shift / scale (one row for every sample: they share the timestep)
 //   wan_sample_step                      guidance combine + Euler update on the state, bf16 copies into the columns [0, Kc) of cols
-// The sampler state x fp32 [B, S, Kc] and the model input cols stay in the patch embedding's operand layout (wan_sample.hip): no patchify between steps.
+// The sampler state x fp32 [B, S, Kc] and the model input cols stay in the patch embedding's operand layout (sample_layout.hip): no patchify between steps.
 // What does not depend on the state (time projection, head shift / scale, text and image rows, rotary tables, sigmas) is the caller's, computed once per call.
 //
 // Workspace: mod for the 40 blocks a launch can address (so the plan does not depend on L), the two activation buffers, pred [P B S, po], one block's saved bytes

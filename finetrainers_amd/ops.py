@@ -1018,7 +1018,7 @@ def wan_patch_lora_backward(cols2, dx0, lora_a, lora_b, g_ws, grad_a, grad_b, s:
           "ftmi_wan_patch_lora_backward")
 
 
-# ---- Wan latent sampling (include/ftmi355.h: ftmi_wan_sample_*; csrc/wan_sample.hip, csrc/wan_sample_dit.hip) -------------------------------------------
+# ---- Wan latent sampling (include/ftmi355.h: ftmi_wan_sample_*; csrc/sample_layout.hip, csrc/wan_sample_dit.hip) -------------------------------------------
 def wan_sample_geometry(B: int, C: int, frames: int, height: int, width: int, Kp: int, extra_channels: int = 0, copies: int = 1, guidance: bool = True,
                         patch_size=(1, 2, 2), po: Optional[int] = None) -> "_lib.WanSampleGeometry":
     """The layout of a sampling run: latents [B, C, frames, height, width] (+ ``extra_channels``), cols [P B S, copies Kp], pred [P B, S, po]."""
@@ -1133,7 +1133,7 @@ def wan_sample(cfg, weights, cols, x, tproj, head_shift, head_scale, enc, enc_im
                                       stream_ptr()), "ftmi_wan_sample")
 
 
-# ---- CogVideoX latent sampling (include/ftmi355.h: ftmi_cog_sample_*; csrc/cog_sample.hip, csrc/cog_dit.hip) ---------------------------------------------
+# ---- CogVideoX latent sampling (include/ftmi355.h: ftmi_cog_sample_*; csrc/sample_layout.hip, csrc/cog_dit.hip) ---------------------------------------------
 def cog_sample_geometry(B: int, C: int, frames: int, height: int, width: int, patch: int = 2, patch_t: Optional[int] = None, guidance: bool = True,
                         drop: int = 0) -> "_lib.CogSampleGeometry":
     """The layout of a sampling run: latents [B, frames, C, height, width], x [B, S, Kc], cols [P B S, Kc], pred [P B, S, Kc]; ``drop``: the padded leading

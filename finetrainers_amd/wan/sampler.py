@@ -3,7 +3,7 @@
 The reference validates by running a diffusers pipeline's denoising loop over the transformer that is being trained (finetrainers/models/wan/
 base_specification.py:495-529; control_specification.py:310-377 with the control latents concatenated on the channels).  Here the loop -- DiT forward on the
 unconditional + conditional prompt, classifier-free-guidance combine, flow-match Euler update -- is ONE C call (``ftmi_wan_sample``, no host synchronisation)
-over this backend's flat-buffer model with its current adapters.  The sampler state stays in the patch embedding's operand layout (csrc/wan_sample.hip), so
+over this backend's flat-buffer model with its current adapters.  The sampler state stays in the patch embedding's operand layout (csrc/sample_layout.hip), so
 nothing is patchified between steps.  Text / image encoding and the VAE stay outside: the sampler takes embeddings and latents and returns denormalised
 latents (INTEGRATION.md shows the hand-over to the reference pipeline's VAE decode).
 

@@ -851,7 +851,7 @@ int ftmi_wan_patch_lora_forward(const ftmi_wan_patch_lora_config* cfg, const voi
 int ftmi_wan_patch_lora_backward(const ftmi_wan_patch_lora_config* cfg, const float* a_f32, const float* b_f32, const void* cols2, const void* dx0, float* g_ws,
                                  float* grad_a, float* grad_b, ftmi_stream stream);
 
-/* ---- Wan latent sampling (csrc/wan_sample.hip, csrc/wan_sample_dit.hip; DESIGN.md "Wan latent sampling") ----
+/* ---- Wan latent sampling (csrc/sample_layout.hip, csrc/wan_sample_dit.hip; DESIGN.md "Wan latent sampling") ----
  * The denoising loop of the reference's validation (finetrainers/models/wan/base_specification.py:495-529, control_specification.py:310-377 run a pipeline over
  * the transformer that is being trained) in latent space.  The sampler state lives in the patch embedding's operand layout:
  *   x     fp32 [B, S, Kc]      Kc = C pt ph pw columns in (c, pt, ph, pw) order, S tokens in (f, h, w) order
@@ -919,7 +919,7 @@ int ftmi_wan_sample(const ftmi_wan_sample_config* cfg, const ftmi_wan_sample_wei
                     const float* head_scale, const void* enc, const void* enc_img, const float* rope_cos, const float* rope_sin, const float* sigmas,
                     void* workspace, size_t workspace_bytes, ftmi_stream stream);
 
-/* ---- CogVideoX latent sampling (csrc/cog_sample.hip: the layout kernels; csrc/cog_dit.hip: the loop) ----
+/* ---- CogVideoX latent sampling (csrc/sample_layout.hip: the layout kernels; csrc/cog_dit.hip: the loop) ----
  * The denoising loop of the reference's validation (finetrainers/models/cogvideox/base_specification.py:335-364 runs CogVideoXPipeline over the transformer
  * that is being trained) in latent space, text-to-video: [upstream, unpinned] CogVideoXPipeline + CogVideoXDDIMScheduler (v-prediction, eta = 0).
  * The patch embedding's operand order and proj_out's column order are the same, (c, ph, pw) or (c, pt, ph, pw) with patch_size_t, so the state lives there:

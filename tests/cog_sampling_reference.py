@@ -1,4 +1,4 @@
-"""Torch restatement of CogVideoX latent sampling for the tests: the operand layout of csrc/cog_sample.hip, the step in fp64, the pipeline loop the GPU
+"""Torch restatement of CogVideoX latent sampling for the tests: the operand layout of csrc/sample_layout.hip, the step in fp64, the pipeline loop the GPU
 trajectory test drives ``oracle.cogvideox.CogVideoXTransformer3DModel`` with, and the oracle / MI355X model pairs.
 
 [upstream, unpinned] ``CogVideoXPipeline`` + ``CogVideoXDDIMScheduler`` (diffusers 0.33, neither is vendored): trailing timesteps, v-prediction, eta = 0,

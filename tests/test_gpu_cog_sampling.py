@@ -1,6 +1,7 @@
 """CogVideoX latent sampling on the GPU: the three layout kernels against tests/cog_sampling_reference.py (bit for bit where the arithmetic is exact, against
 fp64 where it rounds), the one-call loop against its composition from ``model.forward`` and ``ops.cog_sample_step`` bit for bit for the three geometries and
-a model without adapters, the sampler's view of live adapters, the workspace plan, and the trajectory against ``oracle.cogvideox`` in bf16 and fp32."""
+a model without adapters, the sampler's view of live adapters, the workspace plan, the trajectory against ``oracle.cogvideox`` in bf16 and fp32, and the
+Wan entry points against the CogVideoX ones on a geometry both express (one set of layout kernels, csrc/sample_layout.hip)."""
 import ctypes
 
 import pytest
@@ -345,3 +346,33 @@ def test_trajectory_against_the_oracle(models):
     print(f"[cog_sample trajectory n={N_STEPS} g=6] d_oracle {d_oracle:.3e} d_kernel {d_kernel:.3e} moved {moved:.3f}")
     assert moved > 0.1 and _rel(got, c["noise"]) > 0.1
     assert d_kernel <= 1.5 * d_oracle
+
+
+# ---- 5. one layout, two entry families -----------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("P", [1, 2])
+@pytest.mark.parametrize("B", [1, 2])
+@pytest.mark.parametrize("F_,H,W", [(1, 2, 2), (3, 4, 6), (2, 4, 8)])
+def test_wan_and_cog_entry_points_are_one_layout(F_, H, W, B, P):
+    """A geometry both families can express -- C = 16, patch (1, 2, 2), Kp = Kc = 64, one copy, no extra channels, nothing dropped -- through
+    ``wan_sample_*`` on latents [B, C, F, H, W] and through ``cog_sample_*`` on the same values permuted to [B, F, C, H, W]: the same bits.  (1, 2, 2) is one
+    token; (3, 4, 6) has runs of 12 elements that start off the 16-byte grid (the covering vectors of init, the element stores of finish); (2, 4, 8) is the
+    16-byte store path of finish.  Wan's finish runs with mean = 0, std = 1 and CogVideoX's with k = 1: x * 1 + 0 and x * 1 differ only for x = -0 (-0 + 0
+    is +0), and seeded randn draws hold no zero of either sign (asserted), so the two affines agree exactly here."""
+    from finetrainers_amd import ops
+
+    dev = _dev()
+    lat = torch.randn(B, C, F_, H, W, generator=torch.Generator().manual_seed(F_ * 11 + W + B))
+    assert bool((lat != 0).all())
+    wgeo = ops.wan_sample_geometry(B, C, F_, H, W, Kp=64, guidance=P == 2)
+    cgeo = _geo(B, P, F_, H, W, 1)
+    xw, colsw = ops.wan_sample_init(wgeo, lat.to(dev))
+    xc, colsc = ops.cog_sample_init(cgeo, lat.permute(0, 2, 1, 3, 4).contiguous().to(dev))
+    torch.cuda.synchronize()
+    assert xw.shape == xc.shape and colsw.shape == colsc.shape
+    assert torch.equal(_bits(xw.cpu()), _bits(xc.cpu())), "x"
+    assert torch.equal(_bits(colsw.cpu()), _bits(colsc.cpu())), "cols"
+    outw = ops.wan_sample_finish(wgeo, xw, torch.zeros(C, device=dev), torch.ones(C, device=dev))  # [B, C, F, H, W]
+    outc = ops.cog_sample_finish(cgeo, xw, 1.0)  # [B, F, C, H, W]
+    torch.cuda.synchronize()
+    assert torch.equal(_bits(outw.permute(0, 2, 1, 3, 4).cpu()), _bits(outc.cpu())), "finish"
+    assert torch.equal(_bits(outw.cpu()), _bits(lat.to(bf16))), "and both are the inverse of init"

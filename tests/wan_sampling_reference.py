@@ -1,4 +1,4 @@
-"""Torch restatement of the Wan latent sampler (finetrainers_amd/wan/sampler.py, csrc/wan_sample.hip): the three layout kernels -- init, step, finish -- and
+"""Torch restatement of the Wan latent sampler (finetrainers_amd/wan/sampler.py, csrc/sample_layout.hip): the three layout kernels -- init, step, finish -- and
 the denoising loop, on the CPU.  The loop here is the one the GPU trajectory test drives ``oracle.wan.WanTransformer3DModel`` with: the state is fp32 in the
 patch embedding's column order (c, pt, ph, pw), the model output arrives in proj_out's order (pt, ph, pw, c), the guidance combine and the Euler update run in
 the state's precision.  Model builders for the GPU tests live here too (the geometry of tests/test_gpu_wan_control.py)."""
