@@ -348,7 +348,7 @@ int ftmi_fp8_upcast(const void* src, void* dst, int rows, int cols, int transpos
 }
 
 int ftmi_transpose_bf16(const void* in, void* out, int rows, int cols, ftmi_stream stream) {
-    if (!in || !out) return set_error(FTMI_ERR_INVALID, "ftmi_transpose_bf16: null tensor");
+    if (!in || !out || rows < 0 || cols < 0) return set_error(FTMI_ERR_INVALID, "ftmi_transpose_bf16: null tensor or negative size");
     return transpose_bf16((const bf16_t*)in, (bf16_t*)out, rows, cols, (hipStream_t)stream);
 }
 
@@ -575,20 +575,23 @@ int ftmi_ltx_sample_cond(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, 
 int ftmi_ltx_noise_pack(const void* latents, const void* noise, const float* mean, const float* std_, const float* sigma,
                         const float* sigma_first, int first_frame_tokens, void* x_t, void* target, int B, int C, int S, ftmi_stream stream) {
     if (!latents || !noise || !mean || !std_ || !sigma || !x_t || !target) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_noise_pack: null argument");
+    if (B < 0 || C < 0 || S < 0) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_noise_pack: negative size");
     return noise_pack((const bf16_t*)latents, (const bf16_t*)noise, mean, std_, sigma, sigma_first, first_frame_tokens, (bf16_t*)x_t,
                       (bf16_t*)target, B, C, S, (hipStream_t)stream);
 }
 
 int ftmi_ddim_add_noise(const void* latents, const void* noise, const float* sqrt_alpha, const float* sqrt_one_minus_alpha, float scaling_factor,
                         void* x0, void* noisy, int B, long per_sample, ftmi_stream stream) {
-    if (!latents || !noise || !sqrt_alpha || !sqrt_one_minus_alpha || !noisy || B <= 0) return set_error(FTMI_ERR_INVALID, "ftmi_ddim_add_noise: bad argument");
+    if (!latents || !noise || !sqrt_alpha || !sqrt_one_minus_alpha || !noisy || B <= 0 || per_sample < 0)
+        return set_error(FTMI_ERR_INVALID, "ftmi_ddim_add_noise: bad argument");
     return ddim_mix((const bf16_t*)latents, (const bf16_t*)noise, sqrt_alpha, sqrt_one_minus_alpha, scaling_factor, (bf16_t*)x0, (bf16_t*)noisy, B, per_sample, 0,
                     (hipStream_t)stream);
 }
 
 int ftmi_ddim_get_velocity(const void* sample, const void* noise, const float* sqrt_alpha, const float* sqrt_one_minus_alpha, void* out, int B,
                            long per_sample, ftmi_stream stream) {
-    if (!sample || !noise || !sqrt_alpha || !sqrt_one_minus_alpha || !out || B <= 0) return set_error(FTMI_ERR_INVALID, "ftmi_ddim_get_velocity: bad argument");
+    if (!sample || !noise || !sqrt_alpha || !sqrt_one_minus_alpha || !out || B <= 0 || per_sample < 0)
+        return set_error(FTMI_ERR_INVALID, "ftmi_ddim_get_velocity: bad argument");
     return ddim_mix((const bf16_t*)sample, (const bf16_t*)noise, sqrt_alpha, sqrt_one_minus_alpha, 1.0f, nullptr, (bf16_t*)out, B, per_sample, 1, (hipStream_t)stream);
 }
 
@@ -739,10 +742,32 @@ int ftmi_mse_loss(const void* pred, const void* target, const float* weight, flo
     return mse_loss_fwd_bwd((const bf16_t*)pred, (const bf16_t*)target, weight, loss, (bf16_t*)dpred, B, per_sample, grad_scale, scratch, (hipStream_t)stream);
 }
 
+int ftmi_timestep_sinusoid(const float* t, void* out, int B, ftmi_stream stream) {
+    if (!t || !out || B < 0) return set_error(FTMI_ERR_INVALID, "ftmi_timestep_sinusoid: bad argument");
+    return timestep_sinusoid(t, (bf16_t*)out, B, (hipStream_t)stream);
+}
+
+int ftmi_small_linear(const void* x, const void* w, const void* bias, void* y, int rows, int N, int K, int silu_in, ftmi_stream stream) {
+    if (!x || !w || !y || N < 0 || K < 0) return set_error(FTMI_ERR_INVALID, "ftmi_small_linear: bad argument");
+    return small_linear((const bf16_t*)x, (const bf16_t*)w, (const bf16_t*)bias, (bf16_t*)y, rows, N, K, silu_in, 0, (hipStream_t)stream);
+}
+
+int ftmi_ada_prep(const void* tables, const void* temb, void* ada, int L, int B, int D, ftmi_stream stream) {
+    if (!tables || !temb || !ada || L < 0 || B < 0 || D < 0) return set_error(FTMI_ERR_INVALID, "ftmi_ada_prep: bad argument");
+    return ada_prep((const bf16_t*)tables, (const bf16_t*)temb, (bf16_t*)ada, L, B, D, (hipStream_t)stream);
+}
+
+int ftmi_ada_out_prep(const void* table2, const void* emb, void* ada_out, int B, int D, ftmi_stream stream) {
+    if (!table2 || !emb || !ada_out || B < 0 || D < 0) return set_error(FTMI_ERR_INVALID, "ftmi_ada_out_prep: bad argument");
+    return ada_out_prep((const bf16_t*)table2, (const bf16_t*)emb, (bf16_t*)ada_out, B, D, (hipStream_t)stream);
+}
+
 int ftmi_clip_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long n, float max_norm, float lr, float beta1,
                          float beta2, float eps, float weight_decay, int step, float* scratch, float* grad_norm_out, ftmi_stream stream) {
     if (!params || !grads || !exp_avg || !exp_avg_sq || !scratch) return set_error(FTMI_ERR_INVALID, "ftmi_clip_adamw_step: null argument");
     if (step < 1) return set_error(FTMI_ERR_INVALID, "ftmi_clip_adamw_step: step counts from 1");
+    if (n < 0) return set_error(FTMI_ERR_INVALID, "ftmi_clip_adamw_step: negative size");
+    if (n == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(scratch, 0, 2 * sizeof(float), st) != hipSuccess) return set_error(FTMI_ERR_LAUNCH, "ftmi_clip_adamw_step: memset failed");
     int rc = sumsq(grads, n, scratch, st);

@@ -49,6 +49,7 @@ __global__ void ada_prep_kernel(const bf16_t* __restrict__ tables, const bf16_t*
 }
 int ada_prep(const bf16_t* tables, const bf16_t* temb, bf16_t* ada, int L, int B, int D, hipStream_t st) {
     const long n = (long)L * B * D;
+    if (L <= 0 || B <= 0 || D <= 0) return 0;
     hipLaunchKernelGGL(ada_prep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, tables, temb, ada, L, B, D);
     return check_launch("ada_prep");
 }
@@ -68,6 +69,7 @@ __global__ void ada_out_prep_kernel(const bf16_t* __restrict__ table2, const bf1
 }
 int ada_out_prep(const bf16_t* table2, const bf16_t* emb, bf16_t* ada_out, int B, int D, hipStream_t st) {
     const long n = (long)B * D;
+    if (B <= 0 || D <= 0) return 0;
     hipLaunchKernelGGL(ada_out_prep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, table2, emb, ada_out, B, D);
     return check_launch("ada_out_prep");
 }
@@ -416,6 +418,7 @@ __global__ __launch_bounds__(256) void noise_pack_kernel(const bf16_t* __restric
 }
 int noise_pack(const bf16_t* latents, const bf16_t* noise, const float* mean, const float* std_, const float* sigma,
                const float* sigma_first, int first_frame_tokens, bf16_t* xt, bf16_t* target, int B, int C, int S, hipStream_t st) {
+    if (B <= 0 || C <= 0 || S <= 0) return 0;  // nothing to write: no launch (an empty grid is a launch error)
     dim3 grid((S + 63) / 64, (C + 63) / 64, B);
     hipLaunchKernelGGL(noise_pack_kernel, grid, dim3(256), 0, st, latents, noise, mean, std_, sigma, sigma_first, first_frame_tokens, xt,
                        target, C, S);
@@ -460,6 +463,7 @@ __global__ __launch_bounds__(64) void mse_loss_finish_kernel(const float* __rest
 }
 int mse_loss_fwd_bwd(const bf16_t* pred, const bf16_t* target, const float* weight, float* loss, bf16_t* dpred, int B, long per_sample,
                      float grad_scale, float* partials, hipStream_t st) {
+    if (B <= 0 || per_sample <= 0) return set_error(FTMI_ERR_INVALID, "mse_loss: the mean over no element is not defined");
     if (per_sample % 8) return set_error(FTMI_ERR_UNSUPPORTED, "mse_loss: per-sample size % 8");
     long blocks = (per_sample / 8 + 255) / 256;
     if (blocks > FTMI_MSE_SCRATCH_FLOATS_PER_SAMPLE) blocks = FTMI_MSE_SCRATCH_FLOATS_PER_SAMPLE;
@@ -484,6 +488,7 @@ __global__ void timestep_sinusoid_kernel(const float* __restrict__ tval, bf16_t*
     out[(long)b * 256 + k] = f2bf(k < 128 ? cosf(a) : sinf(a));
 }
 int timestep_sinusoid(const float* tval, bf16_t* out, int B, hipStream_t st) {
+    if (B <= 0) return 0;
     hipLaunchKernelGGL(timestep_sinusoid_kernel, dim3(B), dim3(256), 0, st, tval, out, B);
     return check_launch("timestep_sinusoid");
 }
@@ -522,6 +527,8 @@ int small_linear(const bf16_t* x, const bf16_t* W, const bf16_t* bias, bf16_t* y
                  hipStream_t st) {
     (void)silu_out;
     if (K % 8) return set_error(FTMI_ERR_UNSUPPORTED, "small_linear: K % 8");
+    if (rows < 1 || rows > 8) return set_error(FTMI_ERR_UNSUPPORTED, "small_linear: rows must be 1..8");
+    if (N <= 0) return 0;
     dim3 grid((N + 3) / 4);
 #define FTMI_SL(R)                                                                                             \
     case R:                                                                                                    \
@@ -592,6 +599,7 @@ __global__ __launch_bounds__(256) void clip_scale_kernel(float* __restrict__ g, 
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) g[i] *= coef;
 }
 int clip_scale(float* g, long n, const float* sumsq_in, float max_norm, float* grad_norm_out, hipStream_t st) {
+    if (n <= 0) return 0;
     long blocks = (n + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(clip_scale_kernel, dim3((unsigned)blocks), dim3(256), 0, st, g, n, sumsq_in, max_norm, grad_norm_out);
@@ -622,8 +630,10 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
 }
 int adamw_clip_step(float* p, const float* g, float* m, float* v, long n, const float* sumsq_in, float max_norm, float lr, float beta1,
                     float beta2, float eps, float wd, int step, float* grad_norm_out, hipStream_t st) {
-    const float bc1 = 1.0f - powf(beta1, (float)step);
-    const float bc2_sqrt = sqrtf(1.0f - powf(beta2, (float)step));
+    if (n <= 0) return 0;
+    // bias corrections in double from the fp32 betas, like adamw_bf16_step: powf alone is off by up to 7e-6 relative in 1 - beta2^step at small steps
+    const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
+    const float bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
     long blocks = (n + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p, g, m, v, n, sumsq_in, max_norm, lr, beta1, beta2, eps, wd,
@@ -644,6 +654,7 @@ __global__ __launch_bounds__(256) void adamw_bf16_kernel(bf16_t* __restrict__ p,
     if (sumsq_in) {
         const float total_norm = sqrtf(*sumsq_in);
         coef = fminf(max_norm / (total_norm + 1e-6f), 1.0f);
+        if (max_norm <= 0.f) coef = 1.0f;  // no clip, as in adamw_kernel and clip_scale
         if (grad_norm_out && blockIdx.x == 0 && threadIdx.x == 0) *grad_norm_out = total_norm;
     }
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
@@ -707,6 +718,7 @@ __global__ __launch_bounds__(256) void ddim_mix_kernel(const bf16_t* __restrict_
 int ddim_mix(const bf16_t* a, const bf16_t* b, const float* sa, const float* so, float scale, bf16_t* x0_out, bf16_t* out, int B, long per_sample,
              int mode, hipStream_t st) {
     if (per_sample % 8) return set_error(FTMI_ERR_UNSUPPORTED, "ddim_mix: elements per sample must be a multiple of 8");
+    if (B <= 0 || per_sample <= 0) return 0;
     long blocks = (per_sample / 8 + 255) / 256;
     if (blocks > 1024) blocks = 1024;
     hipLaunchKernelGGL(ddim_mix_kernel, dim3((unsigned)blocks, B), dim3(256), 0, st, a, b, sa, so, scale, x0_out, out, per_sample, mode);
@@ -738,6 +750,7 @@ __global__ __launch_bounds__(256) void posterior_sample_kernel(const bf16_t* __r
 }
 int posterior_sample(const bf16_t* moments, const bf16_t* eps, bf16_t* out, int B, long half, hipStream_t st) {
     if (half % 8) return set_error(FTMI_ERR_UNSUPPORTED, "posterior_sample: elements per sample must be a multiple of 8");
+    if (B <= 0 || half <= 0) return 0;
     long blocks = (half / 8 + 255) / 256;
     if (blocks > 1024) blocks = 1024;
     hipLaunchKernelGGL(posterior_sample_kernel, dim3((unsigned)blocks, B), dim3(256), 0, st, moments, eps, out, half);
@@ -836,6 +849,7 @@ int lora_split(const LoraSplitArgs& a, hipStream_t st) {
     return check_launch("lora_split");
 }
 int transpose_bf16(const bf16_t* in, bf16_t* out, int rows, int cols, hipStream_t st) {
+    if (rows <= 0 || cols <= 0) return 0;
     dim3 grid((cols + 31) / 32, (rows + 31) / 32, 1);
     hipLaunchKernelGGL(transpose_cast_kernel<bf16_t>, grid, dim3(256), 0, st, in, (bf16_t*)nullptr, out, rows, cols, 0L, 0L, 0L);
     return check_launch("transpose_bf16");

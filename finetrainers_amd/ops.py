@@ -715,6 +715,49 @@ def posterior_sample(moments, eps):
     return out
 
 
+# ---- the LTX time-embedding chain one launcher at a time (include/ftmi355.h; the forward passes run it inside the C library) --------------------
+def timestep_sinusoid(t: torch.Tensor) -> torch.Tensor:
+    """t fp32 [B] -> bf16 [B, 256] = [cos | sin] of t * 10000^(-j / 128)."""
+    require_gpu_tensor(t, "t", torch.float32)
+    out = torch.empty((t.numel(), 256), dtype=bf16, device=t.device)
+    check(_lib.load().ftmi_timestep_sinusoid(ptr(t), ptr(out), t.numel(), stream_ptr()), "ftmi_timestep_sinusoid")
+    return out
+
+
+def small_linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, silu_in: bool = False) -> torch.Tensor:
+    """x [rows <= 8, K], w [N, K], bias [N] (bf16) -> bf16 [rows, N] = (silu(x) if silu_in else x) w^T + bias."""
+    for t, n in ((x, "x"), (w, "w")) + (((bias, "bias"),) if bias is not None else ()):
+        require_gpu_tensor(t, n, bf16)
+    x, w = x.contiguous(), w.contiguous()
+    if w.shape[1] != x.shape[1] or (bias is not None and bias.numel() != w.shape[0]):
+        raise ValueError(f"small_linear: x {tuple(x.shape)}, w {tuple(w.shape)} and the bias do not fit")
+    out = torch.empty((x.shape[0], w.shape[0]), dtype=bf16, device=x.device)
+    check(_lib.load().ftmi_small_linear(ptr(x), ptr(w), ptr(bias), ptr(out), x.shape[0], w.shape[0], x.shape[1], int(silu_in), stream_ptr()), "ftmi_small_linear")
+    return out
+
+
+def ada_prep(tables: torch.Tensor, temb: torch.Tensor) -> torch.Tensor:
+    """tables [L, 6, D], temb [B, 6, D] (bf16) -> ada [L, B, 8, D]: table + temb in slots 0..5, 1 + slot 1 and 1 + slot 4 in slots 6, 7."""
+    require_gpu_tensor(tables, "tables", bf16)
+    require_gpu_tensor(temb, "temb", bf16)
+    tables, temb = tables.contiguous(), temb.contiguous()
+    (L, _, D), B = tables.shape, temb.shape[0]
+    out = torch.empty((L, B, 8, D), dtype=bf16, device=tables.device)
+    check(_lib.load().ftmi_ada_prep(ptr(tables), ptr(temb), ptr(out), L, B, D, stream_ptr()), "ftmi_ada_prep")
+    return out
+
+
+def ada_out_prep(table2: torch.Tensor, emb: torch.Tensor) -> torch.Tensor:
+    """table2 [2, D], emb [B, D] (bf16) -> [B, 3, D]: shift, scale, 1 + scale of the output norm."""
+    require_gpu_tensor(table2, "table2", bf16)
+    require_gpu_tensor(emb, "emb", bf16)
+    table2, emb = table2.contiguous(), emb.contiguous()
+    B, D = emb.shape
+    out = torch.empty((B, 3, D), dtype=bf16, device=emb.device)
+    check(_lib.load().ftmi_ada_out_prep(ptr(table2), ptr(emb), ptr(out), B, D, stream_ptr()), "ftmi_ada_out_prep")
+    return out
+
+
 MSE_SCRATCH_FLOATS_PER_SAMPLE = 256  # FTMI_MSE_SCRATCH_FLOATS_PER_SAMPLE of include/ftmi355.h
 
 

@@ -249,7 +249,7 @@ int ftmi_gemm_tn_ex(const ftmi_gemm_tn_args* args, ftmi_stream stream);
  * the input-gradient GEMMs read.  Called per block right before it runs; 1 byte read + 2 bytes written per weight. */
 int ftmi_fp8_upcast(const void* src, void* dst, int rows, int cols, int transpose, ftmi_stream stream);
 /* out[cols,rows] = in[rows,cols]^T (bf16); used once at load time for the dgrad copies of frozen weights */
-int ftmi_transpose_bf16(const void* in, void* out, int rows, int cols, ftmi_stream stream);
+int ftmi_transpose_bf16(const void* in, void* out, int rows, int cols, ftmi_stream stream);  /* rows or cols == 0: returns 0 without a launch; negative: FTMI_ERR_INVALID */
 
 /* Row-wise building blocks (width D = 2048; one wavefront per token row; every op of the eager chain fused in registers with a bf16
  * round wherever the reference's eager bf16 graph materialises a tensor).
@@ -390,7 +390,8 @@ int ftmi_ltx_backward_range(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* 
                             int accumulate, ftmi_stream stream);
 
 /* latents, noise [B,C,F*H*W] bf16; mean,std fp32 [C]; sigma fp32 [B]; sigma_first fp32 [B] or NULL (first-frame
- * conditioning branch: tokens < first_frame_tokens use it) -> x_t, target [B,S,C] bf16 */
+ * conditioning branch: tokens < first_frame_tokens use it) -> x_t, target [B,S,C] bf16.
+ * B, C or S == 0: returns 0 without a launch; a negative size is FTMI_ERR_INVALID. */
 int ftmi_ltx_noise_pack(const void* latents, const void* noise, const float* mean, const float* std_, const float* sigma,
                         const float* sigma_first, int first_frame_tokens, void* x_t, void* target, int B, int C, int S,
                         ftmi_stream stream);
@@ -460,6 +461,7 @@ int ftmi_ltx_sample_cond(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, 
  *   add_noise:    x0 = bf16(latents * scaling_factor)  (the training target, may be NULL);  noisy = bf16(bf16(sa x0) + bf16(so noise))
  *   get_velocity: out = bf16(bf16(sa noise) - bf16(so sample))      (the reference calls it as get_velocity(model_out, noisy, t))
  * The loss weight 1 / (1 - alphas_cumprod[t]) (utils/diffusion.py:125-128) goes through ftmi_mse_loss's per-sample weight.
+ * per_sample % 8 == 0 (FTMI_ERR_UNSUPPORTED otherwise); B <= 0 or per_sample < 0: FTMI_ERR_INVALID; per_sample == 0: returns 0 without a launch.
  * ------------------------------------------------------------------------------------------------------------ */
 int ftmi_ddim_add_noise(const void* latents, const void* noise, const float* sqrt_alpha, const float* sqrt_one_minus_alpha,
                         float scaling_factor, void* x0, void* noisy, int B, long per_sample, ftmi_stream stream);
@@ -531,20 +533,36 @@ int ftmi_cog_unpatchify(const void* tokens, void* latents, int B, int F, int C, 
 /* Precomputed-latent path (finetrainers/trainer/sft_trainer/trainer.py:374: --enable_precomputation => compute_posterior = False):
  * moments [B, 2, per_sample] bf16 = the VAE posterior (mean | logvar) as finetrainers-precomputed-data stores it, eps [B, per_sample] bf16
  * the N(0,1) draw; out = mean + exp(0.5 * clamp(logvar, -30, 20)) * eps, one bf16 rounding per torch op of
- * models/ltx_video/base_specification.py:285-289 ([upstream] diffusers DiagonalGaussianDistribution.sample). */
+ * models/ltx_video/base_specification.py:285-289 ([upstream] diffusers DiagonalGaussianDistribution.sample).
+ * per_sample % 8 == 0; B <= 0 or per_sample <= 0: FTMI_ERR_INVALID. */
 int ftmi_posterior_sample(const void* moments, const void* eps, void* out, int B, long per_sample, ftmi_stream stream);
 
 /* loss (device fp32 scalar) = mean_b mean w_b (pred-target)^2 ; dpred = d(loss*grad_scale)/dpred (bf16), may be NULL.
  * scratch: caller-owned device memory, >= FTMI_MSE_SCRATCH_FLOATS_PER_SAMPLE * B floats (per-workgroup partial sums, added in a fixed order:
- * the loss is bitwise reproducible); the library allocates nothing on this path, so the call is legal inside a stream capture. */
+ * the loss is bitwise reproducible); the library allocates nothing on this path, so the call is legal inside a stream capture.
+ * per_sample % 8 == 0; B <= 0 or per_sample <= 0: FTMI_ERR_INVALID (the mean over no element is not defined; nothing is launched or written). */
 #define FTMI_MSE_SCRATCH_FLOATS_PER_SAMPLE 256
 int ftmi_mse_loss(const void* pred, const void* target, const float* weight, float* loss, void* dpred, int B, long per_sample,
                   float grad_scale, float* scratch, ftmi_stream stream);
 
+/* ---- The LTX time-embedding chain, one launcher per call (used by the contract tests only; the forward passes call the launchers directly).  All tensors bf16,
+ * dense, 16-byte aligned.  A zero size returns 0 without a launch, a negative one is FTMI_ERR_INVALID.
+ *   timestep_sinusoid  t fp32 [B] -> out [B, 256] = bf([cos(t f_j) | sin(t f_j)]), f_j = expf(-ln(10000) j / 128), j < 128
+ *   small_linear       y [rows, N] = bf(sum_k xin[r][k] w[n][k] + bias[n]), xin = silu_in ? bf(silu(x)) : x;  x [rows, K], w [N, K], bias [N] or NULL;
+ *                      rows 1..8 and K % 8 == 0 (FTMI_ERR_UNSUPPORTED otherwise)
+ *   ada_prep           tables [L, 6, D], temb [B, 6, D] -> ada [L, B, 8, D]: slots 0..5 = bf(table + temb), 6 = bf(1 + slot 1), 7 = bf(1 + slot 4)
+ *   ada_out_prep       table2 [2, D], emb [B, D] -> ada_out [B, 3, D]: shift = bf(table2[0] + emb), scale = bf(table2[1] + emb), bf(1 + scale) */
+int ftmi_timestep_sinusoid(const float* t, void* out, int B, ftmi_stream stream);
+int ftmi_small_linear(const void* x, const void* w, const void* bias, void* y, int rows, int N, int K, int silu_in, ftmi_stream stream);
+int ftmi_ada_prep(const void* tables, const void* temb, void* ada, int L, int B, int D, ftmi_stream stream);
+int ftmi_ada_out_prep(const void* table2, const void* emb, void* ada_out, int B, int D, ftmi_stream stream);
+
 /* Global L2 clip (max_norm <= 0 disables) + AdamW over flat fp32 buffers; scratch: >= FTMI_CLIP_SCRATCH_FLOATS floats (device).
  * The norm is reduced in a fixed order (block partials in scratch, last block adds them): the same gradients give the same
  * bits on every call and on every rank, so data-parallel replicas keep identical clip coefficients.
- * grad_norm_out (device fp32, may be NULL) receives the pre-clip total norm. */
+ * grad_norm_out (device fp32, may be NULL) receives the pre-clip total norm.
+ * The bias corrections 1 - beta^step are computed in double from the fp32 betas and rounded to fp32 once (as ftmi_adamw_bf16_step does).
+ * n == 0: returns 0 without a launch, nothing is written (grad_norm_out included); n < 0: FTMI_ERR_INVALID. */
 #define FTMI_CLIP_SCRATCH_FLOATS 2050
 int ftmi_clip_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long n, float max_norm, float lr,
                          float beta1, float beta2, float eps, float weight_decay, int step, float* scratch, float* grad_norm_out,
@@ -553,7 +571,8 @@ int ftmi_clip_adamw_step(float* params, const float* grads, float* exp_avg, floa
 /* In-place global L2 clip of a flat fp32 gradient buffer: grads *= min(1, max_norm / (norm + 1e-6)) (finetrainers/utils/torch.py:99-161).
  * The reference loop clips after EVERY backward (trainer/sft_trainer/trainer.py:487-492), also on the micro-steps of a gradient-
  * accumulation window where no optimiser step follows; ftmi_clip_adamw_step covers the stepping micro-step, this call the others.
- * scratch: >= FTMI_CLIP_SCRATCH_FLOATS floats; grad_norm_out (may be NULL) receives the pre-clip norm; order-fixed reduction. */
+ * scratch: >= FTMI_CLIP_SCRATCH_FLOATS floats; grad_norm_out (may be NULL) receives the pre-clip norm; order-fixed reduction.
+ * max_norm <= 0 disables the clip (the norm is still written); n <= 0: FTMI_ERR_INVALID. */
 int ftmi_clip_grad_norm(float* grads, long n, float max_norm, float* scratch, float* grad_norm_out, ftmi_stream stream);
 
 /* HunyuanVideo ([upstream] diffusers Attention(qk_norm = "rms_norm") + HunyuanVideoAttnProcessor2_0, restated in oracle/hunyuan.py): q / k
@@ -791,14 +810,17 @@ int ftmi_wan_lora_ffn_block_backward(const ftmi_wan_lora_ffn_block_config* cfg, 
 
 /* Sum of squares of a flat fp32 gradient (shard): scratch[0] <- sum g^2 (order-fixed; scratch >= FTMI_CLIP_SCRATCH_FLOATS floats).  Sharded training
  * all-reduces scratch[0] over the ranks before the optimiser call below (the reference's clip_grad_norm_ over DTensor shards, utils/torch.py:99-161). */
+/* n <= 0: FTMI_ERR_INVALID. */
 int ftmi_grad_sumsq(const float* grads, long n, float* scratch, ftmi_stream stream);
 /* In-place clip of a flat fp32 gradient (shard) by a global norm given as a device sum of squares: grads *= min(1, max_norm / (sqrt(*sumsq) + 1e-6)).
  * The non-stepping micro-steps of a gradient-accumulation window in sharded training (the reference clips after EVERY backward,
- * trainer/sft_trainer/trainer.py:487-492); the stepping micro-step clips inside ftmi_adamw_bf16_step. */
+ * trainer/sft_trainer/trainer.py:487-492); the stepping micro-step clips inside ftmi_adamw_bf16_step.
+ * max_norm <= 0 disables the clip; n == 0: returns 0 without a launch (grad_norm_out not written); n < 0: FTMI_ERR_INVALID. */
 int ftmi_clip_by_sumsq(float* grads, long n, const float* sumsq, float max_norm, float* grad_norm_out, ftmi_stream stream);
 /* torch.optim.AdamW on bf16 parameters with bf16 moments (the reference's bf16 full fine-tune, optimizer.py:17-46): every torch op of the update is one
  * fp32 computation rounded to bf16.  grads: fp32 (the reduce-scattered shard), multiplied by min(1, max_norm / (sqrt(*sumsq) + 1e-6)) and rounded to
- * bf16 first (sumsq NULL: no clip).  grad_norm_out (may be NULL) receives sqrt(*sumsq). */
+ * bf16 first (sumsq NULL or max_norm <= 0: no clip, the rule of ftmi_clip_adamw_step; a coefficient >= 1 is not applied either).  grad_norm_out
+ * (may be NULL) receives sqrt(*sumsq) when sumsq is given.  n == 0: returns 0 without a launch; n < 0: FTMI_ERR_INVALID. */
 int ftmi_adamw_bf16_step(void* params, const float* grads, void* exp_avg, void* exp_avg_sq, long n, const float* sumsq, float max_norm, float lr,
                          float beta1, float beta2, float eps, float weight_decay, int step, float* grad_norm_out, ftmi_stream stream);
 
@@ -811,7 +833,8 @@ int ftmi_lora_refresh_n(const float* a_f32, const float* b_f32, void* lora_a_sp,
 
 /* The same split for ONE fp32 matrix w [rows, cols] (building block of ftmi_linear_lora_fwd/_bwd callers): any of the four outputs
  * may be NULL.  sp [2 rows, cols]: (hi, lo) row planes interleaved per 32 rows; ext [rows, 3 cols]: [hi | hi | lo];
- * t_sp [2 cols, rows], t_ext [cols, 3 rows]: the same two layouts of w^T. */
+ * t_sp [2 cols, rows], t_ext [cols, 3 rows]: the same two layouts of w^T.  sp needs rows % 32 == 0, t_sp cols % 32 == 0 (FTMI_ERR_UNSUPPORTED).
+ * rows <= 0 or cols <= 0 (ftmi_lora_refresh_n: L, r or D <= 0): returns 0 without a launch. */
 int ftmi_lora_split(const float* w, int rows, int cols, void* sp, void* ext, void* t_sp, void* t_ext, ftmi_stream stream);
 
 /* ---- Wan control LoRA outside the blocks (csrc/wan_control.hip) ----
