@@ -16,6 +16,7 @@
 // Three kernels: forward (O, LSE), backward dQ (one workgroup per 128 queries, loops over keys; also produces
 // delta = rowsum(dO * O)), backward dK/dV (one workgroup per 128 keys, loops over queries).  Scores are recomputed in both
 // backward kernels, so no atomics are needed and results are deterministic.
+#include <cstdio>
 #include <type_traits>
 
 #include "common.hip.h"
@@ -430,10 +431,32 @@ static int attn_pl_switch() {  // read once at the first attention launch (no ge
 #include "../../tools/experimental/attention_experimental_7_dq128_pl.hip.h"  // pipelined dQ at head_dim 128: bit-identical, no faster (EXPERIMENT, not shipped)
 #endif
 
+// Every kernel of this file reads and writes q, k, v, out, dout, dq, dk, dv in 16-byte pieces (s16x8 / u32x4 row fragments, global_load_lds_dwordx4 and
+// buffer_load_dwordx4 tile DMA, the u32x4 stores of store_rows_via_lds) at base + b * batch stride + h * head stride + s * token stride + a multiple of 8
+// elements: the base pointer and all three strides of every tensor a launch touches must keep that alignment.  The key bias is read one fp32 at a time:
+// no rule beyond its own 4 bytes.  Returns the name of the first tensor that breaks the rule, or nullptr.
+static const char* attn_misaligned(const AttnArgs& a, bool bwd) {
+    auto bad = [](const void* p, long sb, long sh, long ss) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0 || (sb % 8) || (sh % 8) || (ss % 8); };
+    if (bad(a.q, a.q_sb, a.q_sh, a.q_ss)) return "q";
+    if (bad(a.k, a.k_sb, a.k_sh, a.k_ss)) return "k";
+    if (bad(a.v, a.v_sb, a.v_sh, a.v_ss)) return "v";
+    if (bad(a.o, a.o_sb, a.o_sh, a.o_ss)) return "out";
+    if (!bwd) return nullptr;
+    if (bad(a.dout, a.do_sb, a.do_sh, a.do_ss)) return "dout";
+    if (bad(a.dq, a.dq_sb, a.dq_sh, a.dq_ss)) return "dq";
+    if (bad(a.dk, a.dk_sb, a.dk_sh, a.dk_ss)) return "dk";
+    if (bad(a.dv, a.dv_sb, a.dv_sh, a.dv_ss)) return "dv";
+    return nullptr;
+}
+static int attn_refuse_misaligned(const char* who, const char* tensor) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "%s: %s: base pointer and batch / head / token strides must keep 16-byte alignment", who, tensor);
+    return set_error(FTMI_ERR_INVALID, msg);
+}
+
 int attn_fwd(const AttnArgs& a, hipStream_t st) {
     if (a.B <= 0 || a.H <= 0 || a.Sq <= 0 || a.Sk <= 0) return set_error(FTMI_ERR_INVALID, "attn_fwd: empty problem");
-    if ((a.q_ss % 8) || (a.k_ss % 8) || (a.v_ss % 8) || (a.o_ss % 8))
-        return set_error(FTMI_ERR_INVALID, "attn_fwd: token strides must keep 16-byte alignment");
+    if (const char* bad = attn_misaligned(a, false)) return attn_refuse_misaligned("attn_fwd", bad);
     dim3 grid(((a.Sq + 127) / 128) * a.H * a.B);
     ProfScope prof(PROF_ATTN_FWD, 4.0 * a.B * a.H * (double)a.Sq * a.Sk * a.d, st);
 #ifdef FTMI_EXPERIMENTAL
@@ -450,7 +473,7 @@ int attn_fwd(const AttnArgs& a, hipStream_t st) {
     }
 #endif
     // lazy rescale + single-statement row max: 148 us against 159 us for the exact running max (cfg-2 self-attention, profiles/README.md)
-    if (a.d == 128) {  // Wan / HunyuanVideo head size: forward only so far
+    if (a.d == 128) {  // Wan / HunyuanVideo head size
         static const bool ok =
             hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_kernel<true, AF_LAZY | AF_MAX16, 2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, kFwdLds128) == hipSuccess &&
             hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_kernel<false, AF_LAZY | AF_MAX16 | AF_RAGGED, 2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, kFwdLds128) == hipSuccess &&
@@ -1340,6 +1363,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq2_kernel(AttnArgs a) {
 int attn_bwd(const AttnArgs& a, hipStream_t st) {
     if (a.B <= 0 || a.H <= 0 || a.Sq <= 0 || a.Sk <= 0) return set_error(FTMI_ERR_INVALID, "attn_bwd: empty problem");
     if (!a.lse2 || !a.delta || !a.dout || !a.o) return set_error(FTMI_ERR_INVALID, "attn_bwd: missing lse/delta/dout/out");
+    if (const char* bad = attn_misaligned(a, true)) return attn_refuse_misaligned("attn_bwd", bad);  // (ahead of the head_dim 128 branch: both head sizes)
     if (a.d == 128) {
         // head_dim 128 (Wan / HunyuanVideo): dQ with 32 query rows per wave (also publishes delta), then dV and dK in two passes of the key-major loop
         constexpr int kDq128 = 2 * 32768 + 2 * 256, kDkv128 = 2 * 32768 + 2 * 512;
@@ -1394,8 +1418,6 @@ int attn_bwd(const AttnArgs& a, hipStream_t st) {
         hipLaunchKernelGGL((attn_bwd_dkdv_kernel<2, 1>), gk, dim3(256), kDkv128, st, a);
         return check_launch("attn_bwd_dkdv");
     }
-    if ((a.q_ss % 8) || (a.k_ss % 8) || (a.v_ss % 8) || (a.o_ss % 8) || (a.do_ss % 8) || (a.dq_ss % 8) || (a.dk_ss % 8) || (a.dv_ss % 8))
-        return set_error(FTMI_ERR_INVALID, "attn_bwd: token strides must keep 16-byte alignment");
     ProfScope prof(PROF_ATTN_BWD, 10.0 * a.B * a.H * (double)a.Sq * a.Sk * 64, st);  // algorithmic: 5 matmuls (2.5x forward)
     // dQ first: it also computes delta = rowsum(dO * O) for its rows and publishes it for the dK/dV kernel
 #ifdef FTMI_EXPERIMENTAL

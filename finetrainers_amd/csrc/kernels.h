@@ -185,7 +185,7 @@ int fp8_upcast(const uint8_t* src, bf16_t* dst, int rows, int cols, int transpos
 // ---- attention -----------------------------------------------------------------------------------
 struct AttnArgs {
     int B = 0, H = 0, Sq = 0, Sk = 0;
-    int d = 64;  // head dim: 64 (forward + backward) or 128 (forward)
+    int d = 64;  // head dim: 64 or 128 (forward and backward)
     // element strides (d contiguous)
     const bf16_t* q = nullptr;
     long q_sb = 0, q_sh = 0, q_ss = 0;

@@ -45,14 +45,25 @@ def _desc(q, k, v, o, scale, dout=None, dq=None, dk=None, dv=None, key_bias=None
     return desc
 
 
+def _placed(t: Optional[torch.Tensor], shape, name: str, like: torch.Tensor) -> torch.Tensor:
+    """An output the caller placed itself (a [B, H, S, head_dim] bf16 view, head_dim contiguous), or a fresh one laid out as [B, S, H, head_dim]."""
+    if t is None:
+        B, H, S, d = shape
+        return torch.empty((B, S, H, d), dtype=bf16, device=like.device).permute(0, 2, 1, 3)
+    if tuple(t.shape) != tuple(shape) or t.dtype != bf16 or t.device != like.device:
+        raise ValueError(f"{name} must be a [B, H, S, head_dim] bf16 view on the inputs' device")
+    return t
+
+
 def attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_bias: Optional[torch.Tensor] = None,
-             scale: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """q,k,v [B,H,S,64] bf16 (strided views allowed).  Returns (out [B,H,Sq,64] laid out as [B,Sq,H,64], lse [B,H,Sq])."""
+             scale: Optional[float] = None, out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """q,k,v [B,H,S,64 | 128] bf16 (strided views allowed).  Returns (out [B,H,Sq,d] laid out as [B,Sq,H,d], lse [B,H,Sq]).  ``out``: an existing
+    [B, H, Sq, d] bf16 view (head_dim contiguous) that receives the result instead."""
     for n, t in (("query", q), ("key", k), ("value", v)):
         require_gpu_tensor(t, n, bf16)
     B, H, Sq, d = q.shape
     scale = (1.0 / d**0.5) if scale is None else scale
-    out = torch.empty((B, Sq, H, d), dtype=bf16, device=q.device).permute(0, 2, 1, 3)
+    out = _placed(out, (B, H, Sq, d), "attn_fwd: out", q)
     lse = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
     if key_bias is not None:
         require_gpu_tensor(key_bias, "key_bias", torch.float32)
@@ -61,15 +72,16 @@ def attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_bias: Option
     return out, lse
 
 
-def attn_bwd(q, k, v, out, lse, dout, key_bias=None, scale=None, dv_out=None):
-    """``dv_out``: an existing [B, H, Sk, d] bf16 view (head_dim contiguous) that receives dV, e.g. the value third of a fused d(q|k|v) buffer."""
+def attn_bwd(q, k, v, out, lse, dout, key_bias=None, scale=None, dv_out=None, dq=None, dk=None):
+    """``dv_out`` / ``dq`` / ``dk``: existing [B, H, S, d] bf16 views (head_dim contiguous) that receive dV / dQ / dK, e.g. the thirds of a fused
+    d(q|k|v) buffer."""
     B, H, Sq, d = q.shape
     Sk = k.shape[2]
     scale = (1.0 / d**0.5) if scale is None else scale
     if dout.stride(3) != 1:
         dout = dout.contiguous()
-    dq = torch.empty((B, Sq, H, d), dtype=bf16, device=q.device).permute(0, 2, 1, 3)
-    dk = torch.empty((B, Sk, H, d), dtype=bf16, device=q.device).permute(0, 2, 1, 3)
+    dq = _placed(dq, (B, H, Sq, d), "attn_bwd: dq", q)
+    dk = _placed(dk, (B, H, Sk, d), "attn_bwd: dk", q)
     dv = torch.empty((B, Sk, H, d), dtype=bf16, device=q.device).permute(0, 2, 1, 3) if dv_out is None else dv_out
     if dv.shape != (B, H, Sk, d) or dv.dtype != bf16:
         raise ValueError("attn_bwd: dv_out must be a [B, H, Sk, head_dim] bf16 view")

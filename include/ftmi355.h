@@ -70,7 +70,12 @@ int ftmi_prof_summary(int kernel_class, double* sampled_ms, long* sampled_launch
  * base + b*stride[0] + h*stride[1] + s*stride[2] (strides in elements).  lse: fp32 [B,H,Sq] (log2 domain,
  * written by fwd, read by bwd).  key_bias: optional fp32 additive bias per (batch, head, key) (an attn_mask that broadcasts over
  * queries; desc.bias_strides = {Sk, 0} for the usual [B,Sk] mask shared by the heads), NULL for none.  A bias of -inf removes the key
- * (softmax weight exactly 0).  Non-causal, no dropout.
+ * (softmax weight exactly 0); a row whose keys ALL carry -inf has no softmax: its out row is NaN (0 / 0) and its lse -inf -- the provider
+ * never sends one (the text mask keeps at least one token).  Non-causal, no dropout.
+ * Refused with FTMI_ERR_INVALID before anything is launched: B, H, Sq or Sk <= 0 ("empty problem"); a null tensor; for every bf16 tensor of the call
+ * (fwd: q, k, v, out; bwd also dout, dq, dk, dv -- at head_dim 64 and 128 alike) a base pointer that is not 16-byte aligned or a batch, head or token
+ * stride that is not a multiple of 8 elements (the kernels move rows in 16-byte pieces; the message names the tensor).  The key bias is read one fp32
+ * at a time: any strides, 4-byte alignment.  FTMI_ERR_UNSUPPORTED: desc.d other than 64 or 128.
  * ------------------------------------------------------------------------------------------------------------ */
 typedef struct {
     int B, H, Sq, Sk, d;
@@ -92,7 +97,10 @@ int ftmi_attn_bwd(const ftmi_attn_desc* desc, const void* q, const void* k, cons
  *   fwd: out = bf16(float(out_first) + float(bf16(softmax(q k^T scale) v))), lse [B,H,Sq] of THIS context written; out_first has desc.o_strides
  *   dq:  dq  = bf16(float(dq_first)  + float(bf16(dq of this context))); reads lse and dout; dq_first has desc.dq_strides and may be dq itself
  * rowsum(dO * O) of this context is formed inside the dq kernel (no output of this context alone is kept).  There is no dK / dV: the only caller's image
- * keys and values are frozen.  Keys past Sk are never read. */
+ * keys and values are frozen.  Keys past Sk are never read.
+ * Refused before anything is launched: desc.d != 128 and desc.Sk > 320 (FTMI_ERR_UNSUPPORTED); Sk <= 0, H <= 0, negative B or Sq, a null tensor, and -- as
+ * for ftmi_attn_fwd / ftmi_attn_bwd -- a base pointer off 16 bytes or a batch / head / token stride that is no multiple of 8 elements, for q, k, v and for
+ * out_first / out (fwd), dout / dq_first / dq (dq) (FTMI_ERR_INVALID).  B == 0 or Sq == 0 returns 0 without a launch. */
 int ftmi_attn_ctx2_fwd(const ftmi_attn_desc* desc, const void* q, const void* k, const void* v, const void* out_first, void* out, float* lse,
                        ftmi_stream stream);
 int ftmi_attn_ctx2_dq(const ftmi_attn_desc* desc, const void* q, const void* k, const void* v, const float* lse, const void* dout, const void* dq_first,
