@@ -224,19 +224,28 @@ class DataParallelBackend:
 
 class GradBucketReducer:
     """Bucketed, overlapped gradient exchange of the DP step -- the role of DDP's reducer (``replicate(bucket_cap_mb=100)``,
-    finetrainers/parallel/ptd.py:462-463) without parameter hooks: the DiT backward runs in block ranges
-    (``ftmi_ltx_backward_range``) and reports each range as soon as its LoRA gradients are final; the slices of the flat fp32
-    gradient buffer are all-reduced (AVG) right away on RCCL's stream while the remaining blocks compute.  At r = 64 a bucket of 7
-    blocks is 2 x 29.4 MB, i.e. 4 buckets per step (DDP's 100 MB cap would give 3); per-link xGMI time of the whole 235 MB exchange is
-    ~3 ms against a ~60 ms step, and only the last bucket (the first blocks) is exposed.  Every rank issues the same collectives in
-    the same order by construction (the bucket schedule is a function of L alone)."""
+    finetrainers/parallel/ptd.py:462-463) without parameter hooks: the backward reports gradients as soon as they are final and the
+    slices of the flat fp32 gradient buffer are all-reduced (AVG) right away on RCCL's stream while the remaining blocks compute.
+    Two ways in, one way out:
+      * ``bucket_ready(lo, hi, grad_a, grad_b)`` -- a block range of an [A | B] buffer (LTX, CogVideoX): two slices per bucket.  At r = 64 an
+        LTX bucket of 7 blocks is 2 x 29.4 MB, i.e. 4 buckets per step (DDP's 100 MB cap would give 3); per-link xGMI time of the whole 235 MB
+        exchange is ~3 ms against a ~60 ms step, and only the last bucket (the first blocks) is exposed;
+      * ``span_done((lo, hi))`` -- one block's element span of ``gflat``, laid out block after block (HunyuanVideo, Wan): every ``bucket_blocks``
+        finished spans -- one contiguous slice, the backward walks the buffer from its end -- go out as one bucket, and so does whatever is ready
+        when a span starting at element 0 arrives (Wan's patch-embedding adapter sits there and is reported after block 0).
+    ``begin()`` opens an exchange, ``finish()`` makes the step wait for it, ``abort()`` ends one whose backward raised.  Every rank issues the
+    same collectives in the same order by construction (the bucket schedule is a function of the model's layout alone)."""
 
-    def __init__(self, backend: DataParallelBackend, native: Optional[bool] = None):
+    def __init__(self, backend: DataParallelBackend, native: Optional[bool] = None, gflat: Optional[torch.Tensor] = None, bucket_blocks: int = 1):
         self.backend = backend
-        self._pending = []
-        self.buckets_issued = 0
+        self.gflat, self.bucket_blocks = gflat, max(1, int(bucket_blocks))
+        self._pending, self._ready = [], []
+        self.buckets_issued = 0    # cumulative over the object's life
+        self.exchange_buckets = 0  # since begin()
+        self.bucket_log = []       # (lo, hi) element slices span_done() issued since begin(), in issue order
         # native: the buckets go through the library's own communicator (ftmi_allreduce_bucket / _wait: RCCL on the library's communication stream) instead
         # of torch.distributed's process group.  Default: FTMI_NATIVE_ALLREDUCE=1 on GPU ranks of an RCCL job; every rank must make the same choice.
+        # With native=False nothing of the backend is touched but all_reduce_mean_async and world_size.
         if native is None:
             native = os.environ.get("FTMI_NATIVE_ALLREDUCE", "0") not in ("", "0") and backend.active and backend.backend == "nccl" and backend.device.type == "cuda"
         self.native = bool(native)
@@ -247,27 +256,53 @@ class GradBucketReducer:
         self.measure_exposed = False
         self._exposed = []
 
-    def bucket_ready(self, l_lo: int, l_hi: int, grad_a: torch.Tensor, grad_b: torch.Tensor) -> None:
-        """Hook signature of ``MI355XLTXVideoTransformer3DModel._grad_bucket_hook``."""
+    def begin(self) -> None:
+        """A new exchange: forget the last one's log and count (nothing is in flight between exchanges: finish() or abort() ended it)."""
+        self._ready, self.bucket_log, self.exchange_buckets = [], [], 0
+
+    def slice_ready(self, t: torch.Tensor) -> None:
+        """Start averaging one contiguous fp32 slice of the flat gradient buffer, in place."""
         if self.native:
             from . import _lib
 
-            lib, st = _lib.load(), torch.cuda.current_stream().cuda_stream
-            for t in (grad_a, grad_b):
-                if not (t.is_contiguous() and t.dtype == torch.float32):
-                    raise ValueError("the in-library exchange reduces contiguous fp32 slices of the flat gradient buffer in place")
-                _lib.check(lib.ftmi_allreduce_bucket(self._ex, t.data_ptr(), t.numel(), 1, st), "ftmi_allreduce_bucket")
+            if not (t.is_contiguous() and t.dtype == torch.float32):
+                raise ValueError("the in-library exchange reduces contiguous fp32 slices of the flat gradient buffer in place")
+            _lib.check(_lib.load().ftmi_allreduce_bucket(self._ex, t.data_ptr(), t.numel(), 1, torch.cuda.current_stream().cuda_stream), "ftmi_allreduce_bucket")
             self._native_pending = True
-            self.buckets_issued += 1
             return
-        for t in (grad_a, grad_b):
-            h = self.backend.all_reduce_mean_async(t)
-            if h is not None:
-                self._pending.append(h)
+        h = self.backend.all_reduce_mean_async(t)
+        if h is not None:
+            self._pending.append(h)
+
+    def _bucket_issued(self) -> None:
         self.buckets_issued += 1
+        self.exchange_buckets += 1
+
+    def bucket_ready(self, l_lo: int, l_hi: int, grad_a: torch.Tensor, grad_b: torch.Tensor) -> None:
+        """Hook signature of ``MI355XLTXVideoTransformer3DModel._grad_bucket_hook``."""
+        self.slice_ready(grad_a)
+        self.slice_ready(grad_b)
+        self._bucket_issued()
+
+    def span_done(self, span) -> None:
+        """The gradients in elements [lo, hi) of ``gflat`` are final (last block first)."""
+        self._ready.append(span)
+        if len(self._ready) >= self.bucket_blocks or span[0] == 0:
+            self._flush()
+
+    def _flush(self) -> None:
+        lo, hi = min(s_[0] for s_ in self._ready), max(s_[1] for s_ in self._ready)
+        assert hi - lo == sum(s_[1] - s_[0] for s_ in self._ready), "finished blocks must form one contiguous slice of the flat gradient"
+        self.slice_ready(self.gflat[lo:hi])
+        self.bucket_log.append((lo, hi))
+        self._ready.clear()
+        self._bucket_issued()
 
     def finish(self) -> None:
-        """Make the current stream wait for every outstanding bucket (device-side wait on RCCL; gloo: host wait + divide)."""
+        """Issue what span_done() still holds, then make the current stream wait for every outstanding bucket (device-side wait on RCCL; gloo:
+        host wait + divide)."""
+        if self._ready:
+            self._flush()
         ev = t_host = None
         if self.native:
             if self._native_pending:
@@ -313,18 +348,22 @@ class GradBucketReducer:
 
     def abort(self) -> None:
         """A backward that raised after issuing some buckets: wait for the collectives already in flight (every rank issued them, so they
-        complete) and forget them -- the next step must neither wait on stale handles nor re-divide their tensors."""
+        complete, and each slice ends up averaged exactly once as in finish()) and forget them together with the spans not yet issued -- the next
+        step must neither wait on stale handles, nor race the collective's stream on the gradient buffer, nor divide a tensor twice."""
         if self.native and self._native_pending:
             from . import _lib
 
             _lib.load().ftmi_allreduce_wait(self._ex, torch.cuda.current_stream().cuda_stream)  # the buckets already on the wire complete (every rank issued them)
             self._native_pending = False
-        for work, _ in self._pending:
+        for work, div in self._pending:
             try:
                 work.wait()
+                if div is not None:
+                    div.div_(self.backend.world_size)
             except Exception:
                 pass
         self._pending.clear()
+        self._ready.clear()
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------------------

@@ -18,6 +18,7 @@ from typing import Any, Dict, Optional
 import torch
 
 from . import ops
+from .lora_step import FlatLoRAStep
 from .utils import diffusion as diffusion_utils
 
 
@@ -47,7 +48,7 @@ def sft_loss(pred: torch.Tensor, target: torch.Tensor, sigmas: torch.Tensor, flo
     return _MSELossFunction.apply(pred, target, weights, 1.0 / gradient_accumulation_steps)
 
 
-class MI355XSFTStep:
+class MI355XSFTStep(FlatLoRAStep):
     """One LoRA SFT optimisation step on one rank (one process per GPU).  ``parallel`` is a
     ``finetrainers_amd.parallel.DataParallelBackend`` (or None for a single GPU).
 
@@ -67,16 +68,10 @@ class MI355XSFTStep:
             raise ValueError("gradient_accumulation_steps must be >= 1")
         self.transformer = transformer
         self.spec = specification
-        self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
-        self.max_grad_norm = max_grad_norm
         self.scheme = flow_weighting_scheme
         self.flow_logit_mean, self.flow_logit_std, self.flow_mode_scale = flow_logit_mean, flow_logit_std, flow_mode_scale
-        self.parallel = parallel
         self.generator = generator
-        self.gradient_accumulation_steps = gradient_accumulation_steps
-        # ``finetrainers_amd.utils.lr_schedule.LRSchedule`` (or anything with current_lr() / step()): its rate is read for every optimiser step
-        # and it is stepped right after, as trainer.py:500-503 does with the LambdaLR
-        self.lr_scheduler = lr_scheduler
+        self.gradient_accumulation_steps, self.grad_bucket_blocks = gradient_accumulation_steps, grad_bucket_blocks
         # False = the batches carry the VAE posterior's moments (what --enable_precomputation stores, trainer.py:374) and every step samples them
         self.compute_posterior = compute_posterior
         # Data parallelism x gradient accumulation: the reference wraps the model with replicate() and never enters no_sync (trainer.py:479-503,
@@ -89,25 +84,17 @@ class MI355XSFTStep:
         transformer._assert_flat_aliasing()
         # flat fp32 optimiser state matching transformer.lora_flat = [A | B]
         self.n_a, self.n_b = transformer._lora_A_full.numel(), transformer._lora_B_full.numel()  # storage size (rank padded to a multiple of 64)
-        self.exp_avg = torch.zeros(self.n_a + self.n_b, dtype=torch.float32, device=dev)
-        self.exp_avg_sq = torch.zeros_like(self.exp_avg)
-        self._scratch = torch.zeros(ops.CLIP_SCRATCH_FLOATS, dtype=torch.float32, device=dev)
-        self.step_count = 0
-        self.reducer = None
+        self._init_optimizer(transformer.lora_flat, lr, betas, eps, weight_decay, max_grad_norm, lr_scheduler)
         # MI355XParallelBackend.apply_ddp() installs the exchange ON THE MODEL (hook + finish, like DDP's reducer): a step that is handed such a model
         # leaves those hooks where they are -- the backward then returns with averaged gradients -- and must not bring a second exchange of its own
         self._model_owns_exchange = getattr(transformer, "_grad_bucket_hook", None) is not None and getattr(transformer, "_grad_bucket_finish", None) is not None
         if self._model_owns_exchange and parallel is not None and parallel.active:
             raise ValueError("MI355XSFTStep(parallel=...) on a model that apply_ddp() already wired for the gradient exchange: the gradients would be averaged "
                              "twice -- pass parallel=None (the model's own hooks do the exchange) or do not call apply_ddp")
-        if parallel is not None and parallel.active:
-            from .parallel import GradBucketReducer
-
-            # replicas must start from the same adapter: add_adapter draws A from each process's own RNG
-            parallel.broadcast_(transformer.lora_flat, src=0)
+        self._init_exchange(parallel, transformer.lora_flat, native=None)  # (native: the in-library communicator where FTMI_NATIVE_ALLREDUCE=1 asks for it)
+        if self.reducer is not None:
             transformer._lora_versions = None
             transformer.grad_bucket_blocks = grad_bucket_blocks
-            self.reducer = GradBucketReducer(parallel)
         from .ltx_video.specification import FlowMatchSigmas
 
         self.scheduler = FlowMatchSigmas()
@@ -146,60 +133,45 @@ class MI355XSFTStep:
         loss, dpred = ops.mse_loss(pred.detach().contiguous(), target.contiguous(), weights, want_grad=True, grad_scale=1.0 / gas)
         loss = loss.reshape(()) / gas if gas > 1 else loss.reshape(())
         exchange = self.reducer is not None and (sync or not self.no_sync_accumulation)
-        prev_hook, prev_fin = tr._grad_bucket_hook, tr._grad_bucket_finish
         # Who owns the exchange is decided PER STEP, not at construction: apply_ddp() may be called on the model after this object was built (a step
         # that then blanked the model's hooks for its backward would leave the replicas to diverge silently).
-        model_owns = prev_hook is not None and prev_fin is not None
-        if model_owns and self.reducer is not None:
+        self._model_owns_exchange = tr._grad_bucket_hook is not None and tr._grad_bucket_finish is not None
+        if self._model_owns_exchange and self.reducer is not None:
             raise RuntimeError("MI355XSFTStep has its own gradient exchange (parallel=...) and the model now carries apply_ddp()'s hooks as well: the gradients "
                                "would be averaged twice -- build the step with parallel=None or do not call apply_ddp on this model")
-        self._model_owns_exchange = model_owns
-        if not model_owns:  # this step's own reducer (or none): install for the duration of the backward, then put back what was there
-            tr._grad_bucket_hook = self.reducer.bucket_ready if exchange else None
-            tr._grad_bucket_finish = None
-        try:
-            pred.backward(dpred)  # DP: buckets of finished blocks are all-reduced (AVG) on RCCL's stream while this still runs
-        except BaseException:
-            if exchange:
-                self.reducer.abort()  # buckets issued before the failure: drained and dropped, never carried into the next step
-            raise
-        finally:
-            tr._grad_bucket_hook, tr._grad_bucket_finish = prev_hook, prev_fin
+        self._backward_exchanging(lambda: pred.backward(dpred), exchange)
         if not sync:
             # the reference clips after every backward (trainer.py:487-492), i.e. also the partial sums of an accumulation window -- in place
             # on .grad (under DP on the all-reduced sums, see no_sync_accumulation)
-            if exchange:
-                self.reducer.finish()
             if self.max_grad_norm and self.max_grad_norm > 0 and (self.reducer is None or exchange):
                 ops.clip_grad_norm_(self._flat_grad(tr.lora_A.grad, tr.lora_B.grad), self.max_grad_norm, scratch=self._scratch)
             return {"loss": loss.detach(), "grad_norm": None}
-        gflat = self._flat_grad(tr.lora_A.grad, tr.lora_B.grad)
-        if self.reducer is not None:
-            self.reducer.finish()
-        # 5-6. clip (utils/torch.py:99-161) + AdamW (optimizer.py:117-125), fused over the flat buffer
-        self.step_count += 1
-        grad_norm = self._clip_adamw(gflat)
+        # 5-6. clip + AdamW, fused over the flat buffer
+        grad_norm = self._clip_adamw(tr.lora_flat, self._flat_grad(tr.lora_A.grad, tr.lora_B.grad))
         tr.lora_A.grad = None  # optimizer.zero_grad(set_to_none=True) (trainer.py:503)
         tr.lora_B.grad = None
         return {"loss": loss.detach(), "grad_norm": grad_norm}
 
-    # ---- resume (reference: utils/state_checkpoint.py saves optimizer + scheduler state next to the model's) ------------------------------
-    def state_dict(self) -> Dict[str, Any]:
-        """Optimiser-side state of the fused step: AdamW moments laid out like ``transformer.lora_flat`` ([A | B], rank-padded storage),
-        the step counters and the schedule clock.  The LoRA parameters themselves travel in ``transformer.state_dict()``."""
-        return {"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq, "step": self.step_count, "micro_step": self._micro_step,
-                "lr_scheduler": None if self.lr_scheduler is None else self.lr_scheduler.state_dict(),
-                "hyper": {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay, "max_grad_norm": self.max_grad_norm}}
+    # ---- the model's hooks for the duration of the backward ---------------------------------------------------------------------------------
+    def _install_hooks(self, reducer) -> None:
+        tr = self.transformer
+        self._prev_hooks = tr._grad_bucket_hook, tr._grad_bucket_finish
+        if not self._model_owns_exchange:  # this step's own reducer (or none); a model wired by apply_ddp() keeps its hooks and ends the exchange itself
+            tr._grad_bucket_hook, tr._grad_bucket_finish = (None if reducer is None else reducer.bucket_ready), None
 
-    @torch.no_grad()
-    def load_state_dict(self, sd: Dict[str, Any]) -> None:
-        if sd["exp_avg"].numel() != self.exp_avg.numel():
-            raise ValueError(f"optimizer state holds {sd['exp_avg'].numel()} values, the attached adapter needs {self.exp_avg.numel()}")
-        self.exp_avg.copy_(sd["exp_avg"])
-        self.exp_avg_sq.copy_(sd["exp_avg_sq"])
-        self.step_count, self._micro_step = int(sd["step"]), int(sd.get("micro_step", 0))
-        if self.lr_scheduler is not None and sd.get("lr_scheduler") is not None:
-            self.lr_scheduler.load_state_dict(sd["lr_scheduler"])
+    def _clear_hooks(self) -> None:  # put back what was there
+        self.transformer._grad_bucket_hook, self.transformer._grad_bucket_finish = self._prev_hooks
+
+    def _after_update(self) -> None:
+        self.transformer._lora_versions = None  # parameters changed in place by the library: refresh the bf16 working copies next forward
+
+    flat = property(lambda self: self.transformer.lora_flat)
+    gflat = property(lambda self: self.transformer._grad_flat)
+
+    def state_dict(self) -> Dict[str, Any]:
+        """AdamW moments laid out like ``transformer.lora_flat`` ([A | B], rank-padded storage); the LoRA parameters travel in ``transformer.state_dict()``."""
+        hyper = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay, "max_grad_norm": self.max_grad_norm}
+        return dict(super().state_dict(), hyper=hyper)
 
     def _flat_grad(self, ga: torch.Tensor, gb: torch.Tensor) -> torch.Tensor:
         gflat = self.transformer._grad_flat
@@ -213,14 +185,3 @@ class MI355XSFTStep:
         flat[:self.n_a].view_as(tr._lora_A_full)[:, :, :tr.lora_rank, :].copy_(ga)
         flat[self.n_a:].view_as(tr._lora_B_full)[:, :, :, :tr.lora_rank].copy_(gb)
         return flat
-
-    def _clip_adamw(self, gflat: torch.Tensor) -> torch.Tensor:
-        tr = self.transformer
-        gn = torch.empty(1, dtype=torch.float32, device=gflat.device)
-        lr = self.lr if self.lr_scheduler is None else self.lr_scheduler.current_lr()
-        ops.clip_adamw_step(tr.lora_flat, gflat, self.exp_avg, self.exp_avg_sq, self.step_count, lr, self.betas, self.eps,
-                            self.weight_decay, self.max_grad_norm, scratch=self._scratch, grad_norm_out=gn)
-        if self.lr_scheduler is not None:
-            self.lr_scheduler.step()
-        tr._lora_versions = None  # parameters changed in place by the library: refresh the bf16 working copies next forward
-        return gn

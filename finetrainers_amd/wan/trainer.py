@@ -11,12 +11,13 @@ adapters in one flat buffer, no parameter sharder."""
 
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, Optional, Tuple
 
 import torch
 import torch.distributed as dist
 
 from .. import ops
+from ..lora_step import FlatLoRAStep
 from .fsdp import ParameterSharder
 from .model import MI355XWanTransformer3DModel
 from .specification import MI355XWanSpecOps
@@ -158,7 +159,7 @@ class MI355XWanFullFinetuneStep:
         return out
 
 
-class MI355XWanLoRAStep:
+class MI355XWanLoRAStep(FlatLoRAStep):
     """One Wan-T2V LoRA SFT optimisation step (reference loop: trainer/sft_trainer/trainer.py:430-503 with ``--training_type lora`` and DDP): posterior
     sample + flow-match noising -> DiT forward over the frozen base -> MSE -> backward producing dx and the adapter gradients only -> average of the
     adapter gradients over the data-parallel ranks -> global-norm clip -> AdamW, the last two fused over ONE flat fp32 buffer the blocks' adapter
@@ -176,18 +177,8 @@ class MI355XWanLoRAStep:
         if not self.params:
             raise ValueError("attach a LoRA adapter first (transformer.add_adapter)")
         self.gradient_accumulation_steps, self._micro_step = gradient_accumulation_steps, 0
-        self.transformer, self.spec = transformer, spec or MI355XWanSpecOps()
-        self.lr, self.betas, self.eps, self.weight_decay, self.max_grad_norm = lr, betas, eps, weight_decay, max_grad_norm
-        self.parallel, self.generator, self.lr_scheduler = parallel, generator, lr_scheduler
-        dev = transformer.device
-        self.flat = torch.cat([p.detach().reshape(-1) for p in self.params]).contiguous()
-        off = 0
-        for p in self.params:  # the adapters now live in one buffer: one fused clip + AdamW launch covers all 240 of them
-            n = p.numel()
-            p.data = self.flat[off:off + n].view(p.shape)
-            off += n
-        if parallel is not None and parallel.active:  # replicas start from rank 0's adapters (DDP broadcasts at construction)
-            parallel.broadcast_(self.flat, src=0)
+        self.transformer, self.spec, self.generator = transformer, spec or MI355XWanSpecOps(), generator
+        self.flat = self.flatten_parameters(self.params)  # all 240 adapters
         self.gflat = torch.zeros_like(self.flat)
         self.grad_bucket_blocks = max(1, int(grad_bucket_blocks))
         self._spans: Dict[int, Tuple[int, int]] = {}
@@ -210,65 +201,26 @@ class MI355XWanLoRAStep:
             blk._grad_ffn_views = tuple(views[2:]) if len(views) > 2 else None
             self._spans[id(blk)] = (lo, off)
         assert off == self.flat.numel()
-        self.buckets_issued = 0
-        self.bucket_log: List[Tuple[int, int]] = []  # (lo, hi) element slices of the last exchange, in issue order
-        self._pending, self._ready = [], []
-        self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
-        self._scratch = torch.zeros(ops.CLIP_SCRATCH_FLOATS, dtype=torch.float32, device=dev)
-        self.step_count = 0
+        self._init_optimizer(self.flat, lr, betas, eps, weight_decay, max_grad_norm, lr_scheduler)
+        self._init_exchange(parallel, self.flat, self.gflat)
 
-    # ---- the bucketed exchange (driven by the blocks' backward through ``_grad_hook``) ------------------------------------------------------------
-    def _begin_exchange(self, exchange: bool) -> None:
-        self._pending, self._ready, self.bucket_log = [], [], []
+    bucket_log = property(lambda self: [] if self.reducer is None else self.reducer.bucket_log)  # (lo, hi) element slices of the last exchange, in issue order
+
+    def _install_hooks(self, reducer) -> None:
         for blk in self.transformer.blocks:
-            blk._grad_hook = self._block_done if exchange else None
-        self.transformer._patch_grad_hook = self._patch_done if exchange and self._patch_span is not None else None
+            blk._grad_hook = None if reducer is None else self._block_done
+        # the patch-embedding adapter's gradients are final after block 0's: its span starts at element 0, so the last bucket goes out with it
+        patch = reducer is not None and self._patch_span is not None
+        self.transformer._patch_grad_hook = (lambda transformer: reducer.span_done(self._patch_span)) if patch else None
 
-    def _flush(self) -> None:
-        lo, hi = min(s_[0] for s_ in self._ready), max(s_[1] for s_ in self._ready)
-        assert hi - lo == sum(s_[1] - s_[0] for s_ in self._ready), "finished blocks must form one contiguous slice of the flat gradient"
-        h = self.parallel.all_reduce_mean_async(self.gflat[lo:hi])
-        if h is not None:
-            self._pending.append(h)
-        self.bucket_log.append((lo, hi))
-        self._ready.clear()
-
-    def _block_done(self, blk) -> None:
-        """A block's adapter gradients are final (last block first): every rank issues the same bucket sequence."""
-        span = self._spans[id(blk)]
-        self._ready.append(span)
-        if len(self._ready) >= self.grad_bucket_blocks or span[0] == 0:
-            self._flush()
-
-    def _patch_done(self, transformer) -> None:
-        """The patch-embedding adapter's gradients are final (after block 0's): the last bucket, which starts at element 0, goes out."""
-        self._ready.append(self._patch_span)
-        self._flush()
-
-    def _finish_exchange(self, failed: bool = False) -> None:
+    def _clear_hooks(self) -> None:
         for blk in self.transformer.blocks:
             blk._grad_hook = None
         self.transformer._patch_grad_hook = None
-        if failed:
-            # a backward that raised after issuing some buckets: every rank issued the same collectives, so they complete -- wait for them and drop
-            # the handles (the next step must not race the collective's stream on the gradient buffer, nor divide a tensor twice)
-            for work, _ in self._pending:
-                try:
-                    work.wait()
-                except Exception:
-                    pass
-            self._pending, self._ready = [], []
-            return
-        if self._ready:
-            self._flush()
-        for work, div in self._pending:  # device-side wait on RCCL; gloo: host wait + divide
-            work.wait()
-            if div is not None:
-                div.div_(self.parallel.world_size)
-        self.buckets_issued = len(self._pending)
-        self._pending = []
 
-    # ---- the step ---------------------------------------------------------------------------------------------------------------------------------
+    def _after_update(self) -> None:
+        self.transformer.mark_patch_adapter_updated()  # (the fused launch moved the adapters in place: the patch adapter folds again)
+
     def step(self, moments: torch.Tensor, encoder_hidden_states: torch.Tensor, latents_mean: torch.Tensor, latents_std: torch.Tensor,
              sigmas: torch.Tensor, posterior_noise: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
              control_latents: Optional[torch.Tensor] = None, **image_conditioning) -> Dict[str, torch.Tensor]:
@@ -283,35 +235,10 @@ class MI355XWanLoRAStep:
             self.gflat.zero_()  # a new accumulation window
         self._micro_step += 1
         sync = self._micro_step % gas == 0  # last micro-step of the window: exchange, clip, optimiser step
-        dp = self.parallel is not None and self.parallel.active
-        self._begin_exchange(dp and sync)
-        try:
-            loss = self.spec.loss_backward(pred, target, grad_scale=1.0 / gas)
-        except BaseException:
-            self._finish_exchange(failed=True)
-            raise
-        self._finish_exchange()
-        gn = torch.empty(1, dtype=torch.float32, device=self.gflat.device)
+        loss = self._backward_exchanging(lambda: self.spec.loss_backward(pred, target, grad_scale=1.0 / gas), exchange=sync)
         if sync:
-            self.step_count += 1
-            lr = self.lr if self.lr_scheduler is None else self.lr_scheduler.current_lr()
-            ops.clip_adamw_step(self.flat, self.gflat, self.exp_avg, self.exp_avg_sq, self.step_count, lr, self.betas, self.eps, self.weight_decay,
-                                self.max_grad_norm, scratch=self._scratch, grad_norm_out=gn)
-            self.transformer.mark_patch_adapter_updated()  # (the fused launch moved the adapters in place: the patch adapter folds again)
-            if self.lr_scheduler is not None:
-                self.lr_scheduler.step()
+            gn = self._clip_adamw(self.flat, self.gflat)
         else:  # report the norm of what has accumulated so far; the window's clip happens with its optimiser step
+            gn = torch.empty(1, dtype=torch.float32, device=self.gflat.device)
             gn.copy_(ops.grad_sumsq(self.gflat, self._scratch).sqrt())
         return {"loss": loss.detach(), "grad_norm": gn}
-
-    def state_dict(self) -> Dict[str, object]:
-        """Optimiser state and counters; the adapters themselves are ``transformer.lora_state_dict()``."""
-        return {"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq, "step": self.step_count, "micro_step": self._micro_step,
-                "lr_scheduler": None if self.lr_scheduler is None else self.lr_scheduler.state_dict()}
-
-    def load_state_dict(self, sd: Dict[str, object]) -> None:
-        self.exp_avg.copy_(sd["exp_avg"])
-        self.exp_avg_sq.copy_(sd["exp_avg_sq"])
-        self.step_count, self._micro_step = int(sd["step"]), int(sd.get("micro_step", 0))
-        if self.lr_scheduler is not None and sd.get("lr_scheduler") is not None:
-            self.lr_scheduler.load_state_dict(sd["lr_scheduler"])
