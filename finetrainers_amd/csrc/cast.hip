@@ -72,6 +72,8 @@ __global__ __launch_bounds__(256) void fp8_upcast_transpose_kernel(const uint8_t
 
 int fp8_upcast(const uint8_t* src, bf16_t* dst, int rows, int cols, int transpose, hipStream_t st) {
     if (rows <= 0 || cols <= 0) return 0;
+    // both kernels move 16-byte vectors at src + a multiple of 16 bytes and dst + a multiple of 8 elements
+    if ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) return set_error(FTMI_ERR_INVALID, "fp8_upcast: tensors must be 16-byte aligned");
     if (!transpose) {
         const long n = (long)rows * cols;
         if (n % 16) return set_error(FTMI_ERR_UNSUPPORTED, "fp8_upcast: element count must be a multiple of 16");

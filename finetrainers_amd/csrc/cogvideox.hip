@@ -346,7 +346,7 @@ int cog_mod_tables(const bf16_t* mod, bf16_t* tables, int L2, int B, int D, hipS
 }
 
 int cog_patch_permute(const bf16_t* src, bf16_t* dst, int B, int F, int C, int H, int W, int p, int to_tokens, hipStream_t st) {
-    if (B <= 0 || F <= 0 || C <= 0 || p <= 0 || H % p || W % p) return set_error(FTMI_ERR_INVALID, "cog_patch_permute: bad geometry");
+    if (B <= 0 || F <= 0 || C <= 0 || H <= 0 || W <= 0 || p <= 0 || H % p || W % p) return set_error(FTMI_ERR_INVALID, "cog_patch_permute: bad geometry");
     const long total = (long)B * F * C * H * W;
     long blocks = (total + 255) / 256;
     if (blocks > 8192) blocks = 8192;

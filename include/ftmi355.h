@@ -254,7 +254,8 @@ typedef struct ftmi_gemm_tn_args {
 int ftmi_gemm_tn_ex(const ftmi_gemm_tn_args* args, ftmi_stream stream);
 /* fp8 weight storage of the layerwise up-casting recipe (finetrainers/trainer/sft_trainer/trainer.py:111-118: storage float8_e4m3fn, compute bf16):
  * dst (bf16) = exact up-cast of src [rows, cols] (OCP e4m3fn bytes); transpose != 0: dst is [cols, rows] = src^T (rows, cols multiples of 64) -- the layout
- * the input-gradient GEMMs read.  Called per block right before it runs; 1 byte read + 2 bytes written per weight. */
+ * the input-gradient GEMMs read.  Called per block right before it runs; 1 byte read + 2 bytes written per weight.  rows or cols <= 0: returns 0 without a
+ * launch.  FTMI_ERR_INVALID: a null or not 16-byte aligned src or dst; FTMI_ERR_UNSUPPORTED: rows * cols % 16 (plain), rows % 64 or cols % 64 (transposing). */
 int ftmi_fp8_upcast(const void* src, void* dst, int rows, int cols, int transpose, ftmi_stream stream);
 /* out[cols,rows] = in[rows,cols]^T (bf16); used once at load time for the dgrad copies of frozen weights */
 int ftmi_transpose_bf16(const void* in, void* out, int rows, int cols, ftmi_stream stream);  /* rows or cols == 0: returns 0 without a launch; negative: FTMI_ERR_INVALID */
@@ -534,7 +535,8 @@ int ftmi_cog_blocks_backward(const ftmi_cog_config* cfg, const ftmi_cog_weights*
                              float* grad_a, float* grad_b, void* workspace, size_t workspace_bytes, int l_hi, int l_lo, int accumulate, ftmi_stream stream);
 
 /* latents [B, F, C, H, W] -> tokens [B, F (H/p) (W/p), C p p] (the im2col of CogVideoXPatchEmbed's Conv2d(kernel = stride = p), channel order
- * (c, py, px) like the flattened conv weight), and back (the model's final un-patchify).  [upstream] CogVideoXPatchEmbed / CogVideoXTransformer3DModel. */
+ * (c, py, px) like the flattened conv weight), and back (the model's final un-patchify).  [upstream] CogVideoXPatchEmbed / CogVideoXTransformer3DModel.
+ * FTMI_ERR_INVALID before anything is launched: a null tensor, an extent or patch <= 0, H or W that is not whole patches. */
 int ftmi_cog_patchify(const void* latents, void* tokens, int B, int F, int C, int H, int W, int patch, ftmi_stream stream);
 int ftmi_cog_unpatchify(const void* tokens, void* latents, int B, int F, int C, int H, int W, int patch, ftmi_stream stream);
 
