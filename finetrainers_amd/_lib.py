@@ -216,6 +216,32 @@ class CogSampleWeights(Structure):
     _fields_ = [("blocks", CogWeights)] + [(n, c_void_p) for n in COG_SAMPLE_WEIGHT_FIELDS]
 
 
+class HySampleGeometry(Structure):
+    """include/ftmi355.h: ftmi_hy_sample_geometry."""
+
+    _fields_ = [(n, c_int) for n in ("B", "C", "F", "H", "W", "p", "pt", "P")]
+
+
+class HySampleUpcast(Structure):
+    """include/ftmi355.h: ftmi_hy_sample_upcast."""
+
+    _fields_ = [("src", c_void_p), ("rows", c_int), ("cols", c_int), ("offset", c_size_t)]
+
+
+class HySampleConfig(Structure):
+    """include/ftmi355.h: ftmi_hy_sample_config."""
+
+    _fields_ = [("geo", HySampleGeometry), ("T", c_int), ("D", c_int), ("H", c_int), ("mlp", c_int), ("Ld", c_int), ("Ls", c_int), ("r", c_int),
+                ("lora_scale", c_float), ("eps", c_float), ("gemm_variant", c_int), ("steps", c_int), ("true_cfg", c_float)]
+
+
+class HySampleWeights(Structure):
+    """include/ftmi355.h: ftmi_hy_sample_weights (``dual`` / ``single`` / ``upcasts`` / ``upcast_count``: host arrays)."""
+
+    _fields_ = [("dual", POINTER(HyDualWeights)), ("single", POINTER(HySingleWeights)), ("upcasts", POINTER(HySampleUpcast)), ("upcast_count", POINTER(c_int)),
+                ("arena", c_void_p)] + [(n, c_void_p) for n in ("patch_w", "patch_b", "proj_w", "proj_b", "ones", "zeros")]
+
+
 class WanRowArgs(Structure):
     """include/ftmi355.h: ftmi_wan_row_args."""
 
@@ -385,6 +411,11 @@ _SIGS = {
     "ftmi_cog_sample_finish": (c_int, [POINTER(CogSampleGeometry), c_void_p, c_float, c_void_p, c_void_p]),
     "ftmi_cog_sample_workspace_bytes": (c_size_t, [POINTER(CogSampleConfig)]),
     "ftmi_cog_sample": (c_int, [POINTER(CogSampleConfig), POINTER(CogSampleWeights)] + [c_void_p] * 8 + [c_size_t, c_void_p]),
+    "ftmi_hy_sample_init": (c_int, [POINTER(HySampleGeometry), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ftmi_hy_sample_step": (c_int, [POINTER(HySampleGeometry), c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p]),
+    "ftmi_hy_sample_finish": (c_int, [POINTER(HySampleGeometry), c_void_p, c_float, c_void_p, c_void_p]),
+    "ftmi_hy_sample_workspace_bytes": (c_size_t, [POINTER(HySampleConfig)]),
+    "ftmi_hy_sample": (c_int, [POINTER(HySampleConfig), POINTER(HySampleWeights)] + [c_void_p] * 11 + [c_size_t, c_void_p]),
     "ftmi_hy_dual_saved_bytes": (c_size_t, [POINTER(HyDualConfig)]),
     "ftmi_hy_dual_scratch_bytes": (c_size_t, [POINTER(HyDualConfig)]),
     "ftmi_hy_dual_forward": (c_int, [POINTER(HyDualConfig), POINTER(HyDualWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

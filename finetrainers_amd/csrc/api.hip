@@ -1030,4 +1030,31 @@ int ftmi_cog_sample(const ftmi_cog_sample_config* cfg, const ftmi_cog_sample_wei
                       workspace_bytes, (hipStream_t)stream);
 }
 
+int ftmi_hy_sample_init(const ftmi_hy_sample_geometry* geo, const float* latents, float* x, void* cols, ftmi_stream stream) {
+    if (!geo || !latents || !x || !cols) return set_error(FTMI_ERR_INVALID, "ftmi_hy_sample_init: null argument");
+    return hy_sample_init(*geo, latents, x, (bf16_t*)cols, (hipStream_t)stream);
+}
+
+int ftmi_hy_sample_step(const ftmi_hy_sample_geometry* geo, const void* pred, float* x, const float* sigmas, int step, float true_cfg, void* cols,
+                        ftmi_stream stream) {
+    if (!geo || !x || (!pred && !cols)) return set_error(FTMI_ERR_INVALID, "ftmi_hy_sample_step: null argument");
+    return hy_sample_step(*geo, (const bf16_t*)pred, x, sigmas, step, true_cfg, (bf16_t*)cols, (hipStream_t)stream);
+}
+
+int ftmi_hy_sample_finish(const ftmi_hy_sample_geometry* geo, const float* x, float k, void* latents, ftmi_stream stream) {
+    if (!geo || !x || !latents) return set_error(FTMI_ERR_INVALID, "ftmi_hy_sample_finish: null argument");
+    return hy_sample_finish(*geo, x, k, (bf16_t*)latents, (hipStream_t)stream);
+}
+
+size_t ftmi_hy_sample_workspace_bytes(const ftmi_hy_sample_config* cfg) { return cfg ? hy_sample_workspace_bytes(*cfg) : 0; }
+
+int ftmi_hy_sample(const ftmi_hy_sample_config* cfg, const ftmi_hy_sample_weights* w, void* cols, float* x, const void* temb_silu, const void* enc,
+                   const void* head_shift, const void* head_onep, const float* key_bias, const float* rope_cos, const float* rope_sin, const float* sigmas,
+                   void* workspace, size_t workspace_bytes, ftmi_stream stream) {
+    if (!cfg || !w || !cols || !x || !temb_silu || !enc || !head_shift || !head_onep || !rope_cos || !rope_sin || !sigmas || !workspace)
+        return set_error(FTMI_ERR_INVALID, "ftmi_hy_sample: null argument");
+    return hy_sample(*cfg, *w, (bf16_t*)cols, x, (const bf16_t*)temb_silu, (const bf16_t*)enc, (const bf16_t*)head_shift, (const bf16_t*)head_onep, key_bias,
+                     rope_cos, rope_sin, sigmas, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -9,7 +9,7 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ["gemm.hip", "attention.hip", "attn_ctx2.hip", "rowwise.hip", "cast.hip", "cogvideox.hip", "ltx_dit.hip", "ltx_sample.hip", "cog_dit.hip", "hy_dit.hip", "wan.hip", "wan_dit.hip", "wan_control.hip", "sample_layout.hip", "wan_sample_dit.hip", "collective.hip", "api.hip"]
+SOURCES = ["gemm.hip", "attention.hip", "attn_ctx2.hip", "rowwise.hip", "cast.hip", "cogvideox.hip", "ltx_dit.hip", "ltx_sample.hip", "cog_dit.hip", "hy_dit.hip", "wan.hip", "wan_dit.hip", "wan_control.hip", "sample_layout.hip", "wan_sample_dit.hip", "hy_sample_dit.hip", "collective.hip", "api.hip"]
 HEADERS = ["common.hip.h", "kernels.h", "lora_proj.hip.h", "sample_step.hip.h", os.path.join("..", "..", "include", "ftmi355.h"), "attention_pl.hip.h"]
 HEADERS += sorted(f for f in os.listdir(HERE) if f.startswith("attn_pl_") and f.endswith(".inc"))  # generated statement lists (tools/gen_attn_pl.py)
 LIB = os.path.join(HERE, "..", "libftmi355.so")

@@ -454,6 +454,15 @@ int hy_dual_backward(const ftmi_hy_dual_config& c, const ftmi_hy_dual_weights& w
                      const float* key_bias, const float* rope_cos, const float* rope_sin, const bf16_t* ones_row, bf16_t* dx_v, bf16_t* dx_t, float* grad_a,
                      float* grad_b, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st);
 
+// HunyuanVideo latent sampling (sample_layout.hip: the layout kernels, shared with Wan and CogVideoX; hy_sample_dit.hip: the loop over the block calls above)
+int hy_sample_init(const ftmi_hy_sample_geometry& g, const float* latents, float* x, bf16_t* cols, hipStream_t st);
+int hy_sample_step(const ftmi_hy_sample_geometry& g, const bf16_t* pred, float* x, const float* sigmas, int step, float true_cfg, bf16_t* cols, hipStream_t st);
+int hy_sample_finish(const ftmi_hy_sample_geometry& g, const float* x, float k, bf16_t* latents, hipStream_t st);
+size_t hy_sample_workspace_bytes(const ftmi_hy_sample_config& c);
+int hy_sample(const ftmi_hy_sample_config& c, const ftmi_hy_sample_weights& w, bf16_t* cols, float* x, const bf16_t* temb_silu, const bf16_t* enc,
+              const bf16_t* head_shift, const bf16_t* head_onep, const float* key_bias, const float* rope_cos, const float* rope_sin, const float* sigmas, void* ws,
+              size_t ws_bytes, hipStream_t st);
+
 int cog_patch_permute(const bf16_t* src, bf16_t* dst, int B, int F, int C, int H, int W, int p, int to_tokens, hipStream_t st);  // latents <-> patch tokens
 
 }  // namespace ftmi

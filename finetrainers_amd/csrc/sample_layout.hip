@@ -1,5 +1,5 @@
-// Wan and CogVideoX latent sampling, the kernels around the DiT forward of a denoising loop (the orchestrators are wan_sample in wan_sample_dit.hip and
-// cog_sample in cog_dit.hip, next to the block walk).
+// Wan, CogVideoX and HunyuanVideo latent sampling, the kernels around the DiT forward of a denoising loop (the orchestrators are wan_sample in
+// wan_sample_dit.hip, cog_sample in cog_dit.hip, next to the block walk, and hy_sample in hy_sample_dit.hip).
 //
 // The sampler state lives in the patch embedding's OPERAND layout, so a step needs no patchify / un-patchify:
 //   state  x     fp32 [B, S, Kc]       Kc = C pt ph pw columns in the patch embedding's order (c, pt, ph, pw): column c pv + dt ph pw + dy pw + dx, pv = pt ph pw;
@@ -33,6 +33,9 @@
 //   CogVideoX: (cx, cv) are the step's two numbers of the host-folded scheduler ([upstream, unpinned] CogVideoXDDIMScheduler.step is linear in (x, v):
 //   finetrainers_amd/cogvideox/sampler.py cog_ddim_tables), read from a device table.  A thread owns 8 consecutive elements; the last workgroup's tail is
 //   masked.  Bytes moved per element of x: 12 + 2 P with guidance = 16; 10 + 2 = 12 without.
+//   HunyuanVideo (hy_sample_step): CogVideoX's layout over [B, C, F, H, W] latents (Lay::sc, sf as Wan's; Cx = 0, copies = 1, Kp = Kc, drop = 0; finish is
+//   the scalar affine with k = 1 / scaling_factor) and Wan's update: dt = sigmas[step + 1] - sigmas[step] read from the device table, x <- fma(dt, v, x).  A
+//   row-major stream like CogVideoX's.  Bytes moved per element of x: 10 without true CFG (pred 2 + x 4 read, x 4 + cols 2 written), 16 with.
 // sample_finish_kernel: x fp32 [B, S, Kc] -> latents bf16 = bf16(affine(x)), the inverse permutation of init; the first `drop` frames are not written.  Wan's std
 //   is the VAE's REAL standard deviation -- not the 1 / std the training processors hand over (finetrainers/models/wan/base_specification.py multiplies by
 //   latents_std = 1 / std when it normalises).  The two affines are two instantiations, not two data sets: v * k + 0 would turn -0 into +0.  16-byte reads along
@@ -210,6 +213,27 @@ __global__ __launch_bounds__(256) void cog_sample_step_kernel(const bf16_t* __re
     if (cols) store_groups8<kCfg>(cols, xv, 8 * i, 8 * n8);
 }
 
+// n8 = B S Kc / 8 vectors, one per thread; grid ceil(n8 / 256).  kCfg: two row groups (pred has an unconditional half).
+template <bool kCfg>
+__global__ __launch_bounds__(256) void hy_sample_step_kernel(const bf16_t* __restrict__ pred, float* __restrict__ x, const float* __restrict__ sigmas, int step,
+                                                             float gd, bf16_t* __restrict__ cols, long n8) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n8) return;
+    f32x4* xp = reinterpret_cast<f32x4*>(x) + 2 * i;
+    const f32x4 x0 = xp[0], x1 = xp[1];
+    float xv[8] = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
+    if (pred) {
+        const float dt = sigmas[step + 1] - sigmas[step];
+        float v[8];
+        cfg_combine8<kCfg>(pred, i, n8, gd, v);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) xv[e] = __builtin_fmaf(dt, v[e], xv[e]);
+        xp[0] = f32x4{xv[0], xv[1], xv[2], xv[3]};
+        xp[1] = f32x4{xv[4], xv[5], xv[6], xv[7]};
+    }
+    if (cols) store_groups8<kCfg>(cols, xv, 8 * i, 8 * n8);
+}
+
 struct ChannelAffine {  // Wan
     const float* __restrict__ mean;
     const float* __restrict__ std_;
@@ -341,6 +365,19 @@ int cog_lay(const ftmi_cog_sample_geometry& g, const char* what, Lay& l) {
     return lay_derive(l, what);
 }
 
+int hy_lay(const ftmi_hy_sample_geometry& g, const char* what, Lay& l) {
+    if (g.B <= 0 || g.C <= 0 || g.F <= 0 || g.H <= 0 || g.W <= 0 || g.p <= 0 || g.pt <= 0) return fail(what, FTMI_ERR_INVALID, "extents must be positive");
+    if (g.P != 1 && g.P != 2) return fail(what, FTMI_ERR_INVALID, "P is 2 with true CFG, 1 without");
+    if (g.F % g.pt || g.H % g.p || g.W % g.p) return fail(what, FTMI_ERR_UNSUPPORTED, "the latent size must be whole patches");
+    const long Kc = (long)g.C * g.pt * g.p * g.p;
+    if (Kc > 2048 || g.W > 8192) return fail(what, FTMI_ERR_UNSUPPORTED, "patch or row too wide");
+    if (Kc % 8) return fail(what, FTMI_ERR_UNSUPPORTED, "C pt p p must be a multiple of 8 (16-byte vectors)");
+    l.B = g.B; l.C = g.C; l.Cx = 0; l.F = g.F; l.H = g.H; l.W = g.W; l.pt = g.pt; l.ph = l.pw = g.p;
+    l.sc = (long)g.F * g.H * g.W; l.sf = (long)g.H * g.W;
+    l.Kp = (int)Kc; l.copies = 1; l.P = g.P; l.drop = 0;
+    return lay_derive(l, what);
+}
+
 int launch_init(const Lay& l, const char* what, const float* latents, const bf16_t* extra, float* x, bf16_t* cols, hipStream_t st) {
     if (misaligned(latents) || misaligned(extra) || misaligned(x) || misaligned(cols)) return fail(what, FTMI_ERR_INVALID, "tensors must be 16-byte aligned");
     size_t lds;
@@ -412,6 +449,32 @@ int cog_sample_finish(const ftmi_cog_sample_geometry& g, const float* x, float k
     Lay l;
     FTMI_TRY(cog_lay(g, "cog_sample_finish", l));
     return launch_finish(l, "cog_sample_finish", x, ScalarAffine{k}, latents, st);
+}
+
+int hy_sample_init(const ftmi_hy_sample_geometry& g, const float* latents, float* x, bf16_t* cols, hipStream_t st) {
+    Lay l;
+    FTMI_TRY(hy_lay(g, "hy_sample_init", l));
+    return launch_init(l, "hy_sample_init", latents, nullptr, x, cols, st);
+}
+
+int hy_sample_step(const ftmi_hy_sample_geometry& g, const bf16_t* pred, float* x, const float* sigmas, int step, float true_cfg, bf16_t* cols, hipStream_t st) {
+    Lay l;
+    FTMI_TRY(hy_lay(g, "hy_sample_step", l));
+    if (pred && (true_cfg != 1.0f) != (g.P == 2)) return set_error(FTMI_ERR_INVALID, "hy_sample_step: P is 2 with true_cfg != 1 and 1 with true_cfg == 1");
+    if (pred && (!sigmas || step < 0)) return set_error(FTMI_ERR_INVALID, "hy_sample_step: the sigma table or the step index is missing");
+    if (misaligned(pred) || misaligned(x) || misaligned(cols)) return set_error(FTMI_ERR_INVALID, "hy_sample_step: tensors must be 16-byte aligned");
+    const long n8 = (long)g.B * l.S * l.Kc / 8, blocks = (n8 + 255) / 256;
+    if (g.P == 2)
+        hipLaunchKernelGGL((hy_sample_step_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, st, pred, x, sigmas, step, true_cfg, cols, n8);
+    else
+        hipLaunchKernelGGL((hy_sample_step_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, st, pred, x, sigmas, step, true_cfg, cols, n8);
+    return check_launch("hy_sample_step");
+}
+
+int hy_sample_finish(const ftmi_hy_sample_geometry& g, const float* x, float k, bf16_t* latents, hipStream_t st) {
+    Lay l;
+    FTMI_TRY(hy_lay(g, "hy_sample_finish", l));
+    return launch_finish(l, "hy_sample_finish", x, ScalarAffine{k}, latents, st);
 }
 
 int wan_sample_mod(const bf16_t* const* tables, int L, const bf16_t* tproj, float* mod, int rows, int D, hipStream_t st) {

@@ -61,7 +61,8 @@ class MI355XHunyuanVideoSpecOps:
 class MI355XHunyuanVideoModelSpecification(MI355XHunyuanVideoSpecOps):
     """Mirror of ``HunyuanVideoModelSpecification`` (finetrainers/models/hunyuan_video/base_specification.py:100-420) for the SFT hot path: same constructor
     keywords, ``_resolution_dim_keys``, ``load_diffusion_models``, ``collate_*``, ``forward`` with the reference's signature, ``_save_lora_weights``.
-    Text encoders (Llama + CLIP), VAE, pipeline and validation stay with the reference."""
+    Text encoders (Llama + CLIP), VAE and pipeline stay with the reference; ``validation_latents`` runs the denoising loop of its validation over this
+    backend's transformer (sampler.py) and hands the latents to the reference's VAE decode."""
 
     def __init__(self, pretrained_model_name_or_path: Optional[str] = "hunyuanvideo-community/HunyuanVideo", tokenizer_id: Optional[str] = None,
                  text_encoder_id: Optional[str] = None, transformer_id: Optional[str] = None, vae_id: Optional[str] = None,
@@ -125,6 +126,25 @@ class MI355XHunyuanVideoModelSpecification(MI355XHunyuanVideoSpecOps):
         cond = {k: condition_model_conditions[k] for k in ("encoder_hidden_states", "encoder_attention_mask", "pooled_projections")}
         return MI355XHunyuanVideoSpecOps.forward(self, transformer, latents, cond, sigmas, guidance=guidance, compute_posterior=compute_posterior,
                                                  posterior_noise=posterior_noise, noise=noise, generator=generator)
+
+    def validation_latents(self, transformer, prompt_embeds: torch.Tensor, prompt_attention_mask: Optional[torch.Tensor], pooled_prompt_embeds: torch.Tensor,
+                           num_frames: int, height: int, width: int, negative_prompt_embeds: Optional[torch.Tensor] = None,
+                           negative_prompt_attention_mask: Optional[torch.Tensor] = None, negative_pooled_prompt_embeds: Optional[torch.Tensor] = None,
+                           num_inference_steps: int = 50, guidance_scale: float = 6.0, true_cfg_scale: float = 1.0,
+                           generator: Optional[torch.Generator] = None, scheduler_config=None, latents: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The denoising loop of ``validation`` (base_specification.py:332-355 runs ``HunyuanVideoPipeline``) over this backend's transformer, in latent space:
+        ``MI355XHunyuanVideoLatentSampler.sample`` on the LATENT grid (``num_frames`` = (video frames - 1) / 4 + 1, ``height`` / ``width`` = pixels / 8) ->
+        ``latents / vae_scaling_factor`` [B, C, num_frames, height, width] bf16 for the reference pipeline's VAE decode.  The noise is
+        ``randn([B, C, F, H, W], fp32, generator)`` on the transformer's device (or ``latents``)."""
+        from .sampler import MI355XHunyuanVideoLatentSampler
+
+        if latents is None:
+            latents = torch.randn((prompt_embeds.shape[0], transformer.config.in_channels, num_frames, height, width), generator=generator,
+                                  device=transformer.device, dtype=torch.float32)
+        return MI355XHunyuanVideoLatentSampler(transformer, scheduler_config).sample(
+            latents, prompt_embeds, prompt_attention_mask, pooled_prompt_embeds, negative_prompt_embeds=negative_prompt_embeds,
+            negative_prompt_attention_mask=negative_prompt_attention_mask, negative_pooled_prompt_embeds=negative_pooled_prompt_embeds,
+            num_inference_steps=num_inference_steps, guidance_scale=guidance_scale, true_cfg_scale=true_cfg_scale, scaling_factor=self.scaling_factor)
 
     def _save_lora_weights(self, directory: str, transformer_state_dict: Optional[Dict[str, torch.Tensor]] = None, scheduler=None,
                            metadata: Optional[Dict[str, str]] = None, *args, **kwargs) -> None:

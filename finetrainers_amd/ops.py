@@ -1271,3 +1271,77 @@ def cog_sample(cfg, weights, cols, x, text, temb_silu, head_shift, head_onep, co
         workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
     check(_lib.load().ftmi_cog_sample(ctypes.byref(cfg), ctypes.byref(weights), ptr(cols), ptr(x), ptr(text), ptr(temb_silu), ptr(head_shift), ptr(head_onep),
                                       ptr(coef), ptr(workspace), workspace.numel(), stream_ptr()), "ftmi_cog_sample")
+
+
+# ---- HunyuanVideo latent sampling (include/ftmi355.h: ftmi_hy_sample_*; csrc/sample_layout.hip, csrc/hy_sample_dit.hip) --------------------------------------
+def hy_sample_geometry(B: int, C: int, frames: int, height: int, width: int, patch: int = 2, patch_t: int = 1, true_cfg: bool = False) -> "_lib.HySampleGeometry":
+    """The layout of a sampling run: latents [B, C, frames, height, width], x [B, S, Kc], cols [P B S, Kc], pred [P B, S, Kc]; P = 2 with true CFG."""
+    return _lib.HySampleGeometry(B=B, C=C, F=frames, H=height, W=width, p=patch, pt=patch_t, P=2 if true_cfg else 1)
+
+
+def hy_sample_init(geo, latents, x=None, cols=None):
+    """noise fp32 [B, C, F, H, W] -> (x fp32 [B, S, Kc], cols bf16 [P B S, Kc]): ftmi_hy_sample_init."""
+    require_gpu_tensor(latents, "latents", torch.float32)
+    if tuple(latents.shape) != (geo.B, geo.C, geo.F, geo.H, geo.W) or not latents.is_contiguous():
+        raise ValueError(f"hy_sample_init: latents must be contiguous [{geo.B}, {geo.C}, {geo.F}, {geo.H}, {geo.W}], got {tuple(latents.shape)}")
+    S, Kc = _cog_sample_dims(geo)
+    x = torch.empty((geo.B, S, Kc), dtype=torch.float32, device=latents.device) if x is None else x
+    cols = torch.empty((geo.P * geo.B * S, Kc), dtype=bf16, device=latents.device) if cols is None else cols
+    _cog_sample_buffers(geo, x, cols, "hy_sample_init")
+    check(_lib.load().ftmi_hy_sample_init(ctypes.byref(geo), ptr(latents), ptr(x), ptr(cols), stream_ptr()), "ftmi_hy_sample_init")
+    return x, cols
+
+
+def hy_sample_step(geo, pred, x, sigmas, step: int, true_cfg: float, cols=None) -> None:
+    """One sampler step in place (ftmi_hy_sample_step): pred bf16 [P B, S, Kc] (None: only the bf16 copies), x fp32 [B, S, Kc], sigmas fp32 [n + 1] on the
+    device (x <- x + (sigmas[step + 1] - sigmas[step]) v), cols bf16 [P B S, Kc] (None: only the update)."""
+    _cog_sample_buffers(geo, x, cols, "hy_sample_step")
+    S, Kc = _cog_sample_dims(geo)
+    if pred is not None:
+        require_gpu_tensor(pred, "pred", bf16)
+        if pred.numel() != geo.P * geo.B * S * Kc or not pred.is_contiguous():
+            raise ValueError(f"hy_sample_step: pred must be contiguous [{geo.P * geo.B}, {S}, {Kc}], got {tuple(pred.shape)}")
+        require_gpu_tensor(sigmas, "sigmas", torch.float32)
+        if sigmas.dim() != 1 or not sigmas.is_contiguous() or not 0 <= int(step) < sigmas.shape[0] - 1:
+            raise ValueError("hy_sample_step: sigmas is a contiguous fp32 [n + 1] table and step one of its first n entries")
+    check(_lib.load().ftmi_hy_sample_step(ctypes.byref(geo), ptr(pred), ptr(x), ptr(sigmas), int(step), float(true_cfg), ptr(cols), stream_ptr()),
+          "ftmi_hy_sample_step")
+
+
+def hy_sample_finish(geo, x, k: float):
+    """x fp32 [B, S, Kc] -> latents bf16 [B, C, F, H, W] = bf16(x * k) (ftmi_hy_sample_finish)."""
+    _cog_sample_buffers(geo, x, None, "hy_sample_finish")
+    out = torch.empty((geo.B, geo.C, geo.F, geo.H, geo.W), dtype=bf16, device=x.device)
+    check(_lib.load().ftmi_hy_sample_finish(ctypes.byref(geo), ptr(x), float(k), ptr(out), stream_ptr()), "ftmi_hy_sample_finish")
+    return out
+
+
+def hy_sample_workspace_bytes(cfg) -> int:
+    n = int(_lib.load().ftmi_hy_sample_workspace_bytes(ctypes.byref(cfg)))
+    if n == 0:
+        raise ValueError(f"hy_sample: {_lib.last_error()}")
+    return n
+
+
+def hy_sample(cfg, weights, cols, x, temb_silu, enc, head_shift, head_onep, key_bias, rope_cos, rope_sin, sigmas, workspace=None) -> None:
+    """The whole denoising loop in ONE call (ftmi_hy_sample), in place on ``x`` / ``cols`` (as ``hy_sample_init`` wrote them).  temb_silu bf16 [steps, P B, D];
+    enc bf16 [steps, P B, T, D] (the refined text of every step, unconditional rows first); head_shift / head_onep bf16 [steps, P B, D]; key_bias fp32
+    [P B, T + S] or None; rope_cos / rope_sin fp32 [S, 128]; sigmas fp32 [steps + 1] on the device.  ``workspace``: a uint8 GPU tensor of at least
+    ``hy_sample_workspace_bytes(cfg)`` (allocated when None)."""
+    geo, n, D = cfg.geo, cfg.steps, cfg.D
+    _cog_sample_buffers(geo, x, cols, "hy_sample")
+    S, _ = _cog_sample_dims(geo)
+    rows = geo.P * geo.B
+    want = [("temb_silu", temb_silu, bf16, (n, rows, D)), ("enc", enc, bf16, (n, rows, cfg.T, D)), ("head_shift", head_shift, bf16, (n, rows, D)),
+            ("head_onep", head_onep, bf16, (n, rows, D)), ("rope_cos", rope_cos, torch.float32, (S, 128)), ("rope_sin", rope_sin, torch.float32, (S, 128)),
+            ("sigmas", sigmas, torch.float32, (n + 1,))]
+    if key_bias is not None:
+        want.append(("key_bias", key_bias, torch.float32, (rows, cfg.T + S)))
+    for name, t, dt, shape in want:
+        if t is None or not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"hy_sample: {name} must be a contiguous {dt} {shape} GPU tensor, got {None if t is None else tuple(t.shape)}")
+    need = hy_sample_workspace_bytes(cfg)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
+    check(_lib.load().ftmi_hy_sample(ctypes.byref(cfg), ctypes.byref(weights), ptr(cols), ptr(x), ptr(temb_silu), ptr(enc), ptr(head_shift), ptr(head_onep),
+                                     ptr(key_bias), ptr(rope_cos), ptr(rope_sin), ptr(sigmas), ptr(workspace), workspace.numel(), stream_ptr()), "ftmi_hy_sample")

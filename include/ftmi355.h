@@ -1014,6 +1014,75 @@ size_t ftmi_cog_sample_workspace_bytes(const ftmi_cog_sample_config* cfg);
 int ftmi_cog_sample(const ftmi_cog_sample_config* cfg, const ftmi_cog_sample_weights* w, void* cols, float* x, const void* text, const void* temb_silu,
                     const void* head_shift, const void* head_onep, const float* coef, void* workspace, size_t workspace_bytes, ftmi_stream stream);
 
+/* ---- HunyuanVideo latent sampling (csrc/sample_layout.hip: the layout kernels; csrc/hy_sample_dit.hip: the loop) ----
+ * The denoising loop of the reference's validation (finetrainers/models/hunyuan_video/base_specification.py:332-355 runs HunyuanVideoPipeline over the
+ * transformer that is being trained) in latent space, text-to-video: [upstream, unpinned] HunyuanVideoPipeline + FlowMatchEulerDiscreteScheduler (static
+ * shift 7, embedded guidance; optional true classifier-free guidance over a negative prompt).
+ * The patch embedding's operand order and proj_out's column order are the same, (c, pt, ph, pw), so the state lives there as for CogVideoX:
+ *   x     fp32 [B, S, Kc]      Kc = C pt p p columns (64 for the checkpoint), S = (F / pt)(H / p)(W / p) tokens in (f, h, w) order
+ *   cols  bf16 [P B S, Kc]     the patch-embedding GEMM's operand, bf16(x) in every row group; P = 2 with true CFG (unconditional rows first), 1 without
+ *   pred  bf16 [P B, S, Kc]    as proj_out writes it: the same columns, so a step is a row-major stream with no permutation
+ * FTMI_ERR_UNSUPPORTED: Kc % 8, a latent size that is not whole patches; FTMI_ERR_INVALID: empty extents, P, misaligned tensors (16 bytes). */
+typedef struct ftmi_hy_sample_geometry {
+    int B, C;    /* samples, latent channels */
+    int F, H, W; /* latent grid */
+    int p, pt;   /* spatial patch, temporal patch (1 for every published checkpoint) */
+    int P;       /* row groups of cols / pred: 2 with true CFG, 1 without */
+} ftmi_hy_sample_geometry;
+/* noise fp32 [B, C, F, H, W] -> x (the patchified values, exact) and bf16(x) in all P row groups of cols (replaces the pipeline's prepare_latents hand-over
+ * and the transformer's per-step Conv3d patchify). */
+int ftmi_hy_sample_init(const ftmi_hy_sample_geometry* geo, const float* latents, float* x, void* cols, ftmi_stream stream);
+/* One step (replaces the pipeline's neg + true_cfg_scale * (noise_pred - neg) and FlowMatchEulerDiscreteScheduler.step): dt = sigmas[step + 1] - sigmas[step]
+ * read on the device from the fp32 table [steps + 1];  d = c - u; v = fma(g, d, u) (true_cfg == 1: v = c, pred has no unconditional half);
+ * x <- fma(dt, v, x) in fp32; bf16(x) into every row group of cols.  pred == NULL: only the copies; cols == NULL: only the update. */
+int ftmi_hy_sample_step(const ftmi_hy_sample_geometry* geo, const void* pred, float* x, const float* sigmas, int step, float true_cfg, void* cols,
+                        ftmi_stream stream);
+/* latents bf16 [B, C, F, H, W] = bf16(x * k), the inverse permutation of init (replaces the pipeline's latents / vae.config.scaling_factor; k = 1 / it). */
+int ftmi_hy_sample_finish(const ftmi_hy_sample_geometry* geo, const float* x, float k, void* latents, ftmi_stream stream);
+
+/* The whole denoising loop as ONE call, no host synchronisation (replaces the loop of HunyuanVideoPipeline.__call__ the reference's validation drives,
+ * base_specification.py:332-355).  Per step, the launches of MI355XHunyuanVideoTransformer3DModel.forward at batch P B, in its order: the patch-embedding NT
+ * GEMM over cols; Ld dual-stream blocks through ftmi_hy_dual_forward (one call per sample row, the streams alternating between two buffers each, the last one
+ * writing into the rows of the joint buffer [P B, T + S, D], text first); Ls single-stream blocks through ftmi_hy_single_forward at batch P B over two joint
+ * buffers; ftmi_cog_ln_mod_fwd on the video rows with the step's per-row shift / 1 + scale (no affine); the proj_out NT GEMM; ftmi_hy_sample_step.  Every
+ * block writes the same `saved` slot and shares one scratch area: nothing in the workspace grows with Ld or Ls.  Bit-identical to that composition.
+ * fp8 storage: upcasts != NULL lists, per block (dual blocks first), what ftmi_fp8_upcast has to write into `arena` right before the block's launches;
+ * upcast_count[l] entries belong to block l.  The block structures then point into the arena.  NULL: bf16 weights.
+ * The caller supplies what does not depend on the state: temb_silu bf16 [steps, P B, D] = silu(conditioning vector), enc bf16 [steps, P B, T, D] (the refined
+ * text depends on the timestep), head_shift / head_onep bf16 [steps, P B, D], key_bias fp32 [P B, T + S] (-inf on padded text keys) or NULL, the rotary tables
+ * fp32 [S, 128], sigmas fp32 [steps + 1] on the device.  x / cols: in and out (ftmi_hy_sample_init wrote them).  Workspace: ftmi_hy_sample_workspace_bytes
+ * (0 for a refused configuration); a smaller one is FTMI_ERR_INVALID. */
+typedef struct ftmi_hy_sample_upcast {
+    const void* src;  /* fp8 e4m3fn [rows, cols] */
+    int rows, cols;
+    size_t offset;    /* bf16 elements from the start of the arena */
+} ftmi_hy_sample_upcast;
+typedef struct ftmi_hy_sample_config {
+    ftmi_hy_sample_geometry geo;
+    int T;                    /* text tokens */
+    int D, H, mlp;            /* width = H x 128, feed-forward width */
+    int Ld, Ls;               /* dual-stream, single-stream blocks */
+    int r;                    /* LoRA rank (0: none; multiple of 64) */
+    float lora_scale, eps;
+    int gemm_variant;         /* 8 */
+    int steps;
+    float true_cfg;           /* != 1 needs geo.P == 2 */
+} ftmi_hy_sample_config;
+typedef struct ftmi_hy_sample_weights {
+    const ftmi_hy_dual_weights* dual;        /* HOST array [Ld]; the "_t" copies are not read */
+    const ftmi_hy_single_weights* single;    /* HOST array [Ls] */
+    const ftmi_hy_sample_upcast* upcasts;    /* HOST array, block after block; NULL: bf16 weights */
+    const int* upcast_count;                 /* HOST array [Ld + Ls] */
+    void* arena;                             /* bf16, device */
+    const void *patch_w, *patch_b;           /* bf16 [D, Kc], [D] */
+    const void *proj_w, *proj_b;             /* bf16 [Kc, D], [Kc] */
+    const void *ones, *zeros;                /* bf16 [D] of 1 and of 0 (the affine-free output norm) */
+} ftmi_hy_sample_weights;
+size_t ftmi_hy_sample_workspace_bytes(const ftmi_hy_sample_config* cfg);
+int ftmi_hy_sample(const ftmi_hy_sample_config* cfg, const ftmi_hy_sample_weights* w, void* cols, float* x, const void* temb_silu, const void* enc,
+                   const void* head_shift, const void* head_onep, const float* key_bias, const float* rope_cos, const float* rope_sin, const float* sigmas,
+                   void* workspace, size_t workspace_bytes, ftmi_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

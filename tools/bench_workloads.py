@@ -364,11 +364,12 @@ def build_wan_i2v_lora(args, par, dev) -> Dict[str, Any]:
 # HunyuanVideo LoRA, fp8 weight storage (configs[4]): 61 x 544 x 960 -> latents [1, 16, 16, 68, 120], 32 640 video + 256 text tokens,
 # 20 dual-stream + 40 single-stream blocks (12.8 B parameters), batch 1 per GPU
 # ------------------------------------------------------------------------------------------------------------------------------------------
-def build_hunyuan(args, par, dev) -> Dict[str, Any]:
+def _random_hunyuan(nd: int, ns: int, rank: int, dev):
+    """Random-init weights of the DiT rounded to fp8-representable values and stored as fp8 bytes (layerwise casting), with rank-``rank`` adapters whose B is
+    non-zero -> (model, the generator that drew them)."""
     from finetrainers_amd import ops
-    from finetrainers_amd.hunyuan_video import HunyuanVideoTransformerConfig, MI355XHunyuanVideoSFTStep, MI355XHunyuanVideoTransformer3DModel
+    from finetrainers_amd.hunyuan_video import HunyuanVideoTransformerConfig, MI355XHunyuanVideoTransformer3DModel
 
-    nd, ns = (20, 40) if args.layers <= 0 else (max(1, args.layers // 3), max(1, args.layers - args.layers // 3))
     cfg = HunyuanVideoTransformerConfig(num_layers=nd, num_single_layers=ns)
     model = MI355XHunyuanVideoTransformer3DModel(cfg, device=dev)
     g = torch.Generator(device=dev).manual_seed(0)
@@ -391,13 +392,22 @@ def build_hunyuan(args, par, dev) -> Dict[str, Any]:
             for name in getattr(blk, "_TRANSPOSED", ("wq", "wk", "wv", "proj_mlp_w", "proj_out_w")):
                 setattr(blk, name + "_t", ops.transpose_bf16(getattr(blk, name)))
     model.apply_layerwise_casting()
-    model.add_adapter(r=args.rank, lora_alpha=float(args.rank))
-    ckpt = bool(getattr(args, "gradient_checkpointing", False))
-    if ckpt:
-        model.apply_activation_checkpointing("full")
+    model.add_adapter(r=rank, lora_alpha=float(rank))
     with torch.no_grad():
         for p in model.lora_parameters()[1::2]:
             p.normal_(0, 0.01, generator=g)  # B != 0 so every gradient path carries data
+    return model, g
+
+
+def build_hunyuan(args, par, dev) -> Dict[str, Any]:
+    from finetrainers_amd.hunyuan_video import MI355XHunyuanVideoSFTStep
+
+    nd, ns = (20, 40) if args.layers <= 0 else (max(1, args.layers // 3), max(1, args.layers - args.layers // 3))
+    model, g = _random_hunyuan(nd, ns, args.rank, dev)
+    cfg = model.config
+    ckpt = bool(getattr(args, "gradient_checkpointing", False))
+    if ckpt:
+        model.apply_activation_checkpointing("full")
     step = MI355XHunyuanVideoSFTStep(model, lr=2e-5, guidance=1.0, generator=torch.Generator(device=dev).manual_seed(1 + par.rank),
                                      parallel=par if par.world_size > 1 else None)
     g.manual_seed(100 + par.rank)
@@ -696,6 +706,114 @@ def build_cog_sample(args, par, dev) -> Dict[str, Any]:
     }
 
 
+# ------------------------------------------------------------------------------------------------------------------------------------------
+# HunyuanVideo validation sampling in latent space (finetrainers_amd/hunyuan_video/sampler.py) at BASELINE configs[4]'s geometry: 61 x 544 x 960 -> latents
+# [1, 16, 16, 68, 120] = 32 640 video + 256 text tokens (200 real), 20 dual-stream + 40 single-stream blocks, fp8 weight storage, random weights with
+# rank-`--rank` adapters (run with --rank 64), embedded guidance 6, no true CFG (the pipeline's default).  One "step" of this workload is one ftmi_hy_sample
+# call of `SAMPLE_STEPS` denoising steps; the report interleaves it with the same loop composed in Python (model.forward under no_grad + ops.hy_sample_step)
+# and times the step kernel on its own.
+# ------------------------------------------------------------------------------------------------------------------------------------------
+def build_hy_sample(args, par, dev) -> Dict[str, Any]:
+    from finetrainers_amd import ops
+    from finetrainers_amd.hunyuan_video import MI355XHunyuanVideoLatentSampler, hy_flow_match_sigmas
+
+    nd, ns = (20, 40) if args.layers <= 0 else (max(1, args.layers // 3), max(1, args.layers - args.layers // 3))
+    model, _ = _random_hunyuan(nd, ns, args.rank, dev)
+    cfg = model.config
+    g = torch.Generator(device=dev).manual_seed(3)
+    B, C, F_, H, W, T, guidance_scale, n = 1, 16, 16, 68, 120, 256, 6.0, SAMPLE_STEPS
+    S, Kc, D = F_ * (H // 2) * (W // 2), 4 * C, cfg.inner_dim
+    sampler = MI355XHunyuanVideoLatentSampler(model)
+    text = torch.randn((B, T, cfg.text_embed_dim), generator=g, device=dev).to(bf16)
+    pooled = torch.randn((B, cfg.pooled_projection_dim), generator=g, device=dev).to(bf16)
+    mask = torch.ones(B, T, dtype=torch.bool, device=dev)
+    mask[:, 200:] = False
+    noise = torch.randn((B, C, F_, H, W), generator=g, device=dev)
+    sig = hy_flow_match_sigmas(n)
+    sig_dev = sig.to(torch.float32).to(dev)
+    geo = sampler.geometry(B, F_, H, W, true_cfg=False)
+    with torch.no_grad():
+        temb, enc, shift, onep = sampler.step_tables(sig, guidance_scale, text, mask, pooled)
+    key_bias = sampler.key_bias(mask, geo, T)
+    cos, sin = (t.contiguous() for t in model._rope(F_, H, W))
+    ccfg, weights, keep = sampler.c_arguments(geo, T, n, 1.0)
+    ws_bytes = ops.hy_sample_workspace_bytes(ccfg)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    guidance = torch.full((B,), guidance_scale, dtype=bf16, device=dev) * 1000.0
+    ts = sampler.timesteps(sig).tolist()
+    torch.cuda.synchronize()
+    resident = torch.cuda.memory_allocated() / 1e9  # the model, the step tables and the planned workspace: what both paths start from
+    torch.cuda.reset_peak_memory_stats()  # (building the model peaks above either loop: bf16 weights and their transposes before the fp8 cast)
+
+    def one_call():
+        x, cols = ops.hy_sample_init(geo, noise)
+        ops.hy_sample(ccfg, weights, cols, x, temb, enc, shift, onep, key_bias, cos, sin, sig_dev, workspace=ws)
+        return None
+
+    one_call.keep = keep  # the host arrays the weight structure points into live as long as the call does
+
+    @torch.no_grad()
+    def composed():
+        x, cols = ops.hy_sample_init(geo, noise)
+        for i in range(n):
+            hidden = cols.view(B, F_, H // 2, W // 2, C, 1, 2, 2).permute(0, 4, 1, 5, 2, 6, 3, 7).reshape(B, C, F_, H, W)
+            out = model(hidden, torch.full((B,), ts[i], dtype=torch.float32, device=dev), text, mask, pooled, guidance=guidance)[0]
+            pred = out.view(B, C, F_, 1, H // 2, 2, W // 2, 2).permute(0, 2, 4, 6, 1, 3, 5, 7).reshape(B, S, Kc)
+            ops.hy_sample_step(geo, pred, x, sig_dev, i, 1.0, cols)
+
+    def once(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    def report(one_call_ms: float) -> Dict[str, Any]:
+        peak_one = torch.cuda.max_memory_allocated() / 1e9
+        torch.cuda.reset_peak_memory_stats()
+        composed()  # warm
+        a_ms, b_ms = [], []
+        for _ in range(3):  # interleaved: both paths see the same clocks and the same neighbours
+            a_ms.append(once(one_call))
+            b_ms.append(once(composed))
+        peak_comp = torch.cuda.max_memory_allocated() / 1e9
+        x, cols = ops.hy_sample_init(geo, noise)
+        pred = torch.randn((B, S, Kc), generator=g, device=dev).to(bf16)
+        reps = 50
+        for _ in range(5):
+            ops.hy_sample_step(geo, pred, x, sig_dev, 1, 1.0, cols)
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps):
+            ops.hy_sample_step(geo, pred, x, sig_dev, 1, 1.0, cols)
+        b.record()
+        torch.cuda.synchronize()
+        us = a.elapsed_time(b) * 1e3 / reps
+        nbytes = B * S * Kc * 10  # per element of x: read pred 2 + x 4, write x 4 + cols 2
+        return {"ms_per_denoising_step_one_call": sorted(a_ms)[1] / n, "ms_per_denoising_step_python_composition": sorted(b_ms)[1] / n,
+                "ms_per_denoising_step_one_call_first_pass": one_call_ms / n, "interleaved_ms_one_call": a_ms, "interleaved_ms_python_composition": b_ms,
+                "peak_memory_gb_one_call": peak_one, "peak_memory_gb_python_composition": peak_comp, "resident_gb_before_either_loop": resident,
+                "workspace_gb": ws_bytes / 1e9, "step_kernel_us": us, "step_kernel_bytes": nbytes, "step_kernel_gbps": nbytes / (us * 1e-6) / 1e9}
+
+    N = T + S
+    mlp = int(D * cfg.mlp_ratio)
+    dual = 2.0 * S * (4 * D * D + 2 * D * mlp) + 2.0 * T * (4 * D * D + 2 * D * mlp) + 4.0 * N * N * D
+    single = 2.0 * N * (3 * D * D + D * mlp + (D + mlp) * D) + 4.0 * N * N * D
+    full = (nd, ns) == (20, 40)
+    return {
+        "one_step": one_call,
+        "report": report,
+        "samples_per_step": 1.0 / n,
+        "step_tflop": n * (nd * dual + ns * single) / 1e12,  # linears + joint attention, forward only
+        "metric": f"ftmi_hy_sample: one call of {n} denoising steps, HunyuanVideo 61x544x960, embedded guidance 6 (value: denoising steps per ms are in the report)",
+        "data": "random noise [1,16,16,68,120] + random text embeds [1,256,4096] (200 real tokens) + pooled [1,768], random-init weights of the HunyuanVideo DiT "
+                "stored as fp8 bytes",
+        "config": {"workload": f"HunyuanVideo latent sampling, rank={args.rank} adapters, fp8 weight storage, {S} video + {T} text tokens, 1 model row, "
+                               f"{nd} dual-stream + {ns} single-stream blocks" + ("" if full else " -- REDUCED depth"), "seq_len": N, "denoising_steps_per_call": n},
+        "layers": nd + ns,
+    }
+
+
 def _cog_training_workspace(model, B: int, N: int) -> int:
     import ctypes
 
@@ -711,6 +829,7 @@ WORKLOADS = {"cogvideox": (build_cogvideox, lambda a, c: cpu_baseline_cogvideox(
              "wan_i2v_lora": (build_wan_i2v_lora, None),  # (no host yardstick: this row runs through this file's own command line only)
              "wan_sample": (build_wan_sample, None),  # (validation sampling: forward only; this file's own command line only)
              "cog_sample": (build_cog_sample, None),  # (validation sampling: forward only; this file's own command line only; --rank 64)
+             "hy_sample": (build_hy_sample, None),  # (validation sampling: forward only; this file's own command line only; --rank 64)
              "hunyuan": (build_hunyuan, cpu_baseline_hunyuan)}
 
 

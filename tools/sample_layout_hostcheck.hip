@@ -1,6 +1,7 @@
-// Stand-alone host check of the latent samplers' layout derivation (csrc/sample_layout.hip: wan_lay / cog_lay, lay_derive, launch_limits) for a sanitizer
-// build: every geometry of tests/test_gpu_wan_sampling.py and tests/test_gpu_cog_sampling.py must be accepted, every refused geometry of
-// tests/test_wan_sampling_host.py and tests/test_cog_sampling_host.py refused with its code and text.  Launches nothing and needs no GPU.
+// Stand-alone host check of the latent samplers' layout derivation (csrc/sample_layout.hip: wan_lay / cog_lay / hy_lay, lay_derive, launch_limits) for a
+// sanitizer build: every geometry of tests/test_gpu_wan_sampling.py, tests/test_gpu_cog_sampling.py and tests/test_gpu_hy_sampling.py must be accepted, every
+// refused geometry of tests/test_wan_sampling_host.py, tests/test_cog_sampling_host.py and tests/test_hy_sampling_host.py refused with its code and text.
+// Launches nothing and needs no GPU.
 //   hipcc --offload-arch=gfx950 -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
 //         -I finetrainers_amd/csrc tools/sample_layout_hostcheck.hip -o tools/bin/sample_layout_hostcheck && tools/bin/sample_layout_hostcheck
 #include <cstdio>
@@ -39,6 +40,11 @@ static ftmi_cog_sample_geometry cog(int B, int F, int H, int W, int pt, int P, i
     g.B = B; g.C = 16; g.F = F; g.H = H; g.W = W; g.p = 2; g.pt = pt; g.P = P; g.drop = drop;
     return g;
 }
+static ftmi_hy_sample_geometry hy(int B, int F, int H, int W, int pt, int P) {
+    ftmi_hy_sample_geometry g = {};
+    g.B = B; g.C = 16; g.F = F; g.H = H; g.W = W; g.p = 2; g.pt = pt; g.P = P;
+    return g;
+}
 
 // an accepted layout: both launch limits hold, and the derived fields are the documented formulas
 static void accepted(const Lay& l, long sc, long sf) {
@@ -53,6 +59,7 @@ static void accepted(const Lay& l, long sc, long sf) {
 
 int main() {
     Lay l;
+    size_t lds0 = 0;
     // ---- accepted: the GPU tests' geometries
     const int wan_layouts[3][3] = {{64, 0, 1}, {192, 20, 1}, {128, 16, 2}};  // (Kp, Cx, copies): t2v, i2v, control
     const int wan_grids[4][3] = {{1, 2, 2}, {3, 4, 6}, {2, 4, 8}, {2, 8, 12}};
@@ -104,6 +111,31 @@ int main() {
     c = c0; c.drop = 1; cbad(c, FTMI_ERR_INVALID, "drop");
     c = c0; c.pt = 2; c.drop = 2; cbad(c, FTMI_ERR_INVALID, "drop");
     c = c0; c.B = 0; cbad(c, FTMI_ERR_INVALID, "positive");
+    // ---- HunyuanVideo: CogVideoX's layout over [B, C, F, H, W] latents (Wan's strides), nothing dropped
+    const int hy_grids[4][3] = {{1, 2, 2}, {3, 4, 6}, {2, 4, 8}, {3, 8, 12}};
+    for (auto& gr : hy_grids)
+        for (int B = 1; B <= 2; ++B)
+            for (int P = 1; P <= 2; ++P) {
+                EXPECT(hy_lay(hy(B, gr[0], gr[1], gr[2], 1, P), "hy", l) == 0);
+                EXPECT(l.Cx == 0 && l.copies == 1 && l.Kp == l.Kc && l.ld == l.Kc && l.Kc == 64 && l.drop == 0 && l.ph == 2 && l.pw == 2 && l.P == P);
+                accepted(l, (long)gr[0] * gr[1] * gr[2], (long)gr[1] * gr[2]);
+            }
+    auto hbad = [&](ftmi_hy_sample_geometry g, int code, const char* text) {
+        EXPECT(hy_lay(g, "hy_sample_step", l) == code && g_last.find(text) != std::string::npos && g_last.rfind("hy_sample_step: ", 0) == 0);
+    };
+    ftmi_hy_sample_geometry h0 = hy(1, 3, 8, 12, 1, 1), h = h0;
+    h = h0; h.C = 15; hbad(h, FTMI_ERR_UNSUPPORTED, "multiple of 8");
+    h = h0; h.C = 8; EXPECT(hy_lay(h, "hy", l) == 0);  // the layout holds; hy_sample refuses the patch width
+    h = h0; h.W = 13; hbad(h, FTMI_ERR_UNSUPPORTED, "whole patches");
+    h = h0; h.H = 7; hbad(h, FTMI_ERR_UNSUPPORTED, "whole patches");
+    h = h0; h.pt = 2; hbad(h, FTMI_ERR_UNSUPPORTED, "whole patches");
+    h = h0; h.P = 3; hbad(h, FTMI_ERR_INVALID, "P is 2");
+    h = h0; h.P = 0; hbad(h, FTMI_ERR_INVALID, "P is 2");
+    h = h0; h.B = 0; hbad(h, FTMI_ERR_INVALID, "positive");
+    h = h0; h.p = 0; hbad(h, FTMI_ERR_INVALID, "positive");
+    EXPECT(hy_lay(hy(1, 1, 2, 8194, 1, 1), "hy", l) == FTMI_ERR_UNSUPPORTED && g_last.find("patch or row too wide") != std::string::npos);
+    EXPECT(hy_lay(hy(0x7fffffff, 1, 2, 2, 1, 2), "hy", l) == 0 && launch_limits(l, true, "hy", lds0) == 0 && launch_limits(l, false, "hy", lds0) == 0);
+    EXPECT(hy_lay(hy(0x7fffffff, 2, 2, 2, 1, 2), "hy_sample_init", l) == FTMI_ERR_UNSUPPORTED && g_last == "hy_sample_init: too many elements for one launch");
     // ---- the launch limits: the LDS, whole 16-byte vectors, the grids
     size_t lds = 0;
     EXPECT(cog_lay(cog(1, 1, 2, 8192, 1, 1, 0), "cog", l) == 0 && launch_limits(l, true, "cog_sample_init", lds) == FTMI_ERR_UNSUPPORTED &&
