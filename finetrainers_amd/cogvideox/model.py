@@ -142,7 +142,8 @@ def unpatches_3d(tokens: torch.Tensor, F_: int, C: int, H: int, W: int, p: int, 
 
 class _BlockStackFunction(torch.autograd.Function):
     """All blocks in one C call per direction (``ftmi_cog_blocks_forward`` / ``_backward``, csrc/cog_dit.hip): the workspace holds every activation the
-    backward needs.  The LoRA gradients land in the model's flat gradient buffer (= the blocks' ``.grad`` views); with a data-parallel hook installed the
+    backward needs, or -- ``gradient_checkpointing`` -- the blocks' inputs and one block slot that the backward refills (``cfg`` travels in ``ctx``, so both
+    directions see the same layout).  The LoRA gradients land in the model's flat gradient buffer (= the blocks' ``.grad`` views); with a data-parallel hook installed the
     backward runs in block ranges and each finished range is handed to the hook (bucketed all-reduce overlapped with the remaining blocks)."""
 
     @staticmethod
@@ -269,6 +270,9 @@ class MI355XCogVideoXTransformer3DModel(nn.Module):
         self._ws_pool: List[torch.Tensor] = []
         self._grad_bucket_hook = None  # callable(lo, hi, grad_a[lo:hi], grad_b[lo:hi]) set by the data-parallel step
         self.grad_bucket_blocks = 0
+        # --gradient_checkpointing (trainer/sft_trainer/trainer.py:155-157; the reference's CogVideoX recipe sets it): off by default, see
+        # apply_activation_checkpointing
+        self.gradient_checkpointing = False
 
     @property
     def device(self) -> torch.device:
@@ -328,7 +332,8 @@ class MI355XCogVideoXTransformer3DModel(nn.Module):
         c = self.config
         return CogConfig(B=B, T=c.max_text_seq_length, S=N - c.max_text_seq_length, D=c.inner_dim, H=c.num_attention_heads, L=c.num_layers,
                          D_ff=c.ff_mult * c.inner_dim, D_temb=c.time_embed_dim, r=self.lora_rank,
-                         lora_scale=(self.transformer_blocks[0].lora_scale if self.lora_rank else 0.0), eps_norm=c.norm_eps, eps_qk=1e-6, gemm_variant=8)
+                         lora_scale=(self.transformer_blocks[0].lora_scale if self.lora_rank else 0.0), eps_norm=c.norm_eps, eps_qk=1e-6, gemm_variant=8,
+                         checkpoint=int(bool(self.gradient_checkpointing)))
 
     @torch.no_grad()
     def _refresh_lora_copies(self) -> None:
@@ -371,6 +376,30 @@ class MI355XCogVideoXTransformer3DModel(nn.Module):
     def _release_workspace(self, ws: Optional[torch.Tensor]) -> None:
         if ws is not None:
             self._ws_pool.append(ws)
+
+    # ---- --gradient_checkpointing (trainer/sft_trainer/trainer.py:155-157 -> utils/activation_checkpoint.py:24-49) ---------------------------------------
+    def apply_activation_checkpointing(self, checkpointing_type: str = "full", n_layer: int = 1) -> "MI355XCogVideoXTransformer3DModel":
+        """The reference wraps every transformer block ("full"; the trainer passes nothing else).  Here, for the native block stack: the workspace holds
+        one block slot instead of ``num_layers`` (``ftmi_cog_config.checkpoint = 1``), the forward keeps only the blocks' inputs and
+        ``ftmi_cog_blocks_backward`` runs a block's forward launches again, up to the feed-forward's pre-activation, right before its gradient launches.
+        The input-gradient chain is bit-identical to the un-checkpointed step; the LoRA weight gradients are launched per block instead of per range
+        (fp32 atomics: equal to summation order).  The price is about one extra forward per step.  "block_skip" would mix kept and recomputed blocks in
+        one workspace: not offered for this model.  The per-block Python composition (``native_blocks = False``) is a test vehicle and refuses the flag."""
+        if checkpointing_type != "full":
+            raise ValueError(f"CogVideoX: checkpointing_type {checkpointing_type!r} is not supported (only 'full', what the reference trainer uses)")
+        self.gradient_checkpointing = True
+        self._ws_pool.clear()  # a pooled kept-activation workspace would serve the smaller request and keep its size
+        return self
+
+    def enable_gradient_checkpointing(self) -> None:  # diffusers ModelMixin spelling
+        self.apply_activation_checkpointing("full")
+
+    def disable_gradient_checkpointing(self) -> None:
+        self.gradient_checkpointing = False
+
+    @property
+    def is_gradient_checkpointing(self) -> bool:
+        return bool(self.gradient_checkpointing)
 
     def add_adapter(self, r: int = 64, lora_alpha: float = 64.0) -> None:
         """LoRA on to_q / to_k / to_v / to_out.0 of every block (the default target regex, sft_trainer/config.py:24-26).  All adapters live in ONE
@@ -459,6 +488,8 @@ class MI355XCogVideoXTransformer3DModel(nn.Module):
             image_rotary_emb = tuple(t.to(device=self.device, dtype=torch.float32).contiguous() for t in image_rotary_emb)
         if self.proj_out_w_t is None:
             raise RuntimeError("load_diffusers_state_dict first")
+        if self.gradient_checkpointing and not self.native_blocks:
+            raise NotImplementedError("gradient checkpointing covers the native block stack (native_blocks = True); the per-block Python composition keeps its activations")
         tokens, emb, onep_out, shift_out = self._embed(hidden_states, encoder_hidden_states, timestep, ofs)
         T = self.config.max_text_seq_length
         if self.native_blocks and self.lora_flat is not None:

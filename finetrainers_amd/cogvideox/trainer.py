@@ -2,7 +2,8 @@
 specification): sigma draw -> DDIM noising -> DiT forward -> velocity -> x0 -> 1 / (1 - alphas_cumprod) weighted MSE -> backward -> LoRA-gradient
 average over the data-parallel ranks -> global-norm clip -> AdamW, the last two fused over the model-wide flat LoRA buffer.  The gradients of a
 block (native block stack: of a range of blocks) are all-reduced (AVG, asynchronously on RCCL's stream) as soon as the backward has produced them,
-while the earlier blocks still compute (``lora_step.FlatLoRAStep``)."""
+while the earlier blocks still compute (``lora_step.FlatLoRAStep``).  ``--gradient_checkpointing`` is the transformer's flag
+(``apply_activation_checkpointing`` / ``enable_gradient_checkpointing``): the step follows it, block ranges and buckets included, and takes no argument for it."""
 
 from __future__ import annotations
 

@@ -722,14 +722,18 @@ int ftmi_cog_unpatchify(const void* tokens, void* latents, int B, int F, int C, 
 
 size_t ftmi_cog_workspace_bytes(const ftmi_cog_config* cfg) { return cfg ? cog_workspace_bytes(*cfg) : 0; }
 
+static bool cog_checkpoint_ok(const ftmi_cog_config* cfg) { return !cfg || cfg->checkpoint == 0 || cfg->checkpoint == 1; }
+
 int ftmi_cog_blocks_forward(const ftmi_cog_config* cfg, const ftmi_cog_weights* w, const void* tokens_in, const void* temb_silu, void* tokens_out,
                             void* workspace, size_t workspace_bytes, ftmi_stream stream) {
+    if (!cog_checkpoint_ok(cfg)) return set_error(FTMI_ERR_INVALID, "ftmi_cog_blocks_forward: checkpoint must be 0 or 1");
     if (!cfg || !w || !tokens_in || !temb_silu || !tokens_out || !workspace) return set_error(FTMI_ERR_INVALID, "ftmi_cog_blocks_forward: null argument");
     return cog_blocks_forward(*cfg, *w, (const bf16_t*)tokens_in, (const bf16_t*)temb_silu, (bf16_t*)tokens_out, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int ftmi_cog_blocks_backward(const ftmi_cog_config* cfg, const ftmi_cog_weights* w, const void* tokens_in, const void* d_tokens_out, void* d_tokens_in,
                              float* grad_a, float* grad_b, void* workspace, size_t workspace_bytes, int l_hi, int l_lo, int accumulate, ftmi_stream stream) {
+    if (!cog_checkpoint_ok(cfg)) return set_error(FTMI_ERR_INVALID, "ftmi_cog_blocks_backward: checkpoint must be 0 or 1");
     if (!cfg || !w || !tokens_in || !d_tokens_out || !workspace || (cfg->r > 0 && (!grad_a || !grad_b)))
         return set_error(FTMI_ERR_INVALID, "ftmi_cog_blocks_backward: null argument");
     return cog_blocks_backward(*cfg, *w, (const bf16_t*)tokens_in, (const bf16_t*)d_tokens_out, (bf16_t*)d_tokens_in, grad_a, grad_b, workspace, workspace_bytes,

@@ -1,6 +1,7 @@
 // CogVideoX DiT block stack, forward / backward orchestrator: one C call launches all L blocks (or a range of blocks of the backward) on the
-// caller's stream; every activation the backward needs lives in the caller-provided workspace (no recompute).  The same design as ltx_dit.hip,
-// for the joint text+video block of CogVideoX (BASELINE config 3):
+// caller's stream; every activation the backward needs lives in the caller-provided workspace (no recompute), or -- cfg.checkpoint = 1, gradient
+// checkpointing -- only the inputs of the blocks do, and the backward refills ONE block slot by running the block's forward launches again up to the
+// feed-forward's pre-activation.  The same design as ltx_dit.hip, for the joint text+video block of CogVideoX (BASELINE config 3):
 //
 //   tokens [B, N = T + S, D] (text first)  ->  for each block:
 //     n1 = LN(x) * (1 + scale) + shift            (CogVideoXLayerNormZero; text rows and video rows have their own shift / scale / gate)
@@ -23,8 +24,9 @@ namespace ftmi {
 
 namespace {
 
-// What the forward walk reads of a workspace plan: the training layout (make_layout: one slot per block, the inputs of blocks 1 .. L-1 kept) and the
-// sampling layout (make_sample_plan: every block writes the SAME slot, blk_stride = 0, and the hidden state alternates between two buffers) share it.
+// What the forward walk reads of a workspace plan: the training layout (make_layout: one slot per block -- under gradient checkpointing one slot for
+// all, blk_stride = 0 --, the inputs of blocks 1 .. L-1 kept) and the sampling layout (make_sample_plan: every block writes the SAME slot, blk_stride = 0,
+// and the hidden state alternates between two buffers) share it.
 struct CogFwdLayout {
     size_t mod_raw, tables, hs, blk0, blk_stride;
     int hs_slots = 1;                                         // block l > 0 reads slot (l - 1) % hs_slots of hs and block l < L - 1 writes slot l % hs_slots
@@ -67,8 +69,10 @@ CogLayout make_layout(const ftmi_cog_config& c) {
     w.g_o = b.take(M * D * e2);
     w.dxa_qkv = b.take(M * 9 * r * e2);
     w.dxa_o = b.take(M * 3 * r * e2);
-    w.blk_stride = b.off;
-    w.blk0 = g.take(w.blk_stride * c.L);
+    // gradient checkpointing (cfg.checkpoint, the reference's --gradient_checkpointing: utils/activation_checkpoint.py:24-49 wraps every block): ONE block slot
+    // that every block writes -- the forward leaves only hs behind, the backward refills the slot block by block (cog_block_forward, for_backward)
+    w.blk_stride = c.checkpoint ? 0 : b.off;
+    w.blk0 = g.take(b.off * (c.checkpoint ? 1 : c.L));
     w.s_act = g.take(M * (size_t)c.D_ff * e2);
     w.s_f = g.take(M * D * e2);
     w.s_big = g.take(M * (size_t)c.D_ff * e2);
@@ -86,6 +90,7 @@ CogLayout make_layout(const ftmi_cog_config& c) {
 
 int check_cfg(const ftmi_cog_config& c) {
     if (c.B <= 0 || c.S <= 0 || c.T < 0 || c.L <= 0) return set_error(FTMI_ERR_INVALID, "cog: empty problem");
+    if (c.checkpoint != 0 && c.checkpoint != 1) return set_error(FTMI_ERR_INVALID, "cog: checkpoint must be 0 or 1");
     if (c.H * 64 != c.D || c.D % 128 != 0 || c.D > 4096) return set_error(FTMI_ERR_UNSUPPORTED, "cog: width must be heads x 64, a multiple of 128, at most 4096");
     if (c.r < 0 || (c.r % 64) != 0) return set_error(FTMI_ERR_UNSUPPORTED, "cog: LoRA rank must be 0 or a multiple of 64");
     if ((c.D_ff % 128) || (c.D_temb % 64)) return set_error(FTMI_ERR_UNSUPPORTED, "cog: D_ff must be a multiple of 128, the time-embedding width of 64");
@@ -132,12 +137,71 @@ AttnArgs attn_args(const ftmi_cog_config& c, const bf16_t* q, const bf16_t* k, c
     return a;
 }
 
-// The forward walk over all L blocks, for either layout: the modulation GEMM + table pass, then per block the launches listed at the top of this file.
-int cog_walk_forward(const ftmi_cog_config& c, const ftmi_cog_weights& w, const CogFwdLayout& L, const bf16_t* tokens_in, const bf16_t* temb_silu, bf16_t* tokens_out,
-                     void* ws, hipStream_t st) {
+// One block's forward launches (the list at the top of this file): reads h0, fills the block's slot, writes the block's output to hout.
+// for_backward: the recomputation pass of gradient checkpointing -- the same launches refill the slot and stop after the first feed-forward GEMM: its
+// pre-activation z is the last thing the backward reads.  hout is then neither read nor written (for block L - 1 it would be the caller's tokens_out).
+int cog_block_forward(const ftmi_cog_config& c, const ftmi_cog_weights& w, const CogFwdLayout& L, void* ws, int l, const bf16_t* h0, bf16_t* hout, bool for_backward,
+                      hipStream_t st) {
     const int N = c.T + c.S, M = c.B * N, D = c.D, r = c.r, V = c.gemm_variant;
     const long D2 = (long)D * D;
     const float s = c.lora_scale;
+    char* blk = reinterpret_cast<char*>(ws) + L.blk0 + L.blk_stride * l;
+    const Tables t = tables_of(c, ws, L, l);
+    const bf16_t* la = w.lora_a_sp ? P(w.lora_a_sp, (size_t)l * 4 * 2 * r * D) : nullptr;   // [4][2r][D]
+    const bf16_t* lb = w.lora_b_ext ? P(w.lora_b_ext, (size_t)l * 4 * D * 3 * r) : nullptr;  // [4][D][3r]
+    bf16_t* n1 = W(blk, L.n1);
+    bf16_t* qkv = W(blk, L.qkv);
+
+    {  // LayerNorm-zero 1
+        CogLnArgs a = ln_args(c, h0, 0, l, w);
+        a.shift = t.shift1; a.onep = t.onep1; a.y = n1;
+        FTMI_TRY(cog_ln_mod_fwd(a, st));
+    }
+    {  // fused q|k|v projection (+ LoRA)
+        GemmNtArgs a = linear_args(n1, D, M, P(w.w_qkv, (size_t)l * 3 * D2), D, 3 * D, D, P(w.b_qkv, (size_t)l * 3 * D), qkv, 3 * D, V);
+        if (r > 0) {
+            FTMI_TRY(gemm_nt(lora_down_args(n1, D, M, la, 3, D, r, s, W(blk, L.xa_qkv)), st));
+            lora_ext_fwd(a, W(blk, L.xa_qkv), 3, r, lb);
+        }
+        FTMI_TRY(gemm_nt(a, st));
+    }
+    for (int qk = 0; qk < 2; ++qk) {  // per-head LayerNorm of q and k (+ RoPE on the video rows)
+        CogLnArgs a;
+        a.x = qkv + (size_t)qk * D; a.ld = 3 * D; a.y = W(blk, qk ? L.kn : L.qn); a.ld_out = D; a.rows = M; a.D = D; a.eps = c.eps_qk;
+        a.w = P(w.qk_norm, ((size_t)l * 4 + qk * 2) * 64); a.b = P(w.qk_norm, ((size_t)l * 4 + qk * 2 + 1) * 64);
+        a.cos = w.rope_cos; a.sin = w.rope_sin; a.rows_per_batch = N; a.seg0 = w.rope_cos ? c.T : 0;
+        FTMI_TRY(cog_head_ln_fwd(a, st));
+    }
+    {  // joint attention
+        FTMI_TRY(attn_fwd(attn_args(c, W(blk, L.qn), W(blk, L.kn), qkv, W(blk, L.o), WF(blk, L.lse)), st));
+    }
+    {  // to_out (+ LoRA), gated residual
+        GemmNtArgs a = linear_args(W(blk, L.o), D, M, P(w.w_o, (size_t)l * D2), D, D, D, P(w.b_o, (size_t)l * D), W(ws, L.s_f), D, V);
+        if (r > 0) {
+            FTMI_TRY(gemm_nt(lora_down_args(W(blk, L.o), D, M, la + 3L * 2 * r * D, 1, D, r, s, W(blk, L.xa_o)), st));
+            lora_ext_fwd(a, W(blk, L.xa_o), 1, r, lb + 3L * D * 3 * r);
+        }
+        FTMI_TRY(gemm_nt(a, st));
+        FTMI_TRY(gate_res(c, h0, W(ws, L.s_f), t.gate1, W(blk, L.h1), st));
+    }
+    {  // LayerNorm-zero 2, feed-forward, gated residual
+        CogLnArgs a = ln_args(c, W(blk, L.h1), 1, l, w);
+        a.shift = t.shift2; a.onep = t.onep2; a.y = W(blk, L.n2);
+        FTMI_TRY(cog_ln_mod_fwd(a, st));
+        GemmNtArgs f1 = linear_args(W(blk, L.n2), D, M, P(w.w_ff1, (size_t)l * c.D_ff * D), D, c.D_ff, D, P(w.b_ff1, (size_t)l * c.D_ff), W(ws, L.s_act), c.D_ff, V);
+        f1.out2 = W(blk, L.z); f1.ldo2 = c.D_ff; f1.epi = EPI_GELU;
+        FTMI_TRY(gemm_nt(f1, st));
+        if (for_backward) return 0;
+        FTMI_TRY(gemm_nt(linear_args(W(ws, L.s_act), c.D_ff, M, P(w.w_ff2, (size_t)l * D * c.D_ff), c.D_ff, D, c.D_ff, P(w.b_ff2, (size_t)l * D), W(ws, L.s_f), D, V), st));
+        FTMI_TRY(gate_res(c, W(blk, L.h1), W(ws, L.s_f), t.gate2, hout, st));
+    }
+    return 0;
+}
+
+// The forward walk over all L blocks, for either layout: the modulation GEMM + table pass, then per block the launches listed at the top of this file.
+int cog_walk_forward(const ftmi_cog_config& c, const ftmi_cog_weights& w, const CogFwdLayout& L, const bf16_t* tokens_in, const bf16_t* temb_silu, bf16_t* tokens_out,
+                     void* ws, hipStream_t st) {
+    const int N = c.T + c.S, M = c.B * N, D = c.D, V = c.gemm_variant;
 
     // modulation of every LayerNorm-zero of every block: one GEMM over the stacked [L, 2, 6D, D_temb] weights, one table-building pass
     {
@@ -147,57 +211,9 @@ int cog_walk_forward(const ftmi_cog_config& c, const ftmi_cog_weights& w, const 
     }
 
     for (int l = 0; l < c.L; ++l) {
-        char* blk = reinterpret_cast<char*>(ws) + L.blk0 + L.blk_stride * l;
         const bf16_t* h0 = l == 0 ? tokens_in : W(ws, L.hs) + (size_t)((l - 1) % L.hs_slots) * M * D;
         bf16_t* hout = l == c.L - 1 ? tokens_out : W(ws, L.hs) + (size_t)(l % L.hs_slots) * M * D;
-        const Tables t = tables_of(c, ws, L, l);
-        const bf16_t* la = w.lora_a_sp ? P(w.lora_a_sp, (size_t)l * 4 * 2 * r * D) : nullptr;   // [4][2r][D]
-        const bf16_t* lb = w.lora_b_ext ? P(w.lora_b_ext, (size_t)l * 4 * D * 3 * r) : nullptr;  // [4][D][3r]
-        bf16_t* n1 = W(blk, L.n1);
-        bf16_t* qkv = W(blk, L.qkv);
-
-        {  // LayerNorm-zero 1
-            CogLnArgs a = ln_args(c, h0, 0, l, w);
-            a.shift = t.shift1; a.onep = t.onep1; a.y = n1;
-            FTMI_TRY(cog_ln_mod_fwd(a, st));
-        }
-        {  // fused q|k|v projection (+ LoRA)
-            GemmNtArgs a = linear_args(n1, D, M, P(w.w_qkv, (size_t)l * 3 * D2), D, 3 * D, D, P(w.b_qkv, (size_t)l * 3 * D), qkv, 3 * D, V);
-            if (r > 0) {
-                FTMI_TRY(gemm_nt(lora_down_args(n1, D, M, la, 3, D, r, s, W(blk, L.xa_qkv)), st));
-                lora_ext_fwd(a, W(blk, L.xa_qkv), 3, r, lb);
-            }
-            FTMI_TRY(gemm_nt(a, st));
-        }
-        for (int qk = 0; qk < 2; ++qk) {  // per-head LayerNorm of q and k (+ RoPE on the video rows)
-            CogLnArgs a;
-            a.x = qkv + (size_t)qk * D; a.ld = 3 * D; a.y = W(blk, qk ? L.kn : L.qn); a.ld_out = D; a.rows = M; a.D = D; a.eps = c.eps_qk;
-            a.w = P(w.qk_norm, ((size_t)l * 4 + qk * 2) * 64); a.b = P(w.qk_norm, ((size_t)l * 4 + qk * 2 + 1) * 64);
-            a.cos = w.rope_cos; a.sin = w.rope_sin; a.rows_per_batch = N; a.seg0 = w.rope_cos ? c.T : 0;
-            FTMI_TRY(cog_head_ln_fwd(a, st));
-        }
-        {  // joint attention
-            FTMI_TRY(attn_fwd(attn_args(c, W(blk, L.qn), W(blk, L.kn), qkv, W(blk, L.o), WF(blk, L.lse)), st));
-        }
-        {  // to_out (+ LoRA), gated residual
-            GemmNtArgs a = linear_args(W(blk, L.o), D, M, P(w.w_o, (size_t)l * D2), D, D, D, P(w.b_o, (size_t)l * D), W(ws, L.s_f), D, V);
-            if (r > 0) {
-                FTMI_TRY(gemm_nt(lora_down_args(W(blk, L.o), D, M, la + 3L * 2 * r * D, 1, D, r, s, W(blk, L.xa_o)), st));
-                lora_ext_fwd(a, W(blk, L.xa_o), 1, r, lb + 3L * D * 3 * r);
-            }
-            FTMI_TRY(gemm_nt(a, st));
-            FTMI_TRY(gate_res(c, h0, W(ws, L.s_f), t.gate1, W(blk, L.h1), st));
-        }
-        {  // LayerNorm-zero 2, feed-forward, gated residual
-            CogLnArgs a = ln_args(c, W(blk, L.h1), 1, l, w);
-            a.shift = t.shift2; a.onep = t.onep2; a.y = W(blk, L.n2);
-            FTMI_TRY(cog_ln_mod_fwd(a, st));
-            GemmNtArgs f1 = linear_args(W(blk, L.n2), D, M, P(w.w_ff1, (size_t)l * c.D_ff * D), D, c.D_ff, D, P(w.b_ff1, (size_t)l * c.D_ff), W(ws, L.s_act), c.D_ff, V);
-            f1.out2 = W(blk, L.z); f1.ldo2 = c.D_ff; f1.epi = EPI_GELU;
-            FTMI_TRY(gemm_nt(f1, st));
-            FTMI_TRY(gemm_nt(linear_args(W(ws, L.s_act), c.D_ff, M, P(w.w_ff2, (size_t)l * D * c.D_ff), c.D_ff, D, c.D_ff, P(w.b_ff2, (size_t)l * D), W(ws, L.s_f), D, V), st));
-            FTMI_TRY(gate_res(c, W(blk, L.h1), W(ws, L.s_f), t.gate2, hout, st));
-        }
+        FTMI_TRY(cog_block_forward(c, w, L, ws, l, h0, hout, false, st));
     }
     return 0;
 }
@@ -235,6 +251,25 @@ int cog_blocks_backward(const ftmi_cog_config& c, const ftmi_cog_weights& w, con
     bf16_t *d1 = W(ws, L.s_d1), *d2 = W(ws, L.s_d2), *d3 = W(ws, L.s_d3);
     int cur = (c.L - l_hi) & 1;  // the gradient of the token stream ping-pongs between two buffers, one flip per finished block
 
+    // LoRA weight gradients dB += dY^T XA, dA += dXA^T X of blocks [l0, l0 + nb): one batched launch per adapter group
+    auto lora_wgrad = [&](int l0, int nb) -> int {
+        char* blk0 = reinterpret_cast<char*>(ws) + L.blk0 + L.blk_stride * l0;
+        const long bs = (long)(L.blk_stride / 2);
+        struct G { size_t dy; long lddy; int nadp, adp; size_t xa, dxa, x; };
+        const G groups[2] = {{L.g_o, D, 1, 3, L.xa_o, L.dxa_o, L.o}, {L.g_qkv, 3L * D, 3, 0, L.xa_qkv, L.dxa_qkv, L.n1}};
+        float* ga = grad_a + (size_t)l0 * 4 * r * D;
+        float* gb = grad_b + (size_t)l0 * 4 * D * r;
+        for (const G& gr : groups) {
+            GemmTnArgs tb = lora_db_args(W(blk0, gr.dy), gr.lddy, W(blk0, gr.xa), gr.nadp, r, D, gb + (size_t)gr.adp * D * r, M);  // dB[l] += dY[l]^T XA[l]
+            tn_batch(tb, nb, bs, bs, 4L * D * r);
+            FTMI_TRY(gemm_tn(tb, st));
+            GemmTnArgs ta = lora_da_args(W(blk0, gr.dxa), gr.nadp, r, W(blk0, gr.x), D, D, ga + (size_t)gr.adp * r * D, M);  // dA[l] += dXA[l]^T X[l]
+            tn_batch(ta, nb, bs, bs, 4L * r * D);
+            FTMI_TRY(gemm_tn(ta, st));
+        }
+        return 0;
+    };
+
     for (int l = l_hi - 1; l >= l_lo; --l) {
         char* blk = reinterpret_cast<char*>(ws) + L.blk0 + L.blk_stride * l;
         const bf16_t* h0 = l == 0 ? tokens_in : W(ws, L.hs) + (size_t)(l - 1) * M * D;
@@ -246,6 +281,7 @@ int cog_blocks_backward(const ftmi_cog_config& c, const ftmi_cog_weights& w, con
         const bf16_t* qkv = W(blk, L.qkv);
         bf16_t* gqkv = W(blk, L.g_qkv);
         bf16_t* go = W(blk, L.g_o);
+        if (c.checkpoint) FTMI_TRY(cog_block_forward(c, w, L, ws, l, h0, nullptr, true, st));  // the block's activations again, into the one slot
 
         // ---- feed-forward branch ----
         FTMI_TRY(gate_res(c, nullptr, dout, t.gate2, d1, st));  // d f = gate_ff * d out
@@ -292,26 +328,9 @@ int cog_blocks_backward(const ftmi_cog_config& c, const ftmi_cog_weights& w, con
             FTMI_TRY(cog_ln_mod_bwd(n, st));
         }
         cur ^= 1;
+        if (c.checkpoint && r > 0) FTMI_TRY(lora_wgrad(l, 1));  // the slot is about to be reused: this block's weight gradients now
     }
-
-    // LoRA weight gradients dB += dY^T XA, dA += dXA^T X: one batched launch per adapter group over the blocks of this range
-    if (r > 0) {
-        const int nb = l_hi - l_lo;
-        char* blk0 = reinterpret_cast<char*>(ws) + L.blk0 + L.blk_stride * l_lo;
-        const long bs = (long)(L.blk_stride / 2);
-        struct G { size_t dy; long lddy; int nadp, adp; size_t xa, dxa, x; };
-        const G groups[2] = {{L.g_o, D, 1, 3, L.xa_o, L.dxa_o, L.o}, {L.g_qkv, 3L * D, 3, 0, L.xa_qkv, L.dxa_qkv, L.n1}};
-        float* ga = grad_a + (size_t)l_lo * 4 * r * D;
-        float* gb = grad_b + (size_t)l_lo * 4 * D * r;
-        for (const G& gr : groups) {
-            GemmTnArgs tb = lora_db_args(W(blk0, gr.dy), gr.lddy, W(blk0, gr.xa), gr.nadp, r, D, gb + (size_t)gr.adp * D * r, M);  // dB[l] += dY[l]^T XA[l]
-            tn_batch(tb, nb, bs, bs, 4L * D * r);
-            FTMI_TRY(gemm_tn(tb, st));
-            GemmTnArgs ta = lora_da_args(W(blk0, gr.dxa), gr.nadp, r, W(blk0, gr.x), D, D, ga + (size_t)gr.adp * r * D, M);  // dA[l] += dXA[l]^T X[l]
-            tn_batch(ta, nb, bs, bs, 4L * r * D);
-            FTMI_TRY(gemm_tn(ta, st));
-        }
-    }
+    if (r > 0 && !c.checkpoint) FTMI_TRY(lora_wgrad(l_lo, l_hi - l_lo));  // over the blocks of this range
     return 0;
 }
 
@@ -350,6 +369,7 @@ int make_sample_plan(const ftmi_cog_sample_config& c, CogSamplePlan& p) {
     ftmi_cog_config& b = p.bc;
     b.B = g.P * g.B; b.T = c.T; b.S = (int)p.S; b.D = c.D; b.H = c.heads; b.L = c.L; b.D_ff = c.D_ff; b.D_temb = c.D_temb; b.r = c.r;
     b.lora_scale = c.lora_scale; b.eps_norm = c.eps_norm; b.eps_qk = c.eps_qk; b.gemm_variant = c.gemm_variant;
+    b.checkpoint = 0;  // no backward follows: the plan below is its own one-slot layout
     FTMI_TRY(check_cfg(b));
     const size_t M = (size_t)b.B * (c.T + p.S), Mv = (size_t)b.B * p.S, D = c.D, e2 = 2;
     Bump w;

@@ -502,7 +502,7 @@ int ftmi_cog_gate_residual(const void* res, const void* y, const void* gate, voi
                            ftmi_stream stream);
 
 /* The whole CogVideoX block stack as one call per direction (the LTX orchestrator's design: caller-owned workspace, every activation of the backward
- * kept, nothing recomputed; the backward runs over block ranges so a data-parallel caller can all-reduce finished ranges while the rest computes).
+ * kept, nothing recomputed unless cfg->checkpoint asks for it; the backward runs over block ranges so a data-parallel caller can all-reduce finished ranges while the rest computes).
  * Weights are stacked per kind along a leading layer axis, bf16; "_t" = transposed copies for the dgrads (made once at load time). */
 typedef struct {
     int B, T, S;      /* batch, text tokens, video tokens: token buffers are [B, T + S, D], text first */
@@ -511,6 +511,12 @@ typedef struct {
     int r;            /* LoRA rank (0: none; multiple of 64) on to_q, to_k, to_v, to_out.0 */
     float lora_scale, eps_norm, eps_qk;
     int gemm_variant; /* 8 */
+    /* 1 = gradient checkpointing (the reference's --gradient_checkpointing, trainer/sft_trainer/trainer.py:155-157 -> utils/activation_checkpoint.py:24-49,
+     * every block wrapped; its CogVideoX recipe sets it): the workspace holds ONE block slot instead of L (ftmi_cog_workspace_bytes shrinks accordingly), the
+     * forward keeps only the inputs of blocks 1 .. L-1, and the backward runs a block's forward launches again -- up to the feed-forward's pre-activation,
+     * the last thing it reads; the caller's tokens_out is not touched -- right before its gradient launches, then that block's LoRA weight gradients.
+     * 0 = every activation kept.  Any other value: FTMI_ERR_INVALID.  Forward and backward of one step must use the same value. */
+    int checkpoint;
 } ftmi_cog_config;
 typedef struct {
     const void *mod_w, *mod_b;   /* [L,2,6D,D_temb], [L,2,6D]: norm1.linear and norm2.linear of every block */

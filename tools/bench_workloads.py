@@ -54,6 +54,9 @@ def build_cogvideox(args, par, dev) -> Dict[str, Any]:
     model.load_diffusers_state_dict(sd)
     del sd
     model.add_adapter(r=args.rank, lora_alpha=float(args.rank))
+    ckpt = bool(getattr(args, "gradient_checkpointing", False))
+    if ckpt:
+        model.apply_activation_checkpointing("full")
     with torch.no_grad():
         n = model.lora_flat.numel() // 2
         model.lora_flat[n:].normal_(0, 0.01, generator=g)  # B != 0 so every gradient path carries data
@@ -63,8 +66,12 @@ def build_cogvideox(args, par, dev) -> Dict[str, Any]:
     lat = torch.randn((1, 13, 16, 60, 90), generator=g, device=dev).to(bf16)
     text = torch.randn((1, 226, 4096), generator=g, device=dev).to(bf16)
     N = 226 + 17550
-    flop = layers * (2.0 * N * D * D * 12 * 2 + 4.0 * N * N * D * 3.5)  # linears forward + dgrad, attention forward + 2.5 x backward (LoRA / embed / head terms omitted)
+    # linears forward + dgrad, attention forward + 2.5 x backward (LoRA / embed / head terms omitted); checkpointing: the forward again without the second
+    # feed-forward GEMM (8 of the 12 D x D units)
+    flop = layers * (2.0 * N * D * D * (12 * 2 + (8 if ckpt else 0)) + 4.0 * N * N * D * (4.5 if ckpt else 3.5))
     return {
+        "gradient_checkpointing": ckpt,
+        "workspace_bytes": int(_cog_training_workspace(model, 1, N)),
         "one_step": lambda: step.step(lat, text),
         "samples_per_step": 1,
         "step_tflop": flop / 1e12,
@@ -73,7 +80,7 @@ def build_cogvideox(args, par, dev) -> Dict[str, Any]:
         "config": {"workload": f"CogVideoX-2b LoRA rank={args.rank} bf16 SFT step, 49x480x720 clip (226 text + 17550 video tokens), batch 1 per GPU, {layers} blocks (BASELINE configs[2])"
                                + ("" if layers == 30 else " -- REDUCED depth"),
                    "model": "CogVideoX-2b DiT: 30 blocks, width 1920, 30 x 64 heads, joint text + video attention", "seq_len": N,
-                   "activation_checkpointing": False, "orchestration": "C block stack (ftmi_cog_blocks_forward / _backward)"},
+                   "activation_checkpointing": ckpt, "orchestration": "C block stack (ftmi_cog_blocks_forward / _backward)"},
         "layers": layers,
     }
 
