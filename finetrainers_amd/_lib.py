@@ -106,7 +106,8 @@ class HySingleWeights(Structure):
 class HyDualConfig(Structure):
     """include/ftmi355.h: ftmi_hy_dual_config."""
 
-    _fields_ = [("T", c_int), ("S", c_int), ("D", c_int), ("H", c_int), ("mlp", c_int), ("r", c_int), ("lora_scale", c_float), ("eps", c_float), ("gemm_variant", c_int)]
+    _fields_ = [("T", c_int), ("S", c_int), ("D", c_int), ("H", c_int), ("mlp", c_int), ("r", c_int), ("lora_scale", c_float), ("eps", c_float), ("gemm_variant", c_int),
+                ("text_adapters", c_int)]
 
 
 HY_DUAL_WEIGHT_FIELDS = [
@@ -234,6 +235,12 @@ class HySampleConfig(Structure):
 
     _fields_ = [("geo", HySampleGeometry), ("T", c_int), ("D", c_int), ("H", c_int), ("mlp", c_int), ("Ld", c_int), ("Ls", c_int), ("r", c_int),
                 ("lora_scale", c_float), ("eps", c_float), ("gemm_variant", c_int), ("steps", c_int), ("true_cfg", c_float)]
+
+
+class HySampleTextConfig(Structure):
+    """include/ftmi355.h: ftmi_hy_sample_text_config."""
+
+    _fields_ = [("base", HySampleConfig), ("text_adapters", c_int)]
 
 
 class HySampleWeights(Structure):
@@ -417,6 +424,8 @@ _SIGS = {
     "ftmi_hy_sample_finish": (c_int, [POINTER(HySampleGeometry), c_void_p, c_float, c_void_p, c_void_p]),
     "ftmi_hy_sample_workspace_bytes": (c_size_t, [POINTER(HySampleConfig)]),
     "ftmi_hy_sample": (c_int, [POINTER(HySampleConfig), POINTER(HySampleWeights)] + [c_void_p] * 11 + [c_size_t, c_void_p]),
+    "ftmi_hy_sample_text_workspace_bytes": (c_size_t, [POINTER(HySampleTextConfig)]),
+    "ftmi_hy_sample_text": (c_int, [POINTER(HySampleTextConfig), POINTER(HySampleWeights)] + [c_void_p] * 11 + [c_size_t, c_void_p]),
     "ftmi_hy_dual_saved_bytes": (c_size_t, [POINTER(HyDualConfig)]),
     "ftmi_hy_dual_scratch_bytes": (c_size_t, [POINTER(HyDualConfig)]),
     "ftmi_hy_dual_forward": (c_int, [POINTER(HyDualConfig), POINTER(HyDualWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -1050,15 +1050,25 @@ int ftmi_hy_sample_finish(const ftmi_hy_sample_geometry* geo, const float* x, fl
     return hy_sample_finish(*geo, x, k, (bf16_t*)latents, (hipStream_t)stream);
 }
 
-size_t ftmi_hy_sample_workspace_bytes(const ftmi_hy_sample_config* cfg) { return cfg ? hy_sample_workspace_bytes(*cfg) : 0; }
+size_t ftmi_hy_sample_workspace_bytes(const ftmi_hy_sample_config* cfg) { return cfg ? hy_sample_workspace_bytes(*cfg, 0) : 0; }
+size_t ftmi_hy_sample_text_workspace_bytes(const ftmi_hy_sample_text_config* cfg) { return cfg ? hy_sample_workspace_bytes(cfg->base, cfg->text_adapters) : 0; }
 
 int ftmi_hy_sample(const ftmi_hy_sample_config* cfg, const ftmi_hy_sample_weights* w, void* cols, float* x, const void* temb_silu, const void* enc,
                    const void* head_shift, const void* head_onep, const float* key_bias, const float* rope_cos, const float* rope_sin, const float* sigmas,
                    void* workspace, size_t workspace_bytes, ftmi_stream stream) {
     if (!cfg || !w || !cols || !x || !temb_silu || !enc || !head_shift || !head_onep || !rope_cos || !rope_sin || !sigmas || !workspace)
         return set_error(FTMI_ERR_INVALID, "ftmi_hy_sample: null argument");
-    return hy_sample(*cfg, *w, (bf16_t*)cols, x, (const bf16_t*)temb_silu, (const bf16_t*)enc, (const bf16_t*)head_shift, (const bf16_t*)head_onep, key_bias,
+    return hy_sample(*cfg, 0, *w, (bf16_t*)cols, x, (const bf16_t*)temb_silu, (const bf16_t*)enc, (const bf16_t*)head_shift, (const bf16_t*)head_onep, key_bias,
                      rope_cos, rope_sin, sigmas, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int ftmi_hy_sample_text(const ftmi_hy_sample_text_config* cfg, const ftmi_hy_sample_weights* w, void* cols, float* x, const void* temb_silu, const void* enc,
+                        const void* head_shift, const void* head_onep, const float* key_bias, const float* rope_cos, const float* rope_sin, const float* sigmas,
+                        void* workspace, size_t workspace_bytes, ftmi_stream stream) {
+    if (!cfg || !w || !cols || !x || !temb_silu || !enc || !head_shift || !head_onep || !rope_cos || !rope_sin || !sigmas || !workspace)
+        return set_error(FTMI_ERR_INVALID, "ftmi_hy_sample_text: null argument");
+    return hy_sample(cfg->base, cfg->text_adapters, *w, (bf16_t*)cols, x, (const bf16_t*)temb_silu, (const bf16_t*)enc, (const bf16_t*)head_shift,
+                     (const bf16_t*)head_onep, key_bias, rope_cos, rope_sin, sigmas, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -278,15 +278,16 @@ int hy_single_backward(const ftmi_hy_single_config& c, const ftmi_hy_single_weig
 // ------------------------------------------------------------------------------------------------------------------------------------------------
 // Dual-stream block (20 of the 60 blocks), ONE sample per call (modulation, attention and text mask are per sample):
 //   video x_v [S, D] and text x_t [T, D] keep their own AdaLayerNormZero modulation (6 rows each), q / k / v projections (LoRA on the VIDEO stream's
-//   to_q / to_k / to_v / to_out.0), per-head q / k RMSNorm (rotary embedding on the video rows) and GELU-tanh feed-forward; q, k, v of both streams are
-//   laid out as ONE joint sequence [text | video] for the attention.
+//   to_q / to_k / to_v / to_out.0; with text_adapters also on the TEXT stream's add_q_proj / add_k_proj / add_v_proj / to_add_out, adapters 4..7),
+//   per-head q / k RMSNorm (rotary embedding on the video rows) and GELU-tanh feed-forward; q, k, v of both streams are laid out as ONE joint sequence
+//   [text | video] for the attention.
 // Reference: [upstream] diffusers HunyuanVideoTransformerBlock, restated in oracle/hunyuan.py (DualStreamBlock); kernel sequence = the one
 // finetrainers_amd/hunyuan_video/block.py (_DualBlockFunction) issues from Python.
 namespace {
 
 struct HyDualLayout {
     // saved: tables[s][i] (s = 0 video, 1 text; i: 0 shift, 1 gate, 2 shift_mlp, 3 gate_mlp, 4 1 + scale, 5 1 + scale_mlp), each [D]
-    size_t mod, tables, n_v, n_t, q_v, k_v, q_t, k_t, qj, kj, vj, o, lse, h_v, h_t, pre_v, pre_t, xa, saved_total;
+    size_t mod, tables, n_v, n_t, q_v, k_v, q_t, k_t, qj, kj, vj, o, lse, h_v, h_t, pre_v, pre_t, xa, xa_t, saved_total;
     // scratch, forward
     size_t a_v, a_t, n2_v, n2_t, act_v, act_t, f_v, f_t, a_sp, b_ext;
     // scratch, backward
@@ -297,6 +298,9 @@ struct HyDualLayout {
 HyDualLayout make_dual_layout(const ftmi_hy_dual_config& c) {
     HyDualLayout w;
     const size_t S = c.S, T = c.T, N = S + T, D = c.D, mlp = c.mlp, r = c.r > 0 ? c.r : 0, e2 = 2;
+    // text_adapters: eight adapters instead of four, the text rows' down-projections kept next to the video rows', dxa large enough for either stream
+    const bool text = c.text_adapters == 1;
+    const size_t nm = text ? 8 : 4, dxa_rows = text && T > S ? T : S;
     Bump s;
     w.mod = s.take(2 * 6 * D * e2);
     w.tables = s.take(2 * 6 * D * e2);
@@ -316,6 +320,7 @@ HyDualLayout make_dual_layout(const ftmi_hy_dual_config& c) {
     w.pre_v = s.take(S * mlp * e2);
     w.pre_t = s.take(T * mlp * e2);
     w.xa = s.take(4 * S * 3 * r * e2);
+    w.xa_t = s.take(text ? 4 * T * 3 * r * e2 : 0);
     w.saved_total = s.off;
     Bump f;
     w.a_v = f.take(S * D * e2);
@@ -326,8 +331,8 @@ HyDualLayout make_dual_layout(const ftmi_hy_dual_config& c) {
     w.act_t = f.take(T * mlp * e2);
     w.f_v = f.take(S * D * e2);
     w.f_t = f.take(T * D * e2);
-    w.a_sp = f.take(4 * 2 * r * D * e2);
-    w.b_ext = f.take(4 * D * 3 * r * e2);
+    w.a_sp = f.take(nm * 2 * r * D * e2);
+    w.b_ext = f.take(nm * D * 3 * r * e2);
     Bump b;
     w.df_v = b.take(S * D * e2);
     w.df_t = b.take(T * D * e2);
@@ -356,11 +361,18 @@ HyDualLayout make_dual_layout(const ftmi_hy_dual_config& c) {
     w.t2 = b.take(T * D * e2);
     w.t3 = b.take(T * D * e2);
     w.dn_t = b.take(T * D * e2);
-    w.dxa = b.take(S * 3 * r * e2);
-    w.bt_sp = b.take(4 * 2 * r * D * e2);
-    w.at_ext = b.take(4 * D * 3 * r * e2);
+    w.dxa = b.take(dxa_rows * 3 * r * e2);
+    w.bt_sp = b.take(nm * 2 * r * D * e2);
+    w.at_ext = b.take(nm * D * 3 * r * e2);
     w.scratch_total = f.off > b.off ? f.off : b.off;
     return w;
+}
+
+// text_adapters: 0, or 1 with a LoRA rank (the planners answer 0 bytes for anything else, the block calls refuse it before any launch)
+int check_text_flag(const ftmi_hy_dual_config& c) {
+    if (c.text_adapters != 0 && c.text_adapters != 1) return set_error(FTMI_ERR_INVALID, "hy_dual: text_adapters is 0 or 1");
+    if (c.text_adapters == 1 && c.r == 0) return set_error(FTMI_ERR_INVALID, "hy_dual: text-stream adapters need a LoRA rank");
+    return 0;
 }
 
 int check_dual_cfg(const ftmi_hy_dual_config& c) {
@@ -368,7 +380,7 @@ int check_dual_cfg(const ftmi_hy_dual_config& c) {
     if (c.H * 128 != c.D || c.D % 128 != 0 || c.D > 4096) return set_error(FTMI_ERR_UNSUPPORTED, "hy_dual: width must be heads x 128, at most 4096");
     if (c.r < 0 || (c.r % 64) != 0) return set_error(FTMI_ERR_UNSUPPORTED, "hy_dual: LoRA rank must be 0 or a multiple of 64 (pad smaller ranks with zeros)");
     if (c.mlp <= 0 || (c.mlp % 128)) return set_error(FTMI_ERR_UNSUPPORTED, "hy_dual: the feed-forward width must be a multiple of 128");
-    return 0;
+    return check_text_flag(c);
 }
 
 // mod [6D] = (shift, scale, gate, shift_mlp, scale_mlp, gate_mlp) -> tables (shift, gate, shift_mlp, gate_mlp, bf(1 + scale), bf(1 + scale_mlp)), for both streams
@@ -415,27 +427,26 @@ int head_norm(const bf16_t* x, const void* wn, bf16_t* y, const bf16_t* dy, int 
     a.y = y;
     return cog_head_ln_fwd(a, st);
 }
-// y = x W^T + b (+ LoRA adapter i); xa_i kept
-int lora_linear_fwd(const bf16_t* X, int M, int D, const void* Wm, const void* bias, int i, int r, float s, void* scratch, const HyDualLayout& L, bf16_t* xa_all,
-                    size_t xa_stride, bf16_t* out, int V, hipStream_t st) {
+// y = x W^T + b (+ LoRA adapter i); xa = adapter i's down-projection of these rows [M, 3r], kept
+int lora_linear_fwd(const bf16_t* X, int M, int D, const void* Wm, const void* bias, int i, int r, float s, void* scratch, const HyDualLayout& L, bf16_t* xa,
+                    bf16_t* out, int V, hipStream_t st) {
     GemmNtArgs a = linear_args(X, D, M, C16(Wm), D, D, D, C16(bias), out, D, V);
     if (r > 0) {
-        bf16_t* xa = xa_all + (size_t)i * xa_stride;
         FTMI_TRY(gemm_nt(lora_down_args(X, D, M, W(scratch, L.a_sp) + (size_t)i * 2 * r * D, 1, D, r, s, xa), st));
         lora_ext_fwd(a, xa, 1, r, W(scratch, L.b_ext) + (size_t)i * D * 3 * r);
     }
     return gemm_nt(a, st);
 }
 // dx = dy W (+ dxa A_i);  dB_i += dy^T xa_i, dA_i += dxa^T x
-int lora_linear_bwd(const bf16_t* X, const bf16_t* dy, int M, int D, const void* Wt, int i, int r, float s, void* scratch, const HyDualLayout& L, const bf16_t* xa_all,
-                    size_t xa_stride, bf16_t* dx, float* grad_a, float* grad_b, int V, hipStream_t st) {
+int lora_linear_bwd(const bf16_t* X, const bf16_t* dy, int M, int D, const void* Wt, int i, int r, float s, void* scratch, const HyDualLayout& L, const bf16_t* xa,
+                    bf16_t* dx, float* grad_a, float* grad_b, int V, hipStream_t st) {
     bf16_t* dxa = W(scratch, L.dxa);
     if (r > 0) FTMI_TRY(gemm_nt(lora_down_args(dy, D, M, W(scratch, L.bt_sp) + (size_t)i * 2 * r * D, 1, D, r, s, dxa), st));
     GemmNtArgs a = linear_args(dy, D, M, C16(Wt), D, D, D, nullptr, dx, D, V);
     if (r > 0) lora_ext_bwd(a, dxa, 1, r, W(scratch, L.at_ext) + (size_t)i * D * 3 * r, 3 * r);
     FTMI_TRY(gemm_nt(a, st));
     if (r > 0) {
-        FTMI_TRY(gemm_tn(lora_db_args(dy, D, xa_all + (size_t)i * xa_stride, 1, r, D, grad_b + (size_t)i * D * r, M), st));
+        FTMI_TRY(gemm_tn(lora_db_args(dy, D, xa, 1, r, D, grad_b + (size_t)i * D * r, M), st));
         FTMI_TRY(gemm_tn(lora_da_args(dxa, 1, r, X, D, D, grad_a + (size_t)i * r * D, M), st));
     }
     return 0;
@@ -443,8 +454,8 @@ int lora_linear_bwd(const bf16_t* X, const bf16_t* dy, int M, int D, const void*
 
 }  // namespace
 
-size_t hy_dual_saved_bytes(const ftmi_hy_dual_config& c) { return make_dual_layout(c).saved_total; }
-size_t hy_dual_scratch_bytes(const ftmi_hy_dual_config& c) { return make_dual_layout(c).scratch_total; }
+size_t hy_dual_saved_bytes(const ftmi_hy_dual_config& c) { return check_text_flag(c) ? 0 : make_dual_layout(c).saved_total; }
+size_t hy_dual_scratch_bytes(const ftmi_hy_dual_config& c) { return check_text_flag(c) ? 0 : make_dual_layout(c).scratch_total; }
 
 // out_v == nullptr: the recomputation pass of gradient checkpointing (stops before the second feed-forward GEMMs)
 int hy_dual_forward(const ftmi_hy_dual_config& c, const ftmi_hy_dual_weights& w, const bf16_t* x_v, const bf16_t* x_t, const bf16_t* temb_silu, const float* key_bias,
@@ -455,7 +466,7 @@ int hy_dual_forward(const ftmi_hy_dual_config& c, const ftmi_hy_dual_weights& w,
     if (saved_bytes < L.saved_total || scratch_bytes < L.scratch_total) return set_error(FTMI_ERR_INVALID, "hy_dual_forward: buffer too small");
     if (c.r > 0 && (!w.lora_a || !w.lora_b)) return set_error(FTMI_ERR_INVALID, "hy_dual_forward: LoRA rank without adapters");
     if ((out_v == nullptr) != (out_t == nullptr)) return set_error(FTMI_ERR_INVALID, "hy_dual_forward: both outputs or none");
-    const int S = c.S, T = c.T, N = S + T, D = c.D, mlp = c.mlp, r = c.r, V = c.gemm_variant;
+    const int S = c.S, T = c.T, N = S + T, D = c.D, mlp = c.mlp, r = c.r, V = c.gemm_variant, nmat = c.text_adapters ? 8 : 4;
     const float s = c.lora_scale, eps = c.eps;
     bf16_t* tab = W(saved, L.tables);
     auto TV = [&](int i) { return tab + (size_t)i * D; };            // video: shift, gate, shift_mlp, gate_mlp, 1 + scale, 1 + scale_mlp
@@ -469,22 +480,23 @@ int hy_dual_forward(const ftmi_hy_dual_config& c, const ftmi_hy_dual_weights& w,
     FTMI_TRY(ln_mod(x_t, w, TT(0), TT(4), n_t, T, D, eps, st));
     if (r > 0) {
         LoraSplitArgs sa;
-        sa.w = w.lora_a; sa.rows = r; sa.cols = D; sa.nmat = 4; sa.in_bstride = (long)r * D; sa.sp = W(scratch, L.a_sp); sa.sp_bstride = 2L * r * D;
+        sa.w = w.lora_a; sa.rows = r; sa.cols = D; sa.nmat = nmat; sa.in_bstride = (long)r * D; sa.sp = W(scratch, L.a_sp); sa.sp_bstride = 2L * r * D;
         FTMI_TRY(lora_split(sa, st));
         LoraSplitArgs sb;
-        sb.w = w.lora_b; sb.rows = D; sb.cols = r; sb.nmat = 4; sb.in_bstride = (long)D * r; sb.ext = W(scratch, L.b_ext); sb.ext_bstride = 3L * D * r; sb.ld_ext = 3 * r;
+        sb.w = w.lora_b; sb.rows = D; sb.cols = r; sb.nmat = nmat; sb.in_bstride = (long)D * r; sb.ext = W(scratch, L.b_ext); sb.ext_bstride = 3L * D * r; sb.ld_ext = 3 * r;
         FTMI_TRY(lora_split(sb, st));
     }
-    bf16_t *qj = W(saved, L.qj), *kj = W(saved, L.kj), *vj = W(saved, L.vj), *xa = W(saved, L.xa);
-    const size_t xas = (size_t)S * 3 * r;
-    FTMI_TRY(lora_linear_fwd(n_v, S, D, w.wq, w.bq, 0, r, s, scratch, L, xa, xas, W(saved, L.q_v), V, st));
-    FTMI_TRY(lora_linear_fwd(n_v, S, D, w.wk, w.bk, 1, r, s, scratch, L, xa, xas, W(saved, L.k_v), V, st));
-    FTMI_TRY(lora_linear_fwd(n_v, S, D, w.wv, w.bv, 2, r, s, scratch, L, xa, xas, vj + (size_t)T * D, V, st));  // v of the video rows straight into the joint buffer
+    bf16_t *qj = W(saved, L.qj), *kj = W(saved, L.kj), *vj = W(saved, L.vj), *xa = W(saved, L.xa), *xa_t = W(saved, L.xa_t);
+    const size_t xas = (size_t)S * 3 * r, xats = (size_t)T * 3 * r;  // one adapter's down-projection of the video / of the text rows
+    const int rt = c.text_adapters ? r : 0;                        // the text projections' rank: 0 = the plain GEMMs
+    FTMI_TRY(lora_linear_fwd(n_v, S, D, w.wq, w.bq, 0, r, s, scratch, L, xa, W(saved, L.q_v), V, st));
+    FTMI_TRY(lora_linear_fwd(n_v, S, D, w.wk, w.bk, 1, r, s, scratch, L, xa + xas, W(saved, L.k_v), V, st));
+    FTMI_TRY(lora_linear_fwd(n_v, S, D, w.wv, w.bv, 2, r, s, scratch, L, xa + 2 * xas, vj + (size_t)T * D, V, st));  // v of the video rows straight into the joint buffer
     FTMI_TRY(head_norm(W(saved, L.q_v), w.norm_q_w, qj + (size_t)T * D, nullptr, S, D, eps, rope_cos, rope_sin, false, st));
     FTMI_TRY(head_norm(W(saved, L.k_v), w.norm_k_w, kj + (size_t)T * D, nullptr, S, D, eps, rope_cos, rope_sin, false, st));
-    FTMI_TRY(linear(n_t, T, D, w.add_q_w, w.add_q_b, D, W(saved, L.q_t), V, st));
-    FTMI_TRY(linear(n_t, T, D, w.add_k_w, w.add_k_b, D, W(saved, L.k_t), V, st));
-    FTMI_TRY(linear(n_t, T, D, w.add_v_w, w.add_v_b, D, vj, V, st));
+    FTMI_TRY(lora_linear_fwd(n_t, T, D, w.add_q_w, w.add_q_b, 4, rt, s, scratch, L, xa_t, W(saved, L.q_t), V, st));
+    FTMI_TRY(lora_linear_fwd(n_t, T, D, w.add_k_w, w.add_k_b, 5, rt, s, scratch, L, xa_t + xats, W(saved, L.k_t), V, st));
+    FTMI_TRY(lora_linear_fwd(n_t, T, D, w.add_v_w, w.add_v_b, 6, rt, s, scratch, L, xa_t + 2 * xats, vj, V, st));
     FTMI_TRY(head_norm(W(saved, L.q_t), w.norm_added_q_w, qj, nullptr, T, D, eps, nullptr, nullptr, false, st));
     FTMI_TRY(head_norm(W(saved, L.k_t), w.norm_added_k_w, kj, nullptr, T, D, eps, nullptr, nullptr, false, st));
     bf16_t* o = W(saved, L.o);
@@ -494,8 +506,8 @@ int hy_dual_forward(const ftmi_hy_dual_config& c, const ftmi_hy_dual_weights& w,
         FTMI_TRY(attn_fwd(a, st));
     }
     bf16_t *a_v = W(scratch, L.a_v), *a_t = W(scratch, L.a_t), *h_v = W(saved, L.h_v), *h_t = W(saved, L.h_t);
-    FTMI_TRY(lora_linear_fwd(o + (size_t)T * D, S, D, w.wo, w.bo, 3, r, s, scratch, L, xa, xas, a_v, V, st));
-    FTMI_TRY(linear(o, T, D, w.add_out_w, w.add_out_b, D, a_t, V, st));
+    FTMI_TRY(lora_linear_fwd(o + (size_t)T * D, S, D, w.wo, w.bo, 3, r, s, scratch, L, xa + 3 * xas, a_v, V, st));
+    FTMI_TRY(lora_linear_fwd(o, T, D, w.add_out_w, w.add_out_b, 7, rt, s, scratch, L, xa_t + 3 * xats, a_t, V, st));
     FTMI_TRY(gate_res(x_v, a_v, TV(1), h_v, S, D, st));
     FTMI_TRY(gate_res(x_t, a_t, TT(1), h_t, T, D, st));
     bf16_t *n2_v = W(scratch, L.n2_v), *n2_t = W(scratch, L.n2_t);
@@ -515,7 +527,7 @@ int hy_dual_forward(const ftmi_hy_dual_config& c, const ftmi_hy_dual_weights& w,
     return 0;
 }
 
-// ones_row: bf16 [D] of 1.0.  grad_a [4, r, D] / grad_b [4, D, r] fp32 are ADDED to.
+// ones_row: bf16 [D] of 1.0.  grad_a [4, r, D] / grad_b [4, D, r] fp32 ([8, ..] with text_adapters) are ADDED to.
 int hy_dual_backward(const ftmi_hy_dual_config& c, const ftmi_hy_dual_weights& w, const bf16_t* x_v, const bf16_t* x_t, const bf16_t* dout_v, const bf16_t* dout_t,
                      const float* key_bias, const float* rope_cos, const float* rope_sin, const bf16_t* ones_row, bf16_t* dx_v, bf16_t* dx_t, float* grad_a,
                      float* grad_b, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st) {
@@ -525,7 +537,7 @@ int hy_dual_backward(const ftmi_hy_dual_config& c, const ftmi_hy_dual_weights& w
     if (c.r > 0 && (!w.lora_a || !w.lora_b || !grad_a || !grad_b)) return set_error(FTMI_ERR_INVALID, "hy_dual_backward: LoRA rank without adapters / gradient buffers");
     if (!w.wq_t || !w.wk_t || !w.wv_t || !w.wo_t || !w.add_q_w_t || !w.add_k_w_t || !w.add_v_w_t || !w.add_out_w_t || !w.ff1_w_t || !w.ff2_w_t || !w.ffc1_w_t || !w.ffc2_w_t)
         return set_error(FTMI_ERR_INVALID, "hy_dual_backward: transposed weights missing");
-    const int S = c.S, T = c.T, N = S + T, D = c.D, mlp = c.mlp, r = c.r, V = c.gemm_variant;
+    const int S = c.S, T = c.T, N = S + T, D = c.D, mlp = c.mlp, r = c.r, V = c.gemm_variant, nmat = c.text_adapters ? 8 : 4;
     const float s = c.lora_scale, eps = c.eps;
     const bf16_t* tab = W(saved, L.tables);
     auto TV = [&](int i) { return tab + (size_t)i * D; };
@@ -545,20 +557,21 @@ int hy_dual_backward(const ftmi_hy_dual_config& c, const ftmi_hy_dual_weights& w
     }
     if (r > 0) {
         LoraSplitArgs sb;
-        sb.w = w.lora_b; sb.rows = D; sb.cols = r; sb.nmat = 4; sb.in_bstride = (long)D * r; sb.t_sp = W(scratch, L.bt_sp); sb.t_sp_bstride = 2L * r * D;
+        sb.w = w.lora_b; sb.rows = D; sb.cols = r; sb.nmat = nmat; sb.in_bstride = (long)D * r; sb.t_sp = W(scratch, L.bt_sp); sb.t_sp_bstride = 2L * r * D;
         FTMI_TRY(lora_split(sb, st));
         LoraSplitArgs sa;
-        sa.w = w.lora_a; sa.rows = r; sa.cols = D; sa.nmat = 4; sa.in_bstride = (long)r * D; sa.t_ext = W(scratch, L.at_ext); sa.t_ext_bstride = 3L * D * r; sa.ld_t_ext = 3 * r;
+        sa.w = w.lora_a; sa.rows = r; sa.cols = D; sa.nmat = nmat; sa.in_bstride = (long)r * D; sa.t_ext = W(scratch, L.at_ext); sa.t_ext_bstride = 3L * D * r; sa.ld_t_ext = 3 * r;
         FTMI_TRY(lora_split(sa, st));
     }
-    const bf16_t *dh_v = W(scratch, L.dh_v), *dh_t = W(scratch, L.dh_t), *o = W(saved, L.o), *xa = W(saved, L.xa);
-    const size_t xas = (size_t)S * 3 * r;
+    const bf16_t *dh_v = W(scratch, L.dh_v), *dh_t = W(scratch, L.dh_t), *o = W(saved, L.o), *xa = W(saved, L.xa), *xa_t = W(saved, L.xa_t);
+    const size_t xas = (size_t)S * 3 * r, xats = (size_t)T * 3 * r;
+    const int rt = c.text_adapters ? r : 0;
     bf16_t* doj = W(scratch, L.doj);
     // attention outputs: h = x + gate_msa * (o W_o^T + b)
     FTMI_TRY(gate_res(nullptr, dh_v, TV(1), W(scratch, L.da_v), S, D, st));
-    FTMI_TRY(lora_linear_bwd(o + (size_t)T * D, W(scratch, L.da_v), S, D, w.wo_t, 3, r, s, scratch, L, xa, xas, doj + (size_t)T * D, grad_a, grad_b, V, st));
+    FTMI_TRY(lora_linear_bwd(o + (size_t)T * D, W(scratch, L.da_v), S, D, w.wo_t, 3, r, s, scratch, L, xa + 3 * xas, doj + (size_t)T * D, grad_a, grad_b, V, st));
     FTMI_TRY(gate_res(nullptr, dh_t, TT(1), W(scratch, L.da_t), T, D, st));
-    FTMI_TRY(linear(W(scratch, L.da_t), T, D, w.add_out_w_t, nullptr, D, doj, V, st));
+    FTMI_TRY(lora_linear_bwd(o, W(scratch, L.da_t), T, D, w.add_out_w_t, 7, rt, s, scratch, L, xa_t + 3 * xats, doj, grad_a, grad_b, V, st));
     {
         AttnArgs a = attn_args(1, c.H, N, D, key_bias);
         a.q = W(saved, L.qj); a.k = W(saved, L.kj); a.v = W(saved, L.vj); a.o = W(saved, L.o); a.lse2 = WF(saved, L.lse);
@@ -571,19 +584,20 @@ int hy_dual_backward(const ftmi_hy_dual_config& c, const ftmi_hy_dual_weights& w
     FTMI_TRY(head_norm(W(saved, L.q_v), w.norm_q_w, W(scratch, L.dq_v), dqj + (size_t)T * D, S, D, eps, rope_cos, rope_sin, true, st));
     FTMI_TRY(head_norm(W(saved, L.k_v), w.norm_k_w, W(scratch, L.dk_v), dkj + (size_t)T * D, S, D, eps, rope_cos, rope_sin, true, st));
     const bf16_t* n_v = W(saved, L.n_v);
-    FTMI_TRY(lora_linear_bwd(n_v, W(scratch, L.dq_v), S, D, w.wq_t, 0, r, s, scratch, L, xa, xas, W(scratch, L.dn_q), grad_a, grad_b, V, st));
-    FTMI_TRY(lora_linear_bwd(n_v, W(scratch, L.dk_v), S, D, w.wk_t, 1, r, s, scratch, L, xa, xas, W(scratch, L.dn_k), grad_a, grad_b, V, st));
-    FTMI_TRY(lora_linear_bwd(n_v, dvj + (size_t)T * D, S, D, w.wv_t, 2, r, s, scratch, L, xa, xas, W(scratch, L.dn_vv), grad_a, grad_b, V, st));
+    FTMI_TRY(lora_linear_bwd(n_v, W(scratch, L.dq_v), S, D, w.wq_t, 0, r, s, scratch, L, xa, W(scratch, L.dn_q), grad_a, grad_b, V, st));
+    FTMI_TRY(lora_linear_bwd(n_v, W(scratch, L.dk_v), S, D, w.wk_t, 1, r, s, scratch, L, xa + xas, W(scratch, L.dn_k), grad_a, grad_b, V, st));
+    FTMI_TRY(lora_linear_bwd(n_v, dvj + (size_t)T * D, S, D, w.wv_t, 2, r, s, scratch, L, xa + 2 * xas, W(scratch, L.dn_vv), grad_a, grad_b, V, st));
     FTMI_TRY(gate_res(W(scratch, L.dn_vv), W(scratch, L.dn_k), ones_row, W(scratch, L.dn_v), S, D, st));   // bf16 accumulation of the three gradients of n_v
     FTMI_TRY(gate_res(W(scratch, L.dn_v), W(scratch, L.dn_q), ones_row, W(scratch, L.dn_v), S, D, st));
     FTMI_TRY(ln_mod_back(x_v, w, TV(4), W(scratch, L.dn_v), dh_v, dx_v, S, D, eps, st));
     // text stream
     FTMI_TRY(head_norm(W(saved, L.q_t), w.norm_added_q_w, W(scratch, L.dq_t), dqj, T, D, eps, nullptr, nullptr, true, st));
     FTMI_TRY(head_norm(W(saved, L.k_t), w.norm_added_k_w, W(scratch, L.dk_t), dkj, T, D, eps, nullptr, nullptr, true, st));
-    FTMI_TRY(linear(dvj, T, D, w.add_v_w_t, nullptr, D, W(scratch, L.t1), V, st));
-    FTMI_TRY(linear(W(scratch, L.dk_t), T, D, w.add_k_w_t, nullptr, D, W(scratch, L.t2), V, st));
+    const bf16_t* n_t = W(saved, L.n_t);
+    FTMI_TRY(lora_linear_bwd(n_t, dvj, T, D, w.add_v_w_t, 6, rt, s, scratch, L, xa_t + 2 * xats, W(scratch, L.t1), grad_a, grad_b, V, st));
+    FTMI_TRY(lora_linear_bwd(n_t, W(scratch, L.dk_t), T, D, w.add_k_w_t, 5, rt, s, scratch, L, xa_t + xats, W(scratch, L.t2), grad_a, grad_b, V, st));
     FTMI_TRY(gate_res(W(scratch, L.t1), W(scratch, L.t2), ones_row, W(scratch, L.dn_t), T, D, st));
-    FTMI_TRY(linear(W(scratch, L.dq_t), T, D, w.add_q_w_t, nullptr, D, W(scratch, L.t3), V, st));
+    FTMI_TRY(lora_linear_bwd(n_t, W(scratch, L.dq_t), T, D, w.add_q_w_t, 4, rt, s, scratch, L, xa_t, W(scratch, L.t3), grad_a, grad_b, V, st));
     FTMI_TRY(gate_res(W(scratch, L.dn_t), W(scratch, L.t3), ones_row, W(scratch, L.dn_t), T, D, st));
     FTMI_TRY(ln_mod_back(x_t, w, TT(4), W(scratch, L.dn_t), dh_t, dx_t, T, D, eps, st));
     return 0;

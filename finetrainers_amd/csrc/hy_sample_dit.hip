@@ -31,7 +31,7 @@ struct HySamplePlan {
     ftmi_hy_single_config sc;
 };
 
-int make_plan(const ftmi_hy_sample_config& c, HySamplePlan& p) {
+int make_plan(const ftmi_hy_sample_config& c, int text_adapters, HySamplePlan& p) {
     const ftmi_hy_sample_geometry& g = c.geo;
     if (g.B <= 0 || g.C <= 0 || g.F <= 0 || g.H <= 0 || g.W <= 0 || g.p <= 0 || g.pt <= 0 || c.T <= 0 || c.steps <= 0)
         return set_error(FTMI_ERR_INVALID, "hy_sample: extents and steps must be positive");
@@ -45,12 +45,15 @@ int make_plan(const ftmi_hy_sample_config& c, HySamplePlan& p) {
     const int rows = g.P * g.B;
     ftmi_hy_dual_config& d = p.dc;
     d.T = c.T; d.S = (int)p.S; d.D = c.D; d.H = c.H; d.mlp = c.mlp; d.r = c.r; d.lora_scale = c.lora_scale; d.eps = c.eps; d.gemm_variant = c.gemm_variant;
+    d.text_adapters = text_adapters;  // the dual blocks' lora_a / lora_b hold eight matrices; the single blocks have no text projections of their own
     ftmi_hy_single_config& s = p.sc;
     s.B = rows; s.T = c.T; s.S = (int)p.S; s.D = c.D; s.H = c.H; s.mlp = c.mlp; s.r = c.r; s.lora_scale = c.lora_scale; s.eps = c.eps; s.gemm_variant = c.gemm_variant;
     // the two block orchestrators refuse the same widths and ranks; asking the bytes of a refused configuration would size buffers from nonsense
     if (c.H * 128 != c.D || c.D % 128 != 0 || c.D > 4096) return set_error(FTMI_ERR_UNSUPPORTED, "hy_sample: width must be heads x 128, at most 4096");
     if (c.r < 0 || (c.r % 64) != 0) return set_error(FTMI_ERR_UNSUPPORTED, "hy_sample: LoRA rank must be 0 or a multiple of 64 (pad smaller ranks with zeros)");
     if (c.mlp <= 0 || (c.mlp % 128)) return set_error(FTMI_ERR_UNSUPPORTED, "hy_sample: the feed-forward width must be a multiple of 128");
+    if ((text_adapters != 0 && text_adapters != 1) || (text_adapters == 1 && c.r == 0))
+        return set_error(FTMI_ERR_INVALID, "hy_sample: text_adapters is 0 or 1, and 1 needs a LoRA rank");
     p.saved_dual = hy_dual_saved_bytes(d); p.scratch_dual = hy_dual_scratch_bytes(d);
     p.saved_single = hy_single_saved_bytes(s); p.scratch_single = hy_single_scratch_bytes(s);
     const size_t Mv = (size_t)rows * p.S, Mt = (size_t)rows * c.T, D = c.D, e2 = 2;
@@ -73,16 +76,16 @@ int copy_rows(bf16_t* dst, const bf16_t* src, size_t elements, hipStream_t st) {
 
 }  // namespace
 
-size_t hy_sample_workspace_bytes(const ftmi_hy_sample_config& c) {
+size_t hy_sample_workspace_bytes(const ftmi_hy_sample_config& c, int text_adapters) {
     HySamplePlan p;
-    return make_plan(c, p) ? 0 : p.total;
+    return make_plan(c, text_adapters, p) ? 0 : p.total;
 }
 
-int hy_sample(const ftmi_hy_sample_config& c, const ftmi_hy_sample_weights& w, bf16_t* cols, float* x, const bf16_t* temb_silu, const bf16_t* enc,
+int hy_sample(const ftmi_hy_sample_config& c, int text_adapters, const ftmi_hy_sample_weights& w, bf16_t* cols, float* x, const bf16_t* temb_silu, const bf16_t* enc,
               const bf16_t* head_shift, const bf16_t* head_onep, const float* key_bias, const float* rope_cos, const float* rope_sin, const float* sigmas, void* ws,
               size_t ws_bytes, hipStream_t st) {
     HySamplePlan p;
-    FTMI_TRY(make_plan(c, p));
+    FTMI_TRY(make_plan(c, text_adapters, p));
     if (ws_bytes < p.total) return set_error(FTMI_ERR_INVALID, "hy_sample: workspace too small (ftmi_hy_sample_workspace_bytes)");
     if (reinterpret_cast<uintptr_t>(ws) & 255) return set_error(FTMI_ERR_INVALID, "hy_sample: the workspace must be 256-byte aligned");
     if (!w.patch_w || !w.patch_b || !w.proj_w || !w.proj_b || !w.ones || !w.zeros || (c.Ld > 0 && !w.dual) || (c.Ls > 0 && !w.single))

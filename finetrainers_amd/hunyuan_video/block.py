@@ -401,6 +401,7 @@ class _DualBlockFunction(torch.autograd.Function):
         N, H, hd, s = T + S, blk.heads, 128, blk.lora_scale
         A = lambda i: None if lora_a is None else lora_a[i]
         Bm = lambda i: None if lora_b is None else lora_b[i]
+        text = lora_a is not None and lora_a.shape[0] == 8  # adapters 4..7 on add_q_proj / add_k_proj / add_v_proj / to_add_out
         rope = (rope_cos, rope_sin)
 
         def modulation(w, b):  # AdaLayerNormZero: (shift, scale, gate) of the attention, then of the feed-forward, each [1, D]
@@ -418,16 +419,26 @@ class _DualBlockFunction(torch.autograd.Function):
         ops.head_rms_rope(q_v, blk.norm_q_w, hd, 1e-6, rope=rope, rows_per_batch=S, rope_from=0, out=qj[T:])
         ops.head_rms_rope(k_v, blk.norm_k_w, hd, 1e-6, rope=rope, rows_per_batch=S, rope_from=0, out=kj[T:])
         vj[T:].copy_(v_v)
-        q_t = ops.gemm_nt(n_t, blk.add_q_w, blk.add_q_b)
-        k_t = ops.gemm_nt(n_t, blk.add_k_w, blk.add_k_b)
-        ops.gemm_nt(n_t, blk.add_v_w, blk.add_v_b, out=vj[:T])
+        xa_tq = xa_tk = xa_tv = xa_to = None
+        if text:
+            q_t, xa_tq = ops.linear_lora_fwd(n_t, blk.add_q_w, blk.add_q_b, A(4), Bm(4), s)
+            k_t, xa_tk = ops.linear_lora_fwd(n_t, blk.add_k_w, blk.add_k_b, A(5), Bm(5), s)
+            v_t, xa_tv = ops.linear_lora_fwd(n_t, blk.add_v_w, blk.add_v_b, A(6), Bm(6), s)
+            vj[:T].copy_(v_t)
+        else:
+            q_t = ops.gemm_nt(n_t, blk.add_q_w, blk.add_q_b)
+            k_t = ops.gemm_nt(n_t, blk.add_k_w, blk.add_k_b)
+            ops.gemm_nt(n_t, blk.add_v_w, blk.add_v_b, out=vj[:T])
         ops.head_rms_rope(q_t, blk.norm_added_q_w, hd, 1e-6, out=qj[:T])
         ops.head_rms_rope(k_t, blk.norm_added_k_w, hd, 1e-6, out=kj[:T])
         heads = lambda t: t.view(1, N, H, hd).permute(0, 2, 1, 3)
         o, lse = ops.attn_fwd(heads(qj), heads(kj), heads(vj), key_bias)
         o2d = o.permute(0, 2, 1, 3).reshape(N, D)
         a_v, xa_o = ops.linear_lora_fwd(o2d[T:], blk.wo, blk.bo, A(3), Bm(3), s)
-        a_t = ops.gemm_nt(o2d[:T], blk.add_out_w, blk.add_out_b)
+        if text:
+            a_t, xa_to = ops.linear_lora_fwd(o2d[:T], blk.add_out_w, blk.add_out_b, A(7), Bm(7), s)
+        else:
+            a_t = ops.gemm_nt(o2d[:T], blk.add_out_w, blk.add_out_b)
         h_v = ops.cog_gate_residual(x_v[None], a_v[None], g_v, 0)[0]
         h_t = ops.cog_gate_residual(x_t[None], a_t[None], g_t, 0)[0]
         n2_v = ops.cog_ln_mod(h_v[None], blk.ones, blk.zeros, shm_v, opm_v, 0, 1e-6)[0]
@@ -438,8 +449,8 @@ class _DualBlockFunction(torch.autograd.Function):
         if need_out:  # (the recomputation inside the backward stops before the second feed-forward GEMMs)
             out_v = ops.cog_gate_residual(h_v[None], ops.gemm_nt(act_v, blk.ff2_w, blk.ff2_b)[None], gm_v, 0)[0]
             out_t = ops.cog_gate_residual(h_t[None], ops.gemm_nt(act_t, blk.ffc2_w, blk.ffc2_b)[None], gm_t, 0)[0]
-        return (out_v, out_t), (n_v, n_t, q_v, k_v, q_t, k_t, qj, kj, vj, o, lse, h_v, h_t, pre_v, pre_t, g_v, g_t, gm_v, gm_t, op_v, op_t, opm_v, opm_t,
-                                xa_q, xa_k, xa_v, xa_o)
+        acts = (n_v, n_t, q_v, k_v, q_t, k_t, qj, kj, vj, o, lse, h_v, h_t, pre_v, pre_t, g_v, g_t, gm_v, gm_t, op_v, op_t, opm_v, opm_t, xa_q, xa_k, xa_v, xa_o)
+        return (out_v, out_t), acts + ((xa_tq, xa_tk, xa_tv, xa_to) if text else ())
 
     @staticmethod
     def forward(ctx, blk: "MI355XHunyuanDualBlock", x_v, x_t, temb_silu, key_bias, rope_cos, rope_sin, lora_a, lora_b):
@@ -467,8 +478,10 @@ class _DualBlockFunction(torch.autograd.Function):
             x_v, x_t, *acts, lora_a, lora_b = ctx.saved_tensors
             if not ctx.has_lora:
                 lora_a = lora_b = None
+        text = lora_a is not None and lora_a.shape[0] == 8
         (n_v, n_t, q_v, k_v, q_t, k_t, qj, kj, vj, o, lse, h_v, h_t, pre_v, pre_t, g_v, g_t, gm_v, gm_t, op_v, op_t, opm_v, opm_t,
-         xa_q, xa_k, xa_v, xa_o) = acts
+         xa_q, xa_k, xa_v, xa_o) = acts[:27]
+        xa_tq, xa_tk, xa_tv, xa_to = acts[27:] if text else (None,) * 4
         if blk._bwd_seen == 0:
             blk._materialize_bwd()  # fp8 storage: the transposed bf16 weights of THIS block into the shared arena (no-op otherwise)
         S, D = x_v.shape
@@ -501,7 +514,12 @@ class _DualBlockFunction(torch.autograd.Function):
         da_v = ops.cog_gate_residual(None, dh_v[None], g_v, 0)[0]
         do_v, _, _ = ops.linear_lora_bwd(o2d[T:], da_v, xa_o, blk.wo_t, A(3), Bm(3), s, GA(3), GB(3))
         doj[T:].copy_(do_v)
-        ops.gemm_nt(ops.cog_gate_residual(None, dh_t[None], g_t, 0)[0], blk.add_out_w_t, None, out=doj[:T])
+        da_t = ops.cog_gate_residual(None, dh_t[None], g_t, 0)[0]
+        if text:
+            do_t, _, _ = ops.linear_lora_bwd(o2d[:T], da_t, xa_to, blk.add_out_w_t, A(7), Bm(7), s, GA(7), GB(7))
+            doj[:T].copy_(do_t)
+        else:
+            ops.gemm_nt(da_t, blk.add_out_w_t, None, out=doj[:T])
         heads = lambda t: t.view(1, N, H, hd).permute(0, 2, 1, 3)
         flat = lambda t: t.permute(0, 2, 1, 3).reshape(N, D)
         dqj, dkj, dvj = (flat(t) for t in ops.attn_bwd(heads(qj), heads(kj), heads(vj), o, lse, heads(doj), ctx.key_bias))
@@ -516,7 +534,13 @@ class _DualBlockFunction(torch.autograd.Function):
         # text stream
         dq_t = ops.head_rms_rope_bwd(q_t, blk.norm_added_q_w, dqj[:T], hd, 1e-6)
         dk_t = ops.head_rms_rope_bwd(k_t, blk.norm_added_k_w, dkj[:T], hd, 1e-6)
-        dn_t = add(add(ops.gemm_nt(dvj[:T], blk.add_v_w_t, None), ops.gemm_nt(dk_t, blk.add_k_w_t, None)), ops.gemm_nt(dq_t, blk.add_q_w_t, None))
+        if text:
+            t1, _, _ = ops.linear_lora_bwd(n_t, dvj[:T], xa_tv, blk.add_v_w_t, A(6), Bm(6), s, GA(6), GB(6))
+            t2, _, _ = ops.linear_lora_bwd(n_t, dk_t, xa_tk, blk.add_k_w_t, A(5), Bm(5), s, GA(5), GB(5))
+            t3, _, _ = ops.linear_lora_bwd(n_t, dq_t, xa_tq, blk.add_q_w_t, A(4), Bm(4), s, GA(4), GB(4))
+            dn_t = add(add(t1, t2), t3)
+        else:
+            dn_t = add(add(ops.gemm_nt(dvj[:T], blk.add_v_w_t, None), ops.gemm_nt(dk_t, blk.add_k_w_t, None)), ops.gemm_nt(dq_t, blk.add_q_w_t, None))
         dx_t = ops.cog_ln_mod_bwd(x_t[None], blk.ones, op_t, dn_t[None], 0, 1e-6, dres=dh_t[None])[0]
         if own:
             blk._backward_done(ga, gb)
@@ -530,7 +554,7 @@ class _DualBlockNativeFunction(torch.autograd.Function):
     @staticmethod
     def _args(blk: "MI355XHunyuanDualBlock", S: int, T: int, lora_a, lora_b, backward: bool):
         cfg = HyDualConfig(T=T, S=S, D=blk.dim, H=blk.heads, mlp=int(blk.ff1_w.shape[0]), r=0 if lora_a is None else int(lora_a.shape[1]),
-                           lora_scale=float(blk.lora_scale), eps=1e-6, gemm_variant=8)
+                           lora_scale=float(blk.lora_scale), eps=1e-6, gemm_variant=8, text_adapters=int(lora_a is not None and lora_a.shape[0] == 8))
         w = HyDualWeights()
         keep = []
         for n in HY_DUAL_WEIGHT_FIELDS:
@@ -605,7 +629,8 @@ class _DualBlockNativeFunction(torch.autograd.Function):
 class MI355XHunyuanDualBlock(_FlatGradMixin, _Fp8StorageMixin, nn.Module):
     """HunyuanVideo dual-stream block (20 of the 60 blocks; [upstream] ``HunyuanVideoTransformerBlock``, oracle/hunyuan.py ``DualStreamBlock``): the video and
     the text tokens have their own modulation, projections, q / k norms and feed-forward and meet in ONE joint attention.  LoRA on the video stream's to_q /
-    to_k / to_v / to_out.0 (what the default target regex matches; the text stream's ``add_*_proj`` / ``to_add_out`` stay frozen)."""
+    to_k / to_v / to_out.0 (what the default target regex matches) and, with ``add_adapter(..., text_stream=True)``, also on the text stream's add_q_proj /
+    add_k_proj / add_v_proj / to_add_out (the shipped recipe's regex): eight adapters in the block's two Parameters, in that order."""
 
     _KEYS = {
         "norm1.linear.weight": "norm1_lin_w", "norm1.linear.bias": "norm1_lin_b", "norm1_context.linear.weight": "norm1c_lin_w", "norm1_context.linear.bias": "norm1c_lin_b",
@@ -637,8 +662,8 @@ class MI355XHunyuanDualBlock(_FlatGradMixin, _Fp8StorageMixin, nn.Module):
             self.register_buffer(name + "_t", None, persistent=False)
         self.register_buffer("ones", torch.ones(dim, dtype=bf16, device=dev), persistent=False)
         self.register_buffer("zeros", torch.zeros(dim, dtype=bf16, device=dev), persistent=False)
-        self.lora_A: Optional[nn.Parameter] = None  # [4, r, D]: to_q, to_k, to_v, to_out.0
-        self.lora_B: Optional[nn.Parameter] = None  # [4, D, r]
+        self.lora_A: Optional[nn.Parameter] = None  # [4, r, D]: to_q, to_k, to_v, to_out.0; [8, r, D] with text_stream: + add_q_proj, add_k_proj, add_v_proj, to_add_out
+        self.lora_B: Optional[nn.Parameter] = None  # [4, D, r] / [8, D, r]
         self.lora_scale = 0.0
         self._ones_rows: Dict[int, torch.Tensor] = {}
 
@@ -657,15 +682,21 @@ class MI355XHunyuanDualBlock(_FlatGradMixin, _Fp8StorageMixin, nn.Module):
         for name in self._TRANSPOSED:
             setattr(self, name + "_t", ops.transpose_bf16(getattr(self, name)))
 
-    def add_adapter(self, r: int = 64, lora_alpha: float = 64.0) -> None:
+    @property
+    def text_adapters(self) -> bool:
+        """True when the block carries the text stream's four adapters as well (``lora_A`` [8, r, D])."""
+        return self.lora_A is not None and self.lora_A.shape[0] == 8
+
+    def add_adapter(self, r: int = 64, lora_alpha: float = 64.0, text_stream: bool = False) -> None:
         # ranks that are not multiples of 64 are stored zero-padded (the padding provably stays zero: see the CogVideoX block's add_adapter)
         if r <= 0:
             raise ValueError(f"LoRA rank must be positive, got {r}")
         rp = -(-int(r) // 64) * 64
         dev, D = self.ones.device, self.dim  # (self.wq is gone once the weights are stored in fp8)
-        a = torch.zeros(4, rp, D, dtype=torch.float32, device=dev)
+        nmat = 8 if text_stream else 4
+        a = torch.zeros(nmat, rp, D, dtype=torch.float32, device=dev)
         a[:, :r].uniform_(-(1.0 / D) ** 0.5, (1.0 / D) ** 0.5)  # kaiming_uniform_(a = sqrt(5)) on [r, D]
-        self.lora_A, self.lora_B = nn.Parameter(a), nn.Parameter(torch.zeros(4, D, rp, dtype=torch.float32, device=dev))
+        self.lora_A, self.lora_B = nn.Parameter(a), nn.Parameter(torch.zeros(nmat, D, rp, dtype=torch.float32, device=dev))
         self.lora_rank_user = int(r)
         self.lora_scale = float(lora_alpha) / r
 

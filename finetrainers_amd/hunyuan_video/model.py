@@ -21,6 +21,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..cogvideox.model import timestep_embedding
+from ..wan.model import select_module_names
 from .block import MI355XHunyuanDualBlock, MI355XHunyuanSingleBlock
 
 bf16 = torch.bfloat16
@@ -97,6 +98,50 @@ def _front_keys(cfg: HunyuanVideoTransformerConfig) -> List[Tuple[str, Tuple[int
     return keys
 
 
+_DUAL_VIDEO = ("attn.to_q", "attn.to_k", "attn.to_v", "attn.to_out.0")                      # adapters 0..3 of a dual-stream block
+_DUAL_TEXT = ("attn.add_q_proj", "attn.add_k_proj", "attn.add_v_proj", "attn.to_add_out")  # adapters 4..7 (add_adapter(text_stream=True))
+_SINGLE = ("attn.to_q", "attn.to_k", "attn.to_v")                                         # adapters 0..2 of a single-stream block
+
+
+def linear_module_names(cfg: HunyuanVideoTransformerConfig) -> List[str]:
+    """The diffusers names of every module of the model peft could wrap (the Conv3d patch embedding and every Linear): what a ``target_modules`` is
+    resolved against.  The token refiner's attention projections carry the same leaf names as the blocks' (``...refiner_blocks.N.attn.to_q``)."""
+    names = [k[:-len(".weight")] for k, shape in _front_keys(cfg) if k.endswith(".weight") and len(shape) == 2]
+    for i in range(cfg.num_layers):
+        p = f"transformer_blocks.{i}."
+        names += [p + n for n in ("norm1.linear", "norm1_context.linear") + _DUAL_VIDEO + _DUAL_TEXT
+                  + ("ff.net.0.proj", "ff.net.2", "ff_context.net.0.proj", "ff_context.net.2")]
+    for i in range(cfg.num_single_layers):
+        p = f"single_transformer_blocks.{i}."
+        names += [p + n for n in ("norm.linear", "proj_mlp") + _SINGLE + ("proj_out",)]
+    return names
+
+
+def resolve_target_modules(cfg: HunyuanVideoTransformerConfig, target_modules) -> bool:
+    """Which adapters ``target_modules`` asks for, by peft's rule (``select_module_names``) over ``linear_module_names(cfg)``.  ``None``: the video-only set.
+    Accepted sets are exactly two: to_q / to_k / to_v / to_out.0 of every dual-stream block and to_q / to_k / to_v of every single-stream block (returns
+    False: the reference's default regex), or those plus add_q_proj / add_k_proj / add_v_proj / to_add_out of every dual-stream block (returns True: the
+    shipped recipe's regex).  Anything else raises, naming the first module that is selected but not covered or covered but not selected."""
+    if target_modules is None:
+        return False
+    selected = select_module_names(linear_module_names(cfg), target_modules)
+    video = [f"transformer_blocks.{i}.{n}" for i in range(cfg.num_layers) for n in _DUAL_VIDEO]
+    video += [f"single_transformer_blocks.{i}.{n}" for i in range(cfg.num_single_layers) for n in _SINGLE]
+    text = [f"transformer_blocks.{i}.{n}" for i in range(cfg.num_layers) for n in _DUAL_TEXT]
+    covered = ("this backend places adapters on to_q / to_k / to_v / to_out.0 of every dual-stream block and to_q / to_k / to_v of every single-stream block, "
+               "or on those and add_q_proj / add_k_proj / add_v_proj / to_add_out of every dual-stream block")
+    known = set(video) | set(text)
+    extra = [n for n in selected if n not in known]
+    if extra:
+        raise NotImplementedError(f"target_modules {target_modules!r} selects {extra[0]}; {covered}")
+    sel = set(selected)
+    want = video + text if sel & set(text) else video
+    missing = [n for n in want if n not in sel]
+    if missing:
+        raise NotImplementedError(f"target_modules {target_modules!r} leaves out {missing[0]}; {covered}")
+    return bool(sel & set(text))
+
+
 class _HeadFunction(torch.autograd.Function):
     """Video tokens of the last block -> AdaLN-continuous (LayerNorm without affine, (1 + scale), shift from the conditioning vector) -> proj_out."""
 
@@ -137,6 +182,7 @@ class MI355XHunyuanVideoTransformer3DModel(nn.Module):
         self.transformer_blocks = nn.ModuleList([MI355XHunyuanDualBlock(D, c.num_attention_heads, c.mlp_ratio, dev) for _ in range(c.num_layers)])
         self.single_transformer_blocks = nn.ModuleList([MI355XHunyuanSingleBlock(D, c.num_attention_heads, c.mlp_ratio, dev) for _ in range(c.num_single_layers)])
         self._rope_cache: Dict[Tuple[int, int, int], Tuple[torch.Tensor, torch.Tensor]] = {}
+        self.lora_config: Optional[Dict[str, object]] = None  # set by add_adapter: {"r", "lora_alpha", "target_modules"}
 
     @property
     def device(self) -> torch.device:
@@ -157,10 +203,17 @@ class MI355XHunyuanVideoTransformer3DModel(nn.Module):
                 pre = f"{prefix}.{i}."
                 blk.load_diffusers_state_dict({k[len(pre):]: v for k, v in sd.items() if k.startswith(pre)})
 
-    def add_adapter(self, r: int = 64, lora_alpha: float = 64.0) -> None:
-        """LoRA on to_q / to_k / to_v / to_out.0 of the 60 blocks (the default target regex): 20 x 4 + 40 x 3 = 200 adapters."""
-        for blk in list(self.transformer_blocks) + list(self.single_transformer_blocks):
+    def add_adapter(self, r: int = 64, lora_alpha: float = 64.0, target_modules=None) -> None:
+        """LoRA on what ``target_modules`` selects by peft's rule (``resolve_target_modules``).  ``None`` or the reference's default regex: to_q / to_k / to_v /
+        to_out.0 of the 60 blocks, 20 x 4 + 40 x 3 = 200 adapters.  The shipped recipe's
+        ``"(transformer_blocks|single_transformer_blocks).*(to_q|to_k|to_v|to_out.0|add_q_proj|add_k_proj|add_v_proj|to_add_out)"``: also the dual-stream
+        blocks' text-stream projections, 20 x 8 + 40 x 3 = 280 adapters.  Any other selection raises."""
+        text = resolve_target_modules(self.config, target_modules)
+        for blk in self.transformer_blocks:
+            blk.add_adapter(r, lora_alpha, text_stream=text)
+        for blk in self.single_transformer_blocks:
             blk.add_adapter(r, lora_alpha)
+        self.lora_config = {"r": int(r), "lora_alpha": lora_alpha, "target_modules": target_modules}
 
     def apply_activation_checkpointing(self, checkpointing_type: str = "full", n_layer: int = 1) -> "MI355XHunyuanVideoTransformer3DModel":
         """``--gradient_checkpointing`` (trainer/sft_trainer/trainer.py:155-157 -> utils/activation_checkpoint.py:24-49): "full" = every block of both
@@ -191,34 +244,55 @@ class MI355XHunyuanVideoTransformer3DModel(nn.Module):
     def lora_parameters(self) -> List[nn.Parameter]:
         return [p for blk in list(self.transformer_blocks) + list(self.single_transformer_blocks) for p in (blk.lora_A, blk.lora_B) if p is not None]
 
-    def lora_state_dict(self) -> Dict[str, torch.Tensor]:
-        """peft-format keys: ``transformer_blocks.N.attn.to_q.lora_A.weight`` ..."""
+    def _lora_views(self, grad: bool) -> Dict[str, torch.Tensor]:
         out = {}
-        for prefix, blocks, names in (("transformer_blocks", self.transformer_blocks, ("to_q", "to_k", "to_v", "to_out.0")),
-                                      ("single_transformer_blocks", self.single_transformer_blocks, ("to_q", "to_k", "to_v"))):
+        for prefix, blocks in (("transformer_blocks", self.transformer_blocks), ("single_transformer_blocks", self.single_transformer_blocks)):
             for i, blk in enumerate(blocks):
+                if blk.lora_A is None:
+                    continue
+                names = _SINGLE if prefix.startswith("single") else (_DUAL_VIDEO + _DUAL_TEXT if blk.text_adapters else _DUAL_VIDEO)
                 r = blk.lora_rank_user  # (views of the user's rank inside the zero-padded storage)
+                a, b = (blk.lora_A.grad, blk.lora_B.grad) if grad else (blk.lora_A, blk.lora_B)
                 for j, n in enumerate(names):
-                    out[f"{prefix}.{i}.attn.{n}.lora_A.weight"] = blk.lora_A[j, :r]
-                    out[f"{prefix}.{i}.attn.{n}.lora_B.weight"] = blk.lora_B[j, :, :r]
+                    out[f"{prefix}.{i}.{n}.lora_A.weight"] = a[j, :r]
+                    out[f"{prefix}.{i}.{n}.lora_B.weight"] = b[j, :, :r]
         return out
+
+    def lora_config_metadata(self) -> Dict[str, str]:
+        """The checkpoint metadata of the adapters ``add_adapter`` placed (``wire.lora_config_metadata``): rank, alpha and the ``target_modules`` the user gave
+        (the reference's default regex when none was given)."""
+        from .. import wire
+
+        if self.lora_config is None:
+            raise RuntimeError("add_adapter first")
+        target = self.lora_config["target_modules"]
+        if target is None:
+            target = "(transformer_blocks|single_transformer_blocks).*(to_q|to_k|to_v|to_out.0)"  # sft_trainer/config.py:26
+        return wire.lora_config_metadata(self.lora_config["r"], self.lora_config["lora_alpha"], target)
+
+    def lora_state_dict(self) -> Dict[str, torch.Tensor]:
+        """peft-format keys: ``transformer_blocks.N.attn.to_q.lora_A.weight`` ... (with text-stream adapters also ``...attn.add_q_proj...`` /
+        ``add_k_proj`` / ``add_v_proj`` / ``to_add_out``)."""
+        return self._lora_views(grad=False)
 
     def lora_grad_state_dict(self) -> Dict[str, torch.Tensor]:
         """The adapters' gradients under the same peft-format keys (after a backward)."""
-        out = {}
-        for prefix, blocks, names in (("transformer_blocks", self.transformer_blocks, ("to_q", "to_k", "to_v", "to_out.0")),
-                                      ("single_transformer_blocks", self.single_transformer_blocks, ("to_q", "to_k", "to_v"))):
-            for i, blk in enumerate(blocks):
-                r = blk.lora_rank_user
-                for j, n in enumerate(names):
-                    out[f"{prefix}.{i}.attn.{n}.lora_A.weight"] = blk.lora_A.grad[j, :r]
-                    out[f"{prefix}.{i}.attn.{n}.lora_B.weight"] = blk.lora_B.grad[j, :, :r]
-        return out
+        return self._lora_views(grad=True)
 
     @torch.no_grad()
     def load_lora_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
+        """Every adapter tensor of the model must be in ``sd`` and every LoRA tensor of ``sd`` must have a place in the model: a file trained with the text-stream
+        adapters does not load into a model without them (or the reverse) -- nothing is dropped silently."""
         sd = {k.replace(".default.", "."): v for k, v in sd.items()}
-        for k, v in self.lora_state_dict().items():
+        mine = self.lora_state_dict()
+        missing = [k for k in mine if k not in sd]
+        if missing:
+            raise KeyError(f"LoRA state dict lacks {missing[0]} ({len(missing)} of the model's {len(mine)} adapter tensors are missing)")
+        extra = [k for k in sd if ".lora_" in k and k not in mine]
+        if extra:
+            raise KeyError(f"LoRA state dict holds {extra[0]}, which this model has no adapter for ({len(extra)} such tensors); call add_adapter with the "
+                           "target_modules the file was trained with")
+        for k, v in mine.items():
             v.copy_(sd[k].to(v))
 
     @torch.no_grad()

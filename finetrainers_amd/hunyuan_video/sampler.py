@@ -126,6 +126,9 @@ class MI355XHunyuanVideoLatentSampler:
         scales = {float(b.lora_scale) for b in blocks if b.lora_A is not None}
         if len(ranks) > 1 or len(scales) > 1:
             raise NotImplementedError("sample: every block carries the same adapter rank and scale (add_adapter on the model), or none does")
+        if len({b.text_adapters for b in tr.transformer_blocks}) > 1:
+            raise NotImplementedError("sample: every dual-stream block carries text-stream adapters (add_adapter on the model with the recipe's "
+                                      "target_modules), or none does")
         if tr.proj_out_w_t is None:
             raise RuntimeError("sample: load_diffusers_state_dict first")
 
@@ -160,15 +163,19 @@ class MI355XHunyuanVideoLatentSampler:
         return ops.hy_sample_geometry(B, c.out_channels, frames, height, width, patch=c.patch_size, patch_t=c.patch_size_t, true_cfg=true_cfg)
 
     def c_arguments(self, geo, T: int, steps: int, true_cfg_scale: float = 1.0):
-        """-> (ftmi_hy_sample_config, ftmi_hy_sample_weights, the objects the two structures point into).  The adapters are read here."""
+        """-> (ftmi_hy_sample_config, ftmi_hy_sample_weights, the objects the two structures point into).  The adapters are read here.  A model whose dual-stream
+        blocks carry the text stream's adapters gets the ftmi_hy_sample_text_config extension (``ops.hy_sample`` then calls ftmi_hy_sample_text)."""
         tr = self.transformer
         c = tr.config
         duals, singles = list(tr.transformer_blocks), list(tr.single_transformer_blocks)
         blocks = duals + singles
         first = blocks[0]
         r = 0 if first.lora_A is None else int(first.lora_A.shape[1])
+        text_adapters = int(bool(duals) and duals[0].text_adapters)  # (check_inputs: all dual blocks alike)
         cfg = _lib.HySampleConfig(geo=geo, T=int(T), D=c.inner_dim, H=c.num_attention_heads, mlp=int(c.inner_dim * c.mlp_ratio), Ld=len(duals), Ls=len(singles), r=r,
                                   lora_scale=float(first.lora_scale), eps=1e-6, gemm_variant=8, steps=int(steps), true_cfg=float(true_cfg_scale))
+        if text_adapters:
+            cfg = _lib.HySampleTextConfig(base=cfg, text_adapters=1)
         fp8 = any(b._w8 is not None for b in blocks)
         arena = getattr(tr, "_weight_arena_fwd", None) if fp8 else None
         if fp8 and (arena is None or not all(b._w8 is not None for b in blocks)):

@@ -2,7 +2,7 @@
 noising -> DiT forward -> MSE -> backward -> LoRA-gradient average over the data-parallel ranks -> global-norm clip -> AdamW, the last two fused over ONE flat
 fp32 buffer that the blocks' adapter Parameters are views of.  The gradients live in a second flat buffer of the same layout: the blocks' backward adds into
 its views in place (no concatenation), and under data parallelism every ``grad_bucket_blocks`` finished blocks -- a contiguous slice, the backward walks the
-buffer from its end -- are all-reduced (AVG) asynchronously on RCCL's stream while the earlier blocks still compute (315 MB at rank 64 in 8 buckets)."""
+buffer from its end -- are all-reduced (AVG) asynchronously on RCCL's stream while the earlier blocks still compute (315 MB at rank 64 in 8 buckets for the default 200 adapters)."""
 
 from __future__ import annotations
 
@@ -23,7 +23,7 @@ class MI355XHunyuanVideoSFTStep(FlatLoRAStep):
         if not self.params:
             raise ValueError("attach a LoRA adapter first (transformer.add_adapter)")
         self.transformer, self.spec, self.guidance, self.generator = transformer, spec or MI355XHunyuanVideoSpecOps(), guidance, generator
-        self.flat = self.flatten_parameters(self.params)  # all 200 adapters
+        self.flat = self.flatten_parameters(self.params)  # every adapter of the model: 200 with the default target, 280 with the text-stream adapters
         # gradient storage: one flat buffer laid out like the parameters; every block writes its two views
         self.gflat = torch.zeros_like(self.flat)
         self.grad_bucket_blocks = max(1, int(grad_bucket_blocks))

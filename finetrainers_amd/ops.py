@@ -1317,7 +1317,11 @@ def hy_sample_finish(geo, x, k: float):
 
 
 def hy_sample_workspace_bytes(cfg) -> int:
-    n = int(_lib.load().ftmi_hy_sample_workspace_bytes(ctypes.byref(cfg)))
+    """``cfg``: an ftmi_hy_sample_config, or its ftmi_hy_sample_text_config extension (text-stream adapters in the dual blocks)."""
+    if isinstance(cfg, _lib.HySampleTextConfig):
+        n = int(_lib.load().ftmi_hy_sample_text_workspace_bytes(ctypes.byref(cfg)))
+    else:
+        n = int(_lib.load().ftmi_hy_sample_workspace_bytes(ctypes.byref(cfg)))
     if n == 0:
         raise ValueError(f"hy_sample: {_lib.last_error()}")
     return n
@@ -1327,7 +1331,8 @@ def hy_sample(cfg, weights, cols, x, temb_silu, enc, head_shift, head_onep, key_
     """The whole denoising loop in ONE call (ftmi_hy_sample), in place on ``x`` / ``cols`` (as ``hy_sample_init`` wrote them).  temb_silu bf16 [steps, P B, D];
     enc bf16 [steps, P B, T, D] (the refined text of every step, unconditional rows first); head_shift / head_onep bf16 [steps, P B, D]; key_bias fp32
     [P B, T + S] or None; rope_cos / rope_sin fp32 [S, 128]; sigmas fp32 [steps + 1] on the device.  ``workspace``: a uint8 GPU tensor of at least
-    ``hy_sample_workspace_bytes(cfg)`` (allocated when None)."""
+    ``hy_sample_workspace_bytes(cfg)`` (allocated when None).  ``cfg`` of type ``_lib.HySampleTextConfig``: the same loop through ftmi_hy_sample_text."""
+    text_cfg, cfg = (cfg, cfg.base) if isinstance(cfg, _lib.HySampleTextConfig) else (None, cfg)
     geo, n, D = cfg.geo, cfg.steps, cfg.D
     _cog_sample_buffers(geo, x, cols, "hy_sample")
     S, _ = _cog_sample_dims(geo)
@@ -1340,8 +1345,13 @@ def hy_sample(cfg, weights, cols, x, temb_silu, enc, head_shift, head_onep, key_
     for name, t, dt, shape in want:
         if t is None or not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
             raise ValueError(f"hy_sample: {name} must be a contiguous {dt} {shape} GPU tensor, got {None if t is None else tuple(t.shape)}")
-    need = hy_sample_workspace_bytes(cfg)
+    need = hy_sample_workspace_bytes(text_cfg or cfg)
     if workspace is None:
         workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
+    if text_cfg is not None:
+        check(_lib.load().ftmi_hy_sample_text(ctypes.byref(text_cfg), ctypes.byref(weights), ptr(cols), ptr(x), ptr(temb_silu), ptr(enc), ptr(head_shift), ptr(head_onep),
+                                              ptr(key_bias), ptr(rope_cos), ptr(rope_sin), ptr(sigmas), ptr(workspace), workspace.numel(), stream_ptr()),
+              "ftmi_hy_sample_text")
+        return
     check(_lib.load().ftmi_hy_sample(ctypes.byref(cfg), ctypes.byref(weights), ptr(cols), ptr(x), ptr(temb_silu), ptr(enc), ptr(head_shift), ptr(head_onep),
                                      ptr(key_bias), ptr(rope_cos), ptr(rope_sin), ptr(sigmas), ptr(workspace), workspace.numel(), stream_ptr()), "ftmi_hy_sample")

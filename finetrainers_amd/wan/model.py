@@ -56,6 +56,18 @@ class WanTransformerConfig:
         return cls(**known)
 
 
+def select_module_names(names: List[str], target_modules) -> List[str]:
+    """peft's rule (tuners_utils.check_target_module_exists) over a model's module names: a string is ``re.fullmatch``ed against every name; a list or
+    tuple selects a name that equals an entry or ends with "." + entry.  Shared by every model that resolves a ``target_modules``."""
+    if isinstance(target_modules, str):
+        hit = lambda n: re.fullmatch(target_modules, n) is not None
+    elif isinstance(target_modules, (list, tuple)) and all(isinstance(t, str) for t in target_modules):
+        hit = lambda n: any(n == t or n.endswith("." + t) for t in target_modules)
+    else:
+        raise TypeError("target_modules is a regular expression (str) or a list of module-name suffixes")
+    return [n for n in names if hit(n)]
+
+
 def rotary_tables(cfg: WanTransformerConfig, frames: int, height: int, width: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """``WanRotaryPosEmbed`` for LATENT sizes: (cos, sin) fp32 [F' H' W', head_dim / 2]; the head's complex pairs split t : h : w, position tables in
     float64 like the reference (get_1d_rotary_pos_embed(freqs_dtype=float64))."""
@@ -319,14 +331,7 @@ class MI355XWanTransformer3DModel(nn.Module):
     def select_modules(self, target_modules) -> List[str]:
         """peft's rule (tuners_utils.check_target_module_exists): a string is ``re.fullmatch``ed against every module name; a list or tuple selects a name
         that equals an entry or ends with "." + entry."""
-        names = self.linear_module_names()
-        if isinstance(target_modules, str):
-            hit = lambda n: re.fullmatch(target_modules, n) is not None
-        elif isinstance(target_modules, (list, tuple)) and all(isinstance(t, str) for t in target_modules):
-            hit = lambda n: any(n == t or n.endswith("." + t) for t in target_modules)
-        else:
-            raise TypeError("target_modules is a regular expression (str) or a list of module-name suffixes")
-        return [n for n in names if hit(n)]
+        return select_module_names(self.linear_module_names(), target_modules)
 
     @staticmethod
     def _pattern_lookup(name: str, rank_pattern, alpha_pattern, rank, lora_alpha):

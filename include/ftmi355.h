@@ -642,13 +642,19 @@ int ftmi_hy_single_backward(const ftmi_hy_single_config* cfg, const ftmi_hy_sing
 /* HunyuanVideo dual-stream block (the other 20 blocks; [upstream] diffusers HunyuanVideoTransformerBlock, oracle/hunyuan.py DualStreamBlock), ONE SAMPLE per
  * call: video x_v [S, D] and text x_t [T, D] keep their own modulation (temb_silu [1, D]), projections, q / k norms and feed-forward and meet in one joint
  * attention over [text | video] (key_bias fp32 [T + S] or NULL; rope_cos / rope_sin fp32 [S, 128] on the video rows); LoRA (adapters 0..3) on the video
- * stream's to_q / to_k / to_v / to_out.0.  Buffers and gradient semantics as for the single-stream block; out_v == out_t == NULL: recomputation pass. */
+ * stream's to_q / to_k / to_v / to_out.0 and, with text_adapters = 1, (adapters 4..7) on the text stream's add_q_proj / add_k_proj / add_v_proj / to_add_out:
+ * lora_a / lora_b / grad_a / grad_b then hold eight matrices in that order, `saved` also keeps the text rows' down-projections (the recomputation pass
+ * refills them) and `scratch` holds eight operand copies and a down-projection gradient of max(S, T) rows.  text_adapters = 0 is the layout, the launch
+ * sequence and the result without the field; text_adapters = 1 with r = 0, or any other value, is FTMI_ERR_INVALID before any launch (0 bytes from the
+ * two planners).
+ * Buffers and gradient semantics as for the single-stream block; out_v == out_t == NULL: recomputation pass. */
 typedef struct {
     int T, S;         /* text tokens, video tokens of the sample */
     int D, H, mlp;    /* width = H x 128, feed-forward width */
     int r;            /* LoRA rank: 0 or a multiple of 64 */
     float lora_scale, eps;
     int gemm_variant; /* 8 */
+    int text_adapters; /* 0: adapters on the video stream only; 1: also on the text stream (needs r > 0) */
 } ftmi_hy_dual_config;
 typedef struct {
     const void *norm1_lin_w, *norm1_lin_b, *norm1c_lin_w, *norm1c_lin_b;              /* [6D, D], [6D]: norm1.linear, norm1_context.linear */
@@ -657,7 +663,7 @@ typedef struct {
     const void *norm_q_w, *norm_k_w, *norm_added_q_w, *norm_added_k_w;                /* [128] */
     const void *ff1_w, *ff1_b, *ff2_w, *ff2_b, *ffc1_w, *ffc1_b, *ffc2_w, *ffc2_b;    /* [mlp, D], [mlp], [D, mlp], [D]: ff, ff_context */
     const void *wq_t, *wk_t, *wv_t, *wo_t, *add_q_w_t, *add_k_w_t, *add_v_w_t, *add_out_w_t, *ff1_w_t, *ff2_w_t, *ffc1_w_t, *ffc2_w_t; /* transposed: backward only */
-    const float *lora_a, *lora_b;                                                     /* fp32 [4, r, D], [4, D, r]; NULL when r == 0 */
+    const float *lora_a, *lora_b;                                                     /* fp32 [4, r, D], [4, D, r] ([8, ..] with text_adapters); NULL when r == 0 */
     const void *ones, *zeros;                                                         /* bf16 [D] */
 } ftmi_hy_dual_weights;
 size_t ftmi_hy_dual_saved_bytes(const ftmi_hy_dual_config* cfg);
@@ -665,7 +671,7 @@ size_t ftmi_hy_dual_scratch_bytes(const ftmi_hy_dual_config* cfg);
 int ftmi_hy_dual_forward(const ftmi_hy_dual_config* cfg, const ftmi_hy_dual_weights* w, const void* x_v, const void* x_t, const void* temb_silu,
                          const float* key_bias, const float* rope_cos, const float* rope_sin, void* out_v, void* out_t, void* saved, size_t saved_bytes,
                          void* scratch, size_t scratch_bytes, ftmi_stream stream);
-/* ones_row: bf16 [D] of 1.0; grad_a [4, r, D] / grad_b [4, D, r] fp32 are ADDED to */
+/* ones_row: bf16 [D] of 1.0; grad_a [4, r, D] / grad_b [4, D, r] fp32 ([8, ..] with text_adapters) are ADDED to */
 int ftmi_hy_dual_backward(const ftmi_hy_dual_config* cfg, const ftmi_hy_dual_weights* w, const void* x_v, const void* x_t, const void* dout_v, const void* dout_t,
                           const float* key_bias, const float* rope_cos, const float* rope_sin, const void* ones_row, void* dx_v, void* dx_t, float* grad_a,
                           float* grad_b, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, ftmi_stream stream);
@@ -1088,6 +1094,18 @@ size_t ftmi_hy_sample_workspace_bytes(const ftmi_hy_sample_config* cfg);
 int ftmi_hy_sample(const ftmi_hy_sample_config* cfg, const ftmi_hy_sample_weights* w, void* cols, float* x, const void* temb_silu, const void* enc,
                    const void* head_shift, const void* head_onep, const float* key_bias, const float* rope_cos, const float* rope_sin, const float* sigmas,
                    void* workspace, size_t workspace_bytes, ftmi_stream stream);
+/* The same loop over a model whose dual-stream blocks carry the text stream's adapters as well: `base` as above, text_adapters as in ftmi_hy_dual_config (1: every
+ * dual block's lora_a / lora_b hold 8 matrices; needs base.r > 0; other values than 0 / 1 are FTMI_ERR_INVALID, a workspace size of 0).  The flag is handed to every
+ * ftmi_hy_dual_forward of the walk and the workspace follows that block's layout.  text_adapters = 0 is ftmi_hy_sample: the same workspace, launches and bits.
+ * (ftmi_hy_sample_config keeps its size: the extension is a structure of its own, like ftmi_wan_lora_ffn_block_config over ftmi_wan_i2v_lora_block_config.) */
+typedef struct ftmi_hy_sample_text_config {
+    ftmi_hy_sample_config base;
+    int text_adapters;        /* 0 or 1 */
+} ftmi_hy_sample_text_config;
+size_t ftmi_hy_sample_text_workspace_bytes(const ftmi_hy_sample_text_config* cfg);
+int ftmi_hy_sample_text(const ftmi_hy_sample_text_config* cfg, const ftmi_hy_sample_weights* w, void* cols, float* x, const void* temb_silu, const void* enc,
+                        const void* head_shift, const void* head_onep, const float* key_bias, const float* rope_cos, const float* rope_sin, const float* sigmas,
+                        void* workspace, size_t workspace_bytes, ftmi_stream stream);
 
 #ifdef __cplusplus
 }

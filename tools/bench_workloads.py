@@ -371,9 +371,12 @@ def build_wan_i2v_lora(args, par, dev) -> Dict[str, Any]:
 # HunyuanVideo LoRA, fp8 weight storage (configs[4]): 61 x 544 x 960 -> latents [1, 16, 16, 68, 120], 32 640 video + 256 text tokens,
 # 20 dual-stream + 40 single-stream blocks (12.8 B parameters), batch 1 per GPU
 # ------------------------------------------------------------------------------------------------------------------------------------------
-def _random_hunyuan(nd: int, ns: int, rank: int, dev):
+HY_RECIPE_TARGET = "(transformer_blocks|single_transformer_blocks).*(to_q|to_k|to_v|to_out.0|add_q_proj|add_k_proj|add_v_proj|to_add_out)"
+
+
+def _random_hunyuan(nd: int, ns: int, rank: int, dev, text_adapters: bool = False):
     """Random-init weights of the DiT rounded to fp8-representable values and stored as fp8 bytes (layerwise casting), with rank-``rank`` adapters whose B is
-    non-zero -> (model, the generator that drew them)."""
+    non-zero -> (model, the generator that drew them).  ``text_adapters``: the shipped recipe's target_modules (eight adapters per dual-stream block)."""
     from finetrainers_amd import ops
     from finetrainers_amd.hunyuan_video import HunyuanVideoTransformerConfig, MI355XHunyuanVideoTransformer3DModel
 
@@ -399,7 +402,10 @@ def _random_hunyuan(nd: int, ns: int, rank: int, dev):
             for name in getattr(blk, "_TRANSPOSED", ("wq", "wk", "wv", "proj_mlp_w", "proj_out_w")):
                 setattr(blk, name + "_t", ops.transpose_bf16(getattr(blk, name)))
     model.apply_layerwise_casting()
-    model.add_adapter(r=rank, lora_alpha=float(rank))
+    if text_adapters:
+        model.add_adapter(r=rank, lora_alpha=float(rank), target_modules=HY_RECIPE_TARGET)
+    else:
+        model.add_adapter(r=rank, lora_alpha=float(rank))
     with torch.no_grad():
         for p in model.lora_parameters()[1::2]:
             p.normal_(0, 0.01, generator=g)  # B != 0 so every gradient path carries data
@@ -410,7 +416,8 @@ def build_hunyuan(args, par, dev) -> Dict[str, Any]:
     from finetrainers_amd.hunyuan_video import MI355XHunyuanVideoSFTStep
 
     nd, ns = (20, 40) if args.layers <= 0 else (max(1, args.layers // 3), max(1, args.layers - args.layers // 3))
-    model, g = _random_hunyuan(nd, ns, args.rank, dev)
+    text_adapters = bool(getattr(args, "text_adapters", False))
+    model, g = _random_hunyuan(nd, ns, args.rank, dev, text_adapters)
     cfg = model.config
     ckpt = bool(getattr(args, "gradient_checkpointing", False))
     if ckpt:
@@ -442,7 +449,8 @@ def build_hunyuan(args, par, dev) -> Dict[str, Any]:
         "config": {"workload": f"HunyuanVideo LoRA rank={args.rank} SFT step, fp8 weight storage / bf16 compute, 61x544x960 clip ({S} video + {T} text tokens), batch 1 per GPU, "
                                f"{nd} dual-stream + {ns} single-stream blocks (BASELINE configs[4])" + ("" if full else " -- REDUCED depth"),
                    "model": "HunyuanVideo DiT: 20 dual + 40 single blocks, width 3072, 24 x 128 heads, 12.8 B frozen parameters", "seq_len": N,
-                   "activation_checkpointing": ckpt, "weight_storage": "float8_e4m3fn bytes in HBM, per-block up-cast into a shared bf16 arena",
+                   "activation_checkpointing": ckpt, "adapters": 8 * nd + 3 * ns if text_adapters else 4 * nd + 3 * ns, "text_stream_adapters": text_adapters,
+                   "weight_storage": "float8_e4m3fn bytes in HBM, per-block up-cast into a shared bf16 arena",
                    "orchestration": ("one C call per block and direction (ftmi_hy_single_* / ftmi_hy_dual_*)" if os.environ.get("FTMI_NATIVE_BLOCKS", "1") != "0" else "python, per kernel over the C ABI")},
         "layers": nd + ns,
         "dual_single": (nd, ns, dual, single),
@@ -725,7 +733,8 @@ def build_hy_sample(args, par, dev) -> Dict[str, Any]:
     from finetrainers_amd.hunyuan_video import MI355XHunyuanVideoLatentSampler, hy_flow_match_sigmas
 
     nd, ns = (20, 40) if args.layers <= 0 else (max(1, args.layers // 3), max(1, args.layers - args.layers // 3))
-    model, _ = _random_hunyuan(nd, ns, args.rank, dev)
+    text_adapters = bool(getattr(args, "text_adapters", False))
+    model, _ = _random_hunyuan(nd, ns, args.rank, dev, text_adapters)
     cfg = model.config
     g = torch.Generator(device=dev).manual_seed(3)
     B, C, F_, H, W, T, guidance_scale, n = 1, 16, 16, 68, 120, 256, 6.0, SAMPLE_STEPS
@@ -816,7 +825,8 @@ def build_hy_sample(args, par, dev) -> Dict[str, Any]:
         "data": "random noise [1,16,16,68,120] + random text embeds [1,256,4096] (200 real tokens) + pooled [1,768], random-init weights of the HunyuanVideo DiT "
                 "stored as fp8 bytes",
         "config": {"workload": f"HunyuanVideo latent sampling, rank={args.rank} adapters, fp8 weight storage, {S} video + {T} text tokens, 1 model row, "
-                               f"{nd} dual-stream + {ns} single-stream blocks" + ("" if full else " -- REDUCED depth"), "seq_len": N, "denoising_steps_per_call": n},
+                               f"{nd} dual-stream + {ns} single-stream blocks" + ("" if full else " -- REDUCED depth"), "seq_len": N, "denoising_steps_per_call": n,
+                   "text_stream_adapters": text_adapters},
         "layers": nd + ns,
     }
 
@@ -843,7 +853,7 @@ WORKLOADS = {"cogvideox": (build_cogvideox, lambda a, c: cpu_baseline_cogvideox(
 def main() -> None:
     """One workload on one GPU, outside bench.py (whose --workload list is fixed): 1 JSON line with the builder's static part plus step_ms (median), every
     step's ms, samples/s, achieved TFLOP/s and the peak allocated memory.  ``python tools/bench_workloads.py --workload wan_lora --steps 5 --warmup 1
-    [--gradient-checkpointing] [--ffn-adapters]``."""
+    [--gradient-checkpointing] [--ffn-adapters] [--text-adapters]``."""
     import argparse
     import json
     import sys
@@ -858,6 +868,8 @@ def main() -> None:
     ap.add_argument("--rank", type=int, default=32)
     ap.add_argument("--gradient-checkpointing", dest="gradient_checkpointing", action="store_true")
     ap.add_argument("--ffn-adapters", dest="ffn_adapters", action="store_true", help="wan_lora: adapters on ffn.net.0.proj and ffn.net.2 as well (ten per block)")
+    ap.add_argument("--text-adapters", dest="text_adapters", action="store_true",
+                    help="hunyuan / hy_sample: the shipped recipe's target_modules -- adapters on add_q_proj / add_k_proj / add_v_proj / to_add_out of the dual-stream blocks too")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     ctx = WORKLOADS[args.workload][0](args, types.SimpleNamespace(world_size=1, rank=0), dev)
