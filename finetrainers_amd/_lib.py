@@ -129,18 +129,6 @@ class WanBlockConfig(Structure):
     _fields_ = [("B", c_int), ("S", c_int), ("T", c_int), ("D", c_int), ("H", c_int), ("F", c_int), ("eps", c_float), ("gemm_variant", c_int)]
 
 
-class WanLoraBlockConfig(Structure):
-    """include/ftmi355.h: ftmi_wan_lora_block_config."""
-
-    _fields_ = WanBlockConfig._fields_ + [("r", c_int), ("lora_scale", c_float)]
-
-
-class WanI2VLoraBlockConfig(Structure):
-    """include/ftmi355.h: ftmi_wan_i2v_lora_block_config."""
-
-    _fields_ = WanLoraBlockConfig._fields_ + [("TI", c_int)]
-
-
 WAN_LORA_WEIGHT_FIELDS = ["params", "w_qkv1_t", "w_o1_t", "w_q2_t", "w_kv2_t", "w_o2_t", "w_f1_t", "w_f2_t", "lora_a", "lora_b"]
 
 
@@ -153,7 +141,7 @@ class WanLoraBlockWeights(Structure):
 class WanLoraFfnBlockConfig(Structure):
     """include/ftmi355.h: ftmi_wan_lora_ffn_block_config."""
 
-    _fields_ = WanI2VLoraBlockConfig._fields_ + [("ffn", c_int)]
+    _fields_ = WanBlockConfig._fields_ + [("r", c_int), ("lora_scale", c_float), ("TI", c_int), ("ffn", c_int)]
 
 
 class WanLoraFfnBlockWeights(Structure):
@@ -384,16 +372,6 @@ _SIGS = {
     "ftmi_hy_single_scratch_bytes": (c_size_t, [POINTER(HySingleConfig)]),
     "ftmi_hy_single_forward": (c_int, [POINTER(HySingleConfig), POINTER(HySingleWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
-    "ftmi_wan_lora_block_saved_bytes": (c_size_t, [POINTER(WanLoraBlockConfig)]),
-    "ftmi_wan_lora_block_scratch_bytes": (c_size_t, [POINTER(WanLoraBlockConfig)]),
-    "ftmi_wan_lora_block_forward": (c_int, [POINTER(WanLoraBlockConfig), POINTER(WanLoraBlockWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                            c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
-    "ftmi_wan_lora_block_backward": (c_int, [POINTER(WanLoraBlockConfig), POINTER(WanLoraBlockWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
-    "ftmi_wan_i2v_lora_block_saved_bytes": (c_size_t, [POINTER(WanI2VLoraBlockConfig)]),
-    "ftmi_wan_i2v_lora_block_scratch_bytes": (c_size_t, [POINTER(WanI2VLoraBlockConfig)]),
-    "ftmi_wan_i2v_lora_block_forward": (c_int, [POINTER(WanI2VLoraBlockConfig), POINTER(WanLoraBlockWeights)] + [c_void_p] * 9 + [c_size_t, c_void_p, c_size_t, c_void_p]),
-    "ftmi_wan_i2v_lora_block_backward": (c_int, [POINTER(WanI2VLoraBlockConfig), POINTER(WanLoraBlockWeights)] + [c_void_p] * 13 + [c_size_t, c_void_p, c_size_t, c_void_p]),
     "ftmi_wan_lora_ffn_block_saved_bytes": (c_size_t, [POINTER(WanLoraFfnBlockConfig)]),
     "ftmi_wan_lora_ffn_block_scratch_bytes": (c_size_t, [POINTER(WanLoraFfnBlockConfig)]),
     "ftmi_wan_lora_ffn_block_forward": (c_int, [POINTER(WanLoraFfnBlockConfig), POINTER(WanLoraFfnBlockWeights)] + [c_void_p] * 9 + [c_size_t, c_void_p, c_size_t, c_void_p]),

@@ -143,7 +143,7 @@ using namespace ftmi;
 
 extern "C" {
 
-int ftmi_version(void) { return 100; }
+int ftmi_version(void) { return 101; }
 
 int ftmi_prof_enable(int stride) {
     std::lock_guard<std::mutex> lk(g_prof_mu);
@@ -849,46 +849,6 @@ int ftmi_wan_block_backward(const ftmi_wan_block_config* cfg, const void* params
         return set_error(FTMI_ERR_INVALID, "ftmi_wan_block_backward: null argument");
     return wan_block_backward(*cfg, (const bf16_t*)params, grads, (const bf16_t*)x, (const bf16_t*)enc, mod, rope_cos, rope_sin, (const bf16_t*)dout, (bf16_t*)dx,
                               (bf16_t*)denc, dmod, saved, saved_bytes, scratch, scratch_bytes, (hipStream_t)stream);
-}
-
-size_t ftmi_wan_lora_block_saved_bytes(const ftmi_wan_lora_block_config* cfg) { return cfg ? wan_lora_block_saved_bytes(*cfg) : 0; }
-size_t ftmi_wan_lora_block_scratch_bytes(const ftmi_wan_lora_block_config* cfg) { return cfg ? wan_lora_block_scratch_bytes(*cfg) : 0; }
-int ftmi_wan_lora_block_forward(const ftmi_wan_lora_block_config* cfg, const ftmi_wan_lora_block_weights* w, const void* x, const void* enc, const float* mod,
-                                const float* rope_cos, const float* rope_sin, void* out, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
-                                ftmi_stream stream) {
-    if (!cfg || !w || !w->params || !x || !enc || !mod || !rope_cos || !rope_sin || !saved || !scratch)
-        return set_error(FTMI_ERR_INVALID, "ftmi_wan_lora_block_forward: null argument");
-    return wan_lora_block_forward(*cfg, *w, (const bf16_t*)x, (const bf16_t*)enc, mod, rope_cos, rope_sin, (bf16_t*)out, saved, saved_bytes, scratch, scratch_bytes,
-                                  (hipStream_t)stream);
-}
-int ftmi_wan_lora_block_backward(const ftmi_wan_lora_block_config* cfg, const ftmi_wan_lora_block_weights* w, const void* x, const void* enc, const float* mod,
-                                 const float* rope_cos, const float* rope_sin, const void* dout, void* dx, void* denc, float* grad_a, float* grad_b, void* saved,
-                                 size_t saved_bytes, void* scratch, size_t scratch_bytes, ftmi_stream stream) {
-    if (!cfg || !w || !w->params || !x || !enc || !mod || !rope_cos || !rope_sin || !dout || !dx || !saved || !scratch)
-        return set_error(FTMI_ERR_INVALID, "ftmi_wan_lora_block_backward: null argument");
-    return wan_lora_block_backward(*cfg, *w, (const bf16_t*)x, (const bf16_t*)enc, mod, rope_cos, rope_sin, (const bf16_t*)dout, (bf16_t*)dx, (bf16_t*)denc, grad_a,
-                                   grad_b, saved, saved_bytes, scratch, scratch_bytes, (hipStream_t)stream);
-}
-
-size_t ftmi_wan_i2v_lora_block_saved_bytes(const ftmi_wan_i2v_lora_block_config* cfg) { return cfg ? wan_i2v_lora_block_saved_bytes(*cfg) : 0; }
-size_t ftmi_wan_i2v_lora_block_scratch_bytes(const ftmi_wan_i2v_lora_block_config* cfg) { return cfg ? wan_i2v_lora_block_scratch_bytes(*cfg) : 0; }
-int ftmi_wan_i2v_lora_block_forward(const ftmi_wan_i2v_lora_block_config* cfg, const ftmi_wan_lora_block_weights* w, const void* img_params, const void* x,
-                                    const void* enc, const void* enc_img, const float* mod, const float* rope_cos, const float* rope_sin, void* out, void* saved,
-                                    size_t saved_bytes, void* scratch, size_t scratch_bytes, ftmi_stream stream) {
-    if (!cfg || !w || !w->params || !x || !enc || !mod || !rope_cos || !rope_sin || !saved || !scratch || (cfg->TI > 0 && (!img_params || !enc_img)))
-        return set_error(FTMI_ERR_INVALID, "ftmi_wan_i2v_lora_block_forward: null argument");
-    return wan_i2v_lora_block_forward(*cfg, *w, (const bf16_t*)img_params, (const bf16_t*)x, (const bf16_t*)enc, (const bf16_t*)enc_img, mod, rope_cos, rope_sin,
-                                      (bf16_t*)out, saved, saved_bytes, scratch, scratch_bytes, (hipStream_t)stream);
-}
-int ftmi_wan_i2v_lora_block_backward(const ftmi_wan_i2v_lora_block_config* cfg, const ftmi_wan_lora_block_weights* w, const void* img_params, const void* x,
-                                     const void* enc, const void* enc_img, const float* mod, const float* rope_cos, const float* rope_sin, const void* dout,
-                                     void* dx, void* denc, float* grad_a, float* grad_b, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
-                                     ftmi_stream stream) {
-    if (!cfg || !w || !w->params || !x || !enc || !mod || !rope_cos || !rope_sin || !dout || !dx || !saved || !scratch || (cfg->TI > 0 && (!img_params || !enc_img)))
-        return set_error(FTMI_ERR_INVALID, "ftmi_wan_i2v_lora_block_backward: null argument");
-    return wan_i2v_lora_block_backward(*cfg, *w, (const bf16_t*)img_params, (const bf16_t*)x, (const bf16_t*)enc, (const bf16_t*)enc_img, mod, rope_cos, rope_sin,
-                                       (const bf16_t*)dout, (bf16_t*)dx, (bf16_t*)denc, grad_a, grad_b, saved, saved_bytes, scratch, scratch_bytes,
-                                       (hipStream_t)stream);
 }
 
 size_t ftmi_wan_lora_ffn_block_saved_bytes(const ftmi_wan_lora_ffn_block_config* cfg) { return cfg ? wan_lora_ffn_block_saved_bytes(*cfg) : 0; }

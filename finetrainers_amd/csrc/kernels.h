@@ -393,26 +393,8 @@ int wan_block_forward(const ftmi_wan_block_config& c, const bf16_t* params, cons
 int wan_block_backward(const ftmi_wan_block_config& c, const bf16_t* params, float* grads, const bf16_t* x, const bf16_t* enc, const float* mod,
                        const float* rope_cos, const float* rope_sin, const bf16_t* dout, bf16_t* dx, bf16_t* denc, float* dmod, void* saved,
                        size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st);
-// the same block over a frozen base with LoRA adapters on the eight attention projections (wan_dit.hip)
-size_t wan_lora_block_saved_bytes(const ftmi_wan_lora_block_config& c);
-size_t wan_lora_block_scratch_bytes(const ftmi_wan_lora_block_config& c);
-int wan_lora_block_forward(const ftmi_wan_lora_block_config& c, const ftmi_wan_lora_block_weights& w, const bf16_t* x, const bf16_t* enc, const float* mod,
-                           const float* rope_cos, const float* rope_sin, bf16_t* out, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
-                           hipStream_t st);
-int wan_lora_block_backward(const ftmi_wan_lora_block_config& c, const ftmi_wan_lora_block_weights& w, const bf16_t* x, const bf16_t* enc, const float* mod,
-                            const float* rope_cos, const float* rope_sin, const bf16_t* dout, bf16_t* dx, bf16_t* denc, float* grad_a, float* grad_b, void* saved,
-                            size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st);
-// image-to-video: the LoRA block with the image context in attn2 (cfg.TI image tokens; TI = 0: the calls above)
-size_t wan_i2v_lora_block_saved_bytes(const ftmi_wan_i2v_lora_block_config& c);
-size_t wan_i2v_lora_block_scratch_bytes(const ftmi_wan_i2v_lora_block_config& c);
-int wan_i2v_lora_block_forward(const ftmi_wan_i2v_lora_block_config& c, const ftmi_wan_lora_block_weights& w, const bf16_t* img_params, const bf16_t* x,
-                               const bf16_t* enc, const bf16_t* enc_img, const float* mod, const float* rope_cos, const float* rope_sin, bf16_t* out, void* saved,
-                               size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st);
-int wan_i2v_lora_block_backward(const ftmi_wan_i2v_lora_block_config& c, const ftmi_wan_lora_block_weights& w, const bf16_t* img_params, const bf16_t* x,
-                                const bf16_t* enc, const bf16_t* enc_img, const float* mod, const float* rope_cos, const float* rope_sin, const bf16_t* dout,
-                                bf16_t* dx, bf16_t* denc, float* grad_a, float* grad_b, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
-                                hipStream_t st);
-// ... and with adapters on the two feed-forward projections (cfg.ffn; TI = 0 and ffn = 0: the calls above)
+// the same block over a frozen base with LoRA adapters on the eight attention projections, the image context of attn2 (cfg.TI image tokens, 0: none) and,
+// cfg.ffn = 1, adapters on the two feed-forward projections as well (wan_dit.hip): the one LoRA entry, text-to-video and image-to-video
 size_t wan_lora_ffn_block_saved_bytes(const ftmi_wan_lora_ffn_block_config& c);
 size_t wan_lora_ffn_block_scratch_bytes(const ftmi_wan_lora_ffn_block_config& c);
 int wan_lora_ffn_block_forward(const ftmi_wan_lora_ffn_block_config& c, const ftmi_wan_lora_ffn_block_weights& w, const bf16_t* img_params, const bf16_t* x,

@@ -11,8 +11,8 @@
 //     n3 = LN(x2) * (1 + scale_ff) + shift_ff;  out = x2 + gate_ff * (gelu_tanh(n3 W_1^T + b) W_2^T + b)
 //
 // Reference: [upstream] diffusers WanTransformerBlock / WanAttnProcessor2_0 as driven by finetrainers/models/wan/base_specification.py:433-493,
-// restated in oracle/wan.py.  There is ONE walk per direction (block_forward / block_backward); the four entry points differ in the context they hand
-// it.  The kernel sequence is the one finetrainers_amd/wan/block.py (_block_forward / _block_backward) issues from Python, which stays as the second
+// restated in oracle/wan.py.  There is ONE walk per direction (block_forward / block_backward); the four entry points (wan_block_* for full fine-tuning,
+// wan_lora_ffn_block_* for every LoRA configuration) differ in the context they hand it.  The kernel sequence is the one finetrainers_amd/wan/block.py (_block_forward / _block_backward) issues from Python, which stays as the second
 // implementation (the tests compare the two bit for bit, what is summed with fp32 atomics up to their order).
 //
 // LoRA (the reference's Wan SFT recipes: --training_type lora, --target_modules "blocks.*(to_q|to_k|to_v|to_out.0)"): the base weights are FROZEN, fp32
@@ -51,7 +51,7 @@
 // B S (D + F) 2 bytes per block -- 426 MB at the recipe's bucket (20 280 tokens, D 1536, F 8960).  Gradient checkpointing brings that back to one block's
 // worth: its recomputation pass refills n3, act, pre, xa_f1 with the identical launches and xa_f2 with net.2's down-projection alone.
 //
-// Image-to-video (Wan2.1-I2V: attn2 with added_kv_proj_dim; the ftmi_wan_i2v_lora_block_* entries, TI > 0 image tokens enc_img [B, TI, D]): attn2 attends to a
+// Image-to-video (Wan2.1-I2V: attn2 with added_kv_proj_dim; the same entries with cfg.TI > 0 image tokens enc_img [B, TI, D]): attn2 attends to a
 // second, FROZEN key/value set  k_i = RMSNorm(enc_img W_ak^T + b), v_i = enc_img W_av^T + b  (one N = 2D GEMM and one RMSNorm over the B TI image rows) and
 //   o2 = bf(attention(q2, k2, v2)) + bf(attention(q2, k_i, v_i))
 // -- the second attention (attn_ctx2.hip) reads the first one's output and writes the sum, so the forward adds 3 launches (29) and the backward ONE (36): the
@@ -214,45 +214,29 @@ int check_cfg(const ftmi_wan_block_config& c) {
     return 0;
 }
 
-ftmi_wan_block_config base_cfg(const ftmi_wan_lora_block_config& c) {
+ftmi_wan_block_config base_cfg(const ftmi_wan_lora_ffn_block_config& c) {
     ftmi_wan_block_config b;
     b.B = c.B; b.S = c.S; b.T = c.T; b.D = c.D; b.H = c.H; b.F = c.F; b.eps = c.eps; b.gemm_variant = c.gemm_variant;
     return b;
 }
 
-int check_lora_cfg(const ftmi_wan_lora_block_config& c) {
+// every refusal of the LoRA block: the byte planners and both directions go through it
+int check_lora_cfg(const ftmi_wan_lora_ffn_block_config& c) {
     FTMI_TRY(check_cfg(base_cfg(c)));
     // (the split down-projection and the token-reduction GEMM work on whole groups of 64 adapter rows)
-    if (c.r < 0 || (c.r % 64) != 0 || c.r > 128) return set_error(FTMI_ERR_UNSUPPORTED, "wan_lora_block: LoRA rank must be 0, 64 or 128 (pad other ranks with zeros)");
-    if (c.r > 0 && c.D < 256) return set_error(FTMI_ERR_UNSUPPORTED, "wan_lora_block: adapters need a width of at least 256");
-    return 0;
-}
-
-ftmi_wan_lora_block_config lora_cfg(const ftmi_wan_i2v_lora_block_config& c) {
-    ftmi_wan_lora_block_config l;
-    l.B = c.B; l.S = c.S; l.T = c.T; l.D = c.D; l.H = c.H; l.F = c.F; l.eps = c.eps; l.gemm_variant = c.gemm_variant; l.r = c.r; l.lora_scale = c.lora_scale;
-    return l;
-}
-
-int check_i2v_cfg(const ftmi_wan_i2v_lora_block_config& c) {
-    FTMI_TRY(check_lora_cfg(lora_cfg(c)));
-    if (c.TI < 0 || c.TI > 320) return set_error(FTMI_ERR_UNSUPPORTED, "wan_i2v_lora_block: the image context holds 0 .. 320 tokens");
-    return 0;
-}
-
-ftmi_wan_i2v_lora_block_config i2v_cfg(const ftmi_wan_lora_ffn_block_config& c) {
-    ftmi_wan_i2v_lora_block_config l;
-    l.B = c.B; l.S = c.S; l.T = c.T; l.D = c.D; l.H = c.H; l.F = c.F; l.eps = c.eps; l.gemm_variant = c.gemm_variant; l.r = c.r; l.lora_scale = c.lora_scale; l.TI = c.TI;
-    return l;
-}
-
-int check_ffn_cfg(const ftmi_wan_lora_ffn_block_config& c) {
-    FTMI_TRY(check_i2v_cfg(i2v_cfg(c)));
+    if (c.r < 0 || (c.r % 64) != 0 || c.r > 128) return set_error(FTMI_ERR_UNSUPPORTED, "wan_lora_ffn_block: LoRA rank must be 0, 64 or 128 (pad other ranks with zeros)");
+    if (c.r > 0 && c.D < 256) return set_error(FTMI_ERR_UNSUPPORTED, "wan_lora_ffn_block: adapters need a width of at least 256");
+    if (c.TI < 0 || c.TI > 320) return set_error(FTMI_ERR_UNSUPPORTED, "wan_lora_ffn_block: the image context holds 0 .. 320 tokens");
     if (c.ffn != 0 && c.ffn != 1) return set_error(FTMI_ERR_INVALID, "wan_lora_ffn_block: ffn is 0 or 1");
     if (c.ffn && c.r == 0) return set_error(FTMI_ERR_UNSUPPORTED, "wan_lora_ffn_block: feed-forward adapters take the block's rank, which is 0");
     // (the split down-projection contracts over at least 256 columns: XA_2 = s act A_2^T and dXA_1 = s dpre B_1 contract over F)
     if (c.ffn && c.F < 256) return set_error(FTMI_ERR_UNSUPPORTED, "wan_lora_ffn_block: feed-forward adapters need a feed-forward width of at least 256");
     return 0;
+}
+
+// the frozen base's plan of one LoRA configuration (the byte planners pass no bases)
+Bufs lora_layout(const ftmi_wan_lora_ffn_block_config& c, void* saved = nullptr, void* scratch = nullptr) {
+    return make_layout(base_cfg(c), c.r, true, saved, scratch, c.TI, c.ffn != 0);
 }
 
 // the image context of attn2: TI tokens enc_img [B, TI, D] and the frozen flat buffer  add_k | add_v weight [2D, D], their biases [2D], norm_added_k [D]
@@ -561,8 +545,6 @@ Block make_block(const ftmi_wan_block_config& c, const void* params, const Bufs&
 size_t wan_block_saved_bytes(const ftmi_wan_block_config& c) { return make_layout(c, 0, false).saved_total; }
 size_t wan_block_scratch_bytes(const ftmi_wan_block_config& c) { return make_layout(c, 0, false).scratch_total; }
 size_t wan_block_param_elements(const ftmi_wan_block_config& c) { return offsets_of(c.D, c.F).total; }
-size_t wan_lora_block_saved_bytes(const ftmi_wan_lora_block_config& c) { return make_layout(base_cfg(c), c.r, true).saved_total; }
-size_t wan_lora_block_scratch_bytes(const ftmi_wan_lora_block_config& c) { return make_layout(base_cfg(c), c.r, true).scratch_total; }
 
 int wan_block_forward(const ftmi_wan_block_config& c, const bf16_t* params, const bf16_t* x, const bf16_t* enc, const float* mod, const float* rope_cos,
                       const float* rope_sin, bf16_t* out, void* saved, size_t saved_bytes, hipStream_t st) {
@@ -598,12 +580,6 @@ int wan_block_backward(const ftmi_wan_block_config& c, const bf16_t* params, flo
 
 namespace {
 
-// the feed-forward adapters of one call (on: a1 != null) and, for the backward, where their gradients are added
-struct FfnLora {
-    const float *a1 = nullptr, *b1 = nullptr, *a2 = nullptr, *b2 = nullptr;  // fp32 A_1 [r, D], B_1 [F, r], A_2 [r, F], B_2 [D, r]
-    float *ga1 = nullptr, *gb1 = nullptr, *ga2 = nullptr, *gb2 = nullptr;
-};
-
 // one fp32 matrix [rows, cols] into one of its four operand layouts (LoraSplitArgs)
 int split_one(const float* wm, int rows, int cols, bf16_t* sp, bf16_t* ext, bf16_t* t_sp, bf16_t* t_ext, hipStream_t st) {
     LoraSplitArgs a;
@@ -611,161 +587,99 @@ int split_one(const float* wm, int rows, int cols, bf16_t* sp, bf16_t* ext, bf16
     return lora_split(a, st);
 }
 
-Adp ffn_adp(const ftmi_wan_lora_block_config& c, const bf16_t* sp, const bf16_t* ext, bf16_t* xa, float* ga, float* gb) {
+Adp ffn_adp(const ftmi_wan_lora_ffn_block_config& c, const bf16_t* sp, const bf16_t* ext, bf16_t* xa, float* ga, float* gb) {
     Adp a;
     a.n = 1; a.r = c.r; a.s = c.lora_scale; a.sp = sp; a.ext = ext; a.ld_ext = 3L * c.r; a.xa = xa; a.ga = ga; a.gb = gb;
     return a;
 }
 
-int lora_forward(const ftmi_wan_lora_block_config& c, const ftmi_wan_lora_block_weights& w, const ImgCtx& img, const bf16_t* x, const bf16_t* enc, const float* mod,
-                 const float* rope_cos, const float* rope_sin, bf16_t* out, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st,
-                 const FfnLora& ffn = FfnLora()) {
-    const Bufs L = make_layout(base_cfg(c), c.r, true, saved, scratch, img.TI, ffn.a1 != nullptr);
-    if (saved_bytes < L.saved_total || scratch_bytes < L.scratch_total) return set_error(FTMI_ERR_INVALID, "wan_lora_block_forward: buffer too small");
-    if (c.r > 0 && (!w.lora_a || !w.lora_b)) return set_error(FTMI_ERR_INVALID, "wan_lora_block_forward: LoRA rank without adapters");
-    Block k = make_block(base_cfg(c), w.params, L, x, enc, mod, rope_cos, rope_sin, st);
-    k.img = img;
-    const int D = c.D, r = c.r;
-    k.lo.r = r; k.lo.s = c.lora_scale;
+// the frozen-base block of one LoRA call: its plan, its parameters and the image context of attn2 (TI = 0: none)
+Block lora_block(const ftmi_wan_lora_ffn_block_config& c, const ftmi_wan_lora_ffn_block_weights& w, const Bufs& L, const bf16_t* img_params, const bf16_t* x,
+                 const bf16_t* enc, const bf16_t* enc_img, const float* mod, const float* rope_cos, const float* rope_sin, hipStream_t st) {
+    Block k = make_block(base_cfg(c), w.base.params, L, x, enc, mod, rope_cos, rope_sin, st);
+    k.img.TI = c.TI; k.img.params = img_params; k.img.enc = enc_img;
+    k.lo.r = c.r; k.lo.s = c.lora_scale;
+    return k;
+}
+
+}  // namespace
+
+// The LoRA block: adapters on the eight attention projections (cfg.r, 0: none), the image context of attn2 (cfg.TI image tokens, 0: none: text-to-video) and,
+// cfg.ffn = 1, adapters on the two feed-forward projections as well.  (The planners return 0 for a configuration the block refuses: the message is in
+// ftmi_last_error.)
+size_t wan_lora_ffn_block_saved_bytes(const ftmi_wan_lora_ffn_block_config& c) { return check_lora_cfg(c) ? 0 : lora_layout(c).saved_total; }
+size_t wan_lora_ffn_block_scratch_bytes(const ftmi_wan_lora_ffn_block_config& c) { return check_lora_cfg(c) ? 0 : lora_layout(c).scratch_total; }
+
+int wan_lora_ffn_block_forward(const ftmi_wan_lora_ffn_block_config& c, const ftmi_wan_lora_ffn_block_weights& w, const bf16_t* img_params, const bf16_t* x,
+                               const bf16_t* enc, const bf16_t* enc_img, const float* mod, const float* rope_cos, const float* rope_sin, bf16_t* out, void* saved,
+                               size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st) {
+    FTMI_TRY(check_lora_cfg(c));
+    if (c.TI > 0 && (!img_params || !enc_img)) return set_error(FTMI_ERR_INVALID, "wan_lora_ffn_block_forward: image tokens without their parameters");
+    if (c.ffn && (!w.ffn_a1 || !w.ffn_b1 || !w.ffn_a2 || !w.ffn_b2)) return set_error(FTMI_ERR_INVALID, "wan_lora_ffn_block_forward: feed-forward adapters missing");
+    const Bufs L = lora_layout(c, saved, scratch);
+    if (saved_bytes < L.saved_total || scratch_bytes < L.scratch_total) return set_error(FTMI_ERR_INVALID, "wan_lora_ffn_block_forward: buffer too small");
+    if (c.r > 0 && (!w.base.lora_a || !w.base.lora_b)) return set_error(FTMI_ERR_INVALID, "wan_lora_ffn_block_forward: LoRA rank without adapters");
+    Block k = lora_block(c, w, L, img_params, x, enc, enc_img, mod, rope_cos, rope_sin, st);
+    const int D = c.D, F = c.F, r = c.r;
     if (r > 0) {  // operand copies of the fp32 adapters, once per call: A as (hi, lo) row planes, B as [hi | hi | lo] K-extension columns
         LoraSplitArgs sa;
-        sa.w = w.lora_a; sa.rows = r; sa.cols = D; sa.nmat = 8; sa.in_bstride = (long)r * D; sa.sp = L.a_sp; sa.sp_bstride = 2L * r * D;
+        sa.w = w.base.lora_a; sa.rows = r; sa.cols = D; sa.nmat = 8; sa.in_bstride = (long)r * D; sa.sp = L.a_sp; sa.sp_bstride = 2L * r * D;
         FTMI_TRY(lora_split(sa, st));
         LoraSplitArgs sb;
-        sb.w = w.lora_b; sb.rows = D; sb.cols = r; sb.nmat = 8; sb.in_bstride = (long)D * r; sb.ext = L.b_ext; sb.ext_bstride = 3L * D * r; sb.ld_ext = 3 * r;
+        sb.w = w.base.lora_b; sb.rows = D; sb.cols = r; sb.nmat = 8; sb.in_bstride = (long)D * r; sb.ext = L.b_ext; sb.ext_bstride = 3L * D * r; sb.ld_ext = 3 * r;
         FTMI_TRY(lora_split(sb, st));
         k.lo.sp = L.a_sp; k.lo.ext = L.b_ext; k.lo.ext_step = 3L * r * D; k.lo.ld_ext = 3L * r;
     }
-    if (ffn.a1) {
-        const int F = c.F;
-        FTMI_TRY(split_one(ffn.a1, r, D, L.f_a1_sp, nullptr, nullptr, nullptr, st));
-        FTMI_TRY(split_one(ffn.b1, F, r, nullptr, L.f_b1_ext, nullptr, nullptr, st));
-        FTMI_TRY(split_one(ffn.a2, r, F, L.f_a2_sp, nullptr, nullptr, nullptr, st));
-        FTMI_TRY(split_one(ffn.b2, D, r, nullptr, L.f_b2_ext, nullptr, nullptr, st));
+    if (c.ffn) {
+        FTMI_TRY(split_one(w.ffn_a1, r, D, L.f_a1_sp, nullptr, nullptr, nullptr, st));
+        FTMI_TRY(split_one(w.ffn_b1, F, r, nullptr, L.f_b1_ext, nullptr, nullptr, st));
+        FTMI_TRY(split_one(w.ffn_a2, r, F, L.f_a2_sp, nullptr, nullptr, nullptr, st));
+        FTMI_TRY(split_one(w.ffn_b2, D, r, nullptr, L.f_b2_ext, nullptr, nullptr, st));
         k.f1 = ffn_adp(c, L.f_a1_sp, L.f_b1_ext, L.xa_f1, nullptr, nullptr);
         k.f2 = ffn_adp(c, L.f_a2_sp, L.f_b2_ext, L.xa_f2, nullptr, nullptr);
     }
     return block_forward(k, out);
 }
 
-// grad_a fp32 [8, r, D] / grad_b fp32 [8, D, r] ADDED to.
-int lora_backward(const ftmi_wan_lora_block_config& c, const ftmi_wan_lora_block_weights& w, const ImgCtx& img, const bf16_t* x, const bf16_t* enc, const float* mod,
-                  const float* rope_cos, const float* rope_sin, const bf16_t* dout, bf16_t* dx, bf16_t* denc, float* grad_a, float* grad_b, void* saved,
-                  size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st, const FfnLora& ffn = FfnLora()) {
-    const Bufs L = make_layout(base_cfg(c), c.r, true, saved, scratch, img.TI, ffn.a1 != nullptr);
-    if (saved_bytes < L.saved_total || scratch_bytes < L.scratch_total) return set_error(FTMI_ERR_INVALID, "wan_lora_block_backward: buffer too small");
-    if (c.r > 0 && (!w.lora_a || !w.lora_b || !grad_a || !grad_b)) return set_error(FTMI_ERR_INVALID, "wan_lora_block_backward: LoRA rank without adapters / gradient buffers");
-    if (!w.w_qkv1_t || !w.w_o1_t || !w.w_q2_t || !w.w_kv2_t || !w.w_o2_t || !w.w_f1_t || !w.w_f2_t)
-        return set_error(FTMI_ERR_INVALID, "wan_lora_block_backward: transposed weights missing");
-    Block k = make_block(base_cfg(c), w.params, L, x, enc, mod, rope_cos, rope_sin, st);
-    auto WT = [](const void* p) { return reinterpret_cast<const bf16_t*>(p); };
-    k.t.qkv1 = WT(w.w_qkv1_t); k.t.o1 = WT(w.w_o1_t); k.t.q2 = WT(w.w_q2_t); k.t.kv2 = WT(w.w_kv2_t); k.t.o2 = WT(w.w_o2_t); k.t.f1 = WT(w.w_f1_t); k.t.f2 = WT(w.w_f2_t);
-    k.grad_a = grad_a; k.grad_b = grad_b;
-    k.img = img;
-    const int D = c.D, r = c.r;
-    k.lo.r = r; k.lo.s = c.lora_scale;
-    if (r > 0) {
-        LoraSplitArgs sb;  // B^T as (hi, lo) row planes: operand of dXA = s * dY B
-        sb.w = w.lora_b; sb.rows = D; sb.cols = r; sb.nmat = 8; sb.in_bstride = (long)D * r; sb.t_sp = L.bt_sp; sb.t_sp_bstride = 2L * r * D;
-        FTMI_TRY(lora_split(sb, st));
-        LoraSplitArgs sa;  // A^T as K-extension columns, the eight adapters side by side [D, 24r]: dx += dXA A, fused projections take adjacent column groups
-        sa.w = w.lora_a; sa.rows = r; sa.cols = D; sa.nmat = 8; sa.in_bstride = (long)r * D; sa.t_ext = L.at_ext; sa.t_ext_bstride = 3L * r; sa.ld_t_ext = 24L * r;
-        FTMI_TRY(lora_split(sa, st));
-        k.lo.sp = L.bt_sp; k.lo.ext = L.at_ext; k.lo.ext_step = 3L * r; k.lo.ld_ext = 24L * r;
-    }
-    if (ffn.a1) {  // B^T as (hi, lo) row planes, A^T as K-extension columns, per adapter
-        const int F = c.F;
-        FTMI_TRY(split_one(ffn.b1, F, r, nullptr, nullptr, L.f_b1t_sp, nullptr, st));
-        FTMI_TRY(split_one(ffn.a1, r, D, nullptr, nullptr, nullptr, L.f_a1t_ext, st));
-        FTMI_TRY(split_one(ffn.b2, D, r, nullptr, nullptr, L.f_b2t_sp, nullptr, st));
-        FTMI_TRY(split_one(ffn.a2, r, F, nullptr, nullptr, nullptr, L.f_a2t_ext, st));
-        k.f1 = ffn_adp(c, L.f_b1t_sp, L.f_a1t_ext, L.xa_f1, ffn.ga1, ffn.gb1);
-        k.f2 = ffn_adp(c, L.f_b2t_sp, L.f_a2t_ext, L.xa_f2, ffn.ga2, ffn.gb2);
-    }
-    return block_backward(k, dout, dx, denc);
-}
-
-ImgCtx img_ctx(const ftmi_wan_i2v_lora_block_config& c, const bf16_t* img_params, const bf16_t* enc_img) {
-    ImgCtx g;
-    g.TI = c.TI; g.params = img_params; g.enc = enc_img;
-    return g;
-}
-
-}  // namespace
-
-int wan_lora_block_forward(const ftmi_wan_lora_block_config& c, const ftmi_wan_lora_block_weights& w, const bf16_t* x, const bf16_t* enc, const float* mod,
-                           const float* rope_cos, const float* rope_sin, bf16_t* out, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
-                           hipStream_t st) {
-    FTMI_TRY(check_lora_cfg(c));
-    return lora_forward(c, w, ImgCtx(), x, enc, mod, rope_cos, rope_sin, out, saved, saved_bytes, scratch, scratch_bytes, st);
-}
-int wan_lora_block_backward(const ftmi_wan_lora_block_config& c, const ftmi_wan_lora_block_weights& w, const bf16_t* x, const bf16_t* enc, const float* mod,
-                            const float* rope_cos, const float* rope_sin, const bf16_t* dout, bf16_t* dx, bf16_t* denc, float* grad_a, float* grad_b, void* saved,
-                            size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st) {
-    FTMI_TRY(check_lora_cfg(c));
-    return lora_backward(c, w, ImgCtx(), x, enc, mod, rope_cos, rope_sin, dout, dx, denc, grad_a, grad_b, saved, saved_bytes, scratch, scratch_bytes, st);
-}
-
-// (0 for a configuration the block refuses: the message is in ftmi_last_error)
-size_t wan_i2v_lora_block_saved_bytes(const ftmi_wan_i2v_lora_block_config& c) {
-    return check_i2v_cfg(c) ? 0 : make_layout(base_cfg(lora_cfg(c)), c.r, true, nullptr, nullptr, c.TI).saved_total;
-}
-size_t wan_i2v_lora_block_scratch_bytes(const ftmi_wan_i2v_lora_block_config& c) {
-    return check_i2v_cfg(c) ? 0 : make_layout(base_cfg(lora_cfg(c)), c.r, true, nullptr, nullptr, c.TI).scratch_total;
-}
-int wan_i2v_lora_block_forward(const ftmi_wan_i2v_lora_block_config& c, const ftmi_wan_lora_block_weights& w, const bf16_t* img_params, const bf16_t* x,
-                               const bf16_t* enc, const bf16_t* enc_img, const float* mod, const float* rope_cos, const float* rope_sin, bf16_t* out, void* saved,
-                               size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st) {
-    FTMI_TRY(check_i2v_cfg(c));
-    if (c.TI > 0 && (!img_params || !enc_img)) return set_error(FTMI_ERR_INVALID, "wan_i2v_lora_block_forward: image tokens without their parameters");
-    return lora_forward(lora_cfg(c), w, img_ctx(c, img_params, enc_img), x, enc, mod, rope_cos, rope_sin, out, saved, saved_bytes, scratch, scratch_bytes, st);
-}
-int wan_i2v_lora_block_backward(const ftmi_wan_i2v_lora_block_config& c, const ftmi_wan_lora_block_weights& w, const bf16_t* img_params, const bf16_t* x,
-                                const bf16_t* enc, const bf16_t* enc_img, const float* mod, const float* rope_cos, const float* rope_sin, const bf16_t* dout,
-                                bf16_t* dx, bf16_t* denc, float* grad_a, float* grad_b, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
-                                hipStream_t st) {
-    FTMI_TRY(check_i2v_cfg(c));
-    if (c.TI > 0 && (!img_params || !enc_img)) return set_error(FTMI_ERR_INVALID, "wan_i2v_lora_block_backward: image tokens without their parameters");
-    return lora_backward(lora_cfg(c), w, img_ctx(c, img_params, enc_img), x, enc, mod, rope_cos, rope_sin, dout, dx, denc, grad_a, grad_b, saved, saved_bytes, scratch,
-                         scratch_bytes, st);
-}
-
-// the LoRA block with the image context (cfg.TI, 0: none) and, cfg.ffn = 1, adapters on the two feed-forward projections as well
-size_t wan_lora_ffn_block_saved_bytes(const ftmi_wan_lora_ffn_block_config& c) {
-    return check_ffn_cfg(c) ? 0 : make_layout(base_cfg(lora_cfg(i2v_cfg(c))), c.r, true, nullptr, nullptr, c.TI, c.ffn != 0).saved_total;
-}
-size_t wan_lora_ffn_block_scratch_bytes(const ftmi_wan_lora_ffn_block_config& c) {
-    return check_ffn_cfg(c) ? 0 : make_layout(base_cfg(lora_cfg(i2v_cfg(c))), c.r, true, nullptr, nullptr, c.TI, c.ffn != 0).scratch_total;
-}
-int wan_lora_ffn_block_forward(const ftmi_wan_lora_ffn_block_config& c, const ftmi_wan_lora_ffn_block_weights& w, const bf16_t* img_params, const bf16_t* x,
-                               const bf16_t* enc, const bf16_t* enc_img, const float* mod, const float* rope_cos, const float* rope_sin, bf16_t* out, void* saved,
-                               size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st) {
-    FTMI_TRY(check_ffn_cfg(c));
-    if (c.TI > 0 && (!img_params || !enc_img)) return set_error(FTMI_ERR_INVALID, "wan_lora_ffn_block_forward: image tokens without their parameters");
-    FfnLora f;
-    if (c.ffn) {
-        if (!w.ffn_a1 || !w.ffn_b1 || !w.ffn_a2 || !w.ffn_b2) return set_error(FTMI_ERR_INVALID, "wan_lora_ffn_block_forward: feed-forward adapters missing");
-        f.a1 = w.ffn_a1; f.b1 = w.ffn_b1; f.a2 = w.ffn_a2; f.b2 = w.ffn_b2;
-    }
-    const ftmi_wan_i2v_lora_block_config ci = i2v_cfg(c);
-    return lora_forward(lora_cfg(ci), w.base, img_ctx(ci, img_params, enc_img), x, enc, mod, rope_cos, rope_sin, out, saved, saved_bytes, scratch, scratch_bytes, st, f);
-}
+// grad_a fp32 [8, r, D] / grad_b fp32 [8, D, r] and the feed-forward adapters' grad_ffn_a1 [r, D], grad_ffn_b1 [F, r], grad_ffn_a2 [r, F], grad_ffn_b2 [D, r] ADDED to.
 int wan_lora_ffn_block_backward(const ftmi_wan_lora_ffn_block_config& c, const ftmi_wan_lora_ffn_block_weights& w, const bf16_t* img_params, const bf16_t* x,
                                 const bf16_t* enc, const bf16_t* enc_img, const float* mod, const float* rope_cos, const float* rope_sin, const bf16_t* dout,
                                 bf16_t* dx, bf16_t* denc, float* grad_a, float* grad_b, float* grad_ffn_a1, float* grad_ffn_b1, float* grad_ffn_a2,
                                 float* grad_ffn_b2, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, hipStream_t st) {
-    FTMI_TRY(check_ffn_cfg(c));
+    FTMI_TRY(check_lora_cfg(c));
     if (c.TI > 0 && (!img_params || !enc_img)) return set_error(FTMI_ERR_INVALID, "wan_lora_ffn_block_backward: image tokens without their parameters");
-    FfnLora f;
-    if (c.ffn) {
-        if (!w.ffn_a1 || !w.ffn_b1 || !w.ffn_a2 || !w.ffn_b2 || !grad_ffn_a1 || !grad_ffn_b1 || !grad_ffn_a2 || !grad_ffn_b2)
-            return set_error(FTMI_ERR_INVALID, "wan_lora_ffn_block_backward: feed-forward adapters / gradient buffers missing");
-        f.a1 = w.ffn_a1; f.b1 = w.ffn_b1; f.a2 = w.ffn_a2; f.b2 = w.ffn_b2;
-        f.ga1 = grad_ffn_a1; f.gb1 = grad_ffn_b1; f.ga2 = grad_ffn_a2; f.gb2 = grad_ffn_b2;
+    if (c.ffn && (!w.ffn_a1 || !w.ffn_b1 || !w.ffn_a2 || !w.ffn_b2 || !grad_ffn_a1 || !grad_ffn_b1 || !grad_ffn_a2 || !grad_ffn_b2))
+        return set_error(FTMI_ERR_INVALID, "wan_lora_ffn_block_backward: feed-forward adapters / gradient buffers missing");
+    const ftmi_wan_lora_block_weights& wb = w.base;
+    const Bufs L = lora_layout(c, saved, scratch);
+    if (saved_bytes < L.saved_total || scratch_bytes < L.scratch_total) return set_error(FTMI_ERR_INVALID, "wan_lora_ffn_block_backward: buffer too small");
+    if (c.r > 0 && (!wb.lora_a || !wb.lora_b || !grad_a || !grad_b))
+        return set_error(FTMI_ERR_INVALID, "wan_lora_ffn_block_backward: LoRA rank without adapters / gradient buffers");
+    if (!wb.w_qkv1_t || !wb.w_o1_t || !wb.w_q2_t || !wb.w_kv2_t || !wb.w_o2_t || !wb.w_f1_t || !wb.w_f2_t)
+        return set_error(FTMI_ERR_INVALID, "wan_lora_ffn_block_backward: transposed weights missing");
+    Block k = lora_block(c, w, L, img_params, x, enc, enc_img, mod, rope_cos, rope_sin, st);
+    auto WT = [](const void* p) { return reinterpret_cast<const bf16_t*>(p); };
+    k.t.qkv1 = WT(wb.w_qkv1_t); k.t.o1 = WT(wb.w_o1_t); k.t.q2 = WT(wb.w_q2_t); k.t.kv2 = WT(wb.w_kv2_t); k.t.o2 = WT(wb.w_o2_t); k.t.f1 = WT(wb.w_f1_t); k.t.f2 = WT(wb.w_f2_t);
+    k.grad_a = grad_a; k.grad_b = grad_b;
+    const int D = c.D, F = c.F, r = c.r;
+    if (r > 0) {
+        LoraSplitArgs sb;  // B^T as (hi, lo) row planes: operand of dXA = s * dY B
+        sb.w = wb.lora_b; sb.rows = D; sb.cols = r; sb.nmat = 8; sb.in_bstride = (long)D * r; sb.t_sp = L.bt_sp; sb.t_sp_bstride = 2L * r * D;
+        FTMI_TRY(lora_split(sb, st));
+        LoraSplitArgs sa;  // A^T as K-extension columns, the eight adapters side by side [D, 24r]: dx += dXA A, fused projections take adjacent column groups
+        sa.w = wb.lora_a; sa.rows = r; sa.cols = D; sa.nmat = 8; sa.in_bstride = (long)r * D; sa.t_ext = L.at_ext; sa.t_ext_bstride = 3L * r; sa.ld_t_ext = 24L * r;
+        FTMI_TRY(lora_split(sa, st));
+        k.lo.sp = L.bt_sp; k.lo.ext = L.at_ext; k.lo.ext_step = 3L * r; k.lo.ld_ext = 24L * r;
     }
-    const ftmi_wan_i2v_lora_block_config ci = i2v_cfg(c);
-    return lora_backward(lora_cfg(ci), w.base, img_ctx(ci, img_params, enc_img), x, enc, mod, rope_cos, rope_sin, dout, dx, denc, grad_a, grad_b, saved, saved_bytes,
-                         scratch, scratch_bytes, st, f);
+    if (c.ffn) {  // B^T as (hi, lo) row planes, A^T as K-extension columns, per adapter
+        FTMI_TRY(split_one(w.ffn_b1, F, r, nullptr, nullptr, L.f_b1t_sp, nullptr, st));
+        FTMI_TRY(split_one(w.ffn_a1, r, D, nullptr, nullptr, nullptr, L.f_a1t_ext, st));
+        FTMI_TRY(split_one(w.ffn_b2, D, r, nullptr, nullptr, L.f_b2t_sp, nullptr, st));
+        FTMI_TRY(split_one(w.ffn_a2, r, F, nullptr, nullptr, nullptr, L.f_a2t_ext, st));
+        k.f1 = ffn_adp(c, L.f_b1t_sp, L.f_a1t_ext, L.xa_f1, grad_ffn_a1, grad_ffn_b1);
+        k.f2 = ffn_adp(c, L.f_b2t_sp, L.f_a2t_ext, L.xa_f2, grad_ffn_a2, grad_ffn_b2);
+    }
+    return block_backward(k, dout, dx, denc);
 }
 
 }  // namespace ftmi

@@ -22,8 +22,7 @@ import ctypes
 import os
 
 from .. import _lib, ops
-from .._lib import (WanBlockConfig, WanI2VLoraBlockConfig, WanLoraBlockConfig, WanLoraBlockWeights, WanLoraFfnBlockConfig, WanLoraFfnBlockWeights, check, ptr,
-                     stream_ptr)
+from .._lib import WanBlockConfig, WanLoraFfnBlockConfig, WanLoraFfnBlockWeights, check, ptr, stream_ptr
 
 bf16 = torch.bfloat16
 _NATIVE_SCRATCH: Dict[int, torch.Tensor] = {}  # device index -> byte buffer shared by every natively run block on that device (one stream at a time)
@@ -432,92 +431,51 @@ def _grad_targets(blk: "MI355XWanBlock", lora_a, lora_b, ffn=None):
 
 
 class _WanLoRABlockFunction(torch.autograd.Function):
-    """The block over a FROZEN base with the adapters on the eight attention projections, through the Python walks.  The backward forms dx, denc (only if
-    asked for) and the 16 adapter gradients -- no base-weight gradient, no bias / norm / modulation reduction, and it keeps neither a1, n3, act nor f."""
+    """The block over a FROZEN base through the Python walks, text-to-video and image-to-video.  ``lora_a`` [8, r, D] / ``lora_b`` [8, D, r]: the adapters on
+    the eight attention projections; ``enc_img`` [B, TI, D]: the image context of an image-to-video block in attn2 (frozen: no gradient flows into it);
+    ``fa1`` [r, D], ``fb1`` [F, r], ``fa2`` [r, F], ``fb2`` [D, r]: the adapters on ffn.net.0.proj and ffn.net.2 -- each None where the block has none.  The
+    backward forms dx, denc (only if asked for) and the adapter gradients -- no base-weight gradient, no bias / norm / modulation reduction, and it keeps
+    neither a1 nor f (n3 and act only for the feed-forward adapters)."""
 
     @staticmethod
-    def forward(ctx, blk: "MI355XWanBlock", x, enc, temb, rope_cos, rope_sin, lora_a, lora_b):
-        return _WanLoRABlockFunction._fwd(ctx, blk, x, enc, None, temb, rope_cos, rope_sin, lora_a, lora_b)
-
-    @staticmethod
-    def backward(ctx, dout):
-        dx, denc, ga, gb, _ = _WanLoRABlockFunction._bwd(ctx, dout)
-        return None, dx, denc, None, None, None, ga, gb
-
-    @staticmethod
-    def _fwd(ctx, blk, x, enc, enc_img, temb, rope_cos, rope_sin, lora_a, lora_b, ffn=None):
+    def forward(ctx, blk: "MI355XWanBlock", x, enc, temb, rope_cos, rope_sin, lora_a, lora_b, enc_img, fa1, fb1, fa2, fb2):
+        ffn = None if fa1 is None else (fa1, fb1, fa2, fb2)
         mod = (blk.param("scale_shift_table").float() + temb.float()).contiguous()
         out, acts = _block_forward(blk, x, enc, mod, (rope_cos, rope_sin), _Lora(lora_a, lora_b, f=ffn), enc_img=enc_img)
-        ctx.blk, ctx.rope, ctx.has_lora, ctx.has_img, ctx.has_ffn = blk, (rope_cos, rope_sin), lora_a is not None, enc_img is not None, ffn is not None
-        ctx.recompute = bool(blk.gradient_checkpointing)
-        la, lb = (lora_a, lora_b) if lora_a is not None else (x.new_empty(0), x.new_empty(0))
-        ctx.save_for_backward(x, enc, mod, la, lb, enc_img if enc_img is not None else x.new_empty(0), *(ffn or ()))
+        ctx.blk, ctx.rope, ctx.recompute = blk, (rope_cos, rope_sin), bool(blk.gradient_checkpointing)
+        ctx.save_for_backward(x, enc, mod, lora_a, lora_b, enc_img, fa1, fb1, fa2, fb2)
         ctx.acts = None if ctx.recompute else acts.for_frozen_base()
         return out
 
     @staticmethod
-    def _bwd(ctx, dout):
-        """Returns (dx, denc, ga, gb, gf): gf = the feed-forward adapters' four gradients (None when the step object owns them, or without such adapters)."""
+    def backward(ctx, dout):
         blk, rope = ctx.blk, ctx.rope
         x, enc, mod, lora_a, lora_b, enc_img = ctx.saved_tensors[:6]
-        ffn = tuple(ctx.saved_tensors[6:10]) if ctx.has_ffn else None
-        if not ctx.has_lora:
-            lora_a = lora_b = None
-        if not ctx.has_img:
-            enc_img = None
+        ffn = None if ctx.saved_tensors[6] is None else tuple(ctx.saved_tensors[6:10])
         acts, ctx.acts = ctx.acts, None
         if ctx.recompute:
             acts = _block_forward(blk, x, enc, mod, rope, _Lora(lora_a, lora_b, f=ffn), need_out=False, enc_img=enc_img)[1].for_frozen_base()
         own, ga, gb, gf = _grad_targets(blk, lora_a, lora_b, ffn)
         dx, denc, _ = _block_backward(blk, acts, x, enc, mod, rope, dout, _Lora(lora_a, lora_b, ga, gb, ffn, gf), train_base=False, need_denc=ctx.needs_input_grad[2])
-        if own:
+        if own:  # the step object owns the gradients: nothing goes back through autograd
             blk._backward_done()
             ga = gb = gf = None
-        return dx, denc, ga, gb, gf
-
-
-class _WanI2VLoRABlockFunction(torch.autograd.Function):
-    """``_WanLoRABlockFunction`` with the image context ``enc_img`` [B, TI, D] in attn2 (frozen: no gradient flows into it)."""
-
-    @staticmethod
-    def forward(ctx, blk: "MI355XWanBlock", x, enc, temb, rope_cos, rope_sin, lora_a, lora_b, enc_img):
-        return _WanLoRABlockFunction._fwd(ctx, blk, x, enc, enc_img, temb, rope_cos, rope_sin, lora_a, lora_b)
-
-    @staticmethod
-    def backward(ctx, dout):
-        dx, denc, ga, gb, _ = _WanLoRABlockFunction._bwd(ctx, dout)
-        return None, dx, denc, None, None, None, ga, gb, None
-
-
-class _WanFfnLoRABlockFunction(torch.autograd.Function):
-    """``_WanLoRABlockFunction`` with adapters on ffn.net.0.proj and ffn.net.2 as well (``fa1`` [r, D], ``fb1`` [F, r], ``fa2`` [r, F], ``fb2`` [D, r]);
-    ``enc_img``: the image context of an image-to-video block, or None."""
-
-    @staticmethod
-    def forward(ctx, blk: "MI355XWanBlock", x, enc, temb, rope_cos, rope_sin, lora_a, lora_b, enc_img, fa1, fb1, fa2, fb2):
-        return _WanLoRABlockFunction._fwd(ctx, blk, x, enc, enc_img, temb, rope_cos, rope_sin, lora_a, lora_b, (fa1, fb1, fa2, fb2))
-
-    @staticmethod
-    def backward(ctx, dout):
-        dx, denc, ga, gb, gf = _WanLoRABlockFunction._bwd(ctx, dout)
         return (None, dx, denc, None, None, None, ga, gb, None) + (gf or (None,) * 4)
 
 
 class _WanLoRABlockNativeFunction(torch.autograd.Function):
-    """``_WanLoRABlockFunction`` with ONE C call per direction (``ftmi_wan_lora_block_forward / _backward``, csrc/wan_dit.hip).  The K-contiguous twins of
-    the weights come from ``blk.transposed()``: cached, and the frozen base never invalidates them.  Gradient checkpointing keeps the block's input only and
-    refills ``saved`` inside the backward (the forward call with ``out = NULL``)."""
+    """``_WanLoRABlockFunction`` with ONE C call per direction (``ftmi_wan_lora_ffn_block_forward / _backward``, csrc/wan_dit.hip: the one entry for every
+    LoRA configuration -- ``enc_img`` None: TI = 0, ``fa1`` None: ffn = 0).  The K-contiguous twins of the weights come from ``blk.transposed()``: cached, and
+    the frozen base never invalidates them.  Gradient checkpointing keeps the block's input only and refills ``saved`` inside the backward (the forward call
+    with ``out = NULL``)."""
 
     @staticmethod
-    def _args(blk: "MI355XWanBlock", B: int, S: int, T: int, lora_a, lora_b, backward: bool, TI: Optional[int] = None, ffn=None, ffn_entry: bool = False):
-        kw = dict(B=B, S=S, T=T, D=blk.dim, H=blk.heads, F=blk.ffn_dim, eps=float(blk.eps), gemm_variant=8, r=0 if lora_a is None else int(lora_a.shape[1]),
-                  lora_scale=float(blk.lora_scale))
-        if ffn_entry:  # the ftmi_wan_lora_ffn_block_* entries: image context or not, feed-forward adapters or not
-            cfg, wf = WanLoraFfnBlockConfig(TI=TI or 0, ffn=int(ffn is not None), **kw), WanLoraFfnBlockWeights()
-            w = wf.base
-        else:
-            cfg = WanLoraBlockConfig(**kw) if TI is None else WanI2VLoraBlockConfig(TI=TI, **kw)  # TI given: the ftmi_wan_i2v_lora_block_* entries
-            w = wf = WanLoraBlockWeights()
+    def _args(blk: "MI355XWanBlock", B: int, S: int, T: int, lora_a, lora_b, backward: bool, TI: int = 0, ffn=None):
+        """(config, weights, the tensors whose pointers the weights hold: keep them alive over the call)."""
+        cfg = WanLoraFfnBlockConfig(B=B, S=S, T=T, D=blk.dim, H=blk.heads, F=blk.ffn_dim, eps=float(blk.eps), gemm_variant=8,
+                                    r=0 if lora_a is None else int(lora_a.shape[1]), lora_scale=float(blk.lora_scale), TI=TI, ffn=int(ffn is not None))
+        wf = WanLoraFfnBlockWeights()
+        w = wf.base
         params = blk._params()
         if params.numel() != blk.layout.total or not params.is_contiguous():
             raise RuntimeError("Wan block: the flat parameter buffer does not have the layout the C orchestrator expects")
@@ -542,125 +500,52 @@ class _WanLoRABlockNativeFunction(torch.autograd.Function):
     def _forward_call(blk, x, enc, mod, rope_cos, rope_sin, lora_a, lora_b, out, enc_img=None, ffn=None):
         B, S, _ = x.shape
         lib = _lib.load()
-        if ffn is not None or blk.ffn_entry:
-            TI = 0 if enc_img is None else enc_img.shape[1]
-            cfg, w, keep = _WanLoRABlockNativeFunction._args(blk, B, S, enc.shape[1], lora_a, lora_b, backward=False, TI=TI, ffn=ffn, ffn_entry=True)
-            saved = torch.empty(_planned(lib.ftmi_wan_lora_ffn_block_saved_bytes(ctypes.byref(cfg))), dtype=torch.uint8, device=x.device)
-            scratch = _native_scratch(x.device, _planned(lib.ftmi_wan_lora_ffn_block_scratch_bytes(ctypes.byref(cfg))))
-            img = blk._img_params() if TI > 0 else None
-            check(lib.ftmi_wan_lora_ffn_block_forward(ctypes.byref(cfg), ctypes.byref(w), ptr(img), ptr(x), ptr(enc), ptr(enc_img if TI > 0 else None), ptr(mod),
-                                                      ptr(rope_cos), ptr(rope_sin), ptr(out), ptr(saved), saved.numel(), ptr(scratch), scratch.numel(), stream_ptr()),
-                  "ftmi_wan_lora_ffn_block_forward")
-            return saved
-        if enc_img is not None:
-            cfg, w, keep = _WanLoRABlockNativeFunction._args(blk, B, S, enc.shape[1], lora_a, lora_b, backward=False, TI=enc_img.shape[1])
-            saved = torch.empty(lib.ftmi_wan_i2v_lora_block_saved_bytes(ctypes.byref(cfg)), dtype=torch.uint8, device=x.device)
-            scratch = _native_scratch(x.device, lib.ftmi_wan_i2v_lora_block_scratch_bytes(ctypes.byref(cfg)))
-            img = blk._img_params() if cfg.TI > 0 else None
-            check(lib.ftmi_wan_i2v_lora_block_forward(ctypes.byref(cfg), ctypes.byref(w), ptr(img), ptr(x), ptr(enc), ptr(enc_img if cfg.TI > 0 else None), ptr(mod),
-                                                      ptr(rope_cos), ptr(rope_sin), ptr(out), ptr(saved), saved.numel(), ptr(scratch), scratch.numel(), stream_ptr()),
-                  "ftmi_wan_i2v_lora_block_forward")
-            return saved
-        cfg, w, keep = _WanLoRABlockNativeFunction._args(blk, B, S, enc.shape[1], lora_a, lora_b, backward=False)
-        saved = torch.empty(lib.ftmi_wan_lora_block_saved_bytes(ctypes.byref(cfg)), dtype=torch.uint8, device=x.device)
-        scratch = _native_scratch(x.device, lib.ftmi_wan_lora_block_scratch_bytes(ctypes.byref(cfg)))
-        check(lib.ftmi_wan_lora_block_forward(ctypes.byref(cfg), ctypes.byref(w), ptr(x), ptr(enc), ptr(mod), ptr(rope_cos), ptr(rope_sin), ptr(out), ptr(saved),
-                                              saved.numel(), ptr(scratch), scratch.numel(), stream_ptr()), "ftmi_wan_lora_block_forward")
+        TI = 0 if enc_img is None else enc_img.shape[1]
+        cfg, w, keep = _WanLoRABlockNativeFunction._args(blk, B, S, enc.shape[1], lora_a, lora_b, backward=False, TI=TI, ffn=ffn)
+        saved = torch.empty(_planned(lib.ftmi_wan_lora_ffn_block_saved_bytes(ctypes.byref(cfg))), dtype=torch.uint8, device=x.device)
+        scratch = _native_scratch(x.device, _planned(lib.ftmi_wan_lora_ffn_block_scratch_bytes(ctypes.byref(cfg))))
+        img = blk._img_params() if TI > 0 else None
+        check(lib.ftmi_wan_lora_ffn_block_forward(ctypes.byref(cfg), ctypes.byref(w), ptr(img), ptr(x), ptr(enc), ptr(enc_img if TI > 0 else None), ptr(mod),
+                                                  ptr(rope_cos), ptr(rope_sin), ptr(out), ptr(saved), saved.numel(), ptr(scratch), scratch.numel(), stream_ptr()),
+              "ftmi_wan_lora_ffn_block_forward")
         return saved
 
     @staticmethod
-    def forward(ctx, blk: "MI355XWanBlock", x, enc, temb, rope_cos, rope_sin, lora_a, lora_b):
-        return _WanLoRABlockNativeFunction._fwd(ctx, blk, x, enc, None, temb, rope_cos, rope_sin, lora_a, lora_b)
-
-    @staticmethod
-    def backward(ctx, dout):
-        dx, denc, ga, gb, _ = _WanLoRABlockNativeFunction._bwd(ctx, dout)
-        return None, dx, denc, None, None, None, ga, gb
-
-    @staticmethod
-    def _fwd(ctx, blk, x, enc, enc_img, temb, rope_cos, rope_sin, lora_a, lora_b, ffn=None):
+    def forward(ctx, blk: "MI355XWanBlock", x, enc, temb, rope_cos, rope_sin, lora_a, lora_b, enc_img, fa1, fb1, fa2, fb2):
+        ffn = None if fa1 is None else (fa1, fb1, fa2, fb2)
         mod = (blk.param("scale_shift_table").float() + temb.float()).contiguous()
         out = torch.empty_like(x)
         saved = _WanLoRABlockNativeFunction._forward_call(blk, x, enc, mod, rope_cos, rope_sin, lora_a, lora_b, out, enc_img, ffn)
-        ctx.blk, ctx.rope, ctx.has_lora, ctx.has_img, ctx.has_ffn = blk, (rope_cos, rope_sin), lora_a is not None, enc_img is not None, ffn is not None
-        ctx.recompute = bool(blk.gradient_checkpointing)
-        la, lb = (lora_a, lora_b) if lora_a is not None else (x.new_empty(0), x.new_empty(0))
-        keep = (x, enc, mod, la, lb, enc_img if enc_img is not None else x.new_empty(0)) + tuple(ffn or ())
-        ctx.save_for_backward(*(keep if ctx.recompute else keep + (saved,)))
+        ctx.blk, ctx.rope, ctx.recompute = blk, (rope_cos, rope_sin), bool(blk.gradient_checkpointing)
+        ctx.save_for_backward(x, enc, mod, lora_a, lora_b, enc_img, fa1, fb1, fa2, fb2, None if ctx.recompute else saved)
         return out
 
     @staticmethod
-    def _bwd(ctx, dout):
-        """Returns (dx, denc, ga, gb, gf) like ``_WanLoRABlockFunction._bwd``."""
+    def backward(ctx, dout):
         blk, rope = ctx.blk, ctx.rope
         x, enc, mod, lora_a, lora_b, enc_img = ctx.saved_tensors[:6]
-        ffn = tuple(ctx.saved_tensors[6:10]) if ctx.has_ffn else None
-        if not ctx.has_lora:
-            lora_a = lora_b = None
-        if not ctx.has_img:
-            enc_img = None
+        ffn = None if ctx.saved_tensors[6] is None else tuple(ctx.saved_tensors[6:10])
+        saved = ctx.saved_tensors[10]
         if ctx.recompute:
             saved = _WanLoRABlockNativeFunction._forward_call(blk, x, enc, mod, rope[0], rope[1], lora_a, lora_b, None, enc_img, ffn)
-        else:
-            saved = ctx.saved_tensors[-1]
         B, S, _ = x.shape
+        TI = 0 if enc_img is None else enc_img.shape[1]
         dout = dout.contiguous()
         own, ga, gb, gf = _grad_targets(blk, lora_a, lora_b, ffn)
         lib = _lib.load()
         dx = torch.empty_like(x)
         denc = torch.empty_like(enc) if ctx.needs_input_grad[2] else None  # frozen text embedder: no gradient into the text rows, its GEMM is skipped
-        if ffn is not None or blk.ffn_entry:
-            TI = 0 if enc_img is None else enc_img.shape[1]
-            cfg, w, keep = _WanLoRABlockNativeFunction._args(blk, B, S, enc.shape[1], lora_a, lora_b, backward=True, TI=TI, ffn=ffn, ffn_entry=True)
-            scratch = _native_scratch(x.device, _planned(lib.ftmi_wan_lora_ffn_block_scratch_bytes(ctypes.byref(cfg))))
-            img = blk._img_params() if TI > 0 else None
-            g4 = gf or (None,) * 4
-            check(lib.ftmi_wan_lora_ffn_block_backward(ctypes.byref(cfg), ctypes.byref(w), ptr(img), ptr(x), ptr(enc), ptr(enc_img if TI > 0 else None), ptr(mod),
-                                                       ptr(rope[0]), ptr(rope[1]), ptr(dout), ptr(dx), ptr(denc), ptr(ga), ptr(gb), ptr(g4[0]), ptr(g4[1]),
-                                                       ptr(g4[2]), ptr(g4[3]), ptr(saved), saved.numel(), ptr(scratch), scratch.numel(), stream_ptr()),
-                  "ftmi_wan_lora_ffn_block_backward")
-        elif enc_img is not None:
-            cfg, w, keep = _WanLoRABlockNativeFunction._args(blk, B, S, enc.shape[1], lora_a, lora_b, backward=True, TI=enc_img.shape[1])
-            scratch = _native_scratch(x.device, lib.ftmi_wan_i2v_lora_block_scratch_bytes(ctypes.byref(cfg)))
-            img = blk._img_params() if cfg.TI > 0 else None
-            check(lib.ftmi_wan_i2v_lora_block_backward(ctypes.byref(cfg), ctypes.byref(w), ptr(img), ptr(x), ptr(enc), ptr(enc_img if cfg.TI > 0 else None), ptr(mod),
-                                                       ptr(rope[0]), ptr(rope[1]), ptr(dout), ptr(dx), ptr(denc), ptr(ga), ptr(gb), ptr(saved), saved.numel(),
-                                                       ptr(scratch), scratch.numel(), stream_ptr()), "ftmi_wan_i2v_lora_block_backward")
-        else:
-            cfg, w, keep = _WanLoRABlockNativeFunction._args(blk, B, S, enc.shape[1], lora_a, lora_b, backward=True)
-            scratch = _native_scratch(x.device, lib.ftmi_wan_lora_block_scratch_bytes(ctypes.byref(cfg)))
-            check(lib.ftmi_wan_lora_block_backward(ctypes.byref(cfg), ctypes.byref(w), ptr(x), ptr(enc), ptr(mod), ptr(rope[0]), ptr(rope[1]), ptr(dout), ptr(dx),
-                                                   ptr(denc), ptr(ga), ptr(gb), ptr(saved), saved.numel(), ptr(scratch), scratch.numel(), stream_ptr()),
-                  "ftmi_wan_lora_block_backward")
-        if own:
+        cfg, w, keep = _WanLoRABlockNativeFunction._args(blk, B, S, enc.shape[1], lora_a, lora_b, backward=True, TI=TI, ffn=ffn)
+        scratch = _native_scratch(x.device, _planned(lib.ftmi_wan_lora_ffn_block_scratch_bytes(ctypes.byref(cfg))))
+        img = blk._img_params() if TI > 0 else None
+        g4 = gf or (None,) * 4
+        check(lib.ftmi_wan_lora_ffn_block_backward(ctypes.byref(cfg), ctypes.byref(w), ptr(img), ptr(x), ptr(enc), ptr(enc_img if TI > 0 else None), ptr(mod),
+                                                   ptr(rope[0]), ptr(rope[1]), ptr(dout), ptr(dx), ptr(denc), ptr(ga), ptr(gb), ptr(g4[0]), ptr(g4[1]),
+                                                   ptr(g4[2]), ptr(g4[3]), ptr(saved), saved.numel(), ptr(scratch), scratch.numel(), stream_ptr()),
+              "ftmi_wan_lora_ffn_block_backward")
+        if own:  # the step object owns the gradients: nothing goes back through autograd
             blk._backward_done()
             ga = gb = gf = None
-        return dx, denc, ga, gb, gf
-
-
-class _WanI2VLoRABlockNativeFunction(torch.autograd.Function):
-    """``_WanLoRABlockNativeFunction`` with the image context: ``ftmi_wan_i2v_lora_block_forward / _backward``."""
-
-    @staticmethod
-    def forward(ctx, blk: "MI355XWanBlock", x, enc, temb, rope_cos, rope_sin, lora_a, lora_b, enc_img):
-        return _WanLoRABlockNativeFunction._fwd(ctx, blk, x, enc, enc_img, temb, rope_cos, rope_sin, lora_a, lora_b)
-
-    @staticmethod
-    def backward(ctx, dout):
-        dx, denc, ga, gb, _ = _WanLoRABlockNativeFunction._bwd(ctx, dout)
-        return None, dx, denc, None, None, None, ga, gb, None
-
-
-class _WanFfnLoRABlockNativeFunction(torch.autograd.Function):
-    """``_WanFfnLoRABlockFunction`` with ONE C call per direction: ``ftmi_wan_lora_ffn_block_forward / _backward`` (``enc_img`` None: TI = 0)."""
-
-    @staticmethod
-    def forward(ctx, blk: "MI355XWanBlock", x, enc, temb, rope_cos, rope_sin, lora_a, lora_b, enc_img, fa1, fb1, fa2, fb2):
-        return _WanLoRABlockNativeFunction._fwd(ctx, blk, x, enc, enc_img, temb, rope_cos, rope_sin, lora_a, lora_b, (fa1, fb1, fa2, fb2))
-
-    @staticmethod
-    def backward(ctx, dout):
-        dx, denc, ga, gb, gf = _WanLoRABlockNativeFunction._bwd(ctx, dout)
         return (None, dx, denc, None, None, None, ga, gb, None) + (gf or (None,) * 4)
 
 
@@ -670,9 +555,6 @@ class MI355XWanBlock(nn.Module):
 
     # one C call per direction (csrc/wan_dit.hip); False (or FTMI_NATIVE_BLOCKS=0 in the environment): the per-kernel composition from Python -- the tests compare the two
     native = os.environ.get("FTMI_NATIVE_BLOCKS", "1") != "0"
-    # True: a natively run LoRA block goes through ftmi_wan_lora_ffn_block_* also WITHOUT feed-forward adapters (with them it always does) -- the tests compare
-    # the entries bit for bit
-    ffn_entry = False
 
     def __init__(self, dim: int = 1536, heads: int = 12, ffn_dim: int = 8960, eps: float = 1e-6, device: Optional[torch.device] = None,
                  added_kv_proj_dim: Optional[int] = None):
@@ -844,17 +726,11 @@ class MI355XWanBlock(nn.Module):
             raise ValueError("Wan block: the image context goes with added_kv_proj_dim, and only with it")
         if self.img_layout is not None and not self.frozen:
             raise NotImplementedError("Wan image-to-video: full fine-tuning is not covered; attach adapters (add_adapter) or freeze the base (freeze_base)")
-        if self.lora_ffn is not None:
-            fn = _WanFfnLoRABlockNativeFunction if self.native else _WanFfnLoRABlockFunction
-            img = None if encoder_hidden_states_image is None else encoder_hidden_states_image.detach().contiguous()
-            return fn.apply(self, hidden_states.contiguous(), encoder_hidden_states.contiguous(), temb.contiguous(), rotary[0], rotary[1], self.lora_A, self.lora_B,
-                            img, *self.lora_ffn)
-        if self.img_layout is not None:
-            fn = _WanI2VLoRABlockNativeFunction if self.native else _WanI2VLoRABlockFunction
-            return fn.apply(self, hidden_states.contiguous(), encoder_hidden_states.contiguous(), temb.contiguous(), rotary[0], rotary[1], self.lora_A, self.lora_B,
-                            encoder_hidden_states_image.detach().contiguous())
-        if self.frozen:
+        if self.frozen:  # every LoRA configuration: adapters or none, image context or none, feed-forward adapters or none
             fn = _WanLoRABlockNativeFunction if self.native else _WanLoRABlockFunction
-            return fn.apply(self, hidden_states.contiguous(), encoder_hidden_states.contiguous(), temb.contiguous(), rotary[0], rotary[1], self.lora_A, self.lora_B)
+            img = None if encoder_hidden_states_image is None else encoder_hidden_states_image.detach().contiguous()
+            ffn = (None,) * 4 if self.lora_ffn is None else tuple(self.lora_ffn)
+            return fn.apply(self, hidden_states.contiguous(), encoder_hidden_states.contiguous(), temb.contiguous(), rotary[0], rotary[1], self.lora_A, self.lora_B,
+                            img, *ffn)
         fn = _WanBlockNativeFunction if self.native else _WanBlockFunction
         return fn.apply(self, hidden_states.contiguous(), encoder_hidden_states.contiguous(), temb.contiguous(), rotary[0], rotary[1])

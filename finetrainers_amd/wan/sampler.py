@@ -123,7 +123,7 @@ class MI355XWanLatentSampler:
         first = tr.blocks[0]
         for i, blk in enumerate(tr.blocks):
             ffn = tuple(blk.lora_ffn) if blk.lora_ffn is not None else None
-            _, wf, k = _WanLoRABlockNativeFunction._args(blk, rows, S, T, blk.lora_A, blk.lora_B, backward=False, TI=TI, ffn=ffn, ffn_entry=True)
+            _, wf, k = _WanLoRABlockNativeFunction._args(blk, rows, S, T, blk.lora_A, blk.lora_B, backward=False, TI=TI, ffn=ffn)
             blocks[i] = wf
             keep += k
             if TI > 0:

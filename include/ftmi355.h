@@ -734,77 +734,44 @@ int ftmi_wan_block_backward(const ftmi_wan_block_config* cfg, const void* params
                             const float* rope_cos, const float* rope_sin, const void* dout, void* dx, void* denc, float* dmod, void* saved, size_t saved_bytes,
                             void* scratch, size_t scratch_bytes, ftmi_stream stream);
 
-/* The same block for LoRA fine-tuning (the reference's Wan SFT recipes: --training_type lora --target_modules "blocks.*(to_q|to_k|to_v|to_out.0)"): the
- * same forward and backward walk behind other entry points (one implementation, csrc/wan_dit.hip), run with frozen base weights; fp32 adapters lora_a [8, r, D] / lora_b [8, D, r] sit on attn1.to_q, to_k, to_v, to_out.0, attn2.to_q, to_k, to_v, to_out.0
- * (in this order) and every projection computes x W^T + b + lora_scale (x A^T) B^T.  The configuration is ftmi_wan_block_config plus r and lora_scale.
- * params: the flat bf16 buffer as above; w_*_t: K-contiguous (transposed) twins of the seven weight matrices, backward only -- [D, 3D] of attn1 q|k|v,
- * [D, D] of attn1.to_out.0, attn2.to_q, [D, 2D] of attn2 k|v, [D, D] of attn2.to_out.0, [D, F] of ffn.net.0.proj, [F, D] of ffn.net.2.
- * `saved` (ftmi_wan_lora_block_saved_bytes; smaller than the full fine-tune's by B S (3D + F) 2 bytes, larger by the down-projected rows) lives from the
- * forward to the backward of the block, or is rebuilt inside the backward by calling the forward with out = NULL (gradient checkpointing);
- * `scratch` (ftmi_wan_lora_block_scratch_bytes, both directions) may be shared by all blocks of a stream.  With r = 0 the forward's output and the backward's
- * dx are those of ftmi_wan_block_forward / _backward, bit for bit.  The backward writes dx, writes denc unless it is NULL (frozen text embedder: that
- * GEMM is skipped) and ADDS to grad_a [8, r, D] / grad_b [8, D, r] (fp32); no base-weight, norm, bias or modulation gradient is formed. */
-typedef struct {
-    int B, S, T;      /* batch, video tokens, text tokens */
-    int D, H, F;      /* width = H x 128, feed-forward width */
-    float eps;        /* 1e-6 */
-    int gemm_variant; /* 8 */
-    int r;            /* LoRA rank: 0, 64 or 128 (other ranks zero-padded by the caller) */
-    float lora_scale; /* alpha / (the user's) r */
-} ftmi_wan_lora_block_config;
-typedef struct {
-    const void* params;                                                          /* flat bf16, WanBlockLayout order */
-    const void *w_qkv1_t, *w_o1_t, *w_q2_t, *w_kv2_t, *w_o2_t, *w_f1_t, *w_f2_t; /* transposed twins: backward only */
-    const float *lora_a, *lora_b;                                                /* fp32 [8, r, D], [8, D, r]; NULL when r == 0 */
-} ftmi_wan_lora_block_weights;
-size_t ftmi_wan_lora_block_saved_bytes(const ftmi_wan_lora_block_config* cfg);
-size_t ftmi_wan_lora_block_scratch_bytes(const ftmi_wan_lora_block_config* cfg);
-/* out [B, S, D]; out == NULL: recomputation pass (refills `saved` with the identical kernel sequence) */
-int ftmi_wan_lora_block_forward(const ftmi_wan_lora_block_config* cfg, const ftmi_wan_lora_block_weights* w, const void* x, const void* enc, const float* mod,
-                                const float* rope_cos, const float* rope_sin, void* out, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
-                                ftmi_stream stream);
-int ftmi_wan_lora_block_backward(const ftmi_wan_lora_block_config* cfg, const ftmi_wan_lora_block_weights* w, const void* x, const void* enc, const float* mod,
-                                 const float* rope_cos, const float* rope_sin, const void* dout, void* dx, void* denc, float* grad_a, float* grad_b, void* saved,
-                                 size_t saved_bytes, void* scratch, size_t scratch_bytes, ftmi_stream stream);
-
-/* The LoRA block of a Wan image-to-video model (Wan2.1-I2V: attn2 has added_kv_proj_dim): the same walk with the image context in the cross-attention,
+/* The same block for LoRA fine-tuning over a FROZEN base, text-to-video and image-to-video: ONE entry family, ftmi_wan_lora_ffn_block_*, and the same forward
+ * and backward walk behind it as behind ftmi_wan_block_* (one implementation, csrc/wan_dit.hip).  The configuration is ftmi_wan_block_config plus r and
+ * lora_scale (the adapters), TI (the image context) and ffn (adapters on the feed-forward projections as well).
+ *
+ * Attention adapters (the reference's Wan SFT recipes: --training_type lora --target_modules "blocks.*(to_q|to_k|to_v|to_out.0)"): fp32 lora_a [8, r, D] /
+ * lora_b [8, D, r] sit on attn1.to_q, to_k, to_v, to_out.0, attn2.to_q, to_k, to_v, to_out.0 (in this order) and every projection computes
+ * x W^T + b + lora_scale (x A^T) B^T.  params: the flat bf16 buffer as above; w_*_t: K-contiguous (transposed) twins of the seven weight matrices, backward
+ * only -- [D, 3D] of attn1 q|k|v, [D, D] of attn1.to_out.0, attn2.to_q, [D, 2D] of attn2 k|v, [D, D] of attn2.to_out.0, [D, F] of ffn.net.0.proj, [F, D] of
+ * ffn.net.2.  x [B, S, D], enc [B, T, D] bf16, mod fp32 [B, 6, D], rope_cos / rope_sin fp32 [S, 64] as above.
+ * `saved` (ftmi_wan_lora_ffn_block_saved_bytes; smaller than the full fine-tune's by B S (3D + F) 2 bytes, larger by the down-projected rows) lives from the
+ * forward to the backward of the block, or is rebuilt inside the backward by calling the forward with out = NULL (gradient checkpointing: the recomputation
+ * pass refills `saved` with the identical kernel sequence, the feed-forward adapters' rows included); `scratch` (ftmi_wan_lora_ffn_block_scratch_bytes, both
+ * directions) may be shared by all blocks of a stream.  With r = 0 the forward's output and the backward's dx are those of ftmi_wan_block_forward /
+ * _backward, bit for bit.  The backward writes dx, writes denc unless it is NULL (frozen text embedder: that GEMM is skipped) and ADDS to grad_a [8, r, D] /
+ * grad_b [8, D, r] (fp32); no base-weight, norm, bias or modulation gradient is formed.
+ *
+ * Image context (TI > 0; a Wan image-to-video model, Wan2.1-I2V: attn2 has added_kv_proj_dim): the cross-attention becomes
  *   o2 = bf(SDPA(q2, k_text, v_text)) + bf(SDPA(q2, k_img, v_img)),  k_img = norm_added_k(add_k_proj(enc_img)),  v_img = add_v_proj(enc_img).
- * The configuration is ftmi_wan_lora_block_config plus TI, the number of image tokens (257); enc_img [B, TI, D] bf16 is the image embedder's output.
- * img_params: a SEPARATE flat bf16 buffer (the block's own flat buffer keeps its layout): add_k_proj | add_v_proj weight [2D, D], their biases [2D],
- * norm_added_k weight [D].  No adapter sits on them (the recipe's regex does not match), so the backward adds only the image branch's dQ: no gradient to
- * enc_img or to img_params.  `saved` grows by the projected image rows [B TI, 3D], lse of the image branch and the summed attention output [B, S, D].
- * TI = 0 (img_params / enc_img may then be NULL): the launches and bits of ftmi_wan_lora_block_forward / _backward. */
-typedef struct {
-    int B, S, T;      /* batch, video tokens, text tokens */
-    int D, H, F;      /* width = H x 128 <= 5120, feed-forward width */
-    float eps;        /* 1e-6 */
-    int gemm_variant; /* 8 */
-    int r;            /* LoRA rank: 0, 64 or 128 (other ranks zero-padded by the caller) */
-    float lora_scale; /* alpha / (the user's) r */
-    int TI;           /* image tokens, 0 .. 320 */
-} ftmi_wan_i2v_lora_block_config;
-size_t ftmi_wan_i2v_lora_block_saved_bytes(const ftmi_wan_i2v_lora_block_config* cfg);
-size_t ftmi_wan_i2v_lora_block_scratch_bytes(const ftmi_wan_i2v_lora_block_config* cfg);
-int ftmi_wan_i2v_lora_block_forward(const ftmi_wan_i2v_lora_block_config* cfg, const ftmi_wan_lora_block_weights* w, const void* img_params, const void* x,
-                                    const void* enc, const void* enc_img, const float* mod, const float* rope_cos, const float* rope_sin, void* out, void* saved,
-                                    size_t saved_bytes, void* scratch, size_t scratch_bytes, ftmi_stream stream);
-int ftmi_wan_i2v_lora_block_backward(const ftmi_wan_i2v_lora_block_config* cfg, const ftmi_wan_lora_block_weights* w, const void* img_params, const void* x,
-                                     const void* enc, const void* enc_img, const float* mod, const float* rope_cos, const float* rope_sin, const void* dout,
-                                     void* dx, void* denc, float* grad_a, float* grad_b, void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
-                                     ftmi_stream stream);
-
-/* The LoRA block with adapters on the feed-forward projections as well (ffn = 1): ffn.net.0.proj (A_1 [r, D], B_1 [F, r]) and ffn.net.2 (A_2 [r, F],
- * B_2 [D, r]) next to the eight attention projections, at the same rank and scale -- what peft attaches when the reference's --target_modules (handed over
- * unchanged: finetrainers/trainer/sft_trainer/trainer.py:121-128 builds LoraConfig(r, lora_alpha, target_modules) and calls transformer.add_adapter) also
- * names "ffn.net.0.proj" and "ffn.net.2"; they are the two "ff" members of the control trainer's default list (finetrainers/trainer/control_trainer/config.py:60-62
+ * TI is the number of image tokens (257); enc_img [B, TI, D] bf16 is the image embedder's output.  img_params: a SEPARATE flat bf16 buffer (the block's own
+ * flat buffer keeps its layout): add_k_proj | add_v_proj weight [2D, D], their biases [2D], norm_added_k weight [D].  No adapter sits on them (the recipe's
+ * regex does not match), so the backward adds only the image branch's dQ: no gradient to enc_img or to img_params.  `saved` grows by the projected image
+ * rows [B TI, 3D], lse of the image branch and the summed attention output [B, S, D]; `scratch` does not depend on TI.  TI = 0 (text-to-video; img_params /
+ * enc_img may then be NULL): none of it -- no launch, no byte.
+ *
+ * Feed-forward adapters (ffn = 1): ffn.net.0.proj (A_1 [r, D], B_1 [F, r]) and ffn.net.2 (A_2 [r, F], B_2 [D, r]) next to the eight attention projections,
+ * at the same rank and scale -- what peft attaches when the reference's --target_modules (handed over unchanged: finetrainers/trainer/sft_trainer/trainer.py:121-128
+ * builds LoraConfig(r, lora_alpha, target_modules) and calls transformer.add_adapter) also names "ffn.net.0.proj" and "ffn.net.2"; they are the two "ff"
+ * members of the control trainer's default list (finetrainers/trainer/control_trainer/config.py:60-62
  * --target_modules "(transformer_blocks|single_transformer_blocks).*(to_q|to_k|to_v|to_out.0|ff.net.0.proj|ff.net.2)") spelled for Wan, whose feed-forward
- * module is named "ffn".  One entry for text-to-video (TI = 0) and image-to-video (TI > 0): the configuration is ftmi_wan_i2v_lora_block_config plus ffn, the
- * weights are ftmi_wan_lora_block_weights plus the four fp32 matrices, the same walk (csrc/wan_dit.hip) runs behind it.
+ * module is named "ffn".
  *   pre = n3 W_1^T + b_1 + s (n3 A_1^T) B_1^T,  act = gelu_tanh(pre)  (one launch);   f = act W_2^T + b_2 + s (act A_2^T) B_2^T
  * `saved` grows by the two down-projected rows [B S, 3r] each and by n3 [B S, D] and act [B S, F], which the frozen base otherwise drops (dA_1 and dA_2 read
- * them).  ffn = 0: the launches, bits and byte counts of ftmi_wan_i2v_lora_block_* (ffn_* and grad_ffn_* may be NULL).  ffn = 1 needs r > 0 and F >= 256;
- * what the kernels cannot take returns FTMI_ERR_UNSUPPORTED (the byte planners then return 0).  The backward ADDS to grad_a / grad_b and to
- * grad_ffn_a1 [r, D], grad_ffn_b1 [F, r], grad_ffn_a2 [r, F], grad_ffn_b2 [D, r] (fp32). */
+ * them).  The backward ADDS to grad_ffn_a1 [r, D], grad_ffn_b1 [F, r], grad_ffn_a2 [r, F], grad_ffn_b2 [D, r] (fp32) as well.  ffn = 0 (ffn_* and grad_ffn_*
+ * may then be NULL): none of it -- no launch, no byte.  ffn = 1 needs r > 0 and F >= 256.
+ *
+ * What the kernels cannot take returns FTMI_ERR_UNSUPPORTED, and the byte planners then return 0 (the reason is in ftmi_last_error).
+ * (Until version 100 the library had two narrower entry families next to this one: the same call without TI and ffn, and without ffn.  They issued the
+ * launches and planned the bytes of TI = 0, ffn = 0 / of ffn = 0 here and were folded into it at version 101 -- DESIGN.md 7-N; their names are not reused.) */
 typedef struct {
     int B, S, T;      /* batch, video tokens, text tokens */
     int D, H, F;      /* width = H x 128 <= 5120, feed-forward width */
@@ -816,12 +783,17 @@ typedef struct {
     int ffn;          /* 1: adapters on ffn.net.0.proj and ffn.net.2 as well */
 } ftmi_wan_lora_ffn_block_config;
 typedef struct {
+    const void* params;                                                          /* flat bf16, WanBlockLayout order */
+    const void *w_qkv1_t, *w_o1_t, *w_q2_t, *w_kv2_t, *w_o2_t, *w_f1_t, *w_f2_t; /* transposed twins: backward only */
+    const float *lora_a, *lora_b;                                                /* fp32 [8, r, D], [8, D, r]; NULL when r == 0 */
+} ftmi_wan_lora_block_weights;
+typedef struct {
     ftmi_wan_lora_block_weights base;
     const float *ffn_a1, *ffn_b1, *ffn_a2, *ffn_b2; /* fp32 [r, D], [F, r], [r, F], [D, r]; NULL when ffn == 0 */
 } ftmi_wan_lora_ffn_block_weights;
 size_t ftmi_wan_lora_ffn_block_saved_bytes(const ftmi_wan_lora_ffn_block_config* cfg);
 size_t ftmi_wan_lora_ffn_block_scratch_bytes(const ftmi_wan_lora_ffn_block_config* cfg);
-/* out == NULL: recomputation pass (refills `saved`, the feed-forward adapters' rows included) */
+/* out [B, S, D]; out == NULL: recomputation pass (refills `saved`, the feed-forward adapters' rows included) */
 int ftmi_wan_lora_ffn_block_forward(const ftmi_wan_lora_ffn_block_config* cfg, const ftmi_wan_lora_ffn_block_weights* w, const void* img_params, const void* x,
                                     const void* enc, const void* enc_img, const float* mod, const float* rope_cos, const float* rope_sin, void* out, void* saved,
                                     size_t saved_bytes, void* scratch, size_t scratch_bytes, ftmi_stream stream);
@@ -1097,7 +1069,7 @@ int ftmi_hy_sample(const ftmi_hy_sample_config* cfg, const ftmi_hy_sample_weight
 /* The same loop over a model whose dual-stream blocks carry the text stream's adapters as well: `base` as above, text_adapters as in ftmi_hy_dual_config (1: every
  * dual block's lora_a / lora_b hold 8 matrices; needs base.r > 0; other values than 0 / 1 are FTMI_ERR_INVALID, a workspace size of 0).  The flag is handed to every
  * ftmi_hy_dual_forward of the walk and the workspace follows that block's layout.  text_adapters = 0 is ftmi_hy_sample: the same workspace, launches and bits.
- * (ftmi_hy_sample_config keeps its size: the extension is a structure of its own, like ftmi_wan_lora_ffn_block_config over ftmi_wan_i2v_lora_block_config.) */
+ * (ftmi_hy_sample_config keeps its size: the extension is a structure of its own, like ftmi_wan_lora_ffn_block_config over ftmi_wan_block_config: a name never changes size under its callers.) */
 typedef struct ftmi_hy_sample_text_config {
     ftmi_hy_sample_config base;
     int text_adapters;        /* 0 or 1 */

@@ -241,7 +241,7 @@ def test_i2v_block_exact_degenerations(geom, B, S, T, native):
 @pytest.mark.parametrize("rank", [32, 64])
 @pytest.mark.parametrize("geom,B,S,T", CASES + [(BIG, 1, 136, 16)])
 def test_i2v_block_c_call_python_composition_and_recomputation(geom, B, S, T, rank):
-    """``ftmi_wan_i2v_lora_block_*`` against the per-kernel composition from Python, and the C call with gradient checkpointing (``out = NULL`` refills the
+    """``ftmi_wan_lora_ffn_block_*`` (TI > 0, ffn = 0) against the per-kernel composition from Python, and the C call with gradient checkpointing (``out = NULL`` refills the
     saved buffer inside the backward) against the kept activations: same bits, adapter gradients to the order of their atomics."""
     _, gblk = _block_pair(geom, rank, oracle=False)
     x, enc, temb, dout, img = _inputs(B, S, T, geom[0], seed=S + 7)

@@ -145,7 +145,7 @@ def test_frozen_path_has_the_full_finetune_bits(geom, B, S, T, native):
 @pytest.mark.parametrize("B,S,T", [(2, 48, 16), (1, 200, 64), (2, 320, 40)])
 @pytest.mark.parametrize("rank", [32, 64])
 def test_lora_block_c_call_matches_the_python_composition(B, S, T, rank):
-    """``ftmi_wan_lora_block_forward / _backward`` against the per-kernel composition issued from Python: output, dx and d text bit-identical, the 16
+    """``ftmi_wan_lora_ffn_block_forward / _backward`` (TI = 0, ffn = 0) against the per-kernel composition issued from Python: output, dx and d text bit-identical, the 16
     adapter gradients equal up to the order of their fp32 atomics (the bound of test_wan_block_c_call_matches_the_python_composition)."""
     _, gblk = _block_pair((256, 2, 512), rank=rank, alpha=float(rank))
     x, enc, temb, dout = _block_inputs(B, S, T, 256, seed=B * 1000 + S + 7)

@@ -217,6 +217,7 @@ def test_gradient_hook_buckets_cover_the_ten_adapter_blocks():
 def test_c_abi_exports_and_declares_the_ffn_lora_block():
     """The new symbols are declared in the header, exported by the library and bound (tests/test_host.py's header-driven test then covers them as well), and each
     declaration's comment cites the reference site it stands for."""
+    import wan_lora_bytes
     from finetrainers_amd import _lib
 
     lib = _lib.load()
@@ -224,7 +225,8 @@ def test_c_abi_exports_and_declares_the_ffn_lora_block():
     declared = set(re.findall(r"\b(ftmi_[a-z0-9_]+)\s*\(", header))
     for name in NEW_SYMBOLS:
         assert name in declared and name in _lib.EXPORTED_SYMBOLS and getattr(lib, name) is not None, name
-    before = header[:header.index("} ftmi_wan_lora_ffn_block_config;")].rsplit("typedef struct", 1)[0]
+    wan_lora_bytes.assert_only_the_wide_family(lib, declared, set(_lib.EXPORTED_SYMBOLS))  # ... and they are the only LoRA block entries left
+    before =header[:header.index("} ftmi_wan_lora_ffn_block_config;")].rsplit("typedef struct", 1)[0]
     comment = before.rsplit("/*", 1)[1]
     assert "finetrainers/trainer/sft_trainer/trainer.py" in comment and "ffn.net.0.proj" in comment
 
@@ -238,28 +240,27 @@ def _cfg(**kw):
 
 
 def test_byte_plans_of_the_new_entry():
-    """ffn = 0: the byte counts of the existing entries (T2V and I2V), to the byte.  ffn = 1: `saved` grows by exactly n3, act and the two down-projected rows
-    (each rounded up to the planner's 256-byte granule), whatever TI."""
+    """ffn = 0: the byte counts recorded in tests/golden/wan_lora_entry_bytes.txt, which the text-to-video and image-to-video entries of the time returned as
+    well, to the byte.  ffn = 1: `saved` grows by exactly n3, act and the two down-projected rows (each rounded up to the planner's 256-byte granule),
+    whatever TI, and lands on the recorded bytes."""
+    import wan_lora_bytes
     from finetrainers_amd import _lib
 
     lib = _lib.load()
+    plans = wan_lora_bytes.recorded()
+    geom = (1, 20280, 512, 1536, 12, 8960)
     up = lambda n: (n + 255) // 256 * 256
     for r in (0, 64, 128):
         for TI in (0, 257):
             off = _cfg(r=r, TI=TI)
-            i2v = _lib.WanI2VLoraBlockConfig(B=1, S=20280, T=512, D=1536, H=12, F=8960, eps=1e-6, gemm_variant=8, r=r, lora_scale=1.0, TI=TI)
             saved0, scratch0 = lib.ftmi_wan_lora_ffn_block_saved_bytes(ctypes.byref(off)), lib.ftmi_wan_lora_ffn_block_scratch_bytes(ctypes.byref(off))
-            assert saved0 == lib.ftmi_wan_i2v_lora_block_saved_bytes(ctypes.byref(i2v)) > 0
-            assert scratch0 == lib.ftmi_wan_i2v_lora_block_scratch_bytes(ctypes.byref(i2v)) > 0
-            if TI == 0:
-                t2v = _lib.WanLoraBlockConfig(B=1, S=20280, T=512, D=1536, H=12, F=8960, eps=1e-6, gemm_variant=8, r=r, lora_scale=1.0)
-                assert saved0 == lib.ftmi_wan_lora_block_saved_bytes(ctypes.byref(t2v)) and scratch0 == lib.ftmi_wan_lora_block_scratch_bytes(ctypes.byref(t2v))
+            assert (saved0, scratch0) == plans[geom + (r, TI, 0)] and saved0 > 0 and scratch0 > 0
             if r:
                 on = _cfg(r=r, TI=TI, ffn=1)
                 M = 20280
                 grow = up(M * 1536 * 2) + up(M * 8960 * 2) + 2 * up(M * 3 * r * 2)
-                assert lib.ftmi_wan_lora_ffn_block_saved_bytes(ctypes.byref(on)) == saved0 + grow
-                assert lib.ftmi_wan_lora_ffn_block_scratch_bytes(ctypes.byref(on)) > 0
+                assert lib.ftmi_wan_lora_ffn_block_saved_bytes(ctypes.byref(on)) == saved0 + grow == plans[geom + (r, TI, 1)][0]
+                assert lib.ftmi_wan_lora_ffn_block_scratch_bytes(ctypes.byref(on)) == plans[geom + (r, TI, 1)][1] > 0
 
 
 @pytest.mark.parametrize("kw,code,word", [(dict(ffn=1, r=0), "UNSUPPORTED", "rank"), (dict(ffn=1, F=192), "UNSUPPORTED", "feed-forward width"),

@@ -1,4 +1,4 @@
-"""Wan image-to-video LoRA, the parts that need no GPU: the byte planners of ``ftmi_wan_i2v_lora_block_*``, the width limit, the unchanged T2V plans, the
+"""Wan image-to-video LoRA, the parts that need no GPU: the byte planners of ``ftmi_wan_lora_ffn_block_*`` with an image context, the width limit, the unchanged T2V plans, the
 diffusers I2V state-dict names, the adapter set on an I2V model and the 36-channel input the specification builds."""
 import ctypes
 import os
@@ -9,17 +9,16 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RECIPE_REGEX = "blocks.*(to_q|to_k|to_v|to_out.0)"  # examples/training/sft/wan_i2v/3dgs_dissolve/train.sh --target_modules
-NEW_SYMBOLS = ("ftmi_attn_ctx2_fwd", "ftmi_attn_ctx2_dq", "ftmi_wan_i2v_lora_block_saved_bytes", "ftmi_wan_i2v_lora_block_scratch_bytes",
-               "ftmi_wan_i2v_lora_block_forward", "ftmi_wan_i2v_lora_block_backward")
+NEW_SYMBOLS = ("ftmi_attn_ctx2_fwd", "ftmi_attn_ctx2_dq")
 GEOMS = [(2, 48, 16, 256, 2, 512), (1, 200, 64, 1536, 12, 8960), (1, 136, 16, 5120, 40, 13824)]  # B, S, T, D, H, F
 KW = dict(num_attention_heads=2, attention_head_dim=128, ffn_dim=512, text_dim=64, image_dim=128, in_channels=36)
 bf16 = torch.bfloat16
 
 
 def _cfg(B, S, T, D, H, F, r, TI):
-    from finetrainers_amd import _lib
+    import wan_lora_bytes
 
-    return _lib.WanI2VLoraBlockConfig(B=B, S=S, T=T, D=D, H=H, F=F, eps=1e-6, gemm_variant=8, r=r, lora_scale=1.0, TI=TI)
+    return wan_lora_bytes.config(B, S, T, D, H, F, r, TI)
 
 
 def _last_error(lib):
@@ -29,77 +28,88 @@ def _last_error(lib):
 
 
 def test_c_abi_exports_and_declares_the_i2v_entries():
+    """The image attention's two kernels and the one LoRA block family that takes the image context; the narrow families' names are gone."""
+    import wan_lora_bytes
     from finetrainers_amd import _lib
 
     lib = _lib.load()
     declared = set(re.findall(r"\b(ftmi_[a-z0-9_]+)\s*\(", open(os.path.join(ROOT, "include", "ftmi355.h")).read()))
     for name in NEW_SYMBOLS:
         assert name in declared and getattr(lib, name) is not None, name
+    wan_lora_bytes.assert_only_the_wide_family(lib, declared, set(_lib.EXPORTED_SYMBOLS))
 
 
 @pytest.mark.parametrize("geom", GEOMS)
 @pytest.mark.parametrize("r", [0, 64, 128])
 def test_i2v_planners_are_consistent_and_grow_with_the_image_tokens(geom, r):
-    """TI = 0: the T2V LoRA plan, byte for byte.  TI > 0: saved grows by exactly the four image buffers (each rounded to 256 bytes like every entry of
-    the plan), monotonically in TI; the scratch plan does not depend on TI."""
+    """TI = 0: the T2V LoRA plan as recorded (tests/golden/wan_lora_entry_bytes.txt), byte for byte.  TI > 0: saved grows by exactly the four image buffers
+    (each rounded to 256 bytes like every entry of the plan), monotonically in TI, and lands on the recorded bytes at TI = 257 and 320; the scratch plan does
+    not depend on TI."""
+    import wan_lora_bytes
     from finetrainers_amd import _lib
 
     lib = _lib.load()
     B, S, T, D, H, F = geom
-    t2v = ctypes.byref(_lib.WanLoraBlockConfig(B=B, S=S, T=T, D=D, H=H, F=F, eps=1e-6, gemm_variant=8, r=r, lora_scale=1.0))
-    saved0, scratch0 = lib.ftmi_wan_lora_block_saved_bytes(t2v), lib.ftmi_wan_lora_block_scratch_bytes(t2v)
+    plans = wan_lora_bytes.recorded()
+    saved0, scratch0 = plans[(B, S, T, D, H, F, r, 0, 0)]
     assert saved0 > 0 and scratch0 > 0
     up = lambda n: (n + 255) // 256 * 256
     prev = saved0
     for TI in (0, 1, 64, 257, 320):
-        cfg = ctypes.byref(_cfg(B, S, T, D, H, F, r, TI))
-        saved, scratch = lib.ftmi_wan_i2v_lora_block_saved_bytes(cfg), lib.ftmi_wan_i2v_lora_block_scratch_bytes(cfg)
+        saved, scratch = wan_lora_bytes.planned(B, S, T, D, H, F, r, TI)
         want = saved0 if TI == 0 else saved0 + up(B * TI * 2 * D * 2) + up(B * TI * D * 2) + up(B * H * S * 4) + up(B * S * D * 2)
         assert saved == want and scratch == scratch0, (TI, saved, want, scratch, scratch0)
         assert saved >= prev and (TI == 0 or saved > saved0)
+        if TI in (0, 257, 320):
+            assert (saved, scratch) == plans[(B, S, T, D, H, F, r, TI, 0)]
         prev = saved
-    assert lib.ftmi_wan_i2v_lora_block_saved_bytes(ctypes.byref(_cfg(B, S, T, D, H, F, r, 321))) == 0 and "320" in _last_error(lib)
+    assert lib.ftmi_wan_lora_ffn_block_saved_bytes(ctypes.byref(_cfg(B, S, T, D, H, F, r, 321))) == 0 and "320" in _last_error(lib)
+    assert plans[(B, S, T, D, H, F, r, 321, 0)] == (0, 0)
 
 
 def test_width_5120_is_accepted_and_5184_refused():
     """Through the planner and through the forward entry (which checks the configuration before it touches a pointer: the 5120 call gets as far as the
     buffer-size check, the 5184 call is refused with the limit in its message)."""
+    import wan_lora_bytes
     from finetrainers_amd import _lib
 
     lib = _lib.load()
     ok, bad = _cfg(1, 136, 16, 5120, 40, 13824, 64, 257), _cfg(1, 136, 16, 5184, 40, 13824, 64, 257)
     bad.H = 5184 // 128  # 40.5 heads do not exist: give it a width that is heads x 128 + 64 either way
-    assert lib.ftmi_wan_i2v_lora_block_saved_bytes(ctypes.byref(ok)) > 0
-    assert lib.ftmi_wan_i2v_lora_block_saved_bytes(ctypes.byref(bad)) == 0 and "5120" in _last_error(lib)
+    assert lib.ftmi_wan_lora_ffn_block_saved_bytes(ctypes.byref(ok)) > 0
+    assert lib.ftmi_wan_lora_ffn_block_saved_bytes(ctypes.byref(bad)) == 0 and "5120" in _last_error(lib)
     wide = _cfg(1, 136, 16, 5248, 41, 13824, 64, 257)  # a whole number of heads, past the limit
-    assert lib.ftmi_wan_i2v_lora_block_saved_bytes(ctypes.byref(wide)) == 0 and "at most 5120" in _last_error(lib)
-    w = _lib.WanLoraBlockWeights()
+    assert lib.ftmi_wan_lora_ffn_block_saved_bytes(ctypes.byref(wide)) == 0 and "at most 5120" in _last_error(lib)
+    w = _lib.WanLoraFfnBlockWeights()
     dummy = ctypes.create_string_buffer(64)
     p = ctypes.cast(dummy, ctypes.c_void_p)
-    w.params = p
+    w.base.params = p
     for cfg, msg in ((ok, "buffer too small"), (bad, "at most 5120"), (wide, "at most 5120")):
-        rc = lib.ftmi_wan_i2v_lora_block_forward(ctypes.byref(cfg), ctypes.byref(w), p, p, p, p, p, p, p, p, p, 0, p, 0, None)
+        rc = lib.ftmi_wan_lora_ffn_block_forward(ctypes.byref(cfg), ctypes.byref(w), p, p, p, p, p, p, p, p, p, 0, p, 0, None)
         assert rc != 0 and msg in _last_error(lib), (cfg.D, rc, _last_error(lib))
-    t2v = _lib.WanLoraBlockConfig(B=1, S=136, T=16, D=5120, H=40, F=13824, eps=1e-6, gemm_variant=8, r=64, lora_scale=1.0)
-    assert lib.ftmi_wan_lora_block_saved_bytes(ctypes.byref(t2v)) == lib.ftmi_wan_i2v_lora_block_saved_bytes(ctypes.byref(_cfg(1, 136, 16, 5120, 40, 13824, 64, 0)))
+    plans = wan_lora_bytes.recorded()  # the widest geometry's plans, with and without the image tokens, are the recorded ones
+    for TI in (0, 257):
+        assert wan_lora_bytes.planned(1, 136, 16, 5120, 40, 13824, 64, TI) == plans[(1, 136, 16, 5120, 40, 13824, 64, TI, 0)] > (0, 0)
+    assert plans[(1, 136, 16, 5184, 40, 13824, 64, 257, 0)] == plans[(1, 136, 16, 5248, 41, 13824, 64, 257, 0)] == (0, 0)
 
 
 def test_recorded_t2v_plans_have_not_moved():
-    """tests/golden/wan_block_bytes.txt through the existing planners, and the same bytes through the I2V planner at TI = 0."""
+    """tests/golden/wan_block_bytes.txt: the full fine-tune's columns through its planners, the LoRA columns through the one LoRA entry at TI = 0, ffn = 0 --
+    which tests/golden/wan_lora_entry_bytes.txt records as well, with the same numbers."""
+    import wan_lora_bytes
     from finetrainers_amd import _lib
 
     lib = _lib.load()
     rows = [ln.split() for ln in open(os.path.join(ROOT, "tests", "golden", "wan_block_bytes.txt")) if ln.strip() and not ln.startswith("#")]
     assert len(rows) == 18
+    plans = wan_lora_bytes.recorded()
     for row in rows:
         B, S, T, D, H, F, r, full_saved, full_scratch, elements, lora_saved, lora_scratch = map(int, row)
         full = ctypes.byref(_lib.WanBlockConfig(B=B, S=S, T=T, D=D, H=H, F=F, eps=1e-6, gemm_variant=8))
-        lora = ctypes.byref(_lib.WanLoraBlockConfig(B=B, S=S, T=T, D=D, H=H, F=F, eps=1e-6, gemm_variant=8, r=r, lora_scale=1.0))
-        i2v = ctypes.byref(_cfg(B, S, T, D, H, F, r, 0))
-        got = (lib.ftmi_wan_block_saved_bytes(full), lib.ftmi_wan_block_scratch_bytes(full), lib.ftmi_wan_block_param_elements(full),
-               lib.ftmi_wan_lora_block_saved_bytes(lora), lib.ftmi_wan_lora_block_scratch_bytes(lora))
+        got = (lib.ftmi_wan_block_saved_bytes(full), lib.ftmi_wan_block_scratch_bytes(full), lib.ftmi_wan_block_param_elements(full)) + \
+            wan_lora_bytes.planned(B, S, T, D, H, F, r, 0)
         assert got == (full_saved, full_scratch, elements, lora_saved, lora_scratch), (row, got)
-        assert (lib.ftmi_wan_i2v_lora_block_saved_bytes(i2v), lib.ftmi_wan_i2v_lora_block_scratch_bytes(i2v)) == (lora_saved, lora_scratch)
+        assert plans[(B, S, T, D, H, F, r, 0, 0)] == (lora_saved, lora_scratch)
 
 
 def _pair(layers=2):

@@ -12,42 +12,46 @@ import torch.multiprocessing as mp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RECIPE_REGEX = "blocks.*(to_q|to_k|to_v|to_out.0)"  # examples/training/sft/wan/*/train.sh --target_modules
-NEW_SYMBOLS = ("ftmi_wan_lora_block_saved_bytes", "ftmi_wan_lora_block_scratch_bytes", "ftmi_wan_lora_block_forward", "ftmi_wan_lora_block_backward")
 SMALL = dict(num_attention_heads=2, attention_head_dim=128, ffn_dim=512, text_dim=64)
 
 
 def test_c_abi_exports_and_declares_the_wan_lora_block():
+    """The one LoRA entry family, ``ftmi_wan_lora_ffn_block_*``, is declared, bound and exported; the eight names of the two narrow families folded into it
+    are neither declared nor exported."""
+    import wan_lora_bytes
     from finetrainers_amd import _lib
 
     lib = _lib.load()
     header = open(os.path.join(ROOT, "include", "ftmi355.h")).read()
     declared = set(re.findall(r"\b(ftmi_[a-z0-9_]+)\s*\(", header))
-    for name in NEW_SYMBOLS:
-        assert name in declared, f"{name} is not declared in include/ftmi355.h"
-        assert getattr(lib, name) is not None, f"{name} is not exported by the built library"
+    wan_lora_bytes.assert_only_the_wide_family(lib, declared, set(_lib.EXPORTED_SYMBOLS))
+    assert not re.search(r"\bftmi_wan_(i2v_)?lora_block_config\b", header)  # their configuration typedefs went with them
+    assert lib.ftmi_version() == 101
 
 
 def test_lora_block_keeps_less_than_the_full_finetune_block():
     """At the recipe's bucket (49 x 480 x 832 -> 20 280 video + 512 text tokens, Wan2.1-T2V-1.3B geometry) the frozen base drops a1, n3, act and f:
     the saved buffer must be smaller than the full fine-tune's by at least the activation `act` (B S F 2 bytes), also with the rank-64 down-projections kept."""
+    import wan_lora_bytes
     from finetrainers_amd import _lib
 
     lib = _lib.load()
     B, S, T, D, F = 1, 20280, 512, 1536, 8960
     full = lib.ftmi_wan_block_saved_bytes(ctypes.byref(_lib.WanBlockConfig(B=B, S=S, T=T, D=D, H=12, F=F, eps=1e-6, gemm_variant=8)))
     for r in (0, 64, 128):
-        cfg = _lib.WanLoraBlockConfig(B=B, S=S, T=T, D=D, H=12, F=F, eps=1e-6, gemm_variant=8, r=r, lora_scale=1.0)
-        lora = lib.ftmi_wan_lora_block_saved_bytes(ctypes.byref(cfg))
+        lora, scratch = wan_lora_bytes.planned(B, S, T, D, 12, F, r)
         print(f"[wan-lora] saved bytes per block at {S}+{T} tokens: full fine-tune {full / 1e9:.3f} GB, LoRA r={r} {lora / 1e9:.3f} GB")
         assert 0 < lora and full - lora >= B * S * F * 2
-        assert lib.ftmi_wan_lora_block_scratch_bytes(ctypes.byref(cfg)) > 0
-    r0 = lib.ftmi_wan_lora_block_saved_bytes(ctypes.byref(_lib.WanLoraBlockConfig(B=B, S=S, T=T, D=D, H=12, F=F, eps=1e-6, gemm_variant=8, r=0, lora_scale=1.0)))
+        assert scratch > 0
+    r0 = wan_lora_bytes.planned(B, S, T, D, 12, F, 0)[0]
     assert full - r0 >= B * S * (3 * D + F) * 2  # the four dropped buffers
 
 
 def test_wan_planners_return_the_recorded_bytes():
     """The four byte planners and ``param_elements`` against tests/golden/wan_block_bytes.txt, recorded once from the library as it was before the full and
-    the LoRA block shared one buffer plan: the callers' allocations (and what a checkpoint of ``saved`` would hold) must not move by a byte."""
+    the LoRA block shared one buffer plan: the callers' allocations (and what a checkpoint of ``saved`` would hold) must not move by a byte.  The LoRA
+    columns are read through the one LoRA entry at TI = 0, ffn = 0."""
+    import wan_lora_bytes
     from finetrainers_amd import _lib
 
     lib = _lib.load()
@@ -56,10 +60,22 @@ def test_wan_planners_return_the_recorded_bytes():
     for row in rows:
         B, S, T, D, H, F, r, full_saved, full_scratch, elements, lora_saved, lora_scratch = map(int, row)
         full = ctypes.byref(_lib.WanBlockConfig(B=B, S=S, T=T, D=D, H=H, F=F, eps=1e-6, gemm_variant=8))
-        lora = ctypes.byref(_lib.WanLoraBlockConfig(B=B, S=S, T=T, D=D, H=H, F=F, eps=1e-6, gemm_variant=8, r=r, lora_scale=1.0))
-        got = (lib.ftmi_wan_block_saved_bytes(full), lib.ftmi_wan_block_scratch_bytes(full), lib.ftmi_wan_block_param_elements(full),
-               lib.ftmi_wan_lora_block_saved_bytes(lora), lib.ftmi_wan_lora_block_scratch_bytes(lora))
+        got = (lib.ftmi_wan_block_saved_bytes(full), lib.ftmi_wan_block_scratch_bytes(full), lib.ftmi_wan_block_param_elements(full)) + \
+            wan_lora_bytes.planned(B, S, T, D, H, F, r)
         assert got == (full_saved, full_scratch, elements, lora_saved, lora_scratch), (row, got)
+
+
+def test_the_one_lora_entry_plans_the_recorded_bytes_of_all_three_families():
+    """Every row of tests/golden/wan_lora_entry_bytes.txt -- seven geometries x r in {0, 64, 128} x TI in {0, 257, 320} x ffn in {0, 1}, and the refused
+    configurations (0 0) -- through ``ftmi_wan_lora_ffn_block_*``, to the byte.  The file was recorded when the library still had the two narrow families
+    and they returned the same numbers wherever they accepted the row: what their callers allocated has not moved."""
+    import wan_lora_bytes
+
+    plans = wan_lora_bytes.recorded()
+    assert len(plans) == 123 and sum(v == (0, 0) for v in plans.values()) == 18
+    assert {k[6:] for k, v in plans.items() if v != (0, 0)} == {(r, TI, ffn) for r in (0, 64, 128) for TI in (0, 257, 320) for ffn in (0, 1) if r or not ffn}
+    for key, want in plans.items():
+        assert wan_lora_bytes.planned(*key) == want, (key, want)
 
 
 def _models(layers, rank=32, alpha=32.0):

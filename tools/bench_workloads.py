@@ -239,7 +239,7 @@ def build_wan_lora(args, par, dev) -> Dict[str, Any]:
                                + ("" if layers == 30 else " -- REDUCED depth"),
                    "model": f"Wan2.1-T2V-1.3B DiT: 30 blocks, width 1536, 12 x 128 heads, frozen; {300 if ffn else 240} fp32 adapters", "seq_len": S,
                    "adapters_per_block": 10 if ffn else 8,
-                   "activation_checkpointing": ckpt, "orchestration": (f"one C call per block and direction (ftmi_wan_lora{'_ffn' if ffn else ''}_block_forward / _backward)" if os.environ.get("FTMI_NATIVE_BLOCKS", "1") != "0" else "python, per kernel over the C ABI")},
+                   "activation_checkpointing": ckpt, "orchestration": ("one C call per block and direction (ftmi_wan_lora_ffn_block_forward / _backward)" if os.environ.get("FTMI_NATIVE_BLOCKS", "1") != "0" else "python, per kernel over the C ABI")},
         "layers": layers,
     }
 
@@ -362,7 +362,7 @@ def build_wan_i2v_lora(args, par, dev) -> Dict[str, Any]:
         "config": {"workload": f"Wan-I2V-14B LoRA rank={args.rank} bf16 SFT step over the frozen base, 49x480x832 clip ({S} video + {T} text + {TI} image tokens), batch 1 per GPU, "
                                f"{layers} blocks" + ("" if layers == 40 else " -- REDUCED depth"),
                    "model": "Wan2.1-I2V-14B DiT geometry: width 5120, 40 x 128 heads, feed-forward 13824, frozen; 8 fp32 adapters per block", "seq_len": S,
-                   "activation_checkpointing": True, "orchestration": ("one C call per block and direction (ftmi_wan_i2v_lora_block_forward / _backward)" if os.environ.get("FTMI_NATIVE_BLOCKS", "1") != "0" else "python, per kernel over the C ABI")},
+                   "activation_checkpointing": True, "orchestration": ("one C call per block and direction (ftmi_wan_lora_ffn_block_forward / _backward)" if os.environ.get("FTMI_NATIVE_BLOCKS", "1") != "0" else "python, per kernel over the C ABI")},
         "layers": layers,
     }
 

@@ -7,7 +7,10 @@ file runs against an older checkout: copy it into that checkout's tools/ and run
 
 Modes: full fine-tune; frozen base, r = 0; r = 32 (peft's init, B = 0); r = 64 with non-zero B -- each with ``native`` on and off, at (B, S, T) = (2, 48, 16) and
 (1, 200, 64) at width 256 and (1, 200, 64) at the Wan2.1-T2V-1.3B block geometry; one LoRA case with gradient checkpointing, one with the text input not
-requiring grad.  Output, dx and d text must be equal bit for bit; what is accumulated with fp32 atomics (flat parameter gradients, dmod, adapter
+requiring grad.  The LoRA configurations beyond the eight attention adapters, each with ``native`` on and off at the two width-256 shapes: ``i2v_r32`` (an
+image-to-video block, TI = 257 image tokens, r = 32 with peft's init), ``ffn_r64`` (adapters on the two feed-forward projections as well, non-zero B on all ten)
+and ``i2v_ffn_r64`` (both); ``i2v_r32`` once with an empty image context (TI = 0), ``i2v_ffn_r64`` once with gradient checkpointing, ``ffn_r64`` once at the
+Wan2.1-T2V-1.3B block geometry.  Output, dx and d text must be equal bit for bit; what is accumulated with fp32 atomics (flat parameter gradients, dmod, adapter
 gradients) within a relative distance of 2e-6, the bound of the C-vs-Python tests for the same quantities.  The time projection goes in as fp32, so that dmod
 comes back as the fp32 sums (handed back in bf16, single entries land on the other side of a rounding boundary from run to run)."""
 import argparse
@@ -22,6 +25,8 @@ bf16 = torch.bfloat16
 SMALL, REAL = (256, 2, 512), (1536, 12, 8960)
 SHAPES = [(SMALL, 2, 48, 16), (SMALL, 1, 200, 64), (REAL, 1, 200, 64)]
 MODES = ("full", "frozen_r0", "r32", "r64")
+WIDE_MODES = ("i2v_r32", "ffn_r64", "i2v_ffn_r64")  # [i2v_][ffn_]r<rank>: image context in attn2, adapters on ffn.net.0.proj / ffn.net.2 as well
+TI = 257  # tests/test_gpu_wan_i2v.py
 EXACT = ("out", "dx", "denc")
 ATOMIC_BOUND = 2e-6
 
@@ -30,9 +35,13 @@ def _block(geom, mode, dev):
     from finetrainers_amd.wan import MI355XWanBlock
 
     D, H, F = geom
-    blk = MI355XWanBlock(dim=D, heads=H, ffn_dim=F, device=dev)
+    i2v, ffn = "i2v" in mode, "ffn" in mode
+    blk = MI355XWanBlock(dim=D, heads=H, ffn_dim=F, device=dev, **(dict(added_kv_proj_dim=D) if i2v else {}))
     g = torch.Generator().manual_seed(11)
-    for name, view in blk.layout.named_views(blk.flat.data).items():
+    views = blk.layout.named_views(blk.flat.data)
+    if i2v:
+        views.update(blk.img_layout.named_views(blk.img_flat.data))
+    for name, view in views.items():
         if "norm" in name and name.endswith("weight"):
             v = 1 + 0.1 * torch.randn(view.shape, generator=g)
         elif name.endswith("bias"):
@@ -43,13 +52,19 @@ def _block(geom, mode, dev):
     blk.mark_updated()
     if mode == "frozen_r0":
         blk.freeze_base()
-    elif mode in ("r32", "r64"):
-        rank = int(mode[1:])
-        blk.add_adapter(rank, float(rank))
+    elif mode != "full":
+        rank = int(mode.rsplit("r", 1)[1])
+        blk.add_adapter(rank, float(rank), **(dict(ffn=True) if ffn else {}))
         with torch.no_grad():
             blk.lora_A.data[:, :rank].copy_(torch.randn(8, rank, D, generator=g) * D ** -0.5)
-            if mode == "r64":
+            if rank == 64:
                 blk.lora_B.data[:, :, :rank].copy_(0.02 * torch.randn(8, D, rank, generator=g))
+            if ffn:  # A_1 [r, D], B_1 [F, r], A_2 [r, F], B_2 [D, r], all non-zero
+                a1, b1, a2, b2 = blk.lora_ffn
+                a1.data[:rank].copy_(torch.randn(rank, D, generator=g) * D ** -0.5)
+                b1.data[:, :rank].copy_(0.02 * torch.randn(F, rank, generator=g))
+                a2.data[:rank].copy_(torch.randn(rank, F, generator=g) * F ** -0.5)
+                b2.data[:, :rank].copy_(0.02 * torch.randn(D, rank, generator=g))
     return blk
 
 
@@ -63,15 +78,19 @@ def _inputs(B, S, T, D, dev):
     return [t.to(dev) for t in (x, enc, temb, dout, torch.cos(ang).float(), torch.sin(ang).float())]
 
 
-def _run(blk, inputs, enc_grad=True):
+def _image(B, ti, D, dev):
+    return torch.randn(B, ti, D, generator=torch.Generator().manual_seed(B * 1000 + ti + 3)).to(bf16).to(dev)
+
+
+def _run(blk, inputs, enc_grad=True, img=None):
     x, enc, temb, dout, cos, sin = inputs
     xg, eg = x.clone().requires_grad_(True), enc.clone().requires_grad_(enc_grad)
     tg = temb.float().requires_grad_(not blk.frozen)  # fp32 time projection: its gradient comes back as the fp32 modulation sums, not rounded to bf16
-    if blk.lora_A is not None:
-        blk.lora_A.grad = blk.lora_B.grad = None
+    for p in blk.lora_parameters():
+        p.grad = None
     if not blk.frozen:
         blk.zero_grad_flat()
-    out = blk(xg, eg, tg, (cos, sin))
+    out = blk(xg, eg, tg, (cos, sin), **(dict(encoder_hidden_states_image=img) if img is not None else {}))
     out.backward(dout)
     torch.cuda.synchronize()
     res = {"out": out.detach(), "dx": xg.grad}
@@ -82,6 +101,8 @@ def _run(blk, inputs, enc_grad=True):
         res.update({f"grad.{n}": v for n, v in blk.named_grads().items()})
     if blk.lora_A is not None:
         res["lora_A.grad"], res["lora_B.grad"] = blk.lora_A.grad, blk.lora_B.grad
+    if blk.lora_ffn is not None:
+        res.update({f"lora_ffn.{n}.grad": p.grad for n, p in zip(("A1", "B1", "A2", "B2"), blk.lora_ffn)})
     return {k: v.detach().cpu().clone() for k, v in res.items()}
 
 
@@ -90,17 +111,22 @@ def collect():
     results = {}
     for geom, B, S, T in SHAPES:
         inputs = _inputs(B, S, T, geom[0], dev)
-        for mode in MODES:
+        for mode in MODES + tuple(m for m in WIDE_MODES if geom == SMALL or m == "ffn_r64"):
             blk = _block(geom, mode, dev)
+            img = _image(B, TI, geom[0], dev) if "i2v" in mode else None
             variants = [("", {})]
             if mode == "r64" and (geom, S) == (SMALL, 48):
                 variants += [("+ckpt", dict(ckpt=True)), ("+frozen_text", dict(enc_grad=False))]
+            if mode == "i2v_r32" and S == 48:
+                variants += [("+ti0", dict(ti0=True))]
+            if mode == "i2v_ffn_r64" and S == 48:
+                variants += [("+ckpt", dict(ckpt=True))]
             for tag, kw in variants:
                 for native in (True, False):
                     blk.native = native
                     blk.gradient_checkpointing = bool(kw.get("ckpt", False))
                     case = f"D{geom[0]}.B{B}.S{S}.T{T}/{mode}{tag}/{'native' if native else 'python'}"
-                    for k, v in _run(blk, inputs, enc_grad=kw.get("enc_grad", True)).items():
+                    for k, v in _run(blk, inputs, enc_grad=kw.get("enc_grad", True), img=img[:, :0] if kw.get("ti0") else img).items():
                         results[f"{case}/{k}"] = v
             del blk
     return results
