@@ -141,7 +141,7 @@ class WanLoraBlockWeights(Structure):
 class WanLoraFfnBlockConfig(Structure):
     """include/ftmi355.h: ftmi_wan_lora_ffn_block_config."""
 
-    _fields_ = WanBlockConfig._fields_ + [("r", c_int), ("lora_scale", c_float), ("TI", c_int), ("ffn", c_int)]
+    _fields_ = WanBlockConfig._fields_ + [("r", c_int), ("lora_scale", c_float), ("TI", c_int), ("ffn", c_int), ("TI2", c_int)]
 
 
 class WanLoraFfnBlockWeights(Structure):
@@ -173,7 +173,7 @@ class WanSampleConfig(Structure):
 
     _fields_ = [("geo", WanSampleGeometry), ("T", c_int), ("TI", c_int), ("D", c_int), ("heads", c_int), ("ffn_dim", c_int), ("L", c_int), ("eps", c_float),
                 ("gemm_variant", c_int), ("r", c_int), ("lora_scale", c_float), ("ffn", c_int), ("patch_fold", c_int), ("patch_r", c_int),
-                ("patch_scale", c_float), ("steps", c_int), ("guidance", c_float)]
+                ("patch_scale", c_float), ("steps", c_int), ("guidance", c_float), ("TI2", c_int)]
 
 
 class WanSampleWeights(Structure):
@@ -282,6 +282,8 @@ _SIGS = {
     "ftmi_attn_bwd": (c_int, [POINTER(AttnDesc)] + [c_void_p] * 12),
     "ftmi_attn_ctx2_fwd": (c_int, [POINTER(AttnDesc)] + [c_void_p] * 7),
     "ftmi_attn_ctx2_dq": (c_int, [POINTER(AttnDesc)] + [c_void_p] * 8),
+    "ftmi_attn_ctx2w_fwd": (c_int, [POINTER(AttnDesc)] + [c_void_p] * 7),
+    "ftmi_attn_ctx2w_dq": (c_int, [POINTER(AttnDesc)] + [c_void_p] * 8),
     "ftmi_linear_lora_fwd": (c_int, [c_int, c_int, c_int, c_int, c_float] + [c_void_p] * 7 + [c_int, c_void_p]),
     "ftmi_linear_lora_bwd": (c_int, [c_int, c_int, c_int, c_int, c_float] + [c_void_p] * 10 + [c_int, c_void_p]),
     "ftmi_gemm_nt_plan": (c_int, [c_int, c_int, c_int, c_int, c_int]),
@@ -421,6 +423,8 @@ _EXPERIMENTAL_SIGS = {
     "ftmi_gemm_sk_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int)]),
     "ftmi_gemm_sk_status": (c_int, []),
     "ftmi_gemm_sk_trace": (c_int, [POINTER(ctypes.c_ulonglong), c_int]),
+    "ftmi_attn_ctx2w1_fwd": (c_int, [POINTER(AttnDesc)] + [c_void_p] * 7),
+    "ftmi_attn_ctx2w1_dq": (c_int, [POINTER(AttnDesc)] + [c_void_p] * 8),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -255,6 +255,48 @@ int ftmi_attn_ctx2_dq(const ftmi_attn_desc* desc, const void* q, const void* k, 
     return attn_ctx2_dq(a, (const bf16_t*)dq_first, (hipStream_t)stream);
 }
 
+int ftmi_attn_ctx2w_fwd(const ftmi_attn_desc* desc, const void* q, const void* k, const void* v, const void* out_first, void* out, float* lse,
+                        ftmi_stream stream) {
+    AttnArgs a;
+    int rc = fill_attn(desc, a);
+    if (rc) return rc;
+    if (!q || !k || !v || !out_first || !out || !lse) return set_error(FTMI_ERR_INVALID, "ftmi_attn_ctx2w_fwd: null tensor");
+    a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (bf16_t*)out; a.lse2 = lse;
+    return attn_ctx2w_fwd(a, (const bf16_t*)out_first, (hipStream_t)stream);
+}
+
+int ftmi_attn_ctx2w_dq(const ftmi_attn_desc* desc, const void* q, const void* k, const void* v, const float* lse, const void* dout, const void* dq_first,
+                       void* dq, ftmi_stream stream) {
+    AttnArgs a;
+    int rc = fill_attn(desc, a);
+    if (rc) return rc;
+    if (!q || !k || !v || !lse || !dout || !dq_first || !dq) return set_error(FTMI_ERR_INVALID, "ftmi_attn_ctx2w_dq: null tensor");
+    a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.lse2 = (float*)lse; a.dout = (const bf16_t*)dout; a.dq = (bf16_t*)dq;
+    return attn_ctx2w_dq(a, (const bf16_t*)dq_first, (hipStream_t)stream);
+}
+
+#ifdef FTMI_EXPERIMENTAL
+int ftmi_attn_ctx2w1_fwd(const ftmi_attn_desc* desc, const void* q, const void* k, const void* v, const void* out_first, void* out, float* lse,
+                         ftmi_stream stream) {
+    AttnArgs a;
+    int rc = fill_attn(desc, a);
+    if (rc) return rc;
+    if (!q || !k || !v || !out_first || !out || !lse) return set_error(FTMI_ERR_INVALID, "ftmi_attn_ctx2w1_fwd: null tensor");
+    a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (bf16_t*)out; a.lse2 = lse;
+    return attn_ctx2w1_fwd(a, (const bf16_t*)out_first, (hipStream_t)stream);
+}
+
+int ftmi_attn_ctx2w1_dq(const ftmi_attn_desc* desc, const void* q, const void* k, const void* v, const float* lse, const void* dout, const void* dq_first,
+                        void* dq, ftmi_stream stream) {
+    AttnArgs a;
+    int rc = fill_attn(desc, a);
+    if (rc) return rc;
+    if (!q || !k || !v || !lse || !dout || !dq_first || !dq) return set_error(FTMI_ERR_INVALID, "ftmi_attn_ctx2w1_dq: null tensor");
+    a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.lse2 = (float*)lse; a.dout = (const bf16_t*)dout; a.dq = (bf16_t*)dq;
+    return attn_ctx2w1_dq(a, (const bf16_t*)dq_first, (hipStream_t)stream);
+}
+#endif
+
 int ftmi_gemm_nt_plan(int M, int N, int K, int K2, int epilogue) { return gemm_nt_plan(M, N, K, K2, epilogue); }
 
 int ftmi_reload_switches(void) { return EnvSwitch::reload_all(); }

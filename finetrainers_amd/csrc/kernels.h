@@ -216,6 +216,14 @@ int attn_bwd(const AttnArgs& a, hipStream_t st);  // delta pre-pass + dK/dV kern
 // a.o = bf(o_t + bf(softmax(q k^T) v)), a.lse2 written;  a.dq = bf(dq_t + bf(dq of this context)), a.lse2 / a.dout read.  o_t / dq_t use a.o's / a.dq's strides
 int attn_ctx2_fwd(const AttnArgs& a, const bf16_t* o_t, hipStream_t st);
 int attn_ctx2_dq(const AttnArgs& a, const bf16_t* dq_t, hipStream_t st);
+// the wide pair: the same contract for 1 .. 640 keys (two images: Wan first/last-frame), tile t + 1 staged under tile t; for Sk <= 320 the bits of the pair above
+int attn_ctx2w_fwd(const AttnArgs& a, const bf16_t* o_t, hipStream_t st);
+int attn_ctx2w_dq(const AttnArgs& a, const bf16_t* dq_t, hipStream_t st);
+#ifdef FTMI_EXPERIMENTAL
+// lab yardstick: the wide loop with the single-buffered staging of the narrow pair (profiles/wan_flf_ctx2.txt)
+int attn_ctx2w1_fwd(const AttnArgs& a, const bf16_t* o_t, hipStream_t st);
+int attn_ctx2w1_dq(const AttnArgs& a, const bf16_t* dq_t, hipStream_t st);
+#endif
 
 // ---- row-wise / elementwise ------------------------------------------------------------------------
 // ada[l][b][slot][D]: slots 0..5 = table[i] + temb[b][i] (shift_msa, scale_msa, gate_msa, shift_mlp,

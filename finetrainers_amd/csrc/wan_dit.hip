@@ -57,6 +57,8 @@
 // -- the second attention (attn_ctx2.hip) reads the first one's output and writes the sum, so the forward adds 3 launches (29) and the backward ONE (36): the
 // image branch's dQ, which accumulates onto the text branch's.  No adapter sits on add_k_proj / add_v_proj / norm_added_k (the recipe's regex does not match
 // them): they arrive in a separate flat buffer  W_ak | W_av [2D, D], b_ak | b_av [2D], norm_added_k [D]  and nothing flows back into them or into enc_img.
+// (a second image, cfg.TI2 > 0 -- the first/last-frame model: its rows follow the first image's in enc_img, TI below then counts both and the two launches are
+// attn_ctx2w_fwd / _dq, the wide pair)
 // saved, in addition: kvi [B TI, 2D], kin [B TI, D], lse_i, o2s [B S, D] (the summed output: the input of to_out.0; o2 stays the text branch's own output,
 // which its backward needs for rowsum(dO o O)).
 #include "common.hip.h"
@@ -227,6 +229,8 @@ int check_lora_cfg(const ftmi_wan_lora_ffn_block_config& c) {
     if (c.r < 0 || (c.r % 64) != 0 || c.r > 128) return set_error(FTMI_ERR_UNSUPPORTED, "wan_lora_ffn_block: LoRA rank must be 0, 64 or 128 (pad other ranks with zeros)");
     if (c.r > 0 && c.D < 256) return set_error(FTMI_ERR_UNSUPPORTED, "wan_lora_ffn_block: adapters need a width of at least 256");
     if (c.TI < 0 || c.TI > 320) return set_error(FTMI_ERR_UNSUPPORTED, "wan_lora_ffn_block: the image context holds 0 .. 320 tokens");
+    if (c.TI2 < 0 || c.TI2 > 320) return set_error(FTMI_ERR_UNSUPPORTED, "wan_lora_ffn_block: a second image holds 0 .. 320 tokens");
+    if (c.TI2 > 0 && c.TI == 0) return set_error(FTMI_ERR_INVALID, "wan_lora_ffn_block: a second image (TI2) needs a first one (TI > 0)");
     if (c.ffn != 0 && c.ffn != 1) return set_error(FTMI_ERR_INVALID, "wan_lora_ffn_block: ffn is 0 or 1");
     if (c.ffn && c.r == 0) return set_error(FTMI_ERR_UNSUPPORTED, "wan_lora_ffn_block: feed-forward adapters take the block's rank, which is 0");
     // (the split down-projection contracts over at least 256 columns: XA_2 = s act A_2^T and dXA_1 = s dpre B_1 contract over F)
@@ -236,12 +240,13 @@ int check_lora_cfg(const ftmi_wan_lora_ffn_block_config& c) {
 
 // the frozen base's plan of one LoRA configuration (the byte planners pass no bases)
 Bufs lora_layout(const ftmi_wan_lora_ffn_block_config& c, void* saved = nullptr, void* scratch = nullptr) {
-    return make_layout(base_cfg(c), c.r, true, saved, scratch, c.TI, c.ffn != 0);
+    return make_layout(base_cfg(c), c.r, true, saved, scratch, c.TI + c.TI2, c.ffn != 0);  // the second image's rows follow the first one's
 }
 
 // the image context of attn2: TI tokens enc_img [B, TI, D] and the frozen flat buffer  add_k | add_v weight [2D, D], their biases [2D], norm_added_k [D]
 struct ImgCtx {
-    int TI = 0;
+    int TI = 0;         // all image tokens of a sample: both images of a first/last-frame model
+    bool wide = false;  // a second image: the wide second-context kernels (attn_ctx2w_*), whatever the token count
     const bf16_t* params = nullptr;
     const bf16_t* enc = nullptr;
 };
@@ -434,7 +439,7 @@ int block_forward(const Block& k, bf16_t* out) {
         WanRowArgs a = row_args(L.kvi, 2 * D, L.kin, D, Mi, D, TI, eps);
         a.w = ip + 2 * (size_t)D * D + 2 * D;
         FTMI_TRY(wan_rms_rope_fwd(a, st));
-        FTMI_TRY(attn_ctx2_fwd(attn_args(c, L.q2n, L.kin, L.kvi, 2 * D, L.o2s, L.lse_i, S, TI), L.o2, st));
+        FTMI_TRY((k.img.wide ? attn_ctx2w_fwd : attn_ctx2_fwd)(attn_args(c, L.q2n, L.kin, L.kvi, 2 * D, L.o2s, L.lse_i, S, TI), L.o2, st));
         o2 = L.o2s;
     }
     bf16_t* a2 = L.f;  // (the feed-forward output buffer doubles as the staging of o2 W_o2^T + b: it is consumed by the next launch)
@@ -497,7 +502,7 @@ int block_backward(const Block& k, const bf16_t* dout, bf16_t* dx, bf16_t* denc)
     FTMI_TRY(proj_bwd(k, k.img.TI > 0 ? L.o2s : L.o2, L.dx2, M, D, D, k.t.o2, attn_adp(k, 7, 1, L.xa_o2), L.do2, G(O.w_o2), G(O.b_o2)));
     FTMI_TRY(attn_bwd(attn_bwd_args(attn_args(c, L.q2n, L.k2n, L.kv2, 2 * D, L.o2, L.lse2, S, T), L.do2, L.dq2n, L.dk2n, L.dkv2, L.delta), st));
     if (k.img.TI > 0)  // the image branch's dQ, added onto the text branch's in place (its keys and values are frozen: no dK, dV)
-        FTMI_TRY(attn_ctx2_dq(attn_bwd_args(attn_args(c, L.q2n, L.kin, L.kvi, 2 * D, L.o2s, L.lse_i, S, k.img.TI), L.do2, L.dq2n, nullptr, L.dkv2, nullptr), L.dq2n, st));
+        FTMI_TRY((k.img.wide ? attn_ctx2w_dq : attn_ctx2_dq)(attn_bwd_args(attn_args(c, L.q2n, L.kin, L.kvi, 2 * D, L.o2s, L.lse_i, S, k.img.TI), L.do2, L.dq2n, nullptr, L.dkv2, nullptr), L.dq2n, st));
     {
         WanRowArgs a = row_args(L.q2, D, L.dq2, D, M, D, S, eps);
         a.w = P(O.nq2); a.dy = L.dq2n; a.ld_dy = D; a.red2 = G(O.nq2);
@@ -597,7 +602,7 @@ Adp ffn_adp(const ftmi_wan_lora_ffn_block_config& c, const bf16_t* sp, const bf1
 Block lora_block(const ftmi_wan_lora_ffn_block_config& c, const ftmi_wan_lora_ffn_block_weights& w, const Bufs& L, const bf16_t* img_params, const bf16_t* x,
                  const bf16_t* enc, const bf16_t* enc_img, const float* mod, const float* rope_cos, const float* rope_sin, hipStream_t st) {
     Block k = make_block(base_cfg(c), w.base.params, L, x, enc, mod, rope_cos, rope_sin, st);
-    k.img.TI = c.TI; k.img.params = img_params; k.img.enc = enc_img;
+    k.img.TI = c.TI + c.TI2; k.img.wide = c.TI2 > 0; k.img.params = img_params; k.img.enc = enc_img;
     k.lo.r = c.r; k.lo.s = c.lora_scale;
     return k;
 }

@@ -47,7 +47,7 @@ int make_plan(const ftmi_wan_sample_config& c, Plan& p) {
     if (p.M > 0x7fffffffL) return set_error(FTMI_ERR_UNSUPPORTED, "wan_sample: too many tokens");
     ftmi_wan_lora_ffn_block_config& b = p.bc;
     b.B = g.P * g.B; b.S = (int)p.S; b.T = c.T; b.D = c.D; b.H = c.heads; b.F = c.ffn_dim; b.eps = c.eps; b.gemm_variant = c.gemm_variant;
-    b.r = c.r; b.lora_scale = c.lora_scale; b.TI = c.TI; b.ffn = c.ffn;
+    b.r = c.r; b.lora_scale = c.lora_scale; b.TI = c.TI; b.TI2 = c.TI2; b.ffn = c.ffn;
     p.saved_bytes = wan_lora_ffn_block_saved_bytes(b);
     p.scratch_bytes = wan_lora_ffn_block_scratch_bytes(b);
     if (!p.saved_bytes || !p.scratch_bytes) return FTMI_ERR_UNSUPPORTED;  // (the block's planner set the message)

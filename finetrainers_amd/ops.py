@@ -92,9 +92,8 @@ def attn_bwd(q, k, v, out, lse, dout, key_bias=None, scale=None, dv_out=None, dq
     return dq, dk, dv
 
 
-def attn_ctx2_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out_first: torch.Tensor, scale: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Second context of a two-context cross-attention (head_dim 128, at most 320 keys), run after ``attn_fwd`` on the first one: returns
-    (bf16(out_first + bf16(softmax(q k^T scale) v)) laid out like ``out_first``, lse [B, H, Sq] of this context)."""
+def _ctx2_fwd(entry: str, q, k, v, out_first, scale):
+    """The second-context forward through one C entry of the ``ftmi_attn_ctx2*_fwd`` family (narrow, wide; the tools' lab variant)."""
     for n, t in (("query", q), ("key", k), ("value", v), ("out_first", out_first)):
         require_gpu_tensor(t, n, bf16)
     B, H, Sq, d = q.shape
@@ -104,13 +103,12 @@ def attn_ctx2_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out_first: 
     out = torch.empty_strided(out_first.shape, out_first.stride(), dtype=bf16, device=q.device)
     lse = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
     desc = _desc(q, k, v, out, scale)
-    check(_lib.load().ftmi_attn_ctx2_fwd(ctypes.byref(desc), ptr(q), ptr(k), ptr(v), ptr(out_first), ptr(out), ptr(lse), stream_ptr()), "ftmi_attn_ctx2_fwd")
+    check(getattr(_lib.load(), entry)(ctypes.byref(desc), ptr(q), ptr(k), ptr(v), ptr(out_first), ptr(out), ptr(lse), stream_ptr()), entry)
     return out, lse
 
 
-def attn_ctx2_dq(q, k, v, lse, dout, dq_first, scale=None, inplace: bool = False):
-    """dQ of the second context added onto the first context's: bf16(dq_first + bf16(dq of this context)), laid out like ``dq_first`` (``inplace``: written
-    into it).  There is no dK / dV (the second context's keys and values are frozen where this is used)."""
+def _ctx2_dq(entry: str, q, k, v, lse, dout, dq_first, scale, inplace):
+    """The second-context dQ through one C entry of the ``ftmi_attn_ctx2*_dq`` family."""
     for n, t in (("query", q), ("key", k), ("value", v), ("dout", dout), ("dq_first", dq_first)):
         require_gpu_tensor(t, n, bf16)
     require_gpu_tensor(lse, "lse", torch.float32)
@@ -124,8 +122,31 @@ def attn_ctx2_dq(q, k, v, lse, dout, dq_first, scale=None, inplace: bool = False
         raise ValueError("attn_ctx2_dq: lse must be the contiguous fp32 [B, H, Sq] tensor attn_ctx2_fwd returned")
     dq = dq_first if inplace else torch.empty_strided(dq_first.shape, dq_first.stride(), dtype=bf16, device=q.device)
     desc = _desc(q, k, v, None, scale, dout, dq)
-    check(_lib.load().ftmi_attn_ctx2_dq(ctypes.byref(desc), ptr(q), ptr(k), ptr(v), ptr(lse), ptr(dout), ptr(dq_first), ptr(dq), stream_ptr()), "ftmi_attn_ctx2_dq")
+    check(getattr(_lib.load(), entry)(ctypes.byref(desc), ptr(q), ptr(k), ptr(v), ptr(lse), ptr(dout), ptr(dq_first), ptr(dq), stream_ptr()), entry)
     return dq
+
+
+def attn_ctx2_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out_first: torch.Tensor, scale: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Second context of a two-context cross-attention (head_dim 128, at most 320 keys), run after ``attn_fwd`` on the first one: returns
+    (bf16(out_first + bf16(softmax(q k^T scale) v)) laid out like ``out_first``, lse [B, H, Sq] of this context)."""
+    return _ctx2_fwd("ftmi_attn_ctx2_fwd", q, k, v, out_first, scale)
+
+
+def attn_ctx2_dq(q, k, v, lse, dout, dq_first, scale=None, inplace: bool = False):
+    """dQ of the second context added onto the first context's: bf16(dq_first + bf16(dq of this context)), laid out like ``dq_first`` (``inplace``: written
+    into it).  There is no dK / dV (the second context's keys and values are frozen where this is used)."""
+    return _ctx2_dq("ftmi_attn_ctx2_dq", q, k, v, lse, dout, dq_first, scale, inplace)
+
+
+def attn_ctx2w_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out_first: torch.Tensor, scale: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``attn_ctx2_fwd`` through the wide kernel: up to 640 keys (two images in the second context: Wan first/last-frame), the next key tile staged while the
+    current one is multiplied.  For at most 320 keys the result is ``attn_ctx2_fwd``'s, bit for bit."""
+    return _ctx2_fwd("ftmi_attn_ctx2w_fwd", q, k, v, out_first, scale)
+
+
+def attn_ctx2w_dq(q, k, v, lse, dout, dq_first, scale=None, inplace: bool = False):
+    """``attn_ctx2_dq`` through the wide kernel (up to 640 keys); ``lse`` is the tensor ``attn_ctx2w_fwd`` returned."""
+    return _ctx2_dq("ftmi_attn_ctx2w_dq", q, k, v, lse, dout, dq_first, scale, inplace)
 
 
 def gemm_nt(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, alpha: float = 1.0, epilogue: int = 0,
@@ -1167,7 +1188,7 @@ def wan_sample_workspace_bytes(cfg) -> int:
 
 def wan_sample(cfg, weights, cols, x, tproj, head_shift, head_scale, enc, enc_img, rope, sigmas, workspace=None) -> None:
     """The whole denoising loop in ONE call (ftmi_wan_sample), in place on ``x`` / ``cols`` (as ``wan_sample_init`` wrote them).  tproj bf16 [steps, 6 D];
-    head_shift / head_scale fp32 [steps, D]; enc bf16 [P B, T, D] (unconditional rows first); enc_img bf16 [P B, TI, D] or None; rope = (cos, sin) fp32 [S, 64];
+    head_shift / head_scale fp32 [steps, D]; enc bf16 [P B, T, D] (unconditional rows first); enc_img bf16 [P B, TI + TI2, D] or None; rope = (cos, sin) fp32 [S, 64];
     sigmas fp32 [steps + 1] on the device.  ``workspace``: a uint8 GPU tensor of at least ``wan_sample_workspace_bytes(cfg)`` (allocated when None)."""
     geo, n, D = cfg.geo, cfg.steps, cfg.D
     _wan_sample_buffers(geo, x, cols, "wan_sample")
@@ -1176,7 +1197,7 @@ def wan_sample(cfg, weights, cols, x, tproj, head_shift, head_scale, enc, enc_im
             ("enc", enc, bf16, (rows, cfg.T, D)), ("rope cos", rope[0], torch.float32, (S, 64)), ("rope sin", rope[1], torch.float32, (S, 64)),
             ("sigmas", sigmas, torch.float32, (n + 1,))]
     if cfg.TI > 0:
-        want.append(("enc_img", enc_img, bf16, (rows, cfg.TI, D)))
+        want.append(("enc_img", enc_img, bf16, (rows, cfg.TI + cfg.TI2, D)))
     for name, t, dt, shape in want:
         if t is None or not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
             raise ValueError(f"wan_sample: {name} must be a contiguous {dt} {shape} GPU tensor, got {None if t is None else tuple(t.shape)}")

@@ -247,9 +247,12 @@ def _block_forward(blk: "MI355XWanBlock", x, enc, mod, rope, lora: _Lora, need_o
     kvi = kin = lse_i = o2s = None
     if enc_img is not None and enc_img.shape[1] > 0:  # the image tokens' frozen keys and values; their attention is summed onto the text branch's output
         TI, IP = enc_img.shape[1], blk.img_param
+        blk.first_image_tokens(enc_img, B)  # (refuses rows that cannot hold the declared second image, like the C call's configuration)
         kvi = ops.gemm_nt(enc_img.view(B * TI, D), IP("w_kvi"), IP("b_kvi"))
         kin = ops.wan_rms_rope(kvi[:, :D], IP("attn2.norm_added_k.weight"), TI, eps=eps)
-        o2s, lse_i = ops.attn_ctx2_fwd(heads(q2n, S), heads(kin, TI), heads(kvi[:, D:], TI), o2)
+        # (TI counts both images of a first/last-frame block, whose second context goes through the wide kernels)
+        ctx2_fwd = ops.attn_ctx2w_fwd if blk.second_image_tokens > 0 else ops.attn_ctx2_fwd
+        o2s, lse_i = ctx2_fwd(heads(q2n, S), heads(kin, TI), heads(kvi[:, D:], TI), o2)
     a2, xa_o2 = lin(tok(o2 if o2s is None else o2s), P("attn2.to_out.0.weight"), P("attn2.to_out.0.bias"), 7, 1)
     x2 = ops.wan_gate_res(x1, a2, S)
     # feed-forward
@@ -314,7 +317,8 @@ def _block_backward(blk: "MI355XWanBlock", acts: _Acts, x, enc, mod, rope, dout,
     dq2n, dk2n, _ = ops.attn_bwd(heads(c.q2n, S), heads(c.k2n, T), heads(c.kv2[:, D:], T), c.o2, c.lse2, heads(do2, S), dv_out=heads(dkv2[:, D:], T))
     if c.o2s is not None:  # the image branch's dQ, added onto the text branch's in place (frozen keys and values: no dK, dV)
         TI = c.kin.shape[0] // B
-        ops.attn_ctx2_dq(heads(c.q2n, S), heads(c.kin, TI), heads(c.kvi[:, D:], TI), c.lse_i, heads(do2, S), dq2n, inplace=True)
+        ctx2_dq = ops.attn_ctx2w_dq if blk.second_image_tokens > 0 else ops.attn_ctx2_dq
+        ctx2_dq(heads(c.q2n, S), heads(c.kin, TI), heads(c.kvi[:, D:], TI), c.lse_i, heads(do2, S), dq2n, inplace=True)
     dq2 = ops.wan_rms_rope_bwd(c.q2, P("attn2.norm_q.weight"), tok(dq2n), S, eps=eps, dweight=G("attn2.norm_q.weight"))
     ops.wan_rms_rope_bwd(c.kv2[:, :D], P("attn2.norm_k.weight"), tok(dk2n), T, eps=eps, dweight=G("attn2.norm_k.weight"), out=dkv2[:, :D])
     _linear_grads(dq2, c.n2, G("attn2.to_q.weight"), G("attn2.to_q.bias"))  # (attn2.to_q's weight gradient goes ahead of the text rows' projection)
@@ -432,7 +436,8 @@ def _grad_targets(blk: "MI355XWanBlock", lora_a, lora_b, ffn=None):
 
 class _WanLoRABlockFunction(torch.autograd.Function):
     """The block over a FROZEN base through the Python walks, text-to-video and image-to-video.  ``lora_a`` [8, r, D] / ``lora_b`` [8, D, r]: the adapters on
-    the eight attention projections; ``enc_img`` [B, TI, D]: the image context of an image-to-video block in attn2 (frozen: no gradient flows into it);
+    the eight attention projections; ``enc_img`` [B, TI, D]: the image context of an image-to-video block in attn2 (frozen: no gradient flows into it; a
+    first/last-frame block, ``second_image_tokens`` = TI2 > 0, takes [B, TI + TI2, D], the second image's rows after the first one's);
     ``fa1`` [r, D], ``fb1`` [F, r], ``fa2`` [r, F], ``fb2`` [D, r]: the adapters on ffn.net.0.proj and ffn.net.2 -- each None where the block has none.  The
     backward forms dx, denc (only if asked for) and the adapter gradients -- no base-weight gradient, no bias / norm / modulation reduction, and it keeps
     neither a1 nor f (n3 and act only for the feed-forward adapters)."""
@@ -473,7 +478,8 @@ class _WanLoRABlockNativeFunction(torch.autograd.Function):
     def _args(blk: "MI355XWanBlock", B: int, S: int, T: int, lora_a, lora_b, backward: bool, TI: int = 0, ffn=None):
         """(config, weights, the tensors whose pointers the weights hold: keep them alive over the call)."""
         cfg = WanLoraFfnBlockConfig(B=B, S=S, T=T, D=blk.dim, H=blk.heads, F=blk.ffn_dim, eps=float(blk.eps), gemm_variant=8,
-                                    r=0 if lora_a is None else int(lora_a.shape[1]), lora_scale=float(blk.lora_scale), TI=TI, ffn=int(ffn is not None))
+                                    r=0 if lora_a is None else int(lora_a.shape[1]), lora_scale=float(blk.lora_scale), TI=TI, ffn=int(ffn is not None),
+                                    TI2=blk.second_image_tokens if TI > 0 else 0)
         wf = WanLoraFfnBlockWeights()
         w = wf.base
         params = blk._params()
@@ -500,7 +506,7 @@ class _WanLoRABlockNativeFunction(torch.autograd.Function):
     def _forward_call(blk, x, enc, mod, rope_cos, rope_sin, lora_a, lora_b, out, enc_img=None, ffn=None):
         B, S, _ = x.shape
         lib = _lib.load()
-        TI = 0 if enc_img is None else enc_img.shape[1]
+        TI = 0 if enc_img is None else blk.first_image_tokens(enc_img, B)
         cfg, w, keep = _WanLoRABlockNativeFunction._args(blk, B, S, enc.shape[1], lora_a, lora_b, backward=False, TI=TI, ffn=ffn)
         saved = torch.empty(_planned(lib.ftmi_wan_lora_ffn_block_saved_bytes(ctypes.byref(cfg))), dtype=torch.uint8, device=x.device)
         scratch = _native_scratch(x.device, _planned(lib.ftmi_wan_lora_ffn_block_scratch_bytes(ctypes.byref(cfg))))
@@ -529,7 +535,7 @@ class _WanLoRABlockNativeFunction(torch.autograd.Function):
         if ctx.recompute:
             saved = _WanLoRABlockNativeFunction._forward_call(blk, x, enc, mod, rope[0], rope[1], lora_a, lora_b, None, enc_img, ffn)
         B, S, _ = x.shape
-        TI = 0 if enc_img is None else enc_img.shape[1]
+        TI = 0 if enc_img is None else blk.first_image_tokens(enc_img, B)
         dout = dout.contiguous()
         own, ga, gb, gf = _grad_targets(blk, lora_a, lora_b, ffn)
         lib = _lib.load()
@@ -557,8 +563,11 @@ class MI355XWanBlock(nn.Module):
     native = os.environ.get("FTMI_NATIVE_BLOCKS", "1") != "0"
 
     def __init__(self, dim: int = 1536, heads: int = 12, ffn_dim: int = 8960, eps: float = 1e-6, device: Optional[torch.device] = None,
-                 added_kv_proj_dim: Optional[int] = None):
+                 added_kv_proj_dim: Optional[int] = None, second_image_tokens: int = 0):
         super().__init__()
+        if second_image_tokens < 0 or second_image_tokens > 320 or (second_image_tokens and added_kv_proj_dim is None):
+            raise ValueError("Wan first/last-frame: the second image holds 0 .. 320 tokens and needs the image context (added_kv_proj_dim)")
+        self.second_image_tokens = int(second_image_tokens)  # TI2 of ftmi_wan_lora_ffn_block_config: the last rows of enc_img [B, TI + TI2, D]
         if added_kv_proj_dim is not None and added_kv_proj_dim != dim:
             raise ValueError("Wan image-to-video: added_kv_proj_dim is the block width (the image embedder projects to it)")
         if dim % heads != 0 or dim // heads != 128:
@@ -599,6 +608,15 @@ class MI355XWanBlock(nn.Module):
 
     def _img_params(self) -> torch.Tensor:
         return self.img_flat.data
+
+    def first_image_tokens(self, enc_img: torch.Tensor, batch: Optional[int] = None) -> int:
+        """TI of the C call for ``enc_img`` [B, TI + TI2, D]; ``batch``: the B its rows are read with."""
+        n = int(enc_img.shape[1])
+        if batch is not None and (enc_img.dim() != 3 or enc_img.shape[0] != batch or enc_img.shape[2] != self.dim or not enc_img.is_contiguous()):
+            raise ValueError(f"Wan block: the image context must be a contiguous [{batch}, tokens, {self.dim}] tensor, got {tuple(enc_img.shape)}")
+        if n > 0 and n <= self.second_image_tokens:
+            raise ValueError(f"Wan first/last-frame block: {n} image tokens, of which {self.second_image_tokens} belong to the second image")
+        return n - self.second_image_tokens if n > 0 else 0
 
     def img_param(self, name: str) -> torch.Tensor:
         return self.img_layout.view(self.img_flat.data, name)

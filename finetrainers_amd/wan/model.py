@@ -43,6 +43,25 @@ class WanTransformerConfig:
     eps: float = 1e-6
     image_dim: Optional[int] = None
     rope_max_seq_len: int = 1024
+    # first/last-frame image-to-video (Wan2.1-FLF2V): the image embedder holds ``pos_embed`` [1, pos_embed_seq_len, image_dim] and attn2's image context is
+    # the tokens of TWO images (2 x 257 = 514)
+    pos_embed_seq_len: Optional[int] = None
+
+    def __post_init__(self):
+        n = self.pos_embed_seq_len
+        if n is None:
+            return
+        if self.image_dim is None:
+            raise ValueError("pos_embed_seq_len (first/last-frame) belongs to an image-to-video model: image_dim is missing")
+        if not isinstance(n, int) or n <= 0 or n % 2 != 0:
+            raise ValueError(f"pos_embed_seq_len must be a positive even number (the tokens of two images), got {n}")
+        if n > 640:
+            raise ValueError(f"pos_embed_seq_len = {n}: the image context of attn2 holds at most 640 tokens (two images of up to 320)")
+
+    @property
+    def second_image_tokens(self) -> int:
+        """TI2 of the block: the tokens of the last frame's image (0: a single image)."""
+        return 0 if self.pos_embed_seq_len is None else self.pos_embed_seq_len // 2
 
     @property
     def inner_dim(self) -> int:
@@ -115,6 +134,8 @@ class RootLayout:
             Di, ie = cfg.image_dim, "condition_embedder.image_embedder."
             self.entries += [(ie + "norm1.weight", (Di,)), (ie + "norm1.bias", (Di,)), (ie + "ff.net.0.proj.weight", (Di, Di)), (ie + "ff.net.0.proj.bias", (Di,)),
                              (ie + "ff.net.2.weight", (D, Di)), (ie + "ff.net.2.bias", (D,)), (ie + "norm2.weight", (D,)), (ie + "norm2.bias", (D,))]
+            if cfg.pos_embed_seq_len is not None:  # appended: without it no offset moves
+                self.entries.append((ie + "pos_embed", (1, cfg.pos_embed_seq_len, Di)))
         self.offsets: Dict[str, Tuple[int, Tuple[int, ...]]] = {}
         off = 0
         for name, shape in self.entries:
@@ -248,7 +269,8 @@ class MI355XWanTransformer3DModel(nn.Module):
         self.root = nn.Parameter(torch.zeros(self.root_layout.total, dtype=bf16, device=dev), requires_grad=False)
         self.root_grad: Optional[torch.Tensor] = None
         self._root_src: Optional[torch.Tensor] = None  # sharded training: the all-gathered root parameters
-        self.blocks = nn.ModuleList([MI355XWanBlock(c.inner_dim, c.num_attention_heads, c.ffn_dim, c.eps, dev, added_kv_proj_dim=c.inner_dim if c.image_dim is not None else None)
+        self.blocks = nn.ModuleList([MI355XWanBlock(c.inner_dim, c.num_attention_heads, c.ffn_dim, c.eps, dev, added_kv_proj_dim=c.inner_dim if c.image_dim is not None else None,
+                                                    second_image_tokens=c.second_image_tokens)
                                      for _ in range(c.num_layers)])
         self._rope_cache: Dict[Tuple[int, int, int], Tuple[torch.Tensor, torch.Tensor]] = {}
         self._anchor = torch.zeros(1, dtype=bf16, device=dev, requires_grad=True)  # tells autograd that the graph has trainable inputs
@@ -507,14 +529,27 @@ class MI355XWanTransformer3DModel(nn.Module):
     @torch.no_grad()
     def _embed_image(self, image_embeds: torch.Tensor) -> torch.Tensor:
         """``condition_embedder.image_embedder`` on [B, TI, image_dim] (frozen; B x 257 rows once per step, plain torch ops at the reference's rounding
-        points): FP32LayerNorm -> Linear -> exact GELU -> Linear -> FP32LayerNorm."""
+        points): FP32LayerNorm -> Linear -> exact GELU -> Linear -> FP32LayerNorm.
+
+        First/last-frame (``config.pos_embed_seq_len`` = P, two images of P / 2 tokens): [upstream] WanImageEmbedding.forward first views its input as
+        [-1, P, image_dim] and adds ``pos_embed`` in the model's dtype, x = bf(x + pos_embed).  Accepted are therefore [B, P, image_dim] (a sample's first
+        image, then its last) and [2B, P / 2, image_dim], whose rows 2b and 2b + 1 the view pairs as sample b; the result is [B, P, D] either way.  NOTE: the
+        reference's processor stacks ALL first frames and then ALL last frames (finetrainers/models/wan/base_specification.py:201, ``torch.stack([image, last_image], dim=0)``),
+        which agrees with this pairing only at batch size 1 -- the recipe's batch.  The rows are taken as upstream takes them; nothing is reordered here."""
         F_, ie = torch.nn.functional, "condition_embedder.image_embedder."
         P = lambda n: self.rparam(ie + n)
         x = image_embeds.to(self.device, bf16)
         if x.dim() != 3 or x.shape[-1] != self.config.image_dim:
             raise ValueError(f"encoder_hidden_states_image must be [B, tokens, {self.config.image_dim}]")
-        if x.shape[1] > 320:
-            raise NotImplementedError("the image context holds at most 320 tokens (257 CLIP tokens; the first/last-frame form is not covered)")
+        n_pos = self.config.pos_embed_seq_len
+        if n_pos is None:
+            if x.shape[1] > 320:
+                raise NotImplementedError("the image context of a model without pos_embed_seq_len holds at most 320 tokens (257 CLIP tokens of one image)")
+        else:
+            if x.shape[1] != n_pos and not (2 * x.shape[1] == n_pos and x.shape[0] % 2 == 0):
+                raise ValueError(f"first/last-frame image embedder: got {x.shape[1]} tokens per row, pos_embed_seq_len is {n_pos} "
+                                 f"([B, {n_pos}, image_dim] or [2B, {n_pos // 2}, image_dim])")
+            x = x.reshape(-1, n_pos, x.shape[-1]) + P("pos_embed")  # bf16 + bf16: one rounding, as upstream
         ln = lambda t, n: F_.layer_norm(t.float(), (t.shape[-1],), P(n + ".weight").float(), P(n + ".bias").float(), 1e-5).to(bf16)
         x = F_.gelu(F_.linear(ln(x, "norm1"), P("ff.net.0.proj.weight"), P("ff.net.0.proj.bias")))
         return ln(F_.linear(x, P("ff.net.2.weight"), P("ff.net.2.bias")), "norm2").contiguous()
@@ -549,6 +584,10 @@ class MI355XWanTransformer3DModel(nn.Module):
             mod = self.rparam("scale_shift_table") + temb.unsqueeze(1)  # [B, 2, D] bf16
             shift, scale = mod[:, 0].float(), (1 + mod[:, 1]).float() - 1
             enc_img = None if encoder_hidden_states_image is None else self._embed_image(encoder_hidden_states_image)
+            if enc_img is not None and enc_img.shape[0] != B:  # (the blocks read B rows of it: a [2B', L] input of a first/last-frame model makes B' rows)
+                raise ValueError(f"encoder_hidden_states_image {tuple(encoder_hidden_states_image.shape)} makes {enc_img.shape[0]} image rows of {enc_img.shape[1]} tokens "
+                                 f"for a batch of {B}" + ("" if c.pos_embed_seq_len is None else
+                                                          f" (pos_embed_seq_len {c.pos_embed_seq_len}: [B, {c.pos_embed_seq_len}, image_dim] or [2B, {c.pos_embed_seq_len // 2}, image_dim])"))
         for blk in self.blocks:
             x = blk(x, enc, tproj, rope, enc_img)
         y = _LnModFunction.apply(x, shift, scale, c.eps)
@@ -574,7 +613,9 @@ class MI355XWanTransformer3DModel(nn.Module):
     def forward(self, hidden_states, timestep, encoder_hidden_states, encoder_hidden_states_image=None, return_dict: bool = False, patch_columns=None,
                 latent_shape=None, **kwargs):
         """``patch_columns`` (LoRA training of a control model): the patch embedding's GEMM operand [B S, 2 Kp] = [cols | cols] as ``ops.wan_control_pack``
-        writes it, in place of ``hidden_states`` (then None, with ``latent_shape`` = (B, F, H, W) of the latents)."""
+        writes it, in place of ``hidden_states`` (then None, with ``latent_shape`` = (B, F, H, W) of the latents).  ``encoder_hidden_states_image``
+        (image-to-video): the CLIP tokens [B, TI, image_dim]; of a first/last-frame model (``config.pos_embed_seq_len``) [B, TI + TI2, image_dim] or
+        [2B, TI, image_dim], see ``_embed_image`` -- every block's attn2 then attends to TI + TI2 = pos_embed_seq_len image keys."""
         c = self.config
         if (encoder_hidden_states_image is not None) != (c.image_dim is not None):
             raise NotImplementedError("encoder_hidden_states_image goes with an image-to-video model (config.image_dim), and such a model needs it")

@@ -112,9 +112,14 @@ class MI355XWanLatentSampler:
                                        po=tr.root_layout.offsets["proj_out.weight"][1][0])
 
     def c_arguments(self, geo, T: int, TI: int, steps: int, guidance_scale: float):
-        """-> (ftmi_wan_sample_config, ftmi_wan_sample_weights, the objects the two structures point into)."""
+        """-> (ftmi_wan_sample_config, ftmi_wan_sample_weights, the objects the two structures point into).  ``TI``: the image tokens of one row of enc_img; of a
+        first/last-frame model (``config.pos_embed_seq_len``) both images', whose second half goes into the structures as TI2."""
         tr = self.transformer
         c = tr.config
+        TI2 = c.second_image_tokens if TI > 0 else 0
+        if TI2 and TI != 2 * TI2:
+            raise ValueError(f"sample: a first/last-frame model takes {2 * TI2} image tokens (pos_embed_seq_len), got {TI}")
+        TI -= TI2
         S, rows = (geo.F // geo.pt) * (geo.H // geo.ph) * (geo.W // geo.pw), geo.P * geo.B
         L = len(tr.blocks)
         blocks = (_lib.WanLoraFfnBlockWeights * L)()
@@ -133,7 +138,7 @@ class MI355XWanLatentSampler:
         cfg = _lib.WanSampleConfig(geo=geo, T=T, TI=TI, D=c.inner_dim, heads=c.num_attention_heads, ffn_dim=c.ffn_dim, L=L, eps=float(c.eps), gemm_variant=8, r=r,
                                    lora_scale=float(first.lora_scale), ffn=int(first.lora_ffn is not None), patch_fold=int(fold),
                                    patch_r=int(tr.patch_lora_A.shape[0]) if fold else 0, patch_scale=float(tr.patch_lora_scale) if fold else 0.0, steps=steps,
-                                   guidance=float(guidance_scale))
+                                   guidance=float(guidance_scale), TI2=TI2)
         w = _lib.WanSampleWeights()
         w.blocks = ctypes.cast(blocks, ctypes.POINTER(_lib.WanLoraFfnBlockWeights))
         w.img_params = ctypes.cast(img, ctypes.POINTER(ctypes.c_void_p)) if TI > 0 else None
@@ -188,7 +193,12 @@ class MI355XWanLatentSampler:
         want = (B, self.extra_channels, num_frames, height, width)
         if tuple(extra.shape) != want:
             raise ValueError(f"sample: {'condition_latents' if i2v else 'control_latents'} must be {list(want)}, got {list(extra.shape)}")
-        if i2v and (image_embeds.dim() != 3 or image_embeds.shape[0] != B or image_embeds.shape[-1] != c.image_dim):
+        if i2v and c.pos_embed_seq_len is not None:  # first/last-frame: both layouts of the image embedder, see MI355XWanTransformer3DModel._embed_image
+            n = c.pos_embed_seq_len
+            if image_embeds.dim() != 3 or tuple(image_embeds.shape) not in ((B, n, c.image_dim), (2 * B, n // 2, c.image_dim)):
+                raise ValueError(f"sample: image_embeds of a first/last-frame model must be [{B}, {n}, {c.image_dim}] or [{2 * B}, {n // 2}, {c.image_dim}], "
+                                 f"got {tuple(image_embeds.shape)}")
+        elif i2v and (image_embeds.dim() != 3 or image_embeds.shape[0] != B or image_embeds.shape[-1] != c.image_dim):
             raise ValueError(f"sample: image_embeds must be [{B}, TI, {c.image_dim}], got {tuple(image_embeds.shape)}")
         return extra.to(tr.device, bf16).contiguous()
 
@@ -206,7 +216,8 @@ class MI355XWanLatentSampler:
         ``latents``.  ``latents_mean`` / ``latents_std`` ([C]: the VAE's statistics, the standard deviation ITSELF, not the 1 / std of the training
         processors) denormalise the result; without them it stays normalised.
 
-        Image-to-video: ``image_embeds`` [B, TI, image_dim] (the CLIP tokens, sent through the model's image embedder) and ``condition_latents``
+        Image-to-video: ``image_embeds`` [B, TI, image_dim] (the CLIP tokens, sent through the model's image embedder; a first/last-frame model takes
+        [B, TI + TI2, image_dim] = [B, pos_embed_seq_len, image_dim], a sample's first image and then its last, or [2B, TI, image_dim]) and ``condition_latents``
         [B, 20, F, H, W] (4 mask + 16 normalised condition channels, what the pipeline concatenates to the latents).  Control: ``control_latents``
         [B, 16, F, H, W], normalised and frame-conditioned (``validation_latents`` of the control specification does both).  These channels are constant over
         the loop: they are written into the model input once."""
@@ -226,6 +237,8 @@ class MI355XWanLatentSampler:
         enc = self.text_rows(prompt_embeds, negative_prompt_embeds if g != 1.0 else None)
         enc_img = None
         if image_embeds is not None:
+            if c.pos_embed_seq_len is not None:
+                image_embeds = image_embeds.reshape(B, c.pos_embed_seq_len, c.image_dim)
             enc_img = tr._embed_image(torch.cat([image_embeds] * geo.P, dim=0))
         tproj, shift, scale = self.step_tables(ts, geo.P * B)
         cfg, weights, keep = self.c_arguments(geo, T, 0 if enc_img is None else enc_img.shape[1], ts.numel(), g)

@@ -158,13 +158,32 @@ class MI355XWanModelSpecification(MI355XWanSpecOps):
                                         latent_condition_mask=latent_model_conditions.pop("latent_condition_mask", None),
                                         encoder_hidden_states_image=condition_model_conditions.get("encoder_hidden_states_image"))
 
+    @staticmethod
+    def condition_mask(num_frames: int, latent_height: int, latent_width: int, use_last_frame: bool, temporal_downsample: int = 4) -> torch.Tensor:
+        """The conditioning mask of ``WanImageConditioningLatentEncodeProcessor`` (base_specification.py:145-155) for one sample, [1, 4, F_latent, h, w] fp32:
+        ones on the kept pixel frames -- the first, and with ``use_last_frame`` (a first/last-frame model: config.pos_embed_seq_len) the last as well --
+        zeros on the others; the first frame repeated ``temporal_downsample`` times so that the ``num_frames`` pixel frames fold into
+        F_latent = (num_frames - 1) / temporal_downsample + 1 latent frames of ``temporal_downsample`` channels.  With the normalised condition latents it
+        makes the ``condition_latents`` [B, 20, F, H, W] of ``validation_latents``: torch.cat([mask, latents], dim=1)."""
+        if num_frames < 1 or (num_frames - 1) % temporal_downsample != 0:
+            raise ValueError(f"condition_mask: num_frames must be k * {temporal_downsample} + 1, got {num_frames}")
+        mask = torch.ones(1, 1, num_frames, latent_height, latent_width)
+        if use_last_frame:
+            mask[:, :, 1:-1] = 0
+        else:
+            mask[:, :, 1:] = 0
+        mask = torch.cat([torch.repeat_interleave(mask[:, :, :1], dim=2, repeats=temporal_downsample), mask[:, :, 1:]], dim=2)
+        return mask.view(1, -1, temporal_downsample, latent_height, latent_width).transpose(1, 2).contiguous()
+
     def validation_latents(self, transformer, prompt_embeds: torch.Tensor, negative_prompt_embeds: Optional[torch.Tensor], num_frames: int, height: int, width: int,
                            num_inference_steps: int = 50, guidance_scale: float = 5.0, generator: Optional[torch.Generator] = None, scheduler_config=None,
                            **sample_kwargs) -> torch.Tensor:
         """The denoising loop of ``validation`` (base_specification.py:495-529 runs a pipeline) over this backend's transformer, in latent space:
         ``MI355XWanLatentSampler.sample`` on the LATENT grid -> denormalised latents [B, C, F, H, W] bf16 for the reference pipeline's VAE decode.
         ``sample_kwargs``: ``latents_mean`` / ``latents_std`` (the VAE's statistics themselves), ``image_embeds`` / ``condition_latents`` for an
-        image-to-video model, ``sigmas`` / ``timesteps`` / ``latents``."""
+        image-to-video model, ``sigmas`` / ``timesteps`` / ``latents``.  A first/last-frame model (the reference hands ``last_image`` to its pipeline,
+        :524-526) takes the CLIP tokens of BOTH images, ``image_embeds`` [B, pos_embed_seq_len, image_dim] (first image, then last), and
+        ``condition_latents`` whose mask channels keep the last frame too: ``condition_mask(..., use_last_frame=True)``."""
         from .sampler import MI355XWanLatentSampler
 
         return MI355XWanLatentSampler(transformer, scheduler_config).sample(prompt_embeds, negative_prompt_embeds, num_frames, height, width,

@@ -105,6 +105,14 @@ int ftmi_attn_ctx2_fwd(const ftmi_attn_desc* desc, const void* q, const void* k,
                        ftmi_stream stream);
 int ftmi_attn_ctx2_dq(const ftmi_attn_desc* desc, const void* q, const void* k, const void* v, const float* lse, const void* dout, const void* dq_first,
                       void* dq, ftmi_stream stream);
+/* The WIDE pair: the same contract, arguments, alignment rules and error codes for 1 <= desc.Sk <= 640 (two images in the second context: the Wan first/last-frame
+ * model, 2 x 257 = 514 keys); desc.Sk > 640 is FTMI_ERR_UNSUPPORTED.  The arithmetic is the narrow pair's in the same order (64-key steps, the same online-softmax
+ * updates and rounding points); what differs is the staging: two LDS slots, the next key tile on its way while the current one is multiplied, one barrier per tile,
+ * in the dq kernel across its two walks.  For every Sk <= 320 the results are the narrow pair's bit for bit. */
+int ftmi_attn_ctx2w_fwd(const ftmi_attn_desc* desc, const void* q, const void* k, const void* v, const void* out_first, void* out, float* lse,
+                        ftmi_stream stream);
+int ftmi_attn_ctx2w_dq(const ftmi_attn_desc* desc, const void* q, const void* k, const void* v, const float* lse, const void* dout, const void* dq_first,
+                       void* dq, ftmi_stream stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Linear (+ LoRA) building block:  y = bf16( bf16(x W^T + b) + lora_scale * (x A^T) B^T ), the LoRA branch at fp32-equivalent
@@ -192,6 +200,11 @@ int ftmi_gemm_sk_status(void);
 /* Debugging aid (FTMI_SK_TRACE=1): shader-clock stamps of the last stream-K launch, out[n_workgroups][16] (start, end of each K phase,
  * hand-off waits, segment ends; 0 = unused); returns n_workgroups, 0 if nothing was traced.  Synchronises the device. */
 int ftmi_gemm_sk_trace(unsigned long long* out, int capacity);
+/* The wide second-context pair with the narrow pair's single-buffered staging (two barriers per tile): the yardstick of profiles/wan_flf_ctx2.txt. */
+int ftmi_attn_ctx2w1_fwd(const ftmi_attn_desc* desc, const void* q, const void* k, const void* v, const void* out_first, void* out, float* lse,
+                         ftmi_stream stream);
+int ftmi_attn_ctx2w1_dq(const ftmi_attn_desc* desc, const void* q, const void* k, const void* v, const float* lse, const void* dout, const void* dq_first,
+                        void* dq, ftmi_stream stream);
 #endif /* FTMI_EXPERIMENTAL */
 /* c[P,Q] (fp32) += scale * u[M,P]^T v[M,Q] */
 int ftmi_gemm_tn(int M, int P, int Q, const void* u, long ldu, const void* v, long ldv, float* c, long ldc, float scale,
@@ -757,6 +770,11 @@ int ftmi_wan_block_backward(const ftmi_wan_block_config* cfg, const void* params
  * regex does not match), so the backward adds only the image branch's dQ: no gradient to enc_img or to img_params.  `saved` grows by the projected image
  * rows [B TI, 3D], lse of the image branch and the summed attention output [B, S, D]; `scratch` does not depend on TI.  TI = 0 (text-to-video; img_params /
  * enc_img may then be NULL): none of it -- no launch, no byte.
+ * A second image (TI2 > 0; the first/last-frame model, Wan2.1-FLF2V, whose image embedder carries pos_embed): its TI2 tokens follow the first image's in
+ * enc_img [B, TI + TI2, D]; the image GEMM and RMSNorm run over B (TI + TI2) rows, the projected rows in `saved` grow to that count (nothing else moves) and both
+ * directions call ftmi_attn_ctx2w_* with Sk = TI + TI2.  TI2 = 0: the plans, launches and bits of the single image.  TI2 needs TI > 0; each is at most 320.
+ * (ftmi_wan_lora_ffn_block_config and ftmi_wan_sample_config grew by this one trailing int without a version step: ftmi_version() stays 101, and the Python
+ * structures of finetrainers_amd/_lib.py are their only callers.)
  *
  * Feed-forward adapters (ffn = 1): ffn.net.0.proj (A_1 [r, D], B_1 [F, r]) and ffn.net.2 (A_2 [r, F], B_2 [D, r]) next to the eight attention projections,
  * at the same rank and scale -- what peft attaches when the reference's --target_modules (handed over unchanged: finetrainers/trainer/sft_trainer/trainer.py:121-128
@@ -781,6 +799,7 @@ typedef struct {
     float lora_scale; /* alpha / (the user's) r */
     int TI;           /* image tokens, 0 .. 320 */
     int ffn;          /* 1: adapters on ffn.net.0.proj and ffn.net.2 as well */
+    int TI2;          /* tokens of a second image, 0 .. 320 (first/last-frame); needs TI > 0 */
 } ftmi_wan_lora_ffn_block_config;
 typedef struct {
     const void* params;                                                          /* flat bf16, WanBlockLayout order */
@@ -903,7 +922,7 @@ int ftmi_wan_sample_mod(const void* const* tables, int L, const void* tproj, flo
  * adapters), all blocks sharing ONE `saved` slot and one scratch area, activations alternating between two [P B S, D] buffers; ftmi_wan_ln_fwd with the step's
  * head shift / scale and the proj_out NT GEMM; ftmi_wan_sample_step.  Bit-identical to that composition issued call by call.
  * The caller supplies what does not depend on the state: tproj bf16 [steps, 6 D], head_shift / head_scale fp32 [steps, D], enc bf16 [P B, T, D] (unconditional
- * rows first), enc_img bf16 [P B, TI, D], the rotary tables fp32 [S, 64], sigmas fp32 [steps + 1] on the device.  The rows of one step share one timestep.
+ * rows first), enc_img bf16 [P B, TI + TI2, D], the rotary tables fp32 [S, 64], sigmas fp32 [steps + 1] on the device.  The rows of one step share one timestep.
  * x / cols: in and out (ftmi_wan_sample_init wrote them; on return x is the final state and cols its bf16 copies).
  * Workspace: ftmi_wan_sample_workspace_bytes (0 for a refused configuration; it does not depend on L); a smaller one is FTMI_ERR_INVALID. */
 typedef struct ftmi_wan_sample_config {
@@ -921,6 +940,7 @@ typedef struct ftmi_wan_sample_config {
     float patch_scale;
     int steps;
     float guidance;     /* != 1 needs geo.P == 2 */
+    int TI2;            /* tokens of a second image (0: none), handed to the block */
 } ftmi_wan_sample_config;
 typedef struct ftmi_wan_sample_weights {
     const ftmi_wan_lora_ffn_block_weights* blocks; /* HOST array [L] */

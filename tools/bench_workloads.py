@@ -312,12 +312,15 @@ def build_wan_control_lora(args, par, dev) -> Dict[str, Any]:
 # Wan2.1-I2V-14B-480P LoRA (examples/training/sft/wan_i2v/3dgs_dissolve/train.sh): the same adapters on the image-to-video model -- width 5120,
 # 40 x 128 heads, feed-forward 13824, 40 blocks, 36 input channels, 257 CLIP image tokens in every block's attn2; the recipe's 49 x 480 x 832 bucket
 # (20 280 video + 512 text tokens), gradient checkpointing as in the recipe.  --layers N runs fewer blocks; the row states how many ran.
+# --last-frame: the first/last-frame model (Wan2.1-FLF2V-14B: pos_embed_seq_len = 514) at the same geometry -- the CLIP tokens of two images, 514 image keys in
+# every block's attn2 (ftmi_attn_ctx2w_*), the last frame kept in the conditioning mask.
 # ------------------------------------------------------------------------------------------------------------------------------------------
 def build_wan_i2v_lora(args, par, dev) -> Dict[str, Any]:
     from finetrainers_amd.wan import MI355XWanLoRAStep, MI355XWanTransformer3DModel, WanTransformerConfig
 
     layers = args.layers if args.layers > 0 else 40
-    cfg = WanTransformerConfig(num_layers=layers, num_attention_heads=40, ffn_dim=13824, in_channels=36, image_dim=1280)
+    last_frame = bool(getattr(args, "last_frame", False))
+    cfg = WanTransformerConfig(num_layers=layers, num_attention_heads=40, ffn_dim=13824, in_channels=36, image_dim=1280, pos_embed_seq_len=514 if last_frame else None)
     model = MI355XWanTransformer3DModel(cfg, device=dev)
     g = torch.Generator(device=dev).manual_seed(0)
     D = cfg.inner_dim
@@ -340,11 +343,13 @@ def build_wan_i2v_lora(args, par, dev) -> Dict[str, Any]:
             p[:, :, :args.rank].normal_(0, 0.01, generator=g)
     step = MI355XWanLoRAStep(model, lr=1e-4, generator=torch.Generator(device=dev).manual_seed(1 + par.rank), parallel=par if par.world_size > 1 else None)
     g.manual_seed(100 + par.rank)
-    B, C, F_, H, W, T, TI = 1, 16, 13, 60, 104, 512, 257
+    B, C, F_, H, W, T, TI = 1, 16, 13, 60, 104, 512, 514 if last_frame else 257
     mom = lambda: torch.cat([torch.randn((B, C, F_, H, W), generator=g, device=dev), 0.3 * torch.randn((B, C, F_, H, W), generator=g, device=dev) - 2.0], dim=1).to(bf16)
     moments, cond = mom(), mom()
     mask = torch.zeros((B, 4, F_, H, W), dtype=bf16, device=dev)
     mask[:, :, 0] = 1  # the first frame is the conditioning image
+    if last_frame:
+        mask[:, 3, -1] = 1  # ... and the last pixel frame, the last channel of the last latent frame (MI355XWanModelSpecification.condition_mask)
     text = torch.randn((B, T, cfg.text_dim), generator=g, device=dev).to(bf16)
     image = torch.randn((B, TI, cfg.image_dim), generator=g, device=dev).to(bf16)
     mean, std = torch.zeros(C, device=dev), torch.ones(C, device=dev)
@@ -357,9 +362,9 @@ def build_wan_i2v_lora(args, par, dev) -> Dict[str, Any]:
         "one_step": lambda: step.step(moments, text, mean, std, sig, latent_condition=cond, latent_condition_mask=mask, encoder_hidden_states_image=image),
         "samples_per_step": 1,
         "step_tflop": flop / 1e12,
-        "metric": "train samples/sec (+ step ms) Wan-I2V-14B LoRA 49x480x832 (the reference's wan_i2v SFT recipe)",
-        "data": "synthetic posterior moments [1,32,13,60,104] + conditioning moments + first-frame mask + random text [1,512,4096] and image [1,257,1280] embeds, random-init weights",
-        "config": {"workload": f"Wan-I2V-14B LoRA rank={args.rank} bf16 SFT step over the frozen base, 49x480x832 clip ({S} video + {T} text + {TI} image tokens), batch 1 per GPU, "
+        "metric": "train samples/sec (+ step ms) Wan-I2V-14B LoRA 49x480x832 (the reference's wan_i2v SFT recipe)" + (", first/last-frame model" if last_frame else ""),
+        "data": f"synthetic posterior moments [1,32,13,60,104] + conditioning moments + {'first/last' if last_frame else 'first'}-frame mask + random text [1,512,4096] and image [1,{TI},1280] embeds, random-init weights",
+        "config": {"workload": f"Wan-{'FLF2V' if last_frame else 'I2V'}-14B LoRA rank={args.rank} bf16 SFT step over the frozen base, 49x480x832 clip ({S} video + {T} text + {TI} image tokens), batch 1 per GPU, "
                                f"{layers} blocks" + ("" if layers == 40 else " -- REDUCED depth"),
                    "model": "Wan2.1-I2V-14B DiT geometry: width 5120, 40 x 128 heads, feed-forward 13824, frozen; 8 fp32 adapters per block", "seq_len": S,
                    "activation_checkpointing": True, "orchestration": ("one C call per block and direction (ftmi_wan_lora_ffn_block_forward / _backward)" if os.environ.get("FTMI_NATIVE_BLOCKS", "1") != "0" else "python, per kernel over the C ABI")},
@@ -870,6 +875,8 @@ def main() -> None:
     ap.add_argument("--ffn-adapters", dest="ffn_adapters", action="store_true", help="wan_lora: adapters on ffn.net.0.proj and ffn.net.2 as well (ten per block)")
     ap.add_argument("--text-adapters", dest="text_adapters", action="store_true",
                     help="hunyuan / hy_sample: the shipped recipe's target_modules -- adapters on add_q_proj / add_k_proj / add_v_proj / to_add_out of the dual-stream blocks too")
+    ap.add_argument("--last-frame", dest="last_frame", action="store_true",
+                    help="wan_i2v_lora: the first/last-frame model (pos_embed_seq_len = 514: two images, 514 image keys in attn2) at the same geometry")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     ctx = WORKLOADS[args.workload][0](args, types.SimpleNamespace(world_size=1, rank=0), dev)
