@@ -64,6 +64,15 @@ class LtxWeights(Structure):
     _fields_ = [(n, c_void_p) for n in LTX_WEIGHT_FIELDS]
 
 
+LTX_FF_WEIGHT_FIELDS = ["ff_a1_sp", "ff_a1t_ext", "ff_b1_ext", "ff_b1t_sp", "ff_a2_sp", "ff_a2t_ext", "ff_b2_ext", "ff_b2t_sp"]
+
+
+class LtxFfWeights(Structure):
+    """include/ftmi355.h: ftmi_ltx_ff_weights -- the base structure first, then the feed-forward adapters' operand copies (all NULL: none)."""
+
+    _fields_ = [("base", LtxWeights)] + [(n, c_void_p) for n in LTX_FF_WEIGHT_FIELDS]
+
+
 class CogConfig(Structure):
     _fields_ = [
         ("B", c_int), ("T", c_int), ("S", c_int),
@@ -337,6 +346,22 @@ _SIGS = {
     "ftmi_ltx_sample_cond_workspace_bytes": (c_size_t, [POINTER(LtxConfig), c_int, c_int]),
     "ftmi_ltx_sample_cond": (c_int, [POINTER(LtxConfig), POINTER(LtxWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float,
                                      c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "ftmi_ltx_ff_workspace_bytes": (c_size_t, [POINTER(LtxConfig), POINTER(LtxFfWeights)]),
+    "ftmi_ltx_ff_workspace_offset": (c_int, [POINTER(LtxConfig), POINTER(LtxFfWeights), c_char_p, c_int, POINTER(c_size_t)]),
+    "ftmi_ltx_ff_forward": (c_int, [POINTER(LtxConfig), POINTER(LtxFfWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ftmi_ltx_ff_forward_frames_workspace_bytes": (c_size_t, [POINTER(LtxConfig), POINTER(LtxFfWeights), c_int]),
+    "ftmi_ltx_ff_forward_frames": (c_int, [POINTER(LtxConfig), POINTER(LtxFfWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                           c_size_t, c_void_p]),
+    "ftmi_ltx_ff_backward_range": (c_int, [POINTER(LtxConfig), POINTER(LtxFfWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_size_t, c_int, c_int, c_int, c_void_p]),
+    "ftmi_ltx_ff_sample_workspace_bytes": (c_size_t, [POINTER(LtxConfig), POINTER(LtxFfWeights), c_int]),
+    "ftmi_ltx_ff_sample": (c_int, [POINTER(LtxConfig), POINTER(LtxFfWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float,
+                                   c_void_p, c_size_t, c_void_p]),
+    "ftmi_ltx_ff_sample_cond_workspace_bytes": (c_size_t, [POINTER(LtxConfig), POINTER(LtxFfWeights), c_int, c_int]),
+    "ftmi_ltx_ff_sample_cond": (c_int, [POINTER(LtxConfig), POINTER(LtxFfWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                        c_float, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "ftmi_gelu_from_pre": (c_int, [c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_void_p]),
+    "ftmi_lora_refresh_rect": (c_int, [c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ftmi_ddim_add_noise": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_long, c_void_p]),
     "ftmi_ddim_get_velocity": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_void_p]),
     "ftmi_posterior_sample": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_long, c_void_p]),

@@ -102,21 +102,22 @@ void prof_end(int k, hipStream_t st) {
     g_prof_recs.push_back(ProfRec{g_prof_open[k], g_prof_open_b[k], k, g_prof_open_flops[k]});
 }
 
-size_t ltx_workspace_bytes(const ftmi_ltx_config& c);
-int ltx_workspace_offset(const ftmi_ltx_config& c, const char* name, int layer, size_t* off);
-int ltx_forward(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const bf16_t* x_t, const bf16_t* text, const float* key_bias,
+// (ff: the feed-forward adapters of the _ff entries, null = none)
+size_t ltx_workspace_bytes(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights* ff);
+int ltx_workspace_offset(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights* ff, const char* name, int layer, size_t* off);
+int ltx_forward(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const ftmi_ltx_ff_weights* ff, const bf16_t* x_t, const bf16_t* text, const float* key_bias,
                 const float* sigma, bf16_t* pred, void* ws, size_t ws_bytes, hipStream_t st);
-int ltx_backward_range(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const bf16_t* text, const float* key_bias, const bf16_t* dpred,
-                       float* grad_a, float* grad_b, void* ws, size_t ws_bytes, int l_hi, int l_lo, int accumulate, hipStream_t st);
-size_t ltx_forward_frames_workspace_bytes(const ftmi_ltx_config& c, int frames);
-int ltx_forward_frames(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const bf16_t* x_t, const bf16_t* text, const float* key_bias,
+int ltx_backward_range(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const ftmi_ltx_ff_weights* ff, const bf16_t* text, const float* key_bias, const bf16_t* dpred,
+                       float* grad_a, float* grad_b, float* grad_ff, void* ws, size_t ws_bytes, int l_hi, int l_lo, int accumulate, hipStream_t st);
+size_t ltx_forward_frames_workspace_bytes(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights* ff, int frames);
+int ltx_forward_frames(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const ftmi_ltx_ff_weights* ff, const bf16_t* x_t, const bf16_t* text, const float* key_bias,
                        const float* timesteps, int frames, bf16_t* pred, void* ws, size_t ws_bytes, hipStream_t st);
-size_t ltx_sample_workspace_bytes(const ftmi_ltx_config& c, int two_pass);
-size_t ltx_sample_cond_workspace_bytes(const ftmi_ltx_config& c, int two_pass, int frames);
-int ltx_sample_cond(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const bf16_t* text_cond, const bf16_t* text_uncond, const float* kbias_cond,
+size_t ltx_sample_workspace_bytes(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights* ff, int two_pass);
+size_t ltx_sample_cond_workspace_bytes(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights* ff, int two_pass, int frames);
+int ltx_sample_cond(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const ftmi_ltx_ff_weights* ff, const bf16_t* text_cond, const bf16_t* text_uncond, const float* kbias_cond,
                     const float* kbias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, int frames,
                     int cond_frames, void* ws, size_t ws_bytes, hipStream_t st);
-int ltx_sample(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const bf16_t* text_cond, const bf16_t* text_uncond, const float* kbias_cond,
+int ltx_sample(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const ftmi_ltx_ff_weights* ff, const bf16_t* text_cond, const bf16_t* text_uncond, const float* kbias_cond,
                const float* kbias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, void* ws, size_t ws_bytes,
                hipStream_t st);
 
@@ -528,37 +529,72 @@ int ftmi_qknorm_rope_bwd_ex(const void* x, long ldx, const void* w, const float*
                            (hipStream_t)stream, w_rows, (const bf16_t*)x2, (const bf16_t*)w2, (const bf16_t*)dy2, (bf16_t*)dx2, row_grp, row_grp_span);
 }
 
-size_t ftmi_ltx_workspace_bytes(const ftmi_ltx_config* cfg) { return cfg ? ltx_workspace_bytes(*cfg) : 0; }
+size_t ftmi_ltx_workspace_bytes(const ftmi_ltx_config* cfg) { return cfg ? ltx_workspace_bytes(*cfg, nullptr) : 0; }
 
 int ftmi_ltx_workspace_offset(const ftmi_ltx_config* cfg, const char* name, int layer, size_t* offset) {
     if (!cfg || !name || !offset) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_workspace_offset: null argument");
-    return ltx_workspace_offset(*cfg, name, layer, offset);
+    return ltx_workspace_offset(*cfg, nullptr, name, layer, offset);
 }
 
-int ftmi_ltx_forward(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const void* x_t, const void* text, const float* key_bias,
-                     const float* sigma, void* pred, void* ws, size_t ws_bytes, ftmi_stream stream) {
+// The entries that run blocks and their _ff twins share one body each: ff == null is the entry without feed-forward adapters.
+static int ltx_forward_entry(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const ftmi_ltx_ff_weights* ff, const void* x_t, const void* text, const float* key_bias,
+                             const float* sigma, void* pred, void* ws, size_t ws_bytes, ftmi_stream stream) {
     if (!cfg || !w || !x_t || !text || !sigma || !pred || !ws) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_forward: null argument");
     if (cfg->r > 0 && (!w->lora_a_sp || !w->lora_b_ext)) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_forward: LoRA working copies missing");
-    return ltx_forward(*cfg, *w, (const bf16_t*)x_t, (const bf16_t*)text, key_bias, sigma, (bf16_t*)pred, ws, ws_bytes, (hipStream_t)stream);
+    return ltx_forward(*cfg, *w, ff, (const bf16_t*)x_t, (const bf16_t*)text, key_bias, sigma, (bf16_t*)pred, ws, ws_bytes, (hipStream_t)stream);
+}
+int ftmi_ltx_forward(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const void* x_t, const void* text, const float* key_bias,
+                     const float* sigma, void* pred, void* ws, size_t ws_bytes, ftmi_stream stream) {
+    return ltx_forward_entry(cfg, w, nullptr, x_t, text, key_bias, sigma, pred, ws, ws_bytes, stream);
+}
+int ftmi_ltx_ff_forward(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, const void* x_t, const void* text, const float* key_bias,
+                        const float* sigma, void* pred, void* ws, size_t ws_bytes, ftmi_stream stream) {
+    return ltx_forward_entry(cfg, w ? &w->base : nullptr, w, x_t, text, key_bias, sigma, pred, ws, ws_bytes, stream);
+}
+size_t ftmi_ltx_ff_workspace_bytes(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w) { return cfg && w ? ltx_workspace_bytes(*cfg, w) : 0; }
+int ftmi_ltx_ff_workspace_offset(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, const char* name, int layer, size_t* offset) {
+    if (!cfg || !w || !name || !offset) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_ff_workspace_offset: null argument");
+    return ltx_workspace_offset(*cfg, w, name, layer, offset);
 }
 
-size_t ftmi_ltx_forward_frames_workspace_bytes(const ftmi_ltx_config* cfg, int frames) { return cfg ? ltx_forward_frames_workspace_bytes(*cfg, frames) : 0; }
+size_t ftmi_ltx_forward_frames_workspace_bytes(const ftmi_ltx_config* cfg, int frames) { return cfg ? ltx_forward_frames_workspace_bytes(*cfg, nullptr, frames) : 0; }
+size_t ftmi_ltx_ff_forward_frames_workspace_bytes(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, int frames) {
+    return cfg && w ? ltx_forward_frames_workspace_bytes(*cfg, w, frames) : 0;
+}
 
-int ftmi_ltx_forward_frames(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const void* x_t, const void* text, const float* key_bias,
-                            const float* timesteps, int frames, void* pred, void* ws, size_t ws_bytes, ftmi_stream stream) {
+static int ltx_forward_frames_entry(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const ftmi_ltx_ff_weights* ff, const void* x_t, const void* text,
+                                    const float* key_bias, const float* timesteps, int frames, void* pred, void* ws, size_t ws_bytes, ftmi_stream stream) {
     if (!cfg || !w || !x_t || !text || !timesteps || !pred || !ws) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_forward_frames: null argument");
     if (cfg->r > 0 && (!w->lora_a_sp || !w->lora_b_ext)) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_forward_frames: LoRA working copies missing");
-    return ltx_forward_frames(*cfg, *w, (const bf16_t*)x_t, (const bf16_t*)text, key_bias, timesteps, frames, (bf16_t*)pred, ws, ws_bytes,
+    return ltx_forward_frames(*cfg, *w, ff, (const bf16_t*)x_t, (const bf16_t*)text, key_bias, timesteps, frames, (bf16_t*)pred, ws, ws_bytes,
                               (hipStream_t)stream);
 }
+int ftmi_ltx_forward_frames(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const void* x_t, const void* text, const float* key_bias,
+                            const float* timesteps, int frames, void* pred, void* ws, size_t ws_bytes, ftmi_stream stream) {
+    return ltx_forward_frames_entry(cfg, w, nullptr, x_t, text, key_bias, timesteps, frames, pred, ws, ws_bytes, stream);
+}
+int ftmi_ltx_ff_forward_frames(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, const void* x_t, const void* text, const float* key_bias,
+                               const float* timesteps, int frames, void* pred, void* ws, size_t ws_bytes, ftmi_stream stream) {
+    return ltx_forward_frames_entry(cfg, w ? &w->base : nullptr, w, x_t, text, key_bias, timesteps, frames, pred, ws, ws_bytes, stream);
+}
 
-int ftmi_ltx_backward_range(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const void* text, const float* key_bias, const void* dpred,
-                            float* grad_a, float* grad_b, void* ws, size_t ws_bytes, int l_hi, int l_lo, int accumulate, ftmi_stream stream) {
+static int ltx_backward_range_entry(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const ftmi_ltx_ff_weights* ff, const void* text, const float* key_bias,
+                                    const void* dpred, float* grad_a, float* grad_b, float* grad_ff, void* ws, size_t ws_bytes, int l_hi, int l_lo, int accumulate,
+                                    ftmi_stream stream) {
     if (!cfg || !w || !dpred || !ws) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_backward: null argument");
     if (cfg->r > 0 && (!grad_a || !grad_b || !w->lora_at_ext || !w->lora_bt_sp || !w->lora_at_qkv_ext))
         return set_error(FTMI_ERR_INVALID, "ftmi_ltx_backward: LoRA gradient buffers / working copies missing");
-    return ltx_backward_range(*cfg, *w, (const bf16_t*)text, key_bias, (const bf16_t*)dpred, grad_a, grad_b, ws, ws_bytes, l_hi, l_lo, accumulate,
+    return ltx_backward_range(*cfg, *w, ff, (const bf16_t*)text, key_bias, (const bf16_t*)dpred, grad_a, grad_b, grad_ff, ws, ws_bytes, l_hi, l_lo, accumulate,
                               (hipStream_t)stream);
+}
+int ftmi_ltx_backward_range(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const void* text, const float* key_bias, const void* dpred,
+                            float* grad_a, float* grad_b, void* ws, size_t ws_bytes, int l_hi, int l_lo, int accumulate, ftmi_stream stream) {
+    return ltx_backward_range_entry(cfg, w, nullptr, text, key_bias, dpred, grad_a, grad_b, nullptr, ws, ws_bytes, l_hi, l_lo, accumulate, stream);
+}
+int ftmi_ltx_ff_backward_range(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, const void* text, const float* key_bias, const void* dpred,
+                               float* grad_a, float* grad_b, float* grad_ff, void* ws, size_t ws_bytes, int l_hi, int l_lo, int accumulate,
+                               ftmi_stream stream) {
+    return ltx_backward_range_entry(cfg, w ? &w->base : nullptr, w, text, key_bias, dpred, grad_a, grad_b, grad_ff, ws, ws_bytes, l_hi, l_lo, accumulate, stream);
 }
 
 int ftmi_ltx_backward(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const void* text, const float* key_bias, const void* dpred,
@@ -584,34 +620,63 @@ int ftmi_ltx_unpack_denorm(const float* x, const float* mean, const float* std_,
     return unpack_denorm(x, mean, std_, (bf16_t*)latents, B, C, S, (hipStream_t)stream);
 }
 
-size_t ftmi_ltx_sample_workspace_bytes(const ftmi_ltx_config* cfg, int two_pass) { return cfg ? ltx_sample_workspace_bytes(*cfg, two_pass) : 0; }
+size_t ftmi_ltx_sample_workspace_bytes(const ftmi_ltx_config* cfg, int two_pass) { return cfg ? ltx_sample_workspace_bytes(*cfg, nullptr, two_pass) : 0; }
+size_t ftmi_ltx_ff_sample_workspace_bytes(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, int two_pass) {
+    return cfg && w ? ltx_sample_workspace_bytes(*cfg, w, two_pass) : 0;
+}
 
-int ftmi_ltx_sample(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const void* text_cond, const void* text_uncond, const float* key_bias_cond,
-                    const float* key_bias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, void* ws,
-                    size_t ws_bytes, ftmi_stream stream) {
+static int ltx_sample_entry(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const ftmi_ltx_ff_weights* ff, const void* text_cond, const void* text_uncond,
+                            const float* key_bias_cond, const float* key_bias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps,
+                            float guidance, void* ws, size_t ws_bytes, ftmi_stream stream) {
     if (!cfg || !w || !text_cond || !x || !sigmas || !timesteps || !ws) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_sample: null argument");
     if (guidance != 1.0f && !text_uncond) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_sample: guidance != 1 needs the unconditional prompt embeddings");
     if (guidance != 1.0f && (key_bias_cond == nullptr) != (key_bias_uncond == nullptr))
         return set_error(FTMI_ERR_INVALID, "ftmi_ltx_sample: give the key bias of both prompts or of neither");
     if (cfg->r > 0 && (!w->lora_a_sp || !w->lora_b_ext)) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_sample: LoRA working copies missing");
-    return ltx_sample(*cfg, *w, (const bf16_t*)text_cond, (const bf16_t*)text_uncond, key_bias_cond, key_bias_uncond, x, sigmas, timesteps, n_steps,
+    return ltx_sample(*cfg, *w, ff, (const bf16_t*)text_cond, (const bf16_t*)text_uncond, key_bias_cond, key_bias_uncond, x, sigmas, timesteps, n_steps,
                       guidance, ws, ws_bytes, (hipStream_t)stream);
+}
+int ftmi_ltx_sample(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const void* text_cond, const void* text_uncond, const float* key_bias_cond,
+                    const float* key_bias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, void* ws,
+                    size_t ws_bytes, ftmi_stream stream) {
+    return ltx_sample_entry(cfg, w, nullptr, text_cond, text_uncond, key_bias_cond, key_bias_uncond, x, sigmas, timesteps, n_steps, guidance, ws, ws_bytes, stream);
+}
+int ftmi_ltx_ff_sample(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, const void* text_cond, const void* text_uncond, const float* key_bias_cond,
+                       const float* key_bias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, void* ws,
+                       size_t ws_bytes, ftmi_stream stream) {
+    return ltx_sample_entry(cfg, w ? &w->base : nullptr, w, text_cond, text_uncond, key_bias_cond, key_bias_uncond, x, sigmas, timesteps, n_steps, guidance, ws, ws_bytes,
+                            stream);
 }
 
 size_t ftmi_ltx_sample_cond_workspace_bytes(const ftmi_ltx_config* cfg, int two_pass, int frames) {
-    return cfg ? ltx_sample_cond_workspace_bytes(*cfg, two_pass, frames) : 0;
+    return cfg ? ltx_sample_cond_workspace_bytes(*cfg, nullptr, two_pass, frames) : 0;
+}
+size_t ftmi_ltx_ff_sample_cond_workspace_bytes(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, int two_pass, int frames) {
+    return cfg && w ? ltx_sample_cond_workspace_bytes(*cfg, w, two_pass, frames) : 0;
 }
 
-int ftmi_ltx_sample_cond(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const void* text_cond, const void* text_uncond, const float* key_bias_cond,
-                         const float* key_bias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, int frames,
-                         int cond_frames, void* ws, size_t ws_bytes, ftmi_stream stream) {
+static int ltx_sample_cond_entry(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const ftmi_ltx_ff_weights* ff, const void* text_cond, const void* text_uncond,
+                                 const float* key_bias_cond, const float* key_bias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps,
+                                 float guidance, int frames, int cond_frames, void* ws, size_t ws_bytes, ftmi_stream stream) {
     if (!cfg || !w || !text_cond || !x || !sigmas || !timesteps || !ws) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_sample_cond: null argument");
     if (guidance != 1.0f && !text_uncond) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_sample_cond: guidance != 1 needs the unconditional prompt embeddings");
     if (guidance != 1.0f && (key_bias_cond == nullptr) != (key_bias_uncond == nullptr))
         return set_error(FTMI_ERR_INVALID, "ftmi_ltx_sample_cond: give the key bias of both prompts or of neither");
     if (cfg->r > 0 && (!w->lora_a_sp || !w->lora_b_ext)) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_sample_cond: LoRA working copies missing");
-    return ltx_sample_cond(*cfg, *w, (const bf16_t*)text_cond, (const bf16_t*)text_uncond, key_bias_cond, key_bias_uncond, x, sigmas, timesteps, n_steps,
+    return ltx_sample_cond(*cfg, *w, ff, (const bf16_t*)text_cond, (const bf16_t*)text_uncond, key_bias_cond, key_bias_uncond, x, sigmas, timesteps, n_steps,
                            guidance, frames, cond_frames, ws, ws_bytes, (hipStream_t)stream);
+}
+int ftmi_ltx_sample_cond(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const void* text_cond, const void* text_uncond, const float* key_bias_cond,
+                         const float* key_bias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, int frames,
+                         int cond_frames, void* ws, size_t ws_bytes, ftmi_stream stream) {
+    return ltx_sample_cond_entry(cfg, w, nullptr, text_cond, text_uncond, key_bias_cond, key_bias_uncond, x, sigmas, timesteps, n_steps, guidance, frames, cond_frames,
+                                 ws, ws_bytes, stream);
+}
+int ftmi_ltx_ff_sample_cond(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, const void* text_cond, const void* text_uncond,
+                            const float* key_bias_cond, const float* key_bias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps,
+                            float guidance, int frames, int cond_frames, void* ws, size_t ws_bytes, ftmi_stream stream) {
+    return ltx_sample_cond_entry(cfg, w ? &w->base : nullptr, w, text_cond, text_uncond, key_bias_cond, key_bias_uncond, x, sigmas, timesteps, n_steps, guidance, frames,
+                                 cond_frames, ws, ws_bytes, stream);
 }
 
 int ftmi_ltx_noise_pack(const void* latents, const void* noise, const float* mean, const float* std_, const float* sigma,
@@ -950,6 +1015,23 @@ int ftmi_lora_split(const float* w, int rows, int cols, void* sp, void* ext, voi
     a.w = w; a.rows = rows; a.cols = cols; a.nmat = 1;
     a.sp = (bf16_t*)sp; a.ext = (bf16_t*)ext; a.ld_ext = 3L * cols; a.t_sp = (bf16_t*)t_sp; a.t_ext = (bf16_t*)t_ext; a.ld_t_ext = 3L * rows;
     return lora_split(a, (hipStream_t)stream);
+}
+
+int ftmi_lora_refresh_rect(const float* w, long w_stride, int nmat, int rows, int cols, void* sp, void* ext, void* t_sp, void* t_ext, ftmi_stream stream) {
+    if (nmat <= 0 || rows <= 0 || cols <= 0) return 0;
+    if (!w || w_stride < (long)rows * cols) return set_error(FTMI_ERR_INVALID, "ftmi_lora_refresh_rect: null matrix or a stride below one matrix");
+    const long per = (long)rows * cols;
+    LoraSplitArgs a;
+    a.w = w; a.rows = rows; a.cols = cols; a.nmat = nmat; a.in_bstride = w_stride;
+    a.sp = (bf16_t*)sp; a.sp_bstride = 2 * per;
+    a.ext = (bf16_t*)ext; a.ext_bstride = 3 * per; a.ld_ext = 3L * cols;
+    a.t_sp = (bf16_t*)t_sp; a.t_sp_bstride = 2 * per;
+    a.t_ext = (bf16_t*)t_ext; a.t_ext_bstride = 3 * per; a.ld_t_ext = 3L * rows;
+    return lora_split(a, (hipStream_t)stream);
+}
+
+int ftmi_gelu_from_pre(const void* z, long ldz, void* g, long ldg, int rows, int width, ftmi_stream stream) {
+    return gelu_from_pre((const bf16_t*)z, ldz, (bf16_t*)g, ldg, rows, width, (hipStream_t)stream);
 }
 
 int ftmi_f32_gemm(int M, int N, int K, const float* a, long lda_row, long lda_col, const float* b, long ldb_row, long ldb_col, float* c, long ldc, float scale,

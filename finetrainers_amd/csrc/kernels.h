@@ -311,6 +311,8 @@ struct LoraSplitArgs {
 int lora_split(const LoraSplitArgs& a, hipStream_t st);
 // plain bf16 transpose [rows, cols] -> [cols, rows]
 int transpose_bf16(const bf16_t* in, bf16_t* out, int rows, int cols, hipStream_t st);
+// g [rows, width] (row stride ldg) = bf16(gelu_tanh(z)) from the bf16 pre-activation z (row stride ldz) a GELU GEMM stashed: the bits that GEMM wrote as g
+int gelu_from_pre(const bf16_t* z, long ldz, bf16_t* g, long ldg, int rows, int width, hipStream_t st);
 
 // ---- CogVideoX row-wise kernels (cogvideox.hip): any row width D % 64 == 0, D <= 4096 ----------------------------------------------
 // Tokens [B, rows_per_batch, D]; seg0 > 0: the first seg0 tokens of a sample (text) use modulation row 2b, the others (video) row 2b + 1 of

@@ -7,6 +7,11 @@
 // the upstream LTXVideoTransformerBlock it iterates, with the peft LoRA branches of
 // to_q/to_k/to_v/to_out.0 fused into the projections, and the autograd backward of the same graph with
 // frozen base weights (dgrad only) and trainable LoRA A/B.
+//
+// Feed-forward adapters (the ftmi_ltx_ff_* entries; peft attaches them when --target_modules names ff.net.0.proj and ff.net.2, as the default of
+// trainer/control_trainer/config.py:60 does): two more adapters per block at the same rank, through the same builders (lora_proj.hip.h) and the block's
+// proj_with / proj_bwd_with.  Their weight-gradient operands n2, g, dz and the gated dO are scratch shared by all blocks, so the backward writes n2 and g again
+// per block (norm_modulate_fwd; gelu_from_pre on the kept z) and launches the four TN products inside the block loop -- see DESIGN.md 7-V.
 #include <string.h>
 
 #include "common.hip.h"
@@ -30,6 +35,8 @@ struct WsLayout {
     // scratch
     size_t s_n2, s_g, s_ln, s_dh0, s_dh1, s_d1, s_d2, s_d3, s_dqr, s_dkr, s_dbig, s_delta;
     size_t sk_flags;
+    // feed-forward adapters (ff = true): their down-projected rows per block slot, the two dXA of the block in hand as scratch
+    size_t xa_ff1 = 0, xa_ff2 = 0, s_dxa_ff1 = 0, s_dxa_ff2 = 0;
     size_t blk_slot;  // bytes of one block slot (blk_stride is 0 under gradient checkpointing: every block uses the same slot)
 };
 
@@ -38,7 +45,7 @@ struct WsLayout {
 struct ModGroups { int n, rows; };
 constexpr int kMaxModGroups = 128;  // 8 model rows (the batch cap of the sampler) x 16 latent frames (a 121-frame clip)
 
-WsLayout make_layout(const ftmi_ltx_config& c, int groups = 0) {
+WsLayout make_layout(const ftmi_ltx_config& c, int groups = 0, bool ff = false) {
     WsLayout w;
     const size_t M = (size_t)c.B * c.S, Mt = (size_t)c.B * c.T, D = c.D, r = c.r > 0 ? c.r : 64;
     const size_t G = groups > 0 ? groups : c.B;  // rows of the conditioning tables
@@ -86,6 +93,10 @@ WsLayout make_layout(const ftmi_ltx_config& c, int groups = 0) {
     w.dxa_q2 = b.take(M * 3 * r * e2);
     w.dxa_o = b.take(M * 3 * r * e2);
     w.dxa_qkv = b.take(M * 9 * r * e2);
+    if (ff) {  // (after everything the eight-adapter slot holds: that layout is a prefix of this one)
+        w.xa_ff1 = b.take(M * 3 * r * e2);
+        w.xa_ff2 = b.take(M * 3 * r * e2);
+    }
     // gradient checkpointing (cfg.checkpoint, the reference's --gradient_checkpointing: utils/activation_checkpoint.py:24-49 wraps every block): ONE block slot
     // instead of L -- a block keeps only its input (the residual stream hs[l], kept for every block either way) and its forward runs again inside its backward
     w.blk_slot = b.off;
@@ -103,6 +114,10 @@ WsLayout make_layout(const ftmi_ltx_config& c, int groups = 0) {
     w.s_dkr = g.take(M * D * e2);
     w.s_dbig = g.take(M * (size_t)c.D_ff * e2);
     w.s_delta = g.take((size_t)c.B * c.H * c.S * 4);
+    if (ff) {
+        w.s_dxa_ff1 = g.take(M * 3 * r * e2);
+        w.s_dxa_ff2 = g.take(M * 3 * r * e2);
+    }
     w.total = g.off;
     return w;
 }
@@ -120,6 +135,33 @@ int check_cfg(const ftmi_ltx_config& c, int frames = 0) {
     if (c.d_valid < 0 || c.d_valid > c.D || c.head_dim_valid < 0 || c.head_dim_valid > 64)
         return set_error(FTMI_ERR_INVALID, "ltx: d_valid / head_dim_valid describe a model narrower than the layout (0 = full width)");
     return 0;
+}
+
+// The feed-forward adapters of a call (ftmi_ltx_ff_weights): typed operand copies, `on` = all eight present.  ff == null or all eight null: none.
+struct FfOps {
+    bool on = false;
+    const bf16_t *a1_sp = nullptr, *a1t_ext = nullptr, *b1_ext = nullptr, *b1t_sp = nullptr, *a2_sp = nullptr, *a2t_ext = nullptr, *b2_ext = nullptr, *b2t_sp = nullptr;
+};
+int ff_ops(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights* ff, FfOps* o) {
+    *o = FfOps();
+    if (!ff) return 0;
+    const void* p[8] = {ff->ff_a1_sp, ff->ff_a1t_ext, ff->ff_b1_ext, ff->ff_b1t_sp, ff->ff_a2_sp, ff->ff_a2t_ext, ff->ff_b2_ext, ff->ff_b2t_sp};
+    int n = 0;
+    for (const void* q : p) n += q != nullptr;
+    if (n == 0) return 0;
+    if (n != 8) return set_error(FTMI_ERR_INVALID, "ltx: feed-forward adapters need all eight operand copies (or none)");
+    if (c.r <= 0) return set_error(FTMI_ERR_INVALID, "ltx: feed-forward adapters take the model's rank, which is 0");
+    o->on = true;
+    o->a1_sp = P(p[0], 0); o->a1t_ext = P(p[1], 0); o->b1_ext = P(p[2], 0); o->b1t_sp = P(p[3], 0);
+    o->a2_sp = P(p[4], 0); o->a2t_ext = P(p[5], 0); o->b2_ext = P(p[6], 0); o->b2t_sp = P(p[7], 0);
+    return 0;
+}
+// (for the planners, which return a size: a refused combination plans nothing)
+bool ff_on(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights* ff, bool* ok = nullptr) {
+    FfOps o;
+    const int rc = ff_ops(c, ff, &o);
+    if (ok) *ok = rc == 0;
+    return o.on;
 }
 
 // A projection with its LoRA: the down-projection `dn` (writes a.X2) and the GEMM `a` (K-extension over X2) -- one fused launch where the pair is eligible
@@ -160,10 +202,16 @@ AttnArgs cross_attn_args(const ftmi_ltx_config& c, const WsLayout& L, void* ws, 
 
 }  // namespace
 
-size_t ltx_workspace_bytes(const ftmi_ltx_config& c) { return make_layout(c).total; }
+size_t ltx_workspace_bytes(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights* ff) {
+    bool ok;
+    const bool on = ff_on(c, ff, &ok);
+    return ok ? make_layout(c, 0, on).total : 0;
+}
 
-int ltx_workspace_offset(const ftmi_ltx_config& c, const char* name, int layer, size_t* off) {
-    const WsLayout L = make_layout(c);
+int ltx_workspace_offset(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights* ff, const char* name, int layer, size_t* off) {
+    FfOps fo;
+    FTMI_TRY(ff_ops(c, ff, &fo));
+    const WsLayout L = make_layout(c, 0, fo.on);
     const size_t M = (size_t)c.B * c.S;
     struct E { const char* n; size_t o; };
     const E globals[] = {{"kv2_all", L.kv2_all}, {"k2n_all", L.k2n_all}, {"xa_kv2_all", L.xa_kv2_all}, {"e", L.e}, {"emb", L.emb}, {"temb", L.temb}, {"ada", L.ada}, {"ada_out", L.ada_out}, {"tsin", L.tsin}};
@@ -181,14 +229,19 @@ int ltx_workspace_offset(const ftmi_ltx_config& c, const char* name, int layer, 
     if (layer < 0 || layer >= c.L) return set_error(FTMI_ERR_INVALID, "workspace_offset: layer out of range");
     for (const E& b : blocks)
         if (!strcmp(name, b.n)) { *off = L.blk0 + L.blk_stride * layer + b.o; return 0; }
+    if (fo.on) {
+        const E ffb[] = {{"xa_ff1", L.xa_ff1}, {"xa_ff2", L.xa_ff2}};
+        for (const E& b : ffb)
+            if (!strcmp(name, b.n)) { *off = L.blk0 + L.blk_stride * layer + b.o; return 0; }
+    }
     return set_error(FTMI_ERR_INVALID, "workspace_offset: unknown name");
 }
 
 // One transformer block of the forward (steps 1-13 of patches/models/ltx_video/patch.py:82-123 + the upstream block): reads hs[l], writes hs[l+1] and the
 // block's activations into its slot.  Called by the forward for every block and -- under gradient checkpointing -- again by the backward right before a
 // block's gradient computation (deterministic kernels: the recomputed activations are the forward's, bit for bit).
-static int ltx_block_forward(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const WsLayout& L, void* ws, int l, const float* key_bias, hipStream_t st, FuseCtx& fx,
-                             const ModGroups& mg) {
+static int ltx_block_forward(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const FfOps& ff, const WsLayout& L, void* ws, int l, const float* key_bias, hipStream_t st,
+                             FuseCtx& fx, const ModGroups& mg) {
     const int M = c.B * c.S, D = c.D, r = c.r, V = c.gemm_variant;
     const long D2 = (long)D * D;
     const float s = c.lora_scale;
@@ -203,10 +256,14 @@ static int ltx_block_forward(const ftmi_ltx_config& c, const ftmi_ltx_weights& w
         bf16_t* n1 = W(blk, L.n1);
         bf16_t* qkv = W(blk, L.qkv);
         // the projection `a` (+ the adapters adp .. adp + nadp - 1 on its input, xa [M, 3 nadp r] kept for the backward)
+        // the same for any operand pair: sp = the (hi, lo) row planes of A [nadp 2r, a.K], b_ext [a.N, 3r] (the feed-forward adapters are rectangular)
+        auto proj_with = [&](GemmNtArgs& a, const bf16_t* sp, const bf16_t* b_ext, int nadp, bf16_t* xa) -> int {
+            lora_ext_fwd(a, xa, nadp, r, b_ext);
+            return lora_gemm(a, lora_down_args(a.X, a.ldx, M, sp, nadp, a.K, r, s, xa), fx, st);
+        };
         auto proj = [&](GemmNtArgs& a, int adp, int nadp, bf16_t* xa) -> int {
             if (r <= 0) return gemm_nt(a, st);
-            lora_ext_fwd(a, xa, nadp, r, lb + (size_t)adp * D * 3 * r);
-            return lora_gemm(a, lora_down_args(a.X, a.ldx, M, la + (size_t)adp * 2 * r * D, nadp, D, r, s, xa), fx, st);
+            return proj_with(a, la + (size_t)adp * 2 * r * D, lb + (size_t)adp * D * 3 * r, nadp, xa);
         };
 
         // 1. norm1 + AdaLN modulate
@@ -248,12 +305,14 @@ static int ltx_block_forward(const ftmi_ltx_config& c, const ftmi_ltx_weights& w
         {
             GemmNtArgs a = linear_args(W(ws, L.s_n2), D, M, P(w.w_ff1, (size_t)l * c.D_ff * D), D, c.D_ff, D, P(w.b_ff1, (size_t)l * c.D_ff), W(ws, L.s_g), c.D_ff, V);
             a.out2 = W(blk, L.z); a.ldo2 = c.D_ff; a.epi = EPI_GELU;
-            FTMI_TRY(gemm_nt(a, st));
+            if (ff.on) FTMI_TRY(proj_with(a, ff.a1_sp + (size_t)l * 2 * r * D, ff.b1_ext + (size_t)l * c.D_ff * 3 * r, 1, W(blk, L.xa_ff1)));  // adapter 8: ff.net.0.proj
+            else FTMI_TRY(gemm_nt(a, st));
         }
         {
             GemmNtArgs a = linear_args(W(ws, L.s_g), c.D_ff, M, P(w.w_ff2, (size_t)l * D * c.D_ff), c.D_ff, D, c.D_ff, P(w.b_ff2, (size_t)l * D), hout, D, V);
             a.epi = EPI_RESID; a.resid = h2; a.ldr = D; a.gate = ada + 5 * D; a.gate_bstride = ab; a.rows_per_batch = mg.rows;
-            FTMI_TRY(gemm_nt(a, st));
+            if (ff.on) FTMI_TRY(proj_with(a, ff.a2_sp + (size_t)l * 2 * r * c.D_ff, ff.b2_ext + (size_t)l * D * 3 * r, 1, W(blk, L.xa_ff2)));  // adapter 9: ff.net.2 (contracts over D_ff)
+            else FTMI_TRY(gemm_nt(a, st));
         }
     }
     return 0;
@@ -324,12 +383,12 @@ static int ltx_proj_in(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, cons
 }
 
 // The block stack and the tail (LayerNorm + modulate + proj_out) over a prepared workspace: hs[0], the conditioning and the text-side k|v are in place.
-static int ltx_blocks_tail(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const WsLayout& L, void* ws, const float* key_bias, bf16_t* pred,
+static int ltx_blocks_tail(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const FfOps& ff, const WsLayout& L, void* ws, const float* key_bias, bf16_t* pred,
                            hipStream_t st, const ModGroups& mg) {
     const int M = c.B * c.S, D = c.D, V = c.gemm_variant;
     FuseCtx fx{reinterpret_cast<int*>(reinterpret_cast<char*>(ws) + L.sk_flags), 0};
     if (hipMemsetAsync(fx.flags, 0, 4096, st) != hipSuccess) return set_error(FTMI_ERR_LAUNCH, "ltx_forward: memset of the row-tile counters failed");
-    for (int l = 0; l < c.L; ++l) FTMI_TRY(ltx_block_forward(c, w, L, ws, l, key_bias, st, fx, mg));
+    for (int l = 0; l < c.L; ++l) FTMI_TRY(ltx_block_forward(c, w, ff, L, ws, l, key_bias, st, fx, mg));
 
     // ---- tail: LayerNorm + modulate + proj_out ----
     const bf16_t* hL = W(ws, L.hs) + (size_t)c.L * M * D;
@@ -339,19 +398,21 @@ static int ltx_blocks_tail(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, 
     return 0;
 }
 
-int ltx_forward(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const bf16_t* x_t, const bf16_t* text, const float* key_bias,
+int ltx_forward(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const ftmi_ltx_ff_weights* ffw, const bf16_t* x_t, const bf16_t* text, const float* key_bias,
                 const float* sigma, bf16_t* pred, void* ws, size_t ws_bytes, hipStream_t st) {
     FTMI_TRY(check_cfg(c));
     struct ValidWidth {  // (normalisations of a zero-padded narrow model take their mean over d_valid channels; reset when the pass has queued its launches)
         explicit ValidWidth(int dv) { rowwise_set_valid_width(dv); }
         ~ValidWidth() { rowwise_set_valid_width(0); }
     } valid_width_guard(c.d_valid);
-    const WsLayout L = make_layout(c);
+    FfOps ff;
+    FTMI_TRY(ff_ops(c, ffw, &ff));
+    const WsLayout L = make_layout(c, 0, ff.on);
     if (ws_bytes < L.total) return set_error(FTMI_ERR_INVALID, "ltx_forward: workspace too small");
     FTMI_TRY(ltx_prologue_time(c, w, L, ws, sigma, c.B, st));
     FTMI_TRY(ltx_proj_in(c, w, L, ws, x_t, st));
     FTMI_TRY(ltx_prologue_text(c, w, L, ws, text, st));
-    return ltx_blocks_tail(c, w, L, ws, key_bias, pred, st, ModGroups{c.B, c.S});
+    return ltx_blocks_tail(c, w, ff, L, ws, key_bias, pred, st, ModGroups{c.B, c.S});
 }
 
 // ---- forward with one timestep per latent frame (forward only) -----------------------------------------------------------------------------------
@@ -364,22 +425,26 @@ static ftmi_ltx_config frames_cfg(const ftmi_ltx_config& c) {
     fc.checkpoint = 1;
     return fc;
 }
-size_t ltx_forward_frames_workspace_bytes(const ftmi_ltx_config& c, int frames) {
-    return frames > 0 ? make_layout(frames_cfg(c), c.B * frames).total : 0;
+size_t ltx_forward_frames_workspace_bytes(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights* ffw, int frames) {
+    bool ok;
+    const bool on = ff_on(c, ffw, &ok);
+    return frames > 0 && ok ? make_layout(frames_cfg(c), c.B * frames, on).total : 0;
 }
-int ltx_forward_frames(const ftmi_ltx_config& c0, const ftmi_ltx_weights& w, const bf16_t* x_t, const bf16_t* text, const float* key_bias,
+int ltx_forward_frames(const ftmi_ltx_config& c0, const ftmi_ltx_weights& w, const ftmi_ltx_ff_weights* ffw, const bf16_t* x_t, const bf16_t* text, const float* key_bias,
                        const float* timesteps, int frames, bf16_t* pred, void* ws, size_t ws_bytes, hipStream_t st) {
     if (frames <= 0) return set_error(FTMI_ERR_INVALID, "ltx_forward_frames: frames must be positive");
     if (c0.d_valid || c0.head_dim_valid) return set_error(FTMI_ERR_UNSUPPORTED, "ltx_forward_frames: narrow (zero-padded) geometries are not supported");
     const ftmi_ltx_config c = frames_cfg(c0);
     FTMI_TRY(check_cfg(c, frames));
     const int G = c.B * frames;
-    const WsLayout L = make_layout(c, G);
+    FfOps ff;
+    FTMI_TRY(ff_ops(c, ffw, &ff));
+    const WsLayout L = make_layout(c, G, ff.on);
     if (ws_bytes < L.total) return set_error(FTMI_ERR_INVALID, "ltx_forward_frames: workspace too small");
     FTMI_TRY(ltx_prologue_time(c, w, L, ws, timesteps, G, st));
     FTMI_TRY(ltx_proj_in(c, w, L, ws, x_t, st));
     FTMI_TRY(ltx_prologue_text(c, w, L, ws, text, st));
-    return ltx_blocks_tail(c, w, L, ws, key_bias, pred, st, ModGroups{G, c.S / frames});
+    return ltx_blocks_tail(c, w, ff, L, ws, key_bias, pred, st, ModGroups{G, c.S / frames});
 }
 
 // ---- latent sampling: the whole denoising loop as one call, zero host syncs -------------------------------------------------------------------------
@@ -391,12 +456,12 @@ struct SampleLayout {
     size_t xin, pred, text, kbias, tval, total;
     size_t emb2, temb2;  // conditioned sampling (frames > 0): the embedding rows of the two distinct timesteps of a step, [2][D] and [2][6D] (row 0: timestep 0)
 };
-static SampleLayout make_sample_layout(const ftmi_ltx_config& c, int two_pass, int frames = 0) {
+static SampleLayout make_sample_layout(const ftmi_ltx_config& c, int two_pass, int frames = 0, bool ff = false) {
     SampleLayout s;
     s.mc = c;
     s.mc.B = c.B * (two_pass ? 2 : 1);
     s.mc.checkpoint = 1;
-    s.L = make_layout(s.mc, frames > 0 ? s.mc.B * frames : 0);
+    s.L = make_layout(s.mc, frames > 0 ? s.mc.B * frames : 0, ff);
     Bump g;
     g.off = s.L.total;
     const size_t nb = (size_t)s.mc.B;
@@ -414,9 +479,15 @@ static SampleLayout make_sample_layout(const ftmi_ltx_config& c, int two_pass, i
     return s;
 }
 
-size_t ltx_sample_workspace_bytes(const ftmi_ltx_config& c, int two_pass) { return make_sample_layout(c, two_pass).total; }
-size_t ltx_sample_cond_workspace_bytes(const ftmi_ltx_config& c, int two_pass, int frames) {
-    return frames > 0 ? make_sample_layout(c, two_pass, frames).total : 0;
+size_t ltx_sample_workspace_bytes(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights* ffw, int two_pass) {
+    bool ok;
+    const bool on = ff_on(c, ffw, &ok);
+    return ok ? make_sample_layout(c, two_pass, 0, on).total : 0;
+}
+size_t ltx_sample_cond_workspace_bytes(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights* ffw, int two_pass, int frames) {
+    bool ok;
+    const bool on = ff_on(c, ffw, &ok);
+    return frames > 0 && ok ? make_sample_layout(c, two_pass, frames, on).total : 0;
 }
 
 // FTMI_SAMPLE_HOIST=0 (read once; ftmi_reload_switches() re-reads it) repeats the text part of the prologue in every step, as a loop over ltx_forward
@@ -428,7 +499,7 @@ size_t ltx_sample_cond_workspace_bytes(const ftmi_ltx_config& c, int two_pass, i
 // (model row, frame).  A step knows two distinct timesteps only, so the embedding MLP runs on ONE row per step (the live timestep); the timestep-0 row is
 // computed once per call, next to the text hoist, and cond_rows_expand deals the two rows out to the groups.  With FTMI_SAMPLE_HOIST=0 every step runs the
 // whole per-frame prologue of ltx_forward_frames instead (all groups through the MLP): same bits, a row's embedding does not depend on its neighbours.
-static int ltx_sample_impl(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const bf16_t* text_cond, const bf16_t* text_uncond, const float* kbias_cond,
+static int ltx_sample_impl(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const ftmi_ltx_ff_weights* ffw, const bf16_t* text_cond, const bf16_t* text_uncond, const float* kbias_cond,
                            const float* kbias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, int frames,
                            int cond_frames, void* ws, size_t ws_bytes, hipStream_t st) {
     static const EnvSwitch hoist_sw("FTMI_SAMPLE_HOIST", 1);
@@ -440,7 +511,9 @@ static int ltx_sample_impl(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, 
     if (c.d_valid || c.head_dim_valid) return set_error(FTMI_ERR_UNSUPPORTED, "ltx_sample: narrow (zero-padded) geometries are not supported");
     if (frames > 0 && (cond_frames < 0 || cond_frames > frames)) return set_error(FTMI_ERR_INVALID, "ltx_sample_cond: cond_frames must lie in [0, frames]");
     if (frames > 0 && c.C_in % 8) return set_error(FTMI_ERR_UNSUPPORTED, "ltx_sample_cond: the channel count must be a multiple of 8 (the held prefix moves in 16-byte vectors)");
-    const SampleLayout sl = make_sample_layout(c, two_pass, frames);
+    FfOps ff;
+    FTMI_TRY(ff_ops(c, ffw, &ff));
+    const SampleLayout sl = make_sample_layout(c, two_pass, frames, ff.on);
     const ftmi_ltx_config& mc = sl.mc;
     FTMI_TRY(check_cfg(mc, frames));
     if (ws_bytes < sl.total) return set_error(FTMI_ERR_INVALID, "ltx_sample: workspace too small");
@@ -495,44 +568,50 @@ static int ltx_sample_impl(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, 
         }
         FTMI_TRY(ltx_proj_in(mc, w, L, ws, xin, st));
         if (!hoist) FTMI_TRY(ltx_prologue_text(mc, w, L, ws, text, st));
-        FTMI_TRY(ltx_blocks_tail(mc, w, L, ws, kbias, pred, st, mg));
+        FTMI_TRY(ltx_blocks_tail(mc, w, ff, L, ws, kbias, pred, st, mg));
         FTMI_TRY(cfg_euler_step(pred, x, sigmas + i, sigmas + i + 1, 0, guidance, i + 1 < n_steps ? xin : nullptr, B, per_sample, st, hold));
     }
     return 0;
 }
 
-int ltx_sample(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const bf16_t* text_cond, const bf16_t* text_uncond, const float* kbias_cond,
+int ltx_sample(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const ftmi_ltx_ff_weights* ffw, const bf16_t* text_cond, const bf16_t* text_uncond, const float* kbias_cond,
                const float* kbias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, void* ws, size_t ws_bytes,
                hipStream_t st) {
-    return ltx_sample_impl(c, w, text_cond, text_uncond, kbias_cond, kbias_uncond, x, sigmas, timesteps, n_steps, guidance, 0, 0, ws, ws_bytes, st);
+    return ltx_sample_impl(c, w, ffw, text_cond, text_uncond, kbias_cond, kbias_uncond, x, sigmas, timesteps, n_steps, guidance, 0, 0, ws, ws_bytes, st);
 }
 
-int ltx_sample_cond(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const bf16_t* text_cond, const bf16_t* text_uncond, const float* kbias_cond,
+int ltx_sample_cond(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const ftmi_ltx_ff_weights* ffw, const bf16_t* text_cond, const bf16_t* text_uncond, const float* kbias_cond,
                     const float* kbias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, int frames,
                     int cond_frames, void* ws, size_t ws_bytes, hipStream_t st) {
     if (frames <= 0) return set_error(FTMI_ERR_INVALID, "ltx_sample_cond: frames must be positive");
-    return ltx_sample_impl(c, w, text_cond, text_uncond, kbias_cond, kbias_uncond, x, sigmas, timesteps, n_steps, guidance, frames, cond_frames, ws, ws_bytes, st);
+    return ltx_sample_impl(c, w, ffw, text_cond, text_uncond, kbias_cond, kbias_uncond, x, sigmas, timesteps, n_steps, guidance, frames, cond_frames, ws, ws_bytes, st);
 }
 
 // Backward of blocks [l_lo, l_hi) in descending order (the tail first when l_hi == L).  When the call returns (stream order) the LoRA
 // gradients of exactly those blocks are FINAL -- all 8 adapters, the text-side ones included -- so a data-parallel caller can start
 // the gradient exchange of that block range while the next call computes the blocks below it (DDP's bucketed overlap,
 // finetrainers/parallel/ptd.py:462-463, without a reducer).  State between calls lives in the workspace; l_hi..l_lo must tile L..0.
-int ltx_backward_range(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const bf16_t* text, const float* key_bias, const bf16_t* dpred,
-                       float* grad_a, float* grad_b, void* ws, size_t ws_bytes, int l_hi, int l_lo, int accumulate, hipStream_t st) {
+int ltx_backward_range(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const ftmi_ltx_ff_weights* ffw, const bf16_t* text, const float* key_bias, const bf16_t* dpred,
+                       float* grad_a, float* grad_b, float* grad_ff, void* ws, size_t ws_bytes, int l_hi, int l_lo, int accumulate, hipStream_t st) {
     (void)text;
     FTMI_TRY(check_cfg(c));
     struct ValidWidth {  // (normalisations of a zero-padded narrow model take their mean over d_valid channels; reset when the pass has queued its launches)
         explicit ValidWidth(int dv) { rowwise_set_valid_width(dv); }
         ~ValidWidth() { rowwise_set_valid_width(0); }
     } valid_width_guard(c.d_valid);
-    const WsLayout L = make_layout(c);
+    FfOps ff;
+    FTMI_TRY(ff_ops(c, ffw, &ff));
+    if (ff.on && !grad_ff) return set_error(FTMI_ERR_INVALID, "ltx_backward: feed-forward adapters without their gradient buffer");
+    const WsLayout L = make_layout(c, 0, ff.on);
     if (ws_bytes < L.total) return set_error(FTMI_ERR_INVALID, "ltx_backward: workspace too small");
+    const size_t ff_per_block = 2 * (size_t)c.r * ((size_t)c.D + c.D_ff);  // [A1 r D | B1 F r | A2 r F | B2 D r]
     if (l_lo < 0 || l_hi > c.L || l_lo >= l_hi) return set_error(FTMI_ERR_INVALID, "ltx_backward: bad block range");
     if (c.r > 0 && !accumulate && l_hi == c.L) {  // .grad was None: the weight-gradient kernels accumulate (split-token atomics), so start from zero
         const size_t nbytes = (size_t)c.L * 8 * c.r * c.D * sizeof(float);
         if (hipMemsetAsync(grad_a, 0, nbytes, st) != hipSuccess || hipMemsetAsync(grad_b, 0, nbytes, st) != hipSuccess)
             return set_error(FTMI_ERR_LAUNCH, "ltx_backward: memset of the gradient buffer failed");
+        if (ff.on && hipMemsetAsync(grad_ff, 0, (size_t)c.L * ff_per_block * sizeof(float), st) != hipSuccess)
+            return set_error(FTMI_ERR_LAUNCH, "ltx_backward: memset of the feed-forward gradient buffer failed");
     }
     const int M = c.B * c.S, Mt = c.B * c.T, D = c.D, r = c.r, V = c.gemm_variant;
     const long D2 = (long)D * D;
@@ -604,16 +683,44 @@ int ltx_backward_range(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, cons
             lora_ext_bwd(a, dxa, nadp, r, at_ext, 3L * nadp * r);
             return lora_gemm(a, lora_dxa(a.X, a.ldx, M, nadp, adp, l, dxa), fx, st);
         };
-        if (c.checkpoint) FTMI_TRY(ltx_block_forward(c, w, L, ws, l, key_bias, st, fx, ModGroups{c.B, c.S}));  // the block's activations again, into the one slot
+        if (c.checkpoint) FTMI_TRY(ltx_block_forward(c, w, ff, L, ws, l, key_bias, st, fx, ModGroups{c.B, c.S}));  // the block's activations again, into the one slot
 
         // ---- feed-forward ----
         // (dO holds bf(dhin * gate_mlp): written by the kernel that produced dhin)
-        {
-            GemmNtArgs a = linear_args(dO, D, M, P(w.w_ff2_t, (size_t)l * c.D_ff * D), D, c.D_ff, D, nullptr, W(ws, L.s_dbig), c.D_ff, V);
-            a.epi = EPI_DGELU; a.aux = W(blk, L.z); a.ldaux = c.D_ff;
-            FTMI_TRY(gemm_nt(a, st));
+        const int F = c.D_ff;
+        bf16_t* dz = W(ws, L.s_dbig);
+        // the same for any operand pair: bt_sp = the (hi, lo) row planes of B^T [2r, a.K], at_ext [a.N, 3r] (the rectangular feed-forward adapters)
+        auto proj_bwd_with = [&](GemmNtArgs& a, const bf16_t* bt_sp, const bf16_t* at_ext, bf16_t* dxa) -> int {
+            lora_ext_bwd(a, dxa, 1, r, at_ext, 3L * r);
+            return lora_gemm(a, lora_down_args(a.X, a.ldx, M, bt_sp, 1, a.K, r, s, dxa), fx, st);
+        };
+        if (ff.on && !c.checkpoint) {
+            // n2 and g are scratch shared by all blocks (kept per block they would be 5.5 GB over 28 blocks at M = 5376): written again right before they are read.
+            // Under checkpoint = 1 the recomputation pass above has just refilled both for this block.
+            FTMI_TRY(norm_modulate_fwd(h2, ada + 3 * D, ada + 7 * D, ab, W(ws, L.s_n2), M, c.S, D, c.eps_norm, 0, st));
+            FTMI_TRY(gelu_from_pre(W(blk, L.z), F, W(ws, L.s_g), F, M, F, st));
         }
-        FTMI_TRY(gemm_nt(linear_args(W(ws, L.s_dbig), c.D_ff, M, P(w.w_ff1_t, (size_t)l * D * c.D_ff), c.D_ff, D, c.D_ff, nullptr, d2, D, V), st));
+        {   // dz = (dO W2 [+ dXA2 A2]) * gelu'(z)
+            GemmNtArgs a = linear_args(dO, D, M, P(w.w_ff2_t, (size_t)l * F * D), D, F, D, nullptr, dz, F, V);
+            a.epi = EPI_DGELU; a.aux = W(blk, L.z); a.ldaux = F;
+            if (ff.on) FTMI_TRY(proj_bwd_with(a, ff.b2t_sp + (size_t)l * 2 * r * D, ff.a2t_ext + (size_t)l * F * 3 * r, W(ws, L.s_dxa_ff2)));
+            else FTMI_TRY(gemm_nt(a, st));
+        }
+        {   // dn2 = dz W1 [+ dXA1 A1]
+            GemmNtArgs a = linear_args(dz, F, M, P(w.w_ff1_t, (size_t)l * D * F), F, D, F, nullptr, d2, D, V);
+            if (ff.on) FTMI_TRY(proj_bwd_with(a, ff.b1t_sp + (size_t)l * 2 * r * F, ff.a1t_ext + (size_t)l * D * 3 * r, W(ws, L.s_dxa_ff1)));
+            else FTMI_TRY(gemm_nt(a, st));
+        }
+        if (ff.on) {
+            // the four feed-forward weight gradients of this block now, while dz and the gated dO are live (their operands are not kept per block; with P or Q =
+            // D_ff = 8192 one launch is four times an attention adapter's: no longer latency-sized)
+            float* g0 = grad_ff + (size_t)l * ff_per_block;
+            float *gA1 = g0, *gB1 = gA1 + (size_t)r * D, *gA2 = gB1 + (size_t)F * r, *gB2 = gA2 + (size_t)r * F;
+            FTMI_TRY(gemm_tn(lora_db_args(dO, D, W(blk, L.xa_ff2), 1, r, D, gB2, M), st));                    // dB2 += dO^T XA2
+            FTMI_TRY(gemm_tn(lora_da_args(W(ws, L.s_dxa_ff2), 1, r, W(ws, L.s_g), F, F, gA2, M), st));        // dA2 += dXA2^T g
+            FTMI_TRY(gemm_tn(lora_db_args(dz, F, W(blk, L.xa_ff1), 1, r, F, gB1, M), st));                    // dB1 += dz^T XA1
+            FTMI_TRY(gemm_tn(lora_da_args(W(ws, L.s_dxa_ff1), 1, r, W(ws, L.s_n2), D, D, gA1, M), st));       // dA1 += dXA1^T n2
+        }
         bf16_t* d3 = W(blk, L.g_o2);  // dh2: also the dY of attn2.to_out
         FTMI_TRY(norm_modulate_bwd(h2, d2, ada + 7 * D, ab, dhin, d3, M, c.S, D, c.eps_norm, 0, st));
 

@@ -855,4 +855,45 @@ int transpose_bf16(const bf16_t* in, bf16_t* out, int rows, int cols, hipStream_
     return check_launch("transpose_bf16");
 }
 
+// g = bf16(gelu_tanh(z)) from the stashed pre-activation of a GELU GEMM (rows x width, row strides ldz / ldg).  Both GEMM families round z to bf16 first and
+// compute the activation from the rounded value with gelu_tanh_f, so this reproduces the g they wrote next to z bit for bit: the LTX backward refills its shared
+// g scratch with it instead of keeping 88 MB of g per block.  One 16-byte vector (8 elements) per thread and trip; the width % 8 tail of a row, and every element
+// when a base or a stride breaks the 16-byte alignment, goes through the scalar loop.  Nothing outside the rows x width window is read or written.
+__global__ __launch_bounds__(256) void gelu_from_pre_kernel(const bf16_t* __restrict__ z, long ldz, bf16_t* __restrict__ g, long ldg, int rows, int width, int vec) {
+    const int nv = vec ? width >> 3 : 0;  // whole vectors per row
+    const long nvec = (long)rows * nv;
+    const long stride = (long)gridDim.x * blockDim.x;
+    const long t0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    for (long i = t0; i < nvec; i += stride) {
+        const long r = i / nv;
+        const int c = (int)(i - r * nv) << 3;
+        const u32x4 in = *reinterpret_cast<const u32x4*>(z + r * ldz + c);
+        u32x4 out;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float a = gelu_tanh_f(bf2f((bf16_t)(in[j] & 0xffff)));
+            const float b = gelu_tanh_f(bf2f((bf16_t)(in[j] >> 16)));
+            out[j] = pack2bf(a, b);
+        }
+        *reinterpret_cast<u32x4*>(g + r * ldg + c) = out;
+    }
+    const int tail0 = nv << 3, nt = width - tail0;  // scalar columns [tail0, width) of every row
+    const long ntail = (long)rows * nt;
+    for (long i = t0; i < ntail; i += stride) {
+        const long r = i / nt;
+        const int c = tail0 + (int)(i - r * nt);
+        g[r * ldg + c] = f2bf(gelu_tanh_f(bf2f(z[r * ldz + c])));
+    }
+}
+int gelu_from_pre(const bf16_t* z, long ldz, bf16_t* g, long ldg, int rows, int width, hipStream_t st) {
+    if (rows <= 0 || width <= 0) return 0;
+    if (!z || !g || ldz < width || ldg < width) return set_error(FTMI_ERR_INVALID, "gelu_from_pre: null tensor or a row stride below the width");
+    const int vec = ((reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(g)) % 16 == 0) && ldz % 8 == 0 && ldg % 8 == 0;
+    const long work = vec ? (long)rows * ((width + 7) / 8) : (long)rows * width;
+    long blocks = (work + 255) / 256;
+    if (blocks > 256 * 16) blocks = 256 * 16;  // 16 workgroups of 4 waves per CU, grid-stride beyond
+    hipLaunchKernelGGL(gelu_from_pre_kernel, dim3((unsigned)blocks), dim3(256), 0, st, z, ldz, g, ldg, rows, width, vec);
+    return check_launch("gelu_from_pre");
+}
+
 }  // namespace ftmi

@@ -192,7 +192,9 @@ class MI355XLTXLatentSampler:
         cfg = tr._c_config(B, S, T)
         weights = tr._c_weights(cos, sin)
         conditioned = image_latents is not None or cond_frames is not None
-        ws_bytes = ops.ltx_sample_cond_workspace_bytes(cfg, two_pass, num_frames) if conditioned else ops.ltx_sample_workspace_bytes(cfg, two_pass)
+        # (a model with feed-forward adapters hands over _lib.LtxFfWeights: ops then sizes and runs the _ff twins of the two entries)
+        ws_bytes = (ops.ltx_sample_cond_workspace_bytes(cfg, two_pass, num_frames, weights=weights) if conditioned
+                    else ops.ltx_sample_workspace_bytes(cfg, two_pass, weights=weights))
         ws = tr._acquire_workspace(ws_bytes, dev)
         try:
             if conditioned:

@@ -13,6 +13,9 @@ HBM layout (designed for 288 GB, not ported from the reference's per-module para
     (adapter order q,k,v,out of attn1 then attn2) -> one fused clip+AdamW launch and one contiguous
     all-reduce; the LoRA branch runs at fp32-equivalent precision like the reference's (fp32 adapters,
     trainer.py:132-136): bf16 (hi, lo) working copies of A / B are refreshed after each optimiser step;
+  * with a ``target_modules`` that also names ``ff.net.0.proj`` and ``ff.net.2`` (the control trainer's default) every block gets two more adapters:
+    ``lora_ff_A1`` [L,r,D], ``lora_ff_B1`` [L,F,r], ``lora_ff_A2`` [L,r,F], ``lora_ff_B2`` [L,D,r], strided views of a third region of the same flat
+    buffer ([A | B | FF], FF per block [A1 | B1 | A2 | B2]); the C calls are then the ``ftmi_ltx_ff_*`` twins;
   * all activations of a step live in one caller-owned workspace (about 0.37 GB per block at B=2).
 ``state_dict()`` / ``load_state_dict()`` speak the diffusers + peft key layout (views, no copies); ``lora_state_dict()`` is the
 ``get_peft_model_state_dict`` form.
@@ -30,13 +33,17 @@ import torch
 import torch.nn as nn
 
 from .. import _lib, ops
-from .._lib import LtxConfig, LtxWeights, check, ptr, stream_ptr
+from .._lib import LTX_FF_WEIGHT_FIELDS, LtxConfig, LtxFfWeights, LtxWeights, check, ptr, stream_ptr
 
 bf16 = torch.bfloat16
 
 LORA_ORDER = ("attn1.to_q", "attn1.to_k", "attn1.to_v", "attn1.to_out.0", "attn2.to_q", "attn2.to_k", "attn2.to_v", "attn2.to_out.0")
 # finetrainers/trainer/sft_trainer/config.py:24-26
 DEFAULT_TARGET_MODULES = "(transformer_blocks|single_transformer_blocks).*(to_q|to_k|to_v|to_out.0)"
+# The feed-forward adapters (adapters 8 and 9 of a block), attached when target_modules names them as well -- as the default of the reference's control
+# trainer does (finetrainers/trainer/control_trainer/config.py:60).
+LORA_FF_ORDER = ("ff.net.0.proj", "ff.net.2")
+CONTROL_TARGET_MODULES = "(transformer_blocks|single_transformer_blocks).*(to_q|to_k|to_v|to_out.0|ff.net.0.proj|ff.net.2)"
 
 
 @dataclass
@@ -100,23 +107,24 @@ class _LTXDiTFunction(torch.autograd.Function):
     """One autograd node for the whole DiT: Python overhead is O(1) per step."""
 
     @staticmethod
-    def forward(ctx, module, x_t, text, key_bias, tvals, cos, sin, lora_a, lora_b):
+    def forward(ctx, module, x_t, text, key_bias, tvals, cos, sin, lora_a, lora_b, *lora_ff):
         B, S, _ = x_t.shape
         T = text.shape[1]
         # gradient checkpointing only where a backward will follow (a forward under no_grad keeps every activation readable for the tests / tools)
         cfg = module._c_config(B, S, T, checkpoint=module.gradient_checkpointing and any(ctx.needs_input_grad) and module.lora_A is not None)
         weights = module._c_weights(cos, sin)
         lib = _lib.load()
-        ws_bytes = lib.ftmi_ltx_workspace_bytes(ctypes.byref(cfg))
+        ff = module.lora_ff  # ten adapters per block: the _ff twins of the C entries, over ftmi_ltx_ff_weights
+        ws_bytes = lib.ftmi_ltx_ff_workspace_bytes(ctypes.byref(cfg), ctypes.byref(weights)) if ff else lib.ftmi_ltx_workspace_bytes(ctypes.byref(cfg))
         # the activation workspace (10.4 GB at cfg 2) is recycled across steps instead of going back to the caching allocator:
         # a multi-GB block that is freed and re-requested every step occasionally costs a device-synchronising hipMalloc
         ws = module._acquire_workspace(ws_bytes, x_t.device)
         pred = torch.empty((B, S, module.config.out_channels), dtype=bf16, device=x_t.device)
-        check(lib.ftmi_ltx_forward(ctypes.byref(cfg), ctypes.byref(weights), ptr(x_t), ptr(text), ptr(key_bias), ptr(tvals), ptr(pred),
-                                   ptr(ws), ws_bytes, stream_ptr()), "ftmi_ltx_forward")
+        check((lib.ftmi_ltx_ff_forward if ff else lib.ftmi_ltx_forward)(ctypes.byref(cfg), ctypes.byref(weights), ptr(x_t), ptr(text), ptr(key_bias), ptr(tvals),
+                                                                          ptr(pred), ptr(ws), ws_bytes, stream_ptr()), "ftmi_ltx_forward")
         ctx.module, ctx.cfg, ctx.weights, ctx.ws, ctx.ws_bytes = module, cfg, weights, ws, ws_bytes
         ctx.keep = (x_t, text, key_bias, tvals, cos, sin)
-        module._last_workspace = (cfg, ws)
+        module._last_workspace = (cfg, ws, weights if ff else None)
         if not any(ctx.needs_input_grad) or module.lora_A is None:
             module._release_workspace(ws)  # no backward will come for this call (its content stays readable until the next forward)
             ctx.ws = None
@@ -125,33 +133,41 @@ class _LTXDiTFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dpred):
         module = ctx.module
+        ff = module.lora_ff
+        n_in = 9 + (4 if ff else 0)
         if module.lora_A is None:
-            return (None,) * 9
+            return (None,) * n_in
         dpred = dpred.contiguous()
         # ONE flat fp32 gradient buffer [A | B] -- a contiguous all-reduce per block range and a single clip+AdamW launch downstream.
         # The buffer IS lora_A.grad / lora_B.grad: the kernels write (or, under gradient accumulation, add) straight into it and
         # autograd gets None for the two parameters, so nothing is copied or re-added on the way.
         n_a, n_b = module._lora_A_full.numel(), module._lora_B_full.numel()  # padded rank (== the parameters' own size unless r % 64 != 0)
         ga_live, gb_live = module.lora_A.grad, module.lora_B.grad
+        # ten adapters: the buffer is [A | B | FF], FF per block [A1 | B1 | A2 | B2] like lora_flat, and the four feed-forward .grad are strided views of it
+        ff_params = module._ff_params()
+        n_ff = module._lora_ff_full.numel() if ff else 0
+        ff_live = [p.grad for p in ff_params]
         gflat = module._grad_flat_buf
-        own = gflat is not None and gflat.numel() == n_a + n_b and gflat.device == dpred.device
+        own = gflat is not None and gflat.numel() == n_a + n_b + n_ff and gflat.device == dpred.device
         foreign = None
-        if ga_live is None and gb_live is None:  # zero_grad(set_to_none=True) happened (trainer.py:503): start from zero
+        if ga_live is None and gb_live is None and all(g is None for g in ff_live):  # zero_grad(set_to_none=True) happened (trainer.py:503): start from zero
             if not own:
-                gflat = module._grad_flat_buf = torch.empty(n_a + n_b, dtype=torch.float32, device=dpred.device)
+                gflat = module._grad_flat_buf = torch.empty(n_a + n_b + n_ff, dtype=torch.float32, device=dpred.device)
             accumulate = 0
         elif (own and ga_live is not None and gb_live is not None and ga_live.data_ptr() == gflat.data_ptr()
-              and gb_live.data_ptr() == gflat.data_ptr() + 4 * n_a):
+              and gb_live.data_ptr() == gflat.data_ptr() + 4 * n_a
+              and all(g is not None and g.data_ptr() == gflat.data_ptr() + 4 * (n_a + n_b + off) for g, off in zip(ff_live, module._ff_offsets()))):
             accumulate = 1  # gradient accumulation: add into the live buffer
         else:  # somebody installed their own .grad tensors: compute into a scratch buffer and let autograd accumulate
             if module._grad_bucket_hook is not None or module._grad_bucket_finish is not None:
                 raise RuntimeError("the gradient exchange is installed on this model (apply_ddp / a data-parallel step) but lora_A.grad / lora_B.grad are not the "
                                    "backend's flat gradient buffer: foreign .grad tensors would never be all-reduced and the replicas would diverge silently -- "
                                    "use optimizer.zero_grad(set_to_none=True) (the reference trainer's default) instead of installing .grad tensors")
-            foreign = gflat = torch.empty(n_a + n_b, dtype=torch.float32, device=dpred.device)
+            foreign = gflat = torch.empty(n_a + n_b + n_ff, dtype=torch.float32, device=dpred.device)
             accumulate = 0
         ga = gflat[:n_a].view_as(module._lora_A_full)
-        gb = gflat[n_a:].view_as(module._lora_B_full)
+        gb = gflat[n_a:n_a + n_b].view_as(module._lora_B_full)
+        gff = gflat[n_a + n_b:].view_as(module._lora_ff_full) if ff else None  # [L, per block]
         r_user = module.lora_rank  # the parameters (and their .grad) are the first r_user rows / columns of the padded storage
         _, text, key_bias, _, _, _ = ctx.keep
         lib = _lib.load()
@@ -161,10 +177,17 @@ class _LTXDiTFunction(torch.autograd.Function):
         hi = L
         while hi > 0:  # block ranges in backward order; each range's gradients are final when its call returns (stream order)
             lo = max(0, hi - step)
-            check(lib.ftmi_ltx_backward_range(ctypes.byref(ctx.cfg), ctypes.byref(ctx.weights), ptr(text), ptr(key_bias), ptr(dpred), ptr(ga), ptr(gb),
-                                              ptr(ctx.ws), ctx.ws_bytes, hi, lo, accumulate, stream_ptr()), "ftmi_ltx_backward")
+            if ff:
+                check(lib.ftmi_ltx_ff_backward_range(ctypes.byref(ctx.cfg), ctypes.byref(ctx.weights), ptr(text), ptr(key_bias), ptr(dpred), ptr(ga), ptr(gb),
+                                                     ptr(gff), ptr(ctx.ws), ctx.ws_bytes, hi, lo, accumulate, stream_ptr()), "ftmi_ltx_ff_backward")
+            else:
+                check(lib.ftmi_ltx_backward_range(ctypes.byref(ctx.cfg), ctypes.byref(ctx.weights), ptr(text), ptr(key_bias), ptr(dpred), ptr(ga), ptr(gb),
+                                                  ptr(ctx.ws), ctx.ws_bytes, hi, lo, accumulate, stream_ptr()), "ftmi_ltx_backward")
             if hook is not None:
-                hook(lo, hi, ga[lo:hi], gb[lo:hi])
+                if ff:  # the range's feed-forward gradients are one contiguous slice: a third slice of the same bucket
+                    hook(lo, hi, ga[lo:hi], gb[lo:hi], gff[lo:hi])
+                else:
+                    hook(lo, hi, ga[lo:hi], gb[lo:hi])
             hi = lo
         # MI355XParallelBackend.apply_ddp installs the exchange permanently, the way DDP's reducer sits on the module: the backward then also
         # ends it (the compute stream waits for the last bucket), so an unmodified loop may clip and step right after loss.backward()
@@ -173,12 +196,15 @@ class _LTXDiTFunction(torch.autograd.Function):
             fin()
         module._release_workspace(ctx.ws)
         ctx.ws = None
+        gff_views = module._ff_views(gff) if ff else ()
         if foreign is not None:
-            return None, None, None, None, None, None, None, ga[:, :, :r_user, :], gb[:, :, :, :r_user]
+            return (None, None, None, None, None, None, None, ga[:, :, :r_user, :], gb[:, :, :, :r_user]) + tuple(gff_views)
         module._grad_flat = gflat
         if ga_live is None:
             module.lora_A.grad, module.lora_B.grad = ga[:, :, :r_user, :], gb[:, :, :, :r_user]
-        return (None,) * 9
+            for p_, g_ in zip(ff_params, gff_views):
+                p_.grad = g_
+        return (None,) * n_in
 
 
 class MI355XLTXVideoTransformer3DModel(nn.Module):
@@ -224,6 +250,11 @@ class MI355XLTXVideoTransformer3DModel(nn.Module):
         self.lora_rank = 0
         self.lora_rank_padded = 0
         self._lora_A_full = self._lora_B_full = None
+        # the feed-forward adapters (add_adapter with a target_modules that names them): four more parameters, strided views of lora_flat's third region
+        self.lora_ff = False
+        self.lora_ff_A1 = self.lora_ff_B1 = self.lora_ff_A2 = self.lora_ff_B2 = None
+        self._lora_ff_full = None
+        self.lora_target_modules = None
         self.lora_alpha = 0.0
         self._lora_versions = None
         self._rope_cache: Dict[tuple, Tuple[torch.Tensor, torch.Tensor]] = {}
@@ -381,18 +412,32 @@ class MI355XLTXVideoTransformer3DModel(nn.Module):
             r = getattr(adapter_config, "r", r)
             lora_alpha = getattr(adapter_config, "lora_alpha", lora_alpha)
             target_modules = getattr(adapter_config, "target_modules", target_modules)
+        want_ff = False
         if target_modules is not None:
+            # One matching rule for all ten names: an entry hits a module by re.fullmatch or re.search (what it has always been for the eight).  Served
+            # selections: the eight attention projections, or those plus BOTH feed-forward projections; anything else names the first module it lacks.
             pats = [target_modules] if isinstance(target_modules, str) else list(target_modules)
-            names = [f"transformer_blocks.0.{n}" for n in LORA_ORDER]
-            hit = [any(re.fullmatch(p, n) or re.search(p, n) for p in pats) for n in names]
+            hits = lambda n: any(re.fullmatch(p, n) or re.search(p, n) for p in pats)  # noqa: E731
+            hit = [hits(f"transformer_blocks.0.{n}") for n in LORA_ORDER]
+            hit_ff = [hits(f"transformer_blocks.0.{n}") for n in LORA_FF_ORDER]
             if not all(hit):
-                raise ValueError("the MI355X LTX backend fuses LoRA into to_q/to_k/to_v/to_out.0 of attn1+attn2; "
-                                 f"target_modules={target_modules!r} does not cover exactly that set")
+                missing = LORA_ORDER[hit.index(False)]
+                raise ValueError("the MI355X LTX backend fuses LoRA into to_q/to_k/to_v/to_out.0 of attn1+attn2 (and, with them, into ff.net.0.proj + ff.net.2); "
+                                 f"target_modules={target_modules!r} does not cover exactly that set: it leaves out {missing}")
+            if any(hit_ff) and not all(hit_ff):
+                missing = LORA_FF_ORDER[hit_ff.index(False)]
+                raise ValueError("the MI355X LTX backend attaches the feed-forward adapters as a pair; "
+                                 f"target_modules={target_modules!r} selects one of them and leaves out {missing}")
+            want_ff = all(hit_ff)
+            if want_ff and getattr(self, "_narrow", None) is not None:
+                raise ValueError("the narrow zero-padded geometry (ltx_video/narrow.py) does not pad D_ff for adapters: feed-forward adapters "
+                                 f"(target_modules={target_modules!r}) are not supported on it -- select the eight attention projections")
         if r is None or r <= 0:
             raise ValueError(f"LoRA rank must be positive, got {r}")
         if self.lora_A is not None:
             raise ValueError(f"adapter {adapter_name!r}: an adapter is already attached")
         L, D = self.config.num_layers, self.config.inner_dim
+        F = D * self.config.ff_mult
         # The gfx950 kernels work on ranks that are multiples of 64 (one MFMA K-extension step).  Any other rank -- the reference's LTX
         # example trains with --rank 32 (examples/training/sft/ltx_video/crush_smol_lora/train.sh:75) -- is stored padded: the extra rows
         # of A and columns of B are zero and STAY zero (their gradients are exact zeros: x A_pad^T = 0 and dY B_pad = 0; AdamW and weight
@@ -400,28 +445,72 @@ class MI355XLTXVideoTransformer3DModel(nn.Module):
         # the trainer sees are the [.., :r, :] / [.., :r] views.
         rp = -(-int(r) // 64) * 64
         n = L * 8 * rp * D
-        # one flat fp32 buffer [A | B]; the two Parameters are views into it
-        self.lora_flat = torch.zeros(2 * n, dtype=torch.float32, device=self.device)
+        # one flat fp32 buffer [A | B] (ten adapters: [A | B | FF]); the Parameters are views into it
+        n_ff = L * 2 * rp * (D + F) if want_ff else 0
+        self.lora_flat = torch.zeros(2 * n + n_ff, dtype=torch.float32, device=self.device)
         self._lora_A_full = self.lora_flat[:n].view(L, 8, rp, D)
-        self._lora_B_full = self.lora_flat[n:].view(L, 8, D, rp)
+        self._lora_B_full = self.lora_flat[n:2 * n].view(L, 8, D, rp)
         bound = math.sqrt(6.0 / ((1 + 5.0) * D))  # kaiming_uniform_(a=sqrt(5)) on [r, D]: bound = sqrt(6/((1+a^2) fan_in))
         self._lora_A_full[:, :, :r, :].uniform_(-bound, bound)
         self.lora_A = nn.Parameter(self._lora_A_full[:, :, :r, :])
         self.lora_B = nn.Parameter(self._lora_B_full[:, :, :, :r])
         self.lora_rank, self.lora_alpha = int(r), float(lora_alpha if lora_alpha is not None else r)
         self.lora_rank_padded = rp
+        self.lora_target_modules = target_modules
+        if want_ff:
+            # FF is laid out per block as [A1 rp D | B1 F rp | A2 rp F | B2 D rp]: the feed-forward gradients of a block range are one contiguous slice of the
+            # gradient buffer (same layout), and the four Parameters are strided views [L, ...] into it like the rank-padded A and B
+            self.lora_ff = True
+            self._lora_ff_full = self.lora_flat[2 * n:].view(L, 2 * rp * (D + F))
+            a1, b1, a2, b2 = self._ff_views(self._lora_ff_full, padded=True)
+            a1[:, :r, :].uniform_(-bound, bound)  # kaiming_uniform_(a=sqrt(5)) on [r, D]: 1 / sqrt(D)
+            a2[:, :r, :].uniform_(-1.0 / math.sqrt(F), 1.0 / math.sqrt(F))  # ... on [r, F]: 1 / sqrt(F)
+            self.lora_ff_A1, self.lora_ff_B1 = nn.Parameter(a1[:, :r, :]), nn.Parameter(b1[:, :, :r])
+            self.lora_ff_A2, self.lora_ff_B2 = nn.Parameter(a2[:, :r, :]), nn.Parameter(b2[:, :, :r])
         r = rp  # working copies and kernels: padded rank
         # bf16 (hi, lo) working copies for the fp32-equivalent LoRA branch (include/ftmi355.h, ftmi_ltx_weights)
         for n, shp in (("lora_a_sp", (L, 8, 2 * r, D)), ("lora_bt_sp", (L, 8, 2 * r, D)), ("lora_b_ext", (L, 8, D, 3 * r)),
                        ("lora_at_ext", (L, 8, D, 3 * r)), ("lora_at_qkv_ext", (L, D, 9 * r))):
             self.register_buffer(n, torch.zeros(shp, dtype=bf16, device=self.device), persistent=False)
+        if want_ff:  # include/ftmi355.h, ftmi_ltx_ff_weights
+            for n, shp in (("ff_a1_sp", (L, 2 * r, D)), ("ff_a1t_ext", (L, D, 3 * r)), ("ff_b1_ext", (L, F, 3 * r)), ("ff_b1t_sp", (L, 2 * r, F)),
+                           ("ff_a2_sp", (L, 2 * r, F)), ("ff_a2t_ext", (L, F, 3 * r)), ("ff_b2_ext", (L, D, 3 * r)), ("ff_b2t_sp", (L, 2 * r, D))):
+                self.register_buffer(n, torch.zeros(shp, dtype=bf16, device=self.device), persistent=False)
         self._lora_versions = None
+
+    # ---- the feed-forward region of lora_flat / of the gradient buffer ----
+    def _ff_offsets(self) -> Tuple[int, int, int, int]:
+        """Element offsets of A1, B1, A2, B2 inside one block's feed-forward record."""
+        D, rp = self.config.inner_dim, self.lora_rank_padded
+        F = D * self.config.ff_mult
+        return 0, rp * D, rp * D + F * rp, rp * D + 2 * F * rp
+
+    def _ff_views(self, full: torch.Tensor, padded: bool = False):
+        """(A1 [L, r, D], B1 [L, F, r], A2 [L, r, F], B2 [L, D, r]) as strided views of a [L, per-block] feed-forward region (parameters or gradients);
+        ``padded``: the rank-padded storage instead of the first ``lora_rank`` rows / columns."""
+        D, rp, r = self.config.inner_dim, self.lora_rank_padded, self.lora_rank
+        F = D * self.config.ff_mult
+        L = full.shape[0]
+        o = self._ff_offsets()
+        a1 = full[:, o[0]:o[1]].view(L, rp, D)
+        b1 = full[:, o[1]:o[2]].view(L, F, rp)
+        a2 = full[:, o[2]:o[3]].view(L, rp, F)
+        b2 = full[:, o[3]:].view(L, D, rp)
+        if padded:
+            return a1, b1, a2, b2
+        return a1[:, :r, :], b1[:, :, :r], a2[:, :r, :], b2[:, :, :r]
+
+    def _ff_params(self):
+        return (self.lora_ff_A1, self.lora_ff_B1, self.lora_ff_A2, self.lora_ff_B2) if self.lora_ff else ()
 
     def lora_views(self) -> Iterable[Tuple[str, torch.Tensor, torch.Tensor]]:
         """(module path, A view [r,D], B view [D,r]) for each of the L*8 adapters (views into the flat parameters)."""
         for l in range(self.config.num_layers):
             for i, n in enumerate(LORA_ORDER):
                 yield f"transformer_blocks.{l}.{n}", self.lora_A[l, i], self.lora_B[l, i]
+            if self.lora_ff:
+                yield f"transformer_blocks.{l}.{LORA_FF_ORDER[0]}", self.lora_ff_A1[l], self.lora_ff_B1[l]
+                yield f"transformer_blocks.{l}.{LORA_FF_ORDER[1]}", self.lora_ff_A2[l], self.lora_ff_B2[l]
 
     def lora_state_dict(self, adapter_name: Optional[str] = None) -> Dict[str, torch.Tensor]:
         """peft-format keys (what ``get_peft_model_state_dict`` returns: adapter name stripped)."""
@@ -435,6 +524,10 @@ class MI355XLTXVideoTransformer3DModel(nn.Module):
     @torch.no_grad()
     def load_lora_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
         sd = {k.replace(".default.", "."): v for k, v in sd.items()}
+        file_ff = any(f".{LORA_FF_ORDER[0]}.lora_" in k or f".{LORA_FF_ORDER[1]}.lora_" in k for k in sd)
+        if file_ff != self.lora_ff:
+            raise ValueError("load_lora_state_dict: the state dict " + ("holds" if file_ff else "does not hold") + " feed-forward adapters (ff.net.0.proj / ff.net.2) "
+                             "and the model " + ("has them" if self.lora_ff else "has none") + ": attach the adapter with the target_modules the file was trained with")
         for path, a, b in self.lora_views():
             a.copy_(sd[f"{path}.lora_A.weight"].to(a))
             b.copy_(sd[f"{path}.lora_B.weight"].to(b))
@@ -513,6 +606,10 @@ class MI355XLTXVideoTransformer3DModel(nn.Module):
         if self.lora_A.data_ptr() != self.lora_flat.data_ptr() or self.lora_B.data_ptr() != self.lora_flat.data_ptr() + 4 * n:
             raise RuntimeError("lora_A / lora_B no longer alias transformer.lora_flat (the module was moved or re-assigned after add_adapter); "
                                "re-attach the adapter on the target device")
+        for p_, off in zip(self._ff_params(), self._ff_offsets() if self.lora_ff else ()):
+            if p_.data_ptr() != self.lora_flat.data_ptr() + 4 * (2 * n + off):
+                raise RuntimeError("the feed-forward LoRA parameters no longer alias transformer.lora_flat (the module was moved or re-assigned after "
+                                   "add_adapter); re-attach the adapter on the target device")
 
     def lora_grad_views(self) -> Dict[str, torch.Tensor]:
         out = {}
@@ -522,19 +619,33 @@ class MI355XLTXVideoTransformer3DModel(nn.Module):
             for i, n in enumerate(LORA_ORDER):
                 out[f"transformer_blocks.{l}.{n}.lora_A.weight"] = self.lora_A.grad[l, i]
                 out[f"transformer_blocks.{l}.{n}.lora_B.weight"] = self.lora_B.grad[l, i]
+            if self.lora_ff and self.lora_ff_A1.grad is not None:
+                for n, pa, pb in ((LORA_FF_ORDER[0], self.lora_ff_A1, self.lora_ff_B1), (LORA_FF_ORDER[1], self.lora_ff_A2, self.lora_ff_B2)):
+                    out[f"transformer_blocks.{l}.{n}.lora_A.weight"] = pa.grad[l]
+                    out[f"transformer_blocks.{l}.{n}.lora_B.weight"] = pb.grad[l]
         return out
 
     @torch.no_grad()
     def refresh_lora_copies(self, force: bool = False) -> None:
         if self.lora_A is None:
             return
-        ver = (self.lora_A._version, self.lora_B._version, self.lora_A.data_ptr(), self.lora_B.data_ptr())
+        ver = (self.lora_A._version, self.lora_B._version, self.lora_A.data_ptr(), self.lora_B.data_ptr()) + tuple(p_._version for p_ in self._ff_params())
         if not force and ver == self._lora_versions:
             return
         c = self.config
         check(_lib.load().ftmi_lora_refresh(ptr(self._lora_A_full), ptr(self._lora_B_full), ptr(self.lora_a_sp), ptr(self.lora_bt_sp), ptr(self.lora_b_ext),
                                              ptr(self.lora_at_ext), ptr(self.lora_at_qkv_ext), c.num_layers, self.lora_rank_padded, c.inner_dim, stream_ptr()),
               "ftmi_lora_refresh")
+        if self.lora_ff:  # one launch per matrix family over the L blocks (block stride = one feed-forward record)
+            D, rp = c.inner_dim, self.lora_rank_padded
+            F = D * c.ff_mult
+            per_block = self._lora_ff_full.shape[1]
+            base, o = self._lora_ff_full.data_ptr(), self._ff_offsets()
+            lib = _lib.load()
+            for off, rows, cols, sp, ext, t_sp, t_ext in ((o[0], rp, D, self.ff_a1_sp, None, None, self.ff_a1t_ext), (o[1], F, rp, None, self.ff_b1_ext, self.ff_b1t_sp, None),
+                                                          (o[2], rp, F, self.ff_a2_sp, None, None, self.ff_a2t_ext), (o[3], D, rp, None, self.ff_b2_ext, self.ff_b2t_sp, None)):
+                check(lib.ftmi_lora_refresh_rect(base + 4 * off, per_block, c.num_layers, rows, cols, ptr(sp), ptr(ext), ptr(t_sp), ptr(t_ext), stream_ptr()),
+                      "ftmi_lora_refresh_rect")
         self._lora_versions = ver
 
     # ------------------------------------------------------------------ C structs
@@ -547,8 +658,17 @@ class MI355XLTXVideoTransformer3DModel(nn.Module):
                          # (a narrow model embedded by zero padding -- ltx_video/narrow.py -- tells the kernels its true width and head width; 0 = this geometry)
                          d_valid=getattr(self, "_narrow", (0, 0))[0], head_dim_valid=getattr(self, "_narrow", (0, 0))[1])
 
-    def _c_weights(self, cos: torch.Tensor, sin: torch.Tensor) -> LtxWeights:
-        w = LtxWeights()
+    def _c_weights(self, cos: torch.Tensor, sin: torch.Tensor):
+        """``LtxWeights``; with the feed-forward adapters ``LtxFfWeights`` (the base first, then their operand copies) for the ``_ff`` entries."""
+        if self.lora_ff:
+            wf = LtxFfWeights()
+            self._fill_c_weights(wf.base, cos, sin)
+            for n in LTX_FF_WEIGHT_FIELDS:
+                setattr(wf, n, getattr(self, n).data_ptr())
+            return wf
+        return self._fill_c_weights(LtxWeights(), cos, sin)
+
+    def _fill_c_weights(self, w: LtxWeights, cos: torch.Tensor, sin: torch.Tensor) -> LtxWeights:
         for n in self._frozen_names:
             setattr(w, n, getattr(self, n).data_ptr())
         if self.lora_A is not None:
@@ -598,7 +718,7 @@ class MI355XLTXVideoTransformer3DModel(nn.Module):
         self.refresh_lora_copies()
         la = self.lora_A if self.lora_A is not None else None
         lb = self.lora_B if self.lora_B is not None else None
-        out = _LTXDiTFunction.apply(self, x_t, text, key_bias, tvals, cos, sin, la, lb)
+        out = _LTXDiTFunction.apply(self, x_t, text, key_bias, tvals, cos, sin, la, lb, *self._ff_params())
         if not return_dict:
             return (out,)
         return {"sample": out}
@@ -631,9 +751,10 @@ class MI355XLTXVideoTransformer3DModel(nn.Module):
         cos, sin = self.rope_tables(num_frames, height, width, rope_interpolation_scale)
         self.refresh_lora_copies()
         cfg = self._c_config(B, S, T)
-        ws = self._acquire_workspace(ops.ltx_forward_frames_workspace_bytes(cfg, num_frames), x_t.device)
+        weights = self._c_weights(cos, sin)
+        ws = self._acquire_workspace(ops.ltx_forward_frames_workspace_bytes(cfg, num_frames, weights=weights), x_t.device)
         try:
-            out = ops.ltx_forward_frames(cfg, self._c_weights(cos, sin), x_t, text, key_bias, tvals, workspace=ws)
+            out = ops.ltx_forward_frames(cfg, weights, x_t, text, key_bias, tvals, workspace=ws)
         finally:
             self._release_workspace(ws)
         if not return_dict:
@@ -655,9 +776,12 @@ class MI355XLTXVideoTransformer3DModel(nn.Module):
     # ------------------------------------------------------------------ debugging / tests
     def workspace_tensor(self, name: str, layer: int, shape, dtype=bf16) -> torch.Tensor:
         """View of a stashed activation of the most recent forward (tests / debugging only)."""
-        cfg, ws = self._last_workspace
+        cfg, ws, ffw = self._last_workspace
         off = ctypes.c_size_t(0)
-        check(_lib.load().ftmi_ltx_workspace_offset(ctypes.byref(cfg), name.encode(), layer, ctypes.byref(off)), "ftmi_ltx_workspace_offset")
+        if ffw is not None:  # the ten-adapter layout (also knows "xa_ff1" / "xa_ff2")
+            check(_lib.load().ftmi_ltx_ff_workspace_offset(ctypes.byref(cfg), ctypes.byref(ffw), name.encode(), layer, ctypes.byref(off)), "ftmi_ltx_ff_workspace_offset")
+        else:
+            check(_lib.load().ftmi_ltx_workspace_offset(ctypes.byref(cfg), name.encode(), layer, ctypes.byref(off)), "ftmi_ltx_workspace_offset")
         n = 1
         for s in shape:
             n *= s

@@ -465,7 +465,14 @@ def ltx_cfg_euler_step_held(pred, x, sigma, sigma_next, guidance: float, hold: i
     return x_next
 
 
-def ltx_forward_frames_workspace_bytes(cfg, frames: int) -> int:
+def _ltx_ff(weights) -> bool:
+    """True for the ten-adapter model's weights (``_lib.LtxFfWeights``): the ``_ff`` twins of the LTX entries take them."""
+    return isinstance(weights, _lib.LtxFfWeights)
+
+
+def ltx_forward_frames_workspace_bytes(cfg, frames: int, weights=None) -> int:
+    if _ltx_ff(weights):
+        return int(_lib.load().ftmi_ltx_ff_forward_frames_workspace_bytes(ctypes.byref(cfg), ctypes.byref(weights), int(frames)))
     return int(_lib.load().ftmi_ltx_forward_frames_workspace_bytes(ctypes.byref(cfg), int(frames)))
 
 
@@ -489,16 +496,34 @@ def ltx_forward_frames(cfg, weights, x_t, text, key_bias, timesteps, workspace=N
         require_gpu_tensor(key_bias, "key_bias", torch.float32)
         if tuple(key_bias.shape) != (B, T) or not key_bias.is_contiguous():
             raise ValueError(f"ltx_forward_frames: key_bias must be a contiguous [{B}, {T}] tensor")
-    ws_bytes = ltx_forward_frames_workspace_bytes(cfg, frames)
+    ws_bytes = ltx_forward_frames_workspace_bytes(cfg, frames, weights=weights)
     if workspace is None:
         workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=x_t.device)
     elif workspace.numel() < ws_bytes:
         raise ValueError("ltx_forward_frames: workspace too small")
     if pred is None:
         pred = torch.empty((B, S, cfg.C_out), dtype=bf16, device=x_t.device)
-    check(_lib.load().ftmi_ltx_forward_frames(ctypes.byref(cfg), ctypes.byref(weights), ptr(x_t), ptr(text), ptr(key_bias), ptr(timesteps), frames, ptr(pred),
-                                               ptr(workspace), workspace.numel(), stream_ptr()), "ftmi_ltx_forward_frames")
+    lib = _lib.load()
+    check((lib.ftmi_ltx_ff_forward_frames if _ltx_ff(weights) else lib.ftmi_ltx_forward_frames)(ctypes.byref(cfg), ctypes.byref(weights), ptr(x_t), ptr(text), ptr(key_bias), ptr(timesteps), frames, ptr(pred),
+        ptr(workspace), workspace.numel(), stream_ptr()), "ftmi_ltx_forward_frames")
     return pred
+
+
+def gelu_from_pre(z, out=None):
+    """``g = bf16(gelu_tanh(z))`` from the bf16 pre-activation a GELU GEMM stashed (include/ftmi355.h: ftmi_gelu_from_pre): the bits that GEMM wrote as its
+    activation.  ``z`` [rows, width] with any row stride (a column window of a wider tensor is fine); ``out`` likewise, allocated contiguous when None."""
+    require_gpu_tensor(z, "z", bf16)
+    if z.ndim != 2 or (z.shape[1] > 1 and z.stride(1) != 1):
+        raise ValueError("gelu_from_pre: z must be [rows, width] with unit column stride")
+    rows, width = z.shape
+    if out is None:
+        out = torch.empty((rows, width), dtype=bf16, device=z.device)
+    require_gpu_tensor(out, "out", bf16)
+    if tuple(out.shape) != (rows, width) or (width > 1 and out.stride(1) != 1):
+        raise ValueError("gelu_from_pre: out must be shaped like z with unit column stride")
+    check(_lib.load().ftmi_gelu_from_pre(ptr(z), z.stride(0) if rows > 1 else max(width, z.stride(0)), ptr(out), out.stride(0) if rows > 1 else max(width, out.stride(0)),
+                                          rows, width, stream_ptr()), "ftmi_gelu_from_pre")
+    return out
 
 
 def ltx_unpack_denorm(x, mean, std, num_frames: int, height: int, width: int):
@@ -517,7 +542,9 @@ def ltx_unpack_denorm(x, mean, std, num_frames: int, height: int, width: int):
     return out
 
 
-def ltx_sample_workspace_bytes(cfg, two_pass: bool) -> int:
+def ltx_sample_workspace_bytes(cfg, two_pass: bool, weights=None) -> int:
+    if _ltx_ff(weights):
+        return int(_lib.load().ftmi_ltx_ff_sample_workspace_bytes(ctypes.byref(cfg), ctypes.byref(weights), int(bool(two_pass))))
     return int(_lib.load().ftmi_ltx_sample_workspace_bytes(ctypes.byref(cfg), int(bool(two_pass))))
 
 
@@ -551,18 +578,21 @@ def ltx_sample(cfg, weights, text_cond, text_uncond, key_bias_cond, key_bias_unc
             require_gpu_tensor(b, name, torch.float32)
             if tuple(b.shape) != (B, T) or not b.is_contiguous():
                 raise ValueError(f"ltx_sample: {name} must be a contiguous [{B}, {T}] tensor")
-    ws_bytes = ltx_sample_workspace_bytes(cfg, two_pass)
+    ws_bytes = ltx_sample_workspace_bytes(cfg, two_pass, weights=weights)
     if workspace is None:
         workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=x.device)
     elif workspace.numel() < ws_bytes:
         raise ValueError("ltx_sample: workspace too small")
-    check(_lib.load().ftmi_ltx_sample(ctypes.byref(cfg), ctypes.byref(weights), ptr(text_cond), ptr(text_uncond) if two_pass else None, ptr(key_bias_cond),
-                                       ptr(key_bias_uncond) if two_pass else None, ptr(x), ptr(sigmas), ptr(timesteps), n, float(guidance), ptr(workspace),
-                                       workspace.numel(), stream_ptr()), "ftmi_ltx_sample")
+    lib = _lib.load()
+    check((lib.ftmi_ltx_ff_sample if _ltx_ff(weights) else lib.ftmi_ltx_sample)(ctypes.byref(cfg), ctypes.byref(weights), ptr(text_cond), ptr(text_uncond) if two_pass else None, ptr(key_bias_cond),
+        ptr(key_bias_uncond) if two_pass else None, ptr(x), ptr(sigmas), ptr(timesteps), n, float(guidance), ptr(workspace),
+        workspace.numel(), stream_ptr()), "ftmi_ltx_sample")
     return x
 
 
-def ltx_sample_cond_workspace_bytes(cfg, two_pass: bool, frames: int) -> int:
+def ltx_sample_cond_workspace_bytes(cfg, two_pass: bool, frames: int, weights=None) -> int:
+    if _ltx_ff(weights):
+        return int(_lib.load().ftmi_ltx_ff_sample_cond_workspace_bytes(ctypes.byref(cfg), ctypes.byref(weights), int(bool(two_pass)), int(frames)))
     return int(_lib.load().ftmi_ltx_sample_cond_workspace_bytes(ctypes.byref(cfg), int(bool(two_pass)), int(frames)))
 
 
@@ -601,14 +631,15 @@ def ltx_sample_cond(cfg, weights, text_cond, text_uncond, key_bias_cond, key_bia
             require_gpu_tensor(b, name, torch.float32)
             if tuple(b.shape) != (B, T) or not b.is_contiguous():
                 raise ValueError(f"ltx_sample_cond: {name} must be a contiguous [{B}, {T}] tensor")
-    ws_bytes = ltx_sample_cond_workspace_bytes(cfg, two_pass, frames)
+    ws_bytes = ltx_sample_cond_workspace_bytes(cfg, two_pass, frames, weights=weights)
     if workspace is None:
         workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=x.device)
     elif workspace.numel() < ws_bytes:
         raise ValueError("ltx_sample_cond: workspace too small")
-    check(_lib.load().ftmi_ltx_sample_cond(ctypes.byref(cfg), ctypes.byref(weights), ptr(text_cond), ptr(text_uncond) if two_pass else None,
-                                            ptr(key_bias_cond), ptr(key_bias_uncond) if two_pass else None, ptr(x), ptr(sigmas), ptr(timesteps), n,
-                                            float(guidance), frames, cond_frames, ptr(workspace), workspace.numel(), stream_ptr()), "ftmi_ltx_sample_cond")
+    lib = _lib.load()
+    check((lib.ftmi_ltx_ff_sample_cond if _ltx_ff(weights) else lib.ftmi_ltx_sample_cond)(ctypes.byref(cfg), ctypes.byref(weights), ptr(text_cond), ptr(text_uncond) if two_pass else None,
+        ptr(key_bias_cond), ptr(key_bias_uncond) if two_pass else None, ptr(x), ptr(sigmas), ptr(timesteps), n,
+        float(guidance), frames, cond_frames, ptr(workspace), workspace.numel(), stream_ptr()), "ftmi_ltx_sample_cond")
     return x
 
 

@@ -278,10 +278,13 @@ class GradBucketReducer:
         self.buckets_issued += 1
         self.exchange_buckets += 1
 
-    def bucket_ready(self, l_lo: int, l_hi: int, grad_a: torch.Tensor, grad_b: torch.Tensor) -> None:
-        """Hook signature of ``MI355XLTXVideoTransformer3DModel._grad_bucket_hook``."""
+    def bucket_ready(self, l_lo: int, l_hi: int, grad_a: torch.Tensor, grad_b: torch.Tensor, grad_ff: Optional[torch.Tensor] = None) -> None:
+        """Hook signature of ``MI355XLTXVideoTransformer3DModel._grad_bucket_hook``.  ``grad_ff``: the range's feed-forward gradients (the ten-adapter LTX
+        model: one more contiguous slice of the same bucket)."""
         self.slice_ready(grad_a)
         self.slice_ready(grad_b)
+        if grad_ff is not None:
+            self.slice_ready(grad_ff)
         self._bucket_issued()
 
     def span_done(self, span) -> None:

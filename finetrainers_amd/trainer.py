@@ -82,8 +82,10 @@ class MI355XSFTStep(FlatLoRAStep):
         self._micro_step = 0
         dev = transformer.device
         transformer._assert_flat_aliasing()
-        # flat fp32 optimiser state matching transformer.lora_flat = [A | B]
+        # flat fp32 optimiser state matching transformer.lora_flat = [A | B] (with feed-forward adapters [A | B | FF]: the fused clip + AdamW and the
+        # exchange cover the whole buffer either way)
         self.n_a, self.n_b = transformer._lora_A_full.numel(), transformer._lora_B_full.numel()  # storage size (rank padded to a multiple of 64)
+        self.n_ff = transformer._lora_ff_full.numel() if getattr(transformer, "lora_ff", False) else 0
         self._init_optimizer(transformer.lora_flat, lr, betas, eps, weight_decay, max_grad_norm, lr_scheduler)
         # MI355XParallelBackend.apply_ddp() installs the exchange ON THE MODEL (hook + finish, like DDP's reducer): a step that is handed such a model
         # leaves those hooks where they are -- the backward then returns with averaged gradients -- and must not bring a second exchange of its own
@@ -144,12 +146,14 @@ class MI355XSFTStep(FlatLoRAStep):
             # the reference clips after every backward (trainer.py:487-492), i.e. also the partial sums of an accumulation window -- in place
             # on .grad (under DP on the all-reduced sums, see no_sync_accumulation)
             if self.max_grad_norm and self.max_grad_norm > 0 and (self.reducer is None or exchange):
-                ops.clip_grad_norm_(self._flat_grad(tr.lora_A.grad, tr.lora_B.grad), self.max_grad_norm, scratch=self._scratch)
+                ops.clip_grad_norm_(self._flat_grad(tr.lora_A.grad, tr.lora_B.grad, [p.grad for p in self._ff_params()]), self.max_grad_norm, scratch=self._scratch)
             return {"loss": loss.detach(), "grad_norm": None}
         # 5-6. clip + AdamW, fused over the flat buffer
-        grad_norm = self._clip_adamw(tr.lora_flat, self._flat_grad(tr.lora_A.grad, tr.lora_B.grad))
+        grad_norm = self._clip_adamw(tr.lora_flat, self._flat_grad(tr.lora_A.grad, tr.lora_B.grad, [p.grad for p in self._ff_params()]))
         tr.lora_A.grad = None  # optimizer.zero_grad(set_to_none=True) (trainer.py:503)
         tr.lora_B.grad = None
+        for p in self._ff_params():
+            p.grad = None
         return {"loss": loss.detach(), "grad_norm": grad_norm}
 
     # ---- the model's hooks for the duration of the backward ---------------------------------------------------------------------------------
@@ -173,15 +177,25 @@ class MI355XSFTStep(FlatLoRAStep):
         hyper = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay, "max_grad_norm": self.max_grad_norm}
         return dict(super().state_dict(), hyper=hyper)
 
-    def _flat_grad(self, ga: torch.Tensor, gb: torch.Tensor) -> torch.Tensor:
+    def _ff_params(self):
+        tr = self.transformer
+        return tr._ff_params() if self.n_ff else ()
+
+    def _flat_grad(self, ga: torch.Tensor, gb: torch.Tensor, gff=()) -> torch.Tensor:
         gflat = self.transformer._grad_flat
-        if gflat is not None and ga.data_ptr() == gflat.data_ptr() and gb.data_ptr() == gflat.data_ptr() + 4 * self.n_a:
+        n_ab = self.n_a + self.n_b
+        ff_own = self.n_ff == 0 or (gflat is not None and all(g is not None and g.data_ptr() == gflat.data_ptr() + 4 * (n_ab + off)
+                                                              for g, off in zip(gff, self.transformer._ff_offsets())))
+        if gflat is not None and ga.data_ptr() == gflat.data_ptr() and gb.data_ptr() == gflat.data_ptr() + 4 * self.n_a and ff_own:
             return gflat  # .grad IS the flat buffer the kernels wrote (the usual case)
         if self.reducer is not None:
             raise RuntimeError("data-parallel step: lora_A.grad / lora_B.grad are not the backend's flat gradient buffer (foreign .grad tensors "
                                "were installed); the bucketed exchange would have missed them")
         tr = self.transformer  # foreign .grad tensors (single GPU only): lay them out like the (rank-padded) parameter storage
-        flat = torch.zeros(self.n_a + self.n_b, dtype=torch.float32, device=ga.device)
+        flat = torch.zeros(n_ab + self.n_ff, dtype=torch.float32, device=ga.device)
         flat[:self.n_a].view_as(tr._lora_A_full)[:, :, :tr.lora_rank, :].copy_(ga)
-        flat[self.n_a:].view_as(tr._lora_B_full)[:, :, :, :tr.lora_rank].copy_(gb)
+        flat[self.n_a:n_ab].view_as(tr._lora_B_full)[:, :, :, :tr.lora_rank].copy_(gb)
+        if self.n_ff:
+            for dst, g in zip(tr._ff_views(flat[n_ab:].view_as(tr._lora_ff_full)), gff):
+                dst.copy_(g)
         return flat

@@ -324,10 +324,27 @@ def _lora_param_views(lora_rank: int, a_full: torch.Tensor, b_full: torch.Tensor
         yield f"{path}.lora_B.default.weight", b_full[l, i, :, :lora_rank]
 
 
+def _ff_moment_views(tr, ff_region: torch.Tensor):
+    """(fqn, view) of the feed-forward adapters' tensors inside a [L, per-block] region laid out like ``transformer._lora_ff_full`` (a moment buffer)."""
+    a1, b1, a2, b2 = tr._ff_views(ff_region)
+    for l in range(ff_region.shape[0]):
+        p = f"transformer_blocks.{l}."
+        yield p + "ff.net.0.proj.lora_A.default.weight", a1[l]
+        yield p + "ff.net.0.proj.lora_B.default.weight", b1[l]
+        yield p + "ff.net.2.lora_A.default.weight", a2[l]
+        yield p + "ff.net.2.lora_B.default.weight", b2[l]
+
+
+def _attn_lora_paths(tr) -> List[str]:
+    """Module paths of the adapters that live in lora_A / lora_B (the feed-forward ones have their own region of the flat buffer)."""
+    return [p for p, _, _ in tr.lora_views() if ".ff.net." not in p]
+
+
 def training_state_dict(model_state_dict: Dict[str, torch.Tensor], lora_paths: List[str], lora_rank: int, exp_avg_a: torch.Tensor,
                         exp_avg_b: torch.Tensor, exp_avg_sq_a: torch.Tensor, exp_avg_sq_b: torch.Tensor, step_count: int, hyper: Dict[str, Any],
                         lr_scheduler_state: Optional[Dict[str, Any]] = None, train_state: Optional[Dict[str, Any]] = None,
-                        dataloader_state: Optional[Dict[str, Any]] = None, dp_rank: int = 0) -> Dict[str, Any]:
+                        dataloader_state: Optional[Dict[str, Any]] = None, dp_rank: int = 0,
+                        extra_moments: Optional[Dict[str, Tuple[torch.Tensor, torch.Tensor]]] = None) -> Dict[str, Any]:
     """The nested dictionary the reference hands to ``torch.distributed.checkpoint.save``.  ``exp_avg_a`` ... are the moments in the
     transformer's (rank-padded) parameter storage shapes; ``hyper``: lr, betas, eps, weight_decay; ``train_state``: step,
     observed_data_samples, global_avg_losses, global_max_losses, log_steps."""
@@ -336,6 +353,8 @@ def training_state_dict(model_state_dict: Dict[str, torch.Tensor], lora_paths: L
     opt: Dict[str, Any] = {}
     m1 = dict(_lora_param_views(lora_rank, exp_avg_a, exp_avg_b, lora_paths))
     m2 = dict(_lora_param_views(lora_rank, exp_avg_sq_a, exp_avg_sq_b, lora_paths))
+    for fqn, (e1, e2) in (extra_moments or {}).items():  # fqn -> (exp_avg, exp_avg_sq) of parameters outside lora_A / lora_B (LTX feed-forward adapters)
+        m1[fqn], m2[fqn] = e1, e2
     for fqn in m1:
         opt[f"state.{fqn}.step"] = torch.tensor(float(step_count), dtype=torch.float32)
         opt[f"state.{fqn}.exp_avg"] = m1[fqn]
@@ -386,15 +405,22 @@ def save_training_state(output_dir: str, step: int, transformer, sft_step, train
 
     tr = transformer
     n_a = tr._lora_A_full.numel()
+    n_ab = n_a + tr._lora_B_full.numel()
     sched = getattr(sft_step, "lr_scheduler", None)
     lr_now = sft_step.lr if sched is None else sched.current_lr()
+    extra = None
+    if getattr(tr, "lora_ff", False):  # the third region of the flat moment buffers, under the feed-forward adapters' peft names
+        m1 = dict(_ff_moment_views(tr, sft_step.exp_avg[n_ab:].view_as(tr._lora_ff_full).cpu()))
+        m2 = dict(_ff_moment_views(tr, sft_step.exp_avg_sq[n_ab:].view_as(tr._lora_ff_full).cpu()))
+        extra = {k: (m1[k], m2[k]) for k in m1}
     sd = training_state_dict(
-        {k: v.detach().cpu() for k, v in tr.state_dict().items()}, [p for p, _, _ in tr.lora_views()], tr.lora_rank,
-        sft_step.exp_avg[:n_a].view_as(tr._lora_A_full).cpu(), sft_step.exp_avg[n_a:].view_as(tr._lora_B_full).cpu(),
-        sft_step.exp_avg_sq[:n_a].view_as(tr._lora_A_full).cpu(), sft_step.exp_avg_sq[n_a:].view_as(tr._lora_B_full).cpu(),
+        {k: v.detach().cpu() for k, v in tr.state_dict().items()}, _attn_lora_paths(tr), tr.lora_rank,
+        sft_step.exp_avg[:n_a].view_as(tr._lora_A_full).cpu(), sft_step.exp_avg[n_a:n_ab].view_as(tr._lora_B_full).cpu(),
+        sft_step.exp_avg_sq[:n_a].view_as(tr._lora_A_full).cpu(), sft_step.exp_avg_sq[n_a:n_ab].view_as(tr._lora_B_full).cpu(),
         sft_step.step_count, {"lr": lr_now, "betas": sft_step.betas, "eps": sft_step.eps, "weight_decay": sft_step.weight_decay, "initial_lr": sft_step.lr},
         lr_scheduler_state=None if sched is None else lambda_lr_state(sched.base_lr, sched.last_epoch, lr_now),
-        train_state=train_state, dataloader_state=dataloader_state, dp_rank=dp_rank)  # every data-parallel rank writes ITS dataloader entry (dp_rank_<r>)
+        train_state=train_state, dataloader_state=dataloader_state, dp_rank=dp_rank,  # every data-parallel rank writes ITS dataloader entry (dp_rank_<r>)
+        extra_moments=extra)
     path = os.path.join(output_dir, f"{DCP_PREFIX}_{step}")
     dcp.save(sd, checkpoint_id=path)
     return path
@@ -432,13 +458,22 @@ def load_training_state(checkpoint_dir: str, transformer, sft_step, dp_rank: int
 
     tr = transformer
     n_a = tr._lora_A_full.numel()
+    n_ab = n_a + tr._lora_B_full.numel()
+    ff = getattr(tr, "lora_ff", False)
+    ff1 = torch.zeros_like(tr._lora_ff_full, device="cpu") if ff else None  # exp_avg / exp_avg_sq of the feed-forward region, filled through their views
+    ff2 = torch.zeros_like(tr._lora_ff_full, device="cpu") if ff else None
+    extra = None
+    if ff:
+        m1, m2 = dict(_ff_moment_views(tr, ff1)), dict(_ff_moment_views(tr, ff2))
+        extra = {k: (m1[k].contiguous(), m2[k].contiguous()) for k in m1}  # (DCP loads into whole tensors; copied into the region below)
     # DCP loads INTO a template of the right structure: build it from fresh CPU tensors of the current shapes
     tmpl = training_state_dict(
-        {k: torch.empty_like(v, device="cpu") for k, v in tr.state_dict().items()}, [p for p, _, _ in tr.lora_views()], tr.lora_rank,
+        {k: torch.empty_like(v, device="cpu") for k, v in tr.state_dict().items()}, _attn_lora_paths(tr), tr.lora_rank,
         torch.zeros_like(tr._lora_A_full, device="cpu"), torch.zeros_like(tr._lora_B_full, device="cpu"),
         torch.zeros_like(tr._lora_A_full, device="cpu"), torch.zeros_like(tr._lora_B_full, device="cpu"),
         0, {"lr": sft_step.lr, "betas": sft_step.betas, "eps": sft_step.eps, "weight_decay": sft_step.weight_decay},
-        lr_scheduler_state=lambda_lr_state(sft_step.lr, 0, sft_step.lr) if getattr(sft_step, "lr_scheduler", None) is not None else None, dp_rank=dp_rank)
+        lr_scheduler_state=lambda_lr_state(sft_step.lr, 0, sft_step.lr) if getattr(sft_step, "lr_scheduler", None) is not None else None, dp_rank=dp_rank,
+        extra_moments=extra)
     tmpl.pop("train_state")
     tmpl["train_state"] = {"step": torch.zeros((), dtype=torch.int32), "observed_data_samples": torch.zeros((), dtype=torch.int32)}
     # Load what the checkpoint HOLDS: a strict dcp.load raises on every template key the file does not have, and checkpoints differ in their
@@ -451,17 +486,21 @@ def load_training_state(checkpoint_dir: str, transformer, sft_step, dp_rank: int
     ea, eb = torch.zeros_like(tr._lora_A_full, device="cpu"), torch.zeros_like(tr._lora_B_full, device="cpu")
     qa, qb = torch.zeros_like(ea), torch.zeros_like(eb)
     steps = set()
-    for (fqn, va), (_, vq) in zip(_lora_param_views(tr.lora_rank, ea, eb, [p for p, _, _ in tr.lora_views()]),
-                                  _lora_param_views(tr.lora_rank, qa, qb, [p for p, _, _ in tr.lora_views()])):
+    views1 = list(_lora_param_views(tr.lora_rank, ea, eb, _attn_lora_paths(tr))) + (list(_ff_moment_views(tr, ff1)) if ff else [])
+    views2 = list(_lora_param_views(tr.lora_rank, qa, qb, _attn_lora_paths(tr))) + (list(_ff_moment_views(tr, ff2)) if ff else [])
+    for (fqn, va), (_, vq) in zip(views1, views2):
         va.copy_(opt[f"state.{fqn}.exp_avg"])
         vq.copy_(opt[f"state.{fqn}.exp_avg_sq"])
         steps.add(int(opt[f"state.{fqn}.step"].item()))
     if len(steps) != 1:
         raise ValueError(f"optimizer state holds different step counts per parameter: {sorted(steps)}")
     sft_step.exp_avg[:n_a].copy_(ea.flatten())
-    sft_step.exp_avg[n_a:].copy_(eb.flatten())
+    sft_step.exp_avg[n_a:n_ab].copy_(eb.flatten())
     sft_step.exp_avg_sq[:n_a].copy_(qa.flatten())
-    sft_step.exp_avg_sq[n_a:].copy_(qb.flatten())
+    sft_step.exp_avg_sq[n_a:n_ab].copy_(qb.flatten())
+    if ff:
+        sft_step.exp_avg[n_ab:].copy_(ff1.flatten())
+        sft_step.exp_avg_sq[n_ab:].copy_(ff2.flatten())
     sft_step.step_count = steps.pop()
     sched = getattr(sft_step, "lr_scheduler", None)
     if sched is not None and "lr_scheduler" in tmpl:

@@ -475,6 +475,63 @@ int ftmi_ltx_sample_cond(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, 
                          const float* key_bias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, int frames,
                          int cond_frames, void* ws, size_t ws_bytes, ftmi_stream stream);
 
+/* ---- LTX-Video feed-forward adapters: ff.net.0.proj and ff.net.2 of every block next to the eight attention adapters.  The reference hands --target_modules
+ * to peft unchanged (trainer/sft_trainer/trainer.py:121-128), and its control trainer's default (trainer/control_trainer/config.py:60) names
+ * "...|ff.net.0.proj|ff.net.2": ten adapters per block at one rank r and scale s = alpha / r.
+ *   ff.net.0.proj  A1 [r, D], B1 [D_ff, r]:  z = n2 W1^T + b1 + (s n2 A1^T) B1^T and g = gelu(z) in one launch (K-extension under the GELU epilogue)
+ *   ff.net.2       A2 [r, D_ff], B2 [D, r]:  h_out = h2 + gate (g W2^T + b2 + (s g A2^T) B2^T)
+ * A name never changes size under its callers: ftmi_ltx_weights and every entry above keep their layout, the feed-forward operands travel in an extension
+ * structure whose first member is the base, and the entries that run blocks have _ff twins -- thin wrappers over the same internal functions, of which the
+ * entries above are the "no feed-forward adapters" case.  All eight operand pointers NULL = no feed-forward adapters (the twin then computes the bits of
+ * its original); some of them set, or any set with cfg->r == 0, is FTMI_ERR_INVALID and launches nothing. */
+typedef struct {
+    ftmi_ltx_weights base;
+    /* bf16 (hi, lo) working copies of the fp32 matrices (ftmi_lora_refresh_rect: one launch per family over the L blocks) */
+    const void* ff_a1_sp;   /* [L,2r,D]     A1 as (hi, lo) row planes:              operand of n2 A1^T       */
+    const void* ff_a1t_ext; /* [L,D,3r]     [A1^T_hi | A1^T_hi | A1^T_lo]:          K-extension of dn2       */
+    const void* ff_b1_ext;  /* [L,D_ff,3r]  [B1_hi | B1_hi | B1_lo]:                K-extension of z         */
+    const void* ff_b1t_sp;  /* [L,2r,D_ff]  B1^T as (hi, lo) row planes:            operand of dz B1         */
+    const void* ff_a2_sp;   /* [L,2r,D_ff]  A2 as (hi, lo) row planes:              operand of g A2^T        */
+    const void* ff_a2t_ext; /* [L,D_ff,3r]  [A2^T_hi | A2^T_hi | A2^T_lo]:          K-extension of dz        */
+    const void* ff_b2_ext;  /* [L,D,3r]     [B2_hi | B2_hi | B2_lo]:                K-extension of h_out     */
+    const void* ff_b2t_sp;  /* [L,2r,D]     B2^T as (hi, lo) row planes:            operand of dO B2         */
+} ftmi_ltx_ff_weights;
+
+/* ftmi_ltx_workspace_bytes / _offset for the ten-adapter model (trainer/sft_trainer/trainer.py:121-128 with the control trainer's target_modules): a block slot
+ * additionally keeps "xa_ff1" and "xa_ff2" ([B*S, 3r], the down-projected rows of the two adapters), the scratch two more [B*S, 3r] buffers. */
+size_t ftmi_ltx_ff_workspace_bytes(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w);
+int ftmi_ltx_ff_workspace_offset(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, const char* name, int layer, size_t* offset);
+/* ftmi_ltx_forward with the feed-forward adapters (the transformer call of LTXVideoModelSpecification.forward, models/ltx_video/base_specification.py:313-330,
+ * on a peft model whose target_modules name ff.net.0.proj and ff.net.2). */
+int ftmi_ltx_ff_forward(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, const void* x_t, const void* text, const float* key_bias,
+                        const float* timestep, void* pred, void* ws, size_t ws_bytes, ftmi_stream stream);
+/* ftmi_ltx_forward_frames with the feed-forward adapters (validation of an image row, base_specification.py:360-361). */
+size_t ftmi_ltx_ff_forward_frames_workspace_bytes(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, int frames);
+int ftmi_ltx_ff_forward_frames(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, const void* x_t, const void* text, const float* key_bias,
+                               const float* timesteps, int frames, void* pred, void* ws, size_t ws_bytes, ftmi_stream stream);
+/* ftmi_ltx_backward_range with the feed-forward adapters (loss.backward() of trainer/sft_trainer/trainer.py:481 over the ten-adapter peft model).
+ * grad_ff fp32 [L][A1 r*D | B1 D_ff*r | A2 r*D_ff | B2 D*r]: the four feed-forward gradients of a block adjacent, so those of a block range are ONE
+ * contiguous slice for the gradient exchange; final for [l_lo, l_hi) when the call returns, zeroed with grad_a / grad_b when accumulate = 0.
+ * n2 and g are recomputed per block (norm + modulate; ftmi_gelu_from_pre on the kept z) instead of being kept: 5.5 GB over 28 blocks at B*S = 5376. */
+int ftmi_ltx_ff_backward_range(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, const void* text, const float* key_bias, const void* dpred,
+                               float* grad_a, float* grad_b, float* grad_ff, void* ws, size_t ws_bytes, int l_hi, int l_lo, int accumulate,
+                               ftmi_stream stream);
+/* ftmi_ltx_sample / ftmi_ltx_sample_cond over the ten-adapter model (the validation pipelines of base_specification.py:347-377 run the peft model as it is). */
+size_t ftmi_ltx_ff_sample_workspace_bytes(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, int two_pass);
+int ftmi_ltx_ff_sample(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, const void* text_cond, const void* text_uncond, const float* key_bias_cond,
+                       const float* key_bias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, void* ws,
+                       size_t ws_bytes, ftmi_stream stream);
+size_t ftmi_ltx_ff_sample_cond_workspace_bytes(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, int two_pass, int frames);
+int ftmi_ltx_ff_sample_cond(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, const void* text_cond, const void* text_uncond,
+                            const float* key_bias_cond, const float* key_bias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps,
+                            float guidance, int frames, int cond_frames, void* ws, size_t ws_bytes, ftmi_stream stream);
+
+/* g [rows, width] = bf16(gelu_tanh(z)) from the bf16 pre-activation z a GELU GEMM stashed (row strides ldz, ldg >= width, in elements): bit for bit the g that
+ * GEMM wrote next to z (both GEMM families compute the activation from the rounded z).  Replaces nothing of the reference -- its autograd keeps the
+ * activation of ff.net.0 (approximate="tanh", [upstream] diffusers FeedForward) -- it is what lets the LTX backward not keep it.  16-byte vectors where bases
+ * and strides are 16-byte aligned, element by element otherwise and for the width % 8 tail.  rows <= 0 or width <= 0: returns 0 without a launch. */
+int ftmi_gelu_from_pre(const void* z, long ldz, void* g, long ldg, int rows, int width, ftmi_stream stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * CogVideoX spec level (first kernels of the next model family): the DDIM noising and the velocity -> x0 conversion of
  * CogVideoXModelSpecification.forward (finetrainers/models/cogvideox/base_specification.py:283-293 and :326-329; scheduler ops
@@ -849,6 +906,13 @@ int ftmi_lora_refresh_n(const float* a_f32, const float* b_f32, void* lora_a_sp,
  * t_sp [2 cols, rows], t_ext [cols, 3 rows]: the same two layouts of w^T.  sp needs rows % 32 == 0, t_sp cols % 32 == 0 (FTMI_ERR_UNSUPPORTED).
  * rows <= 0 or cols <= 0 (ftmi_lora_refresh_n: L, r or D <= 0): returns 0 without a launch. */
 int ftmi_lora_split(const float* w, int rows, int cols, void* sp, void* ext, void* t_sp, void* t_ext, ftmi_stream stream);
+
+/* ftmi_lora_split for `nmat` rectangular fp32 matrices [rows, cols] in ONE launch: matrix m starts at w + m * w_stride (elements; the matrices of one family
+ * inside a per-block parameter record, e.g. the A1 of every LTX block), its outputs are packed per matrix in the layouts above (sp / t_sp 2 rows cols apart, ext /
+ * t_ext 3 rows cols apart).  What ftmi_lora_refresh_n does for the square attention adapters, for the feed-forward ones of ftmi_ltx_ff_weights: the refresh after
+ * an optimiser step (the reference's fp32 adapters need none, trainer/sft_trainer/trainer.py:132-136) is four launches instead of four per block.
+ * w_stride >= rows * cols; nmat, rows or cols <= 0: returns 0 without a launch. */
+int ftmi_lora_refresh_rect(const float* w, long w_stride, int nmat, int rows, int cols, void* sp, void* ext, void* t_sp, void* t_ext, ftmi_stream stream);
 
 /* ---- Wan control LoRA outside the blocks (csrc/wan_control.hip) ----
  * c [M, N] (fp32, row stride ldc) = (accumulate ? c : 0) + scale * a b, a (m, k) at a[m * lda_row + k * lda_col], b (k, n) at b[k * ldb_row + n * ldb_col]: strides

@@ -844,6 +844,63 @@ def _cog_training_workspace(model, B: int, N: int) -> int:
     return _lib.load().ftmi_cog_workspace_bytes(ctypes.byref(model._c_config(B, N)))
 
 
+# ------------------------------------------------------------------------------------------------------------------------------------------
+# LTX-Video LoRA at BASELINE config 2 (bench.py's flagship step: 49 x 512 x 768 clip, batch 2, rank 64 -- run with --rank 64), here so that --ffn-adapters can
+# select the ten-adapter set (the control trainer's default target_modules): same weights, data and optimiser as bench.py's builder.
+# ------------------------------------------------------------------------------------------------------------------------------------------
+def build_ltx_lora(args, par, dev) -> Dict[str, Any]:
+    import ctypes
+
+    from finetrainers_amd import _lib
+    from finetrainers_amd.ltx_video import LTXTransformerConfig, MI355XLTXVideoModelSpecification
+    from finetrainers_amd.ltx_video.transformer import CONTROL_TARGET_MODULES, DEFAULT_TARGET_MODULES
+    from finetrainers_amd.trainer import MI355XSFTStep
+
+    layers = args.layers if args.layers > 0 else 28
+    ffn = bool(getattr(args, "ffn_adapters", False))
+    ckpt = bool(getattr(args, "gradient_checkpointing", False))
+    tcfg = LTXTransformerConfig(num_layers=layers)
+    spec = MI355XLTXVideoModelSpecification(transformer_config=tcfg)
+    model = spec.load_diffusion_models(device=dev, random_init_seed=0)["transformer"]
+    model.add_adapter(r=args.rank, lora_alpha=float(args.rank), target_modules=CONTROL_TARGET_MODULES if ffn else DEFAULT_TARGET_MODULES)
+    if ckpt:
+        model.enable_gradient_checkpointing()
+    with torch.no_grad():  # B != 0 so every gradient path carries data (the [A | B] part holds bench.py's draws)
+        g = torch.Generator(device=dev).manual_seed(1)
+        model.lora_flat.copy_(torch.randn(model.lora_flat.shape, generator=g, device=dev) * 0.01)
+    step = MI355XSFTStep(model, spec, lr=5e-5, betas=(0.9, 0.99), eps=1e-8, weight_decay=1e-4, max_grad_norm=1.0,
+                         parallel=par if par.world_size > 1 else None, generator=torch.Generator(device=dev).manual_seed(1234 + par.rank))
+    B, C, F_, H, W, T = 2, tcfg.in_channels, 7, 16, 24, 128
+    gd = torch.Generator(device=dev).manual_seed(100 + par.rank)
+    latents = torch.randn((B, C, F_, H, W), generator=gd, device=dev).to(bf16)
+    text = torch.randn((B, T, tcfg.caption_channels), generator=gd, device=dev).to(bf16)
+    mask = torch.zeros((B, T), dtype=bf16, device=dev)
+    for i in range(B):
+        mask[i, : (32 if i % 2 == 0 else 96)] = 1
+    cond = {"encoder_hidden_states": text, "encoder_attention_mask": mask}
+    lat = {"latents": latents, "latents_mean": torch.zeros(C, device=dev), "latents_std": torch.ones(C, device=dev), "num_frames": F_, "height": H, "width": W}
+    S, D, Fd = F_ * H * W, tcfg.inner_dim, tcfg.inner_dim * tcfg.ff_mult
+    lin = 2.0 * S * (5 * D * D + 2 * D * Fd) + 2.0 * T * 2 * D * D
+    att = 4.0 * S * S * D + 4.0 * S * T * D
+    flop = B * layers * ((3.0 if ckpt else 2.0) * lin + (4.5 if ckpt else 3.5) * att)  # linears: forward + input gradient (frozen base); checkpointing: one more forward
+    cfg = model._c_config(B, S, T, checkpoint=ckpt)
+    cos, sin = model.rope_tables(F_, H, W, None)
+    w = model._c_weights(cos, sin)
+    lib = _lib.load()
+    ws = lib.ftmi_ltx_ff_workspace_bytes(ctypes.byref(cfg), ctypes.byref(w)) if ffn else lib.ftmi_ltx_workspace_bytes(ctypes.byref(cfg))
+    return {
+        "one_step": lambda: step.step(cond, lat),
+        "samples_per_step": B,
+        "step_tflop": flop / 1e12,
+        "metric": "train samples/sec (+ step ms) LTX-Video LoRA 49x512x768 (BASELINE configs[1]), eight or ten adapters per block",
+        "data": "synthetic latents [2,128,7,16,24] + random text embeds, random-init weights of the production LTX-Video DiT (bench.py's)",
+        "config": {"workload": f"LTX-Video LoRA rank={args.rank} bf16 SFT step, 49x512x768 clip ({S} tokens), batch 2, {layers} blocks" + ("" if layers == 28 else " -- REDUCED depth"),
+                   "adapters_per_block": 10 if ffn else 8, "lora_parameters": int(model.lora_flat.numel()), "workspace_bytes": int(ws), "seq_len": S,
+                   "activation_checkpointing": ckpt},
+        "layers": layers,
+    }
+
+
 WORKLOADS = {"cogvideox": (build_cogvideox, lambda a, c: cpu_baseline_cogvideox(a, c["layers"])),
              "wan": (build_wan, lambda a, c: cpu_baseline_wan(a, c["layers"])),
              "wan_lora": (build_wan_lora, lambda a, c: cpu_baseline_wan(a, c["layers"])),  # (yardstick on the host: the full fine-tune block, an upper bound of the LoRA block's work)
@@ -852,6 +909,7 @@ WORKLOADS = {"cogvideox": (build_cogvideox, lambda a, c: cpu_baseline_cogvideox(
              "wan_sample": (build_wan_sample, None),  # (validation sampling: forward only; this file's own command line only)
              "cog_sample": (build_cog_sample, None),  # (validation sampling: forward only; this file's own command line only; --rank 64)
              "hy_sample": (build_hy_sample, None),  # (validation sampling: forward only; this file's own command line only; --rank 64)
+             "ltx_lora": (build_ltx_lora, None),  # (bench.py's flagship step with a choice of adapter set; this file's own command line only; --rank 64)
              "hunyuan": (build_hunyuan, cpu_baseline_hunyuan)}
 
 
@@ -872,7 +930,7 @@ def main() -> None:
     ap.add_argument("--layers", type=int, default=0)
     ap.add_argument("--rank", type=int, default=32)
     ap.add_argument("--gradient-checkpointing", dest="gradient_checkpointing", action="store_true")
-    ap.add_argument("--ffn-adapters", dest="ffn_adapters", action="store_true", help="wan_lora: adapters on ffn.net.0.proj and ffn.net.2 as well (ten per block)")
+    ap.add_argument("--ffn-adapters", dest="ffn_adapters", action="store_true", help="wan_lora / ltx_lora: adapters on the two feed-forward projections as well (ten per block)")
     ap.add_argument("--text-adapters", dest="text_adapters", action="store_true",
                     help="hunyuan / hy_sample: the shipped recipe's target_modules -- adapters on add_q_proj / add_k_proj / add_v_proj / to_add_out of the dual-stream blocks too")
     ap.add_argument("--last-frame", dest="last_frame", action="store_true",
