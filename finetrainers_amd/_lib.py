@@ -185,6 +185,12 @@ class WanSampleConfig(Structure):
                 ("patch_scale", c_float), ("steps", c_int), ("guidance", c_float), ("TI2", c_int)]
 
 
+class WanSampleMsConfig(Structure):
+    """include/ftmi355.h: ftmi_wan_sample_ms_config (``solver``: 1 = UniPC)."""
+
+    _fields_ = [("base", WanSampleConfig), ("solver", c_int)]
+
+
 class WanSampleWeights(Structure):
     """include/ftmi355.h: ftmi_wan_sample_weights (``blocks``: a host array of WanLoraFfnBlockWeights, ``img_params``: a host array of pointers)."""
 
@@ -419,6 +425,9 @@ _SIGS = {
     "ftmi_wan_sample_mod": (c_int, [POINTER(c_void_p), c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "ftmi_wan_sample_workspace_bytes": (c_size_t, [POINTER(WanSampleConfig)]),
     "ftmi_wan_sample": (c_int, [POINTER(WanSampleConfig), POINTER(WanSampleWeights)] + [c_void_p] * 11 + [c_size_t, c_void_p]),
+    "ftmi_wan_sample_step_unipc": (c_int, [POINTER(WanSampleGeometry)] + [c_void_p] * 7 + [c_float, c_void_p, c_void_p]),
+    "ftmi_wan_sample_ms_workspace_bytes": (c_size_t, [POINTER(WanSampleMsConfig)]),
+    "ftmi_wan_sample_ms": (c_int, [POINTER(WanSampleMsConfig), POINTER(WanSampleWeights)] + [c_void_p] * 12 + [c_size_t, c_void_p]),
     "ftmi_cog_sample_init": (c_int, [POINTER(CogSampleGeometry), c_void_p, c_void_p, c_void_p, c_void_p]),
     "ftmi_cog_sample_step": (c_int, [POINTER(CogSampleGeometry), c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p]),
     "ftmi_cog_sample_finish": (c_int, [POINTER(CogSampleGeometry), c_void_p, c_float, c_void_p, c_void_p]),

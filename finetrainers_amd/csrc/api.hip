@@ -1092,6 +1092,23 @@ int ftmi_wan_sample(const ftmi_wan_sample_config* cfg, const ftmi_wan_sample_wei
                       workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+int ftmi_wan_sample_step_unipc(const ftmi_wan_sample_geometry* geo, const void* pred, float* x, float* last, const float* m1, float* m2, const float* coef_row,
+                               const float* sigma, float guidance, void* cols, ftmi_stream stream) {
+    if (!geo || !pred || !x || !last || !m1 || !m2 || !coef_row || !sigma) return set_error(FTMI_ERR_INVALID, "ftmi_wan_sample_step_unipc: null argument");
+    return wan_sample_step_unipc(*geo, (const bf16_t*)pred, x, last, m1, m2, coef_row, sigma, guidance, (bf16_t*)cols, (hipStream_t)stream);
+}
+
+size_t ftmi_wan_sample_ms_workspace_bytes(const ftmi_wan_sample_ms_config* cfg) { return cfg ? wan_sample_ms_workspace_bytes(*cfg) : 0; }
+
+int ftmi_wan_sample_ms(const ftmi_wan_sample_ms_config* cfg, const ftmi_wan_sample_weights* w, void* cols, float* x, const void* tproj, const float* head_shift,
+                       const float* head_scale, const void* enc, const void* enc_img, const float* rope_cos, const float* rope_sin, const float* coef,
+                       const float* sigmas, void* workspace, size_t workspace_bytes, ftmi_stream stream) {
+    if (!cfg || !w || !cols || !x || !tproj || !head_shift || !head_scale || !enc || !rope_cos || !rope_sin || !coef || !sigmas || !workspace)
+        return set_error(FTMI_ERR_INVALID, "ftmi_wan_sample_ms: null argument");
+    return wan_sample_ms(*cfg, *w, (bf16_t*)cols, x, (const bf16_t*)tproj, head_shift, head_scale, (const bf16_t*)enc, (const bf16_t*)enc_img, rope_cos, rope_sin, coef,
+                         sigmas, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 int ftmi_cog_sample_init(const ftmi_cog_sample_geometry* geo, const float* latents, float* x, void* cols, ftmi_stream stream) {
     if (!geo || !latents || !x || !cols) return set_error(FTMI_ERR_INVALID, "ftmi_cog_sample_init: null argument");
     return cog_sample_init(*geo, latents, x, (bf16_t*)cols, (hipStream_t)stream);

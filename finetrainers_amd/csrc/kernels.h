@@ -424,6 +424,13 @@ size_t wan_sample_workspace_bytes(const ftmi_wan_sample_config& c);
 int wan_sample(const ftmi_wan_sample_config& c, const ftmi_wan_sample_weights& w, bf16_t* cols, float* x, const bf16_t* tproj, const float* head_shift,
                const float* head_scale, const bf16_t* enc, const bf16_t* enc_img, const float* rope_cos, const float* rope_sin, const float* sigmas, void* ws,
                size_t ws_bytes, hipStream_t st);
+// the multistep (UniPC) step and loop: coef_row fp32 [8] and sigma fp32 [1] on the device; last / m1 / m2 fp32 [B, S, Kc], m2 receives the step's data prediction
+int wan_sample_step_unipc(const ftmi_wan_sample_geometry& g, const bf16_t* pred, float* x, float* last, const float* m1, float* m2, const float* coef_row,
+                          const float* sigma, float guidance, bf16_t* cols, hipStream_t st);
+size_t wan_sample_ms_workspace_bytes(const ftmi_wan_sample_ms_config& c);
+int wan_sample_ms(const ftmi_wan_sample_ms_config& c, const ftmi_wan_sample_weights& w, bf16_t* cols, float* x, const bf16_t* tproj, const float* head_shift,
+                  const float* head_scale, const bf16_t* enc, const bf16_t* enc_img, const float* rope_cos, const float* rope_sin, const float* coef,
+                  const float* sigmas, void* ws, size_t ws_bytes, hipStream_t st);
 int adamw_bf16_step(bf16_t* p, const float* g, bf16_t* m, bf16_t* v, long n, const float* sumsq_in, float max_norm, float lr, float beta1, float beta2,
                     float eps, float wd, int step, float* grad_norm_out, hipStream_t st);
 

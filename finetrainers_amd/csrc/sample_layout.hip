@@ -30,6 +30,17 @@
 //   half of pred in pred's order and hands v to the thread that owns the state columns through the LDS: state column c pv + p is pred column p C + c, so a
 //   token's columns are permuted on chip and every global access stays a 16-byte vector.  Bytes moved per element of x: 12 + 2 P copies with guidance (read
 //   u 2 + c 2 + x 4, write x 4 + cols): 16 for T2V / I2V, 20 with the folded patch adapter; 10 + 2 copies without guidance: 12 / 14.
+//   Wan, multistep (wan_sample_step_unipc): the checkpoint's UniPCMultistepScheduler (data prediction, flow sigmas, bh2, order <= 2), folded on the host into eight
+//   numbers per step (finetrainers_amd/wan/sampler.py wan_unipc_tables; the step is linear in the state, the last corrected state and three data predictions).
+//   Same mapping, combine and on-chip permutation as the Euler step; per element, all fp32, one rounding per operation:
+//       m  = fma(-sigma, v, x)                                          the data prediction of this step
+//       x~ = c_x x + c_l last + c_1 m1 + c_2 m2 + c_t m                  the corrector (c_x = 1, the others 0: none)
+//       x' = p_x x~ + p_0 m + p_1 m1                                     the predictor
+//   each sum a product followed by fmas in the order written; a term whose coefficient is 0 is neither loaded nor added (step 0 has no history, and 0 * NaN of
+//   an uninitialised workspace must not reach x): the coefficients are one row of a device table, so the branches are uniform over the launch.  x' goes to x and,
+//   as bf16, to cols; x~ to last; m over m2, the OLDER of the two history buffers (the caller swaps m1 / m2 after the step).  Bytes moved per element of x with
+//   guidance, full order-2 row: read u 2 + c 2 + x 4 + last 4 + m1 4 + m2 4 = 20, write x 4 + last 4 + m 4 + 2 P copies = 16 at P = 2, copies = 1: 36 (40 with
+//   the folded patch adapter) against Euler's 16; step 0 reads 8 and the last step writes the same 16.
 //   CogVideoX: (cx, cv) are the step's two numbers of the host-folded scheduler ([upstream, unpinned] CogVideoXDDIMScheduler.step is linear in (x, v):
 //   finetrainers_amd/cogvideox/sampler.py cog_ddim_tables), read from a device table.  A thread owns 8 consecutive elements; the last workgroup's tail is
 //   masked.  Bytes moved per element of x: 12 + 2 P with guidance = 16; 10 + 2 = 12 without.
@@ -190,6 +201,80 @@ __global__ __launch_bounds__(256) void wan_sample_step_kernel(Lay g, const bf16_
     }
     if (cols)
         for (int cp = 0; cp < g.copies; ++cp) store_groups8<kCfg>(cols, xv, (b * g.S + t) * g.ld + (long)cp * g.Kp + j0, (long)g.B * g.S * g.ld);
+}
+
+// acc (+)= c val over a thread's 8 elements, one rounding per element (the first term is a product, every further one an fma).  A zero coefficient leaves its
+// term out: the caller does not load that buffer either, whose values may be uninitialised (0 * NaN).  c is one value per launch: the branch is uniform.
+FTMI_DEVICE void lin_term8(float c, const float* val, float* acc, bool& first) {
+    if (c == 0.0f) return;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = first ? c * val[e] : __builtin_fmaf(c, val[e], acc[e]);
+    first = false;
+}
+
+FTMI_DEVICE void load8(const float* __restrict__ p, long i, float* v) {
+    const f32x4 a = reinterpret_cast<const f32x4*>(p)[2 * i], b = reinterpret_cast<const f32x4*>(p)[2 * i + 1];
+    v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3]; v[4] = b[0]; v[5] = b[1]; v[6] = b[2]; v[7] = b[3];
+}
+
+FTMI_DEVICE void store8(float* __restrict__ p, long i, const float* v) {
+    reinterpret_cast<f32x4*>(p)[2 * i] = f32x4{v[0], v[1], v[2], v[3]};
+    reinterpret_cast<f32x4*>(p)[2 * i + 1] = f32x4{v[4], v[5], v[6], v[7]};
+}
+
+// The multistep step: wan_sample_step_kernel's thread-to-data mapping (n8 = B S Kc / 8 vectors, a workgroup's 2048 elements are whole tokens, v through the
+// LDS into the state's column order) with the UniPC update of the file header.  coef: the step's row (c_x, c_l, c_1, c_2, c_t, p_x, p_0, p_1), sigma: its sigma.
+// last / m1 / m2 fp32 [B, S, Kc] like x; m2 (the OLDER history buffer) receives m: vector i of it is read and written by thread i alone.
+template <bool kCfg>
+__global__ __launch_bounds__(256) void wan_sample_step_unipc_kernel(Lay g, const bf16_t* __restrict__ pred, float* __restrict__ x, float* __restrict__ last,
+                                                                    const float* __restrict__ m1, float* __restrict__ m2, const float* __restrict__ coef,
+                                                                    const float* __restrict__ sigma, float gd, bf16_t* __restrict__ cols, long n8) {
+    __shared__ __attribute__((aligned(16))) float sv[2048];  // the combined prediction of the workgroup's tokens, in the STATE's column order
+    const int tid = threadIdx.x;
+    const long i = (long)blockIdx.x * 256 + tid;
+    const bool live = i < n8;
+    const int vpt = g.Kc / 8;
+    const long tok = i / vpt;
+    const int j0 = (int)(i - tok * vpt) * 8;
+    if (live) {
+        float v[8];
+        cfg_combine8<kCfg>(pred, i, n8, gd, v);
+        const int base = (tid / vpt) * g.Kc;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {  // pred column j = p C + c  ->  state column c pv + p
+            const int j = j0 + e;
+            sv[base + (j % g.C) * g.pv + j / g.C] = v[e];
+        }
+    }
+    __syncthreads();
+    if (!live) return;
+    const float cx = coef[0], cl = coef[1], c1 = coef[2], c2 = coef[3], ct = coef[4], px = coef[5], p0 = coef[6], p1 = coef[7], sg = sigma[0];
+    float xv[8], v[8], m[8], lv[8], h1[8], h2[8];
+    load8(x, i, xv);
+    load8(sv, tid, v);
+    if (cl != 0.0f) load8(last, i, lv);
+    if (c1 != 0.0f || p1 != 0.0f) load8(m1, i, h1);
+    if (c2 != 0.0f) load8(m2, i, h2);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) m[e] = __builtin_fmaf(-sg, v[e], xv[e]);
+    float xt[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, xn[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    bool first = true;
+    lin_term8(cx, xv, xt, first);
+    lin_term8(cl, lv, xt, first);
+    lin_term8(c1, h1, xt, first);
+    lin_term8(c2, h2, xt, first);
+    lin_term8(ct, m, xt, first);
+    first = true;
+    lin_term8(px, xt, xn, first);
+    lin_term8(p0, m, xn, first);
+    lin_term8(p1, h1, xn, first);
+    store8(x, i, xn);
+    store8(last, i, xt);
+    store8(m2, i, m);
+    if (cols) {
+        const long b = tok / g.S, t = tok - b * g.S;
+        for (int cp = 0; cp < g.copies; ++cp) store_groups8<kCfg>(cols, xn, (b * g.S + t) * g.ld + (long)cp * g.Kp + j0, (long)g.B * g.S * g.ld);
+    }
 }
 
 // n8 = B S Kc / 8 vectors, one per thread; grid ceil(n8 / 256).  kCfg: two row groups (pred has an unconditional half).
@@ -417,6 +502,23 @@ int wan_sample_step(const ftmi_wan_sample_geometry& g, const bf16_t* pred, float
     else
         hipLaunchKernelGGL((wan_sample_step_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, st, l, pred, x, sigma, sigma_next, sig_stride, guidance, cols, n8);
     return check_launch("wan_sample_step");
+}
+
+int wan_sample_step_unipc(const ftmi_wan_sample_geometry& g, const bf16_t* pred, float* x, float* last, const float* m1, float* m2, const float* coef_row,
+                          const float* sigma, float guidance, bf16_t* cols, hipStream_t st) {
+    Lay l;
+    FTMI_TRY(wan_lay(g, "wan_sample_step_unipc", l));
+    if (!pred || !last || !m1 || !m2 || !coef_row || !sigma) return set_error(FTMI_ERR_INVALID, "wan_sample_step_unipc: pred, the history buffers, the coefficient row or sigma missing");
+    if ((guidance != 1.0f) != (g.P == 2)) return set_error(FTMI_ERR_INVALID, "wan_sample_step_unipc: P is 2 with guidance != 1 and 1 with guidance == 1");
+    if (misaligned(pred) || misaligned(x) || misaligned(last) || misaligned(m1) || misaligned(m2) || misaligned(cols))
+        return set_error(FTMI_ERR_INVALID, "wan_sample_step_unipc: tensors must be 16-byte aligned");
+    if (x == last || x == m1 || x == m2 || last == m1 || last == m2 || m1 == m2) return set_error(FTMI_ERR_INVALID, "wan_sample_step_unipc: x, last, m1 and m2 are four buffers");
+    const long n8 = (long)g.B * l.S * l.Kc / 8, blocks = (n8 + 255) / 256;  // blocks fits an int: lay_derive bounds P B S ld / 8 >= n8
+    if (g.P == 2)
+        hipLaunchKernelGGL((wan_sample_step_unipc_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, st, l, pred, x, last, m1, m2, coef_row, sigma, guidance, cols, n8);
+    else
+        hipLaunchKernelGGL((wan_sample_step_unipc_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, st, l, pred, x, last, m1, m2, coef_row, sigma, guidance, cols, n8);
+    return check_launch("wan_sample_step_unipc");
 }
 
 int wan_sample_finish(const ftmi_wan_sample_geometry& g, const float* x, const float* mean, const float* std_, bf16_t* latents, hipStream_t st) {

@@ -13,6 +13,11 @@
 // The sampler state x fp32 [B, S, Kc] and the model input cols stay in the patch embedding's operand layout (sample_layout.hip): no patchify between steps.
 // What does not depend on the state (time projection, head shift / scale, text and image rows, rotary tables, sigmas) is the caller's, computed once per call.
 //
+// ftmi_wan_sample_ms is the same loop (sample_loop, one body for both) whose last launch is wan_sample_step_unipc: the checkpoint's UniPC multistep scheduler, which
+// is what the reference's validation pipeline runs (the trainers pass no scheduler to load_pipeline, so from_pretrained loads the checkpoint's).  Its history
+// -- the last corrected state and two data predictions, three [B, S, Kc] fp32 buffers behind the Euler workspace -- never leaves the device; the two
+// data-prediction pointers swap per step on the host side of the call, the step's eight coefficients come from a device table folded once on the host.
+//
 // Workspace: mod for the 40 blocks a launch can address (so the plan does not depend on L), the two activation buffers, pred [P B S, po], one block's saved bytes
 // and one block's scratch.
 #include "common.hip.h"
@@ -69,12 +74,27 @@ size_t wan_sample_workspace_bytes(const ftmi_wan_sample_config& c) {
     return make_plan(c, p) ? 0 : p.total;
 }
 
-int wan_sample(const ftmi_wan_sample_config& c, const ftmi_wan_sample_weights& w, bf16_t* cols, float* x, const bf16_t* tproj, const float* head_shift,
-               const float* head_scale, const bf16_t* enc, const bf16_t* enc_img, const float* rope_cos, const float* rope_sin, const float* sigmas, void* ws,
-               size_t ws_bytes, hipStream_t st) {
-    Plan p;
-    FTMI_TRY(make_plan(c, p));
-    if (ws_bytes < p.total) return set_error(FTMI_ERR_INVALID, "wan_sample: workspace too small (ftmi_wan_sample_workspace_bytes)");
+namespace {
+
+// The history of the multistep solver behind the Euler plan: last, m1, m2 fp32 [B, S, Kc] (Kc * 4 bytes is a multiple of 32: every buffer stays 16-byte aligned
+// behind the 256-byte multiple p.total).
+int make_ms_plan(const ftmi_wan_sample_ms_config& c, Plan& p, size_t& hist, size_t& hist_bytes, size_t& total) {
+    if (c.solver != 1) return set_error(FTMI_ERR_UNSUPPORTED, "wan_sample_ms: solver 1 (UniPC) is the one multistep solver");
+    FTMI_TRY(make_plan(c.base, p));
+    const ftmi_wan_sample_geometry& g = c.base.geo;
+    if (g.C <= 0 || (long)g.C * g.pt * g.ph * g.pw != g.po) return set_error(FTMI_ERR_INVALID, "wan_sample_ms: C pt ph pw must equal po, the width of proj_out");
+    hist = p.total;
+    hist_bytes = (size_t)g.B * p.S * g.po * sizeof(float);
+    total = p.total + 3 * hist_bytes;
+    return 0;
+}
+
+// The loop of both entry points.  step(i, pred): the launch that takes the step's prediction into the state and cols.  `need`: the entry point's workspace.
+template <class Step>
+int sample_loop(const ftmi_wan_sample_config& c, const Plan& p, size_t need, const ftmi_wan_sample_weights& w, bf16_t* cols, const bf16_t* tproj,
+                const float* head_shift, const float* head_scale, const bf16_t* enc, const bf16_t* enc_img, const float* rope_cos, const float* rope_sin, void* ws,
+                size_t ws_bytes, hipStream_t st, Step step) {
+    if (ws_bytes < need) return set_error(FTMI_ERR_INVALID, "wan_sample: workspace too small (ftmi_wan_sample_workspace_bytes)");
     if (reinterpret_cast<uintptr_t>(ws) & 255) return set_error(FTMI_ERR_INVALID, "wan_sample: the workspace must be 256-byte aligned");
     if (!w.blocks || !w.patch_w || !w.proj_w) return set_error(FTMI_ERR_INVALID, "wan_sample: weights missing");
     if (c.TI > 0 && (!w.img_params || !enc_img)) return set_error(FTMI_ERR_INVALID, "wan_sample: image tokens without their parameters");
@@ -116,9 +136,43 @@ int wan_sample(const ftmi_wan_sample_config& c, const ftmi_wan_sample_weights& w
             FTMI_TRY(wan_ln_fwd(a, st));
             FTMI_TRY(gemm_nt(linear_args(nxt, D, M, (const bf16_t*)w.proj_w, D, g.po, D, (const bf16_t*)w.proj_b, pred, g.po, c.gemm_variant), st));
         }
-        FTMI_TRY(wan_sample_step(g, pred, x, sigmas + i, sigmas + i + 1, 0, c.guidance, cols, st));
+        FTMI_TRY(step(i, pred));
     }
     return 0;
+}
+
+}  // namespace
+
+int wan_sample(const ftmi_wan_sample_config& c, const ftmi_wan_sample_weights& w, bf16_t* cols, float* x, const bf16_t* tproj, const float* head_shift,
+               const float* head_scale, const bf16_t* enc, const bf16_t* enc_img, const float* rope_cos, const float* rope_sin, const float* sigmas, void* ws,
+               size_t ws_bytes, hipStream_t st) {
+    Plan p;
+    FTMI_TRY(make_plan(c, p));
+    return sample_loop(c, p, p.total, w, cols, tproj, head_shift, head_scale, enc, enc_img, rope_cos, rope_sin, ws, ws_bytes, st, [&](int i, const bf16_t* pred) {
+        return wan_sample_step(c.geo, pred, x, sigmas + i, sigmas + i + 1, 0, c.guidance, cols, st);
+    });
+}
+
+size_t wan_sample_ms_workspace_bytes(const ftmi_wan_sample_ms_config& c) {
+    Plan p;
+    size_t hist, hist_bytes, total;
+    return make_ms_plan(c, p, hist, hist_bytes, total) ? 0 : total;
+}
+
+int wan_sample_ms(const ftmi_wan_sample_ms_config& c, const ftmi_wan_sample_weights& w, bf16_t* cols, float* x, const bf16_t* tproj, const float* head_shift,
+                  const float* head_scale, const bf16_t* enc, const bf16_t* enc_img, const float* rope_cos, const float* rope_sin, const float* coef,
+                  const float* sigmas, void* ws, size_t ws_bytes, hipStream_t st) {
+    Plan p;
+    size_t hist, hist_bytes, total;
+    FTMI_TRY(make_ms_plan(c, p, hist, hist_bytes, total));
+    char* h = reinterpret_cast<char*>(ws) + hist;
+    float* last = reinterpret_cast<float*>(h);
+    float *m1 = reinterpret_cast<float*>(h + hist_bytes), *m2 = reinterpret_cast<float*>(h + 2 * hist_bytes);  // step i reads m_{i-1}, m_{i-2} and writes m_i over m2
+    return sample_loop(c.base, p, total, w, cols, tproj, head_shift, head_scale, enc, enc_img, rope_cos, rope_sin, ws, ws_bytes, st, [&](int i, const bf16_t* pred) {
+        const int rc = wan_sample_step_unipc(c.base.geo, pred, x, last, m1, m2, coef + (size_t)i * 8, sigmas + i, c.base.guidance, cols, st);
+        float* t = m1; m1 = m2; m2 = t;
+        return rc;
+    });
 }
 
 }  // namespace ftmi

@@ -1184,6 +1184,27 @@ def wan_sample_step(geo, pred, x, sigma, sigma_next, guidance: float, cols=None)
           "ftmi_wan_sample_step")
 
 
+def wan_sample_step_unipc(geo, pred, x, last, m1, m2, coef_row, sigma, guidance: float, cols=None) -> None:
+    """One step of the multistep (UniPC) sampler in place (ftmi_wan_sample_step_unipc): pred bf16 [P B, S, po]; x / last / m1 / m2 fp32 [B, S, Kc], four buffers
+    -- x receives the predictor's state, last the corrected one, m2 (the OLDER history buffer) this step's data prediction: swap m1 and m2 after the call;
+    coef_row fp32 [8] (a row of ``wan_unipc_tables``) and sigma fp32 [1] on the device; cols bf16 [P B S, copies Kp] (None: no copies)."""
+    _wan_sample_buffers(geo, x, cols, "wan_sample_step_unipc")
+    S = _wan_sample_tokens(geo)
+    require_gpu_tensor(pred, "pred", bf16)
+    if pred.numel() != geo.P * geo.B * S * geo.po or not pred.is_contiguous():
+        raise ValueError(f"wan_sample_step_unipc: pred must be contiguous [{geo.P * geo.B}, {S}, {geo.po}], got {tuple(pred.shape)}")
+    for n, t in (("last", last), ("m1", m1), ("m2", m2)):
+        require_gpu_tensor(t, n, torch.float32)
+        if tuple(t.shape) != tuple(x.shape) or not t.is_contiguous():
+            raise ValueError(f"wan_sample_step_unipc: {n} must be a contiguous fp32 {list(x.shape)} tensor like x, got {tuple(t.shape)}")
+    for n, t, k in (("coef_row", coef_row, 8), ("sigma", sigma, 1)):
+        require_gpu_tensor(t, n, torch.float32)
+        if t.numel() != k or not t.is_contiguous():
+            raise ValueError(f"wan_sample_step_unipc: {n} holds {k} contiguous value(s)")
+    check(_lib.load().ftmi_wan_sample_step_unipc(ctypes.byref(geo), ptr(pred), ptr(x), ptr(last), ptr(m1), ptr(m2), ptr(coef_row), ptr(sigma), float(guidance),
+                                                 ptr(cols), stream_ptr()), "ftmi_wan_sample_step_unipc")
+
+
 def wan_sample_finish(geo, x, mean, std):
     """x fp32 [B, S, Kc] -> latents bf16 [B, C, F, H, W] = bf16(x * std[c] + mean[c]); ``std`` is the VAE's standard deviation itself (ftmi_wan_sample_finish)."""
     _wan_sample_buffers(geo, x, None, "wan_sample_finish")
@@ -1217,10 +1238,8 @@ def wan_sample_workspace_bytes(cfg) -> int:
     return n
 
 
-def wan_sample(cfg, weights, cols, x, tproj, head_shift, head_scale, enc, enc_img, rope, sigmas, workspace=None) -> None:
-    """The whole denoising loop in ONE call (ftmi_wan_sample), in place on ``x`` / ``cols`` (as ``wan_sample_init`` wrote them).  tproj bf16 [steps, 6 D];
-    head_shift / head_scale fp32 [steps, D]; enc bf16 [P B, T, D] (unconditional rows first); enc_img bf16 [P B, TI + TI2, D] or None; rope = (cos, sin) fp32 [S, 64];
-    sigmas fp32 [steps + 1] on the device.  ``workspace``: a uint8 GPU tensor of at least ``wan_sample_workspace_bytes(cfg)`` (allocated when None)."""
+def _wan_sample_loop_inputs(cfg, cols, x, tproj, head_shift, head_scale, enc, enc_img, rope, sigmas, coef=None) -> None:
+    """The tensor checks of ``wan_sample`` and ``wan_sample_ms`` (``coef``: the multistep table fp32 [steps, 8])."""
     geo, n, D = cfg.geo, cfg.steps, cfg.D
     _wan_sample_buffers(geo, x, cols, "wan_sample")
     S, rows = _wan_sample_tokens(geo), geo.P * geo.B
@@ -1229,9 +1248,45 @@ def wan_sample(cfg, weights, cols, x, tproj, head_shift, head_scale, enc, enc_im
             ("sigmas", sigmas, torch.float32, (n + 1,))]
     if cfg.TI > 0:
         want.append(("enc_img", enc_img, bf16, (rows, cfg.TI + cfg.TI2, D)))
+    if coef is not None:
+        want.append(("coef", coef, torch.float32, (n, 8)))
     for name, t, dt, shape in want:
         if t is None or not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
             raise ValueError(f"wan_sample: {name} must be a contiguous {dt} {shape} GPU tensor, got {None if t is None else tuple(t.shape)}")
+
+
+def wan_sample_ms_config(cfg, solver: int = 1) -> "_lib.WanSampleMsConfig":
+    """ftmi_wan_sample_ms_config over a ``WanSampleConfig`` (``solver`` 1: UniPC)."""
+    return _lib.WanSampleMsConfig(base=cfg, solver=solver)
+
+
+def wan_sample_ms_workspace_bytes(cfg, solver: int = 1) -> int:
+    n = int(_lib.load().ftmi_wan_sample_ms_workspace_bytes(ctypes.byref(wan_sample_ms_config(cfg, solver))))
+    if n == 0:
+        raise ValueError(f"wan_sample_ms: {_lib.last_error()}")
+    return n
+
+
+def wan_sample_ms(cfg, weights, cols, x, tproj, head_shift, head_scale, enc, enc_img, rope, coef, sigmas, workspace=None, solver: int = 1) -> None:
+    """``wan_sample`` with the multistep (UniPC) step (ftmi_wan_sample_ms): ``cfg`` is the same ``WanSampleConfig``; coef fp32 [steps, 8] (``wan_unipc_tables``) and
+    sigmas fp32 [steps + 1] on the device.  ``workspace``: at least ``wan_sample_ms_workspace_bytes(cfg)`` bytes -- the solver's history lives there."""
+    if coef is None:
+        raise ValueError("wan_sample_ms: the coefficient table is missing")
+    _wan_sample_loop_inputs(cfg, cols, x, tproj, head_shift, head_scale, enc, enc_img, rope, sigmas, coef)
+    need = wan_sample_ms_workspace_bytes(cfg, solver)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
+    ms = wan_sample_ms_config(cfg, solver)
+    check(_lib.load().ftmi_wan_sample_ms(ctypes.byref(ms), ctypes.byref(weights), ptr(cols), ptr(x), ptr(tproj), ptr(head_shift), ptr(head_scale), ptr(enc),
+                                         ptr(enc_img if cfg.TI > 0 else None), ptr(rope[0]), ptr(rope[1]), ptr(coef), ptr(sigmas), ptr(workspace),
+                                         workspace.numel(), stream_ptr()), "ftmi_wan_sample_ms")
+
+
+def wan_sample(cfg, weights, cols, x, tproj, head_shift, head_scale, enc, enc_img, rope, sigmas, workspace=None) -> None:
+    """The whole denoising loop in ONE call (ftmi_wan_sample), in place on ``x`` / ``cols`` (as ``wan_sample_init`` wrote them).  tproj bf16 [steps, 6 D];
+    head_shift / head_scale fp32 [steps, D]; enc bf16 [P B, T, D] (unconditional rows first); enc_img bf16 [P B, TI + TI2, D] or None; rope = (cos, sin) fp32 [S, 64];
+    sigmas fp32 [steps + 1] on the device.  ``workspace``: a uint8 GPU tensor of at least ``wan_sample_workspace_bytes(cfg)`` (allocated when None)."""
+    _wan_sample_loop_inputs(cfg, cols, x, tproj, head_shift, head_scale, enc, enc_img, rope, sigmas)
     need = wan_sample_workspace_bytes(cfg)
     if workspace is None:
         workspace = torch.empty(need, dtype=torch.uint8, device=x.device)

@@ -175,6 +175,19 @@ class MI355XWanModelSpecification(MI355XWanSpecOps):
         mask = torch.cat([torch.repeat_interleave(mask[:, :, :1], dim=2, repeats=temporal_downsample), mask[:, :, 1:]], dim=2)
         return mask.view(1, -1, temporal_downsample, latent_height, latent_width).transpose(1, 2).contiguous()
 
+    def validation_scheduler_config(self) -> Optional[Dict[str, object]]:
+        """The ``scheduler_config`` for ``validation_latents`` that makes it sample as the reference's validation does: the scheduler stored in the checkpoint
+        (``load_pipeline`` passes none, so ``from_pretrained`` loads ``<pretrained_model_name_or_path>/scheduler``; ``UniPCMultistepScheduler`` for Wan2.1).
+        None when the path is not a local directory (a hub id cannot be resolved here)."""
+        import os
+
+        from .. import wire
+
+        root = self.pretrained_model_name_or_path
+        if not root or not os.path.isdir(root):
+            return None
+        return wire.load_scheduler_config(root)
+
     def validation_latents(self, transformer, prompt_embeds: torch.Tensor, negative_prompt_embeds: Optional[torch.Tensor], num_frames: int, height: int, width: int,
                            num_inference_steps: int = 50, guidance_scale: float = 5.0, generator: Optional[torch.Generator] = None, scheduler_config=None,
                            **sample_kwargs) -> torch.Tensor:
@@ -183,7 +196,8 @@ class MI355XWanModelSpecification(MI355XWanSpecOps):
         ``sample_kwargs``: ``latents_mean`` / ``latents_std`` (the VAE's statistics themselves), ``image_embeds`` / ``condition_latents`` for an
         image-to-video model, ``sigmas`` / ``timesteps`` / ``latents``.  A first/last-frame model (the reference hands ``last_image`` to its pipeline,
         :524-526) takes the CLIP tokens of BOTH images, ``image_embeds`` [B, pos_embed_seq_len, image_dim] (first image, then last), and
-        ``condition_latents`` whose mask channels keep the last frame too: ``condition_mask(..., use_last_frame=True)``."""
+        ``condition_latents`` whose mask channels keep the last frame too: ``condition_mask(..., use_last_frame=True)``.  ``scheduler_config``: None runs
+        flow-match Euler at shift 1; ``validation_scheduler_config()`` gives the checkpoint's own scheduler, which is what the reference's pipeline runs."""
         from .sampler import MI355XWanLatentSampler
 
         return MI355XWanLatentSampler(transformer, scheduler_config).sample(prompt_embeds, negative_prompt_embeds, num_frames, height, width,

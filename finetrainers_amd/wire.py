@@ -295,6 +295,16 @@ def load_transformer_config(directory: str) -> Dict[str, Any]:
         return json.load(f)
 
 
+def load_scheduler_config(pretrained_dir: str) -> Dict[str, Any]:
+    """``<pretrained_dir>/scheduler/scheduler_config.json`` of a local diffusers checkpoint: the scheduler ``from_pretrained`` hands the validation pipeline
+    when the trainer passes none (``_class_name`` names it).  A directory without one RAISES: there is no default to fall back to."""
+    p = os.path.join(pretrained_dir, "scheduler", "scheduler_config.json")
+    if not os.path.exists(p):
+        raise FileNotFoundError(f"no scheduler/scheduler_config.json under {pretrained_dir!r}")
+    with open(p) as f:
+        return json.load(f)
+
+
 # --------------------------------------------------------------------------------------------------------------------------
 # training-state checkpoint in the reference's torch.distributed.checkpoint (DCP) layout
 # --------------------------------------------------------------------------------------------------------------------------

@@ -1020,6 +1020,28 @@ int ftmi_wan_sample(const ftmi_wan_sample_config* cfg, const ftmi_wan_sample_wei
                     const float* head_scale, const void* enc, const void* enc_img, const float* rope_cos, const float* rope_sin, const float* sigmas,
                     void* workspace, size_t workspace_bytes, ftmi_stream stream);
 
+/* The multistep form of the loop: the scheduler of the Wan2.1 checkpoints, [upstream, unpinned] UniPCMultistepScheduler (flow sigmas, data prediction, bh2,
+ * solver_order <= 2), which is what the reference's validation pipeline samples with.  The scheduler is folded on the host into eight numbers per step
+ * (finetrainers_amd/wan/sampler.py wan_unipc_tables): coef_row = (c_x, c_l, c_1, c_2, c_t, p_x, p_0, p_1).
+ * One step, per element in fp32: v as in ftmi_wan_sample_step; m = fma(-sigma, v, x); x~ = c_x x + c_l last + c_1 m1 + c_2 m2 + c_t m; x' = p_x x~ + p_0 m + p_1 m1
+ * (each sum a product, then fmas in this order; a term whose coefficient is 0 is left out and its buffer is not read).  x <- x', last <- x~, m2 <- m (the OLDER
+ * history buffer: the caller swaps m1 and m2 after the step), bf16(x') into columns [0, Kc) of every row group and copy of cols (NULL: no copies).
+ * last / m1 / m2: fp32 [B, S, Kc] like x, four different buffers; coef_row: device fp32 [8]; sigma: device fp32 [1], the step's sigma (it is not one of the eight
+ * numbers: m itself is stored).  Validation and status codes of ftmi_wan_sample_step; pred is required. */
+int ftmi_wan_sample_step_unipc(const ftmi_wan_sample_geometry* geo, const void* pred, float* x, float* last, const float* m1, float* m2, const float* coef_row,
+                               const float* sigma, float guidance, void* cols, ftmi_stream stream);
+/* ftmi_wan_sample's loop with ftmi_wan_sample_step_unipc as the step's last launch; bit-identical to the same launches issued call by call.  coef: device fp32
+ * [steps, 8]; sigmas: device fp32 [steps + 1].  The history lives in the workspace: ftmi_wan_sample_ms_workspace_bytes = ftmi_wan_sample_workspace_bytes(base) plus
+ * three [B, S, Kc] fp32 buffers (0 for a refused configuration; independent of L).  solver: 1 = UniPC; any other value is FTMI_ERR_UNSUPPORTED. */
+typedef struct ftmi_wan_sample_ms_config {
+    ftmi_wan_sample_config base;
+    int solver;
+} ftmi_wan_sample_ms_config;
+size_t ftmi_wan_sample_ms_workspace_bytes(const ftmi_wan_sample_ms_config* cfg);
+int ftmi_wan_sample_ms(const ftmi_wan_sample_ms_config* cfg, const ftmi_wan_sample_weights* w, void* cols, float* x, const void* tproj, const float* head_shift,
+                       const float* head_scale, const void* enc, const void* enc_img, const float* rope_cos, const float* rope_sin, const float* coef,
+                       const float* sigmas, void* workspace, size_t workspace_bytes, ftmi_stream stream);
+
 /* ---- CogVideoX latent sampling (csrc/sample_layout.hip: the layout kernels; csrc/cog_dit.hip: the loop) ----
  * The denoising loop of the reference's validation (finetrainers/models/cogvideox/base_specification.py:335-364 runs CogVideoXPipeline over the transformer
  * that is being trained) in latent space, text-to-video: [upstream, unpinned] CogVideoXPipeline + CogVideoXDDIMScheduler (v-prediction, eta = 0).

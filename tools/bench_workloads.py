@@ -498,6 +498,7 @@ def cpu_baseline_hunyuan(args, ctx) -> Dict[str, Any]:
 # Wan2.1-T2V-1.3B validation sampling in latent space (finetrainers_amd/wan/sampler.py): 49 x 480 x 832 -> latents 13 x 60 x 104 = 20 280 tokens, unconditional +
 # conditional rows (guidance 5), random weights with rank-`--rank` adapters.  One "step" of this workload is one ftmi_wan_sample call of `SAMPLE_STEPS`
 # denoising steps; the report adds the same loop composed in Python (model.forward + ops.wan_sample_step) and the step kernel on its own.
+# `--scheduler unipc`: the checkpoint's UniPCMultistepScheduler at flow_shift 3 (ftmi_wan_sample_ms, ops.wan_sample_step_unipc) instead of flow-match Euler.
 # ------------------------------------------------------------------------------------------------------------------------------------------
 SAMPLE_STEPS = 4
 
@@ -529,7 +530,8 @@ def build_wan_sample(args, par, dev) -> Dict[str, Any]:
             blk.lora_B[:, :, :args.rank].normal_(0, 0.01, generator=g)
     B, C, F_, H, W, T, guidance, n = 1, 16, 13, 60, 104, 512, 5.0, SAMPLE_STEPS
     S = F_ * (H // 2) * (W // 2)
-    sampler = MI355XWanLatentSampler(model)
+    unipc = getattr(args, "scheduler", "euler") == "unipc"  # the checkpoint's UniPCMultistepScheduler (flow_shift 3.0): ftmi_wan_sample_ms
+    sampler = MI355XWanLatentSampler(model, {"_class_name": "UniPCMultistepScheduler", "flow_shift": 3.0} if unipc else None)
     pos, neg = (torch.randn((B, T, cfg.text_dim), generator=g, device=dev).to(bf16) for _ in range(2))
     latents = torch.randn((B, C, F_, H, W), generator=g, device=dev)
     sig, ts = sampler.schedule(n, None, None)
@@ -537,13 +539,25 @@ def build_wan_sample(args, par, dev) -> Dict[str, Any]:
     enc = sampler.text_rows(pos, neg)
     tproj, shift, scale = sampler.step_tables(ts, 2 * B)
     ccfg, weights, keep = sampler.c_arguments(geo, T, 0, n, guidance)
-    ws_bytes = ops.wan_sample_workspace_bytes(ccfg)
+    ws_bytes = ops.wan_sample_ms_workspace_bytes(ccfg) if unipc else ops.wan_sample_workspace_bytes(ccfg)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    rope, sig_dev = model._rope(F_, H, W), sig.to(dev)
+    rope, sig_dev = model._rope(F_, H, W), sig.float().to(dev)
+    coef = sampler.unipc_tables(sig).to(dev) if unipc else None
+
+    def step(i, pred, x, cols, hist):
+        """The step launch of denoising step i from Python; ``hist``: [last, m1, m2] of the multistep solver, swapped here as the C loop swaps them."""
+        if unipc:
+            ops.wan_sample_step_unipc(geo, pred, x, hist[0], hist[1], hist[2], coef[i], sig_dev[i:i + 1], guidance, cols)
+            hist[1], hist[2] = hist[2], hist[1]
+        else:
+            ops.wan_sample_step(geo, pred, x, sig_dev[i:i + 1].expand(B).contiguous(), sig_dev[i + 1:i + 2].expand(B).contiguous(), guidance, cols)
 
     def one_call():
         x, cols = ops.wan_sample_init(geo, latents)
-        ops.wan_sample(ccfg, weights, cols, x, tproj, shift, scale, enc, None, rope, sig_dev, workspace=ws)
+        if unipc:
+            ops.wan_sample_ms(ccfg, weights, cols, x, tproj, shift, scale, enc, None, rope, coef, sig_dev, workspace=ws)
+        else:
+            ops.wan_sample(ccfg, weights, cols, x, tproj, shift, scale, enc, None, rope, sig_dev, workspace=ws)
         return None
 
     def timed(fn, reps):
@@ -559,13 +573,14 @@ def build_wan_sample(args, par, dev) -> Dict[str, Any]:
     @torch.no_grad()
     def composed():
         x, cols = ops.wan_sample_init(geo, latents)
+        hist = [torch.empty_like(x) for _ in range(3)] if unipc else None
         text = torch.cat([neg, pos])
         for i in range(n):
             t = torch.full((2 * B,), float(ts[i]), dtype=torch.float32, device=dev)
             hidden = cols.view(2 * B, F_, H // 2, W // 2, C, 1, 2, 2).permute(0, 4, 1, 5, 2, 6, 3, 7).reshape(2 * B, C, F_, H, W)
             out = model(hidden, t, text)[0]
             pred = out.reshape(2 * B, C, F_, 1, H // 2, 2, W // 2, 2).permute(0, 2, 4, 6, 3, 5, 7, 1).reshape(2 * B, S, 4 * C).contiguous()
-            ops.wan_sample_step(geo, pred, x, sig_dev[i:i + 1].expand(B).contiguous(), sig_dev[i + 1:i + 2].expand(B).contiguous(), guidance, cols)
+            step(i, pred, x, cols, hist)
 
     def report(one_call_ms: float) -> Dict[str, Any]:
         peak_one = torch.cuda.max_memory_allocated() / 1e9
@@ -575,18 +590,20 @@ def build_wan_sample(args, par, dev) -> Dict[str, Any]:
         peak_comp = torch.cuda.max_memory_allocated() / 1e9
         x, cols = ops.wan_sample_init(geo, latents)
         pred = torch.randn((2 * B, S, 4 * C), generator=g, device=dev).to(bf16)
-        s0, s1 = sig_dev[0:1].contiguous(), sig_dev[1:2].contiguous()
+        hist = [torch.zeros_like(x) for _ in range(3)] if unipc else None
+        k = 2 if unipc else 0  # the multistep kernel is timed on a full order-2 row (step 2 of the run): every buffer is read
         reps = 50
         for _ in range(5):
-            ops.wan_sample_step(geo, pred, x, s0, s1, guidance, cols)
+            step(k, pred, x, cols, hist)
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
         for _ in range(reps):
-            ops.wan_sample_step(geo, pred, x, s0, s1, guidance, cols)
+            step(k, pred, x, cols, hist)
         b.record()
         torch.cuda.synchronize()
         us = a.elapsed_time(b) * 1e3 / reps
-        nbytes = B * S * 4 * C * 16  # per element of x: read u 2 + c 2 + x 4, write x 4 + 2 x 2
+        # per element of x: read u 2 + c 2 + x 4, write x 4 + 2 x 2; the multistep step reads last, m1, m2 and writes last, m on top: 20 more
+        nbytes = B * S * 4 * C * (36 if unipc else 16)
         return {"ms_per_denoising_step_one_call": one_call_ms / n, "ms_per_denoising_step_python_composition": comp_ms / n,
                 "peak_memory_gb_one_call": peak_one, "peak_memory_gb_python_composition": peak_comp, "workspace_gb": ws_bytes / 1e9,
                 "step_kernel_us": us, "step_kernel_bytes": nbytes, "step_kernel_gbps": nbytes / (us * 1e-6) / 1e9}
@@ -598,10 +615,11 @@ def build_wan_sample(args, par, dev) -> Dict[str, Any]:
         "report": report,
         "samples_per_step": 1.0 / n,
         "step_tflop": n * layers * (lin + att) / 1e12,
-        "metric": f"ftmi_wan_sample: one call of {n} denoising steps, Wan-T2V-1.3B 49x480x832, guidance 5 (value: denoising steps per ms are in the report)",
+        "metric": f"{'ftmi_wan_sample_ms (UniPC, flow_shift 3)' if unipc else 'ftmi_wan_sample'}: one call of {n} denoising steps, Wan-T2V-1.3B 49x480x832, guidance 5 "
+                  "(value: denoising steps per ms are in the report)",
         "data": "random noise [1,16,13,60,104] + random text embeds [1,512,4096] (conditional and unconditional), random-init weights of the Wan2.1-T2V-1.3B DiT",
         "config": {"workload": f"Wan-T2V-1.3B latent sampling, rank={args.rank} adapters, {S} video + {T} text tokens, 2 model rows (unconditional + conditional), {layers} blocks"
-                               + ("" if layers == 30 else " -- REDUCED depth"), "seq_len": S, "denoising_steps_per_call": n},
+                               + ("" if layers == 30 else " -- REDUCED depth"), "seq_len": S, "denoising_steps_per_call": n, "scheduler": "unipc" if unipc else "euler"},
         "layers": layers,
     }
 
@@ -933,6 +951,8 @@ def main() -> None:
     ap.add_argument("--ffn-adapters", dest="ffn_adapters", action="store_true", help="wan_lora / ltx_lora: adapters on the two feed-forward projections as well (ten per block)")
     ap.add_argument("--text-adapters", dest="text_adapters", action="store_true",
                     help="hunyuan / hy_sample: the shipped recipe's target_modules -- adapters on add_q_proj / add_k_proj / add_v_proj / to_add_out of the dual-stream blocks too")
+    ap.add_argument("--scheduler", choices=("euler", "unipc"), default="euler",
+                    help="wan_sample: flow-match Euler at shift 1 (ftmi_wan_sample) or the checkpoint's UniPC multistep scheduler at flow_shift 3 (ftmi_wan_sample_ms)")
     ap.add_argument("--last-frame", dest="last_frame", action="store_true",
                     help="wan_i2v_lora: the first/last-frame model (pos_embed_seq_len = 514: two images, 514 image keys in attn2) at the same geometry")
     args = ap.parse_args()
