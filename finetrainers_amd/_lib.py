@@ -211,6 +211,12 @@ class CogSampleConfig(Structure):
                 ("r", c_int), ("lora_scale", c_float), ("eps_norm", c_float), ("eps_qk", c_float), ("gemm_variant", c_int), ("steps", c_int), ("guidance", c_float)]
 
 
+class CogSampleMsConfig(Structure):
+    """include/ftmi355.h: ftmi_cog_sample_ms_config (``solver``: 1 = DPM)."""
+
+    _fields_ = [("base", CogSampleConfig), ("solver", c_int)]
+
+
 COG_SAMPLE_WEIGHT_FIELDS = ["patch_w", "patch_b", "text_w", "text_b", "pos", "norm_final_w", "norm_final_b", "norm_out_w", "norm_out_b", "proj_w", "proj_b", "ones",
                             "zeros"]
 
@@ -433,6 +439,10 @@ _SIGS = {
     "ftmi_cog_sample_finish": (c_int, [POINTER(CogSampleGeometry), c_void_p, c_float, c_void_p, c_void_p]),
     "ftmi_cog_sample_workspace_bytes": (c_size_t, [POINTER(CogSampleConfig)]),
     "ftmi_cog_sample": (c_int, [POINTER(CogSampleConfig), POINTER(CogSampleWeights)] + [c_void_p] * 8 + [c_size_t, c_void_p]),
+    "ftmi_cog_sample_step_dpm": (c_int, [POINTER(CogSampleGeometry)] + [c_void_p] * 7),
+    "ftmi_cog_sample_pack": (c_int, [POINTER(CogSampleGeometry), c_void_p, c_int, c_void_p, c_void_p]),
+    "ftmi_cog_sample_ms_workspace_bytes": (c_size_t, [POINTER(CogSampleMsConfig)]),
+    "ftmi_cog_sample_ms": (c_int, [POINTER(CogSampleMsConfig), POINTER(CogSampleWeights)] + [c_void_p] * 8 + [c_int, c_void_p, c_size_t, c_void_p]),
     "ftmi_hy_sample_init": (c_int, [POINTER(HySampleGeometry), c_void_p, c_void_p, c_void_p, c_void_p]),
     "ftmi_hy_sample_step": (c_int, [POINTER(HySampleGeometry), c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p]),
     "ftmi_hy_sample_finish": (c_int, [POINTER(HySampleGeometry), c_void_p, c_float, c_void_p, c_void_p]),

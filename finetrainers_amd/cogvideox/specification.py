@@ -203,7 +203,11 @@ class MI355XCogVideoXModelSpecification(MI355XCogVideoXSpecOps):
         """The denoising loop of ``validation`` (base_specification.py:335-364 runs ``CogVideoXPipeline``) over this backend's transformer, in latent space:
         ``MI355XCogVideoXLatentSampler.sample`` on the LATENT grid -> denormalised latents [B, num_frames, C, height, width] bf16 for the reference
         pipeline's VAE decode.  The noise is ``randn([B, F_pad, C, H, W], fp32, generator)`` on the transformer's device (or ``latents``), ``F_pad`` =
-        ``num_frames`` raised to a multiple of ``patch_size_t``: the pipeline pads at the front and drops those frames after the loop, and so does this."""
+        ``num_frames`` raised to a multiple of ``patch_size_t``: the pipeline pads at the front and drops those frames after the loop, and so does this.
+        ``scheduler_config``: None runs DDIM with the 2b checkpoint's settings; ``validation_scheduler_config()`` gives the checkpoint's own scheduler, which
+        is what the reference's pipeline runs.  With ``CogVideoXDPMScheduler`` the same ``generator`` then gives the noise of every step, initial noise first,
+        the pipeline's order (``sample_kwargs``: ``step_noise`` instead; ``use_dynamic_cfg``, with that scheduler only); that noise costs ``4 n B S Kc`` bytes for the whole call, about
+        23 MB per step and 1.1 GB for 50 steps at 81 x 768 x 1360."""
         from .sampler import MI355XCogVideoXLatentSampler
 
         c = transformer.config
@@ -214,7 +218,25 @@ class MI355XCogVideoXModelSpecification(MI355XCogVideoXSpecOps):
                                   dtype=torch.float32)
         return MI355XCogVideoXLatentSampler(transformer, scheduler_config).sample(
             latents, prompt_embeds, negative_prompt_embeds, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale, drop_frames=extra,
-            scaling_factor=self.vae_scaling_factor, invert_scale_latents=self.invert_scale_latents, **sample_kwargs)
+            scaling_factor=self.vae_scaling_factor, invert_scale_latents=self.invert_scale_latents, generator=generator, **sample_kwargs)
+
+    def validation_scheduler_config(self, transformer=None) -> Dict[str, object]:
+        """The ``scheduler_config`` for ``validation_latents`` that makes it sample as the reference's validation does: the scheduler stored in the checkpoint
+        (``load_pipeline`` passes none, so ``from_pretrained`` loads ``<pretrained_model_name_or_path>/scheduler``).  When the path is not a local directory
+        (a hub id cannot be resolved here) the default of the geometry: ``COG_DPM_SCHEDULER_CONFIG`` for a rotary model (5b, 1.5), the DDIM one for a sincos
+        model (2b).  The geometry is ``transformer.config`` or the specification's ``transformer_config``."""
+        import os
+
+        from .. import wire
+        from .sampler import COG_DPM_SCHEDULER_CONFIG, COG_SCHEDULER_CONFIG
+
+        root = self.pretrained_model_name_or_path
+        if root and os.path.isdir(root):
+            return wire.load_scheduler_config(root)
+        cfg = transformer.config if transformer is not None else self.transformer_config
+        if cfg is None:
+            raise ValueError("validation_scheduler_config: no checkpoint directory and no transformer config to tell the rotary models from the sincos one")
+        return dict(COG_DPM_SCHEDULER_CONFIG if cfg.use_rotary_positional_embeddings else COG_SCHEDULER_CONFIG)
 
     def _save_lora_weights(self, directory: str, transformer_state_dict: Optional[Dict[str, torch.Tensor]] = None, scheduler=None,
                            metadata: Optional[Dict[str, str]] = None, *args, **kwargs) -> None:

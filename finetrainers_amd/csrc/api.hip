@@ -1135,6 +1135,28 @@ int ftmi_cog_sample(const ftmi_cog_sample_config* cfg, const ftmi_cog_sample_wei
                       workspace_bytes, (hipStream_t)stream);
 }
 
+int ftmi_cog_sample_step_dpm(const ftmi_cog_sample_geometry* geo, const void* pred, float* x, float* old, const float* noise, const float* coef_row, void* cols,
+                             ftmi_stream stream) {
+    if (!geo || !pred || !x || !old || !coef_row) return set_error(FTMI_ERR_INVALID, "ftmi_cog_sample_step_dpm: null argument");
+    return cog_sample_step_dpm(*geo, (const bf16_t*)pred, x, old, noise, coef_row, (bf16_t*)cols, (hipStream_t)stream);
+}
+
+int ftmi_cog_sample_pack(const ftmi_cog_sample_geometry* geo, const float* latents, int n, float* out, ftmi_stream stream) {
+    if (!geo || !latents || !out) return set_error(FTMI_ERR_INVALID, "ftmi_cog_sample_pack: null argument");
+    return cog_sample_pack(*geo, latents, n, out, (hipStream_t)stream);
+}
+
+size_t ftmi_cog_sample_ms_workspace_bytes(const ftmi_cog_sample_ms_config* cfg) { return cfg ? cog_sample_ms_workspace_bytes(*cfg) : 0; }
+
+int ftmi_cog_sample_ms(const ftmi_cog_sample_ms_config* cfg, const ftmi_cog_sample_weights* w, void* cols, float* x, const void* text, const void* temb_silu,
+                       const void* head_shift, const void* head_onep, const float* coef, const float* noise, int noise_steps, void* workspace,
+                       size_t workspace_bytes, ftmi_stream stream) {
+    if (!cfg || !w || !cols || !x || !text || !temb_silu || !head_shift || !head_onep || !coef || !workspace)
+        return set_error(FTMI_ERR_INVALID, "ftmi_cog_sample_ms: null argument");
+    return cog_sample_ms(*cfg, *w, (bf16_t*)cols, x, (const bf16_t*)text, (const bf16_t*)temb_silu, (const bf16_t*)head_shift, (const bf16_t*)head_onep, coef, noise,
+                         noise_steps, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 int ftmi_hy_sample_init(const ftmi_hy_sample_geometry* geo, const float* latents, float* x, void* cols, ftmi_stream stream) {
     if (!geo || !latents || !x || !cols) return set_error(FTMI_ERR_INVALID, "ftmi_hy_sample_init: null argument");
     return hy_sample_init(*geo, latents, x, (bf16_t*)cols, (hipStream_t)stream);

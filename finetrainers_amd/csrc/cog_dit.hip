@@ -347,6 +347,9 @@ int cog_blocks_backward(const ftmi_cog_config& c, const ftmi_cog_weights& w, con
 //   cog_sample_step                 guidance combine + DDIM update on the state, bf16 copies into cols
 // Workspace: the modulation GEMM's output and tables (the only part that grows with L), tokens_in, the two hidden-state buffers, ONE block's forward slot, the
 // two forward scratch buffers, nf / no of the head and pred.  None of the backward's stash or scratch areas.
+// ftmi_cog_sample_ms is the same loop (cog_sample_loop, one body for both) whose last launch is cog_sample_step_dpm: the 5b / 1.5 checkpoints'
+// CogVideoXDPMScheduler, which is what the reference's validation pipeline runs for them.  Its history, the previous step's x0 prediction, is one [B, S, Kc]
+// fp32 buffer behind the DDIM workspace; the step's eight numbers (its guidance scale among them) and its noise slice come from device tables the caller filled.
 namespace {
 
 struct CogSamplePlan {
@@ -398,11 +401,13 @@ size_t cog_sample_workspace_bytes(const ftmi_cog_sample_config& c) {
     return make_sample_plan(c, p) ? 0 : p.total;
 }
 
-int cog_sample(const ftmi_cog_sample_config& c, const ftmi_cog_sample_weights& w, bf16_t* cols, float* x, const bf16_t* text, const bf16_t* temb_silu,
-               const bf16_t* head_shift, const bf16_t* head_onep, const float* coef, void* ws, size_t ws_bytes, hipStream_t st) {
-    CogSamplePlan p;
-    FTMI_TRY(make_sample_plan(c, p));
-    if (ws_bytes < p.total) return set_error(FTMI_ERR_INVALID, "cog_sample: workspace too small (ftmi_cog_sample_workspace_bytes)");
+namespace {
+
+// The loop of both entry points.  step(i, pred): the launch that takes the step's prediction into the state and cols.  `need`: the entry point's workspace.
+template <class Step>
+int cog_sample_loop(const ftmi_cog_sample_config& c, const CogSamplePlan& p, size_t need, const ftmi_cog_sample_weights& w, bf16_t* cols, const bf16_t* text,
+                    const bf16_t* temb_silu, const bf16_t* head_shift, const bf16_t* head_onep, void* ws, size_t ws_bytes, hipStream_t st, Step step) {
+    if (ws_bytes < need) return set_error(FTMI_ERR_INVALID, "cog_sample: workspace too small (ftmi_cog_sample_workspace_bytes)");
     if (reinterpret_cast<uintptr_t>(ws) & 255) return set_error(FTMI_ERR_INVALID, "cog_sample: the workspace must be 256-byte aligned");
     if (!w.patch_w || !w.patch_b || !w.text_w || !w.text_b || !w.norm_final_w || !w.norm_final_b || !w.norm_out_w || !w.norm_out_b || !w.proj_w || !w.proj_b ||
         !w.ones || !w.zeros || !w.blocks.mod_w || !w.blocks.w_qkv)
@@ -444,9 +449,52 @@ int cog_sample(const ftmi_cog_sample_config& c, const ftmi_cog_sample_weights& w
             FTMI_TRY(cog_ln_mod_fwd(a, st));
             FTMI_TRY(gemm_nt(linear_args(no, D, rows * S, P(w.proj_w, 0), D, Kc, D, P(w.proj_b, 0), pred, Kc, V), st));
         }
-        FTMI_TRY(cog_sample_step(g, pred, x, coef, i, c.guidance, cols, st));
+        FTMI_TRY(step(i, pred));
     }
     return 0;
+}
+
+// The history of the multistep solver behind the DDIM plan: old fp32 [B, S, Kc] (p.total is a multiple of 256: the buffer is 16-byte aligned).
+int make_sample_ms_plan(const ftmi_cog_sample_ms_config& c, CogSamplePlan& p, size_t& old_off, size_t& total) {
+    if (c.solver != 1) return set_error(FTMI_ERR_UNSUPPORTED, "cog_sample_ms: solver 1 (DPM) is the one multistep solver");
+    FTMI_TRY(make_sample_plan(c.base, p));
+    Bump w;
+    w.off = p.total;
+    old_off = w.take((size_t)c.base.geo.B * p.S * p.Kc * sizeof(float));
+    total = w.off;
+    return 0;
+}
+
+}  // namespace
+
+int cog_sample(const ftmi_cog_sample_config& c, const ftmi_cog_sample_weights& w, bf16_t* cols, float* x, const bf16_t* text, const bf16_t* temb_silu,
+               const bf16_t* head_shift, const bf16_t* head_onep, const float* coef, void* ws, size_t ws_bytes, hipStream_t st) {
+    CogSamplePlan p;
+    FTMI_TRY(make_sample_plan(c, p));
+    return cog_sample_loop(c, p, p.total, w, cols, text, temb_silu, head_shift, head_onep, ws, ws_bytes, st,
+                           [&](int i, const bf16_t* pred) { return cog_sample_step(c.geo, pred, x, coef, i, c.guidance, cols, st); });
+}
+
+size_t cog_sample_ms_workspace_bytes(const ftmi_cog_sample_ms_config& c) {
+    CogSamplePlan p;
+    size_t old_off, total;
+    return make_sample_ms_plan(c, p, old_off, total) ? 0 : total;
+}
+
+int cog_sample_ms(const ftmi_cog_sample_ms_config& c, const ftmi_cog_sample_weights& w, bf16_t* cols, float* x, const bf16_t* text, const bf16_t* temb_silu,
+                  const bf16_t* head_shift, const bf16_t* head_onep, const float* coef, const float* noise, int noise_steps, void* ws, size_t ws_bytes,
+                  hipStream_t st) {
+    CogSamplePlan p;
+    size_t old_off, total;
+    FTMI_TRY(make_sample_ms_plan(c, p, old_off, total));
+    // The rows live on the device; what the host knows is how many leading steps have a slice.  A step past them runs with no noise (its row has mn == 0).
+    if (noise_steps < 0 || noise_steps > c.base.steps) return set_error(FTMI_ERR_INVALID, "cog_sample_ms: noise_steps counts the leading steps with a noise slice, 0 .. steps");
+    if ((noise_steps > 0) != (noise != nullptr)) return set_error(FTMI_ERR_INVALID, "cog_sample_ms: noise goes with noise_steps > 0, and only with it");
+    float* old = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + old_off);
+    const size_t slice = (size_t)c.base.geo.B * p.S * p.Kc;
+    return cog_sample_loop(c.base, p, total, w, cols, text, temb_silu, head_shift, head_onep, ws, ws_bytes, st, [&](int i, const bf16_t* pred) {
+        return cog_sample_step_dpm(c.base.geo, pred, x, old, i < noise_steps ? noise + (size_t)i * slice : nullptr, coef + (size_t)i * 8, cols, st);
+    });
 }
 
 }  // namespace ftmi

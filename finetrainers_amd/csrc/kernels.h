@@ -354,6 +354,14 @@ int cog_sample_finish(const ftmi_cog_sample_geometry& g, const float* x, float k
 size_t cog_sample_workspace_bytes(const ftmi_cog_sample_config& c);
 int cog_sample(const ftmi_cog_sample_config& c, const ftmi_cog_sample_weights& w, bf16_t* cols, float* x, const bf16_t* text, const bf16_t* temb_silu,
                const bf16_t* head_shift, const bf16_t* head_onep, const float* coef, void* ws, size_t ws_bytes, hipStream_t st);
+// the multistep (DPM) step, the noise packer and the loop that carries them (include/ftmi355.h: ftmi_cog_sample_ms)
+int cog_sample_step_dpm(const ftmi_cog_sample_geometry& g, const bf16_t* pred, float* x, float* old, const float* noise, const float* coef_row, bf16_t* cols,
+                        hipStream_t st);
+int cog_sample_pack(const ftmi_cog_sample_geometry& g, const float* latents, int n, float* out, hipStream_t st);
+size_t cog_sample_ms_workspace_bytes(const ftmi_cog_sample_ms_config& c);
+int cog_sample_ms(const ftmi_cog_sample_ms_config& c, const ftmi_cog_sample_weights& w, bf16_t* cols, float* x, const bf16_t* text, const bf16_t* temb_silu,
+                  const bf16_t* head_shift, const bf16_t* head_onep, const float* coef, const float* noise, int noise_steps, void* ws, size_t ws_bytes,
+                  hipStream_t st);
 // ---- Wan-T2V row-wise kernels (wan.hip): one argument block for the seven launchers --------------------------------------------------------
 struct WanRowArgs {
     const bf16_t* x = nullptr;   // input rows [rows, ld_x]   (gate_res_bwd: d out)

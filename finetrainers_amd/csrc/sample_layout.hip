@@ -44,6 +44,15 @@
 //   CogVideoX: (cx, cv) are the step's two numbers of the host-folded scheduler ([upstream, unpinned] CogVideoXDDIMScheduler.step is linear in (x, v):
 //   finetrainers_amd/cogvideox/sampler.py cog_ddim_tables), read from a device table.  A thread owns 8 consecutive elements; the last workgroup's tail is
 //   masked.  Bytes moved per element of x: 12 + 2 P with guidance = 16; 10 + 2 = 12 without.
+//   CogVideoX, multistep (cog_sample_step_dpm): the 5b / 1.5 checkpoints' [upstream, unpinned] CogVideoXDPMScheduler, a second-order multistep SDE solver that
+//   keeps the previous step's x0 prediction and adds fresh noise z at every step but the last, folded on the host into eight numbers per step
+//   (finetrainers_amd/cogvideox/sampler.py cog_dpm_tables): row = (sa, sb, m0, e0, e1, mn, g, 0), g the step's guidance scale.  The same stream; per element:
+//       x0 = fma(-sb, v, sa x)                                          the data prediction of this step
+//       x' = m0 x;  x' = fma(e0, x0, x');  fma(e1, old, x');  fma(mn, z, x')
+//   a term whose coefficient is 0 is neither loaded nor added (old is uninitialised at step 0, the last step has no noise).  x' goes to x and, as bf16, to cols;
+//   x0 to old.  Bytes moved per element of x with guidance, full row: read u 2 + c 2 + x 4 + old 4 + z 4 = 16, write x 4 + old 4 + 2 P copies = 12: 28.
+//   cog_sample_pack: init's permutation over n noise tensors at once (the per-step noise of that solver, into the state's layout): sample_init_kernel over n B
+//   samples with no row group of cols to write.
 //   HunyuanVideo (hy_sample_step): CogVideoX's layout over [B, C, F, H, W] latents (Lay::sc, sf as Wan's; Cx = 0, copies = 1, Kp = Kc, drop = 0; finish is
 //   the scalar affine with k = 1 / scaling_factor) and Wan's update: dt = sigmas[step + 1] - sigmas[step] read from the device table, x <- fma(dt, v, x).  A
 //   row-major stream like CogVideoX's.  Bytes moved per element of x: 10 without true CFG (pred 2 + x 4 read, x 4 + cols 2 written), 16 with.
@@ -298,6 +307,33 @@ __global__ __launch_bounds__(256) void cog_sample_step_kernel(const bf16_t* __re
     if (cols) store_groups8<kCfg>(cols, xv, 8 * i, 8 * n8);
 }
 
+// The multistep step of CogVideoX: cog_sample_step_kernel's stream (n8 = B S Kc / 8 vectors, one per thread) with the DPM update of the file header.  row: the
+// step's eight numbers (sa, sb, m0, e0, e1, mn, g, 0) on the device.  old / z fp32 [B, S, Kc] like x; vector i of x and old is read and written by thread i alone.
+// A zero e1 / mn leaves its term out and its buffer unread (lin_term8); z == nullptr is read as mn == 0.
+template <bool kCfg>
+__global__ __launch_bounds__(256) void cog_sample_step_dpm_kernel(const bf16_t* __restrict__ pred, float* __restrict__ x, float* __restrict__ old,
+                                                                  const float* __restrict__ z, const float* __restrict__ row, bf16_t* __restrict__ cols, long n8) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n8) return;
+    const float sa = row[0], sb = row[1], m0 = row[2], e0 = row[3], e1 = row[4], mn = z ? row[5] : 0.0f, gd = row[6];
+    float xv[8], v[8], p0[8], ov[8], zv[8], a[8];
+    load8(x, i, xv);
+    cfg_combine8<kCfg>(pred, i, n8, gd, v);
+    if (e1 != 0.0f) load8(old, i, ov);
+    if (mn != 0.0f) load8(z, i, zv);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        p0[e] = __builtin_fmaf(-sb, v[e], sa * xv[e]);
+        a[e] = __builtin_fmaf(e0, p0[e], m0 * xv[e]);
+    }
+    bool first = false;
+    lin_term8(e1, ov, a, first);
+    lin_term8(mn, zv, a, first);
+    store8(x, i, a);
+    store8(old, i, p0);
+    if (cols) store_groups8<kCfg>(cols, a, 8 * i, 8 * n8);
+}
+
 // n8 = B S Kc / 8 vectors, one per thread; grid ceil(n8 / 256).  kCfg: two row groups (pred has an unconditional half).
 template <bool kCfg>
 __global__ __launch_bounds__(256) void hy_sample_step_kernel(const bf16_t* __restrict__ pred, float* __restrict__ x, const float* __restrict__ sigmas, int step,
@@ -545,6 +581,33 @@ int cog_sample_step(const ftmi_cog_sample_geometry& g, const bf16_t* pred, float
     else
         hipLaunchKernelGGL((cog_sample_step_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, st, pred, x, coef, step, guidance, cols, n8);
     return check_launch("cog_sample_step");
+}
+
+int cog_sample_step_dpm(const ftmi_cog_sample_geometry& g, const bf16_t* pred, float* x, float* old, const float* noise, const float* coef_row, bf16_t* cols,
+                        hipStream_t st) {
+    Lay l;
+    FTMI_TRY(cog_lay(g, "cog_sample_step_dpm", l));
+    if (!pred || !x || !old || !coef_row) return set_error(FTMI_ERR_INVALID, "cog_sample_step_dpm: pred, x, old or the coefficient row missing");
+    if (misaligned(pred) || misaligned(x) || misaligned(old) || misaligned(noise) || misaligned(cols))
+        return set_error(FTMI_ERR_INVALID, "cog_sample_step_dpm: tensors must be 16-byte aligned");
+    if (x == old || x == noise || old == noise) return set_error(FTMI_ERR_INVALID, "cog_sample_step_dpm: x, old and noise are three buffers");
+    const long n8 = (long)g.B * l.S * l.Kc / 8, blocks = (n8 + 255) / 256;
+    if (g.P == 2)
+        hipLaunchKernelGGL((cog_sample_step_dpm_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, st, pred, x, old, noise, coef_row, cols, n8);
+    else
+        hipLaunchKernelGGL((cog_sample_step_dpm_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, st, pred, x, old, noise, coef_row, cols, n8);
+    return check_launch("cog_sample_step_dpm");
+}
+
+int cog_sample_pack(const ftmi_cog_sample_geometry& g, const float* latents, int n, float* out, hipStream_t st) {
+    if (n <= 0 || g.B <= 0 || (long)n * g.B > 0x7fffffffL) return set_error(FTMI_ERR_INVALID, "cog_sample_pack: n and B must be positive (and n B fit an int)");
+    ftmi_cog_sample_geometry gn = g;
+    gn.B = n * g.B;  // n tensors of B samples are n B samples to the index map
+    Lay l;
+    FTMI_TRY(cog_lay(gn, "cog_sample_pack", l));
+    if ((long)l.B * l.S * l.Kc / 8 > 0x7fffffffL * 256L) return fail("cog_sample_pack", FTMI_ERR_UNSUPPORTED, "too many elements for one launch");
+    l.P = 0;  // no row group of cols is written
+    return launch_init(l, "cog_sample_pack", latents, nullptr, out, nullptr, st);
 }
 
 int cog_sample_finish(const ftmi_cog_sample_geometry& g, const float* x, float k, bf16_t* latents, hipStream_t st) {

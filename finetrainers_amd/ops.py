@@ -1380,6 +1380,82 @@ def cog_sample(cfg, weights, cols, x, text, temb_silu, head_shift, head_onep, co
                                       ptr(coef), ptr(workspace), workspace.numel(), stream_ptr()), "ftmi_cog_sample")
 
 
+def cog_sample_step_dpm(geo, pred, x, old, noise, coef_row, cols=None) -> None:
+    """One step of the multistep (DPM) sampler in place (ftmi_cog_sample_step_dpm): pred bf16 [P B, S, Kc]; x / old fp32 [B, S, Kc], two buffers (x <- x',
+    old <- x0); noise fp32 [B, S, Kc], the step's slice in the state's layout, or None for a row with mn == 0; coef_row fp32 [8] on the device
+    (``cog_dpm_tables``: sa, sb, m0, e0, e1, mn, g, 0); cols bf16 [P B S, Kc] (None: only the update)."""
+    _cog_sample_buffers(geo, x, cols, "cog_sample_step_dpm")
+    S, Kc = _cog_sample_dims(geo)
+    require_gpu_tensor(pred, "pred", bf16)
+    if pred.numel() != geo.P * geo.B * S * Kc or not pred.is_contiguous():
+        raise ValueError(f"cog_sample_step_dpm: pred must be contiguous [{geo.P * geo.B}, {S}, {Kc}], got {tuple(pred.shape)}")
+    for n, t in (("old", old), ("noise", noise)):
+        if t is None and n == "noise":
+            continue
+        require_gpu_tensor(t, n, torch.float32)
+        if tuple(t.shape) != tuple(x.shape) or not t.is_contiguous():
+            raise ValueError(f"cog_sample_step_dpm: {n} must be a contiguous fp32 {list(x.shape)} tensor like x, got {tuple(t.shape)}")
+    require_gpu_tensor(coef_row, "coef_row", torch.float32)
+    if coef_row.numel() != 8 or not coef_row.is_contiguous():
+        raise ValueError("cog_sample_step_dpm: coef_row holds 8 contiguous values")
+    check(_lib.load().ftmi_cog_sample_step_dpm(ctypes.byref(geo), ptr(pred), ptr(x), ptr(old), ptr(noise), ptr(coef_row), ptr(cols), stream_ptr()),
+          "ftmi_cog_sample_step_dpm")
+
+
+def cog_sample_pack(geo, latents, out=None):
+    """latents fp32 [n, B, F, C, H, W] -> fp32 [n, B, S, Kc], ``cog_sample_init``'s permutation over n tensors at once (ftmi_cog_sample_pack).  ``out``: a
+    contiguous fp32 [>= n, B, S, Kc] GPU tensor whose first n slices are written (allocated when None)."""
+    require_gpu_tensor(latents, "latents", torch.float32)
+    if latents.dim() != 6 or tuple(latents.shape[1:]) != (geo.B, geo.F, geo.C, geo.H, geo.W) or not latents.is_contiguous() or latents.shape[0] < 1:
+        raise ValueError(f"cog_sample_pack: latents must be contiguous [n, {geo.B}, {geo.F}, {geo.C}, {geo.H}, {geo.W}], got {tuple(latents.shape)}")
+    n = latents.shape[0]
+    S, Kc = _cog_sample_dims(geo)
+    out = torch.empty((n, geo.B, S, Kc), dtype=torch.float32, device=latents.device) if out is None else out
+    if not out.is_cuda or out.dtype != torch.float32 or out.dim() != 4 or tuple(out.shape[1:]) != (geo.B, S, Kc) or out.shape[0] < n or not out.is_contiguous():
+        raise ValueError(f"cog_sample_pack: out must be a contiguous fp32 [>= {n}, {geo.B}, {S}, {Kc}] GPU tensor, got {tuple(out.shape)}")
+    check(_lib.load().ftmi_cog_sample_pack(ctypes.byref(geo), ptr(latents), n, ptr(out), stream_ptr()), "ftmi_cog_sample_pack")
+    return out
+
+
+def cog_sample_ms_config(cfg, solver: int = 1) -> "_lib.CogSampleMsConfig":
+    """ftmi_cog_sample_ms_config over a ``CogSampleConfig`` (``solver`` 1: DPM)."""
+    return _lib.CogSampleMsConfig(base=cfg, solver=int(solver))
+
+
+def cog_sample_ms_workspace_bytes(cfg, solver: int = 1) -> int:
+    n = int(_lib.load().ftmi_cog_sample_ms_workspace_bytes(ctypes.byref(cog_sample_ms_config(cfg, solver))))
+    if n == 0:
+        raise ValueError(f"cog_sample_ms: {_lib.last_error()}")
+    return n
+
+
+def cog_sample_ms(cfg, weights, cols, x, text, temb_silu, head_shift, head_onep, coef, noise=None, workspace=None, solver: int = 1) -> None:
+    """``cog_sample`` with the multistep (DPM) step (ftmi_cog_sample_ms): ``cfg`` is the same ``CogSampleConfig``; coef fp32 [steps, 8] (``cog_dpm_tables``) on the
+    device; noise fp32 [k, B, S, Kc] (``cog_sample_pack``), the slices of the k <= steps leading steps -- every later row must have mn == 0 -- or None when no
+    row has noise.  ``workspace``: at least ``cog_sample_ms_workspace_bytes(cfg)`` bytes -- the previous x0 prediction lives there."""
+    geo, n, D = cfg.geo, cfg.steps, cfg.D
+    _cog_sample_buffers(geo, x, cols, "cog_sample_ms")
+    S, Kc = _cog_sample_dims(geo)
+    rows = geo.P * geo.B
+    want = [("text", text, bf16, (rows, cfg.T, cfg.D_text)), ("temb_silu", temb_silu, bf16, (n, rows, cfg.D_temb)), ("head_shift", head_shift, bf16, (n, D)),
+            ("head_onep", head_onep, bf16, (n, D)), ("coef", coef, torch.float32, (n, 8))]
+    for name, t, dt, shape in want:
+        if t is None or not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"cog_sample_ms: {name} must be a contiguous {dt} {shape} GPU tensor, got {None if t is None else tuple(t.shape)}")
+    k = 0
+    if noise is not None:
+        if not noise.is_cuda or noise.dtype != torch.float32 or noise.dim() != 4 or tuple(noise.shape[1:]) != (geo.B, S, Kc) or not noise.is_contiguous() \
+                or not 1 <= noise.shape[0] <= n:
+            raise ValueError(f"cog_sample_ms: noise must be a contiguous fp32 [1 .. {n}, {geo.B}, {S}, {Kc}] GPU tensor, got {tuple(noise.shape)}")
+        k = noise.shape[0]
+    need = cog_sample_ms_workspace_bytes(cfg, solver)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
+    ms = cog_sample_ms_config(cfg, solver)
+    check(_lib.load().ftmi_cog_sample_ms(ctypes.byref(ms), ctypes.byref(weights), ptr(cols), ptr(x), ptr(text), ptr(temb_silu), ptr(head_shift), ptr(head_onep),
+                                         ptr(coef), ptr(noise), k, ptr(workspace), workspace.numel(), stream_ptr()), "ftmi_cog_sample_ms")
+
+
 # ---- HunyuanVideo latent sampling (include/ftmi355.h: ftmi_hy_sample_*; csrc/sample_layout.hip, csrc/hy_sample_dit.hip) --------------------------------------
 def hy_sample_geometry(B: int, C: int, frames: int, height: int, width: int, patch: int = 2, patch_t: int = 1, true_cfg: bool = False) -> "_lib.HySampleGeometry":
     """The layout of a sampling run: latents [B, C, frames, height, width], x [B, S, Kc], cols [P B S, Kc], pred [P B, S, Kc]; P = 2 with true CFG."""

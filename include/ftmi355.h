@@ -1104,6 +1104,34 @@ size_t ftmi_cog_sample_workspace_bytes(const ftmi_cog_sample_config* cfg);
 int ftmi_cog_sample(const ftmi_cog_sample_config* cfg, const ftmi_cog_sample_weights* w, void* cols, float* x, const void* text, const void* temb_silu,
                     const void* head_shift, const void* head_onep, const float* coef, void* workspace, size_t workspace_bytes, ftmi_stream stream);
 
+/* The multistep form of the loop: the scheduler of the CogVideoX-5b and CogVideoX1.5-5B checkpoints, [upstream, unpinned] CogVideoXDPMScheduler (v-prediction,
+ * trailing spacing), a second-order multistep SDE solver: it keeps the previous step's x0 prediction and adds fresh Gaussian noise at every step but the last.
+ * The scheduler is folded on the host into eight numbers per step (finetrainers_amd/cogvideox/sampler.py cog_dpm_tables):
+ * coef_row = (sa, sb, m0, e0, e1, mn, g, 0), g the step's guidance scale (use_dynamic_cfg changes it per step).
+ * One step, per element in fp32, the row read on the device: v as in ftmi_cog_sample_step with g = coef_row[6] (geo.P == 1: v = c);
+ * x0 = fma(-sb, v, sa x); x' = m0 x; x' = fma(e0, x0, x'); e1 != 0: x' = fma(e1, old, x'); mn != 0: x' = fma(mn, z, x').  x <- x', old <- x0, bf16(x') into
+ * every row group of cols (NULL: no copies).  A term whose coefficient is 0 is left out and its buffer is not read: old may hold anything at step 0, noise may
+ * be NULL when mn == 0 (a NULL noise is read as mn == 0).  old fp32 [B, S, Kc] like x; noise fp32 [B, S, Kc], the step's slice in the state's layout
+ * (ftmi_cog_sample_pack); x, old and noise are three buffers.  Validation, alignment rules and status codes of ftmi_cog_sample_step; pred is required. */
+int ftmi_cog_sample_step_dpm(const ftmi_cog_sample_geometry* geo, const void* pred, float* x, float* old, const float* noise, const float* coef_row, void* cols,
+                             ftmi_stream stream);
+/* latents fp32 [n, B, F, C, H, W] -> out fp32 [n, B, S, Kc]: the permutation of ftmi_cog_sample_init over n tensors at once, values exact, no cols. */
+int ftmi_cog_sample_pack(const ftmi_cog_sample_geometry* geo, const float* latents, int n, float* out, ftmi_stream stream);
+/* ftmi_cog_sample's loop with ftmi_cog_sample_step_dpm as the step's last launch; bit-identical to the same launches issued call by call.  coef: device fp32
+ * [steps, 8]; noise: device fp32 [noise_steps, B, S, Kc], the slices of the leading noise_steps steps (0 .. steps; the caller passes steps - 1 when the last row
+ * has mn == 0, 0 and NULL when no row has noise); a step past them runs without noise.  noise != NULL exactly when noise_steps > 0, else FTMI_ERR_INVALID.
+ * base.guidance only decides P (!= 1 exactly when geo.P == 2): the scale of a step is its row's.  The history lives in the workspace:
+ * ftmi_cog_sample_ms_workspace_bytes = ftmi_cog_sample_workspace_bytes(base) plus ONE [B, S, Kc] fp32 buffer (0 for a refused configuration).
+ * solver: 1 = DPM; any other value is FTMI_ERR_UNSUPPORTED. */
+typedef struct ftmi_cog_sample_ms_config {
+    ftmi_cog_sample_config base;
+    int solver;
+} ftmi_cog_sample_ms_config;
+size_t ftmi_cog_sample_ms_workspace_bytes(const ftmi_cog_sample_ms_config* cfg);
+int ftmi_cog_sample_ms(const ftmi_cog_sample_ms_config* cfg, const ftmi_cog_sample_weights* w, void* cols, float* x, const void* text, const void* temb_silu,
+                       const void* head_shift, const void* head_onep, const float* coef, const float* noise, int noise_steps, void* workspace,
+                       size_t workspace_bytes, ftmi_stream stream);
+
 /* ---- HunyuanVideo latent sampling (csrc/sample_layout.hip: the layout kernels; csrc/hy_sample_dit.hip: the loop) ----
  * The denoising loop of the reference's validation (finetrainers/models/hunyuan_video/base_specification.py:332-355 runs HunyuanVideoPipeline over the
  * transformer that is being trained) in latent space, text-to-video: [upstream, unpinned] HunyuanVideoPipeline + FlowMatchEulerDiscreteScheduler (static

@@ -660,8 +660,10 @@ def _random_cogvideox(cfg, rank: int, dev):
 
 def build_cog_sample(args, par, dev) -> Dict[str, Any]:
     from finetrainers_amd import ops
-    from finetrainers_amd.cogvideox import CogVideoXTransformerConfig, MI355XCogVideoXLatentSampler, cog_ddim_tables
+    from finetrainers_amd.cogvideox import (COG_DPM_SCHEDULER_CONFIG, CogVideoXTransformerConfig, MI355XCogVideoXLatentSampler, cog_ddim_tables,
+                                            cog_dpm_tables)
 
+    dpm = getattr(args, "scheduler", "euler") == "dpm"  # the 5b / 1.5 checkpoints' CogVideoXDPMScheduler: ftmi_cog_sample_ms
     layers = args.layers if args.layers > 0 else 30
     cfg = CogVideoXTransformerConfig(num_layers=layers)
     model = _random_cogvideox(cfg, args.rank, dev)
@@ -677,13 +679,26 @@ def build_cog_sample(args, par, dev) -> Dict[str, Any]:
     text = torch.cat([neg, pos]).contiguous()
     temb, shift, onep = sampler.step_tables(ts, 2 * B)
     ccfg, weights, keep = sampler.c_arguments(geo, n, guidance)
-    ws_bytes = ops.cog_sample_workspace_bytes(ccfg)
+    ws_bytes = ops.cog_sample_ms_workspace_bytes(ccfg) if dpm else ops.cog_sample_workspace_bytes(ccfg)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    if dpm:  # the folded rows of the checkpoints' table and the noise of every step but the last, packed once into the state's layout
+        rows = cog_dpm_tables(n, COG_DPM_SCHEDULER_CONFIG, guidance)[1]
+        k = max(i + 1 for i in range(n) if float(rows[i, 5]) != 0.0)
+        rows = rows.to(dev)
+        packed = ops.cog_sample_pack(geo, torch.randn((k, B, F_, C, H, W), generator=g, device=dev))
+        old = torch.empty((B, S, Kc), dtype=torch.float32, device=dev)
 
-    def one_call():
+    def ddim_call():
         x, cols = ops.cog_sample_init(geo, noise)
         ops.cog_sample(ccfg, weights, cols, x, text, temb, shift, onep, coef, workspace=ws)
         return None
+
+    def dpm_call():
+        x, cols = ops.cog_sample_init(geo, noise)
+        ops.cog_sample_ms(ccfg, weights, cols, x, text, temb, shift, onep, rows, packed, workspace=ws)
+        return None
+
+    one_call = dpm_call if dpm else ddim_call
 
     @torch.no_grad()
     def composed():
@@ -692,7 +707,10 @@ def build_cog_sample(args, par, dev) -> Dict[str, Any]:
             t = torch.full((2 * B,), int(ts[i]), dtype=torch.int64, device=dev)
             hidden = ops.cog_unpatchify(cols.view(2 * B, S, Kc), F_, C, H, W, 2)
             out = model(hidden, text, t)[0]
-            ops.cog_sample_step(geo, ops.cog_patchify(out, 2), x, coef, i, guidance, cols)
+            if dpm:
+                ops.cog_sample_step_dpm(geo, ops.cog_patchify(out, 2), x, old, packed[i] if i < k else None, rows[i], cols)
+            else:
+                ops.cog_sample_step(geo, ops.cog_patchify(out, 2), x, coef, i, guidance, cols)
 
     def once(fn):
         torch.cuda.synchronize()
@@ -705,25 +723,33 @@ def build_cog_sample(args, par, dev) -> Dict[str, Any]:
         peak_one = torch.cuda.max_memory_allocated() / 1e9
         torch.cuda.reset_peak_memory_stats()
         composed()  # warm (allocates the training workspace)
-        a_ms, b_ms = [], []
-        for _ in range(3):  # interleaved: both paths see the same clocks and the same neighbours
+        a_ms, b_ms, d_ms = [], [], []
+        for _ in range(3):  # interleaved: the paths see the same clocks and the same neighbours
             a_ms.append(once(one_call))
             b_ms.append(once(composed))
+            if dpm:  # the DDIM call on the same box, in the same workspace
+                d_ms.append(once(ddim_call))
         peak_comp = torch.cuda.max_memory_allocated() / 1e9
         x, cols = ops.cog_sample_init(geo, noise)
         pred = torch.randn((2 * B, S, Kc), generator=g, device=dev).to(bf16)
         reps = 50
+        if dpm:  # a full row (step 2: history and noise): per element of x read u 2 + c 2 + x 4 + old 4 + z 4, write x 4 + old 4 + 2 x 2
+            step, per = (lambda: ops.cog_sample_step_dpm(geo, pred, x, old, packed[2], rows[2], cols)), 28
+        else:  # per element of x: read u 2 + c 2 + x 4, write x 4 + 2 x 2
+            step, per = (lambda: ops.cog_sample_step(geo, pred, x, coef, 1, guidance, cols)), 16
         for _ in range(5):
-            ops.cog_sample_step(geo, pred, x, coef, 1, guidance, cols)
+            step()
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
         for _ in range(reps):
-            ops.cog_sample_step(geo, pred, x, coef, 1, guidance, cols)
+            step()
         b.record()
         torch.cuda.synchronize()
         us = a.elapsed_time(b) * 1e3 / reps
-        nbytes = B * S * Kc * 16  # per element of x: read u 2 + c 2 + x 4, write x 4 + 2 x 2
-        return {"ms_per_denoising_step_one_call": sorted(a_ms)[1] / n, "ms_per_denoising_step_python_composition": sorted(b_ms)[1] / n,
+        nbytes = B * S * Kc * per
+        extra = {"scheduler": "dpm", "ms_per_denoising_step_ddim_one_call": sorted(d_ms)[1] / n, "interleaved_ms_ddim_one_call": d_ms,
+                 "step_noise_gb": packed.numel() * 4 / 1e9, "step_kernel_bytes_per_element": per} if dpm else {}
+        return {**extra, "ms_per_denoising_step_one_call": sorted(a_ms)[1] / n, "ms_per_denoising_step_python_composition": sorted(b_ms)[1] / n,
                 "ms_per_denoising_step_one_call_first_pass": one_call_ms / n, "interleaved_ms_one_call": a_ms, "interleaved_ms_python_composition": b_ms,
                 "peak_memory_gb_one_call": peak_one, "peak_memory_gb_python_composition": peak_comp, "workspace_gb": ws_bytes / 1e9,
                 "training_workspace_gb": int(_cog_training_workspace(model, 2 * B, T + S)) / 1e9,
@@ -736,10 +762,11 @@ def build_cog_sample(args, par, dev) -> Dict[str, Any]:
         "report": report,
         "samples_per_step": 1.0 / n,
         "step_tflop": n * flop / 1e12,
-        "metric": f"ftmi_cog_sample: one call of {n} denoising steps, CogVideoX-2b 49x480x720, guidance 6 (value: denoising steps per ms are in the report)",
+        "metric": f"{'ftmi_cog_sample_ms (DPM)' if dpm else 'ftmi_cog_sample'}: one call of {n} denoising steps, CogVideoX-2b 49x480x720, guidance 6 (value: "
+                  "denoising steps per ms are in the report)",
         "data": "random noise [1,13,16,60,90] + random text embeds [1,226,4096] (conditional and unconditional), random-init weights of the CogVideoX-2b DiT",
         "config": {"workload": f"CogVideoX-2b latent sampling, rank={args.rank} adapters, {S} video + {T} text tokens, 2 model rows (unconditional + conditional), {layers} blocks"
-                               + ("" if layers == 30 else " -- REDUCED depth"), "seq_len": N, "denoising_steps_per_call": n},
+                               + ("" if layers == 30 else " -- REDUCED depth"), "seq_len": N, "denoising_steps_per_call": n, "scheduler": "dpm" if dpm else "ddim"},
         "layers": layers,
     }
 
@@ -951,8 +978,9 @@ def main() -> None:
     ap.add_argument("--ffn-adapters", dest="ffn_adapters", action="store_true", help="wan_lora / ltx_lora: adapters on the two feed-forward projections as well (ten per block)")
     ap.add_argument("--text-adapters", dest="text_adapters", action="store_true",
                     help="hunyuan / hy_sample: the shipped recipe's target_modules -- adapters on add_q_proj / add_k_proj / add_v_proj / to_add_out of the dual-stream blocks too")
-    ap.add_argument("--scheduler", choices=("euler", "unipc"), default="euler",
-                    help="wan_sample: flow-match Euler at shift 1 (ftmi_wan_sample) or the checkpoint's UniPC multistep scheduler at flow_shift 3 (ftmi_wan_sample_ms)")
+    ap.add_argument("--scheduler", choices=("euler", "unipc", "dpm"), default="euler",
+                    help="wan_sample: flow-match Euler at shift 1 (ftmi_wan_sample) or the checkpoint's UniPC multistep scheduler at flow_shift 3 (ftmi_wan_sample_ms); "
+                         "cog_sample: dpm = the 5b / 1.5 checkpoints' CogVideoXDPMScheduler (ftmi_cog_sample_ms) instead of DDIM (the default)")
     ap.add_argument("--last-frame", dest="last_frame", action="store_true",
                     help="wan_i2v_lora: the first/last-frame model (pos_embed_seq_len = 514: two images, 514 image keys in attn2) at the same geometry")
     args = ap.parse_args()
