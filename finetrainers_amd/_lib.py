@@ -68,7 +68,8 @@ LTX_FF_WEIGHT_FIELDS = ["ff_a1_sp", "ff_a1t_ext", "ff_b1_ext", "ff_b1t_sp", "ff_
 
 
 class LtxFfWeights(Structure):
-    """include/ftmi355.h: ftmi_ltx_ff_weights -- the base structure first, then the feed-forward adapters' operand copies (all NULL: none)."""
+    """include/ftmi355.h: ftmi_ltx_ff_weights, what every LTX entry that runs blocks takes -- the base structure first, then the feed-forward adapters' operand
+    copies (all NULL: none)."""
 
     _fields_ = [("base", LtxWeights)] + [(n, c_void_p) for n in LTX_FF_WEIGHT_FIELDS]
 
@@ -337,27 +338,10 @@ _SIGS = {
                                         c_void_p, c_int, c_void_p]),
     "ftmi_qknorm_rope_bwd_ex": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_int, c_float, c_int,
                                         c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "ftmi_ltx_workspace_bytes": (c_size_t, [POINTER(LtxConfig)]),
-    "ftmi_ltx_workspace_offset": (c_int, [POINTER(LtxConfig), c_char_p, c_int, POINTER(c_size_t)]),
-    "ftmi_ltx_forward": (c_int, [POINTER(LtxConfig), POINTER(LtxWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                 c_size_t, c_void_p]),
-    "ftmi_ltx_forward_frames_workspace_bytes": (c_size_t, [POINTER(LtxConfig), c_int]),
-    "ftmi_ltx_forward_frames": (c_int, [POINTER(LtxConfig), POINTER(LtxWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                                        c_size_t, c_void_p]),
-    "ftmi_ltx_backward": (c_int, [POINTER(LtxConfig), POINTER(LtxWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                  c_size_t, c_void_p]),
-    "ftmi_ltx_backward_range": (c_int, [POINTER(LtxConfig), POINTER(LtxWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                        c_size_t, c_int, c_int, c_int, c_void_p]),
     "ftmi_ltx_noise_pack": (c_int, [c_void_p] * 6 + [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "ftmi_ltx_cfg_euler_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_long, c_void_p]),
     "ftmi_ltx_unpack_denorm": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "ftmi_ltx_sample_workspace_bytes": (c_size_t, [POINTER(LtxConfig), c_int]),
-    "ftmi_ltx_sample": (c_int, [POINTER(LtxConfig), POINTER(LtxWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float,
-                                c_void_p, c_size_t, c_void_p]),
     "ftmi_ltx_cfg_euler_step_held": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_long, c_long, c_void_p]),
-    "ftmi_ltx_sample_cond_workspace_bytes": (c_size_t, [POINTER(LtxConfig), c_int, c_int]),
-    "ftmi_ltx_sample_cond": (c_int, [POINTER(LtxConfig), POINTER(LtxWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float,
-                                     c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "ftmi_ltx_ff_workspace_bytes": (c_size_t, [POINTER(LtxConfig), POINTER(LtxFfWeights)]),
     "ftmi_ltx_ff_workspace_offset": (c_int, [POINTER(LtxConfig), POINTER(LtxFfWeights), c_char_p, c_int, POINTER(c_size_t)]),
     "ftmi_ltx_ff_forward": (c_int, [POINTER(LtxConfig), POINTER(LtxFfWeights), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -446,8 +430,6 @@ _SIGS = {
     "ftmi_hy_sample_init": (c_int, [POINTER(HySampleGeometry), c_void_p, c_void_p, c_void_p, c_void_p]),
     "ftmi_hy_sample_step": (c_int, [POINTER(HySampleGeometry), c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p]),
     "ftmi_hy_sample_finish": (c_int, [POINTER(HySampleGeometry), c_void_p, c_float, c_void_p, c_void_p]),
-    "ftmi_hy_sample_workspace_bytes": (c_size_t, [POINTER(HySampleConfig)]),
-    "ftmi_hy_sample": (c_int, [POINTER(HySampleConfig), POINTER(HySampleWeights)] + [c_void_p] * 11 + [c_size_t, c_void_p]),
     "ftmi_hy_sample_text_workspace_bytes": (c_size_t, [POINTER(HySampleTextConfig)]),
     "ftmi_hy_sample_text": (c_int, [POINTER(HySampleTextConfig), POINTER(HySampleWeights)] + [c_void_p] * 11 + [c_size_t, c_void_p]),
     "ftmi_hy_dual_saved_bytes": (c_size_t, [POINTER(HyDualConfig)]),

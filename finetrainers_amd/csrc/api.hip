@@ -102,22 +102,21 @@ void prof_end(int k, hipStream_t st) {
     g_prof_recs.push_back(ProfRec{g_prof_open[k], g_prof_open_b[k], k, g_prof_open_flops[k]});
 }
 
-// (ff: the feed-forward adapters of the _ff entries, null = none)
-size_t ltx_workspace_bytes(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights* ff);
-int ltx_workspace_offset(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights* ff, const char* name, int layer, size_t* off);
-int ltx_forward(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const ftmi_ltx_ff_weights* ff, const bf16_t* x_t, const bf16_t* text, const float* key_bias,
-                const float* sigma, bf16_t* pred, void* ws, size_t ws_bytes, hipStream_t st);
-int ltx_backward_range(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const ftmi_ltx_ff_weights* ff, const bf16_t* text, const float* key_bias, const bf16_t* dpred,
-                       float* grad_a, float* grad_b, float* grad_ff, void* ws, size_t ws_bytes, int l_hi, int l_lo, int accumulate, hipStream_t st);
-size_t ltx_forward_frames_workspace_bytes(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights* ff, int frames);
-int ltx_forward_frames(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const ftmi_ltx_ff_weights* ff, const bf16_t* x_t, const bf16_t* text, const float* key_bias,
+size_t ltx_workspace_bytes(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights& w);
+int ltx_workspace_offset(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights& w, const char* name, int layer, size_t* off);
+int ltx_forward(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights& w, const bf16_t* x_t, const bf16_t* text, const float* key_bias, const float* sigma,
+                bf16_t* pred, void* ws, size_t ws_bytes, hipStream_t st);
+int ltx_backward_range(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights& w, const bf16_t* text, const float* key_bias, const bf16_t* dpred, float* grad_a,
+                       float* grad_b, float* grad_ff, void* ws, size_t ws_bytes, int l_hi, int l_lo, int accumulate, hipStream_t st);
+size_t ltx_forward_frames_workspace_bytes(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights& w, int frames);
+int ltx_forward_frames(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights& w, const bf16_t* x_t, const bf16_t* text, const float* key_bias,
                        const float* timesteps, int frames, bf16_t* pred, void* ws, size_t ws_bytes, hipStream_t st);
-size_t ltx_sample_workspace_bytes(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights* ff, int two_pass);
-size_t ltx_sample_cond_workspace_bytes(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights* ff, int two_pass, int frames);
-int ltx_sample_cond(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const ftmi_ltx_ff_weights* ff, const bf16_t* text_cond, const bf16_t* text_uncond, const float* kbias_cond,
+size_t ltx_sample_workspace_bytes(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights& w, int two_pass);
+size_t ltx_sample_cond_workspace_bytes(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights& w, int two_pass, int frames);
+int ltx_sample_cond(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights& w, const bf16_t* text_cond, const bf16_t* text_uncond, const float* kbias_cond,
                     const float* kbias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, int frames,
                     int cond_frames, void* ws, size_t ws_bytes, hipStream_t st);
-int ltx_sample(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const ftmi_ltx_ff_weights* ff, const bf16_t* text_cond, const bf16_t* text_uncond, const float* kbias_cond,
+int ltx_sample(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights& w, const bf16_t* text_cond, const bf16_t* text_uncond, const float* kbias_cond,
                const float* kbias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, void* ws, size_t ws_bytes,
                hipStream_t st);
 
@@ -529,78 +528,40 @@ int ftmi_qknorm_rope_bwd_ex(const void* x, long ldx, const void* w, const float*
                            (hipStream_t)stream, w_rows, (const bf16_t*)x2, (const bf16_t*)w2, (const bf16_t*)dy2, (bf16_t*)dx2, row_grp, row_grp_span);
 }
 
-size_t ftmi_ltx_workspace_bytes(const ftmi_ltx_config* cfg) { return cfg ? ltx_workspace_bytes(*cfg, nullptr) : 0; }
+size_t ftmi_ltx_ff_workspace_bytes(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w) { return cfg && w ? ltx_workspace_bytes(*cfg, *w) : 0; }
 
-int ftmi_ltx_workspace_offset(const ftmi_ltx_config* cfg, const char* name, int layer, size_t* offset) {
-    if (!cfg || !name || !offset) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_workspace_offset: null argument");
-    return ltx_workspace_offset(*cfg, nullptr, name, layer, offset);
-}
-
-// The entries that run blocks and their _ff twins share one body each: ff == null is the entry without feed-forward adapters.
-static int ltx_forward_entry(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const ftmi_ltx_ff_weights* ff, const void* x_t, const void* text, const float* key_bias,
-                             const float* sigma, void* pred, void* ws, size_t ws_bytes, ftmi_stream stream) {
-    if (!cfg || !w || !x_t || !text || !sigma || !pred || !ws) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_forward: null argument");
-    if (cfg->r > 0 && (!w->lora_a_sp || !w->lora_b_ext)) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_forward: LoRA working copies missing");
-    return ltx_forward(*cfg, *w, ff, (const bf16_t*)x_t, (const bf16_t*)text, key_bias, sigma, (bf16_t*)pred, ws, ws_bytes, (hipStream_t)stream);
-}
-int ftmi_ltx_forward(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const void* x_t, const void* text, const float* key_bias,
-                     const float* sigma, void* pred, void* ws, size_t ws_bytes, ftmi_stream stream) {
-    return ltx_forward_entry(cfg, w, nullptr, x_t, text, key_bias, sigma, pred, ws, ws_bytes, stream);
-}
-int ftmi_ltx_ff_forward(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, const void* x_t, const void* text, const float* key_bias,
-                        const float* sigma, void* pred, void* ws, size_t ws_bytes, ftmi_stream stream) {
-    return ltx_forward_entry(cfg, w ? &w->base : nullptr, w, x_t, text, key_bias, sigma, pred, ws, ws_bytes, stream);
-}
-size_t ftmi_ltx_ff_workspace_bytes(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w) { return cfg && w ? ltx_workspace_bytes(*cfg, w) : 0; }
 int ftmi_ltx_ff_workspace_offset(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, const char* name, int layer, size_t* offset) {
     if (!cfg || !w || !name || !offset) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_ff_workspace_offset: null argument");
-    return ltx_workspace_offset(*cfg, w, name, layer, offset);
+    return ltx_workspace_offset(*cfg, *w, name, layer, offset);
 }
 
-size_t ftmi_ltx_forward_frames_workspace_bytes(const ftmi_ltx_config* cfg, int frames) { return cfg ? ltx_forward_frames_workspace_bytes(*cfg, nullptr, frames) : 0; }
+int ftmi_ltx_ff_forward(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, const void* x_t, const void* text, const float* key_bias,
+                        const float* sigma, void* pred, void* ws, size_t ws_bytes, ftmi_stream stream) {
+    if (!cfg || !w || !x_t || !text || !sigma || !pred || !ws) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_ff_forward: null argument");
+    if (cfg->r > 0 && (!w->base.lora_a_sp || !w->base.lora_b_ext)) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_ff_forward: LoRA working copies missing");
+    return ltx_forward(*cfg, *w, (const bf16_t*)x_t, (const bf16_t*)text, key_bias, sigma, (bf16_t*)pred, ws, ws_bytes, (hipStream_t)stream);
+}
+
 size_t ftmi_ltx_ff_forward_frames_workspace_bytes(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, int frames) {
-    return cfg && w ? ltx_forward_frames_workspace_bytes(*cfg, w, frames) : 0;
+    return cfg && w ? ltx_forward_frames_workspace_bytes(*cfg, *w, frames) : 0;
 }
 
-static int ltx_forward_frames_entry(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const ftmi_ltx_ff_weights* ff, const void* x_t, const void* text,
-                                    const float* key_bias, const float* timesteps, int frames, void* pred, void* ws, size_t ws_bytes, ftmi_stream stream) {
-    if (!cfg || !w || !x_t || !text || !timesteps || !pred || !ws) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_forward_frames: null argument");
-    if (cfg->r > 0 && (!w->lora_a_sp || !w->lora_b_ext)) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_forward_frames: LoRA working copies missing");
-    return ltx_forward_frames(*cfg, *w, ff, (const bf16_t*)x_t, (const bf16_t*)text, key_bias, timesteps, frames, (bf16_t*)pred, ws, ws_bytes,
-                              (hipStream_t)stream);
-}
-int ftmi_ltx_forward_frames(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const void* x_t, const void* text, const float* key_bias,
-                            const float* timesteps, int frames, void* pred, void* ws, size_t ws_bytes, ftmi_stream stream) {
-    return ltx_forward_frames_entry(cfg, w, nullptr, x_t, text, key_bias, timesteps, frames, pred, ws, ws_bytes, stream);
-}
 int ftmi_ltx_ff_forward_frames(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, const void* x_t, const void* text, const float* key_bias,
                                const float* timesteps, int frames, void* pred, void* ws, size_t ws_bytes, ftmi_stream stream) {
-    return ltx_forward_frames_entry(cfg, w ? &w->base : nullptr, w, x_t, text, key_bias, timesteps, frames, pred, ws, ws_bytes, stream);
+    if (!cfg || !w || !x_t || !text || !timesteps || !pred || !ws) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_ff_forward_frames: null argument");
+    if (cfg->r > 0 && (!w->base.lora_a_sp || !w->base.lora_b_ext))
+        return set_error(FTMI_ERR_INVALID, "ftmi_ltx_ff_forward_frames: LoRA working copies missing");
+    return ltx_forward_frames(*cfg, *w, (const bf16_t*)x_t, (const bf16_t*)text, key_bias, timesteps, frames, (bf16_t*)pred, ws, ws_bytes, (hipStream_t)stream);
 }
 
-static int ltx_backward_range_entry(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const ftmi_ltx_ff_weights* ff, const void* text, const float* key_bias,
-                                    const void* dpred, float* grad_a, float* grad_b, float* grad_ff, void* ws, size_t ws_bytes, int l_hi, int l_lo, int accumulate,
-                                    ftmi_stream stream) {
-    if (!cfg || !w || !dpred || !ws) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_backward: null argument");
-    if (cfg->r > 0 && (!grad_a || !grad_b || !w->lora_at_ext || !w->lora_bt_sp || !w->lora_at_qkv_ext))
-        return set_error(FTMI_ERR_INVALID, "ftmi_ltx_backward: LoRA gradient buffers / working copies missing");
-    return ltx_backward_range(*cfg, *w, ff, (const bf16_t*)text, key_bias, (const bf16_t*)dpred, grad_a, grad_b, grad_ff, ws, ws_bytes, l_hi, l_lo, accumulate,
-                              (hipStream_t)stream);
-}
-int ftmi_ltx_backward_range(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const void* text, const float* key_bias, const void* dpred,
-                            float* grad_a, float* grad_b, void* ws, size_t ws_bytes, int l_hi, int l_lo, int accumulate, ftmi_stream stream) {
-    return ltx_backward_range_entry(cfg, w, nullptr, text, key_bias, dpred, grad_a, grad_b, nullptr, ws, ws_bytes, l_hi, l_lo, accumulate, stream);
-}
 int ftmi_ltx_ff_backward_range(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, const void* text, const float* key_bias, const void* dpred,
                                float* grad_a, float* grad_b, float* grad_ff, void* ws, size_t ws_bytes, int l_hi, int l_lo, int accumulate,
                                ftmi_stream stream) {
-    return ltx_backward_range_entry(cfg, w ? &w->base : nullptr, w, text, key_bias, dpred, grad_a, grad_b, grad_ff, ws, ws_bytes, l_hi, l_lo, accumulate, stream);
-}
-
-int ftmi_ltx_backward(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const void* text, const float* key_bias, const void* dpred,
-                      float* grad_a, float* grad_b, void* ws, size_t ws_bytes, ftmi_stream stream) {
-    if (!cfg) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_backward: null argument");
-    return ftmi_ltx_backward_range(cfg, w, text, key_bias, dpred, grad_a, grad_b, ws, ws_bytes, cfg->L, 0, /*accumulate=*/1, stream);
+    if (!cfg || !w || !dpred || !ws) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_ff_backward_range: null argument");
+    if (cfg->r > 0 && (!grad_a || !grad_b || !w->base.lora_at_ext || !w->base.lora_bt_sp || !w->base.lora_at_qkv_ext))
+        return set_error(FTMI_ERR_INVALID, "ftmi_ltx_ff_backward_range: LoRA gradient buffers / working copies missing");
+    return ltx_backward_range(*cfg, *w, (const bf16_t*)text, key_bias, (const bf16_t*)dpred, grad_a, grad_b, grad_ff, ws, ws_bytes, l_hi, l_lo, accumulate,
+                              (hipStream_t)stream);
 }
 
 int ftmi_ltx_cfg_euler_step(const void* pred, float* x, const float* sigma, const float* sigma_next, float guidance, void* x_next_bf16, int B,
@@ -620,63 +581,37 @@ int ftmi_ltx_unpack_denorm(const float* x, const float* mean, const float* std_,
     return unpack_denorm(x, mean, std_, (bf16_t*)latents, B, C, S, (hipStream_t)stream);
 }
 
-size_t ftmi_ltx_sample_workspace_bytes(const ftmi_ltx_config* cfg, int two_pass) { return cfg ? ltx_sample_workspace_bytes(*cfg, nullptr, two_pass) : 0; }
 size_t ftmi_ltx_ff_sample_workspace_bytes(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, int two_pass) {
-    return cfg && w ? ltx_sample_workspace_bytes(*cfg, w, two_pass) : 0;
+    return cfg && w ? ltx_sample_workspace_bytes(*cfg, *w, two_pass) : 0;
 }
 
-static int ltx_sample_entry(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const ftmi_ltx_ff_weights* ff, const void* text_cond, const void* text_uncond,
-                            const float* key_bias_cond, const float* key_bias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps,
-                            float guidance, void* ws, size_t ws_bytes, ftmi_stream stream) {
-    if (!cfg || !w || !text_cond || !x || !sigmas || !timesteps || !ws) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_sample: null argument");
-    if (guidance != 1.0f && !text_uncond) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_sample: guidance != 1 needs the unconditional prompt embeddings");
-    if (guidance != 1.0f && (key_bias_cond == nullptr) != (key_bias_uncond == nullptr))
-        return set_error(FTMI_ERR_INVALID, "ftmi_ltx_sample: give the key bias of both prompts or of neither");
-    if (cfg->r > 0 && (!w->lora_a_sp || !w->lora_b_ext)) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_sample: LoRA working copies missing");
-    return ltx_sample(*cfg, *w, ff, (const bf16_t*)text_cond, (const bf16_t*)text_uncond, key_bias_cond, key_bias_uncond, x, sigmas, timesteps, n_steps,
-                      guidance, ws, ws_bytes, (hipStream_t)stream);
-}
-int ftmi_ltx_sample(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const void* text_cond, const void* text_uncond, const float* key_bias_cond,
-                    const float* key_bias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, void* ws,
-                    size_t ws_bytes, ftmi_stream stream) {
-    return ltx_sample_entry(cfg, w, nullptr, text_cond, text_uncond, key_bias_cond, key_bias_uncond, x, sigmas, timesteps, n_steps, guidance, ws, ws_bytes, stream);
-}
 int ftmi_ltx_ff_sample(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, const void* text_cond, const void* text_uncond, const float* key_bias_cond,
                        const float* key_bias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, void* ws,
                        size_t ws_bytes, ftmi_stream stream) {
-    return ltx_sample_entry(cfg, w ? &w->base : nullptr, w, text_cond, text_uncond, key_bias_cond, key_bias_uncond, x, sigmas, timesteps, n_steps, guidance, ws, ws_bytes,
-                            stream);
-}
-
-size_t ftmi_ltx_sample_cond_workspace_bytes(const ftmi_ltx_config* cfg, int two_pass, int frames) {
-    return cfg ? ltx_sample_cond_workspace_bytes(*cfg, nullptr, two_pass, frames) : 0;
-}
-size_t ftmi_ltx_ff_sample_cond_workspace_bytes(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, int two_pass, int frames) {
-    return cfg && w ? ltx_sample_cond_workspace_bytes(*cfg, w, two_pass, frames) : 0;
-}
-
-static int ltx_sample_cond_entry(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const ftmi_ltx_ff_weights* ff, const void* text_cond, const void* text_uncond,
-                                 const float* key_bias_cond, const float* key_bias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps,
-                                 float guidance, int frames, int cond_frames, void* ws, size_t ws_bytes, ftmi_stream stream) {
-    if (!cfg || !w || !text_cond || !x || !sigmas || !timesteps || !ws) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_sample_cond: null argument");
-    if (guidance != 1.0f && !text_uncond) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_sample_cond: guidance != 1 needs the unconditional prompt embeddings");
+    if (!cfg || !w || !text_cond || !x || !sigmas || !timesteps || !ws) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_ff_sample: null argument");
+    if (guidance != 1.0f && !text_uncond) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_ff_sample: guidance != 1 needs the unconditional prompt embeddings");
     if (guidance != 1.0f && (key_bias_cond == nullptr) != (key_bias_uncond == nullptr))
-        return set_error(FTMI_ERR_INVALID, "ftmi_ltx_sample_cond: give the key bias of both prompts or of neither");
-    if (cfg->r > 0 && (!w->lora_a_sp || !w->lora_b_ext)) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_sample_cond: LoRA working copies missing");
-    return ltx_sample_cond(*cfg, *w, ff, (const bf16_t*)text_cond, (const bf16_t*)text_uncond, key_bias_cond, key_bias_uncond, x, sigmas, timesteps, n_steps,
-                           guidance, frames, cond_frames, ws, ws_bytes, (hipStream_t)stream);
+        return set_error(FTMI_ERR_INVALID, "ftmi_ltx_ff_sample: give the key bias of both prompts or of neither");
+    if (cfg->r > 0 && (!w->base.lora_a_sp || !w->base.lora_b_ext)) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_ff_sample: LoRA working copies missing");
+    return ltx_sample(*cfg, *w, (const bf16_t*)text_cond, (const bf16_t*)text_uncond, key_bias_cond, key_bias_uncond, x, sigmas, timesteps, n_steps, guidance, ws,
+                      ws_bytes, (hipStream_t)stream);
 }
-int ftmi_ltx_sample_cond(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const void* text_cond, const void* text_uncond, const float* key_bias_cond,
-                         const float* key_bias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, int frames,
-                         int cond_frames, void* ws, size_t ws_bytes, ftmi_stream stream) {
-    return ltx_sample_cond_entry(cfg, w, nullptr, text_cond, text_uncond, key_bias_cond, key_bias_uncond, x, sigmas, timesteps, n_steps, guidance, frames, cond_frames,
-                                 ws, ws_bytes, stream);
+
+size_t ftmi_ltx_ff_sample_cond_workspace_bytes(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, int two_pass, int frames) {
+    return cfg && w ? ltx_sample_cond_workspace_bytes(*cfg, *w, two_pass, frames) : 0;
 }
+
 int ftmi_ltx_ff_sample_cond(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, const void* text_cond, const void* text_uncond,
                             const float* key_bias_cond, const float* key_bias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps,
                             float guidance, int frames, int cond_frames, void* ws, size_t ws_bytes, ftmi_stream stream) {
-    return ltx_sample_cond_entry(cfg, w ? &w->base : nullptr, w, text_cond, text_uncond, key_bias_cond, key_bias_uncond, x, sigmas, timesteps, n_steps, guidance, frames,
-                                 cond_frames, ws, ws_bytes, stream);
+    if (!cfg || !w || !text_cond || !x || !sigmas || !timesteps || !ws) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_ff_sample_cond: null argument");
+    if (guidance != 1.0f && !text_uncond)
+        return set_error(FTMI_ERR_INVALID, "ftmi_ltx_ff_sample_cond: guidance != 1 needs the unconditional prompt embeddings");
+    if (guidance != 1.0f && (key_bias_cond == nullptr) != (key_bias_uncond == nullptr))
+        return set_error(FTMI_ERR_INVALID, "ftmi_ltx_ff_sample_cond: give the key bias of both prompts or of neither");
+    if (cfg->r > 0 && (!w->base.lora_a_sp || !w->base.lora_b_ext)) return set_error(FTMI_ERR_INVALID, "ftmi_ltx_ff_sample_cond: LoRA working copies missing");
+    return ltx_sample_cond(*cfg, *w, (const bf16_t*)text_cond, (const bf16_t*)text_uncond, key_bias_cond, key_bias_uncond, x, sigmas, timesteps, n_steps, guidance,
+                           frames, cond_frames, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int ftmi_ltx_noise_pack(const void* latents, const void* noise, const float* mean, const float* std_, const float* sigma,
@@ -1173,17 +1108,7 @@ int ftmi_hy_sample_finish(const ftmi_hy_sample_geometry* geo, const float* x, fl
     return hy_sample_finish(*geo, x, k, (bf16_t*)latents, (hipStream_t)stream);
 }
 
-size_t ftmi_hy_sample_workspace_bytes(const ftmi_hy_sample_config* cfg) { return cfg ? hy_sample_workspace_bytes(*cfg, 0) : 0; }
 size_t ftmi_hy_sample_text_workspace_bytes(const ftmi_hy_sample_text_config* cfg) { return cfg ? hy_sample_workspace_bytes(cfg->base, cfg->text_adapters) : 0; }
-
-int ftmi_hy_sample(const ftmi_hy_sample_config* cfg, const ftmi_hy_sample_weights* w, void* cols, float* x, const void* temb_silu, const void* enc,
-                   const void* head_shift, const void* head_onep, const float* key_bias, const float* rope_cos, const float* rope_sin, const float* sigmas,
-                   void* workspace, size_t workspace_bytes, ftmi_stream stream) {
-    if (!cfg || !w || !cols || !x || !temb_silu || !enc || !head_shift || !head_onep || !rope_cos || !rope_sin || !sigmas || !workspace)
-        return set_error(FTMI_ERR_INVALID, "ftmi_hy_sample: null argument");
-    return hy_sample(*cfg, 0, *w, (bf16_t*)cols, x, (const bf16_t*)temb_silu, (const bf16_t*)enc, (const bf16_t*)head_shift, (const bf16_t*)head_onep, key_bias,
-                     rope_cos, rope_sin, sigmas, workspace, workspace_bytes, (hipStream_t)stream);
-}
 
 int ftmi_hy_sample_text(const ftmi_hy_sample_text_config* cfg, const ftmi_hy_sample_weights* w, void* cols, float* x, const void* temb_silu, const void* enc,
                         const void* head_shift, const void* head_onep, const float* key_bias, const float* rope_cos, const float* rope_sin, const float* sigmas,

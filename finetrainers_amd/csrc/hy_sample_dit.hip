@@ -1,4 +1,4 @@
-// HunyuanVideo latent sampling: the whole denoising loop of a validation run as ONE call (include/ftmi355.h: ftmi_hy_sample; the layout and step kernels
+// HunyuanVideo latent sampling: the whole denoising loop of a validation run as ONE call (include/ftmi355.h: ftmi_hy_sample_text; the layout and step kernels
 // are in sample_layout.hip, the two block orchestrators in hy_dit.hip).
 // Restates what the reference gets from HunyuanVideoPipeline over the transformer it trains (finetrainers/models/hunyuan_video/base_specification.py:332-355),
 // in latent space, text-to-video.  Per step, on one stream, no host synchronisation -- the launches of MI355XHunyuanVideoTransformer3DModel.forward (under
@@ -86,7 +86,7 @@ int hy_sample(const ftmi_hy_sample_config& c, int text_adapters, const ftmi_hy_s
               size_t ws_bytes, hipStream_t st) {
     HySamplePlan p;
     FTMI_TRY(make_plan(c, text_adapters, p));
-    if (ws_bytes < p.total) return set_error(FTMI_ERR_INVALID, "hy_sample: workspace too small (ftmi_hy_sample_workspace_bytes)");
+    if (ws_bytes < p.total) return set_error(FTMI_ERR_INVALID, "hy_sample: workspace too small (ftmi_hy_sample_text_workspace_bytes)");
     if (reinterpret_cast<uintptr_t>(ws) & 255) return set_error(FTMI_ERR_INVALID, "hy_sample: the workspace must be 256-byte aligned");
     if (!w.patch_w || !w.patch_b || !w.proj_w || !w.proj_b || !w.ones || !w.zeros || (c.Ld > 0 && !w.dual) || (c.Ls > 0 && !w.single))
         return set_error(FTMI_ERR_INVALID, "hy_sample: weights missing");

@@ -465,7 +465,7 @@ int hy_dual_backward(const ftmi_hy_dual_config& c, const ftmi_hy_dual_weights& w
 int hy_sample_init(const ftmi_hy_sample_geometry& g, const float* latents, float* x, bf16_t* cols, hipStream_t st);
 int hy_sample_step(const ftmi_hy_sample_geometry& g, const bf16_t* pred, float* x, const float* sigmas, int step, float true_cfg, bf16_t* cols, hipStream_t st);
 int hy_sample_finish(const ftmi_hy_sample_geometry& g, const float* x, float k, bf16_t* latents, hipStream_t st);
-// text_adapters: ftmi_hy_dual_config's flag for every dual block of the walk (ftmi_hy_sample: 0; ftmi_hy_sample_text: the extension's field)
+// text_adapters: ftmi_hy_dual_config's flag for every dual block of the walk (ftmi_hy_sample_text_config's field)
 size_t hy_sample_workspace_bytes(const ftmi_hy_sample_config& c, int text_adapters);
 int hy_sample(const ftmi_hy_sample_config& c, int text_adapters, const ftmi_hy_sample_weights& w, bf16_t* cols, float* x, const bf16_t* temb_silu, const bf16_t* enc,
               const bf16_t* head_shift, const bf16_t* head_onep, const float* key_bias, const float* rope_cos, const float* rope_sin, const float* sigmas, void* ws,

@@ -8,7 +8,7 @@
 // to_q/to_k/to_v/to_out.0 fused into the projections, and the autograd backward of the same graph with
 // frozen base weights (dgrad only) and trainable LoRA A/B.
 //
-// Feed-forward adapters (the ftmi_ltx_ff_* entries; peft attaches them when --target_modules names ff.net.0.proj and ff.net.2, as the default of
+// Feed-forward adapters (the eight trailing pointers of ftmi_ltx_ff_weights, all NULL = none; peft attaches them when --target_modules names ff.net.0.proj and ff.net.2, as the default of
 // trainer/control_trainer/config.py:60 does): two more adapters per block at the same rank, through the same builders (lora_proj.hip.h) and the block's
 // proj_with / proj_bwd_with.  Their weight-gradient operands n2, g, dz and the gated dO are scratch shared by all blocks, so the backward writes n2 and g again
 // per block (norm_modulate_fwd; gelu_from_pre on the kept z) and launches the four TN products inside the block loop -- see DESIGN.md 7-V.
@@ -137,15 +137,14 @@ int check_cfg(const ftmi_ltx_config& c, int frames = 0) {
     return 0;
 }
 
-// The feed-forward adapters of a call (ftmi_ltx_ff_weights): typed operand copies, `on` = all eight present.  ff == null or all eight null: none.
+// The feed-forward adapters of a call (the extension of ftmi_ltx_ff_weights): typed operand copies, `on` = all eight present.  All eight null: none.
 struct FfOps {
     bool on = false;
     const bf16_t *a1_sp = nullptr, *a1t_ext = nullptr, *b1_ext = nullptr, *b1t_sp = nullptr, *a2_sp = nullptr, *a2t_ext = nullptr, *b2_ext = nullptr, *b2t_sp = nullptr;
 };
-int ff_ops(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights* ff, FfOps* o) {
+int ff_ops(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights& w, FfOps* o) {
     *o = FfOps();
-    if (!ff) return 0;
-    const void* p[8] = {ff->ff_a1_sp, ff->ff_a1t_ext, ff->ff_b1_ext, ff->ff_b1t_sp, ff->ff_a2_sp, ff->ff_a2t_ext, ff->ff_b2_ext, ff->ff_b2t_sp};
+    const void* p[8] = {w.ff_a1_sp, w.ff_a1t_ext, w.ff_b1_ext, w.ff_b1t_sp, w.ff_a2_sp, w.ff_a2t_ext, w.ff_b2_ext, w.ff_b2t_sp};
     int n = 0;
     for (const void* q : p) n += q != nullptr;
     if (n == 0) return 0;
@@ -155,13 +154,6 @@ int ff_ops(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights* ff, FfOps* o) {
     o->a1_sp = P(p[0], 0); o->a1t_ext = P(p[1], 0); o->b1_ext = P(p[2], 0); o->b1t_sp = P(p[3], 0);
     o->a2_sp = P(p[4], 0); o->a2t_ext = P(p[5], 0); o->b2_ext = P(p[6], 0); o->b2t_sp = P(p[7], 0);
     return 0;
-}
-// (for the planners, which return a size: a refused combination plans nothing)
-bool ff_on(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights* ff, bool* ok = nullptr) {
-    FfOps o;
-    const int rc = ff_ops(c, ff, &o);
-    if (ok) *ok = rc == 0;
-    return o.on;
 }
 
 // A projection with its LoRA: the down-projection `dn` (writes a.X2) and the GEMM `a` (K-extension over X2) -- one fused launch where the pair is eligible
@@ -202,15 +194,15 @@ AttnArgs cross_attn_args(const ftmi_ltx_config& c, const WsLayout& L, void* ws, 
 
 }  // namespace
 
-size_t ltx_workspace_bytes(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights* ff) {
-    bool ok;
-    const bool on = ff_on(c, ff, &ok);
-    return ok ? make_layout(c, 0, on).total : 0;
+// (the planners return a size: a combination ff_ops refuses plans nothing)
+size_t ltx_workspace_bytes(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights& w) {
+    FfOps ff;
+    return ff_ops(c, w, &ff) == 0 ? make_layout(c, 0, ff.on).total : 0;
 }
 
-int ltx_workspace_offset(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights* ff, const char* name, int layer, size_t* off) {
+int ltx_workspace_offset(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights& w, const char* name, int layer, size_t* off) {
     FfOps fo;
-    FTMI_TRY(ff_ops(c, ff, &fo));
+    FTMI_TRY(ff_ops(c, w, &fo));
     const WsLayout L = make_layout(c, 0, fo.on);
     const size_t M = (size_t)c.B * c.S;
     struct E { const char* n; size_t o; };
@@ -398,21 +390,21 @@ static int ltx_blocks_tail(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, 
     return 0;
 }
 
-int ltx_forward(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const ftmi_ltx_ff_weights* ffw, const bf16_t* x_t, const bf16_t* text, const float* key_bias,
-                const float* sigma, bf16_t* pred, void* ws, size_t ws_bytes, hipStream_t st) {
+int ltx_forward(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights& w, const bf16_t* x_t, const bf16_t* text, const float* key_bias, const float* sigma,
+                bf16_t* pred, void* ws, size_t ws_bytes, hipStream_t st) {
     FTMI_TRY(check_cfg(c));
     struct ValidWidth {  // (normalisations of a zero-padded narrow model take their mean over d_valid channels; reset when the pass has queued its launches)
         explicit ValidWidth(int dv) { rowwise_set_valid_width(dv); }
         ~ValidWidth() { rowwise_set_valid_width(0); }
     } valid_width_guard(c.d_valid);
     FfOps ff;
-    FTMI_TRY(ff_ops(c, ffw, &ff));
+    FTMI_TRY(ff_ops(c, w, &ff));
     const WsLayout L = make_layout(c, 0, ff.on);
     if (ws_bytes < L.total) return set_error(FTMI_ERR_INVALID, "ltx_forward: workspace too small");
-    FTMI_TRY(ltx_prologue_time(c, w, L, ws, sigma, c.B, st));
-    FTMI_TRY(ltx_proj_in(c, w, L, ws, x_t, st));
-    FTMI_TRY(ltx_prologue_text(c, w, L, ws, text, st));
-    return ltx_blocks_tail(c, w, ff, L, ws, key_bias, pred, st, ModGroups{c.B, c.S});
+    FTMI_TRY(ltx_prologue_time(c, w.base, L, ws, sigma, c.B, st));
+    FTMI_TRY(ltx_proj_in(c, w.base, L, ws, x_t, st));
+    FTMI_TRY(ltx_prologue_text(c, w.base, L, ws, text, st));
+    return ltx_blocks_tail(c, w.base, ff, L, ws, key_bias, pred, st, ModGroups{c.B, c.S});
 }
 
 // ---- forward with one timestep per latent frame (forward only) -----------------------------------------------------------------------------------
@@ -425,12 +417,11 @@ static ftmi_ltx_config frames_cfg(const ftmi_ltx_config& c) {
     fc.checkpoint = 1;
     return fc;
 }
-size_t ltx_forward_frames_workspace_bytes(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights* ffw, int frames) {
-    bool ok;
-    const bool on = ff_on(c, ffw, &ok);
-    return frames > 0 && ok ? make_layout(frames_cfg(c), c.B * frames, on).total : 0;
+size_t ltx_forward_frames_workspace_bytes(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights& w, int frames) {
+    FfOps ff;
+    return ff_ops(c, w, &ff) == 0 && frames > 0 ? make_layout(frames_cfg(c), c.B * frames, ff.on).total : 0;
 }
-int ltx_forward_frames(const ftmi_ltx_config& c0, const ftmi_ltx_weights& w, const ftmi_ltx_ff_weights* ffw, const bf16_t* x_t, const bf16_t* text, const float* key_bias,
+int ltx_forward_frames(const ftmi_ltx_config& c0, const ftmi_ltx_ff_weights& w, const bf16_t* x_t, const bf16_t* text, const float* key_bias,
                        const float* timesteps, int frames, bf16_t* pred, void* ws, size_t ws_bytes, hipStream_t st) {
     if (frames <= 0) return set_error(FTMI_ERR_INVALID, "ltx_forward_frames: frames must be positive");
     if (c0.d_valid || c0.head_dim_valid) return set_error(FTMI_ERR_UNSUPPORTED, "ltx_forward_frames: narrow (zero-padded) geometries are not supported");
@@ -438,13 +429,13 @@ int ltx_forward_frames(const ftmi_ltx_config& c0, const ftmi_ltx_weights& w, con
     FTMI_TRY(check_cfg(c, frames));
     const int G = c.B * frames;
     FfOps ff;
-    FTMI_TRY(ff_ops(c, ffw, &ff));
+    FTMI_TRY(ff_ops(c, w, &ff));
     const WsLayout L = make_layout(c, G, ff.on);
     if (ws_bytes < L.total) return set_error(FTMI_ERR_INVALID, "ltx_forward_frames: workspace too small");
-    FTMI_TRY(ltx_prologue_time(c, w, L, ws, timesteps, G, st));
-    FTMI_TRY(ltx_proj_in(c, w, L, ws, x_t, st));
-    FTMI_TRY(ltx_prologue_text(c, w, L, ws, text, st));
-    return ltx_blocks_tail(c, w, ff, L, ws, key_bias, pred, st, ModGroups{G, c.S / frames});
+    FTMI_TRY(ltx_prologue_time(c, w.base, L, ws, timesteps, G, st));
+    FTMI_TRY(ltx_proj_in(c, w.base, L, ws, x_t, st));
+    FTMI_TRY(ltx_prologue_text(c, w.base, L, ws, text, st));
+    return ltx_blocks_tail(c, w.base, ff, L, ws, key_bias, pred, st, ModGroups{G, c.S / frames});
 }
 
 // ---- latent sampling: the whole denoising loop as one call, zero host syncs -------------------------------------------------------------------------
@@ -479,15 +470,13 @@ static SampleLayout make_sample_layout(const ftmi_ltx_config& c, int two_pass, i
     return s;
 }
 
-size_t ltx_sample_workspace_bytes(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights* ffw, int two_pass) {
-    bool ok;
-    const bool on = ff_on(c, ffw, &ok);
-    return ok ? make_sample_layout(c, two_pass, 0, on).total : 0;
+size_t ltx_sample_workspace_bytes(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights& w, int two_pass) {
+    FfOps ff;
+    return ff_ops(c, w, &ff) == 0 ? make_sample_layout(c, two_pass, 0, ff.on).total : 0;
 }
-size_t ltx_sample_cond_workspace_bytes(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights* ffw, int two_pass, int frames) {
-    bool ok;
-    const bool on = ff_on(c, ffw, &ok);
-    return frames > 0 && ok ? make_sample_layout(c, two_pass, frames, on).total : 0;
+size_t ltx_sample_cond_workspace_bytes(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights& w, int two_pass, int frames) {
+    FfOps ff;
+    return ff_ops(c, w, &ff) == 0 && frames > 0 ? make_sample_layout(c, two_pass, frames, ff.on).total : 0;
 }
 
 // FTMI_SAMPLE_HOIST=0 (read once; ftmi_reload_switches() re-reads it) repeats the text part of the prologue in every step, as a loop over ltx_forward
@@ -499,7 +488,7 @@ size_t ltx_sample_cond_workspace_bytes(const ftmi_ltx_config& c, const ftmi_ltx_
 // (model row, frame).  A step knows two distinct timesteps only, so the embedding MLP runs on ONE row per step (the live timestep); the timestep-0 row is
 // computed once per call, next to the text hoist, and cond_rows_expand deals the two rows out to the groups.  With FTMI_SAMPLE_HOIST=0 every step runs the
 // whole per-frame prologue of ltx_forward_frames instead (all groups through the MLP): same bits, a row's embedding does not depend on its neighbours.
-static int ltx_sample_impl(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const ftmi_ltx_ff_weights* ffw, const bf16_t* text_cond, const bf16_t* text_uncond, const float* kbias_cond,
+static int ltx_sample_impl(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights& w, const bf16_t* text_cond, const bf16_t* text_uncond, const float* kbias_cond,
                            const float* kbias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, int frames,
                            int cond_frames, void* ws, size_t ws_bytes, hipStream_t st) {
     static const EnvSwitch hoist_sw("FTMI_SAMPLE_HOIST", 1);
@@ -512,7 +501,7 @@ static int ltx_sample_impl(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, 
     if (frames > 0 && (cond_frames < 0 || cond_frames > frames)) return set_error(FTMI_ERR_INVALID, "ltx_sample_cond: cond_frames must lie in [0, frames]");
     if (frames > 0 && c.C_in % 8) return set_error(FTMI_ERR_UNSUPPORTED, "ltx_sample_cond: the channel count must be a multiple of 8 (the held prefix moves in 16-byte vectors)");
     FfOps ff;
-    FTMI_TRY(ff_ops(c, ffw, &ff));
+    FTMI_TRY(ff_ops(c, w, &ff));
     const SampleLayout sl = make_sample_layout(c, two_pass, frames, ff.on);
     const ftmi_ltx_config& mc = sl.mc;
     FTMI_TRY(check_cfg(mc, frames));
@@ -546,53 +535,53 @@ static int ltx_sample_impl(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, 
     }
     if (!ok) return set_error(FTMI_ERR_LAUNCH, "ltx_sample: copy of the prompt embeddings failed");
 
-    if (hoist) FTMI_TRY(ltx_prologue_text(mc, w, L, ws, text, st));
+    if (hoist) FTMI_TRY(ltx_prologue_text(mc, w.base, L, ws, text, st));
     bf16_t* emb2 = frames > 0 ? W(ws, sl.emb2) : nullptr;
     bf16_t* temb2 = frames > 0 ? W(ws, sl.temb2) : nullptr;
     if (frames > 0 && hoist) {  // the timestep-0 row of the conditioning: constant over the loop
         if (hipMemsetAsync(tval, 0, 4, st) != hipSuccess) return set_error(FTMI_ERR_LAUNCH, "ltx_sample_cond: memset of the timestep failed");
-        FTMI_TRY(ltx_time_embed(mc, w, L, ws, tval, 1, emb2, temb2, st));
+        FTMI_TRY(ltx_time_embed(mc, w.base, L, ws, tval, 1, emb2, temb2, st));
     }
     FTMI_TRY(cfg_euler_step(nullptr, x, nullptr, nullptr, 0, guidance, xin, B, per_sample, st));  // the first model input: bf16(x) in every half
     for (int i = 0; i < n_steps; ++i) {
         if (frames <= 0) {
             FTMI_TRY(bcast_f32(timesteps + i, tval, nb, st));
-            FTMI_TRY(ltx_prologue_time(mc, w, L, ws, tval, nb, st));
+            FTMI_TRY(ltx_prologue_time(mc, w.base, L, ws, tval, nb, st));
         } else if (hoist) {
-            FTMI_TRY(ltx_time_embed(mc, w, L, ws, timesteps + i, 1, emb2 + mc.D, temb2 + 6 * (size_t)mc.D, st));
+            FTMI_TRY(ltx_time_embed(mc, w.base, L, ws, timesteps + i, 1, emb2 + mc.D, temb2 + 6 * (size_t)mc.D, st));
             FTMI_TRY(cond_rows_expand(emb2, temb2, W(ws, L.emb), W(ws, L.temb), mg.n, frames, cond_frames, mc.D, st));
-            FTMI_TRY(ltx_ada_tables(mc, w, L, ws, mg.n, st));
+            FTMI_TRY(ltx_ada_tables(mc, w.base, L, ws, mg.n, st));
         } else {
             FTMI_TRY(frame_timesteps(timesteps + i, tval, mg.n, frames, cond_frames, st));
-            FTMI_TRY(ltx_prologue_time(mc, w, L, ws, tval, mg.n, st));
+            FTMI_TRY(ltx_prologue_time(mc, w.base, L, ws, tval, mg.n, st));
         }
-        FTMI_TRY(ltx_proj_in(mc, w, L, ws, xin, st));
-        if (!hoist) FTMI_TRY(ltx_prologue_text(mc, w, L, ws, text, st));
-        FTMI_TRY(ltx_blocks_tail(mc, w, ff, L, ws, kbias, pred, st, mg));
+        FTMI_TRY(ltx_proj_in(mc, w.base, L, ws, xin, st));
+        if (!hoist) FTMI_TRY(ltx_prologue_text(mc, w.base, L, ws, text, st));
+        FTMI_TRY(ltx_blocks_tail(mc, w.base, ff, L, ws, kbias, pred, st, mg));
         FTMI_TRY(cfg_euler_step(pred, x, sigmas + i, sigmas + i + 1, 0, guidance, i + 1 < n_steps ? xin : nullptr, B, per_sample, st, hold));
     }
     return 0;
 }
 
-int ltx_sample(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const ftmi_ltx_ff_weights* ffw, const bf16_t* text_cond, const bf16_t* text_uncond, const float* kbias_cond,
+int ltx_sample(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights& w, const bf16_t* text_cond, const bf16_t* text_uncond, const float* kbias_cond,
                const float* kbias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, void* ws, size_t ws_bytes,
                hipStream_t st) {
-    return ltx_sample_impl(c, w, ffw, text_cond, text_uncond, kbias_cond, kbias_uncond, x, sigmas, timesteps, n_steps, guidance, 0, 0, ws, ws_bytes, st);
+    return ltx_sample_impl(c, w, text_cond, text_uncond, kbias_cond, kbias_uncond, x, sigmas, timesteps, n_steps, guidance, 0, 0, ws, ws_bytes, st);
 }
 
-int ltx_sample_cond(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const ftmi_ltx_ff_weights* ffw, const bf16_t* text_cond, const bf16_t* text_uncond, const float* kbias_cond,
+int ltx_sample_cond(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights& w, const bf16_t* text_cond, const bf16_t* text_uncond, const float* kbias_cond,
                     const float* kbias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, int frames,
                     int cond_frames, void* ws, size_t ws_bytes, hipStream_t st) {
     if (frames <= 0) return set_error(FTMI_ERR_INVALID, "ltx_sample_cond: frames must be positive");
-    return ltx_sample_impl(c, w, ffw, text_cond, text_uncond, kbias_cond, kbias_uncond, x, sigmas, timesteps, n_steps, guidance, frames, cond_frames, ws, ws_bytes, st);
+    return ltx_sample_impl(c, w, text_cond, text_uncond, kbias_cond, kbias_uncond, x, sigmas, timesteps, n_steps, guidance, frames, cond_frames, ws, ws_bytes, st);
 }
 
 // Backward of blocks [l_lo, l_hi) in descending order (the tail first when l_hi == L).  When the call returns (stream order) the LoRA
 // gradients of exactly those blocks are FINAL -- all 8 adapters, the text-side ones included -- so a data-parallel caller can start
 // the gradient exchange of that block range while the next call computes the blocks below it (DDP's bucketed overlap,
 // finetrainers/parallel/ptd.py:462-463, without a reducer).  State between calls lives in the workspace; l_hi..l_lo must tile L..0.
-int ltx_backward_range(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, const ftmi_ltx_ff_weights* ffw, const bf16_t* text, const float* key_bias, const bf16_t* dpred,
-                       float* grad_a, float* grad_b, float* grad_ff, void* ws, size_t ws_bytes, int l_hi, int l_lo, int accumulate, hipStream_t st) {
+int ltx_backward_range(const ftmi_ltx_config& c, const ftmi_ltx_ff_weights& w, const bf16_t* text, const float* key_bias, const bf16_t* dpred, float* grad_a,
+                       float* grad_b, float* grad_ff, void* ws, size_t ws_bytes, int l_hi, int l_lo, int accumulate, hipStream_t st) {
     (void)text;
     FTMI_TRY(check_cfg(c));
     struct ValidWidth {  // (normalisations of a zero-padded narrow model take their mean over d_valid channels; reset when the pass has queued its launches)
@@ -600,7 +589,7 @@ int ltx_backward_range(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, cons
         ~ValidWidth() { rowwise_set_valid_width(0); }
     } valid_width_guard(c.d_valid);
     FfOps ff;
-    FTMI_TRY(ff_ops(c, ffw, &ff));
+    FTMI_TRY(ff_ops(c, w, &ff));
     if (ff.on && !grad_ff) return set_error(FTMI_ERR_INVALID, "ltx_backward: feed-forward adapters without their gradient buffer");
     const WsLayout L = make_layout(c, 0, ff.on);
     if (ws_bytes < L.total) return set_error(FTMI_ERR_INVALID, "ltx_backward: workspace too small");
@@ -625,7 +614,7 @@ int ltx_backward_range(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, cons
 
     // ---- tail ----
     if (l_hi == c.L) {
-        FTMI_TRY(gemm_nt(linear_args(dpred, c.C_out, M, P(w.proj_out_w_t, 0), c.C_out, D, c.C_out, nullptr, d1, D, V), st));
+        FTMI_TRY(gemm_nt(linear_args(dpred, c.C_out, M, P(w.base.proj_out_w_t, 0), c.C_out, D, c.C_out, nullptr, d1, D, V), st));
         const bf16_t* hL = W(ws, L.hs) + (size_t)c.L * M * D;
         const bf16_t* ao = W(ws, L.ada_out);
         // the gated copy bf(dh * gate_mlp) that opens the last block's backward is written by the same kernel (into dO, idle here)
@@ -638,7 +627,7 @@ int ltx_backward_range(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, cons
     // gradients dB += dY^T XA and dA += dXA^T X only feed the gradient buffer, so dY / dXA are kept per block and all 28
     // blocks of one adapter are reduced by ONE batched launch after the loop (fills the GPU instead of 28 latency-bound ones).
     auto lora_dxa = [&](const bf16_t* dY, long lddy, int rows, int nadp, int adp, int l, bf16_t* dxa_out) -> GemmNtArgs {
-        const bf16_t* lbt = P(w.lora_bt_sp, ((size_t)l * 8 + adp) * 2 * r * D);  // [nadp * 2r][D]: (hi, lo) planes of B^T
+        const bf16_t* lbt = P(w.base.lora_bt_sp, ((size_t)l * 8 + adp) * 2 * r * D);  // [nadp * 2r][D]: (hi, lo) planes of B^T
         return lora_down_args(dY, lddy, rows, lbt, nadp, D, r, s, dxa_out, nadp > 1 ? D : 0);
     };
     FuseCtx fx{reinterpret_cast<int*>(reinterpret_cast<char*>(ws) + L.sk_flags), 0};  // row-tile counters of the fused down-projection + GEMM launches of this call
@@ -673,7 +662,7 @@ int ltx_backward_range(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, cons
         const bf16_t* h0 = W(ws, L.hs) + (size_t)l * M * D;
         const bf16_t* ada = W(ws, L.ada) + (size_t)l * c.B * 8 * D;
         const long ab = 8L * D;
-        const bf16_t* lat = w.lora_at_ext ? P(w.lora_at_ext, (size_t)l * 8 * D * 3 * r) : nullptr;  // [8][D][3r]  [A^T_hi | A^T_hi | A^T_lo]
+        const bf16_t* lat = w.base.lora_at_ext ? P(w.base.lora_at_ext, (size_t)l * 8 * D * 3 * r) : nullptr;  // [8][D][3r]  [A^T_hi | A^T_hi | A^T_lo]
         const bf16_t* h1 = W(blk, L.h1);
         const bf16_t* h2 = W(blk, L.h2);
         const bf16_t* dhin = dh[cur];
@@ -683,7 +672,7 @@ int ltx_backward_range(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, cons
             lora_ext_bwd(a, dxa, nadp, r, at_ext, 3L * nadp * r);
             return lora_gemm(a, lora_dxa(a.X, a.ldx, M, nadp, adp, l, dxa), fx, st);
         };
-        if (c.checkpoint) FTMI_TRY(ltx_block_forward(c, w, ff, L, ws, l, key_bias, st, fx, ModGroups{c.B, c.S}));  // the block's activations again, into the one slot
+        if (c.checkpoint) FTMI_TRY(ltx_block_forward(c, w.base, ff, L, ws, l, key_bias, st, fx, ModGroups{c.B, c.S}));  // the block's activations again, into the one slot
 
         // ---- feed-forward ----
         // (dO holds bf(dhin * gate_mlp): written by the kernel that produced dhin)
@@ -701,13 +690,13 @@ int ltx_backward_range(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, cons
             FTMI_TRY(gelu_from_pre(W(blk, L.z), F, W(ws, L.s_g), F, M, F, st));
         }
         {   // dz = (dO W2 [+ dXA2 A2]) * gelu'(z)
-            GemmNtArgs a = linear_args(dO, D, M, P(w.w_ff2_t, (size_t)l * F * D), D, F, D, nullptr, dz, F, V);
+            GemmNtArgs a = linear_args(dO, D, M, P(w.base.w_ff2_t, (size_t)l * F * D), D, F, D, nullptr, dz, F, V);
             a.epi = EPI_DGELU; a.aux = W(blk, L.z); a.ldaux = F;
             if (ff.on) FTMI_TRY(proj_bwd_with(a, ff.b2t_sp + (size_t)l * 2 * r * D, ff.a2t_ext + (size_t)l * F * 3 * r, W(ws, L.s_dxa_ff2)));
             else FTMI_TRY(gemm_nt(a, st));
         }
         {   // dn2 = dz W1 [+ dXA1 A1]
-            GemmNtArgs a = linear_args(dz, F, M, P(w.w_ff1_t, (size_t)l * D * F), F, D, F, nullptr, d2, D, V);
+            GemmNtArgs a = linear_args(dz, F, M, P(w.base.w_ff1_t, (size_t)l * D * F), F, D, F, nullptr, d2, D, V);
             if (ff.on) FTMI_TRY(proj_bwd_with(a, ff.b1t_sp + (size_t)l * 2 * r * F, ff.a1t_ext + (size_t)l * D * 3 * r, W(ws, L.s_dxa_ff1)));
             else FTMI_TRY(gemm_nt(a, st));
         }
@@ -726,7 +715,7 @@ int ltx_backward_range(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, cons
 
         // ---- cross-attention ----
         {
-            GemmNtArgs a = linear_args(d3, D, M, P(w.w_o2_t, (size_t)l * D2), D, D, D, nullptr, d1, D, V);
+            GemmNtArgs a = linear_args(d3, D, M, P(w.base.w_o2_t, (size_t)l * D2), D, D, D, nullptr, d1, D, V);
             FTMI_TRY(proj_bwd(a, 7, 1, W(blk, L.dxa_o2), lat + 7L * D * 3 * r));  // d1 = dO2
         }
         {
@@ -739,9 +728,9 @@ int ltx_backward_range(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, cons
             FTMI_TRY(attn_bwd(a, st));
         }
         bf16_t* gq2 = W(blk, L.g_q2);  // dq2raw
-        FTMI_TRY(qknorm_rope_bwd(W(blk, L.q2raw), D, P(w.norm_q2, (size_t)l * D), nullptr, nullptr, d2, D, gq2, D, M, c.S, D, c.eps_qk, st));
+        FTMI_TRY(qknorm_rope_bwd(W(blk, L.q2raw), D, P(w.base.norm_q2, (size_t)l * D), nullptr, nullptr, d2, D, gq2, D, M, c.S, D, c.eps_qk, st));
         {
-            GemmNtArgs a = linear_args(gq2, D, M, P(w.w_q2_t, (size_t)l * D2), D, D, D, nullptr, d2, D, V);
+            GemmNtArgs a = linear_args(gq2, D, M, P(w.base.w_q2_t, (size_t)l * D2), D, D, D, nullptr, d2, D, V);
             a.epi = EPI_RESID; a.resid = d3; a.ldr = D;
             a.out2 = W(blk, L.g_o); a.ldo2 = D; a.gate2 = ada + 2 * D; a.gate2_bstride = ab; a.rows_per_batch = c.S;  // go = bf(dh1 * gate_msa), fused
             FTMI_TRY(proj_bwd(a, 4, 1, W(blk, L.dxa_q2), lat + 4L * D * 3 * r));  // d2 = dh1
@@ -750,7 +739,7 @@ int ltx_backward_range(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, cons
         // ---- self-attention ----
         bf16_t* go = W(blk, L.g_o);  // d(attn1.to_out output)
         {
-            GemmNtArgs a = linear_args(go, D, M, P(w.w_o_t, (size_t)l * D2), D, D, D, nullptr, dO, D, V);
+            GemmNtArgs a = linear_args(go, D, M, P(w.base.w_o_t, (size_t)l * D2), D, D, D, nullptr, dO, D, V);
             FTMI_TRY(proj_bwd(a, 3, 1, W(blk, L.dxa_o), lat + 3L * D * 3 * r));
         }
         bf16_t* dqkv = W(blk, L.g_qkv);
@@ -764,12 +753,12 @@ int ltx_backward_range(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, cons
             a.dv = dqkv + 2 * D;   tok_strides(a.dv_sb, a.dv_sh, a.dv_ss, c.S, 3 * D, 64);
             FTMI_TRY(attn_bwd(a, st));
         }
-        FTMI_TRY(qknorm_rope_bwd(qkv, 3 * D, P(w.norm_q, (size_t)l * D), w.rope_cos, w.rope_sin, W(ws, L.s_dqr), D, dqkv, 3 * D, M, c.S, D, c.eps_qk, st, 1,
-                                 qkv + D, P(w.norm_k, (size_t)l * D), W(ws, L.s_dkr), dqkv + D));  // q and k in one launch
+        FTMI_TRY(qknorm_rope_bwd(qkv, 3 * D, P(w.base.norm_q, (size_t)l * D), w.base.rope_cos, w.base.rope_sin, W(ws, L.s_dqr), D, dqkv, 3 * D, M, c.S, D, c.eps_qk, st, 1,
+                                 qkv + D, P(w.base.norm_k, (size_t)l * D), W(ws, L.s_dkr), dqkv + D));  // q and k in one launch
         if (r > 0 && l == 0) FTMI_TRY(gemm_nt(lora_dxa(dqkv, 3 * D, M, 3, 0, l, W(blk, L.dxa_qkv)), st));  // (block 0 has no input gradient: the dXA alone, for dA)
         if (l > 0) {
-            GemmNtArgs a = linear_args(dqkv, 3 * D, M, P(w.w_qkv_t, (size_t)l * 3 * D2), 3 * D, D, 3 * D, nullptr, d1, D, V);
-            FTMI_TRY(proj_bwd(a, 0, 3, W(blk, L.dxa_qkv), P(w.lora_at_qkv_ext, (size_t)l * D * 9 * r)));  // d1 = dn1
+            GemmNtArgs a = linear_args(dqkv, 3 * D, M, P(w.base.w_qkv_t, (size_t)l * 3 * D2), 3 * D, D, 3 * D, nullptr, d1, D, V);
+            FTMI_TRY(proj_bwd(a, 0, 3, W(blk, L.dxa_qkv), P(w.base.lora_at_qkv_ext, (size_t)l * D * 9 * r)));  // d1 = dn1
             const bf16_t* ada_prev = W(ws, L.ada) + (size_t)(l - 1) * c.B * 8 * D;  // the next block processed is l - 1
             FTMI_TRY(norm_modulate_bwd(h0, d1, ada + 6 * D, ab, d2, dh[cur ^ 1], M, c.S, D, c.eps_norm, 0, st, ada_prev + 5 * D, ab, dO));
             cur ^= 1;
@@ -783,11 +772,11 @@ int ltx_backward_range(const ftmi_ltx_config& c, const ftmi_ltx_weights& w, cons
     if (r > 0) {
         // d(k2raw) = RMSNorm backward of d(k2n); rows ordered (token, block) like the forward
         // (row i of this call = (token i / nb, block l_lo + i % nb): rows of one token are L apart in the all-block arrays)
-        FTMI_TRY(qknorm_rope_bwd(W(ws, L.kv2_all) + (size_t)l_lo * 2 * D, 2 * D, P(w.norm_k2, (size_t)l_lo * D), nullptr, nullptr,
+        FTMI_TRY(qknorm_rope_bwd(W(ws, L.kv2_all) + (size_t)l_lo * 2 * D, 2 * D, P(w.base.norm_k2, (size_t)l_lo * D), nullptr, nullptr,
                                  W(ws, L.g_k2n_all) + (size_t)l_lo * D, D, W(ws, L.g_kv2_all) + (size_t)l_lo * 2 * D, 2 * D,
                                  Mt * nb, Mt * nb, D, c.eps_qk, st, nb, nullptr, nullptr, nullptr, nullptr, nb, c.L));
         // dXA[:, (l,k|v)] = s * dY[:, (l,k|v) slice] B_{l,k|v}: the 2 nb adapters of this range, written into their columns of the all-block array
-        GemmNtArgs a = lora_down_args(W(ws, L.g_kv2_all) + (size_t)l_lo * 2 * D, (long)c.L * 2 * D, Mt, P(w.lora_bt_sp, ((size_t)l_lo * 8 + 5) * 2 * r * D), 2 * nb, D, r, s,
+        GemmNtArgs a = lora_down_args(W(ws, L.g_kv2_all) + (size_t)l_lo * 2 * D, (long)c.L * 2 * D, Mt, P(w.base.lora_bt_sp, ((size_t)l_lo * 8 + 5) * 2 * r * D), 2 * nb, D, r, s,
                                       W(ws, L.dxa_kv2_all) + (size_t)l_lo * 6 * r, D);
         a.w_grp_n = 4 * r; a.w_grp_stride = 16L * r * D; a.ldo = (long)c.L * 6 * r; a.variant = V;
         FTMI_TRY(gemm_nt(a, st));

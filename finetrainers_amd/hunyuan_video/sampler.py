@@ -5,7 +5,7 @@ The reference validates by running ``HunyuanVideoPipeline`` over a diffusers tra
 pipeline cannot take this backend's blocks -- flat frozen buffers, fp32 adapters, fp8 bytes that exist as bf16 only inside a shared arena -- and
 ``MI355XHunyuanVideoTransformer3DModel.forward`` is a training path: an autograd function and a ``saved`` area per block, torch permutes around the patch
 embedding, a ``torch.cat`` of the two streams.  Here the loop -- DiT forward, optional true-CFG combine, flow-match Euler update -- is ONE C call
-(``ftmi_hy_sample``, no host synchronisation) that issues the same block launches out of a workspace that does not grow with the number of blocks, with the
+(``ftmi_hy_sample_text``, no host synchronisation) that issues the same block launches out of a workspace that does not grow with the number of blocks, with the
 adapters as they are at the moment of the call.  The sampler state stays in the patch embedding's operand layout, which is also ``proj_out``'s column order
 (csrc/sample_layout.hip), so nothing is patchified between steps.  Text encoding and the VAE stay outside: the sampler takes embeddings and noise and returns
 ``latents / scaling_factor`` (INTEGRATION.md shows the hand-over to the reference pipeline's VAE decode).
@@ -83,7 +83,7 @@ def _block_weights(blk, fields, struct, arena: Optional[torch.Tensor]):
 
 
 class MI355XHunyuanVideoLatentSampler:
-    """Denoising loop over a ``MI355XHunyuanVideoTransformer3DModel`` (``ftmi_hy_sample``).  The adapters are read at every ``sample``: a sample taken between
+    """Denoising loop over a ``MI355XHunyuanVideoTransformer3DModel`` (``ftmi_hy_sample_text``).  The adapters are read at every ``sample``: a sample taken between
     two optimiser steps sees them as they are."""
 
     def __init__(self, transformer: MI355XHunyuanVideoTransformer3DModel, scheduler_config: Optional[Dict[str, Any]] = None):
@@ -163,8 +163,8 @@ class MI355XHunyuanVideoLatentSampler:
         return ops.hy_sample_geometry(B, c.out_channels, frames, height, width, patch=c.patch_size, patch_t=c.patch_size_t, true_cfg=true_cfg)
 
     def c_arguments(self, geo, T: int, steps: int, true_cfg_scale: float = 1.0):
-        """-> (ftmi_hy_sample_config, ftmi_hy_sample_weights, the objects the two structures point into).  The adapters are read here.  A model whose dual-stream
-        blocks carry the text stream's adapters gets the ftmi_hy_sample_text_config extension (``ops.hy_sample`` then calls ftmi_hy_sample_text)."""
+        """-> (ftmi_hy_sample_text_config, ftmi_hy_sample_weights, the objects the two structures point into).  The adapters are read here; ``text_adapters`` is 1
+        for a model whose dual-stream blocks carry the text stream's adapters."""
         tr = self.transformer
         c = tr.config
         duals, singles = list(tr.transformer_blocks), list(tr.single_transformer_blocks)
@@ -172,10 +172,9 @@ class MI355XHunyuanVideoLatentSampler:
         first = blocks[0]
         r = 0 if first.lora_A is None else int(first.lora_A.shape[1])
         text_adapters = int(bool(duals) and duals[0].text_adapters)  # (check_inputs: all dual blocks alike)
-        cfg = _lib.HySampleConfig(geo=geo, T=int(T), D=c.inner_dim, H=c.num_attention_heads, mlp=int(c.inner_dim * c.mlp_ratio), Ld=len(duals), Ls=len(singles), r=r,
-                                  lora_scale=float(first.lora_scale), eps=1e-6, gemm_variant=8, steps=int(steps), true_cfg=float(true_cfg_scale))
-        if text_adapters:
-            cfg = _lib.HySampleTextConfig(base=cfg, text_adapters=1)
+        base = _lib.HySampleConfig(geo=geo, T=int(T), D=c.inner_dim, H=c.num_attention_heads, mlp=int(c.inner_dim * c.mlp_ratio), Ld=len(duals), Ls=len(singles), r=r,
+                                   lora_scale=float(first.lora_scale), eps=1e-6, gemm_variant=8, steps=int(steps), true_cfg=float(true_cfg_scale))
+        cfg = _lib.HySampleTextConfig(base=base, text_adapters=text_adapters)
         fp8 = any(b._w8 is not None for b in blocks)
         arena = getattr(tr, "_weight_arena_fwd", None) if fp8 else None
         if fp8 and (arena is None or not all(b._w8 is not None for b in blocks)):

@@ -2,9 +2,9 @@
 
 The reference validates by building an ``LTXPipeline`` and running its denoising loop per prompt (finetrainers/models/ltx_video/
 base_specification.py:347-377).  Here the loop -- DiT forward on the conditional + unconditional prompt, classifier-free-guidance combine, flow-match Euler
-update -- is ONE C call (``ftmi_ltx_sample``, no host synchronisation) over the transformer that is being trained, with its current LoRA state.  A
+update -- is ONE C call (``ftmi_ltx_ff_sample``, no host synchronisation) over the transformer that is being trained, with its current LoRA state.  A
 validation row with an image runs the image-to-video pipeline there (:360-361); here that is ``image_latents``: the first latent frames held, timestep 0
-on them (``ftmi_ltx_sample_cond``).  Text encoding, VAE encoding of the image and VAE decoding stay outside: the sampler takes prompt embeddings and returns denormalised latents (INTEGRATION.md shows the hand-over to the
+on them (``ftmi_ltx_ff_sample_cond``).  Text encoding, VAE encoding of the image and VAE decoding stay outside: the sampler takes prompt embeddings and returns denormalised latents (INTEGRATION.md shows the hand-over to the
 reference pipeline's VAE decode).
 """
 
@@ -74,7 +74,7 @@ def latent_grid(num_frames: int, height: int, width: int, temporal_compression: 
 
 
 class MI355XLTXLatentSampler:
-    """Denoising loop over a ``MI355XLTXVideoTransformer3DModel`` (``ftmi_ltx_sample`` / ``ftmi_ltx_sample_cond``)."""
+    """Denoising loop over a ``MI355XLTXVideoTransformer3DModel`` (``ftmi_ltx_ff_sample`` / ``ftmi_ltx_ff_sample_cond``)."""
 
     def __init__(self, transformer: MI355XLTXVideoTransformer3DModel, scheduler_config: Optional[Dict[str, Any]] = None, frame_rate: int = 25):
         if getattr(transformer, "_narrow", None) is not None:
@@ -143,7 +143,7 @@ class MI355XLTXLatentSampler:
         NORMALISED latents of the conditioning frames -- the VAE encoding of the image after ``_normalize_latents`` (base_specification.py:427-436), not the
         raw encoder output; ``latents_mean`` / ``latents_std`` are used for the final denormalisation only.  They occupy latent frames [0, k) of the initial
         state and are held: the model sees timestep 0 on them, the guidance combine and the Euler update skip them, and they come back in the result,
-        denormalised like the rest (``ftmi_ltx_sample_cond``).  The noise is drawn for the whole [B, C, F, H, W] shape first and the held frames are then
+        denormalised like the rest (``ftmi_ltx_ff_sample_cond``).  The noise is drawn for the whole [B, C, F, H, W] shape first and the held frames are then
         overwritten, so one seed gives the noise the pipeline draws; upstream repeats the one encoded frame over all frames and blends by its mask, which for
         k = 1 is this state.  ``cond_frames`` (default: the k of ``image_latents``; 0 without them) holds the first frames of ``latents`` when the caller
         supplies the whole initial state itself."""
@@ -192,9 +192,8 @@ class MI355XLTXLatentSampler:
         cfg = tr._c_config(B, S, T)
         weights = tr._c_weights(cos, sin)
         conditioned = image_latents is not None or cond_frames is not None
-        # (a model with feed-forward adapters hands over _lib.LtxFfWeights: ops then sizes and runs the _ff twins of the two entries)
-        ws_bytes = (ops.ltx_sample_cond_workspace_bytes(cfg, two_pass, num_frames, weights=weights) if conditioned
-                    else ops.ltx_sample_workspace_bytes(cfg, two_pass, weights=weights))
+        ws_bytes = (ops.ltx_sample_cond_workspace_bytes(cfg, two_pass, num_frames, weights) if conditioned
+                    else ops.ltx_sample_workspace_bytes(cfg, two_pass, weights))
         ws = tr._acquire_workspace(ws_bytes, dev)
         try:
             if conditioned:

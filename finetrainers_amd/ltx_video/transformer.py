@@ -3,7 +3,7 @@
 ``MI355XLTXVideoTransformer3DModel`` is an ``nn.Module`` whose ``forward`` has the signature of the
 reference's patched ``LTXVideoTransformer3DModel.forward`` (finetrainers/patches/models/ltx_video/
 patch.py:38-50) and whose backward yields LoRA gradients -- but the whole 28-block forward and backward
-run as hand-written gfx950 kernels launched by two C calls (``ftmi_ltx_forward`` / ``ftmi_ltx_backward``).
+run as hand-written gfx950 kernels launched by two C calls (``ftmi_ltx_ff_forward`` / ``ftmi_ltx_ff_backward_range``).
 
 HBM layout (designed for 288 GB, not ported from the reference's per-module parameters):
   * frozen bf16 base weights are stacked per kind along a leading layer axis ([L,3D,D] fused q|k|v, ...)
@@ -15,7 +15,7 @@ HBM layout (designed for 288 GB, not ported from the reference's per-module para
     trainer.py:132-136): bf16 (hi, lo) working copies of A / B are refreshed after each optimiser step;
   * with a ``target_modules`` that also names ``ff.net.0.proj`` and ``ff.net.2`` (the control trainer's default) every block gets two more adapters:
     ``lora_ff_A1`` [L,r,D], ``lora_ff_B1`` [L,F,r], ``lora_ff_A2`` [L,r,F], ``lora_ff_B2`` [L,D,r], strided views of a third region of the same flat
-    buffer ([A | B | FF], FF per block [A1 | B1 | A2 | B2]); the C calls are then the ``ftmi_ltx_ff_*`` twins;
+    buffer ([A | B | FF], FF per block [A1 | B1 | A2 | B2]); their operand copies fill the extension of ``ftmi_ltx_ff_weights``, NULL without them;
   * all activations of a step live in one caller-owned workspace (about 0.37 GB per block at B=2).
 ``state_dict()`` / ``load_state_dict()`` speak the diffusers + peft key layout (views, no copies); ``lora_state_dict()`` is the
 ``get_peft_model_state_dict`` form.
@@ -33,7 +33,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib, ops
-from .._lib import LTX_FF_WEIGHT_FIELDS, LtxConfig, LtxFfWeights, LtxWeights, check, ptr, stream_ptr
+from .._lib import LTX_FF_WEIGHT_FIELDS, LtxConfig, LtxFfWeights, check, ptr, stream_ptr
 
 bf16 = torch.bfloat16
 
@@ -114,17 +114,16 @@ class _LTXDiTFunction(torch.autograd.Function):
         cfg = module._c_config(B, S, T, checkpoint=module.gradient_checkpointing and any(ctx.needs_input_grad) and module.lora_A is not None)
         weights = module._c_weights(cos, sin)
         lib = _lib.load()
-        ff = module.lora_ff  # ten adapters per block: the _ff twins of the C entries, over ftmi_ltx_ff_weights
-        ws_bytes = lib.ftmi_ltx_ff_workspace_bytes(ctypes.byref(cfg), ctypes.byref(weights)) if ff else lib.ftmi_ltx_workspace_bytes(ctypes.byref(cfg))
+        ws_bytes = lib.ftmi_ltx_ff_workspace_bytes(ctypes.byref(cfg), ctypes.byref(weights))
         # the activation workspace (10.4 GB at cfg 2) is recycled across steps instead of going back to the caching allocator:
         # a multi-GB block that is freed and re-requested every step occasionally costs a device-synchronising hipMalloc
         ws = module._acquire_workspace(ws_bytes, x_t.device)
         pred = torch.empty((B, S, module.config.out_channels), dtype=bf16, device=x_t.device)
-        check((lib.ftmi_ltx_ff_forward if ff else lib.ftmi_ltx_forward)(ctypes.byref(cfg), ctypes.byref(weights), ptr(x_t), ptr(text), ptr(key_bias), ptr(tvals),
-                                                                          ptr(pred), ptr(ws), ws_bytes, stream_ptr()), "ftmi_ltx_forward")
+        check(lib.ftmi_ltx_ff_forward(ctypes.byref(cfg), ctypes.byref(weights), ptr(x_t), ptr(text), ptr(key_bias), ptr(tvals), ptr(pred), ptr(ws), ws_bytes,
+                                      stream_ptr()), "ftmi_ltx_ff_forward")
         ctx.module, ctx.cfg, ctx.weights, ctx.ws, ctx.ws_bytes = module, cfg, weights, ws, ws_bytes
         ctx.keep = (x_t, text, key_bias, tvals, cos, sin)
-        module._last_workspace = (cfg, ws, weights if ff else None)
+        module._last_workspace = (cfg, ws, weights)
         if not any(ctx.needs_input_grad) or module.lora_A is None:
             module._release_workspace(ws)  # no backward will come for this call (its content stays readable until the next forward)
             ctx.ws = None
@@ -167,7 +166,7 @@ class _LTXDiTFunction(torch.autograd.Function):
             accumulate = 0
         ga = gflat[:n_a].view_as(module._lora_A_full)
         gb = gflat[n_a:n_a + n_b].view_as(module._lora_B_full)
-        gff = gflat[n_a + n_b:].view_as(module._lora_ff_full) if ff else None  # [L, per block]
+        gff = gflat[n_a + n_b:].view_as(module._lora_ff_full) if ff else None  # [L, per block]; None: no feed-forward adapters, the C call takes NULL
         r_user = module.lora_rank  # the parameters (and their .grad) are the first r_user rows / columns of the padded storage
         _, text, key_bias, _, _, _ = ctx.keep
         lib = _lib.load()
@@ -177,12 +176,8 @@ class _LTXDiTFunction(torch.autograd.Function):
         hi = L
         while hi > 0:  # block ranges in backward order; each range's gradients are final when its call returns (stream order)
             lo = max(0, hi - step)
-            if ff:
-                check(lib.ftmi_ltx_ff_backward_range(ctypes.byref(ctx.cfg), ctypes.byref(ctx.weights), ptr(text), ptr(key_bias), ptr(dpred), ptr(ga), ptr(gb),
-                                                     ptr(gff), ptr(ctx.ws), ctx.ws_bytes, hi, lo, accumulate, stream_ptr()), "ftmi_ltx_ff_backward")
-            else:
-                check(lib.ftmi_ltx_backward_range(ctypes.byref(ctx.cfg), ctypes.byref(ctx.weights), ptr(text), ptr(key_bias), ptr(dpred), ptr(ga), ptr(gb),
-                                                  ptr(ctx.ws), ctx.ws_bytes, hi, lo, accumulate, stream_ptr()), "ftmi_ltx_backward")
+            check(lib.ftmi_ltx_ff_backward_range(ctypes.byref(ctx.cfg), ctypes.byref(ctx.weights), ptr(text), ptr(key_bias), ptr(dpred), ptr(ga), ptr(gb), ptr(gff),
+                                                 ptr(ctx.ws), ctx.ws_bytes, hi, lo, accumulate, stream_ptr()), "ftmi_ltx_ff_backward_range")
             if hook is not None:
                 if ff:  # the range's feed-forward gradients are one contiguous slice: a third slice of the same bucket
                     hook(lo, hi, ga[lo:hi], gb[lo:hi], gff[lo:hi])
@@ -384,7 +379,7 @@ class MI355XLTXVideoTransformer3DModel(nn.Module):
     # ---- --gradient_checkpointing (trainer/sft_trainer/trainer.py:155-157 -> utils/activation_checkpoint.py:24-49) ---------------------------------------
     def apply_activation_checkpointing(self, checkpointing_type: str = "full", n_layer: int = 1) -> "MI355XLTXVideoTransformer3DModel":
         """The reference wraps every transformer block ("full"; the trainer passes nothing else).  Here: the activation workspace holds one block slot
-        instead of ``num_layers`` (10.4 GB -> 1.3 GB at BASELINE config 2), the forward keeps only the residual stream and ``ftmi_ltx_backward_range`` runs a
+        instead of ``num_layers`` (10.4 GB -> 1.3 GB at BASELINE config 2), the forward keeps only the residual stream and ``ftmi_ltx_ff_backward_range`` runs a
         block's forward kernels again right before its gradient kernels.  Gradients are bit-identical to the un-checkpointed step (deterministic kernels);
         the price is one extra forward per step (``bench.py --gradient-checkpointing``).  "block_skip" would mix kept and recomputed blocks in one
         workspace: not offered for this model (HunyuanVideo, where memory matters, has it)."""
@@ -658,17 +653,13 @@ class MI355XLTXVideoTransformer3DModel(nn.Module):
                          # (a narrow model embedded by zero padding -- ltx_video/narrow.py -- tells the kernels its true width and head width; 0 = this geometry)
                          d_valid=getattr(self, "_narrow", (0, 0))[0], head_dim_valid=getattr(self, "_narrow", (0, 0))[1])
 
-    def _c_weights(self, cos: torch.Tensor, sin: torch.Tensor):
-        """``LtxWeights``; with the feed-forward adapters ``LtxFfWeights`` (the base first, then their operand copies) for the ``_ff`` entries."""
+    def _c_weights(self, cos: torch.Tensor, sin: torch.Tensor) -> LtxFfWeights:
+        """The base structure, then the feed-forward adapters' operand copies: NULL without them."""
+        wf = LtxFfWeights()
         if self.lora_ff:
-            wf = LtxFfWeights()
-            self._fill_c_weights(wf.base, cos, sin)
             for n in LTX_FF_WEIGHT_FIELDS:
                 setattr(wf, n, getattr(self, n).data_ptr())
-            return wf
-        return self._fill_c_weights(LtxWeights(), cos, sin)
-
-    def _fill_c_weights(self, w: LtxWeights, cos: torch.Tensor, sin: torch.Tensor) -> LtxWeights:
+        w = wf.base
         for n in self._frozen_names:
             setattr(w, n, getattr(self, n).data_ptr())
         if self.lora_A is not None:
@@ -676,7 +667,7 @@ class MI355XLTXVideoTransformer3DModel(nn.Module):
             w.lora_b_ext, w.lora_at_ext = self.lora_b_ext.data_ptr(), self.lora_at_ext.data_ptr()
             w.lora_at_qkv_ext = self.lora_at_qkv_ext.data_ptr()
         w.rope_cos, w.rope_sin = cos.data_ptr(), sin.data_ptr()
-        return w
+        return wf
 
     def rope_tables(self, num_frames: int, height: int, width: int, rope_interpolation_scale) -> Tuple[torch.Tensor, torch.Tensor]:
         key = (num_frames, height, width, None if rope_interpolation_scale is None else tuple(float(x) for x in rope_interpolation_scale))
@@ -690,7 +681,7 @@ class MI355XLTXVideoTransformer3DModel(nn.Module):
                 encoder_attention_mask: Optional[torch.Tensor], num_frames: int, height: int, width: int,
                 rope_interpolation_scale=None, return_dict: bool = True, *args, frame_timestep: Optional[torch.Tensor] = None, **kwargs):
         """``frame_timestep`` [B, num_frames] (an addition to the patch.py signature): one timestep per latent frame -- what the image-to-video pipeline
-        feeds the model (0 on the conditioning frame, t on the others).  ``timestep`` is then not read.  Forward only (``ftmi_ltx_forward_frames``)."""
+        feeds the model (0 on the conditioning frame, t on the others).  ``timestep`` is then not read.  Forward only (``ftmi_ltx_ff_forward_frames``)."""
         if frame_timestep is not None:
             return self._forward_frames(hidden_states, encoder_hidden_states, frame_timestep, encoder_attention_mask, num_frames, height, width,
                                         rope_interpolation_scale, return_dict)
@@ -729,7 +720,7 @@ class MI355XLTXVideoTransformer3DModel(nn.Module):
         if tuple(frame_timestep.shape) != (hidden_states.shape[0], num_frames):
             raise ValueError(f"frame_timestep must be [batch, num_frames] = [{hidden_states.shape[0]}, {num_frames}], got {tuple(frame_timestep.shape)}")
         if torch.is_grad_enabled() and self.lora_A is not None and (self.lora_A.requires_grad or self.lora_B.requires_grad):
-            raise NotImplementedError("frame_timestep: the per-frame forward (ftmi_ltx_forward_frames) has no backward -- call it under torch.no_grad() or "
+            raise NotImplementedError("frame_timestep: the per-frame forward (ftmi_ltx_ff_forward_frames) has no backward -- call it under torch.no_grad() or "
                                       "with no adapter that requires grad")
         if getattr(self, "_narrow", None) is not None:
             raise NotImplementedError("frame_timestep: narrow (zero-padded) geometries (ltx_video/narrow.py) are not supported")
@@ -752,7 +743,7 @@ class MI355XLTXVideoTransformer3DModel(nn.Module):
         self.refresh_lora_copies()
         cfg = self._c_config(B, S, T)
         weights = self._c_weights(cos, sin)
-        ws = self._acquire_workspace(ops.ltx_forward_frames_workspace_bytes(cfg, num_frames, weights=weights), x_t.device)
+        ws = self._acquire_workspace(ops.ltx_forward_frames_workspace_bytes(cfg, num_frames, weights), x_t.device)
         try:
             out = ops.ltx_forward_frames(cfg, weights, x_t, text, key_bias, tvals, workspace=ws)
         finally:
@@ -776,12 +767,9 @@ class MI355XLTXVideoTransformer3DModel(nn.Module):
     # ------------------------------------------------------------------ debugging / tests
     def workspace_tensor(self, name: str, layer: int, shape, dtype=bf16) -> torch.Tensor:
         """View of a stashed activation of the most recent forward (tests / debugging only)."""
-        cfg, ws, ffw = self._last_workspace
-        off = ctypes.c_size_t(0)
-        if ffw is not None:  # the ten-adapter layout (also knows "xa_ff1" / "xa_ff2")
-            check(_lib.load().ftmi_ltx_ff_workspace_offset(ctypes.byref(cfg), ctypes.byref(ffw), name.encode(), layer, ctypes.byref(off)), "ftmi_ltx_ff_workspace_offset")
-        else:
-            check(_lib.load().ftmi_ltx_workspace_offset(ctypes.byref(cfg), name.encode(), layer, ctypes.byref(off)), "ftmi_ltx_workspace_offset")
+        cfg, ws, weights = self._last_workspace
+        off = ctypes.c_size_t(0)  # (the ten-adapter layout also knows "xa_ff1" / "xa_ff2")
+        check(_lib.load().ftmi_ltx_ff_workspace_offset(ctypes.byref(cfg), ctypes.byref(weights), name.encode(), layer, ctypes.byref(off)), "ftmi_ltx_ff_workspace_offset")
         n = 1
         for s in shape:
             n *= s

@@ -465,19 +465,18 @@ def ltx_cfg_euler_step_held(pred, x, sigma, sigma_next, guidance: float, hold: i
     return x_next
 
 
-def _ltx_ff(weights) -> bool:
-    """True for the ten-adapter model's weights (``_lib.LtxFfWeights``): the ``_ff`` twins of the LTX entries take them."""
-    return isinstance(weights, _lib.LtxFfWeights)
+# The LTX wrappers below take ``weights``: a ``_lib.LtxFfWeights`` (its feed-forward extension all NULL: the eight attention adapters alone, which is also
+# what the planners size for when they get no weights).
+def _ltx_plan_weights(weights):
+    return ctypes.byref(weights if weights is not None else _lib.LtxFfWeights())
 
 
 def ltx_forward_frames_workspace_bytes(cfg, frames: int, weights=None) -> int:
-    if _ltx_ff(weights):
-        return int(_lib.load().ftmi_ltx_ff_forward_frames_workspace_bytes(ctypes.byref(cfg), ctypes.byref(weights), int(frames)))
-    return int(_lib.load().ftmi_ltx_forward_frames_workspace_bytes(ctypes.byref(cfg), int(frames)))
+    return int(_lib.load().ftmi_ltx_ff_forward_frames_workspace_bytes(ctypes.byref(cfg), _ltx_plan_weights(weights), int(frames)))
 
 
 def ltx_forward_frames(cfg, weights, x_t, text, key_bias, timesteps, workspace=None, pred=None):
-    """DiT forward with one timestep per latent frame, forward only (include/ftmi355.h: ftmi_ltx_forward_frames).  ``x_t`` bf16 [B, S, C_in], ``text`` bf16
+    """DiT forward with one timestep per latent frame, forward only (include/ftmi355.h: ftmi_ltx_ff_forward_frames).  ``x_t`` bf16 [B, S, C_in], ``text`` bf16
     [B, T, D_cap], ``key_bias`` fp32 [B, T] or None, ``timesteps`` fp32 [B, F] with S % F == 0.  Returns ``pred`` bf16 [B, S, C_out]."""
     require_gpu_tensor(x_t, "x_t", bf16)
     require_gpu_tensor(text, "text", bf16)
@@ -503,9 +502,8 @@ def ltx_forward_frames(cfg, weights, x_t, text, key_bias, timesteps, workspace=N
         raise ValueError("ltx_forward_frames: workspace too small")
     if pred is None:
         pred = torch.empty((B, S, cfg.C_out), dtype=bf16, device=x_t.device)
-    lib = _lib.load()
-    check((lib.ftmi_ltx_ff_forward_frames if _ltx_ff(weights) else lib.ftmi_ltx_forward_frames)(ctypes.byref(cfg), ctypes.byref(weights), ptr(x_t), ptr(text), ptr(key_bias), ptr(timesteps), frames, ptr(pred),
-        ptr(workspace), workspace.numel(), stream_ptr()), "ftmi_ltx_forward_frames")
+    check(_lib.load().ftmi_ltx_ff_forward_frames(ctypes.byref(cfg), ctypes.byref(weights), ptr(x_t), ptr(text), ptr(key_bias), ptr(timesteps), frames, ptr(pred),
+                                                 ptr(workspace), workspace.numel(), stream_ptr()), "ftmi_ltx_ff_forward_frames")
     return pred
 
 
@@ -543,14 +541,12 @@ def ltx_unpack_denorm(x, mean, std, num_frames: int, height: int, width: int):
 
 
 def ltx_sample_workspace_bytes(cfg, two_pass: bool, weights=None) -> int:
-    if _ltx_ff(weights):
-        return int(_lib.load().ftmi_ltx_ff_sample_workspace_bytes(ctypes.byref(cfg), ctypes.byref(weights), int(bool(two_pass))))
-    return int(_lib.load().ftmi_ltx_sample_workspace_bytes(ctypes.byref(cfg), int(bool(two_pass))))
+    return int(_lib.load().ftmi_ltx_ff_sample_workspace_bytes(ctypes.byref(cfg), _ltx_plan_weights(weights), int(bool(two_pass))))
 
 
 def ltx_sample(cfg, weights, text_cond, text_uncond, key_bias_cond, key_bias_uncond, x, sigmas, timesteps, guidance: float, workspace=None):
-    """The whole denoising loop as one C call (include/ftmi355.h: ftmi_ltx_sample).  ``cfg`` / ``weights``: ``_lib.LtxConfig`` (B = videos) /
-    ``_lib.LtxWeights``; text_* bf16 [B, T, D_cap]; key_bias_* fp32 [B, T] or None; ``x`` fp32 [B, S, C] (noise in, latents out, IN PLACE);
+    """The whole denoising loop as one C call (include/ftmi355.h: ftmi_ltx_ff_sample).  ``cfg`` / ``weights``: ``_lib.LtxConfig`` (B = videos) /
+    ``_lib.LtxFfWeights``; text_* bf16 [B, T, D_cap]; key_bias_* fp32 [B, T] or None; ``x`` fp32 [B, S, C] (noise in, latents out, IN PLACE);
     ``sigmas`` fp32 [n + 1], ``timesteps`` fp32 [n] on the device.  Returns ``x``."""
     two_pass = float(guidance) != 1.0
     require_gpu_tensor(text_cond, "text_cond", bf16)
@@ -583,22 +579,19 @@ def ltx_sample(cfg, weights, text_cond, text_uncond, key_bias_cond, key_bias_unc
         workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=x.device)
     elif workspace.numel() < ws_bytes:
         raise ValueError("ltx_sample: workspace too small")
-    lib = _lib.load()
-    check((lib.ftmi_ltx_ff_sample if _ltx_ff(weights) else lib.ftmi_ltx_sample)(ctypes.byref(cfg), ctypes.byref(weights), ptr(text_cond), ptr(text_uncond) if two_pass else None, ptr(key_bias_cond),
-        ptr(key_bias_uncond) if two_pass else None, ptr(x), ptr(sigmas), ptr(timesteps), n, float(guidance), ptr(workspace),
-        workspace.numel(), stream_ptr()), "ftmi_ltx_sample")
+    check(_lib.load().ftmi_ltx_ff_sample(ctypes.byref(cfg), ctypes.byref(weights), ptr(text_cond), ptr(text_uncond) if two_pass else None, ptr(key_bias_cond),
+                                         ptr(key_bias_uncond) if two_pass else None, ptr(x), ptr(sigmas), ptr(timesteps), n, float(guidance), ptr(workspace),
+                                         workspace.numel(), stream_ptr()), "ftmi_ltx_ff_sample")
     return x
 
 
 def ltx_sample_cond_workspace_bytes(cfg, two_pass: bool, frames: int, weights=None) -> int:
-    if _ltx_ff(weights):
-        return int(_lib.load().ftmi_ltx_ff_sample_cond_workspace_bytes(ctypes.byref(cfg), ctypes.byref(weights), int(bool(two_pass)), int(frames)))
-    return int(_lib.load().ftmi_ltx_sample_cond_workspace_bytes(ctypes.byref(cfg), int(bool(two_pass)), int(frames)))
+    return int(_lib.load().ftmi_ltx_ff_sample_cond_workspace_bytes(ctypes.byref(cfg), _ltx_plan_weights(weights), int(bool(two_pass)), int(frames)))
 
 
 def ltx_sample_cond(cfg, weights, text_cond, text_uncond, key_bias_cond, key_bias_uncond, x, sigmas, timesteps, guidance: float, frames: int, cond_frames: int,
                     workspace=None):
-    """``ltx_sample`` with the first ``cond_frames`` of the ``frames`` latent frames of every sample held (include/ftmi355.h: ftmi_ltx_sample_cond): those
+    """``ltx_sample`` with the first ``cond_frames`` of the ``frames`` latent frames of every sample held (include/ftmi355.h: ftmi_ltx_ff_sample_cond): those
     tokens of ``x`` are the clean conditioning latents on entry and are never written; the model sees timestep 0 on them.  Returns ``x``."""
     two_pass = float(guidance) != 1.0
     require_gpu_tensor(text_cond, "text_cond", bf16)
@@ -636,10 +629,9 @@ def ltx_sample_cond(cfg, weights, text_cond, text_uncond, key_bias_cond, key_bia
         workspace = torch.empty((ws_bytes,), dtype=torch.uint8, device=x.device)
     elif workspace.numel() < ws_bytes:
         raise ValueError("ltx_sample_cond: workspace too small")
-    lib = _lib.load()
-    check((lib.ftmi_ltx_ff_sample_cond if _ltx_ff(weights) else lib.ftmi_ltx_sample_cond)(ctypes.byref(cfg), ctypes.byref(weights), ptr(text_cond), ptr(text_uncond) if two_pass else None,
-        ptr(key_bias_cond), ptr(key_bias_uncond) if two_pass else None, ptr(x), ptr(sigmas), ptr(timesteps), n,
-        float(guidance), frames, cond_frames, ptr(workspace), workspace.numel(), stream_ptr()), "ftmi_ltx_sample_cond")
+    check(_lib.load().ftmi_ltx_ff_sample_cond(ctypes.byref(cfg), ctypes.byref(weights), ptr(text_cond), ptr(text_uncond) if two_pass else None,
+                                              ptr(key_bias_cond), ptr(key_bias_uncond) if two_pass else None, ptr(x), ptr(sigmas), ptr(timesteps), n,
+                                              float(guidance), frames, cond_frames, ptr(workspace), workspace.numel(), stream_ptr()), "ftmi_ltx_ff_sample_cond")
     return x
 
 
@@ -1500,22 +1492,19 @@ def hy_sample_finish(geo, x, k: float):
 
 
 def hy_sample_workspace_bytes(cfg) -> int:
-    """``cfg``: an ftmi_hy_sample_config, or its ftmi_hy_sample_text_config extension (text-stream adapters in the dual blocks)."""
-    if isinstance(cfg, _lib.HySampleTextConfig):
-        n = int(_lib.load().ftmi_hy_sample_text_workspace_bytes(ctypes.byref(cfg)))
-    else:
-        n = int(_lib.load().ftmi_hy_sample_workspace_bytes(ctypes.byref(cfg)))
+    """``cfg``: a ``_lib.HySampleTextConfig`` (``text_adapters`` 1: text-stream adapters in the dual blocks)."""
+    n = int(_lib.load().ftmi_hy_sample_text_workspace_bytes(ctypes.byref(cfg)))
     if n == 0:
         raise ValueError(f"hy_sample: {_lib.last_error()}")
     return n
 
 
 def hy_sample(cfg, weights, cols, x, temb_silu, enc, head_shift, head_onep, key_bias, rope_cos, rope_sin, sigmas, workspace=None) -> None:
-    """The whole denoising loop in ONE call (ftmi_hy_sample), in place on ``x`` / ``cols`` (as ``hy_sample_init`` wrote them).  temb_silu bf16 [steps, P B, D];
+    """The whole denoising loop in ONE call (ftmi_hy_sample_text), in place on ``x`` / ``cols`` (as ``hy_sample_init`` wrote them).  temb_silu bf16 [steps, P B, D];
     enc bf16 [steps, P B, T, D] (the refined text of every step, unconditional rows first); head_shift / head_onep bf16 [steps, P B, D]; key_bias fp32
     [P B, T + S] or None; rope_cos / rope_sin fp32 [S, 128]; sigmas fp32 [steps + 1] on the device.  ``workspace``: a uint8 GPU tensor of at least
-    ``hy_sample_workspace_bytes(cfg)`` (allocated when None).  ``cfg`` of type ``_lib.HySampleTextConfig``: the same loop through ftmi_hy_sample_text."""
-    text_cfg, cfg = (cfg, cfg.base) if isinstance(cfg, _lib.HySampleTextConfig) else (None, cfg)
+    ``hy_sample_workspace_bytes(cfg)`` (allocated when None).  ``cfg``: as for ``hy_sample_workspace_bytes``."""
+    text_cfg, cfg = cfg, cfg.base
     geo, n, D = cfg.geo, cfg.steps, cfg.D
     _cog_sample_buffers(geo, x, cols, "hy_sample")
     S, _ = _cog_sample_dims(geo)
@@ -1528,13 +1517,9 @@ def hy_sample(cfg, weights, cols, x, temb_silu, enc, head_shift, head_onep, key_
     for name, t, dt, shape in want:
         if t is None or not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
             raise ValueError(f"hy_sample: {name} must be a contiguous {dt} {shape} GPU tensor, got {None if t is None else tuple(t.shape)}")
-    need = hy_sample_workspace_bytes(text_cfg or cfg)
+    need = hy_sample_workspace_bytes(text_cfg)
     if workspace is None:
         workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
-    if text_cfg is not None:
-        check(_lib.load().ftmi_hy_sample_text(ctypes.byref(text_cfg), ctypes.byref(weights), ptr(cols), ptr(x), ptr(temb_silu), ptr(enc), ptr(head_shift), ptr(head_onep),
-                                              ptr(key_bias), ptr(rope_cos), ptr(rope_sin), ptr(sigmas), ptr(workspace), workspace.numel(), stream_ptr()),
-              "ftmi_hy_sample_text")
-        return
-    check(_lib.load().ftmi_hy_sample(ctypes.byref(cfg), ctypes.byref(weights), ptr(cols), ptr(x), ptr(temb_silu), ptr(enc), ptr(head_shift), ptr(head_onep),
-                                     ptr(key_bias), ptr(rope_cos), ptr(rope_sin), ptr(sigmas), ptr(workspace), workspace.numel(), stream_ptr()), "ftmi_hy_sample")
+    check(_lib.load().ftmi_hy_sample_text(ctypes.byref(text_cfg), ctypes.byref(weights), ptr(cols), ptr(x), ptr(temb_silu), ptr(enc), ptr(head_shift), ptr(head_onep),
+                                          ptr(key_bias), ptr(rope_cos), ptr(rope_sin), ptr(sigmas), ptr(workspace), workspace.numel(), stream_ptr()),
+          "ftmi_hy_sample_text")

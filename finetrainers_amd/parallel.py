@@ -6,7 +6,7 @@ PTD backend parallel/ptd.py:41-279: ``init_process_group("nccl")``, ``replicate(
 
   * the trainable state is ONE flat fp32 LoRA-gradient buffer (234.9 MB at r=64) laid out [A | B] with the layer axis leading, so
     the gradients of a contiguous block range are two contiguous slices.  The DiT backward runs in block ranges
-    (``ftmi_ltx_backward_range``) and ``GradBucketReducer`` all-reduces (AVG) the two slices of each finished range right away,
+    (``ftmi_ltx_ff_backward_range``) and ``GradBucketReducer`` all-reduces (AVG) the two slices of each finished range right away,
     asynchronously on RCCL's stream, while the earlier blocks still compute -- the role of the c10d reducer's 100 MB buckets
     without parameter hooks (default 7 blocks per bucket: 4 buckets of 2 x 29.4 MB; only the last one is exposed).  Averaging is
     folded into the collective (``ReduceOp.AVG`` on RCCL, SUM + scale on gloo);

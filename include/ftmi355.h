@@ -11,13 +11,13 @@
  *
  *   ftmi_attn_fwd / ftmi_attn_bwd ...... a provider function of finetrainers/models/attention_dispatch.py:405-447
  *                                        (contract :295-362; native provider :938-962) and its autograd backward
- *   ftmi_ltx_forward / ftmi_ltx_backward[_range] the transformer call inside LTXVideoModelSpecification.forward
+ *   ftmi_ltx_ff_forward / ftmi_ltx_ff_backward_range the transformer call inside LTXVideoModelSpecification.forward
  *                                        (finetrainers/models/ltx_video/base_specification.py:336-342), i.e.
  *                                        _patched_LTXVideoTransformer3D_forward (finetrainers/patches/models/
  *                                        ltx_video/patch.py:38-127) + loss.backward() through it
  *                                        (finetrainers/trainer/sft_trainer/trainer.py:481)
- *   ftmi_ltx_sample (+ _cfg_euler_step, _unpack_denorm) the denoising loop of the validation pipeline, latents only
- *   ftmi_ltx_forward_frames / ftmi_ltx_sample_cond        the same with one timestep per latent frame / the first latent frames held (image-to-video)
+ *   ftmi_ltx_ff_sample (+ ftmi_ltx_cfg_euler_step, _unpack_denorm) the denoising loop of the validation pipeline, latents only
+ *   ftmi_ltx_ff_forward_frames / ftmi_ltx_ff_sample_cond  the same with one timestep per latent frame / the first latent frames held (image-to-video)
  *                                        (finetrainers/models/ltx_video/base_specification.py:347-377)
  *   ftmi_ltx_noise_pack ................ normalise / noise / flow-match mix / pack / target of
  *                                        base_specification.py:295-320,343,427-459 + functional/diffusion.py:4-11
@@ -158,7 +158,7 @@ int ftmi_gemm_nt_plan(int M, int N, int K, int K2, int epilogue);
  *   ftmi_allreduce_bucket    : all-reduce (mean if average != 0, else sum) of count fp32 values IN PLACE, ordered after everything already queued on
  *                              compute_stream (event hand-over, no host sync), running on the communication stream: the caller goes on queueing the
  *                              backward of the earlier blocks while the bucket is on the wire.  Every rank must issue the same buckets in the same order
- *                              (the block-range schedule of ftmi_ltx_backward_range is a function of L alone).
+ *                              (the block-range schedule of ftmi_ltx_ff_backward_range is a function of L alone).
  *   ftmi_allreduce_wait      : compute_stream waits (device side) for every bucket issued so far -- call before clip + AdamW.
  * Thread-safe per handle (a mutex); no thread-local state. */
 typedef void* ftmi_exchange;
@@ -323,7 +323,7 @@ typedef struct {
     float eps_qk;     /* 1e-5 (norm_q / norm_k) */
     int gemm_variant; /* 8 = automatic tile / K-loop choice (production); other ids select one fixed kernel (A/B partners, gemm.hip) */
     /* 1 = gradient checkpointing (the reference's --gradient_checkpointing, trainer/sft_trainer/trainer.py:155-157 -> utils/activation_checkpoint.py:24-49,
-     * every block wrapped): the workspace holds ONE block's activations instead of L (ftmi_ltx_workspace_bytes shrinks accordingly), the forward keeps only
+     * every block wrapped): the workspace holds ONE block's activations instead of L (ftmi_ltx_ff_workspace_bytes shrinks accordingly), the forward keeps only
      * the residual stream, and the backward runs every block's forward kernels again right before its gradient kernels.  Gradients are bit-identical to
      * checkpoint = 0 (deterministic kernels).  Forward and backward of one step must use the same value. */
     int checkpoint;
@@ -370,46 +370,70 @@ typedef struct {
     const float *rope_cos, *rope_sin; /* fp32 [S, D/2]: one (cos, sin) per rotated pair */
 } ftmi_ltx_weights;
 
-size_t ftmi_ltx_workspace_bytes(const ftmi_ltx_config* cfg);
+/* What every entry that runs blocks takes: the structure above, then the feed-forward adapters.  The reference hands --target_modules to peft unchanged
+ * (trainer/sft_trainer/trainer.py:121-128), and its control trainer's default (trainer/control_trainer/config.py:60) names "...|ff.net.0.proj|ff.net.2": ten
+ * adapters per block at one rank r and scale s = alpha / r.
+ *   ff.net.0.proj  A1 [r, D], B1 [D_ff, r]:  z = n2 W1^T + b1 + (s n2 A1^T) B1^T and g = gelu(z) in one launch (K-extension under the GELU epilogue)
+ *   ff.net.2       A2 [r, D_ff], B2 [D, r]:  h_out = h2 + gate (g W2^T + b2 + (s g A2^T) B2^T)
+ * All eight operand pointers NULL = the eight attention adapters alone (or none, cfg->r == 0); some of them set, or any set with cfg->r == 0, is
+ * FTMI_ERR_INVALID and launches nothing (a planner returns 0). */
+typedef struct {
+    ftmi_ltx_weights base;
+    /* bf16 (hi, lo) working copies of the fp32 matrices (ftmi_lora_refresh_rect: one launch per family over the L blocks) */
+    const void* ff_a1_sp;   /* [L,2r,D]     A1 as (hi, lo) row planes:              operand of n2 A1^T       */
+    const void* ff_a1t_ext; /* [L,D,3r]     [A1^T_hi | A1^T_hi | A1^T_lo]:          K-extension of dn2       */
+    const void* ff_b1_ext;  /* [L,D_ff,3r]  [B1_hi | B1_hi | B1_lo]:                K-extension of z         */
+    const void* ff_b1t_sp;  /* [L,2r,D_ff]  B1^T as (hi, lo) row planes:            operand of dz B1         */
+    const void* ff_a2_sp;   /* [L,2r,D_ff]  A2 as (hi, lo) row planes:              operand of g A2^T        */
+    const void* ff_a2t_ext; /* [L,D_ff,3r]  [A2^T_hi | A2^T_hi | A2^T_lo]:          K-extension of dz        */
+    const void* ff_b2_ext;  /* [L,D,3r]     [B2_hi | B2_hi | B2_lo]:                K-extension of h_out     */
+    const void* ff_b2t_sp;  /* [L,2r,D]     B2^T as (hi, lo) row planes:            operand of dO B2         */
+} ftmi_ltx_ff_weights;
+
+/* Bytes of the workspace of ftmi_ltx_ff_forward / ftmi_ltx_ff_backward_range (0: a refused pointer set).  With the feed-forward adapters a block slot
+ * additionally keeps "xa_ff1" and "xa_ff2" ([B*S, 3r], the down-projected rows of the two adapters), the scratch two more [B*S, 3r] buffers. */
+size_t ftmi_ltx_ff_workspace_bytes(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w);
 /* Byte offset of a named activation inside the workspace (for tests / debugging): global names "hs" (residual
  * stream [L+1,B*S,D]; layer selects the slice), "e", "emb", "temb", "ada", "ada_out", "kv2_all" ([B*T, L*2D] text-side k|v of
  * every block), "k2n_all" ([B*T, L, D]), "xa_kv2_all"; per-block names "n1", "qkv", "qrot", "krot", "o1", "lse1", "xa_qkv",
- * "xa_o", "h1", "q2raw", "q2n", "o2", "lse2", "xa_q2", "xa_o2", "h2", "z". */
-int ftmi_ltx_workspace_offset(const ftmi_ltx_config* cfg, const char* name, int layer, size_t* offset);
+ * "xa_o", "h1", "q2raw", "q2n", "o2", "lse2", "xa_q2", "xa_o2", "h2", "z" and, with the feed-forward adapters only, "xa_ff1", "xa_ff2". */
+int ftmi_ltx_ff_workspace_offset(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, const char* name, int layer, size_t* offset);
 
-/* Forward of the DiT: x_t [B,S,C_in], text [B,T,D_cap], key_bias fp32 [B,T] ((1-mask) * -10000 as the reference
- * builds it), timestep fp32 [B] (= float(long(sigma*1000)), base_specification.py:320; one per sample) -> pred [B,S,C_out].
- * Activations needed by the backward are kept in ws. */
-int ftmi_ltx_forward(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const void* x_t, const void* text,
-                     const float* key_bias, const float* timestep, void* pred, void* ws, size_t ws_bytes, ftmi_stream stream);
+/* Forward of the DiT (the transformer call of LTXVideoModelSpecification.forward, models/ltx_video/base_specification.py:313-330): x_t [B,S,C_in],
+ * text [B,T,D_cap], key_bias fp32 [B,T] ((1-mask) * -10000 as the reference builds it), timestep fp32 [B] (= float(long(sigma*1000)),
+ * base_specification.py:320; one per sample) -> pred [B,S,C_out].  Activations needed by the backward are kept in ws. */
+int ftmi_ltx_ff_forward(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, const void* x_t, const void* text, const float* key_bias,
+                        const float* timestep, void* pred, void* ws, size_t ws_bytes, ftmi_stream stream);
 
 /* Forward with ONE TIMESTEP PER LATENT FRAME -- forward only.  The image-to-video mode of the reference's validation (finetrainers/models/ltx_video/
  * base_specification.py:360-361 switches to LTXImageToVideoPipeline when a validation row has an image; its training counterpart is the first-frame branch,
  * :282-311) feeds the model timestep 0 on the conditioning frame and t on the others; the oracle takes per-token timesteps as upstream does
- * (oracle/ltx.py:450-457).  Same arguments as ftmi_ltx_forward, except timesteps fp32 [B, frames] (device): the S / frames tokens of latent frame f of
+ * (oracle/ltx.py:450-457).  Same arguments as ftmi_ltx_ff_forward, except timesteps fp32 [B, frames] (device): the S / frames tokens of latent frame f of
  * sample b are modulated by the conditioning of timesteps[b * frames + f].  S % frames == 0 and B * frames <= 128 (8 model rows x 16 latent frames, a
  * 121-frame clip; B itself is not limited to 8 here); narrow geometries (d_valid / head_dim_valid) are refused.  With all timesteps of a sample equal the
- * result is ftmi_ltx_forward's, bit for bit.
+ * result is ftmi_ltx_ff_forward's, bit for bit.
  * NO BACKWARD MAY FOLLOW: cfg->checkpoint is ignored, the workspace is the checkpoint = 1 layout (one block slot + the residual stream) with conditioning
- * tables of B * frames rows -- ftmi_ltx_forward_frames_workspace_bytes(cfg, frames) -- and ftmi_ltx_backward* would read tables of another shape. */
-size_t ftmi_ltx_forward_frames_workspace_bytes(const ftmi_ltx_config* cfg, int frames);
-int ftmi_ltx_forward_frames(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const void* x_t, const void* text, const float* key_bias,
-                            const float* timesteps, int frames, void* pred, void* ws, size_t ws_bytes, ftmi_stream stream);
+ * tables of B * frames rows -- ftmi_ltx_ff_forward_frames_workspace_bytes(cfg, w, frames) -- and ftmi_ltx_ff_backward_range would read tables of another
+ * shape. */
+size_t ftmi_ltx_ff_forward_frames_workspace_bytes(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, int frames);
+int ftmi_ltx_ff_forward_frames(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, const void* x_t, const void* text, const float* key_bias,
+                               const float* timesteps, int frames, void* pred, void* ws, size_t ws_bytes, ftmi_stream stream);
 
-/* Backward: dpred [B,S,C_out] bf16 -> LoRA gradients ACCUMULATED (+=) into fp32 grad_a [L,8,r,D] and grad_b [L,8,D,r]. */
-int ftmi_ltx_backward(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const void* text, const float* key_bias,
-                      const void* dpred, float* grad_a, float* grad_b, void* ws, size_t ws_bytes, ftmi_stream stream);
-
-/* The same backward in pieces: blocks [l_lo, l_hi) in descending order (the tail first when l_hi == L).  Successive calls must tile
+/* Backward (loss.backward() of trainer/sft_trainer/trainer.py:481): dpred [B,S,C_out] bf16 -> LoRA gradients into fp32 grad_a [L,8,r,D], grad_b [L,8,D,r]
+ * and, with the feed-forward adapters (NULL without), grad_ff [L][A1 r*D | B1 D_ff*r | A2 r*D_ff | B2 D*r]: the four feed-forward gradients of a block
+ * adjacent, so those of a block range are ONE contiguous slice for the gradient exchange.
+ * In pieces: blocks [l_lo, l_hi) in descending order (the tail first when l_hi == L; l_hi = L, l_lo = 0 is the whole backward).  Successive calls must tile
  * L..0 (e.g. [21,28) [14,21) [7,14) [0,7)); the state between calls lives in ws.  When a call returns (stream order) the gradients of
- * all 8 adapters of exactly those blocks are final, so a data-parallel caller starts the all-reduce of grad_a[l_lo:l_hi] /
- * grad_b[l_lo:l_hi] on its communication stream while the next call computes -- the bucketed, overlapped gradient exchange of the
+ * all adapters of exactly those blocks are final, so a data-parallel caller starts the all-reduce of grad_a[l_lo:l_hi] /
+ * grad_b[l_lo:l_hi] / grad_ff[l_lo:l_hi] on its communication stream while the next call computes -- the bucketed, overlapped gradient exchange of the
  * reference's DDP (finetrainers/parallel/ptd.py:462-463: replicate(bucket_cap_mb=100)) without a reducer.
  * accumulate = 0: the whole gradient buffer is zeroed first (by the call with l_hi == L), i.e. ".grad was None";
- * accumulate = 1: gradients are added to the buffer's content (gradient accumulation). */
-int ftmi_ltx_backward_range(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const void* text, const float* key_bias,
-                            const void* dpred, float* grad_a, float* grad_b, void* ws, size_t ws_bytes, int l_hi, int l_lo,
-                            int accumulate, ftmi_stream stream);
+ * accumulate = 1: gradients are added to the buffer's content (gradient accumulation).
+ * n2 and g of the feed-forward adapters are recomputed per block (norm + modulate; ftmi_gelu_from_pre on the kept z) instead of being kept: 5.5 GB over 28
+ * blocks at B*S = 5376. */
+int ftmi_ltx_ff_backward_range(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, const void* text, const float* key_bias, const void* dpred,
+                               float* grad_a, float* grad_b, float* grad_ff, void* ws, size_t ws_bytes, int l_hi, int l_lo, int accumulate,
+                               ftmi_stream stream);
 
 /* latents, noise [B,C,F*H*W] bf16; mean,std fp32 [C]; sigma fp32 [B]; sigma_first fp32 [B] or NULL (first-frame
  * conditioning branch: tokens < first_frame_tokens use it) -> x_t, target [B,S,C] bf16.
@@ -444,83 +468,32 @@ int ftmi_ltx_unpack_denorm(const float* x, const float* mean, const float* std_,
 /* The whole denoising loop as ONE call with no host synchronisation.  cfg->B = number of videos; the model runs at batch 2 cfg->B (unconditional rows
  * first) or, with guidance == 1, at batch cfg->B on the conditional prompt alone (text_uncond / key_bias_uncond may then be NULL).  cfg->checkpoint is
  * ignored: nothing is kept for a backward, the workspace is the checkpoint = 1 layout (one block slot + the residual stream) at the model's batch plus
- * the sampler's own buffers -- ftmi_ltx_sample_workspace_bytes(cfg, guidance != 1).
- *   text_cond, text_uncond bf16 [B, T, D_cap]; key_bias_* fp32 [B, T] as for ftmi_ltx_forward (both NULL: no mask)
+ * the sampler's own buffers -- ftmi_ltx_ff_sample_workspace_bytes(cfg, w, guidance != 1).
+ *   text_cond, text_uncond bf16 [B, T, D_cap]; key_bias_* fp32 [B, T] as for ftmi_ltx_ff_forward (both NULL: no mask)
  *   x fp32 [B, S, C_in]: the initial noise in packed token order on entry, the final normalised latents on return (ftmi_ltx_unpack_denorm turns them
  *     into the VAE's input)
  *   sigmas fp32 [n_steps + 1] (device), timesteps fp32 [n_steps] (device): step i feeds the model timesteps[i] for every sample and moves x from
  *     sigmas[i] to sigmas[i + 1] with ftmi_ltx_cfg_euler_step.  The caller supplies both, so the timestep rounding convention is the caller's.
  * What depends on the prompt and the adapters only -- the caption projection and the text-side k|v of every block with its LoRA extension and norm_k2
- * -- runs once per call, not once per step; w->rope_cos / rope_sin are the caller's tables as for the forward.  The LoRA working copies in w are used
- * as they are (refresh them after an optimiser step); cfg->r == 0 samples the base model.  The result is, bit for bit, that of a loop over
- * ftmi_ltx_forward at batch 2B and ftmi_ltx_cfg_euler_step. */
-size_t ftmi_ltx_sample_workspace_bytes(const ftmi_ltx_config* cfg, int two_pass);
-int ftmi_ltx_sample(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const void* text_cond, const void* text_uncond, const float* key_bias_cond,
-                    const float* key_bias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, void* ws,
-                    size_t ws_bytes, ftmi_stream stream);
+ * -- runs once per call, not once per step; w->base.rope_cos / rope_sin are the caller's tables as for the forward.  The LoRA working copies in w are
+ * used as they are (refresh them after an optimiser step; the validation pipelines of base_specification.py:347-377 run the peft model as it is);
+ * cfg->r == 0 samples the base model.  The result is, bit for bit, that of a loop over ftmi_ltx_ff_forward at batch 2B and ftmi_ltx_cfg_euler_step. */
+size_t ftmi_ltx_ff_sample_workspace_bytes(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, int two_pass);
+int ftmi_ltx_ff_sample(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, const void* text_cond, const void* text_uncond, const float* key_bias_cond,
+                       const float* key_bias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, void* ws,
+                       size_t ws_bytes, ftmi_stream stream);
 
-/* Conditioned (image-to-video) sampling: ftmi_ltx_sample with the first cond_frames of the `frames` latent frames of every sample HELD.  Replaces the
+/* Conditioned (image-to-video) sampling: ftmi_ltx_ff_sample with the first cond_frames of the `frames` latent frames of every sample HELD.  Replaces the
  * denoising loop of the pipeline the reference's validation builds for a row with an image (base_specification.py:360-361); restates [upstream, unpinned]
  * LTXImageToVideoPipeline.__call__:
  *   - on entry the first cond_frames * (S / frames) tokens of every sample of x are the clean, normalised conditioning latents, the rest noise; the held
  *     tokens are never written: on return they are the input, bit for bit
  *   - the model sees timestep 0 on the held frames and timesteps[i] on the others (timestep * (1 - conditioning_mask)), through the per-frame conditioning
- *     of ftmi_ltx_forward_frames
+ *     of ftmi_ltx_ff_forward_frames
  *   - the guidance combine and the Euler update apply to the other tokens only (ftmi_ltx_cfg_euler_step_held)
- * S % frames == 0, C_in % 8 == 0, (model rows) * frames <= 128.  cond_frames == 0 computes the bits of ftmi_ltx_sample.  The timestep-0 conditioning row
+ * S % frames == 0, C_in % 8 == 0, (model rows) * frames <= 128.  cond_frames == 0 computes the bits of ftmi_ltx_ff_sample.  The timestep-0 conditioning row
  * is computed once per call, the embedding MLP runs on the one live timestep per step; the result is, bit for bit, that of a loop over
- * ftmi_ltx_forward_frames and ftmi_ltx_cfg_euler_step_held.  No host synchronisation.  Workspace: ftmi_ltx_sample_cond_workspace_bytes. */
-size_t ftmi_ltx_sample_cond_workspace_bytes(const ftmi_ltx_config* cfg, int two_pass, int frames);
-int ftmi_ltx_sample_cond(const ftmi_ltx_config* cfg, const ftmi_ltx_weights* w, const void* text_cond, const void* text_uncond, const float* key_bias_cond,
-                         const float* key_bias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, int frames,
-                         int cond_frames, void* ws, size_t ws_bytes, ftmi_stream stream);
-
-/* ---- LTX-Video feed-forward adapters: ff.net.0.proj and ff.net.2 of every block next to the eight attention adapters.  The reference hands --target_modules
- * to peft unchanged (trainer/sft_trainer/trainer.py:121-128), and its control trainer's default (trainer/control_trainer/config.py:60) names
- * "...|ff.net.0.proj|ff.net.2": ten adapters per block at one rank r and scale s = alpha / r.
- *   ff.net.0.proj  A1 [r, D], B1 [D_ff, r]:  z = n2 W1^T + b1 + (s n2 A1^T) B1^T and g = gelu(z) in one launch (K-extension under the GELU epilogue)
- *   ff.net.2       A2 [r, D_ff], B2 [D, r]:  h_out = h2 + gate (g W2^T + b2 + (s g A2^T) B2^T)
- * A name never changes size under its callers: ftmi_ltx_weights and every entry above keep their layout, the feed-forward operands travel in an extension
- * structure whose first member is the base, and the entries that run blocks have _ff twins -- thin wrappers over the same internal functions, of which the
- * entries above are the "no feed-forward adapters" case.  All eight operand pointers NULL = no feed-forward adapters (the twin then computes the bits of
- * its original); some of them set, or any set with cfg->r == 0, is FTMI_ERR_INVALID and launches nothing. */
-typedef struct {
-    ftmi_ltx_weights base;
-    /* bf16 (hi, lo) working copies of the fp32 matrices (ftmi_lora_refresh_rect: one launch per family over the L blocks) */
-    const void* ff_a1_sp;   /* [L,2r,D]     A1 as (hi, lo) row planes:              operand of n2 A1^T       */
-    const void* ff_a1t_ext; /* [L,D,3r]     [A1^T_hi | A1^T_hi | A1^T_lo]:          K-extension of dn2       */
-    const void* ff_b1_ext;  /* [L,D_ff,3r]  [B1_hi | B1_hi | B1_lo]:                K-extension of z         */
-    const void* ff_b1t_sp;  /* [L,2r,D_ff]  B1^T as (hi, lo) row planes:            operand of dz B1         */
-    const void* ff_a2_sp;   /* [L,2r,D_ff]  A2 as (hi, lo) row planes:              operand of g A2^T        */
-    const void* ff_a2t_ext; /* [L,D_ff,3r]  [A2^T_hi | A2^T_hi | A2^T_lo]:          K-extension of dz        */
-    const void* ff_b2_ext;  /* [L,D,3r]     [B2_hi | B2_hi | B2_lo]:                K-extension of h_out     */
-    const void* ff_b2t_sp;  /* [L,2r,D]     B2^T as (hi, lo) row planes:            operand of dO B2         */
-} ftmi_ltx_ff_weights;
-
-/* ftmi_ltx_workspace_bytes / _offset for the ten-adapter model (trainer/sft_trainer/trainer.py:121-128 with the control trainer's target_modules): a block slot
- * additionally keeps "xa_ff1" and "xa_ff2" ([B*S, 3r], the down-projected rows of the two adapters), the scratch two more [B*S, 3r] buffers. */
-size_t ftmi_ltx_ff_workspace_bytes(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w);
-int ftmi_ltx_ff_workspace_offset(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, const char* name, int layer, size_t* offset);
-/* ftmi_ltx_forward with the feed-forward adapters (the transformer call of LTXVideoModelSpecification.forward, models/ltx_video/base_specification.py:313-330,
- * on a peft model whose target_modules name ff.net.0.proj and ff.net.2). */
-int ftmi_ltx_ff_forward(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, const void* x_t, const void* text, const float* key_bias,
-                        const float* timestep, void* pred, void* ws, size_t ws_bytes, ftmi_stream stream);
-/* ftmi_ltx_forward_frames with the feed-forward adapters (validation of an image row, base_specification.py:360-361). */
-size_t ftmi_ltx_ff_forward_frames_workspace_bytes(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, int frames);
-int ftmi_ltx_ff_forward_frames(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, const void* x_t, const void* text, const float* key_bias,
-                               const float* timesteps, int frames, void* pred, void* ws, size_t ws_bytes, ftmi_stream stream);
-/* ftmi_ltx_backward_range with the feed-forward adapters (loss.backward() of trainer/sft_trainer/trainer.py:481 over the ten-adapter peft model).
- * grad_ff fp32 [L][A1 r*D | B1 D_ff*r | A2 r*D_ff | B2 D*r]: the four feed-forward gradients of a block adjacent, so those of a block range are ONE
- * contiguous slice for the gradient exchange; final for [l_lo, l_hi) when the call returns, zeroed with grad_a / grad_b when accumulate = 0.
- * n2 and g are recomputed per block (norm + modulate; ftmi_gelu_from_pre on the kept z) instead of being kept: 5.5 GB over 28 blocks at B*S = 5376. */
-int ftmi_ltx_ff_backward_range(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, const void* text, const float* key_bias, const void* dpred,
-                               float* grad_a, float* grad_b, float* grad_ff, void* ws, size_t ws_bytes, int l_hi, int l_lo, int accumulate,
-                               ftmi_stream stream);
-/* ftmi_ltx_sample / ftmi_ltx_sample_cond over the ten-adapter model (the validation pipelines of base_specification.py:347-377 run the peft model as it is). */
-size_t ftmi_ltx_ff_sample_workspace_bytes(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, int two_pass);
-int ftmi_ltx_ff_sample(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, const void* text_cond, const void* text_uncond, const float* key_bias_cond,
-                       const float* key_bias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps, float guidance, void* ws,
-                       size_t ws_bytes, ftmi_stream stream);
+ * ftmi_ltx_ff_forward_frames and ftmi_ltx_cfg_euler_step_held.  No host synchronisation.  Workspace: ftmi_ltx_ff_sample_cond_workspace_bytes. */
 size_t ftmi_ltx_ff_sample_cond_workspace_bytes(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, int two_pass, int frames);
 int ftmi_ltx_ff_sample_cond(const ftmi_ltx_config* cfg, const ftmi_ltx_ff_weights* w, const void* text_cond, const void* text_uncond,
                             const float* key_bias_cond, const float* key_bias_uncond, float* x, const float* sigmas, const float* timesteps, int n_steps,
@@ -1168,8 +1141,8 @@ int ftmi_hy_sample_finish(const ftmi_hy_sample_geometry* geo, const float* x, fl
  * upcast_count[l] entries belong to block l.  The block structures then point into the arena.  NULL: bf16 weights.
  * The caller supplies what does not depend on the state: temb_silu bf16 [steps, P B, D] = silu(conditioning vector), enc bf16 [steps, P B, T, D] (the refined
  * text depends on the timestep), head_shift / head_onep bf16 [steps, P B, D], key_bias fp32 [P B, T + S] (-inf on padded text keys) or NULL, the rotary tables
- * fp32 [S, 128], sigmas fp32 [steps + 1] on the device.  x / cols: in and out (ftmi_hy_sample_init wrote them).  Workspace: ftmi_hy_sample_workspace_bytes
- * (0 for a refused configuration); a smaller one is FTMI_ERR_INVALID. */
+ * fp32 [S, 128], sigmas fp32 [steps + 1] on the device.  x / cols: in and out (ftmi_hy_sample_init wrote them).  Workspace:
+ * ftmi_hy_sample_text_workspace_bytes (0 for a refused configuration); a smaller one is FTMI_ERR_INVALID. */
 typedef struct ftmi_hy_sample_upcast {
     const void* src;  /* fp8 e4m3fn [rows, cols] */
     int rows, cols;
@@ -1196,14 +1169,9 @@ typedef struct ftmi_hy_sample_weights {
     const void *proj_w, *proj_b;             /* bf16 [Kc, D], [Kc] */
     const void *ones, *zeros;                /* bf16 [D] of 1 and of 0 (the affine-free output norm) */
 } ftmi_hy_sample_weights;
-size_t ftmi_hy_sample_workspace_bytes(const ftmi_hy_sample_config* cfg);
-int ftmi_hy_sample(const ftmi_hy_sample_config* cfg, const ftmi_hy_sample_weights* w, void* cols, float* x, const void* temb_silu, const void* enc,
-                   const void* head_shift, const void* head_onep, const float* key_bias, const float* rope_cos, const float* rope_sin, const float* sigmas,
-                   void* workspace, size_t workspace_bytes, ftmi_stream stream);
-/* The same loop over a model whose dual-stream blocks carry the text stream's adapters as well: `base` as above, text_adapters as in ftmi_hy_dual_config (1: every
- * dual block's lora_a / lora_b hold 8 matrices; needs base.r > 0; other values than 0 / 1 are FTMI_ERR_INVALID, a workspace size of 0).  The flag is handed to every
- * ftmi_hy_dual_forward of the walk and the workspace follows that block's layout.  text_adapters = 0 is ftmi_hy_sample: the same workspace, launches and bits.
- * (ftmi_hy_sample_config keeps its size: the extension is a structure of its own, like ftmi_wan_lora_ffn_block_config over ftmi_wan_block_config: a name never changes size under its callers.) */
+/* What the loop takes: `base` as above, then text_adapters as in ftmi_hy_dual_config (0: the video stream's adapters alone; 1: every dual block's lora_a /
+ * lora_b hold 8 matrices, the text stream's adapters as well; needs base.r > 0; other values than 0 / 1 are FTMI_ERR_INVALID, a workspace size of 0).  The flag
+ * is handed to every ftmi_hy_dual_forward of the walk and the workspace follows that block's layout. */
 typedef struct ftmi_hy_sample_text_config {
     ftmi_hy_sample_config base;
     int text_adapters;        /* 0 or 1 */

@@ -67,8 +67,9 @@ def test_gradient_checkpointing_gives_the_same_gradients_from_one_block_slot():
     ga0, gb0 = _grads(spec, model, cond, latd, sig, noise)
     pred0, _, _ = spec.forward(transformer=model, condition_model_conditions=dict(cond), latent_model_conditions=dict(latd), sigmas=sig, noise=noise,
                                force_first_frame_branch=False)
-    full = _lib.load().ftmi_ltx_workspace_bytes(ctypes.byref(model._c_config(2, 2688, 128)))  # (sized at config 2's token count; this model has 5 blocks)
-    one = _lib.load().ftmi_ltx_workspace_bytes(ctypes.byref(model._c_config(2, 2688, 128, checkpoint=True)))
+    none = ctypes.byref(_lib.LtxFfWeights())  # (no feed-forward adapters; a planner never dereferences the weights)
+    full = _lib.load().ftmi_ltx_ff_workspace_bytes(ctypes.byref(model._c_config(2, 2688, 128)), none)  # (sized at config 2's token count; this model has 5 blocks)
+    one = _lib.load().ftmi_ltx_ff_workspace_bytes(ctypes.byref(model._c_config(2, 2688, 128, checkpoint=True)), none)
     print(f"[ckpt] workspace at 2 x 2688 tokens, 5 blocks: {full / 2**30:.2f} GiB kept, {one / 2**30:.2f} GiB checkpointed")
     assert one < 0.5 * full, (one, full)  # 5 block slots -> 1 (the rest: the residual stream, the all-block text-side arrays, the backward's scratch)
     model.enable_gradient_checkpointing()
@@ -124,7 +125,7 @@ def test_fused_down_projection_launch_gives_the_bits_of_the_two_launches():
 
 
 def test_block_range_backward_matches_single_call():
-    """ftmi_ltx_backward_range over [3,5) [1,3) [0,1) == one ftmi_ltx_backward over [0,5): same gradients (fp32 atomics order aside),
+    """ftmi_ltx_ff_backward_range over [3,5) [1,3) [0,1) == one call over [0,5): same gradients (fp32 atomics order aside),
     ranges reported in backward order, each exactly once."""
     spec, model, cond, latd, sig, noise = _model_and_batch(5, 2, 2, 4, 6)
     ga0, gb0 = _grads(spec, model, cond, latd, sig, noise)

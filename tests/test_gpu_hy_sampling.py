@@ -314,7 +314,7 @@ CASES = [("lora", 1, False, 1.0), ("lora", 2, True, 3.0), ("lora", 1, True, 3.0)
 
 @pytest.mark.parametrize("kind,B,masked,true_cfg", CASES)
 def test_one_call_loop_is_its_composition_bit_for_bit(models, kind, B, masked, true_cfg):
-    """ftmi_hy_sample against model.forward + ops.hy_sample_step on the same model: state and output bit for bit.  "lora": 2 dual + 3 single blocks with
+    """ftmi_hy_sample_text against model.forward + ops.hy_sample_step on the same model: state and output bit for bit.  "lora": 2 dual + 3 single blocks with
     adapters of rank 64; "plain": no adapters; "single": (Ld, Ls) = (0, 1); "fp8": apply_layerwise_casting() with real fp8 storage."""
     model = models[kind]
     d = _inputs(B, masked)
@@ -355,7 +355,7 @@ def test_public_sample_is_the_one_call_and_sees_the_adapters_as_they_are(models)
 # ---- 6. trajectory ---------------------------------------------------------------------------------------------------------------------------------------------------
 def test_trajectory_against_the_oracle(models):
     """The loop of tests/hy_sampling_reference.py over ``oracle.hunyuan``'s model in bf16 with the state rounded to bf16 after every step, as upstream keeps
-    it, over an fp32 copy of the same weights, and ``ftmi_hy_sample``: d_kernel = rel_l2(kernels, fp32) may not exceed 1.5 d_oracle = 1.5 rel_l2(bf16, fp32),
+    it, over an fp32 copy of the same weights, and ``ftmi_hy_sample_text``: d_kernel = rel_l2(kernels, fp32) may not exceed 1.5 d_oracle = 1.5 rel_l2(bf16, fp32),
     the factor of the LTX, Wan and CogVideoX trajectory tests against the same kind of yardstick.  The state must have moved by more than 0.1 relative, so
     that a loop that does nothing fails.  The embedded guidance is bf16(6000) = 6016 in all three.
     Measured on an MI355X: d_oracle 3.862e-3, d_kernel 2.290e-3, the state moved by 0.579."""

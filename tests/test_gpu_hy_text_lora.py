@@ -452,7 +452,7 @@ GRID, T_S, N_STEPS, C = (3, 8, 12), 8, 2, 16  # the smallest geometry of tests/t
 
 
 def _sample_both_ways(model, B=2, g_cfg=3.0):
-    """(ftmi_hy_sample, model.forward + ops.hy_sample_step) on the same model: the final states."""
+    """(ftmi_hy_sample_text, model.forward + ops.hy_sample_step) on the same model: the final states."""
     import hy_sampling_reference as ref
 
     from finetrainers_amd import _lib, ops
@@ -493,7 +493,7 @@ def _sample_both_ways(model, B=2, g_cfg=3.0):
 
 
 def test_one_call_sampling_with_text_adapters_is_its_composition_and_sees_them():
-    """Two denoising steps with an eight-adapter model (non-zero lora_B): ``ftmi_hy_sample`` is ``model.forward`` + ``ops.hy_sample_step`` bit for bit, and the
+    """Two denoising steps with an eight-adapter model (non-zero lora_B): ``ftmi_hy_sample_text`` is ``model.forward`` + ``ops.hy_sample_step`` bit for bit, and the
     result depends on the text adapters; a model whose dual blocks disagree about them is refused."""
     from finetrainers_amd.hunyuan_video import MI355XHunyuanVideoLatentSampler
 

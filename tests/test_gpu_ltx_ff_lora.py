@@ -1,6 +1,6 @@
 """LTX-Video feed-forward adapters (ff.net.0.proj, ff.net.2) on the MI355X: the gelu_from_pre kernel against fp64 and against the GELU GEMM's own bits, the
 ten-adapter block stack against the CPU oracle (tests/ltx_ff_lora_reference.py) with the yardstick measured inside the test, exact zeros, the backward's
-schedules against each other, the fused step and its DCP training state, the sampler, and the refusals of the _ff entries.  Run on the MI355X box: pytest -m gpu.
+schedules against each other, the fused step and its DCP training state, the sampler, and the refusals of the ftmi_ltx_ff_* entries.  Run on the MI355X box: pytest -m gpu.
 
 Geometry: the suite's smallest LTX case -- 2 blocks, B = 2, F x H x W = 3 x 4 x 6, i.e. M = 144 token rows (no multiple of 64: the K = 8192 down-projection
 and the TN launches see a ragged row tile), text masks of 32 and 96 valid keys."""
@@ -627,11 +627,11 @@ def test_ff_entries_refuse_before_any_launch(rank64):
     rc, untouched = forward(c0, good, ws_bytes)
     assert rc in refusals and untouched
     # a workspace sized for the eight
-    eight_bytes = lib.ftmi_ltx_workspace_bytes(ctypes.byref(cfg))
+    eight_bytes = lib.ftmi_ltx_ff_workspace_bytes(ctypes.byref(cfg), ctypes.byref(variant(**{n: None for n in _lib.LTX_FF_WEIGHT_FIELDS})))
     assert eight_bytes < ws_bytes
     rc, untouched = forward(cfg, good, eight_bytes)
     assert rc in refusals and untouched
-    # the backward and the sampler twins refuse the same way
+    # the backward and the sampler refuse the same way
     ga = torch.zeros(gmodel.lora_flat.numel(), device=dev)
     dpred = torch.zeros((B, S, 128), dtype=bf16, device=dev)
     n_a, n_b = gmodel._lora_A_full.numel(), gmodel._lora_B_full.numel()

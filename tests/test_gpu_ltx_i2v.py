@@ -171,7 +171,7 @@ def _bias(mask):
 # ---------------------------------------------------------------------------------------------------------------- c. uniform timesteps
 def test_forward_frames_with_uniform_timesteps_is_the_forward_bit_for_bit(two_blocks):
     """2 blocks, production width, rank 64 with non-zero B, 2 samples x 2 688 tokens: all 7 frame timesteps of a sample equal (and different between the
-    samples) -> the bits of ftmi_ltx_forward, through the C entry and through the module's ``frame_timestep`` keyword."""
+    samples) -> the bits of ftmi_ltx_ff_forward, through the C entry and through the module's ``frame_timestep`` keyword."""
     from finetrainers_amd import _lib, ops
     from finetrainers_amd._lib import check, ptr, stream_ptr
 
@@ -188,11 +188,11 @@ def test_forward_frames_with_uniform_timesteps_is_the_forward_bit_for_bit(two_bl
     model.refresh_lora_copies()
     weights = model._c_weights(cos, sin)
     cfg = model._c_config(B, S, T2, checkpoint=False)
-    ws_bytes = lib.ftmi_ltx_workspace_bytes(ctypes.byref(cfg))
+    ws_bytes = lib.ftmi_ltx_ff_workspace_bytes(ctypes.byref(cfg), ctypes.byref(weights))
     ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
     want = torch.empty((B, S, 128), dtype=bf16, device=dev)
-    check(lib.ftmi_ltx_forward(ctypes.byref(cfg), ctypes.byref(weights), ptr(x_t), ptr(text), ptr(kb), ptr(tv), ptr(want), ptr(ws), ws_bytes, stream_ptr()),
-          "ftmi_ltx_forward")
+    check(lib.ftmi_ltx_ff_forward(ctypes.byref(cfg), ctypes.byref(weights), ptr(x_t), ptr(text), ptr(kb), ptr(tv), ptr(want), ptr(ws), ws_bytes, stream_ptr()),
+          "ftmi_ltx_ff_forward")
     del ws
     got = ops.ltx_forward_frames(cfg, weights, x_t, text, kb, tv.view(B, 1).expand(B, F2).contiguous())
     torch.cuda.synchronize()
@@ -299,7 +299,7 @@ def _cond_inputs(B, k, seed=11):
 
 
 def _composition_cond(model, text_c, text_u, kb_c, kb_u, x0, sigmas, timesteps, guidance, k):
-    """The loop in Python over ftmi_ltx_forward_frames (the model's batch in one call) + ftmi_ltx_cfg_euler_step_held."""
+    """The loop in Python over ftmi_ltx_ff_forward_frames (the model's batch in one call) + ftmi_ltx_cfg_euler_step_held."""
     from finetrainers_amd import ops
 
     B, S, C = x0.shape
@@ -350,8 +350,8 @@ def _unhoisted(fn):
 
 
 def test_sample_cond_is_the_composition_bit_for_bit(two_blocks):
-    """2 blocks, config-2 width, S = 7 x 384, T = 128, rank 64, 3 steps: ftmi_ltx_sample_cond (timestep-0 row hoisted, one live embedding row per step)
-    against the Python loop over ftmi_ltx_forward_frames + ftmi_ltx_cfg_euler_step_held -- every bit of the final state, hoisting on and off; the held
+    """2 blocks, config-2 width, S = 7 x 384, T = 128, rank 64, 3 steps: ftmi_ltx_ff_sample_cond (timestep-0 row hoisted, one live embedding row per step)
+    against the Python loop over ftmi_ltx_ff_forward_frames + ftmi_ltx_cfg_euler_step_held -- every bit of the final state, hoisting on and off; the held
     frames of x are the input, bit for bit."""
     _, model = two_blocks
     for B, k, guidance, seed in ((1, 1, 3.0, 11), (2, 2, 3.0, 21), (1, 1, 1.0, 31)):
@@ -391,7 +391,7 @@ def test_sample_cond_with_nothing_held_is_sample_bit_for_bit(two_blocks):
 
 def test_sample_cond_trajectory_vs_oracle():
     """4 steps, g = 3, 2 blocks, 1 video of 3 x 8 x 10 tokens, the first latent frame held: the oracle (bf16, CPU; timestep 0 on the held tokens,
-    per-token timesteps) driven by the torch loop of tests/test_ltx_i2v_host.py against ftmi_ltx_sample_cond on the same prompt embeddings, initial
+    per-token timesteps) driven by the torch loop of tests/test_ltx_i2v_host.py against ftmi_ltx_ff_sample_cond on the same prompt embeddings, initial
     state and sigmas.  Yardstick measured here as in test_sample_trajectory_vs_oracle: the oracle loop against itself under
     accumulation_order_variant(512); kernel-vs-oracle may be at most 2 x that.
 

@@ -151,7 +151,7 @@ def _bias(mask):
 
 
 def _composition(model, text_c, text_u, kb_c, kb_u, x0, sigmas, timesteps, guidance, F_, H_, W_):
-    """The loop in Python over the EXISTING ftmi_ltx_forward (checkpoint = 0, the model's batch in one call) + ftmi_ltx_cfg_euler_step."""
+    """The loop in Python over the training forward, ftmi_ltx_ff_forward (checkpoint = 0, the model's batch in one call) + ftmi_ltx_cfg_euler_step."""
     from finetrainers_amd import _lib, ops
     from finetrainers_amd._lib import check, ptr, stream_ptr
 
@@ -166,15 +166,15 @@ def _composition(model, text_c, text_u, kb_c, kb_u, x0, sigmas, timesteps, guida
     model.refresh_lora_copies()
     cfg = model._c_config(nb, S, text.shape[1], checkpoint=False)
     weights = model._c_weights(cos, sin)
-    ws_bytes = lib.ftmi_ltx_workspace_bytes(ctypes.byref(cfg))
+    ws_bytes = lib.ftmi_ltx_ff_workspace_bytes(ctypes.byref(cfg), ctypes.byref(weights))
     ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
     x = x0.clone()
     xin = torch.cat([x.to(bf16)] * (2 if two else 1)).contiguous()
     pred = torch.empty((nb, S, C), dtype=bf16, device=dev)
     for i in range(timesteps.numel()):
         tv = timesteps[i].expand(nb).contiguous()
-        check(lib.ftmi_ltx_forward(ctypes.byref(cfg), ctypes.byref(weights), ptr(xin), ptr(text), ptr(kb), ptr(tv), ptr(pred), ptr(ws), ws_bytes,
-                                   stream_ptr()), "ftmi_ltx_forward")
+        check(lib.ftmi_ltx_ff_forward(ctypes.byref(cfg), ctypes.byref(weights), ptr(xin), ptr(text), ptr(kb), ptr(tv), ptr(pred), ptr(ws), ws_bytes,
+                                      stream_ptr()), "ftmi_ltx_ff_forward")
         xin = ops.ltx_cfg_euler_step(pred, x, sigmas[i].expand(B).contiguous(), sigmas[i + 1].expand(B).contiguous(), guidance)
     torch.cuda.synchronize()
     return x
@@ -213,8 +213,8 @@ def _loop_inputs(B, seed=11):
 
 
 def test_sample_is_the_composition_bit_for_bit(two_blocks):
-    """2 blocks, config-2 width, S = 2 688, T = 128, rank 64 with non-zero B, 3 steps, g = 3: ftmi_ltx_sample (forward-only workspace, text-side work
-    hoisted out of the step loop) against the Python loop over ftmi_ltx_forward + ftmi_ltx_cfg_euler_step -- every bit of the final state."""
+    """2 blocks, config-2 width, S = 2 688, T = 128, rank 64 with non-zero B, 3 steps, g = 3: ftmi_ltx_ff_sample (forward-only workspace, text-side work
+    hoisted out of the step loop) against the Python loop over ftmi_ltx_ff_forward + ftmi_ltx_cfg_euler_step -- every bit of the final state."""
     _, model = two_blocks
     args = _loop_inputs(1)
     want = _composition(model, *args, 3.0, F2, H2, W2)
@@ -249,9 +249,10 @@ def test_guidance_one_runs_the_conditional_rows_only(two_blocks):
     text_c, text_u, kb_c, kb_u, x0, sigmas, timesteps = _loop_inputs(1, seed=31)
     S = x0.shape[1]
     cfg = model._c_config(1, S, T2)
+    none = _lib.LtxFfWeights()  # (this model has no feed-forward adapters; a planner never dereferences the weights)
     one, two = ops.ltx_sample_workspace_bytes(cfg, False), ops.ltx_sample_workspace_bytes(cfg, True)
-    ref1 = lib.ftmi_ltx_workspace_bytes(ctypes.byref(model._c_config(1, S, T2, checkpoint=True)))
-    ref2 = lib.ftmi_ltx_workspace_bytes(ctypes.byref(model._c_config(2, S, T2, checkpoint=True)))
+    ref1 = lib.ftmi_ltx_ff_workspace_bytes(ctypes.byref(model._c_config(1, S, T2, checkpoint=True)), ctypes.byref(none))
+    ref2 = lib.ftmi_ltx_ff_workspace_bytes(ctypes.byref(model._c_config(2, S, T2, checkpoint=True)), ctypes.byref(none))
     assert ref1 <= one <= 1.05 * ref1 and ref2 <= two <= 1.05 * ref2 and one < 0.6 * two
 
     want = _composition(model, text_c, None, kb_c, None, x0, sigmas, timesteps, 1.0, F2, H2, W2)
@@ -274,7 +275,7 @@ def test_guidance_one_runs_the_conditional_rows_only(two_blocks):
 # ---------------------------------------------------------------------------------------------------------------- d. oracle parity over a trajectory
 def test_sample_trajectory_vs_oracle():
     """4 steps, g = 3, 2 blocks, 240 video tokens: the oracle (bf16, CPU) driven by the torch loop of tests/test_ltx_sampling_host.py against
-    ftmi_ltx_sample on the same prompt embeddings, noise and sigmas.  bf16 errors compound over steps, so the yardstick is measured here: the oracle
+    ftmi_ltx_ff_sample on the same prompt embeddings, noise and sigmas.  bf16 errors compound over steps, so the yardstick is measured here: the oracle
     against itself under accumulation_order_variant, and kernel-vs-oracle may be at most 2 x that (the headroom of the full-depth
     parity test: 2.0e-3 claimed over 1.17e-3 self-distance).
 

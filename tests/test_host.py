@@ -48,14 +48,15 @@ def test_c_abi_error_reporting(lib):
 
     cfg = _lib.LtxConfig(B=2, S=2688, T=128, D=2048, H=32, L=28, C_in=128, C_out=128, D_ff=8192, D_cap=4096, r=64, lora_scale=1.0,
                          eps_norm=1e-6, eps_qk=1e-5, gemm_variant=8)
-    ws = lib.ftmi_ltx_workspace_bytes(ctypes.byref(cfg))
+    w = ctypes.byref(_lib.LtxFfWeights())  # (no feed-forward adapters; a planner never dereferences the weights)
+    ws = lib.ftmi_ltx_ff_workspace_bytes(ctypes.byref(cfg), w)
     assert 8 * 2**30 < ws < 16 * 2**30  # ~10.4 GB of activations at the headline shape
     off = ctypes.c_size_t(0)
-    assert lib.ftmi_ltx_workspace_offset(ctypes.byref(cfg), b"qkv", 3, ctypes.byref(off)) == 0 and 0 < off.value < ws
-    rc = lib.ftmi_ltx_workspace_offset(ctypes.byref(cfg), b"no_such_tensor", 0, ctypes.byref(off))
+    assert lib.ftmi_ltx_ff_workspace_offset(ctypes.byref(cfg), w, b"qkv", 3, ctypes.byref(off)) == 0 and 0 < off.value < ws
+    rc = lib.ftmi_ltx_ff_workspace_offset(ctypes.byref(cfg), w, b"no_such_tensor", 0, ctypes.byref(off))
     assert rc == _lib.FTMI_ERR_INVALID and "unknown name" in _lib.last_error()
     with pytest.raises(ValueError):
-        _lib.check(rc, "ftmi_ltx_workspace_offset")
+        _lib.check(rc, "ftmi_ltx_ff_workspace_offset")
     # NULL tensors are rejected before any launch
     rc = lib.ftmi_gemm_nt(128, 128, 64, None, 64, None, 64, None, 1.0, None, 128, 0, None, None, None, 0, None, 0, 0, None)
     assert rc == _lib.FTMI_ERR_INVALID

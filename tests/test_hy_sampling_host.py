@@ -13,7 +13,7 @@ import hy_sampling_reference as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 bf16 = torch.bfloat16
-NEW_SYMBOLS = ("ftmi_hy_sample_init", "ftmi_hy_sample_step", "ftmi_hy_sample_finish", "ftmi_hy_sample_workspace_bytes", "ftmi_hy_sample")
+NEW_SYMBOLS = ("ftmi_hy_sample_init", "ftmi_hy_sample_step", "ftmi_hy_sample_finish", "ftmi_hy_sample_text_workspace_bytes", "ftmi_hy_sample_text")
 
 
 # ---- the schedule ------------------------------------------------------------------------------------------------------------------------------------------------
@@ -169,6 +169,9 @@ def test_c_abi_declares_exports_and_binds_the_sampling_symbols():
     declared = set(re.findall(r"\b(ftmi_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", header, flags=re.S)))
     for name in NEW_SYMBOLS:
         assert name in declared and name in _lib.EXPORTED_SYMBOLS and getattr(lib, name) is not None, name
+    import hy_sample_bytes
+
+    hy_sample_bytes.assert_only_the_text_entries(lib, declared, set(_lib.EXPORTED_SYMBOLS))  # the pair over the bare ftmi_hy_sample_config is gone
     assert ctypes.sizeof(_lib.HySampleGeometry) == 32 and ctypes.sizeof(_lib.HySampleUpcast) == 24
     assert ctypes.sizeof(_lib.HySampleConfig) == 32 + 12 * 4 and ctypes.sizeof(_lib.HySampleWeights) == 11 * 8
 
@@ -202,13 +205,13 @@ def test_layout_kernels_check_their_arguments_before_any_launch():
 
 
 def _cfg(Ld=2, Ls=3, true_cfg=1.0, **kw):
-    """The small model of tests/test_gpu_hunyuan.py on the (3, 8, 12) grid: 72 video tokens, 8 text tokens."""
+    """The small model of tests/test_gpu_hunyuan.py on the (3, 8, 12) grid: 72 video tokens, 8 text tokens (as the C entries take it: text_adapters = 0)."""
     from finetrainers_amd import _lib
 
     base = dict(geo=_geo(P=2 if true_cfg != 1.0 else 1), T=8, D=256, H=2, mlp=1024, Ld=Ld, Ls=Ls, r=64, lora_scale=1.0, eps=1e-6, gemm_variant=8, steps=4,
                 true_cfg=true_cfg)
     base.update(kw)
-    return _lib.HySampleConfig(**base)
+    return _lib.HySampleTextConfig(base=_lib.HySampleConfig(**base), text_adapters=0)
 
 
 def _training_saved_bytes(Ld, Ls, B=1):
@@ -229,7 +232,7 @@ def test_workspace_plan_is_forward_only():
     from finetrainers_amd import _lib
 
     lib = _lib.load()
-    ws = lambda **kw: lib.ftmi_hy_sample_workspace_bytes(ctypes.byref(_cfg(**kw)))
+    ws = lambda **kw: lib.ftmi_hy_sample_text_workspace_bytes(ctypes.byref(_cfg(**kw)))
     assert ws(Ld=1, Ls=1) > 0 and ws(Ld=1, Ls=1) == ws(Ld=20, Ls=40) == ws(Ld=2, Ls=3) == ws(Ld=0, Ls=1) == ws(Ld=1, Ls=0)
     for Ld, Ls in ((1, 1), (1, 2), (2, 1), (0, 4)):
         assert ws() >= _training_saved_bytes(Ld, Ls), "fewer blocks keep less than the plan"
@@ -251,10 +254,10 @@ def test_sample_refuses_a_small_workspace_and_missing_weights():
 
     lib = _lib.load()
     cfg = _cfg()
-    need = lib.ftmi_hy_sample_workspace_bytes(ctypes.byref(cfg))
+    need = lib.ftmi_hy_sample_text_workspace_bytes(ctypes.byref(cfg))
     p = ctypes.c_void_p(256)
     w = _lib.HySampleWeights()
-    call = lambda nbytes, ws=p, w=w: lib.ftmi_hy_sample(ctypes.byref(cfg), ctypes.byref(w), p, p, p, p, p, p, None, p, p, p, ws, nbytes, None)
+    call = lambda nbytes, ws=p, w=w: lib.ftmi_hy_sample_text(ctypes.byref(cfg), ctypes.byref(w), p, p, p, p, p, p, None, p, p, p, ws, nbytes, None)
     assert call(need - 1) == _lib.FTMI_ERR_INVALID and "workspace too small" in _lib.last_error()
     assert call(need, ctypes.c_void_p(264)) == _lib.FTMI_ERR_INVALID and "256-byte aligned" in _lib.last_error()
     assert call(need) == _lib.FTMI_ERR_INVALID and "weights missing" in _lib.last_error()
@@ -266,5 +269,5 @@ def test_sample_refuses_a_small_workspace_and_missing_weights():
     ups = (_lib.HySampleUpcast * 1)()
     w.upcasts = ctypes.cast(ups, ctypes.POINTER(_lib.HySampleUpcast))
     assert call(need) == _lib.FTMI_ERR_INVALID and "counts and the arena" in _lib.last_error()
-    assert lib.ftmi_hy_sample(ctypes.byref(cfg), ctypes.byref(w), None, p, p, p, p, p, None, p, p, p, p, need, None) == _lib.FTMI_ERR_INVALID
-    assert lib.ftmi_hy_sample(ctypes.byref(cfg), ctypes.byref(w), p, p, p, p, p, p, None, p, p, None, p, need, None) == _lib.FTMI_ERR_INVALID
+    assert lib.ftmi_hy_sample_text(ctypes.byref(cfg), ctypes.byref(w), None, p, p, p, p, p, None, p, p, p, p, need, None) == _lib.FTMI_ERR_INVALID
+    assert lib.ftmi_hy_sample_text(ctypes.byref(cfg), ctypes.byref(w), p, p, p, p, p, p, None, p, p, None, p, need, None) == _lib.FTMI_ERR_INVALID

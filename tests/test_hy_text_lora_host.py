@@ -240,17 +240,22 @@ def _sample_cfg(**kw):
     base = dict(geo=geo, T=8, D=256, H=2, mlp=1024, Ld=2, Ls=1, r=64, lora_scale=1.0, eps=1e-6, gemm_variant=8, steps=2, true_cfg=1.0)
     text = kw.pop("text_adapters", None)
     base.update(kw)
-    cfg = _lib.HySampleConfig(**base)
-    return cfg if text is None else _lib.HySampleTextConfig(base=cfg, text_adapters=text)
+    cfg = _lib.HySampleTextConfig(base=_lib.HySampleConfig(**base))
+    if text is not None:
+        cfg.text_adapters = text
+    return cfg
 
 
 def test_sample_workspace_follows_the_dual_layout_and_refuses_bad_flags():
     from finetrainers_amd import _lib
 
     lib = _lib.load()
-    ws = lambda cfg: (lib.ftmi_hy_sample_text_workspace_bytes if isinstance(cfg, _lib.HySampleTextConfig) else lib.ftmi_hy_sample_workspace_bytes)(ctypes.byref(cfg))
+    import hy_sample_bytes
+
+    ws = lambda cfg: lib.ftmi_hy_sample_text_workspace_bytes(ctypes.byref(cfg))
     off, explicit, on = ws(_sample_cfg()), ws(_sample_cfg(text_adapters=0)), ws(_sample_cfg(text_adapters=1))
-    assert off == explicit > 0
+    # the field left at its default, the field set to 0, and what the planner over the bare ftmi_hy_sample_config returned before it went
+    assert off == explicit == hy_sample_bytes.recorded()[(1, 3, 8, 12, 1, 8, 2, 1, 64, 2, 1, 0)] > 0
     d0 = _dual_bytes(_dual_cfg(T=8, S=72))
     d1 = _dual_bytes(_dual_cfg(T=8, S=72, text_adapters=1))
     single = _lib.HySingleConfig(B=1, T=8, S=72, D=256, H=2, mlp=1024, r=64, lora_scale=1.0, eps=1e-6, gemm_variant=8)
@@ -266,3 +271,15 @@ def test_sample_workspace_follows_the_dual_layout_and_refuses_bad_flags():
         p = ctypes.addressof(buf)
         rc = lib.ftmi_hy_sample_text(ctypes.byref(cfg), ctypes.byref(w), p, p, p, p, p, p, None, p, p, p, p, 1 << 40, None)
         assert rc == _lib.FTMI_ERR_INVALID and "text_adapters" in _lib.last_error()
+
+
+def test_the_sample_planner_reproduces_every_recorded_row():
+    """Every row recorded at the parent of the fold through ftmi_hy_sample_workspace_bytes (text_adapters = 0, where the two planners agreed) and through
+    ftmi_hy_sample_text_workspace_bytes, the refused ones (text_adapters = 1 with r = 0, text_adapters = 2) as 0."""
+    import hy_sample_bytes
+
+    plans = hy_sample_bytes.recorded()
+    assert {k[11] for k in plans} == {0, 1, 2} and any(v > 0 for k, v in plans.items() if k[11] == 1)
+    assert all(v == 0 for k, v in plans.items() if k[11] == 2 or (k[11] == 1 and k[8] == 0)) and all(v > 0 for k, v in plans.items() if k[11] == 0)
+    for key, want in plans.items():
+        assert hy_sample_bytes.planned(*key) == want, (key, want)

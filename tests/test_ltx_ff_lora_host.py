@@ -1,5 +1,6 @@
 """LTX-Video feed-forward adapters, host side (no GPU): the ``target_modules`` selection table, the four new parameters and the [A | B | FF] flat layout, the peft
-state dict and its safetensors round trip, the C ABI of the ``_ff`` entries against include/ftmi355.h, and the refusal on the narrow geometry."""
+state dict and its safetensors round trip, the C ABI of the ``ftmi_ltx_ff_*`` entries (the only LTX entries that run blocks) against include/ftmi355.h and the
+byte plans recorded when the narrow family still stood beside them (tests/ltx_entry_bytes.py), and the refusal on the narrow geometry."""
 import ctypes
 import json
 import math
@@ -115,7 +116,9 @@ def test_the_eight_adapter_model_is_what_it_was():
     assert set(dict(m.named_parameters())) == {"lora_A", "lora_B"}
     assert m.lora_flat.numel() == 2 * L * 8 * r * D
     assert not m.lora_ff and m._ff_params() == ()
-    assert isinstance(m._c_weights(torch.zeros(1), torch.zeros(1)), _lib.LtxWeights)
+    w = m._c_weights(torch.zeros(1), torch.zeros(1))  # the one weights structure, its feed-forward extension NULL
+    assert isinstance(w, _lib.LtxFfWeights) and all(getattr(w, n) is None for n in _lib.LTX_FF_WEIGHT_FIELDS)
+    assert w.base.proj_in_w == m.proj_in_w.data_ptr() and w.base.lora_a_sp == m.lora_a_sp.data_ptr()
 
 
 # ---- state dict and wire ---------------------------------------------------------------------------------------------------------------------------------------------
@@ -224,6 +227,10 @@ def test_new_symbols_are_declared_bound_and_exported():
     for s in NEW_SYMBOLS:
         assert getattr(lib, s) is not None
     assert lib.ftmi_version() == 101
+    import ltx_entry_bytes
+
+    declared = set(re.findall(r"\b(ftmi_[a-z0-9_]+)\s*\(", text))
+    ltx_entry_bytes.assert_only_the_wide_family(lib, declared, set(_lib.EXPORTED_SYMBOLS))  # ... and the narrow family they were twins of is gone
 
 
 def _cfg(r=64, **kw):
@@ -234,16 +241,20 @@ def _cfg(r=64, **kw):
 
 
 def test_workspace_plans_no_device():
-    """All eight pointers NULL: the twin plans what the original plans.  All set: the plan grows by the two kept [M, 3r] buffers per block slot and the two
-    scratch ones.  Some set, or any with r = 0: refused (a planner returns 0)."""
+    """All eight pointers NULL: the entry plans what the narrow entry planned (the recorded number).  All set: the plan grows by the two kept [M, 3r] buffers
+    per block slot and the two scratch ones.  Some set, or any with r = 0: refused (a planner returns 0)."""
     if not _lib.lib_available():
         pytest.skip("libftmi355.so is not built")
+    import ltx_entry_bytes
+
     lib = _lib.load()
+    plans = ltx_entry_bytes.recorded()
     for ck in (0, 1):
         cfg = _cfg(checkpoint=ck)
         none = _lib.LtxFfWeights()
-        eight = lib.ftmi_ltx_workspace_bytes(ctypes.byref(cfg))
-        assert lib.ftmi_ltx_ff_workspace_bytes(ctypes.byref(cfg), ctypes.byref(none)) == eight
+        narrow = plans[(cfg.B, cfg.S, 3, cfg.L, cfg.r, ck, 0)]  # (workspace, ..., sample(two_pass = 1), ...) of the narrow family, recorded before it went
+        eight = narrow[0]
+        assert lib.ftmi_ltx_ff_workspace_bytes(ctypes.byref(cfg), ctypes.byref(none)) == eight > 0
         full = _lib.LtxFfWeights()
         for n in _lib.LTX_FF_WEIGHT_FIELDS:
             setattr(full, n, 256)  # (never dereferenced by a planner)
@@ -254,10 +265,10 @@ def test_workspace_plans_no_device():
         off = ctypes.c_size_t(0)
         assert lib.ftmi_ltx_ff_workspace_offset(ctypes.byref(cfg), ctypes.byref(full), b"xa_ff2", 0, ctypes.byref(off)) == 0
         assert lib.ftmi_ltx_ff_workspace_offset(ctypes.byref(cfg), ctypes.byref(none), b"xa_ff2", 0, ctypes.byref(off)) != 0
-        assert lib.ftmi_ltx_workspace_offset(ctypes.byref(cfg), b"xa_ff1", 0, ctypes.byref(off)) != 0
+        assert lib.ftmi_ltx_ff_workspace_offset(ctypes.byref(cfg), ctypes.byref(none), b"xa_ff1", 0, ctypes.byref(off)) != 0
         # the eight-adapter slot is a prefix of the ten-adapter one
         o8, o10 = ctypes.c_size_t(0), ctypes.c_size_t(0)
-        assert lib.ftmi_ltx_workspace_offset(ctypes.byref(cfg), b"z", 0, ctypes.byref(o8)) == 0
+        assert lib.ftmi_ltx_ff_workspace_offset(ctypes.byref(cfg), ctypes.byref(none), b"z", 0, ctypes.byref(o8)) == 0
         assert lib.ftmi_ltx_ff_workspace_offset(ctypes.byref(cfg), ctypes.byref(full), b"z", 0, ctypes.byref(o10)) == 0
         assert o8.value == o10.value
         some = _lib.LtxFfWeights()
@@ -265,8 +276,26 @@ def test_workspace_plans_no_device():
         assert lib.ftmi_ltx_ff_workspace_bytes(ctypes.byref(cfg), ctypes.byref(some)) == 0
         assert lib.ftmi_ltx_ff_workspace_bytes(ctypes.byref(_cfg(r=0, checkpoint=ck)), ctypes.byref(full)) == 0
         assert lib.ftmi_ltx_ff_sample_workspace_bytes(ctypes.byref(cfg), ctypes.byref(some), 1) == 0
-        assert lib.ftmi_ltx_ff_sample_workspace_bytes(ctypes.byref(cfg), ctypes.byref(none), 1) == lib.ftmi_ltx_sample_workspace_bytes(ctypes.byref(cfg), 1)
-        assert lib.ftmi_ltx_ff_sample_workspace_bytes(ctypes.byref(cfg), ctypes.byref(full), 1) > lib.ftmi_ltx_sample_workspace_bytes(ctypes.byref(cfg), 1)
+        assert lib.ftmi_ltx_ff_sample_workspace_bytes(ctypes.byref(cfg), ctypes.byref(none), 1) == narrow[3] > 0
+        assert lib.ftmi_ltx_ff_sample_workspace_bytes(ctypes.byref(cfg), ctypes.byref(full), 1) > narrow[3]
+
+
+def test_the_planners_reproduce_every_recorded_row():
+    """Every row recorded through both families at the parent of the fold -- accepted and refused (ff with r = 0, a partial pointer set, frames = 0 for the
+    per-frame planners) -- and the offset of every name at layers 0 and L - 1, to the byte."""
+    if not _lib.lib_available():
+        pytest.skip("libftmi355.so is not built")
+    import ltx_entry_bytes
+
+    plans = ltx_entry_bytes.recorded()
+    assert len(plans) >= 192 + 32 + 32
+    assert sum(1 for v in plans.values() if v == (0,) * 6) >= 64 + 8 and sum(1 for k, v in plans.items() if k[2] == 0 and v[0] > 0 and v[1] == v[4] == v[5] == 0) >= 16
+    for key, want in plans.items():
+        assert ltx_entry_bytes.planned(*key) == want, (key, want)
+    offsets = ltx_entry_bytes.recorded_offsets()
+    assert {k[5] for k in offsets} == {0, 1} and len(offsets) == 4
+    for key, want in offsets.items():
+        assert ltx_entry_bytes.planned_offsets(*key) == want, key
 
 
 # ---- narrow geometry -------------------------------------------------------------------------------------------------------------------------------------------------

@@ -11,7 +11,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-I2V_SYMBOLS = ("ftmi_ltx_forward_frames", "ftmi_ltx_forward_frames_workspace_bytes", "ftmi_ltx_sample_cond", "ftmi_ltx_sample_cond_workspace_bytes",
+I2V_SYMBOLS = ("ftmi_ltx_ff_forward_frames", "ftmi_ltx_ff_forward_frames_workspace_bytes", "ftmi_ltx_ff_sample_cond", "ftmi_ltx_ff_sample_cond_workspace_bytes",
                "ftmi_ltx_cfg_euler_step_held")
 
 
@@ -235,7 +235,7 @@ def test_i2v_entry_points_check_arguments(lib):
     from finetrainers_amd import _lib
 
     p = ctypes.c_void_p(256)
-    w = _lib.LtxWeights()
+    w = _lib.LtxFfWeights()
     big = 1 << 40
     # held step: null, hold outside the sample, hold off a 16-byte vector
     assert lib.ftmi_ltx_cfg_euler_step_held(None, None, None, None, 3.0, None, 1, 64, 8, None) == _lib.FTMI_ERR_INVALID
@@ -244,7 +244,7 @@ def test_i2v_entry_points_check_arguments(lib):
     assert lib.ftmi_ltx_cfg_euler_step_held(p, p, p, p, 3.0, p, 1, 64, 12, None) == _lib.FTMI_ERR_UNSUPPORTED and "multiple of 8" in _lib.last_error()
     # per-frame forward: frames must divide the tokens; B x frames is bounded; no narrow geometry; workspace checked
     cfg = _cfg(S=64)
-    fwd = lambda c, frames, ws_bytes=big: lib.ftmi_ltx_forward_frames(ctypes.byref(c), ctypes.byref(w), p, p, None, p, frames, p, p, ws_bytes, None)
+    fwd = lambda c, frames, ws_bytes=big: lib.ftmi_ltx_ff_forward_frames(ctypes.byref(c), ctypes.byref(w), p, p, None, p, frames, p, p, ws_bytes, None)
     assert fwd(cfg, 0) == _lib.FTMI_ERR_INVALID
     assert fwd(cfg, 3) == _lib.FTMI_ERR_UNSUPPORTED and "frames" in _lib.last_error()
     assert fwd(cfg, 4, 1024) == _lib.FTMI_ERR_INVALID and "workspace too small" in _lib.last_error()
@@ -252,9 +252,9 @@ def test_i2v_entry_points_check_arguments(lib):
     assert fwd(_cfg(B=8, S=160), 16, 1024) == _lib.FTMI_ERR_INVALID  # 128 groups pass the bound (and 8 model rows x 16 frames is the stated cap)
     assert fwd(_cfg(B=16, S=64), 4, 1024) == _lib.FTMI_ERR_INVALID  # the batch itself is not limited to 8 here
     assert fwd(_cfg(S=64, d_valid=32, head_dim_valid=8), 4) == _lib.FTMI_ERR_UNSUPPORTED and "narrow" in _lib.last_error()
-    assert lib.ftmi_ltx_forward_frames(ctypes.byref(cfg), ctypes.byref(w), p, p, None, None, 4, p, p, big, None) == _lib.FTMI_ERR_INVALID
+    assert lib.ftmi_ltx_ff_forward_frames(ctypes.byref(cfg), ctypes.byref(w), p, p, None, None, 4, p, p, big, None) == _lib.FTMI_ERR_INVALID
     # conditioned sampler
-    smp = lambda c, frames, k, g=3.0, ws_bytes=big, tu=p: lib.ftmi_ltx_sample_cond(ctypes.byref(c), ctypes.byref(w), p, tu, None, None, p, p, p, 2, g, frames, k, p,
+    smp = lambda c, frames, k, g=3.0, ws_bytes=big, tu=p: lib.ftmi_ltx_ff_sample_cond(ctypes.byref(c), ctypes.byref(w), p, tu, None, None, p, p, p, 2, g, frames, k, p,
                                                                                   ws_bytes, None)
     assert smp(cfg, 0, 0) == _lib.FTMI_ERR_INVALID
     assert smp(cfg, 4, 5) == _lib.FTMI_ERR_INVALID and "cond_frames" in _lib.last_error()  # k > F
@@ -269,19 +269,22 @@ def test_i2v_entry_points_check_arguments(lib):
 def test_conditioned_workspace_is_the_sampler_workspace_plus_taller_tables(lib):
     """Config-2 size: per-frame conditioning adds (G - nb) rows to the tables and the embedding scratch, G = nb x frames, plus the two hoisted embedding
     rows -- nothing that grows with the token count."""
+    from finetrainers_amd import _lib
+
     L, D, F_ = 28, 2048, 7
+    w = ctypes.byref(_lib.LtxFfWeights())  # (no feed-forward adapters; a planner never dereferences the weights)
     for videos, two_pass in ((1, 1), (2, 1), (1, 0)):
         cfg = _cfg(B=videos, S=2688, L=L)
         nb = videos * (2 if two_pass else 1)
-        plain = lib.ftmi_ltx_sample_workspace_bytes(ctypes.byref(cfg), two_pass)
-        cond = lib.ftmi_ltx_sample_cond_workspace_bytes(ctypes.byref(cfg), two_pass, F_)
+        plain = lib.ftmi_ltx_ff_sample_workspace_bytes(ctypes.byref(cfg), w, two_pass)
+        cond = lib.ftmi_ltx_ff_sample_cond_workspace_bytes(ctypes.byref(cfg), w, two_pass, F_)
         rows = nb * F_ - nb
         tables = rows * 2 * (256 + D + D + 6 * D + L * 8 * D + 3 * D) + rows * 4 + 2 * 7 * D * 2
         assert plain < cond <= plain + tables + 10 * 256, (plain, cond, tables)  # (every buffer is rounded up to 256 bytes)
         assert cond - plain < 0.01 * plain
         # one frame: one group per model row, the plain layout plus the two hoisted rows
-        one = lib.ftmi_ltx_sample_cond_workspace_bytes(ctypes.byref(cfg), two_pass, 1)
+        one = lib.ftmi_ltx_ff_sample_cond_workspace_bytes(ctypes.byref(cfg), w, two_pass, 1)
         assert plain < one <= plain + 2 * 7 * D * 2 + 2 * 256
-        fwd = lib.ftmi_ltx_forward_frames_workspace_bytes(ctypes.byref(_cfg(B=nb, S=2688, L=L)), F_)
-        ref = lib.ftmi_ltx_workspace_bytes(ctypes.byref(_cfg(B=nb, S=2688, L=L, checkpoint=1)))
+        fwd = lib.ftmi_ltx_ff_forward_frames_workspace_bytes(ctypes.byref(_cfg(B=nb, S=2688, L=L)), w, F_)
+        ref = lib.ftmi_ltx_ff_workspace_bytes(ctypes.byref(_cfg(B=nb, S=2688, L=L, checkpoint=1)), w)
         assert ref < fwd <= ref + tables + 10 * 256

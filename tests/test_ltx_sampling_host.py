@@ -10,7 +10,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-SAMPLING_SYMBOLS = ("ftmi_ltx_cfg_euler_step", "ftmi_ltx_unpack_denorm", "ftmi_ltx_sample", "ftmi_ltx_sample_workspace_bytes")
+SAMPLING_SYMBOLS = ("ftmi_ltx_cfg_euler_step", "ftmi_ltx_unpack_denorm", "ftmi_ltx_ff_sample", "ftmi_ltx_ff_sample_workspace_bytes")
 
 
 @pytest.fixture(scope="module")
@@ -61,15 +61,16 @@ def test_sample_workspace_is_forward_only(lib):
         return _lib.LtxConfig(B=B, S=2688, T=128, D=2048, H=32, L=28, C_in=128, C_out=128, D_ff=8192, D_cap=4096, r=64, lora_scale=1.0, eps_norm=1e-6,
                               eps_qk=1e-5, gemm_variant=8, checkpoint=checkpoint)
 
+    w = ctypes.byref(_lib.LtxFfWeights())  # (no feed-forward adapters; a planner never dereferences the weights)
     for videos in (1, 2):
-        ws_two = lib.ftmi_ltx_sample_workspace_bytes(ctypes.byref(cfg(videos, 0)), 1)
-        ws_one = lib.ftmi_ltx_sample_workspace_bytes(ctypes.byref(cfg(videos, 0)), 0)
-        ref_two = lib.ftmi_ltx_workspace_bytes(ctypes.byref(cfg(2 * videos, 1)))
-        ref_one = lib.ftmi_ltx_workspace_bytes(ctypes.byref(cfg(videos, 1)))
+        ws_two = lib.ftmi_ltx_ff_sample_workspace_bytes(ctypes.byref(cfg(videos, 0)), w, 1)
+        ws_one = lib.ftmi_ltx_ff_sample_workspace_bytes(ctypes.byref(cfg(videos, 0)), w, 0)
+        ref_two = lib.ftmi_ltx_ff_workspace_bytes(ctypes.byref(cfg(2 * videos, 1)), w)
+        ref_one = lib.ftmi_ltx_ff_workspace_bytes(ctypes.byref(cfg(videos, 1)), w)
         assert ref_two <= ws_two <= 1.05 * ref_two, (ws_two, ref_two)
         assert ref_one <= ws_one <= 1.05 * ref_one, (ws_one, ref_one)
         assert ws_one < 0.6 * ws_two  # guidance == 1 runs B rows only
-        assert ws_two < 0.25 * lib.ftmi_ltx_workspace_bytes(ctypes.byref(cfg(2 * videos, 0)))  # far from a full activation stash
+        assert ws_two < 0.25 * lib.ftmi_ltx_ff_workspace_bytes(ctypes.byref(cfg(2 * videos, 0)), w)  # far from a full activation stash
 
 
 def test_sampling_entry_points_check_arguments(lib):
@@ -82,13 +83,13 @@ def test_sampling_entry_points_check_arguments(lib):
     assert lib.ftmi_ltx_unpack_denorm(p, p, p, p, 1, 126, 64, None) == _lib.FTMI_ERR_UNSUPPORTED
     cfg = _lib.LtxConfig(B=1, S=64, T=128, D=2048, H=32, L=1, C_in=128, C_out=128, D_ff=8192, D_cap=4096, r=0, lora_scale=0.0, eps_norm=1e-6, eps_qk=1e-5,
                          gemm_variant=8)
-    w = _lib.LtxWeights()
+    w = _lib.LtxFfWeights()
     # guidance != 1 without the unconditional prompt, and a workspace that is too small: refused before any launch
-    assert lib.ftmi_ltx_sample(ctypes.byref(cfg), ctypes.byref(w), p, None, None, None, p, p, p, 2, 3.0, p, 1 << 40, None) == _lib.FTMI_ERR_INVALID
-    assert lib.ftmi_ltx_sample(ctypes.byref(cfg), ctypes.byref(w), p, p, None, None, p, p, p, 2, 3.0, p, 1024, None) == _lib.FTMI_ERR_INVALID
+    assert lib.ftmi_ltx_ff_sample(ctypes.byref(cfg), ctypes.byref(w), p, None, None, None, p, p, p, 2, 3.0, p, 1 << 40, None) == _lib.FTMI_ERR_INVALID
+    assert lib.ftmi_ltx_ff_sample(ctypes.byref(cfg), ctypes.byref(w), p, p, None, None, p, p, p, 2, 3.0, p, 1024, None) == _lib.FTMI_ERR_INVALID
     assert "workspace too small" in _lib.last_error()
     cfg.B = 5  # 10 model rows
-    assert lib.ftmi_ltx_sample(ctypes.byref(cfg), ctypes.byref(w), p, p, None, None, p, p, p, 2, 3.0, p, 1 << 40, None) == _lib.FTMI_ERR_UNSUPPORTED
+    assert lib.ftmi_ltx_ff_sample(ctypes.byref(cfg), ctypes.byref(w), p, p, None, None, p, p, p, 2, 3.0, p, 1 << 40, None) == _lib.FTMI_ERR_UNSUPPORTED
 
 
 def test_sampler_refuses_cpu_and_narrow_models():

@@ -1,6 +1,6 @@
 """LTX-Video latent sampling at BASELINE config 2 size (28 blocks, one 49 x 512 x 768 video = 2 688 tokens, cond + uncond, rank 64): HIP-event time per
-denoising step of ftmi_ltx_sample with the text-side work hoisted out of the step loop (the product) and repeated in every step (FTMI_SAMPLE_HOIST=0),
-interleaved on one box, beside a plain batch-2 forward of the same model.  --cond-frames K (repeatable) adds ftmi_ltx_sample_cond with the first K latent
+denoising step of ftmi_ltx_ff_sample with the text-side work hoisted out of the step loop (the product) and repeated in every step (FTMI_SAMPLE_HOIST=0),
+interleaved on one box, beside a plain batch-2 forward of the same model.  --cond-frames K (repeatable) adds ftmi_ltx_ff_sample_cond with the first K latent
 frames held to the interleaved rounds (K = 0: per-frame conditioning tables, nothing held).
 `python tools/bench_sampling.py [--steps 8] [--rounds 5] [--cond-frames 0 --cond-frames 1] [--out FILE]`"""
 import argparse
@@ -20,7 +20,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--steps", type=int, default=8)
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--layers", type=int, default=28)
-ap.add_argument("--cond-frames", type=int, action="append", default=[], help="also time ftmi_ltx_sample_cond with this many latent frames held (repeatable)")
+ap.add_argument("--cond-frames", type=int, action="append", default=[], help="also time ftmi_ltx_ff_sample_cond with this many latent frames held (repeatable)")
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 
@@ -47,7 +47,7 @@ cos, sin = model.rope_tables(F_, H_, W_, [1 / (25 / 8), 32, 32])
 model.refresh_lora_copies()
 cfg = model._c_config(1, S, T)
 weights = model._c_weights(cos, sin)
-ws = torch.empty((max([ops.ltx_sample_workspace_bytes(cfg, True)] + [ops.ltx_sample_cond_workspace_bytes(cfg, True, F_) for _ in a.cond_frames]),),
+ws = torch.empty((max([ops.ltx_sample_workspace_bytes(cfg, True, weights)] + [ops.ltx_sample_cond_workspace_bytes(cfg, True, F_, weights) for _ in a.cond_frames]),),
                  dtype=torch.uint8, device=dev)
 lib = _lib.load()
 
@@ -77,7 +77,7 @@ def sample_cond(k):
 
 # plain forward at batch 2 (what one denoising step would cost through the training forward, activations kept)
 fcfg = model._c_config(2, S, T, checkpoint=False)
-fws_bytes = lib.ftmi_ltx_workspace_bytes(ctypes.byref(fcfg))
+fws_bytes = lib.ftmi_ltx_ff_workspace_bytes(ctypes.byref(fcfg), ctypes.byref(weights))
 fws = torch.empty((fws_bytes,), dtype=torch.uint8, device=dev)
 xin = torch.cat([x0, x0]).to(bf16)
 text2, kb2 = torch.cat([text_u, text_c]).contiguous(), torch.cat([kb_u, kb_c]).contiguous()
@@ -88,8 +88,8 @@ pred = torch.empty((2, S, 128), dtype=bf16, device=dev)
 def forward():
     def run():
         for _ in range(a.steps):
-            _lib.check(lib.ftmi_ltx_forward(ctypes.byref(fcfg), ctypes.byref(weights), _lib.ptr(xin), _lib.ptr(text2), _lib.ptr(kb2), _lib.ptr(tv), _lib.ptr(pred),
-                                            _lib.ptr(fws), fws_bytes, _lib.stream_ptr()), "ftmi_ltx_forward")
+            _lib.check(lib.ftmi_ltx_ff_forward(ctypes.byref(fcfg), ctypes.byref(weights), _lib.ptr(xin), _lib.ptr(text2), _lib.ptr(kb2), _lib.ptr(tv), _lib.ptr(pred),
+                                               _lib.ptr(fws), fws_bytes, _lib.stream_ptr()), "ftmi_ltx_ff_forward")
     return event_ms(run) / a.steps
 
 

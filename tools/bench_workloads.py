@@ -774,7 +774,7 @@ def build_cog_sample(args, par, dev) -> Dict[str, Any]:
 # ------------------------------------------------------------------------------------------------------------------------------------------
 # HunyuanVideo validation sampling in latent space (finetrainers_amd/hunyuan_video/sampler.py) at BASELINE configs[4]'s geometry: 61 x 544 x 960 -> latents
 # [1, 16, 16, 68, 120] = 32 640 video + 256 text tokens (200 real), 20 dual-stream + 40 single-stream blocks, fp8 weight storage, random weights with
-# rank-`--rank` adapters (run with --rank 64), embedded guidance 6, no true CFG (the pipeline's default).  One "step" of this workload is one ftmi_hy_sample
+# rank-`--rank` adapters (run with --rank 64), embedded guidance 6, no true CFG (the pipeline's default).  One "step" of this workload is one ftmi_hy_sample_text
 # call of `SAMPLE_STEPS` denoising steps; the report interleaves it with the same loop composed in Python (model.forward under no_grad + ops.hy_sample_step)
 # and times the step kernel on its own.
 # ------------------------------------------------------------------------------------------------------------------------------------------
@@ -871,7 +871,7 @@ def build_hy_sample(args, par, dev) -> Dict[str, Any]:
         "report": report,
         "samples_per_step": 1.0 / n,
         "step_tflop": n * (nd * dual + ns * single) / 1e12,  # linears + joint attention, forward only
-        "metric": f"ftmi_hy_sample: one call of {n} denoising steps, HunyuanVideo 61x544x960, embedded guidance 6 (value: denoising steps per ms are in the report)",
+        "metric": f"ftmi_hy_sample_text: one call of {n} denoising steps, HunyuanVideo 61x544x960, embedded guidance 6 (value: denoising steps per ms are in the report)",
         "data": "random noise [1,16,16,68,120] + random text embeds [1,256,4096] (200 real tokens) + pooled [1,768], random-init weights of the HunyuanVideo DiT "
                 "stored as fp8 bytes",
         "config": {"workload": f"HunyuanVideo latent sampling, rank={args.rank} adapters, fp8 weight storage, {S} video + {T} text tokens, 1 model row, "
@@ -932,7 +932,7 @@ def build_ltx_lora(args, par, dev) -> Dict[str, Any]:
     cos, sin = model.rope_tables(F_, H, W, None)
     w = model._c_weights(cos, sin)
     lib = _lib.load()
-    ws = lib.ftmi_ltx_ff_workspace_bytes(ctypes.byref(cfg), ctypes.byref(w)) if ffn else lib.ftmi_ltx_workspace_bytes(ctypes.byref(cfg))
+    ws = lib.ftmi_ltx_ff_workspace_bytes(ctypes.byref(cfg), ctypes.byref(w))
     return {
         "one_step": lambda: step.step(cond, lat),
         "samples_per_step": B,
