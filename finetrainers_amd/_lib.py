@@ -306,6 +306,8 @@ _SIGS = {
     "ftmi_attn_ctx2_dq": (c_int, [POINTER(AttnDesc)] + [c_void_p] * 8),
     "ftmi_attn_ctx2w_fwd": (c_int, [POINTER(AttnDesc)] + [c_void_p] * 7),
     "ftmi_attn_ctx2w_dq": (c_int, [POINTER(AttnDesc)] + [c_void_p] * 8),
+    "ftmi_attn_fwd_carry": (c_int, [POINTER(AttnDesc)] + [c_void_p] * 7 + [c_int, c_void_p]),
+    "ftmi_accum_bf16": (c_int, [POINTER(AttnDesc)] + [c_void_p] * 4),
     "ftmi_linear_lora_fwd": (c_int, [c_int, c_int, c_int, c_int, c_float] + [c_void_p] * 7 + [c_int, c_void_p]),
     "ftmi_linear_lora_bwd": (c_int, [c_int, c_int, c_int, c_int, c_float] + [c_void_p] * 10 + [c_int, c_void_p]),
     "ftmi_gemm_nt_plan": (c_int, [c_int, c_int, c_int, c_int, c_int]),

@@ -92,6 +92,45 @@ def attn_bwd(q, k, v, out, lse, dout, key_bias=None, scale=None, dv_out=None, dq
     return dq, dk, dv
 
 
+def attn_fwd_carry(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, acc: torch.Tensor, lse: torch.Tensor, key_bias: Optional[torch.Tensor] = None,
+                   scale: Optional[float] = None, first: bool = False, last: bool = False, out: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """Attention of ``q`` over the next chunk of keys, continuing the softmax state (``acc`` fp32 [B,H,Sq,d] contiguous, ``lse`` fp32 [B,H,Sq], log2 domain)
+    in place: ``ftmi_attn_fwd_carry``.  ``first``: the state is not read (it may be uninitialised memory).  ``last``: also returns bf16(acc) of the new
+    state, in ``out`` when given (a [B, H, Sq, d] bf16 view) or in a fresh tensor laid out as [B, Sq, H, d]; otherwise returns None."""
+    for n, t in (("query", q), ("key", k), ("value", v)):
+        require_gpu_tensor(t, n, bf16)
+    require_gpu_tensor(acc, "acc", torch.float32)
+    require_gpu_tensor(lse, "lse", torch.float32)
+    B, H, Sq, d = q.shape
+    if acc.shape != (B, H, Sq, d) or not acc.is_contiguous() or lse.shape != (B, H, Sq) or not lse.is_contiguous():
+        raise ValueError("attn_fwd_carry: the state is acc [B, H, Sq, head_dim] and lse [B, H, Sq], fp32 and contiguous")
+    scale = (1.0 / d**0.5) if scale is None else scale
+    if last:
+        out = _placed(out, (B, H, Sq, d), "attn_fwd_carry: out", q)
+    elif out is not None:
+        raise ValueError("attn_fwd_carry: out is written with the last chunk only")
+    if key_bias is not None:
+        require_gpu_tensor(key_bias, "key_bias", torch.float32)
+    desc = _desc(q, k, v, out, scale, key_bias=key_bias)
+    check(_lib.load().ftmi_attn_fwd_carry(ctypes.byref(desc), ptr(q), ptr(k), ptr(v), ptr(acc), ptr(lse), ptr(out), ptr(key_bias), int(bool(first)),
+                                           stream_ptr()), "ftmi_attn_fwd_carry")
+    return out
+
+
+def accum_bf16(acc: torch.Tensor, x: torch.Tensor, last: bool = False) -> Optional[torch.Tensor]:
+    """``acc += float(x)`` for a bf16 [B, H, S, d] view ``x`` (head_dim contiguous) and its contiguous fp32 sum ``acc``: ``ftmi_accum_bf16``.  ``last``: bf16(acc)
+    is also written over ``x``, which is returned."""
+    require_gpu_tensor(x, "x", bf16)
+    require_gpu_tensor(acc, "acc", torch.float32)
+    if acc.shape != x.shape or not acc.is_contiguous():
+        raise ValueError("accum_bf16: acc must be the contiguous fp32 [B, H, S, head_dim] sum of x")
+    desc = AttnDesc()
+    desc.B, desc.H, desc.Sq, desc.d = x.shape
+    desc.dq_strides[0], desc.dq_strides[1], desc.dq_strides[2] = _strides3(x)
+    check(_lib.load().ftmi_accum_bf16(ctypes.byref(desc), ptr(acc), ptr(x), ptr(x) if last else None, stream_ptr()), "ftmi_accum_bf16")
+    return x if last else None
+
+
 def _ctx2_fwd(entry: str, q, k, v, out_first, scale):
     """The second-context forward through one C entry of the ``ftmi_attn_ctx2*_fwd`` family (narrow, wide; the tools' lab variant)."""
     for n, t in (("query", q), ("key", k), ("value", v), ("out_first", out_first)):

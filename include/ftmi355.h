@@ -114,6 +114,27 @@ int ftmi_attn_ctx2w_fwd(const ftmi_attn_desc* desc, const void* q, const void* k
 int ftmi_attn_ctx2w_dq(const ftmi_attn_desc* desc, const void* q, const void* k, const void* v, const float* lse, const void* dout, const void* dq_first,
                        void* dq, ftmi_stream stream);
 
+/* Forward attention that CONTINUES a softmax state carried in fp32 over the next chunk of desc.Sk keys (context parallelism: one call per rank's key / value
+ * chunk; keys that live in several buffers).  n chunks are n calls and nothing in between.  The state of a query row:
+ *   acc  fp32 [B,H,Sq,d] contiguous: the normalised running output;   lse  fp32 [B,H,Sq], log2 domain as ftmi_attn_fwd writes it: the running log-sum-exp
+ * first != 0: the state is not read -- an ordinary forward over this chunk that leaves its state in acc / lse.  first == 0: each row re-enters the online
+ * softmax at running max = lse, running sum = 1, accumulator = its acc row (exact: acc * 2^lse is the un-normalised numerator), runs over the chunk and
+ * writes back acc = accumulator / sum, lse = max + log2 sum.  out: bf16 with desc.o_strides, or NULL; when given it receives bf16(acc) of the NEW state (pass
+ * it with the last chunk).  After the last chunk acc / lse / out are the one-call forward's result over all keys up to summation order; (out, lse) feed
+ * ftmi_attn_bwd per chunk, which then returns that chunk's share of dQ and its dK / dV.
+ * key_bias as for ftmi_attn_fwd, for this chunk's keys.  A key with a -inf bias has weight exactly 0; a chunk whose keys are all -inf for a row leaves that
+ * row's acc and lse unchanged bit for bit; a row whose carried lse is -inf (no key seen yet) comes out as if this chunk were the first; a row that has
+ * still seen no key keeps acc = 0, lse = -inf (and out = 0).  No NaN in any of these.
+ * Refused before anything is launched, in this order: a null descriptor (FTMI_ERR_INVALID), desc.d other than 64 or 128 (FTMI_ERR_UNSUPPORTED); then with
+ * FTMI_ERR_INVALID a null q / k / v ("null tensor"), a null acc or lse ("null state"), B, H, Sq or Sk <= 0 ("empty problem"), the alignment rule of
+ * ftmi_attn_fwd for q, k, v and (when given) out, and an acc that is not 16-byte aligned (its rows are moved in 16-byte pieces). */
+int ftmi_attn_fwd_carry(const ftmi_attn_desc* desc, const void* q, const void* k, const void* v, float* acc, float* lse, void* out, const float* key_bias,
+                        int first, ftmi_stream stream);
+/* acc[b,h,s,:] += float(x[b,h,s,:]) over desc.B x desc.H x desc.Sq rows of desc.d: acc fp32 contiguous, x bf16 with desc.dq_strides.  out: NULL, or a bf16
+ * destination with desc.dq_strides (x itself is allowed) that receives bf16(acc) -- pass it with the last call.  Sums the per-chunk dQ that ftmi_attn_bwd
+ * returns in bf16, in fp32.  Refusals as above: descriptor, null acc / x, empty problem, 16-byte alignment of x (base and strides), out and acc (base). */
+int ftmi_accum_bf16(const ftmi_attn_desc* desc, float* acc, const void* x, void* out, ftmi_stream stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Linear (+ LoRA) building block:  y = bf16( bf16(x W^T + b) + lora_scale * (x A^T) B^T ), the LoRA branch at fp32-equivalent
  * precision (peft lora.Linear with fp32 adapter weights).  a_sp [2r,K] and b_ext [N,3r] are working copies of the fp32 A [r,K] and
