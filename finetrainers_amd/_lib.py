@@ -294,6 +294,16 @@ class GemmTnArgs(Structure):
     ]
 
 
+class GemmNnArgs(Structure):
+    """include/ftmi355.h: ftmi_gemm_nn_args."""
+
+    _fields_ = [
+        ("dy", c_void_p), ("lddy", c_long), ("w", c_void_p), ("ldw", c_long), ("M", c_int), ("N", c_int), ("K", c_int),
+        ("x2", c_void_p), ("ldx2", c_long), ("w2", c_void_p), ("ldw2", c_long), ("K2", c_int),
+        ("aux", c_void_p), ("ldaux", c_long), ("out", c_void_p), ("ldo", c_long), ("epilogue", c_int),
+    ]
+
+
 _SIGS = {
     "ftmi_version": (c_int, []),
     "ftmi_last_error": (c_int, [c_char_p, c_size_t]),
@@ -326,6 +336,7 @@ _SIGS = {
     "ftmi_gemm_nt_ex": (c_int, [POINTER(GemmNtArgs), c_void_p]),
     "ftmi_gemm_nt_route": (c_int, [POINTER(GemmNtArgs), POINTER(c_int)]),
     "ftmi_gemm_tn_ex": (c_int, [POINTER(GemmTnArgs), c_void_p]),
+    "ftmi_gemm_nn": (c_int, [POINTER(GemmNnArgs), c_void_p]),
     "ftmi_fp8_upcast": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "ftmi_transpose_bf16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "ftmi_norm_modulate_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p]),

@@ -384,6 +384,15 @@ int ftmi_gemm_tn_ex(const ftmi_gemm_tn_args* p, ftmi_stream stream) {
     return gemm_tn(a, (hipStream_t)stream);
 }
 
+int ftmi_gemm_nn(const ftmi_gemm_nn_args* p, ftmi_stream stream) {
+    if (!p) return set_error(FTMI_ERR_INVALID, "ftmi_gemm_nn: null argument block");
+    GemmNnArgs a;
+    a.dY = (const bf16_t*)p->dy; a.lddy = p->lddy; a.W = (const bf16_t*)p->w; a.ldw = p->ldw; a.M = p->M; a.N = p->N; a.K = p->K;
+    a.X2 = (const bf16_t*)p->x2; a.ldx2 = p->ldx2; a.W2 = (const bf16_t*)p->w2; a.ldw2 = p->ldw2; a.K2 = p->K2;
+    a.aux = (const bf16_t*)p->aux; a.ldaux = p->ldaux; a.out = (bf16_t*)p->out; a.ldo = p->ldo; a.epi = p->epilogue;
+    return gemm_nn(a, (hipStream_t)stream);
+}
+
 int ftmi_fp8_upcast(const void* src, void* dst, int rows, int cols, int transpose, ftmi_stream stream) {
     if (!src || !dst) return set_error(FTMI_ERR_INVALID, "ftmi_fp8_upcast: null tensor");
     return fp8_upcast((const uint8_t*)src, (bf16_t*)dst, rows, cols, transpose, (hipStream_t)stream);

@@ -179,6 +179,26 @@ struct GemmTnArgs {
     long u_bstride = 0, v_bstride = 0, c_bstride = 0;
 };
 int gemm_tn(const GemmTnArgs& a, hipStream_t st);
+// NN GEMM (gemm_nn.hip): out [M, K] = epi(bf(dY [M, N] . W [N, K]) (+ X2 [M, K2] . W2 [K, K2]^T)) -- the input gradient of a linear layer against the weight as
+// the forward reads it (row-major, the reduction index is its ROW), with the NT launcher's rounding points.  N % 64, K % 128, K2 % 64; epi EPI_STORE or EPI_DGELU.
+struct GemmNnArgs {
+    const bf16_t* dY = nullptr;  // [M, lddy]
+    long lddy = 0;
+    const bf16_t* W = nullptr;  // [N, ldw]
+    long ldw = 0;
+    int M = 0, N = 0, K = 0;
+    const bf16_t* X2 = nullptr;  // [M, ldx2]   K-extension in the NT operand layout (lora_ext_bwd)
+    long ldx2 = 0;
+    const bf16_t* W2 = nullptr;  // [K, ldw2]
+    long ldw2 = 0;
+    int K2 = 0;
+    const bf16_t* aux = nullptr;  // EPI_DGELU: pre-activation [M, ldaux]
+    long ldaux = 0;
+    bf16_t* out = nullptr;  // [M, ldo]
+    long ldo = 0;
+    int epi = EPI_STORE;
+};
+int gemm_nn(const GemmNnArgs& a, hipStream_t st);
 // fp8 (e4m3fn) weight storage: exact up-cast to bf16, plain [rows, cols] or transposed [cols, rows] (cast.hip)
 int fp8_upcast(const uint8_t* src, bf16_t* dst, int rows, int cols, int transpose, hipStream_t st);
 

@@ -289,6 +289,7 @@ struct Block {
     float *grad_a = nullptr, *grad_b = nullptr;  // backward: fp32 [8, r, D] / [8, D, r] (ADDED to)
     Adp f1, f2;                                  // the feed-forward adapters on ffn.net.0.proj / ffn.net.2 (n = 0: none), filled for the call's direction
     Twins t;
+    bool nn = false;                             // frozen base without twins: every input gradient is the NN GEMM against the forward weight
     ImgCtx img;
     hipStream_t st = nullptr;
 };
@@ -364,13 +365,20 @@ int proj_fwd(const Block& k, const bf16_t* X, int rows, int K, const bf16_t* Wm,
 // The backward of proj_fwd for dY [rows, N], X [rows, K], Wt [K, N] the K-contiguous twin of W, in this order: dW += dY^T X and db += column sums (gw != null:
 // the base trains); dXA = s dY B (adapters); dx [rows, K] = dY Wt^T (+ dXA A) (dx == null: skipped); dB += dY^T XA, dA += dXA^T X (adapters).
 // pre != null: dx = (the sum) * gelu_tanh'(pre), pre [rows, K] (the feed-forward's second projection hands its input gradient through the activation)
-int proj_bwd(const Block& k, const bf16_t* X, const bf16_t* dy, int rows, int N, int K, const bf16_t* Wt, const Adp& ad, bf16_t* dx, float* gw, float* gb,
-             const bf16_t* pre = nullptr) {
+// k.nn (a frozen base without twins): Wt is null and dx = dY Wf runs as the NN GEMM against the forward weight Wf [N, ldwf] itself, same rounding points
+int proj_bwd(const Block& k, const bf16_t* X, const bf16_t* dy, int rows, int N, int K, const bf16_t* Wt, const bf16_t* Wf, long ldwf, const Adp& ad, bf16_t* dx,
+             float* gw, float* gb, const bf16_t* pre = nullptr) {
     const int r = ad.n > 0 ? ad.r : 0, No = ad.n > 0 ? N / ad.n : N;  // (No: outputs per adapter)
     bf16_t* dxa = k.L.dxa;
     FTMI_TRY(linear_grads(dy, N, X, K, rows, N, K, gw, gb, k.st));
     if (r > 0) FTMI_TRY(lora_down(ad, dy, N, rows, No, ad.n > 1 ? No : 0, dxa, k.st));
-    if (dx) {
+    if (dx && k.nn) {
+        GemmNnArgs a;
+        a.dY = dy; a.lddy = N; a.W = Wf; a.ldw = ldwf; a.M = rows; a.N = N; a.K = K; a.out = dx; a.ldo = K;
+        if (pre) { a.epi = EPI_DGELU; a.aux = pre; a.ldaux = K; }
+        if (r > 0) { a.X2 = dxa; a.ldx2 = 3L * ad.n * r; a.W2 = ad.ext; a.ldw2 = ad.ld_ext; a.K2 = 3 * ad.n * r; }  // (lora_ext_bwd's operands)
+        FTMI_TRY(gemm_nn(a, k.st));
+    } else if (dx) {
         GemmNtArgs a = linear_args(dy, N, rows, Wt, N, K, N, nullptr, dx, K, k.c.gemm_variant);
         if (pre) { a.epi = EPI_DGELU; a.aux = pre; a.ldaux = K; }
         if (r > 0) lora_ext_bwd(a, dxa, ad.n, r, ad.ext, ad.ld_ext);
@@ -491,15 +499,15 @@ int block_backward(const Block& k, const bf16_t* dout, bf16_t* dx, bf16_t* denc)
 
     // feed-forward branch: out = x2 + f * gate_ff
     FTMI_TRY(gate_bwd(dout, L.df, L.f, 5));
-    FTMI_TRY(proj_bwd(k, L.act, L.df, M, D, F, k.t.f2, k.f2, L.dpre, G(O.w_f2), G(O.b_f2), L.pre));  // (d f W2 [+ dXA_2 A_2]) * gelu'(pre)
-    FTMI_TRY(proj_bwd(k, L.n3, L.dpre, M, F, D, k.t.f1, k.f1, L.dn3, G(O.w_f1), G(O.b_f1)));
+    FTMI_TRY(proj_bwd(k, L.act, L.df, M, D, F, k.t.f2, P(O.w_f2), F, k.f2, L.dpre, G(O.w_f2), G(O.b_f2), L.pre));  // (d f W2 [+ dXA_2 A_2]) * gelu'(pre)
+    FTMI_TRY(proj_bwd(k, L.n3, L.dpre, M, F, D, k.t.f1, P(O.w_f1), D, k.f1, L.dn3, G(O.w_f1), G(O.b_f1)));
     {
         WanRowArgs a = row_args(L.x2, D, L.dx2, D, M, D, S, eps);
         a.scale = MOD(4); a.mod_bstride = mb; a.dy = L.dn3; a.ld_dy = D; a.dres = dout; a.red1 = DMOD(3); a.red2 = DMOD(4); a.red_per_batch = per_batch;
         FTMI_TRY(wan_ln_bwd(a, st));
     }
     // cross-attention branch: x2 = x1 + a2
-    FTMI_TRY(proj_bwd(k, k.img.TI > 0 ? L.o2s : L.o2, L.dx2, M, D, D, k.t.o2, attn_adp(k, 7, 1, L.xa_o2), L.do2, G(O.w_o2), G(O.b_o2)));
+    FTMI_TRY(proj_bwd(k, k.img.TI > 0 ? L.o2s : L.o2, L.dx2, M, D, D, k.t.o2, P(O.w_o2), D, attn_adp(k, 7, 1, L.xa_o2), L.do2, G(O.w_o2), G(O.b_o2)));
     FTMI_TRY(attn_bwd(attn_bwd_args(attn_args(c, L.q2n, L.k2n, L.kv2, 2 * D, L.o2, L.lse2, S, T), L.do2, L.dq2n, L.dk2n, L.dkv2, L.delta), st));
     if (k.img.TI > 0)  // the image branch's dQ, added onto the text branch's in place (its keys and values are frozen: no dK, dV)
         FTMI_TRY((k.img.wide ? attn_ctx2w_dq : attn_ctx2_dq)(attn_bwd_args(attn_args(c, L.q2n, L.kin, L.kvi, 2 * D, L.o2s, L.lse_i, S, k.img.TI), L.do2, L.dq2n, nullptr, L.dkv2, nullptr), L.dq2n, st));
@@ -512,8 +520,8 @@ int block_backward(const Block& k, const bf16_t* dout, bf16_t* dx, bf16_t* denc)
         FTMI_TRY(wan_rms_rope_bwd(b, st));
     }
     FTMI_TRY(linear_grads(L.dq2, D, L.n2, D, M, D, D, G(O.w_q2), G(O.b_q2), st));  // (attn2.to_q's weight gradient goes ahead of the text rows' projection)
-    FTMI_TRY(proj_bwd(k, k.enc, L.dkv2, Mt, 2 * D, D, k.t.kv2, attn_adp(k, 5, 2, L.xa_kv2), denc, G(O.w_kv2), G(O.b_kv2)));
-    FTMI_TRY(proj_bwd(k, L.n2, L.dq2, M, D, D, k.t.q2, attn_adp(k, 4, 1, L.xa_q2), L.dn2, nullptr, nullptr));
+    FTMI_TRY(proj_bwd(k, k.enc, L.dkv2, Mt, 2 * D, D, k.t.kv2, P(O.w_kv2), D, attn_adp(k, 5, 2, L.xa_kv2), denc, G(O.w_kv2), G(O.b_kv2)));
+    FTMI_TRY(proj_bwd(k, L.n2, L.dq2, M, D, D, k.t.q2, P(O.w_q2), D, attn_adp(k, 4, 1, L.xa_q2), L.dn2, nullptr, nullptr));
     {
         WanRowArgs a = row_args(L.x1, D, L.dx1, D, M, D, S, eps);
         a.w = P(O.n2w); a.dy = L.dn2; a.ld_dy = D; a.dres = L.dx2; a.red1 = G(O.n2b); a.red2 = G(O.n2w);
@@ -521,7 +529,7 @@ int block_backward(const Block& k, const bf16_t* dout, bf16_t* dx, bf16_t* denc)
     }
     // self-attention branch: x1 = x + a1 * gate_msa
     FTMI_TRY(gate_bwd(L.dx1, L.da1, L.a1, 2));
-    FTMI_TRY(proj_bwd(k, L.o1, L.da1, M, D, D, k.t.o1, attn_adp(k, 3, 1, L.xa_o1), L.do1, G(O.w_o1), G(O.b_o1)));
+    FTMI_TRY(proj_bwd(k, L.o1, L.da1, M, D, D, k.t.o1, P(O.w_o1), D, attn_adp(k, 3, 1, L.xa_o1), L.do1, G(O.w_o1), G(O.b_o1)));
     FTMI_TRY(attn_bwd(attn_bwd_args(attn_args(c, L.qn, L.kn, L.qkv, 3 * D, L.o1, L.lse1, S, S), L.do1, L.dqn, L.dkn, L.dqkv, L.delta), st));
     for (int i = 0; i < 2; ++i) {
         WanRowArgs a = row_args(L.qkv + (size_t)i * D, 3 * D, L.dqkv + (size_t)i * D, 3 * D, M, D, S, eps);
@@ -529,7 +537,7 @@ int block_backward(const Block& k, const bf16_t* dout, bf16_t* dx, bf16_t* denc)
         FTMI_TRY(wan_rms_rope_bwd(a, st));
     }
     // the three projections' input gradients (and their adapters') summed in the fp32 accumulator
-    FTMI_TRY(proj_bwd(k, L.n1, L.dqkv, M, 3 * D, D, k.t.qkv1, attn_adp(k, 0, 3, L.xa_qkv), L.dn1, G(O.w_qkv1), G(O.b_qkv1)));
+    FTMI_TRY(proj_bwd(k, L.n1, L.dqkv, M, 3 * D, D, k.t.qkv1, P(O.w_qkv1), D, attn_adp(k, 0, 3, L.xa_qkv), L.dn1, G(O.w_qkv1), G(O.b_qkv1)));
     {
         WanRowArgs a = row_args(k.x, D, dx, D, M, D, S, eps);
         a.scale = MOD(1); a.mod_bstride = mb; a.dy = L.dn1; a.ld_dy = D; a.dres = L.dx1; a.red1 = DMOD(0); a.red2 = DMOD(1); a.red_per_batch = per_batch;
@@ -660,9 +668,13 @@ int wan_lora_ffn_block_backward(const ftmi_wan_lora_ffn_block_config& c, const f
     if (saved_bytes < L.saved_total || scratch_bytes < L.scratch_total) return set_error(FTMI_ERR_INVALID, "wan_lora_ffn_block_backward: buffer too small");
     if (c.r > 0 && (!wb.lora_a || !wb.lora_b || !grad_a || !grad_b))
         return set_error(FTMI_ERR_INVALID, "wan_lora_ffn_block_backward: LoRA rank without adapters / gradient buffers");
-    if (!wb.w_qkv1_t || !wb.w_o1_t || !wb.w_q2_t || !wb.w_kv2_t || !wb.w_o2_t || !wb.w_f1_t || !wb.w_f2_t)
+    // all seven twins NULL: the block runs without them (gemm_nn against the forward weights in params); some of them: refused as before
+    const bool no_twins = !wb.w_qkv1_t && !wb.w_o1_t && !wb.w_q2_t && !wb.w_kv2_t && !wb.w_o2_t && !wb.w_f1_t && !wb.w_f2_t;
+    if (!no_twins && (!wb.w_qkv1_t || !wb.w_o1_t || !wb.w_q2_t || !wb.w_kv2_t || !wb.w_o2_t || !wb.w_f1_t || !wb.w_f2_t))
         return set_error(FTMI_ERR_INVALID, "wan_lora_ffn_block_backward: transposed weights missing");
+    if (no_twins && (c.D % 128 || c.F % 128)) return set_error(FTMI_ERR_UNSUPPORTED, "wan_lora_ffn_block_backward: without transposed weights the widths must be multiples of 128");
     Block k = lora_block(c, w, L, img_params, x, enc, enc_img, mod, rope_cos, rope_sin, st);
+    k.nn = no_twins;
     auto WT = [](const void* p) { return reinterpret_cast<const bf16_t*>(p); };
     k.t.qkv1 = WT(wb.w_qkv1_t); k.t.o1 = WT(wb.w_o1_t); k.t.q2 = WT(wb.w_q2_t); k.t.kv2 = WT(wb.w_kv2_t); k.t.o2 = WT(wb.w_o2_t); k.t.f1 = WT(wb.w_f1_t); k.t.f2 = WT(wb.w_f2_t);
     k.grad_a = grad_a; k.grad_b = grad_b;

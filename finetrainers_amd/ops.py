@@ -290,6 +290,36 @@ def gemm_tn_ex(u: torch.Tensor, v: torch.Tensor, c: torch.Tensor, *, M: int, P: 
     check(_lib.load().ftmi_gemm_tn_ex(ctypes.byref(a), stream_ptr()), "ftmi_gemm_tn_ex")
 
 
+def gemm_nn(dy: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = None, *, x2: Optional[torch.Tensor] = None, w2: Optional[torch.Tensor] = None,
+            aux: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The NN GEMM (ftmi_gemm_nn; the contract is stated in include/ftmi355.h): out [M, K] = bf(dy [M, N] @ w [N, K]) -- the input gradient of a linear layer
+    against the weight as its forward reads it, no transposed copy.  ``x2`` [M, K2] / ``w2`` [K, K2]: the LoRA K-extension, out = bf(bf(dy w) + x2 w2^T);
+    ``aux`` [M, K]: the GELU' epilogue, out = bf(bf(y) * gelu_tanh'(aux)).  Tensors are 2-D bf16 views with contiguous columns; their row strides travel."""
+    for n, t in (("dy", dy), ("w", w)) + tuple((n, t) for n, t in (("out", out), ("x2", x2), ("w2", w2), ("aux", aux)) if t is not None):
+        require_gpu_tensor(t, n, bf16)
+    if dy.dim() != 2 or w.dim() != 2 or dy.shape[1] != w.shape[0]:
+        raise ValueError(f"gemm_nn: dy [M, N] and w [N, K] do not chain: {tuple(dy.shape)} and {tuple(w.shape)}")
+    M, N = dy.shape
+    K = w.shape[1]
+    if (x2 is None) != (w2 is None):
+        raise ValueError("gemm_nn: the K-extension needs both x2 and w2")
+    K2 = 0 if x2 is None else int(x2.shape[1])
+    if x2 is not None and (x2.shape != (M, K2) or w2.shape != (K, K2)):
+        raise ValueError(f"gemm_nn: x2 must be [M, K2] and w2 [K, K2], got {tuple(x2.shape)} and {tuple(w2.shape)}")
+    if aux is not None and aux.shape != (M, K):
+        raise ValueError("gemm_nn: aux must be an [M, K] view")
+    if out is None:
+        out = torch.empty((M, K), dtype=bf16, device=dy.device)
+    elif out.shape != (M, K):
+        raise ValueError("gemm_nn: out must be an [M, K] bf16 view with contiguous columns")
+    a = _lib.GemmNnArgs()
+    a.dy, a.lddy, a.w, a.ldw, a.M, a.N, a.K = ptr(dy), _ld(dy, "dy"), ptr(w), _ld(w, "w"), M, N, K
+    a.x2, a.ldx2, a.w2, a.ldw2, a.K2 = ptr(x2), _ld(x2, "x2"), ptr(w2), _ld(w2, "w2"), K2
+    a.aux, a.ldaux, a.out, a.ldo, a.epilogue = ptr(aux), _ld(aux, "aux"), ptr(out), _ld(out, "out"), (_lib.EPI_DGELU if aux is not None else _lib.EPI_STORE)
+    check(_lib.load().ftmi_gemm_nn(ctypes.byref(a), stream_ptr()), "ftmi_gemm_nn")
+    return out
+
+
 def fp8_upcast(w8: torch.Tensor, out: Optional[torch.Tensor] = None, transpose: bool = False) -> torch.Tensor:
     """bf16 copy of a [rows, cols] ``torch.float8_e4m3fn`` weight (exact), optionally transposed to [cols, rows]; ``out``: a contiguous bf16 tensor of the
     result's size (e.g. a slice of a per-model weight arena)."""

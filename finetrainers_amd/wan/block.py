@@ -487,7 +487,7 @@ class _WanLoRABlockNativeFunction(torch.autograd.Function):
             raise RuntimeError("Wan block: the flat parameter buffer does not have the layout the C orchestrator expects")
         keep = [params]
         w.params = ptr(params)
-        if backward:
+        if backward and blk.weight_twins:  # (without twins the seven pointers stay NULL: the C call then runs every input gradient through ftmi_gemm_nn)
             Wt = blk.transposed()
             for field, name in _TWINS:
                 keep.append(Wt[name])
@@ -584,7 +584,8 @@ class MI355XWanBlock(nn.Module):
         self.grad_flat: Optional[torch.Tensor] = None  # fp32, allocated by ``zero_grad_flat`` (the sharded trainer hands in its own buffer)
         self._transposed: Optional[Dict[str, torch.Tensor]] = None
         self._transposed_version = None
-        self._grad_hook = None     # callable(block) at the end of the block's backward (its gradients are final)
+        self.weight_twins = True   # False (use_weight_twins): a frozen base trains without the transposed copies, its input gradients read the forward weights
+        self._grad_hook = None    # callable(block) at the end of the block's backward (its gradients are final)
         self._pre_forward = None   # callable(block) before the block's forward / backward: sharded training gathers the parameters there
         self._pre_backward = None
         self._param_src: Optional[torch.Tensor] = None  # sharded training: the all-gathered parameters to compute with instead of ``flat``
@@ -648,6 +649,19 @@ class MI355XWanBlock(nn.Module):
             self._transposed = {n: ops.transpose_bf16(self.param(n)) for n in names}
             self._transposed_version = ver
         return self._transposed
+
+    def use_weight_twins(self, enabled: bool) -> None:
+        """``False``: the frozen-base backward passes no transposed twins (``ftmi_wan_lora_ffn_block_backward`` with NULL ``w_*_t``: the NN GEMM reads the
+        forward weights) and the cached ones are dropped.  Only the C call over a frozen base has that path."""
+        if not enabled:
+            if not self.frozen:
+                raise ValueError("Wan block: training without weight twins needs a frozen base (add_adapter / freeze_base); the full fine-tune transposes per call")
+            if not self.native:
+                raise ValueError("Wan block: the per-launch Python composition has no twin-less path; use the native block calls")
+            if self.ffn_dim % 128:
+                raise ValueError("Wan block: training without weight twins needs a feed-forward width that is a multiple of 128")
+            self._transposed, self._transposed_version = None, None
+        self.weight_twins = bool(enabled)
 
     _epoch = 0
 
@@ -746,6 +760,8 @@ class MI355XWanBlock(nn.Module):
             raise NotImplementedError("Wan image-to-video: full fine-tuning is not covered; attach adapters (add_adapter) or freeze the base (freeze_base)")
         if self.frozen:  # every LoRA configuration: adapters or none, image context or none, feed-forward adapters or none
             fn = _WanLoRABlockNativeFunction if self.native else _WanLoRABlockFunction
+            if not self.weight_twins and not self.native:
+                raise ValueError("Wan block: the per-launch Python composition has no twin-less path; use the native block calls")
             img = None if encoder_hidden_states_image is None else encoder_hidden_states_image.detach().contiguous()
             ffn = (None,) * 4 if self.lora_ffn is None else tuple(self.lora_ffn)
             return fn.apply(self, hidden_states.contiguous(), encoder_hidden_states.contiguous(), temb.contiguous(), rotary[0], rotary[1], self.lora_A, self.lora_B,

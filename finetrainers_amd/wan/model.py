@@ -192,16 +192,19 @@ def _dgelu(dy: torch.Tensor, pre: torch.Tensor) -> torch.Tensor:
 
 
 class _FrozenLinearFunction(torch.autograd.Function):
-    """y = x W^T + b over FROZEN W, b (LoRA training: the root's output projection): input gradient only, against a cached K-contiguous twin of W."""
+    """y = x W^T + b over FROZEN W, b (LoRA training: the root's output projection): input gradient only, against a cached K-contiguous twin of W -- or,
+    ``w_t`` None (use_weight_twins(False)), against W itself through the NN GEMM."""
 
     @staticmethod
     def forward(ctx, x, w, b, w_t):
-        ctx.w_t, ctx.xshape = w_t, x.shape
+        ctx.w, ctx.w_t, ctx.xshape = w, w_t, x.shape
         return ops.gemm_nt(x.reshape(-1, x.shape[-1]), w, b).view(*x.shape[:-1], w.shape[0])
 
     @staticmethod
     def backward(ctx, dy):
-        return ops.gemm_nt(dy.reshape(-1, dy.shape[-1]).contiguous(), ctx.w_t, None).view(ctx.xshape), None, None, None
+        dy2d = dy.reshape(-1, dy.shape[-1]).contiguous()
+        dx = ops.gemm_nn(dy2d, ctx.w) if ctx.w_t is None else ops.gemm_nt(dy2d, ctx.w_t, None)
+        return dx.view(ctx.xshape), None, None, None
 
 
 class _LnModFunction(torch.autograd.Function):
@@ -276,6 +279,7 @@ class MI355XWanTransformer3DModel(nn.Module):
         self._anchor = torch.zeros(1, dtype=bf16, device=dev, requires_grad=True)  # tells autograd that the graph has trainable inputs
         self.lora_config: Optional[Dict[str, object]] = None  # set by add_adapter: {"r", "lora_alpha", "target_modules"}
         self._proj_out_t: Optional[torch.Tensor] = None       # LoRA training: the frozen output projection's K-contiguous twin
+        self.weight_twins = True                              # use_weight_twins(False): no transposed copy of any frozen weight is made or kept
         # control LoRA: the full-rank adapter of the (widened) patch embedding, fp32 [r, Kp] / [D, r] with r = D; state-dict shapes are the Conv3d ones
         self.patch_lora_A: Optional[nn.Parameter] = None
         self.patch_lora_B: Optional[nn.Parameter] = None
@@ -336,6 +340,20 @@ class MI355XWanTransformer3DModel(nn.Module):
         return [("root", self.root.data, self.root_grad)] + [(f"blocks.{i}", b.flat.data, b.grad_flat) for i, b in enumerate(self.blocks)]
 
     # -- LoRA over the frozen base ------------------------------------------------------------------------------------------------------------
+    def use_weight_twins(self, enabled: bool) -> None:
+        """``True`` (the default): every frozen weight keeps a transposed twin for its input-gradient GEMM (8 D^2 + 2 D F bf16 values per block).  ``False``:
+        no twin is made or kept -- the blocks' backward passes NULL twins to the C call and the frozen output projection's input gradient reads
+        ``proj_out.weight``, both through the NN GEMM (``ops.gemm_nn``); same rounding points, not the same bits.  Holds for every LoRA configuration
+        (text-to-video, image-to-video, first/last-frame, control, feed-forward adapters, with and without gradient checkpointing).  A model that trains its
+        base (full fine-tune, sharded) or runs the per-launch Python composition raises ValueError."""
+        if not enabled and (self.lora_config is None and not all(b.frozen for b in self.blocks)):
+            raise ValueError("use_weight_twins(False) needs a frozen base (add_adapter): the full fine-tune transposes its weights inside every backward call")
+        for blk in self.blocks:
+            blk.use_weight_twins(enabled)
+        self.weight_twins = bool(enabled)
+        if not enabled:
+            self._proj_out_t = None
+
     def linear_module_names(self) -> List[str]:
         """The diffusers names of every module of this model peft could wrap (the Conv3d patch embedding and every Linear), in ``named_modules`` order:
         what a ``target_modules`` is resolved against."""
@@ -591,7 +609,7 @@ class MI355XWanTransformer3DModel(nn.Module):
         for blk in self.blocks:
             x = blk(x, enc, tproj, rope, enc_img)
         y = _LnModFunction.apply(x, shift, scale, c.eps)
-        if self._proj_out_t is None:
+        if self._proj_out_t is None and self.weight_twins:
             self._proj_out_t = ops.transpose_bf16(self.rparam("proj_out.weight"))
         y = _FrozenLinearFunction.apply(y, self.rparam("proj_out.weight"), self.rparam("proj_out.bias"), self._proj_out_t)
         out = y.reshape(B, f, h, w, pt, ph, pw, -1).permute(0, 7, 1, 4, 2, 5, 3, 6).reshape(B, -1, F_, H, W)

@@ -286,6 +286,26 @@ typedef struct ftmi_gemm_tn_args {
     long u_bstride, v_bstride, c_bstride;
 } ftmi_gemm_tn_args;
 int ftmi_gemm_tn_ex(const ftmi_gemm_tn_args* args, ftmi_stream stream);
+/* The NN GEMM: the input gradient of a linear layer against the weight AS THE FORWARD READS IT -- autograd's grad_input of F.linear / peft lora.Linear
+ * (grad_output @ weight) without a transposed copy of the weight:
+ *   out[M, K] = epi( bf(dy[M, N] w[N, K])  (+ x2[M, K2] w2[K, K2]^T  when K2 > 0) )
+ * dy (row stride lddy) and w (row stride ldw, the reduction index is its ROW) are row-major bf16; x2 / w2 are the LoRA K-extension in the NT operand layout
+ * (dxa [M, 3 n r], at_ext [K, ld_ext]).  Rounding points are those of ftmi_gemm_nt_ex: y = bf(dy w); with an extension y = bf(y) + x2 w2^T; epilogue 0:
+ * out = bf(y); epilogue 3: out = bf(bf(y) * gelu_tanh'(aux)), aux [M, K] with row stride ldaux.  No bias, no residual epilogue, no column groups.
+ * Any M >= 1 (nothing is stored past row M); N % 64 == 0, K % 128 == 0, K2 % 64 == 0 and epilogue in {0, 3}, else FTMI_ERR_UNSUPPORTED; a null tensor,
+ * epilogue 3 without aux, a pointer off 16 bytes, a row stride off 8 elements or shorter than its row: FTMI_ERR_INVALID.  Nothing is launched on a refusal. */
+typedef struct ftmi_gemm_nn_args {
+    const void* dy; long lddy;
+    const void* w; long ldw;
+    int M, N, K;
+    const void* x2; long ldx2;
+    const void* w2; long ldw2;
+    int K2;
+    const void* aux; long ldaux;
+    void* out; long ldo;
+    int epilogue;
+} ftmi_gemm_nn_args;
+int ftmi_gemm_nn(const ftmi_gemm_nn_args* args, ftmi_stream stream);
 /* fp8 weight storage of the layerwise up-casting recipe (finetrainers/trainer/sft_trainer/trainer.py:111-118: storage float8_e4m3fn, compute bf16):
  * dst (bf16) = exact up-cast of src [rows, cols] (OCP e4m3fn bytes); transpose != 0: dst is [cols, rows] = src^T (rows, cols multiples of 64) -- the layout
  * the input-gradient GEMMs read.  Called per block right before it runs; 1 byte read + 2 bytes written per weight.  rows or cols <= 0: returns 0 without a
@@ -806,7 +826,8 @@ int ftmi_wan_block_backward(const ftmi_wan_block_config* cfg, const void* params
  * lora_b [8, D, r] sit on attn1.to_q, to_k, to_v, to_out.0, attn2.to_q, to_k, to_v, to_out.0 (in this order) and every projection computes
  * x W^T + b + lora_scale (x A^T) B^T.  params: the flat bf16 buffer as above; w_*_t: K-contiguous (transposed) twins of the seven weight matrices, backward
  * only -- [D, 3D] of attn1 q|k|v, [D, D] of attn1.to_out.0, attn2.to_q, [D, 2D] of attn2 k|v, [D, D] of attn2.to_out.0, [D, F] of ffn.net.0.proj, [F, D] of
- * ffn.net.2.  x [B, S, D], enc [B, T, D] bf16, mod fp32 [B, 6, D], rope_cos / rope_sin fp32 [S, 64] as above.
+ * ffn.net.2.  ALL SEVEN w_*_t NULL: the backward needs no twins -- every input gradient runs as ftmi_gemm_nn against the forward weights in params (same
+ * rounding points, not the same bits; F % 128 == 0); some of them NULL is refused.  x [B, S, D], enc [B, T, D] bf16, mod fp32 [B, 6, D], rope_cos / rope_sin fp32 [S, 64] as above.
  * `saved` (ftmi_wan_lora_ffn_block_saved_bytes; smaller than the full fine-tune's by B S (3D + F) 2 bytes, larger by the down-projected rows) lives from the
  * forward to the backward of the block, or is rebuilt inside the backward by calling the forward with out = NULL (gradient checkpointing: the recomputation
  * pass refills `saved` with the identical kernel sequence, the feed-forward adapters' rows included); `scratch` (ftmi_wan_lora_ffn_block_scratch_bytes, both

@@ -211,6 +211,8 @@ def build_wan_lora(args, par, dev) -> Dict[str, Any]:
     ckpt = bool(getattr(args, "gradient_checkpointing", False))
     if ckpt:
         model.apply_activation_checkpointing("full")
+    if getattr(args, "no_weight_twins", False):  # --no-weight-twins: input gradients through ftmi_gemm_nn against the forward weights
+        model.use_weight_twins(False)
     with torch.no_grad():
         for blk in model.blocks:
             blk.lora_B[:, :, :args.rank].normal_(0, 0.01, generator=g)  # B != 0 so every gradient path carries data
@@ -338,6 +340,8 @@ def build_wan_i2v_lora(args, par, dev) -> Dict[str, Any]:
         blk.mark_updated()
     model.add_adapter(args.rank, float(args.rank))
     model.apply_activation_checkpointing("full")
+    if getattr(args, "no_weight_twins", False):
+        model.use_weight_twins(False)
     with torch.no_grad():
         for p in model.lora_parameters()[1::2]:
             p[:, :, :args.rank].normal_(0, 0.01, generator=g)
@@ -976,6 +980,8 @@ def main() -> None:
     ap.add_argument("--rank", type=int, default=32)
     ap.add_argument("--gradient-checkpointing", dest="gradient_checkpointing", action="store_true")
     ap.add_argument("--ffn-adapters", dest="ffn_adapters", action="store_true", help="wan_lora / ltx_lora: adapters on the two feed-forward projections as well (ten per block)")
+    ap.add_argument("--no-weight-twins", dest="no_weight_twins", action="store_true",
+                    help="wan_lora / wan_i2v_lora: no transposed copies of the frozen weights (use_weight_twins(False): input gradients through ftmi_gemm_nn)")
     ap.add_argument("--text-adapters", dest="text_adapters", action="store_true",
                     help="hunyuan / hy_sample: the shipped recipe's target_modules -- adapters on add_q_proj / add_k_proj / add_v_proj / to_add_out of the dual-stream blocks too")
     ap.add_argument("--scheduler", choices=("euler", "unipc", "dpm"), default="euler",
