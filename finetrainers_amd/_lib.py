@@ -304,6 +304,16 @@ class GemmNnArgs(Structure):
     ]
 
 
+class GemmW8Args(Structure):
+    """include/ftmi355.h: ftmi_gemm_w8_args."""
+
+    _fields_ = [
+        ("x", c_void_p), ("ldx", c_long), ("w8", c_void_p), ("ldw8", c_long), ("bias", c_void_p), ("M", c_int), ("N", c_int), ("K", c_int),
+        ("x2", c_void_p), ("ldx2", c_long), ("w2", c_void_p), ("ldw2", c_long), ("K2", c_int),
+        ("out", c_void_p), ("ldo", c_long), ("out2", c_void_p), ("ldo2", c_long), ("epilogue", c_int),
+    ]
+
+
 _SIGS = {
     "ftmi_version": (c_int, []),
     "ftmi_last_error": (c_int, [c_char_p, c_size_t]),
@@ -337,6 +347,10 @@ _SIGS = {
     "ftmi_gemm_nt_route": (c_int, [POINTER(GemmNtArgs), POINTER(c_int)]),
     "ftmi_gemm_tn_ex": (c_int, [POINTER(GemmTnArgs), c_void_p]),
     "ftmi_gemm_nn": (c_int, [POINTER(GemmNnArgs), c_void_p]),
+    "ftmi_gemm_nt_w8": (c_int, [POINTER(GemmW8Args), c_void_p]),
+    "ftmi_gemm_nn_w8": (c_int, [POINTER(GemmNnArgs), c_void_p]),
+    "ftmi_linear_lora_w8_fwd": (c_int, [c_int, c_int, c_int, c_int, c_float] + [c_void_p] * 7 + [c_void_p]),
+    "ftmi_linear_lora_w8_bwd": (c_int, [c_int, c_int, c_int, c_int, c_float] + [c_void_p] * 10 + [c_void_p]),
     "ftmi_fp8_upcast": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "ftmi_transpose_bf16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "ftmi_norm_modulate_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p]),

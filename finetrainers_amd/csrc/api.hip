@@ -460,6 +460,67 @@ int ftmi_linear_lora_bwd(int M, int K, int N, int r, float lora_scale, const voi
     return 0;
 }
 
+int ftmi_gemm_nt_w8(const ftmi_gemm_w8_args* p, ftmi_stream stream) {
+    if (!p) return set_error(FTMI_ERR_INVALID, "ftmi_gemm_nt_w8: null argument block");
+    GemmW8Args a;
+    a.X = (const bf16_t*)p->x; a.ldx = p->ldx; a.W8 = (const uint8_t*)p->w8; a.ldw8 = p->ldw8; a.bias = (const bf16_t*)p->bias; a.M = p->M; a.N = p->N; a.K = p->K;
+    a.X2 = (const bf16_t*)p->x2; a.ldx2 = p->ldx2; a.W2 = (const bf16_t*)p->w2; a.ldw2 = p->ldw2; a.K2 = p->K2;
+    a.out = (bf16_t*)p->out; a.ldo = p->ldo; a.out2 = (bf16_t*)p->out2; a.ldo2 = p->ldo2; a.epi = p->epilogue;
+    return gemm_nt_w8(a, (hipStream_t)stream);
+}
+
+int ftmi_gemm_nn_w8(const ftmi_gemm_nn_args* p, ftmi_stream stream) {
+    if (!p) return set_error(FTMI_ERR_INVALID, "ftmi_gemm_nn_w8: null argument block");
+    GemmW8Args a;
+    a.X = (const bf16_t*)p->dy; a.ldx = p->lddy; a.W8 = (const uint8_t*)p->w; a.ldw8 = p->ldw; a.M = p->M; a.N = p->N; a.K = p->K;
+    a.X2 = (const bf16_t*)p->x2; a.ldx2 = p->ldx2; a.W2 = (const bf16_t*)p->w2; a.ldw2 = p->ldw2; a.K2 = p->K2;
+    a.aux = (const bf16_t*)p->aux; a.ldaux = p->ldaux; a.out = (bf16_t*)p->out; a.ldo = p->ldo; a.epi = p->epilogue;
+    return gemm_nn_w8(a, (hipStream_t)stream);
+}
+
+// the main GEMM of the two calls below; dxa / xa [M, 3 r] and the ext operand [output width, 3 r] as lora_down_call and ftmi_lora_split lay them out
+static GemmW8Args linear_w8_args(int M, int K, int N, int r, const void* act, long ldact, const void* w8, const void* x2, const void* w2, void* out, long ldo) {
+    GemmW8Args a;
+    a.X = (const bf16_t*)act; a.ldx = ldact; a.W8 = (const uint8_t*)w8; a.ldw8 = K; a.M = M; a.N = N; a.K = K; a.out = (bf16_t*)out; a.ldo = ldo;
+    if (r > 0) { a.X2 = (const bf16_t*)x2; a.ldx2 = 3 * r; a.W2 = (const bf16_t*)w2; a.ldw2 = 3 * r; a.K2 = 3 * r; }
+    return a;
+}
+
+int ftmi_linear_lora_w8_fwd(int M, int K, int N, int r, float lora_scale, const void* x, const void* w8, const void* bias, const void* a_sp,
+                            const void* b_ext, void* y, void* xa_out, ftmi_stream stream) {
+    if (!x || !w8 || !y) return set_error(FTMI_ERR_INVALID, "ftmi_linear_lora_w8_fwd: null tensor");
+    if (r > 0 && (!a_sp || !b_ext || !xa_out)) return set_error(FTMI_ERR_INVALID, "ftmi_linear_lora_w8_fwd: LoRA tensors missing");
+    if (r < 0 || (r % 64)) return set_error(FTMI_ERR_UNSUPPORTED, "ftmi_linear_lora_w8_fwd: rank must be 0 or a multiple of 64");
+    hipStream_t st = (hipStream_t)stream;
+    GemmW8Args a = linear_w8_args(M, K, N, r, x, K, w8, xa_out, b_ext, y, N);
+    a.bias = (const bf16_t*)bias;
+    FTMI_TRY(gemm_w8_refuse(a, false));  // before the down-projection: nothing is launched on a refusal
+    if (r > 0) FTMI_TRY(lora_down_call((const bf16_t*)x, K, M, (const bf16_t*)a_sp, r, K, lora_scale, (bf16_t*)xa_out, st));
+    return gemm_nt_w8(a, st);
+}
+
+int ftmi_linear_lora_w8_bwd(int M, int K, int N, int r, float lora_scale, const void* x, const void* dy, const void* xa, const void* w8,
+                            const void* bt_sp, const void* at_ext, void* dxa_ws, void* dx, float* grad_a, float* grad_b, ftmi_stream stream) {
+    if (!dy || (dx && !w8)) return set_error(FTMI_ERR_INVALID, "ftmi_linear_lora_w8_bwd: null tensor");
+    if (r < 0 || (r % 64)) return set_error(FTMI_ERR_UNSUPPORTED, "ftmi_linear_lora_w8_bwd: rank must be 0 or a multiple of 64");
+    if (r > 0 && (!x || !xa || !bt_sp || !at_ext || !dxa_ws || !grad_a || !grad_b))
+        return set_error(FTMI_ERR_INVALID, "ftmi_linear_lora_w8_bwd: LoRA tensors missing");
+    hipStream_t st = (hipStream_t)stream;
+    const GemmW8Args a = linear_w8_args(M, K, N, r, dy, N, w8, dxa_ws, at_ext, dx, K);  // dx = dy W (+ dxa A as a K-extension)
+    if (dx) FTMI_TRY(gemm_w8_refuse(a, true));
+    if (r > 0) FTMI_TRY(lora_down_call((const bf16_t*)dy, N, M, (const bf16_t*)bt_sp, r, N, lora_scale, (bf16_t*)dxa_ws, st));  // dxa = s * dy B, fp32-equivalent
+    if (dx) FTMI_TRY(gemm_nn_w8(a, st));
+    if (r > 0) {
+        GemmTnArgs t;  // dB += dy^T xa   (xa = hi + lo planes)
+        t.U = (const bf16_t*)dy; t.ldu = N; t.V = (const bf16_t*)xa; t.ldv = 3 * r; t.v_fold = r; t.C = grad_b; t.ldc = r; t.M = M; t.P = N; t.Q = r;
+        FTMI_TRY(gemm_tn(t, st));
+        GemmTnArgs u;  // dA += dxa^T x
+        u.U = (const bf16_t*)dxa_ws; u.ldu = 3 * r; u.u_fold = r; u.V = (const bf16_t*)x; u.ldv = K; u.C = grad_a; u.ldc = K; u.M = M; u.P = r; u.Q = K;
+        FTMI_TRY(gemm_tn(u, st));
+    }
+    return 0;
+}
+
 int ftmi_norm_modulate_fwd(const void* x, const void* shift, const void* onep, long mod_bstride, void* y, int rows, int rows_per_batch, int D,
                            float eps, int layernorm, ftmi_stream stream) {
     if (!x || !shift || !onep || !y || rows <= 0 || rows_per_batch <= 0) return set_error(FTMI_ERR_INVALID, "ftmi_norm_modulate_fwd: bad argument");

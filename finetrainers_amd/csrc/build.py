@@ -9,7 +9,7 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ["gemm.hip", "gemm_nn.hip", "attention.hip", "attn_ctx2.hip", "attn_carry.hip", "rowwise.hip", "cast.hip", "cogvideox.hip", "ltx_dit.hip", "ltx_sample.hip", "cog_dit.hip", "hy_dit.hip", "wan.hip", "wan_dit.hip", "wan_control.hip", "sample_layout.hip", "wan_sample_dit.hip", "hy_sample_dit.hip", "collective.hip", "api.hip"]
+SOURCES = ["gemm.hip", "gemm_nn.hip", "gemm_w8.hip", "attention.hip", "attn_ctx2.hip", "attn_carry.hip", "rowwise.hip", "cast.hip", "cogvideox.hip", "ltx_dit.hip", "ltx_sample.hip", "cog_dit.hip", "hy_dit.hip", "wan.hip", "wan_dit.hip", "wan_control.hip", "sample_layout.hip", "wan_sample_dit.hip", "hy_sample_dit.hip", "collective.hip", "api.hip"]
 HEADERS = ["common.hip.h", "kernels.h", "lora_proj.hip.h", "sample_step.hip.h", os.path.join("..", "..", "include", "ftmi355.h"), "attention_pl.hip.h"]
 HEADERS += sorted(f for f in os.listdir(HERE) if f.startswith("attn_pl_") and f.endswith(".inc"))  # generated statement lists (tools/gen_attn_pl.py)
 LIB = os.path.join(HERE, "..", "libftmi355.so")
@@ -37,6 +37,9 @@ EXTRA_FLAGS["attn_carry.hip"] = ["-mllvm", "-amdgpu-mfma-vgpr-form", "-Xclang", 
 # 128 v_pk_add_f32 and 256 v_pk_fma_f32 across the two epilogue-3 instances; with it there is none.  Registers with / without the switch: 80 / 80, 164 / 161,
 # 210 / 200, 244 / 228 VGPRs (+ 128 AGPRs), no scratch either way; the epilogue's time difference is not measured.
 EXTRA_FLAGS["gemm_nn.hip"] = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+# gemm_w8: the same switch for the same reason (its GELU and GELU' epilogues run gelu_tanh_f / gelu_tanh_grad_f over four columns at a time, which hipcc
+# would otherwise pack).  Registers with the switch: DESIGN 7-AA; no scratch in any of the eight instances.
+EXTRA_FLAGS["gemm_w8.hip"] = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 # FTMI_EXPERIMENTAL=1: also compile the research K loops / timing experiments of tools/experimental/gemm_experimental.hip.h (tools/bench_gemm.py,
 # tools/ab_variants.sh).  Never set for the product library.
 if os.environ.get("FTMI_EXPERIMENTAL", "0") not in ("", "0"):

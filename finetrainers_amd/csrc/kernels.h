@@ -199,6 +199,33 @@ struct GemmNnArgs {
     int epi = EPI_STORE;
 };
 int gemm_nn(const GemmNnArgs& a, hipStream_t st);
+// GEMMs over e4m3fn-stored weights (gemm_w8.hip): W8 [N, ldw8] bytes as the forward stores them, ldw8 in bytes; everything else bf16.
+//   gemm_nt_w8: out [M, N] = epi(bf(X [M, K] . W8^T + bias) (+ X2 [M, K2] . W2 [N, K2]^T));  epi EPI_STORE, or EPI_GELU with out2 = bf(y)
+//   gemm_nn_w8: out [M, K] = epi(bf(X [M, N] . W8)          (+ X2 [M, K2] . W2 [K, K2]^T));  epi EPI_STORE, or EPI_DGELU with aux  (gemm_nn's contract)
+// Reduction % 64, output width % 128, K2 % 64.  gemm_w8_refuse: the launchers' refusals alone (0: the launch may go), without a call into the runtime.
+struct GemmW8Args {
+    const bf16_t* X = nullptr;  // [M, ldx]: x (NT) / dY (NN)
+    long ldx = 0;
+    const uint8_t* W8 = nullptr;  // [N, ldw8]
+    long ldw8 = 0;
+    const bf16_t* bias = nullptr;  // NT: [N] or null
+    int M = 0, N = 0, K = 0;
+    const bf16_t* X2 = nullptr;  // [M, ldx2]
+    long ldx2 = 0;
+    const bf16_t* W2 = nullptr;  // [output width, ldw2]
+    long ldw2 = 0;
+    int K2 = 0;
+    const bf16_t* aux = nullptr;  // NN, EPI_DGELU: pre-activation [M, ldaux]
+    long ldaux = 0;
+    bf16_t* out = nullptr;  // [M, ldo]
+    long ldo = 0;
+    bf16_t* out2 = nullptr;  // NT, EPI_GELU: pre-activation [M, ldo2]
+    long ldo2 = 0;
+    int epi = EPI_STORE;
+};
+int gemm_w8_refuse(const GemmW8Args& a, bool nn);
+int gemm_nt_w8(const GemmW8Args& a, hipStream_t st);
+int gemm_nn_w8(const GemmW8Args& a, hipStream_t st);
 // fp8 (e4m3fn) weight storage: exact up-cast to bf16, plain [rows, cols] or transposed [cols, rows] (cast.hip)
 int fp8_upcast(const uint8_t* src, bf16_t* dst, int rows, int cols, int transpose, hipStream_t st);
 

@@ -320,6 +320,115 @@ def gemm_nn(dy: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = Non
     return out
 
 
+def _w8_operands(who: str, act: torch.Tensor, w8: torch.Tensor, others) -> None:
+    """The checks the two fp8-weight GEMMs share: bf16 GPU views, one float8_e4m3fn GPU weight view with contiguous columns."""
+    for n, t in (("activation", act),) + tuple((n, t) for n, t in others if t is not None):
+        require_gpu_tensor(t, n, bf16)
+    require_gpu_tensor(w8, "w8", torch.float8_e4m3fn)
+    if act.dim() != 2 or w8.dim() != 2 or w8.stride(1) != 1:
+        raise ValueError(f"{who}: the activation and w8 must be 2-D views with contiguous columns")
+
+
+def gemm_nt_w8(x: torch.Tensor, w8: torch.Tensor, bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, *, x2: Optional[torch.Tensor] = None,
+               w2: Optional[torch.Tensor] = None, gelu: bool = False):
+    """The forward GEMM over an fp8-stored weight (ftmi_gemm_nt_w8; include/ftmi355.h): out [M, N] = bf(x [M, K] @ w8 [N, K]^T + bias), the e4m3fn bytes read
+    as they are stored -- no up-cast launch, no bf16 copy.  ``x2`` [M, K2] / ``w2`` [N, K2]: the LoRA K-extension, out = bf(bf(x w8^T + bias) + x2 w2^T);
+    ``gelu``: returns (out, pre) with pre = bf(y) and out = bf(gelu_tanh(pre)).  ``w8``: a 2-D float8_e4m3fn view whose row stride travels; the rest bf16."""
+    _w8_operands("gemm_nt_w8", x, w8, (("bias", bias), ("out", out), ("x2", x2), ("w2", w2)))
+    if x.shape[1] != w8.shape[1]:
+        raise ValueError(f"gemm_nt_w8: x [M, K] and w8 [N, K] do not chain: {tuple(x.shape)} and {tuple(w8.shape)}")
+    M, K = x.shape
+    N = w8.shape[0]
+    if bias is not None and (bias.shape != (N,) or bias.stride(0) != 1):
+        raise ValueError("gemm_nt_w8: bias must be a contiguous [N] vector")
+    if (x2 is None) != (w2 is None):
+        raise ValueError("gemm_nt_w8: the K-extension needs both x2 and w2")
+    K2 = 0 if x2 is None else int(x2.shape[1])
+    if x2 is not None and (x2.shape != (M, K2) or w2.shape != (N, K2)):
+        raise ValueError(f"gemm_nt_w8: x2 must be [M, K2] and w2 [N, K2], got {tuple(x2.shape)} and {tuple(w2.shape)}")
+    if out is None:
+        out = torch.empty((M, N), dtype=bf16, device=x.device)
+    elif out.shape != (M, N):
+        raise ValueError("gemm_nt_w8: out must be an [M, N] bf16 view with contiguous columns")
+    pre = torch.empty((M, N), dtype=bf16, device=x.device) if gelu else None
+    a = _lib.GemmW8Args()
+    a.x, a.ldx, a.w8, a.ldw8, a.bias, a.M, a.N, a.K = ptr(x), _ld(x, "x"), ptr(w8), _ld(w8, "w8"), ptr(bias), M, N, K
+    a.x2, a.ldx2, a.w2, a.ldw2, a.K2 = ptr(x2), _ld(x2, "x2"), ptr(w2), _ld(w2, "w2"), K2
+    a.out, a.ldo, a.out2, a.ldo2, a.epilogue = ptr(out), _ld(out, "out"), ptr(pre), _ld(pre, "pre"), (_lib.EPI_GELU if gelu else _lib.EPI_STORE)
+    check(_lib.load().ftmi_gemm_nt_w8(ctypes.byref(a), stream_ptr()), "ftmi_gemm_nt_w8")
+    return (out, pre) if gelu else out
+
+
+def gemm_nn_w8(dy: torch.Tensor, w8: torch.Tensor, out: Optional[torch.Tensor] = None, *, x2: Optional[torch.Tensor] = None, w2: Optional[torch.Tensor] = None,
+               aux: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``gemm_nn`` over the same fp8-stored weight the forward reads (ftmi_gemm_nn_w8): out [M, K] = bf(dy [M, N] @ w8 [N, K]), extension and GELU' epilogue
+    as there.  ``w8``: a 2-D float8_e4m3fn view with contiguous columns whose row stride (in bytes) travels."""
+    _w8_operands("gemm_nn_w8", dy, w8, (("out", out), ("x2", x2), ("w2", w2), ("aux", aux)))
+    if dy.shape[1] != w8.shape[0]:
+        raise ValueError(f"gemm_nn_w8: dy [M, N] and w8 [N, K] do not chain: {tuple(dy.shape)} and {tuple(w8.shape)}")
+    M, N = dy.shape
+    K = w8.shape[1]
+    if (x2 is None) != (w2 is None):
+        raise ValueError("gemm_nn_w8: the K-extension needs both x2 and w2")
+    K2 = 0 if x2 is None else int(x2.shape[1])
+    if x2 is not None and (x2.shape != (M, K2) or w2.shape != (K, K2)):
+        raise ValueError(f"gemm_nn_w8: x2 must be [M, K2] and w2 [K, K2], got {tuple(x2.shape)} and {tuple(w2.shape)}")
+    if aux is not None and aux.shape != (M, K):
+        raise ValueError("gemm_nn_w8: aux must be an [M, K] view")
+    if out is None:
+        out = torch.empty((M, K), dtype=bf16, device=dy.device)
+    elif out.shape != (M, K):
+        raise ValueError("gemm_nn_w8: out must be an [M, K] bf16 view with contiguous columns")
+    a = _lib.GemmNnArgs()
+    a.dy, a.lddy, a.w, a.ldw, a.M, a.N, a.K = ptr(dy), _ld(dy, "dy"), ptr(w8), _ld(w8, "w8"), M, N, K
+    a.x2, a.ldx2, a.w2, a.ldw2, a.K2 = ptr(x2), _ld(x2, "x2"), ptr(w2), _ld(w2, "w2"), K2
+    a.aux, a.ldaux, a.out, a.ldo, a.epilogue = ptr(aux), _ld(aux, "aux"), ptr(out), _ld(out, "out"), (_lib.EPI_DGELU if aux is not None else _lib.EPI_STORE)
+    check(_lib.load().ftmi_gemm_nn_w8(ctypes.byref(a), stream_ptr()), "ftmi_gemm_nn_w8")
+    return out
+
+
+def _w8_dense(who: str, w8: torch.Tensor) -> None:
+    if w8.dtype != torch.float8_e4m3fn or w8.dim() != 2 or not w8.is_contiguous() or not w8.is_cuda:
+        raise ValueError(f"{who}: w8 must be a contiguous 2-D float8_e4m3fn tensor on the GPU")
+
+
+def linear_lora_w8_fwd(x, w8, bias, lora_a, lora_b, lora_scale: float):
+    """``linear_lora_fwd`` over an fp8-stored frozen weight ``w8`` [N, K] (float8_e4m3fn, read as stored).  Returns (y [M, N] bf16, xa [M, 3r] or None)."""
+    _w8_dense("linear_lora_w8_fwd", w8)
+    M, K = x.shape
+    N = w8.shape[0]
+    r = 0 if lora_a is None else lora_a.shape[0]
+    y = torch.empty((M, N), dtype=bf16, device=x.device)
+    xa = torch.empty((M, 3 * r), dtype=bf16, device=x.device) if r else None
+    a_sp = b_ext = None
+    if r:
+        (a_sp,) = lora_split(lora_a, sp=True)
+        (b_ext,) = lora_split(lora_b, ext=True)
+    check(_lib.load().ftmi_linear_lora_w8_fwd(M, K, N, r, float(lora_scale), ptr(x), ptr(w8), ptr(bias), ptr(a_sp), ptr(b_ext), ptr(y), ptr(xa), stream_ptr()),
+          "ftmi_linear_lora_w8_fwd")
+    return y, xa
+
+
+def linear_lora_w8_bwd(x, dy, xa, w8, lora_a, lora_b, lora_scale: float, grad_a=None, grad_b=None, need_dx: bool = True):
+    """Backward of ``linear_lora_w8_fwd`` against the SAME ``w8`` [N, K] (no transposed copy): returns (dx [M, K] bf16 or None, grad_a [r, K] fp32,
+    grad_b [N, r] fp32); the gradient buffers are accumulated into when given."""
+    _w8_dense("linear_lora_w8_bwd", w8)
+    M, N = dy.shape
+    K = w8.shape[1]
+    r = 0 if lora_a is None else lora_a.shape[0]
+    dx = torch.empty((M, K), dtype=bf16, device=dy.device) if need_dx else None
+    dxa = torch.empty((M, 3 * r), dtype=bf16, device=dy.device) if r else None
+    bt_sp = at_ext = None
+    if r:
+        (at_ext,) = lora_split(lora_a, t_ext=True)
+        (bt_sp,) = lora_split(lora_b, t_sp=True)
+        grad_a = torch.zeros((r, K), dtype=torch.float32, device=dy.device) if grad_a is None else grad_a
+        grad_b = torch.zeros((N, r), dtype=torch.float32, device=dy.device) if grad_b is None else grad_b
+    check(_lib.load().ftmi_linear_lora_w8_bwd(M, K, N, r, float(lora_scale), ptr(x), ptr(dy), ptr(xa), ptr(w8), ptr(bt_sp), ptr(at_ext), ptr(dxa), ptr(dx),
+                                               ptr(grad_a), ptr(grad_b), stream_ptr()), "ftmi_linear_lora_w8_bwd")
+    return dx, grad_a, grad_b
+
+
 def fp8_upcast(w8: torch.Tensor, out: Optional[torch.Tensor] = None, transpose: bool = False) -> torch.Tensor:
     """bf16 copy of a [rows, cols] ``torch.float8_e4m3fn`` weight (exact), optionally transposed to [cols, rows]; ``out``: a contiguous bf16 tensor of the
     result's size (e.g. a slice of a per-model weight arena)."""

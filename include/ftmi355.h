@@ -29,6 +29,8 @@
  *                                        (trainer/sft_trainer/trainer.py:121-136 injects them) and the autograd
  *                                        backward the reference gets from loss.backward() (trainer.py:481): dgrad to
  *                                        the input, weight gradients of A and B only (the base weight is frozen)
+ *   ftmi_linear_lora_w8_fwd / _bwd ..... the same over a weight STORED as float8_e4m3fn (trainer.py:111-118, layerwise
+ *                                        up-casting): ftmi_gemm_nt_w8 / ftmi_gemm_nn_w8 read the bytes, no bf16 copy
  */
 #ifndef FTMI355_H
 #define FTMI355_H
@@ -306,6 +308,44 @@ typedef struct ftmi_gemm_nn_args {
     int epilogue;
 } ftmi_gemm_nn_args;
 int ftmi_gemm_nn(const ftmi_gemm_nn_args* args, ftmi_stream stream);
+/* GEMMs that read e4m3fn-STORED weights (the layerwise up-casting recipe: storage float8_e4m3fn, compute bf16) without an up-cast launch or a bf16 copy: the
+ * weight operand is w8 [N, ldw8], row-major OCP e4m3fn bytes as the forward stores them, ldw8 in BYTES; ONE copy serves both directions.  The bytes are
+ * converted to bf16 in registers, exactly (all 254 non-NaN codes, subnormals included; 0x7f / 0xff give NaN), so the results are those of the bf16 kernels on
+ * ftmi_fp8_upcast(w8) up to fp32 summation order.  Everything else is bf16.
+ *   ftmi_gemm_nt_w8 (forward):        out[M, N] = epi( bf(x[M, K] w8[N, K]^T + bias)  (+ x2[M, K2] w2[N, K2]^T  when K2 > 0) )
+ *     rounding points of ftmi_gemm_nt_ex: y = bf(x w8^T + bias); with an extension y = bf(y) + x2 w2^T; epilogue 0: out = bf(y); epilogue 1 (GELU, tanh form):
+ *     out2 = bf(y), out = bf(gelu(out2)).  bias [N] may be NULL.  No alpha, no residual / gate epilogue, no column groups.
+ *     Any M >= 1; N % 128 == 0, K % 64 == 0, K2 % 64 == 0, epilogue in {0, 1}.
+ *   ftmi_gemm_nn_w8 (input gradient): out[M, K] = epi( bf(dy[M, N] w8[N, K])  (+ x2[M, K2] w2[K, K2]^T) ) -- ftmi_gemm_nn's contract (epilogues 0 and 3, its
+ *     shape rules) with args->w pointing at the bytes and args->ldw in bytes.
+ * Refusals, in ftmi_gemm_nn's order, texts prefixed with the entry's name; nothing is launched and the runtime is not called on a refusal.
+ * FTMI_ERR_INVALID: a null tensor, an epilogue without its side tensor (1: out2, 3: aux), an extension without its operands, a pointer off 16 bytes, a bf16
+ * row stride off 8 elements or an fp8 row stride off 16 bytes, a stride shorter than its row.  FTMI_ERR_UNSUPPORTED: a shape off the multiples above, an
+ * unknown epilogue, a stride too large for the 32-bit offsets inside one tile. */
+typedef struct ftmi_gemm_w8_args {
+    const void* x; long ldx;
+    const void* w8; long ldw8;
+    const void* bias;
+    int M, N, K;
+    const void* x2; long ldx2;
+    const void* w2; long ldw2;
+    int K2;
+    void* out; long ldo;
+    void* out2; long ldo2;
+    int epilogue;
+} ftmi_gemm_w8_args;
+int ftmi_gemm_nt_w8(const ftmi_gemm_w8_args* args, ftmi_stream stream);
+int ftmi_gemm_nn_w8(const ftmi_gemm_nn_args* args, ftmi_stream stream);
+/* ftmi_linear_lora_fwd / _bwd (above) over an fp8-stored frozen weight: both take the SAME w8 [N, K] bytes (dense, row stride K) -- no w_t, no bf16 copy.
+ * The forward's GEMM is ftmi_gemm_nt_w8, the backward's dx is ftmi_gemm_nn_w8; the down-projections and the two weight-gradient launches are those of the
+ * bf16 pair, unchanged.  r == 0: the plain frozen linear.  K % 128 == 0 and N % 128 == 0 (each is a reduction depth in one direction and an output width in
+ * the other).  Refused before the first launch: a null tensor, missing LoRA tensors (FTMI_ERR_INVALID), a rank that is neither 0 nor a multiple of 64
+ * (FTMI_ERR_UNSUPPORTED), then whatever the GEMM entry refuses. */
+int ftmi_linear_lora_w8_fwd(int M, int K, int N, int r, float lora_scale, const void* x, const void* w8, const void* bias,
+                            const void* a_sp, const void* b_ext, void* y, void* xa_out, ftmi_stream stream);
+int ftmi_linear_lora_w8_bwd(int M, int K, int N, int r, float lora_scale, const void* x, const void* dy, const void* xa,
+                            const void* w8, const void* bt_sp, const void* at_ext, void* dxa_ws, void* dx, float* grad_a,
+                            float* grad_b, ftmi_stream stream);
 /* fp8 weight storage of the layerwise up-casting recipe (finetrainers/trainer/sft_trainer/trainer.py:111-118: storage float8_e4m3fn, compute bf16):
  * dst (bf16) = exact up-cast of src [rows, cols] (OCP e4m3fn bytes); transpose != 0: dst is [cols, rows] = src^T (rows, cols multiples of 64) -- the layout
  * the input-gradient GEMMs read.  Called per block right before it runs; 1 byte read + 2 bytes written per weight.  rows or cols <= 0: returns 0 without a
