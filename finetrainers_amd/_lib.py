@@ -328,6 +328,9 @@ _SIGS = {
     "ftmi_attn_ctx2w_dq": (c_int, [POINTER(AttnDesc)] + [c_void_p] * 8),
     "ftmi_attn_fwd_carry": (c_int, [POINTER(AttnDesc)] + [c_void_p] * 7 + [c_int, c_void_p]),
     "ftmi_accum_bf16": (c_int, [POINTER(AttnDesc)] + [c_void_p] * 4),
+    "ftmi_attn_q8_workspace_bytes": (c_size_t, [POINTER(AttnDesc)]),
+    "ftmi_attn_q8_quant": (c_int, [POINTER(AttnDesc), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "ftmi_attn_fwd_q8": (c_int, [POINTER(AttnDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     "ftmi_linear_lora_fwd": (c_int, [c_int, c_int, c_int, c_int, c_float] + [c_void_p] * 7 + [c_int, c_void_p]),
     "ftmi_linear_lora_bwd": (c_int, [c_int, c_int, c_int, c_int, c_float] + [c_void_p] * 10 + [c_int, c_void_p]),
     "ftmi_gemm_nt_plan": (c_int, [c_int, c_int, c_int, c_int, c_int]),

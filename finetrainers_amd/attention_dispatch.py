@@ -2,8 +2,8 @@
 
 Mirror of the reference's operator plugin point (finetrainers/models/attention_dispatch.py): the same
 registry class, decorator, context manager and ``attention_dispatch(query, key, value, attn_mask, dropout_p,
-is_causal, scale, enable_gqa, attention_kwargs)`` entry, with ONE provider registered -- ``mi355x`` -- that runs
-``ftmi_attn_fwd`` / ``ftmi_attn_bwd``.  The reference's other providers (flash / sage / xformers / flex / ATen
+is_causal, scale, enable_gqa, attention_kwargs)`` entry, with the provider ``mi355x`` that runs ``ftmi_attn_fwd`` / ``ftmi_attn_bwd`` and its
+inference-only sibling ``mi355x_sage`` (``ftmi_attn_fwd_q8``: int8 scores, fp8 weights; the reference's ``--attn_provider_inference transformer:sage``).  The reference's other providers (flash / sage / xformers / flex / ATen
 variants) are deliberately absent: no multi-backend dispatch.  With the reference installed, the same function is
 registered into ITS registry by ``register_into_finetrainers()``, after which
 ``--attn_provider_training transformer:mi355x`` selects it for an unmodified diffusers model.
@@ -36,6 +36,7 @@ FINETRAINERS_ATTN_CHECKS = os.getenv("FINETRAINERS_ATTN_CHECKS", "0") in {"1", "
 
 class AttentionProvider(str, Enum):
     MI355X = "mi355x"
+    MI355X_SAGE = "mi355x_sage"  # inference only: int8 scores, fp8 weights (the reference's --attn_provider_inference transformer:sage, which is CUDA-only)
 
 
 class _AttentionProviderRegistry:
@@ -355,6 +356,23 @@ def _mi355x_attention(query: torch.Tensor, key: torch.Tensor, value: torch.Tenso
     return _MI355XAttention.apply(query, key, value, key_bias, scale)
 
 
+@_AttentionProviderRegistry.register(
+    AttentionProvider.MI355X_SAGE,
+    constraints=[_check_device_gpu, _check_qkv_dtype_bf16, _check_head_dim, _check_no_dropout_causal_gqa],
+    supports_cp=False,
+)
+def _mi355x_sage_attention(query: torch.Tensor, key: torch.Tensor, value: torch.Tensor, attn_mask: Optional[torch.Tensor] = None,
+                           dropout_p: float = 0.0, is_causal: bool = False, scale: Optional[float] = None, enable_gqa: bool = False) -> torch.Tensor:
+    """The sage providers' place (attention_dispatch.py:1651-1760): ``ftmi_attn_fwd_q8``.  Forward only -- there is no backward kernel, so a call that
+    autograd would have to differentiate is refused instead of returning a result without a graph."""
+    if dropout_p != 0.0 or is_causal or enable_gqa:
+        raise ValueError("mi355x_sage provider: dropout, causal masking and GQA are not supported")
+    if torch.is_grad_enabled() and (query.requires_grad or key.requires_grad or value.requires_grad):
+        raise ValueError("mi355x_sage provider: inference only (no backward); call it under torch.no_grad() or use the mi355x provider for training")
+    B, H, _, _ = query.shape
+    return ops.attn_fwd_q8(query, key, value, _key_bias_from_mask(attn_mask, B, H, key.shape[2]), scale)
+
+
 def register_into_finetrainers() -> bool:
     """Register the provider into the reference's own registry when finetrainers is importable (it needs an
     ``AttentionProvider`` enum member named MI355X = "mi355x").  Returns False when the reference is
@@ -369,6 +387,11 @@ def register_into_finetrainers() -> bool:
     ref._AttentionProviderRegistry.register(member, constraints=[_check_device_gpu, _check_qkv_dtype_bf16, _check_head_dim], supports_cp=True)(
         _mi355x_attention
     )
+    sage = getattr(ref.AttentionProvider, "MI355X_SAGE", None)  # optional: registered only where the reference's enum has the member
+    if sage is not None:
+        ref._AttentionProviderRegistry.register(sage, constraints=[_check_device_gpu, _check_qkv_dtype_bf16, _check_head_dim], supports_cp=False)(
+            _mi355x_sage_attention
+        )
     global _ref_registry
     _ref_registry = ref._AttentionProviderRegistry
     return True

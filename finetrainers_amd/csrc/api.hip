@@ -235,6 +235,29 @@ int ftmi_attn_bwd(const ftmi_attn_desc* desc, const void* q, const void* k, cons
     return attn_bwd(a, (hipStream_t)stream);
 }
 
+size_t ftmi_attn_q8_workspace_bytes(const ftmi_attn_desc* desc) {
+    return desc ? attn_q8_workspace_bytes(desc->B, desc->H, desc->Sq, desc->Sk, desc->d) : 0;
+}
+
+int ftmi_attn_q8_quant(const ftmi_attn_desc* desc, const void* q, const void* k, const void* v, int smooth_k, void* ws, size_t ws_bytes, ftmi_stream stream) {
+    AttnQ8Args a8;
+    int rc = fill_attn(desc, a8.a);
+    if (rc) return rc;
+    a8.a.q = (const bf16_t*)q; a8.a.k = (const bf16_t*)k; a8.a.v = (const bf16_t*)v;
+    a8.smooth_k = smooth_k; a8.ws = ws; a8.ws_bytes = ws_bytes;
+    return attn_q8_quant(a8, (hipStream_t)stream);
+}
+
+int ftmi_attn_fwd_q8(const ftmi_attn_desc* desc, const void* q, const void* k, const void* v, void* out, const float* key_bias, int smooth_k, void* ws,
+                     size_t ws_bytes, ftmi_stream stream) {
+    AttnQ8Args a8;
+    int rc = fill_attn(desc, a8.a);
+    if (rc) return rc;
+    a8.a.q = (const bf16_t*)q; a8.a.k = (const bf16_t*)k; a8.a.v = (const bf16_t*)v; a8.a.o = (bf16_t*)out; a8.a.kbias = key_bias;
+    a8.smooth_k = smooth_k; a8.ws = ws; a8.ws_bytes = ws_bytes;
+    return attn_fwd_q8(a8, (hipStream_t)stream);
+}
+
 int ftmi_attn_ctx2_fwd(const ftmi_attn_desc* desc, const void* q, const void* k, const void* v, const void* out_first, void* out, float* lse,
                        ftmi_stream stream) {
     AttnArgs a;

@@ -266,6 +266,19 @@ int attn_ctx2_dq(const AttnArgs& a, const bf16_t* dq_t, hipStream_t st);
 // the wide pair: the same contract for 1 .. 640 keys (two images: Wan first/last-frame), tile t + 1 staged under tile t; for Sk <= 320 the bits of the pair above
 int attn_ctx2w_fwd(const AttnArgs& a, const bf16_t* o_t, hipStream_t st);
 int attn_ctx2w_dq(const AttnArgs& a, const bf16_t* dq_t, hipStream_t st);
+// inference-only forward on the int8 / fp8 matrix instructions (attn_q8.hip): a.q / a.k / a.v bf16 -> int8 Q and K codes (K smoothed by its mean over the keys
+// when smooth_k), e4m3 V codes and their scales in the caller's workspace (attn_q8_quant), then a.o = softmax(q k^T scale + bias) v from those codes, no lse.
+// attn_fwd_q8 runs the pre-pass itself unless `prequantised` says the workspace already holds this problem's codes.
+struct AttnQ8Args {
+    AttnArgs a;
+    int smooth_k = 1;
+    int prequantised = 0;
+    void* ws = nullptr;
+    size_t ws_bytes = 0;
+};
+size_t attn_q8_workspace_bytes(int B, int H, int Sq, int Sk, int d);  // 0 for a problem the kernels refuse
+int attn_q8_quant(const AttnQ8Args& q, hipStream_t st);
+int attn_fwd_q8(const AttnQ8Args& q, hipStream_t st);
 #ifdef FTMI_EXPERIMENTAL
 // lab yardstick: the wide loop with the single-buffered staging of the narrow pair (profiles/wan_flf_ctx2.txt)
 int attn_ctx2w1_fwd(const AttnArgs& a, const bf16_t* o_t, hipStream_t st);

@@ -117,6 +117,79 @@ def attn_fwd_carry(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, acc: torch
     return out
 
 
+def _q8_pieces(B: int, H: int, Sq: int, Sk: int, d: int):
+    """The workspace of ``ftmi_attn_fwd_q8`` as include/ftmi355.h documents it: {name: (byte offset, bytes)} and the total, every piece rounded up to 256."""
+    nt, nc = -(-Sk // 64), -(-Sk // 256)
+    sizes = (("q8", B * H * Sq * d), ("sq", B * H * Sq * 4), ("k8", B * H * nt * 64 * d), ("sk", B * H * nt * 4), ("v8", B * H * nt * 64 * d),
+             ("sv", B * H * d * 4), ("ksum", B * H * nc * d * 4), ("vmax", B * H * nc * d * 4))
+    pieces, off = {}, 0
+    for name, n in sizes:
+        pieces[name] = (off, n)
+        off += (n + 255) & ~255
+    return pieces, off
+
+
+def _q8_operands(who: str, q, k, v, scale, key_bias=None):
+    """Shape and dtype rules first (they need no device), the device last; returns (scale, descriptor without an output, workspace)."""
+    for n, t in (("query", q), ("key", k), ("value", v)):
+        if t.dtype != bf16:
+            raise ValueError(f"{who}: {n} must be {bf16}, got {t.dtype}")
+    scale = (1.0 / q.shape[-1] ** 0.5) if scale is None else scale
+    desc = _desc(q, k, v, None, scale, key_bias=key_bias)
+    for n, t in (("query", q), ("key", k), ("value", v)):
+        require_gpu_tensor(t, n, bf16)
+    if key_bias is not None:
+        require_gpu_tensor(key_bias, "key_bias", torch.float32)
+    need = _lib.load().ftmi_attn_q8_workspace_bytes(ctypes.byref(desc))
+    if need != _q8_pieces(desc.B, desc.H, desc.Sq, desc.Sk, desc.d)[1]:
+        raise RuntimeError(f"{who}: the library plans a workspace of {need} bytes, not the documented layout; rebuild it")
+    return scale, desc, torch.empty(need, dtype=torch.uint8, device=q.device)
+
+
+def attn_fwd_q8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_bias: Optional[torch.Tensor] = None, scale: Optional[float] = None,
+                smooth_k: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Inference-only attention on the int8 / fp8 matrix instructions (``ftmi_attn_fwd_q8``; csrc/attn_q8.hip): q, k, v as for ``attn_fwd``; int8 scores
+    (K smoothed by its mean over the keys when ``smooth_k``), e4m3 weights and values, fp32 accumulation.  Returns out [B, H, Sq, d] bf16 (laid out as
+    [B, Sq, H, d], or ``out`` when given); no lse, no backward."""
+    scale, desc, ws = _q8_operands("attn_fwd_q8", q, k, v, scale, key_bias)
+    B, H, Sq, d = q.shape
+    out = _placed(out, (B, H, Sq, d), "attn_fwd_q8: out", q)
+    desc.o_strides[0], desc.o_strides[1], desc.o_strides[2] = _strides3(out)
+    check(_lib.load().ftmi_attn_fwd_q8(ctypes.byref(desc), ptr(q), ptr(k), ptr(v), ptr(out), ptr(key_bias), int(bool(smooth_k)), ptr(ws), ws.numel(),
+                                        stream_ptr()), "ftmi_attn_fwd_q8")
+    return out
+
+
+def attn_q8_quantize(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: Optional[float] = None, smooth_k: bool = True):
+    """The pre-pass of ``attn_fwd_q8`` alone (``ftmi_attn_q8_quant``), its tile images undone: (q8 [B,H,Sq,d] int8, sq [B,H,Sq], k8 [B,H,nt*64,d] int8,
+    sk [B,H,nt], v8 [B,H,nt*64,d] float8_e4m3fn, sv [B,H,d]) with nt = ceil(Sk / 64) and the keys past Sk padded.  q ~ q8 * sq per row,
+    k - mean_keys(k) ~ k8 * sk per 64 keys, v ~ v8 * sv per channel.  ``scale`` is not folded into the codes (the forward multiplies it onto sq)."""
+    scale, desc, ws = _q8_operands("attn_q8_quantize", q, k, v, scale)
+    check(_lib.load().ftmi_attn_q8_quant(ctypes.byref(desc), ptr(q), ptr(k), ptr(v), int(bool(smooth_k)), ptr(ws), ws.numel(), stream_ptr()),
+          "ftmi_attn_q8_quant")
+    B, H, Sq, d = q.shape
+    nt = -(-k.shape[2] // 64)
+    pieces, _ = _q8_pieces(B, H, Sq, k.shape[2], d)
+
+    def piece(name, dtype, *shape):
+        off, n = pieces[name]
+        return ws[off:off + n].view(dtype).view(*shape)
+
+    dev = q.device
+    r, col = torch.arange(64, device=dev)[:, None], torch.arange(d, device=dev)[None, :]
+    # K image [64 keys][d bytes]: 16-byte piece col >> 4 of row r at r * d + ((piece ^ f(r)) << 4), f as in csrc/attn_q8.hip (img_off)
+    f = ((r >> 1) & 7) if d == 128 else ((r >> 2) & 3)
+    k_at = r * d + (((col >> 4) ^ f) << 4) + (col & 15)
+    # V image [d rows][64 bytes]: key r = 32 js + crow(r16, g) of channel col at byte 32 g + 16 js + r16 of its row, pieces swizzled by (col >> 2) & 3
+    rr, js = r & 31, r >> 5
+    g, r16 = (rr >> 2) & 1, (rr & 3) + 4 * (rr >> 3)
+    v_at = col * 64 + (((2 * g + js) ^ ((col >> 2) & 3)) << 4) + r16
+    k8 = piece("k8", torch.int8, B, H, nt, 64 * d)[..., k_at.reshape(-1)].reshape(B, H, nt * 64, d)
+    v8 = piece("v8", torch.uint8, B, H, nt, 64 * d)[..., v_at.reshape(-1)].reshape(B, H, nt * 64, d).view(torch.float8_e4m3fn)
+    return (piece("q8", torch.int8, B, H, Sq, d), piece("sq", torch.float32, B, H, Sq), k8, piece("sk", torch.float32, B, H, nt), v8,
+            piece("sv", torch.float32, B, H, d))
+
+
 def accum_bf16(acc: torch.Tensor, x: torch.Tensor, last: bool = False) -> Optional[torch.Tensor]:
     """``acc += float(x)`` for a bf16 [B, H, S, d] view ``x`` (head_dim contiguous) and its contiguous fp32 sum ``acc``: ``ftmi_accum_bf16``.  ``last``: bf16(acc)
     is also written over ``x``, which is returned."""

@@ -31,6 +31,7 @@
  *                                        the input, weight gradients of A and B only (the base weight is frozen)
  *   ftmi_linear_lora_w8_fwd / _bwd ..... the same over a weight STORED as float8_e4m3fn (trainer.py:111-118, layerwise
  *                                        up-casting): ftmi_gemm_nt_w8 / ftmi_gemm_nn_w8 read the bytes, no bf16 copy
+ *   ftmi_attn_fwd_q8 (+ _q8_quant, _q8_workspace_bytes) the sage providers of attention_dispatch.py:1651-1760 (inference only: int8 scores, fp8 weights)
  */
 #ifndef FTMI355_H
 #define FTMI355_H
@@ -136,6 +137,27 @@ int ftmi_attn_fwd_carry(const ftmi_attn_desc* desc, const void* q, const void* k
  * destination with desc.dq_strides (x itself is allowed) that receives bf16(acc) -- pass it with the last call.  Sums the per-chunk dQ that ftmi_attn_bwd
  * returns in bf16, in fp32.  Refusals as above: descriptor, null acc / x, empty problem, 16-byte alignment of x (base and strides), out and acc (base). */
 int ftmi_accum_bf16(const ftmi_attn_desc* desc, float* acc, const void* x, void* out, ftmi_stream stream);
+
+/* Inference-only forward on the int8 / fp8 matrix instructions: what the reference's sage providers (finetrainers/models/attention_dispatch.py:1651-1760,
+ * selected with --attn_provider_inference transformer:sage, CUDA only) do for validation sampling.  q, k, v, out as for ftmi_attn_fwd (bf16, desc strides);
+ * no lse, no backward.  out = softmax(q k^T scale + key_bias) v computed as
+ *   scores: int8 codes of q (one scale per row) times int8 codes of k - mean_keys(k) (one scale per 64 keys; smooth_k = 0: of k itself), i32 accumulation;
+ *   weights p = exp2(. - running max) * 448 as e4m3, values as e4m3 codes of v / sv[channel], sv = absmax_keys |v| / 448, fp32 accumulation;
+ *   out = bf16(sv * sum(p8 v8) / sum(p8)).  A weight below 2^-10 / 448 of the row's running maximum is dropped (e4m3's subnormal floor).
+ * A key with a -inf bias has weight exactly 0; a row whose keys are all removed comes out as 0.
+ * ws: device memory of at least ftmi_attn_q8_workspace_bytes(desc) bytes, 256-byte aligned, owned by the caller; it holds, each rounded up to 256 bytes and in
+ * this order: q8 [B,H,Sq,d] int8, sq [B,H,Sq] fp32, k8 [B,H,nt,64 d] int8, sk [B,H,nt] fp32, v8 [B,H,nt,64 d] e4m3, sv [B,H,d] fp32, and two statistics buffers
+ * [B,H,nc,d] fp32 (nt = ceil(Sk / 64), nc = ceil(Sk / 256)).  k8 / v8 are per-tile images in the kernel's LDS order (csrc/attn_q8.hip gives the map;
+ * ops.attn_q8_quantize undoes it).  ftmi_attn_q8_workspace_bytes returns 0 for a problem the kernels refuse.
+ * ftmi_attn_q8_quant runs the pre-pass alone (two launches) and leaves codes and scales in ws; ftmi_attn_fwd_q8 runs the pre-pass and the forward (three
+ * launches).  Same inputs, same bits: nothing in either is summed in an order that depends on the run.
+ * Refused before anything is launched, in this order: a null descriptor (FTMI_ERR_INVALID), desc.d other than 64 or 128 (FTMI_ERR_UNSUPPORTED); then with
+ * FTMI_ERR_INVALID B, H, Sq or Sk <= 0 ("empty problem"), a null q / k / v (/ out) ("null tensor"), the alignment rule of ftmi_attn_fwd for q, k, v (and out),
+ * a null workspace, a workspace off 256 bytes or smaller than needed; FTMI_ERR_UNSUPPORTED for B * H > 65535. */
+size_t ftmi_attn_q8_workspace_bytes(const ftmi_attn_desc* desc);
+int ftmi_attn_q8_quant(const ftmi_attn_desc* desc, const void* q, const void* k, const void* v, int smooth_k, void* ws, size_t ws_bytes, ftmi_stream stream);
+int ftmi_attn_fwd_q8(const ftmi_attn_desc* desc, const void* q, const void* k, const void* v, void* out, const float* key_bias, int smooth_k, void* ws,
+                     size_t ws_bytes, ftmi_stream stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Linear (+ LoRA) building block:  y = bf16( bf16(x W^T + b) + lora_scale * (x A^T) B^T ), the LoRA branch at fp32-equivalent
